@@ -11,7 +11,13 @@ Contract: python bench.py --gpus N --steps K --warmup W ; rank 0 prints ONE JSON
 WORLD_SIZE in the environment the script starts the N ranks itself (torch.distributed.run, before any GPU call) and
 relays rank 0's line.
 
-Beside `value` (device-resident in / out, as the contract asks) the line carries:
+A plain run sets up, runs W warm-up steps and K timed steps, and prints the line: `value`, `ms_per_step` and the config
+(at N > 1: the strong-scaling leg alone).  --dump-outputs DIR also writes the result tables of the last timed step
+(dump_outputs).  Everything else runs with --full only (--kernels-only = --full without its legs).
+
+With --full, beside `value` (device-resident in / out, as the contract asks) the line carries:
+  stage_ms       per-stage HIP-event times of three extra steps after the timed ones
+  weak           N > 1: the weak-scaling leg (N partitions), beside the strong one
   roofline       the chain kernels against the HBM peak (algorithmic bytes / HIP-event time; traffic from profiles/)
   host_to_host   SURVEY section 8(d)'s own region: rows in pinned host memory -> all four tables in pinned host memory
                  (msgpu_overlap_batched: batches on two streams, the copy of batch k behind the compute of batch k+1)
@@ -769,6 +775,29 @@ def n50(lengths):
     return int(ls[np.searchsorted(np.cumsum(ls), ls.sum() / 2.0)])
 
 
+DUMP_ROWS = 1 << 17  # rows kept per table by --dump-outputs: ~30 MB in all, whatever the workload
+
+
+def dump_outputs(d, tables):
+    """--dump-outputs DIR: the result tables of the last timed step (what a caller of the timed path receives), as float64
+    arrays (the integer fields stay exact below 2**53): DIR/<table>_<field>.npy per field (padding left out), DIR/<table>.npy
+    for a table of plain ids, DIR/<table>_count.npy = its row count.  A table of more than DUMP_ROWS rows is cut to the same
+    seeded sample of DUMP_ROWS rows on every run; DIR/<table>_row.npy holds the row indices kept."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in tables.items():
+        n = len(t)
+        keep = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+        np.save(os.path.join(d, name + "_count.npy"), np.array([n], dtype=np.float64))
+        np.save(os.path.join(d, name + "_row.npy"), keep.astype(np.float64))
+        part = t[keep]
+        if part.dtype.names is None:
+            np.save(os.path.join(d, name + ".npy"), part.astype(np.float64))
+            continue
+        for field in part.dtype.names:
+            if field != "pad":
+                np.save(os.path.join(d, "%s_%s.npy" % (name, field)), part[field].astype(np.float64))
+
+
 def tiled_leg(torch, dev, args, workload, threads, seed_offset=0):
     """NOT a BASELINE configuration: the same number of reads on the shape the graph stage and assemblePath exist for --
     unitigs that TILE the genome (no two anchors overlap, synth.TILED) and reads of mixed length (short ones contained in
@@ -956,13 +985,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: stage markers, rooflines, the weak-scaling leg, the "
+                         "host-to-host, group, consensus, graph, tiled, e2e and CPU-baseline legs (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result tables of the last timed step to DIR/*.npy (float64; see dump_outputs)")
     ap.add_argument("--cpu-sample-reads", type=int, default=25_000,
                     help="reads in the CPU-baseline sample (0 disables the baseline leg)")
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="host cores of the CPU-baseline leg (0 = min(16, cores this process may run on))")
     ap.add_argument("--no-consensus", action="store_true", help="skip the consensus (sequence gather) leg")
     ap.add_argument("--kernels-only", action="store_true",
-                    help="only the timed steps (profiling runs): no host-to-host, consensus, graph or CPU leg")
+                    help="--full without its legs (profiling runs): the timed steps, stage markers and rooflines; no "
+                         "host-to-host, consensus, graph or CPU leg")
     ap.add_argument("--assemble-window-mb", type=float, default=0.0,
                     help="assemblePath leg: chain the reads starting in the first this-many Mb of the genome "
                          "(0 = the whole genome, the default; negative = skip the assemblePath / graph legs)")
@@ -973,8 +1008,8 @@ def main():
                     help="N > 1: weak = every rank runs one partition of an N-partition job (each of the workload's shape; "
                          "disjoint read / anchor id ranges), the merged edge list all-gathered on a communication stream "
                          "beside the next step's compute; strong = the ONE job of the workload sharded over the ranks by "
-                         "v1 %% N (BASELINE.json configs[3]).  auto = strong is `value` (the configuration BASELINE names), the "
-                         "weak figure and the rank-sharded host-to-host figure are reported beside it")
+                         "v1 %% N (BASELINE.json configs[3]).  auto = strong is `value` (the configuration BASELINE names); with --full "
+                         "the weak figure and the rank-sharded host-to-host figure are reported beside it")
     ap.add_argument("--exchange-format", default="wire", choices=("wire", "whole"),
                     help="what the N > 1 exchange sends: the wire form of include/msgpu.h (17-byte edges, 33-byte orders; "
                          "msgpu_pack_wire / msgpu_merge_wire) or whole records (msgpu_copy_tables_device / msgpu_merge_gathered)")
@@ -988,9 +1023,13 @@ def main():
     ap.add_argument("--self-launch", action="store_true",
                     help="start the rank processes through torch.distributed.run even for --gpus 1 (tests the relay)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.kernels_only:
+        args.full = True
         args.no_consensus, args.cpu_sample_reads, args.assemble_window_mb = True, 0, -1.0
         args.no_tiled = args.no_e2e = True
+    legs = args.full and not args.kernels_only  # the legs beside the metric (host-to-host, group, consensus, ...)
 
     if (args.gpus > 1 or args.self_launch) and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, [a for a in sys.argv[1:] if a != "--self-launch"]))
@@ -1040,7 +1079,7 @@ def main():
         rccl_ranks = dist.get_world_size()  # what RCCL saw, not what the command line asked for
 
     w = WORKLOADS[args.workload]
-    weak = multi and args.scaling in ("auto", "weak")
+    weak = multi and (args.scaling == "weak" or (args.scaling == "auto" and args.full))
     # weak scaling: rank r holds partition r of an N-partition job -- the workload's shape, its own seed (rank 0: the
     # workload itself), its own reads and anchors (ids from 0; the merge adds the partition's id bases).  Reads of
     # different partitions share no anchor, so no edge crosses a partition: what sharding a genome by chromosome gives.
@@ -1087,7 +1126,7 @@ def main():
 
     def timed_region(step, finish=None):
         """W warm-up steps, then K timed steps between barrier + synchronize on both sides; chain-kernel events of the
-        timed steps; three more steps with stage markers.  -> (seconds, last step's result, chain kernel ms, stage ms)"""
+        timed steps.  -> (seconds, last step's result, chain kernel ms)"""
         with torch.cuda.stream(work):
             ctx.set_stage_events(False)
             for _ in range(args.warmup):
@@ -1108,13 +1147,28 @@ def main():
                 dist.barrier()
             dt = time.perf_counter() - t0
             k_ms = ctx.timings().chain_kernel_ms  # HIP events around the chain kernels of every timed step, averaged
+        return dt, res, k_ms
+
+    def stage_markers(step, finish=None):
+        """--full: three more steps with stage markers -> their stage timings (None without --full)"""
+        if not args.full:
+            return None
+        with torch.cuda.stream(work):
             ctx.set_stage_events(True)
             for _ in range(3):
                 step()
             if finish:
                 finish()
-            tm = ctx.timings()
-        return dt, res, k_ms, tm
+            return ctx.timings()
+
+    def stage_ms(tm, k_ms):
+        return {"index": tm.index_ms, "candidates": tm.candidates_ms, "chain_total": tm.chain_ms,
+                "chain_kernel": float(k_ms), "compact": tm.compact_ms} if tm is not None else None
+
+    def dump_merged(keep, k):
+        if args.dump_outputs and rank == 0:
+            me, mo, mi = merged_tables(keep, k)
+            dump_outputs(args.dump_outputs, {"edges": me, "orders": mo, "ids": mi})
 
     def over_ranks(dt):
         """-> (max over ranks, {min, max, per_rank} ms per step)"""
@@ -1145,7 +1199,10 @@ def main():
     merge_ok = rank_ms = None
     scaling = "weak"
     if not multi:
-        dt, c, k_ms, tm = timed_region(compute)
+        dt, c, k_ms = timed_region(compute)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, ctx.tables())
+        tm = stage_markers(compute)
         n_edges_total = int(c.n_edges)
     elif weak:
         try:
@@ -1184,7 +1241,10 @@ def main():
             def finish():
                 pe.drain()
 
-            dt, c, k_ms, tm = timed_region(step, finish)
+            dt, c, k_ms = timed_region(step, finish)
+            if args.scaling == "weak":  # (auto: the strong leg below is `value`, and its tables are the ones dumped)
+                dump_merged(merged_keep, merged_keep["last"])
+            tm = stage_markers(step, finish)
             pe.close()
             allc = merged_keep["allc"]
             n_edges_total = int(allc[:, 0].sum())
@@ -1243,7 +1303,9 @@ def main():
             s_keep.update(e=[m_e], o=[m_o], i=[m_i], tot=[tot], allc=allc)
             return c
 
-        s_dt, s_c, s_k_ms, s_tm = timed_region(strong_step)
+        s_dt, s_c, s_k_ms = timed_region(strong_step)
+        dump_merged(s_keep, 0)
+        s_tm = stage_markers(strong_step)
         s_dt, s_rank_ms = over_ranks(s_dt)
         s_edges = int(s_keep["allc"][:, 0].sum())
         s_ok = None
@@ -1260,8 +1322,7 @@ def main():
                       "exchange": {"collectives_per_step": exchange.collectives / max(1, exchange.calls),
                                    "slab_bytes": int(exchange.slab_bytes), "regrows": exchange.regrows,
                                    "format": form_name()},
-                      "stage_ms": {"index": s_tm.index_ms, "candidates": s_tm.candidates_ms, "chain_total": s_tm.chain_ms,
-                                   "chain_kernel": s_k_ms, "compact": s_tm.compact_ms},
+                      "stage_ms": stage_ms(s_tm, s_k_ms),
                       "workload": "%s as ONE job: every rank indexes the whole row table (replicated), owns the edges with "
                                   "v1 %% %d == rank, one all-gather + merge per step on the compute stream "
                                   "(BASELINE.json configs[3] at N = 8)" % (w["name"], world)}
@@ -1271,8 +1332,7 @@ def main():
             weak_leg = {"scaling": "weak", "value": n_edges_total / (dt / args.steps), "unit": "overlap-pairs/s",
                         "ms_per_step": 1e3 * dt / args.steps, "edges": n_edges_total, "rank_ms_per_step": rank_ms,
                         "merged_edge_list_consistent": merge_ok, "exchange": exchange_info,
-                        "stage_ms": {"index": tm.index_ms, "candidates": tm.candidates_ms, "chain_total": tm.chain_ms,
-                                     "chain_kernel": float(k_ms), "compact": tm.compact_ms},
+                        "stage_ms": stage_ms(tm, k_ms),
                         "workload": "%d partitions, each: %s (seeds %d..%d; disjoint read / anchor id ranges, so no edge crosses "
                                     "a partition), one partition per GPU; the all-gather + merge of step k on a communication "
                                     "stream beside the compute of step k + 1.  NOT a BASELINE configuration"
@@ -1281,10 +1341,11 @@ def main():
         scaling = "strong"
         dt, c, k_ms, tm, rank_ms, n_edges_total, merge_ok = s_dt, s_c, s_k_ms, s_tm, s_rank_ms, s_edges, s_ok
         exchange_info, strong_leg = strong_leg["exchange"], None
-        try:
-            sharded_h2h = sharded_host_to_host_leg(torch, dist, D, dev, ctx, rows_s, world, rank, args.batches)
-        except Exception as exc:  # noqa: BLE001 -- (raised on every rank alike: same code, same sizes)
-            sharded_h2h = {"error": "%s: %s" % (type(exc).__name__, exc)}
+        if args.full:
+            try:
+                sharded_h2h = sharded_host_to_host_leg(torch, dist, D, dev, ctx, rows_s, world, rank, args.batches)
+            except Exception as exc:  # noqa: BLE001 -- (raised on every rank alike: same code, same sizes)
+                sharded_h2h = {"error": "%s: %s" % (type(exc).__name__, exc)}
         ctx.set_shard(0, 1)
         ctx.set_id_space(len(read_names), len(anchor_names))
         if partition_rows:
@@ -1292,7 +1353,7 @@ def main():
 
     h2h = asm_leg = graph_leg = grp_leg = None
     errors = {}
-    if world == 1 and rank == 0 and not args.kernels_only:
+    if world == 1 and rank == 0 and legs:
         try:
             if args.batches >= 0 and not (args.batches == 0 and args.assemble_window_mb < 0):  # counter passes skip it
                 h2h = host_to_host_leg(ctx, rows, args.batches)
@@ -1312,7 +1373,7 @@ def main():
             except Exception as exc:  # noqa: BLE001
                 errors["assemble_path"] = "%s: %s" % (type(exc).__name__, exc)
     cons = None
-    if not args.no_consensus:
+    if legs and not args.no_consensus:
         ctx.close()  # give the arena back before the ~3 GB of sequence buffers
         try:
             cons = consensus_leg(torch, dev, world, rank, w, args.steps, args.warmup)
@@ -1325,7 +1386,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         cons["ms"] = float(tt.item())
     cons_weak = None
-    if multi and not args.kernels_only and args.workload in synth.TILED:
+    if multi and legs and args.workload in synth.TILED:
         # the consensus half at N GPUs: partitions are independent (no collective on the path) -- every rank runs the flow
         # behind the overlap tables (contraction test, graph stage, path EdgeMatches, assemblePath) on its own partition of
         # the tiled shape; bases of all ranks / the slowest rank's time
@@ -1350,7 +1411,7 @@ def main():
                                   "partition of the tiled shape (synth.TILED, seed + rank; NOT a BASELINE configuration); no "
                                   "collective on the path; contig bases of all ranks / the slowest rank's time"}
     tiled = e2e = None
-    if world == 1 and rank == 0 and not args.kernels_only:
+    if world == 1 and rank == 0 and legs:
         host_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
         ctx.close()
         if not args.no_tiled and args.workload in synth.TILED:
@@ -1367,44 +1428,6 @@ def main():
 
     if rank == 0:
         ms_per_step = 1e3 * dt / args.steps
-        # algorithmic bytes of the dominant kernels: 96 B per EdgeMatch (32 B EdgeMatch written +
-        # two 32 B VertexMatch rows read) + 64 B per order + 4 B per id; one launch set processes all edges of the rank
-        alg_bytes = 96 * c.n_ems + 64 * c.n_orders + 4 * c.n_ids
-        k_ms = float(k_ms)
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        traffic, traffic_src, valu = pmc_traffic(args.workload, world, CHAIN_KERNELS)
-        if traffic is None and "lacks FETCH_SIZE" in str(traffic_src):  # (a capture of the build that still made a launch per width)
-            traffic, traffic_src, valu = pmc_traffic(args.workload, world, CHAIN_KERNELS_BEFORE)
-        roof = {"bound": "hbm", "kernel": "k_chain + k_chain_sub_all (one pass over the edges: a launch for the edges of 33..64 "
-                                          "EdgeMatches, a launch for the three sub-wavefront widths)",
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic, "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_ms": k_ms,
-                "note": "kernel_ms = the two launches together (HIP events around them on the launch stream); these "
-                        "kernels are bound by vector-ALU issue, not by HBM (valu_issue_frac)"}
-        roof["time_share_of_value"] = k_ms / ms_per_step if ms_per_step > 0 else None
-        if valu and k_ms > 0:
-            # SQ_INSTS_VALU counts wave-instructions; one costs 4 cycles of its SIMD's issue (MI355X_MICROARCH.md); 1024 SIMDs
-            insts = sum(valu.values())
-            roof["valu_issue_frac"] = insts * 4.0 / (k_ms * 1e-3 * 2.4e9 * 1024)
-            roof["valu_note"] = "SQ_INSTS_VALU of the four kernels (%s) x 4 cycles / (kernel_ms x 2.4 GHz x 1024 SIMDs)" % traffic_src
-        # every stage against the HBM roofline: algorithmic bytes (DESIGN.md section 4's formulas) / HIP-event time of the stage
-        # (stage markers of an extra step), counter traffic of the stage's kernels from the newest capture under profiles/
-        R_rows, P_emit = int(len(rows)), int(c.n_ems)
-        stage_alg = {"index": 40 * R_rows + 80 * R_rows,                       # rows in; by_read + by_anchor + scan view out
-                     "candidates": 16 * R_rows + 32 * P_emit + 8 * P_emit,     # scan view + scaffold rows read, (j, t) written
-                     "compact": 2 * (64 * int(c.n_orders) + 4 * int(c.n_ids))}  # order slots + ids read, dense tables written
-        stage_t = {"index": tm.index_ms, "candidates": tm.candidates_ms, "compact": tm.compact_ms}
-        roof_stages = {}
-        for name, nbytes in stage_alg.items():
-            t_ms = float(stage_t[name])
-            tr, src, used = pmc_stage(args.workload, world, STAGE_KERNELS[name])
-            ach = nbytes / (t_ms * 1e-3) / 1e9 if t_ms > 0 else 0.0
-            roof_stages[name] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                                 "algorithmic_bytes": int(nbytes), "stage_ms": t_ms, "traffic": tr, "traffic_source": src,
-                                 "traffic_kernels": used, "time_share_of_value": t_ms / ms_per_step if ms_per_step > 0 else None}
-        roof_stages["index"]["path"] = {0: "bin (no global atomic per row)", 1: "atomic", 2: "two-pass"}.get(int(c.index_path) & 3, "?") + (
-            " + generic scaffolds" if int(c.index_path) & 4 else "")
         out = {
             "metric": "overlap-pairs/s", "value": n_edges_total / (dt / args.steps), "unit": "overlap-pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -1425,17 +1448,55 @@ def main():
                                        "a communication stream" % world if weak else "edges sharded by v1 %% %d" % world),
                        "edges_proven_clean_rank0": int(c.n_edges_fastpath), "merged_edge_list_consistent": merge_ok,
                        "note": "value = the overlap half of the metric with the row table resident in HBM when the timed region "
-                               "starts (the bench contract); survey_8d_region = SURVEY 8(d)'s own region, host memory to host "
+                               "starts (the bench contract); with --full: survey_8d_region = SURVEY 8(d)'s own region, host memory to host "
                                "memory; host_to_host = that region's details; the consensus half is under 'consensus' "
                                "(gather kernel at full size), 'assemble_path' (assemblePath over the whole genome) and "
                                "'graph_stage' (the paths the real graph stage yields)"},
-            "stage_ms": {"index": tm.index_ms, "candidates": tm.candidates_ms, "chain_total": tm.chain_ms,
-                         "chain_kernel": k_ms, "compact": tm.compact_ms,
-                         "note": "index / candidates / chain_total / compact: stage markers (HIP events) of an extra step "
-                                 "after the timed ones; chain_kernel: mean over the timed steps"},
-            "roofline": roof,
-            "roofline_stages": roof_stages,
         }
+        if args.full:  # the per-stage and roofline figures: the stage markers of three extra steps + counter captures
+            # algorithmic bytes of the dominant kernels: 96 B per EdgeMatch (32 B EdgeMatch written +
+            # two 32 B VertexMatch rows read) + 64 B per order + 4 B per id; one launch set processes all edges of the rank
+            alg_bytes = 96 * c.n_ems + 64 * c.n_orders + 4 * c.n_ids
+            k_ms = float(k_ms)
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            traffic, traffic_src, valu = pmc_traffic(args.workload, world, CHAIN_KERNELS)
+            if traffic is None and "lacks FETCH_SIZE" in str(traffic_src):  # (a capture of the build that still made a launch per width)
+                traffic, traffic_src, valu = pmc_traffic(args.workload, world, CHAIN_KERNELS_BEFORE)
+            roof = {"bound": "hbm", "kernel": "k_chain + k_chain_sub_all (one pass over the edges: a launch for the edges of 33..64 "
+                                              "EdgeMatches, a launch for the three sub-wavefront widths)",
+                    "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_ms": k_ms,
+                    "note": "kernel_ms = the two launches together (HIP events around them on the launch stream); these "
+                            "kernels are bound by vector-ALU issue, not by HBM (valu_issue_frac)"}
+            roof["time_share_of_value"] = k_ms / ms_per_step if ms_per_step > 0 else None
+            if valu and k_ms > 0:
+                # SQ_INSTS_VALU counts wave-instructions; one costs 4 cycles of its SIMD's issue (wave64 on CDNA); 1024 SIMDs
+                insts = sum(valu.values())
+                roof["valu_issue_frac"] = insts * 4.0 / (k_ms * 1e-3 * 2.4e9 * 1024)
+                roof["valu_note"] = "SQ_INSTS_VALU of the four kernels (%s) x 4 cycles / (kernel_ms x 2.4 GHz x 1024 SIMDs)" % traffic_src
+            # every stage against the HBM roofline: algorithmic bytes (DESIGN.md section 4's formulas) / HIP-event time of the stage
+            # (stage markers of an extra step), counter traffic of the stage's kernels from the newest capture under profiles/
+            R_rows, P_emit = int(len(rows)), int(c.n_ems)
+            stage_alg = {"index": 40 * R_rows + 80 * R_rows,                       # rows in; by_read + by_anchor + scan view out
+                         "candidates": 16 * R_rows + 32 * P_emit + 8 * P_emit,     # scan view + scaffold rows read, (j, t) written
+                         "compact": 2 * (64 * int(c.n_orders) + 4 * int(c.n_ids))}  # order slots + ids read, dense tables written
+            stage_t = {"index": tm.index_ms, "candidates": tm.candidates_ms, "compact": tm.compact_ms}
+            roof_stages = {}
+            for name, nbytes in stage_alg.items():
+                t_ms = float(stage_t[name])
+                tr, src, used = pmc_stage(args.workload, world, STAGE_KERNELS[name])
+                ach = nbytes / (t_ms * 1e-3) / 1e9 if t_ms > 0 else 0.0
+                roof_stages[name] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                                     "algorithmic_bytes": int(nbytes), "stage_ms": t_ms, "traffic": tr, "traffic_source": src,
+                                     "traffic_kernels": used, "time_share_of_value": t_ms / ms_per_step if ms_per_step > 0 else None}
+            roof_stages["index"]["path"] = {0: "bin (no global atomic per row)", 1: "atomic", 2: "two-pass"}.get(int(c.index_path) & 3, "?") + (
+                " + generic scaffolds" if int(c.index_path) & 4 else "")
+            out["stage_ms"] = dict(stage_ms(tm, k_ms),
+                                   note="index / candidates / chain_total / compact: stage markers (HIP events) of "
+                                        "an extra step after the timed ones; chain_kernel: mean over the timed steps")
+            out["roofline"] = roof
+            out["roofline_stages"] = roof_stages
         if multi:
             out["rccl_ranks"] = rccl_ranks if args.backend == "nccl" else None
             if args.backend != "nccl":
@@ -1521,7 +1582,7 @@ def main():
         for k, v in errors.items():
             out.setdefault(k, {})
             out[k] = {"error": v}
-        if world == 1 and args.cpu_sample_reads > 0:
+        if world == 1 and legs and args.cpu_sample_reads > 0:
             avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             cores = args.cpu_cores if args.cpu_cores > 0 else max(1, min(16, avail))
             try:
@@ -1563,7 +1624,7 @@ def main():
             out.update(extra)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
-    want_group = multi and args.backend == "nccl" and not args.single_device and not args.kernels_only
+    want_group = multi and args.backend == "nccl" and not args.single_device and legs
     group_limit_s = float(os.environ.get("MSGPU_BENCH_GROUP_LIMIT_S", "150"))
 
     def watchdog():

@@ -685,7 +685,7 @@ def test_bench_distributed_path_smoke():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2",
-                          "--warmup", "1", "--cpu-sample-reads", "0", "--force-dist"], env=env, capture_output=True,
+                          "--warmup", "1", "--cpu-sample-reads", "0", "--force-dist", "--full"], env=env, capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -779,6 +779,47 @@ def test_bench_starts_its_own_ranks():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["value"] > 0
     assert line["config"]["merged_edge_list_consistent"] is True
+
+
+def test_bench_plain_run_and_dumped_outputs(oracle, tmp_path):
+    """A plain `bench.py` run (no --full) is the timed steps alone: the line holds the headline figures and none of --full's.
+    --dump-outputs writes the tables of the last timed step, and they are the oracle's tables for the same rows."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from muchsalsa_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    d = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == line["unit"] == "overlap-pairs/s" and line["higher_is_better"] is True and line["dtype"] == "int32+f64"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - line["config"]["edges"] / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not set(line) & {"stage_ms", "roofline", "roofline_stages", "host_to_host", "group", "consensus", "graph_stage",
+                            "assemble_path", "tiled_unitigs", "e2e", "cpu_baseline"}
+    w = bench.WORKLOADS["tiny"]
+    rows, _, _ = synth.accepted_rows(synth.paf_table(w["n_reads"], w["read_len"], w["n_anchors"], w["seed"]))
+    want = oracle.overlap(rows)
+    assert line["config"]["edges"] == len(want["edges"])
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    for name in ("edges", "ems", "orders", "ids"):
+        t = want[name]
+        assert np.load(d / (name + "_count.npy")).tolist() == [len(t)]
+        part = t[np.load(d / (name + "_row.npy")).astype(np.int64)]
+        if t.dtype.names is None:
+            assert np.array_equal(np.load(d / (name + ".npy")), part.astype(np.float64)), name
+            continue
+        for f in t.dtype.names:
+            if f != "pad":
+                got = np.load(d / ("%s_%s.npy" % (name, f)))
+                assert got.dtype == np.float64 and np.array_equal(got, part[f].astype(np.float64)), (name, f)
 
 
 def test_group_of_one_over_rccl_equals_single_context(oracle):

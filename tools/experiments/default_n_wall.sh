@@ -4,11 +4,11 @@ set -u
 OUT=gpurun_out/r4_31
 mkdir -p "$OUT"
 SECONDS=0
-timeout -k 10 500 python3 bench.py --force-dist > "$OUT/default_force_dist.json" 2> "$OUT/default_force_dist.err" || { echo "force-dist failed"; tail -20 "$OUT/default_force_dist.err"; }
+timeout -k 10 500 python3 bench.py --full --force-dist > "$OUT/default_force_dist.json" 2> "$OUT/default_force_dist.err" || { echo "force-dist failed"; tail -20 "$OUT/default_force_dist.err"; }
 echo "force-dist wall ${SECONDS}s"
 for n in 2 4; do
 SECONDS=0
-timeout -k 10 600 python3 bench.py --gpus $n --backend gloo --single-device > "$OUT/default_rehearsal_$n.json" 2> "$OUT/default_rehearsal_$n.err" || { echo "rehearsal $n failed"; tail -20 "$OUT/default_rehearsal_$n.err"; }
+timeout -k 10 600 python3 bench.py --full --gpus $n --backend gloo --single-device > "$OUT/default_rehearsal_$n.json" 2> "$OUT/default_rehearsal_$n.err" || { echo "rehearsal $n failed"; tail -20 "$OUT/default_rehearsal_$n.err"; }
 echo "rehearsal $n wall ${SECONDS}s"
 done
 python3 - <<'PY'

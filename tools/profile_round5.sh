@@ -6,7 +6,7 @@ for f in muchsalsa_amd/csrc/*.hip muchsalsa_amd/csrc/*.cpp muchsalsa_amd/csrc/*.
 done
 bash tools/pmc_passes.sh "$out/pmc" cfg3 > "$out/pmc_passes.log" 2>&1; tail -2 "$out/pmc_passes.log"
 cp "$out/pmc/pmc_summary.csv" "$out/pmc/pmc_meta.json" "$out/" 2>/dev/null
-timeout -k 10 500 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err" || tail -20 "$out/bench_default.err"
+timeout -k 10 500 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err" || tail -20 "$out/bench_default.err"
 python - "$out/bench_default.json" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))
