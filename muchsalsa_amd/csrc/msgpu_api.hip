@@ -242,7 +242,7 @@ struct msgpu_ctx {
   uint32_t     prologue_lists[4] = {0, 0, 0, 0};
   uint64_t     readback_seq = 0;
   uint64_t     lost_publications = 0; // read-backs whose publication never arrived (wait_scalars fell back to a copy)
-  bool         readback_polled = false;
+  bool         readback_mapped = false; // the stage-closing kernels publish the scalar block into h_scalars (else: a copy)
   hipEvent_t   ev_readback = nullptr; // the synchronising read-back path waits for the copy only
   hipEvent_t   ev_order = nullptr;    // msgpu_stream_wait / msgpu_stream_release
   uint32_t     decl_V = 0, decl_A = 0; // msgpu_set_id_space: id counts declared by the caller (0 = find them)
@@ -271,6 +271,9 @@ struct msgpu_ctx {
   uint64_t    n_big_edges = 0, n_big_ems = 0;
   bool   fast_path = true;
   bool   sub_wave  = true; // short edges share a wavefront (k_chain_sub); MSGPU_NO_SUBWAVE=1 sends them all to k_chain
+  bool   use_fork  = true; // the candidate classes side by side (MSGPU_NO_FORK: one after the other)
+  bool   use_prologue = true; // the candidate stage's opening inside the index build (MSGPU_NO_PROLOGUE: never)
+  bool   chain_serial = false; // MSGPU_CHAIN_SERIAL: the chain stage's classes one after the other, a launch each
   uint32_t n_cls[4] = {0, 0, 0, 0}; // edges of 9..16, 17..32, 33..64 and <= 8 EdgeMatches
   uint64_t n_edges_fast = 0;
   DevBuf ems, order_scr, ids_scr, edge_norders, edge_nids, orders, ids, big_list, cls_list, big_elems,
@@ -312,13 +315,6 @@ struct msgpu_ctx {
 
 namespace {
 
-// scalar slots in ctx->scalars (uint64 each)
-enum { SC_MAXIDS = 0 /*2 x u32*/, SC_ERR = 1, SC_TOTAL_A = 2, SC_TOTAL_B = 3, SC_TOTAL_C = 4, SC_NLISTS = 5 /*4 x u32, spans 5..6*/,
-       SC_NBIG = 7, SC_NALIVE = 8, SC_IXFLAGS = 9, SC_BIGSTATS = 10 /*2 x u64*/, SC_BIGCUR = 12 /*2 x u64*/,
-       SC_CLS = 14 /*4 x u32: edges per width class, spans 14..15*/,
-       SC_HEADS = 16 /*k_index_bin: finished workgroups (low half) | scaffolds that begin (high half)*/, SC_DONE = 17 /*u32: finished workgroups of k_index_epilogue*/,
-       SC_OWN = 18 /*visits of the owner reads classified by k_index_epilogue*/, SC_COUNT = 19 };
-
 int fail(msgpu_ctx *c, int code, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -348,7 +344,6 @@ static uint32_t *cand_hist(msgpu_ctx *c, uint32_t V) { return reinterpret_cast<u
 // what k_classify_reads zeroes in front of the candidate kernels (buffers must exist)
 static CandZero cand_zero(msgpu_ctx *c, uint32_t V) {
   static_assert(SC_BIGCUR == SC_BIGSTATS + 2 && SC_CLS == SC_BIGCUR + 2 && SC_HEADS == SC_CLS + 2, "adjacent scalar slots");
-  static_assert(SC_COUNT <= SC_PUBLISH_MAX, "a fused read-back publishes the whole scalar block");
   CandZero z;
   z.n_cand         = c->n_cand.as<uint32_t>();
   z.n_edge         = c->n_edge.as<uint32_t>();
@@ -357,14 +352,15 @@ static CandZero cand_zero(msgpu_ctx *c, uint32_t V) {
   return z;
 }
 
-// One copy of the whole scalar block into pinned memory + a stream synchronisation.  (Separate 4-byte copies into
-// pageable host variables cost ~20 us each on this stack; there were up to three per read-back.)
-// Default: no copy and no stream synchronisation -- a one-wavefront kernel writes the block into the (mapped) pinned
-// mirror and publishes a sequence number; the host polls for it (about half the latency of copy + synchronise, and
-// the host is back on the stream sooner).  A stream that stops making progress (a failed launch) is noticed by
-// hipStreamQuery and handled by the synchronising path, which is also what MSGPU_SYNC_READBACK=1 selects.
-// publish_scalars() enqueues the publication, wait_scalars() polls for it: work that does not depend on the values can
-// be enqueued in between and keeps the GPU busy while the host turns around.
+// The read-back of the scalar block, in one of two modes decided when the context is created (readback_mapped):
+// - mapped (default): no copy and no stream synchronisation -- the launch that closes a stage carries arm_readback()'s
+//   HostPublish, one wavefront of it writes the block into the mapped pinned mirror and publishes a sequence number
+//   (publish_to_host), the host polls for it (about half the latency of copy + synchronise, and the host is back on the
+//   stream sooner).  A stream that stops making progress (a failed launch) is noticed by hipStreamQuery and handled by a copy.
+// - copy (MSGPU_SYNC_READBACK, or no mapped pointer): the launch is not armed; one copy of the whole block into the pinned
+//   mirror behind it and a wait for that copy.  (Separate 4-byte copies into pageable host variables cost ~20 us each.)
+// arm_readback() goes into the closing launch, close_readback() behind it: work that does not depend on the values can be
+// enqueued in between and keeps the GPU busy while the host turns around.
 bool past_deadline(const msgpu_ctx *c) { return c->has_deadline && std::chrono::steady_clock::now() >= c->deadline; }
 // A host wait for a stream (or an event) that honours the context's deadline: without one the runtime's blocking wait, with
 // one a poll that gives up with MSGPU_E_TIMEOUT and leaves the work queued (the caller aborts what blocks it, or destroys).
@@ -385,20 +381,11 @@ int host_sync(msgpu_ctx *c, hipStream_t st, hipEvent_t ev = nullptr) {
   }
 }
 
-int publish_scalars(msgpu_ctx *c, hipEvent_t mark = nullptr) {
-  static const bool sync_path = getenv("MSGPU_SYNC_READBACK") != nullptr;
-  c->readback_polled = !sync_path && c->h_scalars_dev;
-  if (c->readback_polled) {
-    launch_publish_scalars(c->stream, c->scalars.as<uint64_t>(), c->h_scalars_dev, SC_COUNT, ++c->readback_seq);
-  } else {
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_readback, c->stream));
-  }
-  if (mark) HIPCHK(c, hipEventRecord(mark, c->stream));
-  return MSGPU_OK;
+HostPublish arm_readback(msgpu_ctx *c) {
+  return c->readback_mapped ? HostPublish{c->h_scalars_dev, ++c->readback_seq} : HostPublish{nullptr, 0};
 }
 int wait_scalars(msgpu_ctx *c) {
-  if (c->readback_polled) {
+  if (c->readback_mapped) {
     const uint64_t     seq  = c->readback_seq;
     volatile uint64_t *flag = c->h_scalars + SC_COUNT;
     for (uint64_t spins = 1;; ++spins) {
@@ -426,9 +413,20 @@ int wait_scalars(msgpu_ctx *c) {
   }
   return host_sync(c, nullptr, c->ev_readback); // the copy, not whatever was enqueued behind it
 }
-int read_scalars(msgpu_ctx *c, hipEvent_t mark = nullptr) {
-  if (int rc = publish_scalars(c, mark)) return rc;
+int close_readback(msgpu_ctx *c) {
+  if (!c->readback_mapped) {
+    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_readback, c->stream));
+  }
   return wait_scalars(c);
+}
+// the block as it stands, where no closing launch carries the publication: a one-wavefront launch of its own (mark: an event
+// recorded behind it)
+int read_scalars(msgpu_ctx *c, hipEvent_t mark = nullptr) {
+  const HostPublish p = arm_readback(c);
+  if (p.seq) launch_publish_scalars(c->stream, c->scalars.as<uint64_t>(), p);
+  if (mark) HIPCHK(c, hipEventRecord(mark, c->stream));
+  return close_readback(c);
 }
 
 void release_all(msgpu_ctx *c) {
@@ -507,9 +505,8 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
     ENSURE(c, bin_start, (size_t(nb) + 2) * 4);
     ENSURE(c, bucket_visits, ((size_t(V) >> BIN_RPB_SHIFT) + 2) * 4);
   }
-  static const bool sync_path = getenv("MSGPU_SYNC_READBACK") != nullptr;
-  const bool fused_readback = bshift != 0 && !sync_path && c->h_scalars_dev; // k_index_epilogue publishes (and zeroes behind it)
-  if (!(bshift && c->scalars_clean && fused_readback))
+  const bool fused_readback = bshift != 0 && c->readback_mapped; // k_index_epilogue publishes (and zeroes behind it)
+  if (!(fused_readback && c->scalars_clean))
     if (int rc = zero_scalars()) return rc;
   c->scalars_clean = false; // (until this build's publisher has left it so again)
   ENSURE(c, bkt_key, (bshift ? size_t(nb) * bcap * 2 : cap ? size_t(V) * cap : nz) * sizeof(IRow)); // (bin path: 64-byte records)
@@ -541,9 +538,8 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   // the index flags instead of costing a read-back of their own.  Valid for a fast index of an unsharded context; anything
   // else redoes it there.
   c->prologue_ok           = false;
-  static const bool env_no_prologue = getenv("MSGPU_NO_PROLOGUE") != nullptr; // measurement switch
   // (the bin path classifies for the context's shard; the atomic path's prologue is the unsharded one)
-  const bool want_prologue = !env_no_prologue && !force_generic && !c->no_prologue && V != 0 && (c->nshards == 1 || bshift) && c->win_lo == 0 && c->win_hi >= V;
+  const bool want_prologue = c->use_prologue && !force_generic && !c->no_prologue && V != 0 && (c->nshards == 1 || bshift) && c->win_lo == 0 && c->win_hi >= V;
   if (want_prologue) {
     ENSURE(c, n_cand, (size_t(V) + 1) * 4);
     ENSURE(c, n_edge, (size_t(V) + 1) * 4);
@@ -656,10 +652,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
     k.z              = want_prologue ? cand_zero(c, V) : CandZero{};
     k.done           = scalar<uint32_t>(c, SC_DONE);
     k.scalars        = c->scalars.as<uint64_t>();
-    k.host_scalars   = fused_readback ? c->h_scalars_dev : nullptr;
-    k.n_scalars      = SC_COUNT;
-    c->readback_polled = fused_readback;
-    k.seq            = fused_readback ? ++c->readback_seq : 0;
+    k.pub            = arm_readback(c);
     // zeroed behind the publication: error bits, index flags, the scaffold count, the finished-workgroup counters, the owner
     // reads' visits.  (Not with the synchronising read-back: its copy comes after the kernel.)
     k.zero_mask      = fused_readback ? ((1ull << SC_ERR) | (1ull << SC_IXFLAGS) | (1ull << SC_HEADS) | (1ull << SC_DONE) | (1ull << SC_OWN)) : 0ull;
@@ -667,11 +660,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
     if (want_prologue) c->nlists_clean = false;
     HIPCHK(c, hipGetLastError());
     if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[1], st));
-    if (!fused_readback) {
-      HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipEventRecord(c->ev_readback, st));
-    }
-    if (int rc = wait_scalars(c)) return rc;
+    if (int rc = close_readback(c)) return rc;
   } else {
   // the Registry-order check on the first lines the sort found and, in the same launch, the scaffold offsets: fast mode
   // (input grouped by anchor, ascending lines: what the PAF loader hands over) is finished here but for them, and they are
@@ -701,8 +690,8 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   c->cand_zeroed = false;
   c->full_scan_ok = bshift && ixf == 0 && err == 0;
   c->index_total  = c->full_scan_ok ? *host_scalar<uint64_t>(c, SC_TOTAL_A) : 0;
-  c->own_accum    = (bshift && fused_readback) ? 0 : *host_scalar<uint64_t>(c, SC_OWN); // (the publisher zeroed it, or it stands)
-  if (bshift && fused_readback && ixf == 0 && err == 0) { // (zero at rest, see above)
+  c->own_accum    = fused_readback ? 0 : *host_scalar<uint64_t>(c, SC_OWN); // (the publisher zeroed it, or it stands)
+  if (fused_readback && ixf == 0 && err == 0) { // (zero at rest, see above)
     c->scalars_clean = c->bin_clean = true;
     c->bin_zero_words = zero_words_known;
   }
@@ -841,6 +830,7 @@ int msgpu_create(int device, const msgpu_params *params, msgpu_ctx **out) {
   }
   memset(c->h_scalars, 0, (SC_COUNT + 1) * sizeof(uint64_t));
   if (hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_scalars_dev), c->h_scalars, 0) != hipSuccess) c->h_scalars_dev = nullptr;
+  c->readback_mapped = c->h_scalars_dev && !getenv("MSGPU_SYNC_READBACK"); // (any value: the copy read-back)
   {
     const char *nf = getenv("MSGPU_NO_FASTPATH"); // test hook: force the full pair sweep on every edge
     c->fast_path   = !(nf && nf[0] == '1');
@@ -850,6 +840,10 @@ int msgpu_create(int device, const msgpu_params *params, msgpu_ctx **out) {
     c->wire_copy   = !(nw && nw[0] == '1');
     const char *nbin = getenv("MSGPU_NO_BIN"); // A/B switch: the index build's atomic path (rounds 1-3) for every input
     c->use_bin       = !(nbin && nbin[0] == '1');
+    // measurement switches (any value)
+    c->use_prologue = !getenv("MSGPU_NO_PROLOGUE"); // no classification inside the index build
+    c->use_fork     = !getenv("MSGPU_NO_FORK");     // the candidate classes one after the other
+    c->chain_serial = getenv("MSGPU_CHAIN_SERIAL") != nullptr;
   }
   for (auto &ev : c->ev)
     if (hipEventCreate(&ev) != hipSuccess) {
@@ -1146,8 +1140,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   // workgroups of BASELINE.json configs[2] waited for the END of class 0 (240 us for a few microseconds of work,
   // profiles/r2_08/timeline_one_step.txt) and class 1 queued behind them.  Launched first they take their CUs while
   // those are empty and class 0 fills the rest.
-  static const bool no_fork = getenv("MSGPU_NO_FORK") != nullptr; // measurement switch: the classes one after the other
-  const bool fork = (c->n_list[1] || c->n_list[2]) && c->n_list[0] && !no_fork;
+  const bool fork = (c->n_list[1] || c->n_list[2]) && c->n_list[0] && c->use_fork;
   if (fork) {
     // class 1 beside class 0 on a stream of its own, and the handful of class-2 workgroups on the other side stream (idle until
     // the chain stage), launched FIRST: alone in front of class 0 on the main stream they cost 17 us of every step (one or two
@@ -1188,8 +1181,6 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   // tables are written, so the GPU is busy while the host turns around.  The launch goes into whatever the tables hold from
   // earlier calls; kernel and host compare the same counts with the same capacities: if something does not fit the kernel
   // has written nothing and the host allocates and launches again (the first call of a context always does).
-  static const bool sync_path = getenv("MSGPU_SYNC_READBACK") != nullptr;
-  c->readback_polled = !sync_path && c->h_scalars_dev;
   auto capacities = [&](uint64_t *cap_edges, uint64_t *cap_big) {
     uint64_t ce = c->edges.room() / sizeof(msgpu_edge);
     if (c->edge_cand.cap / 8 < ce) ce = c->edge_cand.cap / 8;
@@ -1223,12 +1214,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     k.chain_chunk_sums    = c->chain_chunks.as<unsigned long long>();
     k.n_chain_chunk_words = cap_edges ? static_cast<uint32_t>(chunk_words(cap_edges)) : 0u;
     k.scalars        = c->scalars.as<uint64_t>();
-    k.host_scalars   = (publish && c->readback_polled) ? c->h_scalars_dev : nullptr;
-    k.slot_ems       = SC_TOTAL_A;
-    k.slot_edges     = SC_TOTAL_B;
-    k.slot_cls       = SC_CLS;
-    k.n_scalars      = SC_COUNT;
-    k.seq            = (publish && c->readback_polled) ? ++c->readback_seq : 0;
+    k.pub            = publish ? arm_readback(c) : HostPublish{nullptr, 0};
     k.nlists         = scalar<unsigned long long>(c, SC_NLISTS);
     launch_emit_edges(st, k, publish); // (the first launch of a call: with k_cand_reduce in front)
   };
@@ -1237,11 +1223,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   emit(cap_edges, cap_big, true);
   c->nlists_clean = true; // (its first workgroup zeroes the list cursors behind the publication)
   HIPCHK(c, hipGetLastError());
-  if (!c->readback_polled) { // the synchronising read-back path: a copy behind the kernel
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipEventRecord(c->ev_readback, st));
-  }
-  if (int rc = wait_scalars(c)) return rc;
+  if (int rc = close_readback(c)) return rc;
   const uint64_t *tot = host_scalar<uint64_t>(c, SC_TOTAL_A), *big = host_scalar<uint64_t>(c, SC_BIGSTATS);
   c->n_big_edges = big[0];
   c->n_big_ems   = big[1];
@@ -1362,7 +1344,7 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
     // as ONE of its wavefronts (45 us each for the 16- and 8-wide classes of a shard of eight, one after the other behind
     // k_chain and k_chain_sub<32>: a third of that shard's chain stage, profiles/r5_05); side by side they fill what the long
     // class leaves.  On the whole job the kernels' work is the same either way.
-    const bool serial = getenv("MSGPU_CHAIN_SERIAL") != nullptr; // A/B switch (read per call: a test flips it): the four classes one after the other, a launch each
+    const bool serial = c->chain_serial; // A/B switch: the four classes one after the other, a launch each
     const bool any_sub = c->n_cls[0] || c->n_cls[1] || c->n_cls[3];
     const bool beside  = !serial && any_sub && c->n_cls[2];
     if (beside) HIPCHK(c, hipStreamWaitEvent(c->side_stream2, ck_begin, 0));
@@ -1392,8 +1374,6 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   // table sizes into the scalar block and publishes it to the host, and the move into the dense tables follows in the same
   // kernel -- into what the two tables hold from earlier calls (see msgpu_calculate_edges): the GPU is busy while the host
   // turns around; if the tables turn out too small the kernel has written nothing and is launched again behind the allocation.
-  static const bool sync_path = getenv("MSGPU_SYNC_READBACK") != nullptr;
-  c->readback_polled = !sync_path && c->h_scalars_dev;
   auto compact = [&](bool publish) {
     CompactArgs k;
     k.edges        = c->edges.as<msgpu_edge>();
@@ -1403,12 +1383,7 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
     k.chunk_sums   = c->chain_chunks.as<unsigned long long>();
     k.n_chunks     = static_cast<uint32_t>((E + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
     k.scalars      = c->scalars.as<uint64_t>();
-    k.host_scalars = (publish && c->readback_polled) ? c->h_scalars_dev : nullptr;
-    k.slot_orders  = SC_TOTAL_A;
-    k.slot_ids     = SC_TOTAL_B;
-    k.slot_fast    = SC_TOTAL_C;
-    k.n_scalars    = SC_COUNT;
-    k.seq          = (publish && c->readback_polled) ? ++c->readback_seq : 0;
+    k.pub          = publish ? arm_readback(c) : HostPublish{nullptr, 0};
     k.order_scr    = c->order_scr.as<msgpu_order>();
     k.ids_scr      = c->ids_scr.as<uint32_t>();
     k.orders       = c->orders.as<msgpu_order>();
@@ -1424,11 +1399,7 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   const uint64_t cap_orders = c->orders.room() / sizeof(msgpu_order), cap_ids = c->ids.room() / 4;
   compact(true);
   HIPCHK(c, hipGetLastError());
-  if (!c->readback_polled) { // the synchronising read-back path (MSGPU_SYNC_READBACK=1, or no mapped mirror): a copy behind the kernel
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipEventRecord(c->ev_readback, st));
-  }
-  if (int rc = wait_scalars(c)) return rc;
+  if (int rc = close_readback(c)) return rc;
   c->n_edges_fast     = *host_scalar<uint64_t>(c, SC_TOTAL_C);
   const uint64_t *tot = host_scalar<uint64_t>(c, SC_TOTAL_A);
   c->n_orders = tot[0];

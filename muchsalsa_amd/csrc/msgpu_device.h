@@ -59,6 +59,17 @@ __device__ __forceinline__ double rl_f64(double v, int lane) {
   return __longlong_as_double(static_cast<long long>(rl_u64(static_cast<uint64_t>(__double_as_longlong(v)), lane)));
 }
 
+// The read-back of the scalar block without a copy or a stream synchronisation, called by one whole wavefront:
+// lane k holds the value of slot k.  The words go into the mapped host mirror, a system-scope fence makes them visible, then
+// lane 0 release-stores the sequence number the host polls for.  Fence and store are the wavefront's own, so nothing else needs
+// to wait: no barrier (in a workgroup of several wavefronts only the calling one gets here).  p.seq == 0: nothing is published.
+__device__ __forceinline__ void publish_to_host(const HostPublish &p, int lane, uint64_t v) {
+  if (!p.seq) return;
+  if (lane < SC_COUNT) p.host[lane] = v;
+  __threadfence_system();
+  if (lane == 0) __hip_atomic_store(&p.host[SC_COUNT], p.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // std::max / std::min on doubles with the library's tie and NaN behaviour (NOT fmax/fmin)
 __device__ __forceinline__ double std_max(double a, double b) { return (a < b) ? b : a; }
 __device__ __forceinline__ double std_min(double a, double b) { return (b < a) ? b : a; }

@@ -21,6 +21,20 @@ constexpr uint32_t PF_POS_MASK = 0x3fffffffu;
 constexpr uint32_t PF_DIR      = 1u << 30;
 constexpr uint32_t PF_PRIM     = 1u << 31;
 
+// scalar slots of the context's scalar block (uint64 each): sizes, counters and flags the host reads back after a stage
+enum { SC_MAXIDS = 0 /*2 x u32*/, SC_ERR = 1, SC_TOTAL_A = 2, SC_TOTAL_B = 3, SC_TOTAL_C = 4, SC_NLISTS = 5 /*4 x u32, spans 5..6*/,
+       SC_NBIG = 7, SC_NALIVE = 8, SC_IXFLAGS = 9, SC_BIGSTATS = 10 /*2 x u64*/, SC_BIGCUR = 12 /*2 x u64*/,
+       SC_CLS = 14 /*4 x u32: edges per width class, spans 14..15*/,
+       SC_HEADS = 16 /*k_index_bin: finished workgroups (low half) | scaffolds that begin (high half)*/, SC_DONE = 17 /*u32: finished workgroups of k_index_epilogue*/,
+       SC_OWN = 18 /*visits of the owner reads classified by k_index_epilogue*/, SC_COUNT = 19 };
+static_assert(SC_COUNT <= 64, "one wavefront publishes the whole scalar block (publish_to_host)");
+// A stage-closing kernel's publication of the scalar block (publish_to_host): the mapped host mirror (SC_COUNT words, then the
+// sequence number the host polls for) and the number to publish.  seq = 0: no publication (the copy read-back, or a launch again).
+struct HostPublish {
+  uint64_t *host;
+  uint64_t  seq;
+};
+
 // one owner read of an LDS class, as its candidate workgroup needs it (written by k_classify_reads)
 struct CandDesc {
   uint32_t r, rb, n1, bound; // read id, first row in by_read, rows, scaffold rows to visit
@@ -42,7 +56,6 @@ struct CandArgs {
   uint32_t        th_overlap;
 };
 constexpr uint32_t CAND_CHUNK = 256;     // read ids per chunk of the candidate stage's sums = per workgroup of k_emit_edges
-constexpr uint32_t SC_PUBLISH_MAX = 64;  // scalar words a fused read-back can publish (one wavefront)
 // what k_classify_reads zeroes for the candidate kernels (they ADD to it)
 struct CandZero {
   uint32_t *n_cand, *n_edge;   // per read, V + 1 entries
@@ -68,9 +81,8 @@ struct EmitArgs {
   uint64_t        cap_edges, cap_big;
   unsigned long long *chain_chunk_sums; // zeroed here for the chain kernels
   uint32_t        n_chain_chunk_words;
-  uint64_t       *scalars, *host_scalars; // the read-back (see CompactArgs)
-  uint32_t        slot_ems, slot_edges, slot_cls, n_scalars;
-  uint64_t        seq;
+  uint64_t       *scalars;              // the scalar block: SC_TOTAL_A / SC_TOTAL_B / SC_CLS written here (see CompactArgs)
+  HostPublish     pub;
   unsigned long long *nlists;           // the four list cursors of k_classify_reads (2 words): zero at rest, zeroed here
 };
 
@@ -103,11 +115,10 @@ struct CompactArgs {
   const uint32_t    *edge_norders, *edge_nids;
   const unsigned long long *chunk_sums; // [2 n_chunks], left by the chain kernels
   uint32_t           n_chunks;          // ceil(n_edges / COMPACT_CHUNK)
-  // the read-back of the table sizes rides on workgroup 0: the scalar block (device), its mapped host mirror (null: no
-  // publication), the slots of the three sizes, the words to publish and the sequence number the host polls for (0: none)
-  uint64_t          *scalars, *host_scalars;
-  uint32_t           slot_orders, slot_ids, slot_fast, n_scalars;
-  uint64_t           seq;
+  // the read-back of the table sizes rides on workgroup 0: it writes them into the scalar block (device; SC_TOTAL_A / _B / _C:
+  // orders, ids, shortcut edges) and publishes the block to the host
+  uint64_t          *scalars;
+  HostPublish        pub;
   const msgpu_order *order_scr;
   const uint32_t    *ids_scr;
   msgpu_order       *orders;
@@ -210,9 +221,8 @@ struct IndexEpilogueArgs {
   unsigned long long *own_total;          // visits of the reads classified (= total without shards)
   CandZero        z;
   uint32_t       *done;                   // zero at rest
-  uint64_t       *scalars, *host_scalars;
-  uint32_t        n_scalars;
-  uint64_t        seq;
+  uint64_t       *scalars;
+  HostPublish     pub;
   uint64_t        zero_mask;              // scalar words zeroed behind the publication (bit = slot): error bits, flags, counters
 };
 void launch_index_epilogue(hipStream_t st, const IndexEpilogueArgs &a);
@@ -225,7 +235,7 @@ void launch_index_sort_bin(hipStream_t st, uint32_t *cursor, const uint32_t *bin
                            uint32_t cap, const uint4 *bin_rec, IRow *by_read, IRow *by_anchor, uint4 *vis, uint32_t *read_off,
                            uint32_t *read_cnt, int32_t *read_len, uint32_t *read_first, uint32_t *visits, const msgpu_row *rows,
                            uint32_t *flags, uint32_t *err, uint32_t *bucket_visits);
-void launch_publish_scalars(hipStream_t st, const uint64_t *src, uint64_t *dst_host, uint32_t n, uint64_t seq);
+void launch_publish_scalars(hipStream_t st, const uint64_t *src, const HostPublish &p);
 void launch_index_init(hipStream_t st, uint32_t *const zero[4], const uint32_t n_zero[4], uint32_t *const ones[2],
                        const uint32_t n_ones[2]);
 void launch_index_init8(hipStream_t st, uint32_t *const zero[8], const uint32_t n_zero[8], uint32_t *const ones[2],

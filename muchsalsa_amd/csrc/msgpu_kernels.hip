@@ -102,18 +102,14 @@ template <class T> void exclusive_scan(hipStream_t st, const uint32_t *in, uint6
 template void exclusive_scan<uint32_t>(hipStream_t, const uint32_t *, uint64_t, uint32_t *, uint32_t *, uint32_t *);
 template void exclusive_scan<uint64_t>(hipStream_t, const uint32_t *, uint64_t, uint64_t *, uint64_t *, uint64_t *);
 
-// read-back without a copy engine and without a stream synchronisation: one wavefront writes the scalar block into
-// mapped host memory, makes it visible system-wide and then publishes a sequence number the host is polling for
-__global__ __launch_bounds__(64) void k_publish_scalars(const uint64_t *src, uint64_t *dst_host, uint32_t n, uint64_t seq) {
-  if (threadIdx.x < n) dst_host[threadIdx.x] = src[threadIdx.x];
-  __threadfence_system();
-  __builtin_amdgcn_s_barrier();
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&dst_host[n], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+// the scalar block as it stands, published to the host (publish_to_host) by a launch of its own: for the read-backs that no
+// stage-closing kernel carries
+__global__ __launch_bounds__(64) void k_publish_scalars(const uint64_t *src, HostPublish p) {
+  const int lane = threadIdx.x;
+  publish_to_host(p, lane, lane < SC_COUNT ? src[lane] : 0ull);
 }
-void launch_publish_scalars(hipStream_t st, const uint64_t *src, uint64_t *dst_host, uint32_t n, uint64_t seq) {
-  hipLaunchKernelGGL(k_publish_scalars, dim3(1), dim3(64), 0, st, src, dst_host, n, seq);
+void launch_publish_scalars(hipStream_t st, const uint64_t *src, const HostPublish &p) {
+  hipLaunchKernelGGL(k_publish_scalars, dim3(1), dim3(64), 0, st, src, p);
 }
 
 // Window cuts of the dispatcher by measured work: cum[r] = scaffold rows the owner reads before r visit (exclusive prefix of
@@ -1131,13 +1127,7 @@ __global__ __launch_bounds__(1024) void k_index_epilogue(IndexEpilogueArgs a) {
   __syncthreads();
   if (!s_last) return;
   if (threadIdx.x < 64) {
-    uint64_t v = 0;
-    if (static_cast<uint32_t>(lane) < a.n_scalars) v = __hip_atomic_load(&a.scalars[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a.host_scalars && a.seq) {
-      if (static_cast<uint32_t>(lane) < a.n_scalars) a.host_scalars[lane] = v;
-      __threadfence_system();
-      if (lane == 0) __hip_atomic_store(&a.host_scalars[a.n_scalars], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    publish_to_host(a.pub, lane, lane < SC_COUNT ? __hip_atomic_load(&a.scalars[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull);
     // zero at rest: the error bits, the index flags and the counters of this build (the host has them, or reads the block with a
     // copy BEFORE this point never: the synchronising read-back path does not use this kernel's zeroing, see the host side)
     if ((a.zero_mask >> lane) & 1ull) a.scalars[lane] = 0;
@@ -1326,7 +1316,7 @@ __global__ __launch_bounds__(1024) void k_cand_reduce(const uint32_t *n_edge, co
 // (nearly) the same size, the longest edges of a launch start first), the class sizes, and the read-back of all the sizes.
 // A workgroup per chunk of CAND_CHUNK reads.  Every workgroup sums the rows k_cand_reduce left per chunk: the sums of the chunks before its own are its bases -- first edge, first EdgeMatch, and per size the first
 // list position of the chunk's edges of that size -- the sums over all chunks the table sizes; workgroup 0 writes those into the
-// scalar block and publishes it to the host at once (k_publish_scalars' protocol), the host turns around while the tables are
+// scalar block and publishes it to the host at once (publish_to_host), the host turns around while the tables are
 // written.  The launch may be speculative (into whatever the tables hold from earlier calls): if the edges or the list of big
 // edges do not fit nothing is written; the host, which compares the same numbers, allocates and launches again.
 __global__ __launch_bounds__(1024) void k_emit_edges(EmitArgs a) {
@@ -1421,24 +1411,17 @@ __global__ __launch_bounds__(1024) void k_emit_edges(EmitArgs a) {
     const unsigned long long cls_lo = static_cast<unsigned long long>(c16) | (static_cast<unsigned long long>(c32) << 32);
     const unsigned long long cls_hi = static_cast<unsigned long long>(c64) | (static_cast<unsigned long long>(c8) << 32);
     if (lane == 0) {
-      a.scalars[a.slot_ems]     = tot_m;
-      a.scalars[a.slot_edges]   = tot_e;
-      a.scalars[a.slot_cls]     = cls_lo;
-      a.scalars[a.slot_cls + 1] = cls_hi;
+      a.scalars[SC_TOTAL_A] = tot_m;
+      a.scalars[SC_TOTAL_B] = tot_e;
+      a.scalars[SC_CLS]     = cls_lo;
+      a.scalars[SC_CLS + 1] = cls_hi;
     }
-    if (a.host_scalars && a.seq) {
-      if (static_cast<uint32_t>(lane) < a.n_scalars) {
-        const uint32_t k = lane;
-        a.host_scalars[k] = k == a.slot_ems ? tot_m : k == a.slot_edges ? tot_e : k == a.slot_cls ? cls_lo : k == a.slot_cls + 1 ? cls_hi : a.scalars[k];
-      }
-      __threadfence_system();
-      if (lane == 0) __hip_atomic_store(&a.host_scalars[a.n_scalars], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    publish_to_host(a.pub, lane, lane == SC_TOTAL_A ? tot_m : lane == SC_TOTAL_B ? tot_e : lane == SC_CLS ? cls_lo : lane == SC_CLS + 1 ? cls_hi
+                                 : lane < SC_COUNT ? a.scalars[lane] : 0ull);
     // the list cursors of k_classify_reads are used up (the host read them before it launched the candidate kernels): zero
     // at rest for the next classification
     if (lane == 0 && a.nlists) a.nlists[0] = a.nlists[1] = 0;
   }
-  static_assert(SC_PUBLISH_MAX <= 64, "one wavefront publishes the scalar block");
   if (tot_e > a.cap_edges || a.big_stats[0] >= a.cap_big) return;
   // ---- prefix inside the chunk: a read per thread of the first four wavefronts ------------------------------------------------
   uint32_t ie = 0, im = 0;
@@ -3234,7 +3217,7 @@ __global__ __launch_bounds__(256) void k_fill_pair_tab(uint32_t *tab) {
 // dense, canonical order + id tables -- and the scan that places them, and the read-back of their sizes, in the same launch.
 // A workgroup per chunk of COMPACT_CHUNK edges.  Every workgroup sums the chunk sums the chain kernels left (chunk_add): the
 // ones before its own are its base, all of them the table sizes.  Workgroup 0 writes the sizes into the scalar block and
-// publishes the block to the host AT ONCE (k_publish_scalars' protocol): the host turns around while the tables are still being
+// publishes the block to the host AT ONCE (publish_to_host): the host turns around while the tables are still being
 // written.  Then the prefix inside the chunk (a block scan over the per-edge counts), then the move.
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_compact(CompactArgs a) {
   __shared__ unsigned long long s_red[16][5], s_tot[5], s_em[COMPACT_CHUNK];
@@ -3279,18 +3262,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   if (chunk == 0 && a.scalars && threadIdx.x < 64) {
     // (every launch writes the sizes; only the first launch of a call publishes -- a repeat after a reallocation has seq = 0)
     if (lane == 0) {
-      a.scalars[a.slot_orders] = tot_o;
-      a.scalars[a.slot_ids]    = tot_i;
-      a.scalars[a.slot_fast]   = tot_f;
+      a.scalars[SC_TOTAL_A] = tot_o;
+      a.scalars[SC_TOTAL_B] = tot_i;
+      a.scalars[SC_TOTAL_C] = tot_f;
     }
-    if (a.host_scalars && a.seq) {
-      if (static_cast<uint32_t>(lane) < a.n_scalars) {
-        const uint32_t k = lane;
-        a.host_scalars[k] = k == a.slot_orders ? tot_o : k == a.slot_ids ? tot_i : k == a.slot_fast ? tot_f : a.scalars[k];
-      }
-      __threadfence_system();
-      if (lane == 0) __hip_atomic_store(&a.host_scalars[a.n_scalars], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    publish_to_host(a.pub, lane, lane == SC_TOTAL_A ? tot_o : lane == SC_TOTAL_B ? tot_i : lane == SC_TOTAL_C ? tot_f : lane < SC_COUNT ? a.scalars[lane] : 0ull);
   }
   // (may be launched before the host knows the table sizes, into whatever the tables hold from earlier calls: if they do not
   // fit nothing is written; the host, which compares the same numbers, allocates and launches again)

@@ -332,6 +332,52 @@ def test_one_context_many_jobs_of_changing_size(oracle):
             assert ctx.timings().chain_kernel_launches == 0  # the window of chain-kernel events starts afresh
 
 
+@pytest.mark.parametrize("mode", ["mapped", "copy"])
+def test_both_read_back_modes_on_one_context(oracle, monkeypatch, mode):
+    """The table sizes reach the host one of two ways, fixed when the context is created: the stage-closing kernels publish the
+    scalar block into mapped memory (default), or, with MSGPU_SYNC_READBACK set, a copy follows them.  In each mode: jobs that
+    grow, shrink and grow again on ONE context (k_emit_edges and k_compact launched again behind a reallocation, and not), a
+    dispatcher run of several windows, and bin-path and atomic-path index builds (grouped and shuffled rows) -- every table
+    equal to the oracle's, no publication lost."""
+    from muchsalsa_amd import _lib, overlap, synth
+    if mode == "copy":
+        monkeypatch.setenv("MSGPU_SYNC_READBACK", "1")
+    else:
+        monkeypatch.delenv("MSGPU_SYNC_READBACK", raising=False)
+
+    def tables_of(ctx, rows):
+        ctx.load_rows(rows)
+        ctx.calculate_edges()
+        ctx.chaining_and_overlaps()
+        return ctx.tables(), int(ctx.counts().index_path)
+
+    # edges, orders and ids: 3.1 k / 3.8 k / 20 k, 9.8 k / 11 k / 94 k, 2.8 k / 3.5 k / 18 k, 20 k / 22 k / 208 k
+    shapes = [(300, 3000, 900, 1), (1000, 5000, 4000, 13), (300, 3000, 900, 2), (2000, 5000, 10000, 7)]
+    with overlap.OverlapContext(0) as ctx:
+        for shape in shapes:
+            rows = synth.synth_rows(*shape)
+            got, path = tables_of(ctx, rows)
+            assert path == _lib.INDEX_BIN, (mode, shape, path)
+            assert_tables_equal(got, oracle.overlap(rows), "%s read-back, job %r" % (mode, shape))
+        rows = synth.synth_rows(*shapes[1])
+        got, _ = ctx.overlap_batched(rows, 4)
+        assert_tables_equal(got, oracle.overlap(rows), "%s read-back, four windows" % mode)
+        assert ctx.counts().n_lost_publications == 0
+    monkeypatch.setenv("MSGPU_NO_BIN", "1")
+    rows = synth.synth_rows(*shapes[1])
+    shuffled = rows.copy()
+    np.random.default_rng(5).shuffle(shuffled)
+    want = oracle.overlap(rows)
+    with overlap.OverlapContext(0) as ctx:
+        got, path = tables_of(ctx, rows)
+        assert path in (_lib.INDEX_ATOMIC, _lib.INDEX_TWO_PASS), (mode, path)
+        assert_tables_equal(got, want, "%s read-back, atomic path" % mode)
+        got, path = tables_of(ctx, shuffled)  # generic scaffolds: a second read-back in the index build
+        assert path == (_lib.INDEX_ATOMIC | _lib.INDEX_GENERIC), (mode, path)
+        assert_tables_equal(got, want, "%s read-back, atomic path, shuffled" % mode)
+        assert ctx.counts().n_lost_publications == 0
+
+
 def test_empty_and_tiny(oracle):
     from muchsalsa_amd import synth
     rows = synth.synth_rows(300, 3000, 900, 1)
