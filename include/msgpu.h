@@ -774,6 +774,62 @@ int msgpu_fasta_format(msgpu_seqctx *ctx, const void *d_raw, const msgpu_fasta_r
                        const char *headers, size_t headers_bytes, void *d_text, uint64_t text_capacity,
                        void *hip_stream);
 
+/* ==== unitig coverage filter: the pipeline's own step between the external tools and muchsalsa ==========================
+ * Input: a unitig -> read PAF (every line counts; a block = a maximal run of consecutive lines with the same column 0) and
+ * the unitig FASTA.  Pass 1 (device): per block, the maximum coverage over [0, qlen) by the FIRST line of each read id in
+ * the block.  Per unitig id the value of its last block; q1 / q3 = numpy's linear percentile 25 / 75 over one value per
+ * id, upper = q3 + 1.5 (q3 - q1).  Pass 2 (device): a block whose id's value exceeds upper is an outlier; its coverage by
+ * ALL its lines is cut into maximal runs of cov <= q3, and runs of >= 500 positions become fragments.  Output (device
+ * gather + FASTA wrapping): per block in PAF order, the unitig's whole record (normal) or its fragments (outlier). */
+typedef struct msgpu_uf msgpu_uf;       /* a parsed filter PAF (host)                 */
+typedef struct msgpu_ufctx msgpu_ufctx; /* a device context of the stage              */
+typedef struct msgpu_uf_result msgpu_uf_result;
+typedef struct msgpu_uf_tables { /* views into a msgpu_uf (valid while it lives)                                       */
+  uint64_t        n_lines;
+  uint32_t        n_blocks, n_unitigs, n_reads, pad;
+  const uint32_t *line_block, *line_qs, *line_qe, *line_read;     /* per line; qe exclusive; ids first-seen          */
+  const uint32_t *block_first, *block_n, *block_qlen, *block_unitig; /* per block; qlen = its first line's column 1 */
+  const uint32_t *unitig_last_block;                               /* per unitig id: the block whose value it takes */
+} msgpu_uf_tables;
+/* mmap + one tokenising thread per chunk (as msgpu_parse_paf).  A line the stage rejects -- an empty file, a blank line,
+ * fewer than 7 fields (MSGPU_E_FORMAT), an empty column 0 (MSGPU_E_FORMAT), column 1/2/3/6 not a decimal integer of
+ * int32 range or a negative column 1/2/3, qend > the block's qlen (MSGPU_E_NUMBER) -- fails the parse with *err_line =
+ * its 1-based number (1 for an empty file). */
+int         msgpu_uf_parse(const char *path, msgpu_uf **out, uint64_t *err_line);
+void        msgpu_uf_free(msgpu_uf *u);
+int         msgpu_uf_get_tables(const msgpu_uf *u, msgpu_uf_tables *out);
+const char *msgpu_uf_unitig_name(const msgpu_uf *u, uint32_t id);
+const char *msgpu_uf_read_name(const msgpu_uf *u, uint32_t id);
+uint32_t    msgpu_uf_unitig_id(const msgpu_uf *u, const char *name); /* 0xffffffff: no line names it */
+/* numpy.percentile(values, [25, 75]) (linear method) and q3 + 1.5 * (q3 - q1), bit for bit; n >= 1 (host) */
+int msgpu_uf_quartiles(const uint32_t *values, size_t n, double *q1, double *q3, double *upper);
+
+/* device = HIP ordinal (MSGPU_E_NODEVICE without a GPU) */
+int         msgpu_uf_create(int device, msgpu_ufctx **out);
+void        msgpu_uf_destroy(msgpu_ufctx *ctx);
+const char *msgpu_uf_last_error(const msgpu_ufctx *ctx);
+uint64_t    msgpu_uf_error_line(const msgpu_ufctx *ctx); /* after MSGPU_E_IDS: 1-based PAF line of the first block whose unitig the FASTA lacks */
+#define MSGPU_UF_PACKED 1u /* gather from the 2-bit store (msgpu_seq_pack_store) instead of the byte-per-base one */
+typedef struct msgpu_uf_stats {
+  uint64_t n_lines, n_blocks, n_ids, n_outliers, n_rescued, n_fragments, n_records, bases, text_bytes;
+  uint32_t n_wave, n_group, n_giant, pad; /* pass-1 blocks per width class                                    */
+  double   q1, q3, upper;
+  float    load_ms;    /* host: FASTA parse + upload + descriptions (wall)                                   */
+  float    upload_ms;  /* device: the PAF tables to HBM (events, as every *_ms below but plan_ms / wall_ms)   */
+  float    pass1_ms;   /* block values, per-id values                                                        */
+  float    pass2_ms;   /* outlier sweep: count + emit (plus the count read-back between them)                */
+  float    plan_ms;    /* host: records, headers, gather plan                                                */
+  float    gather_ms, format_ms, copy_ms;
+  float    wall_ms;
+  float    pad2;
+} msgpu_uf_stats;
+/* The whole stage on a parsed PAF: the unitigs are read as FASTA (first record of an id wins), the text of out.fa is kept
+ * in the result.  MSGPU_E_IDS when a block names a unitig the FASTA lacks (msgpu_uf_error_line). Synchronous. */
+int         msgpu_uf_run(msgpu_ufctx *ctx, const msgpu_uf *u, const char *unitigs_path, uint32_t flags, msgpu_uf_result **out);
+int         msgpu_uf_result_stats(const msgpu_uf_result *r, msgpu_uf_stats *out);
+const char *msgpu_uf_result_text(const msgpu_uf_result *r, uint64_t *len);
+void        msgpu_uf_result_free(msgpu_uf_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

@@ -107,6 +107,25 @@ class Timings(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class UfTables(C.Structure):  # msgpu_uf_tables
+    _fields_ = [("n_lines", C.c_uint64), ("n_blocks", C.c_uint32), ("n_unitigs", C.c_uint32), ("n_reads", C.c_uint32),
+                ("pad", C.c_uint32)] + [(n, C.POINTER(C.c_uint32)) for n in (
+                    "line_block", "line_qs", "line_qe", "line_read", "block_first", "block_n", "block_qlen",
+                    "block_unitig", "unitig_last_block")]
+
+
+class UfStats(C.Structure):  # msgpu_uf_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_lines", "n_blocks", "n_ids", "n_outliers", "n_rescued", "n_fragments",
+                                           "n_records", "bases", "text_bytes")] +
+                [(n, C.c_uint32) for n in ("n_wave", "n_group", "n_giant", "pad")] +
+                [(n, C.c_double) for n in ("q1", "q3", "upper")] +
+                [(n, C.c_float) for n in ("load_ms", "upload_ms", "pass1_ms", "pass2_ms", "plan_ms", "gather_ms",
+                                          "format_ms", "copy_ms", "wall_ms", "pad2")])
+
+
+UF_PACKED = 1
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -268,6 +287,22 @@ SYMBOLS = [
     ("msgpu_toggle_mul", C.c_int, [C.c_int, C.c_int]),
     ("msgpu_gather_plan_create", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("msgpu_gather_plan_free", None, [C.c_void_p]),
+    ("msgpu_uf_parse", C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    ("msgpu_uf_free", None, [C.c_void_p]),
+    ("msgpu_uf_get_tables", C.c_int, [C.c_void_p, C.POINTER(UfTables)]),
+    ("msgpu_uf_unitig_name", C.c_char_p, [C.c_void_p, C.c_uint32]),
+    ("msgpu_uf_read_name", C.c_char_p, [C.c_void_p, C.c_uint32]),
+    ("msgpu_uf_unitig_id", C.c_uint32, [C.c_void_p, C.c_char_p]),
+    ("msgpu_uf_quartiles", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double)]),
+    ("msgpu_uf_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_uf_destroy", None, [C.c_void_p]),
+    ("msgpu_uf_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_uf_error_line", C.c_uint64, [C.c_void_p]),
+    ("msgpu_uf_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("msgpu_uf_result_stats", C.c_int, [C.c_void_p, C.POINTER(UfStats)]),
+    ("msgpu_uf_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_uf_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

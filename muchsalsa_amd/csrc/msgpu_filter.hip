@@ -1,0 +1,741 @@
+// msgpu_filter.hip -- the unitig coverage filter (include/msgpu.h, "unitig coverage filter"; DESIGN.md section
+// "Unitig coverage filter").
+//
+// Pass 1 computes, per block of the PAF, the maximum coverage by the first line of each read id in three width classes:
+//   * <= UF_WAVE lines    k_uf_wave    one wavefront per block, one line per lane: de-duplication and depth by shuffles;
+//                                      the maximum depth is reached at a kept interval's start, so no sort is needed;
+//   * <= UF_GROUP lines   k_uf_group   one workgroup per block, the lines staged in LDS, the same all-pairs rule;
+//   * larger              giant        de-duplication by a segmented sort of (read, line), then a segmented sort of the
+//                                      interval endpoints and one wavefront per block sweeping them (k_uf_sweep_max).
+// Per unitig id the value of its last block is taken (k_uf_id_values), copied back (4 bytes per id) and the quartiles
+// are order statistics on the host (nth_element).  Pass 2 sorts the endpoints of ALL lines of the outlier blocks and
+// sweeps each block twice (count, then emit at the scanned offsets), so fragments come out in (block, position) order
+// whatever the scheduling.  The output is one gather of whole records and fragments and one FASTA wrapping launch on the
+// sequence store of msgpu_seq.hip.
+//
+// Kernel rules: vector stores only; no inline asm; this file is built with -ffp-contract=off (q1 / q3 / upper).
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "msgpu.h"
+
+namespace msgpu {
+
+constexpr uint32_t UF_WAVE  = 64;   // lines of a block in the wavefront class
+constexpr uint32_t UF_GROUP = 1024; // lines of a block in the workgroup class (LDS: 16 bytes per line)
+constexpr uint32_t UF_RUN   = 500;  // shortest fragment
+
+// one wavefront per block; 4 blocks per 256-thread workgroup
+__global__ __launch_bounds__(256) void k_uf_wave(const uint32_t *blocks, uint32_t n_blocks, const uint32_t *bfirst,
+                                                 const uint32_t *bn, const uint32_t *qs, const uint32_t *qe,
+                                                 const uint32_t *rd, uint32_t *val) {
+  const uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= n_blocks) return; // (the whole wavefront leaves together)
+  const int      lane = threadIdx.x & 63;
+  const uint32_t b = blocks[w], n = bn[b], f = bfirst[b];
+  const bool     have = static_cast<uint32_t>(lane) < n;
+  const uint32_t s = have ? qs[f + lane] : 0, e = have ? qe[f + lane] : 0, r = have ? rd[f + lane] : 0xffffffffu;
+  bool           kept = have && s < e;
+  for (int j = 0; j < 64; ++j) { // the first line of a read id in the block counts, later ones add nothing
+    const uint32_t rj = __shfl(r, j);
+    if (j < lane && static_cast<uint32_t>(j) < n && rj == r) kept = false;
+  }
+  uint32_t depth = 0; // lines of the block covering this line's start
+  for (int j = 0; j < 64; ++j) {
+    const uint32_t sj = __shfl(s, j), ej = __shfl(e, j);
+    const int      kj = __shfl(static_cast<int>(kept), j);
+    if (kj && sj <= s && s < ej) ++depth;
+  }
+  uint32_t m = kept ? depth : 0;
+  for (int o = 32; o > 0; o >>= 1) m = max(m, static_cast<uint32_t>(__shfl_xor(m, o)));
+  if (lane == 0) val[b] = m;
+}
+
+// one workgroup per block, lines in LDS; all pairs, 256 threads
+__global__ __launch_bounds__(256) void k_uf_group(const uint32_t *blocks, const uint32_t *bfirst, const uint32_t *bn,
+                                                  const uint32_t *qs, const uint32_t *qe, const uint32_t *rd,
+                                                  uint32_t *val) {
+  __shared__ uint32_t ls[UF_GROUP], le[UF_GROUP], lr[UF_GROUP], lk[UF_GROUP];
+  __shared__ uint32_t wmax[4];
+  const uint32_t      b = blocks[blockIdx.x], n = min(bn[b], UF_GROUP), f = bfirst[b];
+  for (uint32_t i = threadIdx.x; i < n; i += 256) {
+    ls[i] = qs[f + i];
+    le[i] = qe[f + i];
+    lr[i] = rd[f + i];
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n; i += 256) {
+    bool kept = ls[i] < le[i];
+    for (uint32_t j = 0; j < i && kept; ++j)
+      if (lr[j] == lr[i]) kept = false;
+    lk[i] = kept;
+  }
+  __syncthreads();
+  uint32_t m = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += 256) {
+    if (!lk[i]) continue;
+    const uint32_t s = ls[i];
+    uint32_t       depth = 0;
+    for (uint32_t j = 0; j < n; ++j) depth += (lk[j] && ls[j] <= s && s < le[j]) ? 1u : 0u;
+    m = max(m, depth);
+  }
+  for (int o = 32; o > 0; o >>= 1) m = max(m, static_cast<uint32_t>(__shfl_xor(m, o)));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) val[b] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+}
+
+// the segment (of seg_off, n_seg + 1 entries) that element i lies in
+__device__ inline uint32_t uf_segment(const uint64_t *seg_off, uint32_t n_seg, uint64_t i) {
+  uint32_t lo = 0, hi = n_seg; // seg_off[lo] <= i < seg_off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (seg_off[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// giant blocks, step 1: (read << 32 | line inside the block) per line
+__global__ __launch_bounds__(256) void k_uf_read_keys(const uint32_t *blocks, const uint64_t *seg_off, uint32_t n_seg,
+                                                      const uint32_t *bfirst, const uint32_t *rd, uint64_t *keys) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= seg_off[n_seg]) return;
+  const uint32_t g = uf_segment(seg_off, n_seg, i), local = static_cast<uint32_t>(i - seg_off[g]);
+  keys[i] = (static_cast<uint64_t>(rd[bfirst[blocks[g]] + local]) << 32) | local;
+}
+
+// endpoint keys: (pos << 1 | 1) for a start, (pos << 1) for an end, so that at one position the ends come first.  A line
+// that does not count (a repeated read id in pass 1, an empty interval) gives the neutral pair (end 0, start 0).
+__device__ inline void uf_put_events(uint64_t *ev, uint64_t at, bool counts, uint32_t s, uint32_t e) {
+  const uint64_t a = counts ? ((static_cast<uint64_t>(s) << 1) | 1) : 1, z = counts ? (static_cast<uint64_t>(e) << 1) : 0;
+  ev[2 * at]     = a;
+  ev[2 * at + 1] = z;
+}
+
+// giant blocks, step 2: the sorted (read, line) keys -> endpoint keys of the lines that count
+__global__ __launch_bounds__(256) void k_uf_dedup_events(const uint32_t *blocks, const uint64_t *seg_off, uint32_t n_seg,
+                                                         const uint32_t *bfirst, const uint32_t *qs, const uint32_t *qe,
+                                                         const uint64_t *sorted, uint64_t *ev) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= seg_off[n_seg]) return;
+  const uint32_t g     = uf_segment(seg_off, n_seg, i);
+  const uint64_t k     = sorted[i];
+  const bool     first = i == seg_off[g] || (sorted[i - 1] >> 32) != (k >> 32); // stable by line: the read's first line
+  const uint32_t line  = bfirst[blocks[g]] + static_cast<uint32_t>(k & 0xffffffffu);
+  const uint32_t s = qs[line], e = qe[line];
+  uf_put_events(ev, i, first && s < e, s, e);
+}
+
+// pass 2: endpoint keys of every line of the outlier blocks
+__global__ __launch_bounds__(256) void k_uf_all_events(const uint32_t *blocks, const uint64_t *seg_off, uint32_t n_seg,
+                                                       const uint32_t *bfirst, const uint32_t *qs, const uint32_t *qe,
+                                                       uint64_t *ev) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= seg_off[n_seg]) return;
+  const uint32_t g    = uf_segment(seg_off, n_seg, i);
+  const uint32_t line = bfirst[blocks[g]] + static_cast<uint32_t>(i - seg_off[g]);
+  const uint32_t s = qs[line], e = qe[line];
+  uf_put_events(ev, i, s < e, s, e);
+}
+
+// giant blocks, step 3: one wavefront per block sweeps its sorted endpoints 64 at a time (inclusive scan of +1 / -1);
+// the maximum of the running depth after a start is the block's value
+__global__ __launch_bounds__(256) void k_uf_sweep_max(const uint32_t *blocks, const uint64_t *seg_off, uint32_t n_seg,
+                                                      const uint64_t *ev, uint32_t *val) {
+  const uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= n_seg) return;
+  const int      lane = threadIdx.x & 63;
+  const uint64_t e0 = 2 * seg_off[g], e1 = 2 * seg_off[g + 1];
+  int32_t        carry = 0, m = 0;
+  for (uint64_t t = e0; t < e1; t += 64) {
+    const uint64_t i    = t + lane;
+    const uint64_t k    = i < e1 ? ev[i] : 0;
+    int32_t        x    = i < e1 ? ((k & 1) ? 1 : -1) : 0;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int32_t y = __shfl_up(x, o);
+      if (lane >= o) x += y;
+    }
+    const int32_t depth = carry + x;
+    int32_t       c     = (i < e1 && (k & 1)) ? depth : 0;
+    for (int o = 32; o > 0; o >>= 1) c = max(c, __shfl_xor(c, o));
+    m = max(m, c);
+    carry += __shfl(x, 63);
+  }
+  if (lane == 0) val[blocks[g]] = static_cast<uint32_t>(m);
+}
+
+__global__ __launch_bounds__(256) void k_uf_id_values(const uint32_t *last_block, uint32_t n_ids, const uint32_t *val,
+                                                      uint32_t *id_val) {
+  const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+  if (u < n_ids) id_val[u] = val[last_block[u]];
+}
+
+// pass 2: one thread per outlier block walks its sorted endpoints.  Coverage is constant between two distinct endpoint
+// positions; runs of cov <= t of >= UF_RUN positions are fragments.  EMIT = false: count them; true: write them at
+// frag_off[g] (in position order).
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_uf_runs(const uint32_t *blocks, const uint64_t *seg_off, uint32_t n_seg,
+                                                 const uint32_t *bqlen, const uint64_t *ev, int64_t t, uint32_t *count,
+                                                 const uint32_t *frag_off, uint2 *frags) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n_seg) return;
+  const uint64_t e1 = 2 * seg_off[g + 1];
+  const uint32_t qlen = bqlen[blocks[g]];
+  uint32_t       k = 0, at = EMIT ? frag_off[g] : 0;
+  int64_t        depth = 0, run = -1; // run: start of the open run of good positions (-1: none)
+  uint32_t       cur = 0;             // coverage is `depth` on [cur, next endpoint)
+  auto           segment = [&](uint32_t a, uint32_t z) { // [a, z) with coverage depth
+    if (depth <= t) {
+      if (run < 0) run = a;
+    } else if (run >= 0) {
+      if (a - static_cast<uint32_t>(run) >= UF_RUN) {
+        if (EMIT) frags[at + k] = make_uint2(static_cast<uint32_t>(run), a - 1);
+        ++k;
+      }
+      run = -1;
+    }
+  };
+  for (uint64_t i = 2 * seg_off[g]; i < e1;) {
+    const uint32_t p = static_cast<uint32_t>(ev[i] >> 1);
+    if (p > cur) segment(cur, p);
+    for (; i < e1 && static_cast<uint32_t>(ev[i] >> 1) == p; ++i) depth += (ev[i] & 1) ? 1 : -1;
+    cur = p;
+  }
+  if (qlen > cur) segment(cur, qlen);
+  if (run >= 0 && qlen - static_cast<uint32_t>(run) >= UF_RUN) {
+    if (EMIT) frags[at + k] = make_uint2(static_cast<uint32_t>(run), qlen - 1);
+    ++k;
+  }
+  if (!EMIT) count[g] = k;
+}
+
+} // namespace msgpu
+
+using namespace msgpu;
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+struct msgpu_ufctx {
+  int           device = 0;
+  hipStream_t   stream = nullptr;
+  msgpu_seqctx *seq    = nullptr;
+  char          err[256] = {0};
+  uint64_t      err_line = 0;
+};
+
+struct msgpu_uf_result {
+  msgpu_uf_stats    stats{};
+  std::vector<char> text;
+};
+
+namespace {
+
+int ufail(msgpu_ufctx *c, int code, const char *what, hipError_t e) {
+  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
+  return code;
+}
+#define UHIP(c, expr)                                                                                                  \
+  do {                                                                                                                 \
+    hipError_t _e = (expr);                                                                                            \
+    if (_e != hipSuccess) return ufail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
+  } while (0)
+
+struct DevBuf { // device memory freed on every way out of msgpu_uf_run
+  std::vector<void *> p;
+  ~DevBuf() {
+    for (void *x : p) (void)hipFree(x);
+  }
+  template <class T> hipError_t get(T **out, size_t count) {
+    void      *m = nullptr;
+    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
+    if (e == hipSuccess) p.push_back(m);
+    *out = static_cast<T *>(m);
+    return e;
+  }
+};
+
+inline bool uf_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+// The description line (text after '>', trailing whitespace removed) of the first record of every unitig id the PAF
+// names: what the output's header of a normal block is.  A record is a line starting with '>' (seq_loader.cpp's FASTA
+// rule), its id the description cut at the first whitespace.
+int uf_descriptions(const char *path, const msgpu_uf *u, uint32_t n_ids, std::vector<std::string> &desc) {
+  int fd = open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return MSGPU_E_IO;
+  struct stat st;
+  if (fstat(fd, &st) != 0) {
+    close(fd);
+    return MSGPU_E_IO;
+  }
+  const size_t len  = static_cast<size_t>(st.st_size);
+  const char  *data = nullptr;
+  if (len) {
+    void *m = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m == MAP_FAILED) {
+      close(fd);
+      return MSGPU_E_IO;
+    }
+    data = static_cast<const char *>(m);
+  }
+  close(fd);
+  desc.assign(n_ids, std::string());
+  std::vector<char> seen(n_ids, 0);
+  std::string       id;
+  for (const char *q = data, *end = data + len; q < end;) {
+    const void *nlp = memchr(q, '\n', static_cast<size_t>(end - q));
+    const char *ls = q, *le = nlp ? static_cast<const char *>(nlp) : end;
+    q = nlp ? le + 1 : end;
+    if (*ls != '>') continue;
+    const char *ds = ls + 1, *de = le;
+    while (de > ds && uf_space(de[-1])) --de;
+    const char *ie = ds;
+    while (ie < de && !uf_space(*ie) && *ie) ++ie;
+    id.assign(ds, ie);
+    const uint32_t k = msgpu_uf_unitig_id(u, id.c_str());
+    if (k < n_ids && !seen[k]) {
+      seen[k] = 1;
+      desc[k].assign(ds, de);
+    }
+  }
+  if (data) munmap(const_cast<char *>(data), len);
+  return MSGPU_OK;
+}
+
+float ms_between(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, a, b);
+  return ms;
+}
+
+} // namespace
+
+extern "C" {
+
+// numpy.percentile, method "linear": virtual index (n - 1) q, neighbours floor / floor + 1 (the last value at or beyond
+// n - 1), numpy's lerp a + (b - a) t, or b - (b - a)(1 - t) for t >= 0.5.  Integer values: b - a is exact.
+int msgpu_uf_quartiles(const uint32_t *values, size_t n, double *q1, double *q3, double *upper) {
+  if (!values || !n || !q1 || !q3 || !upper) return MSGPU_E_ARG;
+  try {
+    std::vector<uint32_t> v(values, values + n);
+    auto at = [&](size_t k) {
+      std::nth_element(v.begin(), v.begin() + k, v.end());
+      return static_cast<int64_t>(v[k]);
+    };
+    auto q = [&](double p) {
+      const double vi   = static_cast<double>(n - 1) * p; // exact: p is 0.25 or 0.75
+      const double prev = std::floor(vi);
+      size_t       i0   = static_cast<size_t>(prev), i1 = i0 + 1;
+      if (vi >= static_cast<double>(n - 1)) i0 = i1 = n - 1;
+      const double  t = vi - prev;
+      const int64_t a = at(i0), b = at(i1);
+      const double  d = static_cast<double>(b - a);
+      return t >= 0.5 ? static_cast<double>(b) - d * (1.0 - t) : static_cast<double>(a) + d * t;
+    };
+    *q1    = q(0.25);
+    *q3    = q(0.75);
+    *upper = *q3 + 1.5 * (*q3 - *q1);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  return MSGPU_OK;
+}
+
+int msgpu_uf_create(int device, msgpu_ufctx **out) {
+  if (!out) return MSGPU_E_ARG;
+  *out    = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
+  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
+  auto *c = new (std::nothrow) msgpu_ufctx();
+  if (!c) return MSGPU_E_NOMEM;
+  c->device = device;
+  int rc    = msgpu_seq_create(device, &c->seq);
+  if (rc == MSGPU_OK && (hipSetDevice(device) != hipSuccess ||
+                         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess))
+    rc = MSGPU_E_HIP;
+  if (rc != MSGPU_OK) {
+    msgpu_uf_destroy(c);
+    return rc;
+  }
+  *out = c;
+  return MSGPU_OK;
+}
+
+void msgpu_uf_destroy(msgpu_ufctx *c) {
+  if (!c) return;
+  if (c->stream) {
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamDestroy(c->stream);
+  }
+  msgpu_seq_destroy(c->seq);
+  delete c;
+}
+
+const char *msgpu_uf_last_error(const msgpu_ufctx *c) { return c ? c->err : "null context"; }
+uint64_t    msgpu_uf_error_line(const msgpu_ufctx *c) { return c ? c->err_line : 0; }
+
+int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, uint32_t flags, msgpu_uf_result **out) {
+  if (!c || !u || !unitigs_path || !out) return MSGPU_E_ARG;
+  *out        = nullptr;
+  c->err[0]   = 0;
+  c->err_line = 0;
+  msgpu_uf_tables tb;
+  if (msgpu_uf_get_tables(u, &tb) != MSGPU_OK || !tb.n_lines) return MSGPU_E_ARG;
+  const auto w0 = std::chrono::steady_clock::now();
+  auto       since = [](std::chrono::steady_clock::time_point a) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
+  };
+  UHIP(c, hipSetDevice(c->device));
+  const uint32_t NB = tb.n_blocks, NI = tb.n_unitigs;
+  std::unique_ptr<msgpu_uf_result> res;
+  try {
+    res.reset(new msgpu_uf_result());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  msgpu_uf_stats &S = res->stats;
+  S.n_lines         = tb.n_lines;
+  S.n_blocks        = NB;
+  S.n_ids           = NI;
+
+  // ---- the unitigs: bases to the store, ids, descriptions
+  msgpu_seqfile *f = nullptr;
+  int            rc = msgpu_seq_parse_upload(c->seq, 1, unitigs_path, 0, &f);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "unitigs %s: %s", unitigs_path, msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  struct FreeSeq {
+    msgpu_seqfile *f;
+    ~FreeSeq() { msgpu_seq_free(f); }
+  } free_seq{f};
+  std::vector<uint32_t>    rec_ids, rec_of(NI, 0xffffffffu);
+  std::vector<std::string> desc;
+  try {
+    const uint32_t nr = msgpu_seq_count(f);
+    rec_ids.resize(nr);
+    for (uint32_t i = 0; i < nr; ++i) {
+      rec_ids[i] = msgpu_uf_unitig_id(u, msgpu_seq_name(f, i));
+      if (rec_ids[i] != 0xffffffffu && rec_of[rec_ids[i]] == 0xffffffffu) rec_of[rec_ids[i]] = i;
+    }
+    for (uint32_t b = 0; b < NB; ++b)
+      if (rec_of[tb.block_unitig[b]] == 0xffffffffu) { // a unitig the FASTA lacks: the first block naming it
+        c->err_line = static_cast<uint64_t>(tb.block_first[b]) + 1;
+        snprintf(c->err, sizeof(c->err), "unitig %s (PAF line %llu) is not in %s", msgpu_uf_unitig_name(u, tb.block_unitig[b]),
+                 static_cast<unsigned long long>(c->err_line), unitigs_path);
+        return MSGPU_E_IDS;
+      }
+    rc = uf_descriptions(unitigs_path, u, NI, desc);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  if (rc != MSGPU_OK) return rc;
+  rc = msgpu_seq_set_ids(c->seq, 1, f, rec_ids.data(), NI);
+  if (rc == MSGPU_OK && (flags & MSGPU_UF_PACKED)) rc = msgpu_seq_pack_store(c->seq, 1);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "sequence store: %s", msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  S.load_ms = since(w0);
+
+  // ---- width classes
+  std::vector<uint32_t> wave, group, giant;
+  std::vector<uint64_t> giant_off(1, 0);
+  for (uint32_t b = 0; b < NB; ++b) {
+    const uint32_t n = tb.block_n[b];
+    if (n <= UF_WAVE) wave.push_back(b);
+    else if (n <= UF_GROUP) group.push_back(b);
+    else {
+      giant.push_back(b);
+      giant_off.push_back(giant_off.back() + n);
+    }
+  }
+  S.n_wave  = static_cast<uint32_t>(wave.size());
+  S.n_group = static_cast<uint32_t>(group.size());
+  S.n_giant = static_cast<uint32_t>(giant.size());
+
+  hipStream_t st = c->stream;
+  hipEvent_t  ev[10] = {};
+  struct FreeEv {
+    hipEvent_t *e;
+    ~FreeEv() {
+      for (int i = 0; i < 10; ++i)
+        if (e[i]) (void)hipEventDestroy(e[i]);
+    }
+  } free_ev{ev};
+  for (auto &e : ev) UHIP(c, hipEventCreate(&e));
+  DevBuf    D;
+  uint32_t *d_qs, *d_qe, *d_rd, *d_bfirst, *d_bn, *d_bqlen, *d_last, *d_val, *d_idval, *d_cls;
+  const size_t NL = tb.n_lines;
+  UHIP(c, D.get(&d_qs, NL));
+  UHIP(c, D.get(&d_qe, NL));
+  UHIP(c, D.get(&d_rd, NL));
+  UHIP(c, D.get(&d_bfirst, NB));
+  UHIP(c, D.get(&d_bn, NB));
+  UHIP(c, D.get(&d_bqlen, NB));
+  UHIP(c, D.get(&d_last, NI));
+  UHIP(c, D.get(&d_val, NB));
+  UHIP(c, D.get(&d_idval, NI));
+  UHIP(c, D.get(&d_cls, NB)); // the block lists of the classes, back to back: wave, group, giant
+  uint64_t *d_goff;
+  UHIP(c, D.get(&d_goff, giant_off.size()));
+  std::vector<uint32_t> cls;
+  cls.reserve(NB);
+  cls.insert(cls.end(), wave.begin(), wave.end());
+  cls.insert(cls.end(), group.begin(), group.end());
+  cls.insert(cls.end(), giant.begin(), giant.end());
+  UHIP(c, hipEventRecord(ev[0], st));
+  UHIP(c, hipMemcpyAsync(d_qs, tb.line_qs, NL * 4, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_qe, tb.line_qe, NL * 4, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_rd, tb.line_read, NL * 4, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_bfirst, tb.block_first, NB * 4ull, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_bn, tb.block_n, NB * 4ull, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_bqlen, tb.block_qlen, NB * 4ull, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_last, tb.unitig_last_block, NI * 4ull, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_cls, cls.data(), NB * 4ull, hipMemcpyHostToDevice, st));
+  UHIP(c, hipMemcpyAsync(d_goff, giant_off.data(), giant_off.size() * 8, hipMemcpyHostToDevice, st));
+  UHIP(c, hipEventRecord(ev[1], st));
+
+  // rocprim's segmented radix sort: one temporary buffer for every sort of the run (sized by the largest)
+  void  *d_tmp = nullptr;
+  size_t tmp_bytes = 0;
+  auto   sort = [&](const uint64_t *in, uint64_t *outk, size_t n, uint32_t nseg, const uint64_t *off, int end_bit,
+                  size_t *need) -> hipError_t {
+    return rocprim::segmented_radix_sort_keys(need ? nullptr : d_tmp, need ? *need : tmp_bytes, in, outk,
+                                              static_cast<unsigned int>(n), nseg, off, off + 1, 0, end_bit, st);
+  };
+
+  // ---- pass 1
+  if (!wave.empty())
+    hipLaunchKernelGGL(k_uf_wave, dim3((S.n_wave + 3) / 4), dim3(256), 0, st, d_cls, S.n_wave, d_bfirst, d_bn, d_qs, d_qe,
+                       d_rd, d_val);
+  if (!group.empty())
+    hipLaunchKernelGGL(k_uf_group, dim3(S.n_group), dim3(256), 0, st, d_cls + S.n_wave, d_bfirst, d_bn, d_qs, d_qe, d_rd,
+                       d_val);
+  UHIP(c, hipGetLastError());
+  const uint64_t GL = giant_off.back();
+  if (GL) {
+    if (GL >= 0x7fffffffull) {
+      snprintf(c->err, sizeof(c->err), "more than 2^31 - 1 lines in giant blocks");
+      return MSGPU_E_ARG;
+    }
+    const uint32_t *d_gb = d_cls + S.n_wave + S.n_group;
+    uint64_t *d_k0, *d_k1, *d_e0, *d_e1;
+    UHIP(c, D.get(&d_k0, GL));
+    UHIP(c, D.get(&d_k1, GL));
+    UHIP(c, D.get(&d_e0, 2 * GL));
+    UHIP(c, D.get(&d_e1, 2 * GL));
+    uint64_t *d_eoff; // the endpoint segments: twice the line segments
+    std::vector<uint64_t> eoff(giant_off.size());
+    for (size_t i = 0; i < eoff.size(); ++i) eoff[i] = 2 * giant_off[i];
+    UHIP(c, D.get(&d_eoff, eoff.size()));
+    UHIP(c, hipMemcpyAsync(d_eoff, eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice, st));
+    size_t need1 = 0, need2 = 0;
+    UHIP(c, sort(d_k0, d_k1, GL, S.n_giant, d_goff, 64, &need1));
+    UHIP(c, sort(d_e0, d_e1, 2 * GL, S.n_giant, d_eoff, 33, &need2));
+    tmp_bytes = std::max(need1, need2);
+    uint8_t *tmp;
+    UHIP(c, D.get(&tmp, tmp_bytes));
+    d_tmp = tmp;
+    const uint32_t grid = static_cast<uint32_t>((GL + 255) / 256);
+    hipLaunchKernelGGL(k_uf_read_keys, dim3(grid), dim3(256), 0, st, d_gb, d_goff, S.n_giant, d_bfirst, d_rd, d_k0);
+    UHIP(c, hipGetLastError());
+    UHIP(c, sort(d_k0, d_k1, GL, S.n_giant, d_goff, 64, nullptr));
+    hipLaunchKernelGGL(k_uf_dedup_events, dim3(grid), dim3(256), 0, st, d_gb, d_goff, S.n_giant, d_bfirst, d_qs, d_qe, d_k1,
+                       d_e0);
+    UHIP(c, hipGetLastError());
+    UHIP(c, sort(d_e0, d_e1, 2 * GL, S.n_giant, d_eoff, 33, nullptr));
+    hipLaunchKernelGGL(k_uf_sweep_max, dim3((S.n_giant + 3) / 4), dim3(256), 0, st, d_gb, d_goff, S.n_giant, d_e1, d_val);
+    UHIP(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_uf_id_values, dim3((NI + 255) / 256), dim3(256), 0, st, d_last, NI, d_val, d_idval);
+  UHIP(c, hipGetLastError());
+  UHIP(c, hipEventRecord(ev[2], st));
+  std::vector<uint32_t> idval(NI);
+  UHIP(c, hipMemcpyAsync(idval.data(), d_idval, NI * 4ull, hipMemcpyDeviceToHost, st));
+  UHIP(c, hipStreamSynchronize(st));
+
+  // ---- quartiles, outliers (host: one value per id)
+  rc = msgpu_uf_quartiles(idval.data(), NI, &S.q1, &S.q3, &S.upper);
+  if (rc != MSGPU_OK) return rc;
+  std::vector<uint32_t> outl;
+  std::vector<uint64_t> ooff(1, 0);
+  for (uint32_t b = 0; b < NB; ++b)
+    if (static_cast<double>(idval[tb.block_unitig[b]]) > S.upper) {
+      outl.push_back(b);
+      ooff.push_back(ooff.back() + tb.block_n[b]);
+    }
+  const uint32_t NO = static_cast<uint32_t>(outl.size());
+  S.n_outliers      = NO;
+
+  // ---- pass 2: count, scan, emit
+  std::vector<uint32_t> fcount(NO), foff(NO + 1, 0);
+  std::vector<uint2>    frags;
+  UHIP(c, hipEventRecord(ev[3], st));
+  if (NO) {
+    const uint64_t OL = ooff.back();
+    if (OL >= 0x3fffffffull) {
+      snprintf(c->err, sizeof(c->err), "more than 2^30 - 1 lines in outlier blocks");
+      return MSGPU_E_ARG;
+    }
+    uint32_t *d_ob, *d_cnt, *d_foff;
+    uint64_t *d_ooff, *d_e0, *d_e1, *d_eoff;
+    UHIP(c, D.get(&d_ob, NO));
+    UHIP(c, D.get(&d_cnt, NO));
+    UHIP(c, D.get(&d_foff, NO));
+    UHIP(c, D.get(&d_ooff, NO + 1));
+    UHIP(c, D.get(&d_eoff, NO + 1));
+    UHIP(c, D.get(&d_e0, 2 * OL));
+    UHIP(c, D.get(&d_e1, 2 * OL));
+    std::vector<uint64_t> eoff(NO + 1);
+    for (uint32_t i = 0; i <= NO; ++i) eoff[i] = 2 * ooff[i];
+    UHIP(c, hipMemcpyAsync(d_ob, outl.data(), NO * 4ull, hipMemcpyHostToDevice, st));
+    UHIP(c, hipMemcpyAsync(d_ooff, ooff.data(), (NO + 1) * 8ull, hipMemcpyHostToDevice, st));
+    UHIP(c, hipMemcpyAsync(d_eoff, eoff.data(), (NO + 1) * 8ull, hipMemcpyHostToDevice, st));
+    size_t need = 0;
+    UHIP(c, sort(d_e0, d_e1, 2 * OL, NO, d_eoff, 33, &need));
+    if (need > tmp_bytes) {
+      uint8_t *tmp;
+      UHIP(c, D.get(&tmp, need));
+      d_tmp     = tmp;
+      tmp_bytes = need;
+    }
+    hipLaunchKernelGGL(k_uf_all_events, dim3(static_cast<uint32_t>((OL + 255) / 256)), dim3(256), 0, st, d_ob, d_ooff, NO,
+                       d_bfirst, d_qs, d_qe, d_e0);
+    UHIP(c, hipGetLastError());
+    UHIP(c, sort(d_e0, d_e1, 2 * OL, NO, d_eoff, 33, nullptr));
+    const int64_t t = static_cast<int64_t>(std::floor(S.q3)); // cov <= q3 <=> cov <= floor(q3) for an integer cov
+    hipLaunchKernelGGL(k_uf_runs<false>, dim3((NO + 255) / 256), dim3(256), 0, st, d_ob, d_ooff, NO, d_bqlen, d_e1, t,
+                       d_cnt, nullptr, nullptr);
+    UHIP(c, hipGetLastError());
+    UHIP(c, hipMemcpyAsync(fcount.data(), d_cnt, NO * 4ull, hipMemcpyDeviceToHost, st));
+    UHIP(c, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < NO; ++i) foff[i + 1] = foff[i] + fcount[i];
+    S.n_fragments = foff[NO];
+    for (uint32_t i = 0; i < NO; ++i) S.n_rescued += fcount[i] ? 1 : 0;
+    if (S.n_fragments) {
+      uint2 *d_frag;
+      UHIP(c, D.get(&d_frag, S.n_fragments));
+      UHIP(c, hipMemcpyAsync(d_foff, foff.data(), NO * 4ull, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_uf_runs<true>, dim3((NO + 255) / 256), dim3(256), 0, st, d_ob, d_ooff, NO, d_bqlen, d_e1, t,
+                         nullptr, d_foff, d_frag);
+      UHIP(c, hipGetLastError());
+      frags.resize(S.n_fragments);
+      UHIP(c, hipMemcpyAsync(frags.data(), d_frag, S.n_fragments * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    }
+  }
+  UHIP(c, hipEventRecord(ev[4], st));
+  UHIP(c, hipStreamSynchronize(st));
+
+  // ---- output plan: per block in PAF order the whole record or the fragments
+  const auto            p0 = std::chrono::steady_clock::now();
+  std::vector<msgpu_copy>         pieces;
+  std::vector<msgpu_fasta_record> recs;
+  std::string                     hdr;
+  uint64_t                        raw = 0, text = 0;
+  try {
+    auto add = [&](uint32_t id, uint64_t start, uint64_t stop, const char *h, size_t hn) { // bases [start, stop) of id
+      const uint32_t i  = rec_of[id];
+      const uint64_t L  = msgpu_seq_length(f, i);
+      const uint64_t e  = std::min(stop, L), s = std::min(start, e);
+      const uint64_t n  = e - s;
+      // a record without bases: the header without its '\n' (msgpu_fasta_format closes every record with one)
+      const uint32_t hl = static_cast<uint32_t>(n ? hn : hn - 1);
+      if (n) pieces.push_back(msgpu_copy{msgpu_seq_offset(f, i) + s, raw, static_cast<uint32_t>(n), MSGPU_COPY_ILLUMINA});
+      recs.push_back(msgpu_fasta_record{raw, text, static_cast<uint32_t>(n), static_cast<uint32_t>(hdr.size()), hl, 0});
+      hdr.append(h, hl);
+      raw += n;
+      text += msgpu_fasta_text_bytes(hl, n);
+    };
+    std::string h;
+    char        buf[96];
+    for (uint32_t b = 0, o = 0; b < NB; ++b) {
+      const uint32_t id = tb.block_unitig[b];
+      if (o < NO && outl[o] == b) {
+        for (uint32_t k = 0; k < fcount[o]; ++k) {
+          const uint2 fr = frags[foff[o] + k];
+          h.assign(">").append(msgpu_uf_unitig_name(u, id));
+          snprintf(buf, sizeof(buf), "_%u %u %u %u\n", k, fr.y - fr.x + 1, fr.x, fr.y);
+          h.append(buf);
+          add(id, fr.x, static_cast<uint64_t>(fr.y) + 1, h.data(), h.size());
+        }
+        ++o;
+      } else {
+        h.assign(">").append(desc[id]).append("\n");
+        add(id, 0, ~0ull, h.data(), h.size());
+      }
+    }
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  if (hdr.size() >= 0xffffffffull) return MSGPU_E_ARG;
+  S.n_records  = recs.size();
+  S.bases      = raw;
+  S.text_bytes = text;
+  msgpu_gather_plan *plan = nullptr;
+  rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  struct FreePlan {
+    msgpu_gather_plan *p;
+    ~FreePlan() { msgpu_gather_plan_free(p); }
+  } free_plan{plan};
+  S.plan_ms = since(p0);
+  uint8_t *d_raw, *d_text;
+  UHIP(c, D.get(&d_raw, raw + 16));
+  UHIP(c, D.get(&d_text, text + 16));
+  UHIP(c, hipEventRecord(ev[5], st));
+  rc = msgpu_gather_run(c->seq, plan, d_raw, raw + 16, st);
+  if (rc == MSGPU_OK) {
+    UHIP(c, hipEventRecord(ev[6], st));
+    rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
+  }
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "gather / format: %s", msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  UHIP(c, hipEventRecord(ev[7], st));
+  try {
+    res->text.resize(text);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  if (text) UHIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
+  UHIP(c, hipEventRecord(ev[8], st));
+  UHIP(c, hipStreamSynchronize(st));
+  auto el = [&](int a, int b) { return ms_between(ev[a], ev[b]); };
+  S.upload_ms = el(0, 1);
+  S.pass1_ms  = el(1, 2);
+  S.pass2_ms  = el(3, 4);
+  S.gather_ms = el(5, 6);
+  S.format_ms = el(6, 7);
+  S.copy_ms   = el(7, 8);
+  S.wall_ms   = since(w0);
+  *out        = res.release();
+  return MSGPU_OK;
+}
+
+int msgpu_uf_result_stats(const msgpu_uf_result *r, msgpu_uf_stats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->stats;
+  return MSGPU_OK;
+}
+
+const char *msgpu_uf_result_text(const msgpu_uf_result *r, uint64_t *len) {
+  if (len) *len = r ? r->text.size() : 0;
+  return r && !r->text.empty() ? r->text.data() : "";
+}
+
+void msgpu_uf_result_free(msgpu_uf_result *r) { delete r; }
+
+} // extern "C"

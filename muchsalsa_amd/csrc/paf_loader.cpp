@@ -68,6 +68,21 @@ public:
     m_slots[i] = Slot{h, size()};
     return size() - 1;
   }
+  // the id of a name without registering it (0xffffffff: unknown); a registry that was bulk-loaded and not looked up
+  // since is searched name by name
+  uint32_t find(const char *s, size_t n) const {
+    if (m_stale) {
+      for (uint32_t id = 0; id < size(); ++id)
+        if (length(id) == n && memcmp(name(id), s, n) == 0) return id;
+      return 0xffffffffu;
+    }
+    const uint64_t h = name_hash(s, n);
+    for (size_t i = h & (m_slots.size() - 1); m_slots[i].id_plus_1; i = (i + 1) & (m_slots.size() - 1)) {
+      const Slot &sl = m_slots[i];
+      if (sl.hash == h && length(sl.id_plus_1 - 1) == n && memcmp(name(sl.id_plus_1 - 1), s, n) == 0) return sl.id_plus_1 - 1;
+    }
+    return 0xffffffffu;
+  }
   uint32_t operator[](std::string_view name) { return get(name.data(), name.size(), name_hash(name.data(), name.size())); }
   uint32_t size() const { return static_cast<uint32_t>(m_bulk + m_later.size()); }
   void     clear() { // Registry::clear (Registry.cpp:47-52): numbering starts again at 0
@@ -706,5 +721,257 @@ void     msgpu_registry_clear(msgpu_registry *r) {
 
 /* Toggle::operator* / operator*= (include/ms/types/Toggle.h:127-153): XNOR */
 int msgpu_toggle_mul(int a, int b) { return msgpu::toggle_mul(a != 0, b != 0) ? 1 : 0; }
+
+} // extern "C"
+
+/* ---- the unitig coverage filter's PAF (msgpu_uf_parse, include/msgpu.h) --------------------------------------------
+ * Not msgpu_parse_paf's rule set: every line counts (none is filtered, the last one is parsed too), columns 0, 1, 2, 3, 5
+ * and 6 are read, and a block is a maximal run of consecutive lines with the same column 0.  The file is cut into one
+ * chunk per host thread at line boundaries as msgpu_parse_paf does; the threads tokenise and check their lines, then one
+ * pass in line order cuts the blocks and interns the names (first-seen ids) on the registries msgpu_parse_paf uses. */
+
+struct msgpu_uf {
+  std::vector<uint32_t> line_block, line_qs, line_qe, line_read;
+  std::vector<uint32_t> block_first, block_n, block_qlen, block_unitig;
+  std::vector<uint32_t> unitig_last_block; // by unitig id: its last block ("last block wins")
+  NameRegistry          unitigs, reads;
+};
+
+namespace {
+
+// plain decimal digits, optionally after one '-' when `sign` is set; the value must fit int32
+bool uf_int(const char *s, const char *e, bool sign, int64_t &out) {
+  bool neg = false;
+  if (sign && s < e && *s == '-') {
+    neg = true;
+    ++s;
+  }
+  if (s >= e) return false;
+  int64_t v = 0;
+  for (; s < e; ++s) {
+    if (*s < '0' || *s > '9') return false;
+    v = v * 10 + (*s - '0');
+    if (v > INT_MAX) return false;
+  }
+  out = neg ? -v : v;
+  return true;
+}
+
+struct UfLine {
+  const char *name, *read; // column 0 and column 5, in the file image
+  uint32_t    name_n, read_n;
+  uint64_t    read_h;
+  uint32_t    qlen, qs, qe;
+};
+
+struct UfChunk {
+  const char         *begin = nullptr, *end = nullptr;
+  size_t              first_line = 0, n_lines = 0;
+  std::vector<UfLine> lines;
+  int                 err = MSGPU_OK;
+  size_t              err_line = 0; // 0-based
+};
+
+inline bool uf_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+void uf_tokenise(UfChunk &ch) {
+  ch.lines.reserve(ch.n_lines);
+  size_t li = ch.first_line;
+  for (const char *q = ch.begin; q < ch.end; ++li) {
+    const void *nlp = memchr(q, '\n', static_cast<size_t>(ch.end - q));
+    const char *ls = q, *le = nlp ? static_cast<const char *>(nlp) : ch.end;
+    q = nlp ? le + 1 : ch.end;
+    while (le > ls && uf_space(le[-1])) --le; // str.rstrip()
+    const char *tb[7], *te[7];
+    int         nt = 0;
+    for (const char *s = ls, *c = ls; nt < 7; ++c) // str.split('\t'): every tab cuts, empty fields included
+      if (c == le || *c == '\t') {
+        tb[nt] = s;
+        te[nt] = c;
+        ++nt;
+        s = c + 1;
+        if (c == le) break;
+      }
+    auto fail = [&](int code) {
+      ch.err      = code;
+      ch.err_line = li;
+    };
+    if (le == ls || nt < 7) return fail(MSGPU_E_FORMAT); // a blank line or fewer than 7 fields
+    int64_t qlen, qs, qe, unused;
+    if (!uf_int(tb[1], te[1], false, qlen) || !uf_int(tb[2], te[2], false, qs) || !uf_int(tb[3], te[3], false, qe) ||
+        !uf_int(tb[6], te[6], true, unused))
+      return fail(MSGPU_E_NUMBER);
+    if (te[0] == tb[0]) return fail(MSGPU_E_FORMAT); // an empty unitig id
+    UfLine x;
+    x.name   = tb[0];
+    x.name_n = static_cast<uint32_t>(te[0] - tb[0]);
+    x.read   = tb[5];
+    x.read_n = static_cast<uint32_t>(te[5] - tb[5]);
+    x.read_h = name_hash(x.read, x.read_n);
+    x.qlen   = static_cast<uint32_t>(qlen);
+    x.qs     = static_cast<uint32_t>(qs);
+    x.qe     = static_cast<uint32_t>(qe);
+    ch.lines.push_back(x);
+  }
+}
+
+} // namespace
+
+extern "C" {
+
+int msgpu_uf_parse(const char *path, msgpu_uf **out, uint64_t *err_line) {
+  if (!path || !out) return MSGPU_E_ARG;
+  *out = nullptr;
+  if (err_line) *err_line = 0;
+  int fd = open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return MSGPU_E_IO;
+  struct stat st;
+  if (fstat(fd, &st) != 0) {
+    close(fd);
+    return MSGPU_E_IO;
+  }
+  const size_t len  = static_cast<size_t>(st.st_size);
+  const char  *data = nullptr;
+  if (len) {
+    void *m = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m == MAP_FAILED) {
+      close(fd);
+      return MSGPU_E_IO;
+    }
+    data = static_cast<const char *>(m);
+  }
+  close(fd);
+  msgpu_uf *u  = nullptr;
+  int       rc = MSGPU_OK;
+  size_t    bad_line = 0;
+  try {
+    u = new msgpu_uf();
+    unsigned nthr = std::thread::hardware_concurrency();
+    nthr          = nthr == 0 ? 1 : (nthr > 16 ? 16 : nthr);
+    if (const char *e = getenv("MSGPU_PARSE_THREADS"))
+      nthr = static_cast<unsigned>(std::min<size_t>(std::max(1, atoi(e)), std::max<size_t>(1, len)));
+    else
+      while (nthr > 1 && len / nthr < (1u << 20)) --nthr;
+    std::vector<UfChunk> chunks(nthr);
+    const char          *end = data + len, *cur = data;
+    for (unsigned t = 0; t < nthr; ++t) {
+      chunks[t].begin = cur;
+      const char *cut = (t + 1 == nthr) ? end : data + (len / nthr) * (t + 1);
+      if (cut < cur) cut = cur;
+      if (cut < end) {
+        const void *nl = memchr(cut, '\n', static_cast<size_t>(end - cut));
+        cut            = nl ? static_cast<const char *>(nl) + 1 : end;
+      }
+      chunks[t].end = cut;
+      cur           = cut;
+    }
+    std::vector<int> oom(nthr, 0);
+    auto             run = [&](auto &&fn) {
+      std::vector<std::thread> th;
+      struct JoinAll {
+        std::vector<std::thread> &t;
+        ~JoinAll() {
+          for (auto &x : t)
+            if (x.joinable()) x.join();
+        }
+      } join_all{th};
+      for (unsigned t = 1; t < nthr; ++t) th.emplace_back(fn, t);
+      fn(0u);
+      for (auto &x : th) x.join();
+      for (int o : oom)
+        if (o) throw std::bad_alloc();
+    };
+    run([&](unsigned t) { chunks[t].n_lines = count_lines(chunks[t].begin, chunks[t].end); });
+    size_t n_lines = 0;
+    for (auto &c : chunks) {
+      c.first_line = n_lines;
+      n_lines += c.n_lines;
+    }
+    run([&](unsigned t) {
+      try {
+        uf_tokenise(chunks[t]);
+      } catch (std::bad_alloc const &) { oom[t] = 1; }
+    });
+    if (n_lines == 0) { // an empty PAF: line 1 is missing
+      rc       = MSGPU_E_FORMAT;
+      bad_line = 0;
+    } else {
+      // in line order, so that the first bad line of either kind (a tokeniser's or a block's) is the one reported: a
+      // chunk's lines stop in front of its first bad line
+      for (auto *v : {&u->line_block, &u->line_qs, &u->line_qe, &u->line_read}) v->resize(n_lines);
+      const UfLine *prev = nullptr;
+      size_t        li   = 0;
+      for (auto &c : chunks) {
+        for (size_t k = 0; k < c.lines.size(); ++k, ++li) {
+          const UfLine &x = c.lines[k];
+          if (k + 8 < c.lines.size()) u->reads.want(c.lines[k + 8].read_h, 0);
+          if (!prev || prev->name_n != x.name_n || memcmp(prev->name, x.name, x.name_n) != 0) { // a new block
+            const uint32_t b  = static_cast<uint32_t>(u->block_first.size());
+            const uint32_t id = u->unitigs.get(x.name, x.name_n, name_hash(x.name, x.name_n));
+            if (id >= u->unitig_last_block.size()) u->unitig_last_block.resize(id + 1);
+            u->unitig_last_block[id] = b;
+            u->block_first.push_back(static_cast<uint32_t>(li));
+            u->block_n.push_back(0);
+            u->block_qlen.push_back(x.qlen);
+            u->block_unitig.push_back(id);
+          }
+          const uint32_t b = static_cast<uint32_t>(u->block_first.size() - 1);
+          if (x.qe > u->block_qlen[b]) { // the profile of the block is qlen (its first line's) positions long
+            rc       = MSGPU_E_NUMBER;
+            bad_line = li;
+            break;
+          }
+          ++u->block_n[b];
+          u->line_block[li] = b;
+          u->line_qs[li]    = x.qs;
+          u->line_qe[li]    = x.qe;
+          u->line_read[li]  = u->reads.get(x.read, x.read_n, x.read_h);
+          prev              = &x;
+        }
+        if (rc == MSGPU_OK && c.err != MSGPU_OK) {
+          rc       = c.err;
+          bad_line = c.err_line;
+        }
+        if (rc != MSGPU_OK) break;
+      }
+    }
+  } catch (std::bad_alloc const &) { rc = MSGPU_E_NOMEM; } catch (std::system_error const &) {
+    rc = MSGPU_E_NOMEM;
+  }
+  if (data) munmap(const_cast<char *>(data), len);
+  if (rc != MSGPU_OK) {
+    if (err_line) *err_line = bad_line + 1;
+    delete u;
+    return rc;
+  }
+  *out = u;
+  return MSGPU_OK;
+}
+
+void msgpu_uf_free(msgpu_uf *u) { delete u; }
+
+int msgpu_uf_get_tables(const msgpu_uf *u, msgpu_uf_tables *t) {
+  if (!u || !t) return MSGPU_E_ARG;
+  t->n_lines           = u->line_block.size();
+  t->n_blocks          = static_cast<uint32_t>(u->block_first.size());
+  t->n_unitigs         = u->unitigs.size();
+  t->n_reads           = u->reads.size();
+  t->line_block        = u->line_block.data();
+  t->line_qs           = u->line_qs.data();
+  t->line_qe           = u->line_qe.data();
+  t->line_read         = u->line_read.data();
+  t->block_first       = u->block_first.data();
+  t->block_n           = u->block_n.data();
+  t->block_qlen        = u->block_qlen.data();
+  t->block_unitig      = u->block_unitig.data();
+  t->unitig_last_block = u->unitig_last_block.data();
+  return MSGPU_OK;
+}
+
+const char *msgpu_uf_unitig_name(const msgpu_uf *u, uint32_t id) { return u ? u->unitigs.name(id) : nullptr; }
+const char *msgpu_uf_read_name(const msgpu_uf *u, uint32_t id) { return u ? u->reads.name(id) : nullptr; }
+uint32_t    msgpu_uf_unitig_id(const msgpu_uf *u, const char *name) {
+  return u && name ? u->unitigs.find(name, strlen(name)) : 0xffffffffu;
+}
 
 } // extern "C"

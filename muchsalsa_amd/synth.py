@@ -247,3 +247,95 @@ TILED = {
     "cfg2": dict(n_reads=10_000, read_len=5_000, n_anchors=0, seed=42, tiled=True, read_len_min=1_250),
     "cfg3": dict(n_reads=100_000, read_len=10_000, n_anchors=0, seed=43, tiled=True, read_len_min=2_500),
 }
+
+
+def unitig_filter_workload(n_reads, read_len, n_anchors, seed, coverage=10, n_repeats=12, repeat_hits=(200, 3000),
+                           n_long=2, long_len=120000, long_hits=12000, n_dup=2000, n_again=300):
+    """Input of the unitig coverage filter (muchsalsa_amd.unitig_filter): (PAF text, unitig FASTA text), both bytes.
+
+    Built on paf_table / genome_bases: the anchors are the unitigs (u<i>, their bases cut from the genome) and every
+    paf_table row is a PAF line (qlen = the unitig's length).  On top of that shape:
+      * n_repeats repeat unitigs (x<j>, 2-6 kb) that map at many genome positions: ~U{repeat_hits} lines each, all
+        inside the first half of the unitig -- outliers whose second half is a fragment; the largest blocks are giant;
+      * n_long long unitigs (l<j>, long_len bases) with long_hits lines each, piled up in a few windows: outliers with
+        many fragments;
+      * n_dup lines that repeat a read of their block with other coordinates (pass 1 counts a read once per block);
+      * n_again blocks of earlier unitigs that come back at the end of the file (the id's last block decides its value).
+    Deterministic in (seed, shape)."""
+    tab = paf_table(n_reads, read_len, n_anchors, seed, coverage)
+    a_start, a_len = anchor_layout(n_reads, read_len, n_anchors, seed, coverage)
+    genome = genome_bases(tab["genome"], seed)
+    G = int(tab["genome"])
+    names, qlen, qs, qe, reads = [], [], [], [], []  # one entry per block: arrays of its lines
+
+    aid, rid = tab["qname_id"], tab["tname_id"]
+    cut = np.flatnonzero(np.diff(aid)) + 1
+    starts = np.concatenate(([0], cut))
+    ends = np.concatenate((cut, [len(aid)]))
+    dup_blocks = set(_randint(seed, 40, n_dup, 0, max(len(starts) - 1, 0)).tolist()) if len(starts) else set()
+    for bi, (b0, b1) in enumerate(zip(starts.tolist(), ends.tolist())):
+        u = int(aid[b0])
+        s, e, r = tab["qstart"][b0:b1], tab["qend"][b0:b1], rid[b0:b1]
+        if bi in dup_blocks:
+            k = int(_randint(seed + b0, 41, 1, 0, b1 - b0 - 1)[0])
+            ns = int(_randint(seed + b0, 42, 1, 0, max(int(a_len[u]) - 1, 0))[0])
+            ne = int(_randint(seed + b0, 43, 1, ns, int(a_len[u]))[0])
+            s, e, r = np.append(s, ns), np.append(e, ne), np.append(r, r[k])
+        names.append("u%d" % u)
+        qlen.append(int(a_len[u]))
+        qs.append(s)
+        qe.append(e)
+        reads.append(r)
+    n_normal = len(names)
+    seqs = {"u%d" % i: genome[a_start[i]:a_start[i] + a_len[i]].tobytes() for i in range(len(a_start))}
+
+    def piled(name, L, n, stream, lo, hi, lens):
+        s = _randint(seed, stream, n, lo, hi)
+        e = np.minimum(s + _randint(seed, stream + 1, n, lens[0], lens[1]), L)
+        r = _randint(seed, stream + 2, n, 0, n_reads - 1)
+        r[1::17] = r[0::17][: len(r[1::17])]  # reads that hit the same unitig twice
+        names.append(name)
+        qlen.append(L)
+        qs.append(s)
+        qe.append(e)
+        reads.append(r)
+
+    r_len = _randint(seed, 44, n_repeats, 2000, 6000)
+    r_hits = _randint(seed, 45, n_repeats, repeat_hits[0], repeat_hits[1])
+    r_pos = _randint(seed, 46, n_repeats, 0, G - 6000)
+    for j in range(n_repeats):
+        L = int(r_len[j])
+        seqs["x%d" % j] = genome[r_pos[j]:r_pos[j] + L].tobytes()
+        piled("x%d" % j, L, int(r_hits[j]), 100 + 3 * j, 0, L // 2 - 400, (100, 400))
+    l_pos = _randint(seed, 47, n_long, 0, max(G - long_len, 0))
+    for j in range(n_long):
+        L = long_len
+        seqs["l%d" % j] = (genome[l_pos[j]:l_pos[j] + L].tobytes() * (L // max(G, 1) + 1))[:L]
+        # windows of 4 kb every 10 kb: the 6 kb between two windows are fragments
+        w = _randint(seed, 200 + 3 * j, long_hits, 0, L // 10000 - 1) * 10000
+        s = w + _randint(seed, 201 + 3 * j, long_hits, 0, 3000)
+        e = np.minimum(s + _randint(seed, 202 + 3 * j, long_hits, 100, 1000), L)
+        names.append("l%d" % j)
+        qlen.append(L)
+        qs.append(s)
+        qe.append(e)
+        reads.append(_randint(seed, 48 + j, long_hits, 0, n_reads - 1))
+    for k in _randint(seed, 49, min(n_again, n_normal), 0, max(n_normal - 1, 0)).tolist():
+        m = max(1, len(qs[k]) // 2)
+        names.append(names[k])
+        qlen.append(qlen[k])
+        qs.append(qs[k][:m])
+        qe.append(qe[k][:m])
+        reads.append(reads[k][:m])
+
+    out = []
+    for name, L, s, e, r in zip(names, qlen, qs, qe, reads):
+        n = len(s)
+        nm = np.maximum(np.asarray(e) - np.asarray(s), 0)
+        cols = [np.full(n, name, dtype=object), np.full(n, L), s, e, np.full(n, "+", dtype=object),
+                np.char.add("r", np.asarray(r).astype(str)), np.full(n, read_len), np.zeros(n, np.int64), nm, nm, nm,
+                np.full(n, 60)]
+        out.append("\n".join("\t".join(map(str, row)) for row in zip(*cols)))
+    paf = ("\n".join(out) + "\n").encode()
+    fasta = b"".join(b">%s synthetic len=%d\n%s\n" % (k.encode(), len(v), v) for k, v in seqs.items())
+    return paf, fasta
