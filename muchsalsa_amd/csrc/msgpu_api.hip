@@ -1302,6 +1302,10 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   c->chain_zeroed = false;
   a.chunk_sums   = c->chain_chunks.as<unsigned long long>();
   a.fast_path    = c->fast_path ? 1 : 0;
+  // The shortcut compares differences of two int32 bounds (|x| < 2^33) with wiggle - 3 in integers.  Saturating at 2^40
+  // keeps that verdict exact for every wiggle_room and keeps the conversion defined where a device-side
+  // (long long)(double)wiggle would not be (wiggle_room >= 2^63: the reference's reading of a negative argument).
+  a.fast_margin  = static_cast<long long>(std::min<uint64_t>(c->p.wiggle_room, uint64_t(1) << 40)) - 3;
   a.wiggle       = static_cast<double>(c->p.wiggle_room);
   a.ratio_pct    = c->p.ratio_pct;
   a.alt_frac     = c->p.alt_frac;

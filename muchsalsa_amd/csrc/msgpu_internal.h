@@ -104,6 +104,7 @@ struct ChainArgs {
   const uint32_t  *pair_tab_sub; // the width-32 / 16 / 8 tables, 8 bytes per pair, in the form k_chain_sub's sweep consumes
   unsigned long long *chunk_sums; // per chunk of COMPACT_CHUNK edges: {shortcut edges | orders << 32, ids} (see chunk_add)
   int              fast_path; // 0 disables the shortcut (every edge takes the full pair sweep)
+  long long        fast_margin; // the shortcut's integer bound: min(wiggle_room, 2^40) - 3 (host-computed, see launch)
   double           wiggle, ratio_pct, alt_frac;
   uint32_t         out_edge_base; // added to EdgeMatch::edge_idx: position of this batch's first edge in the job's table
 };

@@ -1860,8 +1860,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         b_hi = max(b_hi, __shfl_xor(b_hi, d));
         b_lo = min(b_lo, __shfl_xor(b_lo, d));
       }
-      const long long W = static_cast<long long>(a.wiggle) - 3;
-      clean = static_cast<long long>(a_hi) - b_lo <= W && static_cast<long long>(b_hi) - a_lo <= W;
+      clean = static_cast<long long>(a_hi) - b_lo <= a.fast_margin && static_cast<long long>(b_hi) - a_lo <= a.fast_margin;
     }
   }
 
@@ -2408,8 +2407,7 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
         b_hi = max(b_hi, __shfl_xor(b_hi, d));
         b_lo = min(b_lo, __shfl_xor(b_lo, d));
       }
-      const long long Wg = static_cast<long long>(a.wiggle) - 3;
-      clean = maybe && static_cast<long long>(a_hi) - b_lo <= Wg && static_cast<long long>(b_hi) - a_lo <= Wg;
+      clean = maybe && static_cast<long long>(a_hi) - b_lo <= a.fast_margin && static_cast<long long>(b_hi) - a_lo <= a.fast_margin;
     }
   }
 

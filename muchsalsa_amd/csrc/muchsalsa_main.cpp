@@ -2,6 +2,9 @@
 //     muchsalsa_gpu <contigs.paf> <unitigs.fa> <nanopore.fa|fq> <outdir> [threads] [wiggleRoom = 300]
 // (the argument list of src/Application.cpp:34-39; writes outdir/temp_1.target.fa, temp_1.query.fa, temp_1.align.paf like
 // src/main.cpp:130-322).  The body of main() is msgpu::assemble (include/msgpu_adapter.hpp): straight calls into the C-ABI.
+#include <cctype>
+#include <cerrno>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
@@ -9,6 +12,18 @@
 #include <thread>
 
 #include "msgpu_adapter.hpp"
+
+// wiggleRoom as the reference reads it (src/Application.cpp:76): static_cast<size_t>(std::stoi(arg)), so "-1" is 2^64 - 1, no
+// limit.  The whole argument must be an integer in int's range; anything else is refused (where stoi would throw).
+static bool parse_wiggle(const char *s, std::size_t *out) {
+  if (!(std::isdigit(static_cast<unsigned char>(s[0])) || s[0] == '-' || s[0] == '+')) return false;
+  errno          = 0;
+  char      *end = nullptr;
+  const long v   = std::strtol(s, &end, 10);
+  if (end == s || *end != '\0' || errno == ERANGE || v < INT_MIN || v > INT_MAX) return false;
+  *out = static_cast<std::size_t>(static_cast<int>(v));
+  return true;
+}
 
 int main(int argc, char **argv) {
   if (argc < 5) {
@@ -18,7 +33,11 @@ int main(int argc, char **argv) {
   unsigned threads = std::thread::hardware_concurrency();
   threads          = threads == 0 ? 1 : (threads > 16 ? 16 : threads);
   if (argc > 5) threads = static_cast<unsigned>(std::max(1, std::atoi(argv[5])));
-  const std::size_t wiggle = argc > 6 ? static_cast<std::size_t>(std::max(0, std::atoi(argv[6]))) : 300;
+  std::size_t wiggle = 300;
+  if (argc > 6 && !parse_wiggle(argv[6], &wiggle)) {
+    std::fprintf(stderr, "muchsalsa_gpu: wiggleRoom must be an integer, got '%s'\n", argv[6]);
+    return 2;
+  }
   try {
     const msgpu::AssemblyCounts n = msgpu::assemble(argv[1], argv[2], argv[3], argv[4], threads, wiggle, 0);
     std::printf("{\"rows\": %llu, \"reads\": %llu, \"edges\": %llu, \"orders\": %llu, \"contraction_edges\": %llu, \"paths\": %llu, "

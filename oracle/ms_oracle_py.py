@@ -137,7 +137,7 @@ def _std_min(a, b):
     return b if b < a else a
 
 
-def check_compatibility(mm, edge, id1, id2, wiggle, ratio_pct=15):  # mpp.cpp:38-142
+def check_compatibility(mm, edge, id1, id2, wiggle, ratio_pct=15, counters=None):  # mpp.cpp:38-142
     def nano_check(vertex):
         em1, em2 = mm.edge_matches[edge.vertices][id1], mm.edge_matches[edge.vertices][id2]
         vm1, vm2 = mm.vertex_matches[vertex][id1], mm.vertex_matches[vertex][id2]
@@ -179,13 +179,18 @@ def check_compatibility(mm, edge, id1, id2, wiggle, ratio_pct=15):  # mpp.cpp:38
         o2 = -o2
     if o1 == o2 and o1 != 0:
         diff = _std_max(d1, d2) - _std_min(d1, d2)
-        return diff <= float(wiggle) or _div(diff * 100, _std_max(d1, d2)) <= ratio_pct
+        if diff <= float(wiggle):
+            return True
+        if counters is not None:  # the ratio rule decides this pair
+            counters["ratio"] = counters.get("ratio", 0) + 1
+        return _div(diff * 100, _std_max(d1, d2)) <= ratio_pct
     if (o1 < 0 and o2 < 0) or (o1 > 0 and o2 > 0):
         return d1 + d2 <= float(wiggle)
     return False
 
 
-def get_max_pairwise_paths(mm, edge, illumina_ids, direction, wiggle, counters=None, alt_frac=0.75):  # mpp.cpp:145-305
+def get_max_pairwise_paths(mm, edge, illumina_ids, direction, wiggle, counters=None, alt_frac=0.75,
+                           ratio_pct=15):  # mpp.cpp:145-305
     result = []
     if not illumina_ids:
         return result
@@ -198,7 +203,7 @@ def get_max_pairwise_paths(mm, edge, illumina_ids, direction, wiggle, counters=N
         for l in range(k + 1, limit + 1):
             if counters is not None:
                 counters["compat"] = counters.get("compat", 0) + 1
-            ok = check_compatibility(mm, edge, v_start[k][1], v_start[l][1], wiggle)
+            ok = check_compatibility(mm, edge, v_start[k][1], v_start[l][1], wiggle, ratio_pct, counters)
             score = population[k][1] + ems[v_start[l][1]].score
             ok = ok and score > population[l][1]
             if ok:
@@ -286,14 +291,14 @@ def get_overlap(mm, ids, edge, direction, score, is_primary):  # ol.cpp:53-101
     return None
 
 
-def chaining_and_overlaps(mm, edge, wiggle=300, counters=None):  # src/main.cpp:328-414
+def chaining_and_overlaps(mm, edge, wiggle=300, counters=None, ratio_pct=15, alt_frac=0.75):  # src/main.cpp:328-414
     ems = mm.edge_matches.get(edge.vertices)
     if not ems:
         return
     plus = [i for i, em in ems.items() if em.direction]
     minus = [i for i, em in ems.items() if not em.direction]
-    minus_paths = get_max_pairwise_paths(mm, edge, minus, False, wiggle, counters)
-    plus_paths = get_max_pairwise_paths(mm, edge, plus, True, wiggle, counters)
+    minus_paths = get_max_pairwise_paths(mm, edge, minus, False, wiggle, counters, alt_frac, ratio_pct)
+    plus_paths = get_max_pairwise_paths(mm, edge, plus, True, wiggle, counters, alt_frac, ratio_pct)
     has_primary = any(p[2] for p in plus_paths) or any(p[2] for p in minus_paths)
     if has_primary:
         plus_paths = [p for p in plus_paths if p[2]]
@@ -317,8 +322,9 @@ def chaining_and_overlaps(mm, edge, wiggle=300, counters=None):  # src/main.cpp:
             edge.orders.append(o)
 
 
-def overlap(rows, th_overlap=100, wiggle=300):
-    """rows: iterable of dicts/structured rows with the ms_row fields.  Returns canonical python tables."""
+def overlap(rows, th_overlap=100, wiggle=300, ratio_pct=15, alt_frac=0.75):
+    """rows: iterable of dicts/structured rows with the ms_row fields.  Returns (canonical python tables, counters):
+    counters["compat"] = checkCompatibility calls, counters["ratio"] = pairs the ratio rule of mpp.cpp:136 decided."""
     mm = MatchMap()
     for r in sorted(({k: int(r[k]) for k in ("anchor_id", "read_id", "read_len", "i_lo", "i_hi", "n_lo", "n_hi", "score",
                                              "line", "flags")} for r in rows), key=lambda r: r["line"]):
@@ -326,7 +332,7 @@ def overlap(rows, th_overlap=100, wiggle=300):
     mm.calculate_edges(th_overlap)
     counters = {}
     for e in mm.edges.values():
-        chaining_and_overlaps(mm, e, wiggle, counters)
+        chaining_and_overlaps(mm, e, wiggle, counters, ratio_pct, alt_frac)
     edges = []
     for key in sorted(mm.edges):
         e = mm.edges[key]

@@ -131,3 +131,35 @@ def test_executable_takes_the_reference_argument_list(tmp_path):
     r = subprocess.run([exe, str(tmp_path / "missing.paf"), str(tmp_path / "unitigs.fa"), str(tmp_path / "nanopore.fa"),
                         str(tmp_path / "cpp")], capture_output=True, text=True, timeout=60)
     assert r.returncode == 1 and "muchsalsa_gpu:" in r.stderr
+
+
+@pytest.mark.gpu
+def test_both_executables_read_wiggle_room_like_the_reference(tmp_path):
+    """wiggleRoom is static_cast<size_t>(std::stoi(arg)) in the reference (src/Application.cpp:76): "-1" is 2^64 - 1 (no
+    limit), not 0.  muchsalsa_gpu and python -m muchsalsa_amd write the same files for "-1" and for "50", and both refuse
+    a wiggleRoom that is not an integer, with a message and a non-zero exit, before reading any input."""
+    import sys
+    import __graft_entry__ as g
+    from graphcases import make_dataset
+    g.build()
+    exe = os.path.join(ROOT, "muchsalsa_amd", "muchsalsa_gpu")
+    make_dataset(tmp_path, 4, 150, False)
+    ins = [str(tmp_path / n) for n in ("contigs.paf", "unitigs.fa", "nanopore.fa")]
+    names = ("temp_1.target.fa", "temp_1.query.fa", "temp_1.align.paf")
+    seen = {}
+    for arg in ("-1", "50", "abc", "1.5", ""):
+        outs = []
+        for who, cmd in (("cpp", [exe]), ("py", [sys.executable, "-m", "muchsalsa_amd"])):
+            d = tmp_path / ("%s%s" % (who, arg))
+            d.mkdir()
+            r = subprocess.run(cmd + ins + [str(d), "2", arg], cwd=ROOT, capture_output=True, text=True, timeout=300)
+            if arg in ("-1", "50"):
+                assert r.returncode == 0, (who, arg, r.stderr[-2000:])
+                outs.append([(d / n).read_bytes() for n in names])
+            else:
+                assert r.returncode != 0 and "wiggleRoom" in r.stderr, (who, arg, r.returncode, r.stderr[-2000:])
+                assert not any((d / n).exists() for n in names)
+        if outs:
+            assert outs[0] == outs[1], arg
+            seen[arg] = outs[0]
+    assert seen["-1"] != seen["50"]

@@ -146,3 +146,136 @@ CASES = {
     "chain2301": case_two_anchor_chain(2301), "chain2353": case_two_anchor_chain(2353),
     "chain2354": case_two_anchor_chain(2354), "chain3000": case_two_anchor_chain(3000),
 }
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Non-default msgpu_params: the parameter-dependent rules of checkCompatibility (mpp.cpp:133-139: wiggle room and the
+# ratio rule) and of the alternatives of getMaxPairwisePaths (mpp.cpp:223-249: alt_frac) at their boundaries.
+# ----------------------------------------------------------------------------------------------------------------------
+def case_two_anchors(n0, n1, scores=(580, 570, 560, 550)):
+    """case_two_anchor_chain with the second anchor placed freely: anchor 0 at 1000..1599 on read 0 and 3000..3599 on
+    read 1, anchor 1 at n0..n0+599 on read 0 and n1..n1+599 on read 1 (all '+', full anchor overlaps, rRatio 1: the
+    corrected ranges are the raw ones and the EdgeMatch scores are the row-score sums, exactly)."""
+    return np.array([
+        row(0, 0, 9000, 0, 599, 1000, 1599, scores[0], 0, True),
+        row(0, 1, 9000, 0, 599, 3000, 3599, scores[1], 1, True),
+        row(1, 0, 9000, 0, 599, n0, n0 + 599, scores[2], 2, True),
+        row(1, 1, 9000, 0, 599, n1, n1 + 599, scores[3], 3, True),
+    ], dtype=ROW_DTYPE)
+
+
+def case_gaps(d1, d2, scores=(580, 570, 560, 550)):
+    """Orientation +1 on both reads with diff1 = d1 and diff2 = d2 (diff = c2.lo - c1.hi + 1, mpp.cpp:115-120)."""
+    return case_two_anchors(1598 + d1, 3598 + d2, scores)
+
+
+def case_mixed(d1, d2):
+    """Orientation +2 on read 0 (anchor 1 overlaps anchor 0 by d1 = c1.hi - c2.lo + 1 bases, mpp.cpp:106-110; the raw
+    ranges are in the same order, so nanoCheck does not abort) and +1 on read 1 with a gap diff2 = d2: a mixed pair,
+    compatible iff d1 + d2 <= wiggle (mpp.cpp:137-138); the ratio rule does not apply."""
+    return case_two_anchors(1600 - d1, 3598 + d2)
+
+
+def pad(rows, n_fill):
+    """rows plus n_fill filler anchors shared by reads 0 and 1 with the OPPOSITE strand on read 1: their EdgeMatches are
+    reverse, so no filler is ever compared with a probe EdgeMatch (pairs of unlike direction are not compared,
+    main.cpp:335-347), and all of them sit on the same ranges of both reads, so no two fillers are compatible
+    (orientation 0 on both reads).  They are not primary (score < 500), so the primary filter of main.cpp:355-366 never
+    drops a probe path for them.  They fill the edge into a width class of the chain kernels and leave the probe's
+    chaining verdict as derived by hand."""
+    out = [tuple(r) for r in rows]
+    line = int(rows["line"].max()) + 1
+    for k in range(n_fill):
+        a = int(rows["anchor_id"].max()) + 1 + k
+        out.append(row(a, 0, 9000, 0, 599, 6000, 6599, 450, line, True))
+        out.append(row(a, 1, 9000, 0, 599, 6000, 6599, 440, line + 1, False))
+        line += 2
+    return np.array(out, dtype=ROW_DTYPE)
+
+
+# EdgeMatches per edge in each width class of the chain kernels: <= 8, 9-16, 17-32, 33-64 (sub-wavefront and wavefront
+# bodies), 65-256 (k_chain_big, LDS) and > 256 (k_chain_big, global memory)
+PAD_FILL = {"w8": 4, "w16": 12, "w32": 28, "w64": 60, "w256": 200, "wbig": 300}
+
+
+def chained(t):
+    """Is there an order whose path holds both probe anchors (0 and 1)?  -- the chaining verdict, read off the ids."""
+    o = t["orders"]
+    return any({0, 1} <= set(int(x) for x in t["ids"][int(q["ids_off"]): int(q["ids_off"]) + int(q["ids_cnt"])]) for q in o)
+
+
+def single_paths(t):
+    """The set of one-anchor paths among the orders (anchor ids)."""
+    return {int(t["ids"][int(q["ids_off"])]) for q in t["orders"] if int(q["ids_cnt"]) == 1}
+
+
+def params(oracle, **kw):
+    p = oracle.default_params()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+# (name, rows, msgpu_params fields, expected chaining verdict of the probe)
+PARAM_CASES = []
+for _w in (0, 1, 7, 299, 301, 1000):
+    # ratio 0: only diff == 0 passes the ratio rule, so the wiggle rule alone decides; d1 = 2002
+    PARAM_CASES.append(("wiggle%d_eq" % _w, case_gaps(2002, 2002 + _w), dict(wiggle_room=_w, ratio_pct=0.0), True))
+    PARAM_CASES.append(("wiggle%d_over" % _w, case_gaps(2002, 2003 + _w), dict(wiggle_room=_w, ratio_pct=0.0), False))
+PARAM_CASES += [
+    # 500 * 100 / 2000 == 25.0 exactly in fp64: <= 25 chains; 501 * 100 / 2000 = 25.05 does not (wiggle 0 rules itself out)
+    ("ratio25_eq", case_gaps(2000, 1500), dict(wiggle_room=0, ratio_pct=25.0), True),
+    ("ratio25_over", case_gaps(2000, 1499), dict(wiggle_room=0, ratio_pct=25.0), False),
+    ("ratio25_eq_swapped", case_gaps(1500, 2000), dict(wiggle_room=0, ratio_pct=25.0), True),
+    # the ratio rule beyond wiggle 300: 375 * 100 / 5000 == 7.5 exactly; and at ratio 0 a diff of 301 (13 %) no longer chains
+    ("w300_ratio7.5_eq", case_gaps(5000, 4625), dict(wiggle_room=300, ratio_pct=7.5), True),
+    ("w300_ratio7.5_over", case_gaps(5000, 4624), dict(wiggle_room=300, ratio_pct=7.5), False),
+    ("w300_ratio0_eq", case_gaps(2002, 2302), dict(wiggle_room=300, ratio_pct=0.0), True),
+    ("w300_ratio0_over", case_gaps(2002, 2303), dict(wiggle_room=300, ratio_pct=0.0), False),
+    # mixed pair: d1 + d2 == wiggle chains, one more does not -- at any ratio (100 % would pass every same-orientation pair)
+    ("mixed300_eq", case_mixed(100, 200), dict(wiggle_room=300, ratio_pct=100.0), True),
+    ("mixed300_over", case_mixed(100, 201), dict(wiggle_room=300, ratio_pct=100.0), False),
+    ("mixed50_eq", case_mixed(20, 30), dict(wiggle_room=50, ratio_pct=100.0), True),
+    ("mixed50_over", case_mixed(21, 30), dict(wiggle_room=50, ratio_pct=100.0), False),
+]
+
+# alternatives (mpp.cpp:223-249): two incompatible single-anchor paths (diff 2002 against 5000: 59.96 % apart) with
+# EdgeMatch scores `best` and `alt`; the second one is an alternative iff alt > alt_frac * best (strictly)
+ALT_CASES = [  # (name, best, alt, alt_frac, taken)
+    ("alt075_eq", 2400, 1800, 0.75, False), ("alt075_over", 2400, 1801, 0.75, True),
+    ("alt050_eq", 2400, 1200, 0.5, False), ("alt050_over", 2400, 1201, 0.5, True),
+    ("alt000", 2400, 1000, 0.0, True), ("alt100", 2400, 2399, 1.0, False),
+]
+
+
+def case_alt(best, alt):
+    return case_gaps(2002, 5000, (best // 2, best - best // 2, alt // 2, alt - alt // 2))
+
+
+def test_param_cases_arithmetic():
+    """The boundaries above in the reference's own fp64 arithmetic (mpp.cpp:133-139, :223)."""
+    assert 500.0 * 100 / 2000.0 == 25.0 and 501.0 * 100 / 2000.0 > 25.0
+    assert 375.0 * 100 / 5000.0 == 7.5 and 376.0 * 100 / 5000.0 > 7.5 and 301.0 * 100 / 2303.0 <= 15
+    assert 2400.0 * 0.75 == 1800.0 and 2400.0 * 0.5 == 1200.0
+    assert 2998.0 * 100 / 5000.0 > 15.0
+
+
+@pytest.mark.parametrize("fill", [0] + sorted(PAD_FILL.values()))
+@pytest.mark.parametrize("name,rows,kw,want", PARAM_CASES, ids=[c[0] for c in PARAM_CASES])
+def test_param_cases_oracle(oracle, name, rows, kw, want, fill):
+    t = oracle.overlap(pad(rows, fill), params(oracle, **kw))
+    assert len(t["edges"]) == 1 and int(t["edges"]["em_cnt"][0]) == 2 + fill
+    assert chained(t) == want
+    if fill == 0 and want:
+        assert list(t["ids"]) == [0, 1] and len(t["orders"]) == 1
+    if fill == 0 and not want:  # two single-anchor paths, both kept (1110 > 0.75 * 1150)
+        assert len(t["orders"]) == 2 and single_paths(t) == {0, 1} and t["edges"]["shadow"][0] == 1
+
+
+@pytest.mark.parametrize("fill", [0] + sorted(PAD_FILL.values()))
+@pytest.mark.parametrize("name,best,alt,frac,taken", ALT_CASES, ids=[c[0] for c in ALT_CASES])
+def test_alt_cases_oracle(oracle, name, best, alt, frac, taken, fill):
+    t = oracle.overlap(pad(case_alt(best, alt), fill), params(oracle, alt_frac=frac))
+    assert [float(s) for s in t["ems"]["score"][:2]] == [float(best), float(alt)]
+    assert not chained(t)
+    assert (1 in single_paths(t)) == taken and 0 in single_paths(t)

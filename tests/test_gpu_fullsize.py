@@ -65,6 +65,9 @@ def test_named_config_bit_exact(oracle, cfg):
         assert 90_000 < c.n_edges < 105_000 and 2.4e6 < c.n_ems < 2.8e6
     else:
         assert 0.9e6 < c.n_edges < 1.05e6 and 24e6 < c.n_ems < 28e6
+        # the all-pairs-compatible shortcut at wiggle 300: its margin, now computed on the host and saturated, takes the
+        # edges the device-side (long long)wiggle - 3 took (5372 on this shape); a margin that grew would take more
+        assert c.n_edges_fastpath == 5372
 
 
 def test_cfg4_shards_of_cfg3_bit_exact(oracle):

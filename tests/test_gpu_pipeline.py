@@ -16,11 +16,13 @@ pytestmark = pytest.mark.gpu
 _COMP = bytes.maketrans(b"ACGT", b"TGCA")
 
 
-def oracle_flow(oracle, rows, nano, illu):
+def oracle_flow(oracle, rows, nano, illu, wiggle=300):
     from oracle import ms_graph_py as G
     from oracle.ms_assemble_py import assemble_path
-    t = oracle.overlap(rows)
-    co = oracle.find_contraction_edges(t, len(t["read_len"]))
+    p = oracle.default_params()
+    p.wiggle_room = wiggle
+    t = oracle.overlap(rows, p)
+    co = oracle.find_contraction_edges(t, len(t["read_len"]), wiggle=wiggle)
     vm = {(int(r["read_id"]), int(r["anchor_id"])): r for r in rows}
     g, el, oo = G.build_graph(t, t["read_len"], t["read_first_line"])
     contain = G.clean_up(g, el, oo, co, lambda r, a: (r, a) in vm)
@@ -74,3 +76,24 @@ def test_command_line(tmp_path):
     res = json.loads(p.stdout.strip().splitlines()[-1])
     assert res["contigs"] >= 1 and res["target_bases"] > 200_000
     assert (out_dir / "temp_1.target.fa").stat().st_size > res["target_bases"]
+
+
+def test_files_in_files_out_at_other_wiggle_rooms(oracle, tmp_path):
+    """wiggleRoom (the sixth argument) through pipeline.run into the chain kernels and sanityCheck: at 50 and 2000 the
+    three files equal the oracle flow's at the same wiggle, byte for byte, and differ from the files of wiggle 300 (a
+    jitter of 150 bases puts many anchor pairs between those bounds)."""
+    from muchsalsa_amd import pipeline
+    rows, lay, genome, nano, illu, nano_name = make_dataset(tmp_path, 4, 150, False)
+    names = ("temp_1.target.fa", "temp_1.query.fa", "temp_1.align.paf")
+    files = {}
+    for w in (50, 300, 2000):
+        out_dir = tmp_path / ("out%d" % w)
+        out_dir.mkdir()
+        res = pipeline.run(str(tmp_path / "contigs.paf"), str(tmp_path / "unitigs.fa"), str(tmp_path / nano_name),
+                           str(out_dir), threads=4, wiggle_room=w)
+        want = oracle_flow(oracle, rows, nano, illu, wiggle=w)
+        assert res["contigs"] == len(want)
+        files[w] = [(out_dir / n).read_bytes() for n in names]
+        assert files[w] == [b"".join(r[k] for r in want) for k in ("target_fa", "query_fa", "paf")], w
+    for w in (50, 2000):
+        assert all(a != b for a, b in zip(files[w], files[300])), w

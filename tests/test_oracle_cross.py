@@ -11,9 +11,19 @@ import ms_oracle_py as P
 from muchsalsa_amd import synth
 
 
-def _compare(rows, oracle):
-    c = oracle.overlap(rows)
-    py_edges, counters = P.overlap(rows)
+def _params(oracle, **kw):
+    p = oracle.default_params()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _compare(rows, oracle, **kw):
+    """kw: msgpu_params fields other than the defaults, given to both restatements."""
+    p = _params(oracle, **kw)
+    c = oracle.overlap(rows, p)
+    py_edges, counters = P.overlap(rows, th_overlap=p.th_overlap, wiggle=p.wiggle_room, ratio_pct=p.ratio_pct,
+                                   alt_frac=p.alt_frac)
     assert len(py_edges) == len(c["edges"])
     assert counters.get("compat", 0) == c["compat_checks"]
     ids = c["ids"]
@@ -35,6 +45,7 @@ def _compare(rows, oracle):
             assert float(a["left"]).hex() == float(b["left_offset"]).hex()
             assert float(a["right"]).hex() == float(b["right_offset"]).hex()
             assert a["ids"] == [int(x) for x in ids[int(b["ids_off"]):int(b["ids_off"]) + int(b["ids_cnt"])]]
+    return c, counters
 
 
 @pytest.mark.parametrize("shape", [(60, 3000, 150, 1), (120, 4000, 400, 2), (80, 8000, 500, 3), (200, 2500, 500, 4)])
@@ -71,3 +82,38 @@ def test_parse_agrees(oracle, tmp_path):
     # and both agree with the vectorised generator's own A1 restatement
     rows, rn2, an2 = synth.accepted_rows(tab)
     assert rows.tobytes() == c["rows"].tobytes() and rn2 == rn and an2 == an
+
+
+PARAM_SETS = [
+    dict(wiggle_room=0), dict(wiggle_room=4), dict(wiggle_room=50), dict(wiggle_room=2000),
+    dict(wiggle_room=2 ** 64 - 1), dict(wiggle_room=0, ratio_pct=0.0), dict(wiggle_room=0, ratio_pct=7.5),
+    dict(wiggle_room=0, ratio_pct=100.0), dict(wiggle_room=0, alt_frac=0.0), dict(wiggle_room=0, alt_frac=0.5),
+    dict(wiggle_room=300, alt_frac=0.99), dict(wiggle_room=300, alt_frac=1.0), dict(wiggle_room=300, ratio_pct=0.0),
+    dict(th_overlap=0), dict(th_overlap=400),
+]
+# sets that leave this small workload's tables as they are: at wiggle 300 its few ratio-decided pairs fail the wiggle
+# test by more than 15 % (test_gpu_params.py shows ratio 0 biting at wiggle 300 on a larger workload)
+NO_BITE = [dict(wiggle_room=300, ratio_pct=0.0)]
+
+
+@pytest.mark.parametrize("kw", PARAM_SETS, ids=lambda kw: ",".join("%s=%s" % i for i in kw.items()))
+def test_restatements_agree_at_non_default_params(oracle, kw):
+    """Every field of msgpu_params that the overlap path reads, away from its default: the C oracle's handling of each
+    is pinned by the Python restatement, on mixed-direction input (30 % of the rows flipped) so that mixed pairs, both
+    path lists and the alternatives are exercised; and each set changes the tables (the field is read at all)."""
+    rows = synth.synth_rows(120, 4000, 400, 2).copy()
+    rng = np.random.default_rng(3)
+    rows["flags"] ^= (rng.random(len(rows)) < 0.3).astype(rows["flags"].dtype)
+    c, _ = _compare(rows, oracle, **kw)
+    d = oracle.overlap(rows)
+    assert any(c[k].tobytes() != d[k].tobytes() for k in ("edges", "ems", "orders", "ids")) == (kw not in NO_BITE), kw
+
+
+def test_ratio_rule_decides_many_pairs_at_wiggle_0(oracle):
+    """At wiggle 0 the ratio rule of mpp.cpp:136 decides nearly every same-orientation pair; at wiggle 300 only a few:
+    the branch a hard-coded wiggle would hide."""
+    rows = synth.synth_rows(80, 4000, 200, 5)
+    _, at0 = _compare(rows, oracle, wiggle_room=0)
+    _, at300 = _compare(rows, oracle)
+    assert at0["ratio"] > 1000 and at0["ratio"] > 20 * at300.get("ratio", 0), (at0, at300)
+    assert at0["ratio"] <= at0["compat"]

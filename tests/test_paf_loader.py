@@ -172,3 +172,26 @@ def test_column_counts_and_trailing_tabs(oracle, tmp_path):
     # the same without a trailing newline behind the (never parsed) last line, and with the file ending inside a 16-byte step
     path = _write(tmp_path, lines + ["x"], trailing_newline=False)
     assert overlap.parse_paf(path).rows.tobytes() == want["rows"].tobytes()
+
+
+@pytest.mark.parametrize("min_matches,th_length,th_matches", [(0, 0, 0), (420, 600, 450), (500, 500, 700), (600, 2000, 500)])
+def test_non_default_filter_thresholds_match_oracle(oracle, tmp_path, min_matches, th_length, th_matches):
+    """min_matches (:106-107), th_length and th_matches (:121-122) are read from msgpu_params: at values other than the
+    defaults the accepted rows and their primary flags equal the oracle's parse with the same params, and the
+    thresholds bite (the accepted set or the primary flags differ from the default parse)."""
+    tab = synth.paf_table(150, 4000, 400, 22, min_intersection=300)
+    path = _write(tmp_path, synth.paf_lines(tab))
+    p = overlap.default_params()
+    p.min_matches, p.th_length, p.th_matches = min_matches, th_length, th_matches
+    q = oracle.default_params()
+    q.min_matches, q.th_length, q.th_matches = min_matches, th_length, th_matches
+    got = overlap.parse_paf(path, p)
+    want = oracle.parse_paf(path, q)
+    assert got.rows.tobytes() == want["rows"].tobytes()
+    assert got.read_names == want["read_names"] and got.anchor_names == want["anchor_names"]
+    base = oracle.parse_paf(path)["rows"]
+    if (min_matches, th_length, th_matches) == (0, 0, 0):
+        assert len(want["rows"]) > len(base)
+    assert want["rows"].tobytes() != base.tobytes()
+    span = want["rows"]["i_hi"] - want["rows"]["i_lo"] + 1
+    assert (span >= min_matches).all() and ((want["rows"]["flags"] & 2 != 0) <= (span >= th_length)).all()
