@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "msgpu.h"
 #include "msgpu_internal.h"
@@ -2192,9 +2193,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 // its six fp64 divisions, the path lists, the filters, getOverlap) whatever the edge's size, on 64 lanes of which an
 // edge with n EdgeMatches uses n.  Here every quantity that is wave-uniform in k_chain (the edge, its masks, counters,
 // the path being emitted) is uniform per GROUP of W lanes and lives in vector registers; wavefront masks (__ballot) are
-// cut to the group's W bits, broadcasts are ds_bpermute shuffles inside the group, and loops whose trip count depends
-// on the edge run to the largest count among the groups with the finished groups predicated off.  Same arithmetic in
-// the same order as k_chain, so the same bits.  Edges are assigned through a list built by k_list_edges_by_size.
+// cut to the group's W bits, broadcasts inside the group are DPP / permlane moves (the chaining DP) or ds_bpermute
+// shuffles (elsewhere), and loops whose trip count depends on the edge run to the largest count among the groups with
+// the finished groups predicated off.  Same arithmetic in the same order as k_chain, so the same bits.  Edges are
+// assigned through a list built by k_list_edges_by_size.
 // ---------------------------------------------------------------------------------------------------------------------
 
 struct __attribute__((aligned(16))) SubPath { // a path of one direction; mask bit i = the group's i-th EdgeMatch
@@ -2211,6 +2213,56 @@ __device__ __forceinline__ double shfl_f64(double v, int src) {
 // the W bits of a wavefront mask that belong to this lane's group
 template <int W> __device__ __forceinline__ uint32_t group_bits(unsigned long long m, int gbase) {
   return static_cast<uint32_t>(m >> gbase) & (W == 32 ? 0xffffffffu : ((1u << W) - 1u));
+}
+
+// the largest count over the wavefront's groups, from a mask that holds the lanes sl < count of every group (a prefix per
+// group): OR the groups onto each other and count -- scalar instructions instead of a shuffle reduction
+template <int W> __device__ __forceinline__ int longest_prefix(unsigned long long m) {
+#pragma unroll
+  for (int d = 32; d >= W; d >>= 1) m |= m >> d;
+  // (a 32-bit count: the unrolled DP's exit tests are then scalar compares, not 64-bit vector ones)
+  return __popc(static_cast<uint32_t>(m) & (W == 32 ? 0xffffffffu : ((1u << W) - 1u)));
+}
+
+// lane K of every 16-lane DPP row, to the whole row: row_newbcast:K (DPP control 0x150 + K, gfx90a and later), one
+// v_mov_b32_dpp per half of the value.  The control is an immediate, hence the template.
+template <int K> __device__ __forceinline__ uint32_t row_bcast(uint32_t v) {
+  static_assert(K >= 0 && K < 16, "row lane");
+  return static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), 0x150 + K, 0xf, 0xf, false));
+}
+
+// lane K of this lane's group of W lanes, to the whole group, without LDS.  W = 16: a group is a DPP row.  W = 8: lane K
+// of the row into the lower half-row (bank mask 0b0011: DPP banks are the four lanes 4b..4b+3 of a row), lane 8 + K into
+// the upper one (0b1100).  W = 32: every row takes its own lane K % 16; for K < 16 row_bcast:15 (DPP control 0x142) then
+// copies the even rows' lane 15 onto the odd rows (row mask 0b1010), for K >= 16 v_permlane16_swap (gfx950) swaps the odd
+// rows of one copy with the even rows of the other, and its second result holds each half's odd row on both of its rows.
+// (The second copy is a broadcast of the odd rows only: two distinct registers without a move.)
+template <int W, int K> __device__ __forceinline__ uint32_t group_bcast(uint32_t v) {
+  static_assert(K >= 0 && K < W, "group lane");
+  if constexpr (W == 16) {
+    return row_bcast<K>(v);
+  } else if constexpr (W == 8) {
+    const int lo = __builtin_amdgcn_mov_dpp(static_cast<int>(v), 0x150 + K, 0xf, 0x3, false);
+    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(lo, static_cast<int>(v), 0x150 + 8 + K, 0xf, 0xc, false));
+  } else if constexpr (K < 16) {
+    const int r = static_cast<int>(row_bcast<K>(v));
+    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(r, r, 0x142, 0xa, 0xf, false));
+  } else {
+    const uint32_t r  = row_bcast<K - 16>(v);
+    const uint32_t ro = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), 0x150 + K - 16, 0xa, 0xf, false));
+    return __builtin_amdgcn_permlane16_swap(r, ro, false, false)[1];
+  }
+}
+template <int W, int K> __device__ __forceinline__ double group_bcast_f64(double v) {
+  const unsigned long long b  = __builtin_bit_cast(unsigned long long, v);
+  const uint32_t           lo = group_bcast<W, K>(static_cast<uint32_t>(b));
+  const uint32_t           hi = group_bcast<W, K>(static_cast<uint32_t>(b >> 32));
+  return __builtin_bit_cast(double, (static_cast<unsigned long long>(hi) << 32) | lo);
+}
+
+// f(integral_constant<int, K>) for K = 0, 1, ... while it returns true (an unrolled loop whose step number is a constant)
+template <typename F, int... K> __device__ __forceinline__ void unroll_while(F &&f, std::integer_sequence<int, K...>) {
+  (void)(f(std::integral_constant<int, K>{}) && ...);
 }
 
 // paths_of_direction for a group of W lanes; returns the group's path count (group-uniform, 0 for an empty direction)
@@ -2413,10 +2465,9 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
 
   // ---- checkCompatibility for every pair k < l: a lane takes pair p0 + sl of ITS edge, W pairs per edge and step ------
   const int P = clean ? 0 : static_cast<int>(n * (n - 1) / 2);
-  int       Pmax = P;
-#pragma unroll
-  for (int d = 32; d >= W; d >>= 1) Pmax = max(Pmax, __shfl_xor(Pmax, d));
-  Pmax = __builtin_amdgcn_readfirstlane(Pmax);
+  // the largest P of the wavefront: P grows with n, so it is P of the longest edge that is not clean
+  const int nP   = longest_prefix<W>(__ballot(act && !clean));
+  const int Pmax = nP * (nP - 1) / 2;
   const bool               one_dir = __ballot(m_plus != 0 && m_minus != 0) == 0; // every edge of the wave has one direction
   const unsigned long long KD_one  = __ballot(m_minus == 0);
   // the table of this width through a buffer descriptor (scalar step offset + constant lane offset).  Lanes past their
@@ -2496,11 +2547,14 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
       bits = ok;
     }
     // the pairs of row l are consecutive lanes of the group; the first lane of each run stores the run's bits: `run`
-    // bits from bit `lane` on, put at bit k (run <= 31; the shift count k is the low five bits of its table word)
+    // bits from bit `lane` on, put at bit k (run <= 31; the shift count k is the low five bits of its table word).  The
+    // rows were zeroed before the sweep and every bit has one writer, so an LDS OR without return stores the same words
+    // as a read-modify-write, and nothing in the loop waits for it
     const uint32_t run = (kl.y >> 8) & 0xffu;
     if (run != 0 && in_range) {
       uint32_t *row = reinterpret_cast<uint32_t *>(cmg + (kl.y >> 16));
-      *row |= __builtin_amdgcn_ubfe(static_cast<uint32_t>(bits >> lane), 0u, run) << (kl.y & 31u);
+      __hip_atomic_fetch_or(row, __builtin_amdgcn_ubfe(static_cast<uint32_t>(bits >> lane), 0u, run) << (kl.y & 31u),
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   };
   auto sweep = [&](auto wft, auto dirt) __attribute__((always_inline)) {
@@ -2529,24 +2583,14 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   const uint32_t mycm = clean ? (act ? (1u << sl) - 1u : 0u) : cm[lane];
 
   // ---- chaining DP (mpp.cpp:181-199) ---------------------------------------------------------------------------------
-  int nmax = static_cast<int>(n);
-#pragma unroll
-  for (int d = 32; d >= W; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d));
-  nmax = __builtin_amdgcn_readfirstlane(nmax);
-  double   pop = em_score;
-  uint32_t pm  = 1u << sl;
+  const int nmax = longest_prefix<W>(__ballot(act));
+  double    pop  = em_score;
+  uint32_t  pm   = 1u << sl;
   {
     uint32_t pred = static_cast<uint32_t>(sl);
     uint32_t rev  = __builtin_bitreverse32(mycm); // bit k of mycm -> bit 31 - k
-    const uint32_t base4 = static_cast<uint32_t>(gbase) * 4u; // ds_bpermute takes a byte address: lane * 4
-    for (int k = 0; k + 1 < nmax; ++k) {
-      // population[k] of this lane's group: one address addition per step (__shfl adds, masks and shifts for every call)
-      const int       src = static_cast<int>(base4 + static_cast<uint32_t>(k) * 4u);
-      const long long pb  = __double_as_longlong(pop);
-      const uint32_t  plo = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src, static_cast<int>(static_cast<uint32_t>(pb))));
-      const uint32_t  phi = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src, static_cast<int>(static_cast<uint32_t>(pb >> 32))));
-      const double    k_pop = __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(phi) << 32) | plo));
-      const double    cand  = k_pop + em_score; // :189
+    // cand = population[k].score + this lane's own (:189)
+    auto     dp_step = [&](double cand, int k) __attribute__((always_inline)) {
       // (as in k_chain: bit test and shift are one add with carry-out, the three conditional moves two moves under EXEC)
       unsigned long long comp, saved;
       asm volatile("v_add_co_u32 %0, %1, %0, %0" : "+v"(rev), "=s"(comp));
@@ -2558,13 +2602,30 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
                    : [pop] "+v"(pop), [pred] "+v"(pred), [sv] "=&s"(saved)
                    : [m] "s"(upd), [cand] "v"(cand), [k] "s"(k)
                    : "scc");
-    }
+    };
+    // population[k] of this lane's group reaches the group without LDS (group_bcast_f64).  Step k + 1 reads the score
+    // step k wrote, so a ds_bpermute put an LDS round trip on the chain of every step.  The broadcast's source lane is an
+    // immediate, so the loop is unrolled.
+    unroll_while(
+        [&](auto kc) __attribute__((always_inline)) {
+          constexpr int k = decltype(kc)::value;
+          if (k + 1 >= nmax) return false;
+          dp_step(group_bcast_f64<W, k>(pop) + em_score, k);
+          return true;
+        },
+        std::make_integer_sequence<int, W - 1>{});
     uint32_t ptr = pred;
     for (int span = 1; span < nmax; span <<= 1) {
-      const uint32_t o  = __shfl(pm, gbase + static_cast<int>(ptr));
-      const uint32_t p2 = __shfl(ptr, gbase + static_cast<int>(ptr));
-      pm |= o;
-      ptr = p2;
+      if constexpr (W == 32) {
+        const uint32_t o  = __shfl(pm, gbase + static_cast<int>(ptr));
+        const uint32_t p2 = __shfl(ptr, gbase + static_cast<int>(ptr));
+        pm |= o;
+        ptr = p2;
+      } else { // a path mask has W <= 16 bits: mask and pointer travel in one word
+        const uint32_t o = __shfl(pm | (ptr << 16), gbase + static_cast<int>(ptr));
+        pm |= o & 0xffffu;
+        ptr = o >> 16;
+      }
     }
   }
 
@@ -2688,8 +2749,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W == 32 ? 7
 // the next nb16 the 16-wide one, the rest the 8-wide one -- the longest-lived first.  (One kernel = one register budget for the three bodies.)
 // Wavefronts per SIMD: 7 since the sub-wavefront body parks what only its last lines need -- the four numbers of the overhangs,
 // the anchor id -- in LDS (9 KB a workgroup: seven workgroups still fit a CU) instead of nine registers across the sweep and the
-// DP: 71 registers, six spilled outside every loop.  Six wavefronts (73 registers, none spilled) are 20 us slower, eight spill
-// inside the loops (profiles/r5_08/README.md).
+// DP: 71 registers, none spilled since the chaining DP broadcasts without LDS (six spilled before).  Six wavefronts are 20 us
+// slower (profiles/r5_08/README.md); eight do not fit 64 registers, and the compiler then falls back to four.
 #ifndef MSGPU_SUB_WAVES
 #define MSGPU_SUB_WAVES 7
 #endif
