@@ -1832,10 +1832,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   //       (overlap on one read, gap on the other) need d1 + d2 = |g1 - g2| + 2 <= wiggle (:133-138); and
   //       g1 - g2 = a(l) - b(k) with a = c1lo -+ c2lo/c2hi, b = c1hi -+ c2hi/c2lo, so max a - min b and
   //       max b - min a bound every pair;
-  // then checkCompatibility is true for ALL pairs, and with positive scores the DP of :185-199 takes k = l-1 at every
-  // l: population[l] = population[l-1] + score(l), path = all anchors up to l.  The bound is checked in integers with
-  // a margin of 3 (> every rounding error of the reference's fp64 expressions), so a "clean" verdict is exact; any
-  // edge that is not provably clean takes the full pair sweep below.
+  // then checkCompatibility is true for ALL pairs.  The bound is checked in integers with a margin of 3 (> every rounding
+  // error of the reference's fp64 expressions), so a "clean" verdict on the pairs is exact; any edge that is not provably
+  // clean takes the full pair sweep below.  The DP still runs on a clean edge: with every pair compatible it usually
+  // takes k = l-1, but not where an fp64 sum absorbs a small score (population[l-1] + s == population[l-2] + s: the
+  // strict > of :190 keeps the first k), so "path = all anchors up to l" is no shortcut.
   bool clean = false;
   if ((m_plus == 0 || m_minus == 0) && n >= 2 && a.fast_path) {
     const bool      plus = m_minus == 0;
@@ -1944,9 +1945,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       if (DIR == 2) cl &= valid;
       // :133-138 in one comparison: a pair whose orientations are equal needs |d1 - d2| <= wiggle (or the 15 % rule), a
       // mixed pair d1 + d2 <= wiggle -- so the second difference is negated where the pair is not mixed (exact: a - b is
-      // a + (-b) bit for bit) and ONE sum serves both: |d1 +- d2| <= wiggle (d1 + d2 >= 2 is its own magnitude).  Three
-      // scalar instructions and a compare less per step than testing both and choosing by mask: scalar and vector issue bound
-      // this loop about equally.
+      // a + (-b) bit for bit) and ONE sum serves both: |d1 +- d2| <= wiggle.  In the well-formed instance d = |t| + 1, so
+      // d1 + d2 >= 2 is its own magnitude: three scalar instructions and a compare less per step than testing both and
+      // choosing by mask (scalar and vector issue bound this loop about equally).  In the general one a difference can be
+      // negative (a reversed or empty range) and the mixed pairs test the signed sum, as the reference does.
       double val = d1 - d2;
       {
         M saved; // (the sum for the mixed pairs, written over the difference under their mask as EXEC: one vector instruction)
@@ -1957,8 +1959,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                      : [m] "s"(mixed), [x] "v"(d1), [y] "v"(d2)
                      : "scc");
       }
-      const M pass = __ballot(fabs(val) <= wiggle);
-      M            ok   = cl & pass;
+      M pass = __ballot(fabs(val) <= wiggle);
+      if (!WFT::value) pass = (pass & ~mixed) | (__ballot(val <= wiggle) & mixed);
+      M ok = cl & pass;
       // the fp64 division of :136 only where the first test failed (rare for true overlaps): std::max(d1, d2) -
       // std::min(d1, d2) = |d1 - d2| bit for bit (a - b and b - a round to the same magnitude); the maximum itself is only
       // needed by the division
@@ -2010,9 +2013,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   __builtin_amdgcn_wave_barrier();
   // bit k of mycm: checkCompatibility(k, lane) for k < lane of the same direction = pair lane (lane - 1) / 2 + k: the row
   // starts at bit b of word w and may run on into word w + 1 (bits past the row, and words past the last step, are
-  // masked off: they may hold anything)
+  // masked off: they may hold anything).  A clean edge has them all.
   uint64_t mycm = 0;
-  if (act && lane > 0 && P != 0) {
+  if (clean) {
+    mycm = act ? (1ull << lane) - 1ull : 0ull;
+  } else if (act && lane > 0 && P != 0) {
     const int      pr = lane * (lane - 1) / 2, w = pr >> 6, b = pr & 63;
     const uint64_t lo = cm[w] >> b, hi = (cm[w + 1] << 1) << (63 - b);
     mycm              = (lo | hi) & ((1ull << lane) - 1ull);
@@ -2021,15 +2026,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // ---- chaining DP (mpp.cpp:181-199), both directions at once: they never share a compatible pair -----------------
   double   pop = em_score;      // population[l].score
   uint64_t pm  = 1ull << lane;  // path of population[l] incl. l itself (self index appended at :203)
-  if (clean) {
-    // every pair compatible, scores positive: population[l] = population[l-1] + score(l), summed in the reference's
-    // left-to-right order; path(l) = {0..l}
-    for (int l = 1; l < static_cast<int>(n); ++l) {
-      const double prev = rl_f64(pop, l - 1);
-      if (lane == l) pop = prev + em_score;
-    }
-    pm = lane < 63 ? ((2ull << lane) - 1) : ~0ull;
-  } else {
+  {
     // The loop carries only the score and the predecessor (9 vector instructions per step instead of 15 with the
     // 64-bit path mask): "k compatible with me" is the sign bit of the bit-reversed mask, shifted left once per step.
     uint32_t pred = static_cast<uint32_t>(lane);
@@ -2578,8 +2575,8 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   else sweep_dir(std::false_type{});
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  // bit k: checkCompatibility(k, sl) for k < sl; a clean edge has them all (and then the DP below adds the scores up
-  // left to right, exactly the sum k_chain's shortcut forms)
+  // bit k: checkCompatibility(k, sl) for k < sl; a clean edge has them all (and the DP below still decides its paths:
+  // an fp64 tie between two predecessors goes to the first, see k_chain)
   const uint32_t mycm = clean ? (act ? (1u << sl) - 1u : 0u) : cm[lane];
 
   // ---- chaining DP (mpp.cpp:181-199) ---------------------------------------------------------------------------------
