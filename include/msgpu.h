@@ -313,6 +313,13 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *ctx);
 
 int msgpu_get_counts(msgpu_ctx *ctx, msgpu_counts *out);
 int msgpu_get_timings(msgpu_ctx *ctx, msgpu_timings *out);
+/* The chain stage's banded pair sweep: edges of more than msgpu_chain_band_width() + 1 EdgeMatches in
+ * a kernel that has the band are swept over the pairs (k, l), l - B <= k < l, first, and over all pairs again only when the
+ * band's result is not provably the full one.  n_banded: edges of the context's LAST chaining pass that started on the band;
+ * n_fallback: those of them that were done again.  Both 0 under MSGPU_NO_BAND=1 / MSGPU_NO_FASTPATH=1.  Read from the device
+ * on demand (synchronises the context's stream); not part of msgpu_counts. */
+int msgpu_get_chain_band_counts(msgpu_ctx *ctx, uint64_t *n_banded, uint64_t *n_fallback);
+int msgpu_chain_band_width(void); /* B, a build-time constant (MSGPU_CHAIN_BAND) */
 /* The stage boundaries (index / candidates / chain / compact) are marked with HIP events on the context's stream; every
  * marker costs a few microseconds of command-processor time.  on = 0 drops them: msgpu_get_timings then reports only
  * chain_kernel_ms (the two events around the chain kernels stay) and zeros for the stages.  Default: on. */

@@ -270,12 +270,14 @@ struct msgpu_ctx {
   hipEvent_t  ev_side[2]  = {nullptr, nullptr}, ev_side2 = nullptr;
   uint64_t    n_big_edges = 0, n_big_ems = 0;
   bool   fast_path = true;
+  bool   chain_band = true; // the banded pair sweep of k_chain; MSGPU_NO_BAND=1 (or MSGPU_NO_FASTPATH=1) switches it off
   bool   sub_wave  = true; // short edges share a wavefront (k_chain_sub); MSGPU_NO_SUBWAVE=1 sends them all to k_chain
   bool   use_fork  = true; // the candidate classes side by side (MSGPU_NO_FORK: one after the other)
   bool   use_prologue = true; // the candidate stage's opening inside the index build (MSGPU_NO_PROLOGUE: never)
   bool   chain_serial = false; // MSGPU_CHAIN_SERIAL: the chain stage's classes one after the other, a launch each
   uint32_t n_cls[4] = {0, 0, 0, 0}; // edges of 9..16, 17..32, 33..64 and <= 8 EdgeMatches
   uint64_t n_edges_fast = 0;
+  uint64_t chain_E = 0; // edges of the last chaining pass (where its band counts lie in chain_chunks)
   DevBuf ems, order_scr, ids_scr, edge_norders, edge_nids, orders, ids, big_list, cls_list, big_elems,
       big_paths;
   DevBuf g_deg, g_off, g_adj, g_cand, g_sane, g_out; // findContractionEdges
@@ -834,6 +836,8 @@ int msgpu_create(int device, const msgpu_params *params, msgpu_ctx **out) {
   {
     const char *nf = getenv("MSGPU_NO_FASTPATH"); // test hook: force the full pair sweep on every edge
     c->fast_path   = !(nf && nf[0] == '1');
+    const char *nb = getenv("MSGPU_NO_BAND"); // test hook / way out: no banded pair sweep (the shortcut stays)
+    c->chain_band  = c->fast_path && !(nb && nb[0] == '1');
     const char *ns = getenv("MSGPU_NO_SUBWAVE"); // test hook: one edge per wavefront whatever its size
     c->sub_wave    = !(ns && ns[0] == '1');
     const char *nw = getenv("MSGPU_NO_WIRE_COPY");
@@ -1291,7 +1295,7 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   a.edge_nids    = c->edge_nids.as<uint32_t>();
   a.err          = scalar<uint32_t>(c, SC_ERR);
   if (!c->pair_tab.p) {
-    ENSURE(c, pair_tab, 4 * PAIR_TAB_STRIDE * sizeof(uint32_t) + PAIR_TAB_STRIDE * sizeof(uint2) + 3 * PAIR_TAB_STRIDE * 8);
+    ENSURE(c, pair_tab, PAIR_TAB_WORDS * sizeof(uint32_t));
     launch_fill_pair_tab(st, c->pair_tab.as<uint32_t>());
   }
   a.pair_tab     = c->pair_tab.as<uint32_t>();
@@ -1301,7 +1305,8 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
     HIPCHK(c, hipMemsetAsync(c->chain_chunks.p, 0, chunk_words(E) * 8, st));
   c->chain_zeroed = false;
   a.chunk_sums   = c->chain_chunks.as<unsigned long long>();
-  a.fast_path    = c->fast_path ? 1 : 0;
+  a.fast_path    = (c->fast_path ? CHAIN_FAST_SHORTCUT : 0) | (c->chain_band ? CHAIN_FAST_BAND : 0);
+  c->chain_E     = E;
   // The shortcut compares differences of two int32 bounds (|x| < 2^33) with wiggle - 3 in integers.  Saturating at 2^40
   // keeps that verdict exact for every wiggle_room and keeps the conversion defined where a device-side
   // (long long)(double)wiggle would not be (wiggle_room >= 2^63: the reference's reading of a negative argument).
@@ -1442,6 +1447,25 @@ int msgpu_get_counts(msgpu_ctx *c, msgpu_counts *out) {
   out->n_edges_fastpath = c->state >= ST_CHAINED ? c->n_edges_fast : 0;
   out->n_lost_publications = c->lost_publications;
   out->index_path          = c->index_path;
+  return MSGPU_OK;
+}
+
+int msgpu_chain_band_width(void) { return MSGPU_CHAIN_BAND; }
+
+// The chain kernels leave the banded edges in bits 16..31 of every chunk sum and the fallbacks in the spare chunk behind the
+// last one (chunk_add, band_fallback_add); nothing on the hot path reads them, this call copies the words on demand.
+int msgpu_get_chain_band_counts(msgpu_ctx *c, uint64_t *n_banded, uint64_t *n_fallback) {
+  if (!c || !n_banded || !n_fallback) return MSGPU_E_ARG;
+  *n_banded = *n_fallback = 0;
+  if (c->state < ST_CHAINED || !c->chain_chunks.p) return MSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n_chunks = static_cast<size_t>((c->chain_E + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
+  const size_t fb_word  = 2 * static_cast<size_t>(c->chain_E / COMPACT_CHUNK + 1);
+  std::vector<unsigned long long> w(fb_word + 1);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(w.data(), c->chain_chunks.p, w.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < n_chunks; ++k) *n_banded += (w[2 * k] >> 16) & 0xffffull;
+  *n_fallback = w[fb_word];
   return MSGPU_OK;
 }
 

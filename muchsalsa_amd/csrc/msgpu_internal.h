@@ -102,8 +102,8 @@ struct ChainArgs {
   const uint32_t  *pair_tab; // four tables (sweep width 64, 32, 16, 8) of PAIR_TAB_STRIDE entries: k | l << 8 | run << 16
   const uint32_t  *pair_tab64; // the width-64 table with every field k_chain's sweep needs ready to use (k_fill_pair_tab)
   const uint32_t  *pair_tab_sub; // the width-32 / 16 / 8 tables, 8 bytes per pair, in the form k_chain_sub's sweep consumes
-  unsigned long long *chunk_sums; // per chunk of COMPACT_CHUNK edges: {shortcut edges | orders << 32, ids} (see chunk_add)
-  int              fast_path; // 0 disables the shortcut (every edge takes the full pair sweep)
+  unsigned long long *chunk_sums; // per chunk of COMPACT_CHUNK edges: {shortcut edges | banded edges << 16 | orders << 32, ids} (see chunk_add); band fallbacks in the spare chunk behind the last
+  int              fast_path; // CHAIN_FAST_* bits; 0: every edge takes the full pair sweep
   long long        fast_margin; // the shortcut's integer bound: min(wiggle_room, 2^40) - 3 (host-computed, see launch)
   double           wiggle, ratio_pct, alt_frac;
   uint32_t         out_edge_base; // added to EdgeMatch::edge_idx: position of this batch's first edge in the job's table
@@ -273,6 +273,19 @@ void launch_candidates_big(hipStream_t st, const CandArgs &a, const uint32_t *li
                            uint32_t *big_t, uint32_t *big_r2s, uint32_t *big_pfx);
 void launch_emit_edges(hipStream_t st, const EmitArgs &a, bool reduce); // reduce: k_cand_reduce in front (a repeat after a reallocation needs none)
 constexpr uint32_t PAIR_TAB_STRIDE = 2016 + 128; // pairs k < l < 64 + padding read by lanes past the last pair
+// Band width of the chain kernels' banded pair sweep (k_chain): pairs (k, l) with l - B <= k < l.  0 < B < 63.
+#ifndef MSGPU_CHAIN_BAND
+#define MSGPU_CHAIN_BAND 12
+#endif
+static_assert(MSGPU_CHAIN_BAND >= 1 && MSGPU_CHAIN_BAND <= 62, "band width");
+// pairs of the band of an edge of n > B + 1 rows (rows 1 .. B whole, B pairs in each of the n - 1 - B rows behind them)
+constexpr int chain_band_pairs(int n) { return MSGPU_CHAIN_BAND * (MSGPU_CHAIN_BAND + 1) / 2 + (n - 1 - MSGPU_CHAIN_BAND) * MSGPU_CHAIN_BAND; }
+static_assert(chain_band_pairs(64) <= 2016, "the band table fits the stride of the others");
+// words of the pair tables: four of 4 bytes per pair, tab64 and the three sub-wavefront tables of 8, k_chain's band table of 8
+constexpr uint32_t PAIR_TAB_BAND64_OFF = 4 * PAIR_TAB_STRIDE + 2 * PAIR_TAB_STRIDE + 3 * 2 * PAIR_TAB_STRIDE;
+constexpr uint32_t PAIR_TAB_WORDS      = PAIR_TAB_BAND64_OFF + 2 * PAIR_TAB_STRIDE;
+// ChainArgs::fast_path: bit 0 the all-pairs-compatible shortcut, bit 1 the banded sweep
+constexpr int CHAIN_FAST_SHORTCUT = 1, CHAIN_FAST_BAND = 2;
 void launch_fill_pair_tab(hipStream_t st, uint32_t *tab);
 void launch_chain(hipStream_t st, const ChainArgs &a, const uint32_t *list, uint32_t n_list);
 void launch_chain_sub(hipStream_t st, const ChainArgs &a, int width, const uint32_t *list, uint32_t n_list);

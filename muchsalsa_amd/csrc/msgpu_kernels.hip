@@ -1519,11 +1519,18 @@ void launch_emit_edges(hipStream_t st, const EmitArgs &a, bool reduce) {
 // took it) to the sums of its CHUNK of COMPACT_CHUNK consecutive edges -- two fire-and-forget atomics per edge on ~10^3
 // counters (1 M edges: nothing beside the kernels' own work) -- and k_compact takes a workgroup per chunk: the chunk's base is
 // the sum of the chunks before it (a few hundred words, summed by every workgroup), the prefix inside the chunk a block scan.
-//   chunk_sums[2 c]     += shortcut | orders << 32        chunk_sums[2 c + 1] += ids
-__device__ __forceinline__ void chunk_add(unsigned long long *chunk_sums, uint64_t e, bool clean, uint32_t n_orders, uint32_t n_ids) {
+//   chunk_sums[2 c]     += shortcut | banded << 16 | orders << 32        chunk_sums[2 c + 1] += ids
+// (shortcut: edges proven all-pairs-compatible; banded: edges whose sweep started on the band, see k_chain -- at most COMPACT_CHUNK
+// of either in a chunk, so 16 bits each.)  The edges whose band was rejected are counted in the first word of the spare chunk
+// behind the last one (band_fallback_add), read by the host on demand like the banded counts.
+__device__ __forceinline__ void chunk_add(unsigned long long *chunk_sums, uint64_t e, bool clean, uint32_t n_orders, uint32_t n_ids, bool banded = false) {
+  static_assert(COMPACT_CHUNK < (1u << 16), "two 16-bit edge counts in the low half of a chunk sum");
   unsigned long long *c = chunk_sums + 2 * (e / COMPACT_CHUNK);
-  __hip_atomic_fetch_add(c, (clean ? 1ull : 0ull) | (static_cast<unsigned long long>(n_orders) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_add(c, (clean ? 1ull : 0ull) | (banded ? 1ull << 16 : 0ull) | (static_cast<unsigned long long>(n_orders) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_fetch_add(c + 1, static_cast<unsigned long long>(n_ids), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void band_fallback_add(unsigned long long *chunk_sums, uint64_t n_edges) {
+  __hip_atomic_fetch_add(chunk_sums + 2 * (n_edges / COMPACT_CHUNK + 1), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 struct PathRec {
@@ -1838,7 +1845,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // takes k = l-1, but not where an fp64 sum absorbs a small score (population[l-1] + s == population[l-2] + s: the
   // strict > of :190 keeps the first k), so "path = all anchors up to l" is no shortcut.
   bool clean = false;
-  if ((m_plus == 0 || m_minus == 0) && n >= 2 && a.fast_path) {
+  if ((m_plus == 0 || m_minus == 0) && n >= 2 && (a.fast_path & CHAIN_FAST_SHORTCUT)) {
     const bool      plus = m_minus == 0;
     const ChainElem Pv   = el[lane > 0 ? lane - 1 : 0];
     bool            good = true;
@@ -1868,7 +1875,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
   // ---- checkCompatibility (mpp.cpp:38-142) for every pair k < l of one direction, all 64 lanes busy ---------------
   // pair p = l(l-1)/2 + k, row-major over l; a lane handles p = it*64 + lane
-  const int P = __builtin_amdgcn_readfirstlane(clean ? 0 : static_cast<int>(n * (n - 1) / 2)); // scalar loop control
+  // every element well formed (see nano_check) and v1's raw ranges in list order: the lean pair test; else the general one
+  bool wf_lane = true;
+  if (act) {
+    const int prev_rlo1 = el[lane > 0 ? lane - 1 : 0].rlo1;
+    wf_lane = (x.clo1 <= x.chi1) & (x.clo2 <= x.chi2) & (x.rlo1 <= x.rhi1) & (lane == 0 || prev_rlo1 <= x.rlo1);
+  }
+  const bool wf = __ballot(!wf_lane) == 0; // (decided in front of the loop below: inside it the element would wait in ten registers for a second pass)
+  // THE BAND.  The compatibility matrix has one consumer, the DP below, and on a true overlap the DP takes a predecessor a few rows
+  // back.  So the sweep and the DP first run over the pairs (k, l) with l - B <= k < l only (B = MSGPU_CHAIN_BAND), and the result is
+  // kept if it is provably the full one: with pmax[j] = max(pop[0..j]), row l > B is accepted when
+  //     pmax[l - B - 1] + s[l] < pop[l]          (strictly; a NaN rejects)
+  // By induction the rows before l hold their true scores; fp64 addition is monotone, so the left side bounds pop[k] + s[l] for every k
+  // outside the band, compatible or not; the reference visits k in increasing order with a strict > (mpp.cpp:189-197), so those k come
+  // first and leave a running value below pop[l], and the final value and its predecessor (the first in-band k that reaches it) are
+  // what the banded DP took.  A tie with an out-of-band k must reject (the reference keeps the smaller k): hence the strict <.  The
+  // prefix maximum runs over the lanes of both directions: only more conservative.  If any row rejects, the edge is done again with
+  // the full table -- ONE loop executed at most twice (a second copy of the six sweep instances would not fit the instruction cache).
+  bool     band = !clean && (a.fast_path & CHAIN_FAST_BAND) && n > MSGPU_CHAIN_BAND + 1;
+  const bool banded = band;
+  double   pop;
+  uint64_t pm;
+  for (;;) {
+  const int P = __builtin_amdgcn_readfirstlane(clean ? 0 : band ? chain_band_pairs(static_cast<int>(n)) : static_cast<int>(n * (n - 1) / 2)); // scalar loop control
   // Pair p: k | l << 8 | run << 16 | (64 - run - k) << 24 from a table that is the same for every edge (run = length of
   // the stretch of row l that starts at this lane of a 64-wide step, 0 if none starts here).  The table is padded with
   // (0, 1, 0) beyond the last pair and every (k, l) in it is < 64, so lanes past P read without a clamp or a branch and
@@ -1877,7 +1906,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // the pair table through a buffer descriptor: scalar offset (the step) + constant lane offset, no vector address
   // arithmetic in the loop
   const __amdgpu_buffer_rsrc_t tab_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.pair_tab64), 0, PAIR_TAB_STRIDE * 8, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.pair_tab64) + (band ? PAIR_TAB_BAND64_OFF - 4 * PAIR_TAB_STRIDE : 0u), 0, PAIR_TAB_STRIDE * 8, 0x00020000);
   const uint32_t tab_lane = static_cast<uint32_t>(lane) * 8u;
   typedef uint32_t pair_t __attribute__((ext_vector_type(2))); // {LDS offset of element k, of element l}
   auto           load_pairs = [&](int p0) __attribute__((always_inline)) -> pair_t {
@@ -1887,13 +1916,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // re-read (v_readlane) in every step.  The one constant the common path compares with lives in a vector register.
   double wiggle = a.wiggle;
   asm volatile("" : "+v"(wiggle));
-  // every element well formed (see nano_check) and v1's raw ranges in list order: the lean pair test; else the general one
-  bool wf_lane = true;
-  if (act) {
-    const int prev_rlo1 = el[lane > 0 ? lane - 1 : 0].rlo1;
-    wf_lane = (x.clo1 <= x.chi1) & (x.clo2 <= x.chi2) & (x.rlo1 <= x.rhi1) & (lane == 0 || prev_rlo1 <= x.rlo1);
-  }
-  const bool wf = __ballot(!wf_lane) == 0;
   // (The lean raw test for the SECOND vertex too -- its raw ranges in list order on forward edges, in reverse order on reverse
   // ones, nano_check<.., 1 / 2> -- was built and measured in round 5: on BASELINE.json's reads the +-15 bp jitter of the
   // alignment coordinates puts some neighbouring anchors of nearly every edge out of order on the second read, the instances
@@ -2014,22 +2036,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // bit k of mycm: checkCompatibility(k, lane) for k < lane of the same direction = pair lane (lane - 1) / 2 + k: the row
   // starts at bit b of word w and may run on into word w + 1 (bits past the row, and words past the last step, are
   // masked off: they may hold anything).  A clean edge has them all.
+  // (The lane number behind an empty asm from here to the end of the loop: what is computed from it -- the row's place in the verdict
+  // words, the masks of the scan -- is then computed here, as it was before there was a loop, instead of once in front of the loop
+  // and held in registers across the sweep, which has none to spare.)
+  int ln = lane;
+  asm volatile("" : "+v"(ln));
   uint64_t mycm = 0;
   if (clean) {
-    mycm = act ? (1ull << lane) - 1ull : 0ull;
-  } else if (act && lane > 0 && P != 0) {
-    const int      pr = lane * (lane - 1) / 2, w = pr >> 6, b = pr & 63;
+    mycm = act ? (1ull << ln) - 1ull : 0ull;
+  } else if (act && ln > 0 && P != 0) {
+    // (band: row l starts at pair l (l - 1) / 2 for l <= B and B (B - 1) / 2 + (l - B) B behind that, is min(l, B) bits wide, and
+    // its bits belong at positions l - width .. l - 1)
+    constexpr int  B  = MSGPU_CHAIN_BAND;
+    const bool     tri = !band || ln <= B;
+    const int      pr = tri ? ln * (ln - 1) / 2 : B * (B - 1) / 2 + (ln - B) * B, w = pr >> 6, b = pr & 63;
+    const int      wd = tri ? ln : B;
     const uint64_t lo = cm[w] >> b, hi = (cm[w + 1] << 1) << (63 - b);
-    mycm              = (lo | hi) & ((1ull << lane) - 1ull);
+    mycm              = ((lo | hi) & ((1ull << wd) - 1ull)) << (ln - wd);
   }
 
   // ---- chaining DP (mpp.cpp:181-199), both directions at once: they never share a compatible pair -----------------
-  double   pop = em_score;      // population[l].score
-  uint64_t pm  = 1ull << lane;  // path of population[l] incl. l itself (self index appended at :203)
+  pop = em_score;      // population[l].score
+  pm  = 1ull << ln;  // path of population[l] incl. l itself (self index appended at :203)
   {
     // The loop carries only the score and the predecessor (9 vector instructions per step instead of 15 with the
     // 64-bit path mask): "k compatible with me" is the sign bit of the bit-reversed mask, shifted left once per step.
-    uint32_t pred = static_cast<uint32_t>(lane);
+    uint32_t pred = static_cast<uint32_t>(ln);
     // bit k of mycm -> the sign bit after k shifts, in two 32-bit halves (k < 32, k >= 32): 32-bit compare and shift
     uint32_t rev = __builtin_bitreverse32(static_cast<uint32_t>(mycm));
     const int n1 = static_cast<int>(n) - 1, nlo = n1 < 32 ? n1 : 32;
@@ -2064,6 +2096,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       pm |= (static_cast<uint64_t>(hi) << 32) | lo;
       ptr = p2;
     }
+  }
+  if (!band) break;
+  {
+    // the band rule: inclusive prefix maximum of pop over the lanes (the lanes past the edge hold 0 and lie behind every row; a NaN
+    // score is skipped by the maximum and never updates a later row either), read from lane l - B - 1
+    double pmax = pop;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const double up = __shfl_up(pmax, d);
+      if (ln >= d) pmax = __builtin_fmax(pmax, up);
+    }
+    const double out = __shfl(pmax, ln > MSGPU_CHAIN_BAND ? ln - MSGPU_CHAIN_BAND - 1 : 0);
+    const bool   rej = ln > MSGPU_CHAIN_BAND && ln < static_cast<int>(n) && !(out + em_score < pop);
+    if (__ballot(rej) == 0) break;
+  }
+  band = false; // some row may owe its score to a predecessor outside the band: the full sweep decides
+  if (lane == 0) band_fallback_add(a.chunk_sums, a.n_edges);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
   }
 
   // src/main.cpp:341-353: split by EdgeMatch direction, minus then plus
@@ -2179,7 +2230,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     a.edge_norders[e] = n_orders;
     a.edge_nids[e]    = n_ids;
     a.edges[e].shadow = shadow ? 1 : 0;
-    chunk_add(a.chunk_sums, e, clean, n_orders, n_ids);
+    chunk_add(a.chunk_sums, e, clean, n_orders, n_ids, banded);
   }
 }
 
@@ -2431,7 +2482,7 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   // ---- all-pairs-compatible shortcut (see k_chain) -------------------------------------------------------------------
   bool clean = false;
   {
-    const bool      try_clean = (m_plus == 0 || m_minus == 0) && n >= 2 && a.fast_path;
+    const bool      try_clean = (m_plus == 0 || m_minus == 0) && n >= 2 && (a.fast_path & CHAIN_FAST_SHORTCUT);
     const bool      plus      = m_minus == 0;
     const ChainElem Pv        = el[sl > 0 ? lane - 1 : lane];
     bool            good      = true;
@@ -3250,10 +3301,34 @@ __device__ __forceinline__ void tabsub_entry(uint32_t *tab, int t, int p, int k,
   e[0]        = static_cast<uint32_t>(k * 48) | (static_cast<uint32_t>(l * 48) << 16);
   e[1]        = static_cast<uint32_t>(k) | (static_cast<uint32_t>(run) << 8) | (static_cast<uint32_t>(l * 4) << 16);
 }
+// The BAND table of k_chain (see the band rule there): the pairs (k, l) with l - B <= k < l only, row-major over l, in tab64's form.
+// Rows l <= B are whole (the first B (B + 1) / 2 entries are tab64's own), every later row has B entries; an edge of n > B + 1 rows
+// uses the first chain_band_pairs(n) of them.  Padded with (0, 1) beyond row 63.
+__device__ __forceinline__ void band64_entry(uint32_t *tab, int p) {
+  constexpr int B = MSGPU_CHAIN_BAND, TRI = B * (B + 1) / 2;
+  int k = 0, l = 1;
+  if (p < TRI) {
+    l = static_cast<int>((1.0f + __fsqrt_rn(1.0f + 8.0f * static_cast<float>(p))) * 0.5f);
+    if (l * (l - 1) / 2 > p) --l;
+    if ((l + 1) * l / 2 <= p) ++l;
+    k = p - l * (l - 1) / 2;
+  } else {
+    const int q = p - TRI;
+    l = B + 1 + q / B;
+    k = l - B + q % B;
+    if (l >= 64) {
+      k = 0;
+      l = 1;
+    }
+  }
+  tab[PAIR_TAB_BAND64_OFF + 2 * p]     = static_cast<uint32_t>(k * 48);
+  tab[PAIR_TAB_BAND64_OFF + 2 * p + 1] = static_cast<uint32_t>(l * 48);
+}
 __global__ __launch_bounds__(256) void k_fill_pair_tab(uint32_t *tab) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 4 * static_cast<int>(PAIR_TAB_STRIDE)) return;
   const int t = i / static_cast<int>(PAIR_TAB_STRIDE), p = i % static_cast<int>(PAIR_TAB_STRIDE), W = 64 >> t;
+  if (t == 0) band64_entry(tab, p);
   if (p >= 2016) {
     tab[i] = 1u << 8;
     if (t == 0) tab64_entry(tab, p, 0, 1, 0);
@@ -3288,7 +3363,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   unsigned long long t[5] = {0, 0, 0, 0, 0}; // orders, ids of the chunks before this one | orders, ids, shortcut edges of all chunks
   for (uint32_t c = threadIdx.x; c < a.n_chunks; c += 1024) {
     const unsigned long long w0 = a.chunk_sums[2 * c], w1 = a.chunk_sums[2 * c + 1];
-    const unsigned long long no = w0 >> 32, nf = w0 & 0xffffffffull;
+    const unsigned long long no = w0 >> 32, nf = w0 & 0xffffull; // (bits 16..31: the banded edges, read by the host on demand)
     if (c < chunk) {
       t[0] += no;
       t[1] += w1;

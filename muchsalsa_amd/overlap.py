@@ -237,6 +237,16 @@ class OverlapContext:
         self._check(self._L.msgpu_get_counts(self._h, C.byref(c)))
         return c
 
+    def chain_band_counts(self):
+        """(edges of the last chaining pass that started on the banded pair sweep, those of them done again with the full one)"""
+        nb, nf = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.msgpu_get_chain_band_counts(self._h, C.byref(nb), C.byref(nf)))
+        return int(nb.value), int(nf.value)
+
+    def chain_band_width(self):
+        """B of the banded pair sweep (a build-time constant of the library)"""
+        return int(self._L.msgpu_chain_band_width())
+
     def set_stage_events(self, on):
         """mark the stage boundaries with events (timings() per stage) or not (a few microseconds less per marker)"""
         self._check(self._L.msgpu_set_stage_events(self._h, 1 if on else 0))
