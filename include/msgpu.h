@@ -837,6 +837,101 @@ int         msgpu_uf_result_stats(const msgpu_uf_result *r, msgpu_uf_stats *out)
 const char *msgpu_uf_result_text(const msgpu_uf_result *r, uint64_t *len);
 void        msgpu_uf_result_free(msgpu_uf_result *r);
 
+/* ==== read scrubber: the pipeline's own step that cuts every long read into the stretches evidence covers ===============
+ * (pipeline/scrubber_bfs.py).  Input: the anchor -> read PAF, the reads, and a read-to-read PAF
+ * mapped once over all reads (the script maps every batch with minimap2; the stage uses the lines whose two reads are in
+ * the batch, in file order).  The rules:
+ *  1. anchor PAF, in line order: a line of one token is skipped, one of 2..8 fields is MSGPU_E_FORMAT; a line with
+ *     col3 - col2 < 500 is skipped; a read (column 5) is a node from its first surviving line on (ids in that order, length
+ *     = column 6 of that line); of several surviving lines of one (read, anchor) the first counts, with the read-side range
+ *     (col7, col8); a chunk is a maximal run of counting lines with one column 0; a counting line joins its read to every
+ *     read already in the chunk (an edge is added once) and a node's neighbours are ordered by when their edge was added;
+ *  2. batches: breadth-first from the smallest remaining name outside the subset (bytewise order), nodes in discovery order
+ *     until the subset holds subset_size nodes; a component that leaves it smaller merges into the next start; the centre of
+ *     a closed batch is every subset node without a remaining neighbour outside the subset;
+ *  3. read-to-read lines of a batch, in file order: skipped are lines of fewer than 6 fields, col0 == col5, a name that is
+ *     not a node, col3 - col2 < 500; a line folds (col2, col3, strand) into the entry of (col0, col5) and (col7, col8,
+ *     strand) into that of (col5, col0): the first line creates (S, E, D); a later (s, e, d) with d == D and (|S - e| < 500
+ *     or |s - E| < 500) makes it (min(s, S), max(e, E), D).  Entries persist from batch to batch;
+ *  4. per centre node: its entries' (S, E) and its anchor ranges sorted as pairs and merged left to right (a range joins
+ *     the last covered one when cs <= e and s <= ce); covered range i is the record ">{read}_{i}" with the bases
+ *     [max(cs, 200), min(ce, length - 200)], end inclusive, clipped to the record, in lines of 60.  The centre leaves the
+ *     graph.  Records come out batch after batch, inside a batch by node id. */
+typedef struct msgpu_scrub msgpu_scrub;           /* the two parsed PAFs (host)           */
+typedef struct msgpu_scrub_plan msgpu_scrub_plan; /* the batches of rule 2 (host)         */
+typedef struct msgpu_scrubctx msgpu_scrubctx;     /* a device context of the stage        */
+typedef struct msgpu_scrub_result msgpu_scrub_result;
+typedef struct msgpu_scrub_tables { /* views into a msgpu_scrub (valid while it lives)                                 */
+  uint64_t        n_anchor_lines, n_ava_lines; /* lines of the two files                                                */
+  uint64_t        n_hits, n_ava;               /* counting anchor lines; surviving read-to-read lines                   */
+  uint32_t        n_nodes, n_anchors, n_chunks, pad;
+  const int32_t  *node_length;                 /* per node: column 6 of its first surviving line                        */
+  const uint32_t *node_line;                   /* per node: that line (0-based)                                         */
+  const uint32_t *hit_node, *hit_anchor, *hit_line; /* per counting line, in line order                                 */
+  const int32_t  *hit_s, *hit_e;               /* columns 7, 8                                                          */
+  const uint32_t *chunk_first, *chunk_n;       /* per chunk: its counting lines [first, first + n)                      */
+  const uint32_t *ava_a, *ava_b, *ava_strand, *ava_line; /* per surviving line: nodes of columns 0 / 5, strand id (0 '+',
+                                                  1 '-', others from 2 in first-seen order), line (0-based)              */
+  const int32_t  *ava_sa, *ava_ea, *ava_sb, *ava_eb; /* columns 2, 3, 7, 8                                             */
+} msgpu_scrub_tables;
+/* mmap + one tokenising thread per chunk of each file, then one pass in line order (first-seen ids, first-hit test,
+ * chunks).  A line the script would stop on fails the parse with *err_line = its 1-based number and *err_file = 0 (anchor
+ * PAF) or 1 (read-to-read PAF): 2..8 fields where 9 are read (MSGPU_E_FORMAT), an empty column 0 of an anchor line
+ * (MSGPU_E_FORMAT), a column that is not a decimal integer of int32 range (MSGPU_E_NUMBER; columns 2, 3, 7, 8 without
+ * sign, column 6 with an optional '-'), a node whose length is below 200 (MSGPU_E_NUMBER: its slice would end at a
+ * negative index).  An anchor PAF without a node is MSGPU_E_FORMAT at line 1. */
+int         msgpu_scrub_parse(const char *anchors_path, const char *ava_path, msgpu_scrub **out, uint64_t *err_line,
+                              int *err_file);
+void        msgpu_scrub_free(msgpu_scrub *s);
+int         msgpu_scrub_get_tables(const msgpu_scrub *s, msgpu_scrub_tables *out);
+const char *msgpu_scrub_node_name(const msgpu_scrub *s, uint32_t id);
+uint32_t    msgpu_scrub_node_id(const msgpu_scrub *s, const char *name); /* 0xffffffff: not a node */
+int         msgpu_scrub_name_order(const msgpu_scrub *s, uint32_t *out); /* the node ids sorted by name (n_nodes entries) */
+/* Rule 2 on a graph in CSR form (row_off: n_nodes + 1 entries; a row's neighbours in insertion order) with by_name = the
+ * node ids sorted by name.  MSGPU_E_LAYOUT when a batch closes with an empty centre (the script would build it again for
+ * ever): *bad_node = the batch's first start.  Host only. */
+typedef struct msgpu_scrub_plan_tables {
+  uint32_t        n_batches, pad;
+  const uint64_t *subset_off, *centre_off; /* n_batches + 1 entries each                                              */
+  const uint32_t *subset;                  /* a batch's subset in the order its nodes were added                      */
+  const uint32_t *centre;                  /* a batch's centre by ascending node id                                   */
+  const uint32_t *start;                   /* per batch: its first start                                              */
+} msgpu_scrub_plan_tables;
+int  msgpu_scrub_plan_create(uint32_t n_nodes, const uint32_t *by_name, const uint64_t *row_off, const uint32_t *adj,
+                             uint32_t subset_size, msgpu_scrub_plan **out, uint32_t *bad_node);
+int  msgpu_scrub_plan_get(const msgpu_scrub_plan *p, msgpu_scrub_plan_tables *out);
+void msgpu_scrub_plan_free(msgpu_scrub_plan *p);
+
+/* device = HIP ordinal (MSGPU_E_NODEVICE without a GPU) */
+int         msgpu_scrub_create(int device, msgpu_scrubctx **out);
+void        msgpu_scrub_destroy(msgpu_scrubctx *ctx);
+const char *msgpu_scrub_last_error(const msgpu_scrubctx *ctx);
+uint64_t    msgpu_scrub_error_line(const msgpu_scrubctx *ctx); /* after MSGPU_E_IDS: 1-based anchor PAF line of the first node the reads file lacks */
+#define MSGPU_SCRUB_SUBSET 60000u /* the script's subset_size */
+typedef struct msgpu_scrub_stats {
+  uint64_t n_nodes, n_hits, n_pairs, n_edges, n_ava, n_batches, n_subset_total, n_intervals, n_records, bases,
+      text_bytes;
+  float load_ms;    /* host: reads parse + upload (wall)                                                              */
+  float graph_ms;   /* device: pairs, two sorts, CSR, its copy back (events, as fold / union / gather / format / copy) */
+  float batch_ms;   /* host: rule 2                                                                                   */
+  float fold_ms;    /* device: the sort of the directed entries and one launch pair per batch                         */
+  float union_ms;   /* device: intervals, segmented sort, count, scan, emit, the ranges' copy back                    */
+  float plan_ms;    /* host: records, headers, gather plan                                                            */
+  float gather_ms, format_ms, copy_ms;
+  float wall_ms;
+} msgpu_scrub_stats;
+/* The whole stage on the parsed PAFs: the reads are a FASTA when reads_path ends in "fa" or "fasta", else a FASTQ (first
+ * record of a name wins); the text of the output is kept in the result.  MSGPU_E_IDS when a node is missing from the reads
+ * (msgpu_scrub_error_line), MSGPU_E_LAYOUT for a batch with an empty centre (msgpu_scrub_last_error names its start read).
+ * Synchronous. */
+int         msgpu_scrub_run(msgpu_scrubctx *ctx, const msgpu_scrub *s, const char *reads_path, uint32_t subset_size,
+                            msgpu_scrub_result **out);
+int         msgpu_scrub_result_stats(const msgpu_scrub_result *r, msgpu_scrub_stats *out);
+const char *msgpu_scrub_result_text(const msgpu_scrub_result *r, uint64_t *len);
+/* the read graph the device built: row_off (n_nodes + 1 entries) and the neighbours in insertion order */
+int         msgpu_scrub_result_graph(const msgpu_scrub_result *r, const uint64_t **row_off, const uint32_t **adj);
+void        msgpu_scrub_result_free(msgpu_scrub_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

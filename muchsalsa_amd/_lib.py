@@ -126,6 +126,33 @@ class UfStats(C.Structure):  # msgpu_uf_stats
 UF_PACKED = 1
 
 
+class ScrubTables(C.Structure):  # msgpu_scrub_tables
+    _fields_ = ([(n, C.c_uint64) for n in ("n_anchor_lines", "n_ava_lines", "n_hits", "n_ava")] +
+                [(n, C.c_uint32) for n in ("n_nodes", "n_anchors", "n_chunks", "pad")] +
+                [("node_length", C.POINTER(C.c_int32)), ("node_line", C.POINTER(C.c_uint32))] +
+                [(n, C.POINTER(C.c_uint32)) for n in ("hit_node", "hit_anchor", "hit_line")] +
+                [(n, C.POINTER(C.c_int32)) for n in ("hit_s", "hit_e")] +
+                [(n, C.POINTER(C.c_uint32)) for n in ("chunk_first", "chunk_n", "ava_a", "ava_b", "ava_strand",
+                                                      "ava_line")] +
+                [(n, C.POINTER(C.c_int32)) for n in ("ava_sa", "ava_ea", "ava_sb", "ava_eb")])
+
+
+class ScrubPlanTables(C.Structure):  # msgpu_scrub_plan_tables
+    _fields_ = [("n_batches", C.c_uint32), ("pad", C.c_uint32), ("subset_off", C.POINTER(C.c_uint64)),
+                ("centre_off", C.POINTER(C.c_uint64)), ("subset", C.POINTER(C.c_uint32)),
+                ("centre", C.POINTER(C.c_uint32)), ("start", C.POINTER(C.c_uint32))]
+
+
+class ScrubStats(C.Structure):  # msgpu_scrub_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_nodes", "n_hits", "n_pairs", "n_edges", "n_ava", "n_batches",
+                                           "n_subset_total", "n_intervals", "n_records", "bases", "text_bytes")] +
+                [(n, C.c_float) for n in ("load_ms", "graph_ms", "batch_ms", "fold_ms", "union_ms", "plan_ms",
+                                          "gather_ms", "format_ms", "copy_ms", "wall_ms")])
+
+
+SCRUB_SUBSET = 60000
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -305,6 +332,27 @@ SYMBOLS = [
     ("msgpu_uf_result_stats", C.c_int, [C.c_void_p, C.POINTER(UfStats)]),
     ("msgpu_uf_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msgpu_uf_result_free", None, [C.c_void_p]),
+    ("msgpu_scrub_parse", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_int)]),
+    ("msgpu_scrub_free", None, [C.c_void_p]),
+    ("msgpu_scrub_get_tables", C.c_int, [C.c_void_p, C.POINTER(ScrubTables)]),
+    ("msgpu_scrub_node_name", C.c_char_p, [C.c_void_p, C.c_uint32]),
+    ("msgpu_scrub_node_id", C.c_uint32, [C.c_void_p, C.c_char_p]),
+    ("msgpu_scrub_name_order", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("msgpu_scrub_plan_create", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
+    ("msgpu_scrub_plan_get", C.c_int, [C.c_void_p, C.POINTER(ScrubPlanTables)]),
+    ("msgpu_scrub_plan_free", None, [C.c_void_p]),
+    ("msgpu_scrub_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_scrub_destroy", None, [C.c_void_p]),
+    ("msgpu_scrub_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_scrub_error_line", C.c_uint64, [C.c_void_p]),
+    ("msgpu_scrub_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("msgpu_scrub_result_stats", C.c_int, [C.c_void_p, C.POINTER(ScrubStats)]),
+    ("msgpu_scrub_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_scrub_result_graph", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)),
+                                           C.POINTER(C.POINTER(C.c_uint32))]),
+    ("msgpu_scrub_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

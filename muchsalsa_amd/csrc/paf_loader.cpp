@@ -975,3 +975,515 @@ uint32_t    msgpu_uf_unitig_id(const msgpu_uf *u, const char *name) {
 }
 
 } // extern "C"
+
+/* ---- the read scrubber's two PAFs and its batches (msgpu_scrub_parse, msgpu_scrub_plan_create; include/msgpu.h) --------
+ * Both files are cut into one chunk per host thread at line boundaries and tokenised on the threads (nine columns, Python's
+ * rstrip + split('\t')).  One pass over the anchor lines in line order then gives the nodes (first-seen ids), the first hit
+ * of every (read, anchor) and the chunks; the read-to-read lines are resolved against the finished node registry on the
+ * threads again.  A read-to-read line is judged in the script's order: names first (a line whose reads are not both nodes
+ * is in no batch), then the field count and the integers, then the span. */
+
+struct msgpu_scrub {
+  std::vector<int32_t>  node_length;
+  std::vector<uint32_t> node_line;
+  std::vector<uint32_t> hit_node, hit_anchor, hit_line;
+  std::vector<int32_t>  hit_s, hit_e;
+  std::vector<uint32_t> chunk_first, chunk_n;
+  std::vector<uint32_t> ava_a, ava_b, ava_strand, ava_line;
+  std::vector<int32_t>  ava_sa, ava_ea, ava_sb, ava_eb;
+  uint64_t              n_anchor_lines = 0, n_ava_lines = 0;
+  NameRegistry          nodes, anchors;
+};
+
+struct msgpu_scrub_plan {
+  std::vector<uint64_t> subset_off{0}, centre_off{0};
+  std::vector<uint32_t> subset, centre, start;
+};
+
+namespace {
+
+struct ScLine {
+  const char *a, *b, *strand; // columns 0, 5 and 4 in the file image
+  uint32_t    a_n, b_n, strand_n;
+  uint32_t    line;           // 0-based
+  uint64_t    a_h, b_h;       // anchor lines: the names' hashes (computed on the threads)
+  int32_t     c2, c3, c6, c7, c8;
+  uint32_t    ia, ib;         // read-to-read lines: the node ids of columns 0 and 5
+  int         status;         // MSGPU_OK, or what the line fails with once it is known to be read
+};
+
+struct ScChunk {
+  const char         *begin = nullptr, *end = nullptr;
+  size_t              first_line = 0, n_lines = 0;
+  std::vector<ScLine> lines;
+  int                 err = MSGPU_OK;
+  size_t              err_line = 0; // 0-based
+};
+
+struct ScFile {
+  const char *data = nullptr;
+  size_t      len  = 0;
+  ~ScFile() {
+    if (data) munmap(const_cast<char *>(data), len);
+  }
+  int map(const char *path) {
+    int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return MSGPU_E_IO;
+    struct stat st;
+    if (fstat(fd, &st) != 0) {
+      close(fd);
+      return MSGPU_E_IO;
+    }
+    len = static_cast<size_t>(st.st_size);
+    if (len) {
+      void *m = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m == MAP_FAILED) {
+        close(fd);
+        len = 0;
+        return MSGPU_E_IO;
+      }
+      data = static_cast<const char *>(m);
+    }
+    close(fd);
+    return MSGPU_OK;
+  }
+};
+
+// ava = false: the anchor PAF (a bad line ends the chunk); true: the read-to-read PAF (a bad line is kept with its status)
+void sc_tokenise(ScChunk &ch, bool ava) {
+  size_t li = ch.first_line;
+  for (const char *q = ch.begin; q < ch.end; ++li) {
+    const void *nlp = memchr(q, '\n', static_cast<size_t>(ch.end - q));
+    const char *ls = q, *le = nlp ? static_cast<const char *>(nlp) : ch.end;
+    q = nlp ? le + 1 : ch.end;
+    while (le > ls && uf_space(le[-1])) --le; // str.rstrip()
+    const char *tb[9], *te[9];
+    int         nt = 0;
+    for (const char *s = ls, *c = ls; nt < 9; ++c) // str.split('\t')
+      if (c == le || *c == '\t') {
+        tb[nt] = s;
+        te[nt] = c;
+        ++nt;
+        s = c + 1;
+        if (c == le) break;
+      }
+    if (nt <= 1) continue; // one token
+    if (ava && nt < 6) continue;
+    ScLine x{};
+    x.line   = static_cast<uint32_t>(li);
+    x.status = MSGPU_OK;
+    x.a      = tb[0];
+    x.a_n    = static_cast<uint32_t>(te[0] - tb[0]);
+    if (nt >= 6) {
+      x.b   = tb[5];
+      x.b_n = static_cast<uint32_t>(te[5] - tb[5]);
+    }
+    if (ava && x.a_n == x.b_n && memcmp(x.a, x.b, x.a_n) == 0) continue;
+    int64_t c2 = 0, c3 = 0, c6 = 0, c7 = 0, c8 = 0;
+    if (nt < 9 || (!ava && x.a_n == 0)) x.status = MSGPU_E_FORMAT;
+    else if (!uf_int(tb[2], te[2], false, c2) || !uf_int(tb[3], te[3], false, c3) || !uf_int(tb[7], te[7], false, c7) ||
+             !uf_int(tb[8], te[8], false, c8) || (!ava && !uf_int(tb[6], te[6], true, c6)))
+      x.status = MSGPU_E_NUMBER;
+    if (x.status != MSGPU_OK) {
+      if (!ava) {
+        ch.err      = x.status;
+        ch.err_line = li;
+        return;
+      }
+      ch.lines.push_back(x);
+      continue;
+    }
+    if (c3 - c2 < 500) continue;
+    x.strand   = tb[4];
+    x.strand_n = static_cast<uint32_t>(te[4] - tb[4]);
+    x.c2       = static_cast<int32_t>(c2);
+    x.c3       = static_cast<int32_t>(c3);
+    x.c6       = static_cast<int32_t>(c6);
+    x.c7       = static_cast<int32_t>(c7);
+    x.c8       = static_cast<int32_t>(c8);
+    if (!ava) {
+      x.a_h = name_hash(x.a, x.a_n);
+      x.b_h = name_hash(x.b, x.b_n);
+    }
+    ch.lines.push_back(x);
+  }
+}
+
+// the (node, anchor) pairs that have counted: open addressing over the packed pair + 1
+class PairSet {
+public:
+  PairSet() : m_slots(1024, 0) {}
+  bool insert(uint64_t key) { // true: new
+    if ((m_n + 1) * 2 > m_slots.size()) grow();
+    const uint64_t k = key + 1;
+    size_t         i = mix(k) & (m_slots.size() - 1);
+    while (m_slots[i]) {
+      if (m_slots[i] == k) return false;
+      i = (i + 1) & (m_slots.size() - 1);
+    }
+    m_slots[i] = k;
+    ++m_n;
+    return true;
+  }
+
+private:
+  static uint64_t mix(uint64_t x) {
+    x ^= x >> 31;
+    x *= 0x9fb21c651e98df25ull;
+    return x ^ (x >> 29);
+  }
+  void grow() {
+    std::vector<uint64_t> old(m_slots.size() * 2, 0);
+    old.swap(m_slots);
+    for (uint64_t k : old)
+      if (k) {
+        size_t i = mix(k) & (m_slots.size() - 1);
+        while (m_slots[i]) i = (i + 1) & (m_slots.size() - 1);
+        m_slots[i] = k;
+      }
+  }
+  std::vector<uint64_t> m_slots;
+  size_t                m_n = 0;
+};
+
+void sc_cut(const ScFile &f, unsigned nthr, std::vector<ScChunk> &chunks) {
+  chunks.assign(nthr, ScChunk());
+  const char *end = f.data + f.len, *cur = f.data;
+  for (unsigned t = 0; t < nthr; ++t) {
+    chunks[t].begin = cur;
+    const char *cut = (t + 1 == nthr) ? end : f.data + (f.len / nthr) * (t + 1);
+    if (cut < cur) cut = cur;
+    if (cut < end) {
+      const void *nl = memchr(cut, '\n', static_cast<size_t>(end - cut));
+      cut            = nl ? static_cast<const char *>(nl) + 1 : end;
+    }
+    chunks[t].end = cut;
+    cur           = cut;
+  }
+}
+
+} // namespace
+
+extern "C" {
+
+int msgpu_scrub_parse(const char *anchors_path, const char *ava_path, msgpu_scrub **out, uint64_t *err_line, int *err_file) {
+  if (!anchors_path || !ava_path || !out) return MSGPU_E_ARG;
+  *out = nullptr;
+  if (err_line) *err_line = 0;
+  if (err_file) *err_file = 0;
+  ScFile fa, fv;
+  int    rc = fa.map(anchors_path);
+  if (rc != MSGPU_OK) return rc;
+  rc = fv.map(ava_path);
+  if (rc != MSGPU_OK) {
+    if (err_file) *err_file = 1;
+    return rc;
+  }
+  std::unique_ptr<msgpu_scrub> s;
+  size_t                       bad_line = 0;
+  int                          bad_file = 0;
+  try {
+    s.reset(new msgpu_scrub());
+    unsigned nthr = std::thread::hardware_concurrency();
+    nthr          = nthr == 0 ? 1 : (nthr > 16 ? 16 : nthr);
+    const size_t len = std::max(fa.len, fv.len);
+    if (const char *e = getenv("MSGPU_PARSE_THREADS"))
+      nthr = static_cast<unsigned>(std::min<size_t>(std::max(1, atoi(e)), std::max<size_t>(1, std::min(fa.len, fv.len))));
+    else
+      while (nthr > 1 && len / nthr < (1u << 20)) --nthr;
+    std::vector<ScChunk> ca, cv;
+    sc_cut(fa, nthr, ca);
+    sc_cut(fv, nthr, cv);
+    std::vector<int> oom(nthr, 0);
+    auto             run = [&](auto &&fn) {
+      std::vector<std::thread> th;
+      struct JoinAll {
+        std::vector<std::thread> &t;
+        ~JoinAll() {
+          for (auto &x : t)
+            if (x.joinable()) x.join();
+        }
+      } join_all{th};
+      for (unsigned t = 1; t < nthr; ++t) th.emplace_back(fn, t);
+      fn(0u);
+      for (auto &x : th) x.join();
+      for (int o : oom)
+        if (o) throw std::bad_alloc();
+    };
+    run([&](unsigned t) {
+      ca[t].n_lines = count_lines(ca[t].begin, ca[t].end);
+      cv[t].n_lines = count_lines(cv[t].begin, cv[t].end);
+    });
+    for (auto *cs : {&ca, &cv}) {
+      size_t n = 0;
+      for (auto &c : *cs) {
+        c.first_line = n;
+        n += c.n_lines;
+      }
+      (cs == &ca ? s->n_anchor_lines : s->n_ava_lines) = n;
+    }
+    if (s->n_anchor_lines >= 0xffffffffull || s->n_ava_lines >= 0xffffffffull) throw std::bad_alloc();
+    run([&](unsigned t) {
+      try {
+        sc_tokenise(ca[t], false);
+        sc_tokenise(cv[t], true);
+      } catch (std::bad_alloc const &) { oom[t] = 1; }
+    });
+    // ---- rule 1, in line order
+    PairSet  seen;
+    uint32_t prev_anchor = 0xffffffffu;
+    {
+      size_t total = 0;
+      for (auto &c : ca) total += c.lines.size();
+      for (auto *v : {&s->hit_node, &s->hit_anchor, &s->hit_line}) v->reserve(total);
+      for (auto *v : {&s->hit_s, &s->hit_e}) v->reserve(total);
+    }
+    const ScLine *last = nullptr; // the line before: lines of one anchor follow each other, its id is known
+    uint32_t      last_anchor = 0;
+    for (auto &c : ca) {
+      for (size_t k = 0; k < c.lines.size(); ++k) {
+        const ScLine &x = c.lines[k];
+        if (k + 8 < c.lines.size()) s->nodes.want(c.lines[k + 8].b_h, 0);
+        const uint32_t before = s->nodes.size();
+        const uint32_t v      = s->nodes.get(x.b, x.b_n, x.b_h);
+        if (v == before) { // a new node
+          if (x.c6 < 200) {
+            rc       = MSGPU_E_NUMBER;
+            bad_line = x.line;
+            break;
+          }
+          s->node_length.push_back(x.c6);
+          s->node_line.push_back(x.line);
+        }
+        const uint32_t a = (last && last->a_n == x.a_n && memcmp(last->a, x.a, x.a_n) == 0)
+                               ? last_anchor
+                               : s->anchors.get(x.a, x.a_n, x.a_h);
+        last        = &x;
+        last_anchor = a;
+        if (!seen.insert((static_cast<uint64_t>(v) << 32) | a)) continue; // a later hit of the same (read, anchor)
+        if (a != prev_anchor) {
+          s->chunk_first.push_back(static_cast<uint32_t>(s->hit_node.size()));
+          s->chunk_n.push_back(0);
+          prev_anchor = a;
+        }
+        ++s->chunk_n.back();
+        s->hit_node.push_back(v);
+        s->hit_anchor.push_back(a);
+        s->hit_line.push_back(x.line);
+        s->hit_s.push_back(x.c7);
+        s->hit_e.push_back(x.c8);
+      }
+      if (rc == MSGPU_OK && c.err != MSGPU_OK) {
+        rc       = c.err;
+        bad_line = c.err_line;
+      }
+      if (rc != MSGPU_OK) break;
+    }
+    if (rc == MSGPU_OK && s->nodes.size() == 0) { // no node: nothing to scrub
+      rc       = MSGPU_E_FORMAT;
+      bad_line = 0;
+    }
+    if (rc == MSGPU_OK) {
+      // ---- rule 3's line tests that do not depend on the batch
+      const msgpu_scrub *cs = s.get();
+      run([&](unsigned t) {
+        ScChunk &c = cv[t];
+        size_t   w = 0;
+        for (size_t k = 0; k < c.lines.size(); ++k) {
+          ScLine &x = c.lines[k];
+          x.ia      = cs->nodes.find(x.a, x.a_n);
+          x.ib      = x.ia == 0xffffffffu ? x.ia : cs->nodes.find(x.b, x.b_n);
+          if (x.ia == 0xffffffffu || x.ib == 0xffffffffu) continue;
+          if (x.status != MSGPU_OK) {
+            c.err      = x.status;
+            c.err_line = x.line;
+            break;
+          }
+          c.lines[w++] = x;
+        }
+        c.lines.resize(w);
+      });
+      size_t total = 0;
+      for (auto &c : cv) total += c.lines.size();
+      for (auto *v : {&s->ava_a, &s->ava_b, &s->ava_strand, &s->ava_line}) v->reserve(total);
+      for (auto *v : {&s->ava_sa, &s->ava_ea, &s->ava_sb, &s->ava_eb}) v->reserve(total);
+      std::vector<std::string> strands; // other than "+" and "-"
+      for (auto &c : cv) {
+        for (const ScLine &x : c.lines) {
+          uint32_t d;
+          if (x.strand_n == 1 && *x.strand == '+') d = 0;
+          else if (x.strand_n == 1 && *x.strand == '-') d = 1;
+          else {
+            const std::string str(x.strand, x.strand_n);
+            size_t            k = 0;
+            while (k < strands.size() && strands[k] != str) ++k;
+            if (k == strands.size()) strands.push_back(str);
+            d = static_cast<uint32_t>(k) + 2;
+          }
+          s->ava_a.push_back(x.ia);
+          s->ava_b.push_back(x.ib);
+          s->ava_strand.push_back(d);
+          s->ava_line.push_back(x.line);
+          s->ava_sa.push_back(x.c2);
+          s->ava_ea.push_back(x.c3);
+          s->ava_sb.push_back(x.c7);
+          s->ava_eb.push_back(x.c8);
+        }
+        if (c.err != MSGPU_OK) {
+          rc       = c.err;
+          bad_line = c.err_line;
+          bad_file = 1;
+          break;
+        }
+      }
+    }
+  } catch (std::bad_alloc const &) { rc = MSGPU_E_NOMEM; } catch (std::system_error const &) {
+    rc = MSGPU_E_NOMEM;
+  }
+  if (rc != MSGPU_OK) {
+    if (err_line) *err_line = bad_line + 1;
+    if (err_file) *err_file = bad_file;
+    return rc;
+  }
+  *out = s.release();
+  return MSGPU_OK;
+}
+
+void msgpu_scrub_free(msgpu_scrub *s) { delete s; }
+
+int msgpu_scrub_get_tables(const msgpu_scrub *s, msgpu_scrub_tables *t) {
+  if (!s || !t) return MSGPU_E_ARG;
+  t->n_anchor_lines = s->n_anchor_lines;
+  t->n_ava_lines    = s->n_ava_lines;
+  t->n_hits         = s->hit_node.size();
+  t->n_ava          = s->ava_a.size();
+  t->n_nodes        = s->nodes.size();
+  t->n_anchors      = s->anchors.size();
+  t->n_chunks       = static_cast<uint32_t>(s->chunk_first.size());
+  t->pad            = 0;
+  t->node_length    = s->node_length.data();
+  t->node_line      = s->node_line.data();
+  t->hit_node       = s->hit_node.data();
+  t->hit_anchor     = s->hit_anchor.data();
+  t->hit_line       = s->hit_line.data();
+  t->hit_s          = s->hit_s.data();
+  t->hit_e          = s->hit_e.data();
+  t->chunk_first    = s->chunk_first.data();
+  t->chunk_n        = s->chunk_n.data();
+  t->ava_a          = s->ava_a.data();
+  t->ava_b          = s->ava_b.data();
+  t->ava_strand     = s->ava_strand.data();
+  t->ava_line       = s->ava_line.data();
+  t->ava_sa         = s->ava_sa.data();
+  t->ava_ea         = s->ava_ea.data();
+  t->ava_sb         = s->ava_sb.data();
+  t->ava_eb         = s->ava_eb.data();
+  return MSGPU_OK;
+}
+
+const char *msgpu_scrub_node_name(const msgpu_scrub *s, uint32_t id) { return s ? s->nodes.name(id) : nullptr; }
+uint32_t    msgpu_scrub_node_id(const msgpu_scrub *s, const char *name) {
+  return s && name ? s->nodes.find(name, strlen(name)) : 0xffffffffu;
+}
+
+// Python compares str by code point; for UTF-8 that is the order of the bytes
+int msgpu_scrub_name_order(const msgpu_scrub *s, uint32_t *out) {
+  if (!s || !out) return MSGPU_E_ARG;
+  const uint32_t n = s->nodes.size();
+  for (uint32_t i = 0; i < n; ++i) out[i] = i;
+  const NameRegistry &r = s->nodes;
+  std::sort(out, out + n, [&](uint32_t x, uint32_t y) {
+    const size_t nx = r.length(x), ny = r.length(y);
+    const int    c  = memcmp(r.name(x), r.name(y), std::min(nx, ny));
+    return c ? c < 0 : nx < ny;
+  });
+  return MSGPU_OK;
+}
+
+int msgpu_scrub_plan_create(uint32_t n_nodes, const uint32_t *by_name, const uint64_t *row_off, const uint32_t *adj,
+                            uint32_t subset_size, msgpu_scrub_plan **out, uint32_t *bad_node) {
+  if (!out || !n_nodes || !by_name || !row_off || (!adj && row_off[n_nodes]) || !subset_size) return MSGPU_E_ARG;
+  *out = nullptr;
+  if (bad_node) *bad_node = 0xffffffffu;
+  try {
+    std::unique_ptr<msgpu_scrub_plan> p(new msgpu_scrub_plan());
+    constexpr uint32_t    NONE = 0xffffffffu;
+    std::vector<uint8_t>  alive(n_nodes, 1);
+    std::vector<uint32_t> in_subset(n_nodes, NONE), seen(n_nodes, NONE); // the batch / the search that marked the node
+    std::vector<uint32_t> queue, depth;
+    uint32_t n_alive = n_nodes, first_alive = 0, search = 0;
+    while (n_alive) {
+      const uint32_t b     = static_cast<uint32_t>(p->start.size());
+      const size_t   sub0  = p->subset.size();
+      uint32_t       first = NONE;
+      for (;;) {
+        while (first_alive < n_nodes && !alive[by_name[first_alive]]) ++first_alive; // the dead stay dead
+        uint32_t k = first_alive;
+        while (k < n_nodes && (!alive[by_name[k]] || in_subset[by_name[k]] == b)) ++k;
+        if (k == n_nodes) break; // (cannot happen: nodes outside the subset remain)
+        const uint32_t start = by_name[k];
+        if (first == NONE) first = start;
+        // breadth-first over the remaining graph, depth_limit = subset_size; nodes join the subset in discovery order
+        queue.assign(1, start);
+        depth.assign(1, 0);
+        seen[start] = search;
+        for (size_t qi = 0; qi < queue.size() && p->subset.size() - sub0 < subset_size; ++qi) {
+          const uint32_t u = queue[qi];
+          if (in_subset[u] != b) {
+            in_subset[u] = b;
+            p->subset.push_back(u);
+          }
+          if (depth[qi] >= subset_size) continue;
+          for (uint64_t e = row_off[u]; e < row_off[u + 1]; ++e) {
+            const uint32_t w = adj[e];
+            if (w >= n_nodes) return MSGPU_E_ARG;
+            if (alive[w] && seen[w] != search) {
+              seen[w] = search;
+              queue.push_back(w);
+              depth.push_back(depth[qi] + 1);
+            }
+          }
+        }
+        ++search;
+        const size_t n_sub = p->subset.size() - sub0;
+        if (!(n_sub < subset_size && n_alive > n_sub)) break; // else: the component was small, merge the next one in
+      }
+      for (size_t k = sub0; k < p->subset.size(); ++k) {
+        const uint32_t v = p->subset[k];
+        bool           inner = true;
+        for (uint64_t e = row_off[v]; e < row_off[v + 1] && inner; ++e)
+          if (alive[adj[e]] && in_subset[adj[e]] != b) inner = false;
+        if (inner) p->centre.push_back(v);
+      }
+      const size_t cen0 = static_cast<size_t>(p->centre_off.back());
+      if (p->centre.size() == cen0) {
+        if (bad_node) *bad_node = first;
+        return MSGPU_E_LAYOUT;
+      }
+      std::sort(p->centre.begin() + static_cast<ptrdiff_t>(cen0), p->centre.end());
+      for (size_t k = cen0; k < p->centre.size(); ++k) alive[p->centre[k]] = 0;
+      n_alive -= static_cast<uint32_t>(p->centre.size() - cen0);
+      p->start.push_back(first);
+      p->subset_off.push_back(p->subset.size());
+      p->centre_off.push_back(p->centre.size());
+    }
+    *out = p.release();
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  return MSGPU_OK;
+}
+
+int msgpu_scrub_plan_get(const msgpu_scrub_plan *p, msgpu_scrub_plan_tables *t) {
+  if (!p || !t) return MSGPU_E_ARG;
+  t->n_batches  = static_cast<uint32_t>(p->start.size());
+  t->pad        = 0;
+  t->subset_off = p->subset_off.data();
+  t->centre_off = p->centre_off.data();
+  t->subset     = p->subset.data();
+  t->centre     = p->centre.data();
+  t->start      = p->start.data();
+  return MSGPU_OK;
+}
+
+void msgpu_scrub_plan_free(msgpu_scrub_plan *p) { delete p; }
+
+} // extern "C"

@@ -339,3 +339,125 @@ def unitig_filter_workload(n_reads, read_len, n_anchors, seed, coverage=10, n_re
     paf = ("\n".join(out) + "\n").encode()
     fasta = b"".join(b">%s synthetic len=%d\n%s\n" % (k.encode(), len(v), v) for k, v in seqs.items())
     return paf, fasta
+
+
+def scrubber_workload(n_reads, read_len, n_anchors, seed, coverage=10, read_len_min=None, hole_every=7, dup_frac=0.05,
+                      n_again=200, n_strangers=50, fastq=False):
+    """Input of the read scrubber (muchsalsa_amd.scrubber): (anchor PAF, read-to-read PAF, reads file), all bytes.
+
+    Built on paf_table / genome_bases: every paf_table row is an anchor line (its hits of 420..499 positions are the ones
+    the scrubber skips), the reads are r<i> = their stretch of the genome (FASTA, or FASTQ with fastq=True).  On top:
+      * a fraction dup_frac of the anchor lines is followed by a second hit of the same (read, anchor) with other read
+        coordinates, and every second line of n_again anchors comes back at the end of the file (a later chunk of an
+        anchor seen before);
+      * the read-to-read PAF has one pair per two reads that overlap by >= 800 positions, in either column order; a pair of
+        > 1300 positions is split, half of the time, into two lines (of > 3000 positions sometimes into three) whose gaps
+        are drawn from {50, 300, 499, 500, 700, 1500} (the second read's coordinates are shifted by a few positions, so the
+        two sides see different gaps), and a later line of a pair flips the strand one time in five; the lines are
+        shuffled;
+      * every hole_every-th read has an uncovered middle: its anchor hits and read-to-read lines that touch the middle fifth
+        are left out, so it is written as several records;
+      * n_strangers read-to-read lines name a read that no anchor line names, one line maps a read to itself, and reads
+        without an anchor hit of >= 500 positions are no nodes although lines name them.
+    Deterministic in (seed, shape)."""
+    tab = paf_table(n_reads, read_len, n_anchors, seed, coverage, read_len_min=read_len_min)
+    G, r_start, r_fwd = read_layout(n_reads, read_len, seed, coverage, read_len_min)
+    L = read_lengths(n_reads, read_len, seed, read_len_min)
+    genome = genome_bases(G, seed)
+    hole = (np.arange(n_reads) % max(int(hole_every), 1)) == (max(int(hole_every), 1) - 1) if hole_every else \
+        np.zeros(n_reads, bool)
+    h_lo, h_hi = (L * 2) // 5, (L * 3) // 5
+
+    # ---- anchor PAF
+    aid, rid = tab["qname_id"], tab["tname_id"]
+    keep = (~(hole[rid] & (tab["tstart"] < h_hi[rid]) & (tab["tend"] > h_lo[rid]))).tolist()
+    n = len(aid)
+    dup = (splitmix64(seed, 60, n) % np.uint64(1000)) < np.uint64(int(dup_frac * 1000))
+    rows = []
+    strand = np.where(tab["strand"], "+", "-")
+    cols = [tab[k].tolist() for k in ("qlen", "qstart", "qend", "tlen", "tstart", "tend", "nmatch")]
+    for i, a_, r_, st_, d_, (ql, qs, qe, tl, ts, te, nm) in zip(range(n), aid.tolist(), rid.tolist(), strand.tolist(),
+                                                               dup.tolist(), zip(*cols)):
+        if not keep[i]:
+            continue
+        rows.append((a_, "u%d\t%d\t%d\t%d\t%s\tr%d\t%d\t%d\t%d\t%d\t%d\t60" % (a_, ql, qs, qe, st_, r_, tl, ts, te, nm,
+                                                                                  qe - qs)))
+        if d_:
+            rows.append((a_, "u%d\t%d\t0\t%d\t-\tr%d\t%d\t5\t700\t600\t600\t60" % (a_, ql, ql, r_, tl)))
+    again = set(_randint(seed, 61, n_again, 0, max(int(aid.max()) if n else 0, 0)).tolist()) if n else set()
+    head, tail, seen_of = [], [], {}
+    for a, text in rows:
+        k = seen_of.get(a, 0)
+        seen_of[a] = k + 1
+        (tail if (a in again and k % 2 == 1) else head).append((a, text))
+    tail.sort(key=lambda x: x[0])
+    anchor_paf = ("\n".join(t for _, t in head + tail) + "\n").encode()
+
+    # ---- read-to-read PAF: reads sorted by start, read x against the later reads that begin >= 800 before its end
+    order = np.argsort(r_start, kind="stable")
+    s_sorted = r_start[order]
+    e_sorted = s_sorted + L[order]
+    hi = np.searchsorted(s_sorted, e_sorted - 800, side="left")
+    cnt = np.maximum(hi - np.arange(n_reads) - 1, 0)
+    x = np.repeat(np.arange(n_reads), cnt)
+    y = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt) + x + 1
+    i, j = order[x], order[y]
+    lo, hi = r_start[j], np.minimum(r_start[i] + L[i], r_start[j] + L[j])
+    ok = (hi - lo) >= 800
+    i, j, lo, hi = i[ok], j[ok], lo[ok], hi[ok]
+    m = len(i)
+    u = splitmix64(seed, 62, m)
+    swap = (u & np.uint64(1)).astype(bool)
+    a, b = np.where(swap, j, i), np.where(swap, i, j)
+    pieces = np.ones(m, np.int64)
+    ov = hi - lo
+    pieces[(ov > 1300) & (((u >> np.uint64(1)) % np.uint64(100)) < np.uint64(50))] = 2
+    pieces[(ov > 3000) & (((u >> np.uint64(1)) % np.uint64(100)) < np.uint64(15))] = 3
+    gaps = np.array([50, 300, 499, 500, 700, 1500])
+    g1 = gaps[(splitmix64(seed, 63, m) % np.uint64(6)).astype(np.int64)]
+    g2 = gaps[(splitmix64(seed, 64, m) % np.uint64(6)).astype(np.int64)]
+    shift = _randint(seed, 65, m, -3, 3)
+    flip = splitmix64(seed, 66, m)
+    base_strand = r_fwd[a] == r_fwd[b]
+    out = []
+    lo_l, hi_l, pc_l, u_l, g1_l, g2_l = lo.tolist(), hi.tolist(), pieces.tolist(), u.tolist(), g1.tolist(), g2.tolist()
+    a_l, b_l, sh_l, fl_l, bs_l = a.tolist(), b.tolist(), shift.tolist(), flip.tolist(), base_strand.tolist()
+    rs_l, L_l, hole_l, hlo_l, hhi_l = r_start.tolist(), L.tolist(), hole.tolist(), h_lo.tolist(), h_hi.tolist()
+    for k in range(m):
+        p, q = lo_l[k], hi_l[k]
+        if pc_l[k] == 1:
+            cuts = [(p, q)]
+        elif pc_l[k] == 2:
+            mid = p + 550 + (u_l[k] >> 8) % (q - p - 1100)
+            cuts = [(p, mid), (min(mid + g1_l[k], q - 520), q)]
+        else:  # every cut stays inside the overlap: 600 + w + 1500 + 600 + w <= q - p - 100
+            w = (q - p - 2800) // 2
+            m1 = p + 600 + (u_l[k] >> 8) % w
+            z1 = m1 + g1_l[k]
+            m2 = z1 + 600 + (u_l[k] >> 24) % w
+            cuts = [(p, m1), (z1, m2), (min(m2 + g2_l[k], q - 520), q)]
+        ra, rb = a_l[k], b_l[k]
+        sa, sb, La, Lb = rs_l[ra], rs_l[rb], L_l[ra], L_l[rb]
+        for c, (l0, h0) in enumerate(cuts):
+            if h0 - l0 < 1:
+                continue
+            plus = bs_l[k] ^ (c > 0 and (fl_l[k] >> (8 * c)) % 5 == 0)
+            a0, a1 = l0 - sa, h0 - sa
+            b0, b1 = max(l0 - sb + sh_l[k] * c, 0), min(h0 - sb + sh_l[k] * c, Lb)
+            if (hole_l[ra] and a0 < hhi_l[ra] and a1 > hlo_l[ra]) or (hole_l[rb] and b0 < hhi_l[rb] and b1 > hlo_l[rb]):
+                continue
+            out.append("r%d\t%d\t%d\t%d\t%s\tr%d\t%d\t%d\t%d\t%d\t%d\t60" % (ra, La, a0, a1, "+" if plus else "-", rb, Lb, b0,
+                                                                              b1, h0 - l0, h0 - l0))
+    for k, r in enumerate(_randint(seed, 67, n_strangers, 0, n_reads - 1).tolist()):
+        out.append("r%d\t%d\t0\t900\t+\tstranger%d\t4000\t10\t910\t900\t900\t60" % (r, int(L[r]), k) if k % 2 else
+                   "stranger%d\t4000\t10\t910\t-\tr%d\t%d\t0\t900\t900\t900\t60" % (k, r, int(L[r])))
+    out.append("r0\t%d\t0\t900\t+\tr0\t%d\t0\t900\t900\t900\t60" % (int(L[0]), int(L[0])))
+    perm = np.argsort(splitmix64(seed, 68, len(out)), kind="stable")
+    ava_paf = ("\n".join(out[k] for k in perm.tolist()) + "\n").encode()
+
+    # ---- the reads
+    recs = []
+    for r in range(n_reads):
+        seq = genome[r_start[r]:r_start[r] + L[r]].tobytes()
+        recs.append(b"@r%d\n%s\n+\n%s\n" % (r, seq, b"I" * len(seq)) if fastq else b">r%d\n%s\n" % (r, seq))
+    return anchor_paf, ava_paf, b"".join(recs)
