@@ -104,6 +104,63 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wave_incl_scan(v)), 63));
 }
 
+// fp64 maxima over lanes without LDS.  Every step is fmax(v, v moved by a DPP control): two v_mov_b32_dpp and one
+// v_max_f64, where a __shfl_xor / __shfl_up step is index arithmetic, two ds_bpermute and a wait for the LDS round trip.
+// The maximum is __builtin_fmax's (a NaN operand is skipped); a lane without a DPP source keeps its own value (the
+// moves' `old` operand is the value itself), so no identity constant takes part.  All 64 lanes must be active.
+// PERMUTES: the control gives every lane a source (quad_perm, the mirrors), so the moves need no `old` operand -- and no
+// copy of the value to tie it to.
+template <int CTRL, int ROW_MASK = 0xf, bool PERMUTES = false> __device__ __forceinline__ double dpp_max_step(double v) {
+  const unsigned long long b  = __builtin_bit_cast(unsigned long long, v);
+  const int                lo = static_cast<int>(static_cast<uint32_t>(b)), hi = static_cast<int>(static_cast<uint32_t>(b >> 32));
+  uint32_t                 ml, mh;
+  if constexpr (PERMUTES) {
+    static_assert(ROW_MASK == 0xf, "every row takes part in a permutation");
+    ml = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false));
+    mh = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false));
+  } else {
+    ml = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false));
+    mh = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false));
+  }
+  return __builtin_fmax(v, __builtin_bit_cast(double, (static_cast<unsigned long long>(mh) << 32) | ml));
+}
+// the maximum of every aligned group of W lanes (W = 8, 16, 32, 64), in all of its lanes.  Inside a row of 16 lanes:
+// quad_perm:[1,0,3,2] and [2,3,0,1] make the quads uniform, row_half_mirror exchanges the two quads of a half-row,
+// row_mirror the two half-rows.  Across rows one exchange per level: v_permlane16_swap of the value with itself returns
+// (row 0, row 0, row 2, row 2) and (row 1, row 1, row 3, row 3), v_permlane32_swap the lower and the upper 32 lanes twice.
+template <int W> __device__ __forceinline__ double group_max_f64(double v) {
+  static_assert(W == 8 || W == 16 || W == 32 || W == 64, "group width");
+  v = dpp_max_step<0xb1, 0xf, true>(v);  // quad_perm:[1,0,3,2]
+  v = dpp_max_step<0x4e, 0xf, true>(v);  // quad_perm:[2,3,0,1]
+  v = dpp_max_step<0x141, 0xf, true>(v); // row_half_mirror
+  if constexpr (W >= 16) v = dpp_max_step<0x140, 0xf, true>(v); // row_mirror
+  if constexpr (W >= 32) {
+    const unsigned long long b  = __builtin_bit_cast(unsigned long long, v);
+    const auto               lo = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(b), static_cast<uint32_t>(b), false, false);
+    const auto               hi = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(b >> 32), static_cast<uint32_t>(b >> 32), false, false);
+    v = __builtin_fmax(__builtin_bit_cast(double, (static_cast<unsigned long long>(hi[0]) << 32) | lo[0]),
+                       __builtin_bit_cast(double, (static_cast<unsigned long long>(hi[1]) << 32) | lo[1]));
+  }
+  if constexpr (W == 64) {
+    const unsigned long long b  = __builtin_bit_cast(unsigned long long, v);
+    const auto               lo = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(b), static_cast<uint32_t>(b), false, false);
+    const auto               hi = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(b >> 32), static_cast<uint32_t>(b >> 32), false, false);
+    v = __builtin_fmax(__builtin_bit_cast(double, (static_cast<unsigned long long>(hi[0]) << 32) | lo[0]),
+                       __builtin_bit_cast(double, (static_cast<unsigned long long>(hi[1]) << 32) | lo[1]));
+  }
+  return v;
+}
+// inclusive prefix maximum over the wavefront: lane l gets the maximum of lanes 0..l (wave_incl_scan's moves)
+__device__ __forceinline__ double wave_prefix_max_f64(double v) {
+  v = dpp_max_step<0x111>(v);      // row_shr:1
+  v = dpp_max_step<0x112>(v);      // row_shr:2
+  v = dpp_max_step<0x114>(v);      // row_shr:4
+  v = dpp_max_step<0x118>(v);      // row_shr:8
+  v = dpp_max_step<0x142, 0xa>(v); // row_bcast:15 into rows 1 and 3
+  v = dpp_max_step<0x143, 0xc>(v); // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
 template <int NT> __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave /*[NT / 64]*/, uint32_t *total) {
   const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t inc  = wave_incl_scan(v);

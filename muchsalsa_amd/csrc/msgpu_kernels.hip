@@ -1629,12 +1629,10 @@ __device__ __forceinline__ int paths_of_direction(unsigned long long act, bool d
   if (act == 0) return 0; // :150-152
   const bool mine = (act >> lane) & 1ull;
   // argmax, :201-210: strict > starting from 0.0, first maximum wins, iterator starts at begin().  The maximum alone is
-  // reduced over the wavefront (one v_max_f64 per butterfly step; the scores are finite, so the hardware maximum is the
-  // comparison's); the FIRST lane that holds it comes out of one ballot -- the index used to travel through the butterfly
+  // reduced over the wavefront (group_max_f64: DPP and permlane moves, no LDS; the scores are finite, so the hardware
+  // maximum is the comparison's); the FIRST lane that holds it comes out of one ballot -- the index used to travel through the butterfly
   // with two compares and three selects per step.
-  double best = mine ? pop : -1.0;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) best = __builtin_fmax(best, __shfl_xor(best, d));
+  const double best = group_max_f64<64>(mine ? pop : -1.0);
   double maxv;
   int    maxi;
   if (best > 0.0) {
@@ -2101,12 +2099,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   {
     // the band rule: inclusive prefix maximum of pop over the lanes (the lanes past the edge hold 0 and lie behind every row; a NaN
     // score is skipped by the maximum and never updates a later row either), read from lane l - B - 1
-    double pmax = pop;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const double up = __shfl_up(pmax, d);
-      if (ln >= d) pmax = __builtin_fmax(pmax, up);
-    }
+    const double pmax = wave_prefix_max_f64(pop);
     const double out = __shfl(pmax, ln > MSGPU_CHAIN_BAND ? ln - MSGPU_CHAIN_BAND - 1 : 0);
     const bool   rej = ln > MSGPU_CHAIN_BAND && ln < static_cast<int>(n) && !(out + em_score < pop);
     if (__ballot(rej) == 0) break;
@@ -2320,9 +2313,8 @@ __device__ __forceinline__ uint32_t paths_of_direction_sub(uint32_t act, bool di
                                                            uint32_t n1, uint32_t n2, double alt_frac, SubPath *paths) {
   const bool live = act != 0; // :150-152
   const bool mine = (act >> sl) & 1u;
-  double     best = mine ? pop : -1.0; // argmax, :201-210 (as in paths_of_direction: the maximum by v_max_f64, its first lane by a ballot)
-#pragma unroll
-  for (int d = W / 2; d > 0; d >>= 1) best = __builtin_fmax(best, __shfl_xor(best, d));
+  // argmax, :201-210 (as in paths_of_direction: the maximum by v_max_f64 over DPP moves, its first lane by a ballot)
+  const double best = group_max_f64<W>(mine ? pop : -1.0);
   double maxv = 0.0;
   int    maxi = live ? __builtin_ctz(act) : 0;
   if (best > 0.0) {
@@ -2679,8 +2671,18 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
 
   // src/main.cpp:341-353: split by EdgeMatch direction, minus then plus
   SubPath *pmn = reinterpret_cast<SubPath *>(s_wavebuf[wave]) + gbase, *ppl = pmn + 64; // el[] is dead from here on
-  const uint32_t n_m = paths_of_direction_sub<W>(m_minus, false, sl, gbase, pop, pm, em_prim, j1, q2, n1, n2, a.alt_frac, pmn);
-  const uint32_t n_p = paths_of_direction_sub<W>(m_plus, true, sl, gbase, pop, pm, em_prim, j1, q2, n1, n2, a.alt_frac, ppl);
+  // The direction is a group's own, so a wavefront cannot skip an empty one the way k_chain does.  One pass serves every
+  // group's first direction (minus where it has one, else plus) with direction, lanes and list per group; the second pass,
+  // the plus list of the groups that have both, runs only in a wavefront that holds such a group.
+  uint32_t n_m = 0, n_p = 0;
+#pragma clang loop unroll(disable)
+  for (int trip = 0; trip < 2; ++trip) {
+    const bool     dir  = trip != 0 || m_minus == 0;
+    const uint32_t actd = trip == 0 ? (m_minus ? m_minus : m_plus) : (m_minus ? m_plus : 0u);
+    const uint32_t np   = paths_of_direction_sub<W>(actd, dir, sl, gbase, pop, pm, em_prim, j1, q2, n1, n2, a.alt_frac, dir ? ppl : pmn);
+    if (actd) (dir ? n_p : n_m) = np; // (a group without a second direction keeps its counts)
+    if (__ballot(m_minus != 0 && m_plus != 0) == 0) break;
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 
@@ -2714,15 +2716,18 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
 
   // getOverlap (ol.cpp:53-101) per kept path, minus first
   uint32_t n_orders = 0, n_ids = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    uint32_t       keep = pass == 0 ? keep_m : keep_p;
-    const SubPath *pv   = pass == 0 ? pmn : ppl;
-    const bool     dir  = pass == 1;
-    while (__ballot(keep != 0)) {
-      const bool has = keep != 0;
-      const int  pi  = has ? __builtin_ctz(keep) : 0;
-      keep &= keep - 1u;
-      const SubPath  rec  = pv[pi];
+  // (one sequence per group, its kept minus paths and then its kept plus paths: the loop runs to the wavefront's largest
+  // number of kept paths, not to the largest minus count plus the largest plus count)
+  {
+    uint32_t km = keep_m, kp = keep_p;
+    while (__ballot((km | kp) != 0)) {
+      const bool     dir  = km == 0;
+      const uint32_t keep = dir ? kp : km;
+      const bool     has  = keep != 0;
+      const int      pi   = has ? __builtin_ctz(keep) : 0;
+      km &= km - 1u;                    // (0 stays 0)
+      kp = dir ? (keep & (keep - 1u)) : kp;
+      const SubPath  rec  = (dir ? ppl : pmn)[pi];
       const uint32_t mask = (has && rec.mask) ? rec.mask : 1u;
       const int      f = __builtin_ctz(mask), l = 31 - __builtin_clz(mask);
       const double  *kf = s_keep[wave][gbase + f], *kl = s_keep[wave][gbase + l];
