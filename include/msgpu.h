@@ -932,6 +932,92 @@ const char *msgpu_scrub_result_text(const msgpu_scrub_result *r, uint64_t *len);
 int         msgpu_scrub_result_graph(const msgpu_scrub_result *r, const uint64_t **row_off, const uint32_t **adj);
 void        msgpu_scrub_result_free(msgpu_scrub_result *r);
 
+/* ==== k-mer abundance filter: the pipeline's first step, "K-mer Filtering of Illumina Reads" =============================
+ * (pipeline/pipeline.sh:136-151: jellyfish count -C / histo, the pipeline's setAbundanceThresholdFromHisto.py, jellyfish
+ * dump -L, bbduk hdist=0).  Input: k (1..64) and two FASTQ files of equally many records; record i
+ * of the one and record i of the other are a pair.  The threshold rule is pinned to the reference script (its outputs
+ * recorded under tests/golden/kmer_filter); counting and filtering are defined by these rules:
+ *  1. FASTQ: four lines per record, only '\n' ends a line, a last line without '\n' counts.  Line 1 starts with '@', line 3
+ *     with '+', lines 2 and 4 have the same number of bytes (0 is allowed).  Anything else is MSGPU_E_FORMAT with the file
+ *     (0 / 1) and the smallest offending 1-based line; a file that ends inside a record is one at the first missing line; two
+ *     files of different record counts are one in the shorter file, at its first missing line.  File 0 is judged first.
+ *  2. k-mers: a window is k consecutive bytes of a line 2, all of them in ACGTacgt (case folded); any other byte breaks the
+ *     windows that hold it.  A=0, C=1, G=2, T=3, first base most significant, a 2k-bit unsigned number; the canonical k-mer
+ *     of a window is the smaller of that number and the number of its reverse complement (jellyfish's -C).  A read shorter
+ *     than k has no window.
+ *  3. counts: count(x) = windows of both files whose canonical k-mer is x.  Exact (the "classic approach" pipeline.sh keeps
+ *     as a comment; the --bf-size run it uses approximates the same table above abundance 1).
+ *  4. histogram: row (a, f): f distinct canonical k-mers have count a, 1 <= a <= 10000; one row a = 10001 holds every k-mer
+ *     with a count above 10000 (jellyfish histo's default --high); rows with f = 0 are left out; text "a f\n", ascending.
+ *  5. threshold: what the script prints for that histogram and total = sum of f over the rows with a != 1:
+ *     q1_th = round((total + 1) * 0.25), q3_th = round((total + 1) * 0.75), half to even; rows with a > 1 in order, a running
+ *     sum of f; q1 = a of the first row where the sum reaches q1_th, q3 = a of the first LATER row where it reaches q3_th (the
+ *     row that sets q1 never sets q3); upper = q3 + 2 * (q3 - q1).  q3 never set (the script prints a number <= 0) or no row
+ *     besides a = 1 (the script dies) is MSGPU_E_LAYOUT, "degenerate histogram".  Whenever q3 is set, q3 > q1 >= 2, hence
+ *     upper >= 5: the count pass discards k-mers with a count below 5 once they are in the histogram.
+ *  6. abundant set: the canonical k-mers with count >= upper (jellyfish dump -L).
+ *  7. verdict: pair i is dropped when read 1 or read 2 has at least one window whose canonical k-mer is in the abundant set
+ *     (bbduk's hdist=0).  Surviving pairs are written in input order, a record as its four input lines byte for byte, each
+ *     ended by '\n'.
+ *  8. report: "abundance threshold for k-mer filtering:  <upper>\n" (two blanks, as the pipeline's echo writes it).
+ * On any error nothing is produced.  Limits: a file below 2^40 bytes and 2^32 records; both files, the partition buffers and
+ * the outputs are resident together, otherwise MSGPU_E_NOMEM with the sizes in msgpu_kf_last_error. */
+typedef struct msgpu_kfctx msgpu_kfctx; /* a device context of the stage */
+typedef struct msgpu_kf_result msgpu_kf_result;
+/* Rule 5 on histogram rows (host only, works without a device).  MSGPU_E_LAYOUT for a degenerate histogram: *q1, *q3 and
+ * *upper then hold what the script would have computed (0 where it set nothing). */
+int         msgpu_kf_threshold(const uint64_t *abundance, const uint64_t *frequency, size_t n, int64_t *q1, int64_t *q3,
+                               int64_t *upper);
+/* device = HIP ordinal (MSGPU_E_NODEVICE without a GPU) */
+int         msgpu_kf_create(int device, msgpu_kfctx **out);
+void        msgpu_kf_destroy(msgpu_kfctx *ctx);
+const char *msgpu_kf_last_error(const msgpu_kfctx *ctx);
+uint64_t    msgpu_kf_error_line(const msgpu_kfctx *ctx); /* after MSGPU_E_FORMAT: the 1-based line */
+int         msgpu_kf_error_file(const msgpu_kfctx *ctx); /* after MSGPU_E_FORMAT / MSGPU_E_IO: 0 or 1 */
+typedef struct msgpu_kf_stats {
+  uint64_t n_pairs, n_pairs_out; /* pairs read; pairs that survive                                                      */
+  uint64_t n_windows;            /* rule 2, both files                                                                   */
+  uint64_t n_distinct;           /* distinct canonical k-mers                                                            */
+  uint64_t n_candidates;         /* of those, count >= 5: what is kept until the threshold is known                      */
+  uint64_t n_abundant;           /* rule 6                                                                               */
+  uint64_t n_hist_rows;
+  uint64_t largest_partition;    /* keys in the largest partition                                                        */
+  uint64_t bytes_in[2], bytes_out[2];
+  int64_t  q1, q3, upper;
+  uint32_t k, n_partitions;
+  float load_ms;    /* host: both files mmap -> page-locked ring -> device (wall)                                        */
+  float records_ms; /* line starts and the format check of both files (wall; device work and four small copies)          */
+  float bins_ms;    /* device, by events from here on: windows per hash bin                                              */
+  float extract_ms; /* keys of a partition, summed over the partitions (as sort / runs / hist / select)                  */
+  float sort_ms, runs_ms, hist_ms;
+  float select_ms;  /* candidates per partition; the abundant set, its sort and its table                                */
+  float verdict_ms;
+  float output_ms;  /* lengths, scan, record copy, both files                                                            */
+  float copy_ms;    /* outputs, verdicts and the abundant set back to the host                                           */
+  float wall_ms;
+} msgpu_kf_stats;
+/* The whole stage.  flags must be 0.  budget_bytes bounds the partition buffers (two key buffers and the run lengths: 20
+ * bytes per key for k <= 32, 36 above); 0 = half of the device memory that is free once both files are resident and the
+ * outputs are set aside.  The keys are cut into the smallest number of partitions (by a hash of the canonical key, so every
+ * k-mer lies in exactly one and the result does not depend on the number) whose largest stays within the budget and below
+ * 2^31 keys.  Synchronous; the outputs' text is kept in the result. */
+int         msgpu_kf_run(msgpu_kfctx *ctx, int k, const char *path_a, const char *path_b, uint32_t flags,
+                         uint64_t budget_bytes, msgpu_kf_result **out);
+int         msgpu_kf_result_stats(const msgpu_kf_result *r, msgpu_kf_stats *out);
+int         msgpu_kf_result_histogram(const msgpu_kf_result *r, const uint64_t **abundance, const uint64_t **frequency,
+                                      uint64_t *n);
+/* rule 6, ascending: the key's upper and lower 64 bits (upper = 0 for k <= 32) and its count */
+int         msgpu_kf_result_abundant(const msgpu_kf_result *r, const uint64_t **key_hi, const uint64_t **key_lo,
+                                     const uint32_t **count, uint64_t *n);
+int         msgpu_kf_result_verdicts(const msgpu_kf_result *r, const uint8_t **verdict, uint64_t *n); /* 1 = dropped */
+#define MSGPU_KF_TEXT_OUT_A 0  /* the surviving records of file 0 */
+#define MSGPU_KF_TEXT_OUT_B 1
+#define MSGPU_KF_TEXT_REPORT 2 /* rule 8 */
+#define MSGPU_KF_TEXT_HISTO 3  /* rule 4 */
+#define MSGPU_KF_TEXT_KMERS 4  /* rule 6 as ">count\nKMER\n" records (jellyfish dump's format), ascending; built on first use */
+const char *msgpu_kf_result_text(msgpu_kf_result *r, int which, uint64_t *len);
+void        msgpu_kf_result_free(msgpu_kf_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

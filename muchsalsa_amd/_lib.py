@@ -153,6 +153,18 @@ class ScrubStats(C.Structure):  # msgpu_scrub_stats
 SCRUB_SUBSET = 60000
 
 
+class KfStats(C.Structure):  # msgpu_kf_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_pairs", "n_pairs_out", "n_windows", "n_distinct", "n_candidates",
+                                           "n_abundant", "n_hist_rows", "largest_partition")] +
+                [("bytes_in", C.c_uint64 * 2), ("bytes_out", C.c_uint64 * 2)] +
+                [(n, C.c_int64) for n in ("q1", "q3", "upper")] + [("k", C.c_uint32), ("n_partitions", C.c_uint32)] +
+                [(n, C.c_float) for n in ("load_ms", "records_ms", "bins_ms", "extract_ms", "sort_ms", "runs_ms",
+                                          "hist_ms", "select_ms", "verdict_ms", "output_ms", "copy_ms", "wall_ms")])
+
+
+KF_TEXT_OUT_A, KF_TEXT_OUT_B, KF_TEXT_REPORT, KF_TEXT_HISTO, KF_TEXT_KMERS = 0, 1, 2, 3, 4
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -353,6 +365,23 @@ SYMBOLS = [
     ("msgpu_scrub_result_graph", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)),
                                            C.POINTER(C.POINTER(C.c_uint32))]),
     ("msgpu_scrub_result_free", None, [C.c_void_p]),
+    ("msgpu_kf_threshold", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]),
+    ("msgpu_kf_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_kf_destroy", None, [C.c_void_p]),
+    ("msgpu_kf_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_kf_error_line", C.c_uint64, [C.c_void_p]),
+    ("msgpu_kf_error_file", C.c_int, [C.c_void_p]),
+    ("msgpu_kf_run", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
+                               C.POINTER(C.c_void_p)]),
+    ("msgpu_kf_result_stats", C.c_int, [C.c_void_p, C.POINTER(KfStats)]),
+    ("msgpu_kf_result_histogram", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)),
+                                            C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]),
+    ("msgpu_kf_result_abundant", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64)),
+                                           C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint64)]),
+    ("msgpu_kf_result_verdicts", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]),
+    ("msgpu_kf_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    ("msgpu_kf_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

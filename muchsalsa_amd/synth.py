@@ -461,3 +461,68 @@ def scrubber_workload(n_reads, read_len, n_anchors, seed, coverage=10, read_len_
         seq = genome[r_start[r]:r_start[r] + L[r]].tobytes()
         recs.append(b"@r%d\n%s\n+\n%s\n" % (r, seq, b"I" * len(seq)) if fastq else b">r%d\n%s\n" % (r, seq))
     return anchor_paf, ava_paf, b"".join(recs)
+
+
+def kmer_filter_workload(genome, coverage, read_len, seed, families=6, copies=25, repeat_len=1500, error=0.005,
+                         n_frac=0.0005, lower_frac=0.001, insert=None):
+    """Input of the k-mer abundance filter (muchsalsa_amd.kmer_filter): (FASTQ file 1, FASTQ file 2), bytes.
+
+    A uniform genome of ``genome`` bases (genome_bases) in which ``families`` repeat units of ``repeat_len`` bases are each
+    written ``copies`` times (identical copies, one per slot of an even grid, at a drawn offset inside the slot): their k-mers
+    are what the filter finds abundant.  genome * coverage / (2 * read_len) fragments of ``insert`` (default 2.5 read
+    lengths) bases at uniform starts; mate 1 is the fragment's first read_len bases, mate 2 the reverse complement of its
+    last; every second fragment comes from the other strand (the mates swap roles).  On the reads: a fraction ``error`` of
+    the bases is replaced by another base, ``n_frac`` become 'N', ``lower_frac`` lower case.  Record i of both files is
+    named p<i, zero padded>/1 and /2; the quality line is all 'I', and starts with '@' in every 97th record.
+    Deterministic in (seed, shape)."""
+    G, L = int(genome), int(read_len)
+    insert = int(insert) if insert else (5 * L) // 2
+    g = genome_bases(G, seed).copy()
+    slots = int(families) * int(copies)
+    if slots:
+        slot = G // slots
+        if slot < repeat_len or G < insert:
+            raise ValueError("genome too short for the repeats")
+        units = genome_bases(int(families) * int(repeat_len), seed + 1).reshape(int(families), int(repeat_len))
+        where = np.argsort(splitmix64(seed, 70, slots), kind="stable")  # which slot a (family, copy) lands in
+        jitter = _randint(seed, 71, slots, 0, slot - int(repeat_len))
+        for i in range(slots):
+            at = int(where[i]) * slot + int(jitter[i])
+            g[at:at + int(repeat_len)] = units[i // int(copies)]
+    n = max(G * int(coverage) // (2 * L), 1)
+    start = _randint(seed, 72, n, 0, G - insert)
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    col = np.arange(L, dtype=np.int64)[None, :]
+    left = g[start[:, None] + col]
+    right = comp[g[(start + insert - 1)[:, None] - col]]
+    other = (np.arange(n) & 1).astype(bool)[:, None]
+    mates = [np.where(other, right, left), np.where(other, left, right)]
+    nb = n * L
+    alt = {65: b"CGT", 67: b"GTA", 71: b"TAC", 84: b"ACG"}
+    sub = np.zeros((256, 3), np.uint8)
+    for b, t in alt.items():
+        sub[b] = list(t)
+    out = []
+    for m, reads in enumerate(mates):
+        flat = np.ascontiguousarray(reads).reshape(-1)
+        pos = _randint(seed, 73 + 10 * m, int(nb * error), 0, nb - 1)
+        flat[pos] = sub[flat[pos], (splitmix64(seed, 74 + 10 * m, len(pos)) % np.uint64(3)).astype(np.int64)]
+        flat[_randint(seed, 75 + 10 * m, int(nb * n_frac), 0, nb - 1)] = ord("N")
+        pos = _randint(seed, 76 + 10 * m, int(nb * lower_frac), 0, nb - 1)
+        flat[pos] |= 0x20
+        width = len(str(n - 1))
+        head = 2 + width + 3  # "@p", digits, "/1\n"
+        rec = np.empty((n, head + L + 3 + L + 1), np.uint8)
+        rec[:, 0], rec[:, 1] = ord("@"), ord("p")
+        idx = np.arange(n, dtype=np.int64)
+        for d in range(width):
+            rec[:, 2 + d] = 48 + (idx // 10 ** (width - 1 - d)) % 10
+        rec[:, 2 + width:head] = np.frombuffer(b"/%d\n" % (m + 1), np.uint8)
+        rec[:, head:head + L] = flat.reshape(n, L)
+        rec[:, head + L:head + L + 3] = np.frombuffer(b"\n+\n", np.uint8)
+        rec[:, head + L + 3:head + 2 * L + 3] = ord("I")
+        rec[::97, head + L + 3] = ord("@")
+        rec[:, -1] = 10
+        out.append(rec.tobytes())
+    return out[0], out[1]
