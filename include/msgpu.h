@@ -1018,6 +1018,96 @@ int         msgpu_kf_result_verdicts(const msgpu_kf_result *r, const uint8_t **v
 const char *msgpu_kf_result_text(msgpu_kf_result *r, int which, uint64_t *len);
 void        msgpu_kf_result_free(msgpu_kf_result *r);
 
+/* ==== short-read unitig assembly: the step behind the k-mer filter, `abyss-pe ... unitigs` and the awk cut at MINLENGTH ===
+ * (pipeline/pipeline.sh).  ABySS is not part of the reference tree, so the stage is defined by these
+ * rules and checked against their plain-Python restatement (tests/ug_oracle.py), not against ABySS.  Parameters: k (2..64),
+ * min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500).
+ *  1. input: one or two FASTQ files.  The FASTQ rules and the window rules are rules 1 and 2 of the k-mer abundance filter,
+ *     word for word, error code, file and line included.  The files are not pairs: their record counts may differ and the
+ *     second path may be NULL.  count(x) = windows of all files whose canonical k-mer is x, exact.
+ *  2. solid set S = the canonical k-mers with count >= min_count.
+ *  3. oriented graph: every k-base string s whose canonical form is in S is an oriented node; s and rc(s) are two nodes of
+ *     one k-mer, or one node if s is its own reverse complement.  succ(s) = { s[1:]+c : c in ACGT, canon(s[1:]+c) in S },
+ *     pred(s) = { c+s[:-1] : c in ACGT, canon(c+s[:-1]) in S }.
+ *  4. tip removal, in rounds on a snapshot of S.  The limits are 1, 2, 4, ... (doubling, every value below trim), then trim;
+ *     each limit runs once, after that the round at trim repeats until a round removes nothing; trim = 0: no round.  In a
+ *     round, for every oriented node s with pred(s) empty: path = [s], then repeat: if |succ(last)| != 1 stop, no tip; let t
+ *     be the one successor; if |pred(t)| >= 2 the path is a tip, stop; if |path| = limit stop, no tip; else append t.  All
+ *     k-mers of all tips of a round leave S together when the round ends.  Islands (dead at both ends) stay.  Each round's
+ *     (limit, k-mers removed) is reported.
+ *  5. unitigs: s -> t is joined iff succ(s) = {t}, pred(t) = {s}, neither s nor t is its own reverse complement and
+ *     canon(s) != canon(t): no self-loop and no hairpin is ever joined.  Unitigs are the maximal chains of joined nodes;
+ *     every k-mer of S lies in exactly one.  Every unitig exists as two mirror chains, which these rules make distinct (a
+ *     one-node chain of a self-complementary k-mer exists once).  Linear chain: the one whose first k-mer, as a 2k-bit
+ *     number, is smaller than its mirror's first k-mer is emitted (no tie is possible).  Cycle: it starts at the smallest
+ *     oriented node among the cycle and its mirror and goes round once: n k-mers give n + k - 1 bases, the closing join is
+ *     not written.  Sequence = the first k-mer and the last base of every further node, upper case.  coverage = sum of
+ *     count over its k-mers (64 bits).
+ *  6. output: the unitigs ascending by the first k-mer of the emitted orientation; id = rank in that order, over all
+ *     unitigs, before any cut.  A record is ">id length coverage\n", the sequence on one line, "\n" (ABySS's header shape;
+ *     the pipeline's awk reads field 2).  Two texts: all records, and the records with length >= min_length, ids unchanged
+ *     (the pipeline's ${NAME}-unitigs.l500.fa).
+ *  7. limits, each an error and never a fault: fewer than 2^31 solid k-mers; the file limits of the k-mer filter; everything
+ *     resident together, else MSGPU_E_NOMEM naming the sizes.  On any error nothing is produced. */
+typedef struct msgpu_ugctx msgpu_ugctx; /* a device context of the stage */
+typedef struct msgpu_ug_result msgpu_ug_result;
+typedef struct msgpu_ug_params {
+  int32_t  k;
+  uint32_t min_count;
+  int32_t  trim; /* -1: k */
+  uint32_t min_length;
+} msgpu_ug_params;
+int         msgpu_ug_create(int device, msgpu_ugctx **out); /* MSGPU_E_NODEVICE without a GPU */
+void        msgpu_ug_destroy(msgpu_ugctx *ctx);
+const char *msgpu_ug_last_error(const msgpu_ugctx *ctx);
+uint64_t    msgpu_ug_error_line(const msgpu_ugctx *ctx); /* after MSGPU_E_FORMAT: the 1-based line */
+int         msgpu_ug_error_file(const msgpu_ugctx *ctx); /* after MSGPU_E_FORMAT / MSGPU_E_IO: 0 or 1 */
+typedef struct msgpu_ug_stats {
+  uint64_t n_records[2];
+  uint64_t n_windows, n_distinct;
+  uint64_t n_solid, n_solid_trimmed; /* rule 2; what rule 4 leaves                                                        */
+  uint64_t n_unitigs, n_unitigs_kept, n_cycles;
+  uint64_t longest_chain;            /* k-mers of the longest unitig                                                       */
+  uint64_t largest_partition;
+  uint64_t n_lost_publications;      /* scalar read-backs that had to fall back to a copy                                  */
+  uint64_t bytes_in[2], bytes_out[2]; /* bytes_out: the all text, the cut text                                            */
+  uint32_t k, min_count, trim, min_length;
+  uint32_t n_tip_rounds, doubling_rounds, n_partitions, reserved;
+  float load_ms, records_ms;         /* host wall, as msgpu_kf_stats                                                       */
+  float bins_ms, extract_ms, sort_ms, runs_ms, select_ms; /* the count, device by events from here on                     */
+  float adjacency_ms;                /* the neighbour bytes: the first fill and the refresh behind every tip round         */
+  float tips_ms;                     /* the tip rounds themselves (walk, apply)                                            */
+  float next_ms;                     /* rule 5's joins                                                                     */
+  float doubling_ms;                 /* pointer doubling, the cycles' minima included                                      */
+  float order_ms;                    /* heads, their sort, the unitig table, coverage                                      */
+  float write_ms;                    /* the bases                                                                          */
+  float copy_ms;                     /* tables and text back to the host                                                   */
+  float host_ms;                     /* host: headers, offsets, the cut text (wall)                                        */
+  float wall_ms;
+} msgpu_ug_stats;
+typedef struct msgpu_ug_round {
+  uint32_t limit, reserved;
+  uint64_t removed;
+  float    tips_ms, adjacency_ms; /* device, by events */
+} msgpu_ug_round;
+typedef struct msgpu_ug_unitig { /* in output order: entry i is the unitig with id i */
+  uint64_t length, coverage;
+  uint64_t first_hi, first_lo;   /* its first k-mer (upper half 0 for k <= 32) */
+  uint64_t offset;               /* of its sequence in the all text */
+  uint32_t cyclic, reserved;
+} msgpu_ug_unitig;
+/* The whole stage.  path_b may be NULL.  flags must be 0.  budget_bytes bounds the count's partition buffers as in
+ * msgpu_kf_run.  Synchronous; both texts are kept in the result. */
+int         msgpu_ug_run(msgpu_ugctx *ctx, const msgpu_ug_params *params, const char *path_a, const char *path_b, uint32_t flags,
+                         uint64_t budget_bytes, msgpu_ug_result **out);
+int         msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out);
+int         msgpu_ug_result_rounds(const msgpu_ug_result *r, const msgpu_ug_round **rounds, uint64_t *n);
+int         msgpu_ug_result_unitigs(const msgpu_ug_result *r, const msgpu_ug_unitig **unitigs, uint64_t *n);
+#define MSGPU_UG_TEXT_ALL 0 /* every record */
+#define MSGPU_UG_TEXT_CUT 1 /* the records with length >= min_length */
+const char *msgpu_ug_result_text(const msgpu_ug_result *r, int which, uint64_t *len);
+void        msgpu_ug_result_free(msgpu_ug_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

@@ -165,6 +165,36 @@ class KfStats(C.Structure):  # msgpu_kf_stats
 KF_TEXT_OUT_A, KF_TEXT_OUT_B, KF_TEXT_REPORT, KF_TEXT_HISTO, KF_TEXT_KMERS = 0, 1, 2, 3, 4
 
 
+class UgParams(C.Structure):  # msgpu_ug_params
+    _fields_ = [("k", C.c_int32), ("min_count", C.c_uint32), ("trim", C.c_int32), ("min_length", C.c_uint32)]
+
+
+class UgStats(C.Structure):  # msgpu_ug_stats
+    _fields_ = ([("n_records", C.c_uint64 * 2)] +
+                [(n, C.c_uint64) for n in ("n_windows", "n_distinct", "n_solid", "n_solid_trimmed", "n_unitigs",
+                                           "n_unitigs_kept", "n_cycles", "longest_chain", "largest_partition",
+                                           "n_lost_publications")] +
+                [("bytes_in", C.c_uint64 * 2), ("bytes_out", C.c_uint64 * 2)] +
+                [(n, C.c_uint32) for n in ("k", "min_count", "trim", "min_length", "n_tip_rounds", "doubling_rounds",
+                                           "n_partitions", "reserved")] +
+                [(n, C.c_float) for n in ("load_ms", "records_ms", "bins_ms", "extract_ms", "sort_ms", "runs_ms", "select_ms",
+                                          "adjacency_ms", "tips_ms", "next_ms", "doubling_ms", "order_ms", "write_ms",
+                                          "copy_ms", "host_ms", "wall_ms")])
+
+
+class UgRound(C.Structure):  # msgpu_ug_round
+    _fields_ = [("limit", C.c_uint32), ("reserved", C.c_uint32), ("removed", C.c_uint64), ("tips_ms", C.c_float),
+                ("adjacency_ms", C.c_float)]
+
+
+class UgUnitig(C.Structure):  # msgpu_ug_unitig
+    _fields_ = [(n, C.c_uint64) for n in ("length", "coverage", "first_hi", "first_lo", "offset")] + [
+        ("cyclic", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+UG_TEXT_ALL, UG_TEXT_CUT = 0, 1
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -382,6 +412,18 @@ SYMBOLS = [
     ("msgpu_kf_result_verdicts", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]),
     ("msgpu_kf_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     ("msgpu_kf_result_free", None, [C.c_void_p]),
+    ("msgpu_ug_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_ug_destroy", None, [C.c_void_p]),
+    ("msgpu_ug_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_ug_error_line", C.c_uint64, [C.c_void_p]),
+    ("msgpu_ug_error_file", C.c_int, [C.c_void_p]),
+    ("msgpu_ug_run", C.c_int, [C.c_void_p, C.POINTER(UgParams), C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
+                               C.POINTER(C.c_void_p)]),
+    ("msgpu_ug_result_stats", C.c_int, [C.c_void_p, C.POINTER(UgStats)]),
+    ("msgpu_ug_result_rounds", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgRound)), C.POINTER(C.c_uint64)]),
+    ("msgpu_ug_result_unitigs", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgUnitig)), C.POINTER(C.c_uint64)]),
+    ("msgpu_ug_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    ("msgpu_ug_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -12,12 +12,13 @@
 //                  abundant set, sorted ascending, and an open-addressing table of indices over it (k_kf_table)
 //   k_kf_verdict   the windows again, each looked up; any hit in either mate sets the pair's byte
 //   k_kf_copy      the surviving records, whole, one wavefront per record, to offsets from a scan of their byte lengths
+// What the short-read unitig assembly (msgpu_unitig.hip) uses as well -- the rolling window, the hash, the partitions, k_kf_bins /
+// k_kf_extract / k_kf_select / k_kf_table, the partitioned count and the sorted gather -- is defined in msgpu_kmer_shared.h;
+// the upload ring, the line starts and the FASTQ check are defined here and declared there.
 //
 // Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 #include <rocprim/block/block_scan.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -26,82 +27,15 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <memory>
 #include <new>
 #include <string>
-#include <vector>
 
-#include "msgpu.h"
+#include "msgpu_kmer_shared.h"
 
 namespace msgpu {
-
-typedef unsigned __int128      kf_u128;
-typedef unsigned long long     kf_ull;
-constexpr uint32_t KF_TILE   = 4096;  // bytes of a file per workgroup in the line kernels (16 per thread)
-constexpr uint32_t KF_BINS   = 4096;  // hash bins the partitions are cut from
-constexpr uint32_t KF_KEEP   = 5;     // a k-mer below this count can never reach the threshold (upper >= 5)
-constexpr uint32_t KF_HIGH   = 10001; // jellyfish histo's last row
-constexpr uint32_t KF_LOWBIN = 1024;  // histogram bins privatised per workgroup
-constexpr uint32_t KF_EMPTY  = 0xffffffffu;
-
-struct KfIn { // the two files as the kernels see them
-  const uint8_t  *buf[2];
-  const uint64_t *ls[2]; // line starts, n_lines + 1 entries: line l is [ls[l], ls[l + 1] - 1)
-  uint64_t        n_pairs;
-  int             k;
-};
-
-// splitmix64's finaliser over both halves of the key
-__device__ inline uint64_t kf_mix(uint64_t lo, uint64_t hi) {
-  uint64_t x = lo ^ (hi * 0x9e3779b97f4a7c15ull);
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-__device__ inline uint64_t kf_hash(uint64_t k) { return kf_mix(k, 0); }
-__device__ inline uint64_t kf_hash(kf_u128 k) { return kf_mix(static_cast<uint64_t>(k), static_cast<uint64_t>(k >> 64)); }
-template <class K> __device__ inline uint32_t kf_bin(K key) { return static_cast<uint32_t>(kf_hash(key) >> 52); } // KF_BINS = 2^12
-__device__ inline uint32_t kf_part(uint32_t bin, uint32_t P) { return (bin * P) >> 12; }
-
-// the rolling window: step() takes one byte of a sequence line and says whether a window ends on it
-template <class K> struct KfRoll {
-  K        fw = 0, rc = 0, mask;
-  uint32_t run = 0, k;
-  int      top;
-  __device__ explicit KfRoll(int k_) : k(static_cast<uint32_t>(k_)), top(2 * (k_ - 1)) {
-    mask = (2 * k_ == static_cast<int>(sizeof(K) * 8)) ? ~static_cast<K>(0) : ((static_cast<K>(1) << (2 * k_)) - 1);
-  }
-  __device__ bool step(uint8_t b, K &key) {
-    const uint32_t u = b & 0xdfu; // case folded
-    if (!(u == 'A' || u == 'C' || u == 'G' || u == 'T')) {
-      run = 0;
-      return false;
-    }
-    const uint32_t c = ((u >> 1) & 3u) ^ ((u >> 2) & 1u); // A 0, C 1, G 2, T 3
-    fw = ((fw << 2) | static_cast<K>(c)) & mask;
-    rc = (rc >> 2) | (static_cast<K>(3u - c) << top);
-    if (++run < k) return false;
-    key = fw < rc ? fw : rc;
-    return true;
-  }
-};
-
-// read t of 2 * n_pairs (file 0 first): its sequence line
-__device__ inline void kf_read(const KfIn &in, uint64_t t, const uint8_t *&s, uint64_t &len) {
-  const int      f = t >= in.n_pairs;
-  const uint64_t r = t - (f ? in.n_pairs : 0);
-  const uint64_t a = in.ls[f][4 * r + 1], e = in.ls[f][4 * r + 2] - 1;
-  s   = in.buf[f] + a;
-  len = e - a;
-}
 
 // 16 bytes at `base` (a multiple of 16; the buffer is padded): bit i = byte i is '\n' and lies inside the file
 __device__ inline uint32_t kf_nl_mask(const uint8_t *buf, uint64_t base, uint64_t size) {
@@ -155,64 +89,6 @@ __global__ __launch_bounds__(256) void k_kf_check(const uint8_t *buf, const uint
   if (wrong) atomicMin(bad, static_cast<kf_ull>(l + 1));
 }
 
-// windows per hash bin
-template <class K> __global__ __launch_bounds__(256) void k_kf_bins(KfIn in, kf_ull *bins) {
-  __shared__ uint32_t h[KF_BINS];
-  for (uint32_t i = threadIdx.x; i < KF_BINS; i += 256) h[i] = 0;
-  __syncthreads();
-  const uint64_t n = 2 * in.n_pairs, stride = static_cast<uint64_t>(gridDim.x) * 256;
-  for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; t < n; t += stride) {
-    const uint8_t *s;
-    uint64_t       len;
-    kf_read(in, t, s, len);
-    KfRoll<K> roll(in.k);
-    K         key;
-    for (uint64_t i = 0; i < len; ++i)
-      if (roll.step(s[i], key)) atomicAdd(&h[kf_bin(key)], 1u);
-  }
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i < KF_BINS; i += 256)
-    if (h[i]) atomicAdd(&bins[i], static_cast<kf_ull>(h[i]));
-}
-
-// the canonical keys of partition p.  Sweep 1 counts the lane's keys; the wavefront reserves one range; sweep 2 walks the
-// 64 reads in step and writes each step's keys side by side.
-template <class K>
-__global__ __launch_bounds__(256) void k_kf_extract(KfIn in, uint32_t P, uint32_t p, K *out, uint64_t cap, kf_ull *cursor) {
-  const uint64_t t = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int      lane = threadIdx.x & 63;
-  const uint8_t *s = nullptr;
-  uint64_t       len = 0;
-  if (t < 2 * in.n_pairs) kf_read(in, t, s, len);
-  uint32_t mine = 0;
-  {
-    KfRoll<K> roll(in.k);
-    K         key;
-    for (uint64_t i = 0; i < len; ++i)
-      if (roll.step(s[i], key) && kf_part(kf_bin(key), P) == p) ++mine;
-  }
-  uint64_t sum = mine, longest = len;
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    longest = max(longest, static_cast<uint64_t>(__shfl_xor(longest, o)));
-  }
-  if (!sum) return; // (the whole wavefront)
-  kf_ull at = 0;
-  if (lane == 0) at = atomicAdd(cursor, static_cast<kf_ull>(sum));
-  at = __shfl(at, 0);
-  KfRoll<K> roll(in.k);
-  for (uint64_t i = 0; i < longest; ++i) {
-    K          key = 0;
-    const bool put = i < len && roll.step(s[i], key) && kf_part(kf_bin(key), P) == p;
-    const uint64_t who = __ballot(put);
-    if (put) {
-      const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
-      if (slot < cap) out[slot] = key;
-    }
-    at += __popcll(who);
-  }
-}
-
 // run lengths -> the bins 1..KF_HIGH
 __global__ __launch_bounds__(256) void k_kf_hist(const uint32_t *cnt, uint32_t n, kf_ull *hist) {
   __shared__ uint32_t h[KF_LOWBIN];
@@ -228,40 +104,11 @@ __global__ __launch_bounds__(256) void k_kf_hist(const uint32_t *cnt, uint32_t n
     if (h[i]) atomicAdd(&hist[i], static_cast<kf_ull>(h[i]));
 }
 
-// the (key, count) with count >= least.  WRITE = false only counts them (into *cursor).
-template <class K, bool WRITE>
-__global__ __launch_bounds__(256) void k_kf_select(const K *keys, const uint32_t *cnt, uint64_t n, uint32_t least, K *out_k,
-                                                   uint32_t *out_c, uint64_t cap, kf_ull *cursor) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int      lane = threadIdx.x & 63;
-  const bool     take = i < n && cnt[i] >= least;
-  const uint64_t who = __ballot(take);
-  if (!who) return;
-  kf_ull at = 0;
-  if (lane == __ffsll(static_cast<long long>(who)) - 1) at = atomicAdd(cursor, static_cast<kf_ull>(__popcll(who)));
-  at = __shfl(at, __ffsll(static_cast<long long>(who)) - 1);
-  if (WRITE && take) {
-    const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
-    if (slot < cap) {
-      out_k[slot] = keys[i];
-      out_c[slot] = cnt[i];
-    }
-  }
-}
-
-// open addressing over the abundant set: a slot holds an index into the sorted keys
-template <class K> __global__ __launch_bounds__(256) void k_kf_table(const K *keys, uint32_t n, uint32_t *slots, uint32_t mask) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  for (uint32_t h = static_cast<uint32_t>(kf_hash(keys[i])) & mask;; h = (h + 1) & mask)
-    if (atomicCAS(&slots[h], KF_EMPTY, i) == KF_EMPTY) return; // (the table has at least 2 n slots)
-}
-
 template <class K>
 __global__ __launch_bounds__(256) void k_kf_verdict(KfIn in, const K *keys, const uint32_t *slots, uint32_t mask,
                                                     uint8_t *verdict) {
   const uint64_t t = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (t >= 2 * in.n_pairs) return;
+  if (t >= in.n_reads) return;
   const uint8_t *s;
   uint64_t       len;
   kf_read(in, t, s, len);
@@ -269,13 +116,9 @@ __global__ __launch_bounds__(256) void k_kf_verdict(KfIn in, const K *keys, cons
   K         key;
   for (uint64_t i = 0; i < len; ++i) {
     if (!roll.step(s[i], key)) continue;
-    for (uint32_t h = static_cast<uint32_t>(kf_hash(key)) & mask;; h = (h + 1) & mask) {
-      const uint32_t j = slots[h];
-      if (j == KF_EMPTY) break;
-      if (keys[j] == key) {
-        verdict[t >= in.n_pairs ? t - in.n_pairs : t] = 1;
-        return;
-      }
+    if (kf_find(keys, slots, mask, key) != KF_EMPTY) {
+      verdict[t >= in.n_first ? t - in.n_first : t] = 1;
+      return;
     }
   }
 }
@@ -298,110 +141,12 @@ __global__ __launch_bounds__(256) void k_kf_copy(const uint8_t *buf, const uint6
   for (uint64_t i = threadIdx.x & 63; i < n; i += 64) out[o + i] = buf[a + i];
 }
 
-} // namespace msgpu
-
-using namespace msgpu;
-
-// ---- host side -----------------------------------------------------------------------------------------------------
-
-struct msgpu_kfctx {
-  int         device = 0;
-  hipStream_t stream = nullptr;
-  char        err[384] = {0};
-  uint64_t    err_line = 0;
-  int         err_file = 0;
-};
-
-struct msgpu_kf_result {
-  msgpu_kf_stats        stats{};
-  std::vector<uint64_t> hist_a, hist_f, key_hi, key_lo;
-  std::vector<uint32_t> count;
-  std::vector<uint8_t>  verdict;
-  char                 *out[2] = {nullptr, nullptr}; // page-locked
-  uint64_t              out_len[2] = {0, 0};
-  std::string           report, histo, dump;
-  bool                  dump_made = false;
-  ~msgpu_kf_result() {
-    for (char *p : out)
-      if (p) (void)hipHostFree(p);
-  }
-};
-
-namespace {
-
-int kfail(msgpu_kfctx *c, int code, const char *what, hipError_t e) {
-  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-  return code;
-}
-#define KHIP(c, expr)                                                                                                  \
-  do {                                                                                                                 \
-    hipError_t _e = (expr);                                                                                            \
-    if (_e != hipSuccess) return kfail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
-  } while (0)
-
-struct KfDev { // device memory freed on every way out of msgpu_kf_run
-  std::vector<void *> p;
-  ~KfDev() {
-    for (void *x : p) (void)hipFree(x);
-  }
-  template <class T> hipError_t get(T **out, size_t count) {
-    void      *m = nullptr;
-    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(m);
-    *out = static_cast<T *>(m);
-    return e;
-  }
-  void drop(void *x) {
-    auto it = std::find(p.begin(), p.end(), x);
-    if (it != p.end()) p.erase(it);
-    (void)hipFree(x);
-  }
-};
-
-struct KfClock { // device steps by event pairs, summed per step after the run's last synchronisation
-  struct Span {
-    hipEvent_t a, b;
-    float     *acc;
-  };
-  std::vector<Span> spans;
-  hipStream_t       st;
-  ~KfClock() {
-    for (auto &s : spans) {
-      (void)hipEventDestroy(s.a);
-      (void)hipEventDestroy(s.b);
-    }
-  }
-  hipError_t begin(float *acc) {
-    Span       s{nullptr, nullptr, acc};
-    hipError_t e = hipEventCreate(&s.a);
-    if (e == hipSuccess) e = hipEventCreate(&s.b);
-    if (e == hipSuccess) e = hipEventRecord(s.a, st);
-    spans.push_back(s);
-    return e;
-  }
-  hipError_t end() { return hipEventRecord(spans.back().b, st); }
-  void       collect() { // (after a synchronisation)
-    for (auto &s : spans) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) *s.acc += ms;
-      (void)hipEventDestroy(s.a);
-      (void)hipEventDestroy(s.b);
-    }
-    spans.clear();
-  }
-};
-
-struct KfFile {
-  uint8_t  *d = nullptr;
-  uint64_t  size = 0, n_lines = 0;
-  uint64_t *ls = nullptr;
-  bool      open_end = false; // the last line has no '\n'
-};
+// ---- host side, shared with msgpu_unitig.hip (msgpu_kmer_shared.h) ---------------------------------------------------
 
 constexpr size_t KF_SLOT = size_t(16) << 20; // page-locked ring: two slots
 
 // mmap -> page-locked ring -> device; the host keeps no copy
-int kf_upload(msgpu_kfctx *c, KfDev &D, const char *path, int which, KfFile &f) {
+int kf_upload(KfCtx *c, KfDev &D, const char *path, int which, KfFile &f) {
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   struct stat st;
   if (fd < 0 || fstat(fd, &st) != 0) {
@@ -466,7 +211,7 @@ int kf_upload(msgpu_kfctx *c, KfDev &D, const char *path, int which, KfFile &f) 
 }
 
 // the line starts of a file on the device
-int kf_lines(msgpu_kfctx *c, KfDev &D, KfFile &f) {
+int kf_lines(KfCtx *c, KfDev &D, KfFile &f) {
   hipStream_t    st = c->stream;
   const uint32_t tiles = static_cast<uint32_t>((f.size + KF_TILE - 1) / KF_TILE);
   uint32_t      *d_cnt;
@@ -497,12 +242,65 @@ int kf_lines(msgpu_kfctx *c, KfDev &D, KfFile &f) {
   return MSGPU_OK;
 }
 
-int kf_format_error(msgpu_kfctx *c, int which, uint64_t line, const char *what) {
+int kf_format_error(KfCtx *c, int which, uint64_t line, const char *what) {
   c->err_file = which;
   c->err_line = line;
   snprintf(c->err, sizeof(c->err), "file %d line %llu: %s", which, static_cast<kf_ull>(line), what);
   return MSGPU_E_FORMAT;
 }
+
+// the line starts of every file and the FASTQ rules, file 0 first
+int kf_records(KfCtx *c, KfDev &D, KfFile *F, int n_files) {
+  kf_ull *d_bad;
+  KHIP(c, D.get(&d_bad, 1));
+  for (int f = 0; f < n_files; ++f) {
+    int rc = kf_lines(c, D, F[f]);
+    if (rc != MSGPU_OK) return rc;
+    kf_ull bad = ~0ull;
+    KHIP(c, hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, c->stream));
+    if (F[f].n_lines)
+      hipLaunchKernelGGL(k_kf_check, dim3(static_cast<uint32_t>((F[f].n_lines + 255) / 256)), dim3(256), 0, c->stream, F[f].d,
+                         F[f].ls, F[f].n_lines, d_bad);
+    KHIP(c, hipGetLastError());
+    KHIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    KHIP(c, hipStreamSynchronize(c->stream));
+    if (bad != ~0ull) {
+      const char *what[4] = {"a record's first line must start with '@'", "", "a record's third line must start with '+'",
+                             "the quality line and the sequence line differ in length"};
+      return kf_format_error(c, f, bad, what[(bad - 1) & 3]);
+    }
+    if (F[f].n_lines & 3) return kf_format_error(c, f, F[f].n_lines + 1, "the file ends inside a record");
+    if ((F[f].n_lines >> 2) >= (1ull << 32)) {
+      c->err_file = f;
+      snprintf(c->err, sizeof(c->err), "file %d has %llu records; the limit is 2^32 - 1", f, static_cast<kf_ull>(F[f].n_lines >> 2));
+      return MSGPU_E_ARG;
+    }
+  }
+  return MSGPU_OK;
+}
+
+} // namespace msgpu
+
+using namespace msgpu;
+
+struct msgpu_kfctx : msgpu::KfCtx {};
+
+struct msgpu_kf_result {
+  msgpu_kf_stats        stats{};
+  std::vector<uint64_t> hist_a, hist_f, key_hi, key_lo;
+  std::vector<uint32_t> count;
+  std::vector<uint8_t>  verdict;
+  char                 *out[2] = {nullptr, nullptr}; // page-locked
+  uint64_t              out_len[2] = {0, 0};
+  std::string           report, histo, dump;
+  bool                  dump_made = false;
+  ~msgpu_kf_result() {
+    for (char *p : out)
+      if (p) (void)hipHostFree(p);
+  }
+};
+
+namespace {
 
 template <class K> void kf_split(const K *keys, size_t n, std::vector<uint64_t> &hi, std::vector<uint64_t> &lo);
 template <> void kf_split<uint64_t>(const uint64_t *keys, size_t n, std::vector<uint64_t> &hi, std::vector<uint64_t> &lo) {
@@ -526,44 +324,26 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
   hipStream_t     st = c->stream;
   KfClock         clock;
   clock.st = st;
-  const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_pairs, k};
   const uint64_t n_reads = 2 * n_pairs;
+  const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_pairs, n_reads, k};
   const uint32_t read_grid = static_cast<uint32_t>((n_reads + 255) / 256);
 
   // ---- windows per hash bin, the partitions
-  kf_ull *d_bins, *d_hist, *d_cur;
-  KHIP(c, D.get(&d_bins, KF_BINS));
+  kf_ull *d_hist, *d_cur;
   KHIP(c, D.get(&d_hist, KF_HIGH + 1));
   KHIP(c, D.get(&d_cur, 1));
-  KHIP(c, hipMemsetAsync(d_bins, 0, KF_BINS * 8, st));
   KHIP(c, hipMemsetAsync(d_hist, 0, (KF_HIGH + 1) * 8, st));
-  KHIP(c, clock.begin(&S.bins_ms));
-  if (n_reads) hipLaunchKernelGGL(k_kf_bins<K>, dim3(std::min<uint32_t>(read_grid, 4096)), dim3(256), 0, st, in, d_bins);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
-  std::vector<kf_ull> bins(KF_BINS);
-  KHIP(c, hipMemcpyAsync(bins.data(), d_bins, KF_BINS * 8, hipMemcpyDeviceToHost, st));
-  KHIP(c, hipStreamSynchronize(st));
-  std::vector<uint64_t> pre(KF_BINS + 1, 0);
-  for (uint32_t b = 0; b < KF_BINS; ++b) pre[b + 1] = pre[b] + bins[b];
+  std::vector<uint64_t> pre;
+  int                   rc = kf_bin_prefix<K>(c, D, clock, in, &S.bins_ms, pre);
+  if (rc != MSGPU_OK) return rc;
   S.n_windows = pre[KF_BINS];
   size_t free_b = 0, total_b = 0;
   KHIP(c, hipMemGetInfo(&free_b, &total_b));
   const uint64_t out_bytes = F[0].size + F[1].size + 2; // the outputs are no larger than the inputs
   const uint64_t per_key = 2 * sizeof(K) + 4;           // two key buffers and the run lengths
   if (!budget) budget = free_b > out_bytes ? (free_b - out_bytes) / 2 : 0;
-  auto first_bin = [](uint32_t p, uint32_t P) { return static_cast<uint32_t>((uint64_t(p) * KF_BINS + P - 1) / P); };
-  uint32_t P = 0;
-  uint64_t largest = 0;
-  for (uint32_t q = 1; q <= KF_BINS && !P; ++q) {
-    uint64_t m = 0;
-    for (uint32_t p = 0; p < q; ++p) m = std::max(m, pre[first_bin(p + 1, q)] - pre[first_bin(p, q)]);
-    if (m < (1ull << 31) && m * per_key <= budget) {
-      P       = q;
-      largest = m;
-    }
-  }
-  if (!P || largest * per_key + out_bytes > free_b) {
+  const KfParts parts = kf_pick_partitions(pre, per_key, budget);
+  if (!parts.P || parts.largest * per_key + out_bytes > free_b) {
     snprintf(c->err, sizeof(c->err),
              "%llu windows of %zu-byte keys need %llu bytes per window in partition buffers (budget %llu bytes, %u hash "
              "bins) next to %llu bytes of output; %zu bytes of device memory are free",
@@ -571,93 +351,24 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
              KF_BINS, static_cast<kf_ull>(out_bytes), free_b);
     return MSGPU_E_NOMEM;
   }
-  S.n_partitions = P;
-  S.largest_partition = largest;
+  S.n_partitions = parts.P;
+  S.largest_partition = parts.largest;
 
   // ---- count: per partition extract, sort, run lengths, histogram, candidates
-  K        *d_a, *d_b;
-  uint32_t *d_rl, *d_nruns;
-  KHIP(c, D.get(&d_a, largest));
-  KHIP(c, D.get(&d_b, largest));
-  KHIP(c, D.get(&d_rl, largest));
-  KHIP(c, D.get(&d_nruns, 1));
-  size_t need_sort = 0, need_rle = 0;
-  {
-    rocprim::double_buffer<K> db(d_a, d_b);
-    KHIP(c, rocprim::radix_sort_keys(nullptr, need_sort, db, largest, 0, 2 * k, st));
-    KHIP(c, rocprim::run_length_encode(nullptr, need_rle, d_a, static_cast<unsigned int>(largest), d_b, d_rl, d_nruns, st));
-  }
-  const size_t tmp_bytes = std::max(need_sort, need_rle);
-  uint8_t     *d_tmp;
-  KHIP(c, D.get(&d_tmp, tmp_bytes));
-  struct Chunk {
-    K        *k;
-    uint32_t *c;
-    uint64_t  n;
-  };
-  std::vector<Chunk> chunks;
-  for (uint32_t p = 0; p < P; ++p) {
-    const uint64_t n = pre[first_bin(p + 1, P)] - pre[first_bin(p, P)];
-    if (!n) continue;
-    KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
-    KHIP(c, clock.begin(&S.extract_ms));
-    hipLaunchKernelGGL(k_kf_extract<K>, dim3(read_grid), dim3(256), 0, st, in, P, p, d_a, n, d_cur);
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
-    rocprim::double_buffer<K> db(d_a, d_b);
-    size_t                    tb = tmp_bytes;
-    KHIP(c, clock.begin(&S.sort_ms));
-    KHIP(c, rocprim::radix_sort_keys(d_tmp, tb, db, n, 0, 2 * k, st));
-    KHIP(c, clock.end());
-    K *sorted = db.current(), *uniq = db.alternate();
-    tb = tmp_bytes;
-    KHIP(c, clock.begin(&S.runs_ms));
-    KHIP(c, rocprim::run_length_encode(d_tmp, tb, sorted, static_cast<unsigned int>(n), uniq, d_rl, d_nruns, st));
-    KHIP(c, clock.end());
-    uint32_t runs = 0;
-    kf_ull   written = 0;
-    KHIP(c, hipMemcpyAsync(&runs, d_nruns, 4, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipMemcpyAsync(&written, d_cur, 8, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipStreamSynchronize(st));
-    if (written != n) { // the two window passes disagree: never seen; a result built on it would be wrong
-      snprintf(c->err, sizeof(c->err), "partition %u: %llu keys extracted where %llu were counted", p, written,
-               static_cast<kf_ull>(n));
-      return MSGPU_E_STATE;
-    }
-    S.n_distinct += runs;
-    const uint32_t run_grid = (runs + 255) / 256;
-    KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
+  std::vector<KfChunk<K>> chunks;
+  auto                    histogram = [&](const uint32_t *d_rl, uint32_t runs) -> int {
     KHIP(c, clock.begin(&S.hist_ms));
-    hipLaunchKernelGGL(k_kf_hist, dim3(std::min<uint32_t>(run_grid, 2048)), dim3(256), 0, st, d_rl, runs, d_hist);
+    hipLaunchKernelGGL(k_kf_hist, dim3(std::min<uint32_t>((runs + 255) / 256, 2048)), dim3(256), 0, st, d_rl, runs, d_hist);
     KHIP(c, hipGetLastError());
     KHIP(c, clock.end());
-    KHIP(c, clock.begin(&S.select_ms));
-    hipLaunchKernelGGL((k_kf_select<K, false>), dim3(run_grid), dim3(256), 0, st, uniq, d_rl, runs, KF_KEEP, nullptr, nullptr,
-                       0, d_cur);
-    KHIP(c, hipGetLastError());
-    kf_ull kept = 0;
-    KHIP(c, hipMemcpyAsync(&kept, d_cur, 8, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipStreamSynchronize(st));
-    if (kept) {
-      Chunk ch{nullptr, nullptr, kept};
-      KHIP(c, D.get(&ch.k, kept));
-      KHIP(c, D.get(&ch.c, kept));
-      KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
-      hipLaunchKernelGGL((k_kf_select<K, true>), dim3(run_grid), dim3(256), 0, st, uniq, d_rl, runs, KF_KEEP, ch.k, ch.c, kept,
-                         d_cur);
-      KHIP(c, hipGetLastError());
-      chunks.push_back(ch);
-      S.n_candidates += kept;
-    }
-    KHIP(c, clock.end());
-  }
+    return MSGPU_OK;
+  };
+  rc = kf_count<K>(c, D, clock, in, pre, parts, k, KF_KEEP, KfCountMs{&S.extract_ms, &S.sort_ms, &S.runs_ms, &S.select_ms}, d_cur,
+                   histogram, chunks, S.n_distinct, S.n_candidates);
+  if (rc != MSGPU_OK) return rc;
   std::vector<kf_ull> hist(KF_HIGH + 1);
   KHIP(c, hipMemcpyAsync(hist.data(), d_hist, (KF_HIGH + 1) * 8, hipMemcpyDeviceToHost, st));
   KHIP(c, hipStreamSynchronize(st));
-  D.drop(d_a);
-  D.drop(d_b);
-  D.drop(d_rl);
-  D.drop(d_tmp);
 
   // ---- threshold (host: at most 10001 rows)
   for (uint32_t a = 1; a <= KF_HIGH; ++a)
@@ -666,7 +377,7 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
       res->hist_f.push_back(hist[a]);
     }
   S.n_hist_rows = res->hist_a.size();
-  int rc = msgpu_kf_threshold(res->hist_a.data(), res->hist_f.data(), res->hist_a.size(), &S.q1, &S.q3, &S.upper);
+  rc = msgpu_kf_threshold(res->hist_a.data(), res->hist_f.data(), res->hist_a.size(), &S.q1, &S.q3, &S.upper);
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "degenerate histogram (%llu rows, q1 %lld, q3 %lld): no abundance threshold",
              static_cast<kf_ull>(S.n_hist_rows), static_cast<long long>(S.q1), static_cast<long long>(S.q3));
@@ -675,55 +386,19 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
 
   // ---- the abundant set, ascending, and the table over it
   const uint32_t least = static_cast<uint32_t>(std::min<int64_t>(S.upper, 0xffffffffll));
-  KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
   KHIP(c, clock.begin(&S.select_ms));
-  for (const Chunk &ch : chunks)
-    hipLaunchKernelGGL((k_kf_select<K, false>), dim3(static_cast<uint32_t>((ch.n + 255) / 256)), dim3(256), 0, st, ch.k, ch.c,
-                       ch.n, least, nullptr, nullptr, 0, d_cur);
-  KHIP(c, hipGetLastError());
   kf_ull n_ab = 0;
-  KHIP(c, hipMemcpyAsync(&n_ab, d_cur, 8, hipMemcpyDeviceToHost, st));
-  KHIP(c, hipStreamSynchronize(st));
+  rc = kf_count_selected<K>(c, chunks, least, d_cur, n_ab);
+  if (rc != MSGPU_OK) return rc;
   if (n_ab >= (1ull << 31)) {
     snprintf(c->err, sizeof(c->err), "%llu abundant k-mers; the limit is 2^31 - 1", n_ab);
     return MSGPU_E_ARG;
   }
   S.n_abundant = n_ab;
-  K        *d_abk = nullptr, *d_abk_in;
-  uint32_t *d_abc = nullptr, *d_abc_in;
-  KHIP(c, D.get(&d_abk, n_ab));
-  KHIP(c, D.get(&d_abc, n_ab));
-  if (n_ab) {
-    KHIP(c, D.get(&d_abk_in, n_ab));
-    KHIP(c, D.get(&d_abc_in, n_ab));
-    KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
-    for (const Chunk &ch : chunks)
-      hipLaunchKernelGGL((k_kf_select<K, true>), dim3(static_cast<uint32_t>((ch.n + 255) / 256)), dim3(256), 0, st, ch.k,
-                         ch.c, ch.n, least, d_abk_in, d_abc_in, n_ab, d_cur);
-    KHIP(c, hipGetLastError());
-    size_t need = 0;
-    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, d_abk_in, d_abk, d_abc_in, d_abc, n_ab, 0, 2 * k, st));
-    uint8_t *tmp;
-    KHIP(c, D.get(&tmp, need));
-    KHIP(c, rocprim::radix_sort_pairs(tmp, need, d_abk_in, d_abk, d_abc_in, d_abc, n_ab, 0, 2 * k, st));
-    KHIP(c, hipStreamSynchronize(st));
-    D.drop(tmp);
-    D.drop(d_abk_in);
-    D.drop(d_abc_in);
-  }
-  for (const Chunk &ch : chunks) {
-    D.drop(ch.k);
-    D.drop(ch.c);
-  }
-  uint32_t slots_n = 64;
-  while (slots_n < 2 * n_ab) slots_n <<= 1;
-  uint32_t *d_slots;
-  KHIP(c, D.get(&d_slots, slots_n));
-  KHIP(c, hipMemsetAsync(d_slots, 0xff, slots_n * 4ull, st));
-  if (n_ab)
-    hipLaunchKernelGGL(k_kf_table<K>, dim3(static_cast<uint32_t>((n_ab + 255) / 256)), dim3(256), 0, st, d_abk,
-                       static_cast<uint32_t>(n_ab), d_slots, slots_n - 1);
-  KHIP(c, hipGetLastError());
+  K        *d_abk = nullptr;
+  uint32_t *d_abc = nullptr, *d_slots = nullptr, slots_n = 0;
+  rc = kf_gather_sorted<K>(c, D, chunks, least, n_ab, k, d_cur, &d_abk, &d_abc, &d_slots, &slots_n);
+  if (rc != MSGPU_OK) return rc;
   KHIP(c, clock.end());
 
   // ---- verdicts
@@ -889,30 +564,9 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
 
   // ---- records: line starts, the format rules
   const auto r0 = std::chrono::steady_clock::now();
-  kf_ull    *d_bad;
-  KHIP(c, D.get(&d_bad, 1));
-  for (int f = 0; f < 2; ++f) {
-    int rc = kf_lines(c, D, F[f]);
+  {
+    const int rc = kf_records(c, D, F, 2);
     if (rc != MSGPU_OK) return rc;
-    kf_ull bad = ~0ull;
-    KHIP(c, hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, c->stream));
-    if (F[f].n_lines)
-      hipLaunchKernelGGL(k_kf_check, dim3(static_cast<uint32_t>((F[f].n_lines + 255) / 256)), dim3(256), 0, c->stream, F[f].d,
-                         F[f].ls, F[f].n_lines, d_bad);
-    KHIP(c, hipGetLastError());
-    KHIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
-    KHIP(c, hipStreamSynchronize(c->stream));
-    if (bad != ~0ull) {
-      const char *what[4] = {"a record's first line must start with '@'", "", "a record's third line must start with '+'",
-                             "the quality line and the sequence line differ in length"};
-      return kf_format_error(c, f, bad, what[(bad - 1) & 3]);
-    }
-    if (F[f].n_lines & 3) return kf_format_error(c, f, F[f].n_lines + 1, "the file ends inside a record");
-    if ((F[f].n_lines >> 2) >= (1ull << 32)) {
-      c->err_file = f;
-      snprintf(c->err, sizeof(c->err), "file %d has %llu records; the limit is 2^32 - 1", f, static_cast<kf_ull>(F[f].n_lines >> 2));
-      return MSGPU_E_ARG;
-    }
   }
   if (F[0].n_lines != F[1].n_lines) {
     const int f = F[0].n_lines < F[1].n_lines ? 0 : 1;

@@ -1,0 +1,860 @@
+// msgpu_unitig.hip -- the short-read unitig assembly (include/msgpu.h, "short-read unitig assembly").
+//
+// The count is the k-mer filter's (msgpu_kmer_shared.h) with least = min_count and no histogram: the solid k-mers come out
+// as one ascending key array with their counts and an open-addressing table of indices over it.  A k-mer is its rank r in
+// that array, an oriented node is 2 r + strand (strand 0: the canonical string, strand 1: its reverse complement; a
+// self-complementary k-mer has strand 0 only).
+//   k_ug_adj     one byte per k-mer: which of the 4 successors (bits 0..3) and 4 predecessors (bits 4..7) of the canonical
+//                string are alive.  The first fill makes 8 look-ups; behind a tip round only the bits still set are asked again
+//   k_ug_tips    a thread per dead-end oriented node walks at most `limit` nodes, one look-up per step; a tip's k-mers are
+//                marked in an array of their own, so the round sees a snapshot
+//   k_ug_apply   marks -> alive; the number removed goes into the scalar block, read back by the publication protocol
+//   k_ug_next    rule 5: next[o] = the node o is joined to.  prev(o) = next[o ^ 1] ^ 1: the mirror chain is the same joins
+//   k_ug_double  pointer doubling towards the chain head: ptr[o] and the distance from it, ping-pong buffers.  A round counts
+//                the nodes that do not point at a head yet; when that number stops falling, what is left lies on cycles
+//   k_ug_cyc_*   cycles: a min-reduction by doubling finds the smallest oriented node, the cycle is cut in front of it
+//                and doubled again as a linear chain
+//   k_ug_heads   the heads that are emitted (rule 5's mirror choice), with their first k-mer; rocPRIM sorts them by it
+//   k_ug_cover   coverage: 64-bit atomics per unitig
+//   k_ug_write   every node writes one base at offset + distance + k - 1, the head writes its k bases and the '\n'
+// No kernel loops over a unitig or over rounds: the longest loops are `limit` <= trim steps (k_ug_tips) and k bases.
+// Kernel rules: vector stores and vector atomics only; no inline asm.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <deque>
+#include <memory>
+#include <new>
+#include <string>
+
+#include "msgpu_internal.h"
+#include "msgpu_kmer_shared.h"
+
+namespace msgpu {
+
+constexpr uint32_t UG_NONE = 0xffffffffu;
+
+template <class K> struct UgGraph { // the solid set as the kernels see it
+  const K        *keys;             // ascending
+  const uint32_t *slots;            // the table over them
+  uint32_t        mask, n;
+  int             k, top;           // top = 2 (k - 1)
+  K               kmask;
+};
+
+// the 2-bit groups of a word in reverse order
+__device__ inline uint64_t ug_rev2(uint64_t x) {
+  x = __brevll(x);
+  return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+}
+__device__ inline uint64_t ug_rc(uint64_t x, int k) { return (~ug_rev2(x)) >> (64 - 2 * k); }
+__device__ inline kf_u128 ug_rc(kf_u128 x, int k) {
+  const kf_u128 f = (static_cast<kf_u128>(ug_rev2(static_cast<uint64_t>(x))) << 64) | ug_rev2(static_cast<uint64_t>(x >> 64));
+  return (~f) >> (128 - 2 * k);
+}
+__device__ inline uint32_t ug_rev4(uint32_t b) { return ((b & 1) << 3) | ((b & 2) << 1) | ((b & 4) >> 1) | ((b & 8) >> 3); }
+
+template <class K> __device__ inline K ug_seq(const UgGraph<K> &g, uint32_t o) {
+  const K x = g.keys[o >> 1];
+  return (o & 1) ? ug_rc(x, g.k) : x;
+}
+// the oriented node of the string t, or UG_NONE when its k-mer is not in the set
+template <class K> __device__ inline uint32_t ug_node(const UgGraph<K> &g, K t) {
+  const K        r = ug_rc(t, g.k);
+  const uint32_t j = kf_find(g.keys, g.slots, g.mask, t < r ? t : r);
+  return j == KF_EMPTY ? UG_NONE : 2 * j + (t > r ? 1u : 0u);
+}
+template <class K> __device__ inline K ug_succ(const UgGraph<K> &g, K s, uint32_t c) { return ((s << 2) | static_cast<K>(c)) & g.kmask; }
+template <class K> __device__ inline K ug_pred(const UgGraph<K> &g, K s, uint32_t c) { return (s >> 2) | (static_cast<K>(c) << g.top); }
+// the successor / predecessor bits of an oriented node from its k-mer's byte: the reverse strand's successor by base c is
+// the mirror of the canonical string's predecessor by base 3 - c
+__device__ inline uint32_t ug_out(uint32_t byte, uint32_t o) { return (o & 1) ? ug_rev4(byte >> 4) : (byte & 0xfu); }
+__device__ inline uint32_t ug_in(uint32_t byte, uint32_t o) { return (o & 1) ? ug_rev4(byte & 0xfu) : (byte >> 4); }
+
+template <class K, bool FIRST>
+__global__ __launch_bounds__(256) void k_ug_adj(UgGraph<K> g, const uint8_t *alive, uint8_t *adj) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= g.n) return;
+  if (!alive[r]) {
+    adj[r] = 0;
+    return;
+  }
+  const K        s = g.keys[r];
+  const uint32_t ask = FIRST ? 0xffu : adj[r];
+  uint32_t       b = 0;
+  for (uint32_t c = 0; c < 4; ++c) {
+    if (ask & (1u << c)) {
+      const uint32_t t = ug_node(g, ug_succ(g, s, c));
+      if (t != UG_NONE && alive[t >> 1]) b |= 1u << c;
+    }
+    if (ask & (16u << c)) {
+      const uint32_t t = ug_node(g, ug_pred(g, s, c));
+      if (t != UG_NONE && alive[t >> 1]) b |= 16u << c;
+    }
+  }
+  adj[r] = static_cast<uint8_t>(b);
+}
+
+// rule 4, one round: alive / adj are the snapshot, mark receives the tips' k-mers
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_tips(UgGraph<K> g, const uint8_t *alive, const uint8_t *adj, uint32_t limit, uint8_t *mark) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= 2ull * g.n) return;
+  const uint32_t o = static_cast<uint32_t>(i);
+  if (!alive[o >> 1] || ug_in(adj[o >> 1], o)) return;
+  const K first = ug_seq(g, o);
+  if ((o & 1) && first == g.keys[o >> 1]) return; // a self-complementary k-mer is one node
+  K        s = first;
+  uint32_t cur = o, len = 1;
+  bool     tip = false;
+  for (;;) { // at most `limit` turns
+    const uint32_t out = ug_out(adj[cur >> 1], cur);
+    if (__popc(out) != 1) break;
+    const K        ts = ug_succ(g, s, static_cast<uint32_t>(__ffs(out)) - 1);
+    const uint32_t t = ug_node(g, ts);
+    if (t == UG_NONE) break; // (the byte said it is there)
+    if (__popc(ug_in(adj[t >> 1], t)) >= 2) {
+      tip = true;
+      break;
+    }
+    if (len == limit) break;
+    s   = ts;
+    cur = t;
+    ++len;
+  }
+  if (!tip) return;
+  s   = first;
+  cur = o;
+  for (uint32_t j = 0;; ++j) { // the same `len` nodes again
+    mark[cur >> 1] = 1;
+    if (j + 1 == len) break;
+    s   = ug_succ(g, s, static_cast<uint32_t>(__ffs(ug_out(adj[cur >> 1], cur))) - 1);
+    cur = ug_node(g, s);
+    if (cur == UG_NONE) break;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ug_apply(uint32_t n, uint8_t *alive, uint8_t *mark, kf_ull *removed) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  const bool     go = r < n && mark[r];
+  if (go) {
+    alive[r] = 0;
+    mark[r]  = 0;
+  }
+  const uint64_t who = __ballot(go);
+  if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(removed, static_cast<kf_ull>(__popcll(who)));
+}
+
+// an oriented node that exists: its k-mer is alive, and strand 1 only where the k-mer is not its own reverse complement
+template <class K> __device__ inline bool ug_valid(const UgGraph<K> &g, const uint8_t *alive, uint32_t o, K s) {
+  return alive[o >> 1] && !((o & 1) && s == g.keys[o >> 1]);
+}
+
+// rule 5's joins
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_next(UgGraph<K> g, const uint8_t *alive, const uint8_t *adj, uint32_t *next) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= 2ull * g.n) return;
+  const uint32_t o = static_cast<uint32_t>(i);
+  uint32_t       nx = UG_NONE;
+  if (alive[o >> 1]) {
+    const K        s = ug_seq(g, o);
+    const uint32_t out = ug_out(adj[o >> 1], o);
+    if (s != ug_rc(s, g.k) && __popc(out) == 1) {
+      const K        ts = ug_succ(g, s, static_cast<uint32_t>(__ffs(out)) - 1);
+      const uint32_t t = ug_node(g, ts);
+      if (t != UG_NONE && (t >> 1) != (o >> 1) && ts != ug_rc(ts, g.k) && __popc(ug_in(adj[t >> 1], t)) == 1) nx = t;
+    }
+  }
+  next[o] = nx;
+}
+
+// ptr = the previous node (a head points at itself, a node that does not exist at UG_NONE), dist = 1 (a head: 0)
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_chain_init(UgGraph<K> g, const uint8_t *alive, const uint32_t *next, uint32_t *ptr,
+                                                       uint32_t *dist) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= 2ull * g.n) return;
+  const uint32_t o = static_cast<uint32_t>(i);
+  const bool     valid = alive[o >> 1] && ug_valid(g, alive, o, ug_seq(g, o));
+  const uint32_t back = next[o ^ 1];
+  ptr[o]  = !valid ? UG_NONE : (back == UG_NONE ? o : (back ^ 1));
+  dist[o] = (valid && back != UG_NONE) ? 1u : 0u;
+}
+
+// one round of pointer doubling; *open counts the nodes that do not point at a head behind it
+__global__ __launch_bounds__(256) void k_ug_double(uint64_t n2, const uint32_t *next, const uint32_t *ptr_in, const uint32_t *dist_in,
+                                                   uint32_t *ptr_out, uint32_t *dist_out, kf_ull *open) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  bool           is_open = false;
+  if (i < n2) {
+    const uint32_t o = static_cast<uint32_t>(i);
+    uint32_t       q = ptr_in[o], d = dist_in[o];
+    if (q != UG_NONE && next[q ^ 1] != UG_NONE) { // q is no head
+      d += dist_in[q];
+      q = ptr_in[q];
+      is_open = next[q ^ 1] != UG_NONE;
+    }
+    ptr_out[o]  = q;
+    dist_out[o] = d;
+  }
+  const uint64_t who = __ballot(is_open);
+  if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(open, static_cast<kf_ull>(__popcll(who)));
+}
+
+// what still points at no head lies on a cycle: back = the previous node, low = the node itself
+__global__ __launch_bounds__(256) void k_ug_cyc_init(uint64_t n2, const uint32_t *next, const uint32_t *ptr, uint8_t *cyc,
+                                                     uint32_t *back, uint32_t *low) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n2) return;
+  const uint32_t o = static_cast<uint32_t>(i), q = ptr[o];
+  const bool     on = q != UG_NONE && next[q ^ 1] != UG_NONE;
+  cyc[o]  = on;
+  back[o] = on ? (next[o ^ 1] ^ 1) : UG_NONE;
+  low[o]  = o;
+}
+
+// one round of the min-reduction: low = the smallest oriented node (as a 2k-bit number) of the 2^round nodes behind
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_cyc_min(UgGraph<K> g, const uint8_t *cyc, const uint32_t *back_in, const uint32_t *low_in,
+                                                    uint32_t *back_out, uint32_t *low_out) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= 2ull * g.n) return;
+  const uint32_t o = static_cast<uint32_t>(i);
+  if (!cyc[o]) return;
+  const uint32_t q = back_in[o], a = low_in[o], b = low_in[q];
+  low_out[o]  = (a == b || ug_seq(g, a) < ug_seq(g, b)) ? a : b;
+  back_out[o] = back_in[q];
+}
+
+// the cycle is cut in front of its smallest node, which becomes a head (low[head] then holds the node in front of it, the
+// cut chain's last: the mirror cycle is cut at its own smallest node, not at the mirror of this one); its nodes start the
+// doubling again
+__global__ __launch_bounds__(256) void k_ug_cyc_cut(uint64_t n2, const uint8_t *cyc, uint32_t *low, uint32_t *next, uint32_t *ptr,
+                                                    uint32_t *dist) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n2) return;
+  const uint32_t o = static_cast<uint32_t>(i);
+  if (!cyc[o]) return;
+  const bool head = low[o] == o;
+  ptr[o]  = head ? o : (next[o ^ 1] ^ 1);
+  dist[o] = head ? 0u : 1u;
+  if (head) { // (only this thread reads next[o ^ 1] and low[o])
+    low[o]      = next[o ^ 1] ^ 1;
+    next[o ^ 1] = UG_NONE;
+  }
+}
+
+// the heads that are emitted.  WRITE = false counts them.
+template <class K, bool WRITE>
+__global__ __launch_bounds__(256) void k_ug_heads(UgGraph<K> g, const uint32_t *next, const uint32_t *ptr, K *first, uint32_t *head,
+                                                  uint64_t cap, kf_ull *cursor) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int      lane = threadIdx.x & 63;
+  bool           take = false;
+  K              s = 0;
+  const uint32_t o = static_cast<uint32_t>(i);
+  if (i < 2ull * g.n && ptr[o] == o && next[o ^ 1] == UG_NONE) {
+    s = ug_seq(g, o);
+    const uint32_t m = ptr[o ^ 1]; // the mirror chain's head (UG_NONE: a self-complementary k-mer, which exists once)
+    take = m == UG_NONE || s < ug_seq(g, m);
+  }
+  const uint64_t who = __ballot(take);
+  if (!who) return;
+  kf_ull at = 0;
+  if (lane == __ffsll(static_cast<long long>(who)) - 1) at = atomicAdd(cursor, static_cast<kf_ull>(__popcll(who)));
+  at = __shfl(at, __ffsll(static_cast<long long>(who)) - 1);
+  if (WRITE && take) {
+    const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
+    if (slot < cap) {
+      first[slot] = s;
+      head[slot]  = o;
+    }
+  }
+}
+
+// per unitig in output order: its k-mers and whether it is a cycle; unit_of[head] = its id
+__global__ __launch_bounds__(256) void k_ug_units(uint32_t n_units, const uint32_t *head, const uint32_t *ptr, const uint32_t *dist,
+                                                  const uint8_t *cyc, const uint32_t *cyc_last, uint32_t *unit_of, uint32_t *n_kmers,
+                                                  uint8_t *cyclic) {
+  const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= n_units) return;
+  const uint32_t h = head[u], m = ptr[h ^ 1];
+  const bool     round = cyc && cyc[h];
+  unit_of[h] = u;
+  // a linear chain: the mirror head's mirror is its last node; a cut cycle: k_ug_cyc_cut kept it
+  n_kmers[u] = round ? dist[cyc_last[h]] + 1 : (m == UG_NONE ? 1u : dist[m ^ 1] + 1);
+  cyclic[u]  = round;
+}
+
+__global__ __launch_bounds__(256) void k_ug_cover(uint64_t n2, const uint32_t *ptr, const uint32_t *unit_of, const uint32_t *count,
+                                                  kf_ull *cover) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n2) return;
+  const uint32_t h = ptr[i];
+  if (h == UG_NONE) return;
+  const uint32_t u = unit_of[h];
+  if (u != UG_NONE) atomicAdd(&cover[u], static_cast<kf_ull>(count[i >> 1]));
+}
+
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_write(UgGraph<K> g, const uint32_t *ptr, const uint32_t *dist, const uint32_t *unit_of,
+                                                  const uint32_t *n_kmers, const uint64_t *seq_off, uint8_t *text, uint64_t cap) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= 2ull * g.n) return;
+  const uint32_t o = static_cast<uint32_t>(i), h = ptr[o];
+  if (h == UG_NONE) return;
+  const uint32_t u = unit_of[h];
+  if (u == UG_NONE) return;
+  const K        s = ug_seq(g, o);
+  const uint64_t at = seq_off[u];
+  const uint32_t d = dist[o];
+  if (d) {
+    const uint64_t w = at + d + g.k - 1;
+    if (w < cap) text[w] = "ACGT"[static_cast<uint32_t>(s) & 3u];
+    return;
+  }
+  if (at + n_kmers[u] + g.k > cap) return;
+  for (int j = 0; j < g.k; ++j) text[at + j] = "ACGT"[static_cast<uint32_t>(s >> (2 * (g.k - 1 - j))) & 3u];
+  text[at + n_kmers[u] + g.k - 1] = '\n';
+}
+
+} // namespace msgpu
+
+using namespace msgpu;
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+struct msgpu_ugctx : msgpu::KfCtx {
+  uint64_t *d_scalars = nullptr;     // the scalar block (SC_COUNT words)
+  uint64_t *h_scalars = nullptr;     // its page-locked, device-mapped mirror and the sequence number behind it
+  uint64_t *h_scalars_dev = nullptr; // (the device's address of the mirror; null: every read-back is a copy)
+  uint64_t  seq = 0, lost = 0;
+};
+
+struct msgpu_ug_result {
+  msgpu_ug_stats               stats{};
+  std::vector<msgpu_ug_round>  rounds;
+  std::vector<msgpu_ug_unitig> units;
+  char                        *all = nullptr; // page-locked
+  uint64_t                     all_len = 0;
+  std::string                  cut;
+  ~msgpu_ug_result() {
+    if (all) (void)hipHostFree(all);
+  }
+};
+
+namespace {
+
+enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOTAL_C };
+
+// The scalar block as it stands, through the project's read-back protocol (msgpu_device.h, publish_to_host): one wavefront
+// writes it into the mapped mirror and publishes a sequence number, the host polls for it.  A stream that ends without
+// the number arriving is answered by a copy, and counted.
+int ug_read_scalars(msgpu_ugctx *c) {
+  if (c->h_scalars_dev) {
+    const uint64_t seq = ++c->seq;
+    launch_publish_scalars(c->stream, c->d_scalars, HostPublish{c->h_scalars_dev, seq});
+    KHIP(c, hipGetLastError());
+    volatile uint64_t *flag = c->h_scalars + SC_COUNT;
+    for (uint64_t spins = 1;; ++spins) {
+      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
+      __builtin_ia32_pause();
+      if ((spins & 0xffff) == 0) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) {
+          if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
+          break;
+        }
+        if (q != hipErrorNotReady) break;
+      }
+    }
+    ++c->lost;
+  }
+  KHIP(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  KHIP(c, hipStreamSynchronize(c->stream));
+  return MSGPU_OK;
+}
+inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->d_scalars + slot, 0, 8, c->stream); }
+
+template <class K> void ug_split(K key, uint64_t &hi, uint64_t &lo);
+template <> void ug_split<uint64_t>(uint64_t key, uint64_t &hi, uint64_t &lo) {
+  hi = 0;
+  lo = key;
+}
+template <> void ug_split<kf_u128>(kf_u128 key, uint64_t &hi, uint64_t &lo) {
+  hi = static_cast<uint64_t>(key >> 64);
+  lo = static_cast<uint64_t>(key);
+}
+
+inline uint32_t ug_grid(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
+
+// everything behind the format check, for one key width
+template <class K>
+int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &prm, uint64_t budget, msgpu_ug_result *res) {
+  msgpu_ug_stats &S = res->stats;
+  hipStream_t     st = c->stream;
+  KfClock         clock;
+  clock.st = st;
+  const int      k = prm.k;
+  const uint64_t n_first = F[0].n_lines >> 2, n_reads = n_first + (F[1].n_lines >> 2);
+  const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_first, n_reads, k};
+
+  // ---- count: the k-mer filter's, least = min_count, no histogram
+  kf_ull *d_cur;
+  KHIP(c, D.get(&d_cur, 1));
+  std::vector<uint64_t> pre;
+  int                   rc = kf_bin_prefix<K>(c, D, clock, in, &S.bins_ms, pre);
+  if (rc != MSGPU_OK) return rc;
+  S.n_windows = pre[KF_BINS];
+  size_t free_b = 0, total_b = 0;
+  KHIP(c, hipMemGetInfo(&free_b, &total_b));
+  const uint64_t per_key = 2 * sizeof(K) + 4; // two key buffers and the run lengths
+  if (!budget) budget = free_b / 2;
+  const KfParts parts = kf_pick_partitions(pre, per_key, budget);
+  if (!parts.P || parts.largest * per_key > free_b) {
+    snprintf(c->err, sizeof(c->err),
+             "%llu windows of %zu-byte keys need %llu bytes per window in partition buffers (budget %llu bytes, %u hash "
+             "bins); %zu bytes of device memory are free",
+             static_cast<kf_ull>(S.n_windows), sizeof(K), static_cast<kf_ull>(per_key), static_cast<kf_ull>(budget), KF_BINS,
+             free_b);
+    return MSGPU_E_NOMEM;
+  }
+  S.n_partitions      = parts.P;
+  S.largest_partition = parts.largest;
+  std::vector<KfChunk<K>> chunks;
+  uint64_t                kept = 0;
+  rc = kf_count<K>(c, D, clock, in, pre, parts, k, prm.min_count, KfCountMs{&S.extract_ms, &S.sort_ms, &S.runs_ms, &S.select_ms},
+                   d_cur, [](const uint32_t *, uint32_t) { return MSGPU_OK; }, chunks, S.n_distinct, kept);
+  if (rc != MSGPU_OK) return rc;
+  if (kept >= (1ull << 31)) {
+    snprintf(c->err, sizeof(c->err), "%llu solid k-mers; the limit is 2^31 - 1", static_cast<kf_ull>(kept));
+    return MSGPU_E_ARG;
+  }
+  S.n_solid = kept;
+  const uint32_t n = static_cast<uint32_t>(kept);
+  const uint64_t n2 = 2ull * n;
+  // what the rest keeps resident: keys, counts, the table, three bytes per k-mer, eight words per oriented node
+  KHIP(c, hipMemGetInfo(&free_b, &total_b));
+  const uint64_t graph_bytes = n * (2 * (sizeof(K) + 4ull) + 8 + 3) + n2 * (8 * 4ull + 1);
+  if (graph_bytes > free_b) {
+    snprintf(c->err, sizeof(c->err), "%u solid k-mers of %zu-byte keys need about %llu bytes for the graph; %zu bytes of device "
+             "memory are free", n, sizeof(K), static_cast<kf_ull>(graph_bytes), free_b);
+    return MSGPU_E_NOMEM;
+  }
+  K        *d_keys = nullptr;
+  uint32_t *d_cnt = nullptr, *d_slots = nullptr, slots_n = 0;
+  KHIP(c, clock.begin(&S.select_ms));
+  rc = kf_gather_sorted<K>(c, D, chunks, prm.min_count, n, k, d_cur, &d_keys, &d_cnt, &d_slots, &slots_n);
+  if (rc != MSGPU_OK) return rc;
+  KHIP(c, clock.end());
+  UgGraph<K> g{d_keys, d_slots, slots_n - 1, n, k, 2 * (k - 1),
+               (2 * k == static_cast<int>(sizeof(K) * 8)) ? ~static_cast<K>(0) : ((static_cast<K>(1) << (2 * k)) - 1)};
+
+  // ---- neighbour bytes, tip rounds
+  uint8_t *d_alive, *d_adj, *d_mark;
+  KHIP(c, D.get(&d_alive, n));
+  KHIP(c, D.get(&d_adj, n));
+  KHIP(c, D.get(&d_mark, n));
+  KHIP(c, hipMemsetAsync(d_alive, 1, n ? n : 1, st));
+  KHIP(c, hipMemsetAsync(d_mark, 0, n ? n : 1, st));
+  KHIP(c, clock.begin(&S.adjacency_ms));
+  if (n) hipLaunchKernelGGL((k_ug_adj<K, true>), dim3(ug_grid(n)), dim3(256), 0, st, g, d_alive, d_adj);
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+  std::deque<msgpu_ug_round> rounds; // (the clock keeps pointers into it)
+  uint64_t                   alive_n = n;
+  const uint32_t             trim = static_cast<uint32_t>(prm.trim);
+  for (uint32_t limit = trim ? 1 : 0; limit;) {
+    if (limit > trim) limit = trim;
+    rounds.push_back(msgpu_ug_round{limit, 0, 0, 0.f, 0.f});
+    msgpu_ug_round &R = rounds.back();
+    KHIP(c, ug_zero_scalar(c, UG_SC_REMOVED));
+    KHIP(c, clock.begin(&R.tips_ms));
+    if (n) {
+      hipLaunchKernelGGL(k_ug_tips<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_alive, d_adj, limit, d_mark);
+      hipLaunchKernelGGL(k_ug_apply, dim3(ug_grid(n)), dim3(256), 0, st, n, d_alive, d_mark, reinterpret_cast<kf_ull *>(c->d_scalars + UG_SC_REMOVED));
+    }
+    KHIP(c, hipGetLastError());
+    KHIP(c, clock.end());
+    rc = ug_read_scalars(c);
+    if (rc != MSGPU_OK) return rc;
+    R.removed = c->h_scalars[UG_SC_REMOVED];
+    alive_n -= R.removed;
+    if (R.removed) {
+      KHIP(c, clock.begin(&R.adjacency_ms));
+      hipLaunchKernelGGL((k_ug_adj<K, false>), dim3(ug_grid(n)), dim3(256), 0, st, g, d_alive, d_adj);
+      KHIP(c, hipGetLastError());
+      KHIP(c, clock.end());
+    }
+    if (limit < trim) limit = limit > trim / 2 ? trim : 2 * limit; // 1, 2, 4, ... below trim, then trim
+    else if (!R.removed) limit = 0;                                // the round at trim repeats until it removes nothing
+  }
+  S.n_solid_trimmed = alive_n;
+  S.n_tip_rounds    = static_cast<uint32_t>(rounds.size());
+  D.drop(d_mark);
+
+  // ---- joins, pointer doubling
+  uint32_t *d_next, *d_ptr[2], *d_dist[2];
+  KHIP(c, D.get(&d_next, n2));
+  for (int i = 0; i < 2; ++i) {
+    KHIP(c, D.get(&d_ptr[i], n2));
+    KHIP(c, D.get(&d_dist[i], n2));
+  }
+  KHIP(c, clock.begin(&S.next_ms));
+  if (n) {
+    hipLaunchKernelGGL(k_ug_next<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_alive, d_adj, d_next);
+    hipLaunchKernelGGL(k_ug_chain_init<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_alive, d_next, d_ptr[0], d_dist[0]);
+  }
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+  int  cur = 0;
+  auto doubling = [&](uint64_t &open) -> int { // rounds until the number of open nodes is 0 or stops falling
+    uint64_t before = ~0ull;
+    for (;;) {
+      if (S.doubling_rounds >= 200) {
+        snprintf(c->err, sizeof(c->err), "pointer doubling did not settle in %u rounds", S.doubling_rounds);
+        return MSGPU_E_STATE;
+      }
+      KHIP(c, ug_zero_scalar(c, UG_SC_OPEN));
+      KHIP(c, clock.begin(&S.doubling_ms));
+      hipLaunchKernelGGL(k_ug_double, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_next, d_ptr[cur], d_dist[cur], d_ptr[cur ^ 1],
+                         d_dist[cur ^ 1], reinterpret_cast<kf_ull *>(c->d_scalars + UG_SC_OPEN));
+      KHIP(c, hipGetLastError());
+      KHIP(c, clock.end());
+      cur ^= 1;
+      ++S.doubling_rounds;
+      const int r2 = ug_read_scalars(c);
+      if (r2 != MSGPU_OK) return r2;
+      open = c->h_scalars[UG_SC_OPEN];
+      if (!open || open == before) return MSGPU_OK;
+      before = open;
+    }
+  };
+  uint64_t  open = 0;
+  uint8_t  *d_cyc = nullptr;
+  uint32_t *d_cyc_last = nullptr;
+  if (n) {
+    rc = doubling(open);
+    if (rc != MSGPU_OK) return rc;
+  }
+  if (open) { // cycles: their smallest node by a min-reduction, the cut, and the doubling again
+    uint32_t *d_back[2], *d_low[2];
+    KHIP(c, D.get(&d_cyc, n2));
+    for (int i = 0; i < 2; ++i) {
+      KHIP(c, D.get(&d_back[i], n2));
+      KHIP(c, D.get(&d_low[i], n2));
+    }
+    KHIP(c, clock.begin(&S.doubling_ms));
+    hipLaunchKernelGGL(k_ug_cyc_init, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_next, d_ptr[cur], d_cyc, d_back[0], d_low[0]);
+    int at = 0;
+    for (uint64_t span = 1; span < open; span *= 2, at ^= 1, ++S.doubling_rounds) // (a cycle has at most `open` nodes)
+      hipLaunchKernelGGL(k_ug_cyc_min<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_cyc, d_back[at], d_low[at], d_back[at ^ 1],
+                         d_low[at ^ 1]);
+    hipLaunchKernelGGL(k_ug_cyc_cut, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_cyc, d_low[at], d_next, d_ptr[cur], d_dist[cur]);
+    KHIP(c, hipGetLastError());
+    KHIP(c, clock.end());
+    rc = doubling(open);
+    if (rc != MSGPU_OK) return rc;
+    if (open) {
+      snprintf(c->err, sizeof(c->err), "%llu nodes reach no chain head after the cycles were cut", static_cast<kf_ull>(open));
+      return MSGPU_E_STATE;
+    }
+    d_cyc_last = d_low[at];
+    D.drop(d_low[at ^ 1]);
+    for (int i = 0; i < 2; ++i) D.drop(d_back[i]);
+  }
+  uint32_t *d_p = d_ptr[cur], *d_d = d_dist[cur];
+  D.drop(d_ptr[cur ^ 1]);
+  D.drop(d_dist[cur ^ 1]);
+
+  // ---- the emitted heads in output order, the unitig table, coverage
+  KHIP(c, clock.begin(&S.order_ms));
+  KHIP(c, ug_zero_scalar(c, UG_SC_UNITS));
+  kf_ull *d_units_n = reinterpret_cast<kf_ull *>(c->d_scalars + UG_SC_UNITS);
+  if (n) hipLaunchKernelGGL((k_ug_heads<K, false>), dim3(ug_grid(n2)), dim3(256), 0, st, g, d_next, d_p, nullptr, nullptr, 0, d_units_n);
+  KHIP(c, hipGetLastError());
+  rc = ug_read_scalars(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t U = static_cast<uint32_t>(c->h_scalars[UG_SC_UNITS]);
+  S.n_unitigs = U;
+  K        *d_first[2];
+  uint32_t *d_head[2], *d_unit_of, *d_nk;
+  uint8_t  *d_cyclic;
+  kf_ull   *d_cover;
+  uint64_t *d_seq_off;
+  for (int i = 0; i < 2; ++i) {
+    KHIP(c, D.get(&d_first[i], U));
+    KHIP(c, D.get(&d_head[i], U));
+  }
+  KHIP(c, D.get(&d_unit_of, n2));
+  KHIP(c, D.get(&d_nk, U));
+  KHIP(c, D.get(&d_cyclic, U));
+  KHIP(c, D.get(&d_cover, U));
+  KHIP(c, D.get(&d_seq_off, U));
+  KHIP(c, hipMemsetAsync(d_unit_of, 0xff, n2 ? n2 * 4 : 4, st));
+  KHIP(c, hipMemsetAsync(d_cover, 0, U ? U * 8ull : 8, st));
+  if (U) {
+    KHIP(c, ug_zero_scalar(c, UG_SC_UNITS));
+    hipLaunchKernelGGL((k_ug_heads<K, true>), dim3(ug_grid(n2)), dim3(256), 0, st, g, d_next, d_p, d_first[0], d_head[0], U, d_units_n);
+    KHIP(c, hipGetLastError());
+    size_t need = 0;
+    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, d_first[0], d_first[1], d_head[0], d_head[1], U, 0, 2 * k, st));
+    uint8_t *tmp;
+    KHIP(c, D.get(&tmp, need));
+    KHIP(c, rocprim::radix_sort_pairs(tmp, need, d_first[0], d_first[1], d_head[0], d_head[1], U, 0, 2 * k, st));
+    hipLaunchKernelGGL(k_ug_units, dim3(ug_grid(U)), dim3(256), 0, st, U, d_head[1], d_p, d_d, d_cyc, d_cyc_last, d_unit_of, d_nk,
+                       d_cyclic);
+    hipLaunchKernelGGL(k_ug_cover, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_p, d_unit_of, d_cnt, d_cover);
+    KHIP(c, hipGetLastError());
+  }
+  KHIP(c, clock.end());
+  std::vector<uint32_t> nk;
+  std::vector<uint8_t>  cyclic;
+  std::vector<kf_ull>   cover;
+  std::vector<K>        first;
+  std::vector<uint64_t> seq_off;
+  try {
+    nk.resize(U);
+    cyclic.resize(U);
+    cover.resize(U);
+    first.resize(U);
+    seq_off.resize(U);
+    res->units.resize(U);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  KHIP(c, clock.begin(&S.copy_ms));
+  if (U) {
+    KHIP(c, hipMemcpyAsync(nk.data(), d_nk, U * 4ull, hipMemcpyDeviceToHost, st));
+    KHIP(c, hipMemcpyAsync(cyclic.data(), d_cyclic, U, hipMemcpyDeviceToHost, st));
+    KHIP(c, hipMemcpyAsync(cover.data(), d_cover, U * 8ull, hipMemcpyDeviceToHost, st));
+    KHIP(c, hipMemcpyAsync(first.data(), d_first[1], U * sizeof(K), hipMemcpyDeviceToHost, st));
+  }
+  KHIP(c, clock.end());
+  KHIP(c, hipStreamSynchronize(st));
+
+  // ---- host: headers and offsets
+  const auto  h0 = std::chrono::steady_clock::now();
+  std::string heads; // every header, one behind the other
+  std::vector<uint32_t> head_len(U);
+  uint64_t              total = 0, solid_sum = 0;
+  char                  buf[96];
+  try {
+    for (uint32_t u = 0; u < U; ++u) {
+      msgpu_ug_unitig &T = res->units[u];
+      T.length   = static_cast<uint64_t>(nk[u]) + k - 1;
+      T.coverage = cover[u];
+      T.cyclic   = cyclic[u];
+      T.reserved = 0;
+      ug_split<K>(first[u], T.first_hi, T.first_lo);
+      head_len[u] = static_cast<uint32_t>(snprintf(buf, sizeof(buf), ">%u %llu %llu\n", u, static_cast<kf_ull>(T.length), cover[u]));
+      heads.append(buf, head_len[u]);
+      T.offset   = total + head_len[u];
+      seq_off[u] = T.offset;
+      total += head_len[u] + T.length + 1;
+      solid_sum += nk[u];
+      S.n_cycles += cyclic[u];
+      S.longest_chain = std::max<uint64_t>(S.longest_chain, nk[u]);
+    }
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  if (solid_sum != alive_n) { // every k-mer lies in exactly one unitig: never seen otherwise
+    snprintf(c->err, sizeof(c->err), "the unitigs hold %llu k-mers where %llu are solid", static_cast<kf_ull>(solid_sum),
+             static_cast<kf_ull>(alive_n));
+    return MSGPU_E_STATE;
+  }
+  S.host_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+
+  // ---- the bases
+  uint8_t *d_text;
+  KHIP(c, D.get(&d_text, total));
+  KHIP(c, clock.begin(&S.write_ms));
+  if (U) {
+    KHIP(c, hipMemcpyAsync(d_seq_off, seq_off.data(), U * 8ull, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ug_write<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_p, d_d, d_unit_of, d_nk, d_seq_off, d_text, total);
+    KHIP(c, hipGetLastError());
+  }
+  KHIP(c, clock.end());
+  KHIP(c, clock.begin(&S.copy_ms));
+  if (total) {
+    KHIP(c, hipHostMalloc(reinterpret_cast<void **>(&res->all), total, hipHostMallocDefault));
+    KHIP(c, hipMemcpyAsync(res->all, d_text, total, hipMemcpyDeviceToHost, st));
+  }
+  KHIP(c, clock.end());
+  KHIP(c, hipStreamSynchronize(st));
+  clock.collect();
+  res->all_len = total;
+
+  // ---- host: the headers into the text, the cut text
+  const auto h1 = std::chrono::steady_clock::now();
+  try {
+    uint64_t at = 0, cut_bytes = 0;
+    for (uint32_t u = 0; u < U; ++u)
+      if (res->units[u].length >= prm.min_length) cut_bytes += head_len[u] + res->units[u].length + 1;
+    res->cut.reserve(cut_bytes);
+    for (uint32_t u = 0; u < U; ++u) {
+      const uint64_t rec = res->units[u].offset - head_len[u], bytes = head_len[u] + res->units[u].length + 1;
+      memcpy(res->all + rec, heads.data() + at, head_len[u]);
+      at += head_len[u];
+      if (res->units[u].length >= prm.min_length) {
+        res->cut.append(res->all + rec, bytes);
+        ++S.n_unitigs_kept;
+      }
+    }
+    res->rounds.assign(rounds.begin(), rounds.end());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  for (const msgpu_ug_round &R : res->rounds) {
+    S.tips_ms += R.tips_ms;
+    S.adjacency_ms += R.adjacency_ms;
+  }
+  S.host_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h1).count();
+  S.bytes_out[0] = res->all_len;
+  S.bytes_out[1] = res->cut.size();
+  return MSGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int msgpu_ug_create(int device, msgpu_ugctx **out) {
+  if (!out) return MSGPU_E_ARG;
+  *out     = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
+  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
+  auto *c = new (std::nothrow) msgpu_ugctx();
+  if (!c) return MSGPU_E_NOMEM;
+  c->device = device;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&c->d_scalars), SC_COUNT * sizeof(uint64_t)) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void **>(&c->h_scalars), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess) {
+    msgpu_ug_destroy(c);
+    return MSGPU_E_HIP;
+  }
+  memset(c->h_scalars, 0, (SC_COUNT + 1) * sizeof(uint64_t));
+  void *dev = nullptr;
+  if (!getenv("MSGPU_SYNC_READBACK") && hipHostGetDevicePointer(&dev, c->h_scalars, 0) == hipSuccess)
+    c->h_scalars_dev = static_cast<uint64_t *>(dev);
+  if (hipMemset(c->d_scalars, 0, SC_COUNT * sizeof(uint64_t)) != hipSuccess) {
+    msgpu_ug_destroy(c);
+    return MSGPU_E_HIP;
+  }
+  *out = c;
+  return MSGPU_OK;
+}
+
+void msgpu_ug_destroy(msgpu_ugctx *c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  if (c->stream) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamDestroy(c->stream);
+  }
+  if (c->d_scalars) (void)hipFree(c->d_scalars);
+  if (c->h_scalars) (void)hipHostFree(c->h_scalars);
+  delete c;
+}
+
+const char *msgpu_ug_last_error(const msgpu_ugctx *c) { return c ? c->err : "null context"; }
+uint64_t    msgpu_ug_error_line(const msgpu_ugctx *c) { return c ? c->err_line : 0; }
+int         msgpu_ug_error_file(const msgpu_ugctx *c) { return c ? c->err_file : 0; }
+
+int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path_a, const char *path_b, uint32_t flags,
+                 uint64_t budget_bytes, msgpu_ug_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out        = nullptr;
+  c->err[0]   = 0;
+  c->err_line = 0;
+  c->err_file = 0;
+  if (!params || !path_a || flags) return MSGPU_E_ARG;
+  msgpu_ug_params prm = *params;
+  if (prm.k < 2 || prm.k > 64) {
+    snprintf(c->err, sizeof(c->err), "k = %d is outside 2..64", prm.k);
+    return MSGPU_E_ARG;
+  }
+  if (prm.trim == -1) prm.trim = prm.k;
+  if (prm.min_count < 1 || prm.trim < 0) {
+    snprintf(c->err, sizeof(c->err), "min_count = %u must be at least 1, trim = %d at least 0 (or -1 for k)", prm.min_count, prm.trim);
+    return MSGPU_E_ARG;
+  }
+  const auto w0 = std::chrono::steady_clock::now();
+  auto       since = [](std::chrono::steady_clock::time_point a) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
+  };
+  KHIP(c, hipSetDevice(c->device));
+  std::unique_ptr<msgpu_ug_result> res;
+  try {
+    res.reset(new msgpu_ug_result());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  msgpu_ug_stats &S = res->stats;
+  S.k          = static_cast<uint32_t>(prm.k);
+  S.min_count  = prm.min_count;
+  S.trim       = static_cast<uint32_t>(prm.trim);
+  S.min_length = prm.min_length;
+  KfDev          D;
+  KfFile         F[2];
+  const char    *paths[2] = {path_a, path_b};
+  const int      n_files = path_b ? 2 : 1;
+  const uint64_t lost0 = c->lost;
+  for (int f = 0; f < n_files; ++f) {
+    const int rc = kf_upload(c, D, paths[f], f, F[f]);
+    if (rc != MSGPU_OK) return rc;
+    S.bytes_in[f] = F[f].size;
+  }
+  S.load_ms = since(w0);
+  const auto r0 = std::chrono::steady_clock::now();
+  int        rc = kf_records(c, D, F, n_files);
+  if (rc != MSGPU_OK) return rc;
+  if (n_files == 1) { // no second file: no read of it is ever asked for
+    F[1].d  = F[0].d;
+    F[1].ls = F[0].ls;
+  }
+  S.n_records[0] = F[0].n_lines >> 2;
+  S.n_records[1] = F[1].n_lines >> 2;
+  S.records_ms   = since(r0);
+  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, prm, budget_bytes, res.get()) : ug_stage<kf_u128>(c, D, F, prm, budget_bytes, res.get());
+  if (rc != MSGPU_OK) return rc;
+  S.n_lost_publications = c->lost - lost0;
+  S.wall_ms             = since(w0);
+  *out                  = res.release();
+  return MSGPU_OK;
+}
+
+int msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->stats;
+  return MSGPU_OK;
+}
+
+int msgpu_ug_result_rounds(const msgpu_ug_result *r, const msgpu_ug_round **rounds, uint64_t *n) {
+  if (!r || !rounds || !n) return MSGPU_E_ARG;
+  *rounds = r->rounds.data();
+  *n      = r->rounds.size();
+  return MSGPU_OK;
+}
+
+int msgpu_ug_result_unitigs(const msgpu_ug_result *r, const msgpu_ug_unitig **unitigs, uint64_t *n) {
+  if (!r || !unitigs || !n) return MSGPU_E_ARG;
+  *unitigs = r->units.data();
+  *n       = r->units.size();
+  return MSGPU_OK;
+}
+
+const char *msgpu_ug_result_text(const msgpu_ug_result *r, int which, uint64_t *len) {
+  if (len) *len = 0;
+  if (!r) return "";
+  if (which == MSGPU_UG_TEXT_ALL) {
+    if (len) *len = r->all_len;
+    return r->all ? r->all : "";
+  }
+  if (which == MSGPU_UG_TEXT_CUT) {
+    if (len) *len = r->cut.size();
+    return r->cut.data();
+  }
+  return "";
+}
+
+void msgpu_ug_result_free(msgpu_ug_result *r) {
+  if (r) delete r;
+}
+
+} // extern "C"

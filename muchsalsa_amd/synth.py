@@ -526,3 +526,30 @@ def kmer_filter_workload(genome, coverage, read_len, seed, families=6, copies=25
         rec[:, -1] = 10
         out.append(rec.tobytes())
     return out[0], out[1]
+
+
+def _revcomp(seq):
+    return seq[::-1].translate(bytes.maketrans(b"ACGT", b"TGCA"))
+
+
+def unitig_cases():
+    """Hand-made inputs of the short-read unitig assembly (muchsalsa_amd.unitigs): name -> (FASTQ file 1, FASTQ file 2 or
+    None, what the case is made of).  Every read is written twice, so its k-mers are solid at min_count = 2.
+
+    rings    two circular sequences of 300 bases, 100-base reads tiled around each at a step of 10: two cyclic unitigs
+             (300 k-mers, 300 + k - 1 bases each).  The smallest oriented k-mer of the first ring lies on the strand the
+             reads were written from, that of the second on the other one.
+    selfcomp a linear sequence of 240 bases with x + rc(x) (16 bases each) in its middle: a self-complementary 32-mer.
+    hairpin  one read x + rc(x) of 2 x 100 bases: the read is its own reverse complement."""
+    def fq(name, reads):
+        return b"".join(b"@%s%d\n%s\n+\n%s\n" % (name, i, r, b"I" * len(r)) for i, r in enumerate(reads))
+
+    rings = [genome_bases(300, 101).tobytes(), genome_bases(300, 102).tobytes()]
+    ring_reads = [[(r + r)[at:at + 100] for at in range(0, 300, 10) for _ in (0, 1)] for r in rings]
+    left, x, right = genome_bases(112, 201).tobytes(), genome_bases(16, 202).tobytes(), genome_bases(112, 203).tobytes()
+    selfcomp = left + x + _revcomp(x) + right
+    h = genome_bases(100, 301).tobytes()
+    hairpin = h + _revcomp(h)
+    return {"rings": (fq(b"a", ring_reads[0]), fq(b"b", ring_reads[1]), {"rings": rings}),
+            "selfcomp": (fq(b"s", [selfcomp, selfcomp]), None, {"sequence": selfcomp, "self_complementary": x + _revcomp(x)}),
+            "hairpin": (fq(b"h", [hairpin, hairpin]), None, {"sequence": hairpin})}

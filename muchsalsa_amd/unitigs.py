@@ -1,0 +1,174 @@
+"""The pipeline's short-read unitig assembly on the GPU: what ``abyss-pe k=K name=NAME in='R1 R2' unitigs`` and the awk cut
+at MINLENGTH behind it write in the reference pipeline -- ``NAME-unitigs.fa`` and ``NAME-unitigs.l500.fa`` -- from one or two
+FASTQ files (the k-mer filter's outputs) alone.
+
+    python -m muchsalsa_amd.unitigs <k> <in_1.fq> <in_2.fq> <out_all.fa> <out_cut.fa>
+            [--min-count N] [--trim N] [--min-length N] [--budget-mb N]
+
+prints one JSON line of counts and seconds.  ABySS is not needed, and it is not part of the reference tree: the stage is
+defined by the rules below and checked, without tolerance, against the tests' restatement in plain Python
+(tests/ug_oracle.py), not against ABySS.  The rules (include/msgpu.h, "short-read unitig assembly"); parameters k (2..64),
+min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500, the pipeline's
+MINLENGTH):
+
+1. Input: one or two FASTQ files.  The FASTQ rules and the window rules are rules 1 and 2 of the k-mer abundance filter
+   (muchsalsa_amd.kmer_filter), word for word, error code, file and line included.  The files are not pairs: their record
+   counts may differ and the second may be missing.  count(x) = windows of all files whose canonical k-mer is x, exact.
+2. Solid set S = the canonical k-mers with count >= min_count.
+3. Oriented graph: every k-base string s whose canonical form is in S is an oriented node; s and rc(s) are two nodes of one
+   k-mer, or one node if s is its own reverse complement.  succ(s) = { s[1:]+c : c in ACGT, canon(s[1:]+c) in S },
+   pred(s) = { c+s[:-1] : c in ACGT, canon(c+s[:-1]) in S }.
+4. Tip removal, in rounds on a snapshot of S.  The limits are 1, 2, 4, ... (doubling, every value below trim), then trim; each
+   limit runs once, after that the round at trim repeats until a round removes nothing; trim = 0: no round.  In a round, for
+   every oriented node s with pred(s) empty: path = [s], then repeat: if |succ(last)| != 1 stop, no tip; let t be the one
+   successor; if |pred(t)| >= 2 the path is a tip, stop; if |path| = limit stop, no tip; else append t.  All k-mers of all
+   tips of a round leave S together when the round ends.  Islands (dead at both ends) stay; the length cut deals with them.
+   Each round's (limit, k-mers removed) is reported.
+5. Unitigs: s -> t is joined iff succ(s) = {t}, pred(t) = {s}, neither s nor t is its own reverse complement and
+   canon(s) != canon(t): no self-loop and no hairpin is ever joined.  Unitigs are the maximal chains of joined nodes; every
+   k-mer of S lies in exactly one.  Every unitig exists as two mirror chains, which these rules make distinct (a one-node
+   chain of a self-complementary k-mer exists once).  Linear chain: the one whose first k-mer, as a 2k-bit number, is smaller
+   than its mirror's first k-mer is emitted (no tie is possible).  Cycle: it starts at the smallest oriented node among the
+   cycle and its mirror and goes round once: n k-mers give n + k - 1 bases, the closing join is not written.  Sequence = the
+   first k-mer and the last base of every further node, upper case.  coverage = sum of count over its k-mers (64 bits).
+6. Output: the unitigs ascending by the first k-mer of the emitted orientation; id = rank in that order, over all unitigs,
+   before any cut.  A record is ``>id length coverage\\n``, the sequence on one line, ``\\n`` (ABySS's header shape; the
+   pipeline's awk reads field 2).  Two texts: all records, and the records with length >= min_length, ids unchanged.
+7. Limits, each an error and never a fault: fewer than 2^31 solid k-mers; the file limits of the k-mer filter; everything
+   resident in device memory together, else the stage fails naming the sizes.  On any error nothing is written.
+
+Known differences from ``abyss-pe unitigs``, none of which could be checked against the program (it is not installed where
+this project is built):
+
+* exact counts, where ABySS 2 keeps its k-mers in a Bloom filter;
+* no bubble popping and no erosion of the ends;
+* islands are kept until the length cut;
+* ids and the order of the records are this stage's;
+* a sequence is one line.
+"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+from . import _lib
+
+__all__ = ["UnitigError", "run", "main"]
+
+
+class UnitigError(RuntimeError):
+    """A rejected input or a device failure; ``line`` = 1-based line (0: none) of ``file`` (0 / 1: the first / second
+    FASTQ)."""
+
+    def __init__(self, code, file=0, line=0, detail=""):
+        msg = _lib.lib().msgpu_strerror(code).decode()
+        where = (" (file %d line %d)" % (file, line)) if line else ""
+        super().__init__("%s (%d)%s%s" % (msg, code, where, (": " + detail) if detail else ""))
+        self.code = code
+        self.file = file
+        self.line = line
+
+
+def _text(L, res, which):
+    """a view of one of the result's texts (valid until the result is freed)"""
+    n = C.c_uint64()
+    p = L.msgpu_ug_result_text(res, which, C.byref(n))
+    return memoryview((C.c_char * n.value).from_address(p)) if n.value else b""
+
+
+def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_length=500, budget_mb=None, tables=None,
+        timings=None):
+    """The whole stage: writes ``out_all`` and ``out_cut``; returns the counts.  ``in_2`` may be None.  ``trim`` None: k.
+    ``budget_mb`` bounds the count's partition buffers (None: half of the free device memory).  ``tables`` (a dict)
+    receives ``rounds`` [(limit, k-mers removed)] and ``unitigs`` [(length, coverage, first k-mer, offset of the sequence in
+    the all text, cyclic)] in output order; ``timings`` (a dict) seconds per step (``files``: writing the two outputs), and ``round_seconds`` [(tips,
+    neighbour bytes)] per round."""
+    L = _lib.lib()
+    t0 = time.perf_counter()
+    ctx = C.c_void_p()
+    rc = L.msgpu_ug_create(device, C.byref(ctx))
+    if rc != _lib.OK:
+        raise UnitigError(rc, detail="device %d" % device)
+    try:
+        res = C.c_void_p()
+        budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
+        prm = _lib.UgParams(int(k), int(min_count) if 0 <= int(min_count) < (1 << 32) else 0, -1 if trim is None else int(trim),
+                            min(max(int(min_length), 0), (1 << 32) - 1))
+        if trim is not None and int(trim) < 0:
+            raise UnitigError(_lib.E_ARG, detail="trim = %d" % int(trim))
+        rc = L.msgpu_ug_run(ctx, C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget,
+                            C.byref(res))
+        if rc != _lib.OK:
+            raise UnitigError(rc, int(L.msgpu_ug_error_file(ctx)), int(L.msgpu_ug_error_line(ctx)),
+                              L.msgpu_ug_last_error(ctx).decode(errors="replace"))
+        try:
+            st = _lib.UgStats()
+            L.msgpu_ug_result_stats(res, C.byref(st))
+            rp, n = C.POINTER(_lib.UgRound)(), C.c_uint64()
+            L.msgpu_ug_result_rounds(res, C.byref(rp), C.byref(n))
+            rounds = [(int(rp[i].limit), int(rp[i].removed)) for i in range(n.value)]
+            round_s = [(rp[i].tips_ms / 1e3, rp[i].adjacency_ms / 1e3) for i in range(n.value)]
+            if tables is not None:
+                up = C.POINTER(_lib.UgUnitig)()
+                L.msgpu_ug_result_unitigs(res, C.byref(up), C.byref(n))
+                tables["rounds"] = rounds
+                tables["unitigs"] = [(int(u.length), int(u.coverage), (int(u.first_hi) << 64) | int(u.first_lo), int(u.offset),
+                                      int(u.cyclic)) for u in (up[i] for i in range(n.value))]
+            t1 = time.perf_counter()
+            for path, which in ((out_all, _lib.UG_TEXT_ALL), (out_cut, _lib.UG_TEXT_CUT)):
+                with open(path, "wb") as h:
+                    h.write(_text(L, res, which))
+            t_write = time.perf_counter() - t1
+        finally:
+            L.msgpu_ug_result_free(res)
+    finally:
+        L.msgpu_ug_destroy(ctx)
+    if timings is not None:
+        timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.UgStats._fields_ if name.endswith("_ms")})
+        timings["stage_wall"] = timings.pop("wall")
+        timings.update({"files": t_write, "total": time.perf_counter() - t0, "round_seconds": round_s})
+    return {"k": int(st.k), "min_count": int(st.min_count), "trim": int(st.trim), "min_length": int(st.min_length),
+            "records": [int(x) for x in st.n_records], "windows": int(st.n_windows), "distinct": int(st.n_distinct),
+            "solid": int(st.n_solid), "solid_after": int(st.n_solid_trimmed), "tip_rounds": int(st.n_tip_rounds),
+            "rounds": [list(r) for r in rounds], "unitigs": int(st.n_unitigs), "kept": int(st.n_unitigs_kept),
+            "cycles": int(st.n_cycles), "longest": int(st.longest_chain), "doubling_rounds": int(st.doubling_rounds),
+            "partitions": int(st.n_partitions), "largest_partition": int(st.largest_partition),
+            "lost_publications": int(st.n_lost_publications), "bytes_in": [int(x) for x in st.bytes_in],
+            "bytes_out": [int(x) for x in st.bytes_out]}
+
+
+def main(argv):
+    args = list(argv)
+    opts = {"--min-count": 2, "--trim": None, "--min-length": 500, "--budget-mb": None}
+    ok = True
+    for name in opts:
+        if name in args:
+            i = args.index(name)
+            try:
+                opts[name] = (float if name == "--budget-mb" else int)(args[i + 1])
+            except (IndexError, ValueError):
+                ok = False
+            del args[i:i + 2]
+    try:
+        k = int(args[0]) if args else 0
+    except ValueError:
+        ok = False
+    ok = ok and opts["--min-count"] >= 1 and (opts["--trim"] is None or opts["--trim"] >= 0) and opts["--min-length"] >= 0
+    ok = ok and (opts["--budget-mb"] is None or opts["--budget-mb"] > 0) and not any(a.startswith("--") for a in args)
+    if not ok or len(args) != 5:
+        sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
+        return 2
+    timings = {}
+    out = run(k, args[1], args[2], args[3], args[4], min_count=opts["--min-count"], trim=opts["--trim"],
+              min_length=opts["--min-length"], budget_mb=opts["--budget-mb"], timings=timings)
+    rs = timings.pop("round_seconds")
+    out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
+    out["round_seconds"] = [[round(a, 5), round(b, 5)] for a, b in rs]
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    _lib.PRELOAD_TORCH = False  # this process never imports torch
+    sys.exit(main(sys.argv[1:]))
