@@ -1108,6 +1108,96 @@ int         msgpu_ug_result_unitigs(const msgpu_ug_result *r, const msgpu_ug_uni
 const char *msgpu_ug_result_text(const msgpu_ug_result *r, int which, uint64_t *len);
 void        msgpu_ug_result_free(msgpu_ug_result *r);
 
+/* ---- unitig-to-read mapping (the pipeline's four minimap2 calls) ------------------------------
+ * Every record of a query file is mapped onto every record of a target file by minimizer seeds and a chaining DP, and a PAF
+ * is written.  minimap2 is not part of the reference tree: the stage is defined by the rules below, in integers only, and is
+ * checked without tolerance against their restatement in plain Python (tests/map_oracle.py), not against minimap2.  Both files
+ * go through msgpu_seq_parse_upload (FASTA or FASTQ, decided as msgpu_seq_parse decides; names are cut at the first
+ * whitespace).  Parameters: k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth (2000),
+ * max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1).
+ *  1. windows: the alphabet, case folding, 2-bit code, canonical key (min(fw, rc) as 2k-bit numbers) and the break at any
+ *     other byte are those of the k-mer filter's rolling window (KfRoll).  A stretch is a maximal run of k-mer start
+ *     positions without a break.  The strand bit of a position is 1 iff rc < fw.
+ *  2. minimizers: h(i) = kf_hash(key(i)).  A window is w consecutive k-mer start positions inside one stretch; a stretch with
+ *     fewer than w positions has none.  A window's minimizer is its position with the smallest (h, position).  A sequence's
+ *     minimizers are the union over its windows, each position once.
+ *  3. index: every target minimizer as (key, target record, position, strand).  A key with more than max_occ entries is left
+ *     out whole; the number of keys and entries left out is reported.
+ *  4. anchors: every query minimizer meets every index entry of its key.  Relative strand s = query strand ^ target strand,
+ *     x = the target position, y = the query position if s = 0, else qlen - k - position (the position in the
+ *     reverse-complemented query, so a collinear chain rises in both coordinates on both strands).  With ava the query file
+ *     is the target file, and an anchor is kept only if the query record index is smaller than the target record index.  A
+ *     group is (query record, target record, s); its anchors are ordered by (x, y); equal (x, y) cannot occur.
+ *  5. chaining, per group over the anchors 0..n-1 in that order: f(i) = max(k, max over j in [max(0, i - 64), i) of
+ *     f(j) + gain - pen), taken over the j with dx = x_i - x_j > 0, dy = y_i - y_j > 0, dx <= max_gap, dy <= max_gap and
+ *     dd = |dx - dy| <= bandwidth; gain = min(dx, dy, k); pen = 0 if dd = 0, else (dd * k) / 100 + (floor(log2(dd)) >> 1)
+ *     with integer division.  pred(i) is the j that gives the maximum, the largest such j on a tie; it is "none" when k
+ *     alone is at least as good.
+ *  6. chains: the anchors of a group are visited by (f descending, index ascending).  An unused anchor starts a chain; the
+ *     chain follows pred over unused anchors and ends before the first used anchor u or at "none";
+ *     score = f(start) - (f(u) if it ended at a used anchor, else 0); all its anchors become used.  The chain is emitted iff
+ *     score >= min_score and it has at least min_count anchors.  A group with fewer than min_count anchors, or with
+ *     n * k < min_score, can emit nothing and is dropped before the DP.
+ *  7. figures of a chain with anchors a_0 < ... < a_{m-1} (rising x).  For each link i >= 1: c_i = min(dx, dy, k),
+ *     lt_i = dx - c_i, lq_i = dy - c_i; the link's segment is target [x_i + k - c_i - lt_i, x_i + k - c_i) against the
+ *     oriented query [y_i + k - c_i - lq_i, y_i + k - c_i); d_i = that pair's Levenshtein distance inside band with
+ *     msgpu_edit_distance's semantics, min(distance, band + 1), over the bytes as the stores hold them (the oriented query
+ *     of s = 1 is MSGPU_COPY_REVCOMP's: reversed, A <-> T and C <-> G in upper case, every other byte as it is); if
+ *     lt_i = lq_i = 0 then d_i = 0; d_i is computed only in exact mode.  block = k + sum (c_i + max(lt_i, lq_i)).  Seed
+ *     mode: matches = k + sum c_i.  Exact mode: matches = k + sum (c_i + max(lt_i, lq_i) - d_i), never negative because
+ *     d_i <= max(lt_i, lq_i).  Target range [x_0, x_{m-1} + k).  Query range in forward coordinates: [y_0, y_{m-1} + k) for
+ *     s = 0, [qlen - y_{m-1} - k, qlen - y_0) for s = 1.
+ *  8. output: one line per chain: the twelve PAF columns ('+' / '-' in column 5, mapping quality 255), then cm:i:<anchors>,
+ *     s1:i:<score> and, in exact mode, NM:i:<sum d_i>.  Lines are ordered by (query record, target record, strand, order of
+ *     emission in the group).  On any error nothing is written.
+ *  9. limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs, at most 2^30
+ *     distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k below 2^31; everything resident together, otherwise MSGPU_E_NOMEM
+ *     naming the sizes.  Larger inputs are out of scope (no target batching). */
+typedef struct msgpu_mapctx msgpu_mapctx; /* a device context of the stage */
+typedef struct msgpu_map_result msgpu_map_result;
+typedef struct msgpu_map_params {
+  int32_t  k, w;
+  uint32_t max_occ;
+  int32_t  max_gap, bandwidth, max_pred, min_score, min_count;
+  int32_t  exact, band, ava, reserved;
+} msgpu_map_params;
+void        msgpu_map_default_params(msgpu_map_params *p);
+int         msgpu_map_create(int device, msgpu_mapctx **out); /* MSGPU_E_NODEVICE without a GPU */
+void        msgpu_map_destroy(msgpu_mapctx *ctx);
+const char *msgpu_map_last_error(const msgpu_mapctx *ctx);
+typedef struct msgpu_map_chain { /* in output order: entry i is line i of the PAF */
+  uint32_t query, target;  /* record indices */
+  uint32_t strand, n_anchors;
+  int32_t  score;
+  uint32_t nm;             /* sum of d_i (exact mode, else 0) */
+  uint32_t q_start, q_end, t_start, t_end;
+  uint32_t matches, block;
+} msgpu_map_chain;
+typedef struct msgpu_map_stats {
+  uint64_t n_records[2], n_bases[2], n_minimizers[2]; /* targets, queries */
+  uint64_t n_keys, n_index_entries, n_keys_dropped, n_entries_dropped; /* rule 3 */
+  uint64_t n_anchors, n_groups;
+  uint64_t n_groups_kept, n_groups_small, n_groups_large; /* behind rule 6's pre-filter; at most 16 anchors; more */
+  uint64_t largest_group;
+  uint64_t n_chains, n_chains_below_score, n_chains_below_count, n_chains_cut; /* emitted; dropped; emitted and cut at a used anchor */
+  uint64_t n_pairs, n_pairs_capped; /* exact mode: segment pairs, and those beyond the band */
+  uint64_t n_lost_publications, bytes_out;
+  uint64_t group_hist[16];          /* kept groups by floor(log2(anchors)), the last bin open */
+  msgpu_map_params params;
+  float load_ms;                    /* host wall: both files into their stores */
+  float sketch_ms, sort_ms, table_ms, anchors_ms, group_ms, chain_ms, backtrack_ms, pairs_ms, distance_ms, copy_ms; /* device, by events */
+  float host_ms;                    /* host: the lines (wall) */
+  float wall_ms;
+} msgpu_map_stats;
+/* The whole stage.  With ava, queries_path is NULL or the targets' path.  flags must be 0; budget_bytes is ignored (rule 9).
+ * Synchronous; the PAF is kept in the result. */
+int         msgpu_map_run(msgpu_mapctx *ctx, const msgpu_map_params *params, const char *targets_path, const char *queries_path,
+                          uint32_t flags, uint64_t budget_bytes, msgpu_map_result **out);
+int         msgpu_map_result_stats(const msgpu_map_result *r, msgpu_map_stats *out);
+int         msgpu_map_result_chains(const msgpu_map_result *r, const msgpu_map_chain **chains, uint64_t *n);
+const char *msgpu_map_result_text(const msgpu_map_result *r, uint64_t *len);
+void        msgpu_map_result_free(msgpu_map_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

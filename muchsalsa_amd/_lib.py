@@ -195,6 +195,29 @@ class UgUnitig(C.Structure):  # msgpu_ug_unitig
 UG_TEXT_ALL, UG_TEXT_CUT = 0, 1
 
 
+class MapParams(C.Structure):  # msgpu_map_params
+    _fields_ = [("k", C.c_int32), ("w", C.c_int32), ("max_occ", C.c_uint32)] + [
+        (n, C.c_int32) for n in ("max_gap", "bandwidth", "max_pred", "min_score", "min_count", "exact", "band", "ava", "reserved")]
+
+
+class MapChain(C.Structure):  # msgpu_map_chain
+    _fields_ = [("query", C.c_uint32), ("target", C.c_uint32), ("strand", C.c_uint32), ("n_anchors", C.c_uint32),
+                ("score", C.c_int32)] + [(n, C.c_uint32) for n in ("nm", "q_start", "q_end", "t_start", "t_end", "matches",
+                                                                   "block")]
+
+
+class MapStats(C.Structure):  # msgpu_map_stats
+    _fields_ = ([("n_records", C.c_uint64 * 2), ("n_bases", C.c_uint64 * 2), ("n_minimizers", C.c_uint64 * 2)] +
+                [(n, C.c_uint64) for n in ("n_keys", "n_index_entries", "n_keys_dropped", "n_entries_dropped", "n_anchors",
+                                           "n_groups", "n_groups_kept", "n_groups_small", "n_groups_large", "largest_group",
+                                           "n_chains", "n_chains_below_score", "n_chains_below_count", "n_chains_cut", "n_pairs",
+                                           "n_pairs_capped", "n_lost_publications", "bytes_out")] +
+                [("group_hist", C.c_uint64 * 16), ("params", MapParams)] +
+                [(n, C.c_float) for n in ("load_ms", "sketch_ms", "sort_ms", "table_ms", "anchors_ms", "group_ms", "chain_ms",
+                                          "backtrack_ms", "pairs_ms", "distance_ms", "copy_ms", "host_ms", "wall_ms")] +
+                [("reserved", C.c_uint32)])
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -424,6 +447,16 @@ SYMBOLS = [
     ("msgpu_ug_result_unitigs", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgUnitig)), C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_free", None, [C.c_void_p]),
+    ("msgpu_map_default_params", None, [C.POINTER(MapParams)]),
+    ("msgpu_map_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_map_destroy", None, [C.c_void_p]),
+    ("msgpu_map_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_map_run", C.c_int, [C.c_void_p, C.POINTER(MapParams), C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
+                                C.POINTER(C.c_void_p)]),
+    ("msgpu_map_result_stats", C.c_int, [C.c_void_p, C.POINTER(MapStats)]),
+    ("msgpu_map_result_chains", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapChain)), C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -150,6 +150,37 @@ template <int W> __device__ __forceinline__ double group_max_f64(double v) {
   }
   return v;
 }
+// The same exchanges on 64-bit integers: the maximum of every aligned group of W lanes (W = 16 or 64), in all of its lanes.
+// The mapper's chain kernels (msgpu_map.hip) reduce (score, predecessor) packed into one word with it.  All 64 lanes must
+// be active.
+template <int CTRL> __device__ __forceinline__ long long dpp_perm_max_i64(long long v) {
+  const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(static_cast<uint32_t>(v)), CTRL, 0xf, 0xf, false));
+  const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(static_cast<uint32_t>(static_cast<unsigned long long>(v) >> 32)), CTRL, 0xf, 0xf, false));
+  const long long o = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
+  return o > v ? o : v;
+}
+template <int W> __device__ __forceinline__ long long group_max_i64(long long v) {
+  static_assert(W == 16 || W == 64, "group width");
+  v = dpp_perm_max_i64<0xb1>(v);  // quad_perm:[1,0,3,2]
+  v = dpp_perm_max_i64<0x4e>(v);  // quad_perm:[2,3,0,1]
+  v = dpp_perm_max_i64<0x141>(v); // row_half_mirror
+  v = dpp_perm_max_i64<0x140>(v); // row_mirror
+  if constexpr (W == 64) {
+    const unsigned long long b = static_cast<unsigned long long>(v);
+    auto lo = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(b), static_cast<uint32_t>(b), false, false);
+    auto hi = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(b >> 32), static_cast<uint32_t>(b >> 32), false, false);
+    long long x = static_cast<long long>((static_cast<unsigned long long>(hi[0]) << 32) | lo[0]);
+    long long y = static_cast<long long>((static_cast<unsigned long long>(hi[1]) << 32) | lo[1]);
+    v = x > y ? x : y;
+    const unsigned long long d = static_cast<unsigned long long>(v);
+    lo = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(d), static_cast<uint32_t>(d), false, false);
+    hi = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(d >> 32), static_cast<uint32_t>(d >> 32), false, false);
+    x = static_cast<long long>((static_cast<unsigned long long>(hi[0]) << 32) | lo[0]);
+    y = static_cast<long long>((static_cast<unsigned long long>(hi[1]) << 32) | lo[1]);
+    v = x > y ? x : y;
+  }
+  return v;
+}
 // inclusive prefix maximum over the wavefront: lane l gets the maximum of lanes 0..l (wave_incl_scan's moves)
 __device__ __forceinline__ double wave_prefix_max_f64(double v) {
   v = dpp_max_step<0x111>(v);      // row_shr:1

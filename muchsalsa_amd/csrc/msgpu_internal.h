@@ -317,6 +317,12 @@ void launch_em_counts(hipStream_t st, const msgpu_edge *edges, const uint32_t *s
 void launch_em_gather(hipStream_t st, const msgpu_edge *edges, const msgpu_edgematch *ems, const uint32_t *sel, uint64_t n,
                       const uint64_t *off, msgpu_edgematch *out);
 
+// msgpu_seq.hip, for the mapper (msgpu_map.hip): the byte-per-base form of a store on the device (null when it is packed or
+// empty), and the furthest-reaching edit distance of msgpu_edit_distance on a DEVICE pair list, distances left on the device
+const uint8_t *seq_store_bases(const msgpu_seqctx *c, int kind, uint64_t *n_bases);
+void launch_edit_distance_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
+                                uint32_t band, uint32_t *d_out);
+
 } // namespace msgpu
 
 #endif

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "msgpu.h"
+#include "msgpu_internal.h"
 
 namespace msgpu {
 
@@ -196,6 +197,36 @@ inline int kfail(KfCtx *c, int code, const char *what, hipError_t e) {
     hipError_t _e = (expr);                                                                                            \
     if (_e != hipSuccess) return kfail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
   } while (0)
+
+// The scalar block as it stands, through the project's read-back protocol (msgpu_device.h, publish_to_host): one wavefront
+// writes it into the mapped mirror and publishes a sequence number, the host polls for it.  A stream that ends without
+// the number arriving is answered by a copy, and counted.  d = the block on the device (SC_COUNT words), h = its page-locked,
+// device-mapped mirror with the sequence number behind it, h_dev = the device's address of the mirror (null: every read-back
+// is a copy).  One definition for the stages that own such a block (msgpu_unitig.hip, msgpu_map.hip).
+inline int kf_read_scalars(KfCtx *c, uint64_t *d, uint64_t *h, uint64_t *h_dev, uint64_t &seq_no, uint64_t &lost) {
+  if (h_dev) {
+    const uint64_t seq = ++seq_no;
+    launch_publish_scalars(c->stream, d, HostPublish{h_dev, seq});
+    KHIP(c, hipGetLastError());
+    volatile uint64_t *flag = h + SC_COUNT;
+    for (uint64_t spins = 1;; ++spins) {
+      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
+      __builtin_ia32_pause();
+      if ((spins & 0xffff) == 0) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) {
+          if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
+          break;
+        }
+        if (q != hipErrorNotReady) break;
+      }
+    }
+    ++lost;
+  }
+  KHIP(c, hipMemcpyAsync(h, d, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  KHIP(c, hipStreamSynchronize(c->stream));
+  return MSGPU_OK;
+}
 
 struct KfDev { // device memory freed on every way out of msgpu_kf_run
   std::vector<void *> p;

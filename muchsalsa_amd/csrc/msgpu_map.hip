@@ -1,0 +1,1111 @@
+// msgpu_map.hip -- the seed-and-chain mapper (include/msgpu.h, "unitig-to-read mapping").
+//
+// Both files go through the sequence loader (msgpu_seq_parse_upload): the bases lie as bytes in HBM, the host keeps names,
+// lengths and offsets.  Everything behind that is count-then-write on the device:
+//   k_mp_sketch    a workgroup per tile of 256 k-mer start positions: the (hash, key, strand) of the tile and of w - 1
+//                  positions on either side go into LDS (every thread rolls k bytes through KfRoll), then a thread per
+//                  position decides rule 2 from its 2 w - 1 neighbours.  Pass 1 counts per tile, pass 2 writes
+//   index          one radix_sort_pairs over bits [0, 2k), run lengths and starts of the keys, k_kf_table over the
+//                  distinct keys; the occurrence cap is applied where a query minimizer looks its key up
+//   k_mp_anchors   count per query minimizer, exclusive scan, expansion; two stable radix sorts bring the anchors into
+//                  (group, x, y) order; run lengths of the group keys are the groups; k_mp_classify applies rule 6's
+//                  pre-filter and splits the kept groups into those of at most 16 anchors and the others
+//   k_mp_chain     rule 5, a wavefront per group: lane l holds the anchors l, l + 64, ... of the group, so the 64
+//                  predecessors of anchor i are one per lane; argmax by DPP / permlane moves (group_max_i64)
+//   k_mp_chain16   the same for groups of at most 16 anchors, four to a wavefront, a row of 16 lanes each
+//   k_mp_walk      rule 6 behind a segmented sort by (f descending, index ascending): a thread per group
+//   k_mp_pairs     exact mode: the segment pairs of the emitted chains; distances by edit_distance_fr_wave (msgpu_seq.hip)
+//                  against a forward and a reverse-complemented copy of the queries (the existing gather)
+// Integers only.  Kernel rules: vector stores and vector atomics only; no inline asm.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/device/device_segmented_reduce.hpp>
+
+#include <chrono>
+#include <memory>
+#include <new>
+#include <string>
+#include <thread>
+
+#include "host_pool.h"
+#include "msgpu_device.h"
+#include "msgpu_internal.h"
+#include "msgpu_kmer_shared.h"
+
+namespace msgpu {
+
+constexpr uint32_t MP_NONE = 0xffffffffu;
+constexpr long long MP_MIN = static_cast<long long>(0x8000000000000000ull);
+
+struct MpRecs { // the records of a store as the kernels see them
+  const uint8_t  *bases;
+  const uint64_t *off; // ascending
+  const uint32_t *len;
+  uint32_t        n;
+  uint64_t        n_bases;
+};
+
+// the record that holds byte p of the store, or MP_NONE (padding between records)
+__device__ inline uint32_t mp_record(const MpRecs &R, uint64_t p) {
+  uint32_t lo = 0, hi = R.n; // the last r with off[r] <= p
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (R.off[mid] <= p) lo = mid + 1;
+    else hi = mid;
+  }
+  if (!lo) return MP_NONE;
+  const uint32_t r = lo - 1;
+  return p < R.off[r] + R.len[r] ? r : MP_NONE;
+}
+
+constexpr int MP_TILE = 256, MP_SPAN = MP_TILE + 2 * 63;
+
+// rule 2.  WRITE = false: minimizers per tile; WRITE = true: (key, record << 32 | position << 1 | strand) at the tile's offset
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_mp_sketch(MpRecs R, int k, int w, uint32_t *tile_cnt, const uint64_t *tile_off,
+                                                   uint64_t *keys, uint64_t *vals, uint64_t cap) {
+  __shared__ uint64_t s_h[MP_SPAN], s_key[MP_SPAN];
+  __shared__ uint8_t  s_v[MP_SPAN]; // bit 0: a k-mer starts here, bit 1: its strand
+  __shared__ uint32_t s_wave[4];
+  const long long base = static_cast<long long>(blockIdx.x) * MP_TILE - (w - 1);
+  const int       span = MP_TILE + 2 * (w - 1);
+  for (int e = threadIdx.x; e < span; e += 256) {
+    const long long p = base + e;
+    uint8_t         v = 0;
+    uint64_t        h = 0, key = 0;
+    if (p >= 0 && static_cast<uint64_t>(p) < R.n_bases) {
+      const uint32_t r = mp_record(R, static_cast<uint64_t>(p));
+      if (r != MP_NONE && static_cast<uint64_t>(p) + k <= R.off[r] + R.len[r]) {
+        KfRoll<uint64_t> roll(k);
+        bool             ok = false;
+        for (int j = 0; j < k; ++j) ok = roll.step(R.bases[p + j], key);
+        if (ok) {
+          v = static_cast<uint8_t>(1u | (roll.rc < roll.fw ? 2u : 0u));
+          h = kf_hash(key);
+        }
+      }
+    }
+    s_h[e]   = h;
+    s_key[e] = key;
+    s_v[e]   = v;
+  }
+  __syncthreads();
+  const int e = static_cast<int>(threadIdx.x) + (w - 1);
+  bool      is_min = false;
+  if (s_v[e]) { // the positions it beats on either side, as far as a window reaches
+    const uint64_t h = s_h[e];
+    int            gl = 0, gr = 0;
+    while (gl < w - 1 && s_v[e - gl - 1] && h < s_h[e - gl - 1]) ++gl;
+    while (gl + gr < w - 1 && s_v[e + gr + 1] && h <= s_h[e + gr + 1]) ++gr;
+    is_min = gl + gr >= w - 1;
+  }
+  uint32_t       total;
+  const uint32_t at = block_excl_scan_256(is_min ? 1u : 0u, s_wave, &total);
+  if (!WRITE) {
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+    return;
+  }
+  if (!is_min) return;
+  const uint64_t p = static_cast<uint64_t>(base + e), slot = tile_off[blockIdx.x] + at;
+  const uint32_t r = mp_record(R, p);
+  if (slot < cap && r != MP_NONE) {
+    keys[slot] = s_key[e];
+    vals[slot] = (static_cast<uint64_t>(r) << 32) | ((p - R.off[r]) << 1) | (s_v[e] >> 1);
+  }
+}
+
+// a device word into the scalar block
+template <class T> __global__ void k_mp_put(uint64_t *scalars, int slot, const T *src) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) scalars[slot] = static_cast<uint64_t>(*src);
+}
+
+__device__ inline void mp_count(bool mine, kf_ull *counter, kf_ull each = 1) { // all lanes of the wavefront call
+  const uint64_t who = __ballot(mine);
+  if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(counter, each * __popcll(who));
+}
+
+// the keys rule 3 leaves out
+__global__ __launch_bounds__(256) void k_mp_occ(const uint32_t *cnt, uint32_t n, uint32_t max_occ, kf_ull *keys_out, kf_ull *entries_out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const bool     over = i < n && cnt[i] > max_occ;
+  mp_count(over, keys_out);
+  if (over) atomicAdd(entries_out, static_cast<kf_ull>(cnt[i]));
+}
+
+struct MpIndex {
+  const uint64_t *ukeys;  // the distinct keys, ascending
+  const uint32_t *ucnt, *ustart, *slots;
+  uint32_t        mask, max_occ;
+  const uint64_t *vals;   // the entries in key order
+};
+
+// rule 4.  WRITE = false: anchors per query minimizer
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_mp_anchors(MpIndex X, const uint64_t *qkeys, const uint64_t *qvals, uint64_t nq,
+                                                    const uint32_t *qlen, int k, int ava, uint32_t *cnt, const uint64_t *off,
+                                                    uint64_t *g, uint64_t *xy, uint64_t cap) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= nq) return;
+  const uint32_t j = kf_find(X.ukeys, X.slots, X.mask, qkeys[i]);
+  uint32_t       c = 0;
+  if (j != KF_EMPTY && X.ucnt[j] <= X.max_occ) {
+    const uint64_t  qv = qvals[i];
+    const uint32_t  q = static_cast<uint32_t>(qv >> 32), qpos = static_cast<uint32_t>(qv & 0xffffffffu) >> 1, qs = qv & 1u;
+    const uint64_t *ent = X.vals + X.ustart[j];
+    const uint32_t  m = X.ucnt[j];
+    if (!WRITE && !ava) c = m;
+    else
+      for (uint32_t e = 0; e < m; ++e) {
+        const uint64_t tv = ent[e];
+        const uint32_t t = static_cast<uint32_t>(tv >> 32);
+        if (ava && q >= t) continue;
+        if (WRITE) {
+          const uint32_t s = qs ^ static_cast<uint32_t>(tv & 1u), x = static_cast<uint32_t>(tv & 0xffffffffu) >> 1;
+          const uint32_t y = s ? qlen[q] - static_cast<uint32_t>(k) - qpos : qpos;
+          const uint64_t slot = off[i] + c;
+          if (slot < cap) {
+            g[slot]  = (static_cast<uint64_t>(q) << 32) | (static_cast<uint64_t>(t) << 1) | s;
+            xy[slot] = (static_cast<uint64_t>(x) << 32) | y;
+          }
+        }
+        ++c;
+      }
+  }
+  if (!WRITE) cnt[i] = c;
+}
+
+// rule 6's pre-filter and the size classes
+__global__ __launch_bounds__(256) void k_mp_classify(const uint32_t *gcnt, uint32_t n_groups, int k, int min_score, int min_count,
+                                                     uint32_t *flag_small, uint32_t *flag_large, kf_ull *hist, kf_ull *largest) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_groups) return;
+  const uint32_t n = gcnt[i];
+  const bool     keep = static_cast<long long>(n) >= min_count && static_cast<long long>(n) * k >= min_score;
+  flag_small[i] = keep && n <= 16;
+  flag_large[i] = keep && n > 16;
+  if (keep) {
+    atomicAdd(&hist[31 - __clz(n | 1u)], 1ull);
+    atomicMax(largest, static_cast<kf_ull>(n));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mp_lists(const uint32_t *gcnt, const uint32_t *gstart, uint32_t n_groups, const uint32_t *flag_small,
+                                                  const uint32_t *flag_large, const uint32_t *pos_small, const uint32_t *pos_large,
+                                                  uint32_t *list_small, uint32_t *list_large, uint32_t *list_kept, uint32_t *seg_begin,
+                                                  uint32_t *seg_end) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_groups) return;
+  if (flag_small[i]) list_small[pos_small[i]] = i;
+  if (flag_large[i]) list_large[pos_large[i]] = i;
+  if (flag_small[i] || flag_large[i]) {
+    const uint32_t kk = pos_small[i] + pos_large[i];
+    list_kept[kk] = i;
+    seg_begin[kk] = gstart[i];
+    seg_end[kk]   = gstart[i] + gcnt[i];
+  }
+}
+
+struct MpChainArgs {
+  const uint32_t *list;
+  uint32_t        n_list;
+  const uint32_t *gstart, *gcnt;
+  const uint64_t *xy;
+  int32_t        *f, *pred;
+  uint64_t       *sortkey; // f << 32 | ~index: descending order is (f descending, index ascending)
+  int             k, max_gap, bandwidth;
+};
+
+// what predecessor j offers anchor i, packed with its distance d = i - 1 - j so that the largest value is the best score and,
+// among equals, the largest j; MP_MIN: j is no predecessor
+__device__ __forceinline__ long long mp_offer(const MpChainArgs &a, int xi, int yi, int xj, int yj, int fj, int d, bool there) {
+  const int dx = xi - xj, dy = yi - yj;
+  if (!there || dx <= 0 || dy <= 0 || dx > a.max_gap || dy > a.max_gap) return MP_MIN;
+  const uint32_t dd = static_cast<uint32_t>(dx > dy ? dx - dy : dy - dx);
+  if (dd > static_cast<uint32_t>(a.bandwidth)) return MP_MIN;
+  const int       gain = min(min(dx, dy), a.k);
+  const long long pen = dd ? static_cast<long long>((static_cast<uint64_t>(dd) * static_cast<uint32_t>(a.k)) / 100u) + ((31 - __clz(dd)) >> 1) : 0;
+  return (static_cast<long long>(fj) + gain - pen) * 64 + (63 - d);
+}
+
+__global__ __launch_bounds__(256) void k_mp_chain(MpChainArgs a) {
+  const uint32_t wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int      lane = threadIdx.x & 63;
+  if (wv >= a.n_list) return; // (whole wavefronts leave)
+  const uint32_t gi = a.list[wv], s0 = a.gstart[gi], n = a.gcnt[gi];
+  int            px = 0, py = 0, pf = 0; // the block of 64 anchors in front of the current one
+  for (uint32_t b0 = 0; b0 < n; b0 += 64) {
+    const uint32_t idx = b0 + lane;
+    const bool     have = idx < n;
+    const uint64_t v = have ? a.xy[s0 + idx] : 0;
+    const int      cx = static_cast<int>(v >> 32), cy = static_cast<int>(static_cast<uint32_t>(v));
+    int            cf = 0, cp = -1;
+    const int      m = static_cast<int>(min(64u, n - b0));
+    for (int c = 0; c < m; ++c) {
+      const int  xi = rl_i32(cx, c), yi = rl_i32(cy, c);
+      const bool cur = lane < c;
+      const int  d = cur ? c - 1 - lane : c + 63 - lane;
+      long long  best = mp_offer(a, xi, yi, cur ? cx : px, cur ? cy : py, cur ? cf : pf, d, cur || b0 > 0);
+      best = group_max_i64<64>(best);
+      if (lane == c) {
+        const long long score = best >> 6;
+        if (best != MP_MIN && score > a.k) {
+          cf = static_cast<int>(score);
+          cp = static_cast<int>(b0) + c - 1 - (63 - static_cast<int>(best & 63));
+        } else {
+          cf = a.k;
+        }
+      }
+    }
+    if (have) {
+      a.f[s0 + idx]       = cf;
+      a.pred[s0 + idx]    = cp;
+      a.sortkey[s0 + idx] = (static_cast<uint64_t>(static_cast<uint32_t>(cf)) << 32) | (0xffffffffu - idx);
+    }
+    px = cx;
+    py = cy;
+    pf = cf;
+  }
+}
+
+// lane c of every row of 16 to all lanes of the row (row_newbcast)
+template <int C> __device__ __forceinline__ int mp_row_bcast(int v) { return __builtin_amdgcn_mov_dpp(v, 0x150 + C, 0xf, 0xf, false); }
+
+template <int C> __device__ __forceinline__ void mp_step16(const MpChainArgs &a, int r, uint32_t n, int cx, int cy, int &cf, int &cp) {
+  const int xi = mp_row_bcast<C>(cx), yi = mp_row_bcast<C>(cy);
+  long long best = mp_offer(a, xi, yi, cx, cy, cf, C - 1 - r, r < C && static_cast<uint32_t>(C) < n);
+  best = group_max_i64<16>(best);
+  if (r == C) {
+    const long long score = best >> 6;
+    if (best != MP_MIN && score > a.k) {
+      cf = static_cast<int>(score);
+      cp = C - 1 - (63 - static_cast<int>(best & 63));
+    } else {
+      cf = a.k;
+    }
+  }
+}
+
+// groups of at most 16 anchors: one per row of 16 lanes, lane r holds anchor r from start to end
+__global__ __launch_bounds__(256) void k_mp_chain16(MpChainArgs a) {
+  const uint32_t sg = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int      r = threadIdx.x & 15;
+  uint32_t       s0 = 0, n = 0;
+  if (sg < a.n_list) { // (a row without a group stays: the reductions need all lanes)
+    const uint32_t gi = a.list[sg];
+    s0 = a.gstart[gi];
+    n  = a.gcnt[gi];
+  }
+  const bool     have = static_cast<uint32_t>(r) < n;
+  const uint64_t v = have ? a.xy[s0 + r] : 0;
+  const int      cx = static_cast<int>(v >> 32), cy = static_cast<int>(static_cast<uint32_t>(v));
+  int            cf = 0, cp = -1;
+  mp_step16<0>(a, r, n, cx, cy, cf, cp);
+  mp_step16<1>(a, r, n, cx, cy, cf, cp);
+  mp_step16<2>(a, r, n, cx, cy, cf, cp);
+  mp_step16<3>(a, r, n, cx, cy, cf, cp);
+  mp_step16<4>(a, r, n, cx, cy, cf, cp);
+  mp_step16<5>(a, r, n, cx, cy, cf, cp);
+  mp_step16<6>(a, r, n, cx, cy, cf, cp);
+  mp_step16<7>(a, r, n, cx, cy, cf, cp);
+  mp_step16<8>(a, r, n, cx, cy, cf, cp);
+  mp_step16<9>(a, r, n, cx, cy, cf, cp);
+  mp_step16<10>(a, r, n, cx, cy, cf, cp);
+  mp_step16<11>(a, r, n, cx, cy, cf, cp);
+  mp_step16<12>(a, r, n, cx, cy, cf, cp);
+  mp_step16<13>(a, r, n, cx, cy, cf, cp);
+  mp_step16<14>(a, r, n, cx, cy, cf, cp);
+  mp_step16<15>(a, r, n, cx, cy, cf, cp);
+  if (have) {
+    a.f[s0 + r]       = cf;
+    a.pred[s0 + r]    = cp;
+    a.sortkey[s0 + r] = (static_cast<uint64_t>(static_cast<uint32_t>(cf)) << 32) | (0xffffffffu - static_cast<uint32_t>(r));
+  }
+}
+
+struct MpLink { // rule 7 on one link
+  uint32_t c, lt, lq;
+};
+__device__ inline MpLink mp_link(uint64_t vi, uint64_t vj, int k) {
+  const uint32_t dx = static_cast<uint32_t>(vi >> 32) - static_cast<uint32_t>(vj >> 32);
+  const uint32_t dy = static_cast<uint32_t>(vi) - static_cast<uint32_t>(vj);
+  const uint32_t c = min(min(dx, dy), static_cast<uint32_t>(k));
+  return MpLink{c, dx - c, dy - c};
+}
+
+struct MpRaw { // a chain as the walk leaves it, in the slot of its group's e-th anchor
+  uint32_t first, last; // local indices: the start of the walk (the largest x) and its end (the smallest)
+  uint32_t n_anchors, block, seed_matches, n_pairs;
+  int32_t  score;
+};
+
+// rule 6: a thread per kept group
+__global__ __launch_bounds__(64) void k_mp_walk(const uint32_t *list_kept, uint32_t n_kept, const uint32_t *gstart, const uint32_t *gcnt,
+                                                const uint64_t *xy, const int32_t *f, const int32_t *pred, const uint64_t *sorted,
+                                                uint8_t *used, int k, int min_score, int min_count, MpRaw *raw, uint32_t *n_emit,
+                                                kf_ull *drop_score, kf_ull *drop_count, kf_ull *cut_chains) {
+  const uint32_t kk = blockIdx.x * 64 + threadIdx.x;
+  uint32_t       by_score = 0, by_count = 0, cuts = 0;
+  if (kk < n_kept) {
+    const uint32_t gi = list_kept[kk], s0 = gstart[gi], n = gcnt[gi];
+    uint32_t       emitted = 0;
+    for (uint32_t p = 0; p < n; ++p) {
+      const uint32_t first = 0xffffffffu - static_cast<uint32_t>(sorted[s0 + p]);
+      if (used[s0 + first]) continue;
+      MpRaw    c{first, first, 0, static_cast<uint32_t>(k), static_cast<uint32_t>(k), 0, f[s0 + first]};
+      bool     cut = false;
+      for (uint32_t cur = first;;) {
+        used[s0 + cur] = 1;
+        ++c.n_anchors;
+        c.last = cur;
+        const int32_t pr = pred[s0 + cur];
+        if (pr < 0) break;
+        if (used[s0 + pr]) {
+          c.score -= f[s0 + pr];
+          cut = true;
+          break;
+        }
+        const MpLink l = mp_link(xy[s0 + cur], xy[s0 + pr], k);
+        c.block += l.c + max(l.lt, l.lq);
+        c.seed_matches += l.c;
+        c.n_pairs += (l.lt | l.lq) ? 1u : 0u;
+        cur = static_cast<uint32_t>(pr);
+      }
+      if (c.score >= min_score && static_cast<long long>(c.n_anchors) >= min_count) {
+        raw[s0 + emitted++] = c;
+        cuts += cut;
+      } else if (c.score < min_score) {
+        ++by_score;
+      } else {
+        ++by_count;
+      }
+    }
+    n_emit[kk] = emitted;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    by_score += __shfl_xor(by_score, o);
+    by_count += __shfl_xor(by_count, o);
+    cuts += __shfl_xor(cuts, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (by_score) atomicAdd(drop_score, static_cast<kf_ull>(by_score));
+    if (by_count) atomicAdd(drop_count, static_cast<kf_ull>(by_count));
+    if (cuts) atomicAdd(cut_chains, static_cast<kf_ull>(cuts));
+  }
+}
+
+struct MpWhere { // where a chain's anchors are
+  uint32_t s0, first;
+};
+
+// the chain table in output order (rule 8), without the exact-mode figures
+__global__ __launch_bounds__(256) void k_mp_table(const uint32_t *list_kept, uint32_t n_kept, const uint32_t *gstart, const uint64_t *ug,
+                                                  const uint64_t *xy, const MpRaw *raw, const uint32_t *n_emit, const uint32_t *chain_off,
+                                                  const uint32_t *qlen, int k, msgpu_map_chain *out, MpWhere *where, uint32_t *n_pairs,
+                                                  uint32_t cap) {
+  const uint32_t kk = blockIdx.x * 256 + threadIdx.x;
+  if (kk >= n_kept) return;
+  const uint32_t gi = list_kept[kk], s0 = gstart[gi];
+  const uint64_t g = ug[gi];
+  const uint32_t q = static_cast<uint32_t>(g >> 32), t = static_cast<uint32_t>(g & 0xffffffffu) >> 1, s = g & 1u;
+  for (uint32_t e = 0; e < n_emit[kk]; ++e) {
+    const uint32_t at = chain_off[kk] + e;
+    if (at >= cap) return;
+    const MpRaw    c = raw[s0 + e];
+    const uint64_t lo = xy[s0 + c.last], hi = xy[s0 + c.first];
+    const uint32_t y0 = static_cast<uint32_t>(lo), y1 = static_cast<uint32_t>(hi);
+    msgpu_map_chain o;
+    o.query     = q;
+    o.target    = t;
+    o.strand    = s;
+    o.n_anchors = c.n_anchors;
+    o.score     = c.score;
+    o.nm        = 0;
+    o.t_start   = static_cast<uint32_t>(lo >> 32);
+    o.t_end     = static_cast<uint32_t>(hi >> 32) + k;
+    o.q_start   = s ? qlen[q] - y1 - k : y0;
+    o.q_end     = s ? qlen[q] - y0 : y1 + k;
+    o.matches   = c.seed_matches;
+    o.block     = c.block;
+    out[at]     = o;
+    where[at]   = MpWhere{s0, c.first};
+    n_pairs[at] = c.n_pairs;
+  }
+}
+
+// exact mode: the segment pairs of every emitted chain, from its last link to its first
+__global__ __launch_bounds__(256) void k_mp_pairs(const msgpu_map_chain *chains, const MpWhere *where, uint32_t n_chains, const uint64_t *xy,
+                                                  const int32_t *pred, const uint32_t *pair_off, const uint64_t *toff, const uint64_t *qoff,
+                                                  uint64_t rc_base, int k, msgpu_align_pair *pairs, uint32_t cap) {
+  const uint32_t ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci >= n_chains) return;
+  const msgpu_map_chain c = chains[ci];
+  const uint32_t        s0 = where[ci].s0;
+  const uint64_t        ta = toff[c.target], qa = qoff[c.query] + (c.strand ? rc_base : 0);
+  uint32_t              at = pair_off[ci], cur = where[ci].first;
+  for (uint32_t l = 1; l < c.n_anchors; ++l) {
+    if (pred[s0 + cur] < 0) break; // (a chain of n_anchors has n_anchors - 1 links)
+    const uint32_t pr = static_cast<uint32_t>(pred[s0 + cur]);
+    const uint64_t vi = xy[s0 + cur];
+    const MpLink   L = mp_link(vi, xy[s0 + pr], k);
+    if ((L.lt | L.lq) && at < cap) {
+      const uint32_t xe = static_cast<uint32_t>(vi >> 32) + k - L.c, ye = static_cast<uint32_t>(vi) + k - L.c;
+      pairs[at++] = msgpu_align_pair{ta + xe - L.lt, qa + ye - L.lq, L.lt, L.lq};
+    }
+    cur = pr;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mp_exact(msgpu_map_chain *chains, uint32_t n_chains, const uint32_t *nm) {
+  const uint32_t ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci >= n_chains) return;
+  chains[ci].nm      = nm[ci];
+  chains[ci].matches = chains[ci].block - nm[ci];
+}
+
+__global__ __launch_bounds__(256) void k_mp_capped(const uint32_t *dist, uint32_t n, uint32_t band, kf_ull *capped) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  mp_count(i < n && dist[i] > band, capped);
+}
+
+} // namespace msgpu
+
+using namespace msgpu;
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+struct msgpu_mapctx : msgpu::KfCtx {
+  msgpu_seqctx *seq = nullptr;
+  uint64_t     *d_scalars = nullptr, *h_scalars = nullptr, *h_scalars_dev = nullptr; // as msgpu_ugctx
+  uint64_t      seq_no = 0, lost = 0;
+};
+
+struct msgpu_map_result {
+  msgpu_map_stats              stats{};
+  std::vector<msgpu_map_chain> chains;
+  std::string                  text;
+};
+
+namespace {
+
+enum { MP_SC_DROPK = 0, MP_SC_DROPE, MP_SC_LARGEST, MP_SC_TOTAL, MP_SC_TOTAL2, MP_SC_TOTAL3, MP_SC_DROP_SCORE, MP_SC_DROP_COUNT, MP_SC_CUT,
+       MP_SC_CAPPED };
+static_assert(MP_SC_CAPPED < SC_COUNT, "the scalar block");
+
+int mp_read_scalars(msgpu_mapctx *c) { return kf_read_scalars(c, c->d_scalars, c->h_scalars, c->h_scalars_dev, c->seq_no, c->lost); } // (msgpu_kmer_shared.h)
+
+inline uint32_t mp_grid(uint64_t n, uint32_t per = 256) { return static_cast<uint32_t>((n + per - 1) / per); }
+inline kf_ull  *mp_slot(msgpu_mapctx *c, int slot) { return reinterpret_cast<kf_ull *>(c->d_scalars + slot); }
+
+// exclusive scan of n + 1 words (the last is the caller's zero), so out[n] is the total
+template <class Out> int mp_scan(msgpu_mapctx *c, KfDev &D, const uint32_t *in, Out *out, uint64_t n_plus_1) {
+  size_t need = 0;
+  KHIP(c, rocprim::exclusive_scan(nullptr, need, in, out, static_cast<Out>(0), n_plus_1, rocprim::plus<Out>(), c->stream));
+  uint8_t *tmp;
+  KHIP(c, D.get(&tmp, need));
+  KHIP(c, rocprim::exclusive_scan(tmp, need, in, out, static_cast<Out>(0), n_plus_1, rocprim::plus<Out>(), c->stream));
+  KHIP(c, hipStreamSynchronize(c->stream));
+  D.drop(tmp);
+  return MSGPU_OK;
+}
+
+struct MpFile { // a file in its store
+  msgpu_seqfile *f = nullptr;
+  MpRecs         recs{};
+  uint64_t      *d_off = nullptr;
+  uint32_t      *d_len = nullptr;
+  ~MpFile() { msgpu_seq_free(f); }
+};
+
+int mp_load(msgpu_mapctx *c, KfDev &D, const char *path, int kind, const char *what, MpFile &F) {
+  int rc = msgpu_seq_parse_upload(c->seq, kind, path, -1, &F.f);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "%s %s: %s", what, path, msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  const uint32_t        n = msgpu_seq_count(F.f);
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  try {
+    off.resize(n);
+    len.resize(n);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  uint64_t n_bases = 0;
+  F.recs.bases = seq_store_bases(c->seq, kind, &n_bases);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t L = msgpu_seq_length(F.f, i);
+    off[i] = msgpu_seq_offset(F.f, i);
+    if (L >= (1ull << 31)) {
+      snprintf(c->err, sizeof(c->err), "%s record %u has %llu bases; the limit is 2^31 - 1", what, i, static_cast<kf_ull>(L));
+      return MSGPU_E_ARG;
+    }
+    if ((i && off[i] < off[i - 1] + len[i - 1]) || off[i] + L > n_bases) {
+      snprintf(c->err, sizeof(c->err), "%s record %u does not lie behind record %u in the store", what, i, i ? i - 1 : 0);
+      return MSGPU_E_STATE;
+    }
+    len[i] = static_cast<uint32_t>(L);
+  }
+  if (n_bases >= (1ull << 38)) {
+    snprintf(c->err, sizeof(c->err), "%s: %llu bases; the limit is 2^38 - 1", what, static_cast<kf_ull>(n_bases));
+    return MSGPU_E_ARG;
+  }
+  KHIP(c, D.get(&F.d_off, n));
+  KHIP(c, D.get(&F.d_len, n));
+  if (n) {
+    KHIP(c, hipMemcpyAsync(F.d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
+    KHIP(c, hipMemcpyAsync(F.d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
+    KHIP(c, hipStreamSynchronize(c->stream));
+  }
+  F.recs.off     = F.d_off;
+  F.recs.len     = F.d_len;
+  F.recs.n       = n;
+  F.recs.n_bases = n_bases;
+  return MSGPU_OK;
+}
+
+struct MpSketch {
+  uint64_t *keys = nullptr, *vals = nullptr;
+  uint64_t  n = 0;
+};
+
+int mp_sketch(msgpu_mapctx *c, KfDev &D, KfClock &clock, float *ms, const MpRecs &R, int k, int w, const char *what, MpSketch &S) {
+  hipStream_t    st = c->stream;
+  const uint32_t tiles = mp_grid(R.n_bases, MP_TILE);
+  uint32_t      *d_cnt;
+  uint64_t      *d_off;
+  KHIP(c, D.get(&d_cnt, tiles + 1ull));
+  KHIP(c, D.get(&d_off, tiles + 1ull));
+  KHIP(c, hipMemsetAsync(d_cnt, 0, (tiles + 1ull) * 4, st));
+  KHIP(c, clock.begin(ms));
+  if (tiles) hipLaunchKernelGGL((k_mp_sketch<false>), dim3(tiles), dim3(256), 0, st, R, k, w, d_cnt, nullptr, nullptr, nullptr, 0);
+  KHIP(c, hipGetLastError());
+  int rc = mp_scan<uint64_t>(c, D, d_cnt, d_off, tiles + 1ull);
+  if (rc != MSGPU_OK) return rc;
+  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_off + tiles);
+  KHIP(c, clock.end());
+  rc = mp_read_scalars(c);
+  if (rc != MSGPU_OK) return rc;
+  S.n = c->h_scalars[MP_SC_TOTAL];
+  if (S.n >= (1ull << 31)) {
+    snprintf(c->err, sizeof(c->err), "%s: %llu minimizers; the limit is 2^31 - 1", what, static_cast<kf_ull>(S.n));
+    return MSGPU_E_ARG;
+  }
+  KHIP(c, D.get(&S.keys, S.n));
+  KHIP(c, D.get(&S.vals, S.n));
+  KHIP(c, clock.begin(ms));
+  if (S.n) hipLaunchKernelGGL((k_mp_sketch<true>), dim3(tiles), dim3(256), 0, st, R, k, w, nullptr, d_off, S.keys, S.vals, S.n);
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+  KHIP(c, hipStreamSynchronize(st));
+  D.drop(d_cnt);
+  D.drop(d_off);
+  return MSGPU_OK;
+}
+
+void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_seqfile *Q, bool exact, std::string &out) {
+  char buf[224];
+  out += msgpu_seq_name(Q, ch.query);
+  int n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%c\t", static_cast<kf_ull>(msgpu_seq_length(Q, ch.query)), ch.q_start, ch.q_end,
+                   ch.strand ? '-' : '+');
+  out.append(buf, n);
+  out += msgpu_seq_name(T, ch.target);
+  n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%u\t%u\t255\tcm:i:%u\ts1:i:%d", static_cast<kf_ull>(msgpu_seq_length(T, ch.target)),
+               ch.t_start, ch.t_end, ch.matches, ch.block, ch.n_anchors, ch.score);
+  out.append(buf, n);
+  if (exact) {
+    n = snprintf(buf, sizeof(buf), "\tNM:i:%u", ch.nm);
+    out.append(buf, n);
+  }
+  out += '\n';
+}
+
+int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, const char *qpath, msgpu_map_result *res) {
+  msgpu_map_stats &S = res->stats;
+  hipStream_t      st = c->stream;
+  KfDev            D;
+  KfClock          clock;
+  clock.st = st;
+  const int  k = prm.k, w = prm.w;
+  const bool ava = prm.ava != 0, exact = prm.exact != 0;
+  const auto w0 = std::chrono::steady_clock::now();
+  auto       since = [](std::chrono::steady_clock::time_point a) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
+  };
+  KHIP(c, hipMemsetAsync(c->d_scalars, 0, SC_COUNT * sizeof(uint64_t), st));
+
+  // ---- the files
+  MpFile Tf, Qf_own;
+  int    rc = mp_load(c, D, tpath, ava ? 0 : 1, "targets", Tf);
+  if (rc != MSGPU_OK) return rc;
+  if (!ava) {
+    rc = mp_load(c, D, qpath, 0, "queries", Qf_own);
+    if (rc != MSGPU_OK) return rc;
+  }
+  const MpFile &Qf = ava ? Tf : Qf_own;
+  S.n_records[0] = Tf.recs.n;
+  S.n_records[1] = Qf.recs.n;
+  S.n_bases[0]   = Tf.recs.n_bases;
+  S.n_bases[1]   = Qf.recs.n_bases;
+  S.load_ms      = since(w0);
+
+  // ---- rule 2 on both files, rule 3
+  MpSketch Ts, Qs_own;
+  rc = mp_sketch(c, D, clock, &S.sketch_ms, Tf.recs, k, w, "targets", Ts);
+  if (rc != MSGPU_OK) return rc;
+  if (!ava) {
+    rc = mp_sketch(c, D, clock, &S.sketch_ms, Qf.recs, k, w, "queries", Qs_own);
+    if (rc != MSGPU_OK) return rc;
+  }
+  const MpSketch &Qs = ava ? Ts : Qs_own;
+  S.n_minimizers[0]  = Ts.n;
+  S.n_minimizers[1]  = Qs.n;
+  const uint32_t NT = static_cast<uint32_t>(Ts.n);
+  uint64_t      *d_ikeys, *d_ivals, *d_ukeys;
+  uint32_t      *d_ucnt, *d_ustart, *d_nruns, *d_slots;
+  KHIP(c, D.get(&d_ikeys, NT));
+  KHIP(c, D.get(&d_ivals, NT));
+  KHIP(c, D.get(&d_ukeys, NT));
+  KHIP(c, D.get(&d_ucnt, NT + 1ull));
+  KHIP(c, D.get(&d_ustart, NT + 1ull));
+  KHIP(c, D.get(&d_nruns, 1));
+  KHIP(c, hipMemsetAsync(d_nruns, 0, 4, st));
+  uint32_t n_keys = 0;
+  if (NT) {
+    size_t need = 0, need2 = 0;
+    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, Ts.keys, d_ikeys, Ts.vals, d_ivals, NT, 0, 2 * k, st));
+    KHIP(c, rocprim::run_length_encode(nullptr, need2, d_ikeys, NT, d_ukeys, d_ucnt, d_nruns, st));
+    uint8_t *tmp;
+    need = std::max(need, need2);
+    KHIP(c, D.get(&tmp, need));
+    KHIP(c, clock.begin(&S.sort_ms));
+    size_t tb = need;
+    KHIP(c, rocprim::radix_sort_pairs(tmp, tb, Ts.keys, d_ikeys, Ts.vals, d_ivals, NT, 0, 2 * k, st));
+    tb = need;
+    KHIP(c, rocprim::run_length_encode(tmp, tb, d_ikeys, NT, d_ukeys, d_ucnt, d_nruns, st));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_nruns);
+    KHIP(c, clock.end());
+    rc = mp_read_scalars(c);
+    if (rc != MSGPU_OK) return rc;
+    n_keys = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]);
+    D.drop(tmp);
+    KHIP(c, hipMemsetAsync(d_ucnt + n_keys, 0, 4, st));
+    rc = mp_scan<uint32_t>(c, D, d_ucnt, d_ustart, n_keys + 1ull);
+    if (rc != MSGPU_OK) return rc;
+  }
+  if (n_keys > (1u << 30)) { // (the table has 2^31 slots at most)
+    snprintf(c->err, sizeof(c->err), "%u distinct target minimizers; the limit is 2^30", n_keys);
+    return MSGPU_E_ARG;
+  }
+  uint32_t sn = 64;
+  while (sn < 2ull * n_keys) sn <<= 1;
+  KHIP(c, D.get(&d_slots, sn));
+  KHIP(c, hipMemsetAsync(d_slots, 0xff, sn * 4ull, st));
+  KHIP(c, clock.begin(&S.table_ms));
+  if (n_keys) {
+    hipLaunchKernelGGL(k_kf_table<uint64_t>, dim3(mp_grid(n_keys)), dim3(256), 0, st, d_ukeys, n_keys, d_slots, sn - 1);
+    hipLaunchKernelGGL(k_mp_occ, dim3(mp_grid(n_keys)), dim3(256), 0, st, d_ucnt, n_keys, prm.max_occ, mp_slot(c, MP_SC_DROPK),
+                       mp_slot(c, MP_SC_DROPE));
+  }
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+  S.n_keys          = n_keys;
+  S.n_index_entries = NT;
+  const MpIndex X{d_ukeys, d_ucnt, d_ustart, d_slots, sn - 1, prm.max_occ, d_ivals};
+
+  // ---- rule 4: count, scan, expand, two stable sorts
+  const uint64_t NQ = Qs.n;
+  uint32_t      *d_acnt;
+  uint64_t      *d_aoff;
+  KHIP(c, D.get(&d_acnt, NQ + 1));
+  KHIP(c, D.get(&d_aoff, NQ + 1));
+  KHIP(c, hipMemsetAsync(d_acnt + NQ, 0, 4, st));
+  KHIP(c, clock.begin(&S.anchors_ms));
+  if (NQ)
+    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(mp_grid(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, d_acnt,
+                       nullptr, nullptr, nullptr, 0);
+  KHIP(c, hipGetLastError());
+  rc = mp_scan<uint64_t>(c, D, d_acnt, d_aoff, NQ + 1);
+  if (rc != MSGPU_OK) return rc;
+  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_aoff + NQ);
+  KHIP(c, clock.end());
+  rc = mp_read_scalars(c);
+  if (rc != MSGPU_OK) return rc;
+  S.n_keys_dropped    = c->h_scalars[MP_SC_DROPK];
+  S.n_entries_dropped = c->h_scalars[MP_SC_DROPE];
+  S.n_anchors         = c->h_scalars[MP_SC_TOTAL];
+  if (S.n_anchors >= (1ull << 31)) {
+    snprintf(c->err, sizeof(c->err), "%llu anchors; the limit is 2^31 - 1", static_cast<kf_ull>(S.n_anchors));
+    return MSGPU_E_ARG;
+  }
+  const uint32_t A = static_cast<uint32_t>(S.n_anchors);
+  {
+    size_t free_b = 0, total_b = 0;
+    KHIP(c, hipMemGetInfo(&free_b, &total_b));
+    const uint64_t bytes = A * (4 * 8ull + 2 * 8 + 2 * 4 + 1 + 28 + 5 * 4) + (exact ? 2 * Qf.recs.n_bases : 0);
+    if (bytes > free_b) {
+      snprintf(c->err, sizeof(c->err), "%u anchors need about %llu bytes for sorting and chaining (%llu of them for the oriented copies "
+               "of the queries); %zu bytes of device memory are free", A, static_cast<kf_ull>(bytes),
+               static_cast<kf_ull>(exact ? 2 * Qf.recs.n_bases : 0), free_b);
+      return MSGPU_E_NOMEM;
+    }
+  }
+  uint64_t *d_g[2], *d_xy[2], *d_ug;
+  uint32_t *d_gcnt, *d_gstart;
+  for (int i = 0; i < 2; ++i) {
+    KHIP(c, D.get(&d_g[i], A));
+    KHIP(c, D.get(&d_xy[i], A));
+  }
+  KHIP(c, D.get(&d_ug, A));
+  KHIP(c, D.get(&d_gcnt, A + 1ull));
+  KHIP(c, D.get(&d_gstart, A + 1ull));
+  uint32_t G = 0;
+  if (A) {
+    KHIP(c, clock.begin(&S.anchors_ms));
+    hipLaunchKernelGGL((k_mp_anchors<true>), dim3(mp_grid(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, nullptr,
+                       d_aoff, d_g[0], d_xy[0], A);
+    KHIP(c, hipGetLastError());
+    KHIP(c, clock.end());
+    size_t need = 0, need2 = 0;
+    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, d_xy[0], d_xy[1], d_g[0], d_g[1], A, 0, 64, st));
+    KHIP(c, rocprim::run_length_encode(nullptr, need2, d_g[0], A, d_ug, d_gcnt, d_nruns, st));
+    need = std::max(need, need2);
+    uint8_t *tmp;
+    KHIP(c, D.get(&tmp, need));
+    KHIP(c, clock.begin(&S.group_ms));
+    size_t tb = need;
+    KHIP(c, rocprim::radix_sort_pairs(tmp, tb, d_xy[0], d_xy[1], d_g[0], d_g[1], A, 0, 64, st)); // by (x, y)
+    tb = need;
+    KHIP(c, rocprim::radix_sort_pairs(tmp, tb, d_g[1], d_g[0], d_xy[1], d_xy[0], A, 0, 64, st)); // then, stable, by group
+    tb = need;
+    KHIP(c, rocprim::run_length_encode(tmp, tb, d_g[0], A, d_ug, d_gcnt, d_nruns, st));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_nruns);
+    KHIP(c, clock.end());
+    rc = mp_read_scalars(c);
+    if (rc != MSGPU_OK) return rc;
+    G = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]);
+    D.drop(tmp);
+    KHIP(c, hipMemsetAsync(d_gcnt + G, 0, 4, st));
+    rc = mp_scan<uint32_t>(c, D, d_gcnt, d_gstart, G + 1ull);
+    if (rc != MSGPU_OK) return rc;
+  }
+  S.n_groups = G;
+  D.drop(d_g[1]);
+  D.drop(d_xy[1]);
+  D.drop(d_acnt);
+  D.drop(d_aoff);
+  const uint64_t *d_xys = d_xy[0];
+
+  // ---- rule 6's pre-filter, the size classes
+  uint32_t *d_fs, *d_fl, *d_ps, *d_pl, *d_ls, *d_ll, *d_lk, *d_sb, *d_se;
+  kf_ull   *d_hist;
+  for (uint32_t **p : {&d_fs, &d_fl, &d_ps, &d_pl}) KHIP(c, D.get(p, G + 1ull));
+  for (uint32_t **p : {&d_ls, &d_ll, &d_lk, &d_sb, &d_se}) KHIP(c, D.get(p, G));
+  KHIP(c, D.get(&d_hist, 32));
+  KHIP(c, hipMemsetAsync(d_hist, 0, 32 * 8, st));
+  KHIP(c, hipMemsetAsync(d_fs + G, 0, 4, st));
+  KHIP(c, hipMemsetAsync(d_fl + G, 0, 4, st));
+  KHIP(c, clock.begin(&S.group_ms));
+  if (G)
+    hipLaunchKernelGGL(k_mp_classify, dim3(mp_grid(G)), dim3(256), 0, st, d_gcnt, G, k, prm.min_score, prm.min_count, d_fs, d_fl, d_hist,
+                       mp_slot(c, MP_SC_LARGEST));
+  KHIP(c, hipGetLastError());
+  rc = mp_scan<uint32_t>(c, D, d_fs, d_ps, G + 1ull);
+  if (rc == MSGPU_OK) rc = mp_scan<uint32_t>(c, D, d_fl, d_pl, G + 1ull);
+  if (rc != MSGPU_OK) return rc;
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL2, d_ps + G);
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL3, d_pl + G);
+  if (G) hipLaunchKernelGGL(k_mp_lists, dim3(mp_grid(G)), dim3(256), 0, st, d_gcnt, d_gstart, G, d_fs, d_fl, d_ps, d_pl, d_ls, d_ll, d_lk, d_sb, d_se);
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+  rc = mp_read_scalars(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t n_small = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL2]), n_large = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL3]);
+  const uint32_t n_kept = n_small + n_large;
+  S.n_groups_small = n_small;
+  S.n_groups_large = n_large;
+  S.n_groups_kept  = n_kept;
+  S.largest_group  = c->h_scalars[MP_SC_LARGEST];
+  if (S.largest_group * static_cast<uint64_t>(k) >= (1ull << 31)) {
+    snprintf(c->err, sizeof(c->err), "a group of %llu anchors: its scores do not fit 31 bits at k = %d", static_cast<kf_ull>(S.largest_group), k);
+    return MSGPU_E_ARG;
+  }
+
+  // ---- rule 5
+  int32_t  *d_f, *d_pred;
+  uint64_t *d_sk[2];
+  uint8_t  *d_used;
+  MpRaw    *d_raw;
+  uint32_t *d_emit, *d_coff;
+  KHIP(c, D.get(&d_f, A));
+  KHIP(c, D.get(&d_pred, A));
+  KHIP(c, D.get(&d_sk[0], A));
+  KHIP(c, D.get(&d_sk[1], A));
+  KHIP(c, D.get(&d_used, A));
+  KHIP(c, D.get(&d_raw, A));
+  KHIP(c, D.get(&d_emit, n_kept + 1ull));
+  KHIP(c, D.get(&d_coff, n_kept + 1ull));
+  KHIP(c, hipMemsetAsync(d_used, 0, A ? A : 1, st));
+  KHIP(c, hipMemsetAsync(d_emit, 0, (n_kept + 1ull) * 4, st));
+  MpChainArgs ca{d_ll, n_large, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[0], k, prm.max_gap, prm.bandwidth};
+  KHIP(c, clock.begin(&S.chain_ms));
+  if (n_large) hipLaunchKernelGGL(k_mp_chain, dim3(mp_grid(n_large, 4)), dim3(256), 0, st, ca);
+  ca.list   = d_ls;
+  ca.n_list = n_small;
+  if (n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(mp_grid(n_small, 16)), dim3(256), 0, st, ca);
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+
+  // ---- rule 6
+  uint32_t C_n = 0;
+  if (n_kept) {
+    size_t need = 0;
+    KHIP(c, rocprim::segmented_radix_sort_keys_desc(nullptr, need, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st));
+    uint8_t *tmp;
+    KHIP(c, D.get(&tmp, need));
+    KHIP(c, clock.begin(&S.backtrack_ms));
+    KHIP(c, rocprim::segmented_radix_sort_keys_desc(tmp, need, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st));
+    hipLaunchKernelGGL(k_mp_walk, dim3(mp_grid(n_kept, 64)), dim3(64), 0, st, d_lk, n_kept, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[1],
+                       d_used, k, prm.min_score, prm.min_count, d_raw, d_emit, mp_slot(c, MP_SC_DROP_SCORE), mp_slot(c, MP_SC_DROP_COUNT),
+                       mp_slot(c, MP_SC_CUT));
+    KHIP(c, hipGetLastError());
+    rc = mp_scan<uint32_t>(c, D, d_emit, d_coff, n_kept + 1ull);
+    if (rc != MSGPU_OK) return rc;
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_coff + n_kept);
+    KHIP(c, clock.end());
+    rc = mp_read_scalars(c);
+    if (rc != MSGPU_OK) return rc;
+    C_n = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]);
+    D.drop(tmp);
+  }
+  S.n_chains               = C_n;
+  S.n_chains_below_score   = c->h_scalars[MP_SC_DROP_SCORE];
+  S.n_chains_below_count   = c->h_scalars[MP_SC_DROP_COUNT];
+  S.n_chains_cut           = c->h_scalars[MP_SC_CUT];
+  msgpu_map_chain *d_chains;
+  MpWhere         *d_where;
+  uint32_t        *d_np, *d_poff;
+  KHIP(c, D.get(&d_chains, C_n));
+  KHIP(c, D.get(&d_where, C_n));
+  KHIP(c, D.get(&d_np, C_n + 1ull));
+  KHIP(c, D.get(&d_poff, C_n + 1ull));
+  KHIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
+  KHIP(c, clock.begin(&S.backtrack_ms));
+  if (C_n)
+    hipLaunchKernelGGL(k_mp_table, dim3(mp_grid(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
+                       Qf.d_len, k, d_chains, d_where, d_np, C_n);
+  KHIP(c, hipGetLastError());
+  KHIP(c, clock.end());
+
+  // ---- rule 7 in exact mode
+  if (exact && C_n) {
+    rc = mp_scan<uint32_t>(c, D, d_np, d_poff, C_n + 1ull);
+    if (rc != MSGPU_OK) return rc;
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_poff + C_n);
+    KHIP(c, hipGetLastError());
+    rc = mp_read_scalars(c);
+    if (rc != MSGPU_OK) return rc;
+    const uint32_t P = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]); // (fewer than the anchors)
+    S.n_pairs        = P;
+    if (P) {
+      // the queries as they are and reverse-complemented, one behind the other
+      const uint64_t          NB = Qf.recs.n_bases;
+      std::vector<msgpu_copy> pieces;
+      try {
+        pieces.reserve(2ull * Qf.recs.n);
+        for (uint32_t i = 0; i < Qf.recs.n; ++i) {
+          const uint64_t o = msgpu_seq_offset(Qf.f, i);
+          const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(Qf.f, i));
+          pieces.push_back(msgpu_copy{o, o, L, 0});
+          pieces.push_back(msgpu_copy{o, NB + o, L, MSGPU_COPY_REVCOMP});
+        }
+      } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+      msgpu_gather_plan *plan = nullptr;
+      rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
+      if (rc != MSGPU_OK) {
+        snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
+        return rc;
+      }
+      struct FreePlan {
+        msgpu_gather_plan *p;
+        ~FreePlan() { msgpu_gather_plan_free(p); }
+      } free_plan{plan};
+      uint8_t          *d_or;
+      msgpu_align_pair *d_pairs;
+      uint32_t         *d_dist, *d_nm;
+      KHIP(c, D.get(&d_or, 2 * NB + 16));
+      KHIP(c, D.get(&d_pairs, P));
+      KHIP(c, D.get(&d_dist, P));
+      KHIP(c, D.get(&d_nm, C_n));
+      KHIP(c, clock.begin(&S.pairs_ms));
+      rc = msgpu_gather_run(c->seq, plan, d_or, 2 * NB + 16, st);
+      if (rc != MSGPU_OK) {
+        snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
+        return rc;
+      }
+      hipLaunchKernelGGL(k_mp_pairs, dim3(mp_grid(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, Tf.d_off, Qf.d_off,
+                         NB, k, d_pairs, P);
+      KHIP(c, hipGetLastError());
+      KHIP(c, clock.end());
+      size_t need = 0;
+      KHIP(c, rocprim::segmented_reduce(nullptr, need, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st));
+      uint8_t *tmp;
+      KHIP(c, D.get(&tmp, need));
+      KHIP(c, clock.begin(&S.distance_ms));
+      launch_edit_distance_pairs(st, Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist);
+      KHIP(c, hipGetLastError());
+      KHIP(c, rocprim::segmented_reduce(tmp, need, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st));
+      hipLaunchKernelGGL(k_mp_capped, dim3(mp_grid(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
+      hipLaunchKernelGGL(k_mp_exact, dim3(mp_grid(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
+      KHIP(c, hipGetLastError());
+      KHIP(c, clock.end());
+      rc = mp_read_scalars(c);
+      if (rc != MSGPU_OK) return rc;
+      S.n_pairs_capped = c->h_scalars[MP_SC_CAPPED];
+    }
+  }
+
+  // ---- the figures come back; the host formats the lines
+  kf_ull hist[32];
+  try {
+    res->chains.resize(C_n);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  KHIP(c, clock.begin(&S.copy_ms));
+  if (C_n) KHIP(c, hipMemcpyAsync(res->chains.data(), d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
+  KHIP(c, hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
+  KHIP(c, clock.end());
+  KHIP(c, hipStreamSynchronize(st));
+  clock.collect();
+  for (int i = 0; i < 32; ++i) S.group_hist[i < 15 ? i : 15] += hist[i];
+  const auto h0 = std::chrono::steady_clock::now();
+  try {
+    unsigned nt = std::thread::hardware_concurrency();
+    nt          = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
+    if (C_n < 4096) nt = 1;
+    std::vector<std::string> part(nt);
+    msgpu::HostPool::get().run(nt, nt, [&](size_t t) {
+      const uint64_t a = static_cast<uint64_t>(C_n) * t / nt, b = static_cast<uint64_t>(C_n) * (t + 1) / nt;
+      part[t].reserve((b - a) * 112);
+      for (uint64_t i = a; i < b; ++i) mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t]);
+    });
+    size_t total = 0;
+    for (const std::string &p : part) total += p.size();
+    res->text.reserve(total);
+    for (const std::string &p : part) res->text += p;
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  S.host_ms   = since(h0);
+  S.bytes_out = res->text.size();
+  S.wall_ms   = since(w0);
+  return MSGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void msgpu_map_default_params(msgpu_map_params *p) {
+  if (!p) return;
+  *p = msgpu_map_params{15, 5, 200, 10000, 2000, 64, 100, 3, 0, 64, 0, 0};
+}
+
+int msgpu_map_create(int device, msgpu_mapctx **out) {
+  if (!out) return MSGPU_E_ARG;
+  *out     = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
+  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
+  auto *c = new (std::nothrow) msgpu_mapctx();
+  if (!c) return MSGPU_E_NOMEM;
+  c->device = device;
+  int rc    = msgpu_seq_create(device, &c->seq);
+  if (rc != MSGPU_OK) {
+    delete c;
+    return rc;
+  }
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&c->d_scalars), SC_COUNT * sizeof(uint64_t)) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void **>(&c->h_scalars), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess) {
+    msgpu_map_destroy(c);
+    return MSGPU_E_HIP;
+  }
+  memset(c->h_scalars, 0, (SC_COUNT + 1) * sizeof(uint64_t));
+  void *dev = nullptr;
+  if (!getenv("MSGPU_SYNC_READBACK") && hipHostGetDevicePointer(&dev, c->h_scalars, 0) == hipSuccess)
+    c->h_scalars_dev = static_cast<uint64_t *>(dev);
+  *out = c;
+  return MSGPU_OK;
+}
+
+void msgpu_map_destroy(msgpu_mapctx *c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  if (c->stream) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamDestroy(c->stream);
+  }
+  if (c->d_scalars) (void)hipFree(c->d_scalars);
+  if (c->h_scalars) (void)hipHostFree(c->h_scalars);
+  msgpu_seq_destroy(c->seq);
+  delete c;
+}
+
+const char *msgpu_map_last_error(const msgpu_mapctx *c) { return c ? c->err : "null context"; }
+
+int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *targets_path, const char *queries_path, uint32_t flags,
+                  uint64_t budget_bytes, msgpu_map_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out      = nullptr;
+  c->err[0] = 0;
+  if (!params || !targets_path || flags) return MSGPU_E_ARG;
+  (void)budget_bytes; // nothing is partitioned: rule 9
+  const msgpu_map_params p = *params;
+  if (p.k < 4 || p.k > 32 || p.w < 1 || p.w > 64 || p.max_occ < 1 || p.max_gap < 0 || p.bandwidth < 0 || p.max_pred != 64 ||
+      p.band < 1 || p.band > 127 || (p.exact != 0 && p.exact != 1) || (p.ava != 0 && p.ava != 1)) {
+    snprintf(c->err, sizeof(c->err), "parameters: k = %d (4..32), w = %d (1..64), max_occ = %u (>= 1), max_gap = %d, bandwidth = %d "
+             "(>= 0), max_pred = %d (64), band = %d (1..127), exact = %d, ava = %d (0 / 1)", p.k, p.w, p.max_occ, p.max_gap, p.bandwidth,
+             p.max_pred, p.band, p.exact, p.ava);
+    return MSGPU_E_ARG;
+  }
+  if (p.ava ? (queries_path && strcmp(queries_path, targets_path) != 0) : !queries_path) {
+    snprintf(c->err, sizeof(c->err), p.ava ? "ava: the query file is the target file" : "no query file");
+    return MSGPU_E_ARG;
+  }
+  KHIP(c, hipSetDevice(c->device));
+  std::unique_ptr<msgpu_map_result> res;
+  try {
+    res.reset(new msgpu_map_result());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  const uint64_t lost0 = c->lost;
+  const int      rc = mp_stage(c, p, targets_path, queries_path, res.get());
+  if (rc != MSGPU_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  res->stats.n_lost_publications = c->lost - lost0;
+  res->stats.params              = p;
+  *out                           = res.release();
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_stats(const msgpu_map_result *r, msgpu_map_stats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->stats;
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_chains(const msgpu_map_result *r, const msgpu_map_chain **chains, uint64_t *n) {
+  if (!r || !chains || !n) return MSGPU_E_ARG;
+  *chains = r->chains.data();
+  *n      = r->chains.size();
+  return MSGPU_OK;
+}
+
+const char *msgpu_map_result_text(const msgpu_map_result *r, uint64_t *len) {
+  if (len) *len = r ? r->text.size() : 0;
+  return r ? r->text.data() : "";
+}
+
+void msgpu_map_result_free(msgpu_map_result *r) {
+  if (r) delete r;
+}
+
+} // extern "C"

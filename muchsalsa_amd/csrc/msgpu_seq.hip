@@ -1412,6 +1412,17 @@ __global__ __launch_bounds__(256) void k_edit_distance(const uint8_t *base_a, co
   if ((threadIdx.x & 63) == 0) out[p] = d;
 }
 
+void launch_edit_distance_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
+                                uint32_t band, uint32_t *d_out) {
+  if (n) hipLaunchKernelGGL(k_edit_distance, dim3((n + 3) / 4), dim3(256), 0, st, d_a, d_b, d_pairs, n, band, d_out);
+}
+
+const uint8_t *seq_store_bases(const msgpu_seqctx *c, int kind, uint64_t *n_bases) {
+  const SeqStore &s = c->st[kind];
+  *n_bases = s.d_buf ? s.n_bases : 0;
+  return s.d_buf ? static_cast<const uint8_t *>(s.d_buf) + SEQ_PAD : nullptr;
+}
+
 } // namespace msgpu
 
 extern "C" {

@@ -348,33 +348,7 @@ namespace {
 
 enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOTAL_C };
 
-// The scalar block as it stands, through the project's read-back protocol (msgpu_device.h, publish_to_host): one wavefront
-// writes it into the mapped mirror and publishes a sequence number, the host polls for it.  A stream that ends without
-// the number arriving is answered by a copy, and counted.
-int ug_read_scalars(msgpu_ugctx *c) {
-  if (c->h_scalars_dev) {
-    const uint64_t seq = ++c->seq;
-    launch_publish_scalars(c->stream, c->d_scalars, HostPublish{c->h_scalars_dev, seq});
-    KHIP(c, hipGetLastError());
-    volatile uint64_t *flag = c->h_scalars + SC_COUNT;
-    for (uint64_t spins = 1;; ++spins) {
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
-      __builtin_ia32_pause();
-      if ((spins & 0xffff) == 0) {
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q == hipSuccess) {
-          if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
-          break;
-        }
-        if (q != hipErrorNotReady) break;
-      }
-    }
-    ++c->lost;
-  }
-  KHIP(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  KHIP(c, hipStreamSynchronize(c->stream));
-  return MSGPU_OK;
-}
+int ug_read_scalars(msgpu_ugctx *c) { return kf_read_scalars(c, c->d_scalars, c->h_scalars, c->h_scalars_dev, c->seq, c->lost); } // (msgpu_kmer_shared.h)
 inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->d_scalars + slot, 0, 8, c->stream); }
 
 template <class K> void ug_split(K key, uint64_t &hi, uint64_t &lo);

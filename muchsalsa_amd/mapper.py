@@ -1,0 +1,186 @@
+"""The pipeline's mapping step on the GPU: what its four ``minimap2 -k15 -w5 -m100 -g10000 -r2000 --max-chain-skip 25`` calls
+write -- a PAF of every record of a query file against every record of a target file, by minimizer seeds and a chaining DP.
+
+    python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--ava]
+            [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N]
+
+prints one JSON line of counts and seconds.  With ``--ava`` the two paths name the same file (the reads against
+themselves: the read-to-read PAF muchsalsa_amd.scrubber takes as its fourth input); ``--exact`` adds the base-level match
+count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call).  minimap2 is not needed, and it is not part of
+the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
+tests' restatement in plain Python (tests/map_oracle.py), not against minimap2.  The rules (include/msgpu.h,
+"unitig-to-read mapping"); parameters k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth
+(2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1):
+
+ 1. windows: the alphabet, case folding, 2-bit code, canonical key (min(fw, rc) as 2k-bit numbers) and the break at any
+    other byte are those of the k-mer filter's rolling window (KfRoll).  A stretch is a maximal run of k-mer start
+    positions without a break.  The strand bit of a position is 1 iff rc < fw.
+ 2. minimizers: h(i) = kf_hash(key(i)).  A window is w consecutive k-mer start positions inside one stretch; a stretch with
+    fewer than w positions has none.  A window's minimizer is its position with the smallest (h, position).  A sequence's
+    minimizers are the union over its windows, each position once.
+ 3. index: every target minimizer as (key, target record, position, strand).  A key with more than max_occ entries is left
+    out whole; the number of keys and entries left out is reported.
+ 4. anchors: every query minimizer meets every index entry of its key.  Relative strand s = query strand ^ target strand,
+    x = the target position, y = the query position if s = 0, else qlen - k - position (the position in the
+    reverse-complemented query, so a collinear chain rises in both coordinates on both strands).  With ava the query file
+    is the target file, and an anchor is kept only if the query record index is smaller than the target record index.  A
+    group is (query record, target record, s); its anchors are ordered by (x, y); equal (x, y) cannot occur.
+ 5. chaining, per group over the anchors 0..n-1 in that order: f(i) = max(k, max over j in [max(0, i - 64), i) of
+    f(j) + gain - pen), taken over the j with dx = x_i - x_j > 0, dy = y_i - y_j > 0, dx <= max_gap, dy <= max_gap and
+    dd = |dx - dy| <= bandwidth; gain = min(dx, dy, k); pen = 0 if dd = 0, else (dd * k) / 100 + (floor(log2(dd)) >> 1)
+    with integer division.  pred(i) is the j that gives the maximum, the largest such j on a tie; it is "none" when k
+    alone is at least as good.
+ 6. chains: the anchors of a group are visited by (f descending, index ascending).  An unused anchor starts a chain; the
+    chain follows pred over unused anchors and ends before the first used anchor u or at "none";
+    score = f(start) - (f(u) if it ended at a used anchor, else 0); all its anchors become used.  The chain is emitted iff
+    score >= min_score and it has at least min_count anchors.  A group with fewer than min_count anchors, or with
+    n * k < min_score, can emit nothing and is dropped before the DP.
+ 7. figures of a chain with anchors a_0 < ... < a_{m-1} (rising x).  For each link i >= 1: c_i = min(dx, dy, k),
+    lt_i = dx - c_i, lq_i = dy - c_i; the link's segment is target [x_i + k - c_i - lt_i, x_i + k - c_i) against the
+    oriented query [y_i + k - c_i - lq_i, y_i + k - c_i); d_i = that pair's Levenshtein distance inside band with
+    msgpu_edit_distance's semantics, min(distance, band + 1), over the bytes as the stores hold them (the oriented query
+    of s = 1 is MSGPU_COPY_REVCOMP's: reversed, A <-> T and C <-> G in upper case, every other byte as it is); if
+    lt_i = lq_i = 0 then d_i = 0; d_i is computed only in exact mode.  block = k + sum (c_i + max(lt_i, lq_i)).  Seed
+    mode: matches = k + sum c_i.  Exact mode: matches = k + sum (c_i + max(lt_i, lq_i) - d_i), never negative because
+    d_i <= max(lt_i, lq_i).  Target range [x_0, x_{m-1} + k).  Query range in forward coordinates: [y_0, y_{m-1} + k) for
+    s = 0, [qlen - y_{m-1} - k, qlen - y_0) for s = 1.
+ 8. output: one line per chain: the twelve PAF columns ('+' / '-' in column 5, mapping quality 255), then cm:i:<anchors>,
+    s1:i:<score> and, in exact mode, NM:i:<sum d_i>.  Lines are ordered by (query record, target record, strand, order of
+    emission in the group).  On any error nothing is written.
+ 9. limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs, at most 2^30
+    distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k below 2^31; everything resident together, otherwise MSGPU_E_NOMEM
+    naming the sizes.  Larger inputs are out of scope (no target batching).
+
+Known differences from minimap2, none of which could be checked against the program (it is not installed where this project
+is built):
+
+* the hash is the project's (kf_hash), not minimap2's;
+* leftmost-minimum windows;
+* an absolute occurrence cap (max_occ) instead of a fraction of the distinct minimizers;
+* a fixed window of 64 predecessors instead of the skip heuristic of ``--max-chain-skip``;
+* an integer gap cost;
+* no ``--dual`` / ``-D`` diagonal filtering beyond the ava rule;
+* no primary / secondary marking, as with ``-P``: all chains are kept;
+* no mapping quality (column 12 is 255);
+* no CIGAR: exact mode gives a match count that is a lower bound from unit-cost distances per link, not minimap2's count
+  of ``=`` columns;
+* no end extension beyond the outermost seeds.
+"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+from . import _lib
+
+__all__ = ["MapError", "run", "main", "DEFAULTS"]
+
+DEFAULTS = dict(k=15, w=5, max_occ=200, max_gap=10000, bandwidth=2000, min_score=100, min_count=3, exact=0, band=64, ava=0)
+
+
+class MapError(RuntimeError):
+    """A rejected input or parameter, or a device failure."""
+
+    def __init__(self, code, detail=""):
+        msg = _lib.lib().msgpu_strerror(code).decode()
+        super().__init__("%s (%d)%s" % (msg, code, (": " + detail) if detail else ""))
+        self.code = code
+
+
+def run(targets, queries, out, device=0, tables=None, timings=None, **params):
+    """The whole stage: writes ``out`` (nothing on an error); returns the counts.  ``params``: the names of DEFAULTS.  With
+    ava = 1, ``queries`` is None or ``targets``.  ``tables`` (a dict) receives ``chains``: per line of the PAF the tuple
+    (query, target, strand, anchors, score, nm, q_start, q_end, t_start, t_end, matches, block) and ``text`` (bytes);
+    ``timings`` (a dict) seconds per step."""
+    unknown = set(params) - set(DEFAULTS)
+    if unknown:
+        raise TypeError("unknown parameters: %s" % ", ".join(sorted(unknown)))
+    p = dict(DEFAULTS, **params)
+    L = _lib.lib()
+    t0 = time.perf_counter()
+    for name, v in p.items():
+        if not -(1 << 31) <= int(v) < (1 << 31) or (name == "max_occ" and int(v) < 0):
+            raise MapError(_lib.E_ARG, "%s = %d" % (name, int(v)))
+    ctx = C.c_void_p()
+    rc = L.msgpu_map_create(device, C.byref(ctx))
+    if rc != _lib.OK:
+        raise MapError(rc, "device %d" % device)
+    try:
+        res = C.c_void_p()
+        prm = _lib.MapParams(int(p["k"]), int(p["w"]), int(p["max_occ"]), int(p["max_gap"]), int(p["bandwidth"]), 64,
+                             int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]), 0)
+        rc = L.msgpu_map_run(ctx, C.byref(prm), os.fsencode(targets), None if queries is None else os.fsencode(queries), 0, 0,
+                             C.byref(res))
+        if rc != _lib.OK:
+            raise MapError(rc, L.msgpu_map_last_error(ctx).decode(errors="replace"))
+        try:
+            st = _lib.MapStats()
+            L.msgpu_map_result_stats(res, C.byref(st))
+            n = C.c_uint64()
+            ptr = L.msgpu_map_result_text(res, C.byref(n))
+            text = memoryview((C.c_char * n.value).from_address(ptr)) if n.value else b""
+            if tables is not None:
+                cp = C.POINTER(_lib.MapChain)()
+                m = C.c_uint64()
+                L.msgpu_map_result_chains(res, C.byref(cp), C.byref(m))
+                names = [f for f, _ in _lib.MapChain._fields_]
+                tables["chains"] = [tuple(int(getattr(cp[i], f)) for f in names) for i in range(m.value)]
+                tables["text"] = bytes(text)
+            t1 = time.perf_counter()
+            with open(out, "wb") as h:
+                h.write(text)
+            t_write = time.perf_counter() - t1
+        finally:
+            L.msgpu_map_result_free(res)
+    finally:
+        L.msgpu_map_destroy(ctx)
+    if timings is not None:
+        timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.MapStats._fields_ if name.endswith("_ms")})
+        timings["stage_wall"] = timings.pop("wall")
+        timings.update({"file": t_write, "total": time.perf_counter() - t0})
+    return {"params": {name: int(getattr(st.params, name)) for name in DEFAULTS}, "records": [int(x) for x in st.n_records],
+            "bases": [int(x) for x in st.n_bases], "minimizers": [int(x) for x in st.n_minimizers], "keys": int(st.n_keys),
+            "keys_dropped": int(st.n_keys_dropped), "entries_dropped": int(st.n_entries_dropped), "anchors": int(st.n_anchors),
+            "n_groups": int(st.n_groups), "groups_kept": int(st.n_groups_kept), "groups_small": int(st.n_groups_small),
+            "groups_large": int(st.n_groups_large), "largest_group": int(st.largest_group),
+            "group_hist": [int(x) for x in st.group_hist], "chains": int(st.n_chains), "below_score": int(st.n_chains_below_score),
+            "below_count": int(st.n_chains_below_count), "chains_cut": int(st.n_chains_cut), "pairs": int(st.n_pairs),
+            "capped": int(st.n_pairs_capped), "lost_publications": int(st.n_lost_publications), "bytes_out": int(st.bytes_out)}
+
+
+_OPTS = {"-k": "k", "-w": "w", "--max-occ": "max_occ", "--min-score": "min_score", "--min-count": "min_count",
+         "--max-gap": "max_gap", "--bandwidth": "bandwidth", "--band": "band"}
+
+
+def main(argv):
+    args, p, ok = list(argv), {}, True
+    for flag in ("--exact", "--ava"):
+        if flag in args:
+            args.remove(flag)
+            p[flag[2:]] = 1
+    for name, key in _OPTS.items():
+        if name in args:
+            i = args.index(name)
+            try:
+                p[key] = int(args[i + 1])
+            except (IndexError, ValueError):
+                ok = False
+            del args[i:i + 2]
+    q = dict(DEFAULTS, **p)
+    ok = ok and 4 <= q["k"] <= 32 and 1 <= q["w"] <= 64 and q["max_occ"] >= 1 and 1 <= q["band"] <= 127
+    ok = ok and q["max_gap"] >= 0 and q["bandwidth"] >= 0 and not any(a.startswith("-") for a in args)
+    ok = ok and len(args) == 3 and (not q["ava"] or args[0] == args[1])
+    if not ok:
+        sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
+        return 2
+    timings = {}
+    out = run(args[0], args[1], args[2], timings=timings, **p)
+    out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    _lib.PRELOAD_TORCH = False  # this process never imports torch
+    sys.exit(main(sys.argv[1:]))

@@ -5,7 +5,9 @@ long reads, ``02_<reads>.scrubbed.fa``), from the anchor PAF, the reads and a re
 
 prints one JSON line of counts and seconds.  The script maps every batch of reads against itself with ``minimap2 -x
 ava-ont``; this stage maps nothing: ``ava.paf`` is all reads against all reads, mapped once, and a batch uses its lines
-whose two reads are both in the batch, in file order.  The rules (include/msgpu.h, "read scrubber"):
+whose two reads are both in the batch, in file order.  ``python -m muchsalsa_amd.mapper <reads> <reads> <ava.paf> --ava``
+writes such a file (and, without ``--ava``, the anchor PAF from the unitigs and the reads).  The rules (include/msgpu.h,
+"read scrubber"):
 
 * anchor PAF in line order: a line of one token is skipped, so is one with col3 - col2 < 500; a read (column 5) is a node
   from its first surviving line on, its length column 6 of that line; the first surviving line of a (read, anchor) counts

@@ -553,3 +553,81 @@ def unitig_cases():
     return {"rings": (fq(b"a", ring_reads[0]), fq(b"b", ring_reads[1]), {"rings": rings}),
             "selfcomp": (fq(b"s", [selfcomp, selfcomp]), None, {"sequence": selfcomp, "self_complementary": x + _revcomp(x)}),
             "hairpin": (fq(b"h", [hairpin, hairpin]), None, {"sequence": hairpin})}
+
+
+def mapper_workload(n_reads, read_len, n_unitigs, seed, coverage=10, error=0.06, families=2, copies=6, repeat_len=600,
+                    n_frac=0.0005, lower_frac=0.001, tiled=False, unitig_len=(500, 3000), fastq=True):
+    """Input of the mapper (muchsalsa_amd.mapper): a dict with ``reads`` (FASTQ bytes, or FASTA with fastq=False),
+    ``unitigs`` (FASTA bytes), ``genome`` (bytes) and the layout (``read_start``, ``read_fwd``, ``unitig_start``,
+    ``unitig_fwd``, ``unitig_len``).
+
+    A uniform genome of n_reads * read_len / coverage bases (at least read_len + 3500) in which ``families`` repeat units of
+    ``repeat_len`` bases are each written ``copies`` times, as kmer_filter_workload does it.  Read r<i> is read_len genome
+    bases from a uniform start, every other one (a drawn bit) reverse-complemented, then edited: a fraction ``error`` of its
+    bases, split evenly, is replaced by another base, followed by an inserted drawn base, or deleted; after that ``n_frac``
+    of the bases become 'N' and ``lower_frac`` lower case.  Unitig u<i> is an error-free stretch of
+    U{unitig_len[0]..unitig_len[1]} bases at a uniform start, or with ``tiled`` the consecutive stretches that cover the
+    genome end to end (n_unitigs is ignored); every other one (a drawn bit) is written reverse-complemented.
+    Deterministic in (seed, shape)."""
+    L = int(read_len)
+    G = max(int(n_reads) * L // int(coverage), L + unitig_len[1] + 500)
+    g = genome_bases(G, seed).copy()
+    slots = int(families) * int(copies)
+    if slots:
+        slot = G // slots
+        if slot < repeat_len:
+            raise ValueError("genome too short for the repeats")
+        units = genome_bases(int(families) * int(repeat_len), seed + 1).reshape(int(families), int(repeat_len))
+        where = np.argsort(splitmix64(seed, 80, slots), kind="stable")
+        jitter = _randint(seed, 81, slots, 0, slot - int(repeat_len))
+        for i in range(slots):
+            at = int(where[i]) * slot + int(jitter[i])
+            g[at:at + int(repeat_len)] = units[i // int(copies)]
+    comp = np.arange(256, dtype=np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    sub = np.zeros((256, 3), np.uint8)
+    for b, t in {65: b"CGT", 67: b"GTA", 71: b"TAC", 84: b"ACG"}.items():
+        sub[b] = list(t)
+    r_start = _randint(seed, 82, n_reads, 0, G - L)
+    r_fwd = (splitmix64(seed, 83, n_reads) & np.uint64(1)).astype(bool)
+    recs = []
+    col = np.arange(L, dtype=np.int64)[None, :]
+    step = max(1, (1 << 22) // L)
+    for lo in range(0, int(n_reads), step):
+        hi = min(lo + step, int(n_reads))
+        n = hi - lo
+        fw = g[r_start[lo:hi, None] + col]
+        rv = comp[g[(r_start[lo:hi] + L - 1)[:, None] - col]]
+        flat = np.ascontiguousarray(np.where(r_fwd[lo:hi, None], fw, rv)).reshape(-1)
+        u = _uniform(seed, 1000 + 4 * (lo // step), n * L, 0.0, 1.0)
+        draw = (splitmix64(seed, 1001 + 4 * (lo // step), n * L) % np.uint64(12)).astype(np.int64)
+        is_sub, is_ins, is_del = u < error / 3, (u >= error / 3) & (u < 2 * error / 3), (u >= 2 * error / 3) & (u < error)
+        flat = np.where(is_sub, sub[flat, draw % 3], flat)
+        count = 1 + is_ins.astype(np.int64) - is_del.astype(np.int64)
+        out = np.repeat(flat, count)
+        first = np.cumsum(count) - count
+        out[first[is_ins] + 1] = np.frombuffer(b"ACGT", np.uint8)[draw[is_ins] // 3]
+        lens = count.reshape(n, L).sum(axis=1)
+        nb = len(out)
+        out[_randint(seed, 1002 + 4 * (lo // step), int(nb * n_frac), 0, nb - 1)] = ord("N")
+        out[_randint(seed, 1003 + 4 * (lo // step), int(nb * lower_frac), 0, nb - 1)] |= 0x20
+        ends = np.cumsum(lens)
+        for i in range(n):
+            seq = out[ends[i] - lens[i]:ends[i]].tobytes()
+            recs.append(b"@r%d\n%s\n+\n%s\n" % (lo + i, seq, b"I" * len(seq)) if fastq else b">r%d\n%s\n" % (lo + i, seq))
+    if tiled:
+        n_max = G // unitig_len[0] + 2
+        u_len = _randint(seed, 84, n_max, unitig_len[0], unitig_len[1])
+        u_start = np.cumsum(u_len) - u_len
+        keep = u_start < G
+        u_start, u_len = u_start[keep], np.minimum(u_len[keep], G - u_start[keep])
+    else:
+        u_len = _randint(seed, 84, n_unitigs, unitig_len[0], unitig_len[1])
+        u_start = _randint(seed, 85, n_unitigs, 0, G - u_len)
+    u_fwd = (splitmix64(seed, 86, len(u_len)) & np.uint64(1)).astype(bool)
+    unitigs = []
+    for i in range(len(u_len)):
+        seq = g[u_start[i]:u_start[i] + u_len[i]]
+        unitigs.append(b">u%d\n%s\n" % (i, (seq if u_fwd[i] else comp[seq[::-1]]).tobytes()))
+    return {"reads": b"".join(recs), "unitigs": b"".join(unitigs), "genome": g.tobytes(), "read_start": r_start, "read_fwd": r_fwd,
+            "unitig_start": u_start, "unitig_fwd": u_fwd, "unitig_len": u_len}
