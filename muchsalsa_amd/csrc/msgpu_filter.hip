@@ -23,7 +23,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -34,6 +33,7 @@
 #include <vector>
 
 #include "msgpu.h"
+#include "msgpu_stage.h"
 
 namespace msgpu {
 
@@ -232,12 +232,9 @@ using namespace msgpu;
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-struct msgpu_ufctx {
-  int           device = 0;
-  hipStream_t   stream = nullptr;
-  msgpu_seqctx *seq    = nullptr;
-  char          err[256] = {0};
-  uint64_t      err_line = 0;
+struct msgpu_ufctx : msgpu::StageCtx {
+  SeqCtxHold seq;
+  int        open() { return msgpu_seq_create(device, &seq.p); }
 };
 
 struct msgpu_uf_result {
@@ -246,30 +243,6 @@ struct msgpu_uf_result {
 };
 
 namespace {
-
-int ufail(msgpu_ufctx *c, int code, const char *what, hipError_t e) {
-  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-  return code;
-}
-#define UHIP(c, expr)                                                                                                  \
-  do {                                                                                                                 \
-    hipError_t _e = (expr);                                                                                            \
-    if (_e != hipSuccess) return ufail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
-  } while (0)
-
-struct DevBuf { // device memory freed on every way out of msgpu_uf_run
-  std::vector<void *> p;
-  ~DevBuf() {
-    for (void *x : p) (void)hipFree(x);
-  }
-  template <class T> hipError_t get(T **out, size_t count) {
-    void      *m = nullptr;
-    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(m);
-    *out = static_cast<T *>(m);
-    return e;
-  }
-};
 
 inline bool uf_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
 
@@ -318,12 +291,6 @@ int uf_descriptions(const char *path, const msgpu_uf *u, uint32_t n_ids, std::ve
   return MSGPU_OK;
 }
 
-float ms_between(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  return ms;
-}
-
 } // namespace
 
 extern "C" {
@@ -355,37 +322,8 @@ int msgpu_uf_quartiles(const uint32_t *values, size_t n, double *q1, double *q3,
   return MSGPU_OK;
 }
 
-int msgpu_uf_create(int device, msgpu_ufctx **out) {
-  if (!out) return MSGPU_E_ARG;
-  *out    = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
-  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
-  auto *c = new (std::nothrow) msgpu_ufctx();
-  if (!c) return MSGPU_E_NOMEM;
-  c->device = device;
-  int rc    = msgpu_seq_create(device, &c->seq);
-  if (rc == MSGPU_OK && (hipSetDevice(device) != hipSuccess ||
-                         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess))
-    rc = MSGPU_E_HIP;
-  if (rc != MSGPU_OK) {
-    msgpu_uf_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return MSGPU_OK;
-}
-
-void msgpu_uf_destroy(msgpu_ufctx *c) {
-  if (!c) return;
-  if (c->stream) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamDestroy(c->stream);
-  }
-  msgpu_seq_destroy(c->seq);
-  delete c;
-}
+int  msgpu_uf_create(int device, msgpu_ufctx **out) { return stage_create(device, out); }
+void msgpu_uf_destroy(msgpu_ufctx *c) { stage_destroy(c); }
 
 const char *msgpu_uf_last_error(const msgpu_ufctx *c) { return c ? c->err : "null context"; }
 uint64_t    msgpu_uf_error_line(const msgpu_ufctx *c) { return c ? c->err_line : 0; }
@@ -397,11 +335,8 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   c->err_line = 0;
   msgpu_uf_tables tb;
   if (msgpu_uf_get_tables(u, &tb) != MSGPU_OK || !tb.n_lines) return MSGPU_E_ARG;
-  const auto w0 = std::chrono::steady_clock::now();
-  auto       since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
-  UHIP(c, hipSetDevice(c->device));
+  const StageTimer wall;
+  STAGE_HIP(c, hipSetDevice(c->device));
   const uint32_t NB = tb.n_blocks, NI = tb.n_unitigs;
   std::unique_ptr<msgpu_uf_result> res;
   try {
@@ -413,32 +348,23 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   S.n_ids           = NI;
 
   // ---- the unitigs: bases to the store, ids, descriptions
-  msgpu_seqfile *f = nullptr;
-  int            rc = msgpu_seq_parse_upload(c->seq, 1, unitigs_path, 0, &f);
+  SeqFileHold f;
+  int         rc = msgpu_seq_parse_upload(c->seq, 1, unitigs_path, 0, &f.f);
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "unitigs %s: %s", unitigs_path, msgpu_seq_last_error(c->seq));
     return rc;
   }
-  struct FreeSeq {
-    msgpu_seqfile *f;
-    ~FreeSeq() { msgpu_seq_free(f); }
-  } free_seq{f};
-  std::vector<uint32_t>    rec_ids, rec_of(NI, 0xffffffffu);
+  std::vector<uint32_t>    rec_ids, rec_of;
   std::vector<std::string> desc;
   try {
-    const uint32_t nr = msgpu_seq_count(f);
-    rec_ids.resize(nr);
-    for (uint32_t i = 0; i < nr; ++i) {
-      rec_ids[i] = msgpu_uf_unitig_id(u, msgpu_seq_name(f, i));
-      if (rec_ids[i] != 0xffffffffu && rec_of[rec_ids[i]] == 0xffffffffu) rec_of[rec_ids[i]] = i;
+    const uint32_t b = stage_first_records(f, [&](const char *name) { return msgpu_uf_unitig_id(u, name); }, NI, tb.block_unitig, NB,
+                                           rec_ids, rec_of);
+    if (b != STAGE_NONE) { // a unitig the FASTA lacks: the first block naming it
+      c->err_line = static_cast<uint64_t>(tb.block_first[b]) + 1;
+      snprintf(c->err, sizeof(c->err), "unitig %s (PAF line %llu) is not in %s", msgpu_uf_unitig_name(u, tb.block_unitig[b]),
+               static_cast<unsigned long long>(c->err_line), unitigs_path);
+      return MSGPU_E_IDS;
     }
-    for (uint32_t b = 0; b < NB; ++b)
-      if (rec_of[tb.block_unitig[b]] == 0xffffffffu) { // a unitig the FASTA lacks: the first block naming it
-        c->err_line = static_cast<uint64_t>(tb.block_first[b]) + 1;
-        snprintf(c->err, sizeof(c->err), "unitig %s (PAF line %llu) is not in %s", msgpu_uf_unitig_name(u, tb.block_unitig[b]),
-                 static_cast<unsigned long long>(c->err_line), unitigs_path);
-        return MSGPU_E_IDS;
-      }
     rc = uf_descriptions(unitigs_path, u, NI, desc);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   if (rc != MSGPU_OK) return rc;
@@ -448,7 +374,7 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
     snprintf(c->err, sizeof(c->err), "sequence store: %s", msgpu_seq_last_error(c->seq));
     return rc;
   }
-  S.load_ms = since(w0);
+  S.load_ms = wall.ms();
 
   // ---- width classes
   std::vector<uint32_t> wave, group, giant;
@@ -467,54 +393,45 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   S.n_giant = static_cast<uint32_t>(giant.size());
 
   hipStream_t st = c->stream;
-  hipEvent_t  ev[10] = {};
-  struct FreeEv {
-    hipEvent_t *e;
-    ~FreeEv() {
-      for (int i = 0; i < 10; ++i)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  } free_ev{ev};
-  for (auto &e : ev) UHIP(c, hipEventCreate(&e));
-  DevBuf    D;
+  StageClock  clock(st);
+  DevArena    D;
   uint32_t *d_qs, *d_qe, *d_rd, *d_bfirst, *d_bn, *d_bqlen, *d_last, *d_val, *d_idval, *d_cls;
   const size_t NL = tb.n_lines;
-  UHIP(c, D.get(&d_qs, NL));
-  UHIP(c, D.get(&d_qe, NL));
-  UHIP(c, D.get(&d_rd, NL));
-  UHIP(c, D.get(&d_bfirst, NB));
-  UHIP(c, D.get(&d_bn, NB));
-  UHIP(c, D.get(&d_bqlen, NB));
-  UHIP(c, D.get(&d_last, NI));
-  UHIP(c, D.get(&d_val, NB));
-  UHIP(c, D.get(&d_idval, NI));
-  UHIP(c, D.get(&d_cls, NB)); // the block lists of the classes, back to back: wave, group, giant
+  STAGE_HIP(c, D.get(&d_qs, NL));
+  STAGE_HIP(c, D.get(&d_qe, NL));
+  STAGE_HIP(c, D.get(&d_rd, NL));
+  STAGE_HIP(c, D.get(&d_bfirst, NB));
+  STAGE_HIP(c, D.get(&d_bn, NB));
+  STAGE_HIP(c, D.get(&d_bqlen, NB));
+  STAGE_HIP(c, D.get(&d_last, NI));
+  STAGE_HIP(c, D.get(&d_val, NB));
+  STAGE_HIP(c, D.get(&d_idval, NI));
+  STAGE_HIP(c, D.get(&d_cls, NB)); // the block lists of the classes, back to back: wave, group, giant
   uint64_t *d_goff;
-  UHIP(c, D.get(&d_goff, giant_off.size()));
+  STAGE_HIP(c, D.get(&d_goff, giant_off.size()));
   std::vector<uint32_t> cls;
   cls.reserve(NB);
   cls.insert(cls.end(), wave.begin(), wave.end());
   cls.insert(cls.end(), group.begin(), group.end());
   cls.insert(cls.end(), giant.begin(), giant.end());
-  UHIP(c, hipEventRecord(ev[0], st));
-  UHIP(c, hipMemcpyAsync(d_qs, tb.line_qs, NL * 4, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_qe, tb.line_qe, NL * 4, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_rd, tb.line_read, NL * 4, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_bfirst, tb.block_first, NB * 4ull, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_bn, tb.block_n, NB * 4ull, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_bqlen, tb.block_qlen, NB * 4ull, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_last, tb.unitig_last_block, NI * 4ull, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_cls, cls.data(), NB * 4ull, hipMemcpyHostToDevice, st));
-  UHIP(c, hipMemcpyAsync(d_goff, giant_off.data(), giant_off.size() * 8, hipMemcpyHostToDevice, st));
-  UHIP(c, hipEventRecord(ev[1], st));
+  STAGE_HIP(c, clock.begin(&S.upload_ms));
+  STAGE_HIP(c, hipMemcpyAsync(d_qs, tb.line_qs, NL * 4, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_qe, tb.line_qe, NL * 4, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_rd, tb.line_read, NL * 4, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_bfirst, tb.block_first, NB * 4ull, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_bn, tb.block_n, NB * 4ull, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_bqlen, tb.block_qlen, NB * 4ull, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_last, tb.unitig_last_block, NI * 4ull, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_cls, cls.data(), NB * 4ull, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_goff, giant_off.data(), giant_off.size() * 8, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, clock.begin(&S.pass1_ms)); // (from the same point of the stream)
 
-  // rocprim's segmented radix sort: one temporary buffer for every sort of the run (sized by the largest)
-  void  *d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  auto   sort = [&](const uint64_t *in, uint64_t *outk, size_t n, uint32_t nseg, const uint64_t *off, int end_bit,
-                  size_t *need) -> hipError_t {
-    return rocprim::segmented_radix_sort_keys(need ? nullptr : d_tmp, need ? *need : tmp_bytes, in, outk,
-                                              static_cast<unsigned int>(n), nseg, off, off + 1, 0, end_bit, st);
+  // rocprim's segmented radix sort, on the arena's temporary buffer
+  auto sort = [&](const uint64_t *in, uint64_t *outk, size_t n, uint32_t nseg, const uint64_t *off, int end_bit) -> hipError_t {
+    return stage_rocprim(D, [&](void *tmp, size_t &bytes) {
+      return rocprim::segmented_radix_sort_keys(tmp, bytes, in, outk, static_cast<unsigned int>(n), nseg, off, off + 1, 0, end_bit, st);
+    });
   };
 
   // ---- pass 1
@@ -524,7 +441,7 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   if (!group.empty())
     hipLaunchKernelGGL(k_uf_group, dim3(S.n_group), dim3(256), 0, st, d_cls + S.n_wave, d_bfirst, d_bn, d_qs, d_qe, d_rd,
                        d_val);
-  UHIP(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   const uint64_t GL = giant_off.back();
   if (GL) {
     if (GL >= 0x7fffffffull) {
@@ -533,39 +450,32 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
     }
     const uint32_t *d_gb = d_cls + S.n_wave + S.n_group;
     uint64_t *d_k0, *d_k1, *d_e0, *d_e1;
-    UHIP(c, D.get(&d_k0, GL));
-    UHIP(c, D.get(&d_k1, GL));
-    UHIP(c, D.get(&d_e0, 2 * GL));
-    UHIP(c, D.get(&d_e1, 2 * GL));
+    STAGE_HIP(c, D.get(&d_k0, GL));
+    STAGE_HIP(c, D.get(&d_k1, GL));
+    STAGE_HIP(c, D.get(&d_e0, 2 * GL));
+    STAGE_HIP(c, D.get(&d_e1, 2 * GL));
     uint64_t *d_eoff; // the endpoint segments: twice the line segments
     std::vector<uint64_t> eoff(giant_off.size());
     for (size_t i = 0; i < eoff.size(); ++i) eoff[i] = 2 * giant_off[i];
-    UHIP(c, D.get(&d_eoff, eoff.size()));
-    UHIP(c, hipMemcpyAsync(d_eoff, eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice, st));
-    size_t need1 = 0, need2 = 0;
-    UHIP(c, sort(d_k0, d_k1, GL, S.n_giant, d_goff, 64, &need1));
-    UHIP(c, sort(d_e0, d_e1, 2 * GL, S.n_giant, d_eoff, 33, &need2));
-    tmp_bytes = std::max(need1, need2);
-    uint8_t *tmp;
-    UHIP(c, D.get(&tmp, tmp_bytes));
-    d_tmp = tmp;
-    const uint32_t grid = static_cast<uint32_t>((GL + 255) / 256);
+    STAGE_HIP(c, D.get(&d_eoff, eoff.size()));
+    STAGE_HIP(c, hipMemcpyAsync(d_eoff, eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice, st));
+    const uint32_t grid = grid256(GL);
     hipLaunchKernelGGL(k_uf_read_keys, dim3(grid), dim3(256), 0, st, d_gb, d_goff, S.n_giant, d_bfirst, d_rd, d_k0);
-    UHIP(c, hipGetLastError());
-    UHIP(c, sort(d_k0, d_k1, GL, S.n_giant, d_goff, 64, nullptr));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, sort(d_k0, d_k1, GL, S.n_giant, d_goff, 64));
     hipLaunchKernelGGL(k_uf_dedup_events, dim3(grid), dim3(256), 0, st, d_gb, d_goff, S.n_giant, d_bfirst, d_qs, d_qe, d_k1,
                        d_e0);
-    UHIP(c, hipGetLastError());
-    UHIP(c, sort(d_e0, d_e1, 2 * GL, S.n_giant, d_eoff, 33, nullptr));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, sort(d_e0, d_e1, 2 * GL, S.n_giant, d_eoff, 33));
     hipLaunchKernelGGL(k_uf_sweep_max, dim3((S.n_giant + 3) / 4), dim3(256), 0, st, d_gb, d_goff, S.n_giant, d_e1, d_val);
-    UHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
   }
-  hipLaunchKernelGGL(k_uf_id_values, dim3((NI + 255) / 256), dim3(256), 0, st, d_last, NI, d_val, d_idval);
-  UHIP(c, hipGetLastError());
-  UHIP(c, hipEventRecord(ev[2], st));
+  hipLaunchKernelGGL(k_uf_id_values, dim3(grid256(NI)), dim3(256), 0, st, d_last, NI, d_val, d_idval);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
   std::vector<uint32_t> idval(NI);
-  UHIP(c, hipMemcpyAsync(idval.data(), d_idval, NI * 4ull, hipMemcpyDeviceToHost, st));
-  UHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipMemcpyAsync(idval.data(), d_idval, NI * 4ull, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- quartiles, outliers (host: one value per id)
   rc = msgpu_uf_quartiles(idval.data(), NI, &S.q1, &S.q3, &S.upper);
@@ -583,7 +493,7 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   // ---- pass 2: count, scan, emit
   std::vector<uint32_t> fcount(NO), foff(NO + 1, 0);
   std::vector<uint2>    frags;
-  UHIP(c, hipEventRecord(ev[3], st));
+  STAGE_HIP(c, clock.begin(&S.pass2_ms));
   if (NO) {
     const uint64_t OL = ooff.back();
     if (OL >= 0x3fffffffull) {
@@ -592,55 +502,47 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
     }
     uint32_t *d_ob, *d_cnt, *d_foff;
     uint64_t *d_ooff, *d_e0, *d_e1, *d_eoff;
-    UHIP(c, D.get(&d_ob, NO));
-    UHIP(c, D.get(&d_cnt, NO));
-    UHIP(c, D.get(&d_foff, NO));
-    UHIP(c, D.get(&d_ooff, NO + 1));
-    UHIP(c, D.get(&d_eoff, NO + 1));
-    UHIP(c, D.get(&d_e0, 2 * OL));
-    UHIP(c, D.get(&d_e1, 2 * OL));
+    STAGE_HIP(c, D.get(&d_ob, NO));
+    STAGE_HIP(c, D.get(&d_cnt, NO));
+    STAGE_HIP(c, D.get(&d_foff, NO));
+    STAGE_HIP(c, D.get(&d_ooff, NO + 1));
+    STAGE_HIP(c, D.get(&d_eoff, NO + 1));
+    STAGE_HIP(c, D.get(&d_e0, 2 * OL));
+    STAGE_HIP(c, D.get(&d_e1, 2 * OL));
     std::vector<uint64_t> eoff(NO + 1);
     for (uint32_t i = 0; i <= NO; ++i) eoff[i] = 2 * ooff[i];
-    UHIP(c, hipMemcpyAsync(d_ob, outl.data(), NO * 4ull, hipMemcpyHostToDevice, st));
-    UHIP(c, hipMemcpyAsync(d_ooff, ooff.data(), (NO + 1) * 8ull, hipMemcpyHostToDevice, st));
-    UHIP(c, hipMemcpyAsync(d_eoff, eoff.data(), (NO + 1) * 8ull, hipMemcpyHostToDevice, st));
-    size_t need = 0;
-    UHIP(c, sort(d_e0, d_e1, 2 * OL, NO, d_eoff, 33, &need));
-    if (need > tmp_bytes) {
-      uint8_t *tmp;
-      UHIP(c, D.get(&tmp, need));
-      d_tmp     = tmp;
-      tmp_bytes = need;
-    }
-    hipLaunchKernelGGL(k_uf_all_events, dim3(static_cast<uint32_t>((OL + 255) / 256)), dim3(256), 0, st, d_ob, d_ooff, NO,
+    STAGE_HIP(c, hipMemcpyAsync(d_ob, outl.data(), NO * 4ull, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_ooff, ooff.data(), (NO + 1) * 8ull, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_eoff, eoff.data(), (NO + 1) * 8ull, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_uf_all_events, dim3(grid256(OL)), dim3(256), 0, st, d_ob, d_ooff, NO,
                        d_bfirst, d_qs, d_qe, d_e0);
-    UHIP(c, hipGetLastError());
-    UHIP(c, sort(d_e0, d_e1, 2 * OL, NO, d_eoff, 33, nullptr));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, sort(d_e0, d_e1, 2 * OL, NO, d_eoff, 33));
     const int64_t t = static_cast<int64_t>(std::floor(S.q3)); // cov <= q3 <=> cov <= floor(q3) for an integer cov
-    hipLaunchKernelGGL(k_uf_runs<false>, dim3((NO + 255) / 256), dim3(256), 0, st, d_ob, d_ooff, NO, d_bqlen, d_e1, t,
+    hipLaunchKernelGGL(k_uf_runs<false>, dim3(grid256(NO)), dim3(256), 0, st, d_ob, d_ooff, NO, d_bqlen, d_e1, t,
                        d_cnt, nullptr, nullptr);
-    UHIP(c, hipGetLastError());
-    UHIP(c, hipMemcpyAsync(fcount.data(), d_cnt, NO * 4ull, hipMemcpyDeviceToHost, st));
-    UHIP(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, hipMemcpyAsync(fcount.data(), d_cnt, NO * 4ull, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     for (uint32_t i = 0; i < NO; ++i) foff[i + 1] = foff[i] + fcount[i];
     S.n_fragments = foff[NO];
     for (uint32_t i = 0; i < NO; ++i) S.n_rescued += fcount[i] ? 1 : 0;
     if (S.n_fragments) {
       uint2 *d_frag;
-      UHIP(c, D.get(&d_frag, S.n_fragments));
-      UHIP(c, hipMemcpyAsync(d_foff, foff.data(), NO * 4ull, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_uf_runs<true>, dim3((NO + 255) / 256), dim3(256), 0, st, d_ob, d_ooff, NO, d_bqlen, d_e1, t,
+      STAGE_HIP(c, D.get(&d_frag, S.n_fragments));
+      STAGE_HIP(c, hipMemcpyAsync(d_foff, foff.data(), NO * 4ull, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_uf_runs<true>, dim3(grid256(NO)), dim3(256), 0, st, d_ob, d_ooff, NO, d_bqlen, d_e1, t,
                          nullptr, d_foff, d_frag);
-      UHIP(c, hipGetLastError());
+      STAGE_HIP(c, hipGetLastError());
       frags.resize(S.n_fragments);
-      UHIP(c, hipMemcpyAsync(frags.data(), d_frag, S.n_fragments * sizeof(uint2), hipMemcpyDeviceToHost, st));
+      STAGE_HIP(c, hipMemcpyAsync(frags.data(), d_frag, S.n_fragments * sizeof(uint2), hipMemcpyDeviceToHost, st));
     }
   }
-  UHIP(c, hipEventRecord(ev[4], st));
-  UHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- output plan: per block in PAF order the whole record or the fragments
-  const auto            p0 = std::chrono::steady_clock::now();
+  const StageTimer                planning;
   std::vector<msgpu_copy>         pieces;
   std::vector<msgpu_fasta_record> recs;
   std::string                     hdr;
@@ -692,36 +594,32 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
     msgpu_gather_plan *p;
     ~FreePlan() { msgpu_gather_plan_free(p); }
   } free_plan{plan};
-  S.plan_ms = since(p0);
+  S.plan_ms = planning.ms();
   uint8_t *d_raw, *d_text;
-  UHIP(c, D.get(&d_raw, raw + 16));
-  UHIP(c, D.get(&d_text, text + 16));
-  UHIP(c, hipEventRecord(ev[5], st));
+  STAGE_HIP(c, D.get(&d_raw, raw + 16));
+  STAGE_HIP(c, D.get(&d_text, text + 16));
+  STAGE_HIP(c, clock.begin(&S.gather_ms));
   rc = msgpu_gather_run(c->seq, plan, d_raw, raw + 16, st);
   if (rc == MSGPU_OK) {
-    UHIP(c, hipEventRecord(ev[6], st));
+    STAGE_HIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(&S.format_ms)); // (from the same point of the stream)
     rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
   }
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "gather / format: %s", msgpu_seq_last_error(c->seq));
     return rc;
   }
-  UHIP(c, hipEventRecord(ev[7], st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, clock.begin(&S.copy_ms)); // (from the same point of the stream)
   try {
     res->text.resize(text);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (text) UHIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
-  UHIP(c, hipEventRecord(ev[8], st));
-  UHIP(c, hipStreamSynchronize(st));
-  auto el = [&](int a, int b) { return ms_between(ev[a], ev[b]); };
-  S.upload_ms = el(0, 1);
-  S.pass1_ms  = el(1, 2);
-  S.pass2_ms  = el(3, 4);
-  S.gather_ms = el(5, 6);
-  S.format_ms = el(6, 7);
-  S.copy_ms   = el(7, 8);
-  S.wall_ms   = since(w0);
-  *out        = res.release();
+  if (text) STAGE_HIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  clock.collect();
+  S.wall_ms = wall.ms();
+  *out      = res.release();
   return MSGPU_OK;
 }
 

@@ -27,7 +27,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <new>
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(256) void k_kf_copy(const uint8_t *buf, const uint6
 constexpr size_t KF_SLOT = size_t(16) << 20; // page-locked ring: two slots
 
 // mmap -> page-locked ring -> device; the host keeps no copy
-int kf_upload(KfCtx *c, KfDev &D, const char *path, int which, KfFile &f) {
+int kf_upload(StageCtx *c, DevArena &D, const char *path, int which, KfFile &f) {
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   struct stat st;
   if (fd < 0 || fstat(fd, &st) != 0) {
@@ -183,11 +182,11 @@ int kf_upload(KfCtx *c, KfDev &D, const char *path, int which, KfFile &f) {
   } unmap{data, f.size};
   f.open_end = f.size && data[f.size - 1] != '\n';
   const uint64_t padded = (f.size + 15) / 16 * 16 + 16;
-  KHIP(c, D.get(&f.d, padded));
-  KHIP(c, hipMemsetAsync(f.d + f.size, '\n', padded - f.size, c->stream)); // (byte `size` closes a last open line)
+  STAGE_HIP(c, D.get(&f.d, padded));
+  STAGE_HIP(c, hipMemsetAsync(f.d + f.size, '\n', padded - f.size, c->stream)); // (byte `size` closes a last open line)
   char      *ring = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  KHIP(c, hipHostMalloc(reinterpret_cast<void **>(&ring), 2 * KF_SLOT, hipHostMallocDefault));
+  STAGE_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&ring), 2 * KF_SLOT, hipHostMallocDefault));
   struct FreeRing {
     char       *r;
     hipEvent_t *e;
@@ -197,52 +196,46 @@ int kf_upload(KfCtx *c, KfDev &D, const char *path, int which, KfFile &f) {
         if (e[i]) (void)hipEventDestroy(e[i]);
     }
   } free_ring{ring, ev};
-  for (auto &e : ev) KHIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto &e : ev) STAGE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   int slot = 0;
   for (uint64_t at = 0; at < f.size; at += KF_SLOT, slot ^= 1) {
     const size_t n = static_cast<size_t>(std::min<uint64_t>(KF_SLOT, f.size - at));
-    KHIP(c, hipEventSynchronize(ev[slot])); // (a fresh event is complete)
+    STAGE_HIP(c, hipEventSynchronize(ev[slot])); // (a fresh event is complete)
     memcpy(ring + slot * KF_SLOT, data + at, n);
-    KHIP(c, hipMemcpyAsync(f.d + at, ring + slot * KF_SLOT, n, hipMemcpyHostToDevice, c->stream));
-    KHIP(c, hipEventRecord(ev[slot], c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(f.d + at, ring + slot * KF_SLOT, n, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipEventRecord(ev[slot], c->stream));
   }
-  KHIP(c, hipStreamSynchronize(c->stream));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
   return MSGPU_OK;
 }
 
 // the line starts of a file on the device
-int kf_lines(KfCtx *c, KfDev &D, KfFile &f) {
+int kf_lines(StageCtx *c, DevArena &D, KfFile &f) {
   hipStream_t    st = c->stream;
   const uint32_t tiles = static_cast<uint32_t>((f.size + KF_TILE - 1) / KF_TILE);
   uint32_t      *d_cnt;
   uint64_t      *d_off;
-  KHIP(c, D.get(&d_cnt, tiles + 1));
-  KHIP(c, D.get(&d_off, tiles + 1));
-  KHIP(c, hipMemsetAsync(d_cnt, 0, (tiles + 1) * sizeof(uint32_t), st));
+  STAGE_HIP(c, D.get(&d_cnt, tiles + 1));
+  STAGE_HIP(c, D.get(&d_off, tiles + 1));
+  STAGE_HIP(c, hipMemsetAsync(d_cnt, 0, (tiles + 1) * sizeof(uint32_t), st));
   if (tiles) hipLaunchKernelGGL(k_kf_lines<false>, dim3(tiles), dim3(256), 0, st, f.d, f.size, d_cnt, nullptr, nullptr, 0);
-  KHIP(c, hipGetLastError());
-  auto   in = rocprim::make_transform_iterator(d_cnt, KfWiden());
-  size_t need = 0;
-  KHIP(c, rocprim::exclusive_scan(nullptr, need, in, d_off, uint64_t(0), tiles + 1, rocprim::plus<uint64_t>(), st));
-  uint8_t *tmp;
-  KHIP(c, D.get(&tmp, need));
-  KHIP(c, rocprim::exclusive_scan(tmp, need, in, d_off, uint64_t(0), tiles + 1, rocprim::plus<uint64_t>(), st));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan(D, st, rocprim::make_transform_iterator(d_cnt, KfWiden()), d_off, tiles + 1));
   uint64_t nl = 0;
-  KHIP(c, hipMemcpyAsync(&nl, d_off + tiles, 8, hipMemcpyDeviceToHost, st));
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipMemcpyAsync(&nl, d_off + tiles, 8, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
   f.n_lines = nl + (f.open_end ? 1 : 0);
-  KHIP(c, D.get(&f.ls, f.n_lines + 1));
-  KHIP(c, hipMemsetAsync(f.ls, 0, 8, st)); // (an empty file launches nothing)
+  STAGE_HIP(c, D.get(&f.ls, f.n_lines + 1));
+  STAGE_HIP(c, hipMemsetAsync(f.ls, 0, 8, st)); // (an empty file launches nothing)
   if (tiles) hipLaunchKernelGGL(k_kf_lines<true>, dim3(tiles), dim3(256), 0, st, f.d, f.size, nullptr, d_off, f.ls, f.n_lines);
-  KHIP(c, hipGetLastError());
-  KHIP(c, hipStreamSynchronize(st));
-  D.drop(tmp);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, hipStreamSynchronize(st));
   D.drop(d_cnt);
   D.drop(d_off);
   return MSGPU_OK;
 }
 
-int kf_format_error(KfCtx *c, int which, uint64_t line, const char *what) {
+int kf_format_error(StageCtx *c, int which, uint64_t line, const char *what) {
   c->err_file = which;
   c->err_line = line;
   snprintf(c->err, sizeof(c->err), "file %d line %llu: %s", which, static_cast<kf_ull>(line), what);
@@ -250,20 +243,20 @@ int kf_format_error(KfCtx *c, int which, uint64_t line, const char *what) {
 }
 
 // the line starts of every file and the FASTQ rules, file 0 first
-int kf_records(KfCtx *c, KfDev &D, KfFile *F, int n_files) {
+int kf_records(StageCtx *c, DevArena &D, KfFile *F, int n_files) {
   kf_ull *d_bad;
-  KHIP(c, D.get(&d_bad, 1));
+  STAGE_HIP(c, D.get(&d_bad, 1));
   for (int f = 0; f < n_files; ++f) {
     int rc = kf_lines(c, D, F[f]);
     if (rc != MSGPU_OK) return rc;
     kf_ull bad = ~0ull;
-    KHIP(c, hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, c->stream));
     if (F[f].n_lines)
-      hipLaunchKernelGGL(k_kf_check, dim3(static_cast<uint32_t>((F[f].n_lines + 255) / 256)), dim3(256), 0, c->stream, F[f].d,
+      hipLaunchKernelGGL(k_kf_check, dim3(grid256(F[f].n_lines)), dim3(256), 0, c->stream, F[f].d,
                          F[f].ls, F[f].n_lines, d_bad);
-    KHIP(c, hipGetLastError());
-    KHIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
-    KHIP(c, hipStreamSynchronize(c->stream));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    STAGE_HIP(c, hipStreamSynchronize(c->stream));
     if (bad != ~0ull) {
       const char *what[4] = {"a record's first line must start with '@'", "", "a record's third line must start with '+'",
                              "the quality line and the sequence line differ in length"};
@@ -283,7 +276,7 @@ int kf_records(KfCtx *c, KfDev &D, KfFile *F, int n_files) {
 
 using namespace msgpu;
 
-struct msgpu_kfctx : msgpu::KfCtx {};
+struct msgpu_kfctx : msgpu::StageCtx {};
 
 struct msgpu_kf_result {
   msgpu_kf_stats        stats{};
@@ -318,27 +311,26 @@ template <> void kf_split<kf_u128>(const kf_u128 *keys, size_t n, std::vector<ui
 
 // everything behind the format check, for one key width
 template <class K>
-int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k, uint64_t budget,
+int kf_stage(msgpu_kfctx *c, DevArena &D, const KfFile *F, uint64_t n_pairs, int k, uint64_t budget,
              msgpu_kf_result *res) {
   msgpu_kf_stats &S = res->stats;
   hipStream_t     st = c->stream;
-  KfClock         clock;
-  clock.st = st;
+  StageClock      clock(st);
   const uint64_t n_reads = 2 * n_pairs;
   const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_pairs, n_reads, k};
-  const uint32_t read_grid = static_cast<uint32_t>((n_reads + 255) / 256);
+  const uint32_t read_grid = grid256(n_reads);
 
   // ---- windows per hash bin, the partitions
   kf_ull *d_hist, *d_cur;
-  KHIP(c, D.get(&d_hist, KF_HIGH + 1));
-  KHIP(c, D.get(&d_cur, 1));
-  KHIP(c, hipMemsetAsync(d_hist, 0, (KF_HIGH + 1) * 8, st));
+  STAGE_HIP(c, D.get(&d_hist, KF_HIGH + 1));
+  STAGE_HIP(c, D.get(&d_cur, 1));
+  STAGE_HIP(c, hipMemsetAsync(d_hist, 0, (KF_HIGH + 1) * 8, st));
   std::vector<uint64_t> pre;
   int                   rc = kf_bin_prefix<K>(c, D, clock, in, &S.bins_ms, pre);
   if (rc != MSGPU_OK) return rc;
   S.n_windows = pre[KF_BINS];
   size_t free_b = 0, total_b = 0;
-  KHIP(c, hipMemGetInfo(&free_b, &total_b));
+  STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
   const uint64_t out_bytes = F[0].size + F[1].size + 2; // the outputs are no larger than the inputs
   const uint64_t per_key = 2 * sizeof(K) + 4;           // two key buffers and the run lengths
   if (!budget) budget = free_b > out_bytes ? (free_b - out_bytes) / 2 : 0;
@@ -357,18 +349,18 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
   // ---- count: per partition extract, sort, run lengths, histogram, candidates
   std::vector<KfChunk<K>> chunks;
   auto                    histogram = [&](const uint32_t *d_rl, uint32_t runs) -> int {
-    KHIP(c, clock.begin(&S.hist_ms));
-    hipLaunchKernelGGL(k_kf_hist, dim3(std::min<uint32_t>((runs + 255) / 256, 2048)), dim3(256), 0, st, d_rl, runs, d_hist);
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(&S.hist_ms));
+    hipLaunchKernelGGL(k_kf_hist, dim3(std::min<uint32_t>(grid256(runs), 2048)), dim3(256), 0, st, d_rl, runs, d_hist);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
     return MSGPU_OK;
   };
   rc = kf_count<K>(c, D, clock, in, pre, parts, k, KF_KEEP, KfCountMs{&S.extract_ms, &S.sort_ms, &S.runs_ms, &S.select_ms}, d_cur,
                    histogram, chunks, S.n_distinct, S.n_candidates);
   if (rc != MSGPU_OK) return rc;
   std::vector<kf_ull> hist(KF_HIGH + 1);
-  KHIP(c, hipMemcpyAsync(hist.data(), d_hist, (KF_HIGH + 1) * 8, hipMemcpyDeviceToHost, st));
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipMemcpyAsync(hist.data(), d_hist, (KF_HIGH + 1) * 8, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- threshold (host: at most 10001 rows)
   for (uint32_t a = 1; a <= KF_HIGH; ++a)
@@ -386,7 +378,7 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
 
   // ---- the abundant set, ascending, and the table over it
   const uint32_t least = static_cast<uint32_t>(std::min<int64_t>(S.upper, 0xffffffffll));
-  KHIP(c, clock.begin(&S.select_ms));
+  STAGE_HIP(c, clock.begin(&S.select_ms));
   kf_ull n_ab = 0;
   rc = kf_count_selected<K>(c, chunks, least, d_cur, n_ab);
   if (rc != MSGPU_OK) return rc;
@@ -399,48 +391,44 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
   uint32_t *d_abc = nullptr, *d_slots = nullptr, slots_n = 0;
   rc = kf_gather_sorted<K>(c, D, chunks, least, n_ab, k, d_cur, &d_abk, &d_abc, &d_slots, &slots_n);
   if (rc != MSGPU_OK) return rc;
-  KHIP(c, clock.end());
+  STAGE_HIP(c, clock.end());
 
   // ---- verdicts
   uint8_t *d_verdict;
-  KHIP(c, D.get(&d_verdict, n_pairs));
-  KHIP(c, hipMemsetAsync(d_verdict, 0, n_pairs ? n_pairs : 1, st));
-  KHIP(c, clock.begin(&S.verdict_ms));
+  STAGE_HIP(c, D.get(&d_verdict, n_pairs));
+  STAGE_HIP(c, hipMemsetAsync(d_verdict, 0, n_pairs ? n_pairs : 1, st));
+  STAGE_HIP(c, clock.begin(&S.verdict_ms));
   if (n_reads)
     hipLaunchKernelGGL(k_kf_verdict<K>, dim3(read_grid), dim3(256), 0, st, in, d_abk, d_slots, slots_n - 1, d_verdict);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
 
   // ---- output: lengths, scan, copy, per file
   uint64_t *d_len, *d_off;
-  KHIP(c, D.get(&d_len, n_pairs + 1));
-  KHIP(c, D.get(&d_off, n_pairs + 1));
-  size_t need = 0;
-  KHIP(c, rocprim::exclusive_scan(nullptr, need, d_len, d_off, uint64_t(0), n_pairs + 1, rocprim::plus<uint64_t>(), st));
-  uint8_t *d_scan;
-  KHIP(c, D.get(&d_scan, need));
+  STAGE_HIP(c, D.get(&d_len, n_pairs + 1));
+  STAGE_HIP(c, D.get(&d_off, n_pairs + 1));
   uint8_t *d_out[2];
   for (int f = 0; f < 2; ++f) {
-    KHIP(c, clock.begin(&S.output_ms));
-    hipLaunchKernelGGL(k_kf_rec_len, dim3(static_cast<uint32_t>((n_pairs + 256) / 256)), dim3(256), 0, st, F[f].ls, d_verdict,
+    STAGE_HIP(c, clock.begin(&S.output_ms));
+    hipLaunchKernelGGL(k_kf_rec_len, dim3(grid256(n_pairs + 1)), dim3(256), 0, st, F[f].ls, d_verdict,
                        n_pairs, d_len);
-    KHIP(c, hipGetLastError());
-    KHIP(c, rocprim::exclusive_scan(d_scan, need, d_len, d_off, uint64_t(0), n_pairs + 1, rocprim::plus<uint64_t>(), st));
-    KHIP(c, hipMemcpyAsync(&res->out_len[f], d_off + n_pairs, 8, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_scan(D, st, d_len, d_off, n_pairs + 1));
+    STAGE_HIP(c, hipMemcpyAsync(&res->out_len[f], d_off + n_pairs, 8, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     const uint64_t n = res->out_len[f];
-    KHIP(c, D.get(&d_out[f], n));
+    STAGE_HIP(c, D.get(&d_out[f], n));
     if (n)
-      hipLaunchKernelGGL(k_kf_copy, dim3(static_cast<uint32_t>((n_pairs + 3) / 4)), dim3(256), 0, st, F[f].d, F[f].ls,
+      hipLaunchKernelGGL(k_kf_copy, dim3(grid_of(n_pairs, 4)), dim3(256), 0, st, F[f].d, F[f].ls,
                          d_verdict, d_off, n_pairs, d_out[f], n);
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
   }
-  KHIP(c, clock.begin(&S.copy_ms));
+  STAGE_HIP(c, clock.begin(&S.copy_ms));
   for (int f = 0; f < 2; ++f)
     if (res->out_len[f]) {
-      KHIP(c, hipHostMalloc(reinterpret_cast<void **>(&res->out[f]), res->out_len[f], hipHostMallocDefault));
-      KHIP(c, hipMemcpyAsync(res->out[f], d_out[f], res->out_len[f], hipMemcpyDeviceToHost, st));
+      STAGE_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&res->out[f]), res->out_len[f], hipHostMallocDefault));
+      STAGE_HIP(c, hipMemcpyAsync(res->out[f], d_out[f], res->out_len[f], hipMemcpyDeviceToHost, st));
     }
   std::vector<K> abk;
   try {
@@ -448,13 +436,13 @@ int kf_stage(msgpu_kfctx *c, KfDev &D, const KfFile *F, uint64_t n_pairs, int k,
     res->count.resize(n_ab);
     abk.resize(n_ab);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (n_pairs) KHIP(c, hipMemcpyAsync(res->verdict.data(), d_verdict, n_pairs, hipMemcpyDeviceToHost, st));
+  if (n_pairs) STAGE_HIP(c, hipMemcpyAsync(res->verdict.data(), d_verdict, n_pairs, hipMemcpyDeviceToHost, st));
   if (n_ab) {
-    KHIP(c, hipMemcpyAsync(res->count.data(), d_abc, n_ab * 4, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipMemcpyAsync(abk.data(), d_abk, n_ab * sizeof(K), hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(res->count.data(), d_abc, n_ab * 4, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(abk.data(), d_abk, n_ab * sizeof(K), hipMemcpyDeviceToHost, st));
   }
-  KHIP(c, clock.end());
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
   clock.collect();
   try {
     kf_split<K>(abk.data(), abk.size(), res->key_hi, res->key_lo);
@@ -498,32 +486,8 @@ int msgpu_kf_threshold(const uint64_t *abundance, const uint64_t *frequency, siz
   return (*q3 == 0 || *upper <= 0) ? MSGPU_E_LAYOUT : MSGPU_OK;
 }
 
-int msgpu_kf_create(int device, msgpu_kfctx **out) {
-  if (!out) return MSGPU_E_ARG;
-  *out     = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
-  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
-  auto *c = new (std::nothrow) msgpu_kfctx();
-  if (!c) return MSGPU_E_NOMEM;
-  c->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    msgpu_kf_destroy(c);
-    return MSGPU_E_HIP;
-  }
-  *out = c;
-  return MSGPU_OK;
-}
-
-void msgpu_kf_destroy(msgpu_kfctx *c) {
-  if (!c) return;
-  if (c->stream) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamDestroy(c->stream);
-  }
-  delete c;
-}
+int  msgpu_kf_create(int device, msgpu_kfctx **out) { return stage_create(device, out); }
+void msgpu_kf_destroy(msgpu_kfctx *c) { stage_destroy(c); }
 
 const char *msgpu_kf_last_error(const msgpu_kfctx *c) { return c ? c->err : "null context"; }
 uint64_t    msgpu_kf_error_line(const msgpu_kfctx *c) { return c ? c->err_line : 0; }
@@ -541,18 +505,15 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
     snprintf(c->err, sizeof(c->err), "k = %d is outside 1..64", k);
     return MSGPU_E_ARG;
   }
-  const auto w0 = std::chrono::steady_clock::now();
-  auto       since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
-  KHIP(c, hipSetDevice(c->device));
+  const StageTimer wall;
+  STAGE_HIP(c, hipSetDevice(c->device));
   std::unique_ptr<msgpu_kf_result> res;
   try {
     res.reset(new msgpu_kf_result());
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   msgpu_kf_stats &S = res->stats;
   S.k               = static_cast<uint32_t>(k);
-  KfDev       D;
+  DevArena    D;
   KfFile      F[2];
   const char *paths[2] = {path_a, path_b};
   for (int f = 0; f < 2; ++f) {
@@ -560,10 +521,10 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
     if (rc != MSGPU_OK) return rc;
     S.bytes_in[f] = F[f].size;
   }
-  S.load_ms = since(w0);
+  S.load_ms = wall.ms();
 
   // ---- records: line starts, the format rules
-  const auto r0 = std::chrono::steady_clock::now();
+  const StageTimer records;
   {
     const int rc = kf_records(c, D, F, 2);
     if (rc != MSGPU_OK) return rc;
@@ -574,7 +535,7 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
   }
   const uint64_t n_pairs = F[0].n_lines >> 2;
   S.n_pairs    = n_pairs;
-  S.records_ms = since(r0);
+  S.records_ms = records.ms();
 
   const int rc = k <= 32 ? kf_stage<uint64_t>(c, D, F, n_pairs, k, budget_bytes, res.get())
                          : kf_stage<kf_u128>(c, D, F, n_pairs, k, budget_bytes, res.get());
@@ -590,7 +551,7 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   S.bytes_out[0] = res->out_len[0];
   S.bytes_out[1] = res->out_len[1];
-  S.wall_ms      = since(w0);
+  S.wall_ms      = wall.ms();
   *out           = res.release();
   return MSGPU_OK;
 }

@@ -1,8 +1,9 @@
 // msgpu_kmer_shared.h -- what the k-mer abundance filter (msgpu_kmer.hip) and the short-read unitig assembly
 // (msgpu_unitig.hip) both use, defined once: the rolling window, the hash and the partitions cut from its bins, the window
 // kernels (bins, extract), the selection of (key, count) pairs, the open-addressing table of indices over a sorted key array,
-// and on the host the device-memory and event helpers, the partitioned exact count and the gathering of its chunks into
-// one sorted array.  The file upload, the line starts and the FASTQ check live in msgpu_kmer.hip and are declared here.
+// and on the host the partitioned exact count and the gathering of its chunks into one sorted array (on the stage
+// scaffolding of msgpu_stage.h).  The file upload, the line starts and the FASTQ check live in msgpu_kmer.hip and are
+// declared here.
 #ifndef MSGPU_KMER_SHARED_H
 #define MSGPU_KMER_SHARED_H
 
@@ -17,6 +18,7 @@
 
 #include "msgpu.h"
 #include "msgpu_internal.h"
+#include "msgpu_stage.h"
 
 namespace msgpu {
 
@@ -180,106 +182,6 @@ template <class K> __device__ inline uint32_t kf_find(const K *keys, const uint3
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-struct KfCtx { // what a stage context is made of
-  int         device = 0;
-  hipStream_t stream = nullptr;
-  char        err[384] = {0};
-  uint64_t    err_line = 0;
-  int         err_file = 0;
-};
-
-inline int kfail(KfCtx *c, int code, const char *what, hipError_t e) {
-  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-  return code;
-}
-#define KHIP(c, expr)                                                                                                  \
-  do {                                                                                                                 \
-    hipError_t _e = (expr);                                                                                            \
-    if (_e != hipSuccess) return kfail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
-  } while (0)
-
-// The scalar block as it stands, through the project's read-back protocol (msgpu_device.h, publish_to_host): one wavefront
-// writes it into the mapped mirror and publishes a sequence number, the host polls for it.  A stream that ends without
-// the number arriving is answered by a copy, and counted.  d = the block on the device (SC_COUNT words), h = its page-locked,
-// device-mapped mirror with the sequence number behind it, h_dev = the device's address of the mirror (null: every read-back
-// is a copy).  One definition for the stages that own such a block (msgpu_unitig.hip, msgpu_map.hip).
-inline int kf_read_scalars(KfCtx *c, uint64_t *d, uint64_t *h, uint64_t *h_dev, uint64_t &seq_no, uint64_t &lost) {
-  if (h_dev) {
-    const uint64_t seq = ++seq_no;
-    launch_publish_scalars(c->stream, d, HostPublish{h_dev, seq});
-    KHIP(c, hipGetLastError());
-    volatile uint64_t *flag = h + SC_COUNT;
-    for (uint64_t spins = 1;; ++spins) {
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
-      __builtin_ia32_pause();
-      if ((spins & 0xffff) == 0) {
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q == hipSuccess) {
-          if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
-          break;
-        }
-        if (q != hipErrorNotReady) break;
-      }
-    }
-    ++lost;
-  }
-  KHIP(c, hipMemcpyAsync(h, d, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  KHIP(c, hipStreamSynchronize(c->stream));
-  return MSGPU_OK;
-}
-
-struct KfDev { // device memory freed on every way out of msgpu_kf_run
-  std::vector<void *> p;
-  ~KfDev() {
-    for (void *x : p) (void)hipFree(x);
-  }
-  template <class T> hipError_t get(T **out, size_t count) {
-    void      *m = nullptr;
-    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(m);
-    *out = static_cast<T *>(m);
-    return e;
-  }
-  void drop(void *x) {
-    auto it = std::find(p.begin(), p.end(), x);
-    if (it != p.end()) p.erase(it);
-    (void)hipFree(x);
-  }
-};
-
-struct KfClock { // device steps by event pairs, summed per step after the run's last synchronisation
-  struct Span {
-    hipEvent_t a, b;
-    float     *acc;
-  };
-  std::vector<Span> spans;
-  hipStream_t       st;
-  ~KfClock() {
-    for (auto &s : spans) {
-      (void)hipEventDestroy(s.a);
-      (void)hipEventDestroy(s.b);
-    }
-  }
-  hipError_t begin(float *acc) {
-    Span       s{nullptr, nullptr, acc};
-    hipError_t e = hipEventCreate(&s.a);
-    if (e == hipSuccess) e = hipEventCreate(&s.b);
-    if (e == hipSuccess) e = hipEventRecord(s.a, st);
-    spans.push_back(s);
-    return e;
-  }
-  hipError_t end() { return hipEventRecord(spans.back().b, st); }
-  void       collect() { // (after a synchronisation)
-    for (auto &s : spans) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) *s.acc += ms;
-      (void)hipEventDestroy(s.a);
-      (void)hipEventDestroy(s.b);
-    }
-    spans.clear();
-  }
-};
-
 struct KfFile {
   uint8_t  *d = nullptr;
   uint64_t  size = 0, n_lines = 0;
@@ -288,10 +190,10 @@ struct KfFile {
 };
 
 // defined in msgpu_kmer.hip
-int kf_upload(KfCtx *c, KfDev &D, const char *path, int which, KfFile &f); // mmap -> page-locked ring -> device
-int kf_lines(KfCtx *c, KfDev &D, KfFile &f);                                // the line starts of a file on the device
-int kf_format_error(KfCtx *c, int which, uint64_t line, const char *what);
-int kf_records(KfCtx *c, KfDev &D, KfFile *F, int n_files); // line starts and the FASTQ rules of every file, file 0 first
+int kf_upload(StageCtx *c, DevArena &D, const char *path, int which, KfFile &f); // mmap -> page-locked ring -> device
+int kf_lines(StageCtx *c, DevArena &D, KfFile &f);                                // the line starts of a file on the device
+int kf_format_error(StageCtx *c, int which, uint64_t line, const char *what);
+int kf_records(StageCtx *c, DevArena &D, KfFile *F, int n_files); // line starts and the FASTQ rules of every file, file 0 first
 
 // ---- the partitions: P ranges of the KF_BINS hash bins
 inline uint32_t kf_first_bin(uint32_t p, uint32_t P) { return static_cast<uint32_t>((uint64_t(p) * KF_BINS + P - 1) / P); }
@@ -314,19 +216,19 @@ inline KfParts kf_pick_partitions(const std::vector<uint64_t> &pre, uint64_t per
 }
 
 // windows per hash bin -> their prefix sums (KF_BINS + 1 entries)
-template <class K> int kf_bin_prefix(KfCtx *c, KfDev &D, KfClock &clock, const KfIn &in, float *ms, std::vector<uint64_t> &pre) {
+template <class K> int kf_bin_prefix(StageCtx *c, DevArena &D, StageClock &clock, const KfIn &in, float *ms, std::vector<uint64_t> &pre) {
   hipStream_t st = c->stream;
   kf_ull     *d_bins;
-  KHIP(c, D.get(&d_bins, KF_BINS));
-  KHIP(c, hipMemsetAsync(d_bins, 0, KF_BINS * 8, st));
-  KHIP(c, clock.begin(ms));
-  const uint32_t read_grid = static_cast<uint32_t>((in.n_reads + 255) / 256);
+  STAGE_HIP(c, D.get(&d_bins, KF_BINS));
+  STAGE_HIP(c, hipMemsetAsync(d_bins, 0, KF_BINS * 8, st));
+  STAGE_HIP(c, clock.begin(ms));
+  const uint32_t read_grid = grid256(in.n_reads);
   if (in.n_reads) hipLaunchKernelGGL(k_kf_bins<K>, dim3(std::min<uint32_t>(read_grid, 4096)), dim3(256), 0, st, in, d_bins);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
   std::vector<kf_ull> bins(KF_BINS);
-  KHIP(c, hipMemcpyAsync(bins.data(), d_bins, KF_BINS * 8, hipMemcpyDeviceToHost, st));
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipMemcpyAsync(bins.data(), d_bins, KF_BINS * 8, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
   pre.assign(KF_BINS + 1, 0);
   for (uint32_t b = 0; b < KF_BINS; ++b) pre[b + 1] = pre[b] + bins[b];
   D.drop(d_bins);
@@ -345,81 +247,81 @@ struct KfCountMs {
 // The exact count: per partition extract, sort, run lengths; `each(run lengths, runs)` sees every partition's counts (the
 // filter's histogram); the (key, count) with count >= least stay on the device as one chunk per partition.
 template <class K, class Each>
-int kf_count(KfCtx *c, KfDev &D, KfClock &clock, const KfIn &in, const std::vector<uint64_t> &pre, const KfParts &parts, int k,
+int kf_count(StageCtx *c, DevArena &D, StageClock &clock, const KfIn &in, const std::vector<uint64_t> &pre, const KfParts &parts, int k,
              uint32_t least, const KfCountMs &ms, kf_ull *d_cur, Each &&each, std::vector<KfChunk<K>> &chunks, uint64_t &n_distinct,
              uint64_t &n_kept) {
   hipStream_t    st = c->stream;
-  const uint32_t P = parts.P, read_grid = static_cast<uint32_t>((in.n_reads + 255) / 256);
+  const uint32_t P = parts.P, read_grid = grid256(in.n_reads);
   const uint64_t largest = parts.largest;
   K             *d_a, *d_b;
   uint32_t      *d_rl, *d_nruns;
-  KHIP(c, D.get(&d_a, largest));
-  KHIP(c, D.get(&d_b, largest));
-  KHIP(c, D.get(&d_rl, largest));
-  KHIP(c, D.get(&d_nruns, 1));
+  STAGE_HIP(c, D.get(&d_a, largest));
+  STAGE_HIP(c, D.get(&d_b, largest));
+  STAGE_HIP(c, D.get(&d_rl, largest));
+  STAGE_HIP(c, D.get(&d_nruns, 1));
   size_t need_sort = 0, need_rle = 0;
   {
     rocprim::double_buffer<K> db(d_a, d_b);
-    KHIP(c, rocprim::radix_sort_keys(nullptr, need_sort, db, largest, 0, 2 * k, st));
-    KHIP(c, rocprim::run_length_encode(nullptr, need_rle, d_a, static_cast<unsigned int>(largest), d_b, d_rl, d_nruns, st));
+    STAGE_HIP(c, rocprim::radix_sort_keys(nullptr, need_sort, db, largest, 0, 2 * k, st));
+    STAGE_HIP(c, rocprim::run_length_encode(nullptr, need_rle, d_a, static_cast<unsigned int>(largest), d_b, d_rl, d_nruns, st));
   }
   const size_t tmp_bytes = std::max(need_sort, need_rle);
   uint8_t     *d_tmp;
-  KHIP(c, D.get(&d_tmp, tmp_bytes));
+  STAGE_HIP(c, D.get(&d_tmp, tmp_bytes));
   for (uint32_t p = 0; p < P; ++p) {
     const uint64_t n = pre[kf_first_bin(p + 1, P)] - pre[kf_first_bin(p, P)];
     if (!n) continue;
-    KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
-    KHIP(c, clock.begin(ms.extract));
+    STAGE_HIP(c, hipMemsetAsync(d_cur, 0, 8, st));
+    STAGE_HIP(c, clock.begin(ms.extract));
     hipLaunchKernelGGL(k_kf_extract<K>, dim3(read_grid), dim3(256), 0, st, in, P, p, d_a, n, d_cur);
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
     rocprim::double_buffer<K> db(d_a, d_b);
     size_t                    tb = tmp_bytes;
-    KHIP(c, clock.begin(ms.sort));
-    KHIP(c, rocprim::radix_sort_keys(d_tmp, tb, db, n, 0, 2 * k, st));
-    KHIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(ms.sort));
+    STAGE_HIP(c, rocprim::radix_sort_keys(d_tmp, tb, db, n, 0, 2 * k, st));
+    STAGE_HIP(c, clock.end());
     K *sorted = db.current(), *uniq = db.alternate();
     tb = tmp_bytes;
-    KHIP(c, clock.begin(ms.runs));
-    KHIP(c, rocprim::run_length_encode(d_tmp, tb, sorted, static_cast<unsigned int>(n), uniq, d_rl, d_nruns, st));
-    KHIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(ms.runs));
+    STAGE_HIP(c, rocprim::run_length_encode(d_tmp, tb, sorted, static_cast<unsigned int>(n), uniq, d_rl, d_nruns, st));
+    STAGE_HIP(c, clock.end());
     uint32_t runs = 0;
     kf_ull   written = 0;
-    KHIP(c, hipMemcpyAsync(&runs, d_nruns, 4, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipMemcpyAsync(&written, d_cur, 8, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipMemcpyAsync(&runs, d_nruns, 4, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(&written, d_cur, 8, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     if (written != n) { // the two window passes disagree: never seen; a result built on it would be wrong
       snprintf(c->err, sizeof(c->err), "partition %u: %llu keys extracted where %llu were counted", p, written,
                static_cast<kf_ull>(n));
       return MSGPU_E_STATE;
     }
     n_distinct += runs;
-    const uint32_t run_grid = (runs + 255) / 256;
-    KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
+    const uint32_t run_grid = grid256(runs);
+    STAGE_HIP(c, hipMemsetAsync(d_cur, 0, 8, st));
     const int rc = each(d_rl, runs);
     if (rc != MSGPU_OK) return rc;
-    KHIP(c, clock.begin(ms.select));
+    STAGE_HIP(c, clock.begin(ms.select));
     hipLaunchKernelGGL((k_kf_select<K, false>), dim3(run_grid), dim3(256), 0, st, uniq, d_rl, runs, least, nullptr, nullptr, 0,
                        d_cur);
-    KHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     kf_ull kept = 0;
-    KHIP(c, hipMemcpyAsync(&kept, d_cur, 8, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipMemcpyAsync(&kept, d_cur, 8, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     if (kept) {
       KfChunk<K> ch{nullptr, nullptr, kept};
-      KHIP(c, D.get(&ch.k, kept));
-      KHIP(c, D.get(&ch.c, kept));
-      KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
+      STAGE_HIP(c, D.get(&ch.k, kept));
+      STAGE_HIP(c, D.get(&ch.c, kept));
+      STAGE_HIP(c, hipMemsetAsync(d_cur, 0, 8, st));
       hipLaunchKernelGGL((k_kf_select<K, true>), dim3(run_grid), dim3(256), 0, st, uniq, d_rl, runs, least, ch.k, ch.c, kept,
                          d_cur);
-      KHIP(c, hipGetLastError());
+      STAGE_HIP(c, hipGetLastError());
       chunks.push_back(ch);
       n_kept += kept;
     }
-    KHIP(c, clock.end());
+    STAGE_HIP(c, clock.end());
   }
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
   D.drop(d_a);
   D.drop(d_b);
   D.drop(d_rl);
@@ -429,41 +331,41 @@ int kf_count(KfCtx *c, KfDev &D, KfClock &clock, const KfIn &in, const std::vect
 }
 
 // how many (key, count) of the chunks have count >= least
-template <class K> int kf_count_selected(KfCtx *c, const std::vector<KfChunk<K>> &chunks, uint32_t least, kf_ull *d_cur, kf_ull &n) {
+template <class K> int kf_count_selected(StageCtx *c, const std::vector<KfChunk<K>> &chunks, uint32_t least, kf_ull *d_cur, kf_ull &n) {
   hipStream_t st = c->stream;
-  KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
+  STAGE_HIP(c, hipMemsetAsync(d_cur, 0, 8, st));
   for (const KfChunk<K> &ch : chunks)
-    hipLaunchKernelGGL((k_kf_select<K, false>), dim3(static_cast<uint32_t>((ch.n + 255) / 256)), dim3(256), 0, st, ch.k, ch.c,
+    hipLaunchKernelGGL((k_kf_select<K, false>), dim3(grid256(ch.n)), dim3(256), 0, st, ch.k, ch.c,
                        ch.n, least, nullptr, nullptr, 0, d_cur);
-  KHIP(c, hipGetLastError());
-  KHIP(c, hipMemcpyAsync(&n, d_cur, 8, hipMemcpyDeviceToHost, st));
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, hipMemcpyAsync(&n, d_cur, 8, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
   return MSGPU_OK;
 }
 
 // those n pairs as one array sorted ascending by key (the chunks are freed), and the open-addressing table of indices over it
 template <class K>
-int kf_gather_sorted(KfCtx *c, KfDev &D, std::vector<KfChunk<K>> &chunks, uint32_t least, uint64_t n, int k, kf_ull *d_cur,
+int kf_gather_sorted(StageCtx *c, DevArena &D, std::vector<KfChunk<K>> &chunks, uint32_t least, uint64_t n, int k, kf_ull *d_cur,
                      K **keys, uint32_t **counts, uint32_t **slots, uint32_t *slots_n) {
   hipStream_t st = c->stream;
   K          *d_k = nullptr, *d_k_in;
   uint32_t   *d_c = nullptr, *d_c_in;
-  KHIP(c, D.get(&d_k, n));
-  KHIP(c, D.get(&d_c, n));
+  STAGE_HIP(c, D.get(&d_k, n));
+  STAGE_HIP(c, D.get(&d_c, n));
   if (n) {
-    KHIP(c, D.get(&d_k_in, n));
-    KHIP(c, D.get(&d_c_in, n));
-    KHIP(c, hipMemsetAsync(d_cur, 0, 8, st));
+    STAGE_HIP(c, D.get(&d_k_in, n));
+    STAGE_HIP(c, D.get(&d_c_in, n));
+    STAGE_HIP(c, hipMemsetAsync(d_cur, 0, 8, st));
     for (const KfChunk<K> &ch : chunks)
-      hipLaunchKernelGGL((k_kf_select<K, true>), dim3(static_cast<uint32_t>((ch.n + 255) / 256)), dim3(256), 0, st, ch.k, ch.c,
+      hipLaunchKernelGGL((k_kf_select<K, true>), dim3(grid256(ch.n)), dim3(256), 0, st, ch.k, ch.c,
                          ch.n, least, d_k_in, d_c_in, n, d_cur);
-    KHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     size_t need = 0;
-    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, d_k_in, d_k, d_c_in, d_c, n, 0, 2 * k, st));
+    STAGE_HIP(c, rocprim::radix_sort_pairs(nullptr, need, d_k_in, d_k, d_c_in, d_c, n, 0, 2 * k, st));
     uint8_t *tmp;
-    KHIP(c, D.get(&tmp, need));
-    KHIP(c, rocprim::radix_sort_pairs(tmp, need, d_k_in, d_k, d_c_in, d_c, n, 0, 2 * k, st));
-    KHIP(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, D.get(&tmp, need));
+    STAGE_HIP(c, rocprim::radix_sort_pairs(tmp, need, d_k_in, d_k, d_c_in, d_c, n, 0, 2 * k, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     D.drop(tmp);
     D.drop(d_k_in);
     D.drop(d_c_in);
@@ -476,12 +378,12 @@ int kf_gather_sorted(KfCtx *c, KfDev &D, std::vector<KfChunk<K>> &chunks, uint32
   uint32_t sn = 64;
   while (sn < 2 * n) sn <<= 1;
   uint32_t *d_slots;
-  KHIP(c, D.get(&d_slots, sn));
-  KHIP(c, hipMemsetAsync(d_slots, 0xff, sn * 4ull, st));
+  STAGE_HIP(c, D.get(&d_slots, sn));
+  STAGE_HIP(c, hipMemsetAsync(d_slots, 0xff, sn * 4ull, st));
   if (n)
-    hipLaunchKernelGGL(k_kf_table<K>, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, st, d_k, static_cast<uint32_t>(n),
+    hipLaunchKernelGGL(k_kf_table<K>, dim3(grid256(n)), dim3(256), 0, st, d_k, static_cast<uint32_t>(n),
                        d_slots, sn - 1);
-  KHIP(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   *keys    = d_k;
   *counts  = d_c;
   *slots   = d_slots;

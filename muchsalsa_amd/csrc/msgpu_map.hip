@@ -22,7 +22,6 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/device/device_segmented_reduce.hpp>
 
-#include <chrono>
 #include <memory>
 #include <new>
 #include <string>
@@ -474,10 +473,13 @@ using namespace msgpu;
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-struct msgpu_mapctx : msgpu::KfCtx {
-  msgpu_seqctx *seq = nullptr;
-  uint64_t     *d_scalars = nullptr, *h_scalars = nullptr, *h_scalars_dev = nullptr; // as msgpu_ugctx
-  uint64_t      seq_no = 0, lost = 0;
+struct msgpu_mapctx : msgpu::StageCtx {
+  SeqCtxHold  seq;
+  ScalarBlock sc;
+  int         open() {
+    const int rc = msgpu_seq_create(device, &seq.p);
+    return rc != MSGPU_OK ? rc : sc.create() ? MSGPU_OK : MSGPU_E_HIP;
+  }
 };
 
 struct msgpu_map_result {
@@ -492,22 +494,7 @@ enum { MP_SC_DROPK = 0, MP_SC_DROPE, MP_SC_LARGEST, MP_SC_TOTAL, MP_SC_TOTAL2, M
        MP_SC_CAPPED };
 static_assert(MP_SC_CAPPED < SC_COUNT, "the scalar block");
 
-int mp_read_scalars(msgpu_mapctx *c) { return kf_read_scalars(c, c->d_scalars, c->h_scalars, c->h_scalars_dev, c->seq_no, c->lost); } // (msgpu_kmer_shared.h)
-
-inline uint32_t mp_grid(uint64_t n, uint32_t per = 256) { return static_cast<uint32_t>((n + per - 1) / per); }
-inline kf_ull  *mp_slot(msgpu_mapctx *c, int slot) { return reinterpret_cast<kf_ull *>(c->d_scalars + slot); }
-
-// exclusive scan of n + 1 words (the last is the caller's zero), so out[n] is the total
-template <class Out> int mp_scan(msgpu_mapctx *c, KfDev &D, const uint32_t *in, Out *out, uint64_t n_plus_1) {
-  size_t need = 0;
-  KHIP(c, rocprim::exclusive_scan(nullptr, need, in, out, static_cast<Out>(0), n_plus_1, rocprim::plus<Out>(), c->stream));
-  uint8_t *tmp;
-  KHIP(c, D.get(&tmp, need));
-  KHIP(c, rocprim::exclusive_scan(tmp, need, in, out, static_cast<Out>(0), n_plus_1, rocprim::plus<Out>(), c->stream));
-  KHIP(c, hipStreamSynchronize(c->stream));
-  D.drop(tmp);
-  return MSGPU_OK;
-}
+inline kf_ull *mp_slot(msgpu_mapctx *c, int slot) { return reinterpret_cast<kf_ull *>(c->sc.d + slot); }
 
 struct MpFile { // a file in its store
   msgpu_seqfile *f = nullptr;
@@ -517,7 +504,7 @@ struct MpFile { // a file in its store
   ~MpFile() { msgpu_seq_free(f); }
 };
 
-int mp_load(msgpu_mapctx *c, KfDev &D, const char *path, int kind, const char *what, MpFile &F) {
+int mp_load(msgpu_mapctx *c, DevArena &D, const char *path, int kind, const char *what, MpFile &F) {
   int rc = msgpu_seq_parse_upload(c->seq, kind, path, -1, &F.f);
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "%s %s: %s", what, path, msgpu_seq_last_error(c->seq));
@@ -549,12 +536,12 @@ int mp_load(msgpu_mapctx *c, KfDev &D, const char *path, int kind, const char *w
     snprintf(c->err, sizeof(c->err), "%s: %llu bases; the limit is 2^38 - 1", what, static_cast<kf_ull>(n_bases));
     return MSGPU_E_ARG;
   }
-  KHIP(c, D.get(&F.d_off, n));
-  KHIP(c, D.get(&F.d_len, n));
+  STAGE_HIP(c, D.get(&F.d_off, n));
+  STAGE_HIP(c, D.get(&F.d_len, n));
   if (n) {
-    KHIP(c, hipMemcpyAsync(F.d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
-    KHIP(c, hipMemcpyAsync(F.d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
-    KHIP(c, hipStreamSynchronize(c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(F.d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(F.d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipStreamSynchronize(c->stream));
   }
   F.recs.off     = F.d_off;
   F.recs.len     = F.d_len;
@@ -568,35 +555,36 @@ struct MpSketch {
   uint64_t  n = 0;
 };
 
-int mp_sketch(msgpu_mapctx *c, KfDev &D, KfClock &clock, float *ms, const MpRecs &R, int k, int w, const char *what, MpSketch &S) {
+int mp_sketch(msgpu_mapctx *c, DevArena &D, StageClock &clock, float *ms, const MpRecs &R, int k, int w, const char *what, MpSketch &S) {
   hipStream_t    st = c->stream;
-  const uint32_t tiles = mp_grid(R.n_bases, MP_TILE);
+  const uint32_t tiles = grid_of(R.n_bases, MP_TILE);
   uint32_t      *d_cnt;
   uint64_t      *d_off;
-  KHIP(c, D.get(&d_cnt, tiles + 1ull));
-  KHIP(c, D.get(&d_off, tiles + 1ull));
-  KHIP(c, hipMemsetAsync(d_cnt, 0, (tiles + 1ull) * 4, st));
-  KHIP(c, clock.begin(ms));
+  STAGE_HIP(c, D.get(&d_cnt, tiles + 1ull));
+  STAGE_HIP(c, D.get(&d_off, tiles + 1ull));
+  STAGE_HIP(c, hipMemsetAsync(d_cnt, 0, (tiles + 1ull) * 4, st));
+  STAGE_HIP(c, clock.begin(ms));
   if (tiles) hipLaunchKernelGGL((k_mp_sketch<false>), dim3(tiles), dim3(256), 0, st, R, k, w, d_cnt, nullptr, nullptr, nullptr, 0);
-  KHIP(c, hipGetLastError());
-  int rc = mp_scan<uint64_t>(c, D, d_cnt, d_off, tiles + 1ull);
+  STAGE_HIP(c, hipGetLastError());
+  // (the last word is the zero above: d_off[tiles] is the total; every scan of this file reads through a const pointer, one
+  // instantiation per output type)
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_cnt, d_off, tiles + 1ull));
+  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_off + tiles);
+  STAGE_HIP(c, clock.end());
+  int rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_off + tiles);
-  KHIP(c, clock.end());
-  rc = mp_read_scalars(c);
-  if (rc != MSGPU_OK) return rc;
-  S.n = c->h_scalars[MP_SC_TOTAL];
+  S.n = c->sc.h[MP_SC_TOTAL];
   if (S.n >= (1ull << 31)) {
     snprintf(c->err, sizeof(c->err), "%s: %llu minimizers; the limit is 2^31 - 1", what, static_cast<kf_ull>(S.n));
     return MSGPU_E_ARG;
   }
-  KHIP(c, D.get(&S.keys, S.n));
-  KHIP(c, D.get(&S.vals, S.n));
-  KHIP(c, clock.begin(ms));
+  STAGE_HIP(c, D.get(&S.keys, S.n));
+  STAGE_HIP(c, D.get(&S.vals, S.n));
+  STAGE_HIP(c, clock.begin(ms));
   if (S.n) hipLaunchKernelGGL((k_mp_sketch<true>), dim3(tiles), dim3(256), 0, st, R, k, w, nullptr, d_off, S.keys, S.vals, S.n);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
   D.drop(d_cnt);
   D.drop(d_off);
   return MSGPU_OK;
@@ -622,16 +610,12 @@ void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_se
 int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, const char *qpath, msgpu_map_result *res) {
   msgpu_map_stats &S = res->stats;
   hipStream_t      st = c->stream;
-  KfDev            D;
-  KfClock          clock;
-  clock.st = st;
+  DevArena         D;
+  StageClock       clock(st);
   const int  k = prm.k, w = prm.w;
   const bool ava = prm.ava != 0, exact = prm.exact != 0;
-  const auto w0 = std::chrono::steady_clock::now();
-  auto       since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
-  KHIP(c, hipMemsetAsync(c->d_scalars, 0, SC_COUNT * sizeof(uint64_t), st));
+  const StageTimer wall;
+  STAGE_HIP(c, hipMemsetAsync(c->sc.d, 0, SC_COUNT * sizeof(uint64_t), st));
 
   // ---- the files
   MpFile Tf, Qf_own;
@@ -646,7 +630,7 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   S.n_records[1] = Qf.recs.n;
   S.n_bases[0]   = Tf.recs.n_bases;
   S.n_bases[1]   = Qf.recs.n_bases;
-  S.load_ms      = since(w0);
+  S.load_ms      = wall.ms();
 
   // ---- rule 2 on both files, rule 3
   MpSketch Ts, Qs_own;
@@ -662,35 +646,29 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   const uint32_t NT = static_cast<uint32_t>(Ts.n);
   uint64_t      *d_ikeys, *d_ivals, *d_ukeys;
   uint32_t      *d_ucnt, *d_ustart, *d_nruns, *d_slots;
-  KHIP(c, D.get(&d_ikeys, NT));
-  KHIP(c, D.get(&d_ivals, NT));
-  KHIP(c, D.get(&d_ukeys, NT));
-  KHIP(c, D.get(&d_ucnt, NT + 1ull));
-  KHIP(c, D.get(&d_ustart, NT + 1ull));
-  KHIP(c, D.get(&d_nruns, 1));
-  KHIP(c, hipMemsetAsync(d_nruns, 0, 4, st));
+  STAGE_HIP(c, D.get(&d_ikeys, NT));
+  STAGE_HIP(c, D.get(&d_ivals, NT));
+  STAGE_HIP(c, D.get(&d_ukeys, NT));
+  STAGE_HIP(c, D.get(&d_ucnt, NT + 1ull));
+  STAGE_HIP(c, D.get(&d_ustart, NT + 1ull));
+  STAGE_HIP(c, D.get(&d_nruns, 1));
+  STAGE_HIP(c, hipMemsetAsync(d_nruns, 0, 4, st));
   uint32_t n_keys = 0;
   if (NT) {
-    size_t need = 0, need2 = 0;
-    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, Ts.keys, d_ikeys, Ts.vals, d_ivals, NT, 0, 2 * k, st));
-    KHIP(c, rocprim::run_length_encode(nullptr, need2, d_ikeys, NT, d_ukeys, d_ucnt, d_nruns, st));
-    uint8_t *tmp;
-    need = std::max(need, need2);
-    KHIP(c, D.get(&tmp, need));
-    KHIP(c, clock.begin(&S.sort_ms));
-    size_t tb = need;
-    KHIP(c, rocprim::radix_sort_pairs(tmp, tb, Ts.keys, d_ikeys, Ts.vals, d_ivals, NT, 0, 2 * k, st));
-    tb = need;
-    KHIP(c, rocprim::run_length_encode(tmp, tb, d_ikeys, NT, d_ukeys, d_ucnt, d_nruns, st));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_nruns);
-    KHIP(c, clock.end());
-    rc = mp_read_scalars(c);
+    STAGE_HIP(c, clock.begin(&S.sort_ms));
+    STAGE_HIP(c, stage_sort_pairs(D, st, Ts.keys, d_ikeys, Ts.vals, d_ivals, NT, 2 * k));
+    STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
+      return rocprim::run_length_encode(tmp, bytes, d_ikeys, NT, d_ukeys, d_ucnt, d_nruns, st);
+    }));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_nruns);
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
     if (rc != MSGPU_OK) return rc;
-    n_keys = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]);
-    D.drop(tmp);
-    KHIP(c, hipMemsetAsync(d_ucnt + n_keys, 0, 4, st));
-    rc = mp_scan<uint32_t>(c, D, d_ucnt, d_ustart, n_keys + 1ull);
-    if (rc != MSGPU_OK) return rc;
+    n_keys = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+    D.drop_tmp();
+    STAGE_HIP(c, hipMemsetAsync(d_ucnt + n_keys, 0, 4, st));
+    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_ucnt, d_ustart, n_keys + 1ull));
+    STAGE_HIP(c, hipStreamSynchronize(st));
   }
   if (n_keys > (1u << 30)) { // (the table has 2^31 slots at most)
     snprintf(c->err, sizeof(c->err), "%u distinct target minimizers; the limit is 2^30", n_keys);
@@ -698,16 +676,16 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   }
   uint32_t sn = 64;
   while (sn < 2ull * n_keys) sn <<= 1;
-  KHIP(c, D.get(&d_slots, sn));
-  KHIP(c, hipMemsetAsync(d_slots, 0xff, sn * 4ull, st));
-  KHIP(c, clock.begin(&S.table_ms));
+  STAGE_HIP(c, D.get(&d_slots, sn));
+  STAGE_HIP(c, hipMemsetAsync(d_slots, 0xff, sn * 4ull, st));
+  STAGE_HIP(c, clock.begin(&S.table_ms));
   if (n_keys) {
-    hipLaunchKernelGGL(k_kf_table<uint64_t>, dim3(mp_grid(n_keys)), dim3(256), 0, st, d_ukeys, n_keys, d_slots, sn - 1);
-    hipLaunchKernelGGL(k_mp_occ, dim3(mp_grid(n_keys)), dim3(256), 0, st, d_ucnt, n_keys, prm.max_occ, mp_slot(c, MP_SC_DROPK),
+    hipLaunchKernelGGL(k_kf_table<uint64_t>, dim3(grid256(n_keys)), dim3(256), 0, st, d_ukeys, n_keys, d_slots, sn - 1);
+    hipLaunchKernelGGL(k_mp_occ, dim3(grid256(n_keys)), dim3(256), 0, st, d_ucnt, n_keys, prm.max_occ, mp_slot(c, MP_SC_DROPK),
                        mp_slot(c, MP_SC_DROPE));
   }
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
   S.n_keys          = n_keys;
   S.n_index_entries = NT;
   const MpIndex X{d_ukeys, d_ucnt, d_ustart, d_slots, sn - 1, prm.max_occ, d_ivals};
@@ -716,23 +694,22 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   const uint64_t NQ = Qs.n;
   uint32_t      *d_acnt;
   uint64_t      *d_aoff;
-  KHIP(c, D.get(&d_acnt, NQ + 1));
-  KHIP(c, D.get(&d_aoff, NQ + 1));
-  KHIP(c, hipMemsetAsync(d_acnt + NQ, 0, 4, st));
-  KHIP(c, clock.begin(&S.anchors_ms));
+  STAGE_HIP(c, D.get(&d_acnt, NQ + 1));
+  STAGE_HIP(c, D.get(&d_aoff, NQ + 1));
+  STAGE_HIP(c, hipMemsetAsync(d_acnt + NQ, 0, 4, st));
+  STAGE_HIP(c, clock.begin(&S.anchors_ms));
   if (NQ)
-    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(mp_grid(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, d_acnt,
+    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, d_acnt,
                        nullptr, nullptr, nullptr, 0);
-  KHIP(c, hipGetLastError());
-  rc = mp_scan<uint64_t>(c, D, d_acnt, d_aoff, NQ + 1);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_acnt, d_aoff, NQ + 1));
+  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_aoff + NQ);
+  STAGE_HIP(c, clock.end());
+  rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_aoff + NQ);
-  KHIP(c, clock.end());
-  rc = mp_read_scalars(c);
-  if (rc != MSGPU_OK) return rc;
-  S.n_keys_dropped    = c->h_scalars[MP_SC_DROPK];
-  S.n_entries_dropped = c->h_scalars[MP_SC_DROPE];
-  S.n_anchors         = c->h_scalars[MP_SC_TOTAL];
+  S.n_keys_dropped    = c->sc.h[MP_SC_DROPK];
+  S.n_entries_dropped = c->sc.h[MP_SC_DROPE];
+  S.n_anchors         = c->sc.h[MP_SC_TOTAL];
   if (S.n_anchors >= (1ull << 31)) {
     snprintf(c->err, sizeof(c->err), "%llu anchors; the limit is 2^31 - 1", static_cast<kf_ull>(S.n_anchors));
     return MSGPU_E_ARG;
@@ -740,7 +717,7 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   const uint32_t A = static_cast<uint32_t>(S.n_anchors);
   {
     size_t free_b = 0, total_b = 0;
-    KHIP(c, hipMemGetInfo(&free_b, &total_b));
+    STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
     const uint64_t bytes = A * (4 * 8ull + 2 * 8 + 2 * 4 + 1 + 28 + 5 * 4) + (exact ? 2 * Qf.recs.n_bases : 0);
     if (bytes > free_b) {
       snprintf(c->err, sizeof(c->err), "%u anchors need about %llu bytes for sorting and chaining (%llu of them for the oriented copies "
@@ -752,41 +729,34 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   uint64_t *d_g[2], *d_xy[2], *d_ug;
   uint32_t *d_gcnt, *d_gstart;
   for (int i = 0; i < 2; ++i) {
-    KHIP(c, D.get(&d_g[i], A));
-    KHIP(c, D.get(&d_xy[i], A));
+    STAGE_HIP(c, D.get(&d_g[i], A));
+    STAGE_HIP(c, D.get(&d_xy[i], A));
   }
-  KHIP(c, D.get(&d_ug, A));
-  KHIP(c, D.get(&d_gcnt, A + 1ull));
-  KHIP(c, D.get(&d_gstart, A + 1ull));
+  STAGE_HIP(c, D.get(&d_ug, A));
+  STAGE_HIP(c, D.get(&d_gcnt, A + 1ull));
+  STAGE_HIP(c, D.get(&d_gstart, A + 1ull));
   uint32_t G = 0;
   if (A) {
-    KHIP(c, clock.begin(&S.anchors_ms));
-    hipLaunchKernelGGL((k_mp_anchors<true>), dim3(mp_grid(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, nullptr,
+    STAGE_HIP(c, clock.begin(&S.anchors_ms));
+    hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, nullptr,
                        d_aoff, d_g[0], d_xy[0], A);
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
-    size_t need = 0, need2 = 0;
-    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, d_xy[0], d_xy[1], d_g[0], d_g[1], A, 0, 64, st));
-    KHIP(c, rocprim::run_length_encode(nullptr, need2, d_g[0], A, d_ug, d_gcnt, d_nruns, st));
-    need = std::max(need, need2);
-    uint8_t *tmp;
-    KHIP(c, D.get(&tmp, need));
-    KHIP(c, clock.begin(&S.group_ms));
-    size_t tb = need;
-    KHIP(c, rocprim::radix_sort_pairs(tmp, tb, d_xy[0], d_xy[1], d_g[0], d_g[1], A, 0, 64, st)); // by (x, y)
-    tb = need;
-    KHIP(c, rocprim::radix_sort_pairs(tmp, tb, d_g[1], d_g[0], d_xy[1], d_xy[0], A, 0, 64, st)); // then, stable, by group
-    tb = need;
-    KHIP(c, rocprim::run_length_encode(tmp, tb, d_g[0], A, d_ug, d_gcnt, d_nruns, st));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_nruns);
-    KHIP(c, clock.end());
-    rc = mp_read_scalars(c);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(&S.group_ms));
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_xy[0], d_xy[1], d_g[0], d_g[1], A)); // by (x, y)
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_g[1], d_g[0], d_xy[1], d_xy[0], A)); // then, stable, by group
+    STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
+      return rocprim::run_length_encode(tmp, bytes, d_g[0], A, d_ug, d_gcnt, d_nruns, st);
+    }));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_nruns);
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
     if (rc != MSGPU_OK) return rc;
-    G = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]);
-    D.drop(tmp);
-    KHIP(c, hipMemsetAsync(d_gcnt + G, 0, 4, st));
-    rc = mp_scan<uint32_t>(c, D, d_gcnt, d_gstart, G + 1ull);
-    if (rc != MSGPU_OK) return rc;
+    G = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+    D.drop_tmp();
+    STAGE_HIP(c, hipMemsetAsync(d_gcnt + G, 0, 4, st));
+    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_gcnt, d_gstart, G + 1ull));
+    STAGE_HIP(c, hipStreamSynchronize(st));
   }
   S.n_groups = G;
   D.drop(d_g[1]);
@@ -798,33 +768,34 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   // ---- rule 6's pre-filter, the size classes
   uint32_t *d_fs, *d_fl, *d_ps, *d_pl, *d_ls, *d_ll, *d_lk, *d_sb, *d_se;
   kf_ull   *d_hist;
-  for (uint32_t **p : {&d_fs, &d_fl, &d_ps, &d_pl}) KHIP(c, D.get(p, G + 1ull));
-  for (uint32_t **p : {&d_ls, &d_ll, &d_lk, &d_sb, &d_se}) KHIP(c, D.get(p, G));
-  KHIP(c, D.get(&d_hist, 32));
-  KHIP(c, hipMemsetAsync(d_hist, 0, 32 * 8, st));
-  KHIP(c, hipMemsetAsync(d_fs + G, 0, 4, st));
-  KHIP(c, hipMemsetAsync(d_fl + G, 0, 4, st));
-  KHIP(c, clock.begin(&S.group_ms));
+  for (uint32_t **p : {&d_fs, &d_fl, &d_ps, &d_pl}) STAGE_HIP(c, D.get(p, G + 1ull));
+  for (uint32_t **p : {&d_ls, &d_ll, &d_lk, &d_sb, &d_se}) STAGE_HIP(c, D.get(p, G));
+  STAGE_HIP(c, D.get(&d_hist, 32));
+  STAGE_HIP(c, hipMemsetAsync(d_hist, 0, 32 * 8, st));
+  STAGE_HIP(c, hipMemsetAsync(d_fs + G, 0, 4, st));
+  STAGE_HIP(c, hipMemsetAsync(d_fl + G, 0, 4, st));
+  STAGE_HIP(c, clock.begin(&S.group_ms));
   if (G)
-    hipLaunchKernelGGL(k_mp_classify, dim3(mp_grid(G)), dim3(256), 0, st, d_gcnt, G, k, prm.min_score, prm.min_count, d_fs, d_fl, d_hist,
+    hipLaunchKernelGGL(k_mp_classify, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, G, k, prm.min_score, prm.min_count, d_fs, d_fl, d_hist,
                        mp_slot(c, MP_SC_LARGEST));
-  KHIP(c, hipGetLastError());
-  rc = mp_scan<uint32_t>(c, D, d_fs, d_ps, G + 1ull);
-  if (rc == MSGPU_OK) rc = mp_scan<uint32_t>(c, D, d_fl, d_pl, G + 1ull);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_fs, d_ps, G + 1ull));
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_fl, d_pl, G + 1ull));
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_ps + G);
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL3, d_pl + G);
+  if (G) hipLaunchKernelGGL(k_mp_lists, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, d_gstart, G, d_fs, d_fl, d_ps, d_pl, d_ls, d_ll, d_lk, d_sb, d_se);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL2, d_ps + G);
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL3, d_pl + G);
-  if (G) hipLaunchKernelGGL(k_mp_lists, dim3(mp_grid(G)), dim3(256), 0, st, d_gcnt, d_gstart, G, d_fs, d_fl, d_ps, d_pl, d_ls, d_ll, d_lk, d_sb, d_se);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
-  rc = mp_read_scalars(c);
-  if (rc != MSGPU_OK) return rc;
-  const uint32_t n_small = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL2]), n_large = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL3]);
+  const uint32_t n_small = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]), n_large = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
   const uint32_t n_kept = n_small + n_large;
   S.n_groups_small = n_small;
   S.n_groups_large = n_large;
   S.n_groups_kept  = n_kept;
-  S.largest_group  = c->h_scalars[MP_SC_LARGEST];
+  S.largest_group  = c->sc.h[MP_SC_LARGEST];
   if (S.largest_group * static_cast<uint64_t>(k) >= (1ull << 31)) {
     snprintf(c->err, sizeof(c->err), "a group of %llu anchors: its scores do not fit 31 bits at k = %d", static_cast<kf_ull>(S.largest_group), k);
     return MSGPU_E_ARG;
@@ -836,75 +807,71 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   uint8_t  *d_used;
   MpRaw    *d_raw;
   uint32_t *d_emit, *d_coff;
-  KHIP(c, D.get(&d_f, A));
-  KHIP(c, D.get(&d_pred, A));
-  KHIP(c, D.get(&d_sk[0], A));
-  KHIP(c, D.get(&d_sk[1], A));
-  KHIP(c, D.get(&d_used, A));
-  KHIP(c, D.get(&d_raw, A));
-  KHIP(c, D.get(&d_emit, n_kept + 1ull));
-  KHIP(c, D.get(&d_coff, n_kept + 1ull));
-  KHIP(c, hipMemsetAsync(d_used, 0, A ? A : 1, st));
-  KHIP(c, hipMemsetAsync(d_emit, 0, (n_kept + 1ull) * 4, st));
+  STAGE_HIP(c, D.get(&d_f, A));
+  STAGE_HIP(c, D.get(&d_pred, A));
+  STAGE_HIP(c, D.get(&d_sk[0], A));
+  STAGE_HIP(c, D.get(&d_sk[1], A));
+  STAGE_HIP(c, D.get(&d_used, A));
+  STAGE_HIP(c, D.get(&d_raw, A));
+  STAGE_HIP(c, D.get(&d_emit, n_kept + 1ull));
+  STAGE_HIP(c, D.get(&d_coff, n_kept + 1ull));
+  STAGE_HIP(c, hipMemsetAsync(d_used, 0, A ? A : 1, st));
+  STAGE_HIP(c, hipMemsetAsync(d_emit, 0, (n_kept + 1ull) * 4, st));
   MpChainArgs ca{d_ll, n_large, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[0], k, prm.max_gap, prm.bandwidth};
-  KHIP(c, clock.begin(&S.chain_ms));
-  if (n_large) hipLaunchKernelGGL(k_mp_chain, dim3(mp_grid(n_large, 4)), dim3(256), 0, st, ca);
+  STAGE_HIP(c, clock.begin(&S.chain_ms));
+  if (n_large) hipLaunchKernelGGL(k_mp_chain, dim3(grid_of(n_large, 4)), dim3(256), 0, st, ca);
   ca.list   = d_ls;
   ca.n_list = n_small;
-  if (n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(mp_grid(n_small, 16)), dim3(256), 0, st, ca);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  if (n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(grid_of(n_small, 16)), dim3(256), 0, st, ca);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
 
   // ---- rule 6
   uint32_t C_n = 0;
   if (n_kept) {
-    size_t need = 0;
-    KHIP(c, rocprim::segmented_radix_sort_keys_desc(nullptr, need, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st));
-    uint8_t *tmp;
-    KHIP(c, D.get(&tmp, need));
-    KHIP(c, clock.begin(&S.backtrack_ms));
-    KHIP(c, rocprim::segmented_radix_sort_keys_desc(tmp, need, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st));
-    hipLaunchKernelGGL(k_mp_walk, dim3(mp_grid(n_kept, 64)), dim3(64), 0, st, d_lk, n_kept, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[1],
+    STAGE_HIP(c, clock.begin(&S.backtrack_ms));
+    STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
+      return rocprim::segmented_radix_sort_keys_desc(tmp, bytes, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st);
+    }));
+    hipLaunchKernelGGL(k_mp_walk, dim3(grid_of(n_kept, 64)), dim3(64), 0, st, d_lk, n_kept, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[1],
                        d_used, k, prm.min_score, prm.min_count, d_raw, d_emit, mp_slot(c, MP_SC_DROP_SCORE), mp_slot(c, MP_SC_DROP_COUNT),
                        mp_slot(c, MP_SC_CUT));
-    KHIP(c, hipGetLastError());
-    rc = mp_scan<uint32_t>(c, D, d_emit, d_coff, n_kept + 1ull);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_emit, d_coff, n_kept + 1ull));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_coff + n_kept);
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
     if (rc != MSGPU_OK) return rc;
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_coff + n_kept);
-    KHIP(c, clock.end());
-    rc = mp_read_scalars(c);
-    if (rc != MSGPU_OK) return rc;
-    C_n = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]);
-    D.drop(tmp);
+    C_n = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+    D.drop_tmp();
   }
   S.n_chains               = C_n;
-  S.n_chains_below_score   = c->h_scalars[MP_SC_DROP_SCORE];
-  S.n_chains_below_count   = c->h_scalars[MP_SC_DROP_COUNT];
-  S.n_chains_cut           = c->h_scalars[MP_SC_CUT];
+  S.n_chains_below_score   = c->sc.h[MP_SC_DROP_SCORE];
+  S.n_chains_below_count   = c->sc.h[MP_SC_DROP_COUNT];
+  S.n_chains_cut           = c->sc.h[MP_SC_CUT];
   msgpu_map_chain *d_chains;
   MpWhere         *d_where;
   uint32_t        *d_np, *d_poff;
-  KHIP(c, D.get(&d_chains, C_n));
-  KHIP(c, D.get(&d_where, C_n));
-  KHIP(c, D.get(&d_np, C_n + 1ull));
-  KHIP(c, D.get(&d_poff, C_n + 1ull));
-  KHIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
-  KHIP(c, clock.begin(&S.backtrack_ms));
+  STAGE_HIP(c, D.get(&d_chains, C_n));
+  STAGE_HIP(c, D.get(&d_where, C_n));
+  STAGE_HIP(c, D.get(&d_np, C_n + 1ull));
+  STAGE_HIP(c, D.get(&d_poff, C_n + 1ull));
+  STAGE_HIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
+  STAGE_HIP(c, clock.begin(&S.backtrack_ms));
   if (C_n)
-    hipLaunchKernelGGL(k_mp_table, dim3(mp_grid(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
+    hipLaunchKernelGGL(k_mp_table, dim3(grid256(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
                        Qf.d_len, k, d_chains, d_where, d_np, C_n);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
 
   // ---- rule 7 in exact mode
   if (exact && C_n) {
-    rc = mp_scan<uint32_t>(c, D, d_np, d_poff, C_n + 1ull);
+    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_np, d_poff, C_n + 1ull));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_poff + C_n);
+    STAGE_HIP(c, hipGetLastError());
+    rc = c->sc.read(c);
     if (rc != MSGPU_OK) return rc;
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->d_scalars, MP_SC_TOTAL, d_poff + C_n);
-    KHIP(c, hipGetLastError());
-    rc = mp_read_scalars(c);
-    if (rc != MSGPU_OK) return rc;
-    const uint32_t P = static_cast<uint32_t>(c->h_scalars[MP_SC_TOTAL]); // (fewer than the anchors)
+    const uint32_t P = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]); // (fewer than the anchors)
     S.n_pairs        = P;
     if (P) {
       // the queries as they are and reverse-complemented, one behind the other
@@ -932,35 +899,33 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
       uint8_t          *d_or;
       msgpu_align_pair *d_pairs;
       uint32_t         *d_dist, *d_nm;
-      KHIP(c, D.get(&d_or, 2 * NB + 16));
-      KHIP(c, D.get(&d_pairs, P));
-      KHIP(c, D.get(&d_dist, P));
-      KHIP(c, D.get(&d_nm, C_n));
-      KHIP(c, clock.begin(&S.pairs_ms));
+      STAGE_HIP(c, D.get(&d_or, 2 * NB + 16));
+      STAGE_HIP(c, D.get(&d_pairs, P));
+      STAGE_HIP(c, D.get(&d_dist, P));
+      STAGE_HIP(c, D.get(&d_nm, C_n));
+      STAGE_HIP(c, clock.begin(&S.pairs_ms));
       rc = msgpu_gather_run(c->seq, plan, d_or, 2 * NB + 16, st);
       if (rc != MSGPU_OK) {
         snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
         return rc;
       }
-      hipLaunchKernelGGL(k_mp_pairs, dim3(mp_grid(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, Tf.d_off, Qf.d_off,
+      hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, Tf.d_off, Qf.d_off,
                          NB, k, d_pairs, P);
-      KHIP(c, hipGetLastError());
-      KHIP(c, clock.end());
-      size_t need = 0;
-      KHIP(c, rocprim::segmented_reduce(nullptr, need, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st));
-      uint8_t *tmp;
-      KHIP(c, D.get(&tmp, need));
-      KHIP(c, clock.begin(&S.distance_ms));
+      STAGE_HIP(c, hipGetLastError());
+      STAGE_HIP(c, clock.end());
+      STAGE_HIP(c, clock.begin(&S.distance_ms));
       launch_edit_distance_pairs(st, Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist);
-      KHIP(c, hipGetLastError());
-      KHIP(c, rocprim::segmented_reduce(tmp, need, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st));
-      hipLaunchKernelGGL(k_mp_capped, dim3(mp_grid(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
-      hipLaunchKernelGGL(k_mp_exact, dim3(mp_grid(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
-      KHIP(c, hipGetLastError());
-      KHIP(c, clock.end());
-      rc = mp_read_scalars(c);
+      STAGE_HIP(c, hipGetLastError());
+      STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
+        return rocprim::segmented_reduce(tmp, bytes, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+      }));
+      hipLaunchKernelGGL(k_mp_capped, dim3(grid256(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
+      hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
+      STAGE_HIP(c, hipGetLastError());
+      STAGE_HIP(c, clock.end());
+      rc = c->sc.read(c);
       if (rc != MSGPU_OK) return rc;
-      S.n_pairs_capped = c->h_scalars[MP_SC_CAPPED];
+      S.n_pairs_capped = c->sc.h[MP_SC_CAPPED];
     }
   }
 
@@ -969,14 +934,14 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   try {
     res->chains.resize(C_n);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  KHIP(c, clock.begin(&S.copy_ms));
-  if (C_n) KHIP(c, hipMemcpyAsync(res->chains.data(), d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
-  KHIP(c, hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
-  KHIP(c, clock.end());
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, clock.begin(&S.copy_ms));
+  if (C_n) STAGE_HIP(c, hipMemcpyAsync(res->chains.data(), d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
   clock.collect();
   for (int i = 0; i < 32; ++i) S.group_hist[i < 15 ? i : 15] += hist[i];
-  const auto h0 = std::chrono::steady_clock::now();
+  const StageTimer formatting;
   try {
     unsigned nt = std::thread::hardware_concurrency();
     nt          = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
@@ -992,9 +957,9 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
     res->text.reserve(total);
     for (const std::string &p : part) res->text += p;
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  S.host_ms   = since(h0);
+  S.host_ms   = formatting.ms();
   S.bytes_out = res->text.size();
-  S.wall_ms   = since(w0);
+  S.wall_ms   = wall.ms();
   return MSGPU_OK;
 }
 
@@ -1007,46 +972,8 @@ void msgpu_map_default_params(msgpu_map_params *p) {
   *p = msgpu_map_params{15, 5, 200, 10000, 2000, 64, 100, 3, 0, 64, 0, 0};
 }
 
-int msgpu_map_create(int device, msgpu_mapctx **out) {
-  if (!out) return MSGPU_E_ARG;
-  *out     = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
-  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
-  auto *c = new (std::nothrow) msgpu_mapctx();
-  if (!c) return MSGPU_E_NOMEM;
-  c->device = device;
-  int rc    = msgpu_seq_create(device, &c->seq);
-  if (rc != MSGPU_OK) {
-    delete c;
-    return rc;
-  }
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&c->d_scalars), SC_COUNT * sizeof(uint64_t)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void **>(&c->h_scalars), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess) {
-    msgpu_map_destroy(c);
-    return MSGPU_E_HIP;
-  }
-  memset(c->h_scalars, 0, (SC_COUNT + 1) * sizeof(uint64_t));
-  void *dev = nullptr;
-  if (!getenv("MSGPU_SYNC_READBACK") && hipHostGetDevicePointer(&dev, c->h_scalars, 0) == hipSuccess)
-    c->h_scalars_dev = static_cast<uint64_t *>(dev);
-  *out = c;
-  return MSGPU_OK;
-}
-
-void msgpu_map_destroy(msgpu_mapctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->stream) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamDestroy(c->stream);
-  }
-  if (c->d_scalars) (void)hipFree(c->d_scalars);
-  if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-  msgpu_seq_destroy(c->seq);
-  delete c;
-}
+int  msgpu_map_create(int device, msgpu_mapctx **out) { return stage_create(device, out); }
+void msgpu_map_destroy(msgpu_mapctx *c) { stage_destroy(c); }
 
 const char *msgpu_map_last_error(const msgpu_mapctx *c) { return c ? c->err : "null context"; }
 
@@ -1069,18 +996,18 @@ int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *t
     snprintf(c->err, sizeof(c->err), p.ava ? "ava: the query file is the target file" : "no query file");
     return MSGPU_E_ARG;
   }
-  KHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   std::unique_ptr<msgpu_map_result> res;
   try {
     res.reset(new msgpu_map_result());
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  const uint64_t lost0 = c->lost;
+  const uint64_t lost0 = c->sc.lost;
   const int      rc = mp_stage(c, p, targets_path, queries_path, res.get());
   if (rc != MSGPU_OK) {
     (void)hipStreamSynchronize(c->stream);
     return rc;
   }
-  res->stats.n_lost_publications = c->lost - lost0;
+  res->stats.n_lost_publications = c->sc.lost - lost0;
   res->stats.params              = p;
   *out                           = res.release();
   return MSGPU_OK;

@@ -23,7 +23,6 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -32,6 +31,7 @@
 #include <vector>
 
 #include "msgpu.h"
+#include "msgpu_stage.h"
 
 namespace msgpu {
 
@@ -219,12 +219,9 @@ using namespace msgpu;
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-struct msgpu_scrubctx {
-  int           device = 0;
-  hipStream_t   stream = nullptr;
-  msgpu_seqctx *seq    = nullptr;
-  char          err[320] = {0};
-  uint64_t      err_line = 0;
+struct msgpu_scrubctx : msgpu::StageCtx {
+  SeqCtxHold seq;
+  int        open() { return msgpu_seq_create(device, &seq.p); }
 };
 
 struct msgpu_scrub_result {
@@ -236,78 +233,17 @@ struct msgpu_scrub_result {
 
 namespace {
 
-int sfail(msgpu_scrubctx *c, int code, const char *what, hipError_t e) {
-  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-  return code;
-}
-#define SHIP(c, expr)                                                                                                  \
-  do {                                                                                                                 \
-    hipError_t _e = (expr);                                                                                            \
-    if (_e != hipSuccess) return sfail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
-  } while (0)
-
-struct DevBuf { // device memory freed on every way out of msgpu_scrub_run
-  std::vector<void *> p;
-  ~DevBuf() {
-    for (void *x : p) (void)hipFree(x);
-  }
-  template <class T> hipError_t get(T **out, size_t count) {
-    void      *m = nullptr;
-    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(m);
-    *out = static_cast<T *>(m);
-    return e;
-  }
-};
-
-float ms_between(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  return ms;
-}
-
 bool ends_with(const char *s, const char *tail) {
   const size_t n = strlen(s), m = strlen(tail);
   return n >= m && memcmp(s + n - m, tail, m) == 0;
 }
 
-inline uint32_t grid256(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
-
 } // namespace
 
 extern "C" {
 
-int msgpu_scrub_create(int device, msgpu_scrubctx **out) {
-  if (!out) return MSGPU_E_ARG;
-  *out     = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
-  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
-  auto *c = new (std::nothrow) msgpu_scrubctx();
-  if (!c) return MSGPU_E_NOMEM;
-  c->device = device;
-  int rc    = msgpu_seq_create(device, &c->seq);
-  if (rc == MSGPU_OK && (hipSetDevice(device) != hipSuccess ||
-                         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess))
-    rc = MSGPU_E_HIP;
-  if (rc != MSGPU_OK) {
-    msgpu_scrub_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return MSGPU_OK;
-}
-
-void msgpu_scrub_destroy(msgpu_scrubctx *c) {
-  if (!c) return;
-  if (c->stream) {
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamDestroy(c->stream);
-  }
-  msgpu_seq_destroy(c->seq);
-  delete c;
-}
+int  msgpu_scrub_create(int device, msgpu_scrubctx **out) { return stage_create(device, out); }
+void msgpu_scrub_destroy(msgpu_scrubctx *c) { stage_destroy(c); }
 
 const char *msgpu_scrub_last_error(const msgpu_scrubctx *c) { return c ? c->err : "null context"; }
 uint64_t    msgpu_scrub_error_line(const msgpu_scrubctx *c) { return c ? c->err_line : 0; }
@@ -320,11 +256,8 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
   c->err_line = 0;
   msgpu_scrub_tables tb;
   if (msgpu_scrub_get_tables(s, &tb) != MSGPU_OK || !tb.n_nodes) return MSGPU_E_ARG;
-  const auto w0    = std::chrono::steady_clock::now();
-  auto       since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
-  SHIP(c, hipSetDevice(c->device));
+  const StageTimer wall;
+  STAGE_HIP(c, hipSetDevice(c->device));
   const uint32_t N = tb.n_nodes, NC = tb.n_chunks;
   const uint64_t H = tb.n_hits, A = tb.n_ava, M = 2 * A;
   std::unique_ptr<msgpu_scrub_result> res;
@@ -338,38 +271,29 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
 
   // ---- the reads: bases to the nanopore store; every node needs a record (the first of its name)
   const int      is_fastq = (ends_with(reads_path, "fa") || ends_with(reads_path, "fasta")) ? 0 : 1;
-  msgpu_seqfile *f        = nullptr;
-  int            rc       = msgpu_seq_parse_upload(c->seq, 0, reads_path, is_fastq, &f);
+  SeqFileHold    f;
+  int            rc       = msgpu_seq_parse_upload(c->seq, 0, reads_path, is_fastq, &f.f);
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "reads %s: %s", reads_path, msgpu_seq_last_error(c->seq));
     return rc;
   }
-  struct FreeSeq {
-    msgpu_seqfile *f;
-    ~FreeSeq() { msgpu_seq_free(f); }
-  } free_seq{f};
-  std::vector<uint32_t> rec_ids, rec_of(N, SC_NONE);
+  std::vector<uint32_t> rec_ids, rec_of;
+  uint32_t              x = STAGE_NONE;
   try {
-    const uint32_t nr = msgpu_seq_count(f);
-    rec_ids.resize(nr);
-    for (uint32_t i = 0; i < nr; ++i) {
-      rec_ids[i] = msgpu_scrub_node_id(s, msgpu_seq_name(f, i));
-      if (rec_ids[i] != SC_NONE && rec_of[rec_ids[i]] == SC_NONE) rec_of[rec_ids[i]] = i;
-    }
+    x = stage_first_records(f, [&](const char *name) { return msgpu_scrub_node_id(s, name); }, N, nullptr, N, rec_ids, rec_of);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  for (uint32_t x = 0; x < N; ++x)
-    if (rec_of[x] == SC_NONE) { // nodes are numbered by their first line: the first missing one has the smallest line
-      c->err_line = static_cast<uint64_t>(tb.node_line[x]) + 1;
-      snprintf(c->err, sizeof(c->err), "read %.200s (anchor PAF line %llu) is not in the reads file", msgpu_scrub_node_name(s, x),
-               static_cast<unsigned long long>(c->err_line));
-      return MSGPU_E_IDS;
-    }
+  if (x != STAGE_NONE) { // nodes are numbered by their first line: the first missing one has the smallest line
+    c->err_line = static_cast<uint64_t>(tb.node_line[x]) + 1;
+    snprintf(c->err, sizeof(c->err), "read %.200s (anchor PAF line %llu) is not in the reads file", msgpu_scrub_node_name(s, x),
+             static_cast<unsigned long long>(c->err_line));
+    return MSGPU_E_IDS;
+  }
   rc = msgpu_seq_set_ids(c->seq, 0, f, rec_ids.data(), N);
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "sequence store: %s", msgpu_seq_last_error(c->seq));
     return rc;
   }
-  S.load_ms = since(w0);
+  S.load_ms = wall.ms();
 
   // ---- host tables of the device steps: the pair space, the anchor ranges by node
   std::vector<uint64_t> pair_off, anc_off;
@@ -401,48 +325,13 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
   }
 
   hipStream_t st = c->stream;
-  hipEvent_t  ev[10] = {};
-  struct FreeEv {
-    hipEvent_t *e;
-    ~FreeEv() {
-      for (int i = 0; i < 10; ++i)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  } free_ev{ev};
-  for (auto &e : ev) SHIP(c, hipEventCreate(&e));
-  DevBuf D;
-  // one temporary buffer for every rocprim call of the run, grown when a call needs more
-  void  *d_tmp     = nullptr;
-  size_t tmp_bytes = 0;
-  auto   tmp_room  = [&](size_t need) -> hipError_t {
-    if (need <= tmp_bytes) return hipSuccess;
-    uint8_t   *t = nullptr;
-    hipError_t e = D.get(&t, need);
-    if (e == hipSuccess) {
-      d_tmp     = t;
-      tmp_bytes = need;
-    }
-    return e;
-  };
-  auto sort_pairs = [&](uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, uint64_t n) -> hipError_t {
-    size_t     need = 0;
-    hipError_t e    = rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, static_cast<unsigned int>(n), 0, 64, st);
-    if (e == hipSuccess) e = tmp_room(need);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(d_tmp, need, kin, kout, vin, vout, static_cast<unsigned int>(n), 0, 64, st);
-    return e;
-  };
-  auto scan = [&](uint32_t *in, uint32_t *outp, uint64_t n) -> hipError_t {
-    size_t     need = 0;
-    hipError_t e    = rocprim::exclusive_scan(nullptr, need, in, outp, 0u, static_cast<size_t>(n), rocprim::plus<uint32_t>(), st);
-    if (e == hipSuccess) e = tmp_room(need);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(d_tmp, need, in, outp, 0u, static_cast<size_t>(n), rocprim::plus<uint32_t>(), st);
-    return e;
-  };
+  StageClock  clock(st);
+  DevArena    D;
 
   // ---- read graph
   uint64_t *d_row_off;
-  SHIP(c, D.get(&d_row_off, static_cast<size_t>(N) + 1));
-  SHIP(c, hipEventRecord(ev[0], st));
+  STAGE_HIP(c, D.get(&d_row_off, static_cast<size_t>(N) + 1));
+  STAGE_HIP(c, clock.begin(&S.graph_ms));
   uint64_t E2 = 0; // directed entries of the graph = 2 x edges
   try {
     res->row_off.assign(static_cast<size_t>(N) + 1, 0);
@@ -450,52 +339,52 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
   if (P) {
     uint64_t *d_pair_off, *d_k0, *d_k1;
     uint32_t *d_cfirst, *d_hnode, *d_o0, *d_o1, *d_flag, *d_pos;
-    SHIP(c, D.get(&d_pair_off, pair_off.size()));
-    SHIP(c, D.get(&d_cfirst, NC));
-    SHIP(c, D.get(&d_hnode, H));
-    SHIP(c, D.get(&d_k0, P));
-    SHIP(c, D.get(&d_k1, P));
-    SHIP(c, D.get(&d_o0, P));
-    SHIP(c, D.get(&d_o1, P));
-    SHIP(c, D.get(&d_flag, P));
-    SHIP(c, D.get(&d_pos, P));
-    SHIP(c, hipMemcpyAsync(d_pair_off, pair_off.data(), pair_off.size() * 8, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_cfirst, tb.chunk_first, NC * 4ull, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_hnode, tb.hit_node, H * 4ull, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, D.get(&d_pair_off, pair_off.size()));
+    STAGE_HIP(c, D.get(&d_cfirst, NC));
+    STAGE_HIP(c, D.get(&d_hnode, H));
+    STAGE_HIP(c, D.get(&d_k0, P));
+    STAGE_HIP(c, D.get(&d_k1, P));
+    STAGE_HIP(c, D.get(&d_o0, P));
+    STAGE_HIP(c, D.get(&d_o1, P));
+    STAGE_HIP(c, D.get(&d_flag, P));
+    STAGE_HIP(c, D.get(&d_pos, P));
+    STAGE_HIP(c, hipMemcpyAsync(d_pair_off, pair_off.data(), pair_off.size() * 8, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_cfirst, tb.chunk_first, NC * 4ull, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_hnode, tb.hit_node, H * 4ull, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_scrub_pairs, dim3(grid256(P)), dim3(256), 0, st, d_pair_off, NC, d_cfirst, d_hnode, d_k0, d_o0);
-    SHIP(c, hipGetLastError());
-    SHIP(c, sort_pairs(d_k0, d_k1, d_o0, d_o1, P)); // stable: of the pairs of one edge the earliest comes first
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_k0, d_k1, d_o0, d_o1, P)); // stable: of the pairs of one edge the earliest comes first
     hipLaunchKernelGGL(k_scrub_first, dim3(grid256(P)), dim3(256), 0, st, d_k1, P, d_flag);
-    SHIP(c, hipGetLastError());
-    SHIP(c, scan(d_flag, d_pos, P));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_scan(D, st, d_flag, d_pos, P));
     uint32_t last[2] = {0, 0};
-    SHIP(c, hipMemcpyAsync(&last[0], d_pos + (P - 1), 4, hipMemcpyDeviceToHost, st));
-    SHIP(c, hipMemcpyAsync(&last[1], d_flag + (P - 1), 4, hipMemcpyDeviceToHost, st));
-    SHIP(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipMemcpyAsync(&last[0], d_pos + (P - 1), 4, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(&last[1], d_flag + (P - 1), 4, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     E2 = 2ull * (static_cast<uint64_t>(last[0]) + last[1]);
     uint64_t *d_dk0, *d_dk1;
     uint32_t *d_dv0, *d_dv1;
-    SHIP(c, D.get(&d_dk0, E2));
-    SHIP(c, D.get(&d_dk1, E2));
-    SHIP(c, D.get(&d_dv0, E2));
-    SHIP(c, D.get(&d_dv1, E2));
+    STAGE_HIP(c, D.get(&d_dk0, E2));
+    STAGE_HIP(c, D.get(&d_dk1, E2));
+    STAGE_HIP(c, D.get(&d_dv0, E2));
+    STAGE_HIP(c, D.get(&d_dv1, E2));
     hipLaunchKernelGGL(k_scrub_directed, dim3(grid256(P)), dim3(256), 0, st, d_k1, d_o1, d_flag, d_pos, P, d_dk0, d_dv0);
-    SHIP(c, hipGetLastError());
-    SHIP(c, sort_pairs(d_dk0, d_dk1, d_dv0, d_dv1, E2));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_dk0, d_dk1, d_dv0, d_dv1, E2));
     hipLaunchKernelGGL(k_scrub_rows, dim3(grid256(static_cast<uint64_t>(N) + 1)), dim3(256), 0, st, d_dk1, E2, N, d_row_off);
-    SHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     try {
       res->adj.resize(E2);
     } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-    SHIP(c, hipMemcpyAsync(res->row_off.data(), d_row_off, (static_cast<size_t>(N) + 1) * 8, hipMemcpyDeviceToHost, st));
-    SHIP(c, hipMemcpyAsync(res->adj.data(), d_dv1, E2 * 4, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(res->row_off.data(), d_row_off, (static_cast<size_t>(N) + 1) * 8, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(res->adj.data(), d_dv1, E2 * 4, hipMemcpyDeviceToHost, st));
   }
-  SHIP(c, hipEventRecord(ev[1], st));
-  SHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
   S.n_edges = E2 / 2;
 
   // ---- batches (host)
-  const auto               b0 = std::chrono::steady_clock::now();
+  const StageTimer         batching;
   msgpu_scrub_plan        *plan_raw = nullptr;
   msgpu_scrub_plan_tables  pt{};
   {
@@ -524,121 +413,117 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
   const uint64_t NS  = pt.subset_off[NB];
   S.n_batches        = NB;
   S.n_subset_total   = NS;
-  S.batch_ms         = since(b0);
+  S.batch_ms         = batching.ms();
 
   // ---- fold
   uint64_t *d_ent_off, *d_ek = nullptr;
   int32_t  *d_st_s = nullptr, *d_st_e = nullptr;
   uint32_t *d_st_d = nullptr;
-  SHIP(c, D.get(&d_ent_off, static_cast<size_t>(N) + 1));
-  SHIP(c, hipEventRecord(ev[2], st));
+  STAGE_HIP(c, D.get(&d_ent_off, static_cast<size_t>(N) + 1));
+  STAGE_HIP(c, clock.begin(&S.fold_ms));
   if (M) {
     uint64_t *d_ek0;
     uint32_t *d_a, *d_b, *d_strand, *d_ei0, *d_ei, *d_stamp, *d_subset;
     int32_t  *d_sa, *d_ea, *d_sb, *d_eb;
-    SHIP(c, D.get(&d_a, A));
-    SHIP(c, D.get(&d_b, A));
-    SHIP(c, D.get(&d_strand, A));
-    SHIP(c, D.get(&d_sa, A));
-    SHIP(c, D.get(&d_ea, A));
-    SHIP(c, D.get(&d_sb, A));
-    SHIP(c, D.get(&d_eb, A));
-    SHIP(c, D.get(&d_ek0, M));
-    SHIP(c, D.get(&d_ek, M));
-    SHIP(c, D.get(&d_ei0, M));
-    SHIP(c, D.get(&d_ei, M));
-    SHIP(c, D.get(&d_st_s, M));
-    SHIP(c, D.get(&d_st_e, M));
-    SHIP(c, D.get(&d_st_d, M));
-    SHIP(c, D.get(&d_stamp, N));
-    SHIP(c, D.get(&d_subset, NS));
-    SHIP(c, hipMemcpyAsync(d_a, tb.ava_a, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_b, tb.ava_b, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_strand, tb.ava_strand, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_sa, tb.ava_sa, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_ea, tb.ava_ea, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_sb, tb.ava_sb, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_eb, tb.ava_eb, A * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemcpyAsync(d_subset, pt.subset, NS * 4, hipMemcpyHostToDevice, st));
-    SHIP(c, hipMemsetAsync(d_stamp, 0xff, N * 4ull, st));
-    SHIP(c, hipMemsetAsync(d_st_d, 0xff, M * 4, st));
-    SHIP(c, hipMemsetAsync(d_st_s, 0, M * 4, st));
-    SHIP(c, hipMemsetAsync(d_st_e, 0, M * 4, st));
+    STAGE_HIP(c, D.get(&d_a, A));
+    STAGE_HIP(c, D.get(&d_b, A));
+    STAGE_HIP(c, D.get(&d_strand, A));
+    STAGE_HIP(c, D.get(&d_sa, A));
+    STAGE_HIP(c, D.get(&d_ea, A));
+    STAGE_HIP(c, D.get(&d_sb, A));
+    STAGE_HIP(c, D.get(&d_eb, A));
+    STAGE_HIP(c, D.get(&d_ek0, M));
+    STAGE_HIP(c, D.get(&d_ek, M));
+    STAGE_HIP(c, D.get(&d_ei0, M));
+    STAGE_HIP(c, D.get(&d_ei, M));
+    STAGE_HIP(c, D.get(&d_st_s, M));
+    STAGE_HIP(c, D.get(&d_st_e, M));
+    STAGE_HIP(c, D.get(&d_st_d, M));
+    STAGE_HIP(c, D.get(&d_stamp, N));
+    STAGE_HIP(c, D.get(&d_subset, NS));
+    STAGE_HIP(c, hipMemcpyAsync(d_a, tb.ava_a, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_b, tb.ava_b, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_strand, tb.ava_strand, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_sa, tb.ava_sa, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_ea, tb.ava_ea, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_sb, tb.ava_sb, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_eb, tb.ava_eb, A * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_subset, pt.subset, NS * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemsetAsync(d_stamp, 0xff, N * 4ull, st));
+    STAGE_HIP(c, hipMemsetAsync(d_st_d, 0xff, M * 4, st));
+    STAGE_HIP(c, hipMemsetAsync(d_st_s, 0, M * 4, st));
+    STAGE_HIP(c, hipMemsetAsync(d_st_e, 0, M * 4, st));
     hipLaunchKernelGGL(k_scrub_entries, dim3(grid256(M)), dim3(256), 0, st, d_a, d_b, A, d_ek0, d_ei0);
-    SHIP(c, hipGetLastError());
-    SHIP(c, sort_pairs(d_ek0, d_ek, d_ei0, d_ei, M)); // stable: a group's lines stay in file order
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_ek0, d_ek, d_ei0, d_ei, M)); // stable: a group's lines stay in file order
     hipLaunchKernelGGL(k_scrub_rows, dim3(grid256(static_cast<uint64_t>(N) + 1)), dim3(256), 0, st, d_ek, M, N, d_ent_off);
-    SHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     for (uint32_t b = 0; b < NB; ++b) {
       const uint32_t  n   = static_cast<uint32_t>(pt.subset_off[b + 1] - pt.subset_off[b]);
       const uint32_t *sub = d_subset + pt.subset_off[b];
       hipLaunchKernelGGL(k_scrub_stamp, dim3(grid256(n)), dim3(256), 0, st, sub, n, b, d_stamp);
       hipLaunchKernelGGL(k_scrub_fold, dim3((n + 3) / 4), dim3(256), 0, st, sub, n, b, d_stamp, d_ent_off, d_ek, d_ei, d_sa,
                          d_ea, d_sb, d_eb, d_strand, d_st_s, d_st_e, d_st_d);
-      SHIP(c, hipGetLastError());
+      STAGE_HIP(c, hipGetLastError());
     }
   } else {
-    SHIP(c, hipMemsetAsync(d_ent_off, 0, (static_cast<size_t>(N) + 1) * 8, st));
+    STAGE_HIP(c, hipMemsetAsync(d_ent_off, 0, (static_cast<size_t>(N) + 1) * 8, st));
   }
-  SHIP(c, hipEventRecord(ev[3], st));
+  STAGE_HIP(c, clock.end());
 
   // ---- union over all nodes
   uint64_t *d_anc_off, *d_slot_off, *d_iv0, *d_iv1;
   int32_t  *d_anc_s, *d_anc_e;
   uint32_t *d_cnt, *d_rec_off;
-  SHIP(c, D.get(&d_anc_off, static_cast<size_t>(N) + 1));
-  SHIP(c, D.get(&d_slot_off, static_cast<size_t>(N) + 1));
-  SHIP(c, D.get(&d_anc_s, H));
-  SHIP(c, D.get(&d_anc_e, H));
-  SHIP(c, D.get(&d_iv0, T));
-  SHIP(c, D.get(&d_iv1, T));
-  SHIP(c, D.get(&d_cnt, N));
-  SHIP(c, D.get(&d_rec_off, N));
-  SHIP(c, hipEventRecord(ev[4], st));
-  SHIP(c, hipMemcpyAsync(d_anc_off, anc_off.data(), anc_off.size() * 8, hipMemcpyHostToDevice, st));
-  SHIP(c, hipMemcpyAsync(d_anc_s, anc_s.data(), H * 4, hipMemcpyHostToDevice, st));
-  SHIP(c, hipMemcpyAsync(d_anc_e, anc_e.data(), H * 4, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, D.get(&d_anc_off, static_cast<size_t>(N) + 1));
+  STAGE_HIP(c, D.get(&d_slot_off, static_cast<size_t>(N) + 1));
+  STAGE_HIP(c, D.get(&d_anc_s, H));
+  STAGE_HIP(c, D.get(&d_anc_e, H));
+  STAGE_HIP(c, D.get(&d_iv0, T));
+  STAGE_HIP(c, D.get(&d_iv1, T));
+  STAGE_HIP(c, D.get(&d_cnt, N));
+  STAGE_HIP(c, D.get(&d_rec_off, N));
+  STAGE_HIP(c, clock.begin(&S.union_ms));
+  STAGE_HIP(c, hipMemcpyAsync(d_anc_off, anc_off.data(), anc_off.size() * 8, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_anc_s, anc_s.data(), H * 4, hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_anc_e, anc_e.data(), H * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_scrub_slot_off, dim3(grid256(static_cast<uint64_t>(N) + 1)), dim3(256), 0, st, d_anc_off, d_ent_off, N,
                      d_slot_off);
   hipLaunchKernelGGL(k_scrub_intervals, dim3(grid256(T)), dim3(256), 0, st, d_slot_off, d_anc_off, d_ent_off, N, d_anc_s,
                      d_anc_e, d_ek, d_st_s, d_st_e, d_st_d, d_iv0);
-  SHIP(c, hipGetLastError());
-  {
-    size_t need = 0;
-    SHIP(c, rocprim::segmented_radix_sort_keys(nullptr, need, d_iv0, d_iv1, static_cast<unsigned int>(T), N, d_slot_off,
-                                               d_slot_off + 1, 0, 64, st));
-    SHIP(c, tmp_room(need));
-    SHIP(c, rocprim::segmented_radix_sort_keys(d_tmp, need, d_iv0, d_iv1, static_cast<unsigned int>(T), N, d_slot_off,
-                                               d_slot_off + 1, 0, 64, st));
-  }
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
+    return rocprim::segmented_radix_sort_keys(tmp, bytes, d_iv0, d_iv1, static_cast<unsigned int>(T), N, d_slot_off, d_slot_off + 1, 0, 64,
+                                              st);
+  }));
   hipLaunchKernelGGL(k_scrub_merge<false>, dim3(grid256(N)), dim3(256), 0, st, d_slot_off, N, d_iv1, d_cnt, nullptr, nullptr);
-  SHIP(c, hipGetLastError());
-  SHIP(c, scan(d_cnt, d_rec_off, N));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan(D, st, d_cnt, d_rec_off, N));
   std::vector<uint32_t> rec_off, cnt;
   std::vector<int2>     ranges;
   try {
     rec_off.resize(N);
     cnt.resize(N);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  SHIP(c, hipMemcpyAsync(rec_off.data(), d_rec_off, N * 4ull, hipMemcpyDeviceToHost, st));
-  SHIP(c, hipMemcpyAsync(cnt.data(), d_cnt, N * 4ull, hipMemcpyDeviceToHost, st));
-  SHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, hipMemcpyAsync(rec_off.data(), d_rec_off, N * 4ull, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(cnt.data(), d_cnt, N * 4ull, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
   const uint64_t NR = static_cast<uint64_t>(rec_off[N - 1]) + cnt[N - 1];
   S.n_intervals     = T;
   int2 *d_ranges;
-  SHIP(c, D.get(&d_ranges, NR));
+  STAGE_HIP(c, D.get(&d_ranges, NR));
   hipLaunchKernelGGL(k_scrub_merge<true>, dim3(grid256(N)), dim3(256), 0, st, d_slot_off, N, d_iv1, nullptr, d_rec_off,
                      d_ranges);
-  SHIP(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   try {
     ranges.resize(NR);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (NR) SHIP(c, hipMemcpyAsync(ranges.data(), d_ranges, NR * sizeof(int2), hipMemcpyDeviceToHost, st));
-  SHIP(c, hipEventRecord(ev[5], st));
-  SHIP(c, hipStreamSynchronize(st));
+  if (NR) STAGE_HIP(c, hipMemcpyAsync(ranges.data(), d_ranges, NR * sizeof(int2), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- output plan: batch after batch, the centre nodes by id, a node's covered ranges in order
-  const auto                      p0 = std::chrono::steady_clock::now();
+  const StageTimer                planning;
   std::vector<msgpu_copy>         pieces;
   std::vector<msgpu_fasta_record> recs;
   std::string                     hdr;
@@ -686,36 +571,32 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
     msgpu_gather_plan *p;
     ~FreePlan() { msgpu_gather_plan_free(p); }
   } free_plan{plan};
-  S.plan_ms = since(p0);
+  S.plan_ms = planning.ms();
   uint8_t *d_raw, *d_text;
-  SHIP(c, D.get(&d_raw, raw + 16));
-  SHIP(c, D.get(&d_text, text + 16));
-  SHIP(c, hipEventRecord(ev[6], st));
+  STAGE_HIP(c, D.get(&d_raw, raw + 16));
+  STAGE_HIP(c, D.get(&d_text, text + 16));
+  STAGE_HIP(c, clock.begin(&S.gather_ms));
   rc = msgpu_gather_run(c->seq, plan, d_raw, raw + 16, st);
   if (rc == MSGPU_OK) {
-    SHIP(c, hipEventRecord(ev[7], st));
+    STAGE_HIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(&S.format_ms)); // (from the same point of the stream)
     rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
   }
   if (rc != MSGPU_OK) {
     snprintf(c->err, sizeof(c->err), "gather / format: %s", msgpu_seq_last_error(c->seq));
     return rc;
   }
-  SHIP(c, hipEventRecord(ev[8], st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, clock.begin(&S.copy_ms)); // (from the same point of the stream)
   try {
     res->text.resize(text);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (text) SHIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
-  SHIP(c, hipEventRecord(ev[9], st));
-  SHIP(c, hipStreamSynchronize(st));
-  auto el = [&](int a, int b) { return ms_between(ev[a], ev[b]); };
-  S.graph_ms  = el(0, 1);
-  S.fold_ms   = el(2, 3);
-  S.union_ms  = el(4, 5);
-  S.gather_ms = el(6, 7);
-  S.format_ms = el(7, 8);
-  S.copy_ms   = el(8, 9);
-  S.wall_ms   = since(w0);
-  *out        = res.release();
+  if (text) STAGE_HIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  clock.collect();
+  S.wall_ms = wall.ms();
+  *out      = res.release();
   return MSGPU_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "host_pool.h"
 #include "msgpu.h"
 #include "msgpu_internal.h"
+#include "msgpu_stage.h"
 
 namespace msgpu {
 
@@ -374,18 +375,6 @@ struct msgpu_gather_plan {
   uint64_t n_chunks = 0, n_super = 0, out_bytes = 0, bases = 0;
 };
 
-namespace {
-int sfail(msgpu_seqctx *c, int code, const char *what, hipError_t e) {
-  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-  return code;
-}
-#define SHIP(c, expr)                                                                                                  \
-  do {                                                                                                                 \
-    hipError_t _e = (expr);                                                                                            \
-    if (_e != hipSuccess) return sfail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e);        \
-  } while (0)
-} // namespace
-
 extern "C" {
 
 int msgpu_seq_create(int device, msgpu_seqctx **out) {
@@ -455,18 +444,18 @@ int msgpu_seq_upload_bases(msgpu_seqctx *c, int kind, const msgpu_seqfile *f) {
   s.len.clear();
   s.n_bases = total;
   if (c->device < 0) return MSGPU_OK; // layout-only context: offsets and lengths are all it needs
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   s.drop_packed();
   if (s.d_buf) {
-    SHIP(c, hipFree(s.d_buf));
+    STAGE_HIP(c, hipFree(s.d_buf));
     s.d_buf = nullptr;
   }
-  SHIP(c, hipMalloc(&s.d_buf, total + 2 * SEQ_PAD));
-  SHIP(c, hipMemsetAsync(s.d_buf, 0, SEQ_PAD, s.stream));
-  SHIP(c, hipMemsetAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD + total, 0, SEQ_PAD, s.stream));
+  STAGE_HIP(c, hipMalloc(&s.d_buf, total + 2 * SEQ_PAD));
+  STAGE_HIP(c, hipMemsetAsync(s.d_buf, 0, SEQ_PAD, s.stream));
+  STAGE_HIP(c, hipMemsetAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD + total, 0, SEQ_PAD, s.stream));
   if (total)
-    SHIP(c, hipMemcpyAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD, first, total, hipMemcpyHostToDevice, s.stream));
-  SHIP(c, hipStreamSynchronize(s.stream));
+    STAGE_HIP(c, hipMemcpyAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD, first, total, hipMemcpyHostToDevice, s.stream));
+  STAGE_HIP(c, hipStreamSynchronize(s.stream));
   return MSGPU_OK;
 }
 
@@ -582,7 +571,7 @@ struct DeviceDestination final : msgpu::SeqDestination {
     hipError_t e = hipMemsetAsync(d_bases + extent, 0, SEQ_PAD, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) fail(e);
-    if (err.load() != hipSuccess) return sfail(c, MSGPU_E_HIP, "msgpu_seq_parse_upload", static_cast<hipError_t>(err.load()));
+    if (err.load() != hipSuccess) return stage_fail(c, MSGPU_E_HIP, "msgpu_seq_parse_upload", static_cast<hipError_t>(err.load()));
     s.n_bases = extent;
     return MSGPU_OK;
   }
@@ -639,7 +628,7 @@ int msgpu_seq_upload_device(msgpu_seqctx *c, int kind, const void *d_bases, uint
                             const uint64_t *len, uint32_t n_ids) {
   if (!c || kind < 0 || kind > 1 || (n_bases && !d_bases) || (n_ids && (!off || !len))) return MSGPU_E_ARG;
   if (c->device < 0) return MSGPU_E_NODEVICE;
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   SeqStore &s = c->st[kind];
   for (uint32_t i = 0; i < n_ids; ++i)
     if (off[i] != ~0ull && off[i] + len[i] > n_bases) return MSGPU_E_ARG;
@@ -647,16 +636,16 @@ int msgpu_seq_upload_device(msgpu_seqctx *c, int kind, const void *d_bases, uint
   s.len.assign(len, len + n_ids);
   s.drop_packed();
   if (s.d_buf) {
-    SHIP(c, hipFree(s.d_buf));
+    STAGE_HIP(c, hipFree(s.d_buf));
     s.d_buf = nullptr;
   }
   s.n_bases = n_bases;
-  SHIP(c, hipMalloc(&s.d_buf, n_bases + 2 * SEQ_PAD));
-  SHIP(c, hipMemsetAsync(s.d_buf, 0, SEQ_PAD, c->stream));
-  SHIP(c, hipMemsetAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD + n_bases, 0, SEQ_PAD, c->stream));
+  STAGE_HIP(c, hipMalloc(&s.d_buf, n_bases + 2 * SEQ_PAD));
+  STAGE_HIP(c, hipMemsetAsync(s.d_buf, 0, SEQ_PAD, c->stream));
+  STAGE_HIP(c, hipMemsetAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD + n_bases, 0, SEQ_PAD, c->stream));
   if (n_bases)
-    SHIP(c, hipMemcpyAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD, d_bases, n_bases, hipMemcpyDeviceToDevice, c->stream));
-  SHIP(c, hipStreamSynchronize(c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(static_cast<uint8_t *>(s.d_buf) + SEQ_PAD, d_bases, n_bases, hipMemcpyDeviceToDevice, c->stream));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
   return MSGPU_OK;
 }
 
@@ -678,7 +667,7 @@ int msgpu_gather_plan_create(msgpu_seqctx *c, const msgpu_copy *pieces, size_t n
   if (!c || !out || (n && !pieces) || n >= 0xfffffff0ull) return MSGPU_E_ARG;
   *out = nullptr;
   if (c->device < 0) return MSGPU_E_NODEVICE;
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   // the work partition: every piece is cut into 1-KiB chunks (cmap) and 4-KiB super-chunks (smap) of its output, 2 words
   // each.  A deep assembly has millions of pieces: counted and filled in stretches on host threads (a stretch's first
   // chunk number is the prefix over the stretches before it).
@@ -771,7 +760,7 @@ int msgpu_gather_plan_create(msgpu_seqctx *c, const msgpu_copy *pieces, size_t n
     if (pl->d_chunk_map) (void)hipFree(pl->d_chunk_map);
     if (pl->d_super_map) (void)hipFree(pl->d_super_map);
     delete pl;
-    return sfail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "gather plan", e);
+    return stage_fail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "gather plan", e);
   }
   *out = pl;
   return MSGPU_OK;
@@ -792,7 +781,7 @@ int msgpu_gather_run(msgpu_seqctx *c, const msgpu_gather_plan *pl, void *d_out, 
   if (!c || !pl || (!d_out && pl->out_bytes)) return MSGPU_E_ARG;
   if (out_capacity < pl->out_bytes) return MSGPU_E_ARG;
   if (c->device < 0) return MSGPU_E_NODEVICE;
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   if (!pl->n_chunks) return MSGPU_OK;
   hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
   if ((c->st[0].packed && c->st[1].d_buf) || (c->st[1].packed && c->st[0].d_buf)) {
@@ -811,7 +800,7 @@ int msgpu_gather_run(msgpu_seqctx *c, const msgpu_gather_plan *pl, void *d_out, 
                          static_cast<const uint64_t *>(c->st[0].d_exc_pos), static_cast<const uint8_t *>(c->st[0].d_exc_byte),
                          c->st[0].n_exc, static_cast<const uint64_t *>(c->st[1].d_exc_pos),
                          static_cast<const uint8_t *>(c->st[1].d_exc_byte), c->st[1].n_exc, static_cast<uint8_t *>(d_out));
-    SHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     return MSGPU_OK;
   }
   const uint8_t *b0 = c->st[0].d_buf ? static_cast<const uint8_t *>(c->st[0].d_buf) + SEQ_PAD : nullptr;
@@ -819,7 +808,7 @@ int msgpu_gather_run(msgpu_seqctx *c, const msgpu_gather_plan *pl, void *d_out, 
   hipLaunchKernelGGL(k_gather, dim3(static_cast<uint32_t>((pl->n_chunks + 4 * GUNROLL - 1) / (4 * GUNROLL))), dim3(256), 0, st,
                      static_cast<const msgpu_copy *>(pl->d_pieces), static_cast<const uint2 *>(pl->d_chunk_map),
                      pl->n_chunks, b0, b1, static_cast<uint8_t *>(d_out));
-  SHIP(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   return MSGPU_OK;
 }
 
@@ -828,7 +817,7 @@ int msgpu_gather_run(msgpu_seqctx *c, const msgpu_gather_plan *pl, void *d_out, 
 int msgpu_seq_pack_store(msgpu_seqctx *c, int kind) {
   if (!c || kind < 0 || kind > 1) return MSGPU_E_ARG;
   if (c->device < 0) return MSGPU_E_NODEVICE;
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   {
     SeqStore &s = c->st[kind];
     if (s.packed || !s.d_buf) return MSGPU_OK;
@@ -836,7 +825,7 @@ int msgpu_seq_pack_store(msgpu_seqctx *c, int kind) {
     const uint64_t n_words = (s.n_bases + 15) / 16;
     const uint8_t *bases   = static_cast<const uint8_t *>(s.d_buf) + SEQ_PAD;
     void          *d_cnt   = nullptr;
-    SHIP(c, hipMalloc(&s.d_words, (n_words + 2 * PACK_PAD) * 4));
+    STAGE_HIP(c, hipMalloc(&s.d_words, (n_words + 2 * PACK_PAD) * 4));
     hipError_t e = hipMalloc(&d_cnt, 8);
     if (e == hipSuccess) e = hipMemsetAsync(s.d_words, 0, (n_words + 2 * PACK_PAD) * 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 8, st);
@@ -882,7 +871,7 @@ int msgpu_seq_pack_store(msgpu_seqctx *c, int kind) {
     if (d_cnt) (void)hipFree(d_cnt);
     if (e != hipSuccess) {
       s.drop_packed();
-      return sfail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "msgpu_seq_pack", e);
+      return stage_fail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "msgpu_seq_pack", e);
     }
     s.n_exc  = n_exc;
     s.packed = true;
@@ -911,7 +900,7 @@ int msgpu_fasta_format(msgpu_seqctx *c, const void *d_raw, const msgpu_fasta_rec
                        void *hip_stream) {
   if (!c || (n && (!records || !d_text)) || (headers_bytes && !headers) || n >= 0xfffffff0ull) return MSGPU_E_ARG;
   if (c->device < 0) return MSGPU_E_NODEVICE;
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   if (!n) return MSGPU_OK;
   std::vector<uint32_t> cmap;
   uint64_t              chunks = 0;
@@ -948,7 +937,7 @@ int msgpu_fasta_format(msgpu_seqctx *c, const void *d_raw, const msgpu_fasta_rec
   }
   // the staging copies come from pageable host memory (`cmap` is local): wait before they go out of scope
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return sfail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "fasta format", e);
+  if (e != hipSuccess) return stage_fail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "fasta format", e);
   return MSGPU_OK;
 }
 
@@ -1016,7 +1005,7 @@ int msgpu_assembly_finish(msgpu_assembly *a, void *hip_stream) {
   if (a->finished) return MSGPU_OK;
   msgpu_seqctx *c = a->ctx;
   if (c->device < 0) return MSGPU_E_NODEVICE;
-  SHIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
   // one text buffer: all target records, then (16-byte aligned) all query records; one wrapping launch, one copy back
   std::vector<msgpu_fasta_record> recs;
@@ -1126,7 +1115,7 @@ int msgpu_assembly_finish(msgpu_assembly *a, void *hip_stream) {
   if (e != hipSuccess || rc != MSGPU_OK) {
     if (d_raw) parked().give(d_raw, parked().cap_of(d_raw), c->device);
     if (h_text) parked().give(h_text, parked().cap_of(h_text), -1);
-    if (e != hipSuccess) return sfail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "assembly finish", e);
+    if (e != hipSuccess) return stage_fail(c, e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "assembly finish", e);
     return rc;
   }
   a->text          = h_text;
@@ -1176,7 +1165,7 @@ int msgpu_assembly_validate(msgpu_assembly *a, uint32_t band, uint32_t *distance
 int msgpu_seq_synchronize(msgpu_seqctx *c) {
   if (!c) return MSGPU_E_ARG;
   if (c->device < 0) return MSGPU_OK;
-  SHIP(c, hipStreamSynchronize(c->stream));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
   return MSGPU_OK;
 }
 
@@ -1434,9 +1423,9 @@ int msgpu_edit_distance(msgpu_seqctx *c, const void *d_a, const void *d_b, const
   if (!n) return MSGPU_OK;
   for (size_t i = 0; i < n; ++i)
     if (pairs[i].a_len >= (1u << 30) || pairs[i].b_len >= (1u << 30)) return MSGPU_E_ARG; // (positions are ints on the device)
-  SHIP(c, hipSetDevice(c->device));
-  SHIP(c, c->scr_pairs.ensure(n * sizeof(msgpu_align_pair)));
-  SHIP(c, c->scr_dist.ensure(n * sizeof(uint32_t)));
+  STAGE_HIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, c->scr_pairs.ensure(n * sizeof(msgpu_align_pair)));
+  STAGE_HIP(c, c->scr_dist.ensure(n * sizeof(uint32_t)));
   void *d_pairs = c->scr_pairs.p, *d_out = c->scr_dist.p;
   hipError_t e = hipMemcpyAsync(d_pairs, pairs, n * sizeof(msgpu_align_pair), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
@@ -1457,7 +1446,7 @@ int msgpu_edit_distance(msgpu_seqctx *c, const void *d_a, const void *d_b, const
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return sfail(c, MSGPU_E_HIP, "msgpu_edit_distance", e);
+  if (e != hipSuccess) return stage_fail(c, MSGPU_E_HIP, "msgpu_edit_distance", e);
   return MSGPU_OK;
 }
 

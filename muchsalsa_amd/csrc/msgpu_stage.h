@@ -1,0 +1,270 @@
+// msgpu_stage.h -- the host-side scaffolding of the pipeline stages (msgpu_filter.hip, msgpu_scrub.hip, msgpu_kmer.hip,
+// msgpu_unitig.hip, msgpu_map.hip), defined once: the stage context with its create / destroy, the HIP-error macro, the
+// device arena with its temporary buffer for rocPRIM, the event clock, the wall-clock timer, the scalar block and its
+// read-back, and the record lookup of the stages that name sequences.  No kernels.
+#ifndef MSGPU_STAGE_H
+#define MSGPU_STAGE_H
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "msgpu.h"
+#include "msgpu_internal.h"
+
+namespace msgpu {
+
+// ---- errors: anything with an `err` array takes a failed HIP call's text
+
+template <class C> int stage_fail(C *c, int code, const char *what, hipError_t e) {
+  snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
+  return code;
+}
+#define STAGE_HIP(c, expr)                                                                                             \
+  do {                                                                                                                 \
+    hipError_t _e = (expr);                                                                                            \
+    if (_e != hipSuccess) return msgpu::stage_fail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, #expr, _e); \
+  } while (0)
+
+// ---- the context
+
+struct StageCtx { // what every stage context is made of
+  int         device = 0;
+  hipStream_t stream = nullptr;
+  char        err[384] = {0};
+  uint64_t    err_line = 0;
+  int         err_file = 0;
+  // What a context owns beyond its stream: a context that does shadows open() (called by stage_create on the context's
+  // device, behind the stream) and holds it in members whose destructors release it (run by stage_destroy on that device).
+  int open() { return MSGPU_OK; }
+};
+
+template <class Ctx> void stage_destroy(Ctx *c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  if (c->stream) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamDestroy(c->stream);
+  }
+  delete c;
+}
+
+template <class Ctx> int stage_create(int device, Ctx **out) {
+  if (!out) return MSGPU_E_ARG;
+  *out     = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
+  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
+  auto *c = new (std::nothrow) Ctx();
+  if (!c) return MSGPU_E_NOMEM;
+  c->device = device;
+  int rc    = MSGPU_OK;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
+    rc = MSGPU_E_HIP;
+  if (rc == MSGPU_OK) rc = c->open();
+  if (rc != MSGPU_OK) {
+    stage_destroy(c);
+    return rc;
+  }
+  *out = c;
+  return MSGPU_OK;
+}
+
+struct SeqCtxHold { // the sequence store of a stage that gathers its output from one
+  msgpu_seqctx *p = nullptr;
+  ~SeqCtxHold() { msgpu_seq_destroy(p); }
+  operator msgpu_seqctx *() const { return p; }
+};
+
+struct SeqFileHold { // a parsed sequence file, freed on every way out
+  msgpu_seqfile *f = nullptr;
+  ~SeqFileHold() { msgpu_seq_free(f); }
+  operator const msgpu_seqfile *() const { return f; }
+};
+
+// ---- device memory
+
+struct DevArena { // device memory freed on every way out of a run
+  std::vector<void *> p;
+  void               *tmp = nullptr; // one temporary buffer for every rocPRIM call of the run, grown when a call needs more
+  size_t              tmp_bytes = 0;
+  ~DevArena() {
+    for (void *x : p) (void)hipFree(x);
+  }
+  template <class T> hipError_t get(T **out, size_t count) {
+    void      *m = nullptr;
+    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
+    if (e == hipSuccess) p.push_back(m);
+    *out = static_cast<T *>(m);
+    return e;
+  }
+  void drop(void *x) {
+    auto it = std::find(p.begin(), p.end(), x);
+    if (it != p.end()) p.erase(it);
+    (void)hipFree(x);
+  }
+  hipError_t room(size_t need) {
+    if (tmp && need <= tmp_bytes) return hipSuccess;
+    uint8_t   *t = nullptr;
+    hipError_t e = get(&t, need);
+    if (e == hipSuccess) {
+      tmp       = t;
+      tmp_bytes = need;
+    }
+    return e;
+  }
+  void drop_tmp() { // (after a synchronisation) a large temporary buffer that the rest of the run should not carry
+    drop(tmp);
+    tmp       = nullptr;
+    tmp_bytes = 0;
+  }
+};
+
+// rocPRIM's two calls on the arena's temporary buffer: call(null, bytes) answers the size, call(tmp, bytes) runs
+template <class Call> hipError_t stage_rocprim(DevArena &D, Call &&call) {
+  size_t     need = 0;
+  hipError_t e    = call(static_cast<void *>(nullptr), need);
+  if (e == hipSuccess) e = D.room(need);
+  if (e == hipSuccess) e = call(D.tmp, need);
+  return e;
+}
+// exclusive sums from zero of n values, in the type of `out`
+template <class In, class Out> hipError_t stage_scan(DevArena &D, hipStream_t st, In in, Out *out, size_t n) {
+  return stage_rocprim(D, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, in, out, Out(0), n, rocprim::plus<Out>(), st); });
+}
+// stable sort of n (key, value) pairs by the key's bits [0, end_bit)
+template <class K, class V>
+hipError_t stage_sort_pairs(DevArena &D, hipStream_t st, K *kin, K *kout, V *vin, V *vout, size_t n, unsigned end_bit = 8 * sizeof(K)) {
+  return stage_rocprim(D, [&](void *t, size_t &b) {
+    return rocprim::radix_sort_pairs(t, b, kin, kout, vin, vout, static_cast<unsigned int>(n), 0, end_bit, st);
+  });
+}
+
+inline uint32_t grid_of(uint64_t n, uint32_t per) { return static_cast<uint32_t>((n + per - 1) / per); }
+inline uint32_t grid256(uint64_t n) { return grid_of(n, 256); }
+
+// ---- time
+
+struct StageClock { // device steps by event pairs, summed per step after the run's last synchronisation
+  struct Span {
+    hipEvent_t a, b;
+    float     *acc;
+  };
+  std::vector<Span> spans;
+  hipStream_t       st;
+  explicit StageClock(hipStream_t s) : st(s) {}
+  ~StageClock() {
+    for (auto &s : spans) {
+      (void)hipEventDestroy(s.a);
+      (void)hipEventDestroy(s.b);
+    }
+  }
+  hipError_t begin(float *acc) {
+    Span       s{nullptr, nullptr, acc};
+    hipError_t e = hipEventCreate(&s.a);
+    if (e == hipSuccess) e = hipEventCreate(&s.b);
+    if (e == hipSuccess) e = hipEventRecord(s.a, st);
+    spans.push_back(s);
+    return e;
+  }
+  hipError_t end() { return hipEventRecord(spans.back().b, st); }
+  void       collect() { // (after a synchronisation)
+    for (auto &s : spans) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) *s.acc += ms;
+      (void)hipEventDestroy(s.a);
+      (void)hipEventDestroy(s.b);
+    }
+    spans.clear();
+  }
+};
+
+struct StageTimer { // wall-clock milliseconds since it was made
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  float ms() const { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// ---- the scalar block
+
+// SC_COUNT words on the device, read through the project's read-back protocol (msgpu_device.h, publish_to_host): one wavefront
+// writes them into the mapped mirror and publishes a sequence number, the host polls for it.  A stream that ends without the
+// number arriving is answered by a copy, and counted.
+struct ScalarBlock {
+  uint64_t *d = nullptr;     // the block on the device
+  uint64_t *h = nullptr;     // its page-locked, device-mapped mirror and the sequence number behind it
+  uint64_t *h_dev = nullptr; // the device's address of the mirror; null (MSGPU_SYNC_READBACK): every read-back is a copy
+  uint64_t  seq = 0, lost = 0;
+  ~ScalarBlock() { release(); }
+  bool create() { // on the current device; zeroed
+    if (hipMalloc(reinterpret_cast<void **>(&d), SC_COUNT * sizeof(uint64_t)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&h), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess)
+      return false;
+    memset(h, 0, (SC_COUNT + 1) * sizeof(uint64_t));
+    void *dev = nullptr;
+    if (!getenv("MSGPU_SYNC_READBACK") && hipHostGetDevicePointer(&dev, h, 0) == hipSuccess) h_dev = static_cast<uint64_t *>(dev);
+    return hipMemset(d, 0, SC_COUNT * sizeof(uint64_t)) == hipSuccess;
+  }
+  void release() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    d = h = h_dev = nullptr;
+  }
+  int read(StageCtx *c) { // the block as it stands at this point of c's stream -> h
+    if (h_dev) {
+      const uint64_t s = ++seq;
+      launch_publish_scalars(c->stream, d, HostPublish{h_dev, s});
+      STAGE_HIP(c, hipGetLastError());
+      volatile uint64_t *flag = h + SC_COUNT;
+      for (uint64_t spins = 1;; ++spins) {
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == s) return MSGPU_OK;
+        __builtin_ia32_pause();
+        if ((spins & 0xffff) == 0) {
+          const hipError_t q = hipStreamQuery(c->stream);
+          if (q == hipSuccess) {
+            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == s) return MSGPU_OK;
+            break;
+          }
+          if (q != hipErrorNotReady) break;
+        }
+      }
+      ++lost;
+    }
+    STAGE_HIP(c, hipMemcpyAsync(h, d, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    STAGE_HIP(c, hipStreamSynchronize(c->stream));
+    return MSGPU_OK;
+  }
+};
+
+// ---- the records a stage's ids name
+
+constexpr uint32_t STAGE_NONE = 0xffffffffu;
+
+// rec_ids[i] = id_of_name(name of record i) (STAGE_NONE: no id of the stage's), rec_of[id] = the first record of that id.
+// Returns the first k < n_want whose id want[k] (k itself where want is null) has no record, or STAGE_NONE: the caller says
+// which line asked for it.
+template <class IdOfName>
+uint32_t stage_first_records(const msgpu_seqfile *f, IdOfName id_of_name, uint32_t n_ids, const uint32_t *want, uint32_t n_want,
+                             std::vector<uint32_t> &rec_ids, std::vector<uint32_t> &rec_of) {
+  const uint32_t nr = msgpu_seq_count(f);
+  rec_ids.resize(nr);
+  rec_of.assign(n_ids, STAGE_NONE);
+  for (uint32_t i = 0; i < nr; ++i) {
+    rec_ids[i] = id_of_name(msgpu_seq_name(f, i));
+    if (rec_ids[i] != STAGE_NONE && rec_of[rec_ids[i]] == STAGE_NONE) rec_of[rec_ids[i]] = i;
+  }
+  for (uint32_t k = 0; k < n_want; ++k)
+    if (rec_of[want ? want[k] : k] == STAGE_NONE) return k;
+  return STAGE_NONE;
+}
+
+} // namespace msgpu
+
+#endif

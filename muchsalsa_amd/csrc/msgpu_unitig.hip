@@ -21,7 +21,6 @@
 // Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <deque>
 #include <memory>
 #include <new>
@@ -325,11 +324,9 @@ using namespace msgpu;
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-struct msgpu_ugctx : msgpu::KfCtx {
-  uint64_t *d_scalars = nullptr;     // the scalar block (SC_COUNT words)
-  uint64_t *h_scalars = nullptr;     // its page-locked, device-mapped mirror and the sequence number behind it
-  uint64_t *h_scalars_dev = nullptr; // (the device's address of the mirror; null: every read-back is a copy)
-  uint64_t  seq = 0, lost = 0;
+struct msgpu_ugctx : msgpu::StageCtx {
+  ScalarBlock sc;
+  int         open() { return sc.create() ? MSGPU_OK : MSGPU_E_HIP; }
 };
 
 struct msgpu_ug_result {
@@ -348,8 +345,7 @@ namespace {
 
 enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOTAL_C };
 
-int ug_read_scalars(msgpu_ugctx *c) { return kf_read_scalars(c, c->d_scalars, c->h_scalars, c->h_scalars_dev, c->seq, c->lost); } // (msgpu_kmer_shared.h)
-inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->d_scalars + slot, 0, 8, c->stream); }
+inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->sc.d + slot, 0, 8, c->stream); }
 
 template <class K> void ug_split(K key, uint64_t &hi, uint64_t &lo);
 template <> void ug_split<uint64_t>(uint64_t key, uint64_t &hi, uint64_t &lo) {
@@ -361,28 +357,25 @@ template <> void ug_split<kf_u128>(kf_u128 key, uint64_t &hi, uint64_t &lo) {
   lo = static_cast<uint64_t>(key);
 }
 
-inline uint32_t ug_grid(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
-
 // everything behind the format check, for one key width
 template <class K>
-int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &prm, uint64_t budget, msgpu_ug_result *res) {
+int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const msgpu_ug_params &prm, uint64_t budget, msgpu_ug_result *res) {
   msgpu_ug_stats &S = res->stats;
   hipStream_t     st = c->stream;
-  KfClock         clock;
-  clock.st = st;
+  StageClock      clock(st);
   const int      k = prm.k;
   const uint64_t n_first = F[0].n_lines >> 2, n_reads = n_first + (F[1].n_lines >> 2);
   const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_first, n_reads, k};
 
   // ---- count: the k-mer filter's, least = min_count, no histogram
   kf_ull *d_cur;
-  KHIP(c, D.get(&d_cur, 1));
+  STAGE_HIP(c, D.get(&d_cur, 1));
   std::vector<uint64_t> pre;
   int                   rc = kf_bin_prefix<K>(c, D, clock, in, &S.bins_ms, pre);
   if (rc != MSGPU_OK) return rc;
   S.n_windows = pre[KF_BINS];
   size_t free_b = 0, total_b = 0;
-  KHIP(c, hipMemGetInfo(&free_b, &total_b));
+  STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
   const uint64_t per_key = 2 * sizeof(K) + 4; // two key buffers and the run lengths
   if (!budget) budget = free_b / 2;
   const KfParts parts = kf_pick_partitions(pre, per_key, budget);
@@ -409,7 +402,7 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
   const uint32_t n = static_cast<uint32_t>(kept);
   const uint64_t n2 = 2ull * n;
   // what the rest keeps resident: keys, counts, the table, three bytes per k-mer, eight words per oriented node
-  KHIP(c, hipMemGetInfo(&free_b, &total_b));
+  STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
   const uint64_t graph_bytes = n * (2 * (sizeof(K) + 4ull) + 8 + 3) + n2 * (8 * 4ull + 1);
   if (graph_bytes > free_b) {
     snprintf(c->err, sizeof(c->err), "%u solid k-mers of %zu-byte keys need about %llu bytes for the graph; %zu bytes of device "
@@ -418,24 +411,24 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
   }
   K        *d_keys = nullptr;
   uint32_t *d_cnt = nullptr, *d_slots = nullptr, slots_n = 0;
-  KHIP(c, clock.begin(&S.select_ms));
+  STAGE_HIP(c, clock.begin(&S.select_ms));
   rc = kf_gather_sorted<K>(c, D, chunks, prm.min_count, n, k, d_cur, &d_keys, &d_cnt, &d_slots, &slots_n);
   if (rc != MSGPU_OK) return rc;
-  KHIP(c, clock.end());
+  STAGE_HIP(c, clock.end());
   UgGraph<K> g{d_keys, d_slots, slots_n - 1, n, k, 2 * (k - 1),
                (2 * k == static_cast<int>(sizeof(K) * 8)) ? ~static_cast<K>(0) : ((static_cast<K>(1) << (2 * k)) - 1)};
 
   // ---- neighbour bytes, tip rounds
   uint8_t *d_alive, *d_adj, *d_mark;
-  KHIP(c, D.get(&d_alive, n));
-  KHIP(c, D.get(&d_adj, n));
-  KHIP(c, D.get(&d_mark, n));
-  KHIP(c, hipMemsetAsync(d_alive, 1, n ? n : 1, st));
-  KHIP(c, hipMemsetAsync(d_mark, 0, n ? n : 1, st));
-  KHIP(c, clock.begin(&S.adjacency_ms));
-  if (n) hipLaunchKernelGGL((k_ug_adj<K, true>), dim3(ug_grid(n)), dim3(256), 0, st, g, d_alive, d_adj);
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  STAGE_HIP(c, D.get(&d_alive, n));
+  STAGE_HIP(c, D.get(&d_adj, n));
+  STAGE_HIP(c, D.get(&d_mark, n));
+  STAGE_HIP(c, hipMemsetAsync(d_alive, 1, n ? n : 1, st));
+  STAGE_HIP(c, hipMemsetAsync(d_mark, 0, n ? n : 1, st));
+  STAGE_HIP(c, clock.begin(&S.adjacency_ms));
+  if (n) hipLaunchKernelGGL((k_ug_adj<K, true>), dim3(grid256(n)), dim3(256), 0, st, g, d_alive, d_adj);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
   std::deque<msgpu_ug_round> rounds; // (the clock keeps pointers into it)
   uint64_t                   alive_n = n;
   const uint32_t             trim = static_cast<uint32_t>(prm.trim);
@@ -443,23 +436,23 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
     if (limit > trim) limit = trim;
     rounds.push_back(msgpu_ug_round{limit, 0, 0, 0.f, 0.f});
     msgpu_ug_round &R = rounds.back();
-    KHIP(c, ug_zero_scalar(c, UG_SC_REMOVED));
-    KHIP(c, clock.begin(&R.tips_ms));
+    STAGE_HIP(c, ug_zero_scalar(c, UG_SC_REMOVED));
+    STAGE_HIP(c, clock.begin(&R.tips_ms));
     if (n) {
-      hipLaunchKernelGGL(k_ug_tips<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_alive, d_adj, limit, d_mark);
-      hipLaunchKernelGGL(k_ug_apply, dim3(ug_grid(n)), dim3(256), 0, st, n, d_alive, d_mark, reinterpret_cast<kf_ull *>(c->d_scalars + UG_SC_REMOVED));
+      hipLaunchKernelGGL(k_ug_tips<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_alive, d_adj, limit, d_mark);
+      hipLaunchKernelGGL(k_ug_apply, dim3(grid256(n)), dim3(256), 0, st, n, d_alive, d_mark, reinterpret_cast<kf_ull *>(c->sc.d + UG_SC_REMOVED));
     }
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
-    rc = ug_read_scalars(c);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
     if (rc != MSGPU_OK) return rc;
-    R.removed = c->h_scalars[UG_SC_REMOVED];
+    R.removed = c->sc.h[UG_SC_REMOVED];
     alive_n -= R.removed;
     if (R.removed) {
-      KHIP(c, clock.begin(&R.adjacency_ms));
-      hipLaunchKernelGGL((k_ug_adj<K, false>), dim3(ug_grid(n)), dim3(256), 0, st, g, d_alive, d_adj);
-      KHIP(c, hipGetLastError());
-      KHIP(c, clock.end());
+      STAGE_HIP(c, clock.begin(&R.adjacency_ms));
+      hipLaunchKernelGGL((k_ug_adj<K, false>), dim3(grid256(n)), dim3(256), 0, st, g, d_alive, d_adj);
+      STAGE_HIP(c, hipGetLastError());
+      STAGE_HIP(c, clock.end());
     }
     if (limit < trim) limit = limit > trim / 2 ? trim : 2 * limit; // 1, 2, 4, ... below trim, then trim
     else if (!R.removed) limit = 0;                                // the round at trim repeats until it removes nothing
@@ -470,18 +463,18 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
 
   // ---- joins, pointer doubling
   uint32_t *d_next, *d_ptr[2], *d_dist[2];
-  KHIP(c, D.get(&d_next, n2));
+  STAGE_HIP(c, D.get(&d_next, n2));
   for (int i = 0; i < 2; ++i) {
-    KHIP(c, D.get(&d_ptr[i], n2));
-    KHIP(c, D.get(&d_dist[i], n2));
+    STAGE_HIP(c, D.get(&d_ptr[i], n2));
+    STAGE_HIP(c, D.get(&d_dist[i], n2));
   }
-  KHIP(c, clock.begin(&S.next_ms));
+  STAGE_HIP(c, clock.begin(&S.next_ms));
   if (n) {
-    hipLaunchKernelGGL(k_ug_next<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_alive, d_adj, d_next);
-    hipLaunchKernelGGL(k_ug_chain_init<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_alive, d_next, d_ptr[0], d_dist[0]);
+    hipLaunchKernelGGL(k_ug_next<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_alive, d_adj, d_next);
+    hipLaunchKernelGGL(k_ug_chain_init<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_alive, d_next, d_ptr[0], d_dist[0]);
   }
-  KHIP(c, hipGetLastError());
-  KHIP(c, clock.end());
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
   int  cur = 0;
   auto doubling = [&](uint64_t &open) -> int { // rounds until the number of open nodes is 0 or stops falling
     uint64_t before = ~0ull;
@@ -490,17 +483,17 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
         snprintf(c->err, sizeof(c->err), "pointer doubling did not settle in %u rounds", S.doubling_rounds);
         return MSGPU_E_STATE;
       }
-      KHIP(c, ug_zero_scalar(c, UG_SC_OPEN));
-      KHIP(c, clock.begin(&S.doubling_ms));
-      hipLaunchKernelGGL(k_ug_double, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_next, d_ptr[cur], d_dist[cur], d_ptr[cur ^ 1],
-                         d_dist[cur ^ 1], reinterpret_cast<kf_ull *>(c->d_scalars + UG_SC_OPEN));
-      KHIP(c, hipGetLastError());
-      KHIP(c, clock.end());
+      STAGE_HIP(c, ug_zero_scalar(c, UG_SC_OPEN));
+      STAGE_HIP(c, clock.begin(&S.doubling_ms));
+      hipLaunchKernelGGL(k_ug_double, dim3(grid256(n2)), dim3(256), 0, st, n2, d_next, d_ptr[cur], d_dist[cur], d_ptr[cur ^ 1],
+                         d_dist[cur ^ 1], reinterpret_cast<kf_ull *>(c->sc.d + UG_SC_OPEN));
+      STAGE_HIP(c, hipGetLastError());
+      STAGE_HIP(c, clock.end());
       cur ^= 1;
       ++S.doubling_rounds;
-      const int r2 = ug_read_scalars(c);
+      const int r2 = c->sc.read(c);
       if (r2 != MSGPU_OK) return r2;
-      open = c->h_scalars[UG_SC_OPEN];
+      open = c->sc.h[UG_SC_OPEN];
       if (!open || open == before) return MSGPU_OK;
       before = open;
     }
@@ -514,20 +507,20 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
   }
   if (open) { // cycles: their smallest node by a min-reduction, the cut, and the doubling again
     uint32_t *d_back[2], *d_low[2];
-    KHIP(c, D.get(&d_cyc, n2));
+    STAGE_HIP(c, D.get(&d_cyc, n2));
     for (int i = 0; i < 2; ++i) {
-      KHIP(c, D.get(&d_back[i], n2));
-      KHIP(c, D.get(&d_low[i], n2));
+      STAGE_HIP(c, D.get(&d_back[i], n2));
+      STAGE_HIP(c, D.get(&d_low[i], n2));
     }
-    KHIP(c, clock.begin(&S.doubling_ms));
-    hipLaunchKernelGGL(k_ug_cyc_init, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_next, d_ptr[cur], d_cyc, d_back[0], d_low[0]);
+    STAGE_HIP(c, clock.begin(&S.doubling_ms));
+    hipLaunchKernelGGL(k_ug_cyc_init, dim3(grid256(n2)), dim3(256), 0, st, n2, d_next, d_ptr[cur], d_cyc, d_back[0], d_low[0]);
     int at = 0;
     for (uint64_t span = 1; span < open; span *= 2, at ^= 1, ++S.doubling_rounds) // (a cycle has at most `open` nodes)
-      hipLaunchKernelGGL(k_ug_cyc_min<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_cyc, d_back[at], d_low[at], d_back[at ^ 1],
+      hipLaunchKernelGGL(k_ug_cyc_min<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_cyc, d_back[at], d_low[at], d_back[at ^ 1],
                          d_low[at ^ 1]);
-    hipLaunchKernelGGL(k_ug_cyc_cut, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_cyc, d_low[at], d_next, d_ptr[cur], d_dist[cur]);
-    KHIP(c, hipGetLastError());
-    KHIP(c, clock.end());
+    hipLaunchKernelGGL(k_ug_cyc_cut, dim3(grid256(n2)), dim3(256), 0, st, n2, d_cyc, d_low[at], d_next, d_ptr[cur], d_dist[cur]);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
     rc = doubling(open);
     if (rc != MSGPU_OK) return rc;
     if (open) {
@@ -543,14 +536,14 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
   D.drop(d_dist[cur ^ 1]);
 
   // ---- the emitted heads in output order, the unitig table, coverage
-  KHIP(c, clock.begin(&S.order_ms));
-  KHIP(c, ug_zero_scalar(c, UG_SC_UNITS));
-  kf_ull *d_units_n = reinterpret_cast<kf_ull *>(c->d_scalars + UG_SC_UNITS);
-  if (n) hipLaunchKernelGGL((k_ug_heads<K, false>), dim3(ug_grid(n2)), dim3(256), 0, st, g, d_next, d_p, nullptr, nullptr, 0, d_units_n);
-  KHIP(c, hipGetLastError());
-  rc = ug_read_scalars(c);
+  STAGE_HIP(c, clock.begin(&S.order_ms));
+  STAGE_HIP(c, ug_zero_scalar(c, UG_SC_UNITS));
+  kf_ull *d_units_n = reinterpret_cast<kf_ull *>(c->sc.d + UG_SC_UNITS);
+  if (n) hipLaunchKernelGGL((k_ug_heads<K, false>), dim3(grid256(n2)), dim3(256), 0, st, g, d_next, d_p, nullptr, nullptr, 0, d_units_n);
+  STAGE_HIP(c, hipGetLastError());
+  rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  const uint32_t U = static_cast<uint32_t>(c->h_scalars[UG_SC_UNITS]);
+  const uint32_t U = static_cast<uint32_t>(c->sc.h[UG_SC_UNITS]);
   S.n_unitigs = U;
   K        *d_first[2];
   uint32_t *d_head[2], *d_unit_of, *d_nk;
@@ -558,31 +551,27 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
   kf_ull   *d_cover;
   uint64_t *d_seq_off;
   for (int i = 0; i < 2; ++i) {
-    KHIP(c, D.get(&d_first[i], U));
-    KHIP(c, D.get(&d_head[i], U));
+    STAGE_HIP(c, D.get(&d_first[i], U));
+    STAGE_HIP(c, D.get(&d_head[i], U));
   }
-  KHIP(c, D.get(&d_unit_of, n2));
-  KHIP(c, D.get(&d_nk, U));
-  KHIP(c, D.get(&d_cyclic, U));
-  KHIP(c, D.get(&d_cover, U));
-  KHIP(c, D.get(&d_seq_off, U));
-  KHIP(c, hipMemsetAsync(d_unit_of, 0xff, n2 ? n2 * 4 : 4, st));
-  KHIP(c, hipMemsetAsync(d_cover, 0, U ? U * 8ull : 8, st));
+  STAGE_HIP(c, D.get(&d_unit_of, n2));
+  STAGE_HIP(c, D.get(&d_nk, U));
+  STAGE_HIP(c, D.get(&d_cyclic, U));
+  STAGE_HIP(c, D.get(&d_cover, U));
+  STAGE_HIP(c, D.get(&d_seq_off, U));
+  STAGE_HIP(c, hipMemsetAsync(d_unit_of, 0xff, n2 ? n2 * 4 : 4, st));
+  STAGE_HIP(c, hipMemsetAsync(d_cover, 0, U ? U * 8ull : 8, st));
   if (U) {
-    KHIP(c, ug_zero_scalar(c, UG_SC_UNITS));
-    hipLaunchKernelGGL((k_ug_heads<K, true>), dim3(ug_grid(n2)), dim3(256), 0, st, g, d_next, d_p, d_first[0], d_head[0], U, d_units_n);
-    KHIP(c, hipGetLastError());
-    size_t need = 0;
-    KHIP(c, rocprim::radix_sort_pairs(nullptr, need, d_first[0], d_first[1], d_head[0], d_head[1], U, 0, 2 * k, st));
-    uint8_t *tmp;
-    KHIP(c, D.get(&tmp, need));
-    KHIP(c, rocprim::radix_sort_pairs(tmp, need, d_first[0], d_first[1], d_head[0], d_head[1], U, 0, 2 * k, st));
-    hipLaunchKernelGGL(k_ug_units, dim3(ug_grid(U)), dim3(256), 0, st, U, d_head[1], d_p, d_d, d_cyc, d_cyc_last, d_unit_of, d_nk,
+    STAGE_HIP(c, ug_zero_scalar(c, UG_SC_UNITS));
+    hipLaunchKernelGGL((k_ug_heads<K, true>), dim3(grid256(n2)), dim3(256), 0, st, g, d_next, d_p, d_first[0], d_head[0], U, d_units_n);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_first[0], d_first[1], d_head[0], d_head[1], U, 2 * k));
+    hipLaunchKernelGGL(k_ug_units, dim3(grid256(U)), dim3(256), 0, st, U, d_head[1], d_p, d_d, d_cyc, d_cyc_last, d_unit_of, d_nk,
                        d_cyclic);
-    hipLaunchKernelGGL(k_ug_cover, dim3(ug_grid(n2)), dim3(256), 0, st, n2, d_p, d_unit_of, d_cnt, d_cover);
-    KHIP(c, hipGetLastError());
+    hipLaunchKernelGGL(k_ug_cover, dim3(grid256(n2)), dim3(256), 0, st, n2, d_p, d_unit_of, d_cnt, d_cover);
+    STAGE_HIP(c, hipGetLastError());
   }
-  KHIP(c, clock.end());
+  STAGE_HIP(c, clock.end());
   std::vector<uint32_t> nk;
   std::vector<uint8_t>  cyclic;
   std::vector<kf_ull>   cover;
@@ -596,18 +585,18 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
     seq_off.resize(U);
     res->units.resize(U);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  KHIP(c, clock.begin(&S.copy_ms));
+  STAGE_HIP(c, clock.begin(&S.copy_ms));
   if (U) {
-    KHIP(c, hipMemcpyAsync(nk.data(), d_nk, U * 4ull, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipMemcpyAsync(cyclic.data(), d_cyclic, U, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipMemcpyAsync(cover.data(), d_cover, U * 8ull, hipMemcpyDeviceToHost, st));
-    KHIP(c, hipMemcpyAsync(first.data(), d_first[1], U * sizeof(K), hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(nk.data(), d_nk, U * 4ull, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(cyclic.data(), d_cyclic, U, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(cover.data(), d_cover, U * 8ull, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipMemcpyAsync(first.data(), d_first[1], U * sizeof(K), hipMemcpyDeviceToHost, st));
   }
-  KHIP(c, clock.end());
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- host: headers and offsets
-  const auto  h0 = std::chrono::steady_clock::now();
+  const StageTimer host0;
   std::string heads; // every header, one behind the other
   std::vector<uint32_t> head_len(U);
   uint64_t              total = 0, solid_sum = 0;
@@ -635,30 +624,30 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
              static_cast<kf_ull>(alive_n));
     return MSGPU_E_STATE;
   }
-  S.host_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+  S.host_ms += host0.ms();
 
   // ---- the bases
   uint8_t *d_text;
-  KHIP(c, D.get(&d_text, total));
-  KHIP(c, clock.begin(&S.write_ms));
+  STAGE_HIP(c, D.get(&d_text, total));
+  STAGE_HIP(c, clock.begin(&S.write_ms));
   if (U) {
-    KHIP(c, hipMemcpyAsync(d_seq_off, seq_off.data(), U * 8ull, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ug_write<K>, dim3(ug_grid(n2)), dim3(256), 0, st, g, d_p, d_d, d_unit_of, d_nk, d_seq_off, d_text, total);
-    KHIP(c, hipGetLastError());
+    STAGE_HIP(c, hipMemcpyAsync(d_seq_off, seq_off.data(), U * 8ull, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ug_write<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_p, d_d, d_unit_of, d_nk, d_seq_off, d_text, total);
+    STAGE_HIP(c, hipGetLastError());
   }
-  KHIP(c, clock.end());
-  KHIP(c, clock.begin(&S.copy_ms));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, clock.begin(&S.copy_ms));
   if (total) {
-    KHIP(c, hipHostMalloc(reinterpret_cast<void **>(&res->all), total, hipHostMallocDefault));
-    KHIP(c, hipMemcpyAsync(res->all, d_text, total, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&res->all), total, hipHostMallocDefault));
+    STAGE_HIP(c, hipMemcpyAsync(res->all, d_text, total, hipMemcpyDeviceToHost, st));
   }
-  KHIP(c, clock.end());
-  KHIP(c, hipStreamSynchronize(st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
   clock.collect();
   res->all_len = total;
 
   // ---- host: the headers into the text, the cut text
-  const auto h1 = std::chrono::steady_clock::now();
+  const StageTimer host1;
   try {
     uint64_t at = 0, cut_bytes = 0;
     for (uint32_t u = 0; u < U; ++u)
@@ -679,7 +668,7 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
     S.tips_ms += R.tips_ms;
     S.adjacency_ms += R.adjacency_ms;
   }
-  S.host_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h1).count();
+  S.host_ms += host1.ms();
   S.bytes_out[0] = res->all_len;
   S.bytes_out[1] = res->cut.size();
   return MSGPU_OK;
@@ -689,44 +678,8 @@ int ug_stage(msgpu_ugctx *c, KfDev &D, const KfFile *F, const msgpu_ug_params &p
 
 extern "C" {
 
-int msgpu_ug_create(int device, msgpu_ugctx **out) {
-  if (!out) return MSGPU_E_ARG;
-  *out     = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
-  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
-  auto *c = new (std::nothrow) msgpu_ugctx();
-  if (!c) return MSGPU_E_NOMEM;
-  c->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&c->d_scalars), SC_COUNT * sizeof(uint64_t)) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void **>(&c->h_scalars), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess) {
-    msgpu_ug_destroy(c);
-    return MSGPU_E_HIP;
-  }
-  memset(c->h_scalars, 0, (SC_COUNT + 1) * sizeof(uint64_t));
-  void *dev = nullptr;
-  if (!getenv("MSGPU_SYNC_READBACK") && hipHostGetDevicePointer(&dev, c->h_scalars, 0) == hipSuccess)
-    c->h_scalars_dev = static_cast<uint64_t *>(dev);
-  if (hipMemset(c->d_scalars, 0, SC_COUNT * sizeof(uint64_t)) != hipSuccess) {
-    msgpu_ug_destroy(c);
-    return MSGPU_E_HIP;
-  }
-  *out = c;
-  return MSGPU_OK;
-}
-
-void msgpu_ug_destroy(msgpu_ugctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->stream) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamDestroy(c->stream);
-  }
-  if (c->d_scalars) (void)hipFree(c->d_scalars);
-  if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-  delete c;
-}
+int  msgpu_ug_create(int device, msgpu_ugctx **out) { return stage_create(device, out); }
+void msgpu_ug_destroy(msgpu_ugctx *c) { stage_destroy(c); }
 
 const char *msgpu_ug_last_error(const msgpu_ugctx *c) { return c ? c->err : "null context"; }
 uint64_t    msgpu_ug_error_line(const msgpu_ugctx *c) { return c ? c->err_line : 0; }
@@ -750,11 +703,8 @@ int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path
     snprintf(c->err, sizeof(c->err), "min_count = %u must be at least 1, trim = %d at least 0 (or -1 for k)", prm.min_count, prm.trim);
     return MSGPU_E_ARG;
   }
-  const auto w0 = std::chrono::steady_clock::now();
-  auto       since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
-  KHIP(c, hipSetDevice(c->device));
+  const StageTimer wall;
+  STAGE_HIP(c, hipSetDevice(c->device));
   std::unique_ptr<msgpu_ug_result> res;
   try {
     res.reset(new msgpu_ug_result());
@@ -764,18 +714,18 @@ int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path
   S.min_count  = prm.min_count;
   S.trim       = static_cast<uint32_t>(prm.trim);
   S.min_length = prm.min_length;
-  KfDev          D;
+  DevArena       D;
   KfFile         F[2];
   const char    *paths[2] = {path_a, path_b};
   const int      n_files = path_b ? 2 : 1;
-  const uint64_t lost0 = c->lost;
+  const uint64_t lost0 = c->sc.lost;
   for (int f = 0; f < n_files; ++f) {
     const int rc = kf_upload(c, D, paths[f], f, F[f]);
     if (rc != MSGPU_OK) return rc;
     S.bytes_in[f] = F[f].size;
   }
-  S.load_ms = since(w0);
-  const auto r0 = std::chrono::steady_clock::now();
+  S.load_ms = wall.ms();
+  const StageTimer records;
   int        rc = kf_records(c, D, F, n_files);
   if (rc != MSGPU_OK) return rc;
   if (n_files == 1) { // no second file: no read of it is ever asked for
@@ -784,11 +734,11 @@ int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path
   }
   S.n_records[0] = F[0].n_lines >> 2;
   S.n_records[1] = F[1].n_lines >> 2;
-  S.records_ms   = since(r0);
+  S.records_ms   = records.ms();
   rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, prm, budget_bytes, res.get()) : ug_stage<kf_u128>(c, D, F, prm, budget_bytes, res.get());
   if (rc != MSGPU_OK) return rc;
-  S.n_lost_publications = c->lost - lost0;
-  S.wall_ms             = since(w0);
+  S.n_lost_publications = c->sc.lost - lost0;
+  S.wall_ms             = wall.ms();
   *out                  = res.release();
   return MSGPU_OK;
 }

@@ -63,21 +63,14 @@ import time
 import numpy as np
 
 from . import _lib
+from ._stage import StageError, stage_context, text_view
 
 __all__ = ["KmerFilterError", "threshold", "run", "main"]
 
 
-class KmerFilterError(RuntimeError):
+class KmerFilterError(StageError):
     """A rejected input or a device failure; ``line`` = 1-based line (0: none) of ``file`` (0 / 1: the first / second
     FASTQ)."""
-
-    def __init__(self, code, file=0, line=0, detail=""):
-        msg = _lib.lib().msgpu_strerror(code).decode()
-        where = (" (file %d line %d)" % (file, line)) if line else ""
-        super().__init__("%s (%d)%s%s" % (msg, code, where, (": " + detail) if detail else ""))
-        self.code = code
-        self.file = file
-        self.line = line
 
 
 def threshold(rows):
@@ -98,13 +91,6 @@ def _arr(p, n, dtype):
     return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype)
 
 
-def _text(L, res, which):
-    """a view of one of the result's texts (valid until the result is freed)"""
-    n = C.c_uint64()
-    p = L.msgpu_kf_result_text(res, which, C.byref(n))
-    return memoryview((C.c_char * n.value).from_address(p)) if n.value else b""
-
-
 def run(k, in1, in2, report, out1, out2, device=0, budget_mb=None, histo=None, kmers=None, timings=None, tables=None):
     """The whole stage: writes ``out1``, ``out2`` and ``report`` (and ``histo`` / ``kmers`` when given); returns the
     counts.  ``budget_mb`` bounds the partition buffers (None: half of the free device memory).  ``timings`` (a dict)
@@ -112,18 +98,9 @@ def run(k, in1, in2, report, out1, out2, device=0, budget_mb=None, histo=None, k
     abundant set, ascending) and ``verdict`` (a byte per pair, 1 = dropped)."""
     L = _lib.lib()
     t0 = time.perf_counter()
-    ctx = C.c_void_p()
-    rc = L.msgpu_kf_create(device, C.byref(ctx))
-    if rc != _lib.OK:
-        raise KmerFilterError(rc, detail="device %d" % device)
-    try:
-        res = C.c_void_p()
-        budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
-        rc = L.msgpu_kf_run(ctx, int(k), os.fsencode(in1), os.fsencode(in2), 0, budget, C.byref(res))
-        if rc != _lib.OK:
-            raise KmerFilterError(rc, int(L.msgpu_kf_error_file(ctx)), int(L.msgpu_kf_error_line(ctx)),
-                                  L.msgpu_kf_last_error(ctx).decode(errors="replace"))
-        try:
+    budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
+    with stage_context("kf", device, KmerFilterError) as stage:
+        with stage.run(int(k), os.fsencode(in1), os.fsencode(in2), 0, budget) as res:
             st = _lib.KfStats()
             L.msgpu_kf_result_stats(res, C.byref(st))
             if tables is not None:
@@ -145,12 +122,8 @@ def run(k, in1, in2, report, out1, out2, device=0, budget_mb=None, histo=None, k
                 files.append((kmers, _lib.KF_TEXT_KMERS))
             for path, which in files:
                 with open(path, "wb") as h:
-                    h.write(_text(L, res, which))
+                    h.write(text_view(L.msgpu_kf_result_text, res, which))
             t_write = time.perf_counter() - t1
-        finally:
-            L.msgpu_kf_result_free(res)
-    finally:
-        L.msgpu_kf_destroy(ctx)
     if timings is not None:
         timings.update({"load": st.load_ms / 1e3, "records": st.records_ms / 1e3, "bins": st.bins_ms / 1e3,
                         "extract": st.extract_ms / 1e3, "sort": st.sort_ms / 1e3, "runs": st.runs_ms / 1e3,

@@ -73,19 +73,18 @@ import sys
 import time
 
 from . import _lib
+from ._stage import StageError, stage_context, text_view
 
 __all__ = ["MapError", "run", "main", "DEFAULTS"]
 
 DEFAULTS = dict(k=15, w=5, max_occ=200, max_gap=10000, bandwidth=2000, min_score=100, min_count=3, exact=0, band=64, ava=0)
 
 
-class MapError(RuntimeError):
+class MapError(StageError):
     """A rejected input or parameter, or a device failure."""
 
     def __init__(self, code, detail=""):
-        msg = _lib.lib().msgpu_strerror(code).decode()
-        super().__init__("%s (%d)%s" % (msg, code, (": " + detail) if detail else ""))
-        self.code = code
+        super().__init__(code, detail=detail)
 
 
 def run(targets, queries, out, device=0, tables=None, timings=None, **params):
@@ -102,24 +101,13 @@ def run(targets, queries, out, device=0, tables=None, timings=None, **params):
     for name, v in p.items():
         if not -(1 << 31) <= int(v) < (1 << 31) or (name == "max_occ" and int(v) < 0):
             raise MapError(_lib.E_ARG, "%s = %d" % (name, int(v)))
-    ctx = C.c_void_p()
-    rc = L.msgpu_map_create(device, C.byref(ctx))
-    if rc != _lib.OK:
-        raise MapError(rc, "device %d" % device)
-    try:
-        res = C.c_void_p()
+    with stage_context("map", device, MapError) as stage:
         prm = _lib.MapParams(int(p["k"]), int(p["w"]), int(p["max_occ"]), int(p["max_gap"]), int(p["bandwidth"]), 64,
                              int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]), 0)
-        rc = L.msgpu_map_run(ctx, C.byref(prm), os.fsencode(targets), None if queries is None else os.fsencode(queries), 0, 0,
-                             C.byref(res))
-        if rc != _lib.OK:
-            raise MapError(rc, L.msgpu_map_last_error(ctx).decode(errors="replace"))
-        try:
+        with stage.run(C.byref(prm), os.fsencode(targets), None if queries is None else os.fsencode(queries), 0, 0) as res:
             st = _lib.MapStats()
             L.msgpu_map_result_stats(res, C.byref(st))
-            n = C.c_uint64()
-            ptr = L.msgpu_map_result_text(res, C.byref(n))
-            text = memoryview((C.c_char * n.value).from_address(ptr)) if n.value else b""
+            text = text_view(L.msgpu_map_result_text, res)
             if tables is not None:
                 cp = C.POINTER(_lib.MapChain)()
                 m = C.c_uint64()
@@ -131,10 +119,6 @@ def run(targets, queries, out, device=0, tables=None, timings=None, **params):
             with open(out, "wb") as h:
                 h.write(text)
             t_write = time.perf_counter() - t1
-        finally:
-            L.msgpu_map_result_free(res)
-    finally:
-        L.msgpu_map_destroy(ctx)
     if timings is not None:
         timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.MapStats._fields_ if name.endswith("_ms")})
         timings["stage_wall"] = timings.pop("wall")

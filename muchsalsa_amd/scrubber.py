@@ -51,23 +51,23 @@ import time
 import numpy as np
 
 from . import _lib
+from ._stage import StageError, stage_context, text_view
 
 __all__ = ["ScrubberError", "ScrubPaf", "batches", "run", "main", "SUBSET_SIZE"]
 
 SUBSET_SIZE = _lib.SCRUB_SUBSET
 
 
-class ScrubberError(RuntimeError):
+class ScrubberError(StageError):
     """A rejected input or a device failure; ``line`` = 1-based line (0: none) of ``file`` (0 anchor PAF, 1 read-to-read
     PAF)."""
 
     def __init__(self, code, detail="", line=0, file=0):
-        msg = _lib.lib().msgpu_strerror(code).decode()
-        where = (" (%s line %d)" % (("anchor PAF", "read-to-read PAF")[file], line)) if line else ""
-        super().__init__("%s (%d)%s%s" % (msg, code, where, (": " + detail) if detail else ""))
-        self.code = code
-        self.line = line
-        self.file = file
+        super().__init__(code, file, line, detail)
+
+    @staticmethod
+    def where(file, line):
+        return " (%s line %d)" % (("anchor PAF", "read-to-read PAF")[file], line)
 
 
 def _arr(p, n, dtype):
@@ -161,31 +161,16 @@ def run(anchors, reads, out, ava, subset_size=SUBSET_SIZE, device=0, timings=Non
     t0 = time.perf_counter()
     with ScrubPaf(anchors, ava) as s:
         t_parse = time.perf_counter() - t0
-        ctx = C.c_void_p()
-        rc = L.msgpu_scrub_create(device, C.byref(ctx))
-        if rc != _lib.OK:
-            raise ScrubberError(rc, "device %d" % device)
-        try:
-            res = C.c_void_p()
-            rc = L.msgpu_scrub_run(ctx, s.handle, os.fsencode(reads), int(subset_size), C.byref(res))
-            if rc != _lib.OK:
-                raise ScrubberError(rc, L.msgpu_scrub_last_error(ctx).decode(errors="replace"),
-                                    int(L.msgpu_scrub_error_line(ctx)))
-            try:
+        with stage_context("scrub", device, ScrubberError) as stage:
+            with stage.run(s.handle, os.fsencode(reads), int(subset_size)) as res:
                 st = _lib.ScrubStats()
                 L.msgpu_scrub_result_stats(res, C.byref(st))
-                n = C.c_uint64()
-                p = L.msgpu_scrub_result_text(res, C.byref(n))
-                text = C.string_at(p, n.value) if n.value else b""
+                text = bytes(text_view(L.msgpu_scrub_result_text, res))
                 if graph is not None:
                     ro, ad = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
                     L.msgpu_scrub_result_graph(res, C.byref(ro), C.byref(ad))
                     graph["row_off"] = _arr(ro, int(st.n_nodes) + 1, np.uint64)
                     graph["adj"] = _arr(ad, 2 * int(st.n_edges), np.uint32)
-            finally:
-                L.msgpu_scrub_result_free(res)
-        finally:
-            L.msgpu_scrub_destroy(ctx)
     t1 = time.perf_counter()
     with open(out, "wb") as f:
         f.write(text)

@@ -36,19 +36,20 @@ import time
 import numpy as np
 
 from . import _lib
+from ._stage import StageError, stage_context, text_view
 
 __all__ = ["UnitigFilterError", "UfPaf", "quartiles", "run", "report_text", "main"]
 
 
-class UnitigFilterError(RuntimeError):
+class UnitigFilterError(StageError):
     """A rejected input or a device failure; ``line`` = 1-based PAF line (0: none)."""
 
     def __init__(self, code, detail="", line=0):
-        msg = _lib.lib().msgpu_strerror(code).decode()
-        where = (" (PAF line %d)" % line) if line else ""
-        super().__init__("%s (%d)%s%s" % (msg, code, where, (": " + detail) if detail else ""))
-        self.code = code
-        self.line = line
+        super().__init__(code, 0, line, detail)
+
+    @staticmethod
+    def where(file, line):
+        return " (PAF line %d)" % line
 
 
 class UfPaf:
@@ -123,26 +124,11 @@ def run(paf, unitigs, report, out, device=0, timings=None, packed=False):
     t0 = time.perf_counter()
     with UfPaf(paf) as u:
         t_parse = time.perf_counter() - t0
-        ctx = C.c_void_p()
-        rc = L.msgpu_uf_create(device, C.byref(ctx))
-        if rc != _lib.OK:
-            raise UnitigFilterError(rc, "device %d" % device)
-        try:
-            res = C.c_void_p()
-            rc = L.msgpu_uf_run(ctx, u.handle, os.fsencode(unitigs), _lib.UF_PACKED if packed else 0, C.byref(res))
-            if rc != _lib.OK:
-                raise UnitigFilterError(rc, L.msgpu_uf_last_error(ctx).decode(errors="replace"),
-                                        int(L.msgpu_uf_error_line(ctx)))
-            try:
+        with stage_context("uf", device, UnitigFilterError) as stage:
+            with stage.run(u.handle, os.fsencode(unitigs), _lib.UF_PACKED if packed else 0) as res:
                 st = _lib.UfStats()
                 L.msgpu_uf_result_stats(res, C.byref(st))
-                n = C.c_uint64()
-                p = L.msgpu_uf_result_text(res, C.byref(n))
-                text = C.string_at(p, n.value) if n.value else b""
-            finally:
-                L.msgpu_uf_result_free(res)
-        finally:
-            L.msgpu_uf_destroy(ctx)
+                text = bytes(text_view(L.msgpu_uf_result_text, res))
     t1 = time.perf_counter()
     with open(out, "wb") as f:
         f.write(text)

@@ -53,28 +53,14 @@ import sys
 import time
 
 from . import _lib
+from ._stage import StageError, stage_context, text_view
 
 __all__ = ["UnitigError", "run", "main"]
 
 
-class UnitigError(RuntimeError):
+class UnitigError(StageError):
     """A rejected input or a device failure; ``line`` = 1-based line (0: none) of ``file`` (0 / 1: the first / second
     FASTQ)."""
-
-    def __init__(self, code, file=0, line=0, detail=""):
-        msg = _lib.lib().msgpu_strerror(code).decode()
-        where = (" (file %d line %d)" % (file, line)) if line else ""
-        super().__init__("%s (%d)%s%s" % (msg, code, where, (": " + detail) if detail else ""))
-        self.code = code
-        self.file = file
-        self.line = line
-
-
-def _text(L, res, which):
-    """a view of one of the result's texts (valid until the result is freed)"""
-    n = C.c_uint64()
-    p = L.msgpu_ug_result_text(res, which, C.byref(n))
-    return memoryview((C.c_char * n.value).from_address(p)) if n.value else b""
 
 
 def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_length=500, budget_mb=None, tables=None,
@@ -86,23 +72,13 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
     neighbour bytes)] per round."""
     L = _lib.lib()
     t0 = time.perf_counter()
-    ctx = C.c_void_p()
-    rc = L.msgpu_ug_create(device, C.byref(ctx))
-    if rc != _lib.OK:
-        raise UnitigError(rc, detail="device %d" % device)
-    try:
-        res = C.c_void_p()
+    with stage_context("ug", device, UnitigError) as stage:
         budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
         prm = _lib.UgParams(int(k), int(min_count) if 0 <= int(min_count) < (1 << 32) else 0, -1 if trim is None else int(trim),
                             min(max(int(min_length), 0), (1 << 32) - 1))
         if trim is not None and int(trim) < 0:
             raise UnitigError(_lib.E_ARG, detail="trim = %d" % int(trim))
-        rc = L.msgpu_ug_run(ctx, C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget,
-                            C.byref(res))
-        if rc != _lib.OK:
-            raise UnitigError(rc, int(L.msgpu_ug_error_file(ctx)), int(L.msgpu_ug_error_line(ctx)),
-                              L.msgpu_ug_last_error(ctx).decode(errors="replace"))
-        try:
+        with stage.run(C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget) as res:
             st = _lib.UgStats()
             L.msgpu_ug_result_stats(res, C.byref(st))
             rp, n = C.POINTER(_lib.UgRound)(), C.c_uint64()
@@ -118,12 +94,8 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
             t1 = time.perf_counter()
             for path, which in ((out_all, _lib.UG_TEXT_ALL), (out_cut, _lib.UG_TEXT_CUT)):
                 with open(path, "wb") as h:
-                    h.write(_text(L, res, which))
+                    h.write(text_view(L.msgpu_ug_result_text, res, which))
             t_write = time.perf_counter() - t1
-        finally:
-            L.msgpu_ug_result_free(res)
-    finally:
-        L.msgpu_ug_destroy(ctx)
     if timings is not None:
         timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.UgStats._fields_ if name.endswith("_ms")})
         timings["stage_wall"] = timings.pop("wall")
