@@ -1150,9 +1150,23 @@ void        msgpu_ug_result_free(msgpu_ug_result *r);
  *  8. output: one line per chain: the twelve PAF columns ('+' / '-' in column 5, mapping quality 255), then cm:i:<anchors>,
  *     s1:i:<score> and, in exact mode, NM:i:<sum d_i>.  Lines are ordered by (query record, target record, strand, order of
  *     emission in the group).  On any error nothing is written.
- *  9. limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs, at most 2^30
- *     distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k below 2^31; everything resident together, otherwise MSGPU_E_NOMEM
- *     naming the sizes.  Larger inputs are out of scope (no target batching). */
+ *  9. limits and batches.  Limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs
+ *     per batch, at most 2^30 distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k
+ *     below 2^31.  Resident for the whole run: both stores, both sketches, the index (sorted entries, distinct keys, counts,
+ *     starts, hash table), the anchor count of every query minimizer and its 64-bit exclusive scan.  Everything whose size
+ *     depends on the anchors exists per batch of consecutive query records (a group never spans two query records, and rule 8
+ *     orders by query record first, so the batches' lines one behind the other are the PAF of the whole input): the anchors
+ *     and their sort buffers, the groups, classes and lists, f, pred, the sort keys, the chains with their table and, in
+ *     exact mode, the segment pairs, their distances and the oriented copies of the batch's query records (2 * their bases).
+ *     msgpu_map_batch_bytes(params, anchors, query bases) bounds the device bytes of a batch.  The cut is greedy: with a(r),
+ *     b(r) the anchors and bases of query record r, a batch starts at the first record not yet taken and takes consecutive
+ *     records while msgpu_map_batch_bytes(params, sum a, sum b) <= budget and sum a < 2^31; it holds at least one record;
+ *     records without anchors join the running batch; no query records, no batches.  budget_bytes > 0 is the budget of a
+ *     batch (the resident part is not counted); 0 stands for the free device memory once the resident part is allocated (an
+ *     eighth less, again and again, while the device cannot give the largest batch's bytes as one block).  A
+ *     record that exceeds the budget on its own is MSGPU_E_NOMEM, one with 2^31 anchors or more MSGPU_E_ARG, naming the
+ *     record, its anchors and the bytes against the budget.  Splitting one query record over ranges of targets, and
+ *     splitting the index, are out of scope. */
 typedef struct msgpu_mapctx msgpu_mapctx; /* a device context of the stage */
 typedef struct msgpu_map_result msgpu_map_result;
 typedef struct msgpu_map_params {
@@ -1189,12 +1203,25 @@ typedef struct msgpu_map_stats {
   float host_ms;                    /* host: the lines (wall) */
   float wall_ms;
 } msgpu_map_stats;
-/* The whole stage.  With ava, queries_path is NULL or the targets' path.  flags must be 0; budget_bytes is ignored (rule 9).
- * Synchronous; the PAF is kept in the result. */
+/* An upper bound on the device bytes that a batch of rule 9 with n_anchors anchors and n_query_bases bases of query records
+ * allocates: a constant plus a multiple of each argument; n_query_bases counts only when params->exact is set.  A host
+ * function without any device call. */
+uint64_t    msgpu_map_batch_bytes(const msgpu_map_params *params, uint64_t n_anchors, uint64_t n_query_bases);
+typedef struct msgpu_map_batch { /* a batch of rule 9 */
+  uint32_t first_query, n_queries; /* consecutive query records */
+  uint64_t n_anchors, n_query_bases;
+  uint64_t n_groups, n_chains, n_pairs;
+  uint64_t bytes_bound; /* msgpu_map_batch_bytes of this batch */
+  uint64_t bytes_peak;  /* the most bytes the batch held at once */
+} msgpu_map_batch;
+/* The whole stage.  With ava, queries_path is NULL or the targets' path.  flags must be 0; budget_bytes bounds the bytes of a
+ * batch, 0 = the free device memory (rule 9).  Synchronous; the PAF is kept in the result. */
 int         msgpu_map_run(msgpu_mapctx *ctx, const msgpu_map_params *params, const char *targets_path, const char *queries_path,
                           uint32_t flags, uint64_t budget_bytes, msgpu_map_result **out);
 int         msgpu_map_result_stats(const msgpu_map_result *r, msgpu_map_stats *out);
 int         msgpu_map_result_chains(const msgpu_map_result *r, const msgpu_map_chain **chains, uint64_t *n);
+int         msgpu_map_result_batches(const msgpu_map_result *r, const msgpu_map_batch **batches, uint64_t *n); /* in order */
+uint64_t    msgpu_map_result_budget(const msgpu_map_result *r); /* the budget of a batch in bytes: budget_bytes, or what 0 stood for */
 const char *msgpu_map_result_text(const msgpu_map_result *r, uint64_t *len);
 void        msgpu_map_result_free(msgpu_map_result *r);
 

@@ -218,6 +218,11 @@ class MapStats(C.Structure):  # msgpu_map_stats
                 [("reserved", C.c_uint32)])
 
 
+class MapBatch(C.Structure):  # msgpu_map_batch
+    _fields_ = [("first_query", C.c_uint32), ("n_queries", C.c_uint32)] + [
+        (n, C.c_uint64) for n in ("n_anchors", "n_query_bases", "n_groups", "n_chains", "n_pairs", "bytes_bound", "bytes_peak")]
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -455,6 +460,9 @@ SYMBOLS = [
                                 C.POINTER(C.c_void_p)]),
     ("msgpu_map_result_stats", C.c_int, [C.c_void_p, C.POINTER(MapStats)]),
     ("msgpu_map_result_chains", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapChain)), C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_batches", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapBatch)), C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_budget", C.c_uint64, [C.c_void_p]),
+    ("msgpu_map_batch_bytes", C.c_uint64, [C.POINTER(MapParams), C.c_uint64, C.c_uint64]),
     ("msgpu_map_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msgpu_map_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),

@@ -7,6 +7,9 @@
 //                  position decides rule 2 from its 2 w - 1 neighbours.  Pass 1 counts per tile, pass 2 writes
 //   index          one radix_sort_pairs over bits [0, 2k), run lengths and starts of the keys, k_kf_table over the
 //                  distinct keys; the occurrence cap is applied where a query minimizer looks its key up
+//   batches        rule 9: the index and the anchor counts stay, the query records go through everything below in batches
+//                  under a budget of device bytes (mp_batch_bytes, mp_cut, mp_batch); k_mp_prefix gives the anchors in
+//                  front of every query record, one reserved arena serves every batch
 //   k_mp_anchors   count per query minimizer, exclusive scan, expansion; two stable radix sorts bring the anchors into
 //                  (group, x, y) order; run lengths of the group keys are the groups; k_mp_classify applies rule 6's
 //                  pre-filter and splits the kept groups into those of at most 16 anchors and the others
@@ -139,13 +142,14 @@ struct MpIndex {
   const uint64_t *vals;   // the entries in key order
 };
 
-// rule 4.  WRITE = false: anchors per query minimizer
+// rule 4 for the query minimizers [m0, m1).  WRITE = false: anchors per query minimizer; WRITE = true: the anchors, from
+// slot 0 for the first anchor of minimizer m0 (off: the anchors in front of every minimizer of the file)
 template <bool WRITE>
-__global__ __launch_bounds__(256) void k_mp_anchors(MpIndex X, const uint64_t *qkeys, const uint64_t *qvals, uint64_t nq,
+__global__ __launch_bounds__(256) void k_mp_anchors(MpIndex X, const uint64_t *qkeys, const uint64_t *qvals, uint64_t m0, uint64_t m1,
                                                     const uint32_t *qlen, int k, int ava, uint32_t *cnt, const uint64_t *off,
                                                     uint64_t *g, uint64_t *xy, uint64_t cap) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= nq) return;
+  const uint64_t i = m0 + static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= m1) return;
   const uint32_t j = kf_find(X.ukeys, X.slots, X.mask, qkeys[i]);
   uint32_t       c = 0;
   if (j != KF_EMPTY && X.ucnt[j] <= X.max_occ) {
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(256) void k_mp_anchors(MpIndex X, const uint64_t *q
         if (WRITE) {
           const uint32_t s = qs ^ static_cast<uint32_t>(tv & 1u), x = static_cast<uint32_t>(tv & 0xffffffffu) >> 1;
           const uint32_t y = s ? qlen[q] - static_cast<uint32_t>(k) - qpos : qpos;
-          const uint64_t slot = off[i] + c;
+          const uint64_t slot = off[i] - off[m0] + c;
           if (slot < cap) {
             g[slot]  = (static_cast<uint64_t>(q) << 32) | (static_cast<uint64_t>(t) << 1) | s;
             xy[slot] = (static_cast<uint64_t>(x) << 32) | y;
@@ -172,6 +176,22 @@ __global__ __launch_bounds__(256) void k_mp_anchors(MpIndex X, const uint64_t *q
       }
   }
   if (!WRITE) cnt[i] = c;
+}
+
+// rule 9's prefixes, a thread per query record r <= n_rec: the record's first minimizer (a lower bound: the record index is in
+// the top 32 bits of vals, and vals ascend) and the anchors in front of it
+__global__ __launch_bounds__(256) void k_mp_prefix(const uint64_t *qvals, uint64_t nq, const uint64_t *aoff, uint32_t n_rec,
+                                                   uint64_t *first_min, uint64_t *anchors_before) {
+  const uint64_t r = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (r > n_rec) return;
+  uint64_t lo = 0, hi = nq;
+  while (lo < hi) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if ((qvals[mid] >> 32) < r) lo = mid + 1;
+    else hi = mid;
+  }
+  first_min[r]      = lo;
+  anchors_before[r] = aoff[lo];
 }
 
 // rule 6's pre-filter and the size classes
@@ -432,15 +452,17 @@ __global__ __launch_bounds__(256) void k_mp_table(const uint32_t *list_kept, uin
   }
 }
 
-// exact mode: the segment pairs of every emitted chain, from its last link to its first
+// exact mode: the segment pairs of every emitted chain, from its last link to its first.  The targets lie in their store
+// (toff); the batch's query records lie one behind the other in its oriented buffer, the first at 0 (qpre: the bases in front
+// of every query record of the file, q_base: in front of the batch's first), the reverse complements rc_base further on
 __global__ __launch_bounds__(256) void k_mp_pairs(const msgpu_map_chain *chains, const MpWhere *where, uint32_t n_chains, const uint64_t *xy,
-                                                  const int32_t *pred, const uint32_t *pair_off, const uint64_t *toff, const uint64_t *qoff,
-                                                  uint64_t rc_base, int k, msgpu_align_pair *pairs, uint32_t cap) {
+                                                  const int32_t *pred, const uint32_t *pair_off, const uint64_t *toff, const uint64_t *qpre,
+                                                  uint64_t q_base, uint64_t rc_base, int k, msgpu_align_pair *pairs, uint32_t cap) {
   const uint32_t ci = blockIdx.x * 256 + threadIdx.x;
   if (ci >= n_chains) return;
   const msgpu_map_chain c = chains[ci];
   const uint32_t        s0 = where[ci].s0;
-  const uint64_t        ta = toff[c.target], qa = qoff[c.query] + (c.strand ? rc_base : 0);
+  const uint64_t        ta = toff[c.target], qa = qpre[c.query] - q_base + (c.strand ? rc_base : 0);
   uint32_t              at = pair_off[ci], cur = where[ci].first;
   for (uint32_t l = 1; l < c.n_anchors; ++l) {
     if (pred[s0 + cur] < 0) break; // (a chain of n_anchors has n_anchors - 1 links)
@@ -485,6 +507,8 @@ struct msgpu_mapctx : msgpu::StageCtx {
 struct msgpu_map_result {
   msgpu_map_stats              stats{};
   std::vector<msgpu_map_chain> chains;
+  std::vector<msgpu_map_batch> batches; // rule 9's cut, in order
+  uint64_t                     budget = 0; // the bytes a batch had: budget_bytes, or what it stood for
   std::string                  text;
 };
 
@@ -537,7 +561,8 @@ int mp_load(msgpu_mapctx *c, DevArena &D, const char *path, int kind, const char
     return MSGPU_E_ARG;
   }
   STAGE_HIP(c, D.get(&F.d_off, n));
-  STAGE_HIP(c, D.get(&F.d_len, n));
+  STAGE_HIP(c, D.get(&F.d_len, n + 1ull)); // (a zero behind the lengths: their scan gives n + 1 sums)
+  STAGE_HIP(c, hipMemsetAsync(F.d_len + n, 0, 4, c->stream));
   if (n) {
     STAGE_HIP(c, hipMemcpyAsync(F.d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
     STAGE_HIP(c, hipMemcpyAsync(F.d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
@@ -607,7 +632,299 @@ void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_se
   out += '\n';
 }
 
-int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, const char *qpath, msgpu_map_result *res) {
+// ---- rule 9: the bytes of a batch and the cut
+
+// What mp_batch takes from its reserved arena for A anchors and B query bases, allocation by allocation.  Groups, kept
+// groups, chains and segment pairs are each at most the anchors (a chain holds an anchor that no other chain holds, and a
+// chain of m anchors has m - 1 links).
+constexpr uint64_t MP_BYTES_ANCHOR = 4 * 8           // g and xy, twice each: the grouping sorts go from one to the other; the
+                                                     // second pair carries the sort keys of rule 6 afterwards
+                                     + 8 + 2 * 4     // ug, gcnt, gstart
+                                     + 9 * 4         // the class flags, their scans and the five lists
+                                     + 2 * 4 + 1     // f, pred, used
+                                     + sizeof(MpRaw) // raw
+                                     + 2 * 4         // emit, coff
+                                     + sizeof(msgpu_map_chain) + sizeof(MpWhere) + 2 * 4; // the chain table, where, np, poff
+constexpr uint64_t MP_BYTES_ANCHOR_EXACT = sizeof(msgpu_align_pair) + 4 + 4;              // pairs, dist, nm
+// The rocPRIM temporary, one buffer that the largest call sizes.  That call is radix_sort_pairs on separate input and output
+// arrays: it keeps a second copy of the keys and of the values (2 * 8 bytes per anchor) and, per block of the one-sweep
+// kernel, 256 look-back words of 4 bytes; a block sorts at least 256 items, so that is at most 4 bytes per anchor.
+// segmented_radix_sort_keys keeps one copy of the keys and two segment indices per segment (8 + 2 * 4), run_length_encode,
+// the scans and segmented_reduce keep a few words per block.  24 bytes per anchor cover the largest, and the fixed part
+// (digit histograms of 8 places * 256 * 8 bytes, the merge sort's and the partitioner's block states) stays far below 1 MiB.
+constexpr uint64_t MP_BYTES_ANCHOR_TMP = 24, MP_BYTES_TMP_FIXED = 1ull << 20;
+// every allocation is rounded up to DevArena::ALIGN (fewer than 64 of them per batch), the arrays with one more word than
+// items, the oriented copies' 16 bytes of slack
+constexpr uint64_t MP_BYTES_FIXED = MP_BYTES_TMP_FIXED + 64 * DevArena::ALIGN + 64 * 8;
+static_assert(sizeof(MpRaw) == 28 && sizeof(MpWhere) == 8 && sizeof(msgpu_align_pair) == 24, "rule 9's bytes per anchor");
+
+uint64_t mp_batch_bytes(bool exact, uint64_t n_anchors, uint64_t n_query_bases) {
+  const uint64_t per = MP_BYTES_ANCHOR + MP_BYTES_ANCHOR_TMP + (exact ? MP_BYTES_ANCHOR_EXACT : 0);
+  if (n_anchors >= (1ull << 54) || n_query_bases >= (1ull << 62)) return ~0ull; // (beyond every device; no overflow)
+  return MP_BYTES_FIXED + per * n_anchors + (exact ? 2 * n_query_bases : 0);
+}
+
+// The greedy cut of rule 9 over the prefix sums of the records' anchors and bases (n + 1 entries each): a binary search per
+// batch for the last record that still fits.  Returns the first record that fits no batch on its own, or n.
+uint32_t mp_cut(bool exact, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
+  for (uint32_t first = 0; first < n;) {
+    auto fits = [&](uint32_t end) {
+      const uint64_t a = apre[end] - apre[first];
+      return a < (1ull << 31) && mp_batch_bytes(exact, a, bpre[end] - bpre[first]) <= budget;
+    };
+    if (!fits(first + 1)) return first;
+    uint32_t lo = first + 1, hi = n; // the last end that fits
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo + 1) >> 1);
+      if (fits(mid)) lo = mid;
+      else hi = mid - 1;
+    }
+    msgpu_map_batch b{};
+    b.first_query   = first;
+    b.n_queries     = lo - first;
+    b.n_anchors     = apre[lo] - apre[first];
+    b.n_query_bases = bpre[lo] - bpre[first];
+    b.bytes_bound   = mp_batch_bytes(exact, b.n_anchors, b.n_query_bases);
+    out.push_back(b);
+    first = lo;
+  }
+  return n;
+}
+
+struct MpRun { // what stays on the device for the whole run (rule 9), as a batch sees it
+  msgpu_mapctx           *c;
+  const msgpu_map_params &prm;
+  const MpFile           &Tf, &Qf;
+  const MpSketch         &Qs;
+  MpIndex                 X;
+  const uint64_t         *d_aoff; // the anchors in front of every query minimizer
+  const uint64_t         *d_bpre; // the bases in front of every query record
+  const uint64_t         *first_min, *bpre; // on the host: every query record's first minimizer, and d_bpre
+  uint32_t               *d_nruns;
+  kf_ull                 *d_hist; // 32 bins, summed over the batches
+  StageClock             &clock;
+  msgpu_map_result       *res;
+};
+
+// rules 4 to 8 for the query records of one batch.  Every array is taken from the reserved arena B and indexed from the
+// batch's first anchor; the record indices in g and in the chain table are the file's.  The counters of the scalar block
+// and the histogram are sums (the largest group: a maximum) over the batches so far: nothing resets them.
+int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
+  msgpu_mapctx           *c = R.c;
+  const msgpu_map_params &prm = R.prm;
+  msgpu_map_stats        &S = R.res->stats;
+  StageClock             &clock = R.clock;
+  hipStream_t             st = c->stream;
+  const int               k = prm.k;
+  const bool              exact = prm.exact != 0;
+  const uint32_t          A = static_cast<uint32_t>(bt.n_anchors), q0 = bt.first_query, q1 = q0 + bt.n_queries;
+  const uint64_t          m0 = R.first_min[q0], m1 = R.first_min[q1];
+  int                     rc;
+  B.rewind();
+  if (!A) return MSGPU_OK;
+  if (getenv("MSGPU_POISON")) STAGE_HIP(c, hipMemsetAsync(B.pool, 0xA5, B.pool_bytes, st)); // (see DevBuf::ensure in msgpu_api.hip)
+
+  // ---- rule 4: expand, two stable sorts
+  uint64_t *d_g[2], *d_xy[2], *d_ug;
+  uint32_t *d_gcnt, *d_gstart;
+  for (int i = 0; i < 2; ++i) {
+    STAGE_HIP(c, B.get(&d_g[i], A));
+    STAGE_HIP(c, B.get(&d_xy[i], A));
+  }
+  STAGE_HIP(c, B.get(&d_ug, A));
+  STAGE_HIP(c, B.get(&d_gcnt, A + 1ull));
+  STAGE_HIP(c, B.get(&d_gstart, A + 1ull));
+  STAGE_HIP(c, clock.begin(&S.anchors_ms));
+  hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(m1 - m0)), dim3(256), 0, st, R.X, R.Qs.keys, R.Qs.vals, m0, m1, R.Qf.d_len, k, prm.ava,
+                     nullptr, R.d_aoff, d_g[0], d_xy[0], A);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, clock.begin(&S.group_ms));
+  STAGE_HIP(c, stage_sort_pairs(B, st, d_xy[0], d_xy[1], d_g[0], d_g[1], A)); // by (x, y)
+  STAGE_HIP(c, stage_sort_pairs(B, st, d_g[1], d_g[0], d_xy[1], d_xy[0], A)); // then, stable, by group
+  STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+    return rocprim::run_length_encode(tmp, bytes, d_g[0], A, d_ug, d_gcnt, R.d_nruns, st);
+  }));
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, R.d_nruns);
+  STAGE_HIP(c, clock.end());
+  rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t G = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+  STAGE_HIP(c, hipMemsetAsync(d_gcnt + G, 0, 4, st));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_gcnt, d_gstart, G + 1ull));
+  bt.n_groups = G;
+  S.n_groups += G;
+  const uint64_t *d_xys = d_xy[0];
+  uint64_t       *d_sk[2] = {d_g[1], d_xy[1]}; // (free behind the sorts) rule 6's sort keys
+
+  // ---- rule 6's pre-filter, the size classes
+  uint32_t *d_fs, *d_fl, *d_ps, *d_pl, *d_ls, *d_ll, *d_lk, *d_sb, *d_se;
+  for (uint32_t **p : {&d_fs, &d_fl, &d_ps, &d_pl}) STAGE_HIP(c, B.get(p, G + 1ull));
+  for (uint32_t **p : {&d_ls, &d_ll, &d_lk, &d_sb, &d_se}) STAGE_HIP(c, B.get(p, G));
+  STAGE_HIP(c, hipMemsetAsync(d_fs + G, 0, 4, st));
+  STAGE_HIP(c, hipMemsetAsync(d_fl + G, 0, 4, st));
+  STAGE_HIP(c, clock.begin(&S.group_ms));
+  hipLaunchKernelGGL(k_mp_classify, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, G, k, prm.min_score, prm.min_count, d_fs, d_fl, R.d_hist,
+                     mp_slot(c, MP_SC_LARGEST));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fs, d_ps, G + 1ull));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fl, d_pl, G + 1ull));
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_ps + G);
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL3, d_pl + G);
+  hipLaunchKernelGGL(k_mp_lists, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, d_gstart, G, d_fs, d_fl, d_ps, d_pl, d_ls, d_ll, d_lk, d_sb, d_se);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t n_small = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]), n_large = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
+  const uint32_t n_kept = n_small + n_large;
+  S.n_groups_small += n_small;
+  S.n_groups_large += n_large;
+  S.n_groups_kept += n_kept;
+  S.largest_group = c->sc.h[MP_SC_LARGEST];
+  if (S.largest_group * static_cast<uint64_t>(k) >= (1ull << 31)) {
+    snprintf(c->err, sizeof(c->err), "a group of %llu anchors: its scores do not fit 31 bits at k = %d", static_cast<kf_ull>(S.largest_group), k);
+    return MSGPU_E_ARG;
+  }
+
+  // ---- rule 5
+  int32_t  *d_f, *d_pred;
+  uint8_t  *d_used;
+  MpRaw    *d_raw;
+  uint32_t *d_emit, *d_coff;
+  STAGE_HIP(c, B.get(&d_f, A));
+  STAGE_HIP(c, B.get(&d_pred, A));
+  STAGE_HIP(c, B.get(&d_used, A));
+  STAGE_HIP(c, B.get(&d_raw, A));
+  STAGE_HIP(c, B.get(&d_emit, n_kept + 1ull));
+  STAGE_HIP(c, B.get(&d_coff, n_kept + 1ull));
+  STAGE_HIP(c, hipMemsetAsync(d_used, 0, A, st));
+  STAGE_HIP(c, hipMemsetAsync(d_emit, 0, (n_kept + 1ull) * 4, st));
+  MpChainArgs ca{d_ll, n_large, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[0], k, prm.max_gap, prm.bandwidth};
+  STAGE_HIP(c, clock.begin(&S.chain_ms));
+  if (n_large) hipLaunchKernelGGL(k_mp_chain, dim3(grid_of(n_large, 4)), dim3(256), 0, st, ca);
+  ca.list   = d_ls;
+  ca.n_list = n_small;
+  if (n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(grid_of(n_small, 16)), dim3(256), 0, st, ca);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+
+  // ---- rule 6
+  uint32_t C_n = 0;
+  if (n_kept) {
+    STAGE_HIP(c, clock.begin(&S.backtrack_ms));
+    STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+      return rocprim::segmented_radix_sort_keys_desc(tmp, bytes, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st);
+    }));
+    hipLaunchKernelGGL(k_mp_walk, dim3(grid_of(n_kept, 64)), dim3(64), 0, st, d_lk, n_kept, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[1],
+                       d_used, k, prm.min_score, prm.min_count, d_raw, d_emit, mp_slot(c, MP_SC_DROP_SCORE), mp_slot(c, MP_SC_DROP_COUNT),
+                       mp_slot(c, MP_SC_CUT));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_emit, d_coff, n_kept + 1ull));
+    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_coff + n_kept);
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
+    if (rc != MSGPU_OK) return rc;
+    C_n = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+  }
+  bt.n_chains = C_n;
+  S.n_chains += C_n;
+  if (C_n) {
+    msgpu_map_chain *d_chains;
+    MpWhere         *d_where;
+    uint32_t        *d_np, *d_poff;
+    STAGE_HIP(c, B.get(&d_chains, C_n));
+    STAGE_HIP(c, B.get(&d_where, C_n));
+    STAGE_HIP(c, B.get(&d_np, C_n + 1ull));
+    STAGE_HIP(c, B.get(&d_poff, C_n + 1ull));
+    STAGE_HIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
+    STAGE_HIP(c, clock.begin(&S.backtrack_ms));
+    hipLaunchKernelGGL(k_mp_table, dim3(grid256(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
+                       R.Qf.d_len, k, d_chains, d_where, d_np, C_n);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+
+    // ---- rule 7 in exact mode
+    if (exact) {
+      STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_np, d_poff, C_n + 1ull));
+      hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_poff + C_n);
+      STAGE_HIP(c, hipGetLastError());
+      rc = c->sc.read(c);
+      if (rc != MSGPU_OK) return rc;
+      const uint32_t P = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]); // (fewer than the anchors)
+      bt.n_pairs = P;
+      S.n_pairs += P;
+      if (P) {
+        // the batch's query records as they are and reverse-complemented, one record behind the other, one copy behind the other
+        const uint64_t          NB = bt.n_query_bases, b0 = R.bpre[q0];
+        std::vector<msgpu_copy> pieces;
+        try {
+          pieces.reserve(2ull * bt.n_queries);
+          for (uint32_t i = q0; i < q1; ++i) {
+            const uint64_t o = msgpu_seq_offset(R.Qf.f, i), at = R.bpre[i] - b0;
+            const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(R.Qf.f, i));
+            pieces.push_back(msgpu_copy{o, at, L, 0});
+            pieces.push_back(msgpu_copy{o, NB + at, L, MSGPU_COPY_REVCOMP});
+          }
+        } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+        msgpu_gather_plan *plan = nullptr;
+        rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
+        if (rc != MSGPU_OK) {
+          snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
+          return rc;
+        }
+        struct FreePlan {
+          msgpu_gather_plan *p;
+          ~FreePlan() { msgpu_gather_plan_free(p); }
+        } free_plan{plan};
+        uint8_t          *d_or;
+        msgpu_align_pair *d_pairs;
+        uint32_t         *d_dist, *d_nm;
+        STAGE_HIP(c, B.get(&d_or, 2 * NB + 16));
+        STAGE_HIP(c, B.get(&d_pairs, P));
+        STAGE_HIP(c, B.get(&d_dist, P));
+        STAGE_HIP(c, B.get(&d_nm, C_n));
+        STAGE_HIP(c, clock.begin(&S.pairs_ms));
+        rc = msgpu_gather_run(c->seq, plan, d_or, 2 * NB + 16, st);
+        if (rc != MSGPU_OK) {
+          snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
+          return rc;
+        }
+        hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, R.Tf.d_off, R.d_bpre,
+                           b0, NB, k, d_pairs, P);
+        STAGE_HIP(c, hipGetLastError());
+        STAGE_HIP(c, clock.end());
+        STAGE_HIP(c, clock.begin(&S.distance_ms));
+        launch_edit_distance_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist);
+        STAGE_HIP(c, hipGetLastError());
+        STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+          return rocprim::segmented_reduce(tmp, bytes, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+        }));
+        hipLaunchKernelGGL(k_mp_capped, dim3(grid256(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
+        hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
+        STAGE_HIP(c, hipGetLastError());
+        STAGE_HIP(c, clock.end());
+        STAGE_HIP(c, hipStreamSynchronize(st)); // (the plan goes with this scope)
+      }
+    }
+
+    // ---- the batch's chain table behind those of the batches before it
+    const size_t have = R.res->chains.size();
+    try {
+      R.res->chains.resize(have + C_n);
+    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+    STAGE_HIP(c, clock.begin(&S.copy_ms));
+    STAGE_HIP(c, hipMemcpyAsync(R.res->chains.data() + have, d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, clock.end());
+  }
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  clock.collect();
+  bt.bytes_peak = B.peak;
+  return MSGPU_OK;
+}
+
+int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, const char *qpath, uint64_t budget_bytes,
+             msgpu_map_result *res) {
   msgpu_map_stats &S = res->stats;
   hipStream_t      st = c->stream;
   DevArena         D;
@@ -690,254 +1007,98 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   S.n_index_entries = NT;
   const MpIndex X{d_ukeys, d_ucnt, d_ustart, d_slots, sn - 1, prm.max_occ, d_ivals};
 
-  // ---- rule 4: count, scan, expand, two stable sorts
+  // ---- rule 4's counts: anchors per query minimizer and in front of it; anchors and bases in front of every query record
   const uint64_t NQ = Qs.n;
+  const uint32_t NR = Qf.recs.n;
   uint32_t      *d_acnt;
-  uint64_t      *d_aoff;
+  uint64_t      *d_aoff, *d_pre; // d_pre: NR + 1 words each of anchors in front, bases in front, first minimizer
+  kf_ull        *d_hist;
   STAGE_HIP(c, D.get(&d_acnt, NQ + 1));
   STAGE_HIP(c, D.get(&d_aoff, NQ + 1));
+  STAGE_HIP(c, D.get(&d_pre, 3 * (NR + 1ull)));
+  STAGE_HIP(c, D.get(&d_hist, 32));
+  STAGE_HIP(c, hipMemsetAsync(d_hist, 0, 32 * 8, st));
   STAGE_HIP(c, hipMemsetAsync(d_acnt + NQ, 0, 4, st));
   STAGE_HIP(c, clock.begin(&S.anchors_ms));
   if (NQ)
-    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, d_acnt,
+    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, 0, NQ, Qf.d_len, k, prm.ava, d_acnt,
                        nullptr, nullptr, nullptr, 0);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_acnt, d_aoff, NQ + 1));
-  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_aoff + NQ);
+  hipLaunchKernelGGL(k_mp_prefix, dim3(grid256(NR + 1ull)), dim3(256), 0, st, Qs.vals, NQ, d_aoff, NR, d_pre + 2 * (NR + 1ull), d_pre);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, Qf.d_len, d_pre + (NR + 1ull), NR + 1ull)); // (mp_load: a zero behind the lengths)
   STAGE_HIP(c, clock.end());
+  std::vector<uint64_t> pre;
+  try {
+    pre.resize(3 * (NR + 1ull));
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  STAGE_HIP(c, hipMemcpyAsync(pre.data(), d_pre, pre.size() * 8, hipMemcpyDeviceToHost, st));
   rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  D.drop_tmp();
   S.n_keys_dropped    = c->sc.h[MP_SC_DROPK];
   S.n_entries_dropped = c->sc.h[MP_SC_DROPE];
-  S.n_anchors         = c->sc.h[MP_SC_TOTAL];
-  if (S.n_anchors >= (1ull << 31)) {
-    snprintf(c->err, sizeof(c->err), "%llu anchors; the limit is 2^31 - 1", static_cast<kf_ull>(S.n_anchors));
-    return MSGPU_E_ARG;
-  }
-  const uint32_t A = static_cast<uint32_t>(S.n_anchors);
-  {
+  const uint64_t *apre = pre.data(), *bpre = apre + (NR + 1ull), *first_min = bpre + (NR + 1ull);
+  S.n_anchors = apre[NR];
+
+  // ---- rule 9: the budget, the cut, one reservation for the largest batch
+  uint64_t budget = budget_bytes;
+  if (!budget) {
     size_t free_b = 0, total_b = 0;
     STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t bytes = A * (4 * 8ull + 2 * 8 + 2 * 4 + 1 + 28 + 5 * 4) + (exact ? 2 * Qf.recs.n_bases : 0);
-    if (bytes > free_b) {
-      snprintf(c->err, sizeof(c->err), "%u anchors need about %llu bytes for sorting and chaining (%llu of them for the oriented copies "
-               "of the queries); %zu bytes of device memory are free", A, static_cast<kf_ull>(bytes),
-               static_cast<kf_ull>(exact ? 2 * Qf.recs.n_bases : 0), free_b);
+    budget = free_b;
+  }
+  DevArena B;
+  for (;;) {
+    res->budget = budget;
+    res->batches.clear();
+    const uint32_t bad = mp_cut(exact, apre, bpre, NR, budget, res->batches);
+    if (bad < NR) {
+      const uint64_t a = apre[bad + 1] - apre[bad], b = bpre[bad + 1] - bpre[bad];
+      if (a >= (1ull << 31)) {
+        snprintf(c->err, sizeof(c->err), "query record %u has %llu anchors; the limit of a batch is 2^31 - 1 (rule 9: a record is not split)",
+                 bad, static_cast<kf_ull>(a));
+        return MSGPU_E_ARG;
+      }
+      snprintf(c->err, sizeof(c->err), "query record %u with %llu anchors and %llu bases needs %llu bytes on its own (%llu of them for its "
+               "oriented copies); the budget of a batch is %llu bytes (rule 9: a record is not split)", bad, static_cast<kf_ull>(a),
+               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(exact, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
+               static_cast<kf_ull>(budget));
       return MSGPU_E_NOMEM;
     }
+    uint64_t reserve = 0;
+    for (const msgpu_map_batch &b : res->batches)
+      if (b.n_anchors) reserve = std::max(reserve, b.bytes_bound);
+    const hipError_t e = reserve ? B.reserve(reserve) : hipSuccess;
+    if (e == hipErrorOutOfMemory && !budget_bytes && budget > MP_BYTES_FIXED) {
+      // the free memory is not one block's: the budget that 0 stands for shrinks by an eighth until the reservation succeeds
+      (void)hipGetLastError();
+      budget -= budget / 8;
+      continue;
+    }
+    STAGE_HIP(c, e);
+    break;
   }
-  uint64_t *d_g[2], *d_xy[2], *d_ug;
-  uint32_t *d_gcnt, *d_gstart;
-  for (int i = 0; i < 2; ++i) {
-    STAGE_HIP(c, D.get(&d_g[i], A));
-    STAGE_HIP(c, D.get(&d_xy[i], A));
-  }
-  STAGE_HIP(c, D.get(&d_ug, A));
-  STAGE_HIP(c, D.get(&d_gcnt, A + 1ull));
-  STAGE_HIP(c, D.get(&d_gstart, A + 1ull));
-  uint32_t G = 0;
-  if (A) {
-    STAGE_HIP(c, clock.begin(&S.anchors_ms));
-    hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, NQ, Qf.d_len, k, prm.ava, nullptr,
-                       d_aoff, d_g[0], d_xy[0], A);
-    STAGE_HIP(c, hipGetLastError());
-    STAGE_HIP(c, clock.end());
-    STAGE_HIP(c, clock.begin(&S.group_ms));
-    STAGE_HIP(c, stage_sort_pairs(D, st, d_xy[0], d_xy[1], d_g[0], d_g[1], A)); // by (x, y)
-    STAGE_HIP(c, stage_sort_pairs(D, st, d_g[1], d_g[0], d_xy[1], d_xy[0], A)); // then, stable, by group
-    STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
-      return rocprim::run_length_encode(tmp, bytes, d_g[0], A, d_ug, d_gcnt, d_nruns, st);
-    }));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_nruns);
-    STAGE_HIP(c, clock.end());
-    rc = c->sc.read(c);
-    if (rc != MSGPU_OK) return rc;
-    G = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
-    D.drop_tmp();
-    STAGE_HIP(c, hipMemsetAsync(d_gcnt + G, 0, 4, st));
-    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_gcnt, d_gstart, G + 1ull));
-    STAGE_HIP(c, hipStreamSynchronize(st));
-  }
-  S.n_groups = G;
-  D.drop(d_g[1]);
-  D.drop(d_xy[1]);
-  D.drop(d_acnt);
-  D.drop(d_aoff);
-  const uint64_t *d_xys = d_xy[0];
 
-  // ---- rule 6's pre-filter, the size classes
-  uint32_t *d_fs, *d_fl, *d_ps, *d_pl, *d_ls, *d_ll, *d_lk, *d_sb, *d_se;
-  kf_ull   *d_hist;
-  for (uint32_t **p : {&d_fs, &d_fl, &d_ps, &d_pl}) STAGE_HIP(c, D.get(p, G + 1ull));
-  for (uint32_t **p : {&d_ls, &d_ll, &d_lk, &d_sb, &d_se}) STAGE_HIP(c, D.get(p, G));
-  STAGE_HIP(c, D.get(&d_hist, 32));
-  STAGE_HIP(c, hipMemsetAsync(d_hist, 0, 32 * 8, st));
-  STAGE_HIP(c, hipMemsetAsync(d_fs + G, 0, 4, st));
-  STAGE_HIP(c, hipMemsetAsync(d_fl + G, 0, 4, st));
-  STAGE_HIP(c, clock.begin(&S.group_ms));
-  if (G)
-    hipLaunchKernelGGL(k_mp_classify, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, G, k, prm.min_score, prm.min_count, d_fs, d_fl, d_hist,
-                       mp_slot(c, MP_SC_LARGEST));
-  STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_fs, d_ps, G + 1ull));
-  STAGE_HIP(c, hipStreamSynchronize(st));
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_fl, d_pl, G + 1ull));
-  STAGE_HIP(c, hipStreamSynchronize(st));
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_ps + G);
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL3, d_pl + G);
-  if (G) hipLaunchKernelGGL(k_mp_lists, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, d_gstart, G, d_fs, d_fl, d_ps, d_pl, d_ls, d_ll, d_lk, d_sb, d_se);
-  STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, clock.end());
+  // ---- rules 4 to 8, batch by batch
+  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, d_nruns, d_hist, clock, res};
+  for (msgpu_map_batch &b : res->batches) {
+    rc = mp_batch(run, B, b);
+    if (rc != MSGPU_OK) return rc;
+  }
   rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  const uint32_t n_small = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]), n_large = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
-  const uint32_t n_kept = n_small + n_large;
-  S.n_groups_small = n_small;
-  S.n_groups_large = n_large;
-  S.n_groups_kept  = n_kept;
-  S.largest_group  = c->sc.h[MP_SC_LARGEST];
-  if (S.largest_group * static_cast<uint64_t>(k) >= (1ull << 31)) {
-    snprintf(c->err, sizeof(c->err), "a group of %llu anchors: its scores do not fit 31 bits at k = %d", static_cast<kf_ull>(S.largest_group), k);
-    return MSGPU_E_ARG;
-  }
-
-  // ---- rule 5
-  int32_t  *d_f, *d_pred;
-  uint64_t *d_sk[2];
-  uint8_t  *d_used;
-  MpRaw    *d_raw;
-  uint32_t *d_emit, *d_coff;
-  STAGE_HIP(c, D.get(&d_f, A));
-  STAGE_HIP(c, D.get(&d_pred, A));
-  STAGE_HIP(c, D.get(&d_sk[0], A));
-  STAGE_HIP(c, D.get(&d_sk[1], A));
-  STAGE_HIP(c, D.get(&d_used, A));
-  STAGE_HIP(c, D.get(&d_raw, A));
-  STAGE_HIP(c, D.get(&d_emit, n_kept + 1ull));
-  STAGE_HIP(c, D.get(&d_coff, n_kept + 1ull));
-  STAGE_HIP(c, hipMemsetAsync(d_used, 0, A ? A : 1, st));
-  STAGE_HIP(c, hipMemsetAsync(d_emit, 0, (n_kept + 1ull) * 4, st));
-  MpChainArgs ca{d_ll, n_large, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[0], k, prm.max_gap, prm.bandwidth};
-  STAGE_HIP(c, clock.begin(&S.chain_ms));
-  if (n_large) hipLaunchKernelGGL(k_mp_chain, dim3(grid_of(n_large, 4)), dim3(256), 0, st, ca);
-  ca.list   = d_ls;
-  ca.n_list = n_small;
-  if (n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(grid_of(n_small, 16)), dim3(256), 0, st, ca);
-  STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, clock.end());
-
-  // ---- rule 6
-  uint32_t C_n = 0;
-  if (n_kept) {
-    STAGE_HIP(c, clock.begin(&S.backtrack_ms));
-    STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
-      return rocprim::segmented_radix_sort_keys_desc(tmp, bytes, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st);
-    }));
-    hipLaunchKernelGGL(k_mp_walk, dim3(grid_of(n_kept, 64)), dim3(64), 0, st, d_lk, n_kept, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[1],
-                       d_used, k, prm.min_score, prm.min_count, d_raw, d_emit, mp_slot(c, MP_SC_DROP_SCORE), mp_slot(c, MP_SC_DROP_COUNT),
-                       mp_slot(c, MP_SC_CUT));
-    STAGE_HIP(c, hipGetLastError());
-    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_emit, d_coff, n_kept + 1ull));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_coff + n_kept);
-    STAGE_HIP(c, clock.end());
-    rc = c->sc.read(c);
-    if (rc != MSGPU_OK) return rc;
-    C_n = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
-    D.drop_tmp();
-  }
-  S.n_chains               = C_n;
-  S.n_chains_below_score   = c->sc.h[MP_SC_DROP_SCORE];
-  S.n_chains_below_count   = c->sc.h[MP_SC_DROP_COUNT];
-  S.n_chains_cut           = c->sc.h[MP_SC_CUT];
-  msgpu_map_chain *d_chains;
-  MpWhere         *d_where;
-  uint32_t        *d_np, *d_poff;
-  STAGE_HIP(c, D.get(&d_chains, C_n));
-  STAGE_HIP(c, D.get(&d_where, C_n));
-  STAGE_HIP(c, D.get(&d_np, C_n + 1ull));
-  STAGE_HIP(c, D.get(&d_poff, C_n + 1ull));
-  STAGE_HIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
-  STAGE_HIP(c, clock.begin(&S.backtrack_ms));
-  if (C_n)
-    hipLaunchKernelGGL(k_mp_table, dim3(grid256(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
-                       Qf.d_len, k, d_chains, d_where, d_np, C_n);
-  STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, clock.end());
-
-  // ---- rule 7 in exact mode
-  if (exact && C_n) {
-    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_np, d_poff, C_n + 1ull));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_poff + C_n);
-    STAGE_HIP(c, hipGetLastError());
-    rc = c->sc.read(c);
-    if (rc != MSGPU_OK) return rc;
-    const uint32_t P = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]); // (fewer than the anchors)
-    S.n_pairs        = P;
-    if (P) {
-      // the queries as they are and reverse-complemented, one behind the other
-      const uint64_t          NB = Qf.recs.n_bases;
-      std::vector<msgpu_copy> pieces;
-      try {
-        pieces.reserve(2ull * Qf.recs.n);
-        for (uint32_t i = 0; i < Qf.recs.n; ++i) {
-          const uint64_t o = msgpu_seq_offset(Qf.f, i);
-          const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(Qf.f, i));
-          pieces.push_back(msgpu_copy{o, o, L, 0});
-          pieces.push_back(msgpu_copy{o, NB + o, L, MSGPU_COPY_REVCOMP});
-        }
-      } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-      msgpu_gather_plan *plan = nullptr;
-      rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
-      if (rc != MSGPU_OK) {
-        snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
-        return rc;
-      }
-      struct FreePlan {
-        msgpu_gather_plan *p;
-        ~FreePlan() { msgpu_gather_plan_free(p); }
-      } free_plan{plan};
-      uint8_t          *d_or;
-      msgpu_align_pair *d_pairs;
-      uint32_t         *d_dist, *d_nm;
-      STAGE_HIP(c, D.get(&d_or, 2 * NB + 16));
-      STAGE_HIP(c, D.get(&d_pairs, P));
-      STAGE_HIP(c, D.get(&d_dist, P));
-      STAGE_HIP(c, D.get(&d_nm, C_n));
-      STAGE_HIP(c, clock.begin(&S.pairs_ms));
-      rc = msgpu_gather_run(c->seq, plan, d_or, 2 * NB + 16, st);
-      if (rc != MSGPU_OK) {
-        snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
-        return rc;
-      }
-      hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, Tf.d_off, Qf.d_off,
-                         NB, k, d_pairs, P);
-      STAGE_HIP(c, hipGetLastError());
-      STAGE_HIP(c, clock.end());
-      STAGE_HIP(c, clock.begin(&S.distance_ms));
-      launch_edit_distance_pairs(st, Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist);
-      STAGE_HIP(c, hipGetLastError());
-      STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
-        return rocprim::segmented_reduce(tmp, bytes, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
-      }));
-      hipLaunchKernelGGL(k_mp_capped, dim3(grid256(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
-      hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
-      STAGE_HIP(c, hipGetLastError());
-      STAGE_HIP(c, clock.end());
-      rc = c->sc.read(c);
-      if (rc != MSGPU_OK) return rc;
-      S.n_pairs_capped = c->sc.h[MP_SC_CAPPED];
-    }
-  }
+  S.n_chains_below_score = c->sc.h[MP_SC_DROP_SCORE];
+  S.n_chains_below_count = c->sc.h[MP_SC_DROP_COUNT];
+  S.n_chains_cut         = c->sc.h[MP_SC_CUT];
+  S.n_pairs_capped       = c->sc.h[MP_SC_CAPPED];
+  const uint64_t C_n     = res->chains.size();
 
   // ---- the figures come back; the host formats the lines
   kf_ull hist[32];
-  try {
-    res->chains.resize(C_n);
-  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  STAGE_HIP(c, clock.begin(&S.copy_ms));
-  if (C_n) STAGE_HIP(c, hipMemcpyAsync(res->chains.data(), d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
   STAGE_HIP(c, hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
-  STAGE_HIP(c, clock.end());
   STAGE_HIP(c, hipStreamSynchronize(st));
   clock.collect();
   for (int i = 0; i < 32; ++i) S.group_hist[i < 15 ? i : 15] += hist[i];
@@ -972,6 +1133,10 @@ void msgpu_map_default_params(msgpu_map_params *p) {
   *p = msgpu_map_params{15, 5, 200, 10000, 2000, 64, 100, 3, 0, 64, 0, 0};
 }
 
+uint64_t msgpu_map_batch_bytes(const msgpu_map_params *p, uint64_t n_anchors, uint64_t n_query_bases) {
+  return mp_batch_bytes(p && p->exact, n_anchors, n_query_bases);
+}
+
 int  msgpu_map_create(int device, msgpu_mapctx **out) { return stage_create(device, out); }
 void msgpu_map_destroy(msgpu_mapctx *c) { stage_destroy(c); }
 
@@ -983,7 +1148,6 @@ int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *t
   *out      = nullptr;
   c->err[0] = 0;
   if (!params || !targets_path || flags) return MSGPU_E_ARG;
-  (void)budget_bytes; // nothing is partitioned: rule 9
   const msgpu_map_params p = *params;
   if (p.k < 4 || p.k > 32 || p.w < 1 || p.w > 64 || p.max_occ < 1 || p.max_gap < 0 || p.bandwidth < 0 || p.max_pred != 64 ||
       p.band < 1 || p.band > 127 || (p.exact != 0 && p.exact != 1) || (p.ava != 0 && p.ava != 1)) {
@@ -1002,7 +1166,7 @@ int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *t
     res.reset(new msgpu_map_result());
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   const uint64_t lost0 = c->sc.lost;
-  const int      rc = mp_stage(c, p, targets_path, queries_path, res.get());
+  const int      rc = mp_stage(c, p, targets_path, queries_path, budget_bytes, res.get());
   if (rc != MSGPU_OK) {
     (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -1025,6 +1189,15 @@ int msgpu_map_result_chains(const msgpu_map_result *r, const msgpu_map_chain **c
   *n      = r->chains.size();
   return MSGPU_OK;
 }
+
+int msgpu_map_result_batches(const msgpu_map_result *r, const msgpu_map_batch **batches, uint64_t *n) {
+  if (!r || !batches || !n) return MSGPU_E_ARG;
+  *batches = r->batches.data();
+  *n       = r->batches.size();
+  return MSGPU_OK;
+}
+
+uint64_t msgpu_map_result_budget(const msgpu_map_result *r) { return r ? r->budget : 0; }
 
 const char *msgpu_map_result_text(const msgpu_map_result *r, uint64_t *len) {
   if (len) *len = r ? r->text.size() : 0;

@@ -94,25 +94,73 @@ struct SeqFileHold { // a parsed sequence file, freed on every way out
 
 struct DevArena { // device memory freed on every way out of a run
   std::vector<void *> p;
+  std::vector<size_t> p_bytes;       // the size of every block of p
   void               *tmp = nullptr; // one temporary buffer for every rocPRIM call of the run, grown when a call needs more
   size_t              tmp_bytes = 0;
+  size_t              live = 0, peak = 0; // the bytes held now, and the most that were held at once (since the last rewind())
+  // A reserved arena (reserve()) holds one block and hands out its bytes instead of calling hipMalloc: get() takes them from
+  // the front, 256-byte aligned, the temporary buffer lies at the back and grows towards the front, and rewind() gives
+  // everything back at once.  A stage that runs in batches reserves the largest batch's bytes once: no hipMalloc and no
+  // hipFree (which synchronises the device) per batch, and `peak` is what a batch really touched.
+  uint8_t *pool = nullptr;
+  size_t   pool_bytes = 0, pool_used = 0;
+  static constexpr size_t ALIGN = 256;
+  static size_t           aligned(size_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
   ~DevArena() {
     for (void *x : p) (void)hipFree(x);
+    if (pool) (void)hipFree(pool);
+  }
+  void hold(size_t n) {
+    live += n;
+    peak = std::max(peak, live);
+  }
+  hipError_t reserve(size_t n) { // once, on an arena that holds nothing
+    pool_bytes = aligned(n ? n : 1);
+    return hipMalloc(reinterpret_cast<void **>(&pool), pool_bytes);
+  }
+  void rewind() { // (after a synchronisation) a reserved arena as it was after reserve()
+    pool_used = tmp_bytes = live = peak = 0;
+    tmp = nullptr;
   }
   template <class T> hipError_t get(T **out, size_t count) {
+    const size_t n = (count ? count : 1) * sizeof(T);
+    if (pool) {
+      *out = nullptr;
+      if (aligned(n) > pool_bytes - pool_used - tmp_bytes) return hipErrorOutOfMemory;
+      *out = reinterpret_cast<T *>(pool + pool_used);
+      pool_used += aligned(n);
+      hold(aligned(n));
+      return hipSuccess;
+    }
     void      *m = nullptr;
-    hipError_t e = hipMalloc(&m, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(m);
+    hipError_t e = hipMalloc(&m, n);
+    if (e == hipSuccess) {
+      p.push_back(m);
+      p_bytes.push_back(n);
+      hold(n);
+    }
     *out = static_cast<T *>(m);
     return e;
   }
-  void drop(void *x) {
+  void drop(void *x) { // (not for the blocks of a reserved arena: rewind() returns those)
     auto it = std::find(p.begin(), p.end(), x);
-    if (it != p.end()) p.erase(it);
+    if (it != p.end()) {
+      live -= p_bytes[it - p.begin()];
+      p_bytes.erase(p_bytes.begin() + (it - p.begin()));
+      p.erase(it);
+    }
     (void)hipFree(x);
   }
   hipError_t room(size_t need) {
     if (tmp && need <= tmp_bytes) return hipSuccess;
+    if (pool) {
+      const size_t n = aligned(need ? need : 1);
+      if (n > pool_bytes - pool_used) return hipErrorOutOfMemory;
+      hold(n - tmp_bytes);
+      tmp       = pool + pool_bytes - n;
+      tmp_bytes = n;
+      return hipSuccess;
+    }
     uint8_t   *t = nullptr;
     hipError_t e = get(&t, need);
     if (e == hipSuccess) {
@@ -122,7 +170,8 @@ struct DevArena { // device memory freed on every way out of a run
     return e;
   }
   void drop_tmp() { // (after a synchronisation) a large temporary buffer that the rest of the run should not carry
-    drop(tmp);
+    if (pool) live -= tmp_bytes;
+    else drop(tmp);
     tmp       = nullptr;
     tmp_bytes = 0;
   }

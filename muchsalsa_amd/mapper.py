@@ -2,9 +2,10 @@
 write -- a PAF of every record of a query file against every record of a target file, by minimizer seeds and a chaining DP.
 
     python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--ava]
-            [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N]
+            [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
 
-prints one JSON line of counts and seconds.  With ``--ava`` the two paths name the same file (the reads against
+prints one JSON line of counts and seconds.  ``--budget-mb`` (N > 0) bounds the device memory of a batch of query records
+(rule 9; without it: the free device memory).  With ``--ava`` the two paths name the same file (the reads against
 themselves: the read-to-read PAF muchsalsa_amd.scrubber takes as its fourth input); ``--exact`` adds the base-level match
 count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call).  minimap2 is not needed, and it is not part of
 the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
@@ -47,9 +48,23 @@ tests' restatement in plain Python (tests/map_oracle.py), not against minimap2. 
  8. output: one line per chain: the twelve PAF columns ('+' / '-' in column 5, mapping quality 255), then cm:i:<anchors>,
     s1:i:<score> and, in exact mode, NM:i:<sum d_i>.  Lines are ordered by (query record, target record, strand, order of
     emission in the group).  On any error nothing is written.
- 9. limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs, at most 2^30
-    distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k below 2^31; everything resident together, otherwise MSGPU_E_NOMEM
-    naming the sizes.  Larger inputs are out of scope (no target batching).
+ 9. limits and batches.  Limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs
+    per batch, at most 2^30 distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k
+    below 2^31.  Resident for the whole run: both stores, both sketches, the index (sorted entries, distinct keys, counts,
+    starts, hash table), the anchor count of every query minimizer and its 64-bit exclusive scan.  Everything whose size
+    depends on the anchors exists per batch of consecutive query records (a group never spans two query records, and rule 8
+    orders by query record first, so the batches' lines one behind the other are the PAF of the whole input): the anchors
+    and their sort buffers, the groups, classes and lists, f, pred, the sort keys, the chains with their table and, in
+    exact mode, the segment pairs, their distances and the oriented copies of the batch's query records (2 * their bases).
+    msgpu_map_batch_bytes(params, anchors, query bases) bounds the device bytes of a batch.  The cut is greedy: with a(r),
+    b(r) the anchors and bases of query record r, a batch starts at the first record not yet taken and takes consecutive
+    records while msgpu_map_batch_bytes(params, sum a, sum b) <= budget and sum a < 2^31; it holds at least one record;
+    records without anchors join the running batch; no query records, no batches.  budget_bytes > 0 is the budget of a
+    batch (the resident part is not counted); 0 stands for the free device memory once the resident part is allocated (an
+    eighth less, again and again, while the device cannot give the largest batch's bytes as one block).  A
+    record that exceeds the budget on its own is MSGPU_E_NOMEM, one with 2^31 anchors or more MSGPU_E_ARG, naming the
+    record, its anchors and the bytes against the budget.  Splitting one query record over ranges of targets, and
+    splitting the index, are out of scope.
 
 Known differences from minimap2, none of which could be checked against the program (it is not installed where this project
 is built):
@@ -87,8 +102,10 @@ class MapError(StageError):
         super().__init__(code, detail=detail)
 
 
-def run(targets, queries, out, device=0, tables=None, timings=None, **params):
-    """The whole stage: writes ``out`` (nothing on an error); returns the counts.  ``params``: the names of DEFAULTS.  With
+def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, **params):
+    """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
+    per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
+    ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
     ava = 1, ``queries`` is None or ``targets``.  ``tables`` (a dict) receives ``chains``: per line of the PAF the tuple
     (query, target, strand, anchors, score, nm, q_start, q_end, t_start, t_end, matches, block) and ``text`` (bytes);
     ``timings`` (a dict) seconds per step."""
@@ -98,16 +115,22 @@ def run(targets, queries, out, device=0, tables=None, timings=None, **params):
     p = dict(DEFAULTS, **params)
     L = _lib.lib()
     t0 = time.perf_counter()
+    budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
     for name, v in p.items():
         if not -(1 << 31) <= int(v) < (1 << 31) or (name == "max_occ" and int(v) < 0):
             raise MapError(_lib.E_ARG, "%s = %d" % (name, int(v)))
     with stage_context("map", device, MapError) as stage:
         prm = _lib.MapParams(int(p["k"]), int(p["w"]), int(p["max_occ"]), int(p["max_gap"]), int(p["bandwidth"]), 64,
                              int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]), 0)
-        with stage.run(C.byref(prm), os.fsencode(targets), None if queries is None else os.fsencode(queries), 0, 0) as res:
+        with stage.run(C.byref(prm), os.fsencode(targets), None if queries is None else os.fsencode(queries), 0, budget) as res:
             st = _lib.MapStats()
             L.msgpu_map_result_stats(res, C.byref(st))
             text = text_view(L.msgpu_map_result_text, res)
+            bp = C.POINTER(_lib.MapBatch)()
+            m = C.c_uint64()
+            L.msgpu_map_result_batches(res, C.byref(bp), C.byref(m))
+            batches = [{f: int(getattr(bp[i], f)) for f, _ in _lib.MapBatch._fields_} for i in range(m.value)]
+            budget_used = int(L.msgpu_map_result_budget(res))
             if tables is not None:
                 cp = C.POINTER(_lib.MapChain)()
                 m = C.c_uint64()
@@ -130,7 +153,8 @@ def run(targets, queries, out, device=0, tables=None, timings=None, **params):
             "groups_large": int(st.n_groups_large), "largest_group": int(st.largest_group),
             "group_hist": [int(x) for x in st.group_hist], "chains": int(st.n_chains), "below_score": int(st.n_chains_below_score),
             "below_count": int(st.n_chains_below_count), "chains_cut": int(st.n_chains_cut), "pairs": int(st.n_pairs),
-            "capped": int(st.n_pairs_capped), "lost_publications": int(st.n_lost_publications), "bytes_out": int(st.bytes_out)}
+            "capped": int(st.n_pairs_capped), "lost_publications": int(st.n_lost_publications), "bytes_out": int(st.bytes_out),
+            "batches": batches, "budget_bytes": budget_used}
 
 
 _OPTS = {"-k": "k", "-w": "w", "--max-occ": "max_occ", "--min-score": "min_score", "--min-count": "min_count",
@@ -138,7 +162,7 @@ _OPTS = {"-k": "k", "-w": "w", "--max-occ": "max_occ", "--min-score": "min_score
 
 
 def main(argv):
-    args, p, ok = list(argv), {}, True
+    args, p, ok, budget = list(argv), {}, True, None
     for flag in ("--exact", "--ava"):
         if flag in args:
             args.remove(flag)
@@ -151,6 +175,14 @@ def main(argv):
             except (IndexError, ValueError):
                 ok = False
             del args[i:i + 2]
+    if "--budget-mb" in args:
+        i = args.index("--budget-mb")
+        try:
+            budget = float(args[i + 1])
+            ok = ok and 0 < budget < float("inf")
+        except (IndexError, ValueError):
+            ok = False
+        del args[i:i + 2]
     q = dict(DEFAULTS, **p)
     ok = ok and 4 <= q["k"] <= 32 and 1 <= q["w"] <= 64 and q["max_occ"] >= 1 and 1 <= q["band"] <= 127
     ok = ok and q["max_gap"] >= 0 and q["bandwidth"] >= 0 and not any(a.startswith("-") for a in args)
@@ -159,7 +191,7 @@ def main(argv):
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], timings=timings, **p)
+    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, **p)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0
