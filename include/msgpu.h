@@ -1003,6 +1003,21 @@ typedef struct msgpu_kf_stats {
  * 2^31 keys.  Synchronous; the outputs' text is kept in the result. */
 int         msgpu_kf_run(msgpu_kfctx *ctx, int k, const char *path_a, const char *path_b, uint32_t flags,
                          uint64_t budget_bytes, msgpu_kf_result **out);
+/* A short-read pair that stays in device memory: both files' bytes, their line starts, rule 1 checked --
+ * what msgpu_kf_run leaves on the device in front of its count.  It is opened through a filter context, which takes the
+ * error (msgpu_kf_last_error / _error_file / _error_line as after msgpu_kf_run; two files of different record counts are
+ * accepted here and are msgpu_kf_run_pair's MSGPU_E_FORMAT), lives on that context's device until msgpu_pair_close, and
+ * may outlive the context.  Runs read it and never write into it: any number of runs of the filter and of the unitig
+ * stage (msgpu_ug_run_pair), at any k and in any order, each give what the run by files gives.  A pair on another device
+ * than the running context's is MSGPU_E_ARG.  Budgets: a run on a pair counts the pair as resident -- "0 = what is free"
+ * is measured with the pair in place -- and sets nothing aside for outputs beyond what it writes itself (the filter: its
+ * two output texts; the unitig stage: nothing of the filter's).  msgpu_kf_run is msgpu_kf_open_pair, msgpu_kf_run_pair,
+ * msgpu_pair_close; load_ms and records_ms of a run on a pair are 0, msgpu_kf_run fills them from the opening. */
+typedef struct msgpu_pair msgpu_pair;
+int         msgpu_kf_open_pair(msgpu_kfctx *ctx, const char *path_a, const char *path_b, msgpu_pair **out);
+void        msgpu_pair_close(msgpu_pair *pair);
+int         msgpu_kf_run_pair(msgpu_kfctx *ctx, int k, const msgpu_pair *pair, uint32_t flags, uint64_t budget_bytes,
+                              msgpu_kf_result **out);
 int         msgpu_kf_result_stats(const msgpu_kf_result *r, msgpu_kf_stats *out);
 int         msgpu_kf_result_histogram(const msgpu_kf_result *r, const uint64_t **abundance, const uint64_t **frequency,
                                       uint64_t *n);
@@ -1048,7 +1063,12 @@ void        msgpu_kf_result_free(msgpu_kf_result *r);
  *     the pipeline's awk reads field 2).  Two texts: all records, and the records with length >= min_length, ids unchanged
  *     (the pipeline's ${NAME}-unitigs.l500.fa).
  *  7. limits, each an error and never a fault: fewer than 2^31 solid k-mers; the file limits of the k-mer filter; everything
- *     resident together, else MSGPU_E_NOMEM naming the sizes.  On any error nothing is produced. */
+ *     resident together, else MSGPU_E_NOMEM naming the sizes.  On any error nothing is produced.
+ *  8. the mask (msgpu_ug_run_pair): the stage on a pair with the mask m (a byte per pair, 1 = dropped, what
+ *     msgpu_kf_result_verdicts returns) gives the result of msgpu_ug_run on the two files that hold the records i with
+ *     m[i] = 0, in order: both texts, the unitig table, the rounds, n_windows, n_distinct, n_solid, n_solid_trimmed, the unitig
+ *     counts and longest_chain.  n_records and bytes_in are the pair's own.  A dropped pair's two reads have the length 0 for
+ *     every kernel that forms windows.  With a mask both files hold n_pairs records, else MSGPU_E_ARG. */
 typedef struct msgpu_ugctx msgpu_ugctx; /* a device context of the stage */
 typedef struct msgpu_ug_result msgpu_ug_result;
 typedef struct msgpu_ug_params {
@@ -1100,6 +1120,10 @@ typedef struct msgpu_ug_unitig { /* in output order: entry i is the unitig with 
  * msgpu_kf_run.  Synchronous; both texts are kept in the result. */
 int         msgpu_ug_run(msgpu_ugctx *ctx, const msgpu_ug_params *params, const char *path_a, const char *path_b, uint32_t flags,
                          uint64_t budget_bytes, msgpu_ug_result **out);
+/* The stage on a pair opened by msgpu_kf_open_pair (see there).  dropped: n_pairs bytes on the host, copied to the device
+ * once, or NULL to keep every record (n_pairs is then ignored); rule 8.  msgpu_ug_run is open, this, close. */
+int         msgpu_ug_run_pair(msgpu_ugctx *ctx, const msgpu_ug_params *params, const msgpu_pair *pair, const uint8_t *dropped,
+                              uint64_t n_pairs, uint32_t flags, uint64_t budget_bytes, msgpu_ug_result **out);
 int         msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out);
 int         msgpu_ug_result_rounds(const msgpu_ug_result *r, const msgpu_ug_round **rounds, uint64_t *n);
 int         msgpu_ug_result_unitigs(const msgpu_ug_result *r, const msgpu_ug_unitig **unitigs, uint64_t *n);
@@ -1152,8 +1176,9 @@ void        msgpu_ug_result_free(msgpu_ug_result *r);
  *     emission in the group).  On any error nothing is written.
  *  9. limits and batches.  Limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs
  *     per batch, at most 2^30 distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k
- *     below 2^31.  Resident for the whole run: both stores, both sketches, the index (sorted entries, distinct keys, counts,
- *     starts, hash table), the anchor count of every query minimizer and its 64-bit exclusive scan.  Everything whose size
+ *     below 2^31.  Resident while the index lives (msgpu_map_index): the target store, its sketch and the index (sorted
+ *     entries, distinct keys, counts, starts, hash table); resident for the whole run besides: the query store and sketch,
+ *     the anchor count of every query minimizer and its 64-bit exclusive scan.  Everything whose size
  *     depends on the anchors exists per batch of consecutive query records (a group never spans two query records, and rule 8
  *     orders by query record first, so the batches' lines one behind the other are the PAF of the whole input): the anchors
  *     and their sort buffers, the groups, classes and lists, f, pred, the sort keys, the chains with their table and, in
@@ -1218,6 +1243,35 @@ typedef struct msgpu_map_batch { /* a batch of rule 9 */
  * batch, 0 = the free device memory (rule 9).  Synchronous; the PAF is kept in the result. */
 int         msgpu_map_run(msgpu_mapctx *ctx, const msgpu_map_params *params, const char *targets_path, const char *queries_path,
                           uint32_t flags, uint64_t budget_bytes, msgpu_map_result **out);
+/* A mapper index that outlives a run: the target file in one of the context's two stores, the
+ * per-record offsets and lengths, the target sketch and the index of rule 3 -- everything of a run that depends on the
+ * targets, k and w alone.  Of params only k and w matter to msgpu_map_index_create.  The occurrence cap is applied at
+ * look-up, so max_occ, like every other parameter, may differ from run to run on one index; a run whose k or w differs
+ * from the index's is MSGPU_E_ARG naming both.  With ava, queries_path is NULL and the index's own store and sketch are the
+ * query side; otherwise the queries go into the context's other store, so exact mode works on an index, and the store the
+ * targets lie in does not matter to any result.  A context holds one index at a time: a second create before the free is
+ * MSGPU_E_STATE, an index of another context MSGPU_E_ARG.  A run reads the index and never writes into it: after any
+ * error of a run the index is as good as before.  Free the index before its context is destroyed (msgpu_map_destroy frees
+ * an index that is still held; it must not be freed again).
+ * Stats: n_records[0], n_bases[0], n_minimizers[0], n_keys and n_index_entries of a run come from the index; load_ms,
+ * sketch_ms, sort_ms and table_ms of a run on an index cover the query side only (table_ms: rule 3's count of the capped
+ * keys at the run's max_occ); the index reports the times of its own build; msgpu_map_run is create, run, free and adds
+ * the two, so its stats read as before. */
+typedef struct msgpu_map_index msgpu_map_index;
+typedef struct msgpu_map_istats {
+  uint64_t n_records, n_bases, n_minimizers, n_keys, n_index_entries;
+  int32_t  k, w;
+  float    load_ms;                       /* host wall: the file into its store */
+  float    sketch_ms, sort_ms, table_ms;  /* device, by events */
+  float    wall_ms;
+  uint32_t reserved;
+} msgpu_map_istats;
+int         msgpu_map_index_create(msgpu_mapctx *ctx, const msgpu_map_params *params, const char *targets_path,
+                                   msgpu_map_index **out);
+void        msgpu_map_index_free(msgpu_map_index *index);
+int         msgpu_map_index_stats(const msgpu_map_index *index, msgpu_map_istats *out);
+int         msgpu_map_run_index(msgpu_mapctx *ctx, const msgpu_map_params *params, const msgpu_map_index *index,
+                                const char *queries_path, uint32_t flags, uint64_t budget_bytes, msgpu_map_result **out);
 int         msgpu_map_result_stats(const msgpu_map_result *r, msgpu_map_stats *out);
 int         msgpu_map_result_chains(const msgpu_map_result *r, const msgpu_map_chain **chains, uint64_t *n);
 int         msgpu_map_result_batches(const msgpu_map_result *r, const msgpu_map_batch **batches, uint64_t *n); /* in order */

@@ -218,6 +218,12 @@ class MapStats(C.Structure):  # msgpu_map_stats
                 [("reserved", C.c_uint32)])
 
 
+class MapIndexStats(C.Structure):  # msgpu_map_istats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_records", "n_bases", "n_minimizers", "n_keys", "n_index_entries")] +
+                [("k", C.c_int32), ("w", C.c_int32)] +
+                [(n, C.c_float) for n in ("load_ms", "sketch_ms", "sort_ms", "table_ms", "wall_ms")] + [("reserved", C.c_uint32)])
+
+
 class MapBatch(C.Structure):  # msgpu_map_batch
     _fields_ = [("first_query", C.c_uint32), ("n_queries", C.c_uint32)] + [
         (n, C.c_uint64) for n in ("n_anchors", "n_query_bases", "n_groups", "n_chains", "n_pairs", "bytes_bound", "bytes_peak")]
@@ -432,6 +438,9 @@ SYMBOLS = [
     ("msgpu_kf_error_file", C.c_int, [C.c_void_p]),
     ("msgpu_kf_run", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
                                C.POINTER(C.c_void_p)]),
+    ("msgpu_kf_open_pair", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("msgpu_pair_close", None, [C.c_void_p]),
+    ("msgpu_kf_run_pair", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
     ("msgpu_kf_result_stats", C.c_int, [C.c_void_p, C.POINTER(KfStats)]),
     ("msgpu_kf_result_histogram", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)),
                                             C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]),
@@ -447,6 +456,8 @@ SYMBOLS = [
     ("msgpu_ug_error_file", C.c_int, [C.c_void_p]),
     ("msgpu_ug_run", C.c_int, [C.c_void_p, C.POINTER(UgParams), C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
                                C.POINTER(C.c_void_p)]),
+    ("msgpu_ug_run_pair", C.c_int, [C.c_void_p, C.POINTER(UgParams), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64,
+                                    C.POINTER(C.c_void_p)]),
     ("msgpu_ug_result_stats", C.c_int, [C.c_void_p, C.POINTER(UgStats)]),
     ("msgpu_ug_result_rounds", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgRound)), C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_unitigs", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgUnitig)), C.POINTER(C.c_uint64)]),
@@ -458,6 +469,11 @@ SYMBOLS = [
     ("msgpu_map_last_error", C.c_char_p, [C.c_void_p]),
     ("msgpu_map_run", C.c_int, [C.c_void_p, C.POINTER(MapParams), C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
                                 C.POINTER(C.c_void_p)]),
+    ("msgpu_map_index_create", C.c_int, [C.c_void_p, C.POINTER(MapParams), C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("msgpu_map_index_free", None, [C.c_void_p]),
+    ("msgpu_map_index_stats", C.c_int, [C.c_void_p, C.POINTER(MapIndexStats)]),
+    ("msgpu_map_run_index", C.c_int, [C.c_void_p, C.POINTER(MapParams), C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint64,
+                                      C.POINTER(C.c_void_p)]),
     ("msgpu_map_result_stats", C.c_int, [C.c_void_p, C.POINTER(MapStats)]),
     ("msgpu_map_result_chains", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapChain)), C.POINTER(C.c_uint64)]),
     ("msgpu_map_result_batches", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapBatch)), C.POINTER(C.c_uint64)]),

@@ -48,10 +48,10 @@ class _Stage:
         raise self.error_cls(rc, detail=self._fn("last_error")(self.ctx).decode(errors="replace"), **where)
 
     @contextlib.contextmanager
-    def run(self, *args):
-        """``msgpu_<prefix>_run(ctx, *args, &result)``: the result, freed on the way out"""
+    def run(self, *args, fn="run"):
+        """``msgpu_<prefix>_<fn>(ctx, *args, &result)``: the result, freed on the way out"""
         res = C.c_void_p()
-        self.check(self._fn("run")(self.ctx, *args, C.byref(res)))
+        self.check(self._fn(fn)(self.ctx, *args, C.byref(res)))
         try:
             yield res
         finally:

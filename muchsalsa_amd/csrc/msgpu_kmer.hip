@@ -272,6 +272,38 @@ int kf_records(StageCtx *c, DevArena &D, KfFile *F, int n_files) {
   return MSGPU_OK;
 }
 
+int kf_pair_open(StageCtx *c, const char *path_a, const char *path_b, msgpu_pair **out) {
+  std::unique_ptr<msgpu_pair> p;
+  try {
+    p.reset(new msgpu_pair());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  p->device  = c->device;
+  p->n_files = path_b ? 2 : 1;
+  const StageTimer load;
+  const char      *paths[2] = {path_a, path_b};
+  for (int f = 0; f < p->n_files; ++f) {
+    const int rc = kf_upload(c, p->D, paths[f], f, p->F[f]);
+    if (rc != MSGPU_OK) return rc;
+  }
+  p->load_ms = load.ms();
+  const StageTimer records;
+  const int        rc = kf_records(c, p->D, p->F, p->n_files);
+  if (rc != MSGPU_OK) return rc;
+  if (p->n_files == 1) {
+    p->F[1].d  = p->F[0].d;
+    p->F[1].ls = p->F[0].ls;
+  }
+  p->records_ms = records.ms();
+  *out          = p.release();
+  return MSGPU_OK;
+}
+
+void kf_pair_close(msgpu_pair *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  delete p;
+}
+
 } // namespace msgpu
 
 using namespace msgpu;
@@ -493,14 +525,34 @@ const char *msgpu_kf_last_error(const msgpu_kfctx *c) { return c ? c->err : "nul
 uint64_t    msgpu_kf_error_line(const msgpu_kfctx *c) { return c ? c->err_line : 0; }
 int         msgpu_kf_error_file(const msgpu_kfctx *c) { return c ? c->err_file : 0; }
 
-int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, uint32_t flags, uint64_t budget_bytes,
-                 msgpu_kf_result **out) {
-  if (!c || !out) return MSGPU_E_ARG;
-  *out        = nullptr;
+// every entry point starts with no error
+static void kf_enter(msgpu_kfctx *c) {
   c->err[0]   = 0;
   c->err_line = 0;
   c->err_file = 0;
-  if (!path_a || !path_b || flags) return MSGPU_E_ARG;
+}
+
+int msgpu_kf_open_pair(msgpu_kfctx *c, const char *path_a, const char *path_b, msgpu_pair **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out = nullptr;
+  kf_enter(c);
+  if (!path_a || !path_b) return MSGPU_E_ARG;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  return kf_pair_open(c, path_a, path_b, out);
+}
+
+void msgpu_pair_close(msgpu_pair *pair) { kf_pair_close(pair); }
+
+int msgpu_kf_run_pair(msgpu_kfctx *c, int k, const msgpu_pair *pair, uint32_t flags, uint64_t budget_bytes, msgpu_kf_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out = nullptr;
+  kf_enter(c);
+  if (!pair || flags) return MSGPU_E_ARG;
+  if (pair->device != c->device || pair->n_files != 2) {
+    snprintf(c->err, sizeof(c->err), "the pair holds %d file(s) on device %d; the filter's context is on device %d and takes two",
+             pair->n_files, pair->device, c->device);
+    return MSGPU_E_ARG;
+  }
   if (k < 1 || k > 64) {
     snprintf(c->err, sizeof(c->err), "k = %d is outside 1..64", k);
     return MSGPU_E_ARG;
@@ -513,33 +565,23 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   msgpu_kf_stats &S = res->stats;
   S.k               = static_cast<uint32_t>(k);
-  DevArena    D;
-  KfFile      F[2];
-  const char *paths[2] = {path_a, path_b};
-  for (int f = 0; f < 2; ++f) {
-    const int rc = kf_upload(c, D, paths[f], f, F[f]);
-    if (rc != MSGPU_OK) return rc;
-    S.bytes_in[f] = F[f].size;
-  }
-  S.load_ms = wall.ms();
-
-  // ---- records: line starts, the format rules
-  const StageTimer records;
-  {
-    const int rc = kf_records(c, D, F, 2);
-    if (rc != MSGPU_OK) return rc;
-  }
+  const KfFile *F = pair->F;
+  S.bytes_in[0]   = F[0].size;
+  S.bytes_in[1]   = F[1].size;
   if (F[0].n_lines != F[1].n_lines) {
     const int f = F[0].n_lines < F[1].n_lines ? 0 : 1;
     return kf_format_error(c, f, F[f].n_lines + 1, "the two files differ in their number of records");
   }
   const uint64_t n_pairs = F[0].n_lines >> 2;
-  S.n_pairs    = n_pairs;
-  S.records_ms = records.ms();
+  S.n_pairs = n_pairs;
 
+  DevArena  D; // the run's own: the pair's bytes are read, never written
   const int rc = k <= 32 ? kf_stage<uint64_t>(c, D, F, n_pairs, k, budget_bytes, res.get())
                          : kf_stage<kf_u128>(c, D, F, n_pairs, k, budget_bytes, res.get());
-  if (rc != MSGPU_OK) return rc;
+  if (rc != MSGPU_OK) {
+    (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
+    return rc;
+  }
   char buf[96];
   snprintf(buf, sizeof(buf), "abundance threshold for k-mer filtering:  %lld\n", static_cast<long long>(S.upper));
   try {
@@ -554,6 +596,32 @@ int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, 
   S.wall_ms      = wall.ms();
   *out           = res.release();
   return MSGPU_OK;
+}
+
+// open + run on the pair + close
+int msgpu_kf_run(msgpu_kfctx *c, int k, const char *path_a, const char *path_b, uint32_t flags, uint64_t budget_bytes,
+                 msgpu_kf_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out = nullptr;
+  kf_enter(c);
+  if (!path_a || !path_b || flags) return MSGPU_E_ARG;
+  if (k < 1 || k > 64) {
+    snprintf(c->err, sizeof(c->err), "k = %d is outside 1..64", k);
+    return MSGPU_E_ARG;
+  }
+  const StageTimer wall;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  msgpu_pair *pair = nullptr;
+  int         rc = kf_pair_open(c, path_a, path_b, &pair);
+  if (rc != MSGPU_OK) return rc;
+  rc = msgpu_kf_run_pair(c, k, pair, 0, budget_bytes, out);
+  if (rc == MSGPU_OK) {
+    (*out)->stats.load_ms    = pair->load_ms;
+    (*out)->stats.records_ms = pair->records_ms;
+  }
+  kf_pair_close(pair);
+  if (rc == MSGPU_OK) (*out)->stats.wall_ms = wall.ms();
+  return rc;
 }
 
 int msgpu_kf_result_stats(const msgpu_kf_result *r, msgpu_kf_stats *out) {

@@ -36,6 +36,7 @@ struct KfIn { // the files as the kernels see them: read t < n_first is record t
   const uint64_t *ls[2]; // line starts, n_lines + 1 entries: line l is [ls[l], ls[l + 1] - 1)
   uint64_t        n_first, n_reads;
   int             k;
+  const uint8_t  *dropped = nullptr; // a byte per pair, 1 = the pair's two reads count as empty (msgpu_ug_run_pair); null: no mask
 };
 
 // splitmix64's finaliser over both halves of the key
@@ -82,7 +83,7 @@ __device__ inline void kf_read(const KfIn &in, uint64_t t, const uint8_t *&s, ui
   const uint64_t r = t - (f ? in.n_first : 0);
   const uint64_t a = in.ls[f][4 * r + 1], e = in.ls[f][4 * r + 2] - 1;
   s   = in.buf[f] + a;
-  len = e - a;
+  len = (in.dropped && in.dropped[r]) ? 0 : e - a; // (with a mask both files have n_first records: r is the pair)
 }
 
 // windows per hash bin
@@ -189,11 +190,28 @@ struct KfFile {
   bool      open_end = false; // the last line has no '\n'
 };
 
+} // namespace msgpu
+
+// What kf_upload and kf_records leave on the device, kept until msgpu_pair_close: the bytes of one or two FASTQ files,
+// their line starts, the format check done.  A run reads it and writes nothing into it.
+struct msgpu_pair {
+  int             device = 0;
+  int             n_files = 0;
+  msgpu::DevArena D;
+  msgpu::KfFile   F[2]; // (one file: F[1] points at F[0]'s bytes and has no lines, so no read of it is ever asked for)
+  float           load_ms = 0.f, records_ms = 0.f;
+};
+
+namespace msgpu {
+
 // defined in msgpu_kmer.hip
 int kf_upload(StageCtx *c, DevArena &D, const char *path, int which, KfFile &f); // mmap -> page-locked ring -> device
 int kf_lines(StageCtx *c, DevArena &D, KfFile &f);                                // the line starts of a file on the device
 int kf_format_error(StageCtx *c, int which, uint64_t line, const char *what);
 int kf_records(StageCtx *c, DevArena &D, KfFile *F, int n_files); // line starts and the FASTQ rules of every file, file 0 first
+// both of the above for one or two files (path_b may be null) into a new msgpu_pair on c's device; c takes the error
+int  kf_pair_open(StageCtx *c, const char *path_a, const char *path_b, msgpu_pair **out);
+void kf_pair_close(msgpu_pair *p);
 
 // ---- the partitions: P ranges of the KF_BINS hash bins
 inline uint32_t kf_first_bin(uint32_t p, uint32_t P) { return static_cast<uint32_t>((uint64_t(p) * KF_BINS + P - 1) / P); }

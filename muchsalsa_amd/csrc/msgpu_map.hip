@@ -496,9 +496,11 @@ using namespace msgpu;
 // ---- host side -----------------------------------------------------------------------------------------------------
 
 struct msgpu_mapctx : msgpu::StageCtx {
-  SeqCtxHold  seq;
-  ScalarBlock sc;
-  int         open() {
+  SeqCtxHold       seq;
+  ScalarBlock      sc;
+  msgpu_map_index *index = nullptr; // the one index the context holds (its targets lie in one of seq's two stores)
+  ~msgpu_mapctx();
+  int open() {
     const int rc = msgpu_seq_create(device, &seq.p);
     return rc != MSGPU_OK ? rc : sc.create() ? MSGPU_OK : MSGPU_E_HIP;
   }
@@ -700,6 +702,7 @@ struct MpRun { // what stays on the device for the whole run (rule 9), as a batc
   const uint64_t         *d_aoff; // the anchors in front of every query minimizer
   const uint64_t         *d_bpre; // the bases in front of every query record
   const uint64_t         *first_min, *bpre; // on the host: every query record's first minimizer, and d_bpre
+  int                     qkind;  // the store the query records lie in
   uint32_t               *d_nruns;
   kf_ull                 *d_hist; // 32 bins, summed over the batches
   StageClock             &clock;
@@ -857,14 +860,15 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
       if (P) {
         // the batch's query records as they are and reverse-complemented, one record behind the other, one copy behind the other
         const uint64_t          NB = bt.n_query_bases, b0 = R.bpre[q0];
+        const uint32_t          from = R.qkind ? MSGPU_COPY_ILLUMINA : 0u;
         std::vector<msgpu_copy> pieces;
         try {
           pieces.reserve(2ull * bt.n_queries);
           for (uint32_t i = q0; i < q1; ++i) {
             const uint64_t o = msgpu_seq_offset(R.Qf.f, i), at = R.bpre[i] - b0;
             const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(R.Qf.f, i));
-            pieces.push_back(msgpu_copy{o, at, L, 0});
-            pieces.push_back(msgpu_copy{o, NB + at, L, MSGPU_COPY_REVCOMP});
+            pieces.push_back(msgpu_copy{o, at, L, from});
+            pieces.push_back(msgpu_copy{o, NB + at, L, from | MSGPU_COPY_REVCOMP});
           }
         } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
         msgpu_gather_plan *plan = nullptr;
@@ -923,59 +927,59 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   return MSGPU_OK;
 }
 
-int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, const char *qpath, uint64_t budget_bytes,
-             msgpu_map_result *res) {
-  msgpu_map_stats &S = res->stats;
+} // namespace
+
+// Everything of a run that depends on the targets, k and w only: the target file in its store, the per-record offsets and
+// lengths, the target sketch, and the index over it (sorted entries, distinct keys, counts, starts, hash table).  The
+// occurrence cap is applied at look-up, so max_occ is no part of it.
+struct msgpu_map_index {
+  msgpu_mapctx *owner = nullptr;
+  int           kind = 1; // the store of owner->seq that holds the targets; a run's queries go into the other one
+  int           k = 0, w = 0;
+  DevArena      D;
+  MpFile        Tf;
+  MpSketch      Ts;
+  uint64_t     *d_ivals = nullptr, *d_ukeys = nullptr;
+  uint32_t     *d_ucnt = nullptr, *d_ustart = nullptr, *d_slots = nullptr;
+  uint32_t      n_keys = 0, slots_n = 0;
+  float         load_ms = 0.f, sketch_ms = 0.f, sort_ms = 0.f, table_ms = 0.f, wall_ms = 0.f;
+};
+
+msgpu_mapctx::~msgpu_mapctx() { delete index; }
+
+namespace {
+
+int mp_index_build(msgpu_mapctx *c, int k, int w, const char *tpath, msgpu_map_index &I) {
   hipStream_t      st = c->stream;
-  DevArena         D;
+  DevArena        &D = I.D;
   StageClock       clock(st);
-  const int  k = prm.k, w = prm.w;
-  const bool ava = prm.ava != 0, exact = prm.exact != 0;
   const StageTimer wall;
-  STAGE_HIP(c, hipMemsetAsync(c->sc.d, 0, SC_COUNT * sizeof(uint64_t), st));
-
-  // ---- the files
-  MpFile Tf, Qf_own;
-  int    rc = mp_load(c, D, tpath, ava ? 0 : 1, "targets", Tf);
+  I.k = k;
+  I.w = w;
+  int rc = mp_load(c, D, tpath, I.kind, "targets", I.Tf);
   if (rc != MSGPU_OK) return rc;
-  if (!ava) {
-    rc = mp_load(c, D, qpath, 0, "queries", Qf_own);
-    if (rc != MSGPU_OK) return rc;
-  }
-  const MpFile &Qf = ava ? Tf : Qf_own;
-  S.n_records[0] = Tf.recs.n;
-  S.n_records[1] = Qf.recs.n;
-  S.n_bases[0]   = Tf.recs.n_bases;
-  S.n_bases[1]   = Qf.recs.n_bases;
-  S.load_ms      = wall.ms();
+  I.load_ms = wall.ms();
 
-  // ---- rule 2 on both files, rule 3
-  MpSketch Ts, Qs_own;
-  rc = mp_sketch(c, D, clock, &S.sketch_ms, Tf.recs, k, w, "targets", Ts);
+  // ---- rule 2 on the targets, rule 3
+  MpSketch &Ts = I.Ts;
+  rc = mp_sketch(c, D, clock, &I.sketch_ms, I.Tf.recs, k, w, "targets", Ts);
   if (rc != MSGPU_OK) return rc;
-  if (!ava) {
-    rc = mp_sketch(c, D, clock, &S.sketch_ms, Qf.recs, k, w, "queries", Qs_own);
-    if (rc != MSGPU_OK) return rc;
-  }
-  const MpSketch &Qs = ava ? Ts : Qs_own;
-  S.n_minimizers[0]  = Ts.n;
-  S.n_minimizers[1]  = Qs.n;
   const uint32_t NT = static_cast<uint32_t>(Ts.n);
-  uint64_t      *d_ikeys, *d_ivals, *d_ukeys;
-  uint32_t      *d_ucnt, *d_ustart, *d_nruns, *d_slots;
+  uint64_t      *d_ikeys;
+  uint32_t      *d_nruns;
   STAGE_HIP(c, D.get(&d_ikeys, NT));
-  STAGE_HIP(c, D.get(&d_ivals, NT));
-  STAGE_HIP(c, D.get(&d_ukeys, NT));
-  STAGE_HIP(c, D.get(&d_ucnt, NT + 1ull));
-  STAGE_HIP(c, D.get(&d_ustart, NT + 1ull));
+  STAGE_HIP(c, D.get(&I.d_ivals, NT));
+  STAGE_HIP(c, D.get(&I.d_ukeys, NT));
+  STAGE_HIP(c, D.get(&I.d_ucnt, NT + 1ull));
+  STAGE_HIP(c, D.get(&I.d_ustart, NT + 1ull));
   STAGE_HIP(c, D.get(&d_nruns, 1));
   STAGE_HIP(c, hipMemsetAsync(d_nruns, 0, 4, st));
   uint32_t n_keys = 0;
   if (NT) {
-    STAGE_HIP(c, clock.begin(&S.sort_ms));
-    STAGE_HIP(c, stage_sort_pairs(D, st, Ts.keys, d_ikeys, Ts.vals, d_ivals, NT, 2 * k));
+    STAGE_HIP(c, clock.begin(&I.sort_ms));
+    STAGE_HIP(c, stage_sort_pairs(D, st, Ts.keys, d_ikeys, Ts.vals, I.d_ivals, NT, 2 * k));
     STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
-      return rocprim::run_length_encode(tmp, bytes, d_ikeys, NT, d_ukeys, d_ucnt, d_nruns, st);
+      return rocprim::run_length_encode(tmp, bytes, d_ikeys, NT, I.d_ukeys, I.d_ucnt, d_nruns, st);
     }));
     hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_nruns);
     STAGE_HIP(c, clock.end());
@@ -983,29 +987,84 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
     if (rc != MSGPU_OK) return rc;
     n_keys = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
     D.drop_tmp();
-    STAGE_HIP(c, hipMemsetAsync(d_ucnt + n_keys, 0, 4, st));
-    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_ucnt, d_ustart, n_keys + 1ull));
+    STAGE_HIP(c, hipMemsetAsync(I.d_ucnt + n_keys, 0, 4, st));
+    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, I.d_ucnt, I.d_ustart, n_keys + 1ull));
     STAGE_HIP(c, hipStreamSynchronize(st));
+    D.drop_tmp();
   }
+  D.drop(d_ikeys); // (the distinct keys stand for them from here on)
+  D.drop(d_nruns);
   if (n_keys > (1u << 30)) { // (the table has 2^31 slots at most)
     snprintf(c->err, sizeof(c->err), "%u distinct target minimizers; the limit is 2^30", n_keys);
     return MSGPU_E_ARG;
   }
   uint32_t sn = 64;
   while (sn < 2ull * n_keys) sn <<= 1;
-  STAGE_HIP(c, D.get(&d_slots, sn));
-  STAGE_HIP(c, hipMemsetAsync(d_slots, 0xff, sn * 4ull, st));
-  STAGE_HIP(c, clock.begin(&S.table_ms));
-  if (n_keys) {
-    hipLaunchKernelGGL(k_kf_table<uint64_t>, dim3(grid256(n_keys)), dim3(256), 0, st, d_ukeys, n_keys, d_slots, sn - 1);
-    hipLaunchKernelGGL(k_mp_occ, dim3(grid256(n_keys)), dim3(256), 0, st, d_ucnt, n_keys, prm.max_occ, mp_slot(c, MP_SC_DROPK),
-                       mp_slot(c, MP_SC_DROPE));
+  STAGE_HIP(c, D.get(&I.d_slots, sn));
+  STAGE_HIP(c, hipMemsetAsync(I.d_slots, 0xff, sn * 4ull, st));
+  STAGE_HIP(c, clock.begin(&I.table_ms));
+  if (n_keys) hipLaunchKernelGGL(k_kf_table<uint64_t>, dim3(grid256(n_keys)), dim3(256), 0, st, I.d_ukeys, n_keys, I.d_slots, sn - 1);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  clock.collect();
+  I.n_keys  = n_keys;
+  I.slots_n = sn;
+  I.wall_ms = wall.ms();
+  return MSGPU_OK;
+}
+
+// a run on an index: the query side, rule 3's cap at this run's max_occ, rules 4 to 9
+int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &I, const char *qpath, uint64_t budget_bytes,
+           msgpu_map_result *res) {
+  msgpu_map_stats &S = res->stats;
+  hipStream_t      st = c->stream;
+  DevArena         D; // the run's own: the index is read, never written
+  StageClock       clock(st);
+  const int  k = prm.k, w = prm.w;
+  const bool ava = prm.ava != 0, exact = prm.exact != 0;
+  const StageTimer wall;
+  STAGE_HIP(c, hipMemsetAsync(c->sc.d, 0, SC_COUNT * sizeof(uint64_t), st));
+
+  // ---- the query file (ava: the index's own store and sketch)
+  const MpFile &Tf = I.Tf;
+  MpFile        Qf_own;
+  int           rc;
+  if (!ava) {
+    rc = mp_load(c, D, qpath, 1 - I.kind, "queries", Qf_own);
+    if (rc != MSGPU_OK) return rc;
   }
+  const MpFile &Qf = ava ? Tf : Qf_own;
+  const int     qkind = ava ? I.kind : 1 - I.kind;
+  S.n_records[0] = Tf.recs.n;
+  S.n_records[1] = Qf.recs.n;
+  S.n_bases[0]   = Tf.recs.n_bases;
+  S.n_bases[1]   = Qf.recs.n_bases;
+  S.load_ms      = ava ? 0.f : wall.ms();
+
+  // ---- rule 2 on the queries, rule 3's cap
+  const MpSketch &Ts = I.Ts;
+  MpSketch        Qs_own;
+  if (!ava) {
+    rc = mp_sketch(c, D, clock, &S.sketch_ms, Qf.recs, k, w, "queries", Qs_own);
+    if (rc != MSGPU_OK) return rc;
+  }
+  const MpSketch &Qs = ava ? Ts : Qs_own;
+  S.n_minimizers[0]  = Ts.n;
+  S.n_minimizers[1]  = Qs.n;
+  const uint32_t NT = static_cast<uint32_t>(Ts.n), n_keys = I.n_keys;
+  uint32_t      *d_nruns;
+  STAGE_HIP(c, D.get(&d_nruns, 1));
+  STAGE_HIP(c, hipMemsetAsync(d_nruns, 0, 4, st));
+  STAGE_HIP(c, clock.begin(&S.table_ms));
+  if (n_keys)
+    hipLaunchKernelGGL(k_mp_occ, dim3(grid256(n_keys)), dim3(256), 0, st, I.d_ucnt, n_keys, prm.max_occ, mp_slot(c, MP_SC_DROPK),
+                       mp_slot(c, MP_SC_DROPE));
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, clock.end());
   S.n_keys          = n_keys;
   S.n_index_entries = NT;
-  const MpIndex X{d_ukeys, d_ucnt, d_ustart, d_slots, sn - 1, prm.max_occ, d_ivals};
+  const MpIndex X{I.d_ukeys, I.d_ucnt, I.d_ustart, I.d_slots, I.slots_n - 1, prm.max_occ, I.d_ivals};
 
   // ---- rule 4's counts: anchors per query minimizer and in front of it; anchors and bases in front of every query record
   const uint64_t NQ = Qs.n;
@@ -1083,7 +1142,7 @@ int mp_stage(msgpu_mapctx *c, const msgpu_map_params &prm, const char *tpath, co
   }
 
   // ---- rules 4 to 8, batch by batch
-  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, d_nruns, d_hist, clock, res};
+  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res};
   for (msgpu_map_batch &b : res->batches) {
     rc = mp_batch(run, B, b);
     if (rc != MSGPU_OK) return rc;
@@ -1142,13 +1201,7 @@ void msgpu_map_destroy(msgpu_mapctx *c) { stage_destroy(c); }
 
 const char *msgpu_map_last_error(const msgpu_mapctx *c) { return c ? c->err : "null context"; }
 
-int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *targets_path, const char *queries_path, uint32_t flags,
-                  uint64_t budget_bytes, msgpu_map_result **out) {
-  if (!c || !out) return MSGPU_E_ARG;
-  *out      = nullptr;
-  c->err[0] = 0;
-  if (!params || !targets_path || flags) return MSGPU_E_ARG;
-  const msgpu_map_params p = *params;
+static int mp_check_params(msgpu_mapctx *c, const msgpu_map_params &p) {
   if (p.k < 4 || p.k > 32 || p.w < 1 || p.w > 64 || p.max_occ < 1 || p.max_gap < 0 || p.bandwidth < 0 || p.max_pred != 64 ||
       p.band < 1 || p.band > 127 || (p.exact != 0 && p.exact != 1) || (p.ava != 0 && p.ava != 1)) {
     snprintf(c->err, sizeof(c->err), "parameters: k = %d (4..32), w = %d (1..64), max_occ = %u (>= 1), max_gap = %d, bandwidth = %d "
@@ -1156,8 +1209,80 @@ int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *t
              p.max_pred, p.band, p.exact, p.ava);
     return MSGPU_E_ARG;
   }
-  if (p.ava ? (queries_path && strcmp(queries_path, targets_path) != 0) : !queries_path) {
-    snprintf(c->err, sizeof(c->err), p.ava ? "ava: the query file is the target file" : "no query file");
+  return MSGPU_OK;
+}
+
+// the index of targets_path in store `kind` of the context
+static int mp_index_create(msgpu_mapctx *c, int k, int w, const char *targets_path, int kind, msgpu_map_index **out) {
+  if (c->index) {
+    snprintf(c->err, sizeof(c->err), "the context holds an index already (k = %d, w = %d): free it first", c->index->k, c->index->w);
+    return MSGPU_E_STATE;
+  }
+  STAGE_HIP(c, hipSetDevice(c->device));
+  std::unique_ptr<msgpu_map_index> I;
+  try {
+    I.reset(new msgpu_map_index());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  I->owner = c;
+  I->kind  = kind;
+  const int rc = mp_index_build(c, k, w, targets_path, *I);
+  if (rc != MSGPU_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
+  c->index = I.get();
+  *out     = I.release();
+  return MSGPU_OK;
+}
+
+int msgpu_map_index_create(msgpu_mapctx *c, const msgpu_map_params *params, const char *targets_path, msgpu_map_index **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out      = nullptr;
+  c->err[0] = 0;
+  if (!params || !targets_path) return MSGPU_E_ARG;
+  if (params->k < 4 || params->k > 32 || params->w < 1 || params->w > 64) {
+    snprintf(c->err, sizeof(c->err), "parameters: k = %d (4..32), w = %d (1..64)", params->k, params->w);
+    return MSGPU_E_ARG;
+  }
+  return mp_index_create(c, params->k, params->w, targets_path, 1, out);
+}
+
+void msgpu_map_index_free(msgpu_map_index *index) {
+  if (!index) return;
+  msgpu_mapctx *c = index->owner;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->index == index) c->index = nullptr;
+  delete index;
+}
+
+int msgpu_map_index_stats(const msgpu_map_index *index, msgpu_map_istats *out) {
+  if (!index || !out) return MSGPU_E_ARG;
+  *out = msgpu_map_istats{index->Tf.recs.n, index->Tf.recs.n_bases, index->Ts.n,      index->n_keys,   index->Ts.n,
+                               index->k,         index->w,               index->load_ms,   index->sketch_ms, index->sort_ms,
+                               index->table_ms,  index->wall_ms,         0};
+  return MSGPU_OK;
+}
+
+int msgpu_map_run_index(msgpu_mapctx *c, const msgpu_map_params *params, const msgpu_map_index *index, const char *queries_path,
+                        uint32_t flags, uint64_t budget_bytes, msgpu_map_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out      = nullptr;
+  c->err[0] = 0;
+  if (!params || !index || flags) return MSGPU_E_ARG;
+  const msgpu_map_params p = *params;
+  int                    rc = mp_check_params(c, p);
+  if (rc != MSGPU_OK) return rc;
+  if (index != c->index) {
+    snprintf(c->err, sizeof(c->err), "the index is not this context's");
+    return MSGPU_E_ARG;
+  }
+  if (p.k != index->k || p.w != index->w) {
+    snprintf(c->err, sizeof(c->err), "the run has k = %d, w = %d; the index was built with k = %d, w = %d", p.k, p.w, index->k, index->w);
+    return MSGPU_E_ARG;
+  }
+  if (p.ava ? queries_path != nullptr : !queries_path) {
+    snprintf(c->err, sizeof(c->err), p.ava ? "ava: the index's own records are the queries" : "no query file");
     return MSGPU_E_ARG;
   }
   STAGE_HIP(c, hipSetDevice(c->device));
@@ -1166,7 +1291,7 @@ int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *t
     res.reset(new msgpu_map_result());
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   const uint64_t lost0 = c->sc.lost;
-  const int      rc = mp_stage(c, p, targets_path, queries_path, budget_bytes, res.get());
+  rc = mp_run(c, p, *index, queries_path, budget_bytes, res.get());
   if (rc != MSGPU_OK) {
     (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -1175,6 +1300,39 @@ int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *t
   res->stats.params              = p;
   *out                           = res.release();
   return MSGPU_OK;
+}
+
+// create + run + free
+int msgpu_map_run(msgpu_mapctx *c, const msgpu_map_params *params, const char *targets_path, const char *queries_path, uint32_t flags,
+                  uint64_t budget_bytes, msgpu_map_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out      = nullptr;
+  c->err[0] = 0;
+  if (!params || !targets_path || flags) return MSGPU_E_ARG;
+  const msgpu_map_params p = *params;
+  int                    rc = mp_check_params(c, p);
+  if (rc != MSGPU_OK) return rc;
+  if (p.ava ? (queries_path && strcmp(queries_path, targets_path) != 0) : !queries_path) {
+    snprintf(c->err, sizeof(c->err), p.ava ? "ava: the query file is the target file" : "no query file");
+    return MSGPU_E_ARG;
+  }
+  const StageTimer wall;
+  const uint64_t   lost0 = c->sc.lost;
+  msgpu_map_index *index = nullptr;
+  rc = mp_index_create(c, p.k, p.w, targets_path, p.ava ? 0 : 1, &index); // (the stores the stage has always used)
+  if (rc != MSGPU_OK) return rc;
+  rc = msgpu_map_run_index(c, &p, index, p.ava ? nullptr : queries_path, 0, budget_bytes, out);
+  if (rc == MSGPU_OK) {
+    msgpu_map_stats &S = (*out)->stats;
+    S.load_ms += index->load_ms;
+    S.sketch_ms += index->sketch_ms;
+    S.sort_ms += index->sort_ms;
+    S.table_ms += index->table_ms;
+    S.n_lost_publications = c->sc.lost - lost0;
+  }
+  msgpu_map_index_free(index);
+  if (rc == MSGPU_OK) (*out)->stats.wall_ms = wall.ms();
+  return rc;
 }
 
 int msgpu_map_result_stats(const msgpu_map_result *r, msgpu_map_stats *out) {

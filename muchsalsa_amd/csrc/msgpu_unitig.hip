@@ -359,13 +359,14 @@ template <> void ug_split<kf_u128>(kf_u128 key, uint64_t &hi, uint64_t &lo) {
 
 // everything behind the format check, for one key width
 template <class K>
-int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const msgpu_ug_params &prm, uint64_t budget, msgpu_ug_result *res) {
+int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_dropped, const msgpu_ug_params &prm, uint64_t budget,
+             msgpu_ug_result *res) {
   msgpu_ug_stats &S = res->stats;
   hipStream_t     st = c->stream;
   StageClock      clock(st);
   const int      k = prm.k;
   const uint64_t n_first = F[0].n_lines >> 2, n_reads = n_first + (F[1].n_lines >> 2);
-  const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_first, n_reads, k};
+  const KfIn     in{{F[0].d, F[1].d}, {F[0].ls, F[1].ls}, n_first, n_reads, k, d_dropped};
 
   // ---- count: the k-mer filter's, least = min_count, no histogram
   kf_ull *d_cur;
@@ -685,15 +686,9 @@ const char *msgpu_ug_last_error(const msgpu_ugctx *c) { return c ? c->err : "nul
 uint64_t    msgpu_ug_error_line(const msgpu_ugctx *c) { return c ? c->err_line : 0; }
 int         msgpu_ug_error_file(const msgpu_ugctx *c) { return c ? c->err_file : 0; }
 
-int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path_a, const char *path_b, uint32_t flags,
-                 uint64_t budget_bytes, msgpu_ug_result **out) {
-  if (!c || !out) return MSGPU_E_ARG;
-  *out        = nullptr;
-  c->err[0]   = 0;
-  c->err_line = 0;
-  c->err_file = 0;
-  if (!params || !path_a || flags) return MSGPU_E_ARG;
-  msgpu_ug_params prm = *params;
+// the parameters as a run uses them; the context takes the error
+static int ug_params(msgpu_ugctx *c, const msgpu_ug_params *params, msgpu_ug_params &prm) {
+  prm = *params;
   if (prm.k < 2 || prm.k > 64) {
     snprintf(c->err, sizeof(c->err), "k = %d is outside 2..64", prm.k);
     return MSGPU_E_ARG;
@@ -701,6 +696,31 @@ int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path
   if (prm.trim == -1) prm.trim = prm.k;
   if (prm.min_count < 1 || prm.trim < 0) {
     snprintf(c->err, sizeof(c->err), "min_count = %u must be at least 1, trim = %d at least 0 (or -1 for k)", prm.min_count, prm.trim);
+    return MSGPU_E_ARG;
+  }
+  return MSGPU_OK;
+}
+
+int msgpu_ug_run_pair(msgpu_ugctx *c, const msgpu_ug_params *params, const msgpu_pair *pair, const uint8_t *dropped, uint64_t n_pairs,
+                      uint32_t flags, uint64_t budget_bytes, msgpu_ug_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out        = nullptr;
+  c->err[0]   = 0;
+  c->err_line = 0;
+  c->err_file = 0;
+  if (!params || !pair || flags) return MSGPU_E_ARG;
+  msgpu_ug_params prm;
+  int             rc = ug_params(c, params, prm);
+  if (rc != MSGPU_OK) return rc;
+  if (pair->device != c->device) {
+    snprintf(c->err, sizeof(c->err), "the pair is on device %d, the context on device %d", pair->device, c->device);
+    return MSGPU_E_ARG;
+  }
+  const KfFile *F = pair->F;
+  if (dropped && (pair->n_files != 2 || F[0].n_lines != F[1].n_lines || n_pairs != (F[0].n_lines >> 2))) {
+    snprintf(c->err, sizeof(c->err), "a mask of %llu pairs on files of %llu and %llu records: with a mask both files hold n_pairs records",
+             static_cast<kf_ull>(n_pairs), static_cast<kf_ull>(F[0].n_lines >> 2),
+             static_cast<kf_ull>(pair->n_files == 2 ? F[1].n_lines >> 2 : 0));
     return MSGPU_E_ARG;
   }
   const StageTimer wall;
@@ -714,33 +734,55 @@ int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path
   S.min_count  = prm.min_count;
   S.trim       = static_cast<uint32_t>(prm.trim);
   S.min_length = prm.min_length;
-  DevArena       D;
-  KfFile         F[2];
-  const char    *paths[2] = {path_a, path_b};
-  const int      n_files = path_b ? 2 : 1;
   const uint64_t lost0 = c->sc.lost;
-  for (int f = 0; f < n_files; ++f) {
-    const int rc = kf_upload(c, D, paths[f], f, F[f]);
-    if (rc != MSGPU_OK) return rc;
-    S.bytes_in[f] = F[f].size;
+  for (int f = 0; f < pair->n_files; ++f) {
+    S.bytes_in[f]  = F[f].size;
+    S.n_records[f] = F[f].n_lines >> 2;
   }
-  S.load_ms = wall.ms();
-  const StageTimer records;
-  int        rc = kf_records(c, D, F, n_files);
-  if (rc != MSGPU_OK) return rc;
-  if (n_files == 1) { // no second file: no read of it is ever asked for
-    F[1].d  = F[0].d;
-    F[1].ls = F[0].ls;
+  DevArena D; // the run's own: the pair's bytes are read, never written
+  uint8_t *d_dropped = nullptr;
+  if (dropped) { // the mask goes to the device once
+    STAGE_HIP(c, D.get(&d_dropped, n_pairs));
+    if (n_pairs) STAGE_HIP(c, hipMemcpyAsync(d_dropped, dropped, n_pairs, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipStreamSynchronize(c->stream)); // (the caller's array may go when the call returns)
   }
-  S.n_records[0] = F[0].n_lines >> 2;
-  S.n_records[1] = F[1].n_lines >> 2;
-  S.records_ms   = records.ms();
-  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, prm, budget_bytes, res.get()) : ug_stage<kf_u128>(c, D, F, prm, budget_bytes, res.get());
-  if (rc != MSGPU_OK) return rc;
+  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, budget_bytes, res.get())
+                   : ug_stage<kf_u128>(c, D, F, d_dropped, prm, budget_bytes, res.get());
+  if (rc != MSGPU_OK) {
+    (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
+    return rc;
+  }
   S.n_lost_publications = c->sc.lost - lost0;
   S.wall_ms             = wall.ms();
   *out                  = res.release();
   return MSGPU_OK;
+}
+
+// open + run on the pair + close
+int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path_a, const char *path_b, uint32_t flags,
+                 uint64_t budget_bytes, msgpu_ug_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out        = nullptr;
+  c->err[0]   = 0;
+  c->err_line = 0;
+  c->err_file = 0;
+  if (!params || !path_a || flags) return MSGPU_E_ARG;
+  msgpu_ug_params prm;
+  int             rc = ug_params(c, params, prm);
+  if (rc != MSGPU_OK) return rc;
+  const StageTimer wall;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  msgpu_pair *pair = nullptr;
+  rc = kf_pair_open(c, path_a, path_b, &pair);
+  if (rc != MSGPU_OK) return rc;
+  rc = msgpu_ug_run_pair(c, params, pair, nullptr, 0, 0, budget_bytes, out);
+  if (rc == MSGPU_OK) {
+    (*out)->stats.load_ms    = pair->load_ms;
+    (*out)->stats.records_ms = pair->records_ms;
+  }
+  kf_pair_close(pair);
+  if (rc == MSGPU_OK) (*out)->stats.wall_ms = wall.ms();
+  return rc;
 }
 
 int msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out) {

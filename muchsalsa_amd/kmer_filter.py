@@ -54,6 +54,7 @@ From jellyfish:
 * ``dump`` writes in hash order, ``--kmers`` in ascending key order;
 * the pipeline's progress lines are replaced by the JSON line.
 """
+import contextlib
 import ctypes as C
 import json
 import os
@@ -65,7 +66,7 @@ import numpy as np
 from . import _lib
 from ._stage import StageError, stage_context, text_view
 
-__all__ = ["KmerFilterError", "threshold", "run", "main"]
+__all__ = ["KmerFilterError", "Pair", "threshold", "run", "main"]
 
 
 class KmerFilterError(StageError):
@@ -87,20 +88,53 @@ def threshold(rows):
     return int(q1.value), int(q3.value), int(up.value)
 
 
+class Pair:
+    """The two Illumina files resident in device memory (msgpu_pair): their bytes, their line starts, the FASTQ rules
+    checked.  ``run(..., pair=p)`` here and ``unitigs.run(..., pair=p)`` then read them where they lie, any number of
+    times, at any k; neither changes them.  A context manager; the files are judged when it is entered (two files of
+    different record counts are accepted here: the filter rejects them, the unitig stage takes them without a mask)."""
+
+    def __init__(self, in1, in2, device=0):
+        self.paths, self.device, self.handle = (in1, in2), device, C.c_void_p()
+        self._stack = None
+
+    def __enter__(self):
+        with contextlib.ExitStack() as stack:
+            stage = stack.enter_context(stage_context("kf", self.device, KmerFilterError))
+            stage.check(_lib.lib().msgpu_kf_open_pair(stage.ctx, os.fsencode(self.paths[0]), os.fsencode(self.paths[1]),
+                                                      C.byref(self.handle)))
+            stack.callback(self.close)
+            self.stage = stage
+            self._stack = stack.pop_all()
+        return self
+
+    def close(self):
+        if self.handle:
+            _lib.lib().msgpu_pair_close(self.handle)
+            self.handle = C.c_void_p()
+
+    def __exit__(self, *exc):
+        self._stack.close()
+        return False
+
+
 def _arr(p, n, dtype):
     return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype)
 
 
-def run(k, in1, in2, report, out1, out2, device=0, budget_mb=None, histo=None, kmers=None, timings=None, tables=None):
+def run(k, in1, in2, report, out1, out2, device=0, budget_mb=None, histo=None, kmers=None, timings=None, tables=None,
+        pair=None):
     """The whole stage: writes ``out1``, ``out2`` and ``report`` (and ``histo`` / ``kmers`` when given); returns the
-    counts.  ``budget_mb`` bounds the partition buffers (None: half of the free device memory).  ``timings`` (a dict)
+    counts.  With ``pair`` (an entered Pair) the stage runs on the resident files, ``in1`` / ``in2`` / ``device`` are not
+    read, and ``out1`` / ``out2`` may be None: that text is then not written.  ``budget_mb`` bounds the partition buffers (None: half of the free device memory).  ``timings`` (a dict)
     receives seconds per step; ``tables`` (a dict) receives ``histogram`` (rows), ``key_hi`` / ``key_lo`` / ``count`` (the
     abundant set, ascending) and ``verdict`` (a byte per pair, 1 = dropped)."""
     L = _lib.lib()
     t0 = time.perf_counter()
     budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
-    with stage_context("kf", device, KmerFilterError) as stage:
-        with stage.run(int(k), os.fsencode(in1), os.fsencode(in2), 0, budget) as res:
+    with (stage_context("kf", device, KmerFilterError) if pair is None else contextlib.nullcontext(pair.stage)) as stage:
+        with (stage.run(int(k), os.fsencode(in1), os.fsencode(in2), 0, budget) if pair is None else
+              stage.run(int(k), pair.handle, 0, budget, fn="run_pair")) as res:
             st = _lib.KfStats()
             L.msgpu_kf_result_stats(res, C.byref(st))
             if tables is not None:
@@ -121,6 +155,8 @@ def run(k, in1, in2, report, out1, out2, device=0, budget_mb=None, histo=None, k
             if kmers is not None:
                 files.append((kmers, _lib.KF_TEXT_KMERS))
             for path, which in files:
+                if path is None:
+                    continue
                 with open(path, "wb") as h:
                     h.write(text_view(L.msgpu_kf_result_text, res, which))
             t_write = time.perf_counter() - t1

@@ -50,8 +50,9 @@ tests' restatement in plain Python (tests/map_oracle.py), not against minimap2. 
     emission in the group).  On any error nothing is written.
  9. limits and batches.  Limits, each an error and never a fault: fewer than 2^31 index entries, anchors and segment pairs
     per batch, at most 2^30 distinct target keys; a record shorter than 2^31 bases, a file below 2^38; a group's n * k
-    below 2^31.  Resident for the whole run: both stores, both sketches, the index (sorted entries, distinct keys, counts,
-    starts, hash table), the anchor count of every query minimizer and its 64-bit exclusive scan.  Everything whose size
+    below 2^31.  Resident while the index lives (``Index``): the target store, its sketch and the index (sorted entries,
+    distinct keys, counts, starts, hash table); resident for the whole run besides: the query store and sketch, the
+    anchor count of every query minimizer and its 64-bit exclusive scan.  Everything whose size
     depends on the anchors exists per batch of consecutive query records (a group never spans two query records, and rule 8
     orders by query record first, so the batches' lines one behind the other are the PAF of the whole input): the anchors
     and their sort buffers, the groups, classes and lists, f, pred, the sort keys, the chains with their table and, in
@@ -80,7 +81,13 @@ is built):
 * no CIGAR: exact mode gives a match count that is a lower bound from unit-cost distances per link, not minimap2's count
   of ``=`` columns;
 * no end extension beyond the outermost seeds.
+
+``Index(targets, k=, w=)`` is a context manager that keeps the targets' store, sketch and index on the device;
+``run(None, queries, out, index=ix, ...)`` then maps onto it, any number of times, with any parameters but k and w (the
+occurrence cap is applied at look-up).  With ava the index's own records are the queries.  Every result equals that of
+the run by files.
 """
+import contextlib
 import ctypes as C
 import json
 import os
@@ -90,7 +97,7 @@ import time
 from . import _lib
 from ._stage import StageError, stage_context, text_view
 
-__all__ = ["MapError", "run", "main", "DEFAULTS"]
+__all__ = ["MapError", "Index", "run", "main", "DEFAULTS"]
 
 DEFAULTS = dict(k=15, w=5, max_occ=200, max_gap=10000, bandwidth=2000, min_score=100, min_count=3, exact=0, band=64, ava=0)
 
@@ -102,13 +109,58 @@ class MapError(StageError):
         super().__init__(code, detail=detail)
 
 
-def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, **params):
+def _params(p):
+    return _lib.MapParams(int(p["k"]), int(p["w"]), int(p["max_occ"]), int(p["max_gap"]), int(p["bandwidth"]), 64,
+                          int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]), 0)
+
+
+class Index:
+    """The targets resident in device memory with their sketch and index (msgpu_map_index), in a mapper context of its own.
+    ``stats`` holds the counts and the seconds of the build.  One index serves any number of ``run(..., index=ix)``."""
+
+    def __init__(self, targets, device=0, k=DEFAULTS["k"], w=DEFAULTS["w"]):
+        self.targets, self.device, self.k, self.w = targets, device, int(k), int(w)
+        self.handle, self._stack, self.stats = C.c_void_p(), None, None
+
+    def __enter__(self):
+        with contextlib.ExitStack() as stack:
+            self.stage = stack.enter_context(stage_context("map", self.device, MapError))
+            self.create()
+            stack.callback(self.free)
+            self._stack = stack.pop_all()
+        return self
+
+    def create(self):
+        """(again, after free(): the context holds one index at a time)"""
+        L = _lib.lib()
+        prm = _params(dict(DEFAULTS, k=self.k, w=self.w))
+        self.stage.check(L.msgpu_map_index_create(self.stage.ctx, C.byref(prm), os.fsencode(self.targets), C.byref(self.handle)))
+        st = _lib.MapIndexStats()
+        L.msgpu_map_index_stats(self.handle, C.byref(st))
+        self.stats = {"records": int(st.n_records), "bases": int(st.n_bases), "minimizers": int(st.n_minimizers),
+                      "keys": int(st.n_keys), "index_entries": int(st.n_index_entries), "k": int(st.k), "w": int(st.w),
+                      "seconds": {n[:-3]: getattr(st, n) / 1e3 for n, _ in _lib.MapIndexStats._fields_ if n.endswith("_ms")}}
+
+    def free(self):
+        if self.handle:
+            _lib.lib().msgpu_map_index_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __exit__(self, *exc):
+        self._stack.close()
+        return False
+
+
+def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, **params):
     """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
     per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
     ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
     ava = 1, ``queries`` is None or ``targets``.  ``tables`` (a dict) receives ``chains``: per line of the PAF the tuple
     (query, target, strand, anchors, score, nm, q_start, q_end, t_start, t_end, matches, block) and ``text`` (bytes);
-    ``timings`` (a dict) seconds per step."""
+    ``timings`` (a dict) seconds per step.  With ``index`` (an entered Index) the run maps onto it: ``targets`` and ``device``
+    are not read, k and w default to the index's, and with ava = 1 ``queries`` is None."""
+    if index is not None:
+        params = dict({"k": index.k, "w": index.w}, **params)
     unknown = set(params) - set(DEFAULTS)
     if unknown:
         raise TypeError("unknown parameters: %s" % ", ".join(sorted(unknown)))
@@ -119,10 +171,11 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     for name, v in p.items():
         if not -(1 << 31) <= int(v) < (1 << 31) or (name == "max_occ" and int(v) < 0):
             raise MapError(_lib.E_ARG, "%s = %d" % (name, int(v)))
-    with stage_context("map", device, MapError) as stage:
-        prm = _lib.MapParams(int(p["k"]), int(p["w"]), int(p["max_occ"]), int(p["max_gap"]), int(p["bandwidth"]), 64,
-                             int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]), 0)
-        with stage.run(C.byref(prm), os.fsencode(targets), None if queries is None else os.fsencode(queries), 0, budget) as res:
+    qpath = None if queries is None else os.fsencode(queries)
+    with (stage_context("map", device, MapError) if index is None else contextlib.nullcontext(index.stage)) as stage:
+        prm = _params(p)
+        with (stage.run(C.byref(prm), os.fsencode(targets), qpath, 0, budget) if index is None else
+              stage.run(C.byref(prm), index.handle, qpath, 0, budget, fn="run_index")) as res:
             st = _lib.MapStats()
             L.msgpu_map_result_stats(res, C.byref(st))
             text = text_view(L.msgpu_map_result_text, res)

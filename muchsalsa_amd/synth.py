@@ -477,18 +477,32 @@ def kmer_filter_workload(genome, coverage, read_len, seed, families=6, copies=25
     Deterministic in (seed, shape)."""
     G, L = int(genome), int(read_len)
     insert = int(insert) if insert else (5 * L) // 2
+    g = _planted_genome(G, seed, families, copies, repeat_len, 70, at_least=insert)
+    return _illumina_pairs(g, coverage, L, seed, error, n_frac, lower_frac, insert)
+
+
+def _planted_genome(G, seed, families, copies, repeat_len, stream, at_least=0):
+    """genome_bases(G, seed) with ``families`` repeat units of ``repeat_len`` bases each written ``copies`` times: identical
+    copies, one per slot of an even grid (which slot: drawn from ``stream``), at an offset inside the slot drawn from
+    ``stream`` + 1"""
     g = genome_bases(G, seed).copy()
     slots = int(families) * int(copies)
     if slots:
         slot = G // slots
-        if slot < repeat_len or G < insert:
+        if slot < repeat_len or G < at_least:
             raise ValueError("genome too short for the repeats")
         units = genome_bases(int(families) * int(repeat_len), seed + 1).reshape(int(families), int(repeat_len))
-        where = np.argsort(splitmix64(seed, 70, slots), kind="stable")  # which slot a (family, copy) lands in
-        jitter = _randint(seed, 71, slots, 0, slot - int(repeat_len))
+        where = np.argsort(splitmix64(seed, stream, slots), kind="stable")  # which slot a (family, copy) lands in
+        jitter = _randint(seed, stream + 1, slots, 0, slot - int(repeat_len))
         for i in range(slots):
             at = int(where[i]) * slot + int(jitter[i])
             g[at:at + int(repeat_len)] = units[i // int(copies)]
+    return g
+
+
+def _illumina_pairs(g, coverage, L, seed, error, n_frac, lower_frac, insert):
+    """the read pairs of kmer_filter_workload from the genome ``g`` -> (FASTQ file 1, FASTQ file 2)"""
+    G = len(g)
     n = max(G * int(coverage) // (2 * L), 1)
     start = _randint(seed, 72, n, 0, G - insert)
     comp = np.zeros(256, np.uint8)
@@ -571,18 +585,31 @@ def mapper_workload(n_reads, read_len, n_unitigs, seed, coverage=10, error=0.06,
     Deterministic in (seed, shape)."""
     L = int(read_len)
     G = max(int(n_reads) * L // int(coverage), L + unitig_len[1] + 500)
-    g = genome_bases(G, seed).copy()
-    slots = int(families) * int(copies)
-    if slots:
-        slot = G // slots
-        if slot < repeat_len:
-            raise ValueError("genome too short for the repeats")
-        units = genome_bases(int(families) * int(repeat_len), seed + 1).reshape(int(families), int(repeat_len))
-        where = np.argsort(splitmix64(seed, 80, slots), kind="stable")
-        jitter = _randint(seed, 81, slots, 0, slot - int(repeat_len))
-        for i in range(slots):
-            at = int(where[i]) * slot + int(jitter[i])
-            g[at:at + int(repeat_len)] = units[i // int(copies)]
+    g = _planted_genome(G, seed, families, copies, repeat_len, 80)
+    recs, r_start, r_fwd = _long_reads(g, n_reads, L, seed, error, n_frac, lower_frac, fastq)
+    comp = np.arange(256, dtype=np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    if tiled:
+        n_max = G // unitig_len[0] + 2
+        u_len = _randint(seed, 84, n_max, unitig_len[0], unitig_len[1])
+        u_start = np.cumsum(u_len) - u_len
+        keep = u_start < G
+        u_start, u_len = u_start[keep], np.minimum(u_len[keep], G - u_start[keep])
+    else:
+        u_len = _randint(seed, 84, n_unitigs, unitig_len[0], unitig_len[1])
+        u_start = _randint(seed, 85, n_unitigs, 0, G - u_len)
+    u_fwd = (splitmix64(seed, 86, len(u_len)) & np.uint64(1)).astype(bool)
+    unitigs = []
+    for i in range(len(u_len)):
+        seq = g[u_start[i]:u_start[i] + u_len[i]]
+        unitigs.append(b">u%d\n%s\n" % (i, (seq if u_fwd[i] else comp[seq[::-1]]).tobytes()))
+    return {"reads": b"".join(recs), "unitigs": b"".join(unitigs), "genome": g.tobytes(), "read_start": r_start, "read_fwd": r_fwd,
+            "unitig_start": u_start, "unitig_fwd": u_fwd, "unitig_len": u_len}
+
+
+def _long_reads(g, n_reads, L, seed, error, n_frac, lower_frac, fastq):
+    """the reads of mapper_workload from the genome ``g`` -> (records, start of every read, its strand)"""
+    G = len(g)
     comp = np.arange(256, dtype=np.uint8)
     comp[list(b"ACGT")] = list(b"TGCA")
     sub = np.zeros((256, 3), np.uint8)
@@ -615,19 +642,26 @@ def mapper_workload(n_reads, read_len, n_unitigs, seed, coverage=10, error=0.06,
         for i in range(n):
             seq = out[ends[i] - lens[i]:ends[i]].tobytes()
             recs.append(b"@r%d\n%s\n+\n%s\n" % (lo + i, seq, b"I" * len(seq)) if fastq else b">r%d\n%s\n" % (lo + i, seq))
-    if tiled:
-        n_max = G // unitig_len[0] + 2
-        u_len = _randint(seed, 84, n_max, unitig_len[0], unitig_len[1])
-        u_start = np.cumsum(u_len) - u_len
-        keep = u_start < G
-        u_start, u_len = u_start[keep], np.minimum(u_len[keep], G - u_start[keep])
-    else:
-        u_len = _randint(seed, 84, n_unitigs, unitig_len[0], unitig_len[1])
-        u_start = _randint(seed, 85, n_unitigs, 0, G - u_len)
-    u_fwd = (splitmix64(seed, 86, len(u_len)) & np.uint64(1)).astype(bool)
-    unitigs = []
-    for i in range(len(u_len)):
-        seq = g[u_start[i]:u_start[i] + u_len[i]]
-        unitigs.append(b">u%d\n%s\n" % (i, (seq if u_fwd[i] else comp[seq[::-1]]).tobytes()))
-    return {"reads": b"".join(recs), "unitigs": b"".join(unitigs), "genome": g.tobytes(), "read_start": r_start, "read_fwd": r_fwd,
-            "unitig_start": u_start, "unitig_fwd": u_fwd, "unitig_len": u_len}
+    return recs, r_start, r_fwd
+
+
+def hybrid_workload(genome, seed, coverage=40, read_len=100, n_long=50, long_len=3000, families=2, copies=6, repeat_len=400,
+                    error=0.005, long_error=0.06, n_frac=0.0005, lower_frac=0.001, fastq=True):
+    """Input of the whole pipeline (muchsalsa_amd.hybrid): a dict with ``illumina_1`` / ``illumina_2`` (FASTQ bytes), ``reads``
+    (the long reads: FASTQ bytes, or FASTA with fastq=False) and ``genome`` (bytes), all from ONE genome.
+
+    The genome has ``genome`` bases with planted repeats, made as kmer_filter_workload makes them (``families`` units of
+    ``repeat_len`` bases, ``copies`` each).  The Illumina pairs are drawn from it as kmer_filter_workload draws them
+    (``coverage``, ``read_len``, ``error``); the ``n_long`` long reads of ``long_len`` genome bases as mapper_workload draws
+    and edits them (``long_error``).  Deterministic in (seed, shape).
+
+    The planted repeats carry the k-mer filter's abundant k-mers: the filter drops the pairs that touch them, so the unitigs
+    end at the repeats and none lies inside one.  An outlier of the unitig coverage filter is then no repeat but the unitig
+    on which the drawn long reads happen to pile up; whether there is one depends on the seed and on ``n_long``."""
+    G, L = int(genome), int(read_len)
+    insert = (5 * L) // 2
+    g = _planted_genome(G, seed, families, copies, repeat_len, 70, at_least=insert)
+    one, two = _illumina_pairs(g, coverage, L, seed, error, n_frac, lower_frac, insert)
+    recs, r_start, r_fwd = _long_reads(g, n_long, int(long_len), seed + 2, long_error, n_frac, lower_frac, fastq)  # (streams of their own)
+    return {"illumina_1": one, "illumina_2": two, "reads": b"".join(recs), "genome": g.tobytes(), "read_start": r_start,
+            "read_fwd": r_fwd}

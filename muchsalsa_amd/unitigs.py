@@ -45,6 +45,12 @@ this project is built):
 * islands are kept until the length cut;
 * ids and the order of the records are this stage's;
 * a sequence is one line.
+
+The mask (rule 8 of include/msgpu.h).  ``run(..., pair=p, dropped=m)`` runs on a resident ``kmer_filter.Pair`` instead of
+files; ``m`` is a byte per pair, 1 = dropped, what the k-mer filter returns as its verdicts.  The stage on a pair with the
+mask m gives the result of the stage on the two files that hold the records with m = 0, in order: both texts, the unitig
+table, the rounds, the windows, the distinct and solid k-mers before and after the tips, the unitig counts and the longest
+chain.  ``records`` and ``bytes_in`` are the pair's own.  With a mask both files hold as many records as m has bytes.
 """
 import ctypes as C
 import json
@@ -64,21 +70,27 @@ class UnitigError(StageError):
 
 
 def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_length=500, budget_mb=None, tables=None,
-        timings=None):
+        timings=None, pair=None, dropped=None):
     """The whole stage: writes ``out_all`` and ``out_cut``; returns the counts.  ``in_2`` may be None.  ``trim`` None: k.
+    With ``pair`` (an entered kmer_filter.Pair) the stage runs on the resident files on the pair's device and ``in_1`` /
+    ``in_2`` / ``device`` are not read; ``dropped`` (bytes or a uint8 array, one per pair, 1 = dropped) is the mask.
     ``budget_mb`` bounds the count's partition buffers (None: half of the free device memory).  ``tables`` (a dict)
     receives ``rounds`` [(limit, k-mers removed)] and ``unitigs`` [(length, coverage, first k-mer, offset of the sequence in
     the all text, cyclic)] in output order; ``timings`` (a dict) seconds per step (``files``: writing the two outputs), and ``round_seconds`` [(tips,
     neighbour bytes)] per round."""
     L = _lib.lib()
     t0 = time.perf_counter()
-    with stage_context("ug", device, UnitigError) as stage:
+    if dropped is not None and pair is None:
+        raise TypeError("dropped needs pair")
+    mask = None if dropped is None else bytes(bytearray(dropped))
+    with stage_context("ug", device if pair is None else pair.device, UnitigError) as stage:
         budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
         prm = _lib.UgParams(int(k), int(min_count) if 0 <= int(min_count) < (1 << 32) else 0, -1 if trim is None else int(trim),
                             min(max(int(min_length), 0), (1 << 32) - 1))
         if trim is not None and int(trim) < 0:
             raise UnitigError(_lib.E_ARG, detail="trim = %d" % int(trim))
-        with stage.run(C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget) as res:
+        with (stage.run(C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget) if pair is None
+              else stage.run(C.byref(prm), pair.handle, mask, 0 if mask is None else len(mask), 0, budget, fn="run_pair")) as res:
             st = _lib.UgStats()
             L.msgpu_ug_result_stats(res, C.byref(st))
             rp, n = C.POINTER(_lib.UgRound)(), C.c_uint64()
