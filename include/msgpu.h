@@ -1191,14 +1191,41 @@ void        msgpu_ug_result_free(msgpu_ug_result *r);
  *     eighth less, again and again, while the device cannot give the largest batch's bytes as one block).  A
  *     record that exceeds the budget on its own is MSGPU_E_NOMEM, one with 2^31 anchors or more MSGPU_E_ARG, naming the
  *     record, its anchors and the bytes against the budget.  Splitting one query record over ranges of targets, and
- *     splitting the index, are out of scope. */
+ *     splitting the index, are out of scope.
+ * 10. the alignment of one segment pair, and cigar mode (cigar = 1, which needs exact = 1).  a is the target bytes, n of
+ *     them, b the oriented query bytes, m of them, compared as the stores hold them (rule 7); ks = m - n; slide(i, k) is the
+ *     largest i' >= i with a[i..i') == b[i+k..i'+k), i' <= n, i'+k <= m.  The table: G_0[0] = slide(0, 0) and nothing else
+ *     is defined in row 0.  For e >= 1 and |k| <= e the candidates of cell (e, k) are X: G_{e-1}[k] + 1, valid iff
+ *     G_{e-1}[k] is defined and < min(n, m - k); D (a target base without a query base): G_{e-1}[k+1] + 1, valid iff
+ *     G_{e-1}[k+1] is defined and < n; I (a query base without a target base): G_{e-1}[k-1], valid iff it is defined and
+ *     G_{e-1}[k-1] + k <= m.  x0(e, k) is the largest valid candidate (none: the cell is undefined), G_e[k] = slide(x0, k),
+ *     and the cell's op is the first of X, D, I whose candidate is valid and equals x0.  d is the first e with
+ *     G_e[ks] = n; the pair is capped when |ks| > band or no such e <= band exists, and then d_i = band + 1 as in rule 7.
+ *     The script is read backwards from (d, ks): G_e[k] - x0 '=' columns lie behind the cell's op, which leads to
+ *     (e-1, k) for X, (e-1, k+1) for D, (e-1, k-1) for I; row 0 ends the walk with G_0[0] leading '=' columns.  Only valid
+ *     candidates enter: one that would step outside the matrix is no edit (rule 7's clamped recurrence may hold such
+ *     values; they are harmless for the number, not for a script).  The script has exactly d columns that are not '=',
+ *     every '=' column holds equal bytes and every X column unequal ones, and it consumes exactly n and m bytes.
+ *     With cigar = 1 a chain's alignment is k '=' columns for anchor 0, then for every link in rising order the segment's
+ *     script followed by c_i '=' columns (seed bases: '=' by rule 1's case folding even where the bytes differ in case);
+ *     a link with lt_i = lq_i = 0 has no segment; a capped segment is written lt_i D then lq_i I, zero lengths left out;
+ *     neighbouring runs of one letter are merged.  matches = the '=' columns, block = all columns, nm = block - matches.
+ *     The line is the twelve columns, cm, s1, NM:i:<nm>, then cg:Z:<runs> in target-forward order, which is the oriented
+ *     query's order on both strands.  The runs consume exactly t_end - t_start target bases and q_end - q_start query
+ *     bases; for a chain without a capped segment matches is at least rule 7's exact-mode value (a segment has at least
+ *     max(lt, lq) columns, d of them no '=').  Rule 9 with cigar = 1: msgpu_map_batch_bytes adds the slab of the scripts'
+ *     tables (slots * (band + 1)^2 words, a constant number of slots that MSGPU_ALIGN_SLOTS=<n> lowers; no slab for a band
+ *     of at most 31, whose tables all lie in LDS) to the fixed part
+ *     and, per anchor, band + 1 words of script, the 64-bit offset, the script length, the class list entry, the '='
+ *     columns behind the segment and the two column counts.  Without cigar every byte of every output is as before. */
 typedef struct msgpu_mapctx msgpu_mapctx; /* a device context of the stage */
 typedef struct msgpu_map_result msgpu_map_result;
 typedef struct msgpu_map_params {
   int32_t  k, w;
   uint32_t max_occ;
   int32_t  max_gap, bandwidth, max_pred, min_score, min_count;
-  int32_t  exact, band, ava, reserved;
+  int32_t  exact, band, ava;
+  int32_t  cigar; /* 0 / 1; 1 needs exact = 1 (rule 10) */
 } msgpu_map_params;
 void        msgpu_map_default_params(msgpu_map_params *p);
 int         msgpu_map_create(int device, msgpu_mapctx **out); /* MSGPU_E_NODEVICE without a GPU */
@@ -1277,6 +1304,20 @@ int         msgpu_map_result_chains(const msgpu_map_result *r, const msgpu_map_c
 int         msgpu_map_result_batches(const msgpu_map_result *r, const msgpu_map_batch **batches, uint64_t *n); /* in order */
 uint64_t    msgpu_map_result_budget(const msgpu_map_result *r); /* the budget of a batch in bytes: budget_bytes, or what 0 stood for */
 const char *msgpu_map_result_text(const msgpu_map_result *r, uint64_t *len);
+/* cigar mode (rule 10).  The run tables: the runs of chain i, in output order, are ops[off[i] .. off[i + 1]) (off has n + 1
+ * entries), each len << 4 | op with the BAM codes 1 = I, 2 = D, 7 = '=', 8 = X.  Without cigar *n = 0 (and off[0] = 0). */
+int         msgpu_map_result_cigars(const msgpu_map_result *r, const uint32_t **ops, const uint64_t **off, uint64_t *n);
+typedef struct msgpu_map_astats { /* cigar mode: the segment pairs of rule 10, summed over the batches */
+  uint64_t n_pairs_d0, n_pairs_lds, n_pairs_slab, n_pairs_capped; /* no edit; table in LDS; table in the slab; beyond the band */
+  uint64_t max_d;                                                 /* the largest distance within the band */
+  uint64_t x_columns, i_columns, d_columns;                       /* of the scripts (capped segments not counted) */
+  uint64_t script_words, n_runs;                                  /* words of all scripts; runs of all chains */
+  uint64_t n_inconsistent; /* pairs whose table contradicted their distance: 0, or the kernels are wrong and the scripts too */
+  uint32_t slots, lds_max_d;                                      /* of the slab; the largest d of the LDS class */
+  float    align_ms;                                              /* device, by events: offsets, scripts, figures */
+  float    cigar_host_ms;                                         /* host: the runs of all chains (wall, summed over the ranges) */
+} msgpu_map_astats;
+int         msgpu_map_result_align_stats(const msgpu_map_result *r, msgpu_map_astats *out);
 void        msgpu_map_result_free(msgpu_map_result *r);
 
 /* ---- between the overlap path and assemblePath (host) -----------------------------
@@ -1400,6 +1441,17 @@ typedef struct msgpu_align_pair {
 } msgpu_align_pair;
 int msgpu_edit_distance(msgpu_seqctx *ctx, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n,
                         uint32_t band, uint32_t *out);
+/* The edit script of every pair beside its distance ("unitig-to-read mapping", rule 10, is the definition).  Arguments and
+ * limits as above.  dist[p] is what msgpu_edit_distance returns.  off has n + 1 entries; pair p owns
+ * words[off[p] .. off[p + 1]): d + 1 words for a pair within the band, none for a capped pair.  Word t < d is
+ * kind << 30 | run with the kinds 1 = X, 2 = D (a base of a only), 3 = I (a base of b only), in forward order, run = the
+ * number of '=' columns in front of that edit; word d is kind 0 with the trailing '=' run.  When the words do not fit
+ * capacity: MSGPU_E_ARG with dist, off and *n_words set, so that the caller can call again with room.  MSGPU_E_STATE: a
+ * table on the device contradicted its pair's distance (a defect of the kernels, counted and reported, never passed over).
+ * MSGPU_ALIGN_SLOTS=<n> in the environment lowers the number of tables that pairs of more than 31 edits share. */
+int msgpu_edit_script(msgpu_seqctx *ctx, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n,
+                      uint32_t band, uint32_t *dist, uint64_t *off /* n + 1 */, uint32_t *words, uint64_t capacity,
+                      uint64_t *n_words);
 
 #ifdef __cplusplus
 }

@@ -197,7 +197,7 @@ UG_TEXT_ALL, UG_TEXT_CUT = 0, 1
 
 class MapParams(C.Structure):  # msgpu_map_params
     _fields_ = [("k", C.c_int32), ("w", C.c_int32), ("max_occ", C.c_uint32)] + [
-        (n, C.c_int32) for n in ("max_gap", "bandwidth", "max_pred", "min_score", "min_count", "exact", "band", "ava", "reserved")]
+        (n, C.c_int32) for n in ("max_gap", "bandwidth", "max_pred", "min_score", "min_count", "exact", "band", "ava", "cigar")]
 
 
 class MapChain(C.Structure):  # msgpu_map_chain
@@ -222,6 +222,12 @@ class MapIndexStats(C.Structure):  # msgpu_map_istats
     _fields_ = ([(n, C.c_uint64) for n in ("n_records", "n_bases", "n_minimizers", "n_keys", "n_index_entries")] +
                 [("k", C.c_int32), ("w", C.c_int32)] +
                 [(n, C.c_float) for n in ("load_ms", "sketch_ms", "sort_ms", "table_ms", "wall_ms")] + [("reserved", C.c_uint32)])
+
+
+class MapAlignStats(C.Structure):  # msgpu_map_astats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_pairs_d0", "n_pairs_lds", "n_pairs_slab", "n_pairs_capped", "max_d", "x_columns",
+                                           "i_columns", "d_columns", "script_words", "n_runs", "n_inconsistent")] +
+                [("slots", C.c_uint32), ("lds_max_d", C.c_uint32), ("align_ms", C.c_float), ("cigar_host_ms", C.c_float)])
 
 
 class MapBatch(C.Structure):  # msgpu_map_batch
@@ -480,6 +486,9 @@ SYMBOLS = [
     ("msgpu_map_result_budget", C.c_uint64, [C.c_void_p]),
     ("msgpu_map_batch_bytes", C.c_uint64, [C.POINTER(MapParams), C.c_uint64, C.c_uint64]),
     ("msgpu_map_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_cigars", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint64)),
+                                          C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_align_stats", C.c_int, [C.c_void_p, C.POINTER(MapAlignStats)]),
     ("msgpu_map_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
@@ -487,6 +496,8 @@ SYMBOLS = [
     ("msgpu_seq_synchronize", C.c_int, [C.c_void_p]),
     ("msgpu_edit_distance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                       C.c_void_p]),
+    ("msgpu_edit_script", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 ]
 
 _lib = None

@@ -322,6 +322,20 @@ void launch_em_gather(hipStream_t st, const msgpu_edge *edges, const msgpu_edgem
 const uint8_t *seq_store_bases(const msgpu_seqctx *c, int kind, uint64_t *n_bases);
 void launch_edit_distance_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
                                 uint32_t band, uint32_t *d_out);
+// The edit scripts of msgpu_edit_script on a DEVICE pair list, behind the distance pass (d_dist): d_len gets n + 1 words whose
+// exclusive 64-bit scan is d_off; the words of pair p go to d_words[d_off[p] .. d_off[p + 1]) and stay on the device.  d_list
+// (n words) and d_cnt (ES_CNT_COUNT words, zeroed by the call) are the classes' lists and counters, d_slab the
+// edit_script_slab_words(slots, band) words of the slab class's tables (none, and d_slab may be null, for a band within the LDS
+// class).  d_cnt[ES_CNT_BROKEN] counts the pairs whose table contradicts d_dist (never, unless a kernel is wrong): the caller
+// reads it back and reports it.
+enum { ES_CNT_LDS = 0, ES_CNT_SLAB, ES_CNT_D0, ES_CNT_CAPPED, ES_CNT_MAXD, ES_CNT_BROKEN, ES_CNT_COUNT = 8 };
+void       launch_edit_script_lengths(hipStream_t st, const uint32_t *d_dist, uint32_t n, uint32_t band, uint32_t *d_len);
+uint32_t   edit_script_slots(); // the slots of the slab: a constant, or MSGPU_ALIGN_SLOTS=<n> below it
+uint64_t   edit_script_slab_words(uint32_t slots, uint32_t band);
+uint32_t   edit_script_lds_max_d(); // the largest distance of the class whose table lies in LDS
+hipError_t launch_edit_script_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
+                                    uint32_t band, const uint32_t *d_dist, const uint64_t *d_off, uint32_t *d_list, uint32_t *d_cnt,
+                                    uint32_t *d_slab, uint32_t slots, uint32_t *d_words);
 
 } // namespace msgpu
 

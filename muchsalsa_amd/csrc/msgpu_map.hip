@@ -19,6 +19,8 @@
 //   k_mp_walk      rule 6 behind a segmented sort by (f descending, index ascending): a thread per group
 //   k_mp_pairs     exact mode: the segment pairs of the emitted chains; distances by edit_distance_fr_wave (msgpu_seq.hip)
 //                  against a forward and a reverse-complemented copy of the queries (the existing gather)
+//   cigar mode     rule 10 behind the distances: the scripts' offsets (a scan), launch_edit_script_pairs (msgpu_seq.hip),
+//                  k_mp_columns per pair, two segmented reductions and k_mp_cigar per chain; the host merges the runs
 // Integers only.  Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
@@ -457,13 +459,15 @@ __global__ __launch_bounds__(256) void k_mp_table(const uint32_t *list_kept, uin
 // of every query record of the file, q_base: in front of the batch's first), the reverse complements rc_base further on
 __global__ __launch_bounds__(256) void k_mp_pairs(const msgpu_map_chain *chains, const MpWhere *where, uint32_t n_chains, const uint64_t *xy,
                                                   const int32_t *pred, const uint32_t *pair_off, const uint64_t *toff, const uint64_t *qpre,
-                                                  uint64_t q_base, uint64_t rc_base, int k, msgpu_align_pair *pairs, uint32_t cap) {
+                                                  uint64_t q_base, uint64_t rc_base, int k, msgpu_align_pair *pairs, uint32_t cap,
+                                                  uint32_t *trail, uint32_t *head) {
   const uint32_t ci = blockIdx.x * 256 + threadIdx.x;
   if (ci >= n_chains) return;
   const msgpu_map_chain c = chains[ci];
   const uint32_t        s0 = where[ci].s0;
   const uint64_t        ta = toff[c.target], qa = qpre[c.query] - q_base + (c.strand ? rc_base : 0);
   uint32_t              at = pair_off[ci], cur = where[ci].first;
+  uint32_t              run = 0; // cigar mode: the seed columns ('=') behind the segment that comes next, i.e. in front of `cur`
   for (uint32_t l = 1; l < c.n_anchors; ++l) {
     if (pred[s0 + cur] < 0) break; // (a chain of n_anchors has n_anchors - 1 links)
     const uint32_t pr = static_cast<uint32_t>(pred[s0 + cur]);
@@ -471,10 +475,15 @@ __global__ __launch_bounds__(256) void k_mp_pairs(const msgpu_map_chain *chains,
     const MpLink   L = mp_link(vi, xy[s0 + pr], k);
     if ((L.lt | L.lq) && at < cap) {
       const uint32_t xe = static_cast<uint32_t>(vi >> 32) + k - L.c, ye = static_cast<uint32_t>(vi) + k - L.c;
+      if (trail) trail[at] = run + L.c;
       pairs[at++] = msgpu_align_pair{ta + xe - L.lt, qa + ye - L.lq, L.lt, L.lq};
+      run = 0;
+    } else {
+      run += L.c;
     }
     cur = pr;
   }
+  if (head) head[ci] = run + static_cast<uint32_t>(k); // (anchor 0's k columns lead the alignment)
 }
 
 __global__ __launch_bounds__(256) void k_mp_exact(msgpu_map_chain *chains, uint32_t n_chains, const uint32_t *nm) {
@@ -482,6 +491,46 @@ __global__ __launch_bounds__(256) void k_mp_exact(msgpu_map_chain *chains, uint3
   if (ci >= n_chains) return;
   chains[ci].nm      = nm[ci];
   chains[ci].matches = chains[ci].block - nm[ci];
+}
+
+// rule 10's figures of a segment pair: its '=' columns and all its columns (a capped pair: none, and lt + lq); the X, D
+// and I columns of the scripts are counted on the way (xid[0..2])
+__global__ __launch_bounds__(256) void k_mp_columns(const msgpu_align_pair *pairs, const uint32_t *dist, const uint64_t *off,
+                                                    const uint32_t *words, uint32_t n, uint32_t band, uint32_t *eq, uint32_t *cols,
+                                                    kf_ull *xid) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  uint32_t       cnt[3] = {0, 0, 0};
+  if (i < n) {
+    const uint32_t d = dist[i];
+    if (d > band) {
+      eq[i]   = 0;
+      cols[i] = pairs[i].a_len + pairs[i].b_len;
+    } else {
+      uint32_t e = 0;
+      for (uint64_t w = off[i]; w < off[i + 1]; ++w) {
+        const uint32_t v = words[w];
+        e += v & 0x3fffffffu;
+        if (v >> 30) ++cnt[(v >> 30) - 1];
+      }
+      eq[i]   = e;
+      cols[i] = e + d;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1)
+    for (int j = 0; j < 3; ++j) cnt[j] += __shfl_xor(cnt[j], o);
+  if ((threadIdx.x & 63) == 0)
+    for (int j = 0; j < 3; ++j)
+      if (cnt[j]) atomicAdd(&xid[j], static_cast<kf_ull>(cnt[j]));
+}
+
+// cigar mode's figures of a chain: its seed columns (matches as k_mp_table left it) and its segments' columns
+__global__ __launch_bounds__(256) void k_mp_cigar(msgpu_map_chain *chains, uint32_t n_chains, const uint32_t *eq, const uint32_t *cols) {
+  const uint32_t ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci >= n_chains) return;
+  const uint32_t seed = chains[ci].matches;
+  chains[ci].matches  = seed + eq[ci];
+  chains[ci].block    = seed + cols[ci];
+  chains[ci].nm       = cols[ci] - eq[ci];
 }
 
 __global__ __launch_bounds__(256) void k_mp_capped(const uint32_t *dist, uint32_t n, uint32_t band, kf_ull *capped) {
@@ -512,6 +561,14 @@ struct msgpu_map_result {
   std::vector<msgpu_map_batch> batches; // rule 9's cut, in order
   uint64_t                     budget = 0; // the bytes a batch had: budget_bytes, or what it stood for
   std::string                  text;
+  // cigar mode.  What comes back with the chain table, the batches one behind the other: per chain its '=' columns in front
+  // of the first segment and its pairs (c_poff, n + 1 entries); per pair lt, lq, the '=' columns behind it and its words
+  // (p_woff, pairs + 1 entries; none for a capped pair).  A chain's pairs lie from its last link to its first.
+  msgpu_map_astats      astats{};
+  std::vector<uint32_t> c_head, p_lt, p_lq, p_trail, words;
+  std::vector<uint64_t> c_poff{0}, p_woff{0};
+  std::vector<uint32_t> cg_ops;      // the run tables (msgpu_map_result_cigars)
+  std::vector<uint64_t> cg_off{0};
 };
 
 namespace {
@@ -617,7 +674,33 @@ int mp_sketch(msgpu_mapctx *c, DevArena &D, StageClock &clock, float *ms, const 
   return MSGPU_OK;
 }
 
-void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_seqfile *Q, bool exact, std::string &out) {
+// rule 10: the merged runs of chain i as (BAM code, length), in target-forward order
+constexpr uint32_t CG_INS = 1, CG_DEL = 2, CG_EQ = 7, CG_X = 8;
+void mp_runs(const msgpu_map_result &r, uint64_t i, std::vector<std::pair<uint32_t, uint64_t>> &runs) {
+  runs.clear();
+  auto push = [&](uint32_t op, uint64_t len) {
+    if (!len) return;
+    if (!runs.empty() && runs.back().first == op) runs.back().second += len;
+    else runs.emplace_back(op, len);
+  };
+  static const uint32_t code[4] = {CG_EQ, CG_X, CG_DEL, CG_INS};
+  push(CG_EQ, r.c_head[i]);
+  for (uint64_t p = r.c_poff[i + 1]; p-- > r.c_poff[i];) { // (stored from the last link to the first)
+    if (r.p_woff[p + 1] == r.p_woff[p]) { // capped
+      push(CG_DEL, r.p_lt[p]);
+      push(CG_INS, r.p_lq[p]);
+    } else {
+      for (uint64_t w = r.p_woff[p]; w < r.p_woff[p + 1]; ++w) {
+        push(CG_EQ, r.words[w] & 0x3fffffffu);
+        if (r.words[w] >> 30) push(code[r.words[w] >> 30], 1);
+      }
+    }
+    push(CG_EQ, r.p_trail[p]);
+  }
+}
+
+void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_seqfile *Q, bool exact, std::string &out,
+               const std::vector<std::pair<uint32_t, uint64_t>> *runs = nullptr) {
   char buf[224];
   out += msgpu_seq_name(Q, ch.query);
   int n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%c\t", static_cast<kf_ull>(msgpu_seq_length(Q, ch.query)), ch.q_start, ch.q_end,
@@ -630,6 +713,13 @@ void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_se
   if (exact) {
     n = snprintf(buf, sizeof(buf), "\tNM:i:%u", ch.nm);
     out.append(buf, n);
+  }
+  if (runs) {
+    out += "\tcg:Z:";
+    for (const auto &r : *runs) {
+      n = snprintf(buf, sizeof(buf), "%llu%c", static_cast<kf_ull>(r.second), r.first == CG_EQ ? '=' : r.first == CG_X ? 'X' : r.first == CG_DEL ? 'D' : 'I');
+      out.append(buf, n);
+    }
   }
   out += '\n';
 }
@@ -660,19 +750,28 @@ constexpr uint64_t MP_BYTES_ANCHOR_TMP = 24, MP_BYTES_TMP_FIXED = 1ull << 20;
 constexpr uint64_t MP_BYTES_FIXED = MP_BYTES_TMP_FIXED + 64 * DevArena::ALIGN + 64 * 8;
 static_assert(sizeof(MpRaw) == 28 && sizeof(MpWhere) == 8 && sizeof(msgpu_align_pair) == 24, "rule 9's bytes per anchor");
 
-uint64_t mp_batch_bytes(bool exact, uint64_t n_anchors, uint64_t n_query_bases) {
-  const uint64_t per = MP_BYTES_ANCHOR + MP_BYTES_ANCHOR_TMP + (exact ? MP_BYTES_ANCHOR_EXACT : 0);
-  if (n_anchors >= (1ull << 54) || n_query_bases >= (1ull << 62)) return ~0ull; // (beyond every device; no overflow)
-  return MP_BYTES_FIXED + per * n_anchors + (exact ? 2 * n_query_bases : 0);
+// cigar mode (rule 10), per segment pair beside its band + 1 words of script: len, off (64 bits), list, trail, eq, cols; per
+// chain: head and the two sums; fixed: the slab, the classes' counters and the column counters (two allocations)
+constexpr uint64_t MP_BYTES_ANCHOR_CIGAR = 4 + 8 + 4 + 4 + 4 + 4 + 3 * 4, MP_BYTES_FIXED_CIGAR = 2 * DevArena::ALIGN;
+
+uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint64_t n_anchors, uint64_t n_query_bases) {
+  const bool     exact = prm.exact != 0, cigar = exact && prm.cigar != 0;
+  const uint64_t band1 = static_cast<uint64_t>(prm.band < 0 ? 0 : prm.band > 127 ? 127 : prm.band) + 1;
+  const uint64_t per = MP_BYTES_ANCHOR + MP_BYTES_ANCHOR_TMP + (exact ? MP_BYTES_ANCHOR_EXACT : 0) +
+                       (cigar ? MP_BYTES_ANCHOR_CIGAR + 4 * band1 : 0);
+  // beyond every device, and no overflow: per < 2^8 (2^10 in cigar mode: band + 1 words of script per anchor beside the rest)
+  if (n_anchors >= (1ull << (cigar ? 50 : 54)) || n_query_bases >= (1ull << 62)) return ~0ull;
+  const uint64_t fixed = MP_BYTES_FIXED + (cigar ? MP_BYTES_FIXED_CIGAR + DevArena::aligned(4 * edit_script_slab_words(edit_script_slots(), static_cast<uint32_t>(band1 - 1))) : 0);
+  return fixed + per * n_anchors + (exact ? 2 * n_query_bases : 0);
 }
 
 // The greedy cut of rule 9 over the prefix sums of the records' anchors and bases (n + 1 entries each): a binary search per
 // batch for the last record that still fits.  Returns the first record that fits no batch on its own, or n.
-uint32_t mp_cut(bool exact, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
+uint32_t mp_cut(const msgpu_map_params &prm, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
   for (uint32_t first = 0; first < n;) {
     auto fits = [&](uint32_t end) {
       const uint64_t a = apre[end] - apre[first];
-      return a < (1ull << 31) && mp_batch_bytes(exact, a, bpre[end] - bpre[first]) <= budget;
+      return a < (1ull << 31) && mp_batch_bytes(prm, a, bpre[end] - bpre[first]) <= budget;
     };
     if (!fits(first + 1)) return first;
     uint32_t lo = first + 1, hi = n; // the last end that fits
@@ -686,7 +785,7 @@ uint32_t mp_cut(bool exact, const uint64_t *apre, const uint64_t *bpre, uint32_t
     b.n_queries     = lo - first;
     b.n_anchors     = apre[lo] - apre[first];
     b.n_query_bases = bpre[lo] - bpre[first];
-    b.bytes_bound   = mp_batch_bytes(exact, b.n_anchors, b.n_query_bases);
+    b.bytes_bound   = mp_batch_bytes(prm, b.n_anchors, b.n_query_bases);
     out.push_back(b);
     first = lo;
   }
@@ -719,7 +818,8 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   StageClock             &clock = R.clock;
   hipStream_t             st = c->stream;
   const int               k = prm.k;
-  const bool              exact = prm.exact != 0;
+  const bool              exact = prm.exact != 0, cigar = prm.cigar != 0;
+  msgpu_map_astats       &AS = R.res->astats;
   const uint32_t          A = static_cast<uint32_t>(bt.n_anchors), q0 = bt.first_query, q1 = q0 + bt.n_queries;
   const uint64_t          m0 = R.first_min[q0], m1 = R.first_min[q1];
   int                     rc;
@@ -883,11 +983,15 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
         } free_plan{plan};
         uint8_t          *d_or;
         msgpu_align_pair *d_pairs;
-        uint32_t         *d_dist, *d_nm;
+        uint32_t         *d_dist, *d_nm = nullptr, *d_trail = nullptr, *d_head = nullptr;
         STAGE_HIP(c, B.get(&d_or, 2 * NB + 16));
         STAGE_HIP(c, B.get(&d_pairs, P));
         STAGE_HIP(c, B.get(&d_dist, P));
-        STAGE_HIP(c, B.get(&d_nm, C_n));
+        if (!cigar) STAGE_HIP(c, B.get(&d_nm, C_n));
+        if (cigar) {
+          STAGE_HIP(c, B.get(&d_trail, P));
+          STAGE_HIP(c, B.get(&d_head, C_n));
+        }
         STAGE_HIP(c, clock.begin(&S.pairs_ms));
         rc = msgpu_gather_run(c->seq, plan, d_or, 2 * NB + 16, st);
         if (rc != MSGPU_OK) {
@@ -895,19 +999,111 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
           return rc;
         }
         hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, R.Tf.d_off, R.d_bpre,
-                           b0, NB, k, d_pairs, P);
+                           b0, NB, k, d_pairs, P, d_trail, d_head);
         STAGE_HIP(c, hipGetLastError());
         STAGE_HIP(c, clock.end());
         STAGE_HIP(c, clock.begin(&S.distance_ms));
         launch_edit_distance_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist);
         STAGE_HIP(c, hipGetLastError());
-        STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
-          return rocprim::segmented_reduce(tmp, bytes, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
-        }));
+        if (!cigar)
+          STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+            return rocprim::segmented_reduce(tmp, bytes, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+          }));
         hipLaunchKernelGGL(k_mp_capped, dim3(grid256(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
-        hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
+        if (!cigar) hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
         STAGE_HIP(c, hipGetLastError());
         STAGE_HIP(c, clock.end());
+        if (cigar) {
+          // ---- rule 10: the scripts' offsets, the scripts, the figures of the pairs and of the chains
+          const uint32_t band = static_cast<uint32_t>(prm.band), slots = edit_script_slots();
+          uint32_t      *d_len, *d_list, *d_cnt, *d_slab = nullptr, *d_words, *d_eq, *d_cols;
+          const uint64_t slab_words = edit_script_slab_words(slots, band); // (none for a band within the LDS class)
+          uint64_t      *d_off;
+          kf_ull        *d_xid;
+          STAGE_HIP(c, B.get(&d_len, P + 1ull));
+          STAGE_HIP(c, B.get(&d_off, P + 1ull));
+          STAGE_HIP(c, B.get(&d_list, P));
+          STAGE_HIP(c, B.get(&d_cnt, ES_CNT_COUNT));
+          STAGE_HIP(c, B.get(&d_xid, 4));
+          if (slab_words) STAGE_HIP(c, B.get(&d_slab, slab_words));
+          STAGE_HIP(c, B.get(&d_eq, P));
+          STAGE_HIP(c, B.get(&d_cols, P));
+          STAGE_HIP(c, hipMemsetAsync(d_xid, 0, 4 * sizeof(kf_ull), st));
+          STAGE_HIP(c, clock.begin(&AS.align_ms));
+          launch_edit_script_lengths(st, d_dist, P, band, d_len);
+          STAGE_HIP(c, hipGetLastError());
+          STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_len, d_off, P + 1ull));
+          hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_off + P);
+          STAGE_HIP(c, hipGetLastError());
+          STAGE_HIP(c, clock.end());
+          rc = c->sc.read(c);
+          if (rc != MSGPU_OK) return rc;
+          const uint64_t Wn = c->sc.h[MP_SC_TOTAL2]; // (at most P * (band + 1))
+          STAGE_HIP(c, B.get(&d_words, Wn));
+          STAGE_HIP(c, clock.begin(&AS.align_ms));
+          STAGE_HIP(c, launch_edit_script_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, band, d_dist, d_off, d_list, d_cnt, d_slab, slots, d_words));
+          hipLaunchKernelGGL(k_mp_columns, dim3(grid256(P)), dim3(256), 0, st, d_pairs, d_dist, d_off, d_words, P, band, d_eq, d_cols, d_xid);
+          STAGE_HIP(c, hipGetLastError());
+          uint32_t *d_seq, *d_scols; // the sums per chain
+          STAGE_HIP(c, B.get(&d_seq, C_n));
+          STAGE_HIP(c, B.get(&d_scols, C_n));
+          STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+            return rocprim::segmented_reduce(tmp, bytes, d_eq, d_seq, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+          }));
+          STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+            return rocprim::segmented_reduce(tmp, bytes, d_cols, d_scols, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+          }));
+          hipLaunchKernelGGL(k_mp_cigar, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_seq, d_scols);
+          STAGE_HIP(c, hipGetLastError());
+          STAGE_HIP(c, clock.end());
+          // ---- what the host needs for the runs comes back with the chain table
+          msgpu_map_result &res = *R.res;
+          const size_t      c0 = res.c_head.size(), p0 = res.p_lt.size(), w0 = res.words.size();
+          std::vector<msgpu_align_pair> h_pairs;
+          std::vector<uint32_t>         h_poff;
+          std::vector<uint64_t>         h_off;
+          uint32_t                      h_cnt[ES_CNT_COUNT];
+          kf_ull                        h_xid[4];
+          try {
+            h_pairs.resize(P);
+            h_poff.resize(C_n + 1ull);
+            h_off.resize(P + 1ull);
+            res.c_head.resize(c0 + C_n);
+            res.p_trail.resize(p0 + P);
+            res.p_lt.resize(p0 + P);
+            res.p_lq.resize(p0 + P);
+            res.words.resize(w0 + Wn);
+            res.c_poff.resize(c0 + C_n + 1);
+            res.p_woff.resize(p0 + P + 1);
+          } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+          STAGE_HIP(c, clock.begin(&S.copy_ms));
+          STAGE_HIP(c, hipMemcpyAsync(h_pairs.data(), d_pairs, P * sizeof(msgpu_align_pair), hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, hipMemcpyAsync(h_poff.data(), d_poff, (C_n + 1ull) * 4, hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, hipMemcpyAsync(h_off.data(), d_off, (P + 1ull) * 8, hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, hipMemcpyAsync(res.c_head.data() + c0, d_head, C_n * 4ull, hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, hipMemcpyAsync(res.p_trail.data() + p0, d_trail, P * 4ull, hipMemcpyDeviceToHost, st));
+          if (Wn) STAGE_HIP(c, hipMemcpyAsync(res.words.data() + w0, d_words, Wn * 4, hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, hipMemcpyAsync(h_xid, d_xid, sizeof(h_xid), hipMemcpyDeviceToHost, st));
+          STAGE_HIP(c, clock.end());
+          STAGE_HIP(c, hipStreamSynchronize(st));
+          for (uint32_t i = 0; i < P; ++i) {
+            res.p_lt[p0 + i]       = h_pairs[i].a_len;
+            res.p_lq[p0 + i]       = h_pairs[i].b_len;
+            res.p_woff[p0 + i + 1] = w0 + h_off[i + 1];
+          }
+          for (uint32_t i = 0; i < C_n; ++i) res.c_poff[c0 + i + 1] = p0 + h_poff[i + 1];
+          AS.n_pairs_d0 += h_cnt[ES_CNT_D0];
+          AS.n_pairs_lds += h_cnt[ES_CNT_LDS];
+          AS.n_pairs_slab += h_cnt[ES_CNT_SLAB];
+          AS.n_pairs_capped += h_cnt[ES_CNT_CAPPED];
+          AS.n_inconsistent += h_cnt[ES_CNT_BROKEN];
+          AS.max_d = std::max<uint64_t>(AS.max_d, h_cnt[ES_CNT_MAXD]);
+          AS.x_columns += h_xid[0];
+          AS.d_columns += h_xid[1];
+          AS.i_columns += h_xid[2];
+          AS.script_words += Wn;
+        }
         STAGE_HIP(c, hipStreamSynchronize(st)); // (the plan goes with this scope)
       }
     }
@@ -922,6 +1118,14 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
     STAGE_HIP(c, clock.end());
   }
   STAGE_HIP(c, hipStreamSynchronize(st));
+  if (cigar && R.res->c_head.size() < R.res->chains.size()) { // a batch without a segment pair: a chain is its seed columns
+    try {
+      for (size_t i = R.res->c_head.size(); i < R.res->chains.size(); ++i) {
+        R.res->c_head.push_back(R.res->chains[i].matches);
+        R.res->c_poff.push_back(R.res->p_lt.size());
+      }
+    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  }
   clock.collect();
   bt.bytes_peak = B.peak;
   return MSGPU_OK;
@@ -1113,7 +1317,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   for (;;) {
     res->budget = budget;
     res->batches.clear();
-    const uint32_t bad = mp_cut(exact, apre, bpre, NR, budget, res->batches);
+    const uint32_t bad = mp_cut(prm, apre, bpre, NR, budget, res->batches);
     if (bad < NR) {
       const uint64_t a = apre[bad + 1] - apre[bad], b = bpre[bad + 1] - bpre[bad];
       if (a >= (1ull << 31)) {
@@ -1123,7 +1327,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
       }
       snprintf(c->err, sizeof(c->err), "query record %u with %llu anchors and %llu bases needs %llu bytes on its own (%llu of them for its "
                "oriented copies); the budget of a batch is %llu bytes (rule 9: a record is not split)", bad, static_cast<kf_ull>(a),
-               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(exact, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
+               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(prm, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
                static_cast<kf_ull>(budget));
       return MSGPU_E_NOMEM;
     }
@@ -1166,16 +1370,47 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
     unsigned nt = std::thread::hardware_concurrency();
     nt          = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
     if (C_n < 4096) nt = 1;
-    std::vector<std::string> part(nt);
+    const bool cigar = prm.cigar != 0;
+    std::vector<std::string>           part(nt);
+    std::vector<std::vector<uint32_t>> part_ops(nt), part_cnt(nt); // cigar mode: the packed runs of a range, and how many per chain
+    std::vector<float>                 part_ms(nt, 0.f);
     msgpu::HostPool::get().run(nt, nt, [&](size_t t) {
       const uint64_t a = static_cast<uint64_t>(C_n) * t / nt, b = static_cast<uint64_t>(C_n) * (t + 1) / nt;
       part[t].reserve((b - a) * 112);
-      for (uint64_t i = a; i < b; ++i) mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t]);
+      std::vector<std::pair<uint32_t, uint64_t>> runs;
+      for (uint64_t i = a; i < b; ++i) {
+        if (!cigar) {
+          mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t]);
+          continue;
+        }
+        const StageTimer merging;
+        mp_runs(*res, i, runs);
+        uint32_t n_packed = 0;
+        for (const auto &r : runs) // (a run of 2^28 columns or more takes several entries of the table: 28 bits of length)
+          for (uint64_t left = r.second; left; ++n_packed) {
+            const uint64_t piece = std::min<uint64_t>(left, (1ull << 28) - 1);
+            part_ops[t].push_back(static_cast<uint32_t>(piece << 4) | r.first);
+            left -= piece;
+          }
+        part_cnt[t].push_back(n_packed);
+        part_ms[t] += merging.ms();
+        mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], &runs);
+      }
     });
     size_t total = 0;
     for (const std::string &p : part) total += p.size();
     res->text.reserve(total);
     for (const std::string &p : part) res->text += p;
+    if (cigar) {
+      for (unsigned t = 0; t < nt; ++t) {
+        res->cg_ops.insert(res->cg_ops.end(), part_ops[t].begin(), part_ops[t].end());
+        for (uint32_t n : part_cnt[t]) res->cg_off.push_back(res->cg_off.back() + n);
+        res->astats.cigar_host_ms += part_ms[t];
+      }
+      res->astats.n_runs     = res->cg_ops.size();
+      res->astats.slots      = edit_script_slots();
+      res->astats.lds_max_d  = edit_script_lds_max_d();
+    }
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   S.host_ms   = formatting.ms();
   S.bytes_out = res->text.size();
@@ -1193,7 +1428,9 @@ void msgpu_map_default_params(msgpu_map_params *p) {
 }
 
 uint64_t msgpu_map_batch_bytes(const msgpu_map_params *p, uint64_t n_anchors, uint64_t n_query_bases) {
-  return mp_batch_bytes(p && p->exact, n_anchors, n_query_bases);
+  msgpu_map_params prm{};
+  if (p) prm = *p;
+  return mp_batch_bytes(prm, n_anchors, n_query_bases);
 }
 
 int  msgpu_map_create(int device, msgpu_mapctx **out) { return stage_create(device, out); }
@@ -1203,10 +1440,11 @@ const char *msgpu_map_last_error(const msgpu_mapctx *c) { return c ? c->err : "n
 
 static int mp_check_params(msgpu_mapctx *c, const msgpu_map_params &p) {
   if (p.k < 4 || p.k > 32 || p.w < 1 || p.w > 64 || p.max_occ < 1 || p.max_gap < 0 || p.bandwidth < 0 || p.max_pred != 64 ||
-      p.band < 1 || p.band > 127 || (p.exact != 0 && p.exact != 1) || (p.ava != 0 && p.ava != 1)) {
+      p.band < 1 || p.band > 127 || (p.exact != 0 && p.exact != 1) || (p.ava != 0 && p.ava != 1) || (p.cigar != 0 && p.cigar != 1) ||
+      (p.cigar && !p.exact)) {
     snprintf(c->err, sizeof(c->err), "parameters: k = %d (4..32), w = %d (1..64), max_occ = %u (>= 1), max_gap = %d, bandwidth = %d "
-             "(>= 0), max_pred = %d (64), band = %d (1..127), exact = %d, ava = %d (0 / 1)", p.k, p.w, p.max_occ, p.max_gap, p.bandwidth,
-             p.max_pred, p.band, p.exact, p.ava);
+             "(>= 0), max_pred = %d (64), band = %d (1..127), exact = %d, ava = %d (0 / 1), cigar = %d (0 / 1; 1 needs exact = 1)", p.k, p.w,
+             p.max_occ, p.max_gap, p.bandwidth, p.max_pred, p.band, p.exact, p.ava, p.cigar);
     return MSGPU_E_ARG;
   }
   return MSGPU_OK;
@@ -1356,6 +1594,20 @@ int msgpu_map_result_batches(const msgpu_map_result *r, const msgpu_map_batch **
 }
 
 uint64_t msgpu_map_result_budget(const msgpu_map_result *r) { return r ? r->budget : 0; }
+
+int msgpu_map_result_cigars(const msgpu_map_result *r, const uint32_t **ops, const uint64_t **off, uint64_t *n) {
+  if (!r || !ops || !off || !n) return MSGPU_E_ARG;
+  *ops = r->cg_ops.data();
+  *off = r->cg_off.data();
+  *n   = r->cg_off.size() - 1;
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_align_stats(const msgpu_map_result *r, msgpu_map_astats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->astats;
+  return MSGPU_OK;
+}
 
 const char *msgpu_map_result_text(const msgpu_map_result *r, uint64_t *len) {
   if (len) *len = r ? r->text.size() : 0;

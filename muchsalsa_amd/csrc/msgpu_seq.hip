@@ -1315,6 +1315,49 @@ __device__ __forceinline__ int match_run8(const uint8_t *pa, const uint8_t *pb, 
   return r;
 }
 
+// The slides of one row, shared by the distance and the script kernels: every lane's points nf[c] (negative: none) on the
+// diagonals |k| <= R move along the common prefix of a[x..) and b[x + k..), lane-local first, then at the wavefront's width
+__device__ __forceinline__ void fr_slide_row(const uint8_t *a, int n, const uint8_t *b, int m, int R, int lane, int (&nf)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (!(64 * c - 128 <= R && 64 * c - 65 >= -R)) continue; // (uniform: none of this c's diagonals is in reach)
+    const int k = lane + 64 * c - 128;
+    int       x = nf[c];
+    bool      more = false;
+    if (x >= 0) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int valid = min(8, min(n - x, m - (x + k)));
+        const int run   = match_run8(a + x, b + (x + k), valid);
+        x += run;
+        more = run == 8;
+        if (!more) break;
+      }
+    }
+    unsigned long long mask = __ballot(more);
+    while (mask) { // the diagonals that keep matching, one after the other at the wavefront's width
+      const int L = __builtin_ctzll(mask);
+      mask &= mask - 1;
+      int       xs = __shfl(x, L);
+      const int kk = L + 64 * c - 128;
+      for (;;) {
+        const int px    = xs + 8 * lane;
+        const int valid = min(8, min(n - px, m - (px + kk)));
+        const int run   = valid > 0 ? match_run8(a + px, b + (px + kk), valid) : 0;
+        const unsigned long long stop = __ballot(run < 8);
+        if (stop) {
+          const int F = __builtin_ctzll(stop);
+          xs += 8 * F + __shfl(run, F);
+          break;
+        }
+        xs += 512;
+      }
+      if (lane == L) x = xs;
+    }
+    nf[c] = x;
+  }
+}
+
 __device__ __forceinline__ uint32_t edit_distance_fr_wave(const uint8_t *a, int n, const uint8_t *b, int m, int W) {
   const int lane = threadIdx.x & 63;
   const int ks   = m - n;
@@ -1342,45 +1385,7 @@ __device__ __forceinline__ uint32_t edit_distance_fr_wave(const uint8_t *a, int 
       }
       nf[c] = x;
     }
-    const int R = e < W ? e : W; // diagonals |k| <= R can hold a point
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (!(64 * c - 128 <= R && 64 * c - 65 >= -R)) continue; // (uniform: none of this c's diagonals is in reach)
-      const int k = lane + 64 * c - 128;
-      int       x = nf[c];
-      bool      more = false;
-      if (x >= 0) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int valid = min(8, min(n - x, m - (x + k)));
-          const int run   = match_run8(a + x, b + (x + k), valid);
-          x += run;
-          more = run == 8;
-          if (!more) break;
-        }
-      }
-      unsigned long long mask = __ballot(more);
-      while (mask) { // the diagonals that keep matching, one after the other at the wavefront's width
-        const int L = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        int       xs = __shfl(x, L);
-        const int kk = L + 64 * c - 128;
-        for (;;) {
-          const int px    = xs + 8 * lane;
-          const int valid = min(8, min(n - px, m - (px + kk)));
-          const int run   = valid > 0 ? match_run8(a + px, b + (px + kk), valid) : 0;
-          const unsigned long long stop = __ballot(run < 8);
-          if (stop) {
-            const int F = __builtin_ctzll(stop);
-            xs += 8 * F + __shfl(run, F);
-            break;
-          }
-          xs += 512;
-        }
-        if (lane == L) x = xs;
-      }
-      nf[c] = x;
-    }
+    fr_slide_row(a, n, b, m, e < W ? e : W, lane, nf);
 #pragma unroll
     for (int c = 0; c < 4; ++c) fr[c] = nf[c];
     const int slot = ks + 128, cs = slot >> 6;
@@ -1404,6 +1409,197 @@ __global__ __launch_bounds__(256) void k_edit_distance(const uint8_t *base_a, co
 void launch_edit_distance_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
                                 uint32_t band, uint32_t *d_out) {
   if (n) hipLaunchKernelGGL(k_edit_distance, dim3((n + 3) / 4), dim3(256), 0, st, d_a, d_b, d_pairs, n, band, d_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The edit script of a pair whose distance d <= band is known (include/msgpu.h, "unitig-to-read mapping", rule 10): the
+// furthest-reaching table once more, rows 0..d, this time with rule 10's validity tests (only candidates that stay inside
+// the matrix enter) and remembered: cell (e, k) is word e * e + k + e of a table of (d + 1)^2 words and holds op << 30 | G.
+// The walk back from (d, m - n) is d dependent reads of that table: every lane follows it (the address is uniform), lane 0
+// writes word e of the script.  Two classes of pairs: d <= ES_LDS_MAXD keeps the table in LDS, 4 KiB per wavefront, four
+// wavefronts to a workgroup (16 KiB of the CU's 160 KiB: LDS does not limit the waves per SIMD; the VGPRs do, see the
+// table of resources in DESIGN.md section 12); a larger d keeps it in a slot of (band + 1)^2 words of a slab in device
+// memory, one slot per wavefront, and the wavefronts go through their class's pairs with the stride of the slots, so the
+// slab does not grow with the input (a band of at most ES_LDS_MAXD has no such pairs and no slab).
+// What the table must satisfy because d is the pair's distance (|m - n| <= d, G_d[m - n] = n, every op of the walk leads
+// into row e - 1) is tested where a read or a write depends on it, and a pair that fails a test is counted in
+// cnt[ES_CNT_BROKEN], which the callers report: nothing is skipped silently.
+// ---------------------------------------------------------------------------------------------------------------------
+
+constexpr int      ES_LDS_MAXD = 31;          // (ES_LDS_MAXD + 1)^2 words = 4 KiB
+constexpr uint32_t ES_SLOTS    = 1024;        // slots of the slab (MSGPU_ALIGN_SLOTS lowers it)
+constexpr uint32_t ES_RUN      = 0x3fffffffu; // the low 30 bits of a word: G in the table, a run of '=' in the script
+enum { ES_X = 1, ES_D = 2, ES_I = 3 };
+
+__device__ __forceinline__ void edit_script_wave(const uint8_t *a, int n, const uint8_t *b, int m, int d, uint32_t *T, bool in_lds,
+                                                 uint32_t *out, uint32_t *broken) {
+  const int lane = threadIdx.x & 63;
+  const int ks   = m - n;
+  if ((ks < 0 ? -ks : ks) > d) { // (the walk would start outside row d)
+    if (lane == 0) atomicAdd(broken, 1u);
+    return;
+  }
+  int fr[4] = {FR_NONE, FR_NONE, FR_NONE, FR_NONE};
+  for (int e = 0; e <= d; ++e) {
+    int      nf[4];
+    uint32_t op[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int k = lane + 64 * c - 128;
+      int       x = FR_NONE;
+      uint32_t  o = 0;
+      if (e == 0) {
+        if (k == 0) x = 0;
+      } else {
+        int lo = __shfl_up(fr[c], 1), hi = __shfl_down(fr[c], 1); // diagonals k - 1, k + 1
+        const int lo_edge = c > 0 ? __shfl(fr[c > 0 ? c - 1 : 0], 63) : FR_NONE;
+        const int hi_edge = c < 3 ? __shfl(fr[c < 3 ? c + 1 : 3], 0) : FR_NONE;
+        if (lane == 0) lo = lo_edge;
+        if (lane == 63) hi = hi_edge;
+        if ((k < 0 ? -k : k) <= e) { // rule 10: the largest valid candidate, the first of X, D, I on a tie
+          if (fr[c] >= 0 && fr[c] < min(n, m - k)) {
+            x = fr[c] + 1;
+            o = ES_X;
+          }
+          if (hi >= 0 && hi < n && hi + 1 > x) {
+            x = hi + 1;
+            o = ES_D;
+          }
+          if (lo >= 0 && lo + k <= m && lo > x) {
+            x = lo;
+            o = ES_I;
+          }
+        }
+      }
+      nf[c] = x;
+      op[c] = o;
+    }
+    fr_slide_row(a, n, b, m, e, lane, nf);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int k = lane + 64 * c - 128;
+      if ((k < 0 ? -k : k) <= e && nf[c] >= 0) T[e * e + k + e] = (op[c] << 30) | static_cast<uint32_t>(nf[c]);
+      fr[c] = nf[c];
+    }
+  }
+  // the table was written by all lanes and is read by each: LDS needs the wavefront's order, device memory the device's
+  if (in_lds) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __threadfence();
+  }
+  int      k = ks;
+  uint32_t w = T[d * d + k + d], carry = 0;
+  bool     bad = (w & ES_RUN) != static_cast<uint32_t>(n); // row d does not end the pair: d is not its distance
+  for (int e = d; e >= 1; --e) {
+    const uint32_t o  = w >> 30;
+    const int      ko = o == ES_X ? k : o == ES_D ? k + 1 : k - 1;
+    const int      kp = max(-(e - 1), min(e - 1, ko)); // (no read leaves the table)
+    bad |= o == 0 || kp != ko;
+    const uint32_t wp = T[(e - 1) * (e - 1) + kp + (e - 1)];
+    const uint32_t x0 = (wp & ES_RUN) + (o != ES_I ? 1u : 0u);
+    if (lane == 0) out[e] = (carry << 30) | (((w & ES_RUN) - x0) & ES_RUN);
+    carry = o;
+    k     = kp;
+    w     = wp;
+  }
+  if (lane == 0) {
+    out[0] = (carry << 30) | (w & ES_RUN);
+    if (bad) atomicAdd(broken, 1u);
+  }
+}
+
+template <bool IN_LDS>
+__global__ __launch_bounds__(256) void k_edit_script(const uint8_t *base_a, const uint8_t *base_b, const msgpu_align_pair *pairs,
+                                                     const uint32_t *dist, const uint64_t *off, const uint32_t *list, uint32_t n_pairs,
+                                                     uint32_t *cnt, uint32_t W, uint32_t *slab, uint32_t slots, uint32_t *words) {
+  __shared__ uint32_t s_t[IN_LDS ? 4 : 1][IN_LDS ? (ES_LDS_MAXD + 1) * (ES_LDS_MAXD + 1) : 1];
+  const uint32_t wave = threadIdx.x >> 6, wv = blockIdx.x * 4 + wave;
+  if (IN_LDS) {
+    if (wv >= min(cnt[ES_CNT_LDS], n_pairs)) return; // (whole wavefronts leave)
+    const uint32_t         p = list[wv]; // (k_edit_script_classes wrote the first cnt[ES_CNT_LDS] entries)
+    const msgpu_align_pair pr = pairs[p];
+    const uint32_t         d = dist[p];
+    if (d < 1 || d > static_cast<uint32_t>(ES_LDS_MAXD)) { // (the table would not fit its slice)
+      if ((threadIdx.x & 63) == 0) atomicAdd(&cnt[ES_CNT_BROKEN], 1u);
+      return;
+    }
+    edit_script_wave(base_a + pr.a_off, static_cast<int>(pr.a_len), base_b + pr.b_off, static_cast<int>(pr.b_len), static_cast<int>(d),
+                     s_t[wave], true, words + off[p], &cnt[ES_CNT_BROKEN]);
+  } else {
+    if (wv >= slots) return;
+    uint32_t *const T = slab + static_cast<uint64_t>(wv) * (W + 1) * (W + 1);
+    const uint32_t  n_cls = min(cnt[ES_CNT_SLAB], n_pairs);
+    for (uint32_t i = wv; i < n_cls; i += slots) { // (the class's list grows from the back of `list`)
+      const uint32_t         p = list[n_pairs - 1 - i];
+      const msgpu_align_pair pr = pairs[p];
+      const uint32_t         d = dist[p];
+      if (d < 1 || d > W) { // (the table would not fit its slot)
+        if ((threadIdx.x & 63) == 0) atomicAdd(&cnt[ES_CNT_BROKEN], 1u);
+        continue;
+      }
+      edit_script_wave(base_a + pr.a_off, static_cast<int>(pr.a_len), base_b + pr.b_off, static_cast<int>(pr.b_len), static_cast<int>(d),
+                       T, false, words + off[p], &cnt[ES_CNT_BROKEN]);
+    }
+  }
+}
+
+// a thread per pair: its class; a pair without an edit gets its one word here (no table is needed)
+__global__ __launch_bounds__(256) void k_edit_script_classes(const msgpu_align_pair *pairs, const uint32_t *dist, const uint64_t *off,
+                                                             uint32_t n, uint32_t W, uint32_t *list, uint32_t *cnt, uint32_t *words) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t d = dist[i];
+  if (d > W) {
+    atomicAdd(&cnt[ES_CNT_CAPPED], 1u);
+    return;
+  }
+  atomicMax(&cnt[ES_CNT_MAXD], d);
+  if (d == 0) {
+    words[off[i]] = pairs[i].a_len;
+    atomicAdd(&cnt[ES_CNT_D0], 1u);
+  } else if (d <= static_cast<uint32_t>(ES_LDS_MAXD)) {
+    list[atomicAdd(&cnt[ES_CNT_LDS], 1u)] = i;
+  } else {
+    list[n - 1 - atomicAdd(&cnt[ES_CNT_SLAB], 1u)] = i;
+  }
+}
+
+// the words of every pair's script, and a zero behind them: their exclusive scan gives the offsets
+__global__ __launch_bounds__(256) void k_edit_script_lengths(const uint32_t *dist, uint32_t n, uint32_t W, uint32_t *len) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  len[i] = i < n && dist[i] <= W ? dist[i] + 1 : 0;
+}
+
+void launch_edit_script_lengths(hipStream_t st, const uint32_t *d_dist, uint32_t n, uint32_t band, uint32_t *d_len) {
+  hipLaunchKernelGGL(k_edit_script_lengths, dim3(n / 256 + 1), dim3(256), 0, st, d_dist, n, band, d_len);
+}
+
+uint32_t edit_script_slots() {
+  const char *s = std::getenv("MSGPU_ALIGN_SLOTS");
+  const long  v = s ? std::strtol(s, nullptr, 10) : 0;
+  return v >= 1 && v < static_cast<long>(ES_SLOTS) ? static_cast<uint32_t>(v) : ES_SLOTS;
+}
+uint64_t edit_script_slab_words(uint32_t slots, uint32_t band) { // (a band within the LDS class has no slab class)
+  return band > static_cast<uint32_t>(ES_LDS_MAXD) ? static_cast<uint64_t>(slots) * (band + 1) * (band + 1) : 0;
+}
+uint32_t edit_script_lds_max_d() { return ES_LDS_MAXD; }
+
+hipError_t launch_edit_script_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
+                                    uint32_t band, const uint32_t *d_dist, const uint64_t *d_off, uint32_t *d_list, uint32_t *d_cnt,
+                                    uint32_t *d_slab, uint32_t slots, uint32_t *d_words) {
+  hipError_t e = hipMemsetAsync(d_cnt, 0, ES_CNT_COUNT * sizeof(uint32_t), st);
+  if (e != hipSuccess || !n) return e;
+  hipLaunchKernelGGL(k_edit_script_classes, dim3((n + 255) / 256), dim3(256), 0, st, d_pairs, d_dist, d_off, n, band, d_list, d_cnt, d_words);
+  hipLaunchKernelGGL((k_edit_script<true>), dim3((n + 3) / 4), dim3(256), 0, st, d_a, d_b, d_pairs, d_dist, d_off, d_list, n, d_cnt, band,
+                     d_slab, slots, d_words);
+  if (band > static_cast<uint32_t>(ES_LDS_MAXD) && slots && d_slab)
+    hipLaunchKernelGGL((k_edit_script<false>), dim3((slots + 3) / 4), dim3(256), 0, st, d_a, d_b, d_pairs, d_dist, d_off, d_list, n, d_cnt,
+                       band, d_slab, slots, d_words);
+  return hipGetLastError();
 }
 
 const uint8_t *seq_store_bases(const msgpu_seqctx *c, int kind, uint64_t *n_bases) {
@@ -1447,6 +1643,70 @@ int msgpu_edit_distance(msgpu_seqctx *c, const void *d_a, const void *d_b, const
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return stage_fail(c, MSGPU_E_HIP, "msgpu_edit_distance", e);
+  return MSGPU_OK;
+}
+
+int msgpu_edit_script(msgpu_seqctx *c, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n, uint32_t band,
+                      uint32_t *dist, uint64_t *off, uint32_t *words, uint64_t capacity, uint64_t *n_words) {
+  if (!c || !n_words || !off || (n && (!pairs || !dist || !d_a || !d_b)) || (capacity && !words) || band > ED_MAXW || n >= 0x7fffffffull)
+    return MSGPU_E_ARG;
+  if (c->device < 0) return MSGPU_E_NODEVICE;
+  *n_words = 0;
+  off[0]   = 0;
+  if (!n) return MSGPU_OK;
+  for (size_t i = 0; i < n; ++i)
+    if (pairs[i].a_len >= (1u << 30) || pairs[i].b_len >= (1u << 30)) return MSGPU_E_ARG; // (positions are ints on the device)
+  STAGE_HIP(c, hipSetDevice(c->device));
+  DevArena          D; // (freed on every way out)
+  hipStream_t       st = c->stream;
+  const uint32_t    np = static_cast<uint32_t>(n), slots = edit_script_slots();
+  msgpu_align_pair *d_pairs;
+  uint32_t         *d_dist, *d_len, *d_list, *d_cnt, *d_slab, *d_words;
+  uint64_t         *d_off;
+  STAGE_HIP(c, D.get(&d_pairs, n));
+  STAGE_HIP(c, D.get(&d_dist, n));
+  STAGE_HIP(c, D.get(&d_len, n + 1));
+  STAGE_HIP(c, D.get(&d_off, n + 1));
+  STAGE_HIP(c, D.get(&d_list, n));
+  STAGE_HIP(c, D.get(&d_cnt, ES_CNT_COUNT));
+  STAGE_HIP(c, hipMemcpyAsync(d_pairs, pairs, n * sizeof(msgpu_align_pair), hipMemcpyHostToDevice, st));
+  launch_edit_distance_pairs(st, static_cast<const uint8_t *>(d_a), static_cast<const uint8_t *>(d_b), d_pairs, np, band, d_dist);
+  launch_edit_script_lengths(st, d_dist, np, band, d_len);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_len, d_off, n + 1));
+  STAGE_HIP(c, hipMemcpyAsync(dist, d_dist, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(off, d_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  const uint64_t total = off[n];
+  *n_words = total;
+  if (total > capacity) {
+    snprintf(c->err, sizeof(c->err), "msgpu_edit_script: the scripts take %llu words, the caller has room for %llu",
+             static_cast<unsigned long long>(total), static_cast<unsigned long long>(capacity));
+    return MSGPU_E_ARG;
+  }
+  uint32_t n_slab = 0; // the pairs of the slab class: no more slots than these, and no slab without them
+  for (size_t i = 0; i < n && n_slab < slots; ++i) n_slab += dist[i] > edit_script_lds_max_d() && dist[i] <= band;
+  const uint32_t used       = std::min(slots, n_slab);
+  const uint64_t slab_words = edit_script_slab_words(used, band);
+  STAGE_HIP(c, D.get(&d_words, total));
+  d_slab = nullptr;
+  if (slab_words) STAGE_HIP(c, D.get(&d_slab, slab_words));
+  if (std::getenv("MSGPU_POISON")) { // (see DevBuf::ensure in msgpu_api.hip)
+    if (slab_words) STAGE_HIP(c, hipMemsetAsync(d_slab, 0xA5, slab_words * 4, st));
+    STAGE_HIP(c, hipMemsetAsync(d_words, 0xA5, (total ? total : 1) * 4, st));
+    STAGE_HIP(c, hipMemsetAsync(d_list, 0xA5, n * 4, st));
+  }
+  STAGE_HIP(c, launch_edit_script_pairs(st, static_cast<const uint8_t *>(d_a), static_cast<const uint8_t *>(d_b), d_pairs, np, band, d_dist,
+                                        d_off, d_list, d_cnt, d_slab, used, d_words));
+  uint32_t h_cnt[ES_CNT_COUNT];
+  if (total) STAGE_HIP(c, hipMemcpyAsync(words, d_words, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  if (h_cnt[ES_CNT_BROKEN]) {
+    snprintf(c->err, sizeof(c->err), "msgpu_edit_script: the tables of %u pairs contradict their distances (a defect of the kernels)",
+             h_cnt[ES_CNT_BROKEN]);
+    return MSGPU_E_STATE;
+  }
   return MSGPU_OK;
 }
 

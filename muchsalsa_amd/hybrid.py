@@ -82,10 +82,12 @@ def link_input(path, directory, prefix="00_"):
     return link
 
 
-def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0):
+def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
-    total ``seconds``.  ``bloom_mem`` is ignored."""
+    total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
+    ``cg:Z:`` strings (muchsalsa_amd.mapper's rule 10), as pipeline.sh:175's ``-c --eqx`` asks for; every file written before
+    that PAF is the same."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -128,7 +130,7 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     finally:
         index.__exit__(None, None, None)
     stage("scrubber", scrubber.run, files["corrected_paf"], reads, files["scrubbed"], files["ava_paf"], device=device)
-    stage("map_exact", mapper.run, files["scrubbed"], files["corrected"], files["exact_paf"], device=device, exact=1)
+    stage("map_exact", mapper.run, files["scrubbed"], files["corrected"], files["exact_paf"], device=device, exact=1, cigar=1 if cigar else 0)
     stage("assembly", pipeline.run, files["exact_paf"], files["corrected"], files["scrubbed"], os.path.join(out, "tmp"),
           threads=int(cores), device=device)
     shutil.copyfile(files["target"], files["assembly"])  # pipeline.sh:181

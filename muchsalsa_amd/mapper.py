@@ -1,17 +1,20 @@
 """The pipeline's mapping step on the GPU: what its four ``minimap2 -k15 -w5 -m100 -g10000 -r2000 --max-chain-skip 25`` calls
 write -- a PAF of every record of a query file against every record of a target file, by minimizer seeds and a chaining DP.
 
-    python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--ava]
+    python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--cigar] [--ava]
             [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
 
 prints one JSON line of counts and seconds.  ``--budget-mb`` (N > 0) bounds the device memory of a batch of query records
 (rule 9; without it: the free device memory).  With ``--ava`` the two paths name the same file (the reads against
 themselves: the read-to-read PAF muchsalsa_amd.scrubber takes as its fourth input); ``--exact`` adds the base-level match
-count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call).  minimap2 is not needed, and it is not part of
+count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call); ``--cigar`` (which implies ``--exact``) aligns
+every segment base by base (rule 10): column 10 is then the number of ``=`` columns, column 11 the number of alignment columns,
+and the line ends in a ``cg:Z:`` string of ``=``, ``X``, ``I`` and ``D`` runs.  minimap2 is not needed, and it is not part of
 the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
 tests' restatement in plain Python (tests/map_oracle.py), not against minimap2.  The rules (include/msgpu.h,
 "unitig-to-read mapping"); parameters k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth
-(2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1):
+(2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1); cigar (0 / 1)
+is a keyword of ``run`` beside them:
 
  1. windows: the alphabet, case folding, 2-bit code, canonical key (min(fw, rc) as 2k-bit numbers) and the break at any
     other byte are those of the k-mer filter's rolling window (KfRoll).  A stretch is a maximal run of k-mer start
@@ -66,6 +69,32 @@ tests' restatement in plain Python (tests/map_oracle.py), not against minimap2. 
     record that exceeds the budget on its own is MSGPU_E_NOMEM, one with 2^31 anchors or more MSGPU_E_ARG, naming the
     record, its anchors and the bytes against the budget.  Splitting one query record over ranges of targets, and
     splitting the index, are out of scope.
+10. the alignment of one segment pair, and cigar mode (cigar = 1, which needs exact = 1).  a is the target bytes, n of them,
+    b the oriented query bytes, m of them, compared as the stores hold them (rule 7); ks = m - n; slide(i, k) is the largest
+    i' >= i with a[i..i') == b[i+k..i'+k), i' <= n, i'+k <= m.  The table: G_0[0] = slide(0, 0) and nothing else is defined
+    in row 0.  For e >= 1 and |k| <= e the candidates of cell (e, k) are X: G_{e-1}[k] + 1, valid iff G_{e-1}[k] is defined
+    and < min(n, m - k); D (a target base without a query base): G_{e-1}[k+1] + 1, valid iff G_{e-1}[k+1] is defined and
+    < n; I (a query base without a target base): G_{e-1}[k-1], valid iff it is defined and G_{e-1}[k-1] + k <= m.
+    x0(e, k) is the largest valid candidate (none: the cell is undefined), G_e[k] = slide(x0, k), and the cell's op is the
+    first of X, D, I whose candidate is valid and equals x0.  d is the first e with G_e[ks] = n; the pair is capped when
+    |ks| > band or no such e <= band exists, and then d_i = band + 1 as in rule 7.  The script is read backwards from
+    (d, ks): G_e[k] - x0 ``=`` columns lie behind the cell's op, which leads to (e-1, k) for X, (e-1, k+1) for D,
+    (e-1, k-1) for I; row 0 ends the walk with G_0[0] leading ``=`` columns.  Only valid candidates enter: one that would
+    step outside the matrix is no edit (rule 7's clamped recurrence may hold such values; they are harmless for the number,
+    not for a script).  The script has exactly d columns that are not ``=``, every ``=`` column holds equal bytes and every
+    X column unequal ones, and it consumes exactly n and m bytes.  With cigar = 1 a chain's alignment is k ``=`` columns
+    for anchor 0, then for every link in rising order the segment's script followed by c_i ``=`` columns (seed bases:
+    ``=`` by rule 1's case folding even where the bytes differ in case); a link with lt_i = lq_i = 0 has no segment; a
+    capped segment is written lt_i D then lq_i I, zero lengths left out; neighbouring runs of one letter are merged.
+    matches = the ``=`` columns, block = all columns, nm = block - matches.  The line is the twelve columns, cm, s1,
+    NM:i:<nm>, then cg:Z:<runs> in target-forward order, which is the oriented query's order on both strands.  The runs
+    consume exactly t_end - t_start target bases and q_end - q_start query bases; for a chain without a capped segment
+    matches is at least rule 7's exact-mode value (a segment has at least max(lt, lq) columns, d of them no ``=``).  Rule 9
+    with cigar = 1: msgpu_map_batch_bytes adds the slab of the scripts' tables (slots * (band + 1)^2 words, a constant
+    number of slots that MSGPU_ALIGN_SLOTS=<n> lowers; no slab for a band of at most 31, whose tables all lie in LDS) to
+    the fixed part and, per anchor, band + 1 words of script, the
+    64-bit offset, the script length, the class list entry, the ``=`` columns behind the segment and the two column
+    counts.  Without cigar every byte of every output is as before.
 
 Known differences from minimap2, none of which could be checked against the program (it is not installed where this project
 is built):
@@ -78,8 +107,10 @@ is built):
 * no ``--dual`` / ``-D`` diagonal filtering beyond the ava rule;
 * no primary / secondary marking, as with ``-P``: all chains are kept;
 * no mapping quality (column 12 is 255);
-* no CIGAR: exact mode gives a match count that is a lower bound from unit-cost distances per link, not minimap2's count
-  of ``=`` columns;
+* no CIGAR without ``--cigar``: exact mode alone gives a match count that is a lower bound from unit-cost distances per
+  link, not minimap2's count of ``=`` columns.  With ``--cigar`` the columns are counted on a unit-cost alignment of every
+  segment between two seeds (rule 10), not on minimap2's affine-gap alignment, and a segment beyond the band is written
+  as a deletion and an insertion;
 * no end extension beyond the outermost seeds.
 
 ``Index(targets, k=, w=)`` is a context manager that keeps the targets' store, sketch and index on the device;
@@ -111,7 +142,8 @@ class MapError(StageError):
 
 def _params(p):
     return _lib.MapParams(int(p["k"]), int(p["w"]), int(p["max_occ"]), int(p["max_gap"]), int(p["bandwidth"]), 64,
-                          int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]), 0)
+                          int(p["min_score"]), int(p["min_count"]), int(p["exact"]), int(p["band"]), int(p["ava"]),
+                          int(p.get("cigar", 0)))
 
 
 class Index:
@@ -151,14 +183,17 @@ class Index:
         return False
 
 
-def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, **params):
+def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, **params):
     """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
     per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
     ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
     ava = 1, ``queries`` is None or ``targets``.  ``tables`` (a dict) receives ``chains``: per line of the PAF the tuple
     (query, target, strand, anchors, score, nm, q_start, q_end, t_start, t_end, matches, block) and ``text`` (bytes);
     ``timings`` (a dict) seconds per step.  With ``index`` (an entered Index) the run maps onto it: ``targets`` and ``device``
-    are not read, k and w default to the index's, and with ava = 1 ``queries`` is None."""
+    are not read, k and w default to the index's, and with ava = 1 ``queries`` is None.  ``cigar`` = 1 (rule 10; it needs
+    exact = 1) writes the base-level figures and a ``cg:Z:`` string per line; ``tables`` then also receives ``cigars`` (a list
+    of strings, one per line) and ``runs`` (per line the list of len << 4 | BAM code), and the returned dict's ``align``
+    holds the counts and seconds of msgpu_map_astats."""
     if index is not None:
         params = dict({"k": index.k, "w": index.w}, **params)
     unknown = set(params) - set(DEFAULTS)
@@ -173,7 +208,7 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             raise MapError(_lib.E_ARG, "%s = %d" % (name, int(v)))
     qpath = None if queries is None else os.fsencode(queries)
     with (stage_context("map", device, MapError) if index is None else contextlib.nullcontext(index.stage)) as stage:
-        prm = _params(p)
+        prm = _params(dict(p, cigar=cigar))
         with (stage.run(C.byref(prm), os.fsencode(targets), qpath, 0, budget) if index is None else
               stage.run(C.byref(prm), index.handle, qpath, 0, budget, fn="run_index")) as res:
             st = _lib.MapStats()
@@ -184,6 +219,8 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             L.msgpu_map_result_batches(res, C.byref(bp), C.byref(m))
             batches = [{f: int(getattr(bp[i], f)) for f, _ in _lib.MapBatch._fields_} for i in range(m.value)]
             budget_used = int(L.msgpu_map_result_budget(res))
+            ast = _lib.MapAlignStats()
+            L.msgpu_map_result_align_stats(res, C.byref(ast))
             if tables is not None:
                 cp = C.POINTER(_lib.MapChain)()
                 m = C.c_uint64()
@@ -191,6 +228,10 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
                 names = [f for f, _ in _lib.MapChain._fields_]
                 tables["chains"] = [tuple(int(getattr(cp[i], f)) for f in names) for i in range(m.value)]
                 tables["text"] = bytes(text)
+                ops, off, m = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+                L.msgpu_map_result_cigars(res, C.byref(ops), C.byref(off), C.byref(m))
+                tables["runs"] = [[int(ops[j]) for j in range(off[i], off[i + 1])] for i in range(m.value)]
+                tables["cigars"] = ["".join("%d%s" % (r >> 4, "MIDNSHP=X"[r & 15]) for r in runs) for runs in tables["runs"]]
             t1 = time.perf_counter()
             with open(out, "wb") as h:
                 h.write(text)
@@ -207,7 +248,9 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             "group_hist": [int(x) for x in st.group_hist], "chains": int(st.n_chains), "below_score": int(st.n_chains_below_score),
             "below_count": int(st.n_chains_below_count), "chains_cut": int(st.n_chains_cut), "pairs": int(st.n_pairs),
             "capped": int(st.n_pairs_capped), "lost_publications": int(st.n_lost_publications), "bytes_out": int(st.bytes_out),
-            "batches": batches, "budget_bytes": budget_used}
+            "batches": batches, "budget_bytes": budget_used, "cigar": int(st.params.cigar),
+            "align": dict({name: int(getattr(ast, name)) for name, t in _lib.MapAlignStats._fields_ if t is not C.c_float},
+                          seconds={name[:-3]: getattr(ast, name) / 1e3 for name, t in _lib.MapAlignStats._fields_ if t is C.c_float})}
 
 
 _OPTS = {"-k": "k", "-w": "w", "--max-occ": "max_occ", "--min-score": "min_score", "--min-count": "min_count",
@@ -220,6 +263,10 @@ def main(argv):
         if flag in args:
             args.remove(flag)
             p[flag[2:]] = 1
+    cigar = 0
+    if "--cigar" in args:  # (implies --exact)
+        args.remove("--cigar")
+        cigar = p["exact"] = 1
     for name, key in _OPTS.items():
         if name in args:
             i = args.index(name)
@@ -244,7 +291,7 @@ def main(argv):
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, **p)
+    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, **p)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0

@@ -239,3 +239,23 @@ class SeqStore:
         self._check(self._L.msgpu_edit_distance(self._h, C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), pairs.ctypes.data,
                                                 len(pairs), int(band), out.ctypes.data))
         return out
+
+    def edit_script(self, d_a_ptr, d_b_ptr, pairs, band):
+        """The edit script of every pair beside its distance (msgpu_edit_script; the mapper's rule 10) -> (dist, off, words):
+        pair p owns words[off[p]:off[p + 1]], dist[p] + 1 of them within the band (kind << 30 | the '=' columns in front of
+        the edit, kinds 1 = X, 2 = D, 3 = I; the last word is the trailing '=' run), none beyond it."""
+        from ._lib import ALIGN_PAIR_DTYPE, E_ARG
+        pairs = np.ascontiguousarray(pairs, dtype=ALIGN_PAIR_DTYPE)
+        dist = np.zeros(len(pairs), dtype="<u4")
+        off = np.zeros(len(pairs) + 1, dtype="<u8")
+        words = np.zeros(max(1, 4 * len(pairs)), dtype="<u4")
+        need = C.c_uint64()
+        for _ in range(2):  # (a second call with room when the first guess was too small)
+            rc = self._L.msgpu_edit_script(self._h, C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), pairs.ctypes.data, len(pairs),
+                                           int(band), dist.ctypes.data, off.ctypes.data, words.ctypes.data, len(words),
+                                           C.byref(need))
+            if rc != E_ARG or need.value <= len(words):
+                break
+            words = np.zeros(need.value, dtype="<u4")
+        self._check(rc)
+        return dist, off, words[:need.value]
