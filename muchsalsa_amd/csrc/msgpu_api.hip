@@ -25,6 +25,7 @@
 #include "host_pool.h"
 #include "msgpu.h"
 #include "msgpu_internal.h"
+#include "msgpu_stage.h"
 
 using namespace msgpu;
 
@@ -140,7 +141,7 @@ void host_table_pin(void *q) noexcept {
 
 namespace {
 
-struct DevBuf {
+struct DevBuf { // device memory that grows and is kept from job to job; gives itself back, moves, does not copy
   void  *p   = nullptr; // the allocation
   size_t cap = 0;       // its size in bytes
   // A buffer can be used as a VIEW that starts `off` bytes into the allocation: the job-wide result tables of a
@@ -153,6 +154,19 @@ struct DevBuf {
   // grows with them is freed and allocated again -- a device-wide synchronisation -- in every window of a first call)
   static inline thread_local double grow_by = 1.0;
   double own_grow_by = 0.0; // the same for this buffer alone (a job-wide result table while the job's FIRST window fills it)
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    std::swap(off, o.off);
+    std::swap(hint, o.hint);
+    std::swap(own_grow_by, o.own_grow_by);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
   hipError_t ensure(size_t bytes) { // room for `bytes` behind `off`
     if (off + bytes <= cap) return hipSuccess;
     const size_t need = off + bytes;
@@ -197,15 +211,22 @@ struct DevBuf {
     cap = want;
     return hipSuccess;
   }
-  void release() {
-    if (p) (void)hipFree(p);
-    p   = nullptr;
-    cap = 0;
-    off = hint = 0;
-  }
   template <class T> T *as() const { return reinterpret_cast<T *>(static_cast<char *>(p) + off); }
   void  *at() const { return static_cast<char *>(p) + off; }
   size_t room() const { return cap > off ? cap - off : 0; } // bytes behind `off`
+};
+
+struct HostBuf { // a page-locked host table (ensure_host); gives itself back, moves, does not copy
+  void  *p   = nullptr;
+  size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(HostBuf &&o) noexcept { *this = std::move(o); }
+  HostBuf &operator=(HostBuf &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~HostBuf() { pinned_block_free(p); }
 };
 
 enum State { ST_CREATED = 0, ST_LOADED = 1, ST_EDGES = 2, ST_CHAINED = 3,
@@ -213,18 +234,16 @@ enum State { ST_CREATED = 0, ST_LOADED = 1, ST_EDGES = 2, ST_CHAINED = 3,
 
 } // namespace
 
-struct msgpu_ctx {
-  int          device     = 0;
-  hipStream_t  stream     = nullptr;
+// `stream` (StageCtx) is the stream the calls use, which msgpu_set_stream may point at a caller's; own_stream is the one
+// stage_create made, and the one stage_destroy gets back.  Everything else the context owns is held by members that release it.
+struct msgpu_ctx : msgpu::StageCtx {
   hipStream_t  own_stream = nullptr;
   msgpu_params p;
-  char         err[512]   = {0};
   State        state      = ST_CREATED;
   uint32_t     shard = 0, nshards = 1;
   uint32_t     win_lo = 0, win_hi = 0xffffffffu; // owner-read window of the current batch (msgpu_overlap_batched)
   uint64_t     base_edges = 0, base_ems = 0, base_orders = 0, base_ids = 0; // what precedes it in the job's tables
-  uint64_t    *h_scalars = nullptr; // pinned, device-mapped mirror of `scalars` (+ one word: the read-back sequence number)
-  uint64_t    *h_scalars_dev = nullptr; // the same memory as the device sees it
+  ScalarBlock  sc; // made by open(), never moves; sc.h_dev: the stage-closing kernels publish it into its mirror (else: a copy)
   bool         stage_events = true; // the stage boundaries are marked with events (msgpu_set_stage_events)
   bool         chain_zeroed = false; // msgpu_calculate_edges zeroed the chain stage's per-edge counters
   bool         no_prologue = false; // msgpu_overlap_batched with several windows: every window has its own opening
@@ -240,11 +259,7 @@ struct msgpu_ctx {
   bool         cand_zeroed = false; // ... including the zeroing of the candidate kernels' counters (used up by the next msgpu_calculate_edges)
   uint64_t     prologue_bound = 0;
   uint32_t     prologue_lists[4] = {0, 0, 0, 0};
-  uint64_t     readback_seq = 0;
-  uint64_t     lost_publications = 0; // read-backs whose publication never arrived (wait_scalars fell back to a copy)
-  bool         readback_mapped = false; // the stage-closing kernels publish the scalar block into h_scalars (else: a copy)
-  hipEvent_t   ev_readback = nullptr; // the synchronising read-back path waits for the copy only
-  hipEvent_t   ev_order = nullptr;    // msgpu_stream_wait / msgpu_stream_release
+  EventHold    ev_order;              // msgpu_stream_wait / msgpu_stream_release
   uint32_t     decl_V = 0, decl_A = 0; // msgpu_set_id_space: id counts declared by the caller (0 = find them)
   // msgpu_set_deadline: the host waits of this context's calls give up at this point in time (a collective of the caller's
   // that never completes in front of our work on the stream must not hold a libms caller for ever)
@@ -262,12 +277,11 @@ struct msgpu_ctx {
 
   // arena
   DevBuf rows_in, rows_pk, cnt_read, read_off, cursor, bkt_key, bkt_dead, by_read, read_cnt, alive_rank,
-      anchor_cnt, anchor_off, anchor_first, anchor_off_gen, bkt2_idx, bkt2_line, by_anchor, read_len, read_first, scalars,
+      anchor_cnt, anchor_off, anchor_first, anchor_off_gen, bkt2_idx, bkt2_line, by_anchor, read_len, read_first,
       scan_tmp, vis16, spos2, visits, bin_cursor, bin_start;
   DevBuf bound, cand_off, cand_j, cand_t, scr_v2, scr_start, n_cand, n_edge, lists, edges, edge_cand;
   DevBuf big_key, big_t, big_r2s, big_pfx, pair_tab, chain_chunks, big_off, cand_sums, bucket_visits;
-  hipStream_t side_stream = nullptr, side_stream2 = nullptr;
-  hipEvent_t  ev_side[2]  = {nullptr, nullptr}, ev_side2 = nullptr;
+  EventHold ev_side[2], ev_side2;
   uint64_t    n_big_edges = 0, n_big_ems = 0;
   bool   fast_path = true;
   bool   chain_band = true; // the banded pair sweep of k_chain; MSGPU_NO_BAND=1 (or MSGPU_NO_FASTPATH=1) switches it off
@@ -284,14 +298,10 @@ struct msgpu_ctx {
   DevBuf sel_idx, sel_cnt, sel_off, sel_ems;          // msgpu_get_edgematches
 
   // batched execution (msgpu_overlap_batched): second set of output tables, copy stream, pinned result arena
-  DevBuf      alt_edges, alt_ems, alt_orders, alt_ids;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t  ev_done[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr}, ev_wall[2] = {nullptr, nullptr};
-  struct HostBuf {
-    void  *p   = nullptr;
-    size_t cap = 0;
-  } h_edges, h_ems, h_orders, h_ids, h_read_len, h_read_first, h_sel_off, h_sel_ems, h_wire[2];
-  hipEvent_t ev_part[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; // a window's wire blocks, copied one by one
+  DevBuf    alt_edges, alt_ems, alt_orders, alt_ids;
+  EventHold ev_done[2], ev_copied[2];
+  HostBuf   h_edges, h_ems, h_orders, h_ids, h_read_len, h_read_first, h_sel_off, h_sel_ems, h_wire[2];
+  EventHold ev_part[2][3]; // a window's wire blocks, copied one by one
   // how often the chain kernels have been launched: another thread can wait for the next launch (msgpu_wait_chain_launch) to
   // put its own device work beside the chain stage instead of beside the memory-bound stages before it
   std::mutex              gate_m;
@@ -302,17 +312,49 @@ struct msgpu_ctx {
   bool   wire_copy = true; // MSGPU_NO_WIRE_COPY=1: windows always leave as whole records (A/B switch)
 
   // timing
-  hipEvent_t ev[10] = {nullptr};
+  EventHold ev[10];
   // the two events around the chain kernels, one pair per msgpu_chaining_and_overlaps call in a ring: msgpu_get_timings
   // averages over the calls since the last msgpu_get_timings without having synchronised after each of them
   static constexpr int CK_RING = 256;
-  hipEvent_t ck_ev[CK_RING][2] = {};
+  EventHold  ck_ev[CK_RING][2]; // (created by the call that first uses a slot)
   uint32_t   ck_head = 0, ck_count = 0; // next slot; pairs recorded since the last msgpu_get_timings
   bool       have_index_t = false, have_cand_t = false, have_chain_t = false, index_fast = false;
   bool   have_stage_t = false;
   uint32_t index_path = 0;  // MSGPU_INDEX_* of the last index build
   bool     index_binned = false; // the last build_index_once ran the bin path's kernels
   bool     use_bin = true;  // try the bin path first (MSGPU_NO_BIN=1: never)
+  // The side streams carry the few heavy workgroups that run beside a stage's main kernel (large LDS classes, edges with more
+  // than 64 EdgeMatches), the copy stream a window's tables to the host.  Declared last: they are destroyed first, and have
+  // drained before any buffer above is freed.
+  StreamHold side_stream, side_stream2, copy_stream;
+  int        open() { // stage_create: everything the context owns beyond its stream
+    own_stream = stream;
+    if (int rc = sc.create()) return rc;
+    const char *nf = getenv("MSGPU_NO_FASTPATH"); // test hook: force the full pair sweep on every edge
+    fast_path      = !(nf && nf[0] == '1');
+    const char *nb = getenv("MSGPU_NO_BAND"); // test hook / way out: no banded pair sweep (the shortcut stays)
+    chain_band     = fast_path && !(nb && nb[0] == '1');
+    const char *ns = getenv("MSGPU_NO_SUBWAVE"); // test hook: one edge per wavefront whatever its size
+    sub_wave       = !(ns && ns[0] == '1');
+    const char *nw = getenv("MSGPU_NO_WIRE_COPY");
+    wire_copy      = !(nw && nw[0] == '1');
+    const char *nbin = getenv("MSGPU_NO_BIN"); // A/B switch: the index build's atomic path (rounds 1-3) for every input
+    use_bin          = !(nbin && nbin[0] == '1');
+    // measurement switches (any value)
+    use_prologue = !getenv("MSGPU_NO_PROLOGUE"); // no classification inside the index build
+    use_fork     = !getenv("MSGPU_NO_FORK");     // the candidate classes one after the other
+    chain_serial = getenv("MSGPU_CHAIN_SERIAL") != nullptr;
+    // the side streams have the highest priority, so that their work finishes first and the join never waits for it
+    int prio_least = 0, prio_greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_least = prio_greatest = 0;
+    bool ok = side_stream.create(hipStreamNonBlocking, prio_greatest) == hipSuccess &&
+              side_stream2.create(hipStreamNonBlocking, prio_greatest) == hipSuccess && copy_stream.create() == hipSuccess;
+    for (auto &e : ev) ok = ok && e.create() == hipSuccess; // (the stage boundaries: timed)
+    EventHold *const untimed[] = {&ev_order, &ev_side[0], &ev_side[1], &ev_side2, &ev_done[0], &ev_done[1], &ev_copied[0], &ev_copied[1],
+                                  &ev_part[0][0], &ev_part[0][1], &ev_part[0][2], &ev_part[1][0], &ev_part[1][1], &ev_part[1][2]};
+    for (EventHold *e : untimed) ok = ok && e->create(hipEventDisableTiming) == hipSuccess;
+    return ok ? MSGPU_OK : MSGPU_E_HIP;
+  }
 };
 
 namespace {
@@ -325,19 +367,9 @@ int fail(msgpu_ctx *c, int code, const char *fmt, ...) {
   return code;
 }
 
-#define HIPCHK(c, expr)                                                                                                \
-  do {                                                                                                                 \
-    hipError_t _e = (expr);                                                                                            \
-    if (_e != hipSuccess)                                                                                              \
-      return fail((c), _e == hipErrorOutOfMemory ? MSGPU_E_NOMEM : MSGPU_E_HIP, "%s failed: %s (%s:%d)", #expr,        \
-                  hipGetErrorString(_e), __FILE__, __LINE__);                                                          \
-  } while (0)
-
-#define ENSURE(c, buf, bytes) HIPCHK(c, (c)->buf.ensure(bytes))
-
-template <class T> T *scalar(msgpu_ctx *c, int slot) { return reinterpret_cast<T *>(c->scalars.as<uint64_t>() + slot); }
+template <class T> T *scalar(msgpu_ctx *c, int slot) { return reinterpret_cast<T *>(c->sc.d + slot); }
 // host value of a scalar slot after read_scalars()
-template <class T> const T *host_scalar(const msgpu_ctx *c, int slot) { return reinterpret_cast<const T *>(c->h_scalars + slot); }
+template <class T> const T *host_scalar(const msgpu_ctx *c, int slot) { return reinterpret_cast<const T *>(c->sc.h + slot); }
 // The candidate stage's per-chunk block (cand_sums): [chunks][2] 64-bit sums, then [chunks][64] 32-bit size histograms.
 static uint32_t cand_chunks(uint32_t V) { return (V + CAND_CHUNK - 1) / CAND_CHUNK; }
 static size_t   cand_sums_bytes(uint32_t V) { return static_cast<size_t>(cand_chunks(V) + 1) * (16 + 256); }
@@ -354,22 +386,13 @@ static CandZero cand_zero(msgpu_ctx *c, uint32_t V) {
   return z;
 }
 
-// The read-back of the scalar block, in one of two modes decided when the context is created (readback_mapped):
-// - mapped (default): no copy and no stream synchronisation -- the launch that closes a stage carries arm_readback()'s
-//   HostPublish, one wavefront of it writes the block into the mapped pinned mirror and publishes a sequence number
-//   (publish_to_host), the host polls for it (about half the latency of copy + synchronise, and the host is back on the
-//   stream sooner).  A stream that stops making progress (a failed launch) is noticed by hipStreamQuery and handled by a copy.
-// - copy (MSGPU_SYNC_READBACK, or no mapped pointer): the launch is not armed; one copy of the whole block into the pinned
-//   mirror behind it and a wait for that copy.  (Separate 4-byte copies into pageable host variables cost ~20 us each.)
-// arm_readback() goes into the closing launch, close_readback() behind it: work that does not depend on the values can be
-// enqueued in between and keeps the GPU busy while the host turns around.
 bool past_deadline(const msgpu_ctx *c) { return c->has_deadline && std::chrono::steady_clock::now() >= c->deadline; }
 // A host wait for a stream (or an event) that honours the context's deadline: without one the runtime's blocking wait, with
 // one a poll that gives up with MSGPU_E_TIMEOUT and leaves the work queued (the caller aborts what blocks it, or destroys).
 int host_sync(msgpu_ctx *c, hipStream_t st, hipEvent_t ev = nullptr) {
   if (!c->has_deadline) {
-    if (ev) HIPCHK(c, hipEventSynchronize(ev));
-    else HIPCHK(c, hipStreamSynchronize(st));
+    if (ev) STAGE_HIP(c, hipEventSynchronize(ev));
+    else STAGE_HIP(c, hipStreamSynchronize(st));
     return MSGPU_OK;
   }
   for (uint32_t spins = 0;; ++spins) {
@@ -383,82 +406,38 @@ int host_sync(msgpu_ctx *c, hipStream_t st, hipEvent_t ev = nullptr) {
   }
 }
 
-HostPublish arm_readback(msgpu_ctx *c) {
-  return c->readback_mapped ? HostPublish{c->h_scalars_dev, ++c->readback_seq} : HostPublish{nullptr, 0};
-}
-int wait_scalars(msgpu_ctx *c) {
-  if (c->readback_mapped) {
-    const uint64_t     seq  = c->readback_seq;
-    volatile uint64_t *flag = c->h_scalars + SC_COUNT;
-    for (uint64_t spins = 1;; ++spins) {
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
-      __builtin_ia32_pause();
-      if ((spins & 0xffff) == 0) { // every ~1 ms: is the stream still alive?
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q == hipSuccess) { // everything ran: the flag is there, or something is badly wrong
-          if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return MSGPU_OK;
-          break;
-        }
-        if (q != hipErrorNotReady) break;
-        if (past_deadline(c))
-          return fail(c, MSGPU_E_TIMEOUT, "table sizes did not come back before the deadline (msgpu_set_deadline): the stream is "
-                                          "held up by work queued in front of ours");
-      }
-    }
-    // The stream stopped making progress, or finished without the publication arriving in mapped memory.  Take the values
-    // the slow way, surface a stream error if there is one, and leave a trace either way: a lost publication is counted
-    // (msgpu_counts.n_lost_publications).  The error text is NOT touched on a call that goes on to succeed (msgpu.h,
-    // STREAM AND THREAD CONTRACT rule 4: the text belongs to a non-zero return code).
-    ++c->lost_publications;
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    return host_sync(c, c->stream);
-  }
-  return host_sync(c, nullptr, c->ev_readback); // the copy, not whatever was enqueued behind it
-}
+// The read-back of the scalar block (ScalarBlock, msgpu_stage.h) with this context's deadline: c->sc.arm() goes into the
+// launch that closes a stage, close_readback() behind it.  The copy mode waits for the copy alone, not for the stream:
+// k_emit_edges and k_compact enqueue work behind it on purpose.
 int close_readback(msgpu_ctx *c) {
-  if (!c->readback_mapped) {
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->scalars.p, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_readback, c->stream));
-  }
-  return wait_scalars(c);
+  return c->sc.wait(
+      c,
+      [c] {
+        return !past_deadline(c) ? MSGPU_OK
+                                 : fail(c, MSGPU_E_TIMEOUT, "table sizes did not come back before the deadline (msgpu_set_deadline): the stream is "
+                                                            "held up by work queued in front of ours");
+      },
+      [c](hipEvent_t copied) { return host_sync(c, c->stream, copied); });
 }
 // the block as it stands, where no closing launch carries the publication: a one-wavefront launch of its own (mark: an event
 // recorded behind it)
 int read_scalars(msgpu_ctx *c, hipEvent_t mark = nullptr) {
-  const HostPublish p = arm_readback(c);
-  if (p.seq) launch_publish_scalars(c->stream, c->scalars.as<uint64_t>(), p);
-  if (mark) HIPCHK(c, hipEventRecord(mark, c->stream));
+  const HostPublish p = c->sc.arm();
+  if (p.seq) launch_publish_scalars(c->stream, c->sc.d, p);
+  if (mark) STAGE_HIP(c, hipEventRecord(mark, c->stream));
   return close_readback(c);
-}
-
-void release_all(msgpu_ctx *c) {
-  DevBuf *all[] = {&c->sel_idx, &c->sel_cnt, &c->sel_off, &c->sel_ems, &c->g_deg, &c->g_off, &c->g_adj, &c->g_cand, &c->g_sane, &c->g_out, &c->rows_in, &c->rows_pk, &c->cnt_read, &c->read_off, &c->cursor, &c->bkt_key,
-                   &c->bkt_dead, &c->by_read, &c->read_cnt, &c->alive_rank, &c->anchor_cnt, &c->anchor_off,
-                   &c->anchor_first, &c->anchor_off_gen,
-                   &c->bkt2_idx, &c->bkt2_line, &c->by_anchor, &c->read_len, &c->read_first, &c->scalars, &c->scan_tmp,
-                   &c->bound, &c->cand_off, &c->cand_j, &c->cand_t, &c->scr_v2, &c->scr_start, &c->n_cand, &c->n_edge,
-                   &c->lists, &c->edges, &c->edge_cand,
-                   &c->big_key, &c->big_t, &c->big_r2s, &c->big_pfx, &c->pair_tab, &c->chain_chunks, &c->big_off, &c->cand_sums, &c->bucket_visits, &c->ems, &c->order_scr, &c->ids_scr,
-                   &c->edge_norders, &c->edge_nids, &c->orders, &c->ids, &c->big_list, &c->cls_list, &c->big_elems, &c->big_paths, &c->alt_edges, &c->alt_ems, &c->alt_orders, &c->alt_ids, &c->vis16, &c->visits,
-                   &c->spos2, &c->bin_cursor, &c->bin_start, &c->wire_dev[0], &c->wire_dev[1], &c->win_cuts};
-  for (DevBuf *b : all) b->release();
 }
 
 int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, uint32_t *ix_flags_out) {
   hipStream_t st = c->stream;
   const uint64_t n = c->n_rows;
-  {
-    const void *before = c->scalars.p;
-    ENSURE(c, scalars, SC_COUNT * sizeof(uint64_t));
-    if (c->scalars.p != before) c->scalars_clean = false;
-  }
   // The scalar block is zero at rest where a build counts from nothing (k_index_epilogue's last workgroup leaves it so, behind
   // its publication): a build that follows one of those needs no memset.  Anything else -- a first build, a build after an
   // error, the synchronising read-back path, ids to be discovered -- zeroes the block here.
   bool scalars_zeroed = false;
   auto zero_scalars = [&]() -> int {
     if (scalars_zeroed) return MSGPU_OK;
-    HIPCHK(c, hipMemsetAsync(c->scalars.p, 0, SC_COUNT * sizeof(uint64_t), st));
+    STAGE_HIP(c, hipMemsetAsync(c->sc.d, 0, SC_COUNT * sizeof(uint64_t), st));
     scalars_zeroed  = true;
     c->nlists_clean = true;
     return MSGPU_OK;
@@ -493,46 +472,46 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   const uint32_t bshift  = bcap ? BIN_RPB_SHIFT : 0; // != 0: this build takes the bin path
   const uint32_t nb      = bshift ? static_cast<uint32_t>((size_t(std::min(V, reads_per_pass)) + (1u << bshift) - 1) >> bshift) : 0; // buckets of a (full) pass
   const uint32_t     cap = (!bshift && !two_pass && V && size_t(V) * BUCKET_CAP * sizeof(IRow) <= (size_t(4) << 30)) ? BUCKET_CAP : 0;
-  ENSURE(c, cnt_read, (size_t(V) + 1) * 4);
-  ENSURE(c, read_off, (size_t(V) + 2) * 4);
-  ENSURE(c, cursor, mva * 4);
+  STAGE_HIP(c, c->cnt_read.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->read_off.ensure((size_t(V) + 2) * 4));
+  STAGE_HIP(c, c->cursor.ensure(mva * 4));
   if (bshift) {
     const void *before = c->bin_cursor.p;
-    ENSURE(c, bin_cursor, (size_t(bpasses) * (nb + 1) + 1) * 4); // per pass: the bucket cursors; last word: by_read rows of the passes so far
+    STAGE_HIP(c, c->bin_cursor.ensure((size_t(bpasses) * (nb + 1) + 1) * 4)); // per pass: the bucket cursors; last word: by_read rows of the passes so far
     if (c->bin_cursor.p != before) {
       c->bin_clean      = false;
       c->bin_zero_words = 0;
     }
     if (size_t(bpasses) * (nb + 1) + 1 > c->bin_zero_words) c->bin_clean = false; // (words no init launch has reached yet)
-    ENSURE(c, bin_start, (size_t(nb) + 2) * 4);
-    ENSURE(c, bucket_visits, ((size_t(V) >> BIN_RPB_SHIFT) + 2) * 4);
+    STAGE_HIP(c, c->bin_start.ensure((size_t(nb) + 2) * 4));
+    STAGE_HIP(c, c->bucket_visits.ensure(((size_t(V) >> BIN_RPB_SHIFT) + 2) * 4));
   }
-  const bool fused_readback = bshift != 0 && c->readback_mapped; // k_index_epilogue publishes (and zeroes behind it)
+  const bool fused_readback = bshift != 0 && c->sc.h_dev != nullptr; // k_index_epilogue publishes (and zeroes behind it)
   if (!(fused_readback && c->scalars_clean))
     if (int rc = zero_scalars()) return rc;
   c->scalars_clean = false; // (until this build's publisher has left it so again)
-  ENSURE(c, bkt_key, (bshift ? size_t(nb) * bcap * 2 : cap ? size_t(V) * cap : nz) * sizeof(IRow)); // (bin path: 64-byte records)
-  ENSURE(c, bkt_dead, nz);
-  ENSURE(c, by_read, nz * sizeof(IRow));
-  ENSURE(c, read_cnt, (size_t(V) + 1) * 4);
-  ENSURE(c, alive_rank, nz * 4);
-  ENSURE(c, anchor_cnt, (size_t(A) + 1) * 4);
-  ENSURE(c, anchor_first, (size_t(A) + 2) * 4);
-  ENSURE(c, anchor_off_gen, (size_t(A) + 2) * 4);
-  ENSURE(c, anchor_off, (size_t(A) + 2) * 4);
-  ENSURE(c, bkt2_idx, nz * 4);
-  ENSURE(c, bkt2_line, nz * 4);
-  ENSURE(c, by_anchor, nz * sizeof(IRow));
-  ENSURE(c, vis16, nz * 16);
-  ENSURE(c, spos2, (bshift ? 1 : cap ? size_t(V) * cap : nz) * 8); // one-pass build: by bucket slot, else by source row (bin path: inside the record)
-  ENSURE(c, visits, (size_t(V) + 1) * 4);
-  ENSURE(c, read_len, (size_t(V) + 1) * 4);
-  ENSURE(c, read_first, (size_t(V) + 1) * 4);
+  STAGE_HIP(c, c->bkt_key.ensure((bshift ? size_t(nb) * bcap * 2 : cap ? size_t(V) * cap : nz) * sizeof(IRow))); // (bin path: 64-byte records)
+  STAGE_HIP(c, c->bkt_dead.ensure(nz));
+  STAGE_HIP(c, c->by_read.ensure(nz * sizeof(IRow)));
+  STAGE_HIP(c, c->read_cnt.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->alive_rank.ensure(nz * 4));
+  STAGE_HIP(c, c->anchor_cnt.ensure((size_t(A) + 1) * 4));
+  STAGE_HIP(c, c->anchor_first.ensure((size_t(A) + 2) * 4));
+  STAGE_HIP(c, c->anchor_off_gen.ensure((size_t(A) + 2) * 4));
+  STAGE_HIP(c, c->anchor_off.ensure((size_t(A) + 2) * 4));
+  STAGE_HIP(c, c->bkt2_idx.ensure(nz * 4));
+  STAGE_HIP(c, c->bkt2_line.ensure(nz * 4));
+  STAGE_HIP(c, c->by_anchor.ensure(nz * sizeof(IRow)));
+  STAGE_HIP(c, c->vis16.ensure(nz * 16));
+  STAGE_HIP(c, c->spos2.ensure((bshift ? 1 : cap ? size_t(V) * cap : nz) * 8)); // one-pass build: by bucket slot, else by source row (bin path: inside the record)
+  STAGE_HIP(c, c->visits.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->read_len.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->read_first.ensure((size_t(V) + 1) * 4));
   {
     uint64_t m = n;
     if (V > m) m = V;
     if (A > m) m = A;
-    ENSURE(c, scan_tmp, 3 * (size_t(scan_blocks(m)) + 1) * 8);
+    STAGE_HIP(c, c->scan_tmp.ensure(3 * (size_t(scan_blocks(m)) + 1) * 8));
   }
 
   // The opening of msgpu_calculate_edges for the whole table (scratch offsets from the visit counts the sort leaves, owner
@@ -543,9 +522,9 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   // (the bin path classifies for the context's shard; the atomic path's prologue is the unsharded one)
   const bool want_prologue = c->use_prologue && !force_generic && !c->no_prologue && V != 0 && (c->nshards == 1 || bshift) && c->win_lo == 0 && c->win_hi >= V;
   if (want_prologue) {
-    ENSURE(c, n_cand, (size_t(V) + 1) * 4);
-    ENSURE(c, n_edge, (size_t(V) + 1) * 4);
-    ENSURE(c, cand_sums, cand_sums_bytes(V));
+    STAGE_HIP(c, c->n_cand.ensure((size_t(V) + 1) * 4));
+    STAGE_HIP(c, c->n_edge.ensure((size_t(V) + 1) * 4));
+    STAGE_HIP(c, c->cand_sums.ensure(cand_sums_bytes(V)));
   }
   size_t zero_words_known = 0;
   {
@@ -576,7 +555,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   uint32_t *d_flags = scalar<uint32_t>(c, SC_IXFLAGS);
   if (force_generic) {
     const uint32_t f = IXF_FORCE;
-    HIPCHK(c, hipMemcpyAsync(d_flags, &f, 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_flags, &f, 4, hipMemcpyHostToDevice, st));
   }
 
   if (bshift) {
@@ -615,11 +594,11 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
     // visit counts, the owner reads classified for the candidate kernels (for this context's shard; a window job classifies
     // per window), and the read-back of flags and sizes by its last workgroup -- which also leaves the scalar block zero where
     // the next build counts from nothing.
-    ENSURE(c, cand_off, (size_t(V) + 2) * 8);
-    ENSURE(c, lists, (size_t(V) + 1) * (3 * sizeof(CandDesc) + 4));
+    STAGE_HIP(c, c->cand_off.ensure((size_t(V) + 2) * 8));
+    STAGE_HIP(c, c->lists.ensure((size_t(V) + 1) * (3 * sizeof(CandDesc) + 4)));
     CandDesc *l0 = c->lists.as<CandDesc>(), *l1 = l0 + V + 1, *l2 = l1 + V + 1;
     if (want_prologue && !c->nlists_clean) {
-      HIPCHK(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
+      STAGE_HIP(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
       c->nlists_clean = true;
     }
     IndexEpilogueArgs k;
@@ -653,15 +632,15 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
     k.own_total      = scalar<unsigned long long>(c, SC_OWN);
     k.z              = want_prologue ? cand_zero(c, V) : CandZero{};
     k.done           = scalar<uint32_t>(c, SC_DONE);
-    k.scalars        = c->scalars.as<uint64_t>();
-    k.pub            = arm_readback(c);
+    k.scalars        = c->sc.d;
+    k.pub            = c->sc.arm();
     // zeroed behind the publication: error bits, index flags, the scaffold count, the finished-workgroup counters, the owner
     // reads' visits.  (Not with the synchronising read-back: its copy comes after the kernel.)
     k.zero_mask      = fused_readback ? ((1ull << SC_ERR) | (1ull << SC_IXFLAGS) | (1ull << SC_HEADS) | (1ull << SC_DONE) | (1ull << SC_OWN)) : 0ull;
     launch_index_epilogue(st, k);
     if (want_prologue) c->nlists_clean = false;
-    HIPCHK(c, hipGetLastError());
-    if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[1], st));
+    STAGE_HIP(c, hipGetLastError());
+    if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[1], st));
     if (int rc = close_readback(c)) return rc;
   } else {
   // the Registry-order check on the first lines the sort found and, in the same launch, the scaffold offsets: fast mode
@@ -671,11 +650,11 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   launch_index_finish(st, c->read_first.as<uint32_t>(), V, scalar<uint32_t>(c, SC_ERR), d_flags, c->anchor_first.as<uint32_t>(),
                       c->anchor_off_gen.as<uint32_t>(), A, c->anchor_off.as<uint32_t>(), scalar<uint32_t>(c, SC_NALIVE),
                       static_cast<uint32_t>(n));
-  HIPCHK(c, hipGetLastError());
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[1], st));
+  STAGE_HIP(c, hipGetLastError());
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[1], st));
   if (want_prologue) { // (see the top of this function)
-    ENSURE(c, cand_off, (size_t(V) + 2) * 8);
-    ENSURE(c, lists, (size_t(V) + 1) * (3 * sizeof(CandDesc) + 4));
+    STAGE_HIP(c, c->cand_off.ensure((size_t(V) + 2) * 8));
+    STAGE_HIP(c, c->lists.ensure((size_t(V) + 1) * (3 * sizeof(CandDesc) + 4)));
     CandDesc *l0 = c->lists.as<CandDesc>(), *l1 = l0 + V + 1, *l2 = l1 + V + 1;
     exclusive_scan<uint64_t>(st, c->visits.as<uint32_t>(), V, c->cand_off.as<uint64_t>(), c->scan_tmp.as<uint64_t>(),
                              scalar<uint64_t>(c, SC_TOTAL_A));
@@ -683,7 +662,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
                           c->cand_off.as<uint64_t>(), V, 0, 1, 0, 0xffffffffu, l0, l1, l2,
                           reinterpret_cast<uint32_t *>(l2 + V + 1), scalar<uint32_t>(c, SC_NLISTS), cand_zero(c, V));
     c->nlists_clean = false;
-    HIPCHK(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
   }
 
   if (int rc = read_scalars(c)) return rc;
@@ -725,13 +704,13 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
                              c->scan_tmp.as<uint32_t>(), scalar<uint32_t>(c, SC_NALIVE));
     launch_select_anchor_off(st, d_flags, c->anchor_first.as<uint32_t>(), c->anchor_off_gen.as<uint32_t>(), A,
                              c->anchor_off.as<uint32_t>(), scalar<uint32_t>(c, SC_NALIVE), static_cast<uint32_t>(n));
-    HIPCHK(c, hipMemsetAsync(c->cursor.p, 0, mva * 4, st));
+    STAGE_HIP(c, hipMemsetAsync(c->cursor.p, 0, mva * 4, st));
     launch_scatter_anchor(st, c->d_rows, n, c->alive_rank.as<uint32_t>(), c->anchor_off.as<uint32_t>(),
                           c->cursor.as<uint32_t>(), c->bkt2_idx.as<uint32_t>(), c->bkt2_line.as<uint32_t>(), d_flags);
     launch_rank_anchor(st, c->anchor_off.as<uint32_t>(), n, scalar<uint32_t>(c, SC_NALIVE), c->bkt2_idx.as<uint32_t>(),
                        c->bkt2_line.as<uint32_t>(), c->d_rows, c->alive_rank.as<uint32_t>(), c->by_anchor.as<IRow>(),
                        d_flags, c->read_off.as<uint32_t>(), c->by_read.as<IRow>(), c->vis16.as<uint4>());
-    HIPCHK(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     if (int rc = read_scalars(c, c->ev[1])) return rc;
     n_alive = *host_scalar<uint32_t>(c, SC_NALIVE);
   }
@@ -744,7 +723,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
 }
 
 int build_index(msgpu_ctx *c) {
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[0], c->stream));
   uint32_t ixf = 0;
   bool     two_pass = false;
   int      rc  = build_index_once(c, false, two_pass, c->use_bin, &ixf);
@@ -806,135 +785,28 @@ const char *msgpu_strerror(int code) {
 }
 
 int msgpu_create(int device, const msgpu_params *params, msgpu_ctx **out) {
-  if (!out) return MSGPU_E_ARG;
-  *out = nullptr;
-  int        ndev = 0;
-  hipError_t e    = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0) return MSGPU_E_NODEVICE;
-  if (device < 0 || device >= ndev) return MSGPU_E_ARG;
-  msgpu_ctx *c = new (std::nothrow) msgpu_ctx();
-  if (!c) return MSGPU_E_NOMEM;
-  c->device = device;
+  const int rc = stage_create<msgpu_ctx>(device, out);
+  if (rc != MSGPU_OK) return rc;
   if (params)
-    c->p = *params;
+    (*out)->p = *params;
   else
-    msgpu_default_params(&c->p);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    delete c;
-    return MSGPU_E_HIP;
-  }
-  c->stream = c->own_stream;
-  if (hipHostMalloc(reinterpret_cast<void **>(&c->h_scalars), (SC_COUNT + 1) * sizeof(uint64_t),
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-    c->h_scalars = nullptr;
-    msgpu_destroy(c);
-    return MSGPU_E_NOMEM;
-  }
-  memset(c->h_scalars, 0, (SC_COUNT + 1) * sizeof(uint64_t));
-  if (hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_scalars_dev), c->h_scalars, 0) != hipSuccess) c->h_scalars_dev = nullptr;
-  c->readback_mapped = c->h_scalars_dev && !getenv("MSGPU_SYNC_READBACK"); // (any value: the copy read-back)
-  {
-    const char *nf = getenv("MSGPU_NO_FASTPATH"); // test hook: force the full pair sweep on every edge
-    c->fast_path   = !(nf && nf[0] == '1');
-    const char *nb = getenv("MSGPU_NO_BAND"); // test hook / way out: no banded pair sweep (the shortcut stays)
-    c->chain_band  = c->fast_path && !(nb && nb[0] == '1');
-    const char *ns = getenv("MSGPU_NO_SUBWAVE"); // test hook: one edge per wavefront whatever its size
-    c->sub_wave    = !(ns && ns[0] == '1');
-    const char *nw = getenv("MSGPU_NO_WIRE_COPY");
-    c->wire_copy   = !(nw && nw[0] == '1');
-    const char *nbin = getenv("MSGPU_NO_BIN"); // A/B switch: the index build's atomic path (rounds 1-3) for every input
-    c->use_bin       = !(nbin && nbin[0] == '1');
-    // measurement switches (any value)
-    c->use_prologue = !getenv("MSGPU_NO_PROLOGUE"); // no classification inside the index build
-    c->use_fork     = !getenv("MSGPU_NO_FORK");     // the candidate classes one after the other
-    c->chain_serial = getenv("MSGPU_CHAIN_SERIAL") != nullptr;
-  }
-  for (auto &ev : c->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      msgpu_destroy(c);
-      return MSGPU_E_HIP;
-    }
-  // the side stream carries the few heavy workgroups that run beside a stage's main kernel (large LDS classes, edges with
-  // more than 64 EdgeMatches): highest priority, so that they finish first and the join never waits for them
-  int prio_least = 0, prio_greatest = 0;
-  if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_least = prio_greatest = 0;
-  if (hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, prio_greatest) != hipSuccess ||
-      hipStreamCreateWithPriority(&c->side_stream2, hipStreamNonBlocking, prio_greatest) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_side2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_part[0][0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_part[0][1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_part[0][2], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_part[1][0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_part[1][1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_part[1][2], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_side[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_side[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_readback, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming) != hipSuccess) {
-    msgpu_destroy(c);
-    return MSGPU_E_HIP;
-  }
-  if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) {
-    msgpu_destroy(c);
-    return MSGPU_E_HIP;
-  }
-  for (int k = 0; k < 2; ++k)
-    if (hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_copied[k], hipEventDisableTiming) != hipSuccess) {
-      msgpu_destroy(c);
-      return MSGPU_E_HIP;
-    }
-  *out = c;
+    msgpu_default_params(&(*out)->p);
   return MSGPU_OK;
 }
 
 void msgpu_destroy(msgpu_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  release_all(c);
-  for (auto &ev : c->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto &ev : c->ev_side)
-    if (ev) (void)hipEventDestroy(ev);
-  if (c->ev_readback) (void)hipEventDestroy(c->ev_readback);
-  if (c->ev_order) (void)hipEventDestroy(c->ev_order);
-  if (c->ev_side2) (void)hipEventDestroy(c->ev_side2);
-  for (auto &per_set : c->ev_part)
-    for (hipEvent_t e : per_set)
-      if (e) (void)hipEventDestroy(e);
-  if (c->side_stream2) {
-    (void)hipStreamSynchronize(c->side_stream2);
-    (void)hipStreamDestroy(c->side_stream2);
-  }
-  for (auto &pair : c->ck_ev)
-    for (auto &ev : pair)
-      if (ev) (void)hipEventDestroy(ev);
-  if (c->side_stream) {
-    (void)hipStreamSynchronize(c->side_stream);
-    (void)hipStreamDestroy(c->side_stream);
-  }
-  if (c->copy_stream) {
-    (void)hipStreamSynchronize(c->copy_stream);
-    (void)hipStreamDestroy(c->copy_stream);
-  }
-  for (int k = 0; k < 2; ++k) {
-    if (c->ev_done[k]) (void)hipEventDestroy(c->ev_done[k]);
-    if (c->ev_copied[k]) (void)hipEventDestroy(c->ev_copied[k]);
-  }
-  for (msgpu_ctx::HostBuf *h : {&c->h_edges, &c->h_ems, &c->h_orders, &c->h_ids, &c->h_read_len, &c->h_read_first, &c->h_sel_off,
-                               &c->h_sel_ems, &c->h_wire[0], &c->h_wire[1]})
-    if (h->p) pinned_block_free(h->p);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  if (c->h_scalars) (void)hipHostFree(c->h_scalars);
-  delete c;
+  if (c->stream) (void)hipStreamSynchronize(c->stream); // (before anything is freed; a caller's stream is not ours to destroy)
+  c->stream = c->own_stream;
+  stage_destroy(c);
 }
 
 const char *msgpu_last_error(const msgpu_ctx *c) { return c ? c->err : "null context"; }
 
 int msgpu_set_stream(msgpu_ctx *c, void *hip_stream) {
   if (!c) return MSGPU_E_ARG;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
   c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
   return MSGPU_OK;
 }
@@ -946,18 +818,18 @@ int msgpu_stream_wait(msgpu_ctx *c, void *hip_stream) {
   if (!c) return MSGPU_E_ARG;
   hipStream_t other = static_cast<hipStream_t>(hip_stream);
   if (other == c->stream) return MSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventRecord(c->ev_order, other));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0));
+  STAGE_HIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipEventRecord(c->ev_order, other));
+  STAGE_HIP(c, hipStreamWaitEvent(c->stream, c->ev_order, 0));
   return MSGPU_OK;
 }
 int msgpu_stream_release(msgpu_ctx *c, void *hip_stream) {
   if (!c) return MSGPU_E_ARG;
   hipStream_t other = static_cast<hipStream_t>(hip_stream);
   if (other == c->stream) return MSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventRecord(c->ev_order, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(other, c->ev_order, 0));
+  STAGE_HIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipEventRecord(c->ev_order, c->stream));
+  STAGE_HIP(c, hipStreamWaitEvent(other, c->ev_order, 0));
   return MSGPU_OK;
 }
 
@@ -982,11 +854,11 @@ int msgpu_load_rows(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows) {
   if (!c) return MSGPU_E_ARG;
   if (n_rows && !rows) return fail(c, MSGPU_E_ARG, "Unexpected nullptr.");
   if (n_rows > (1ull << 30)) return fail(c, MSGPU_E_ARG, "row table too large (%zu rows, at most 2^30)", n_rows);
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   c->state = ST_CREATED;
-  ENSURE(c, rows_in, (n_rows ? n_rows : 1) * sizeof(msgpu_row));
+  STAGE_HIP(c, c->rows_in.ensure((n_rows ? n_rows : 1) * sizeof(msgpu_row)));
   if (n_rows)
-    HIPCHK(c, hipMemcpyAsync(c->rows_in.p, rows, n_rows * sizeof(msgpu_row), hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(c->rows_in.p, rows, n_rows * sizeof(msgpu_row), hipMemcpyHostToDevice, c->stream));
   c->d_rows = c->rows_in.as<msgpu_row>();
   c->n_rows = n_rows;
   return build_index(c);
@@ -997,26 +869,26 @@ int msgpu_load_rows_packed(msgpu_ctx *c, const msgpu_packed_rows *p) {
   if (!p || (p->n_rows && (!p->rows || !p->run_start || !p->run_delta || !p->n_runs)) || (p->n_reads && !p->read_len))
     return fail(c, MSGPU_E_ARG, "Unexpected nullptr.");
   if (p->n_rows > (1ull << 30)) return fail(c, MSGPU_E_ARG, "row table too large (%llu rows, at most 2^30)", (unsigned long long)p->n_rows);
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   c->state = ST_CREATED;
   const size_t n = static_cast<size_t>(p->n_rows);
   // 28 bytes per row + the per-read lengths + the line runs cross the link; the 40-byte rows are made in HBM
   const size_t off_len = (n * sizeof(msgpu_row28) + 255) / 256 * 256, off_rs = off_len + (size_t(p->n_reads) * 4 + 255) / 256 * 256,
                off_rd = off_rs + (size_t(p->n_runs) * 4 + 255) / 256 * 256, total = off_rd + size_t(p->n_runs) * 4 + 256;
-  ENSURE(c, rows_pk, total);
-  ENSURE(c, rows_in, (n ? n : 1) * sizeof(msgpu_row));
+  STAGE_HIP(c, c->rows_pk.ensure(total));
+  STAGE_HIP(c, c->rows_in.ensure((n ? n : 1) * sizeof(msgpu_row)));
   char *d = c->rows_pk.as<char>();
   if (n) {
-    HIPCHK(c, hipMemcpyAsync(d, p->rows, n * sizeof(msgpu_row28), hipMemcpyHostToDevice, c->stream));
-    if (p->n_reads) HIPCHK(c, hipMemcpyAsync(d + off_len, p->read_len, size_t(p->n_reads) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + off_rs, p->run_start, size_t(p->n_runs) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + off_rd, p->run_delta, size_t(p->n_runs) * 4, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d, p->rows, n * sizeof(msgpu_row28), hipMemcpyHostToDevice, c->stream));
+    if (p->n_reads) STAGE_HIP(c, hipMemcpyAsync(d + off_len, p->read_len, size_t(p->n_reads) * 4, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d + off_rs, p->run_start, size_t(p->n_runs) * 4, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d + off_rd, p->run_delta, size_t(p->n_runs) * 4, hipMemcpyHostToDevice, c->stream));
     // (a read id beyond the per-read table -- msgpu_pack_rows makes no such table -- gets length 0 and a note in a scratch
     // word; the index build reports ids outside its id space itself)
     launch_expand_rows(c->stream, d, n, reinterpret_cast<const int32_t *>(d + off_len), p->n_reads, reinterpret_cast<const uint32_t *>(d + off_rs),
                        reinterpret_cast<const uint32_t *>(d + off_rd), p->n_runs, c->rows_in.as<msgpu_row>(),
                        reinterpret_cast<uint32_t *>(d + off_rd + size_t(p->n_runs) * 4));
-    HIPCHK(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
   }
   c->d_rows = c->rows_in.as<msgpu_row>();
   c->n_rows = n;
@@ -1027,7 +899,7 @@ int msgpu_load_rows_device(msgpu_ctx *c, const void *d_rows, size_t n_rows) {
   if (!c) return MSGPU_E_ARG;
   if (n_rows && !d_rows) return fail(c, MSGPU_E_ARG, "Unexpected nullptr.");
   if (n_rows > (1ull << 30)) return fail(c, MSGPU_E_ARG, "row table too large (%zu rows, at most 2^30)", n_rows);
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   c->state  = ST_CREATED;
   c->d_rows = static_cast<const msgpu_row *>(d_rows);
   c->n_rows = n_rows;
@@ -1040,18 +912,18 @@ static size_t chunk_words(uint64_t n_edges) { return 2 * static_cast<size_t>(n_e
 int msgpu_calculate_edges(msgpu_ctx *c) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_LOADED) return fail(c, MSGPU_E_STATE, "msgpu_calculate_edges before msgpu_load_rows");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   hipStream_t    st = c->stream;
   const uint32_t V  = c->V;
   c->state          = ST_LOADED;
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[2], st));
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[2], st));
 
-  ENSURE(c, bound, (size_t(V) + 1) * 4);
-  ENSURE(c, cand_off, (size_t(V) + 2) * 8);
-  ENSURE(c, lists, (size_t(V) + 1) * (3 * sizeof(CandDesc) + 4));
-  ENSURE(c, n_cand, (size_t(V) + 1) * 4);
-  ENSURE(c, n_edge, (size_t(V) + 1) * 4);
-  ENSURE(c, cand_sums, cand_sums_bytes(V));
+  STAGE_HIP(c, c->bound.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->cand_off.ensure((size_t(V) + 2) * 8));
+  STAGE_HIP(c, c->lists.ensure((size_t(V) + 1) * (3 * sizeof(CandDesc) + 4)));
+  STAGE_HIP(c, c->n_cand.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->n_edge.ensure((size_t(V) + 1) * 4));
+  STAGE_HIP(c, c->cand_sums.ensure(cand_sums_bytes(V)));
   CandDesc *l0 = c->lists.as<CandDesc>(), *l1 = l0 + V + 1, *l2 = l1 + V + 1;
   uint32_t *l3 = reinterpret_cast<uint32_t *>(l2 + V + 1);
 
@@ -1083,12 +955,12 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     // a window of the dispatcher on a bin-path index: the scan of ALL reads' visit counts stands since the build (the scratch is
     // laid out for the whole table), so the window needs its reads classified and nothing else -- no per-window count of the
     // visits, no scan of its own (three launches per window fewer)
-    if (!c->nlists_clean) HIPCHK(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
+    if (!c->nlists_clean) STAGE_HIP(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
     c->nlists_clean = false;
     launch_classify_reads(st, c->read_off.as<uint32_t>(), c->read_cnt.as<uint32_t>(), c->visits.as<uint32_t>(),
                           c->cand_off.as<uint64_t>(), V, 0, 1, c->win_lo, c->win_hi, l0, l1, l2, l3,
                           scalar<uint32_t>(c, SC_NLISTS), cand_zero(c, V), scalar<unsigned long long>(c, SC_OWN));
-    HIPCHK(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     if (int rc = read_scalars(c)) return rc;
     total_bound  = c->index_total;
     const uint64_t own_now = *host_scalar<uint64_t>(c, SC_OWN);
@@ -1098,7 +970,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   } else {
     // the four list cursors are zero at rest (the scalar block's memset of the index build, k_emit_edges afterwards); a call
     // that ended between k_classify_reads and k_emit_edges left them dirty
-    if (!c->nlists_clean) HIPCHK(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
+    if (!c->nlists_clean) STAGE_HIP(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
     c->full_scan_ok = false; // (cand_off is rewritten below for this subset of the reads)
     if (!all_reads)
       launch_bound(st, c->read_off.as<uint32_t>(), c->read_cnt.as<uint32_t>(), c->vis16.as<uint4>(), V, c->shard,
@@ -1109,7 +981,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     launch_classify_reads(st, c->read_off.as<uint32_t>(), c->read_cnt.as<uint32_t>(), bound,
                           c->cand_off.as<uint64_t>(), V, c->shard, c->nshards, c->win_lo, c->win_hi, l0, l1, l2, l3,
                           scalar<uint32_t>(c, SC_NLISTS), cand_zero(c, V));
-    HIPCHK(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     if (int rc = read_scalars(c)) return rc; // sizes of the candidate scratch
     total_bound = own_bound = *host_scalar<uint64_t>(c, SC_TOTAL_A);
     for (int k = 0; k < 4; ++k) c->n_list[k] = host_scalar<uint32_t>(c, SC_NLISTS)[k];
@@ -1117,10 +989,10 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   c->total_bound = own_bound; // the scaffold rows this context's owner reads visit
 
   const size_t tb = total_bound ? total_bound : 1;
-  ENSURE(c, cand_j, tb * 4);
-  ENSURE(c, cand_t, tb * 4);
-  ENSURE(c, scr_v2, tb * 4);
-  ENSURE(c, scr_start, tb * 4);
+  STAGE_HIP(c, c->cand_j.ensure(tb * 4));
+  STAGE_HIP(c, c->cand_t.ensure(tb * 4));
+  STAGE_HIP(c, c->scr_v2.ensure(tb * 4));
+  STAGE_HIP(c, c->scr_start.ensure(tb * 4));
 
   CandArgs a;
   a.read_off       = c->read_off.as<uint32_t>();
@@ -1150,21 +1022,21 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     // the chain stage), launched FIRST: alone in front of class 0 on the main stream they cost 17 us of every step (one or two
     // workgroups at the latency of a whole kernel -- a fifth of a shard-of-eight's candidate stage, profiles/r5_05)
     // (in front of class 0's launch only what must be there: every runtime call is a few microseconds of the host's turn-around)
-    HIPCHK(c, hipEventRecord(c->ev_side[0], st));
+    STAGE_HIP(c, hipEventRecord(c->ev_side[0], st));
     if (c->n_list[2]) {
-      HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
+      STAGE_HIP(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
       launch_candidates(c->side_stream, a, 2, l2, c->n_list[2]);
     }
     launch_candidates(st, a, 0, l0, c->n_list[0]);
     if (c->n_list[1]) {
-      HIPCHK(c, hipStreamWaitEvent(c->side_stream2, c->ev_side[0], 0));
+      STAGE_HIP(c, hipStreamWaitEvent(c->side_stream2, c->ev_side[0], 0));
       launch_candidates(c->side_stream2, a, 1, l1, c->n_list[1]);
-      HIPCHK(c, hipEventRecord(c->ev_side2, c->side_stream2));
-      HIPCHK(c, hipStreamWaitEvent(st, c->ev_side2, 0));
+      STAGE_HIP(c, hipEventRecord(c->ev_side2, c->side_stream2));
+      STAGE_HIP(c, hipStreamWaitEvent(st, c->ev_side2, 0));
     }
     if (c->n_list[2]) {
-      HIPCHK(c, hipEventRecord(c->ev_side[1], c->side_stream));
-      HIPCHK(c, hipStreamWaitEvent(st, c->ev_side[1], 0));
+      STAGE_HIP(c, hipEventRecord(c->ev_side[1], c->side_stream));
+      STAGE_HIP(c, hipStreamWaitEvent(st, c->ev_side[1], 0));
     }
   } else {
     launch_candidates(st, a, 2, l2, c->n_list[2]);
@@ -1172,14 +1044,14 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     launch_candidates(st, a, 0, l0, c->n_list[0]);
   }
   if (c->n_list[3]) {
-    ENSURE(c, big_key, tb * 8);
-    ENSURE(c, big_t, tb * 4);
-    ENSURE(c, big_r2s, tb * 4);
-    ENSURE(c, big_pfx, (c->n_rows ? c->n_rows : 1) * 4);
+    STAGE_HIP(c, c->big_key.ensure(tb * 8));
+    STAGE_HIP(c, c->big_t.ensure(tb * 4));
+    STAGE_HIP(c, c->big_r2s.ensure(tb * 4));
+    STAGE_HIP(c, c->big_pfx.ensure((c->n_rows ? c->n_rows : 1) * 4));
     launch_candidates_big(st, a, l3, c->n_list[3], c->big_key.as<uint64_t>(), c->big_t.as<uint32_t>(),
                           c->big_r2s.as<uint32_t>(), c->big_pfx.as<uint32_t>());
   }
-  HIPCHK(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   // ONE launch closes the stage (k_emit_edges): the scans of the per-read counts, the edge table, the list of big edges, the
   // size-sorted edge list with its class sizes -- and the read-back: its first workgroup publishes the table sizes before the
   // tables are written, so the GPU is busy while the host turns around.  The launch goes into whatever the tables hold from
@@ -1217,8 +1089,8 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     k.cap_big        = cap_big;
     k.chain_chunk_sums    = c->chain_chunks.as<unsigned long long>();
     k.n_chain_chunk_words = cap_edges ? static_cast<uint32_t>(chunk_words(cap_edges)) : 0u;
-    k.scalars        = c->scalars.as<uint64_t>();
-    k.pub            = publish ? arm_readback(c) : HostPublish{nullptr, 0};
+    k.scalars        = c->sc.d;
+    k.pub            = publish ? c->sc.arm() : HostPublish{nullptr, 0};
     k.nlists         = scalar<unsigned long long>(c, SC_NLISTS);
     launch_emit_edges(st, k, publish); // (the first launch of a call: with k_cand_reduce in front)
   };
@@ -1226,7 +1098,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   capacities(&cap_edges, &cap_big);
   emit(cap_edges, cap_big, true);
   c->nlists_clean = true; // (its first workgroup zeroes the list cursors behind the publication)
-  HIPCHK(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   if (int rc = close_readback(c)) return rc;
   const uint64_t *tot = host_scalar<uint64_t>(c, SC_TOTAL_A), *big = host_scalar<uint64_t>(c, SC_BIGSTATS);
   c->n_big_edges = big[0];
@@ -1237,20 +1109,20 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   c->n_visit = c->total_bound; // the scaffold rows visited = the bound (scaffolds in read-id order: only owned partners)
   if (c->n_edges >= 0xfffffff0ull) return fail(c, MSGPU_E_ARG, "edge table too large (%llu)", (unsigned long long)c->n_edges);
   if (c->n_edges > cap_edges || c->n_big_edges >= cap_big) { // (the kernel's own test, see k_emit_edges)
-    ENSURE(c, edges, (c->n_edges ? c->n_edges : 1) * sizeof(msgpu_edge));
-    ENSURE(c, edge_cand, (c->n_edges ? c->n_edges : 1) * 8);
-    ENSURE(c, cls_list, (c->n_edges + 1) * 4);
+    STAGE_HIP(c, c->edges.ensure((c->n_edges ? c->n_edges : 1) * sizeof(msgpu_edge)));
+    STAGE_HIP(c, c->edge_cand.ensure((c->n_edges ? c->n_edges : 1) * 8));
+    STAGE_HIP(c, c->cls_list.ensure((c->n_edges + 1) * 4));
     // the edges with more than 64 EdgeMatches (counted by the candidate kernels) are listed as they are emitted
-    ENSURE(c, big_list, (c->n_big_edges + 1) * 4);
-    ENSURE(c, big_off, (c->n_big_edges + 1) * 8);
-    ENSURE(c, chain_chunks, chunk_words(c->edges.room() / sizeof(msgpu_edge)) * 8);
+    STAGE_HIP(c, c->big_list.ensure((c->n_big_edges + 1) * 4));
+    STAGE_HIP(c, c->big_off.ensure((c->n_big_edges + 1) * 8));
+    STAGE_HIP(c, c->chain_chunks.ensure(chunk_words(c->edges.room() / sizeof(msgpu_edge)) * 8));
     capacities(&cap_edges, &cap_big);
     emit(cap_edges, cap_big, false);
   }
   // the chain stage's chunk sums were zeroed by k_emit_edges: msgpu_chaining_and_overlaps starts with its kernels
   c->chain_zeroed = true;
-  HIPCHK(c, hipGetLastError());
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[3], st));
+  STAGE_HIP(c, hipGetLastError());
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[3], st));
   c->have_cand_t = c->stage_events;
   c->n_orders    = 0;
   c->n_ids       = 0;
@@ -1262,20 +1134,20 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_EDGES || c->state == ST_RESULT)
     return fail(c, MSGPU_E_STATE, "msgpu_chaining_and_overlaps before msgpu_calculate_edges");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   hipStream_t    st = c->stream;
   const uint64_t E = c->n_edges, M = c->n_ems;
   for (int k = 0; k < 2; ++k)
-    if (!c->ck_ev[c->ck_head][k]) HIPCHK(c, hipEventCreate(&c->ck_ev[c->ck_head][k]));
+    if (!c->ck_ev[c->ck_head][k]) STAGE_HIP(c, c->ck_ev[c->ck_head][k].create());
   const hipEvent_t ck_begin = c->ck_ev[c->ck_head][0], ck_end = c->ck_ev[c->ck_head][1];
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[4], st));
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[4], st));
 
-  ENSURE(c, ems, (M ? M : 1) * sizeof(msgpu_edgematch));
-  ENSURE(c, order_scr, (M ? M : 1) * sizeof(msgpu_order));
-  ENSURE(c, ids_scr, (M ? M : 1) * 4);
-  ENSURE(c, edge_norders, (E + 4) * 4);
-  ENSURE(c, edge_nids, (E + 4) * 4);
-  ENSURE(c, chain_chunks, chunk_words(E) * 8);
+  STAGE_HIP(c, c->ems.ensure((M ? M : 1) * sizeof(msgpu_edgematch)));
+  STAGE_HIP(c, c->order_scr.ensure((M ? M : 1) * sizeof(msgpu_order)));
+  STAGE_HIP(c, c->ids_scr.ensure((M ? M : 1) * 4));
+  STAGE_HIP(c, c->edge_norders.ensure((E + 4) * 4));
+  STAGE_HIP(c, c->edge_nids.ensure((E + 4) * 4));
+  STAGE_HIP(c, c->chain_chunks.ensure(chunk_words(E) * 8));
 
   ChainArgs a;
   a.edges        = c->edges.as<msgpu_edge>();
@@ -1295,14 +1167,14 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   a.edge_nids    = c->edge_nids.as<uint32_t>();
   a.err          = scalar<uint32_t>(c, SC_ERR);
   if (!c->pair_tab.p) {
-    ENSURE(c, pair_tab, PAIR_TAB_WORDS * sizeof(uint32_t));
+    STAGE_HIP(c, c->pair_tab.ensure(PAIR_TAB_WORDS * sizeof(uint32_t)));
     launch_fill_pair_tab(st, c->pair_tab.as<uint32_t>());
   }
   a.pair_tab     = c->pair_tab.as<uint32_t>();
   a.pair_tab64   = c->pair_tab.as<uint32_t>() + 4 * PAIR_TAB_STRIDE;
   a.pair_tab_sub = c->pair_tab.as<uint32_t>() + 4 * PAIR_TAB_STRIDE + 2 * PAIR_TAB_STRIDE;
   if (!c->chain_zeroed) // (msgpu_calculate_edges' size sort left the chunk sums zeroed; a second chaining pass, or a run without the sort, zeroes them here)
-    HIPCHK(c, hipMemsetAsync(c->chain_chunks.p, 0, chunk_words(E) * 8, st));
+    STAGE_HIP(c, hipMemsetAsync(c->chain_chunks.p, 0, chunk_words(E) * 8, st));
   c->chain_zeroed = false;
   a.chunk_sums   = c->chain_chunks.as<unsigned long long>();
   a.fast_path    = (c->fast_path ? CHAIN_FAST_SHORTCUT : 0) | (c->chain_band ? CHAIN_FAST_BAND : 0);
@@ -1320,21 +1192,21 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   // are and how much scratch they need) run in k_chain_big on the side stream, concurrently with k_chain.
   const uint32_t n_big = static_cast<uint32_t>(c->n_big_edges);
   if (n_big) {
-    ENSURE(c, big_elems, (c->n_big_ems ? c->n_big_ems : 1) * big_elem_bytes());
-    ENSURE(c, big_paths, (c->n_big_ems ? c->n_big_ems : 1) * 2 * big_path_bytes());
+    STAGE_HIP(c, c->big_elems.ensure((c->n_big_ems ? c->n_big_ems : 1) * big_elem_bytes()));
+    STAGE_HIP(c, c->big_paths.ensure((c->n_big_ems ? c->n_big_ems : 1) * 2 * big_path_bytes()));
   }
   // Two events mark "the candidate stage is done" on the main stream: the first releases k_chain_big on its side stream, the
   // second opens the chain kernels' timing window and releases the sub-wavefront classes on theirs (a third one for those cost the
   // main stream one more packet in front of k_chain).  k_chain_big keeps an event of its own, recorded FIRST: released by the
   // same event as the others it started behind k_chain, its thousand long-lived wavefronts then sat beside the others for the whole
   // stage instead of its first fifth, and the stage took 30 us longer (gpurun_out/r5_45 against r5_38).
-  if (n_big) HIPCHK(c, hipEventRecord(c->ev_side[0], st)); // (the list and the scratch offsets: k_emit_edges)
+  if (n_big) STAGE_HIP(c, hipEventRecord(c->ev_side[0], st)); // (the list and the scratch offsets: k_emit_edges)
   auto launch_big = [&]() -> int {
     if (!n_big) return MSGPU_OK;
-    HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
+    STAGE_HIP(c, hipStreamWaitEvent(c->side_stream, c->ev_side[0], 0));
     launch_chain_big(c->side_stream, a, c->big_list.as<uint32_t>(), c->big_off.as<uint64_t>(), n_big,
                      c->big_elems.p, c->big_paths.p);
-    HIPCHK(c, hipEventRecord(c->ev_side[1], c->side_stream));
+    STAGE_HIP(c, hipEventRecord(c->ev_side[1], c->side_stream));
     return MSGPU_OK;
   };
   {
@@ -1343,7 +1215,7 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   }
   c->gate_cv.notify_all();
   if (int rc = launch_big()) return rc; // (first: its few long-lived wavefronts get their registers before k_chain fills the device)
-  HIPCHK(c, hipEventRecord(ck_begin, st));
+  STAGE_HIP(c, hipEventRecord(ck_begin, st));
   if (c->sub_wave && E) {
     // the size-sorted edge list and the class sizes are there since msgpu_calculate_edges
     const uint32_t *list = c->cls_list.as<uint32_t>();
@@ -1356,7 +1228,7 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
     const bool serial = c->chain_serial; // A/B switch: the four classes one after the other, a launch each
     const bool any_sub = c->n_cls[0] || c->n_cls[1] || c->n_cls[3];
     const bool beside  = !serial && any_sub && c->n_cls[2];
-    if (beside) HIPCHK(c, hipStreamWaitEvent(c->side_stream2, ck_begin, 0));
+    if (beside) STAGE_HIP(c, hipStreamWaitEvent(c->side_stream2, ck_begin, 0));
     launch_chain(st, a, l64, c->n_cls[2]); // the long ones first: the short classes fill the tail
     if (serial) {
       launch_chain_sub(st, a, 32, l32, c->n_cls[1]);
@@ -1366,19 +1238,19 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
       launch_chain_sub_all(beside ? c->side_stream2 : st, a, l32, c->n_cls[1], l16, c->n_cls[0], l8, c->n_cls[3]);
     }
     if (beside) {
-      HIPCHK(c, hipEventRecord(c->ev_side2, c->side_stream2));
-      HIPCHK(c, hipStreamWaitEvent(st, c->ev_side2, 0));
+      STAGE_HIP(c, hipEventRecord(c->ev_side2, c->side_stream2));
+      STAGE_HIP(c, hipStreamWaitEvent(st, c->ev_side2, 0));
     }
   } else {
     launch_chain(st, a, nullptr, 0);
   }
-  HIPCHK(c, hipEventRecord(ck_end, st));
+  STAGE_HIP(c, hipEventRecord(ck_end, st));
   c->ck_head = (c->ck_head + 1) % msgpu_ctx::CK_RING;
   if (c->ck_count < msgpu_ctx::CK_RING) ++c->ck_count;
-  HIPCHK(c, hipGetLastError());
-  if (n_big) HIPCHK(c, hipStreamWaitEvent(st, c->ev_side[1], 0));
+  STAGE_HIP(c, hipGetLastError());
+  if (n_big) STAGE_HIP(c, hipStreamWaitEvent(st, c->ev_side[1], 0));
 
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[7], st));
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[7], st));
   // ONE launch closes the stage: k_compact sums the chunk sums the chain kernels left (the scan), its first workgroup writes the
   // table sizes into the scalar block and publishes it to the host, and the move into the dense tables follows in the same
   // kernel -- into what the two tables hold from earlier calls (see msgpu_calculate_edges): the GPU is busy while the host
@@ -1391,8 +1263,8 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
     k.edge_nids    = c->edge_nids.as<uint32_t>();
     k.chunk_sums   = c->chain_chunks.as<unsigned long long>();
     k.n_chunks     = static_cast<uint32_t>((E + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
-    k.scalars      = c->scalars.as<uint64_t>();
-    k.pub          = publish ? arm_readback(c) : HostPublish{nullptr, 0};
+    k.scalars      = c->sc.d;
+    k.pub          = publish ? c->sc.arm() : HostPublish{nullptr, 0};
     k.order_scr    = c->order_scr.as<msgpu_order>();
     k.ids_scr      = c->ids_scr.as<uint32_t>();
     k.orders       = c->orders.as<msgpu_order>();
@@ -1407,19 +1279,19 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   };
   const uint64_t cap_orders = c->orders.room() / sizeof(msgpu_order), cap_ids = c->ids.room() / 4;
   compact(true);
-  HIPCHK(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   if (int rc = close_readback(c)) return rc;
   c->n_edges_fast     = *host_scalar<uint64_t>(c, SC_TOTAL_C);
   const uint64_t *tot = host_scalar<uint64_t>(c, SC_TOTAL_A);
   c->n_orders = tot[0];
   c->n_ids    = tot[1];
   if (c->n_orders > cap_orders || c->n_ids > cap_ids) { // (the kernel's own test)
-    ENSURE(c, orders, (c->n_orders ? c->n_orders : 1) * sizeof(msgpu_order));
-    ENSURE(c, ids, (c->n_ids ? c->n_ids : 1) * 4);
+    STAGE_HIP(c, c->orders.ensure((c->n_orders ? c->n_orders : 1) * sizeof(msgpu_order)));
+    STAGE_HIP(c, c->ids.ensure((c->n_ids ? c->n_ids : 1) * 4));
     compact(false);
   }
-  HIPCHK(c, hipGetLastError());
-  if (c->stage_events) HIPCHK(c, hipEventRecord(c->ev[8], st));
+  STAGE_HIP(c, hipGetLastError());
+  if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[8], st));
   c->have_chain_t = true;
   c->have_stage_t = c->stage_events;
   c->state        = ST_CHAINED;
@@ -1445,7 +1317,7 @@ int msgpu_get_counts(msgpu_ctx *c, msgpu_counts *out) {
   out->n_ids           = c->state >= ST_CHAINED ? c->n_ids : 0;
   out->n_pairs_scanned = c->state >= ST_EDGES ? c->n_visit : 0;
   out->n_edges_fastpath = c->state >= ST_CHAINED ? c->n_edges_fast : 0;
-  out->n_lost_publications = c->lost_publications;
+  out->n_lost_publications = c->sc.lost;
   out->index_path          = c->index_path;
   return MSGPU_OK;
 }
@@ -1458,12 +1330,12 @@ int msgpu_get_chain_band_counts(msgpu_ctx *c, uint64_t *n_banded, uint64_t *n_fa
   if (!c || !n_banded || !n_fallback) return MSGPU_E_ARG;
   *n_banded = *n_fallback = 0;
   if (c->state < ST_CHAINED || !c->chain_chunks.p) return MSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   const size_t n_chunks = static_cast<size_t>((c->chain_E + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
   const size_t fb_word  = 2 * static_cast<size_t>(c->chain_E / COMPACT_CHUNK + 1);
   std::vector<unsigned long long> w(fb_word + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(w.data(), c->chain_chunks.p, w.size() * 8, hipMemcpyDeviceToHost));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
+  STAGE_HIP(c, hipMemcpy(w.data(), c->chain_chunks.p, w.size() * 8, hipMemcpyDeviceToHost));
   for (size_t k = 0; k < n_chunks; ++k) *n_banded += (w[2 * k] >> 16) & 0xffffull;
   *n_fallback = w[fb_word];
   return MSGPU_OK;
@@ -1472,13 +1344,13 @@ int msgpu_get_chain_band_counts(msgpu_ctx *c, uint64_t *n_banded, uint64_t *n_fa
 int msgpu_get_timings(msgpu_ctx *c, msgpu_timings *out) {
   if (!c || !out) return MSGPU_E_ARG;
   memset(out, 0, sizeof(*out));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->have_index_t) HIPCHK(c, hipEventElapsedTime(&out->index_ms, c->ev[0], c->ev[1]));
-  if (c->have_cand_t) HIPCHK(c, hipEventElapsedTime(&out->candidates_ms, c->ev[2], c->ev[3]));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
+  if (c->have_index_t) STAGE_HIP(c, hipEventElapsedTime(&out->index_ms, c->ev[0], c->ev[1]));
+  if (c->have_cand_t) STAGE_HIP(c, hipEventElapsedTime(&out->candidates_ms, c->ev[2], c->ev[3]));
   if (c->have_chain_t) {
     if (c->have_stage_t) {
-      HIPCHK(c, hipEventElapsedTime(&out->chain_ms, c->ev[4], c->ev[7]));
-      HIPCHK(c, hipEventElapsedTime(&out->compact_ms, c->ev[7], c->ev[8]));
+      STAGE_HIP(c, hipEventElapsedTime(&out->chain_ms, c->ev[4], c->ev[7]));
+      STAGE_HIP(c, hipEventElapsedTime(&out->compact_ms, c->ev[7], c->ev[8]));
     }
     // mean over the msgpu_chaining_and_overlaps calls since the last msgpu_get_timings (at most CK_RING of them)
     double   sum = 0;
@@ -1486,7 +1358,7 @@ int msgpu_get_timings(msgpu_ctx *c, msgpu_timings *out) {
     for (uint32_t i = 0; i < c->ck_count; ++i) {
       const uint32_t slot = (c->ck_head + msgpu_ctx::CK_RING - 1 - i) % msgpu_ctx::CK_RING;
       float          ms   = 0;
-      HIPCHK(c, hipEventElapsedTime(&ms, c->ck_ev[slot][0], c->ck_ev[slot][1]));
+      STAGE_HIP(c, hipEventElapsedTime(&ms, c->ck_ev[slot][0], c->ck_ev[slot][1]));
       sum += ms;
       ++n;
     }
@@ -1502,13 +1374,13 @@ static int copy_tables(msgpu_ctx *c, void *edges, void *ems, void *orders, void 
   if (c->state < ST_EDGES) return fail(c, MSGPU_E_STATE, "no tables yet");
   if ((ems || orders || ids) && c->state < ST_CHAINED)
     return fail(c, MSGPU_E_STATE, "EdgeMatch/order tables exist only after msgpu_chaining_and_overlaps");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  if (edges && c->n_edges) HIPCHK(c, hipMemcpyAsync(edges, c->edges.at(), c->n_edges * sizeof(msgpu_edge), kind, st));
-  if (ems && c->n_ems) HIPCHK(c, hipMemcpyAsync(ems, c->ems.at(), c->n_ems * sizeof(msgpu_edgematch), kind, st));
-  if (orders && c->n_orders) HIPCHK(c, hipMemcpyAsync(orders, c->orders.at(), c->n_orders * sizeof(msgpu_order), kind, st));
-  if (ids && c->n_ids) HIPCHK(c, hipMemcpyAsync(ids, c->ids.at(), c->n_ids * 4, kind, st));
-  if (kind == hipMemcpyDeviceToHost) HIPCHK(c, hipStreamSynchronize(st));
+  if (edges && c->n_edges) STAGE_HIP(c, hipMemcpyAsync(edges, c->edges.at(), c->n_edges * sizeof(msgpu_edge), kind, st));
+  if (ems && c->n_ems) STAGE_HIP(c, hipMemcpyAsync(ems, c->ems.at(), c->n_ems * sizeof(msgpu_edgematch), kind, st));
+  if (orders && c->n_orders) STAGE_HIP(c, hipMemcpyAsync(orders, c->orders.at(), c->n_orders * sizeof(msgpu_order), kind, st));
+  if (ids && c->n_ids) STAGE_HIP(c, hipMemcpyAsync(ids, c->ids.at(), c->n_ids * 4, kind, st));
+  if (kind == hipMemcpyDeviceToHost) STAGE_HIP(c, hipStreamSynchronize(st));
   return MSGPU_OK;
 }
 
@@ -1522,11 +1394,11 @@ int msgpu_copy_tables_device(msgpu_ctx *c, void *d_edges, void *d_ems, void *d_o
 int msgpu_copy_reads(msgpu_ctx *c, int32_t *read_len, uint32_t *read_first_line) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_LOADED) return fail(c, MSGPU_E_STATE, "no rows loaded");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   if (read_len && c->V)
-    HIPCHK(c, hipMemcpyAsync(read_len, c->read_len.p, size_t(c->V) * 4, hipMemcpyDeviceToHost, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(read_len, c->read_len.p, size_t(c->V) * 4, hipMemcpyDeviceToHost, c->stream));
   if (read_first_line && c->V)
-    HIPCHK(c, hipMemcpyAsync(read_first_line, c->read_first.p, size_t(c->V) * 4, hipMemcpyDeviceToHost, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(read_first_line, c->read_first.p, size_t(c->V) * 4, hipMemcpyDeviceToHost, c->stream));
   return host_sync(c, c->stream);
 }
 
@@ -1548,24 +1420,23 @@ int msgpu_find_contraction_edges(msgpu_ctx *c, const void *d_edges, uint64_t n_e
   if (n_edges && !contraction_order) return MSGPU_E_ARG;
   if (n_edges >= 0x7ffffff0ull || n_orders >= 0xfffffff0ull) return fail(c, MSGPU_E_ARG, "tables too large");
   if (!n_edges) return MSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   const auto *edges  = static_cast<const msgpu_edge *>(d_edges);
   const auto *orders = static_cast<const msgpu_order *>(d_orders);
   const size_t V = n_reads;
-  ENSURE(c, g_deg, (2 * V + 2) * 4);                 // degree | cursor
-  ENSURE(c, g_off, (V + 2) * 8);
-  ENSURE(c, g_adj, 2 * n_edges * 4);
-  ENSURE(c, g_cand, (n_orders + 2) * 4);            // [0] = count, then the list
-  ENSURE(c, g_sane, n_orders + 1);
-  ENSURE(c, g_out, n_edges * 8);
-  ENSURE(c, scan_tmp, (size_t(scan_blocks(V + 1)) + 1) * 8);
-  ENSURE(c, scalars, SC_COUNT * 8);
+  STAGE_HIP(c, c->g_deg.ensure((2 * V + 2) * 4));                 // degree | cursor
+  STAGE_HIP(c, c->g_off.ensure((V + 2) * 8));
+  STAGE_HIP(c, c->g_adj.ensure(2 * n_edges * 4));
+  STAGE_HIP(c, c->g_cand.ensure((n_orders + 2) * 4));            // [0] = count, then the list
+  STAGE_HIP(c, c->g_sane.ensure(n_orders + 1));
+  STAGE_HIP(c, c->g_out.ensure(n_edges * 8));
+  STAGE_HIP(c, c->scan_tmp.ensure((size_t(scan_blocks(V + 1)) + 1) * 8));
   uint32_t *deg = c->g_deg.as<uint32_t>(), *cursor = deg + V + 1;
   uint64_t *off = c->g_off.as<uint64_t>();
   uint32_t *cand = c->g_cand.as<uint32_t>();
-  HIPCHK(c, hipMemsetAsync(deg, 0, (2 * V + 2) * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(cand, 0, 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->g_sane.p, 0, n_orders + 1, c->stream));
+  STAGE_HIP(c, hipMemsetAsync(deg, 0, (2 * V + 2) * 4, c->stream));
+  STAGE_HIP(c, hipMemsetAsync(cand, 0, 4, c->stream));
+  STAGE_HIP(c, hipMemsetAsync(c->g_sane.p, 0, n_orders + 1, c->stream));
   launch_degree(c->stream, edges, n_edges, deg);
   exclusive_scan<uint64_t>(c->stream, deg, V + 1, off, c->scan_tmp.as<uint64_t>(), scalar<uint64_t>(c, SC_TOTAL_A));
   launch_fill_adj(c->stream, edges, n_edges, off, cursor, c->g_adj.as<uint32_t>());
@@ -1573,9 +1444,9 @@ int msgpu_find_contraction_edges(msgpu_ctx *c, const void *d_edges, uint64_t n_e
   launch_check_contraction(c->stream, edges, n_edges, orders, off, c->g_adj.as<uint32_t>(), cand + 1, cand, n_orders,
                            static_cast<double>(c->p.wiggle_room), c->g_sane.as<uint8_t>());
   launch_pick_contraction(c->stream, edges, n_edges, c->g_sane.as<uint8_t>(), c->g_out.as<int64_t>());
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(contraction_order, c->g_out.p, n_edges * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, hipMemcpyAsync(contraction_order, c->g_out.p, n_edges * 8, hipMemcpyDeviceToHost, c->stream));
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
   return MSGPU_OK;
 }
 
@@ -1591,7 +1462,7 @@ int msgpu_merge_gathered_ex(msgpu_ctx *c, const void *d_gathered, uint32_t world
                             const uint32_t *id_base, void *d_edges, void *d_orders, void *d_ids, void *hip_stream) {
   if (!c) return MSGPU_E_ARG;
   if (!d_gathered || !counts || world == 0 || world > MAX_WORLD) return fail(c, MSGPU_E_ARG, "bad merge arguments");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   MergeArgs a;
   a.gathered   = static_cast<const uint8_t *>(d_gathered);
   a.slab_bytes = slab_bytes;
@@ -1613,7 +1484,7 @@ int msgpu_merge_gathered_ex(msgpu_ctx *c, const void *d_gathered, uint32_t world
   a.orders = static_cast<msgpu_order *>(d_orders);
   a.ids    = static_cast<uint32_t *>(d_ids);
   launch_merge_gathered(hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream, a);
-  HIPCHK(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   return MSGPU_OK;
 }
 
@@ -1636,7 +1507,7 @@ int msgpu_pack_wire(msgpu_ctx *c, void *d_wire_edges, void *d_wire_orders, void 
   if ((reinterpret_cast<uintptr_t>(d_wire_edges) & 3) || (reinterpret_cast<uintptr_t>(d_wire_orders) & 7) ||
       (reinterpret_cast<uintptr_t>(d_ids) & 3))
     return fail(c, MSGPU_E_ARG, "msgpu_pack_wire: the edge and id blocks need 4-byte, the order block 8-byte alignment");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   PackWireArgs a;
   a.edges    = static_cast<const msgpu_edge *>(c->edges.at());
   a.orders   = static_cast<const msgpu_order *>(c->orders.at());
@@ -1648,9 +1519,9 @@ int msgpu_pack_wire(msgpu_ctx *c, void *d_wire_edges, void *d_wire_orders, void 
   a.n_ids    = c->n_ids;
   a.w_ids    = static_cast<uint32_t *>(d_ids);
   launch_pack_wire(c->stream, a);
-  HIPCHK(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   if (id_bytes == 4 && c->n_ids)
-    HIPCHK(c, hipMemcpyAsync(d_ids, c->ids.at(), c->n_ids * 4, hipMemcpyDeviceToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d_ids, c->ids.at(), c->n_ids * 4, hipMemcpyDeviceToDevice, c->stream));
   return MSGPU_OK;
 }
 
@@ -1684,7 +1555,7 @@ int msgpu_merge_wire(msgpu_ctx *c, const void *d_gathered, uint32_t world, const
     return fail(c, MSGPU_E_ARG, "msgpu_merge_wire: slabs and order blocks need 8-byte, edge and id blocks 4-byte alignment");
   if ((reinterpret_cast<uintptr_t>(d_edges) & 15) || (reinterpret_cast<uintptr_t>(d_orders) & 15))
     return fail(c, MSGPU_E_ARG, "msgpu_merge_wire: the merged edge and order tables need 16-byte alignment (whole-line stores)");
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   MergeArgs a;
   a.gathered   = static_cast<const uint8_t *>(d_gathered);
   a.slab_bytes = slab_bytes;
@@ -1708,7 +1579,7 @@ int msgpu_merge_wire(msgpu_ctx *c, const void *d_gathered, uint32_t world, const
   a.orders = static_cast<msgpu_order *>(d_orders);
   a.ids    = static_cast<uint32_t *>(d_ids);
   launch_merge_wire(hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream, a, id_bytes == 3);
-  HIPCHK(c, hipGetLastError());
+  STAGE_HIP(c, hipGetLastError());
   return MSGPU_OK;
 }
 
@@ -1725,7 +1596,7 @@ namespace {
 
 // pinned host block of at least `need` bytes that keeps its first `valid` bytes (the copy stream must be idle when it
 // moves); `hint` = expected final size
-int ensure_host(msgpu_ctx *c, msgpu_ctx::HostBuf &h, size_t need, size_t valid, size_t hint) {
+int ensure_host(msgpu_ctx *c, HostBuf &h, size_t need, size_t valid, size_t hint) {
   if (need <= h.cap) return MSGPU_OK;
   size_t want = need + need / 4 + 4096;
   if (hint > want) want = hint;
@@ -1736,7 +1607,7 @@ int ensure_host(msgpu_ctx *c, msgpu_ctx::HostBuf &h, size_t need, size_t valid, 
       hipError_t e = hipStreamSynchronize(c->copy_stream);
       if (e != hipSuccess) {
         pinned_block_free(np);
-        HIPCHK(c, e);
+        STAGE_HIP(c, e);
       }
       // (on the host threads: one thread moves 100 MB in 10 ms, and the GPU waits for the result tables meanwhile)
       const size_t piece = size_t(4) << 20, n_pieces = (valid + piece - 1) / piece;
@@ -1908,11 +1779,11 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
   // Vertex facts (Vertex::getNanoporeLength, metaDatum(0)) go first on the copy stream
   if (int rc = ensure_host(c, c->h_read_len, (size_t(V) + 1) * 4, 0, 0)) return rc;
   if (int rc = ensure_host(c, c->h_read_first, (size_t(V) + 1) * 4, 0, 0)) return rc;
-  HIPCHK(c, hipEventRecord(c->ev_done[0], st));
-  HIPCHK(c, hipStreamWaitEvent(cs, c->ev_done[0], 0));
+  STAGE_HIP(c, hipEventRecord(c->ev_done[0], st));
+  STAGE_HIP(c, hipStreamWaitEvent(cs, c->ev_done[0], 0));
   if (V) {
-    HIPCHK(c, hipMemcpyAsync(c->h_read_len.p, c->read_len.p, size_t(V) * 4, hipMemcpyDeviceToHost, cs));
-    HIPCHK(c, hipMemcpyAsync(c->h_read_first.p, c->read_first.p, size_t(V) * 4, hipMemcpyDeviceToHost, cs));
+    STAGE_HIP(c, hipMemcpyAsync(c->h_read_len.p, c->read_len.p, size_t(V) * 4, hipMemcpyDeviceToHost, cs));
+    STAGE_HIP(c, hipMemcpyAsync(c->h_read_first.p, c->read_first.p, size_t(V) * 4, hipMemcpyDeviceToHost, cs));
   }
 
   // Windows of owner reads, cut by measured work: the index build left, per read, the scaffold rows it visits as an owner
@@ -1938,16 +1809,16 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
       acc += weight(k) / sum;
       wa.frac[k] = static_cast<float>(acc);
     }
-    ENSURE(c, cand_off, (size_t(V) + 2) * 8);
-    ENSURE(c, win_cuts, (2 * size_t(B) + 1) * 8);
+    STAGE_HIP(c, c->cand_off.ensure((size_t(V) + 2) * 8));
+    STAGE_HIP(c, c->win_cuts.ensure((2 * size_t(B) + 1) * 8));
     if (!c->full_scan_ok) // (a bin-path build left exactly this scan in cand_off, its total in cand_off[V]: k_index_epilogue)
       exclusive_scan<uint64_t>(st, c->visits.as<uint32_t>(), V, c->cand_off.as<uint64_t>(), c->scan_tmp.as<uint64_t>(),
                                c->cand_off.as<uint64_t>() + V);
     launch_window_cuts(st, c->cand_off.as<uint64_t>(), V, wa, c->win_cuts.as<uint64_t>());
-    HIPCHK(c, hipGetLastError());
+    STAGE_HIP(c, hipGetLastError());
     std::vector<uint64_t> got(2 * size_t(B) - 1);
-    HIPCHK(c, hipMemcpyAsync(got.data(), c->win_cuts.p, got.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipMemcpyAsync(got.data(), c->win_cuts.p, got.size() * 8, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
     const uint64_t total = got[2 * size_t(B) - 2];
     if (total) {
       measured = true;
@@ -2159,9 +2030,9 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
   reset_views();
   c->state = ST_LOADED; // the context's own tables hold one batch only: results are the host tables
   if (rc != MSGPU_OK) return rc;
-  HIPCHK(c, e0);
-  HIPCHK(c, e1);
-  HIPCHK(c, e2);
+  STAGE_HIP(c, e0);
+  STAGE_HIP(c, e1);
+  STAGE_HIP(c, e2);
   if (resident) { // ... or the whole job: the state msgpu_chaining_and_overlaps leaves, minus the per-edge scratch
     c->n_edges      = tot_e;
     c->n_ems        = tot_m;
@@ -2198,33 +2069,33 @@ int msgpu_get_edgematches(msgpu_ctx *c, const uint32_t *edge_idx, size_t n, cons
   if (n >= 0xfffffff0ull) return fail(c, MSGPU_E_ARG, "edge list too long");
   for (size_t i = 0; i < n; ++i)
     if (edge_idx[i] >= c->n_edges) return fail(c, MSGPU_E_ARG, "edge index %u out of range (%llu edges)", edge_idx[i], (unsigned long long)c->n_edges);
-  HIPCHK(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   if (int rc = ensure_host(c, c->h_sel_off, (n + 1) * 8, 0, 0)) return rc;
   uint64_t *h_off = static_cast<uint64_t *>(c->h_sel_off.p);
   h_off[0]        = 0;
   if (n) {
-    ENSURE(c, sel_idx, n * 4);
-    ENSURE(c, sel_cnt, (n + 1) * 4);
-    ENSURE(c, sel_off, (n + 2) * 8);
-    ENSURE(c, scan_tmp, 3 * (size_t(scan_blocks(n)) + 1) * 8);
-    HIPCHK(c, hipMemcpyAsync(c->sel_idx.p, edge_idx, n * 4, hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, c->sel_idx.ensure(n * 4));
+    STAGE_HIP(c, c->sel_cnt.ensure((n + 1) * 4));
+    STAGE_HIP(c, c->sel_off.ensure((n + 2) * 8));
+    STAGE_HIP(c, c->scan_tmp.ensure(3 * (size_t(scan_blocks(n)) + 1) * 8));
+    STAGE_HIP(c, hipMemcpyAsync(c->sel_idx.p, edge_idx, n * 4, hipMemcpyHostToDevice, st));
     launch_em_counts(st, c->edges.as<msgpu_edge>(), c->sel_idx.as<uint32_t>(), n, c->sel_cnt.as<uint32_t>());
     exclusive_scan<uint64_t>(st, c->sel_cnt.as<uint32_t>(), n, c->sel_off.as<uint64_t>(), c->scan_tmp.as<uint64_t>(),
                              c->sel_off.as<uint64_t>() + n + 1); // (out[n] = the total closes the offset list)
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_off, c->sel_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, hipMemcpyAsync(h_off, c->sel_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
   }
   const uint64_t total = h_off[n];
   if (int rc = ensure_host(c, c->h_sel_ems, (total + 1) * sizeof(msgpu_edgematch), 0, 0)) return rc;
   if (total) {
-    ENSURE(c, sel_ems, total * sizeof(msgpu_edgematch));
+    STAGE_HIP(c, c->sel_ems.ensure(total * sizeof(msgpu_edgematch)));
     launch_em_gather(st, c->edges.as<msgpu_edge>(), c->ems.as<msgpu_edgematch>(), c->sel_idx.as<uint32_t>(), n,
                      c->sel_off.as<uint64_t>(), c->sel_ems.as<msgpu_edgematch>());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_sel_ems.p, c->sel_ems.p, total * sizeof(msgpu_edgematch), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, hipMemcpyAsync(c->h_sel_ems.p, c->sel_ems.p, total * sizeof(msgpu_edgematch), hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, hipStreamSynchronize(st));
   }
   *em_off = h_off;
   *ems    = static_cast<const msgpu_edgematch *>(c->h_sel_ems.p);

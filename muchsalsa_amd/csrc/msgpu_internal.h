@@ -1,4 +1,6 @@
-// msgpu_internal.h -- types shared by the kernels (msgpu_kernels.hip) and the C-ABI host layer (msgpu_api.hip).
+// msgpu_internal.h -- types and launch functions shared by the kernel files and the host layers: the overlap context's
+// (msgpu_api.hip) and, through msgpu_stage.h, which includes this header and holds the host scaffolding of all six contexts,
+// the pipeline stages'.
 #ifndef MSGPU_INTERNAL_H
 #define MSGPU_INTERNAL_H
 

@@ -184,19 +184,14 @@ int kf_upload(StageCtx *c, DevArena &D, const char *path, int which, KfFile &f) 
   const uint64_t padded = (f.size + 15) / 16 * 16 + 16;
   STAGE_HIP(c, D.get(&f.d, padded));
   STAGE_HIP(c, hipMemsetAsync(f.d + f.size, '\n', padded - f.size, c->stream)); // (byte `size` closes a last open line)
-  char      *ring = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  char     *ring = nullptr;
+  EventHold ev[2];
   STAGE_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&ring), 2 * KF_SLOT, hipHostMallocDefault));
   struct FreeRing {
-    char       *r;
-    hipEvent_t *e;
-    ~FreeRing() {
-      (void)hipHostFree(r);
-      for (int i = 0; i < 2; ++i)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  } free_ring{ring, ev};
-  for (auto &e : ev) STAGE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    char *r;
+    ~FreeRing() { (void)hipHostFree(r); }
+  } free_ring{ring};
+  for (auto &e : ev) STAGE_HIP(c, e.create(hipEventDisableTiming));
   int slot = 0;
   for (uint64_t at = 0; at < f.size; at += KF_SLOT, slot ^= 1) {
     const size_t n = static_cast<size_t>(std::min<uint64_t>(KF_SLOT, f.size - at));

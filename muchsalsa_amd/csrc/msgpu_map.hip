@@ -551,7 +551,7 @@ struct msgpu_mapctx : msgpu::StageCtx {
   ~msgpu_mapctx();
   int open() {
     const int rc = msgpu_seq_create(device, &seq.p);
-    return rc != MSGPU_OK ? rc : sc.create() ? MSGPU_OK : MSGPU_E_HIP;
+    return rc != MSGPU_OK ? rc : sc.create();
   }
 };
 

@@ -325,7 +325,7 @@ constexpr size_t PACK_PAD = 16; // words of zero padding in front of and behind 
 struct SeqStore {
   void                 *d_buf = nullptr; // SEQ_PAD + bases + SEQ_PAD (freed by msgpu_seq_pack)
   uint64_t              n_bases = 0;
-  hipStream_t           stream = nullptr; // uploads and the 2-bit conversion of THIS store (the two stores may be filled from two host threads)
+  StreamHold            stream;           // uploads and the 2-bit conversion of THIS store (the two stores may be filled from two host threads)
   void                 *ring = nullptr;   // page-locked slots of msgpu_seq_parse_upload (kept for the next file)
   size_t                ring_bytes = 0;
   // 2-bit form (msgpu_seq_pack): 16 words of zero padding, (n_bases + 15) / 16 words, 16 words of padding
@@ -347,7 +347,7 @@ struct SeqStore {
 
 struct msgpu_seqctx {
   int         device = 0;
-  hipStream_t stream = nullptr;
+  StreamHold  stream;
   SeqStore    st[2];
   char        err[256] = {0};
   // device scratch that only grows (msgpu_assembly_finish / msgpu_fasta_format would otherwise pay several
@@ -393,12 +393,8 @@ int msgpu_seq_create(int device, msgpu_seqctx **out) {
   auto *c = new (std::nothrow) msgpu_seqctx();
   if (!c) return MSGPU_E_NOMEM;
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->st[0].stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->st[1].stream, hipStreamNonBlocking) != hipSuccess) {
-    for (auto &st : c->st)
-      if (st.stream) (void)hipStreamDestroy(st.stream);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (hipSetDevice(device) != hipSuccess || c->stream.create() != hipSuccess || c->st[0].stream.create() != hipSuccess ||
+      c->st[1].stream.create() != hipSuccess) {
     delete c;
     return MSGPU_E_HIP;
   }
@@ -415,17 +411,13 @@ void msgpu_seq_destroy(msgpu_seqctx *c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (auto &s : c->st) {
-    if (s.stream) {
-      (void)hipStreamSynchronize(s.stream);
-      (void)hipStreamDestroy(s.stream);
-    }
+    s.stream.reset();
     if (s.d_buf) (void)hipFree(s.d_buf);
     if (s.ring) msgpu::pinned_block_free(s.ring);
     s.drop_packed();
   }
   for (msgpu_seqctx::Scratch *x : {&c->scr_text, &c->scr_recs, &c->scr_map, &c->scr_hdr, &c->scr_pairs, &c->scr_dist})
     if (x->p) (void)hipFree(x->p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -470,7 +462,7 @@ struct DeviceDestination final : msgpu::SeqDestination {
   struct Sink final : msgpu::ByteSink {
     DeviceDestination *d = nullptr;
     char              *slot[RING_SLOTS] = {nullptr};
-    hipEvent_t         ev[RING_SLOTS]   = {nullptr};
+    EventHold          ev[RING_SLOTS];
     bool               busy[RING_SLOTS] = {false};
     int                cur = 0;
     size_t             fill = 0;
@@ -513,11 +505,6 @@ struct DeviceDestination final : msgpu::SeqDestination {
   std::vector<Sink> sinks;
   std::atomic<int>  err{hipSuccess};
   DeviceDestination(msgpu_seqctx *ctx, SeqStore &st) : c(ctx), s(st), stream(st.stream) {}
-  ~DeviceDestination() override {
-    for (Sink &k : sinks)
-      for (hipEvent_t e : k.ev)
-        if (e) (void)hipEventDestroy(e);
-  }
   void fail(hipError_t e) {
     int none = hipSuccess;
     err.compare_exchange_strong(none, static_cast<int>(e));
@@ -551,7 +538,7 @@ struct DeviceDestination final : msgpu::SeqDestination {
       sinks[k].d = this;
       for (int q = 0; q < RING_SLOTS; ++q) {
         sinks[k].slot[q] = static_cast<char *>(s.ring) + (size_t(k) * RING_SLOTS + q) * RING_SLOT;
-        if (hipEventCreateWithFlags(&sinks[k].ev[q], hipEventDisableTiming) != hipSuccess) throw std::bad_alloc();
+        if (sinks[k].ev[q].create(hipEventDisableTiming) != hipSuccess) throw std::bad_alloc();
       }
     }
   }

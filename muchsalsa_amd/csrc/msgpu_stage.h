@@ -1,7 +1,8 @@
-// msgpu_stage.h -- the host-side scaffolding of the pipeline stages (msgpu_filter.hip, msgpu_scrub.hip, msgpu_kmer.hip,
-// msgpu_unitig.hip, msgpu_map.hip), defined once: the stage context with its create / destroy, the HIP-error macro, the
-// device arena with its temporary buffer for rocPRIM, the event clock, the wall-clock timer, the scalar block and its
-// read-back, and the record lookup of the stages that name sequences.  No kernels.
+// msgpu_stage.h -- the host-side scaffolding of the six contexts, defined once: the overlap context (msgpu_api.hip) and the
+// pipeline stages (msgpu_filter.hip, msgpu_scrub.hip, msgpu_kmer.hip, msgpu_unitig.hip, msgpu_map.hip).  The context with
+// its create / destroy, the HIP-error macro, the holders of an event and of a stream, the device arena with its temporary
+// buffer for rocPRIM, the event clock, the wall-clock timer, the scalar block and its read-back, and the record lookup of
+// the stages that name sequences.  msgpu_seq.hip takes the holders.  No kernels.
 #ifndef MSGPU_STAGE_H
 #define MSGPU_STAGE_H
 
@@ -15,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "msgpu.h"
@@ -77,6 +79,46 @@ template <class Ctx> int stage_create(int device, Ctx **out) {
   *out = c;
   return MSGPU_OK;
 }
+
+// ---- handles that give themselves back: movable, not copyable, and usable wherever the raw handle is
+
+struct EventHold {
+  hipEvent_t e = nullptr;
+  EventHold() = default;
+  EventHold(EventHold &&o) noexcept : e(o.e) { o.e = nullptr; }
+  EventHold &operator=(EventHold &&o) noexcept {
+    std::swap(e, o.e);
+    return *this;
+  }
+  ~EventHold() { reset(); }
+  hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+  void       reset() { // (an event that was never created: nothing)
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+  operator hipEvent_t() const { return e; }
+};
+
+struct StreamHold { // waits for what the stream holds before it destroys it
+  hipStream_t s = nullptr;
+  StreamHold() = default;
+  StreamHold(StreamHold &&o) noexcept : s(o.s) { o.s = nullptr; }
+  StreamHold &operator=(StreamHold &&o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
+  ~StreamHold() { reset(); }
+  hipError_t create(unsigned flags = hipStreamNonBlocking) { return hipStreamCreateWithFlags(&s, flags); }
+  hipError_t create(unsigned flags, int priority) { return hipStreamCreateWithPriority(&s, flags, priority); }
+  void       reset() {
+    if (s) {
+      (void)hipStreamSynchronize(s);
+      (void)hipStreamDestroy(s);
+    }
+    s = nullptr;
+  }
+  operator hipStream_t() const { return s; }
+};
 
 struct SeqCtxHold { // the sequence store of a stage that gathers its output from one
   msgpu_seqctx *p = nullptr;
@@ -204,24 +246,19 @@ inline uint32_t grid256(uint64_t n) { return grid_of(n, 256); }
 
 struct StageClock { // device steps by event pairs, summed per step after the run's last synchronisation
   struct Span {
-    hipEvent_t a, b;
-    float     *acc;
+    EventHold a, b;
+    float    *acc = nullptr;
   };
   std::vector<Span> spans;
   hipStream_t       st;
   explicit StageClock(hipStream_t s) : st(s) {}
-  ~StageClock() {
-    for (auto &s : spans) {
-      (void)hipEventDestroy(s.a);
-      (void)hipEventDestroy(s.b);
-    }
-  }
   hipError_t begin(float *acc) {
-    Span       s{nullptr, nullptr, acc};
-    hipError_t e = hipEventCreate(&s.a);
-    if (e == hipSuccess) e = hipEventCreate(&s.b);
+    Span s;
+    s.acc        = acc;
+    hipError_t e = s.a.create();
+    if (e == hipSuccess) e = s.b.create();
     if (e == hipSuccess) e = hipEventRecord(s.a, st);
-    spans.push_back(s);
+    spans.push_back(std::move(s));
     return e;
   }
   hipError_t end() { return hipEventRecord(spans.back().b, st); }
@@ -229,8 +266,6 @@ struct StageClock { // device steps by event pairs, summed per step after the ru
     for (auto &s : spans) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) *s.acc += ms;
-      (void)hipEventDestroy(s.a);
-      (void)hipEventDestroy(s.b);
     }
     spans.clear();
   }
@@ -243,52 +278,83 @@ struct StageTimer { // wall-clock milliseconds since it was made
 
 // ---- the scalar block
 
-// SC_COUNT words on the device, read through the project's read-back protocol (msgpu_device.h, publish_to_host): one wavefront
-// writes them into the mapped mirror and publishes a sequence number, the host polls for it.  A stream that ends without the
-// number arriving is answered by a copy, and counted.
+// SC_COUNT words on the device, read through the project's read-back protocol (msgpu_device.h, publish_to_host), in one of
+// two modes decided when the block is created:
+// - mapped (default): no copy and no stream synchronisation.  The launch that closes a step carries arm()'s HostPublish, one
+//   wavefront of it writes the block into the mapped mirror and publishes a sequence number, the host polls for it in wait()
+//   (about half the latency of copy + synchronise).  A stream that ends or breaks without the number arriving is answered by
+//   a copy, and counted.
+// - copy (MSGPU_SYNC_READBACK, or no mapped pointer): arm() gives a launch nothing to publish; wait() enqueues one copy of
+//   the block into the mirror and waits for it.
+// Work that does not depend on the values can be enqueued between the armed launch and wait(): it keeps the GPU busy while
+// the host turns around.  read() is the two halves around a one-wavefront launch of its own.
 struct ScalarBlock {
   uint64_t *d = nullptr;     // the block on the device
   uint64_t *h = nullptr;     // its page-locked, device-mapped mirror and the sequence number behind it
-  uint64_t *h_dev = nullptr; // the device's address of the mirror; null (MSGPU_SYNC_READBACK): every read-back is a copy
+  uint64_t *h_dev = nullptr; // the device's address of the mirror; null: every read-back is a copy
   uint64_t  seq = 0, lost = 0;
-  ~ScalarBlock() { release(); }
-  bool create() { // on the current device; zeroed
-    if (hipMalloc(reinterpret_cast<void **>(&d), SC_COUNT * sizeof(uint64_t)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&h), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess)
-      return false;
+  EventHold copied; // recorded behind the copy mode's copy: a caller can wait for that alone
+  ~ScalarBlock() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+  }
+  int create() { // on the current device; zeroed.  The mirror is coherent: the host polls it while a kernel writes it
+    if (hipHostMalloc(reinterpret_cast<void **>(&h), (SC_COUNT + 1) * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+      h = nullptr;
+      return MSGPU_E_NOMEM;
+    }
     memset(h, 0, (SC_COUNT + 1) * sizeof(uint64_t));
     void *dev = nullptr;
     if (!getenv("MSGPU_SYNC_READBACK") && hipHostGetDevicePointer(&dev, h, 0) == hipSuccess) h_dev = static_cast<uint64_t *>(dev);
-    return hipMemset(d, 0, SC_COUNT * sizeof(uint64_t)) == hipSuccess;
+    const bool ok = hipMalloc(reinterpret_cast<void **>(&d), SC_COUNT * sizeof(uint64_t)) == hipSuccess &&
+                    hipMemset(d, 0, SC_COUNT * sizeof(uint64_t)) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+                    copied.create(hipEventDisableTiming) == hipSuccess;
+    return ok ? MSGPU_OK : MSGPU_E_HIP;
   }
-  void release() {
-    if (d) (void)hipFree(d);
-    if (h) (void)hipHostFree(h);
-    d = h = h_dev = nullptr;
-  }
-  int read(StageCtx *c) { // the block as it stands at this point of c's stream -> h
+  HostPublish arm() { return h_dev ? HostPublish{h_dev, ++seq} : HostPublish{nullptr, 0}; }
+  // The block as the launch that took arm() left it -> h.  `late()` is asked about once a millisecond, while c's stream is
+  // still busy, whether the caller has waited long enough: not MSGPU_OK ends the wait with that code.  `sync(event)` is the
+  // caller's wait for a copy: for the event behind it, or (null) for c's stream.
+  template <class Late, class Sync> int wait(StageCtx *c, Late late, Sync sync) {
     if (h_dev) {
-      const uint64_t s = ++seq;
-      launch_publish_scalars(c->stream, d, HostPublish{h_dev, s});
-      STAGE_HIP(c, hipGetLastError());
+      const uint64_t     s    = seq;
       volatile uint64_t *flag = h + SC_COUNT;
       for (uint64_t spins = 1;; ++spins) {
         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == s) return MSGPU_OK;
         __builtin_ia32_pause();
-        if ((spins & 0xffff) == 0) {
+        if ((spins & 0xffff) == 0) { // every ~1 ms: is the stream still alive?
           const hipError_t q = hipStreamQuery(c->stream);
-          if (q == hipSuccess) {
+          if (q == hipSuccess) { // everything ran: the number is there, or something is badly wrong
             if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == s) return MSGPU_OK;
             break;
           }
           if (q != hipErrorNotReady) break;
+          if (int rc = late()) return rc;
         }
       }
+      // The stream stopped making progress, or finished without the publication arriving in mapped memory.  Take the values
+      // the slow way, surface a stream error if there is one, and count it either way.  The error text is NOT touched on a
+      // call that goes on to succeed: the text belongs to a non-zero return code.
       ++lost;
     }
     STAGE_HIP(c, hipMemcpyAsync(h, d, SC_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    STAGE_HIP(c, hipStreamSynchronize(c->stream));
-    return MSGPU_OK;
+    if (h_dev) return sync(nullptr);
+    STAGE_HIP(c, hipEventRecord(copied, c->stream));
+    return sync(copied);
+  }
+  int wait(StageCtx *c) { // no deadline, and a copy is waited for with the stream
+    return wait(c, [] { return MSGPU_OK; }, [c](hipEvent_t) -> int {
+      STAGE_HIP(c, hipStreamSynchronize(c->stream));
+      return MSGPU_OK;
+    });
+  }
+  int read(StageCtx *c) { // the block as it stands at this point of c's stream -> h
+    const HostPublish p = arm();
+    if (p.seq) {
+      launch_publish_scalars(c->stream, d, p);
+      STAGE_HIP(c, hipGetLastError());
+    }
+    return wait(c);
   }
 };
 

@@ -326,7 +326,7 @@ using namespace msgpu;
 
 struct msgpu_ugctx : msgpu::StageCtx {
   ScalarBlock sc;
-  int         open() { return sc.create() ? MSGPU_OK : MSGPU_E_HIP; }
+  int         open() { return sc.create(); }
 };
 
 struct msgpu_ug_result {
