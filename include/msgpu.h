@@ -1068,7 +1068,34 @@ void        msgpu_kf_result_free(msgpu_kf_result *r);
  *     msgpu_kf_result_verdicts returns) gives the result of msgpu_ug_run on the two files that hold the records i with
  *     m[i] = 0, in order: both texts, the unitig table, the rounds, n_windows, n_distinct, n_solid, n_solid_trimmed, the unitig
  *     counts and longest_chain.  n_records and bytes_in are the pair's own.  A dropped pair's two reads have the length 0 for
- *     every kernel that forms windows.  With a mask both files hold n_pairs records, else MSGPU_E_ARG. */
+ *     every kernel that forms windows.  With a mask both files hold n_pairs records, else MSGPU_E_ARG.
+ *  9. bubble popping, on request (msgpu_ug_set_bubbles).  The parameter is bubble >= 0, the longest branch in k-mers; 0 means
+ *     off, and rules 1-8 alone apply; a SNP makes branches of k k-mers, so values from k upwards are useful; values above
+ *     4096 are MSGPU_E_ARG.
+ *     (a) Simple branch.  All degrees are taken in the snapshot S of the round.  Let u be an oriented node with
+ *         |succ(u)| >= 2, and b in succ(u).  If |pred(b)| != 1 there is no branch.  path = [b], then repeat: if
+ *         |succ(last)| != 1 there is no branch; let t be the one successor; if |pred(t)| >= 2 the branch is path and its
+ *         merge is t; otherwise, if |path| = bubble there is no branch; otherwise append t.  This is the tip walk of rule 4
+ *         with a fork in front of it.  A successor of u that is itself a merge (|pred| >= 2) is no branch.
+ *     (b) Bubble.  A bubble is a fork u, a merge t, and the >= 2 simple branches of u whose merge is t.  It must have
+ *         canon(u) != canon(t): a bubble whose fork and merge are one k-mer is never popped (a palindromic passage).  The
+ *         mirror of the bubble (u, t) is the bubble (rc(t), rc(u)).  A bubble is judged once, from the side whose fork is the
+ *         smaller 2k-bit string: from u iff u < rc(t).
+ *     (c) Winner.  The winner is the branch with the greatest mean count: branch A beats branch B iff
+ *         sum(A) len(B) > sum(B) len(A), sum = the sum of count over the branch's k-mers, the products in 64 bits (the cap of
+ *         4096 keeps them below 2^56).  Among equals, the branch entered from the judging fork by the smaller base c wins.
+ *         Every k-mer of every other branch of the bubble leaves S.  One fork may hold several bubbles (different merges);
+ *         each is judged alone.
+ *     (d) Rounds.  A bubble round judges all bubbles on a snapshot; all losers leave together when the round ends.  A
+ *         branch's inner nodes have in- and out-degree 1, so each k-mer lies in at most one branch of one bubble or its
+ *         mirror, and no round removes a winner.  The neighbour bytes are refreshed behind a round as behind a tip round.
+ *     (e) Order of the phases.  Rule 4 runs as it is.  Then a bubble phase: rounds repeat until a round removes nothing (that
+ *         last round is recorded too).  If the bubble phase removed nothing in total, or trim = 0, cleaning is done.
+ *         Otherwise a tip phase runs: the round at trim alone, repeated until it removes nothing; if it removed nothing,
+ *         cleaning is done, otherwise the next bubble phase runs.  Rules 5-8 then run on what is left; n_solid_trimmed is
+ *         what cleaning leaves.
+ *     (f) Not done: complex bubbles (overlapping variants whose branches fork again or merge at different nodes) and
+ *         zero-length branches are left alone, and there is no erosion. */
 typedef struct msgpu_ugctx msgpu_ugctx; /* a device context of the stage */
 typedef struct msgpu_ug_result msgpu_ug_result;
 typedef struct msgpu_ug_params {
@@ -1127,6 +1154,26 @@ int         msgpu_ug_run_pair(msgpu_ugctx *ctx, const msgpu_ug_params *params, c
 int         msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out);
 int         msgpu_ug_result_rounds(const msgpu_ug_result *r, const msgpu_ug_round **rounds, uint64_t *n);
 int         msgpu_ug_result_unitigs(const msgpu_ug_result *r, const msgpu_ug_unitig **unitigs, uint64_t *n);
+/* Rule 9.  msgpu_ug_set_bubbles sets the parameter on the context for every later msgpu_ug_run / msgpu_ug_run_pair, until it is
+ * set again; 0 switches it off (what a new context has).  Above MSGPU_UG_BUBBLE_MAX: MSGPU_E_ARG, the previous value stays
+ * and msgpu_ug_last_error names the value.  With the feature off msgpu_ug_result_bubbles gives zeros and an empty table.
+ * msgpu_ug_result_rounds keeps the tip rounds only, those of later tip phases included (n_tip_rounds counts them). */
+#define MSGPU_UG_BUBBLE_MAX 4096u
+typedef struct msgpu_ug_bubble_stats {
+  uint32_t bubble, n_phases, n_rounds, reserved; /* the parameter; bubble phases; bubble rounds over all phases            */
+  uint64_t n_bubbles, n_branches_removed, n_kmers_removed;
+  uint64_t max_forks;                            /* the largest fork list of a round                                       */
+  float    forks_ms, walk_ms;                    /* device, by events: the fork lists; the walks and their apply           */
+  float    adjacency_ms, reserved2;              /* the neighbour bytes behind the bubble rounds                           */
+} msgpu_ug_bubble_stats;
+typedef struct msgpu_ug_bubble_round {
+  uint32_t after_tip_rounds, reserved; /* entries of the tip-round table that precede this round */
+  uint64_t forks, bubbles, branches_removed, removed;
+  float    forks_ms, walk_ms;          /* device, by events */
+} msgpu_ug_bubble_round;
+int         msgpu_ug_set_bubbles(msgpu_ugctx *ctx, uint32_t bubble);
+int         msgpu_ug_result_bubbles(const msgpu_ug_result *r, msgpu_ug_bubble_stats *out, const msgpu_ug_bubble_round **rounds,
+                                    uint64_t *n);
 #define MSGPU_UG_TEXT_ALL 0 /* every record */
 #define MSGPU_UG_TEXT_CUT 1 /* the records with length >= min_length */
 const char *msgpu_ug_result_text(const msgpu_ug_result *r, int which, uint64_t *len);

@@ -192,6 +192,18 @@ class UgUnitig(C.Structure):  # msgpu_ug_unitig
         ("cyclic", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class UgBubbleStats(C.Structure):  # msgpu_ug_bubble_stats
+    _fields_ = ([(n, C.c_uint32) for n in ("bubble", "n_phases", "n_rounds", "reserved")] +
+                [(n, C.c_uint64) for n in ("n_bubbles", "n_branches_removed", "n_kmers_removed", "max_forks")] +
+                [(n, C.c_float) for n in ("forks_ms", "walk_ms", "adjacency_ms", "reserved2")])
+
+
+class UgBubbleRound(C.Structure):  # msgpu_ug_bubble_round
+    _fields_ = ([("after_tip_rounds", C.c_uint32), ("reserved", C.c_uint32)] +
+                [(n, C.c_uint64) for n in ("forks", "bubbles", "branches_removed", "removed")] +
+                [("forks_ms", C.c_float), ("walk_ms", C.c_float)])
+
+
 UG_TEXT_ALL, UG_TEXT_CUT = 0, 1
 
 
@@ -467,6 +479,9 @@ SYMBOLS = [
     ("msgpu_ug_result_stats", C.c_int, [C.c_void_p, C.POINTER(UgStats)]),
     ("msgpu_ug_result_rounds", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgRound)), C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_unitigs", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(UgUnitig)), C.POINTER(C.c_uint64)]),
+    ("msgpu_ug_set_bubbles", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("msgpu_ug_result_bubbles", C.c_int, [C.c_void_p, C.POINTER(UgBubbleStats), C.POINTER(C.POINTER(UgBubbleRound)),
+                                          C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_free", None, [C.c_void_p]),
     ("msgpu_map_default_params", None, [C.POINTER(MapParams)]),

@@ -9,6 +9,9 @@
 //   k_ug_tips    a thread per dead-end oriented node walks at most `limit` nodes, one look-up per step; a tip's k-mers are
 //                marked in an array of their own, so the round sees a snapshot
 //   k_ug_apply   marks -> alive; the number removed goes into the scalar block, read back by the publication protocol
+//   k_ug_forks   rule 9 (on request): the oriented nodes with two or more successors, from the byte alone, compacted by ballot
+//   k_ug_bubbles rule 9: a quad of lanes per fork walks its up to four branches (at most `bubble` look-ups each), compares
+//                them by shuffles inside the quad and marks the losers; k_ug_apply and k_ug_adj close the round as behind tips
 //   k_ug_next    rule 5: next[o] = the node o is joined to.  prev(o) = next[o ^ 1] ^ 1: the mirror chain is the same joins
 //   k_ug_double  pointer doubling towards the chain head: ptr[o] and the distance from it, ping-pong buffers.  A round counts
 //                the nodes that do not point at a head yet; when that number stops falling, what is left lies on cycles
@@ -17,7 +20,8 @@
 //   k_ug_heads   the heads that are emitted (rule 5's mirror choice), with their first k-mer; rocPRIM sorts them by it
 //   k_ug_cover   coverage: 64-bit atomics per unitig
 //   k_ug_write   every node writes one base at offset + distance + k - 1, the head writes its k bases and the '\n'
-// No kernel loops over a unitig or over rounds: the longest loops are `limit` <= trim steps (k_ug_tips) and k bases.
+// No kernel loops over a unitig or over rounds: the longest loops are `limit` <= trim steps (k_ug_tips), `bubble` steps
+// (k_ug_bubbles) and k bases.
 // Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 
@@ -142,6 +146,102 @@ __global__ __launch_bounds__(256) void k_ug_apply(uint32_t n, uint8_t *alive, ui
   }
   const uint64_t who = __ballot(go);
   if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(removed, static_cast<kf_ull>(__popcll(who)));
+}
+
+// rule 9, the forks of a round: the oriented nodes with two or more successors, compacted into a list (any order)
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_forks(UgGraph<K> g, const uint8_t *alive, const uint8_t *adj, uint32_t *forks, uint64_t cap,
+                                                  kf_ull *cursor) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int      lane = threadIdx.x & 63;
+  const uint32_t o = static_cast<uint32_t>(i);
+  bool           take = false;
+  if (i < 2ull * g.n && alive[o >> 1] && __popc(ug_out(adj[o >> 1], o)) >= 2)
+    take = !(o & 1) || ug_rc(g.keys[o >> 1], g.k) != g.keys[o >> 1]; // a self-complementary k-mer is one node
+  const uint64_t who = __ballot(take);
+  if (!who) return;
+  kf_ull at = 0;
+  if (lane == __ffsll(static_cast<long long>(who)) - 1) at = atomicAdd(cursor, static_cast<kf_ull>(__popcll(who)));
+  at = __shfl(at, __ffsll(static_cast<long long>(who)) - 1);
+  if (take) {
+    const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
+    if (slot < cap) forks[slot] = o;
+  }
+}
+
+// rule 9, one round: a quad of lanes per fork, lane c walks the branch entered by base c (at most `bubble` look-ups) and
+// keeps (merge, length, sum of counts); the quad compares its branches by shuffles, and every losing lane walks its branch
+// again to mark it.  alive / adj are the snapshot, mark receives the losers' k-mers
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_bubbles(UgGraph<K> g, const uint8_t *adj, const uint32_t *count, const uint32_t *forks,
+                                                    uint32_t n_forks, uint32_t bubble, uint8_t *mark, kf_ull *n_bubbles,
+                                                    kf_ull *n_branches) {
+  const uint64_t f = (static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x) >> 2;
+  const uint32_t c = threadIdx.x & 3;
+  uint32_t       u = 0, first = UG_NONE, merge = UG_NONE, len = 0;
+  kf_ull         sum = 0;
+  K              su = 0, bs = 0, ms = 0;
+  if (f < n_forks) {
+    u  = forks[f];
+    su = ug_seq(g, u);
+    if (ug_out(adj[u >> 1], u) & (1u << c)) {
+      bs    = ug_succ(g, su, c);
+      first = ug_node(g, bs);
+    }
+  }
+  if (first != UG_NONE && __popc(ug_in(adj[first >> 1], first)) == 1) {
+    K        s = bs;
+    uint32_t cur = first;
+    len = 1;
+    sum = count[first >> 1];
+    for (;;) { // at most `bubble` turns
+      const uint32_t out = ug_out(adj[cur >> 1], cur);
+      if (__popc(out) != 1) break;
+      const K        ts = ug_succ(g, s, static_cast<uint32_t>(__ffs(out)) - 1);
+      const uint32_t t = ug_node(g, ts);
+      if (t == UG_NONE) break; // (the byte said it is there)
+      if (__popc(ug_in(adj[t >> 1], t)) >= 2) {
+        merge = t;
+        ms    = ts;
+        break;
+      }
+      if (len == bubble) break;
+      s   = ts;
+      cur = t;
+      ++len;
+      sum += count[t >> 1];
+    }
+  }
+  // (b), (c) inside the quad: the branches of this fork with my merge, and whether one of them beats mine
+  const bool has = merge != UG_NONE;
+  bool       others = false, beaten = false;
+  for (int x = 1; x < 4; ++x) {
+    const uint32_t om = __shfl_xor(merge, x), ol = __shfl_xor(len, x);
+    const kf_ull   os = __shfl_xor(sum, x);
+    if (has && om == merge) {
+      others = true;
+      const kf_ull theirs = os * len, mine = sum * ol; // below 2^56: a count has 32 bits, a branch at most 4096 k-mers
+      if (theirs > mine || (theirs == mine && (c ^ static_cast<uint32_t>(x)) < c)) beaten = true;
+    }
+  }
+  // the fork and the merge are two k-mers, and the bubble is judged from the side whose fork is the smaller string
+  const bool     judged = has && others && (merge >> 1) != (u >> 1) && su < ug_rc(ms, g.k);
+  const bool     lose = judged && beaten;
+  const uint64_t won = __ballot(judged && !beaten), lost = __ballot(lose);
+  if ((threadIdx.x & 63) == 0) {
+    if (won) atomicAdd(n_bubbles, static_cast<kf_ull>(__popcll(won)));
+    if (lost) atomicAdd(n_branches, static_cast<kf_ull>(__popcll(lost)));
+  }
+  if (!lose) return;
+  K        s = bs;
+  uint32_t cur = first;
+  for (uint32_t j = 0;; ++j) { // the same `len` nodes again
+    mark[cur >> 1] = 1;
+    if (j + 1 == len) break;
+    s   = ug_succ(g, s, static_cast<uint32_t>(__ffs(ug_out(adj[cur >> 1], cur))) - 1);
+    cur = ug_node(g, s);
+    if (cur == UG_NONE) break;
+  }
 }
 
 // an oriented node that exists: its k-mer is alive, and strand 1 only where the k-mer is not its own reverse complement
@@ -326,12 +426,15 @@ using namespace msgpu;
 
 struct msgpu_ugctx : msgpu::StageCtx {
   ScalarBlock sc;
+  uint32_t    bubble = 0; // rule 9's parameter (msgpu_ug_set_bubbles)
   int         open() { return sc.create(); }
 };
 
 struct msgpu_ug_result {
   msgpu_ug_stats               stats{};
   std::vector<msgpu_ug_round>  rounds;
+  msgpu_ug_bubble_stats              bubble_stats{};
+  std::vector<msgpu_ug_bubble_round> bubble_rounds;
   std::vector<msgpu_ug_unitig> units;
   char                        *all = nullptr; // page-locked
   uint64_t                     all_len = 0;
@@ -343,7 +446,9 @@ struct msgpu_ug_result {
 
 namespace {
 
-enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOTAL_C };
+enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOTAL_C,
+       UG_SC_FORKS = SC_NBIG, UG_SC_BUBBLES = SC_NALIVE, UG_SC_BRANCHES = SC_IXFLAGS }; // (the last three lie side by side)
+static_assert(UG_SC_BUBBLES == UG_SC_FORKS + 1 && UG_SC_BRANCHES == UG_SC_FORKS + 2, "one memset zeroes the bubble rounds' counters");
 
 inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->sc.d + slot, 0, 8, c->stream); }
 
@@ -359,8 +464,8 @@ template <> void ug_split<kf_u128>(kf_u128 key, uint64_t &hi, uint64_t &lo) {
 
 // everything behind the format check, for one key width
 template <class K>
-int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_dropped, const msgpu_ug_params &prm, uint64_t budget,
-             msgpu_ug_result *res) {
+int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_dropped, const msgpu_ug_params &prm, uint32_t bubble,
+             uint64_t budget, msgpu_ug_result *res) {
   msgpu_ug_stats &S = res->stats;
   hipStream_t     st = c->stream;
   StageClock      clock(st);
@@ -433,8 +538,14 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
   std::deque<msgpu_ug_round> rounds; // (the clock keeps pointers into it)
   uint64_t                   alive_n = n;
   const uint32_t             trim = static_cast<uint32_t>(prm.trim);
-  for (uint32_t limit = trim ? 1 : 0; limit;) {
-    if (limit > trim) limit = trim;
+  auto refresh = [&](float *ms) -> int { // the neighbour bytes behind a round that removed something
+    STAGE_HIP(c, clock.begin(ms));
+    hipLaunchKernelGGL((k_ug_adj<K, false>), dim3(grid256(n)), dim3(256), 0, st, g, d_alive, d_adj);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+    return MSGPU_OK;
+  };
+  auto tip_round = [&](uint32_t limit, uint64_t &removed) -> int { // rule 4, one round
     rounds.push_back(msgpu_ug_round{limit, 0, 0, 0.f, 0.f});
     msgpu_ug_round &R = rounds.back();
     STAGE_HIP(c, ug_zero_scalar(c, UG_SC_REMOVED));
@@ -445,18 +556,81 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
     }
     STAGE_HIP(c, hipGetLastError());
     STAGE_HIP(c, clock.end());
-    rc = c->sc.read(c);
-    if (rc != MSGPU_OK) return rc;
-    R.removed = c->sc.h[UG_SC_REMOVED];
+    const int r2 = c->sc.read(c);
+    if (r2 != MSGPU_OK) return r2;
+    removed = R.removed = c->sc.h[UG_SC_REMOVED];
     alive_n -= R.removed;
-    if (R.removed) {
-      STAGE_HIP(c, clock.begin(&R.adjacency_ms));
-      hipLaunchKernelGGL((k_ug_adj<K, false>), dim3(grid256(n)), dim3(256), 0, st, g, d_alive, d_adj);
-      STAGE_HIP(c, hipGetLastError());
-      STAGE_HIP(c, clock.end());
-    }
+    return R.removed ? refresh(&R.adjacency_ms) : MSGPU_OK;
+  };
+  for (uint32_t limit = trim ? 1 : 0; limit;) {
+    if (limit > trim) limit = trim;
+    uint64_t removed = 0;
+    rc = tip_round(limit, removed);
+    if (rc != MSGPU_OK) return rc;
     if (limit < trim) limit = limit > trim / 2 ? trim : 2 * limit; // 1, 2, 4, ... below trim, then trim
-    else if (!R.removed) limit = 0;                                // the round at trim repeats until it removes nothing
+    else if (!removed) limit = 0;                                  // the round at trim repeats until it removes nothing
+  }
+  // ---- rule 9 (on request): bubble phases, with a tip phase at trim behind each that removed something
+  msgpu_ug_bubble_stats            &B = res->bubble_stats;
+  std::deque<msgpu_ug_bubble_round> bubble_rounds; // (the clock keeps pointers into it)
+  B.bubble = bubble;
+  if (bubble) {
+    uint32_t *d_forks; // lives during cleaning only
+    STAGE_HIP(c, D.get(&d_forks, n2));
+    kf_ull *sc_d = reinterpret_cast<kf_ull *>(c->sc.d);
+    for (;;) {
+      uint64_t phase_removed = 0;
+      ++B.n_phases;
+      for (;;) { // rounds until one removes nothing
+        bubble_rounds.push_back(msgpu_ug_bubble_round{static_cast<uint32_t>(rounds.size()), 0, 0, 0, 0, 0, 0.f, 0.f});
+        msgpu_ug_bubble_round &R = bubble_rounds.back();
+        STAGE_HIP(c, hipMemsetAsync(c->sc.d + UG_SC_FORKS, 0, 3 * 8, st));
+        STAGE_HIP(c, ug_zero_scalar(c, UG_SC_REMOVED));
+        STAGE_HIP(c, clock.begin(&R.forks_ms));
+        if (n) hipLaunchKernelGGL(k_ug_forks<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_alive, d_adj, d_forks, n2, sc_d + UG_SC_FORKS);
+        STAGE_HIP(c, hipGetLastError());
+        STAGE_HIP(c, clock.end());
+        rc = c->sc.read(c);
+        if (rc != MSGPU_OK) return rc;
+        R.forks = c->sc.h[UG_SC_FORKS];
+        if (R.forks > n2) {
+          snprintf(c->err, sizeof(c->err), "%llu forks among %llu oriented nodes", static_cast<kf_ull>(R.forks), static_cast<kf_ull>(n2));
+          return MSGPU_E_STATE;
+        }
+        if (R.forks) {
+          STAGE_HIP(c, clock.begin(&R.walk_ms));
+          hipLaunchKernelGGL(k_ug_bubbles<K>, dim3(grid256(4 * R.forks)), dim3(256), 0, st, g, d_adj, d_cnt, d_forks,
+                             static_cast<uint32_t>(R.forks), bubble, d_mark, sc_d + UG_SC_BUBBLES, sc_d + UG_SC_BRANCHES);
+          hipLaunchKernelGGL(k_ug_apply, dim3(grid256(n)), dim3(256), 0, st, n, d_alive, d_mark, sc_d + UG_SC_REMOVED);
+          STAGE_HIP(c, hipGetLastError());
+          STAGE_HIP(c, clock.end());
+          rc = c->sc.read(c);
+          if (rc != MSGPU_OK) return rc;
+          R.bubbles          = c->sc.h[UG_SC_BUBBLES];
+          R.branches_removed = c->sc.h[UG_SC_BRANCHES];
+          R.removed          = c->sc.h[UG_SC_REMOVED];
+        }
+        B.n_bubbles += R.bubbles;
+        B.n_branches_removed += R.branches_removed;
+        B.max_forks = std::max<uint64_t>(B.max_forks, R.forks);
+        if (!R.removed) break;
+        alive_n -= R.removed;
+        phase_removed += R.removed;
+        rc = refresh(&B.adjacency_ms);
+        if (rc != MSGPU_OK) return rc;
+      }
+      B.n_kmers_removed += phase_removed;
+      if (!phase_removed || !trim) break;
+      uint64_t tips_removed = 0;
+      for (uint64_t removed = 1; removed;) { // the round at trim alone, until it removes nothing
+        rc = tip_round(trim, removed);
+        if (rc != MSGPU_OK) return rc;
+        tips_removed += removed;
+      }
+      if (!tips_removed) break;
+    }
+    B.n_rounds = static_cast<uint32_t>(bubble_rounds.size());
+    D.drop(d_forks);
   }
   S.n_solid_trimmed = alive_n;
   S.n_tip_rounds    = static_cast<uint32_t>(rounds.size());
@@ -664,10 +838,15 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
       }
     }
     res->rounds.assign(rounds.begin(), rounds.end());
+    res->bubble_rounds.assign(bubble_rounds.begin(), bubble_rounds.end());
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   for (const msgpu_ug_round &R : res->rounds) {
     S.tips_ms += R.tips_ms;
     S.adjacency_ms += R.adjacency_ms;
+  }
+  for (const msgpu_ug_bubble_round &R : res->bubble_rounds) {
+    B.forks_ms += R.forks_ms;
+    B.walk_ms += R.walk_ms;
   }
   S.host_ms += host1.ms();
   S.bytes_out[0] = res->all_len;
@@ -746,8 +925,8 @@ int msgpu_ug_run_pair(msgpu_ugctx *c, const msgpu_ug_params *params, const msgpu
     if (n_pairs) STAGE_HIP(c, hipMemcpyAsync(d_dropped, dropped, n_pairs, hipMemcpyHostToDevice, c->stream));
     STAGE_HIP(c, hipStreamSynchronize(c->stream)); // (the caller's array may go when the call returns)
   }
-  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, budget_bytes, res.get())
-                   : ug_stage<kf_u128>(c, D, F, d_dropped, prm, budget_bytes, res.get());
+  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, c->bubble, budget_bytes, res.get())
+                   : ug_stage<kf_u128>(c, D, F, d_dropped, prm, c->bubble, budget_bytes, res.get());
   if (rc != MSGPU_OK) {
     (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
     return rc;
@@ -785,6 +964,16 @@ int msgpu_ug_run(msgpu_ugctx *c, const msgpu_ug_params *params, const char *path
   return rc;
 }
 
+int msgpu_ug_set_bubbles(msgpu_ugctx *c, uint32_t bubble) {
+  if (!c) return MSGPU_E_ARG;
+  if (bubble > MSGPU_UG_BUBBLE_MAX) {
+    snprintf(c->err, sizeof(c->err), "bubble = %u is above %u", bubble, MSGPU_UG_BUBBLE_MAX);
+    return MSGPU_E_ARG;
+  }
+  c->bubble = bubble;
+  return MSGPU_OK;
+}
+
 int msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out) {
   if (!r || !out) return MSGPU_E_ARG;
   *out = r->stats;
@@ -795,6 +984,14 @@ int msgpu_ug_result_rounds(const msgpu_ug_result *r, const msgpu_ug_round **roun
   if (!r || !rounds || !n) return MSGPU_E_ARG;
   *rounds = r->rounds.data();
   *n      = r->rounds.size();
+  return MSGPU_OK;
+}
+
+int msgpu_ug_result_bubbles(const msgpu_ug_result *r, msgpu_ug_bubble_stats *out, const msgpu_ug_bubble_round **rounds, uint64_t *n) {
+  if (!r || !out || !rounds || !n) return MSGPU_E_ARG;
+  *out    = r->bubble_stats;
+  *rounds = r->bubble_rounds.data();
+  *n      = r->bubble_rounds.size();
   return MSGPU_OK;
 }
 

@@ -82,12 +82,14 @@ def link_input(path, directory, prefix="00_"):
     return link
 
 
-def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False):
+def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
+        bubble=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
     ``cg:Z:`` strings (muchsalsa_amd.mapper's rule 10), as pipeline.sh:175's ``-c --eqx`` asks for; every file written before
-    that PAF is the same."""
+    that PAF is the same.  ``bubble`` (None or 0: off) is the unitig assembly's rule 9 parameter (muchsalsa_amd.unitigs): bubbles
+    with branches of up to that many k-mers are popped before the unitigs are written."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -116,7 +118,7 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     try:
         stage("filter", kmer_filter.run, int(k_filter), None, None, files["report"], None, None, pair=pair, tables=tables)
         stage("unitigs", unitigs.run, int(k_assembly), None, None, files["unitigs"], files["unitigs_cut"], pair=pair,
-              dropped=tables["verdict"], min_length=MIN_LENGTH)
+              dropped=tables["verdict"], min_length=MIN_LENGTH, bubble=bubble)
     finally:
         pair.__exit__(None, None, None)
     index = mapper.Index(reads, device=device)

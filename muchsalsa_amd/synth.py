@@ -569,6 +569,121 @@ def unitig_cases():
             "hairpin": (fq(b"h", [hairpin, hairpin]), None, {"sequence": hairpin})}
 
 
+def _other_base(b, step):
+    """the base ``step`` (1..3) places behind ``b`` in ACGT"""
+    return b"ACGT"[(b"ACGT".index(b) + step) % 4]
+
+
+def diploid_workload(genome=6000, every=400, coverage=15, read_len=100, seed=7, error=0.0):
+    """Input of the unitig assembly with bubble popping (rule 9): (one FASTQ file, None, what it is made of).
+
+    Haplotype 1 is genome_bases(genome, seed).  Haplotype 2 is haplotype 1 with a variant every ``every`` bases (the first at
+    every / 2): by a draw a substitution, or an insertion or a deletion of 1-3 bases, about half each.  From each haplotype
+    ``coverage`` * its length / read_len reads of read_len bases at uniform starts, every read reverse-complemented with
+    probability 1/2; a fraction ``error`` of the bases of the reads is replaced by another base.  Deterministic in
+    (seed, shape)."""
+    G, L = int(genome), int(read_len)
+    a = genome_bases(G, seed)
+    sites = np.arange(every // 2, G - every // 2 + 1, every, dtype=np.int64)
+    kind = splitmix64(seed, 90, len(sites)) % np.uint64(4)        # 0, 1: substitution, 2: insertion, 3: deletion
+    size = (splitmix64(seed, 91, len(sites)) % np.uint64(3)).astype(np.int64) + 1
+    ins = genome_bases(3 * len(sites), seed + 2)
+    parts, at, variants = [], 0, []
+    for i, p in enumerate(int(x) for x in sites):
+        parts.append(a[at:p])
+        if kind[i] < 2:
+            parts.append(np.array([_other_base(int(a[p]), int(size[i]))], np.uint8))
+            at = p + 1
+            variants.append((p, "snp", 1))
+        elif kind[i] == 2:
+            parts.append(ins[3 * i:3 * i + int(size[i])])
+            at = p
+            variants.append((p, "ins", int(size[i])))
+        else:
+            at = p + int(size[i])
+            variants.append((p, "del", int(size[i])))
+    parts.append(a[at:])
+    b = np.concatenate(parts)
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    col = np.arange(L, dtype=np.int64)[None, :]
+    reads = []
+    for h, hap in enumerate((a, b)):
+        n = max(len(hap) * int(coverage) // L, 1)
+        start = _randint(seed, 92 + h, n, 0, len(hap) - L)
+        r = hap[start[:, None] + col]
+        flip = (splitmix64(seed, 94 + h, n) & np.uint64(1)).astype(bool)[:, None]
+        reads.append(np.where(flip, comp[r[:, ::-1]], r))
+    flat = np.ascontiguousarray(np.concatenate(reads)).reshape(-1)
+    n, nb = len(flat) // L, len(flat)
+    sub = np.zeros((256, 3), np.uint8)
+    for base, t in {65: b"CGT", 67: b"GTA", 71: b"TAC", 84: b"ACG"}.items():
+        sub[base] = list(t)
+    pos = _randint(seed, 96, int(nb * error), 0, nb - 1)
+    flat[pos] = sub[flat[pos], (splitmix64(seed, 97, len(pos)) % np.uint64(3)).astype(np.int64)]
+    width = len(str(n - 1))
+    head = 2 + width + 1  # "@d", digits, "\n"
+    rec = np.empty((n, head + L + 3 + L + 1), np.uint8)
+    rec[:, 0], rec[:, 1] = ord("@"), ord("d")
+    idx = np.arange(n, dtype=np.int64)
+    for d in range(width):
+        rec[:, 2 + d] = 48 + (idx // 10 ** (width - 1 - d)) % 10
+    rec[:, head - 1] = 10
+    rec[:, head:head + L] = flat.reshape(n, L)
+    rec[:, head + L:head + L + 3] = np.frombuffer(b"\n+\n", np.uint8)
+    rec[:, head + L + 3:head + 2 * L + 3] = ord("I")
+    rec[:, -1] = 10
+    return rec.tobytes(), None, {"haplotypes": (a.tobytes(), b.tobytes()), "variants": variants}
+
+
+def unitig_bubble_cases(k=21):
+    """Hand-made inputs of rule 9 (bubble popping) of the unitig assembly: name -> (FASTQ file, None, what the case is made
+    of: ``haplotypes`` [(sequence, multiplicity)], ``bubble`` and ``trim`` to run it with).  A is a random sequence of 400
+    bases; every haplotype is tiled into 80-base reads at a step of 10, each read written ``multiplicity`` times.  p = 200.
+
+    edge        A x 3, A with one substitution at p x 2: one bubble of two branches of k k-mers
+    indel_long  A x 3, A without its bases p, p + 1 x 2: the longer branch is the majority
+    indel_short A x 2, the deletion x 2 and the deletion's read over the site once more: the shorter branch has the greater
+                mean and the smaller sum
+    tie         A x 2, the substitution x 2: equal counts, the smaller base wins
+    three_way   three bases at p, x 3, x 2, x 1: one bubble of three branches
+    nested      A x 3, B = A with substitutions at p and p + 12 x 2, B with a further one at p + 6 x 1: a bubble inside a
+                branch of a bubble
+    overlapped  A x 3, B = A with a substitution at p x 2, B with a further one at p + 5 x 1: the branches merge at
+                different nodes
+    palindrome  P + A + rc(P) x 3 beside P + C + rc(P) x 2 for 150 bases P: fork and merge are one k-mer
+    alternate   A x 3, A with a substitution at k + 9 x 2, and 100 random bases followed by A[k + 16 : k + 76] x 2: a junction
+                just behind the bubble, so the start of A is a tip once the bubble is gone; trim = bubble = 3 k"""
+    def tile(seq, step=10, L=80):
+        starts = list(range(0, len(seq) - L + 1, step))
+        if starts[-1] != len(seq) - L:
+            starts.append(len(seq) - L)
+        return [seq[s:s + L] for s in starts]
+
+    def snp(seq, at, step=1):
+        return seq[:at] + bytes([_other_base(seq[at], step)]) + seq[at + 1:]
+
+    def case(haps, extra=(), **kw):
+        reads = [r for seq, m in haps for r in tile(seq) for _ in range(m)] + list(extra)
+        fq = b"".join(b"@b%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads))
+        return fq, None, dict({"haplotypes": haps, "bubble": 3 * k, "trim": k}, **kw)
+
+    A, p = genome_bases(400, 401).tobytes(), 200
+    dele = A[:p] + A[p + 2:]
+    B = snp(snp(A, p), p + 12)
+    P = genome_bases(150, 402).tobytes()
+    R = genome_bases(100, 403).tobytes()
+    return {"edge": case([(A, 3), (snp(A, p), 2)]),
+            "indel_long": case([(A, 3), (dele, 2)]),
+            "indel_short": case([(A, 2), (dele, 2)], extra=[dele[p - 40:p + 40]]),
+            "tie": case([(A, 2), (snp(A, p), 2)]),
+            "three_way": case([(A, 3), (snp(A, p, 1), 2), (snp(A, p, 2), 1)]),
+            "nested": case([(A, 3), (B, 2), (snp(B, p + 6), 1)]),
+            "overlapped": case([(A, 3), (snp(A, p), 2), (snp(snp(A, p), p + 5), 1)]),
+            "palindrome": case([(P + b"A" + _revcomp(P), 3), (P + b"C" + _revcomp(P), 2)]),
+            "alternate": case([(A, 3), (snp(A, k + 9), 2), (R + A[k + 16:k + 76], 2)], bubble=3 * k, trim=3 * k)}
+
+
 def mapper_workload(n_reads, read_len, n_unitigs, seed, coverage=10, error=0.06, families=2, copies=6, repeat_len=600,
                     n_frac=0.0005, lower_frac=0.001, tiled=False, unitig_len=(500, 3000), fastq=True):
     """Input of the mapper (muchsalsa_amd.mapper): a dict with ``reads`` (FASTQ bytes, or FASTA with fastq=False),

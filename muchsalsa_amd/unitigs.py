@@ -3,13 +3,13 @@ at MINLENGTH behind it write in the reference pipeline -- ``NAME-unitigs.fa`` an
 FASTQ files (the k-mer filter's outputs) alone.
 
     python -m muchsalsa_amd.unitigs <k> <in_1.fq> <in_2.fq> <out_all.fa> <out_cut.fa>
-            [--min-count N] [--trim N] [--min-length N] [--budget-mb N]
+            [--min-count N] [--trim N] [--min-length N] [--budget-mb N] [--bubble N]
 
 prints one JSON line of counts and seconds.  ABySS is not needed, and it is not part of the reference tree: the stage is
 defined by the rules below and checked, without tolerance, against the tests' restatement in plain Python
 (tests/ug_oracle.py), not against ABySS.  The rules (include/msgpu.h, "short-read unitig assembly"); parameters k (2..64),
 min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500, the pipeline's
-MINLENGTH):
+MINLENGTH), bubble (0..4096, default 0 = off: rule 9):
 
 1. Input: one or two FASTQ files.  The FASTQ rules and the window rules are rules 1 and 2 of the k-mer abundance filter
    (muchsalsa_amd.kmer_filter), word for word, error code, file and line included.  The files are not pairs: their record
@@ -37,11 +37,40 @@ MINLENGTH):
 7. Limits, each an error and never a fault: fewer than 2^31 solid k-mers; the file limits of the k-mer filter; everything
    resident in device memory together, else the stage fails naming the sizes.  On any error nothing is written.
 
+9. Bubble popping, on request (``bubble``; msgpu_ug_set_bubbles).  The parameter is bubble >= 0, the longest branch in k-mers;
+   0 means off, and rules 1-8 alone apply; a SNP makes branches of k k-mers, so values from k upwards are useful; values above
+   4096 are MSGPU_E_ARG.
+   (a) Simple branch.  All degrees are taken in the snapshot S of the round.  Let u be an oriented node with
+       |succ(u)| >= 2, and b in succ(u).  If |pred(b)| != 1 there is no branch.  path = [b], then repeat: if
+       |succ(last)| != 1 there is no branch; let t be the one successor; if |pred(t)| >= 2 the branch is path and its
+       merge is t; otherwise, if |path| = bubble there is no branch; otherwise append t.  This is the tip walk of rule 4
+       with a fork in front of it.  A successor of u that is itself a merge (|pred| >= 2) is no branch.
+   (b) Bubble.  A bubble is a fork u, a merge t, and the >= 2 simple branches of u whose merge is t.  It must have
+       canon(u) != canon(t): a bubble whose fork and merge are one k-mer is never popped (a palindromic passage).  The
+       mirror of the bubble (u, t) is the bubble (rc(t), rc(u)).  A bubble is judged once, from the side whose fork is the
+       smaller 2k-bit string: from u iff u < rc(t).
+   (c) Winner.  The winner is the branch with the greatest mean count: branch A beats branch B iff
+       sum(A) len(B) > sum(B) len(A), sum = the sum of count over the branch's k-mers, the products in 64 bits (the cap of
+       4096 keeps them below 2^56).  Among equals, the branch entered from the judging fork by the smaller base c wins.
+       Every k-mer of every other branch of the bubble leaves S.  One fork may hold several bubbles (different merges);
+       each is judged alone.
+   (d) Rounds.  A bubble round judges all bubbles on a snapshot; all losers leave together when the round ends.  A
+       branch's inner nodes have in- and out-degree 1, so each k-mer lies in at most one branch of one bubble or its
+       mirror, and no round removes a winner.  The neighbour bytes are refreshed behind a round as behind a tip round.
+   (e) Order of the phases.  Rule 4 runs as it is.  Then a bubble phase: rounds repeat until a round removes nothing (that
+       last round is recorded too).  If the bubble phase removed nothing in total, or trim = 0, cleaning is done.
+       Otherwise a tip phase runs: the round at trim alone, repeated until it removes nothing; if it removed nothing,
+       cleaning is done, otherwise the next bubble phase runs.  Rules 5-8 then run on what is left; n_solid_trimmed is
+       what cleaning leaves.
+   (f) Not done: complex bubbles (overlapping variants whose branches fork again or merge at different nodes) and
+       zero-length branches are left alone, and there is no erosion.
+
 Known differences from ``abyss-pe unitigs``, none of which could be checked against the program (it is not installed where
 this project is built):
 
 * exact counts, where ABySS 2 keeps its k-mers in a Bloom filter;
-* no bubble popping and no erosion of the ends;
+* bubble popping only on request, and only rule 9's simple bubbles: complex bubbles and zero-length branches are left
+  alone; no erosion of the ends;
 * islands are kept until the length cut;
 * ids and the order of the records are this stage's;
 * a sequence is one line.
@@ -61,7 +90,10 @@ import time
 from . import _lib
 from ._stage import StageError, stage_context, text_view
 
-__all__ = ["UnitigError", "run", "main"]
+__all__ = ["UnitigError", "BUBBLE_MAX", "run", "main"]
+
+
+BUBBLE_MAX = 4096  # MSGPU_UG_BUBBLE_MAX
 
 
 class UnitigError(StageError):
@@ -70,25 +102,34 @@ class UnitigError(StageError):
 
 
 def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_length=500, budget_mb=None, tables=None,
-        timings=None, pair=None, dropped=None):
+        timings=None, pair=None, dropped=None, bubble=None):
     """The whole stage: writes ``out_all`` and ``out_cut``; returns the counts.  ``in_2`` may be None.  ``trim`` None: k.
     With ``pair`` (an entered kmer_filter.Pair) the stage runs on the resident files on the pair's device and ``in_1`` /
     ``in_2`` / ``device`` are not read; ``dropped`` (bytes or a uint8 array, one per pair, 1 = dropped) is the mask.
     ``budget_mb`` bounds the count's partition buffers (None: half of the free device memory).  ``tables`` (a dict)
     receives ``rounds`` [(limit, k-mers removed)] and ``unitigs`` [(length, coverage, first k-mer, offset of the sequence in
     the all text, cyclic)] in output order; ``timings`` (a dict) seconds per step (``files``: writing the two outputs), and ``round_seconds`` [(tips,
-    neighbour bytes)] per round."""
+    neighbour bytes)] per round.  ``bubble`` (None or 0: off) is rule 9's parameter; the dict then holds ``bubble``,
+    ``bubbles``, ``bubble_rounds`` [[tip rounds before it, bubbles, k-mers removed]], ``bubble_kmers`` and ``bubble_max_forks`` (the
+    largest fork list of a round), ``tables`` receives
+    ``bubble_rounds`` [(tip rounds before it, forks, bubbles, branches removed, k-mers removed)] and ``timings``
+    ``bubble_forks`` / ``bubble_walk`` / ``bubble_adjacency`` (seconds)."""
     L = _lib.lib()
     t0 = time.perf_counter()
     if dropped is not None and pair is None:
         raise TypeError("dropped needs pair")
     mask = None if dropped is None else bytes(bytearray(dropped))
+    bubble = 0 if bubble is None else int(bubble)
+    if not 0 <= bubble < (1 << 32):
+        raise UnitigError(_lib.E_ARG, detail="bubble = %d" % bubble)
     with stage_context("ug", device if pair is None else pair.device, UnitigError) as stage:
         budget = 0 if budget_mb is None else max(1, int(float(budget_mb) * (1 << 20)))
         prm = _lib.UgParams(int(k), int(min_count) if 0 <= int(min_count) < (1 << 32) else 0, -1 if trim is None else int(trim),
                             min(max(int(min_length), 0), (1 << 32) - 1))
         if trim is not None and int(trim) < 0:
             raise UnitigError(_lib.E_ARG, detail="trim = %d" % int(trim))
+        if bubble:
+            stage.check(L.msgpu_ug_set_bubbles(stage.ctx, bubble))
         with (stage.run(C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget) if pair is None
               else stage.run(C.byref(prm), pair.handle, mask, 0 if mask is None else len(mask), 0, budget, fn="run_pair")) as res:
             st = _lib.UgStats()
@@ -97,10 +138,15 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
             L.msgpu_ug_result_rounds(res, C.byref(rp), C.byref(n))
             rounds = [(int(rp[i].limit), int(rp[i].removed)) for i in range(n.value)]
             round_s = [(rp[i].tips_ms / 1e3, rp[i].adjacency_ms / 1e3) for i in range(n.value)]
+            bs, bp = _lib.UgBubbleStats(), C.POINTER(_lib.UgBubbleRound)()
+            L.msgpu_ug_result_bubbles(res, C.byref(bs), C.byref(bp), C.byref(n))
+            bubble_rounds = [(int(b.after_tip_rounds), int(b.forks), int(b.bubbles), int(b.branches_removed), int(b.removed))
+                             for b in (bp[i] for i in range(n.value))]
             if tables is not None:
                 up = C.POINTER(_lib.UgUnitig)()
                 L.msgpu_ug_result_unitigs(res, C.byref(up), C.byref(n))
                 tables["rounds"] = rounds
+                tables["bubble_rounds"] = bubble_rounds
                 tables["unitigs"] = [(int(u.length), int(u.coverage), (int(u.first_hi) << 64) | int(u.first_lo), int(u.offset),
                                       int(u.cyclic)) for u in (up[i] for i in range(n.value))]
             t1 = time.perf_counter()
@@ -111,6 +157,7 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
     if timings is not None:
         timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.UgStats._fields_ if name.endswith("_ms")})
         timings["stage_wall"] = timings.pop("wall")
+        timings.update({"bubble_" + name[:-3]: getattr(bs, name) / 1e3 for name in ("forks_ms", "walk_ms", "adjacency_ms")})
         timings.update({"files": t_write, "total": time.perf_counter() - t0, "round_seconds": round_s})
     return {"k": int(st.k), "min_count": int(st.min_count), "trim": int(st.trim), "min_length": int(st.min_length),
             "records": [int(x) for x in st.n_records], "windows": int(st.n_windows), "distinct": int(st.n_distinct),
@@ -119,12 +166,14 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
             "cycles": int(st.n_cycles), "longest": int(st.longest_chain), "doubling_rounds": int(st.doubling_rounds),
             "partitions": int(st.n_partitions), "largest_partition": int(st.largest_partition),
             "lost_publications": int(st.n_lost_publications), "bytes_in": [int(x) for x in st.bytes_in],
-            "bytes_out": [int(x) for x in st.bytes_out]}
+            "bytes_out": [int(x) for x in st.bytes_out], "bubble": int(bs.bubble), "bubbles": int(bs.n_bubbles),
+            "bubble_rounds": [[r[0], r[2], r[4]] for r in bubble_rounds], "bubble_kmers": int(bs.n_kmers_removed),
+            "bubble_max_forks": int(bs.max_forks)}
 
 
 def main(argv):
     args = list(argv)
-    opts = {"--min-count": 2, "--trim": None, "--min-length": 500, "--budget-mb": None}
+    opts = {"--min-count": 2, "--trim": None, "--min-length": 500, "--budget-mb": None, "--bubble": 0}
     ok = True
     for name in opts:
         if name in args:
@@ -140,12 +189,13 @@ def main(argv):
         ok = False
     ok = ok and opts["--min-count"] >= 1 and (opts["--trim"] is None or opts["--trim"] >= 0) and opts["--min-length"] >= 0
     ok = ok and (opts["--budget-mb"] is None or opts["--budget-mb"] > 0) and not any(a.startswith("--") for a in args)
+    ok = ok and 0 <= opts["--bubble"] <= BUBBLE_MAX
     if not ok or len(args) != 5:
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
     out = run(k, args[1], args[2], args[3], args[4], min_count=opts["--min-count"], trim=opts["--trim"],
-              min_length=opts["--min-length"], budget_mb=opts["--budget-mb"], timings=timings)
+              min_length=opts["--min-length"], budget_mb=opts["--budget-mb"], timings=timings, bubble=opts["--bubble"])
     rs = timings.pop("round_seconds")
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     out["round_seconds"] = [[round(a, 5), round(b, 5)] for a, b in rs]

@@ -4,9 +4,13 @@ device steps by events -- the count (bins, extract, sort, runs, select), the nei
 pointer doubling, the order (heads, sort, coverage) and the write -- beside the wall time and the host's share.  --clean
 makes the input error-free and repeat-free, so that it is one chain as long as the genome: the doubling's worst case.  The
 tests' plain-Python restatement (tests/ug_oracle.py -- a restatement, NOT ABySS) is timed on a smaller shape
-(--oracle-genome; 0 = not at all) as orientation, not as a claim.  Prints one JSON object; --out also writes it to a file.
+(--oracle-genome; 0 = not at all) as orientation, not as a claim.  --diploid takes the input from synth.diploid_workload
+instead (two haplotypes with a variant every 400 bases, --coverage / 2 each, one file), --bubble N runs the stage with rule 9
+(bubble popping) at N and reports its fork, walk and neighbour-byte times and its rounds.  Prints one JSON object; --out also
+writes it to a file.
 
-    python tools/unitigs_timing.py [--genome 1000000 --coverage 40 --read-len 150 -k 31] [--clean] [--repeat 3] [--out F]
+    python tools/unitigs_timing.py [--genome 1000000 --coverage 40 --read-len 150 -k 31] [--clean] [--diploid] [--bubble N]
+                                   [--repeat 3] [--out F]
 """
 import argparse
 import json
@@ -36,6 +40,8 @@ def main():
     ap.add_argument("-k", type=int, default=31)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--clean", action="store_true", help="no repeats, no errors, no N: one chain as long as the genome")
+    ap.add_argument("--diploid", action="store_true", help="two haplotypes with a variant every 400 bases (synth.diploid_workload)")
+    ap.add_argument("--bubble", type=int, default=0, help="rule 9's parameter (0: off)")
     ap.add_argument("--repeat", type=int, default=3, help="stage runs (fresh process each); the fastest is reported")
     ap.add_argument("--oracle-genome", type=int, default=0, help="genome of the shape the restatement is timed on")
     ap.add_argument("--timeout", type=int, default=600)
@@ -44,11 +50,14 @@ def main():
     from muchsalsa_amd import synth
     extra = dict(families=0, copies=0, error=0.0, n_frac=0.0) if a.clean else {}
     t0 = time.perf_counter()
-    fq1, fq2 = synth.kmer_filter_workload(a.genome, a.coverage, a.read_len, a.seed, **extra)
+    if a.diploid:
+        fq1, fq2 = synth.diploid_workload(a.genome, 400, a.coverage // 2, a.read_len, a.seed, 0.0 if a.clean else 0.004)[0], b""
+    else:
+        fq1, fq2 = synth.kmer_filter_workload(a.genome, a.coverage, a.read_len, a.seed, **extra)
     gen_s = time.perf_counter() - t0
     note("workload in %.1f s" % gen_s)
     res = {"shape": {"genome": a.genome, "coverage": a.coverage, "read_len": a.read_len, "k": a.k, "seed": a.seed,
-                     "clean": a.clean, "bytes": [len(fq1), len(fq2)]}, "generate_s": round(gen_s, 3), "runs": []}
+                     "clean": a.clean, "diploid": a.diploid, "bubble": a.bubble, "bytes": [len(fq1), len(fq2)]}, "generate_s": round(gen_s, 3), "runs": []}
     with tempfile.TemporaryDirectory() as d:
         paths = [os.path.join(d, n) for n in ("in_1.fq", "in_2.fq", "all.fa", "cut.fa")]
         for p, data in zip(paths, (fq1, fq2)):
@@ -59,7 +68,7 @@ def main():
         for i in range(a.repeat):
             t = time.perf_counter()
             r = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, "-m", "muchsalsa_amd.unitigs", str(a.k)] +
-                               paths, cwd=ROOT, env=env, capture_output=True, text=True)
+                               paths + ["--bubble", str(a.bubble)], cwd=ROOT, env=env, capture_output=True, text=True)
             if r.returncode != 0:
                 res["error"] = {"run": i, "rc": r.returncode, "stderr": r.stderr[-2000:]}
                 break
@@ -78,6 +87,7 @@ def main():
             "counts": {x: v for x, v in best.items() if x not in ("seconds", "process_s", "round_seconds")},
             "rounds": [{"limit": l, "removed": n, "tips_s": t, "adjacency_s": b}
                        for (l, n), (t, b) in zip(best["rounds"], best["round_seconds"])],
+            "bubble_steps_s": {x: s[x] for x in ("bubble_forks", "bubble_walk", "bubble_adjacency")},
             "device_steps_s": round(dev, 5), "count_step_s": round(count, 5),
             "count_share_of_device_steps": round(count / dev, 4) if dev else None,
             "doubling_s_per_round": round(s["doubling"] / best["doubling_rounds"], 6) if best["doubling_rounds"] else None,
