@@ -1367,6 +1367,87 @@ typedef struct msgpu_map_astats { /* cigar mode: the segment pairs of rule 10, s
 int         msgpu_map_result_align_stats(const msgpu_map_result *r, msgpu_map_astats *out);
 void        msgpu_map_result_free(msgpu_map_result *r);
 
+/* ---- pileup consensus: polishing a draft from the mapper's run tables ------------------------------
+ * Every chain of reads against a draft, as the mapper's cigar mode gives it (a chain table and the run tables of
+ * msgpu_map_result_cigars, the reads as queries and the draft as targets), votes on the draft's bases; the polished FASTA is
+ * written.  The reference tree has no polisher: the stage is defined by the rules below, in integers only, and is checked
+ * without tolerance against their restatement in plain Python (tests/pl_oracle.py).  Both files go through
+ * msgpu_seq_parse_upload, as the mapper's do.  Parameters: min_depth (>= 1, default 3), min_identity (a percentage, 0..100,
+ * default 0).
+ *  1. tables.  off[0] = 0 and off never decreases (checked first: nothing else can be read without it).  Then, per chain i
+ *     with runs ops[off[i] .. off[i + 1]): (a) its query record is not smaller than chain i - 1's; (b) strand is 0 or 1;
+ *     (c) the query record and (d) the target record are in range; (e) t_start < t_end <= tlen; (f) q_start <= q_end <= qlen;
+ *     (g) every run has len >= 1 and an op in {1 = I, 2 = D, 7 = '=', 8 = X}; (h) the runs consume exactly t_end - t_start
+ *     target bases ('=', X, D) and (i) q_end - q_start query bases ('=', X, I); a run that breaks (g) consumes nothing.  The
+ *     violation reported is that of the smallest chain index, and of that chain the first in the order (a) .. (i):
+ *     MSGPU_E_ARG, the text "chain <i>: <what>".  The check is a device pass that publishes the smallest bad chain through the
+ *     scalar block, and it is complete before any kernel walks a run: a bad table ends in an error, never in a fault.
+ *  2. voters.  A chain is eligible iff matches * 100 >= min_identity * block.  Per query record the voter is the eligible
+ *     chain with the greatest score, then the greatest block, then the first in table order.  Every other chain is ignored
+ *     and counted.
+ *  3. oriented query.  Column j of a chain reads byte q_start + j_q of the query for strand 0 (j_q: the query bases that the
+ *     columns in front of j consume); for strand 1 the oriented query is MSGPU_COPY_REVCOMP's of the whole record (reversed,
+ *     A <-> T and C <-> G in upper case, every other byte as it is), and the chain starts at qlen - q_end in it.  The byte is
+ *     then folded to upper case; A, C, G and T vote for themselves, any other byte votes "other".
+ *  4. pile-up.  Per draft base six 32-bit counters: A, C, G, T, del, other.  An '=' or X column of a voter adds the class of
+ *     its query byte at its target position, a D column adds del; depth(p) is the sum of the six.  An I run of length L of a
+ *     voter that lies between target positions p - 1 and p is one insertion event at slot p; it is usable iff L <= 32 and
+ *     all its bytes are A, C, G or T, and is then keyed (slot, L, the letters packed at 2 bits, the first in the highest
+ *     bits); an unusable event is counted and ignored, and so is an I run that is the first or the last run of its chain.
+ *  5. call, per position p.  depth(p) < min_depth, or A = C = G = T = del = 0: the draft's byte, verbatim.  Else the winner
+ *     is the greatest of A, C, G, T, del; on a tie the draft's own folded base if it is among the tied, else the first of
+ *     A, C, G, T, del.  The winner is the draft's folded base: the draft's byte, verbatim (case is kept: a polish that
+ *     changes nothing is the identity on bytes); del: nothing; else the winner's upper-case letter.
+ *  6. insertions, per slot p with 0 < p < tlen of a record: the usable events are grouped by (L, letters); the candidate is
+ *     the group with the greatest count, then the smaller L, then the smaller packed letters; with
+ *     m = min(depth(p - 1), depth(p)) it is applied iff m >= min_depth and 2 * count > m, and its letters are emitted in
+ *     front of position p's call.  (Usable events at other slots are counted and never applied.)
+ *  7. output.  The records in the draft's order: '>' + the cleaned name + '\n', then the bases wrapped by msgpu_fasta_format
+ *     (60 columns); a record that comes out without bases is the header and an empty line, as msgpu_fasta_format writes a
+ *     length of 0.  On any error nothing is written.
+ *  8. limits, each an error and never a fault: the file limits are the mapper's (a record below 2^31 bases, a file below
+ *     2^38); fewer than 2^31 chains and runs, fewer than 2^40 columns of voters, a polished record below 2^32 bases.  Device
+ *     memory: the six counters per draft base with the slot's winner, the call, the output length and its scan (45 bytes per
+ *     base), 40 bytes per run, the insertion events with their sort buffers (60 bytes per event) and the output (raw bases
+ *     and text) must fit beside the two stores, else MSGPU_E_NOMEM naming the sizes.  Batching over reads is out of scope. */
+typedef struct msgpu_plctx msgpu_plctx; /* a device context of the stage */
+typedef struct msgpu_pl_result msgpu_pl_result;
+typedef struct msgpu_pl_params {
+  int32_t min_depth, min_identity;
+} msgpu_pl_params;
+typedef struct msgpu_pl_stats {
+  uint64_t n_records, n_bases, n_reads, n_read_bases;  /* the draft; the read file */
+  uint64_t n_chains, n_runs, n_voters, n_ignored;      /* rule 2 */
+  uint64_t cols_eq, cols_x, cols_d, cols_i;            /* the voters' columns by op (I: every I run, whatever becomes of it) */
+  uint64_t pos_verbatim, pos_unchanged, pos_substituted, pos_deleted; /* rule 5: no call made; the draft's base won; ... */
+  uint64_t ins_usable, ins_unusable, ins_at_ends;      /* rule 4: the insertion events */
+  uint64_t ins_applied, bases_inserted;                /* rule 6 */
+  uint64_t max_depth;
+  uint64_t n_lost_publications, bytes_out, bytes_peak; /* bytes_peak: the most device bytes the run held beside the stores */
+  msgpu_pl_params params;
+  float load_ms;                                       /* host wall: both files into their stores */
+  float validate_ms, offsets_ms, voters_ms, pileup_ms, insertions_ms, call_ms, output_ms, format_ms, copy_ms; /* device, by events */
+  float wall_ms;
+  uint32_t reserved;
+} msgpu_pl_stats;
+typedef struct msgpu_pl_record { /* per draft record */
+  uint64_t len_in, len_out, n_substituted, n_deleted, n_inserted; /* n_inserted: insertions applied, not their bases */
+  uint64_t depth_x100;                                            /* floor(100 * sum of depth(p) / len_in); 0 for len_in = 0 */
+} msgpu_pl_record;
+void        msgpu_pl_default_params(msgpu_pl_params *p);
+int         msgpu_pl_create(int device, msgpu_plctx **out); /* MSGPU_E_NODEVICE without a GPU */
+void        msgpu_pl_destroy(msgpu_plctx *ctx);
+const char *msgpu_pl_last_error(const msgpu_plctx *ctx);
+/* The whole stage.  chains: n_chains entries; off: n_chains + 1 entries; ops: off[n_chains] entries (host tables, copied).
+ * flags must be 0.  Synchronous; the FASTA is kept in the result. */
+int         msgpu_pl_run(msgpu_plctx *ctx, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
+                         const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags,
+                         msgpu_pl_result **out);
+const char *msgpu_pl_result_text(const msgpu_pl_result *r, uint64_t *len);
+int         msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out);
+int         msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **records, uint64_t *n);
+void        msgpu_pl_result_free(msgpu_pl_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

@@ -247,6 +247,26 @@ class MapBatch(C.Structure):  # msgpu_map_batch
         (n, C.c_uint64) for n in ("n_anchors", "n_query_bases", "n_groups", "n_chains", "n_pairs", "bytes_bound", "bytes_peak")]
 
 
+class PlParams(C.Structure):  # msgpu_pl_params
+    _fields_ = [("min_depth", C.c_int32), ("min_identity", C.c_int32)]
+
+
+class PlStats(C.Structure):  # msgpu_pl_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_records", "n_bases", "n_reads", "n_read_bases", "n_chains", "n_runs", "n_voters",
+                                           "n_ignored", "cols_eq", "cols_x", "cols_d", "cols_i", "pos_verbatim", "pos_unchanged",
+                                           "pos_substituted", "pos_deleted", "ins_usable", "ins_unusable", "ins_at_ends",
+                                           "ins_applied", "bases_inserted", "max_depth", "n_lost_publications", "bytes_out",
+                                           "bytes_peak")] +
+                [("params", PlParams)] +
+                [(n, C.c_float) for n in ("load_ms", "validate_ms", "offsets_ms", "voters_ms", "pileup_ms", "insertions_ms", "call_ms",
+                                          "output_ms", "format_ms", "copy_ms", "wall_ms")] +
+                [("reserved", C.c_uint32)])
+
+
+class PlRecord(C.Structure):  # msgpu_pl_record
+    _fields_ = [(n, C.c_uint64) for n in ("len_in", "len_out", "n_substituted", "n_deleted", "n_inserted", "depth_x100")]
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -505,6 +525,16 @@ SYMBOLS = [
                                           C.POINTER(C.c_uint64)]),
     ("msgpu_map_result_align_stats", C.c_int, [C.c_void_p, C.POINTER(MapAlignStats)]),
     ("msgpu_map_result_free", None, [C.c_void_p]),
+    ("msgpu_pl_default_params", None, [C.POINTER(PlParams)]),
+    ("msgpu_pl_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_pl_destroy", None, [C.c_void_p]),
+    ("msgpu_pl_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_pl_run", C.c_int, [C.c_void_p, C.POINTER(PlParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                               C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("msgpu_pl_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_pl_result_stats", C.c_int, [C.c_void_p, C.POINTER(PlStats)]),
+    ("msgpu_pl_result_records", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(PlRecord)), C.POINTER(C.c_uint64)]),
+    ("msgpu_pl_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -1,0 +1,792 @@
+// msgpu_polish.hip -- the polishing stage: a pile-up consensus of a draft from the mapper's run tables (include/msgpu.h,
+// "pileup consensus").  Every chain of reads against the draft arrives as runs len << 4 | op; the stage
+// checks the tables on the device (rule 1), picks one voter per read (rule 2), walks every column of every voter into six
+// integer counters per draft base (rules 3 and 4), collects, sorts and counts the insertion events (rules 4 and 6), calls
+// every position (rule 5), and writes the polished records through msgpu_fasta_format (rule 7).
+//
+// The shape of the device work.  A run's start in the target and in the oriented query is the exclusive scan of what the runs
+// consume minus the scan's value at the chain's first run: one global 64-bit scan per side serves as the segmented scan, and
+// the consumption check of rule 1 reads the same sums.  The pile-up (k_pl_pileup) does not walk runs at all: the target span
+// [t_start, t_end) of a voter holds exactly one '=', X or D column per position, so the columns of all voters are numbered by
+// the scan of the voters' spans and every lane takes one column -- lanes of a wavefront lie on consecutive target positions
+// whether the chain is one run of 5,000 columns or 200 runs of a few.  A lane finds its chain and its run by two binary
+// searches over the scans.  The counters are planar by class (six rows of one 32-bit word per draft base): the 64 lanes of a
+// wave instruction then add into stretches of 256 contiguous bytes of at most six rows, the shape global atomics run fastest
+// at, where an interleaved layout (24 bytes per base) would spread the same adds over 1,536 bytes; and the call kernel reads
+// every row coalesced.  Integer atomic adds are order-independent: the counters are exact and the same from run to run.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <new>
+#include <string>
+
+#include "msgpu_device.h"
+#include "msgpu_internal.h"
+#include "msgpu_kmer_shared.h"
+#include "msgpu_stage.h"
+
+namespace msgpu {
+
+constexpr uint32_t PL_NONE = 0xffffffffu;
+constexpr uint32_t PL_I = 1, PL_D = 2, PL_EQ = 7, PL_X = 8;
+constexpr uint32_t PL_MAX_INS = 32;
+enum { PL_A = 0, PL_C, PL_G, PL_T, PL_DEL, PL_OTHER, PL_CLASSES };
+// rule 1: what can be wrong with a chain, in the order in which one chain's violations are looked at
+enum { PL_BAD_ORDER = 0, PL_BAD_STRAND, PL_BAD_QREC, PL_BAD_TREC, PL_BAD_TRANGE, PL_BAD_QRANGE, PL_BAD_RUN, PL_BAD_TCONS, PL_BAD_QCONS,
+       PL_BAD_OFF };
+// the counts of msgpu_pl_stats that the kernels add up, one 64-bit word each
+enum { PL_ST_VOTERS = 0, PL_ST_IGNORED, PL_ST_EQ, PL_ST_X, PL_ST_D, PL_ST_I, PL_ST_VERBATIM, PL_ST_UNCHANGED, PL_ST_SUBST, PL_ST_DELETED,
+       PL_ST_USABLE, PL_ST_UNUSABLE, PL_ST_ENDS, PL_ST_APPLIED, PL_ST_INSERTED, PL_ST_MAXDEPTH, PL_ST_COUNT };
+
+struct PlRecs { // the records of a store as the kernels see them
+  const uint8_t  *bases;
+  const uint64_t *off; // ascending
+  const uint32_t *len;
+  uint32_t        n;
+  uint64_t        n_bases;
+};
+
+struct PlTables { // the chain table and the run tables with their scans
+  const msgpu_map_chain *chains;
+  const uint64_t        *off;  // n_chains + 1
+  const uint32_t        *ops;  // n_runs
+  const uint64_t        *T, *Q; // n_runs + 1: target / query bases that the runs in front of a run consume
+  uint32_t               n_chains, n_runs;
+};
+
+// the record that holds byte p of the store, or PL_NONE (padding between records)
+__device__ inline uint32_t pl_record(const PlRecs &R, uint64_t p) {
+  uint32_t lo = 0, hi = R.n; // the last r with off[r] <= p
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (R.off[mid] <= p) lo = mid + 1;
+    else hi = mid;
+  }
+  if (!lo) return PL_NONE;
+  const uint32_t r = lo - 1;
+  return p < R.off[r] + R.len[r] ? r : PL_NONE;
+}
+
+// the last i in [lo, hi) with a[i] <= x (a ascending, a[lo] <= x)
+__device__ inline uint32_t pl_last_le(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t x) {
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// every lane of the wavefront calls these
+__device__ inline void pl_count(bool mine, kf_ull *counter) {
+  const uint64_t who = __ballot(mine);
+  if (who && (threadIdx.x & 63) == static_cast<uint32_t>(__ffsll(static_cast<long long>(who)) - 1)) atomicAdd(counter, static_cast<kf_ull>(__popcll(who)));
+}
+__device__ inline void pl_add(kf_ull v, kf_ull *counter) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
+}
+__device__ inline void pl_max(kf_ull v, kf_ull *counter) {
+  for (int o = 32; o; o >>= 1) {
+    const kf_ull w = __shfl_xor(v, o);
+    v = w > v ? w : v;
+  }
+  if ((threadIdx.x & 63) == 0 && v) atomicMax(counter, v);
+}
+
+__device__ inline void pl_bad(kf_ull *bad, uint32_t chain, uint32_t what) { atomicMin(bad, (static_cast<kf_ull>(chain) << 4) | what); }
+
+// rule 3: the class of the oriented query's byte; s = 1 reads the complement (upper case only, as MSGPU_COPY_REVCOMP), then folds
+__device__ inline uint32_t pl_class(uint8_t b, uint32_t s) {
+  if (s) b = b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b;
+  if (b >= 'a' && b <= 'z') b -= 32;
+  return b == 'A' ? PL_A : b == 'C' ? PL_C : b == 'G' ? PL_G : b == 'T' ? PL_T : PL_OTHER;
+}
+// byte j of the chain's stretch of the oriented query, in the query store
+__device__ inline uint8_t pl_query_byte(const PlRecs &Q, const msgpu_map_chain &ch, uint64_t j) {
+  const uint64_t qlen = Q.len[ch.query];
+  const uint64_t fwd  = ch.strand ? qlen - 1 - (qlen - ch.q_end + j) : ch.q_start + j;
+  return Q.bases[Q.off[ch.query] + fwd];
+}
+
+template <class T> __global__ void k_pl_put(uint64_t *scalars, int slot, const T *src) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) scalars[slot] = static_cast<uint64_t>(*src);
+}
+
+// rule 1, the offsets: nothing else of the tables can be read without them
+__global__ __launch_bounds__(256) void k_pl_check_off(const uint64_t *off, uint32_t n_chains, uint64_t n_runs, kf_ull *bad) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_chains && (off[i + 1] < off[i] || off[i + 1] > n_runs)) pl_bad(bad, i, PL_BAD_OFF);
+}
+
+// the chain of every run; what the run consumes; rule 1 on the run itself
+__global__ __launch_bounds__(256) void k_pl_runs(const uint64_t *off, uint32_t n_chains, const uint32_t *ops, uint32_t n_runs, uint32_t *run_chain,
+                                                 uint32_t *tc, uint32_t *qc, kf_ull *bad) {
+  const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= n_runs) return;
+  const uint32_t i = pl_last_le(off, 0, n_chains, u); // off[0] = 0 <= u, and off[i + 1] > u as off[n_chains] = n_runs
+  const uint32_t len = ops[u] >> 4, op = ops[u] & 15;
+  const bool     ok = len >= 1 && (op == PL_I || op == PL_D || op == PL_EQ || op == PL_X);
+  if (!ok) pl_bad(bad, i, PL_BAD_RUN);
+  run_chain[u] = i;
+  tc[u]        = ok && op != PL_I ? len : 0;
+  qc[u]        = ok && op != PL_D ? len : 0;
+}
+
+// rule 1 on the chain's fields and on what its runs consume
+__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, PlRecs R, PlRecs Q, kf_ull *bad) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= X.n_chains) return;
+  const msgpu_map_chain ch = X.chains[i];
+  uint32_t              what = PL_NONE;
+  auto                  found = [&](uint32_t w) { what = w < what ? w : what; };
+  if (i && ch.query < X.chains[i - 1].query) found(PL_BAD_ORDER);
+  if (ch.strand > 1) found(PL_BAD_STRAND);
+  if (ch.query >= Q.n) found(PL_BAD_QREC);
+  if (ch.target >= R.n) found(PL_BAD_TREC);
+  if (ch.target < R.n && !(ch.t_start < ch.t_end && ch.t_end <= R.len[ch.target])) found(PL_BAD_TRANGE);
+  if (ch.query < Q.n && !(ch.q_start <= ch.q_end && ch.q_end <= Q.len[ch.query])) found(PL_BAD_QRANGE);
+  const uint64_t a = X.off[i], b = X.off[i + 1];
+  if (X.T[b] - X.T[a] != static_cast<uint64_t>(ch.t_end) - ch.t_start) found(PL_BAD_TCONS);
+  if (X.Q[b] - X.Q[a] != static_cast<uint64_t>(ch.q_end) - ch.q_start) found(PL_BAD_QCONS);
+  if (what != PL_NONE) pl_bad(bad, i, what);
+}
+
+// rule 2 in two order-independent passes: the greatest (score, block) of a query's eligible chains, then the first chain that has it
+__device__ inline bool pl_eligible(const msgpu_map_chain &ch, uint32_t min_identity) {
+  return static_cast<uint64_t>(ch.matches) * 100 >= static_cast<uint64_t>(min_identity) * ch.block;
+}
+__device__ inline kf_ull pl_voter_key(const msgpu_map_chain &ch) {
+  return (static_cast<kf_ull>(static_cast<uint32_t>(ch.score) ^ 0x80000000u) << 32) | ch.block;
+}
+__global__ __launch_bounds__(256) void k_pl_voter_key(const msgpu_map_chain *chains, uint32_t n, uint32_t min_identity, kf_ull *vkey) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && pl_eligible(chains[i], min_identity)) atomicMax(&vkey[chains[i].query], pl_voter_key(chains[i]));
+}
+__global__ __launch_bounds__(256) void k_pl_voter_idx(const msgpu_map_chain *chains, uint32_t n, uint32_t min_identity, const kf_ull *vkey,
+                                                      uint32_t *vidx) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && pl_eligible(chains[i], min_identity) && vkey[chains[i].query] == pl_voter_key(chains[i])) atomicMin(&vidx[chains[i].query], i);
+}
+// the voters' spans (0 for every other chain), the counts, and the sum of the depths per draft record
+__global__ __launch_bounds__(256) void k_pl_spans(const msgpu_map_chain *chains, uint32_t n, const uint32_t *vidx, uint32_t *span, kf_ull *rec_depth,
+                                                  kf_ull *st) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const bool     live = i < n, votes = live && vidx[chains[i].query] == i;
+  if (live) span[i] = votes ? chains[i].t_end - chains[i].t_start : 0;
+  if (votes) atomicAdd(&rec_depth[chains[i].target], static_cast<kf_ull>(chains[i].t_end - chains[i].t_start));
+  pl_count(votes, st + PL_ST_VOTERS);
+  pl_count(live && !votes, st + PL_ST_IGNORED);
+}
+
+// rule 4, the columns: lane g takes column g of the voters' spans laid one behind the other (S = the scan of the spans)
+__global__ __launch_bounds__(256) void k_pl_pileup(PlTables X, const uint64_t *S, uint64_t n_cols, PlRecs R, PlRecs Q, uint32_t *cnt, kf_ull *st) {
+  const uint64_t g = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const bool     live = g < n_cols;
+  uint32_t       op = 0;
+  if (live) {
+    const uint32_t        i = pl_last_le(S, 0, X.n_chains, g); // S[i] <= g < S[i + 1]: a voter, the others have no columns
+    const msgpu_map_chain ch = X.chains[i];
+    const uint64_t        x = g - S[i]; // < t_end - t_start
+    const uint32_t        a = static_cast<uint32_t>(X.off[i]), b = static_cast<uint32_t>(X.off[i + 1]);
+    const uint64_t        t0 = X.T[a];
+    const uint32_t        u = pl_last_le(X.T, a, b, t0 + x); // T[u] <= t0 + x < T[u + 1]: the run consumes target bases
+    op = X.ops[u] & 15;
+    uint32_t cls = PL_DEL;
+    if (op != PL_D) cls = pl_class(pl_query_byte(Q, ch, X.Q[u] - X.Q[a] + (t0 + x - X.T[u])), ch.strand);
+    atomicAdd(&cnt[cls * R.n_bases + R.off[ch.target] + ch.t_start + x], 1u);
+  }
+  pl_count(op == PL_EQ, st + PL_ST_EQ);
+  pl_count(op == PL_X, st + PL_ST_X);
+  pl_count(op == PL_D, st + PL_ST_D);
+}
+
+// rule 4, the insertion events.  FILL = false: flag[u] = the run is a usable event at a slot 0 < p < tlen, and the counts;
+// FILL = true: event E[u] = (slot in the store << 6 | L, the 2-bit packed letters, the first in the highest bits).
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_chain, const uint32_t *vidx, PlRecs R, PlRecs Q, uint32_t *flag,
+                                                const uint32_t *E, uint64_t *ev_key, uint64_t *ev_seq, kf_ull *st) {
+  const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+  bool           ins = false, ends = false, usable = false;
+  uint32_t       L = 0;
+  if (u < X.n_runs && (X.ops[u] & 15) == PL_I && (!FILL || flag[u])) {
+    const uint32_t        i = run_chain[u];
+    const msgpu_map_chain ch = X.chains[i];
+    if (vidx[ch.query] == i) {
+      const uint32_t a = static_cast<uint32_t>(X.off[i]), b = static_cast<uint32_t>(X.off[i + 1]);
+      ins  = true;
+      L    = X.ops[u] >> 4;
+      ends = u == a || u + 1 == b;
+      if (!ends && L <= PL_MAX_INS) {
+        const uint64_t j = X.Q[u] - X.Q[a];
+        uint64_t       packed = 0;
+        usable = true;
+        for (uint32_t x = 0; x < L; ++x) {
+          const uint32_t cls = pl_class(pl_query_byte(Q, ch, j + x), ch.strand);
+          usable = usable && cls < PL_DEL;
+          packed = packed << 2 | (cls & 3);
+        }
+        const uint64_t p = ch.t_start + (X.T[u] - X.T[a]);
+        if (FILL) {
+          ev_key[E[u]] = (R.off[ch.target] + p) << 6 | L;
+          ev_seq[E[u]] = packed;
+        } else {
+          flag[u] = usable && p > 0 && p < R.len[ch.target];
+        }
+      }
+    }
+  }
+  if (!FILL) {
+    pl_add(L, st + PL_ST_I);
+    pl_count(ends, st + PL_ST_ENDS);
+    pl_count(usable, st + PL_ST_USABLE);
+    pl_count(ins && !ends && !usable, st + PL_ST_UNUSABLE);
+  }
+}
+
+// rule 6: the events sorted by (slot, L, letters).  head[e] = event e starts a group of equal events
+__global__ __launch_bounds__(256) void k_pl_heads(const uint64_t *key, const uint64_t *seq, uint32_t n, uint32_t *head) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e < n) head[e] = e == 0 || key[e] != key[e - 1] || seq[e] != seq[e - 1];
+}
+// gstart[g] = the first event of group g (G = the scan of head, G[n] = the groups), gstart[groups] = n
+__global__ __launch_bounds__(256) void k_pl_gstart(const uint32_t *head, const uint32_t *G, uint32_t n, uint32_t *gstart) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e < n && head[e]) gstart[G[e]] = e;
+  if (e == n) gstart[G[n]] = n;
+}
+// per slot the group with the greatest count; groups are numbered by (slot, L, letters), so the smaller number wins a tie
+__global__ __launch_bounds__(256) void k_pl_best(const uint32_t *gstart, const uint32_t *n_groups, const uint64_t *key, kf_ull *best) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= *n_groups) return;
+  const uint32_t e = gstart[g], count = gstart[g + 1] - e;
+  atomicMax(&best[key[e] >> 6], (static_cast<kf_ull>(count) << 32) | (PL_NONE - g));
+}
+
+struct PlCall { // rules 5 and 6 per byte of the draft's store
+  const uint32_t *cnt;
+  kf_ull         *best; // in: the slot's winner (0: none); out: 1 << 63 | its first event when it is applied, else 0
+  const uint32_t *gstart;
+  const uint64_t *key;
+  uint8_t        *call;   // 0: the draft's byte; 'A' 'C' 'G' 'T': that letter; 1: nothing
+  uint32_t       *outlen; // bytes that the position emits
+  kf_ull         *rec_sub, *rec_del, *rec_ins;
+  uint32_t        min_depth;
+};
+constexpr kf_ull PL_APPLIED = 1ull << 63;
+
+__device__ inline uint32_t pl_depth(const uint32_t *cnt, uint64_t plane, uint64_t pos) {
+  uint32_t d = 0;
+  for (int c = 0; c < PL_CLASSES; ++c) d += cnt[c * plane + pos];
+  return d;
+}
+
+__global__ __launch_bounds__(256) void k_pl_call(PlRecs R, PlCall a, kf_ull *st) {
+  const uint64_t pos = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const uint32_t r = pos < R.n_bases ? pl_record(R, pos) : PL_NONE;
+  int            kind = -1; // 0 verbatim, 1 unchanged, 2 substituted, 3 deleted
+  uint32_t       depth = 0, ins_len = 0;
+  if (r != PL_NONE) {
+    uint32_t v[PL_CLASSES];
+    for (int c = 0; c < PL_CLASSES; ++c) {
+      v[c] = a.cnt[c * R.n_bases + pos];
+      depth += v[c];
+    }
+    uint8_t out = 0;
+    kind        = 0;
+    if (depth >= a.min_depth && (v[PL_A] | v[PL_C] | v[PL_G] | v[PL_T] | v[PL_DEL])) {
+      const uint32_t own = pl_class(R.bases[pos], 0); // PL_OTHER: a draft byte that is no base never wins a tie
+      uint32_t       win = PL_A;
+      for (uint32_t c = PL_C; c <= PL_DEL; ++c)
+        if (v[c] > v[win]) win = c;
+      if (own < PL_DEL && v[own] == v[win]) win = own;
+      kind = win == own ? 1 : win == PL_DEL ? 3 : 2;
+      out  = kind == 1 ? 0 : kind == 3 ? 1 : "ACGT"[win];
+    }
+    const kf_ull w = a.best[pos];
+    kf_ull       keep = 0;
+    if (w && pos > R.off[r]) { // (an event's slot is never a record's first position; the test keeps pos - 1 inside the record)
+      const uint32_t count = static_cast<uint32_t>(w >> 32), e = a.gstart[PL_NONE - static_cast<uint32_t>(w)];
+      const uint32_t left = pl_depth(a.cnt, R.n_bases, pos - 1), m = left < depth ? left : depth;
+      if (m >= a.min_depth && 2ull * count > m) {
+        ins_len = static_cast<uint32_t>(a.key[e] & 63);
+        keep    = PL_APPLIED | e;
+      }
+    }
+    a.best[pos]   = keep;
+    a.call[pos]   = out;
+    a.outlen[pos] = ins_len + (kind == 3 ? 0 : 1);
+    if (kind == 2) atomicAdd(&a.rec_sub[r], 1ull);
+    if (kind == 3) atomicAdd(&a.rec_del[r], 1ull);
+    if (ins_len) atomicAdd(&a.rec_ins[r], 1ull);
+  } else if (pos < R.n_bases) {
+    a.outlen[pos] = 0;
+    a.best[pos]   = 0;
+  }
+  pl_count(kind == 0, st + PL_ST_VERBATIM);
+  pl_count(kind == 1, st + PL_ST_UNCHANGED);
+  pl_count(kind == 2, st + PL_ST_SUBST);
+  pl_count(kind == 3, st + PL_ST_DELETED);
+  pl_count(ins_len != 0, st + PL_ST_APPLIED);
+  pl_add(ins_len, st + PL_ST_INSERTED);
+  pl_max(depth, st + PL_ST_MAXDEPTH);
+}
+
+// rule 7: every position's bytes at the scan of the lengths (O), the applied insertion in front of the call
+__global__ __launch_bounds__(256) void k_pl_scatter(PlRecs R, const uint8_t *call, const kf_ull *best, const uint64_t *key, const uint64_t *seq,
+                                                    const uint32_t *outlen, const uint64_t *O, uint8_t *raw) {
+  const uint64_t pos = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (pos >= R.n_bases || !outlen[pos]) return;
+  uint64_t     w = O[pos];
+  const kf_ull b = best[pos];
+  if (b & PL_APPLIED) {
+    const uint32_t e = static_cast<uint32_t>(b), L = static_cast<uint32_t>(key[e] & 63);
+    const uint64_t s = seq[e];
+    for (uint32_t x = 0; x < L; ++x) raw[w++] = "ACGT"[(s >> (2 * (L - 1 - x))) & 3];
+  }
+  if (call[pos] != 1) raw[w] = call[pos] ? call[pos] : R.bases[pos];
+}
+__global__ __launch_bounds__(256) void k_pl_reclen(PlRecs R, const uint64_t *O, uint64_t *rec_start, uint64_t *rec_len) {
+  const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R.n) return;
+  rec_start[r] = O[R.off[r]];
+  rec_len[r]   = O[R.off[r] + R.len[r]] - O[R.off[r]];
+}
+
+} // namespace msgpu
+
+using namespace msgpu;
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+struct msgpu_plctx : msgpu::StageCtx {
+  SeqCtxHold  seq;
+  ScalarBlock sc;
+  int         open() {
+    const int rc = msgpu_seq_create(device, &seq.p);
+    return rc != MSGPU_OK ? rc : sc.create();
+  }
+};
+
+struct msgpu_pl_result {
+  msgpu_pl_stats               stats{};
+  std::vector<msgpu_pl_record> records;
+  std::string                  text;
+};
+
+namespace {
+
+enum { PL_SC_BAD = 0, PL_SC_TOTAL };
+static_assert(PL_SC_TOTAL < SC_COUNT, "the scalar block");
+static_assert(sizeof(msgpu_pl_stats) == 256 && sizeof(msgpu_pl_record) == 48 && sizeof(msgpu_map_chain) == 48, "the C-ABI's sizes");
+
+// (each begins with the words tests/pl_oracle.py uses for it)
+const char *const PL_WHAT[] = {"query order (the chains are not ordered by query record)", "strand (neither 0 nor 1)",
+                               "query record (out of range)", "target record (out of range)", "target range (not t_start < t_end <= tlen)",
+                               "query range (not q_start <= q_end <= qlen)", "run (a length of 0, or an op that is none of I, D, =, X)",
+                               "target consumption (the runs do not consume t_end - t_start target bases)",
+                               "query consumption (the runs do not consume q_end - q_start query bases)",
+                               "offsets (the run offsets decrease or exceed the run table)"};
+
+struct PlFile { // a file in its store
+  SeqFileHold f;
+  PlRecs      recs{};
+};
+
+int pl_load(msgpu_plctx *c, DevArena &D, const char *path, int kind, const char *what, PlFile &F) {
+  int rc = msgpu_seq_parse_upload(c->seq, kind, path, -1, &F.f.f);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "%s %s: %s", what, path, msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  const uint32_t        n = msgpu_seq_count(F.f);
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  try {
+    off.resize(n);
+    len.resize(n);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  uint64_t n_bases = 0;
+  F.recs.bases = seq_store_bases(c->seq, kind, &n_bases);
+  for (uint32_t i = 0; i < n; ++i) { // the file limits are the mapper's
+    const uint64_t L = msgpu_seq_length(F.f, i);
+    off[i] = msgpu_seq_offset(F.f, i);
+    if (L >= (1ull << 31)) {
+      snprintf(c->err, sizeof(c->err), "%s record %u has %llu bases; the limit is 2^31 - 1", what, i, static_cast<kf_ull>(L));
+      return MSGPU_E_ARG;
+    }
+    if ((i && off[i] < off[i - 1] + len[i - 1]) || off[i] + L > n_bases) {
+      snprintf(c->err, sizeof(c->err), "%s record %u does not lie behind record %u in the store", what, i, i ? i - 1 : 0);
+      return MSGPU_E_STATE;
+    }
+    len[i] = static_cast<uint32_t>(L);
+  }
+  if (n_bases >= (1ull << 38)) {
+    snprintf(c->err, sizeof(c->err), "%s: %llu bases; the limit is 2^38 - 1", what, static_cast<kf_ull>(n_bases));
+    return MSGPU_E_ARG;
+  }
+  uint64_t *d_off;
+  uint32_t *d_len;
+  STAGE_HIP(c, D.get(&d_off, n));
+  STAGE_HIP(c, D.get(&d_len, n));
+  if (n) {
+    STAGE_HIP(c, hipMemcpyAsync(d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  F.recs.off     = d_off;
+  F.recs.len     = d_len;
+  F.recs.n       = n;
+  F.recs.n_bases = n_bases;
+  return MSGPU_OK;
+}
+
+// rule 8: `need` more bytes beside what the device holds already
+int pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const char *a_name, uint64_t b, const char *b_name) {
+  size_t free_b = 0, total_b = 0;
+  STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
+  if (need <= free_b) return MSGPU_OK;
+  snprintf(c->err, sizeof(c->err), "%s: %llu %s and %llu %s need %llu bytes of device memory beside the two stores; %zu are free", what,
+           static_cast<kf_ull>(a), a_name, static_cast<kf_ull>(b), b_name, static_cast<kf_ull>(need), free_b);
+  return MSGPU_E_NOMEM;
+}
+
+template <class T> hipError_t pl_zeroed(DevArena &D, hipStream_t st, T **out, size_t n) {
+  hipError_t e = D.get(out, n);
+  return e == hipSuccess && n ? hipMemsetAsync(*out, 0, n * sizeof(T), st) : e;
+}
+
+int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
+           uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, msgpu_pl_result *res) {
+  msgpu_pl_stats &S = res->stats;
+  hipStream_t     st = c->stream;
+  DevArena        D;
+  StageClock      clock(st);
+  int             rc;
+  std::vector<uint64_t> h_rec[6]; // per draft record: start, length out, substitutions, deletions, insertions, sum of the depths
+  uint64_t              h_st[PL_ST_COUNT];
+  struct Drain { // on every way out the stream is idle before the copies' destinations and the arena go
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{st};
+  S.params = prm;
+
+  const uint64_t n_runs64 = n_chains64 ? off[n_chains64] : 0;
+  if (n_chains64 >= (1ull << 31) || n_runs64 >= (1ull << 31) || (n_chains64 && off[0] != 0)) {
+    snprintf(c->err, sizeof(c->err), "%llu chains with %llu runs from offset %llu; the limits are 2^31 - 1 of each, from offset 0",
+             static_cast<kf_ull>(n_chains64), static_cast<kf_ull>(n_runs64), static_cast<kf_ull>(n_chains64 ? off[0] : 0));
+    return MSGPU_E_ARG;
+  }
+  const uint32_t n_chains = static_cast<uint32_t>(n_chains64), n_runs = static_cast<uint32_t>(n_runs64);
+  S.n_chains = n_chains;
+  S.n_runs   = n_runs;
+
+  const StageTimer loading;
+  PlFile           FT, FQ;
+  if ((rc = pl_load(c, D, draft_path, 1, "draft", FT)) != MSGPU_OK) return rc;
+  if ((rc = pl_load(c, D, reads_path, 0, "reads", FQ)) != MSGPU_OK) return rc;
+  S.load_ms = loading.ms();
+  const PlRecs &R = FT.recs, &Q = FQ.recs;
+  S.n_records    = R.n;
+  S.n_bases      = R.n_bases;
+  S.n_reads      = Q.n;
+  S.n_read_bases = Q.n_bases;
+  const uint64_t NB = R.n_bases;
+
+  // rule 8, what does not depend on the events: per draft byte the six counters, the slot's winner, the call, the output
+  // length and its scan; per run the op, what it consumes on both sides with the two scans, its chain, the event flag and
+  // its scan; per chain the entry, the offset, the span and its scan; per read the voter's key and index
+  const uint64_t fixed_bytes = NB * (PL_CLASSES * 4ull + 8 + 1 + 4 + 8) + n_runs * (4ull + 4 + 4 + 8 + 8 + 4 + 4 + 4) +
+                               n_chains * (sizeof(msgpu_map_chain) + 8ull + 4 + 8) + Q.n * 12ull + R.n * 48ull + (8ull << 20);
+  if ((rc = pl_room(c, fixed_bytes, "the pile-up", NB, "draft bases", n_runs, "runs")) != MSGPU_OK) return rc;
+
+  kf_ull *d_st, *d_bad = reinterpret_cast<kf_ull *>(c->sc.d + PL_SC_BAD);
+  STAGE_HIP(c, pl_zeroed(D, st, &d_st, PL_ST_COUNT));
+  STAGE_HIP(c, hipMemsetAsync(d_bad, 0xff, 8, st));
+
+  // ---- rule 1
+  msgpu_map_chain *d_chains;
+  uint64_t        *d_off, *d_T, *d_Q;
+  uint32_t        *d_ops, *d_run_chain, *d_tc, *d_qc;
+  STAGE_HIP(c, D.get(&d_chains, n_chains));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_off, n_chains + 1ull));
+  STAGE_HIP(c, D.get(&d_ops, n_runs));
+  STAGE_HIP(c, D.get(&d_run_chain, n_runs));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_tc, n_runs + 1ull)); // (a zero behind the last run: the scans give n_runs + 1 sums)
+  STAGE_HIP(c, pl_zeroed(D, st, &d_qc, n_runs + 1ull));
+  STAGE_HIP(c, D.get(&d_T, n_runs + 1ull));
+  STAGE_HIP(c, D.get(&d_Q, n_runs + 1ull));
+  if (n_chains) {
+    STAGE_HIP(c, hipMemcpyAsync(d_chains, chains, n_chains * sizeof(msgpu_map_chain), hipMemcpyHostToDevice, st));
+    STAGE_HIP(c, hipMemcpyAsync(d_off, off, (n_chains + 1ull) * 8, hipMemcpyHostToDevice, st));
+  }
+  if (n_runs) STAGE_HIP(c, hipMemcpyAsync(d_ops, ops, n_runs * 4ull, hipMemcpyHostToDevice, st));
+  auto bad_chain = [&]() -> int { // the smallest bad chain, through the scalar block
+    const int r2 = c->sc.read(c);
+    if (r2 != MSGPU_OK) return r2;
+    const uint64_t bad = c->sc.h[PL_SC_BAD];
+    if (bad == ~0ull) return MSGPU_OK;
+    snprintf(c->err, sizeof(c->err), "chain %llu: %s", static_cast<kf_ull>(bad >> 4), PL_WHAT[bad & 15]);
+    return MSGPU_E_ARG;
+  };
+  STAGE_HIP(c, clock.begin(&S.validate_ms));
+  if (n_chains) hipLaunchKernelGGL(k_pl_check_off, dim3(grid256(n_chains)), dim3(256), 0, st, d_off, n_chains, n_runs64, d_bad);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  if ((rc = bad_chain()) != MSGPU_OK) return rc;
+  STAGE_HIP(c, clock.begin(&S.offsets_ms));
+  if (n_runs) hipLaunchKernelGGL(k_pl_runs, dim3(grid256(n_runs)), dim3(256), 0, st, d_off, n_chains, d_ops, n_runs, d_run_chain, d_tc, d_qc, d_bad);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_tc, d_T, n_runs + 1ull));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_qc, d_Q, n_runs + 1ull));
+  STAGE_HIP(c, clock.end());
+  const PlTables X{d_chains, d_off, d_ops, d_T, d_Q, n_chains, n_runs};
+  STAGE_HIP(c, clock.begin(&S.validate_ms));
+  if (n_chains) hipLaunchKernelGGL(k_pl_check_chain, dim3(grid256(n_chains)), dim3(256), 0, st, X, R, Q, d_bad);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  if ((rc = bad_chain()) != MSGPU_OK) return rc; // no kernel below runs on a table that breaks rule 1
+
+  // ---- rule 2
+  kf_ull   *d_vkey, *d_rec_depth, *d_rec_sub, *d_rec_del, *d_rec_ins;
+  uint32_t *d_vidx, *d_span;
+  uint64_t *d_S;
+  STAGE_HIP(c, pl_zeroed(D, st, &d_vkey, Q.n));
+  STAGE_HIP(c, D.get(&d_vidx, Q.n));
+  if (Q.n) STAGE_HIP(c, hipMemsetAsync(d_vidx, 0xff, Q.n * 4ull, st));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_span, n_chains + 1ull));
+  STAGE_HIP(c, D.get(&d_S, n_chains + 1ull));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_depth, R.n));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_sub, R.n));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_del, R.n));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_ins, R.n));
+  STAGE_HIP(c, clock.begin(&S.voters_ms));
+  if (n_chains) {
+    const uint32_t mi = static_cast<uint32_t>(prm.min_identity);
+    hipLaunchKernelGGL(k_pl_voter_key, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey);
+    hipLaunchKernelGGL(k_pl_voter_idx, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey, d_vidx);
+    hipLaunchKernelGGL(k_pl_spans, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, d_vidx, d_span, d_rec_depth, d_st);
+  }
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_span, d_S, n_chains + 1ull));
+  hipLaunchKernelGGL(k_pl_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_S + n_chains);
+  STAGE_HIP(c, clock.end());
+  if ((rc = c->sc.read(c)) != MSGPU_OK) return rc;
+  const uint64_t n_cols = c->sc.h[PL_SC_TOTAL];
+  if (n_cols >= (1ull << 40)) {
+    snprintf(c->err, sizeof(c->err), "the voters have %llu columns; the limit is 2^40 - 1", static_cast<kf_ull>(n_cols));
+    return MSGPU_E_ARG;
+  }
+
+  // ---- rules 3 and 4: the counters
+  uint32_t *d_cnt;
+  STAGE_HIP(c, pl_zeroed(D, st, &d_cnt, PL_CLASSES * NB));
+  STAGE_HIP(c, clock.begin(&S.pileup_ms));
+  if (n_cols) hipLaunchKernelGGL(k_pl_pileup, dim3(grid256(n_cols)), dim3(256), 0, st, X, d_S, n_cols, R, Q, d_cnt, d_st);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+
+  // ---- rules 4 and 6: the insertion events
+  uint32_t *d_flag, *d_E;
+  kf_ull   *d_best;
+  STAGE_HIP(c, pl_zeroed(D, st, &d_flag, n_runs + 1ull));
+  STAGE_HIP(c, D.get(&d_E, n_runs + 1ull));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_best, NB));
+  STAGE_HIP(c, clock.begin(&S.insertions_ms));
+  if (n_runs) hipLaunchKernelGGL((k_pl_ins<false>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, R, Q, d_flag, nullptr, nullptr, nullptr, d_st);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_flag, d_E, n_runs + 1ull));
+  hipLaunchKernelGGL(k_pl_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_E + n_runs);
+  STAGE_HIP(c, clock.end());
+  if ((rc = c->sc.read(c)) != MSGPU_OK) return rc;
+  const uint32_t n_ev = static_cast<uint32_t>(c->sc.h[PL_SC_TOTAL]); // <= n_runs < 2^31
+  uint64_t      *d_key = nullptr, *d_seq = nullptr;
+  uint32_t      *d_gstart = nullptr;
+  if (n_ev) {
+    // two buffers each of keys and letters, the heads, their scan and the groups' starts, and the sorts' temporary buffer
+    if ((rc = pl_room(c, n_ev * (4 * 8ull + 3 * 4 + 16) + (8ull << 20), "the insertion events", n_ev, "events", NB, "draft bases")) != MSGPU_OK) return rc;
+    uint64_t *d_key2, *d_seq2;
+    uint32_t *d_head, *d_G;
+    STAGE_HIP(c, D.get(&d_key, n_ev));
+    STAGE_HIP(c, D.get(&d_seq, n_ev));
+    STAGE_HIP(c, D.get(&d_key2, n_ev));
+    STAGE_HIP(c, D.get(&d_seq2, n_ev));
+    STAGE_HIP(c, pl_zeroed(D, st, &d_head, n_ev + 1ull));
+    STAGE_HIP(c, D.get(&d_G, n_ev + 1ull));
+    STAGE_HIP(c, D.get(&d_gstart, n_ev + 1ull));
+    STAGE_HIP(c, clock.begin(&S.insertions_ms));
+    hipLaunchKernelGGL((k_pl_ins<true>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, R, Q, d_flag, d_E, d_key, d_seq, d_st);
+    STAGE_HIP(c, hipGetLastError());
+    // two stable sorts: by the letters, then by (slot, L), whose 44 bits are the store's 38 and L's 6
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_seq, d_seq2, d_key, d_key2, n_ev));
+    STAGE_HIP(c, stage_sort_pairs(D, st, d_key2, d_key, d_seq2, d_seq, n_ev, 44));
+    hipLaunchKernelGGL(k_pl_heads, dim3(grid256(n_ev)), dim3(256), 0, st, d_key, d_seq, n_ev, d_head);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_head, d_G, n_ev + 1ull));
+    hipLaunchKernelGGL(k_pl_gstart, dim3(grid256(n_ev + 1ull)), dim3(256), 0, st, d_head, d_G, n_ev, d_gstart);
+    hipLaunchKernelGGL(k_pl_best, dim3(grid256(n_ev)), dim3(256), 0, st, d_gstart, d_G + n_ev, d_key, d_best);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+  }
+
+  // ---- rules 5 and 6: the calls
+  uint8_t  *d_call;
+  uint32_t *d_outlen;
+  uint64_t *d_O;
+  STAGE_HIP(c, D.get(&d_call, NB));
+  STAGE_HIP(c, pl_zeroed(D, st, &d_outlen, NB + 1ull));
+  STAGE_HIP(c, D.get(&d_O, NB + 1ull));
+  STAGE_HIP(c, clock.begin(&S.call_ms));
+  const PlCall ca{d_cnt, d_best, d_gstart, d_key, d_call, d_outlen, d_rec_sub, d_rec_del, d_rec_ins, static_cast<uint32_t>(prm.min_depth)};
+  if (NB) hipLaunchKernelGGL(k_pl_call, dim3(grid256(NB)), dim3(256), 0, st, R, ca, d_st);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+
+  // ---- rule 7
+  STAGE_HIP(c, clock.begin(&S.output_ms));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_outlen, d_O, NB + 1ull));
+  hipLaunchKernelGGL(k_pl_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_O + NB);
+  STAGE_HIP(c, clock.end());
+  if ((rc = c->sc.read(c)) != MSGPU_OK) return rc;
+  const uint64_t raw_bytes = c->sc.h[PL_SC_TOTAL];
+  uint64_t       text_bound = raw_bytes + raw_bytes / 60 + 2ull * R.n; // the text without its headers
+  if ((rc = pl_room(c, raw_bytes + text_bound + R.n * 16ull + (1ull << 20), "the output", raw_bytes, "polished bases", R.n, "records")) != MSGPU_OK) return rc;
+  uint8_t  *d_raw;
+  uint64_t *d_rec_start, *d_rec_len;
+  STAGE_HIP(c, D.get(&d_raw, raw_bytes + 16));
+  STAGE_HIP(c, D.get(&d_rec_start, R.n));
+  STAGE_HIP(c, D.get(&d_rec_len, R.n));
+  STAGE_HIP(c, clock.begin(&S.output_ms));
+  if (NB) hipLaunchKernelGGL(k_pl_scatter, dim3(grid256(NB)), dim3(256), 0, st, R, d_call, d_best, d_key, d_seq, d_outlen, d_O, d_raw);
+  if (R.n) hipLaunchKernelGGL(k_pl_reclen, dim3(grid256(R.n)), dim3(256), 0, st, R, d_O, d_rec_start, d_rec_len);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+
+  try {
+    for (auto &v : h_rec) v.resize(R.n);
+    res->records.resize(R.n);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  const kf_ull *d_rec[6] = {reinterpret_cast<kf_ull *>(d_rec_start), reinterpret_cast<kf_ull *>(d_rec_len), d_rec_sub, d_rec_del, d_rec_ins, d_rec_depth};
+  STAGE_HIP(c, clock.begin(&S.copy_ms));
+  for (int k = 0; k < 6 && R.n; ++k) STAGE_HIP(c, hipMemcpyAsync(h_rec[k].data(), d_rec[k], R.n * 8ull, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
+
+  std::vector<msgpu_fasta_record> recs;
+  std::string                     hdr;
+  uint64_t                        text = 0;
+  try {
+    for (uint32_t r = 0; r < R.n; ++r) {
+      const uint64_t len_in = msgpu_seq_length(FT.f, r), len_out = h_rec[1][r];
+      if (len_out > 0xffffffffull) {
+        snprintf(c->err, sizeof(c->err), "draft record %u comes out with %llu bases; the limit is 2^32 - 1", r, static_cast<kf_ull>(len_out));
+        return MSGPU_E_ARG;
+      }
+      res->records[r] = msgpu_pl_record{len_in, len_out, h_rec[2][r], h_rec[3][r], h_rec[4][r], len_in ? h_rec[5][r] * 100 / len_in : 0};
+      const size_t h0 = hdr.size();
+      hdr.append(">").append(msgpu_seq_name(FT.f, r)).append("\n");
+      recs.push_back(msgpu_fasta_record{h_rec[0][r], text, static_cast<uint32_t>(len_out), static_cast<uint32_t>(h0), static_cast<uint32_t>(hdr.size() - h0), 0});
+      text += msgpu_fasta_text_bytes(static_cast<uint32_t>(hdr.size() - h0), len_out);
+    }
+    res->text.resize(text);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  if (hdr.size() >= 0xffffffffull) return MSGPU_E_ARG;
+  uint8_t *d_text;
+  STAGE_HIP(c, D.get(&d_text, text + 16));
+  STAGE_HIP(c, clock.begin(&S.format_ms));
+  rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "format: %s", msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, clock.begin(&S.copy_ms));
+  if (text) STAGE_HIP(c, hipMemcpyAsync(&res->text[0], d_text, text, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  clock.collect();
+
+  S.n_voters        = h_st[PL_ST_VOTERS];
+  S.n_ignored       = h_st[PL_ST_IGNORED];
+  S.cols_eq         = h_st[PL_ST_EQ];
+  S.cols_x          = h_st[PL_ST_X];
+  S.cols_d          = h_st[PL_ST_D];
+  S.cols_i          = h_st[PL_ST_I];
+  S.pos_verbatim    = h_st[PL_ST_VERBATIM];
+  S.pos_unchanged   = h_st[PL_ST_UNCHANGED];
+  S.pos_substituted = h_st[PL_ST_SUBST];
+  S.pos_deleted     = h_st[PL_ST_DELETED];
+  S.ins_usable      = h_st[PL_ST_USABLE];
+  S.ins_unusable    = h_st[PL_ST_UNUSABLE];
+  S.ins_at_ends     = h_st[PL_ST_ENDS];
+  S.ins_applied     = h_st[PL_ST_APPLIED];
+  S.bases_inserted  = h_st[PL_ST_INSERTED];
+  S.max_depth       = h_st[PL_ST_MAXDEPTH];
+  S.bytes_out       = text;
+  S.bytes_peak      = D.peak;
+  return MSGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void msgpu_pl_default_params(msgpu_pl_params *p) {
+  if (p) *p = msgpu_pl_params{3, 0};
+}
+
+int  msgpu_pl_create(int device, msgpu_plctx **out) { return stage_create(device, out); }
+void msgpu_pl_destroy(msgpu_plctx *c) { stage_destroy(c); }
+
+const char *msgpu_pl_last_error(const msgpu_plctx *c) { return c ? c->err : "null context"; }
+
+int msgpu_pl_run(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
+                 uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags, msgpu_pl_result **out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out      = nullptr;
+  c->err[0] = 0;
+  if (!params || !draft_path || !reads_path || flags || (n_chains && (!chains || !off)) || (n_chains && off[n_chains] && !ops)) return MSGPU_E_ARG;
+  const msgpu_pl_params p = *params;
+  if (p.min_depth < 1 || p.min_identity < 0 || p.min_identity > 100) {
+    snprintf(c->err, sizeof(c->err), "min_depth = %d (at least 1), min_identity = %d (0..100)", p.min_depth, p.min_identity);
+    return MSGPU_E_ARG;
+  }
+  STAGE_HIP(c, hipSetDevice(c->device));
+  std::unique_ptr<msgpu_pl_result> res;
+  try {
+    res.reset(new msgpu_pl_result());
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  const StageTimer wall;
+  const uint64_t   lost0 = c->sc.lost;
+  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, res.get());
+  if (rc != MSGPU_OK) return rc;
+  res->stats.n_lost_publications = c->sc.lost - lost0;
+  res->stats.wall_ms             = wall.ms();
+  *out                           = res.release();
+  return MSGPU_OK;
+}
+
+int msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->stats;
+  return MSGPU_OK;
+}
+
+int msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **records, uint64_t *n) {
+  if (!r || !records || !n) return MSGPU_E_ARG;
+  *records = r->records.data();
+  *n       = r->records.size();
+  return MSGPU_OK;
+}
+
+const char *msgpu_pl_result_text(const msgpu_pl_result *r, uint64_t *len) {
+  if (len) *len = r ? r->text.size() : 0;
+  return r ? r->text.data() : "";
+}
+
+void msgpu_pl_result_free(msgpu_pl_result *r) {
+  if (r) delete r;
+}
+
+} // extern "C"

@@ -39,9 +39,10 @@ import time
 
 from . import _lib
 
-__all__ = ["HybridError", "MIN_LENGTH", "output_names", "link_input", "run", "main"]
+__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "output_names", "link_input", "run", "main"]
 
 MIN_LENGTH = 500  # pipeline.sh:29
+POLISHED_NAME = "04.assembly.polished.fa"  # written only by run(..., polish=N): not one of output_names
 
 
 class HybridError(RuntimeError):
@@ -83,13 +84,15 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None):
+        bubble=None, polish=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
     ``cg:Z:`` strings (muchsalsa_amd.mapper's rule 10), as pipeline.sh:175's ``-c --eqx`` asks for; every file written before
     that PAF is the same.  ``bubble`` (None or 0: off) is the unitig assembly's rule 9 parameter (muchsalsa_amd.unitigs): bubbles
-    with branches of up to that many k-mers are popped before the unitigs are written."""
+    with branches of up to that many k-mers are popped before the unitigs are written.  ``polish`` (None or 0: off) = N >= 1 adds a
+    last stage ``"polish"``: N rounds of muchsalsa_amd.polish of the assembly by the scrubbed reads into POLISHED_NAME, named by
+    ``files["polished"]``; every other file is the same."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -137,6 +140,11 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
           threads=int(cores), device=device)
     shutil.copyfile(files["target"], files["assembly"])  # pipeline.sh:181
     result["files"] = dict(files, link=reads)
+    if polish:
+        from . import polish as polisher
+        result["files"]["polished"] = os.path.join(out, POLISHED_NAME)
+        stage("polish", polisher.run, files["assembly"], files["scrubbed"], result["files"]["polished"], rounds=int(polish),
+              device=device)
     result["seconds"] = round(time.perf_counter() - t_all, 4)
     return result
 
