@@ -279,7 +279,7 @@ struct msgpu_ctx : msgpu::StageCtx {
   DevBuf rows_in, rows_pk, cnt_read, read_off, cursor, bkt_key, bkt_dead, by_read, read_cnt, alive_rank,
       anchor_cnt, anchor_off, anchor_first, anchor_off_gen, bkt2_idx, bkt2_line, by_anchor, read_len, read_first,
       scan_tmp, vis16, spos2, visits, bin_cursor, bin_start;
-  DevBuf bound, cand_off, cand_j, cand_t, scr_v2, scr_start, n_cand, n_edge, lists, edges, edge_cand;
+  DevBuf bound, cand_off, cand_j, cand_q, scr_v2, scr_start, n_cand, n_edge, lists, edges, edge_cand;
   DevBuf big_key, big_t, big_r2s, big_pfx, pair_tab, chain_chunks, big_off, cand_sums, bucket_visits;
   EventHold ev_side[2], ev_side2;
   uint64_t    n_big_edges = 0, n_big_ems = 0;
@@ -501,7 +501,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   STAGE_HIP(c, c->anchor_off.ensure((size_t(A) + 2) * 4));
   STAGE_HIP(c, c->bkt2_idx.ensure(nz * 4));
   STAGE_HIP(c, c->bkt2_line.ensure(nz * 4));
-  STAGE_HIP(c, c->by_anchor.ensure(nz * sizeof(IRow)));
+  STAGE_HIP(c, c->by_anchor.ensure(nz * sizeof(SRow)));
   STAGE_HIP(c, c->vis16.ensure(nz * 16));
   STAGE_HIP(c, c->spos2.ensure((bshift ? 1 : cap ? size_t(V) * cap : nz) * 8)); // one-pass build: by bucket slot, else by source row (bin path: inside the record)
   STAGE_HIP(c, c->visits.ensure((size_t(V) + 1) * 4));
@@ -572,7 +572,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
       launch_index_bin(st, c->d_rows, n, V, A, d_flags, scalar<uint32_t>(c, SC_ERR), c->anchor_first.as<uint32_t>(), cur,
                        c->bkt_key.as<uint4>(), rd_lo, nb_p, bcap, tail);
       launch_index_sort_bin(st, cur, c->bin_start.as<uint32_t>(), V, rd_lo, nb_p, bcap, c->bkt_key.as<uint4>(),
-                            c->by_read.as<IRow>(), c->by_anchor.as<IRow>(), c->vis16.as<uint4>(), c->read_off.as<uint32_t>(),
+                            c->by_read.as<IRow>(), c->by_anchor.as<SRow>(), c->vis16.as<uint4>(), c->read_off.as<uint32_t>(),
                             c->read_cnt.as<uint32_t>(), c->read_len.as<int32_t>(), c->read_first.as<uint32_t>(),
                             c->visits.as<uint32_t>(), c->d_rows, d_flags, scalar<uint32_t>(c, SC_ERR), c->bucket_visits.as<uint32_t>());
     }
@@ -585,7 +585,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   launch_sort_read(st, c->read_off.as<uint32_t>(), c->cnt_read.as<uint32_t>(), V, c->bkt_key.as<IRow>(),
                    c->by_read.as<IRow>(), c->read_cnt.as<uint32_t>(),
                    c->alive_rank.as<uint32_t>(), c->anchor_cnt.as<uint32_t>(), c->bkt_dead.as<uint8_t>(), d_flags,
-                   c->by_anchor.as<IRow>(), cap, c->d_rows, c->read_len.as<int32_t>(), c->read_first.as<uint32_t>(),
+                   c->by_anchor.as<SRow>(), cap, c->d_rows, c->read_len.as<int32_t>(), c->read_first.as<uint32_t>(),
                    scalar<uint32_t>(c, SC_ERR), c->spos2.as<uint2>(), c->vis16.as<uint4>(), c->visits.as<uint32_t>()); // fast mode: the sort writes the scaffold rows too (at
                                                                               // the places pass 1 left in spos2); always: the Vertex facts
   }
@@ -708,7 +708,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
     launch_scatter_anchor(st, c->d_rows, n, c->alive_rank.as<uint32_t>(), c->anchor_off.as<uint32_t>(),
                           c->cursor.as<uint32_t>(), c->bkt2_idx.as<uint32_t>(), c->bkt2_line.as<uint32_t>(), d_flags);
     launch_rank_anchor(st, c->anchor_off.as<uint32_t>(), n, scalar<uint32_t>(c, SC_NALIVE), c->bkt2_idx.as<uint32_t>(),
-                       c->bkt2_line.as<uint32_t>(), c->d_rows, c->alive_rank.as<uint32_t>(), c->by_anchor.as<IRow>(),
+                       c->bkt2_line.as<uint32_t>(), c->d_rows, c->alive_rank.as<uint32_t>(), c->by_anchor.as<SRow>(),
                        d_flags, c->read_off.as<uint32_t>(), c->by_read.as<IRow>(), c->vis16.as<uint4>());
     STAGE_HIP(c, hipGetLastError());
     if (int rc = read_scalars(c, c->ev[1])) return rc;
@@ -990,7 +990,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
 
   const size_t tb = total_bound ? total_bound : 1;
   STAGE_HIP(c, c->cand_j.ensure(tb * 4));
-  STAGE_HIP(c, c->cand_t.ensure(tb * 4));
+  STAGE_HIP(c, c->cand_q.ensure(tb * 4));
   STAGE_HIP(c, c->scr_v2.ensure(tb * 4));
   STAGE_HIP(c, c->scr_start.ensure(tb * 4));
 
@@ -999,11 +999,11 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   a.read_cnt       = c->read_cnt.as<uint32_t>();
   a.anchor_off     = c->anchor_off.as<uint32_t>();
   a.by_read        = c->by_read.as<IRow>();
-  a.by_anchor      = c->by_anchor.as<IRow>();
+  a.by_anchor      = c->by_anchor.as<SRow>();
   a.vis            = c->vis16.as<uint4>();
   a.cand_off       = c->cand_off.as<uint64_t>();
   a.cand_j         = c->cand_j.as<uint32_t>();
-  a.cand_t         = c->cand_t.as<uint32_t>();
+  a.cand_q         = c->cand_q.as<uint32_t>();
   a.edge_scr_v2    = c->scr_v2.as<uint32_t>();
   a.edge_scr_start = c->scr_start.as<uint32_t>();
   a.n_cand         = c->n_cand.as<uint32_t>();
@@ -1154,12 +1154,11 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   a.edge_cand    = c->edge_cand.as<uint64_t>();
   a.n_edges      = E;
   a.cand_j       = c->cand_j.as<uint32_t>();
-  a.cand_t       = c->cand_t.as<uint32_t>();
+  a.cand_q       = c->cand_q.as<uint32_t>();
   a.read_off     = c->read_off.as<uint32_t>();
   a.read_cnt     = c->read_cnt.as<uint32_t>();
   a.read_len     = c->read_len.as<int32_t>();
   a.by_read      = c->by_read.as<IRow>();
-  a.by_anchor    = c->by_anchor.as<IRow>();
   a.ems          = c->ems.as<msgpu_edgematch>();
   a.order_scr    = c->order_scr.as<msgpu_order>();
   a.ids_scr      = c->ids_scr.as<uint32_t>();

@@ -1,4 +1,4 @@
-// msgpu_device.h -- device-side helpers shared by the kernel files (msgpu_kernels.hip, msgpu_index.hip): 32-byte row
+// msgpu_device.h -- device-side helpers shared by the kernel files (msgpu_kernels.hip, msgpu_index.hip): 32-byte and 16-byte row
 // loads / stores, readlane of wide types, wavefront and workgroup scans.  gfx950, wave64.
 #ifndef MSGPU_DEVICE_H
 #define MSGPU_DEVICE_H
@@ -42,6 +42,38 @@ __device__ __forceinline__ IRow make_irow(const msgpu_row &row, uint32_t other, 
   out.line  = row.line;
   out.other = other;
   out.pf    = ((row.flags & MSGPU_ROW_DIR) ? PF_DIR : 0u) | ((row.flags & MSGPU_ROW_PRIMARY) ? PF_PRIM : 0u) |
+           (rank & PF_POS_MASK);
+  return out;
+}
+
+// the 16-byte scaffold row: one vector load, one vector store
+__device__ __forceinline__ SRow load_srow(const SRow *p) {
+  const uint4 a = *reinterpret_cast<const uint4 *>(p);
+  SRow        r;
+  r.i_lo = static_cast<int>(a.x);
+  r.i_hi = static_cast<int>(a.y);
+  r.read = a.z;
+  r.pf   = a.w;
+  return r;
+}
+__device__ __forceinline__ void store_srow(SRow *p, const SRow &r) {
+  *reinterpret_cast<uint4 *>(p) = make_uint4(static_cast<uint32_t>(r.i_lo), static_cast<uint32_t>(r.i_hi), r.read, r.pf);
+}
+// the scaffold row of a by_read row: same interval and flags, the read in place of the anchor, the rank in the read attached
+__device__ __forceinline__ SRow make_srow(const IRow &row, uint32_t read, uint32_t rank) {
+  SRow out;
+  out.i_lo = row.i_lo;
+  out.i_hi = row.i_hi;
+  out.read = read;
+  out.pf   = (row.pf & ~PF_POS_MASK) | (rank & PF_POS_MASK);
+  return out;
+}
+__device__ __forceinline__ SRow make_srow(const msgpu_row &row, uint32_t read, uint32_t rank) {
+  SRow out;
+  out.i_lo = row.i_lo;
+  out.i_hi = row.i_hi;
+  out.read = read;
+  out.pf   = ((row.flags & MSGPU_ROW_DIR) ? PF_DIR : 0u) | ((row.flags & MSGPU_ROW_PRIMARY) ? PF_PRIM : 0u) |
            (rank & PF_POS_MASK);
   return out;
 }

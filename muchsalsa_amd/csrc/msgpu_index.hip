@@ -11,8 +11,9 @@
 // LDS -- read once, coalesced -- grouped by read, then ranks every read's rows in registers as k_sort_read does (rank by
 // (nanoporeRange, anchor): mpp.cpp:164-172 / :259-267).  read_off comes from a scan of the bucket counts, not from per-read
 // counters.  What is left per row is what the tables themselves cost: one scattered whole-sector store into the bucket, one
-// scattered 32-byte store into by_anchor (a scattered store of <= 16 bytes costs 60 us per 5 M rows, of 32 bytes 80 us: a
-// read-modify-write of a sector, whatever the lanes do -- same micro-benchmark).
+// scattered 16-byte store into by_anchor (a scattered store of <= 16 bytes costs 60 us per 5 M rows, of 32 bytes 80 us: a
+// read-modify-write of a sector, whatever the lanes do -- same micro-benchmark; the scaffold row was 32 bytes until the
+// chain kernels took v2's row from by_read).
 //
 // Same tables as the atomic path, bit for bit (the sort keys are unique; the arrival order inside a bucket is no input of
 // anything).  What the path does not cover -- rows not grouped by anchor, a duplicate (read, anchor) pair (MatchMap.cpp:64-80:
@@ -352,7 +353,7 @@ __device__ __forceinline__ void bitonic_sort64(uint32_t &khi, uint32_t &klo, uin
 
 template <int K>
 __device__ __forceinline__ bool sort_bin_read(uint32_t r, uint32_t n, uint32_t b /*first by_read row*/, uint32_t off /*first LDS row*/,
-                                              int lane, const BinLds &s, IRow *by_read, IRow *by_anchor, uint4 *vis,
+                                              int lane, const BinLds &s, IRow *by_read, SRow *by_anchor, uint4 *vis,
                                               unsigned long long *first_key /*LDS*/, uint32_t *read_cnt, uint32_t *visits) {
   IRow     row[K];
   uint32_t pk[K], man[K], less[K];
@@ -436,10 +437,7 @@ __device__ __forceinline__ bool sort_bin_read(uint32_t r, uint32_t n, uint32_t b
     if (static_cast<uint32_t>(k) * 64 + lane < n) {
       const uint32_t idx = row[k].pf & PF_POS_MASK; // source row
       const uint32_t sp  = idx + (pk[k] & ((1u << BIN_PACK_BEHIND_SHIFT) - 1)) - BIN_HALO, bh = pk[k] >> BIN_PACK_BEHIND_SHIFT;
-      IRow           w   = row[k];
-      w.other            = r;
-      w.pf               = (row[k].pf & ~PF_POS_MASK) | less[k]; // scaffold rows carry the rank inside their read
-      store_irow(&by_anchor[sp], w);
+      store_srow(&by_anchor[sp], make_srow(row[k], r, less[k])); // scaffold rows carry the rank inside their read
       row[k].pf = (row[k].pf & ~PF_POS_MASK) | sp; // by_read rows carry their place in the scaffold
       vis[b + less[k]] = make_uint4(static_cast<uint32_t>(row[k].i_lo), static_cast<uint32_t>(row[k].i_hi), sp + 1, bh);
       store_irow(&by_read[b + less[k]], row[k]);
@@ -456,7 +454,7 @@ __device__ __forceinline__ bool sort_bin_read(uint32_t r, uint32_t n, uint32_t b
 
 __global__ __launch_bounds__(BIN_SORT_NT) void k_index_sort_bin(uint32_t *cursor, const uint32_t *bin_start, uint32_t V,
                                                                 uint32_t rd_lo, uint32_t cap, const uint4 *bin_rec, IRow *by_read,
-                                                                IRow *by_anchor, uint4 *vis, uint32_t *read_off, uint32_t *read_cnt,
+                                                                SRow *by_anchor, uint4 *vis, uint32_t *read_off, uint32_t *read_cnt,
                                                                 int32_t *read_len, uint32_t *read_first, uint32_t *visits,
                                                                 const msgpu_row *rows, uint32_t *flags, uint32_t *err,
                                                                 uint32_t *bucket_visits /*[all buckets of the job]*/) {
@@ -611,7 +609,7 @@ void launch_index_bin(hipStream_t st, const msgpu_row *rows, uint64_t n, uint32_
                      flags, err, anchor_first, cursor, bin_rec, rd_lo, nb, cap, tail);
 }
 void launch_index_sort_bin(hipStream_t st, uint32_t *cursor, const uint32_t *bin_start, uint32_t V, uint32_t rd_lo, uint32_t nb,
-                           uint32_t cap, const uint4 *bin_rec, IRow *by_read, IRow *by_anchor, uint4 *vis, uint32_t *read_off,
+                           uint32_t cap, const uint4 *bin_rec, IRow *by_read, SRow *by_anchor, uint4 *vis, uint32_t *read_off,
                            uint32_t *read_cnt, int32_t *read_len, uint32_t *read_first, uint32_t *visits, const msgpu_row *rows,
                            uint32_t *flags, uint32_t *err, uint32_t *bucket_visits) {
   if (!nb) return;

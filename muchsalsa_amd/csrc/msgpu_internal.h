@@ -11,14 +11,22 @@
 
 namespace msgpu {
 
-// 32-byte row of the two device tables (two 16-byte vector loads per row).
-//   by_read  : rows of one read sorted by (n_lo, n_hi, anchor) -- `other` = anchor id, pf = flags | its place in by_anchor
-//   by_anchor: rows of one anchor (scaffold) sorted by read id -- `other` = read id,   pf = flags | rank in its read
+// 32-byte row of by_read (two 16-byte vector loads per row): the rows of one read sorted by (n_lo, n_hi, anchor) --
+// `other` = anchor id, pf = flags | its place in by_anchor.  The only full copy of a row on the device: the chain kernels take
+// both rows of an EdgeMatch from it.
 struct IRow {
   int32_t  n_lo, n_hi, i_lo, i_hi;
   uint32_t score, line, other, pf;
 };
 static_assert(sizeof(IRow) == 32, "IRow must be 32 bytes");
+// 16-byte row of by_anchor (one 16-byte vector load or store per row): the rows of one anchor (scaffold) sorted by read id --
+// what the candidate walk needs of a row: the anchor interval, the read and pf = flags | rank in its read = the row's index in
+// that read's by_read segment (among the rows that survive the duplicate rule), where everything else about it lies.
+struct SRow {
+  int32_t  i_lo, i_hi;
+  uint32_t read, pf;
+};
+static_assert(sizeof(SRow) == 16, "SRow must be 16 bytes");
 constexpr uint32_t PF_POS_MASK = 0x3fffffffu;
 constexpr uint32_t PF_DIR      = 1u << 30;
 constexpr uint32_t PF_PRIM     = 1u << 31;
@@ -46,11 +54,12 @@ static_assert(sizeof(CandDesc) == 32, "CandDesc must be 32 bytes");
 
 struct CandArgs {
   const uint32_t *read_off, *read_cnt, *anchor_off;
-  const IRow     *by_read, *by_anchor;
+  const IRow     *by_read;
+  const SRow     *by_anchor;
   const uint4    *vis;  // per by_read row:   {i_lo, i_hi, first scaffold row behind it, rows behind it}
   const uint64_t *cand_off;     // per read: first slot of its candidate / edge scratch (exclusive scan of bound)
   uint32_t       *cand_j;       // sorted candidates: rank of the anchor in v1's row list
-  uint32_t       *cand_t;       // sorted candidates: row of v2 in by_anchor
+  uint32_t       *cand_q;       // sorted candidates: rank of the anchor in v2's row list (the scaffold row carries it)
   uint32_t       *edge_scr_v2;  // per-read edge scratch: v2
   uint32_t       *edge_scr_start; // per-read edge scratch: first candidate of the edge
   uint32_t       *n_cand, *n_edge; // per read
@@ -92,10 +101,10 @@ struct ChainArgs {
   msgpu_edge      *edges;
   const uint64_t  *edge_cand;
   uint64_t         n_edges;
-  const uint32_t  *cand_j, *cand_t;
+  const uint32_t  *cand_j, *cand_q; // per EdgeMatch: its row in v1's and in v2's segment of by_read
   const uint32_t  *read_off, *read_cnt;
   const int32_t   *read_len;
-  const IRow      *by_read, *by_anchor;
+  const IRow      *by_read;
   msgpu_edgematch *ems;
   msgpu_order     *order_scr; // slot em_off + i for the i-th order of an edge
   uint32_t        *ids_scr;   // slots em_off .. em_off + em_cnt of an edge
@@ -235,7 +244,7 @@ void launch_index_bin(hipStream_t st, const msgpu_row *rows, uint64_t n, uint32_
                       uint32_t *anchor_first, uint32_t *cursor, uint4 *bin_rec, uint32_t rd_lo, uint32_t nb, uint32_t cap,
                       const BinTail &tail);
 void launch_index_sort_bin(hipStream_t st, uint32_t *cursor, const uint32_t *bin_start, uint32_t V, uint32_t rd_lo, uint32_t nb,
-                           uint32_t cap, const uint4 *bin_rec, IRow *by_read, IRow *by_anchor, uint4 *vis, uint32_t *read_off,
+                           uint32_t cap, const uint4 *bin_rec, IRow *by_read, SRow *by_anchor, uint4 *vis, uint32_t *read_off,
                            uint32_t *read_cnt, int32_t *read_len, uint32_t *read_first, uint32_t *visits, const msgpu_row *rows,
                            uint32_t *flags, uint32_t *err, uint32_t *bucket_visits);
 void launch_publish_scalars(hipStream_t st, const uint64_t *src, const HostPublish &p);
@@ -249,7 +258,7 @@ void launch_scatter_read(hipStream_t st, const msgpu_row *rows, uint64_t n, cons
                          IRow *bkt_row);
 void launch_sort_read(hipStream_t st, const uint32_t *read_off, const uint32_t *cnt_read, uint32_t V, const IRow *bkt_row,
                       IRow *by_read, uint32_t *read_cnt, uint32_t *alive_rank,
-                      uint32_t *anchor_cnt, uint8_t *bkt_dead, uint32_t *flags, IRow *by_anchor, uint32_t cap,
+                      uint32_t *anchor_cnt, uint8_t *bkt_dead, uint32_t *flags, SRow *by_anchor, uint32_t cap,
                       const msgpu_row *rows, int32_t *read_len, uint32_t *read_first, uint32_t *err,
                       const uint2 *spos, uint4 *vis, uint32_t *visits);
 void launch_index_finish(hipStream_t st, const uint32_t *read_first, uint32_t V, uint32_t *err, const uint32_t *flags,
@@ -262,7 +271,7 @@ void launch_scatter_anchor(hipStream_t st, const msgpu_row *rows, uint64_t n, co
                            const uint32_t *flags);
 void launch_rank_anchor(hipStream_t st, const uint32_t *anchor_off, uint64_t n_rows, const uint32_t *d_n_alive,
                         const uint32_t *bkt_idx, const uint32_t *bkt_line, const msgpu_row *rows,
-                        const uint32_t *alive_rank, IRow *by_anchor, const uint32_t *flags, const uint32_t *read_off,
+                        const uint32_t *alive_rank, SRow *by_anchor, const uint32_t *flags, const uint32_t *read_off,
                         IRow *by_read, uint4 *vis);
 void launch_bound(hipStream_t st, const uint32_t *read_off, const uint32_t *read_cnt, const uint4 *vis, uint32_t V,
                   uint32_t shard, uint32_t nshards, uint32_t lo, uint32_t hi, uint32_t *bound);

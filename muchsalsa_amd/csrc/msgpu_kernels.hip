@@ -360,7 +360,7 @@ template <int K>
 __device__ __forceinline__ bool sort_read_in_registers(uint32_t r, uint64_t bs, uint32_t b, uint32_t n, int lane, bool fast,
                                                        const IRow *bkt_row, IRow *by_read,
                                                        uint32_t *read_cnt, uint32_t *alive_rank, uint32_t *anchor_cnt,
-                                                       IRow *by_anchor, const msgpu_row *rows, int32_t *read_len,
+                                                       SRow *by_anchor, const msgpu_row *rows, int32_t *read_len,
                                                        uint32_t *read_first, const uint2 *spos, uint4 *vis,
                                                        uint32_t *visits, bool by_slot) {
   IRow     row[K];
@@ -408,11 +408,9 @@ __device__ __forceinline__ bool sort_read_in_registers(uint32_t r, uint64_t bs, 
     if (static_cast<uint32_t>(k) * 64 + lane < n) {
       row[k].pf = (row[k].pf & ~PF_POS_MASK) | less[k];
       if (fast) {
-        IRow           w  = row[k];
         const uint2    sc = spos[by_slot ? bs + static_cast<uint32_t>(k) * 64 + lane : idx[k]];
         const uint32_t sp = sc.x;
-        w.other           = r;
-        store_irow(&by_anchor[sp], w);
+        store_srow(&by_anchor[sp], make_srow(row[k], r, less[k]));
         row[k].pf = (row[k].pf & ~PF_POS_MASK) | sp; // by_read rows carry their place in the scaffold
         vis[b + less[k]] = make_uint4(static_cast<uint32_t>(row[k].i_lo), static_cast<uint32_t>(row[k].i_hi), sp + 1, sc.y);
         behind += sc.y;
@@ -440,7 +438,7 @@ __device__ __forceinline__ bool sort_read_in_registers(uint32_t r, uint64_t bs, 
 __global__ __launch_bounds__(256) void k_sort_read(const uint32_t *read_off, const uint32_t *cnt_read, uint32_t V,
                                                    const IRow *bkt_row, IRow *by_read,
                                                    uint32_t *read_cnt, uint32_t *alive_rank, uint32_t *anchor_cnt,
-                                                   uint8_t *bkt_dead, uint32_t *flags, IRow *by_anchor, uint32_t cap,
+                                                   uint8_t *bkt_dead, uint32_t *flags, SRow *by_anchor, uint32_t cap,
                                                    const msgpu_row *rows, int32_t *read_len, uint32_t *read_first,
                                                    uint32_t *err, const uint2 *spos, uint4 *vis, uint32_t *visits) {
   const int      lane = threadIdx.x & 63;
@@ -509,14 +507,12 @@ __global__ __launch_bounds__(256) void k_sort_read(const uint32_t *read_off, con
       row.pf = (row.pf & ~PF_POS_MASK) | less;
       if (fast) {
         // input already grouped by anchor with ascending lines: the scaffold's rows are the input's, so this row's
-        // by_anchor entry (same 32 bytes, `other` = the read, rank in the read attached) goes straight to the place
+        // by_anchor entry (anchor interval, the read, flags | rank in the read: 16 bytes) goes straight to the place
         // pass 1 worked out for it (scaffolds in read-id order).  A duplicate (read, anchor) pair found anywhere voids
         // the fast table: the host rebuilds generically.
-        IRow           w  = row;
         const uint2    sc = spos[cap ? bs + lane : idx];
         const uint32_t sp = sc.x;
-        w.other           = r;
-        store_irow(&by_anchor[sp], w);
+        store_srow(&by_anchor[sp], make_srow(row, r, less));
         row.pf = (row.pf & ~PF_POS_MASK) | sp; // by_read rows carry their place in the scaffold
         // what the candidate scan reads of this row: anchor interval + the stretch of the scaffold behind it (the
         // partners with a higher read id)
@@ -582,11 +578,9 @@ __global__ __launch_bounds__(256) void k_sort_read(const uint32_t *read_off, con
       }
       k.pf = (k.pf & ~PF_POS_MASK) | less;
       if (fast) {
-        IRow           w  = k;
         const uint2    sc = spos[cap ? bs + e : kix];
         const uint32_t sp = sc.x;
-        w.other           = r;
-        store_irow(&by_anchor[sp], w);
+        store_srow(&by_anchor[sp], make_srow(k, r, less));
         k.pf = (k.pf & ~PF_POS_MASK) | sp;
         vis[b + less] = make_uint4(static_cast<uint32_t>(k.i_lo), static_cast<uint32_t>(k.i_hi), sp + 1, sc.y);
         n_behind += sc.y;
@@ -651,7 +645,7 @@ __global__ __launch_bounds__(256) void k_scatter_anchor(const msgpu_row *rows, u
 // by_read copy of the row learns its place in the scaffold.
 __global__ __launch_bounds__(256) void k_rank_anchor(const uint32_t *anchor_off, const uint32_t *d_n_alive, const uint32_t *bkt_idx,
                                                      const uint32_t *bkt_key, const msgpu_row *rows,
-                                                     const uint32_t *alive_rank, IRow *by_anchor, const uint32_t *flags,
+                                                     const uint32_t *alive_rank, SRow *by_anchor, const uint32_t *flags,
                                                      const uint32_t *read_off, IRow *by_read, uint4 *vis) {
   if ((*flags & ~IXF_DUPS) == 0) return;
   uint64_t p = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -662,7 +656,7 @@ __global__ __launch_bounds__(256) void k_rank_anchor(const uint32_t *anchor_off,
   uint32_t  rank = 0;
   for (uint32_t q = b; q < e; ++q) rank += bkt_key[q] < row.read_id ? 1u : 0u;
   const uint32_t ar = alive_rank[idx], sp = b + rank;
-  store_irow(&by_anchor[sp], make_irow(row, row.read_id, ar));
+  store_srow(&by_anchor[sp], make_srow(row, row.read_id, ar));
   const uint32_t at = read_off[row.read_id] + ar;
   uint32_t      *pf = &by_read[at].pf;
   *pf               = (*pf & ~PF_POS_MASK) | sp;
@@ -717,7 +711,7 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
   uint16_t *const g_rank = reinterpret_cast<uint16_t *>(s_regA); // HSZ entries
   uint16_t *const g_slot = reinterpret_cast<uint16_t *>(s_regB);
   uint16_t *const g_off  = g_slot + CMAX; // CMAX + 1 entries
-  __shared__ uint32_t s_t[CMAX];                // by_anchor row of candidate slot c, later (staging) of position pos
+  __shared__ uint32_t s_t[CMAX];                // by_anchor row of visit c, later (staging) v2's rank of position pos
   __shared__ uint16_t s_j[CMAX], s_g[CMAX];     // row j of candidate slot c, later of staging position pos; group of pos
   __shared__ uint32_t h_key[HSZ], h_cnt[HSZ];   // open-addressing table v2 -> group; members per group
   __shared__ uint32_t s_bm[HSZ];                // per group (in v2 order): bitmap of the rows j it holds, R1MAX bits
@@ -796,14 +790,14 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
     if (c < nc) {
       const uint32_t j  = s_j[c];
       const uint32_t vm = s_t[c];
-      const IRow     o  = load_irow(&a.by_anchor[vm]);
+      const SRow     o  = load_srow(&a.by_anchor[vm]);
       const uint4    rw = s_row[j]; // the anchor interval on v1's side: needed only once the scaffold row is here
       const int      ovlo = max(o.i_lo, static_cast<int>(rw.x)), ovhi = min(o.i_hi, static_cast<int>(rw.y));
       // overlap test (MatchMap.cpp:192); the owner rule (v2 > v1 <=> v1 has the lower first line, :204-213) is the
       // choice of the rows visited: scaffolds are in read-id order and the walk starts behind v1's own row
       c_ok[q] = ovlo <= ovhi && (ovhi - ovlo) > static_cast<int>(a.th_overlap);
-      c_v2[q] = o.other;
-      c_t[q]  = vm;
+      c_v2[q] = o.read;
+      c_t[q]  = o.pf & PF_POS_MASK; // the row's rank in v2 = its place in v2's by_read segment: what the chain kernels load
       c_j[q]  = static_cast<uint16_t>(j);
     }
   }
@@ -897,7 +891,7 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
         for (uint32_t w = 0; w < jw; ++w) rr += static_cast<uint32_t>(__popc(g[w]));
         const uint64_t dst = co + g_off[c_rk[q]] + rr;
         a.cand_j[dst]      = c_j[q];
-        a.cand_t[dst]      = c_t[q];
+        a.cand_q[dst]      = c_t[q];
       }
     }
   } else { // more groups than bitmaps fit: stage by group, rank by comparison
@@ -918,7 +912,7 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
       uint32_t       rr = 0;
       for (uint32_t q = gs; q < ge; ++q) rr += (s_j[q] < mj) ? 1u : 0u;
       a.cand_j[co + gs + rr] = mj;
-      a.cand_t[co + gs + rr] = s_t[pos];
+      a.cand_q[co + gs + rr] = s_t[pos];
     }
   }
   // (d) one edge per group (edges with more than 64 EdgeMatches are counted: they take k_chain_big)
@@ -1191,8 +1185,9 @@ __global__ __launch_bounds__(256) void k_candidates_big(CandArgs a, const uint32
       j        = lo;
       IRow me  = load_irow(&a.by_read[rb + j]);
       vm       = (me.pf & PF_POS_MASK) + 1 + (x - pfx[j]);
-      IRow o   = load_irow(&a.by_anchor[vm]);
-      r2       = o.other;
+      SRow o   = load_srow(&a.by_anchor[vm]);
+      r2       = o.read;
+      vm       = o.pf & PF_POS_MASK; // from here on the row's rank in v2 (its place in v2's by_read segment)
       int ovlo = max(o.i_lo, me.i_lo), ovhi = min(o.i_hi, me.i_hi);
       pass     = ovlo <= ovhi && (ovhi - ovlo) > static_cast<int>(a.th_overlap);
     }
@@ -1219,7 +1214,7 @@ __global__ __launch_bounds__(256) void k_candidates_big(CandArgs a, const uint32
     for (uint32_t q = 0; q < nc; ++q) rank += (big_key[bo + q] < k) ? 1u : 0u;
     big_r2s[bo + rank]  = static_cast<uint32_t>(k >> 32);
     a.cand_j[co + rank] = static_cast<uint32_t>(k);
-    a.cand_t[co + rank] = big_t[bo + c];
+    a.cand_q[co + rank] = big_t[bo + c];
   }
   __threadfence_block();
   __syncthreads();
@@ -1760,12 +1755,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   bool     em_dir = false, em_prim = false;
   ChainElem x{};
   if (act) {
-    j1               = a.cand_j[cp + lane];
-    const uint32_t t = a.cand_t[cp + lane];
+    j1            = a.cand_j[cp + lane];
+    q2            = a.cand_q[cp + lane];
+    // both rows from by_read: v2's rows of one edge lie packed in v2's segment (the candidate kernel handed their ranks on)
     const IRow m1 = load_irow(&a.by_read[a.read_off[v1] + j1]);
-    const IRow m2 = load_irow(&a.by_anchor[t]);
+    const IRow m2 = load_irow(&a.by_read[a.read_off[v2] + q2]);
     anchor        = m1.other;
-    q2            = m2.pf & PF_POS_MASK;
     // EdgeMatch, MatchMap.cpp:188-202,218.  outer = the row with the higher line number.
     const int  ov_lo = max(m1.i_lo, m2.i_lo), ov_hi = min(m1.i_hi, m2.i_hi);
     const bool d1 = (m1.pf & PF_DIR) != 0, d2 = (m2.pf & PF_DIR) != 0;
@@ -2401,12 +2396,11 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   ChainElem x{};
   cm[lane] = 0;
   if (act) {
-    j1               = a.cand_j[cp + sl];
-    const uint32_t t = a.cand_t[cp + sl];
+    j1            = a.cand_j[cp + sl];
+    const uint32_t qt = a.cand_q[cp + sl];
     const IRow m1 = load_irow(&a.by_read[a.read_off[v1] + j1]);
-    const IRow m2 = load_irow(&a.by_anchor[t]);
+    const IRow m2 = load_irow(&a.by_read[a.read_off[v2] + qt]);
     anchor        = m1.other;
-    q2            = m2.pf & PF_POS_MASK;
     const int  ov_lo = max(m1.i_lo, m2.i_lo), ov_hi = min(m1.i_hi, m2.i_hi);
     const bool d1 = (m1.pf & PF_DIR) != 0, d2 = (m2.pf & PF_DIR) != 0;
     em_dir           = d1 == d2;
@@ -2458,6 +2452,9 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
     clo1     = x.clo1;
     clo2     = x.clo2;
     el[lane] = x;
+    // v2's rank for the path code far below, fetched a second time (the line has just been read) rather than kept beside the
+    // row's eight words through the set-up: with it live from the first load the body does not fit seven wavefronts' registers
+    q2       = *static_cast<const volatile uint32_t *>(&a.cand_q[cp + sl]);
   }
   // the four numbers the overhangs at the very end are made of wait in LDS, not in eight registers across the sweep and the DP
   // (the element table itself is overwritten by the path lists before then)
@@ -2943,9 +2940,9 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainArgs a, const uint32_t *b
 
   // elements + EdgeMatch table
   for (uint32_t i = lane; i < n; i += 64) {
-    const uint32_t j1 = a.cand_j[cp + i], t = a.cand_t[cp + i];
+    const uint32_t j1 = a.cand_j[cp + i], q2 = a.cand_q[cp + i];
     const IRow     m1 = load_irow(&a.by_read[a.read_off[v1] + j1]);
-    const IRow     m2 = load_irow(&a.by_anchor[t]);
+    const IRow     m2 = load_irow(&a.by_read[a.read_off[v2] + q2]);
     const int      ov_lo = max(m1.i_lo, m2.i_lo), ov_hi = min(m1.i_hi, m2.i_hi);
     const bool     d1 = (m1.pf & PF_DIR) != 0, d2 = (m2.pf & PF_DIR) != 0;
     const bool     em_dir = d1 == d2, em_prim = (m1.pf & PF_PRIM) && (m2.pf & PF_PRIM);
@@ -2960,7 +2957,7 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainArgs a, const uint32_t *b
     x.score  = os + is_;
     x.anchor = m1.other;
     x.j1     = j1;
-    x.q2     = m2.pf & PF_POS_MASK;
+    x.q2     = q2;
     x.flags  = (em_dir ? 1u : 0u) | (em_prim ? 2u : 0u);
     msgpu_edgematch em;
     em.ov_lo     = ov_lo;
@@ -3733,7 +3730,7 @@ void launch_scatter_read(hipStream_t st, const msgpu_row *rows, uint64_t n, cons
 }
 void launch_sort_read(hipStream_t st, const uint32_t *read_off, const uint32_t *cnt_read, uint32_t V, const IRow *bkt_row,
                       IRow *by_read, uint32_t *read_cnt, uint32_t *alive_rank,
-                      uint32_t *anchor_cnt, uint8_t *bkt_dead, uint32_t *flags, IRow *by_anchor, uint32_t cap,
+                      uint32_t *anchor_cnt, uint8_t *bkt_dead, uint32_t *flags, SRow *by_anchor, uint32_t cap,
                       const msgpu_row *rows, int32_t *read_len, uint32_t *read_first, uint32_t *err,
                       const uint2 *spos, uint4 *vis, uint32_t *visits) {
   if (V)
@@ -3762,7 +3759,7 @@ void launch_scatter_anchor(hipStream_t st, const msgpu_row *rows, uint64_t n, co
 }
 void launch_rank_anchor(hipStream_t st, const uint32_t *anchor_off, uint64_t n_rows, const uint32_t *d_n_alive,
                         const uint32_t *bkt_idx, const uint32_t *bkt_line, const msgpu_row *rows,
-                        const uint32_t *alive_rank, IRow *by_anchor, const uint32_t *flags, const uint32_t *read_off,
+                        const uint32_t *alive_rank, SRow *by_anchor, const uint32_t *flags, const uint32_t *read_off,
                         IRow *by_read, uint4 *vis) {
   if (n_rows)
     hipLaunchKernelGGL(k_rank_anchor, grid1(n_rows, 256), dim3(256), 0, st, anchor_off, d_n_alive, bkt_idx, bkt_line,

@@ -49,22 +49,23 @@ int main() {
   const uint32_t nb = (V + 15) / 16, cap = bin_capacity(R, V);
   printf("rows %llu, reads %u, buckets %u, capacity %u rows (%u KB of LDS per sort workgroup)\n", (unsigned long long)R, V, nb, cap, cap * 38 / 1024);
   msgpu_row *d_rows; uint32_t *d_flags, *d_err, *d_first, *d_cursor, *d_start, *d_base, *d_off, *d_cnt, *d_rfirst, *d_vis;
-  int32_t *d_len; uint4 *d_rec, *d_vis16; IRow *d_by_read, *d_by_anchor;
+  int32_t *d_len; uint4 *d_rec, *d_vis16; IRow *d_by_read; SRow *d_by_anchor;
   CK(hipMalloc(&d_rows, R * sizeof(msgpu_row))); CK(hipMemcpy(d_rows, h.data(), R * sizeof(msgpu_row), hipMemcpyHostToDevice));
   CK(hipMalloc(&d_flags, 64)); CK(hipMalloc(&d_err, 64)); CK(hipMalloc(&d_first, (A + 2) * 4ull)); CK(hipMalloc(&d_cursor, (nb + 2) * 4ull));
   CK(hipMalloc(&d_start, (nb + 2) * 4ull)); CK(hipMalloc(&d_base, 64)); CK(hipMalloc(&d_off, (V + 2) * 4ull)); CK(hipMalloc(&d_cnt, (V + 2) * 4ull));
   CK(hipMalloc(&d_rfirst, (V + 2) * 4ull)); CK(hipMalloc(&d_vis, (V + 2) * 4ull)); CK(hipMalloc(&d_len, (V + 2) * 4ull));
-  CK(hipMalloc(&d_rec, size_t(nb) * cap * 64)); CK(hipMalloc(&d_vis16, R * 16)); CK(hipMalloc(&d_by_read, R * 32)); CK(hipMalloc(&d_by_anchor, R * 32));
+  CK(hipMalloc(&d_rec, size_t(nb) * cap * 64)); CK(hipMalloc(&d_vis16, R * 16)); CK(hipMalloc(&d_by_read, R * 32)); CK(hipMalloc(&d_by_anchor, R * 16));
   const size_t wg1 = (R + 2047) / 2048, wg3 = nb;
   unsigned long long *d_st; CK(hipMalloc(&d_st, std::max(wg1, wg3) * 64));
+  unsigned long long *d_heads; CK(hipMalloc(&d_heads, 64)); uint32_t *d_bvis; CK(hipMalloc(&d_bvis, (nb + 2) * 4ull));
   std::vector<unsigned long long> st(std::max(wg1, wg3) * 8);
   for (int rep = 0; rep < 2; ++rep) {
-    CK(hipMemset(d_flags, 0, 64)); CK(hipMemset(d_err, 0, 64)); CK(hipMemset(d_cursor, 0, (nb + 2) * 4ull)); CK(hipMemset(d_base, 0, 64));
+    CK(hipMemset(d_flags, 0, 64)); CK(hipMemset(d_err, 0, 64)); CK(hipMemset(d_cursor, 0, (nb + 2) * 4ull)); CK(hipMemset(d_base, 0, 64)); CK(hipMemset(d_heads, 0, 64));
     CK(hipMemset(d_first, 0xff, (A + 2) * 4ull)); CK(hipMemset(d_st, 0, std::max(wg1, wg3) * 64));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &d_st, sizeof(d_st)));
     hipEvent_t e0, e1, e2; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1)); CK(hipEventCreate(&e2));
     CK(hipEventRecord(e0, 0));
-    launch_index_bin(0, d_rows, R, V, A, d_flags, d_err, d_first, d_cursor, d_rec, 0, nb, cap, d_start, d_base, d_off + V, true);
+    launch_index_bin(0, d_rows, R, V, A, d_flags, d_err, d_first, d_cursor, d_rec, 0, nb, cap, BinTail{d_start, d_base, d_off + V, d_heads});
     CK(hipEventRecord(e1, 0));
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(st.data(), d_st, wg1 * 64, hipMemcpyDeviceToHost));
@@ -72,7 +73,7 @@ int main() {
     if (rep) report("k_index_bin", st, wg1, l1, 5);
     CK(hipMemset(d_st, 0, std::max(wg1, wg3) * 64));
     CK(hipEventRecord(e1, 0));
-    launch_index_sort_bin(0, d_cursor, d_start, V, 0, nb, cap, d_rec, d_by_read, d_by_anchor, d_vis16, d_off, d_cnt, d_len, d_rfirst, d_vis, d_rows, d_flags, d_err);
+    launch_index_sort_bin(0, d_cursor, d_start, V, 0, nb, cap, d_rec, d_by_read, d_by_anchor, d_vis16, d_off, d_cnt, d_len, d_rfirst, d_vis, d_rows, d_flags, d_err, d_bvis);
     CK(hipEventRecord(e2, 0));
     CK(hipDeviceSynchronize());
     uint32_t fl = 0; CK(hipMemcpy(&fl, d_flags, 4, hipMemcpyDeviceToHost));
