@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Pin the read scrubber to the reference pipeline's own script, as data.
 
-    python tools/make_scrubber_fixtures.py <reference checkout> [--only small|big]
+    python tools/make_scrubber_fixtures.py <reference checkout> [--only small|big|edges]
 
 Reads <reference checkout>/pipeline/scrubber_bfs.py at run time and executes it unchanged but for its subset size
 (needs networkx), with two stand-ins: ``Bio.SeqIO.index_db`` returns the reads of the synthetic workload, and ``os.system``
@@ -15,6 +15,9 @@ script's text is kept.  Written under tests/golden/scrubber/:
   big.json                                              the same figures for an input of more than 60000 nodes (the only
                                                         way to meet the script's own batching); its inputs are regenerated
                                                         from (shape, seed) by the test
+  edges.json                                            per scrubber case of tests/scrubedgecases.py the subset size, the
+                                                        script's record count and the SHA-256 of its sorted records; a case
+                                                        the script cannot process is listed under "unprocessed" with the reason
 
 The script never ends on a batch with an empty centre, so every case is first run through the plain-Python restatement
 (tests/scrub_oracle.py), which raises on one: a shape that does is skipped and the next candidate is tried."""
@@ -135,6 +138,26 @@ def case(script, shape, subset_size):
     return (anchors, ava, fa), ref_sorted, meta
 
 
+def edges(script):
+    """The script on every case of tests/scrubedgecases.py -> the content of edges.json."""
+    import scrubedgecases
+    out = {"cases": {}, "unprocessed": {}}
+    for name, c in scrubedgecases.cases().items():
+        reads = scrub_oracle.parse_fasta(c.reads)
+        try:
+            scrub_oracle.scrub(c.anchors, c.ava, reads, c.subset_size)
+        except scrub_oracle.EmptyCentre as e:
+            out["unprocessed"][name] = "empty centre: %s" % e
+            continue
+        except scrub_oracle.OracleError as e:
+            out["unprocessed"][name] = "an accepted difference (the stage raises): %s" % e
+            continue
+        ref_sorted, n = sorted_records(run_script(script, c.anchors, c.ava, reads, c.subset_size))
+        out["cases"][name] = dict(subset_size=c.subset_size, records=n, sha256_sorted=hashlib.sha256(ref_sorted).hexdigest())
+        print("  ", name, out["cases"][name])
+    return out
+
+
 def main(argv):
     only = None
     if "--only" in argv:
@@ -158,6 +181,11 @@ def main(argv):
                 json.dump(meta, f, indent=1, sort_keys=True)
                 f.write("\n")
             print("  ", meta)
+    if only in (None, "edges"):
+        print("edge cases")
+        with open(os.path.join(GOLD, "edges.json"), "w") as f:
+            json.dump(edges(script), f, indent=1, sort_keys=True)
+            f.write("\n")
     if only in (None, "big"):
         for shape in BIG:
             print("big case", shape)
