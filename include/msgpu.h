@@ -1264,7 +1264,30 @@ void        msgpu_ug_result_free(msgpu_ug_result *r);
  *     tables (slots * (band + 1)^2 words, a constant number of slots that MSGPU_ALIGN_SLOTS=<n> lowers; no slab for a band
  *     of at most 31, whose tables all lie in LDS) to the fixed part
  *     and, per anchor, band + 1 words of script, the 64-bit offset, the script length, the class list entry, the '='
- *     columns behind the segment and the two column counts.  Without cigar every byte of every output is as before. */
+ *     columns behind the segment and the two column counts.  Without cigar every byte of every output is as before.
+ * 11. end extension, on request (msgpu_map_set_extension).  The parameter is extend = E: 0 is off (a new context), 1..65535
+ *     the longest flank on either sequence; E > 0 needs cigar = 1 (and so exact = 1), else the run is MSGPU_E_ARG naming
+ *     both.  The penalty is a constant of the rule, P = 8.  (1) Flanks of a chain with anchors a_0..a_{m-1}, oq the oriented
+ *     query of rule 7, tlen and qlen the lengths, rev byte reversal (no complement: oq is oriented already).  Right:
+ *     A = target[t_end .. t_end + n), n = min(E, tlen - t_end); B = oq[yE .. yE + m), yE = y_{m-1} + k,
+ *     m = min(E, qlen - yE).  Left: A = rev(target[x_0 - n .. x_0)), n = min(E, x_0); B = rev(oq[y_0 - m .. y_0)),
+ *     m = min(E, y_0).  (2) The table is rule 10's on (A, n, B, m), rows e = 0..band: the same slide, the same three
+ *     candidates with the same validity tests (only candidates that stay inside the matrix enter), the same tie order X, D,
+ *     I.  Nothing of rule 10's end test is used: |m - n| may exceed the band and no row ends the table early.  (3) Every
+ *     defined cell has x = G_e[k], y = x + k and score = x + y - P * e.  The end cell (e*, k*) is the one with the greatest
+ *     score; on equal scores the smaller e wins, then the smaller |k|, then the negative k.  Cell (0, 0) always exists with
+ *     score 2 * G_0[0] >= 0, so the end cell exists, and x* = y* = 0 means "no extension".  A row e with
+ *     n + m - P * e <= the best score of the rows before it cannot win, nor can a later one: rows, the number of rows an
+ *     end is charged with, is the first such e, or band + 1.  (4) The script is the walk back from (e*, k*) exactly as rule
+ *     10 walks back from (d, ks): e* + 1 words, consuming exactly x* bytes of A and y* bytes of B, every '=' column equal
+ *     and every X column unequal; a left flank's columns are written in reverse order.  (5) The chain: its runs are the left
+ *     columns, rule 10's chain alignment, the right columns, neighbouring runs merged; t_start -= x*_L, t_end += x*_R; the
+ *     oriented query range grows by y*_L and y*_R and rule 7 turns it into forward coordinates; matches, block and nm are
+ *     counted on the columns; cm, s1, n_anchors, score, the chain's place in the output order and which chains exist are
+ *     untouched.  The runs consume exactly the new target and query ranges.  (6) With E = 0 every byte is as before.  It
+ *     follows that a flank whose shorter side matches the longer side's start without an edit is extended to that
+ *     sequence's end: cell (0, 0) wins.  Rule 9 with E > 0: msgpu_map_batch_bytes_ext adds, per anchor, two ends' descriptors
+ *     (24 bytes each), end cells (24 bytes each) and band + 1 script words each; the slab is cigar mode's. */
 typedef struct msgpu_mapctx msgpu_mapctx; /* a device context of the stage */
 typedef struct msgpu_map_result msgpu_map_result;
 typedef struct msgpu_map_params {
@@ -1365,6 +1388,34 @@ typedef struct msgpu_map_astats { /* cigar mode: the segment pairs of rule 10, s
   float    cigar_host_ms;                                         /* host: the runs of all chains (wall, summed over the ranges) */
 } msgpu_map_astats;
 int         msgpu_map_result_align_stats(const msgpu_map_result *r, msgpu_map_astats *out);
+/* Rule 11.  msgpu_map_set_extension sets extend on the context for every later msgpu_map_run / msgpu_map_run_index, until it
+ * is set again; 0 switches it off.  A value above MSGPU_MAP_EXTEND_MAX is MSGPU_E_ARG, the previous value stays and
+ * msgpu_map_last_error names the value.  msgpu_map_batch_bytes_ext is msgpu_map_batch_bytes for a run with that extend (equal
+ * to it for extend = 0): what rule 9's cut and bytes_bound use.  msgpu_map_result_ext_stats gives zeros when the feature was
+ * off.  msgpu_map_result_ext_ends: the end cells, two per chain in output order, entry 2 i the left end of chain i and
+ * 2 i + 1 the right one (*n = 0 when the feature was off). */
+#define MSGPU_MAP_EXTEND_MAX 65535u
+#define MSGPU_MAP_EXTEND_PENALTY 8
+typedef struct msgpu_ext_end { /* the end cell of rule 11.3 */
+  uint32_t e;     /* its row: the script has e + 1 words */
+  int32_t  k;     /* its diagonal */
+  uint32_t x, y;  /* the bytes of A and of B that the extension consumes */
+  int32_t  score; /* x + y - P * e */
+  uint32_t rows;  /* the rows the end is charged with (rule 11.3) */
+} msgpu_ext_end;
+typedef struct msgpu_map_xstats { /* rule 11, summed over the batches */
+  uint32_t extend, reserved;
+  uint64_t n_ends, n_ends_extended, n_ends_at_sequence_end; /* two per chain; x* + y* > 0; the target or the query ends there */
+  uint64_t t_bases, q_bases;                                /* sums of x* and of y* */
+  uint64_t x_columns, i_columns, d_columns;                 /* of the ends' scripts */
+  uint64_t max_e, rows;                                     /* the largest e*; the sum of the ends' rows */
+  uint64_t n_inconsistent; /* ends whose table contradicted itself on the walk: 0, or the kernel is wrong */
+  float    extend_ms;      /* device, by events: descriptors and extension */
+} msgpu_map_xstats;
+int         msgpu_map_set_extension(msgpu_mapctx *ctx, uint32_t extend);
+int         msgpu_map_result_ext_stats(const msgpu_map_result *r, msgpu_map_xstats *out);
+int         msgpu_map_result_ext_ends(const msgpu_map_result *r, const msgpu_ext_end **ends, uint64_t *n);
+uint64_t    msgpu_map_batch_bytes_ext(const msgpu_map_params *params, uint32_t extend, uint64_t n_anchors, uint64_t n_query_bases);
 void        msgpu_map_result_free(msgpu_map_result *r);
 
 /* ---- pileup consensus: polishing a draft from the mapper's run tables ------------------------------
@@ -1580,6 +1631,15 @@ int msgpu_edit_distance(msgpu_seqctx *ctx, const void *d_a, const void *d_b, con
 int msgpu_edit_script(msgpu_seqctx *ctx, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n,
                       uint32_t band, uint32_t *dist, uint64_t *off /* n + 1 */, uint32_t *words, uint64_t capacity,
                       uint64_t *n_words);
+/* Rule 11's extension of every pair on its own ("unitig-to-read mapping", rule 11.2 to 11.4, is the definition): a and b
+ * are the flanks A and B, lengths below 2^29.  flags bit 0 = reversed: a_off and b_off then name the byte BEHIND the flank,
+ * whose byte i is base[off - 1 - i]; every other bit must be 0.  ends[p] is the end cell; off has n + 1 entries and pair p
+ * owns words[off[p] .. off[p + 1]), e + 1 words in msgpu_edit_script's format, in the flank's own order.  Capacity as
+ * msgpu_edit_script: MSGPU_E_ARG with ends, off and *n_words set when the words do not fit.  MSGPU_E_STATE: a table
+ * contradicted itself on the walk (a defect of the kernel, counted and reported, never passed over). */
+int msgpu_extend_ends(msgpu_seqctx *ctx, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n,
+                      uint32_t band, uint32_t flags, msgpu_ext_end *ends, uint64_t *off /* n + 1 */, uint32_t *words,
+                      uint64_t capacity, uint64_t *n_words);
 
 #ifdef __cplusplus
 }

@@ -242,6 +242,22 @@ class MapAlignStats(C.Structure):  # msgpu_map_astats
                 [("slots", C.c_uint32), ("lds_max_d", C.c_uint32), ("align_ms", C.c_float), ("cigar_host_ms", C.c_float)])
 
 
+class ExtEnd(C.Structure):  # msgpu_ext_end
+    _fields_ = [("e", C.c_uint32), ("k", C.c_int32), ("x", C.c_uint32), ("y", C.c_uint32), ("score", C.c_int32), ("rows", C.c_uint32)]
+
+
+class MapExtStats(C.Structure):  # msgpu_map_xstats
+    _fields_ = ([("extend", C.c_uint32), ("reserved", C.c_uint32)] +
+                [(n, C.c_uint64) for n in ("n_ends", "n_ends_extended", "n_ends_at_sequence_end", "t_bases", "q_bases", "x_columns",
+                                           "i_columns", "d_columns", "max_e", "rows", "n_inconsistent")] +
+                [("extend_ms", C.c_float)])
+
+
+MAP_EXTEND_MAX = 65535   # MSGPU_MAP_EXTEND_MAX
+MAP_EXTEND_PENALTY = 8   # MSGPU_MAP_EXTEND_PENALTY
+EXT_END_DTYPE = np.dtype([("e", "<u4"), ("k", "<i4"), ("x", "<u4"), ("y", "<u4"), ("score", "<i4"), ("rows", "<u4")])
+
+
 class MapBatch(C.Structure):  # msgpu_map_batch
     _fields_ = [("first_query", C.c_uint32), ("n_queries", C.c_uint32)] + [
         (n, C.c_uint64) for n in ("n_anchors", "n_query_bases", "n_groups", "n_chains", "n_pairs", "bytes_bound", "bytes_peak")]
@@ -524,6 +540,10 @@ SYMBOLS = [
     ("msgpu_map_result_cigars", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint64)),
                                           C.POINTER(C.c_uint64)]),
     ("msgpu_map_result_align_stats", C.c_int, [C.c_void_p, C.POINTER(MapAlignStats)]),
+    ("msgpu_map_set_extension", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("msgpu_map_result_ext_stats", C.c_int, [C.c_void_p, C.POINTER(MapExtStats)]),
+    ("msgpu_map_result_ext_ends", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(ExtEnd)), C.POINTER(C.c_uint64)]),
+    ("msgpu_map_batch_bytes_ext", C.c_uint64, [C.POINTER(MapParams), C.c_uint32, C.c_uint64, C.c_uint64]),
     ("msgpu_map_result_free", None, [C.c_void_p]),
     ("msgpu_pl_default_params", None, [C.POINTER(PlParams)]),
     ("msgpu_pl_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -542,6 +562,8 @@ SYMBOLS = [
     ("msgpu_edit_distance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                       C.c_void_p]),
     ("msgpu_edit_script", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("msgpu_extend_ends", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 ]
 

@@ -347,6 +347,12 @@ uint32_t   edit_script_lds_max_d(); // the largest distance of the class whose t
 hipError_t launch_edit_script_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
                                     uint32_t band, const uint32_t *d_dist, const uint64_t *d_off, uint32_t *d_list, uint32_t *d_cnt,
                                     uint32_t *d_slab, uint32_t slots, uint32_t *d_words);
+// Rule 11's extension on a DEVICE list of flank pairs (rev: all of them read backwards, their offsets naming the byte behind
+// the flank): d_ends[p] gets the end cell, d_words[p * (band + 1) ..) its e + 1 words; d_slab as above (shared with the
+// scripts, one after the other on the stream); *d_broken counts the ends whose table contradicts itself.
+hipError_t launch_extend_ends(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
+                              uint32_t band, bool rev, uint32_t *d_slab, uint32_t slots, msgpu_ext_end *d_ends, uint32_t *d_words,
+                              uint32_t *d_broken);
 
 } // namespace msgpu
 

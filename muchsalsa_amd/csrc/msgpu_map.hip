@@ -533,6 +533,21 @@ __global__ __launch_bounds__(256) void k_mp_cigar(msgpu_map_chain *chains, uint3
   chains[ci].nm       = cols[ci] - eq[ci];
 }
 
+// rule 11.1: the flank pairs of every chain.  The left ends, read backwards (their offsets name the byte behind the flank),
+// are pairs[0, n_chains); the right ends lie behind them.  The oriented query range is rule 7's, turned back
+__global__ __launch_bounds__(256) void k_mp_ends(const msgpu_map_chain *chains, uint32_t n_chains, const uint64_t *toff, const uint32_t *tlen,
+                                                 const uint64_t *qpre, const uint32_t *qlen, uint64_t q_base, uint64_t rc_base, uint32_t E,
+                                                 msgpu_align_pair *pairs) {
+  const uint32_t ci = blockIdx.x * 256 + threadIdx.x;
+  if (ci >= n_chains) return;
+  const msgpu_map_chain c = chains[ci];
+  const uint32_t        ql = qlen[c.query], tl = tlen[c.target];
+  const uint32_t        y0 = c.strand ? ql - c.q_end : c.q_start, ye = c.strand ? ql - c.q_start : c.q_end;
+  const uint64_t        ta = toff[c.target], qa = qpre[c.query] - q_base + (c.strand ? rc_base : 0);
+  pairs[ci]            = msgpu_align_pair{ta + c.t_start, qa + y0, min(E, c.t_start), min(E, y0)};
+  pairs[n_chains + ci] = msgpu_align_pair{ta + c.t_end, qa + ye, min(E, tl - c.t_end), min(E, ql - ye)};
+}
+
 __global__ __launch_bounds__(256) void k_mp_capped(const uint32_t *dist, uint32_t n, uint32_t band, kf_ull *capped) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   mp_count(i < n && dist[i] > band, capped);
@@ -548,6 +563,7 @@ struct msgpu_mapctx : msgpu::StageCtx {
   SeqCtxHold       seq;
   ScalarBlock      sc;
   msgpu_map_index *index = nullptr; // the one index the context holds (its targets lie in one of seq's two stores)
+  uint32_t         extend = 0;      // rule 11's parameter (msgpu_map_set_extension)
   ~msgpu_mapctx();
   int open() {
     const int rc = msgpu_seq_create(device, &seq.p);
@@ -569,6 +585,11 @@ struct msgpu_map_result {
   std::vector<uint64_t> c_poff{0}, p_woff{0};
   std::vector<uint32_t> cg_ops;      // the run tables (msgpu_map_result_cigars)
   std::vector<uint64_t> cg_off{0};
+  // rule 11.  Two ends per chain, the left one first; end j owns x_words[x_woff[j] .. x_woff[j + 1]), in its flank's order
+  msgpu_map_xstats           xstats{};
+  std::vector<msgpu_ext_end> x_ends;
+  std::vector<uint32_t>      x_words;
+  std::vector<uint64_t>      x_woff{0};
 };
 
 namespace {
@@ -684,6 +705,12 @@ void mp_runs(const msgpu_map_result &r, uint64_t i, std::vector<std::pair<uint32
     else runs.emplace_back(op, len);
   };
   static const uint32_t code[4] = {CG_EQ, CG_X, CG_DEL, CG_INS};
+  const bool ext = r.x_woff.size() > 2 * i + 2; // rule 11: the left end's columns in reverse order in front, the right end's behind
+  if (ext)
+    for (uint64_t w = r.x_woff[2 * i + 1]; w-- > r.x_woff[2 * i];) {
+      if (r.x_words[w] >> 30) push(code[r.x_words[w] >> 30], 1);
+      push(CG_EQ, r.x_words[w] & 0x3fffffffu);
+    }
   push(CG_EQ, r.c_head[i]);
   for (uint64_t p = r.c_poff[i + 1]; p-- > r.c_poff[i];) { // (stored from the last link to the first)
     if (r.p_woff[p + 1] == r.p_woff[p]) { // capped
@@ -697,6 +724,11 @@ void mp_runs(const msgpu_map_result &r, uint64_t i, std::vector<std::pair<uint32
     }
     push(CG_EQ, r.p_trail[p]);
   }
+  if (ext)
+    for (uint64_t w = r.x_woff[2 * i + 1]; w < r.x_woff[2 * i + 2]; ++w) {
+      push(CG_EQ, r.x_words[w] & 0x3fffffffu);
+      if (r.x_words[w] >> 30) push(code[r.x_words[w] >> 30], 1);
+    }
 }
 
 void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_seqfile *Q, bool exact, std::string &out,
@@ -753,25 +785,32 @@ static_assert(sizeof(MpRaw) == 28 && sizeof(MpWhere) == 8 && sizeof(msgpu_align_
 // cigar mode (rule 10), per segment pair beside its band + 1 words of script: len, off (64 bits), list, trail, eq, cols; per
 // chain: head and the two sums; fixed: the slab, the classes' counters and the column counters (two allocations)
 constexpr uint64_t MP_BYTES_ANCHOR_CIGAR = 4 + 8 + 4 + 4 + 4 + 4 + 3 * 4, MP_BYTES_FIXED_CIGAR = 2 * DevArena::ALIGN;
+// rule 11 (extend > 0), per chain two ends: a descriptor and an end cell each beside the band + 1 words of its script; fixed:
+// the counter of inconsistent ends and the rounding of the three arrays (the slab is cigar mode's, allocated once)
+constexpr uint64_t MP_BYTES_ANCHOR_EXT = 2 * (sizeof(msgpu_align_pair) + sizeof(msgpu_ext_end)), MP_BYTES_FIXED_EXT = 4 * DevArena::ALIGN;
+static_assert(sizeof(msgpu_ext_end) == 24, "rule 11's bytes per end");
 
-uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint64_t n_anchors, uint64_t n_query_bases) {
+uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint32_t extend, uint64_t n_anchors, uint64_t n_query_bases) {
   const bool     exact = prm.exact != 0, cigar = exact && prm.cigar != 0;
   const uint64_t band1 = static_cast<uint64_t>(prm.band < 0 ? 0 : prm.band > 127 ? 127 : prm.band) + 1;
+  const bool     ext = cigar && extend != 0;
   const uint64_t per = MP_BYTES_ANCHOR + MP_BYTES_ANCHOR_TMP + (exact ? MP_BYTES_ANCHOR_EXACT : 0) +
-                       (cigar ? MP_BYTES_ANCHOR_CIGAR + 4 * band1 : 0);
-  // beyond every device, and no overflow: per < 2^8 (2^10 in cigar mode: band + 1 words of script per anchor beside the rest)
+                       (cigar ? MP_BYTES_ANCHOR_CIGAR + 4 * band1 : 0) + (ext ? MP_BYTES_ANCHOR_EXT + 2 * 4 * band1 : 0);
+  // beyond every device, and no overflow: per < 2^8 (2^10 in cigar mode: band + 1 words of script per anchor beside the rest;
+  // below 2^12 with rule 11's two more scripts, descriptors and end cells)
   if (n_anchors >= (1ull << (cigar ? 50 : 54)) || n_query_bases >= (1ull << 62)) return ~0ull;
-  const uint64_t fixed = MP_BYTES_FIXED + (cigar ? MP_BYTES_FIXED_CIGAR + DevArena::aligned(4 * edit_script_slab_words(edit_script_slots(), static_cast<uint32_t>(band1 - 1))) : 0);
+  const uint64_t fixed = MP_BYTES_FIXED + (cigar ? MP_BYTES_FIXED_CIGAR + DevArena::aligned(4 * edit_script_slab_words(edit_script_slots(), static_cast<uint32_t>(band1 - 1))) : 0) +
+                         (ext ? MP_BYTES_FIXED_EXT : 0);
   return fixed + per * n_anchors + (exact ? 2 * n_query_bases : 0);
 }
 
 // The greedy cut of rule 9 over the prefix sums of the records' anchors and bases (n + 1 entries each): a binary search per
 // batch for the last record that still fits.  Returns the first record that fits no batch on its own, or n.
-uint32_t mp_cut(const msgpu_map_params &prm, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
+uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
   for (uint32_t first = 0; first < n;) {
     auto fits = [&](uint32_t end) {
       const uint64_t a = apre[end] - apre[first];
-      return a < (1ull << 31) && mp_batch_bytes(prm, a, bpre[end] - bpre[first]) <= budget;
+      return a < (1ull << 31) && mp_batch_bytes(prm, extend, a, bpre[end] - bpre[first]) <= budget;
     };
     if (!fits(first + 1)) return first;
     uint32_t lo = first + 1, hi = n; // the last end that fits
@@ -785,7 +824,7 @@ uint32_t mp_cut(const msgpu_map_params &prm, const uint64_t *apre, const uint64_
     b.n_queries     = lo - first;
     b.n_anchors     = apre[lo] - apre[first];
     b.n_query_bases = bpre[lo] - bpre[first];
-    b.bytes_bound   = mp_batch_bytes(prm, b.n_anchors, b.n_query_bases);
+    b.bytes_bound   = mp_batch_bytes(prm, extend, b.n_anchors, b.n_query_bases);
     out.push_back(b);
     first = lo;
   }
@@ -806,7 +845,142 @@ struct MpRun { // what stays on the device for the whole run (rule 9), as a batc
   kf_ull                 *d_hist; // 32 bins, summed over the batches
   StageClock             &clock;
   msgpu_map_result       *res;
+  uint32_t                extend; // rule 11's parameter
 };
+
+// ---- rule 11: the ends of a batch's chains
+
+struct MpExtBatch { // what the extension of a batch leaves for the host, valid after the batch's last synchronisation
+  std::vector<msgpu_ext_end> ends;  // the left ends of the batch's chains, then the right ends
+  std::vector<uint32_t>      words; // band + 1 words per end, e + 1 of them the script
+  uint32_t                   broken = 0;
+  msgpu_gather_plan         *plan = nullptr; // (of a batch without a segment pair, which has no oriented copies yet)
+  ~MpExtBatch() { msgpu_gather_plan_free(plan); }
+};
+
+// the descriptors (k_mp_ends), the extension of the left ends and of the right ends (launch_extend_ends), and their way back
+int mp_extend(const MpRun &R, DevArena &B, const msgpu_map_batch &bt, const msgpu_map_chain *d_chains, uint32_t C_n, uint8_t *d_or,
+              uint32_t *d_slab, MpExtBatch &xb) {
+  msgpu_mapctx  *c = R.c;
+  hipStream_t    st = c->stream;
+  const uint32_t band = static_cast<uint32_t>(R.prm.band), slots = edit_script_slots(), q0 = bt.first_query, q1 = q0 + bt.n_queries;
+  const uint64_t NB = bt.n_query_bases, b0 = R.bpre[q0], stride = band + 1ull, slab_words = edit_script_slab_words(slots, band);
+  if (!d_or) { // the batch's query records as they are and reverse-complemented, as exact mode lays them out
+    const uint32_t          from = R.qkind ? MSGPU_COPY_ILLUMINA : 0u;
+    std::vector<msgpu_copy> pieces;
+    try {
+      pieces.reserve(2ull * bt.n_queries);
+      for (uint32_t i = q0; i < q1; ++i) {
+        const uint64_t o = msgpu_seq_offset(R.Qf.f, i), at = R.bpre[i] - b0;
+        const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(R.Qf.f, i));
+        pieces.push_back(msgpu_copy{o, at, L, from});
+        pieces.push_back(msgpu_copy{o, NB + at, L, from | MSGPU_COPY_REVCOMP});
+      }
+    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+    int rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &xb.plan);
+    if (rc == MSGPU_OK) {
+      STAGE_HIP(c, B.get(&d_or, 2 * NB + 16));
+      rc = msgpu_gather_run(c->seq, xb.plan, d_or, 2 * NB + 16, st);
+    }
+    if (rc != MSGPU_OK) {
+      snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
+      return rc;
+    }
+  }
+  if (!d_slab && slab_words) STAGE_HIP(c, B.get(&d_slab, slab_words));
+  msgpu_align_pair *d_pairs;
+  msgpu_ext_end    *d_ends;
+  uint32_t         *d_words, *d_broken;
+  STAGE_HIP(c, B.get(&d_pairs, 2ull * C_n));
+  STAGE_HIP(c, B.get(&d_ends, 2ull * C_n));
+  STAGE_HIP(c, B.get(&d_words, 2ull * C_n * stride));
+  STAGE_HIP(c, B.get(&d_broken, 1));
+  try {
+    xb.ends.resize(2ull * C_n);
+    xb.words.resize(2ull * C_n * stride);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  STAGE_HIP(c, hipMemsetAsync(d_broken, 0, 4, st));
+  STAGE_HIP(c, R.clock.begin(&R.res->xstats.extend_ms));
+  hipLaunchKernelGGL(k_mp_ends, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, R.Tf.d_off, R.Tf.d_len, R.d_bpre, R.Qf.d_len, b0, NB, R.extend,
+                     d_pairs);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, launch_extend_ends(st, R.Tf.recs.bases, d_or, d_pairs, C_n, band, true, d_slab, slots, d_ends, d_words, d_broken));
+  STAGE_HIP(c, launch_extend_ends(st, R.Tf.recs.bases, d_or, d_pairs + C_n, C_n, band, false, d_slab, slots, d_ends + C_n,
+                                  d_words + C_n * stride, d_broken));
+  STAGE_HIP(c, R.clock.end());
+  STAGE_HIP(c, R.clock.begin(&R.res->stats.copy_ms));
+  STAGE_HIP(c, hipMemcpyAsync(xb.ends.data(), d_ends, xb.ends.size() * sizeof(msgpu_ext_end), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(xb.words.data(), d_words, xb.words.size() * 4, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(&xb.broken, d_broken, 4, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, R.clock.end());
+  return MSGPU_OK;
+}
+
+// rule 11.5 on the host: the last C_n chains of the result are the batch's; their ranges and figures grow by the ends' columns
+int mp_extend_apply(const MpRun &R, uint32_t C_n, const MpExtBatch &xb) {
+  msgpu_mapctx     *c = R.c;
+  msgpu_map_result &res = *R.res;
+  msgpu_map_xstats &X = res.xstats;
+  const uint32_t    band = static_cast<uint32_t>(R.prm.band);
+  const uint64_t    stride = band + 1ull;
+  const size_t      have = res.chains.size() - C_n;
+  X.n_inconsistent += xb.broken;
+  try {
+    for (uint32_t i = 0; i < C_n; ++i) {
+      msgpu_map_chain &ch = res.chains[have + i];
+      const uint64_t   tlen = msgpu_seq_length(R.Tf.f, ch.target), qlen = msgpu_seq_length(R.Qf.f, ch.query);
+      for (int side = 0; side < 2; ++side) { // the left end, then the right one
+        const size_t         j = side ? C_n + i : i;
+        const msgpu_ext_end &E = xb.ends[j];
+        const uint32_t      *w = xb.words.data() + j * stride;
+        // what the cell claims is checked before anything is moved by it: its row, its words and the room the chain has
+        const uint64_t t_room = side ? tlen - ch.t_end : ch.t_start;
+        const uint64_t q_room = (side != 0) != (ch.strand != 0) ? qlen - ch.q_end : ch.q_start;
+        uint64_t       eq = 0, cnt[4] = {0, 0, 0, 0};
+        bool           bad = E.e > band || E.x > t_room || E.y > q_room;
+        for (uint32_t t = 0; !bad && t <= E.e; ++t) {
+          eq += w[t] & 0x3fffffffu;
+          ++cnt[w[t] >> 30];
+          bad = (t < E.e) != ((w[t] >> 30) != 0);
+        }
+        bad = bad || eq + cnt[1] + cnt[2] != E.x || eq + cnt[1] + cnt[3] != E.y;
+        if (bad) {
+          ++X.n_inconsistent;
+          res.x_ends.push_back(msgpu_ext_end{0, 0, 0, 0, 0, E.rows});
+          res.x_words.push_back(0);
+          res.x_woff.push_back(res.x_words.size());
+          continue;
+        }
+        if (side) ch.t_end += E.x;
+        else ch.t_start -= E.x;
+        if ((side != 0) != (ch.strand != 0)) ch.q_end += E.y;
+        else ch.q_start -= E.y;
+        ch.matches += static_cast<uint32_t>(eq);
+        ch.block += static_cast<uint32_t>(eq) + E.e;
+        ch.nm += E.e;
+        res.x_ends.push_back(E);
+        res.x_words.insert(res.x_words.end(), w, w + E.e + 1);
+        res.x_woff.push_back(res.x_words.size());
+        X.n_ends_extended += (E.x | E.y) != 0;
+        X.n_ends_at_sequence_end += E.x == t_room || E.y == q_room;
+        X.t_bases += E.x;
+        X.q_bases += E.y;
+        X.x_columns += cnt[1];
+        X.d_columns += cnt[2];
+        X.i_columns += cnt[3];
+        X.max_e = std::max<uint64_t>(X.max_e, E.e);
+        X.rows += E.rows;
+      }
+    }
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  X.n_ends += 2ull * C_n;
+  if (X.n_inconsistent) {
+    snprintf(c->err, sizeof(c->err), "the tables of %llu chain ends contradict themselves (a defect of the extension kernel)",
+             static_cast<kf_ull>(X.n_inconsistent));
+    return MSGPU_E_STATE;
+  }
+  return MSGPU_OK;
+}
 
 // rules 4 to 8 for the query records of one batch.  Every array is taken from the reserved arena B and indexed from the
 // batch's first anchor; the record indices in g and in the chain table are the file's.  The counters of the scalar block
@@ -913,7 +1087,8 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   STAGE_HIP(c, clock.end());
 
   // ---- rule 6
-  uint32_t C_n = 0;
+  uint32_t   C_n = 0;
+  MpExtBatch xb; // rule 11: what comes back with the chain table
   if (n_kept) {
     STAGE_HIP(c, clock.begin(&S.backtrack_ms));
     STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
@@ -946,6 +1121,9 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
                        R.Qf.d_len, k, d_chains, d_where, d_np, C_n);
     STAGE_HIP(c, hipGetLastError());
     STAGE_HIP(c, clock.end());
+
+    uint8_t  *d_or = nullptr;   // the batch's oriented query records (exact mode with a segment pair; rule 11 makes its own otherwise)
+    uint32_t *d_slab = nullptr; // the tables of the slab class (cigar mode with a segment pair; likewise)
 
     // ---- rule 7 in exact mode
     if (exact) {
@@ -981,7 +1159,6 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
           msgpu_gather_plan *p;
           ~FreePlan() { msgpu_gather_plan_free(p); }
         } free_plan{plan};
-        uint8_t          *d_or;
         msgpu_align_pair *d_pairs;
         uint32_t         *d_dist, *d_nm = nullptr, *d_trail = nullptr, *d_head = nullptr;
         STAGE_HIP(c, B.get(&d_or, 2 * NB + 16));
@@ -1016,7 +1193,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
         if (cigar) {
           // ---- rule 10: the scripts' offsets, the scripts, the figures of the pairs and of the chains
           const uint32_t band = static_cast<uint32_t>(prm.band), slots = edit_script_slots();
-          uint32_t      *d_len, *d_list, *d_cnt, *d_slab = nullptr, *d_words, *d_eq, *d_cols;
+          uint32_t      *d_len, *d_list, *d_cnt, *d_words, *d_eq, *d_cols;
           const uint64_t slab_words = edit_script_slab_words(slots, band); // (none for a band within the LDS class)
           uint64_t      *d_off;
           kf_ull        *d_xid;
@@ -1108,6 +1285,12 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
       }
     }
 
+    // ---- rule 11: the ends of every chain, behind the scripts (the slab is theirs first)
+    if (R.extend) {
+      rc = mp_extend(R, B, bt, d_chains, C_n, d_or, d_slab, xb);
+      if (rc != MSGPU_OK) return rc;
+    }
+
     // ---- the batch's chain table behind those of the batches before it
     const size_t have = R.res->chains.size();
     try {
@@ -1125,6 +1308,10 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
         R.res->c_poff.push_back(R.res->p_lt.size());
       }
     } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  }
+  if (R.extend && C_n) {
+    rc = mp_extend_apply(R, C_n, xb);
+    if (rc != MSGPU_OK) return rc;
   }
   clock.collect();
   bt.bytes_peak = B.peak;
@@ -1317,7 +1504,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   for (;;) {
     res->budget = budget;
     res->batches.clear();
-    const uint32_t bad = mp_cut(prm, apre, bpre, NR, budget, res->batches);
+    const uint32_t bad = mp_cut(prm, c->extend, apre, bpre, NR, budget, res->batches);
     if (bad < NR) {
       const uint64_t a = apre[bad + 1] - apre[bad], b = bpre[bad + 1] - bpre[bad];
       if (a >= (1ull << 31)) {
@@ -1327,7 +1514,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
       }
       snprintf(c->err, sizeof(c->err), "query record %u with %llu anchors and %llu bases needs %llu bytes on its own (%llu of them for its "
                "oriented copies); the budget of a batch is %llu bytes (rule 9: a record is not split)", bad, static_cast<kf_ull>(a),
-               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(prm, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
+               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(prm, c->extend, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
                static_cast<kf_ull>(budget));
       return MSGPU_E_NOMEM;
     }
@@ -1346,7 +1533,8 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   }
 
   // ---- rules 4 to 8, batch by batch
-  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res};
+  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res, c->extend};
+  res->xstats.extend = c->extend;
   for (msgpu_map_batch &b : res->batches) {
     rc = mp_batch(run, B, b);
     if (rc != MSGPU_OK) return rc;
@@ -1430,7 +1618,24 @@ void msgpu_map_default_params(msgpu_map_params *p) {
 uint64_t msgpu_map_batch_bytes(const msgpu_map_params *p, uint64_t n_anchors, uint64_t n_query_bases) {
   msgpu_map_params prm{};
   if (p) prm = *p;
-  return mp_batch_bytes(prm, n_anchors, n_query_bases);
+  return mp_batch_bytes(prm, 0, n_anchors, n_query_bases);
+}
+
+uint64_t msgpu_map_batch_bytes_ext(const msgpu_map_params *p, uint32_t extend, uint64_t n_anchors, uint64_t n_query_bases) {
+  msgpu_map_params prm{};
+  if (p) prm = *p;
+  return mp_batch_bytes(prm, extend, n_anchors, n_query_bases);
+}
+
+int msgpu_map_set_extension(msgpu_mapctx *c, uint32_t extend) {
+  if (!c) return MSGPU_E_ARG;
+  c->err[0] = 0;
+  if (extend > MSGPU_MAP_EXTEND_MAX) {
+    snprintf(c->err, sizeof(c->err), "extend = %u; the limit is %u (0 switches the extension off)", extend, MSGPU_MAP_EXTEND_MAX);
+    return MSGPU_E_ARG;
+  }
+  c->extend = extend;
+  return MSGPU_OK;
 }
 
 int  msgpu_map_create(int device, msgpu_mapctx **out) { return stage_create(device, out); }
@@ -1445,6 +1650,11 @@ static int mp_check_params(msgpu_mapctx *c, const msgpu_map_params &p) {
     snprintf(c->err, sizeof(c->err), "parameters: k = %d (4..32), w = %d (1..64), max_occ = %u (>= 1), max_gap = %d, bandwidth = %d "
              "(>= 0), max_pred = %d (64), band = %d (1..127), exact = %d, ava = %d (0 / 1), cigar = %d (0 / 1; 1 needs exact = 1)", p.k, p.w,
              p.max_occ, p.max_gap, p.bandwidth, p.max_pred, p.band, p.exact, p.ava, p.cigar);
+    return MSGPU_E_ARG;
+  }
+  if (c->extend && !p.cigar) {
+    snprintf(c->err, sizeof(c->err), "parameters: extend = %u needs cigar = 1 (and so exact = 1); the run has cigar = %d (rule 11)", c->extend,
+             p.cigar);
     return MSGPU_E_ARG;
   }
   return MSGPU_OK;
@@ -1606,6 +1816,19 @@ int msgpu_map_result_cigars(const msgpu_map_result *r, const uint32_t **ops, con
 int msgpu_map_result_align_stats(const msgpu_map_result *r, msgpu_map_astats *out) {
   if (!r || !out) return MSGPU_E_ARG;
   *out = r->astats;
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_ext_stats(const msgpu_map_result *r, msgpu_map_xstats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->xstats;
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_ext_ends(const msgpu_map_result *r, const msgpu_ext_end **ends, uint64_t *n) {
+  if (!r || !ends || !n) return MSGPU_E_ARG;
+  *ends = r->x_ends.data();
+  *n    = r->x_ends.size();
   return MSGPU_OK;
 }
 

@@ -1288,22 +1288,32 @@ __global__ __launch_bounds__(128) void k_edit_distance_dp(const uint8_t *base_a,
 
 constexpr int FR_NONE = -(1 << 30);
 
-// length of the common prefix of pa[0, valid) and pb[0, valid), valid <= 8 (nothing behind `valid` is read)
+// length of the common prefix of pa[0, valid) and pb[0, valid), valid <= 8 (nothing behind `valid` is read).  REV: the same
+// run read backwards, pa[-1 - r] against pb[-1 - r]: an 8-byte load that ends at the position, and the leading zero bytes of
+// the difference (nothing in front of pa[-valid] is read)
+template <bool REV = false>
 __device__ __forceinline__ int match_run8(const uint8_t *pa, const uint8_t *pb, int valid) {
   if (valid >= 8) {
     uint64_t x, y;
-    __builtin_memcpy(&x, pa, 8);
-    __builtin_memcpy(&y, pb, 8);
+    __builtin_memcpy(&x, REV ? pa - 8 : pa, 8);
+    __builtin_memcpy(&y, REV ? pb - 8 : pb, 8);
     const uint64_t d = x ^ y;
+    if (REV) return d ? (__builtin_clzll(d) >> 3) : 8;
     return d ? (__builtin_ctzll(d) >> 3) : 8;
   }
   int r = 0;
+  if (REV) {
+    while (r < valid && pa[-1 - r] == pb[-1 - r]) ++r;
+    return r;
+  }
   while (r < valid && pa[r] == pb[r]) ++r;
   return r;
 }
 
 // The slides of one row, shared by the distance and the script kernels: every lane's points nf[c] (negative: none) on the
-// diagonals |k| <= R move along the common prefix of a[x..) and b[x + k..), lane-local first, then at the wavefront's width
+// diagonals |k| <= R move along the common prefix of a[x..) and b[x + k..), lane-local first, then at the wavefront's width.
+// REV (rule 11's left flanks): byte i of a sequence is base[-1 - i], a and b name the byte behind their flank
+template <bool REV = false>
 __device__ __forceinline__ void fr_slide_row(const uint8_t *a, int n, const uint8_t *b, int m, int R, int lane, int (&nf)[4]) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -1315,7 +1325,7 @@ __device__ __forceinline__ void fr_slide_row(const uint8_t *a, int n, const uint
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int valid = min(8, min(n - x, m - (x + k)));
-        const int run   = match_run8(a + x, b + (x + k), valid);
+        const int run   = match_run8<REV>(REV ? a - x : a + x, REV ? b - (x + k) : b + (x + k), valid);
         x += run;
         more = run == 8;
         if (!more) break;
@@ -1330,7 +1340,7 @@ __device__ __forceinline__ void fr_slide_row(const uint8_t *a, int n, const uint
       for (;;) {
         const int px    = xs + 8 * lane;
         const int valid = min(8, min(n - px, m - (px + kk)));
-        const int run   = valid > 0 ? match_run8(a + px, b + (px + kk), valid) : 0;
+        const int run   = valid > 0 ? match_run8<REV>(REV ? a - px : a + px, REV ? b - (px + kk) : b + (px + kk), valid) : 0;
         const unsigned long long stop = __ballot(run < 8);
         if (stop) {
           const int F = __builtin_ctzll(stop);
@@ -1589,6 +1599,173 @@ hipError_t launch_edit_script_pairs(hipStream_t st, const uint8_t *d_a, const ui
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Rule 11 (include/msgpu.h, "unitig-to-read mapping"): an alignment with a free end.  The table is rule 10's on a flank pair,
+// rows 0..band, with nothing of its end test: every defined cell (e, k) scores x + y - EXT_P * e, and the end cell is the best
+// one by (score, smaller e, smaller |k|, negative k).  The row loop is edit_script_wave's (the valid-candidate recurrence:
+// here the values of all cells decide, so the clamped one of edit_distance_fr_wave will not do); every lane keeps the best
+// of its own cells, one reduction per row gives the wavefront's best score, which ends the loop at the first row that
+// cannot beat it (a cell of row e scores at most n + m - EXT_P * e, and on a tie the smaller e wins), and one reduction
+// behind the loop applies the whole order.  The walk back from the end cell is edit_script_wave's, e* + 1 words.
+// REV reads flank byte i as base[-1 - i] (a left flank: a and b name the byte behind it), so no reversed copy exists.
+// A table that contradicts itself on the walk is counted in *broken.
+// ---------------------------------------------------------------------------------------------------------------------
+
+constexpr int EXT_P = MSGPU_MAP_EXTEND_PENALTY;
+
+__device__ __forceinline__ bool ext_better(int s, int e, int k, int bs, int be, int bk) {
+  if (s != bs) return s > bs;
+  if (e != be) return e < be;
+  const int ak = k < 0 ? -k : k, abk = bk < 0 ? -bk : bk;
+  if (ak != abk) return ak < abk;
+  return k < bk;
+}
+
+template <bool REV>
+__device__ __forceinline__ void extend_wave(const uint8_t *a, int n, const uint8_t *b, int m, int band, uint32_t *T, bool in_lds,
+                                            uint32_t *out, msgpu_ext_end *end, uint32_t *broken) {
+  const int lane = threadIdx.x & 63;
+  int       fr[4] = {FR_NONE, FR_NONE, FR_NONE, FR_NONE};
+  int       bs = -(1 << 30), be = 0, bk = 0; // this lane's best cell
+  int       top = -(1 << 30), rows = 0;      // the wavefront's best score so far; the rows that ran
+  for (int e = 0; e <= band; ++e) {
+    if (n + m - EXT_P * e <= top) break; // (uniform; never at e = 0)
+    int      nf[4];
+    uint32_t op[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int k = lane + 64 * c - 128;
+      int       x = FR_NONE;
+      uint32_t  o = 0;
+      if (e == 0) {
+        if (k == 0) x = 0;
+      } else {
+        int lo = __shfl_up(fr[c], 1), hi = __shfl_down(fr[c], 1); // diagonals k - 1, k + 1
+        const int lo_edge = c > 0 ? __shfl(fr[c > 0 ? c - 1 : 0], 63) : FR_NONE;
+        const int hi_edge = c < 3 ? __shfl(fr[c < 3 ? c + 1 : 3], 0) : FR_NONE;
+        if (lane == 0) lo = lo_edge;
+        if (lane == 63) hi = hi_edge;
+        if ((k < 0 ? -k : k) <= e) { // rule 10: the largest valid candidate, the first of X, D, I on a tie
+          if (fr[c] >= 0 && fr[c] < min(n, m - k)) {
+            x = fr[c] + 1;
+            o = ES_X;
+          }
+          if (hi >= 0 && hi < n && hi + 1 > x) {
+            x = hi + 1;
+            o = ES_D;
+          }
+          if (lo >= 0 && lo + k <= m && lo > x) {
+            x = lo;
+            o = ES_I;
+          }
+        }
+      }
+      nf[c] = x;
+      op[c] = o;
+    }
+    fr_slide_row<REV>(a, n, b, m, e, lane, nf);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int k = lane + 64 * c - 128;
+      if ((k < 0 ? -k : k) <= e && nf[c] >= 0) {
+        T[e * e + k + e] = (op[c] << 30) | static_cast<uint32_t>(nf[c]);
+        const int s = 2 * nf[c] + k - EXT_P * e;
+        if (ext_better(s, e, k, bs, be, bk)) {
+          bs = s;
+          be = e;
+          bk = k;
+        }
+      }
+      fr[c] = nf[c];
+    }
+    top = bs;
+    for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o));
+    ++rows;
+  }
+  for (int o = 32; o > 0; o >>= 1) { // rule 11.3's order over the lanes' bests: every lane ends with the end cell
+    const int os = __shfl_xor(bs, o), oe = __shfl_xor(be, o), ok = __shfl_xor(bk, o);
+    if (ext_better(os, oe, ok, bs, be, bk)) {
+      bs = os;
+      be = oe;
+      bk = ok;
+    }
+  }
+  // the table was written by all lanes and is read by each: LDS needs the wavefront's order, device memory the device's
+  if (in_lds) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __threadfence();
+  }
+  const int es = max(0, min(band, be)); // (no read leaves the table)
+  int       k = max(-es, min(es, bk));
+  bool      bad = es != be || k != bk;
+  uint32_t  w = T[es * es + k + es], carry = 0;
+  const int xs = static_cast<int>(w & ES_RUN);
+  bad |= 2 * xs + k - EXT_P * es != bs; // the end cell is not what the row loop saw
+  for (int e = es; e >= 1; --e) {
+    const uint32_t o  = w >> 30;
+    const int      ko = o == ES_X ? k : o == ES_D ? k + 1 : k - 1;
+    const int      kp = max(-(e - 1), min(e - 1, ko)); // (no read leaves the table)
+    bad |= o == 0 || kp != ko;
+    const uint32_t wp = T[(e - 1) * (e - 1) + kp + (e - 1)];
+    const uint32_t x0 = (wp & ES_RUN) + (o != ES_I ? 1u : 0u);
+    if (lane == 0) out[e] = (carry << 30) | (((w & ES_RUN) - x0) & ES_RUN);
+    carry = o;
+    k     = kp;
+    w     = wp;
+  }
+  bad |= k != 0 || (w >> 30) != 0;
+  if (lane == 0) {
+    out[0] = (carry << 30) | (w & ES_RUN);
+    *end   = msgpu_ext_end{static_cast<uint32_t>(es), bk, static_cast<uint32_t>(xs), static_cast<uint32_t>(xs + bk), bs,
+                           static_cast<uint32_t>(rows)};
+    if (bad) atomicAdd(broken, 1u);
+  }
+}
+
+// one wavefront per end; end p's words go to words[p * (W + 1) ..), e + 1 of them.  IN_LDS (W <= ES_LDS_MAXD): the table in
+// LDS, four wavefronts to a workgroup; otherwise the wavefronts stride over the slots of the slab
+template <bool IN_LDS, bool REV>
+__global__ __launch_bounds__(256) void k_extend_ends(const uint8_t *base_a, const uint8_t *base_b, const msgpu_align_pair *pairs,
+                                                     uint32_t n_pairs, uint32_t W, uint32_t *slab, uint32_t slots, msgpu_ext_end *ends,
+                                                     uint32_t *words, uint32_t *broken) {
+  __shared__ uint32_t s_t[IN_LDS ? 4 : 1][IN_LDS ? (ES_LDS_MAXD + 1) * (ES_LDS_MAXD + 1) : 1];
+  const uint32_t wave = threadIdx.x >> 6, wv = blockIdx.x * 4 + wave;
+  if (IN_LDS) {
+    if (wv >= n_pairs || W > static_cast<uint32_t>(ES_LDS_MAXD)) return; // (whole wavefronts leave)
+    const msgpu_align_pair pr = pairs[wv];
+    extend_wave<REV>(base_a + pr.a_off, static_cast<int>(pr.a_len), base_b + pr.b_off, static_cast<int>(pr.b_len), static_cast<int>(W),
+                     s_t[wave], true, words + static_cast<uint64_t>(wv) * (W + 1), ends + wv, broken);
+  } else {
+    if (wv >= slots) return;
+    uint32_t *const T = slab + static_cast<uint64_t>(wv) * (W + 1) * (W + 1);
+    for (uint32_t p = wv; p < n_pairs; p += slots) {
+      const msgpu_align_pair pr = pairs[p];
+      extend_wave<REV>(base_a + pr.a_off, static_cast<int>(pr.a_len), base_b + pr.b_off, static_cast<int>(pr.b_len), static_cast<int>(W),
+                       T, false, words + static_cast<uint64_t>(p) * (W + 1), ends + p, broken);
+    }
+  }
+}
+
+hipError_t launch_extend_ends(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
+                              uint32_t band, bool rev, uint32_t *d_slab, uint32_t slots, msgpu_ext_end *d_ends, uint32_t *d_words,
+                              uint32_t *d_broken) {
+  if (!n) return hipSuccess;
+  if (band <= static_cast<uint32_t>(ES_LDS_MAXD)) {
+    const dim3 grid((n + 3) / 4);
+    if (rev) hipLaunchKernelGGL((k_extend_ends<true, true>), grid, dim3(256), 0, st, d_a, d_b, d_pairs, n, band, d_slab, slots, d_ends, d_words, d_broken);
+    else hipLaunchKernelGGL((k_extend_ends<true, false>), grid, dim3(256), 0, st, d_a, d_b, d_pairs, n, band, d_slab, slots, d_ends, d_words, d_broken);
+  } else {
+    if (!slots || !d_slab) return hipErrorInvalidValue;
+    const dim3 grid((slots + 3) / 4);
+    if (rev) hipLaunchKernelGGL((k_extend_ends<false, true>), grid, dim3(256), 0, st, d_a, d_b, d_pairs, n, band, d_slab, slots, d_ends, d_words, d_broken);
+    else hipLaunchKernelGGL((k_extend_ends<false, false>), grid, dim3(256), 0, st, d_a, d_b, d_pairs, n, band, d_slab, slots, d_ends, d_words, d_broken);
+  }
+  return hipGetLastError();
+}
+
 const uint8_t *seq_store_bases(const msgpu_seqctx *c, int kind, uint64_t *n_bases) {
   const SeqStore &s = c->st[kind];
   *n_bases = s.d_buf ? s.n_bases : 0;
@@ -1694,6 +1871,70 @@ int msgpu_edit_script(msgpu_seqctx *c, const void *d_a, const void *d_b, const m
              h_cnt[ES_CNT_BROKEN]);
     return MSGPU_E_STATE;
   }
+  return MSGPU_OK;
+}
+
+int msgpu_extend_ends(msgpu_seqctx *c, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n, uint32_t band,
+                      uint32_t flags, msgpu_ext_end *ends, uint64_t *off, uint32_t *words, uint64_t capacity, uint64_t *n_words) {
+  if (!c || !n_words || !off || (n && (!pairs || !ends || !d_a || !d_b)) || (capacity && !words) || band > ED_MAXW || (flags & ~1u) ||
+      n >= 0x7fffffffull)
+    return MSGPU_E_ARG;
+  if (c->device < 0) return MSGPU_E_NODEVICE;
+  *n_words = 0;
+  off[0]   = 0;
+  if (!n) return MSGPU_OK;
+  for (size_t i = 0; i < n; ++i)
+    if (pairs[i].a_len >= (1u << 29) || pairs[i].b_len >= (1u << 29)) return MSGPU_E_ARG; // (scores are ints on the device)
+  STAGE_HIP(c, hipSetDevice(c->device));
+  DevArena          D; // (freed on every way out)
+  hipStream_t       st = c->stream;
+  const uint32_t    np = static_cast<uint32_t>(n), slots = std::min(edit_script_slots(), np);
+  const uint64_t    slab_words = edit_script_slab_words(slots, band), stride = band + 1ull;
+  msgpu_align_pair *d_pairs;
+  msgpu_ext_end    *d_ends;
+  uint32_t         *d_words, *d_slab = nullptr, *d_broken;
+  STAGE_HIP(c, D.get(&d_pairs, n));
+  STAGE_HIP(c, D.get(&d_ends, n));
+  STAGE_HIP(c, D.get(&d_words, n * stride));
+  STAGE_HIP(c, D.get(&d_broken, 1));
+  if (slab_words) STAGE_HIP(c, D.get(&d_slab, slab_words));
+  if (std::getenv("MSGPU_POISON")) { // (see DevBuf::ensure in msgpu_api.hip)
+    if (slab_words) STAGE_HIP(c, hipMemsetAsync(d_slab, 0xA5, slab_words * 4, st));
+    STAGE_HIP(c, hipMemsetAsync(d_words, 0xA5, n * stride * 4, st));
+  }
+  STAGE_HIP(c, hipMemsetAsync(d_broken, 0, 4, st));
+  STAGE_HIP(c, hipMemcpyAsync(d_pairs, pairs, n * sizeof(msgpu_align_pair), hipMemcpyHostToDevice, st));
+  STAGE_HIP(c, launch_extend_ends(st, static_cast<const uint8_t *>(d_a), static_cast<const uint8_t *>(d_b), d_pairs, np, band,
+                                  (flags & 1u) != 0, d_slab, slots, d_ends, d_words, d_broken));
+  uint32_t h_broken = 0;
+  STAGE_HIP(c, hipMemcpyAsync(ends, d_ends, n * sizeof(msgpu_ext_end), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(&h_broken, d_broken, 4, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  if (h_broken) {
+    snprintf(c->err, sizeof(c->err), "msgpu_extend_ends: the tables of %u ends contradict themselves (a defect of the kernels)", h_broken);
+    return MSGPU_E_STATE;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (ends[i].e > band) {
+      snprintf(c->err, sizeof(c->err), "msgpu_extend_ends: end %llu came back with row %u beyond the band", static_cast<unsigned long long>(i), ends[i].e);
+      return MSGPU_E_STATE;
+    }
+    off[i + 1] = off[i] + ends[i].e + 1;
+  }
+  const uint64_t total = off[n];
+  *n_words = total;
+  if (total > capacity) {
+    snprintf(c->err, sizeof(c->err), "msgpu_extend_ends: the scripts take %llu words, the caller has room for %llu",
+             static_cast<unsigned long long>(total), static_cast<unsigned long long>(capacity));
+    return MSGPU_E_ARG;
+  }
+  std::vector<uint32_t> h_words; // (the device keeps band + 1 words per end; e + 1 of them are the script)
+  try {
+    h_words.resize(n * stride);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  STAGE_HIP(c, hipMemcpyAsync(h_words.data(), d_words, n * stride * 4, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipStreamSynchronize(st));
+  for (size_t i = 0; i < n; ++i) std::copy_n(h_words.data() + i * stride, ends[i].e + 1ull, words + off[i]);
   return MSGPU_OK;
 }
 

@@ -84,7 +84,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None):
+        bubble=None, polish=None, extend=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -92,7 +92,9 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     that PAF is the same.  ``bubble`` (None or 0: off) is the unitig assembly's rule 9 parameter (muchsalsa_amd.unitigs): bubbles
     with branches of up to that many k-mers are popped before the unitigs are written.  ``polish`` (None or 0: off) = N >= 1 adds a
     last stage ``"polish"``: N rounds of muchsalsa_amd.polish of the assembly by the scrubbed reads into POLISHED_NAME, named by
-    ``files["polished"]``; every other file is the same."""
+    ``files["polished"]``; every other file is the same.  ``extend`` (None or 0: off) = N is the mapper's rule 11 parameter: step 9
+    then runs with cigar = 1 and extend = N, and so does every mapping of the polish stage; every file written before step 9's
+    PAF is the same."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -135,7 +137,8 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     finally:
         index.__exit__(None, None, None)
     stage("scrubber", scrubber.run, files["corrected_paf"], reads, files["scrubbed"], files["ava_paf"], device=device)
-    stage("map_exact", mapper.run, files["scrubbed"], files["corrected"], files["exact_paf"], device=device, exact=1, cigar=1 if cigar else 0)
+    stage("map_exact", mapper.run, files["scrubbed"], files["corrected"], files["exact_paf"], device=device, exact=1,
+          cigar=1 if cigar or extend else 0, extend=int(extend or 0))
     stage("assembly", pipeline.run, files["exact_paf"], files["corrected"], files["scrubbed"], os.path.join(out, "tmp"),
           threads=int(cores), device=device)
     shutil.copyfile(files["target"], files["assembly"])  # pipeline.sh:181
@@ -144,7 +147,7 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
         from . import polish as polisher
         result["files"]["polished"] = os.path.join(out, POLISHED_NAME)
         stage("polish", polisher.run, files["assembly"], files["scrubbed"], result["files"]["polished"], rounds=int(polish),
-              device=device)
+              device=device, extend=int(extend or 0))
     result["seconds"] = round(time.perf_counter() - t_all, 4)
     return result
 

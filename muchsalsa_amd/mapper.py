@@ -3,18 +3,20 @@ write -- a PAF of every record of a query file against every record of a target 
 
     python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--cigar] [--ava]
             [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
+            [--extend N]
 
 prints one JSON line of counts and seconds.  ``--budget-mb`` (N > 0) bounds the device memory of a batch of query records
 (rule 9; without it: the free device memory).  With ``--ava`` the two paths name the same file (the reads against
 themselves: the read-to-read PAF muchsalsa_amd.scrubber takes as its fourth input); ``--exact`` adds the base-level match
 count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call); ``--cigar`` (which implies ``--exact``) aligns
 every segment base by base (rule 10): column 10 is then the number of ``=`` columns, column 11 the number of alignment columns,
-and the line ends in a ``cg:Z:`` string of ``=``, ``X``, ``I`` and ``D`` runs.  minimap2 is not needed, and it is not part of
+and the line ends in a ``cg:Z:`` string of ``=``, ``X``, ``I`` and ``D`` runs; ``--extend N`` (1..65535, which implies
+``--cigar``) extends every chain beyond its outermost seeds by up to N bases at either end (rule 11).  minimap2 is not needed, and it is not part of
 the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
 tests' restatement in plain Python (tests/map_oracle.py), not against minimap2.  The rules (include/msgpu.h,
 "unitig-to-read mapping"); parameters k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth
 (2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1); cigar (0 / 1)
-is a keyword of ``run`` beside them:
+and extend (0..65535) are keywords of ``run`` beside them:
 
  1. windows: the alphabet, case folding, 2-bit code, canonical key (min(fw, rc) as 2k-bit numbers) and the break at any
     other byte are those of the k-mer filter's rolling window (KfRoll).  A stretch is a maximal run of k-mer start
@@ -95,6 +97,29 @@ is a keyword of ``run`` beside them:
     the fixed part and, per anchor, band + 1 words of script, the
     64-bit offset, the script length, the class list entry, the ``=`` columns behind the segment and the two column
     counts.  Without cigar every byte of every output is as before.
+11. end extension, on request (``extend``; msgpu_map_set_extension).  The parameter is extend = E: 0 is off, 1..65535 the
+    longest flank on either sequence; E > 0 needs cigar = 1 (and so exact = 1), else the run fails with MSGPU_E_ARG naming
+    both.  The penalty is a constant of the rule, P = 8.  (1) Flanks of a chain with anchors a_0..a_{m-1}, oq the oriented
+    query of rule 7, tlen and qlen the lengths, rev byte reversal (no complement: oq is oriented already).  Right:
+    A = target[t_end .. t_end + n), n = min(E, tlen - t_end); B = oq[yE .. yE + m), yE = y_{m-1} + k, m = min(E, qlen - yE).
+    Left: A = rev(target[x_0 - n .. x_0)), n = min(E, x_0); B = rev(oq[y_0 - m .. y_0)), m = min(E, y_0).  (2) The table is
+    rule 10's on (A, n, B, m), rows e = 0..band: the same slide, the same three candidates with the same validity tests
+    (only candidates that stay inside the matrix enter), the same tie order X, D, I.  Nothing of rule 10's end test is used:
+    |m - n| may exceed the band and no row ends the table early.  (3) Every defined cell has x = G_e[k], y = x + k and
+    score = x + y - P * e.  The end cell (e*, k*) is the one with the greatest score; on equal scores the smaller e wins,
+    then the smaller |k|, then the negative k.  Cell (0, 0) always exists with score 2 * G_0[0] >= 0, so the end cell
+    exists, and x* = y* = 0 means "no extension".  A row e with n + m - P * e <= the best score of the rows before it cannot
+    win, nor can a later one: ``rows``, the number of rows an end is charged with, is the first such e, or band + 1.
+    (4) The script is the walk back from (e*, k*) exactly as rule 10 walks back from (d, ks): e* + 1 words, consuming
+    exactly x* bytes of A and y* bytes of B, every ``=`` column equal and every X column unequal; a left flank's columns are
+    written in reverse order.  (5) The chain: its runs are the left columns, rule 10's chain alignment, the right columns,
+    neighbouring runs merged; t_start -= x*_L, t_end += x*_R; the oriented query range grows by y*_L and y*_R and rule 7
+    turns it into forward coordinates; matches, block and nm are counted on the columns; cm, s1, n_anchors, score, the
+    chain's place in the output order and which chains exist are untouched.  The runs consume exactly the new target and
+    query ranges.  (6) With E = 0 every byte is as before.  It follows that a flank whose shorter side matches the longer
+    side's start without an edit is extended to that sequence's end: cell (0, 0) wins.  Rule 9 with E > 0:
+    msgpu_map_batch_bytes_ext adds, per anchor, two ends' descriptors (24 bytes each), end cells (24 bytes each) and
+    band + 1 script words each; the slab is cigar mode's.
 
 Known differences from minimap2, none of which could be checked against the program (it is not installed where this project
 is built):
@@ -111,7 +136,7 @@ is built):
   link, not minimap2's count of ``=`` columns.  With ``--cigar`` the columns are counted on a unit-cost alignment of every
   segment between two seeds (rule 10), not on minimap2's affine-gap alignment, and a segment beyond the band is written
   as a deletion and an insertion;
-* no end extension beyond the outermost seeds.
+* end extension: none without ``--extend``; with it, rule 11 (unit costs, P = 8, no end bonus).
 
 ``Index(targets, k=, w=)`` is a context manager that keeps the targets' store, sketch and index on the device;
 ``run(None, queries, out, index=ix, ...)`` then maps onto it, any number of times, with any parameters but k and w (the
@@ -183,7 +208,7 @@ class Index:
         return False
 
 
-def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, **params):
+def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, extend=0, **params):
     """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
     per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
     ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
@@ -193,7 +218,10 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     are not read, k and w default to the index's, and with ava = 1 ``queries`` is None.  ``cigar`` = 1 (rule 10; it needs
     exact = 1) writes the base-level figures and a ``cg:Z:`` string per line; ``tables`` then also receives ``cigars`` (a list
     of strings, one per line) and ``runs`` (per line the list of len << 4 | BAM code), and the returned dict's ``align``
-    holds the counts and seconds of msgpu_map_astats."""
+    holds the counts and seconds of msgpu_map_astats.  ``extend`` = E > 0 (rule 11; it needs cigar = 1) extends every chain at
+    both ends; the returned dict then has ``extend`` (the fields of msgpu_map_xstats, the time under ``seconds``) and ``tables``
+    receives ``ext``: per line the pair (left end, right end), each (e, k, x, y, score, rows).  The value is set on the context
+    for this run: an ``index`` serves runs with any extend, one after the other."""
     if index is not None:
         params = dict({"k": index.k, "w": index.w}, **params)
     unknown = set(params) - set(DEFAULTS)
@@ -209,6 +237,9 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     qpath = None if queries is None else os.fsencode(queries)
     with (stage_context("map", device, MapError) if index is None else contextlib.nullcontext(index.stage)) as stage:
         prm = _params(dict(p, cigar=cigar))
+        if not 0 <= int(extend) < (1 << 32):
+            raise MapError(_lib.E_ARG, "extend = %d" % int(extend))
+        stage.check(L.msgpu_map_set_extension(stage.ctx, int(extend)))
         with (stage.run(C.byref(prm), os.fsencode(targets), qpath, 0, budget) if index is None else
               stage.run(C.byref(prm), index.handle, qpath, 0, budget, fn="run_index")) as res:
             st = _lib.MapStats()
@@ -221,6 +252,8 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             budget_used = int(L.msgpu_map_result_budget(res))
             ast = _lib.MapAlignStats()
             L.msgpu_map_result_align_stats(res, C.byref(ast))
+            xst = _lib.MapExtStats()
+            L.msgpu_map_result_ext_stats(res, C.byref(xst))
             if tables is not None:
                 cp = C.POINTER(_lib.MapChain)()
                 m = C.c_uint64()
@@ -232,6 +265,11 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
                 L.msgpu_map_result_cigars(res, C.byref(ops), C.byref(off), C.byref(m))
                 tables["runs"] = [[int(ops[j]) for j in range(off[i], off[i + 1])] for i in range(m.value)]
                 tables["cigars"] = ["".join("%d%s" % (r >> 4, "MIDNSHP=X"[r & 15]) for r in runs) for runs in tables["runs"]]
+                if xst.extend:
+                    ep, m = C.POINTER(_lib.ExtEnd)(), C.c_uint64()
+                    L.msgpu_map_result_ext_ends(res, C.byref(ep), C.byref(m))
+                    end = [tuple(int(getattr(ep[i], f)) for f, _ in _lib.ExtEnd._fields_) for i in range(m.value)]
+                    tables["ext"] = list(zip(end[0::2], end[1::2]))
             t1 = time.perf_counter()
             with open(out, "wb") as h:
                 h.write(text)
@@ -240,7 +278,11 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
         timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.MapStats._fields_ if name.endswith("_ms")})
         timings["stage_wall"] = timings.pop("wall")
         timings.update({"file": t_write, "total": time.perf_counter() - t0})
-    return {"params": {name: int(getattr(st.params, name)) for name in DEFAULTS}, "records": [int(x) for x in st.n_records],
+    ext = {}
+    if xst.extend:
+        ext["extend"] = dict({name: int(getattr(xst, name)) for name, t in _lib.MapExtStats._fields_
+                              if t is not C.c_float and name != "reserved"}, seconds={"extend": xst.extend_ms / 1e3})
+    return {**ext, "params": {name: int(getattr(st.params, name)) for name in DEFAULTS}, "records": [int(x) for x in st.n_records],
             "bases": [int(x) for x in st.n_bases], "minimizers": [int(x) for x in st.n_minimizers], "keys": int(st.n_keys),
             "keys_dropped": int(st.n_keys_dropped), "entries_dropped": int(st.n_entries_dropped), "anchors": int(st.n_anchors),
             "n_groups": int(st.n_groups), "groups_kept": int(st.n_groups_kept), "groups_small": int(st.n_groups_small),
@@ -267,6 +309,16 @@ def main(argv):
     if "--cigar" in args:  # (implies --exact)
         args.remove("--cigar")
         cigar = p["exact"] = 1
+    extend = 0
+    if "--extend" in args:  # (implies --cigar)
+        i = args.index("--extend")
+        try:
+            extend = int(args[i + 1])
+            ok = 1 <= extend <= _lib.MAP_EXTEND_MAX
+        except (IndexError, ValueError):
+            ok = False
+        del args[i:i + 2]
+        cigar = p["exact"] = 1
     for name, key in _OPTS.items():
         if name in args:
             i = args.index(name)
@@ -291,7 +343,7 @@ def main(argv):
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, **p)
+    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, extend=extend, **p)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0

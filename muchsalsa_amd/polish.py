@@ -2,6 +2,7 @@
 
     python -m muchsalsa_amd.polish <draft.fa> <reads.fa|fq> <out.fa> [--rounds N] [--min-depth N] [--min-identity N] [--paf F]
             [-k N] [-w N] [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
+            [--extend N]
 
 prints one JSON line of counts and seconds.  Each round maps the reads onto the draft with muchsalsa_amd.mapper in cigar mode
 (its rule 10; the options of the second line are the mapper's) and lets the chains vote; the output of a round is the draft of
@@ -128,12 +129,13 @@ def run_tables(draft, reads, out, chains, runs, device=0, tables=None, timings=N
                 params={name: int(getattr(st.params, name)) for name in DEFAULTS})
 
 
-def run(draft, reads, out, rounds=1, budget_mb=None, device=0, paf=None, tables=None, timings=None, **params):
+def run(draft, reads, out, rounds=1, budget_mb=None, device=0, paf=None, tables=None, timings=None, extend=0, **params):
     """``rounds`` times: mapper.run(draft_i, reads, ..., exact=1, cigar=1) and run_tables on its tables; the output of round i is
     the draft of round i + 1, the last one is ``out``.  Intermediate drafts and PAFs are written beside ``out`` and removed
     afterwards; ``paf`` keeps the last round's PAF.  ``params``: the names of DEFAULTS and of mapper.DEFAULTS (exact and ava are
     the stage's own).  Returns the last round's counts with ``rounds`` (per round ``map`` and ``polish``); ``tables`` and
-    ``timings`` receive the last round's."""
+    ``timings`` receive the last round's.  ``extend`` (0: off) is the mapper's rule 11 parameter for every round's mapping: the
+    reads then vote beyond their outermost seeds too."""
     rounds = int(rounds)
     unknown = set(params) - set(DEFAULTS) - (set(mapper.DEFAULTS) - {"exact", "ava"})
     if unknown or rounds < 1:
@@ -151,7 +153,8 @@ def run(draft, reads, out, rounds=1, budget_mb=None, device=0, paf=None, tables=
             if not last:
                 made.append(target)
             tb, tm = {}, {}
-            mapped = mapper.run(current, reads, paf_r, device=device, tables=tb, budget_mb=budget_mb, cigar=1, exact=1, **theirs)
+            mapped = mapper.run(current, reads, paf_r, device=device, tables=tb, budget_mb=budget_mb, cigar=1, exact=1, extend=extend,
+                                **theirs)
             got = run_tables(current, reads, target, tb["chains"], tb["runs"], device=device, tables=tables if last else None,
                              timings=tm, **own)
             per_round.append({"map": {k: mapped[k] for k in ("chains", "anchors", "pairs", "capped")}, "polish": got})
@@ -189,6 +192,15 @@ def main(argv):
         ok = ok and i + 1 < len(args)
         paf = args[i + 1] if i + 1 < len(args) else None
         del args[i:i + 2]
+    extend = 0
+    if "--extend" in args:
+        i = args.index("--extend")
+        try:
+            extend = int(args[i + 1])
+            ok = ok and 1 <= extend <= _lib.MAP_EXTEND_MAX
+        except (IndexError, ValueError):
+            ok = False
+        del args[i:i + 2]
     rounds = p.pop("rounds", 1)
     q = dict(mapper.DEFAULTS, **dict(DEFAULTS, **p))
     ok = ok and 4 <= q["k"] <= 32 and 1 <= q["w"] <= 64 and q["max_occ"] >= 1 and 1 <= q["band"] <= 127
@@ -198,7 +210,7 @@ def main(argv):
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], rounds=rounds, budget_mb=budget, paf=paf, timings=timings, **p)
+    out = run(args[0], args[1], args[2], rounds=rounds, budget_mb=budget, paf=paf, timings=timings, extend=extend, **p)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0

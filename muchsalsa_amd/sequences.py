@@ -259,3 +259,23 @@ class SeqStore:
             words = np.zeros(need.value, dtype="<u4")
         self._check(rc)
         return dist, off, words[:need.value]
+
+    def extend_ends(self, d_a_ptr, d_b_ptr, pairs, band, reverse=False):
+        """The mapper's rule 11 on pairs of flanks (msgpu_extend_ends) -> (ends, off, words): ends[p] is the end cell (e, k, x,
+        y, score, rows), pair p owns words[off[p]:off[p + 1]], e + 1 of them in edit_script's format.  ``reverse``: every flank
+        is read backwards, and a_off / b_off name the byte behind it."""
+        from ._lib import ALIGN_PAIR_DTYPE, EXT_END_DTYPE, E_ARG
+        pairs = np.ascontiguousarray(pairs, dtype=ALIGN_PAIR_DTYPE)
+        ends = np.zeros(len(pairs), dtype=EXT_END_DTYPE)
+        off = np.zeros(len(pairs) + 1, dtype="<u8")
+        words = np.zeros(max(1, 4 * len(pairs)), dtype="<u4")
+        need = C.c_uint64()
+        for _ in range(2):  # (a second call with room when the first guess was too small)
+            rc = self._L.msgpu_extend_ends(self._h, C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), pairs.ctypes.data, len(pairs),
+                                           int(band), 1 if reverse else 0, ends.ctypes.data, off.ctypes.data, words.ctypes.data,
+                                           len(words), C.byref(need))
+            if rc != E_ARG or need.value <= len(words):
+                break
+            words = np.zeros(need.value, dtype="<u4")
+        self._check(rc)
+        return ends, off, words[:need.value]
