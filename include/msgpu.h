@@ -1287,7 +1287,28 @@ void        msgpu_ug_result_free(msgpu_ug_result *r);
  *     untouched.  The runs consume exactly the new target and query ranges.  (6) With E = 0 every byte is as before.  It
  *     follows that a flank whose shorter side matches the longer side's start without an edit is extended to that
  *     sequence's end: cell (0, 0) wins.  Rule 9 with E > 0: msgpu_map_batch_bytes_ext adds, per anchor, two ends' descriptors
- *     (24 bytes each), end cells (24 bytes each) and band + 1 script words each; the slab is cigar mode's. */
+ *     (24 bytes each), end cells (24 bytes each) and band + 1 script words each; the slab is cigar mode's.
+ * 12. primaries, secondaries and mapping quality, on request (msgpu_map_set_ranking; off on a new context; it needs no other
+ *     mode: seed, exact, cigar, ava and extend all combine with it).  The chains of one query record, over all targets and
+ *     both strands, with their indices in output order (rule 8), are ranked among themselves.  For a chain c:
+ *     len(c) = q_end - q_start of rule 7's forward query range, and ov(c, p) = max(0, min(q_end_c, q_end_p) -
+ *     max(q_start_c, q_start_p)).  Rule 11 changes no rank: rule 12 reads the ranges as rule 7 leaves them, before any
+ *     extension.  (1) Visiting order: by (score descending, output index ascending).  (2) A visited chain c is compared with
+ *     the primaries visited before it, in visiting order: the first primary p with 2 * ov(c, p) > min(len(c), len(p)) makes c
+ *     secondary with parent(c) = p; if there is none, c is primary and parent(c) = c.  The mask level is one half and the
+ *     comparison is strict.  (3) Of a primary p: sub(p) is the greatest score among its secondaries, 0 if it has none;
+ *     n_secondary(p) is the number of its secondaries s with 10 * score(s) >= 9 * score(p); both are 0 for a secondary.
+ *     (4) mapq of a primary with s1 = score(p) > 0: (60 * (s1 - sub) * min(n_anchors, 10)) / (10 * s1), the products in 64
+ *     bits, integer division, clamped to 0..60; 0 if s1 <= 0; 0 for a secondary.  (5) With ranking on column 12 is mapq and
+ *     the tags are tp:A:P or tp:A:S, cm:i, s1:i, s2:i:<sub>, then NM and cg as before; line order, every other column, the
+ *     chain table and the run tables are untouched.  (6) With ranking off every byte is as before: 255, no tp, no s2.
+ *     (7) A query record's chains never span two batches (rule 9), so the rule runs per batch; parent is an index into the
+ *     whole run's chain table (the batch's base is added on the device); with ranking on a run has fewer than 2^32 chains,
+ *     else MSGPU_E_ARG.  msgpu_map_batch_bytes_rank bounds a batch (rule 9's cut and bytes_bound use it; it equals
+ *     msgpu_map_batch_bytes_ext for ranking = 0): per anchor it adds 104 bytes (seven words of segment heads, numbers,
+ *     starts, class flags and their scans, four of class lists and sort bounds, parent, n_secondary, a 64-bit sub, the row,
+ *     two 64-bit sort keys, 12 bytes of the list class's stretch) and a fixed 24 * 256 bytes.  The mask level 1/2, the ratio
+ *     0.9 and the mapq formula are choices modelled on minimap2's, unchecked on real reads. */
 typedef struct msgpu_mapctx msgpu_mapctx; /* a device context of the stage */
 typedef struct msgpu_map_result msgpu_map_result;
 typedef struct msgpu_map_params {
@@ -1416,6 +1437,37 @@ int         msgpu_map_set_extension(msgpu_mapctx *ctx, uint32_t extend);
 int         msgpu_map_result_ext_stats(const msgpu_map_result *r, msgpu_map_xstats *out);
 int         msgpu_map_result_ext_ends(const msgpu_map_result *r, const msgpu_ext_end **ends, uint64_t *n);
 uint64_t    msgpu_map_batch_bytes_ext(const msgpu_map_params *params, uint32_t extend, uint64_t n_anchors, uint64_t n_query_bases);
+/* Rule 12.  msgpu_map_set_ranking switches it on (on != 0) or off for every later msgpu_map_run / msgpu_map_run_index, until it
+ * is set again.  msgpu_map_result_ranks: entry i belongs to line i; *n = 0 when ranking was off.  msgpu_map_result_rank_stats
+ * gives zeros when it was off.  msgpu_map_rank_tables is the table-level entry (as msgpu_extend_ends is rule 11's): rule 12 on
+ * n chains of the host in output order, copied to the device; parent is relative to that table; of a chain only query,
+ * n_anchors, score, q_start and q_end are read.  query must not decrease and q_start <= q_end, else MSGPU_E_ARG naming the
+ * first bad chain: a device pass, complete before any ranking kernel runs.  n = 0 is fine.  msgpu_map_rank_tables_stats: the
+ * counts of the context's last msgpu_map_rank_tables (zeros after an error).
+ * MSGPU_MAP_RANK_LDS: the primaries of a segment of more than 64 chains that the list kernel keeps in LDS; the ones beyond lie
+ * in the batch arena, and the segment is counted in n_segments_spilled. */
+#define MSGPU_MAP_RANK_LDS 512u
+typedef struct msgpu_map_rank { /* in output order: entry i belongs to chain i */
+  uint32_t parent;      /* the chain's primary; its own index for a primary */
+  int32_t  sub;         /* rule 12.3 */
+  uint32_t n_secondary; /* rule 12.3 */
+  uint32_t mapq;        /* rule 12.4 */
+} msgpu_map_rank;
+typedef struct msgpu_map_rstats { /* rule 12, summed over the batches; a segment is the chains of one query record */
+  uint32_t ranking, lds_primaries;                                   /* the switch; MSGPU_MAP_RANK_LDS */
+  uint64_t n_segments, n_primaries, n_secondaries, n_mapq0;          /* n_mapq0: chains with mapq 0, the secondaries among them */
+  uint64_t largest_segment;
+  uint64_t n_segments_single, n_segments_wave, n_segments_list;      /* one chain; 2..64 (a wavefront); more (the list kernel) */
+  uint64_t n_segments_spilled;                                       /* list segments with more than lds_primaries primaries */
+  float    rank_ms, reserved2;                                       /* device, by events */
+} msgpu_map_rstats;
+int         msgpu_map_set_ranking(msgpu_mapctx *ctx, int on);
+int         msgpu_map_result_ranks(const msgpu_map_result *r, const msgpu_map_rank **ranks, uint64_t *n);
+int         msgpu_map_result_rank_stats(const msgpu_map_result *r, msgpu_map_rstats *out);
+uint64_t    msgpu_map_batch_bytes_rank(const msgpu_map_params *params, uint32_t extend, uint32_t ranking, uint64_t n_anchors,
+                                       uint64_t n_query_bases);
+int         msgpu_map_rank_tables(msgpu_mapctx *ctx, const msgpu_map_chain *chains, uint64_t n, msgpu_map_rank *ranks_out);
+int         msgpu_map_rank_tables_stats(const msgpu_mapctx *ctx, msgpu_map_rstats *out);
 void        msgpu_map_result_free(msgpu_map_result *r);
 
 /* ---- pileup consensus: polishing a draft from the mapper's run tables ------------------------------
@@ -1433,9 +1485,14 @@ void        msgpu_map_result_free(msgpu_map_result *r);
  *     violation reported is that of the smallest chain index, and of that chain the first in the order (a) .. (i):
  *     MSGPU_E_ARG, the text "chain <i>: <what>".  The check is a device pass that publishes the smallest bad chain through the
  *     scalar block, and it is complete before any kernel walks a run: a bad table ends in an error, never in a fault.
+ *     In ranked form (msgpu_pl_run_ranked) a check (j) is added and reported last: the rank row's parent is in range and names
+ *     a chain of the same query record that is its own parent, and mapq <= 60; otherwise "chain <i>: rank".
  *  2. voters.  A chain is eligible iff matches * 100 >= min_identity * block.  Per query record the voter is the eligible
  *     chain with the greatest score, then the greatest block, then the first in table order.  Every other chain is ignored
- *     and counted.
+ *     and counted.  Ranked form (msgpu_pl_run_ranked, with the mapper's rule 12 rows): a chain votes iff it is eligible,
+ *     primary (parent == its own index) and mapq >= min_mapq.  So a read may have several voters (a split alignment votes
+ *     with every part), a secondary never votes, and a read placed equally on two repeat copies (mapq 0) votes only at
+ *     min_mapq = 0.  Everything behind the voters' spans is the same in both forms.
  *  3. oriented query.  Column j of a chain reads byte q_start + j_q of the query for strand 0 (j_q: the query bases that the
  *     columns in front of j consume); for strand 1 the oriented query is MSGPU_COPY_REVCOMP's of the whole record (reversed,
  *     A <-> T and C <-> G in upper case, every other byte as it is), and the chain starts at qlen - q_end in it.  The byte is
@@ -1494,6 +1551,11 @@ const char *msgpu_pl_last_error(const msgpu_plctx *ctx);
 int         msgpu_pl_run(msgpu_plctx *ctx, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
                          const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags,
                          msgpu_pl_result **out);
+/* The stage with rule 2 in ranked form: ranks holds n_chains rows of the mapper's rule 12 (msgpu_map_result_ranks or
+ * msgpu_map_rank_tables; parent indexes this chain table), checked by rule 1 (j).  msgpu_pl_run is untouched by it. */
+int         msgpu_pl_run_ranked(msgpu_plctx *ctx, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
+                                const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off,
+                                const msgpu_map_rank *ranks, uint32_t min_mapq, uint32_t flags, msgpu_pl_result **out);
 const char *msgpu_pl_result_text(const msgpu_pl_result *r, uint64_t *len);
 int         msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out);
 int         msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **records, uint64_t *n);

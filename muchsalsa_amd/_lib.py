@@ -258,6 +258,24 @@ MAP_EXTEND_PENALTY = 8   # MSGPU_MAP_EXTEND_PENALTY
 EXT_END_DTYPE = np.dtype([("e", "<u4"), ("k", "<i4"), ("x", "<u4"), ("y", "<u4"), ("score", "<i4"), ("rows", "<u4")])
 
 
+class MapRank(C.Structure):  # msgpu_map_rank
+    _fields_ = [("parent", C.c_uint32), ("sub", C.c_int32), ("n_secondary", C.c_uint32), ("mapq", C.c_uint32)]
+
+
+class MapRankStats(C.Structure):  # msgpu_map_rstats
+    _fields_ = ([("ranking", C.c_uint32), ("lds_primaries", C.c_uint32)] +
+                [(n, C.c_uint64) for n in ("n_segments", "n_primaries", "n_secondaries", "n_mapq0", "largest_segment",
+                                           "n_segments_single", "n_segments_wave", "n_segments_list", "n_segments_spilled")] +
+                [("rank_ms", C.c_float), ("reserved2", C.c_float)])
+
+
+MAP_RANK_LDS = 512   # MSGPU_MAP_RANK_LDS
+MAP_CHAIN_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("strand", "<u4"), ("n_anchors", "<u4"), ("score", "<i4"), ("nm", "<u4"),
+                            ("q_start", "<u4"), ("q_end", "<u4"), ("t_start", "<u4"), ("t_end", "<u4"), ("matches", "<u4"),
+                            ("block", "<u4")])
+MAP_RANK_DTYPE = np.dtype([("parent", "<u4"), ("sub", "<i4"), ("n_secondary", "<u4"), ("mapq", "<u4")])
+
+
 class MapBatch(C.Structure):  # msgpu_map_batch
     _fields_ = [("first_query", C.c_uint32), ("n_queries", C.c_uint32)] + [
         (n, C.c_uint64) for n in ("n_anchors", "n_query_bases", "n_groups", "n_chains", "n_pairs", "bytes_bound", "bytes_peak")]
@@ -544,6 +562,12 @@ SYMBOLS = [
     ("msgpu_map_result_ext_stats", C.c_int, [C.c_void_p, C.POINTER(MapExtStats)]),
     ("msgpu_map_result_ext_ends", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(ExtEnd)), C.POINTER(C.c_uint64)]),
     ("msgpu_map_batch_bytes_ext", C.c_uint64, [C.POINTER(MapParams), C.c_uint32, C.c_uint64, C.c_uint64]),
+    ("msgpu_map_set_ranking", C.c_int, [C.c_void_p, C.c_int]),
+    ("msgpu_map_result_ranks", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapRank)), C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_rank_stats", C.c_int, [C.c_void_p, C.POINTER(MapRankStats)]),
+    ("msgpu_map_batch_bytes_rank", C.c_uint64, [C.POINTER(MapParams), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    ("msgpu_map_rank_tables", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("msgpu_map_rank_tables_stats", C.c_int, [C.c_void_p, C.POINTER(MapRankStats)]),
     ("msgpu_map_result_free", None, [C.c_void_p]),
     ("msgpu_pl_default_params", None, [C.POINTER(PlParams)]),
     ("msgpu_pl_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -551,6 +575,8 @@ SYMBOLS = [
     ("msgpu_pl_last_error", C.c_char_p, [C.c_void_p]),
     ("msgpu_pl_run", C.c_int, [C.c_void_p, C.POINTER(PlParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("msgpu_pl_run_ranked", C.c_int, [C.c_void_p, C.POINTER(PlParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("msgpu_pl_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msgpu_pl_result_stats", C.c_int, [C.c_void_p, C.POINTER(PlStats)]),
     ("msgpu_pl_result_records", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(PlRecord)), C.POINTER(C.c_uint64)]),

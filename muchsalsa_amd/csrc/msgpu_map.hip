@@ -21,6 +21,9 @@
 //                  against a forward and a reverse-complemented copy of the queries (the existing gather)
 //   cigar mode     rule 10 behind the distances: the scripts' offsets (a scan), launch_edit_script_pairs (msgpu_seq.hip),
 //                  k_mp_columns per pair, two segmented reductions and k_mp_cigar per chain; the host merges the runs
+//   ranking        rule 12, on request, behind k_mp_table: the chains of a query record are a segment (k_rk_heads, a scan);
+//                  k_rk_wave ranks a segment of at most 64 chains in one wavefront, a lane per chain; k_rk_list walks a longer
+//                  one in sorted order against its list of primaries (LDS, then the arena); k_rk_figures and k_rk_rows finish
 // Integers only.  Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
@@ -553,6 +556,203 @@ __global__ __launch_bounds__(256) void k_mp_capped(const uint32_t *dist, uint32_
   mp_count(i < n && dist[i] > band, capped);
 }
 
+// ---- rule 12: primaries, secondaries and mapping quality over the chains of a query record ("segment": the chains of one
+// query record, consecutive in the table).  k_rk_heads marks where `query` changes (and, for a table from the host, looks for
+// the first chain that breaks the table's order), a scan numbers the segments, k_rk_classify settles the segments of one chain
+// and splits the others into those of at most 64 chains (k_rk_wave: a lane per chain) and the longer ones (k_rk_list: the
+// chains in 12.1's order by one segmented sort, the primaries found so far in LDS and, beyond MSGPU_MAP_RANK_LDS of them, in
+// the segment's stretch of the arena).  Both write `parent` only; k_rk_figures gathers sub and n_secondary per primary (an
+// integer maximum and an integer sum: no order reaches the output) and k_rk_rows writes the rows in output order.
+
+enum { RK_PRIM = 0, RK_SEC, RK_MAPQ0, RK_LARGEST, RK_SINGLE, RK_WAVE, RK_LIST, RK_SPILL, RK_BAD, RK_COUNT };
+
+struct RkPrim { // a primary of the segment being visited
+  uint32_t qs, qe, idx;
+};
+
+// 12.2's test of a chain's query range against a primary's: 2 * ov > min(len, len)
+__device__ __forceinline__ bool rk_masks(uint32_t cs, uint32_t ce, uint32_t ps, uint32_t pe) {
+  const uint32_t lo = max(cs, ps), hi = min(ce, pe);
+  const uint64_t ov = hi > lo ? hi - lo : 0;
+  return 2 * ov > min(ce - cs, pe - ps);
+}
+
+__device__ __forceinline__ uint64_t rk_key(int32_t score, uint32_t i) { // descending: (score descending, index ascending)
+  return (static_cast<uint64_t>(static_cast<uint32_t>(score) ^ 0x80000000u) << 32) | (0xffffffffu - i);
+}
+
+__global__ __launch_bounds__(256) void k_rk_heads(const msgpu_map_chain *chains, uint32_t n, int validate, uint32_t *head, kf_ull *bad) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t q = chains[i].query, qp = i ? chains[i - 1].query : 0;
+  head[i] = !i || q != qp;
+  if (validate && ((i && q < qp) || chains[i].q_start > chains[i].q_end)) atomicMin(bad, static_cast<kf_ull>(i));
+}
+
+__global__ __launch_bounds__(256) void k_rk_starts(const uint32_t *head, const uint32_t *segid, uint32_t n, uint32_t *start) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (head[i]) start[segid[i]] = i;
+  if (i == n - 1) start[segid[n]] = n;
+}
+
+__global__ __launch_bounds__(256) void k_rk_classify(const uint32_t *start, uint32_t n_seg, uint32_t *flag_wave, uint32_t *flag_list,
+                                                     uint32_t *parent, kf_ull *cnt) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t n = s < n_seg ? start[s + 1] - start[s] : 0;
+  if (s < n_seg) {
+    flag_wave[s] = n >= 2 && n <= 64;
+    flag_list[s] = n > 64;
+    if (n == 1) parent[start[s]] = start[s]; // settled: a primary without a secondary
+  }
+  mp_count(n == 1, cnt + RK_SINGLE);
+  mp_count(n >= 2 && n <= 64, cnt + RK_WAVE);
+  mp_count(n > 64, cnt + RK_LIST);
+  uint32_t big = n;
+  for (int o = 32; o > 0; o >>= 1) big = max(big, static_cast<uint32_t>(__shfl_xor(static_cast<int>(big), o)));
+  if ((threadIdx.x & 63) == 0 && big) atomicMax(cnt + RK_LARGEST, static_cast<kf_ull>(big));
+}
+
+__global__ __launch_bounds__(256) void k_rk_lists(const uint32_t *start, uint32_t n_seg, const uint32_t *flag_wave, const uint32_t *flag_list,
+                                                  const uint32_t *pos_wave, const uint32_t *pos_list, uint32_t *list_wave,
+                                                  uint32_t *list_list, uint32_t *seg_begin, uint32_t *seg_end) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= n_seg) return;
+  if (flag_wave[s]) list_wave[pos_wave[s]] = s;
+  if (flag_list[s]) {
+    list_list[pos_list[s]] = s;
+    seg_begin[pos_list[s]] = start[s];
+    seg_end[pos_list[s]]   = start[s + 1];
+  }
+}
+
+// segments of 2 to 64 chains: a wavefront per segment.  Every lane counts the chains in front of its own in 12.1's order, the
+// chains move to the lane of their rank, and the visit is n uniform steps: step t gives chain t's range to the primaries in the
+// lanes below t, and the lowest lane that answers is the first primary in visiting order
+__global__ __launch_bounds__(256) void k_rk_wave(const msgpu_map_chain *chains, const uint32_t *start, const uint32_t *list, uint32_t n_list,
+                                                 uint32_t *parent) {
+  const uint32_t wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (wv >= n_list) return; // (whole wavefronts leave)
+  const uint32_t s = list[wv], s0 = start[s], n = start[s + 1] - s0;
+  const bool     have = lane < n;
+  int            score = 0, qs = 0, qe = 0;
+  if (have) {
+    score = chains[s0 + lane].score;
+    qs    = static_cast<int>(chains[s0 + lane].q_start);
+    qe    = static_cast<int>(chains[s0 + lane].q_end);
+  }
+  uint32_t r = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    const int sj = __shfl(score, static_cast<int>(j));
+    r += sj > score || (sj == score && j < lane);
+  }
+  if (!have) r = lane; // (the ranks of the chains are 0..n-1: the other lanes keep their place)
+  const int to = static_cast<int>(r * 4);
+  qs = __builtin_amdgcn_ds_permute(to, qs);
+  qe = __builtin_amdgcn_ds_permute(to, qe);
+  const uint32_t idx = static_cast<uint32_t>(__builtin_amdgcn_ds_permute(to, static_cast<int>(lane))); // lane r holds chain idx
+  bool     prim = false;
+  uint32_t par = lane;
+  for (uint32_t t = 0; t < n; ++t) {
+    const uint32_t bs = static_cast<uint32_t>(__shfl(qs, static_cast<int>(t))), be = static_cast<uint32_t>(__shfl(qe, static_cast<int>(t)));
+    const uint64_t who = __ballot(lane < t && prim && rk_masks(bs, be, static_cast<uint32_t>(qs), static_cast<uint32_t>(qe)));
+    if (lane == t) {
+      if (who) par = static_cast<uint32_t>(__ffsll(static_cast<long long>(who))) - 1;
+      else prim = true;
+    }
+  }
+  const uint32_t pidx = static_cast<uint32_t>(__shfl(static_cast<int>(idx), static_cast<int>(par)));
+  if (have) parent[s0 + idx] = s0 + pidx;
+}
+
+__global__ __launch_bounds__(256) void k_rk_keys(const msgpu_map_chain *chains, uint32_t n, uint64_t *keys) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) keys[i] = rk_key(chains[i].score, i);
+}
+
+// segments of more than 64 chains: a wavefront (a workgroup of one) per segment walks the chains in 12.1's order, 64 at a time
+// in registers.  The primaries found so far are a list in visiting order: entry e lies in LDS for e < MSGPU_MAP_RANK_LDS, else
+// at far[e], the segment's own stretch of `spill` (entry e of a segment of n chains has e < n).  A visited chain reads the list
+// 64 entries per ballot and stops at the first ballot that is not empty: its lowest lane is the parent
+__global__ __launch_bounds__(64) void k_rk_list(const msgpu_map_chain *chains, const uint32_t *start, const uint32_t *list,
+                                                const uint64_t *sorted, uint32_t *parent, RkPrim *spill, kf_ull *spilled) {
+  __shared__ RkPrim s_p[MSGPU_MAP_RANK_LDS];
+  const uint32_t s = list[blockIdx.x], s0 = start[s], n = start[s + 1] - s0, lane = threadIdx.x;
+  RkPrim        *far = spill + s0;
+  uint32_t       np = 0;
+  for (uint32_t b0 = 0; b0 < n; b0 += 64) {
+    const bool     have = b0 + lane < n;
+    const uint32_t idx = have ? 0xffffffffu - static_cast<uint32_t>(sorted[s0 + b0 + lane]) : 0;
+    const int      qs = have ? static_cast<int>(chains[idx].q_start) : 0, qe = have ? static_cast<int>(chains[idx].q_end) : 0;
+    const uint32_t m = min(64u, n - b0);
+    for (uint32_t t = 0; t < m; ++t) {
+      const uint32_t bs = static_cast<uint32_t>(__shfl(qs, static_cast<int>(t))), be = static_cast<uint32_t>(__shfl(qe, static_cast<int>(t)));
+      const uint32_t bi = static_cast<uint32_t>(__shfl(static_cast<int>(idx), static_cast<int>(t)));
+      uint32_t       par = bi;
+      bool           found = false;
+      for (uint32_t e0 = 0; e0 < np && !found; e0 += 64) {
+        const uint32_t e = e0 + lane;
+        RkPrim         p{0, 0, 0};
+        if (e < np) p = e < MSGPU_MAP_RANK_LDS ? s_p[e] : far[e];
+        const uint64_t who = __ballot(e < np && rk_masks(bs, be, p.qs, p.qe));
+        if (who) {
+          par   = static_cast<uint32_t>(__shfl(static_cast<int>(p.idx), __ffsll(static_cast<long long>(who)) - 1));
+          found = true;
+        }
+      }
+      if (!found) { // (uniform: `who` is a ballot) a new primary, behind every earlier one
+        if (lane == 0) {
+          if (np < MSGPU_MAP_RANK_LDS) s_p[np] = RkPrim{bs, be, bi};
+          else far[np] = RkPrim{bs, be, bi};
+        }
+        ++np;
+        __syncthreads();
+      }
+      if (lane == 0) parent[bi] = par;
+    }
+  }
+  if (lane == 0 && np > MSGPU_MAP_RANK_LDS) atomicAdd(spilled, 1ull);
+}
+
+// 12.3: sub as the greatest (score biased to unsigned) + 1, so that 0 is "no secondary"
+__global__ __launch_bounds__(256) void k_rk_figures(const msgpu_map_chain *chains, const uint32_t *parent, uint32_t n, kf_ull *sub,
+                                                    uint32_t *n_sec) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = parent[i];
+  if (p == i) return;
+  const int32_t sc = chains[i].score;
+  atomicMax(sub + p, static_cast<kf_ull>(static_cast<uint32_t>(sc) ^ 0x80000000u) + 1);
+  if (10ll * sc >= 9ll * chains[p].score) atomicAdd(n_sec + p, 1u);
+}
+
+// 12.4 and the rows, in output order; `base`: the chains of the run in front of this table
+__global__ __launch_bounds__(256) void k_rk_rows(const msgpu_map_chain *chains, const uint32_t *parent, const kf_ull *sub, const uint32_t *n_sec,
+                                                 uint32_t n, uint32_t base, msgpu_map_rank *rows, kf_ull *cnt) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  bool           prim = false, zero = false;
+  if (i < n) {
+    const uint32_t p = parent[i];
+    msgpu_map_rank r{base + p, 0, 0, 0};
+    prim = p == i;
+    if (prim) {
+      const long long s1 = chains[i].score;
+      r.sub         = sub[i] ? static_cast<int32_t>(static_cast<uint32_t>(sub[i] - 1) ^ 0x80000000u) : 0;
+      r.n_secondary = n_sec[i];
+      if (s1 > 0) {
+        const long long v = (60ll * (s1 - r.sub) * min(chains[i].n_anchors, 10u)) / (10ll * s1);
+        r.mapq = static_cast<uint32_t>(v < 0 ? 0 : v > 60 ? 60 : v);
+      }
+    }
+    zero    = r.mapq == 0;
+    rows[i] = r;
+  }
+  mp_count(prim, cnt + RK_PRIM);
+  mp_count(i < n && !prim, cnt + RK_SEC);
+  mp_count(i < n && zero, cnt + RK_MAPQ0);
+}
+
 } // namespace msgpu
 
 using namespace msgpu;
@@ -564,6 +764,8 @@ struct msgpu_mapctx : msgpu::StageCtx {
   ScalarBlock      sc;
   msgpu_map_index *index = nullptr; // the one index the context holds (its targets lie in one of seq's two stores)
   uint32_t         extend = 0;      // rule 11's parameter (msgpu_map_set_extension)
+  uint32_t         ranking = 0;     // rule 12's switch (msgpu_map_set_ranking)
+  msgpu_map_rstats table_rstats{};  // of the last msgpu_map_rank_tables
   ~msgpu_mapctx();
   int open() {
     const int rc = msgpu_seq_create(device, &seq.p);
@@ -590,6 +792,9 @@ struct msgpu_map_result {
   std::vector<msgpu_ext_end> x_ends;
   std::vector<uint32_t>      x_words;
   std::vector<uint64_t>      x_woff{0};
+  // rule 12.  A row per chain when ranking was on
+  msgpu_map_rstats            rstats{};
+  std::vector<msgpu_map_rank> ranks;
 };
 
 namespace {
@@ -732,15 +937,20 @@ void mp_runs(const msgpu_map_result &r, uint64_t i, std::vector<std::pair<uint32
 }
 
 void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_seqfile *Q, bool exact, std::string &out,
-               const std::vector<std::pair<uint32_t, uint64_t>> *runs = nullptr) {
+               const std::vector<std::pair<uint32_t, uint64_t>> *runs = nullptr, const msgpu_map_rank *rk = nullptr, bool primary = false) {
   char buf[224];
   out += msgpu_seq_name(Q, ch.query);
   int n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%c\t", static_cast<kf_ull>(msgpu_seq_length(Q, ch.query)), ch.q_start, ch.q_end,
                    ch.strand ? '-' : '+');
   out.append(buf, n);
   out += msgpu_seq_name(T, ch.target);
-  n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%u\t%u\t255\tcm:i:%u\ts1:i:%d", static_cast<kf_ull>(msgpu_seq_length(T, ch.target)),
-               ch.t_start, ch.t_end, ch.matches, ch.block, ch.n_anchors, ch.score);
+  if (rk) // rule 12.5
+    n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%u\t%u\t%u\ttp:A:%c\tcm:i:%u\ts1:i:%d\ts2:i:%d",
+                 static_cast<kf_ull>(msgpu_seq_length(T, ch.target)), ch.t_start, ch.t_end, ch.matches, ch.block, rk->mapq, primary ? 'P' : 'S',
+                 ch.n_anchors, ch.score, rk->sub);
+  else
+    n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%u\t%u\t255\tcm:i:%u\ts1:i:%d", static_cast<kf_ull>(msgpu_seq_length(T, ch.target)),
+                 ch.t_start, ch.t_end, ch.matches, ch.block, ch.n_anchors, ch.score);
   out.append(buf, n);
   if (exact) {
     n = snprintf(buf, sizeof(buf), "\tNM:i:%u", ch.nm);
@@ -789,28 +999,37 @@ constexpr uint64_t MP_BYTES_ANCHOR_CIGAR = 4 + 8 + 4 + 4 + 4 + 4 + 3 * 4, MP_BYT
 // the counter of inconsistent ends and the rounding of the three arrays (the slab is cigar mode's, allocated once)
 constexpr uint64_t MP_BYTES_ANCHOR_EXT = 2 * (sizeof(msgpu_align_pair) + sizeof(msgpu_ext_end)), MP_BYTES_FIXED_EXT = 4 * DevArena::ALIGN;
 static_assert(sizeof(msgpu_ext_end) == 24, "rule 11's bytes per end");
+// rule 12 (ranking on), per chain, and a chain holds an anchor of its own: head, segment number, segment start, the two class
+// flags and their scans (seven words); the two class lists and the sort's segment bounds (four words); parent, n_secondary
+// and the 64-bit sub; the row; the sort keys twice; the primary's entry in the list class's stretch.  The sort is
+// segmented_radix_sort_keys over at most as many keys as rule 6's, inside MP_BYTES_ANCHOR_TMP as that one is.  Fixed: the
+// counters and the rounding of the nineteen arrays, each with at most one more word than items
+constexpr uint64_t MP_BYTES_ANCHOR_RANK = 7 * 4 + 4 * 4 + 4 + 4 + 8 + sizeof(msgpu_map_rank) + 2 * 8 + sizeof(RkPrim);
+constexpr uint64_t MP_BYTES_FIXED_RANK = 24 * DevArena::ALIGN;
+static_assert(sizeof(msgpu_map_rank) == 16 && sizeof(RkPrim) == 12 && RK_COUNT * 8 <= DevArena::ALIGN, "rule 12's bytes per chain");
 
-uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint32_t extend, uint64_t n_anchors, uint64_t n_query_bases) {
+uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, uint64_t n_anchors, uint64_t n_query_bases) {
   const bool     exact = prm.exact != 0, cigar = exact && prm.cigar != 0;
   const uint64_t band1 = static_cast<uint64_t>(prm.band < 0 ? 0 : prm.band > 127 ? 127 : prm.band) + 1;
   const bool     ext = cigar && extend != 0;
   const uint64_t per = MP_BYTES_ANCHOR + MP_BYTES_ANCHOR_TMP + (exact ? MP_BYTES_ANCHOR_EXACT : 0) +
-                       (cigar ? MP_BYTES_ANCHOR_CIGAR + 4 * band1 : 0) + (ext ? MP_BYTES_ANCHOR_EXT + 2 * 4 * band1 : 0);
+                       (cigar ? MP_BYTES_ANCHOR_CIGAR + 4 * band1 : 0) + (ext ? MP_BYTES_ANCHOR_EXT + 2 * 4 * band1 : 0) +
+                       (ranking ? MP_BYTES_ANCHOR_RANK : 0);
   // beyond every device, and no overflow: per < 2^8 (2^10 in cigar mode: band + 1 words of script per anchor beside the rest;
   // below 2^12 with rule 11's two more scripts, descriptors and end cells)
   if (n_anchors >= (1ull << (cigar ? 50 : 54)) || n_query_bases >= (1ull << 62)) return ~0ull;
   const uint64_t fixed = MP_BYTES_FIXED + (cigar ? MP_BYTES_FIXED_CIGAR + DevArena::aligned(4 * edit_script_slab_words(edit_script_slots(), static_cast<uint32_t>(band1 - 1))) : 0) +
-                         (ext ? MP_BYTES_FIXED_EXT : 0);
+                         (ext ? MP_BYTES_FIXED_EXT : 0) + (ranking ? MP_BYTES_FIXED_RANK : 0);
   return fixed + per * n_anchors + (exact ? 2 * n_query_bases : 0);
 }
 
 // The greedy cut of rule 9 over the prefix sums of the records' anchors and bases (n + 1 entries each): a binary search per
 // batch for the last record that still fits.  Returns the first record that fits no batch on its own, or n.
-uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
+uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
   for (uint32_t first = 0; first < n;) {
     auto fits = [&](uint32_t end) {
       const uint64_t a = apre[end] - apre[first];
-      return a < (1ull << 31) && mp_batch_bytes(prm, extend, a, bpre[end] - bpre[first]) <= budget;
+      return a < (1ull << 31) && mp_batch_bytes(prm, extend, ranking, a, bpre[end] - bpre[first]) <= budget;
     };
     if (!fits(first + 1)) return first;
     uint32_t lo = first + 1, hi = n; // the last end that fits
@@ -824,7 +1043,7 @@ uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, const uint64_t *ap
     b.n_queries     = lo - first;
     b.n_anchors     = apre[lo] - apre[first];
     b.n_query_bases = bpre[lo] - bpre[first];
-    b.bytes_bound   = mp_batch_bytes(prm, extend, b.n_anchors, b.n_query_bases);
+    b.bytes_bound   = mp_batch_bytes(prm, extend, ranking, b.n_anchors, b.n_query_bases);
     out.push_back(b);
     first = lo;
   }
@@ -846,7 +1065,98 @@ struct MpRun { // what stays on the device for the whole run (rule 9), as a batc
   StageClock             &clock;
   msgpu_map_result       *res;
   uint32_t                extend; // rule 11's parameter
+  uint32_t                ranking; // rule 12's switch
 };
+
+// ---- rule 12 on a chain table that lies on the device
+
+// n chains in output order -> n rows; `base` is added to every parent; `validate`: the table comes from the host and the first
+// chain that breaks its order is an error before any ranking kernel runs (*bad: that chain, else ~0).  cnt: RK_COUNT
+// counters on the host, valid after the caller's next synchronisation; the segments are added to S at once.
+int mp_rank(msgpu_mapctx *c, DevArena &B, StageClock &clock, const msgpu_map_chain *d_chains, uint32_t n, uint32_t base, bool validate,
+            msgpu_map_rank *d_rows, kf_ull *h_cnt, msgpu_map_rstats &S, uint64_t *bad) {
+  hipStream_t st = c->stream;
+  uint32_t   *d_head, *d_segid, *d_start, *d_fw, *d_fl, *d_pw, *d_pl, *d_lw, *d_ll, *d_parent, *d_nsec;
+  kf_ull     *d_sub, *d_cnt;
+  for (uint32_t **p : {&d_head, &d_segid, &d_start, &d_fw, &d_fl, &d_pw, &d_pl}) STAGE_HIP(c, B.get(p, n + 1ull));
+  for (uint32_t **p : {&d_lw, &d_ll, &d_parent, &d_nsec}) STAGE_HIP(c, B.get(p, n));
+  STAGE_HIP(c, B.get(&d_sub, n));
+  STAGE_HIP(c, B.get(&d_cnt, RK_COUNT));
+  STAGE_HIP(c, hipMemsetAsync(d_cnt, 0, RK_COUNT * sizeof(kf_ull), st));
+  STAGE_HIP(c, hipMemsetAsync(d_cnt + RK_BAD, 0xff, sizeof(kf_ull), st));
+  STAGE_HIP(c, hipMemsetAsync(d_head + n, 0, 4, st));
+  STAGE_HIP(c, hipMemsetAsync(d_sub, 0, n * sizeof(kf_ull), st));
+  STAGE_HIP(c, hipMemsetAsync(d_nsec, 0, n * 4ull, st));
+  STAGE_HIP(c, clock.begin(&S.rank_ms));
+  hipLaunchKernelGGL(k_rk_heads, dim3(grid256(n)), dim3(256), 0, st, d_chains, n, validate ? 1 : 0, d_head, d_cnt + RK_BAD);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_head, d_segid, n + 1ull));
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_segid + n);
+  hipLaunchKernelGGL(k_mp_put<kf_ull>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_cnt + RK_BAD);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  int rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t n_seg = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+  *bad = c->sc.h[MP_SC_TOTAL2];
+  if (validate && *bad != ~0ull) return MSGPU_E_ARG; // (the caller names the chain)
+  STAGE_HIP(c, hipMemsetAsync(d_fw + n_seg, 0, 4, st));
+  STAGE_HIP(c, hipMemsetAsync(d_fl + n_seg, 0, 4, st));
+  STAGE_HIP(c, clock.begin(&S.rank_ms));
+  hipLaunchKernelGGL(k_rk_starts, dim3(grid256(n)), dim3(256), 0, st, d_head, d_segid, n, d_start);
+  hipLaunchKernelGGL(k_rk_classify, dim3(grid256(n_seg)), dim3(256), 0, st, d_start, n_seg, d_fw, d_fl, d_parent, d_cnt);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fw, d_pw, n_seg + 1ull));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fl, d_pl, n_seg + 1ull));
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_pw + n_seg);
+  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL3, d_pl + n_seg);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t n_wave = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]), n_list = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
+  uint32_t *d_sb = nullptr, *d_se = nullptr;
+  uint64_t *d_key[2] = {nullptr, nullptr};
+  RkPrim   *d_spill = nullptr;
+  if (n_list) {
+    STAGE_HIP(c, B.get(&d_sb, n_list));
+    STAGE_HIP(c, B.get(&d_se, n_list));
+    STAGE_HIP(c, B.get(&d_key[0], n));
+    STAGE_HIP(c, B.get(&d_key[1], n));
+    STAGE_HIP(c, B.get(&d_spill, n));
+  }
+  STAGE_HIP(c, clock.begin(&S.rank_ms));
+  hipLaunchKernelGGL(k_rk_lists, dim3(grid256(n_seg)), dim3(256), 0, st, d_start, n_seg, d_fw, d_fl, d_pw, d_pl, d_lw, d_ll, d_sb, d_se);
+  if (n_wave) hipLaunchKernelGGL(k_rk_wave, dim3(grid_of(n_wave, 4)), dim3(256), 0, st, d_chains, d_start, d_lw, n_wave, d_parent);
+  STAGE_HIP(c, hipGetLastError());
+  if (n_list) {
+    hipLaunchKernelGGL(k_rk_keys, dim3(grid256(n)), dim3(256), 0, st, d_chains, n, d_key[0]);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+      return rocprim::segmented_radix_sort_keys_desc(tmp, bytes, d_key[0], d_key[1], n, n_list, d_sb, d_se, 0, 64, st);
+    }));
+    hipLaunchKernelGGL(k_rk_list, dim3(n_list), dim3(64), 0, st, d_chains, d_start, d_ll, d_key[1], d_parent, d_spill, d_cnt + RK_SPILL);
+    STAGE_HIP(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_rk_figures, dim3(grid256(n)), dim3(256), 0, st, d_chains, d_parent, n, d_sub, d_nsec);
+  hipLaunchKernelGGL(k_rk_rows, dim3(grid256(n)), dim3(256), 0, st, d_chains, d_parent, d_sub, d_nsec, n, base, d_rows, d_cnt);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, RK_COUNT * sizeof(kf_ull), hipMemcpyDeviceToHost, st));
+  S.n_segments += n_seg;
+  return MSGPU_OK;
+}
+
+void mp_rank_counts(const kf_ull *h, msgpu_map_rstats &S) { // behind the synchronisation
+  S.n_primaries += h[RK_PRIM];
+  S.n_secondaries += h[RK_SEC];
+  S.n_mapq0 += h[RK_MAPQ0];
+  S.largest_segment = std::max<uint64_t>(S.largest_segment, h[RK_LARGEST]);
+  S.n_segments_single += h[RK_SINGLE];
+  S.n_segments_wave += h[RK_WAVE];
+  S.n_segments_list += h[RK_LIST];
+  S.n_segments_spilled += h[RK_SPILL];
+}
 
 // ---- rule 11: the ends of a batch's chains
 
@@ -1089,6 +1399,8 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   // ---- rule 6
   uint32_t   C_n = 0;
   MpExtBatch xb; // rule 11: what comes back with the chain table
+  kf_ull          h_rk[RK_COUNT] = {}; // rule 12: the counters, likewise
+  msgpu_map_rank *d_rows = nullptr;
   if (n_kept) {
     STAGE_HIP(c, clock.begin(&S.backtrack_ms));
     STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
@@ -1121,6 +1433,19 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
                        R.Qf.d_len, k, d_chains, d_where, d_np, C_n);
     STAGE_HIP(c, hipGetLastError());
     STAGE_HIP(c, clock.end());
+
+    // ---- rule 12, directly behind the table: query, score and the query range are final here, and no extension has moved them
+    if (R.ranking) {
+      const uint64_t before = R.res->chains.size();
+      if (before + C_n >= (1ull << 32)) {
+        snprintf(c->err, sizeof(c->err), "%llu chains; with ranking on the limit of a run is 2^32 - 1 (rule 12)", static_cast<kf_ull>(before + C_n));
+        return MSGPU_E_ARG;
+      }
+      uint64_t bad;
+      STAGE_HIP(c, B.get(&d_rows, C_n));
+      rc = mp_rank(c, B, clock, d_chains, C_n, static_cast<uint32_t>(before), false, d_rows, h_rk, R.res->rstats, &bad);
+      if (rc != MSGPU_OK) return rc;
+    }
 
     uint8_t  *d_or = nullptr;   // the batch's oriented query records (exact mode with a segment pair; rule 11 makes its own otherwise)
     uint32_t *d_slab = nullptr; // the tables of the slab class (cigar mode with a segment pair; likewise)
@@ -1295,9 +1620,11 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
     const size_t have = R.res->chains.size();
     try {
       R.res->chains.resize(have + C_n);
+      if (R.ranking) R.res->ranks.resize(have + C_n);
     } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
     STAGE_HIP(c, clock.begin(&S.copy_ms));
     STAGE_HIP(c, hipMemcpyAsync(R.res->chains.data() + have, d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
+    if (R.ranking) STAGE_HIP(c, hipMemcpyAsync(R.res->ranks.data() + have, d_rows, C_n * sizeof(msgpu_map_rank), hipMemcpyDeviceToHost, st));
     STAGE_HIP(c, clock.end());
   }
   STAGE_HIP(c, hipStreamSynchronize(st));
@@ -1309,6 +1636,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
       }
     } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   }
+  if (R.ranking && C_n) mp_rank_counts(h_rk, R.res->rstats);
   if (R.extend && C_n) {
     rc = mp_extend_apply(R, C_n, xb);
     if (rc != MSGPU_OK) return rc;
@@ -1504,7 +1832,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   for (;;) {
     res->budget = budget;
     res->batches.clear();
-    const uint32_t bad = mp_cut(prm, c->extend, apre, bpre, NR, budget, res->batches);
+    const uint32_t bad = mp_cut(prm, c->extend, c->ranking, apre, bpre, NR, budget, res->batches);
     if (bad < NR) {
       const uint64_t a = apre[bad + 1] - apre[bad], b = bpre[bad + 1] - bpre[bad];
       if (a >= (1ull << 31)) {
@@ -1514,7 +1842,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
       }
       snprintf(c->err, sizeof(c->err), "query record %u with %llu anchors and %llu bases needs %llu bytes on its own (%llu of them for its "
                "oriented copies); the budget of a batch is %llu bytes (rule 9: a record is not split)", bad, static_cast<kf_ull>(a),
-               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(prm, c->extend, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
+               static_cast<kf_ull>(b), static_cast<kf_ull>(mp_batch_bytes(prm, c->extend, c->ranking, a, b)), static_cast<kf_ull>(exact ? 2 * b : 0),
                static_cast<kf_ull>(budget));
       return MSGPU_E_NOMEM;
     }
@@ -1533,8 +1861,10 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   }
 
   // ---- rules 4 to 8, batch by batch
-  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res, c->extend};
+  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res, c->extend, c->ranking};
   res->xstats.extend = c->extend;
+  res->rstats.ranking = c->ranking;
+  res->rstats.lds_primaries = MSGPU_MAP_RANK_LDS;
   for (msgpu_map_batch &b : res->batches) {
     rc = mp_batch(run, B, b);
     if (rc != MSGPU_OK) return rc;
@@ -1567,8 +1897,10 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
       part[t].reserve((b - a) * 112);
       std::vector<std::pair<uint32_t, uint64_t>> runs;
       for (uint64_t i = a; i < b; ++i) {
+        const msgpu_map_rank *rk = res->ranks.empty() ? nullptr : &res->ranks[i];
+        const bool            prim = rk && rk->parent == i;
         if (!cigar) {
-          mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t]);
+          mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], nullptr, rk, prim);
           continue;
         }
         const StageTimer merging;
@@ -1582,7 +1914,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
           }
         part_cnt[t].push_back(n_packed);
         part_ms[t] += merging.ms();
-        mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], &runs);
+        mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], &runs, rk, prim);
       }
     });
     size_t total = 0;
@@ -1618,13 +1950,26 @@ void msgpu_map_default_params(msgpu_map_params *p) {
 uint64_t msgpu_map_batch_bytes(const msgpu_map_params *p, uint64_t n_anchors, uint64_t n_query_bases) {
   msgpu_map_params prm{};
   if (p) prm = *p;
-  return mp_batch_bytes(prm, 0, n_anchors, n_query_bases);
+  return mp_batch_bytes(prm, 0, 0, n_anchors, n_query_bases);
 }
 
 uint64_t msgpu_map_batch_bytes_ext(const msgpu_map_params *p, uint32_t extend, uint64_t n_anchors, uint64_t n_query_bases) {
   msgpu_map_params prm{};
   if (p) prm = *p;
-  return mp_batch_bytes(prm, extend, n_anchors, n_query_bases);
+  return mp_batch_bytes(prm, extend, 0, n_anchors, n_query_bases);
+}
+
+uint64_t msgpu_map_batch_bytes_rank(const msgpu_map_params *p, uint32_t extend, uint32_t ranking, uint64_t n_anchors, uint64_t n_query_bases) {
+  msgpu_map_params prm{};
+  if (p) prm = *p;
+  return mp_batch_bytes(prm, extend, ranking, n_anchors, n_query_bases);
+}
+
+int msgpu_map_set_ranking(msgpu_mapctx *c, int on) {
+  if (!c) return MSGPU_E_ARG;
+  c->err[0]  = 0;
+  c->ranking = on != 0;
+  return MSGPU_OK;
 }
 
 int msgpu_map_set_extension(msgpu_mapctx *c, uint32_t extend) {
@@ -1829,6 +2174,69 @@ int msgpu_map_result_ext_ends(const msgpu_map_result *r, const msgpu_ext_end **e
   if (!r || !ends || !n) return MSGPU_E_ARG;
   *ends = r->x_ends.data();
   *n    = r->x_ends.size();
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_ranks(const msgpu_map_result *r, const msgpu_map_rank **ranks, uint64_t *n) {
+  if (!r || !ranks || !n) return MSGPU_E_ARG;
+  *ranks = r->ranks.data();
+  *n     = r->ranks.size();
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_rank_stats(const msgpu_map_result *r, msgpu_map_rstats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->rstats;
+  return MSGPU_OK;
+}
+
+// rule 12 on a chain table of the host
+int msgpu_map_rank_tables(msgpu_mapctx *c, const msgpu_map_chain *chains, uint64_t n, msgpu_map_rank *ranks_out) {
+  if (!c) return MSGPU_E_ARG;
+  c->err[0]       = 0;
+  c->table_rstats = msgpu_map_rstats{};
+  c->table_rstats.ranking       = 1;
+  c->table_rstats.lds_primaries = MSGPU_MAP_RANK_LDS;
+  if (n && (!chains || !ranks_out)) return MSGPU_E_ARG;
+  if (n >= (1ull << 32)) {
+    snprintf(c->err, sizeof(c->err), "%llu chains; the limit of a table is 2^32 - 1 (rule 12)", static_cast<kf_ull>(n));
+    return MSGPU_E_ARG;
+  }
+  if (!n) return MSGPU_OK;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  hipStream_t      st = c->stream;
+  DevArena         D;
+  StageClock       clock(st);
+  msgpu_map_chain *d_chains;
+  msgpu_map_rank  *d_rows;
+  kf_ull           h_cnt[RK_COUNT] = {};
+  uint64_t         bad = ~0ull;
+  STAGE_HIP(c, D.get(&d_chains, n));
+  STAGE_HIP(c, D.get(&d_rows, n));
+  STAGE_HIP(c, hipMemcpyAsync(d_chains, chains, n * sizeof(msgpu_map_chain), hipMemcpyHostToDevice, st));
+  int rc = mp_rank(c, D, clock, d_chains, static_cast<uint32_t>(n), 0, true, d_rows, h_cnt, c->table_rstats, &bad);
+  if (rc == MSGPU_OK) {
+    const hipError_t e = hipMemcpyAsync(ranks_out, d_rows, n * sizeof(msgpu_map_rank), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) rc = stage_fail(c, MSGPU_E_HIP, "rows", e);
+  }
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc == MSGPU_OK && e != hipSuccess) rc = stage_fail(c, MSGPU_E_HIP, "hipStreamSynchronize", e);
+  clock.collect();
+  if (rc == MSGPU_E_ARG && bad != ~0ull && bad < n) {
+    c->table_rstats = msgpu_map_rstats{};
+    if (chains[bad].q_start > chains[bad].q_end)
+      snprintf(c->err, sizeof(c->err), "chain %llu: q_start %u > q_end %u", static_cast<kf_ull>(bad), chains[bad].q_start, chains[bad].q_end);
+    else
+      snprintf(c->err, sizeof(c->err), "chain %llu: query record %u behind %u (the table is ordered by query record)", static_cast<kf_ull>(bad),
+               chains[bad].query, chains[bad - 1].query);
+  }
+  if (rc == MSGPU_OK) mp_rank_counts(h_cnt, c->table_rstats);
+  return rc;
+}
+
+int msgpu_map_rank_tables_stats(const msgpu_mapctx *c, msgpu_map_rstats *out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out = c->table_rstats;
   return MSGPU_OK;
 }
 

@@ -1,6 +1,7 @@
 // msgpu_polish.hip -- the polishing stage: a pile-up consensus of a draft from the mapper's run tables (include/msgpu.h,
 // "pileup consensus").  Every chain of reads against the draft arrives as runs len << 4 | op; the stage
-// checks the tables on the device (rule 1), picks one voter per read (rule 2), walks every column of every voter into six
+// checks the tables on the device (rule 1), picks one voter per read (rule 2; in ranked form every primary of sufficient
+// mapping quality, by the mapper's rule 12 rows), walks every column of every voter into six
 // integer counters per draft base (rules 3 and 4), collects, sorts and counts the insertion events (rules 4 and 6), calls
 // every position (rule 5), and writes the polished records through msgpu_fasta_format (rule 7).
 //
@@ -33,7 +34,7 @@ constexpr uint32_t PL_MAX_INS = 32;
 enum { PL_A = 0, PL_C, PL_G, PL_T, PL_DEL, PL_OTHER, PL_CLASSES };
 // rule 1: what can be wrong with a chain, in the order in which one chain's violations are looked at
 enum { PL_BAD_ORDER = 0, PL_BAD_STRAND, PL_BAD_QREC, PL_BAD_TREC, PL_BAD_TRANGE, PL_BAD_QRANGE, PL_BAD_RUN, PL_BAD_TCONS, PL_BAD_QCONS,
-       PL_BAD_OFF };
+       PL_BAD_OFF, PL_BAD_RANK /* (j), ranked form only: behind every other violation of its chain */ };
 // the counts of msgpu_pl_stats that the kernels add up, one 64-bit word each
 enum { PL_ST_VOTERS = 0, PL_ST_IGNORED, PL_ST_EQ, PL_ST_X, PL_ST_D, PL_ST_I, PL_ST_VERBATIM, PL_ST_UNCHANGED, PL_ST_SUBST, PL_ST_DELETED,
        PL_ST_USABLE, PL_ST_UNUSABLE, PL_ST_ENDS, PL_ST_APPLIED, PL_ST_INSERTED, PL_ST_MAXDEPTH, PL_ST_COUNT };
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void k_pl_runs(const uint64_t *off, uint32_t n
 }
 
 // rule 1 on the chain's fields and on what its runs consume
-__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, PlRecs R, PlRecs Q, kf_ull *bad) {
+__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, PlRecs R, PlRecs Q, const msgpu_map_rank *ranks, kf_ull *bad) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= X.n_chains) return;
   const msgpu_map_chain ch = X.chains[i];
@@ -149,6 +150,12 @@ __global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, PlRecs R, Pl
   const uint64_t a = X.off[i], b = X.off[i + 1];
   if (X.T[b] - X.T[a] != static_cast<uint64_t>(ch.t_end) - ch.t_start) found(PL_BAD_TCONS);
   if (X.Q[b] - X.Q[a] != static_cast<uint64_t>(ch.q_end) - ch.q_start) found(PL_BAD_QCONS);
+  if (ranks) { // (j): the parent is a chain of the table, of the same query record, and its own parent
+    const msgpu_map_rank r = ranks[i];
+    bool                 ok = r.parent < X.n_chains && r.mapq <= 60;
+    if (ok) ok = X.chains[r.parent].query == ch.query && ranks[r.parent].parent == r.parent;
+    if (!ok) found(PL_BAD_RANK);
+  }
   if (what != PL_NONE) pl_bad(bad, i, what);
 }
 
@@ -168,11 +175,21 @@ __global__ __launch_bounds__(256) void k_pl_voter_idx(const msgpu_map_chain *cha
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n && pl_eligible(chains[i], min_identity) && vkey[chains[i].query] == pl_voter_key(chains[i])) atomicMin(&vidx[chains[i].query], i);
 }
-// the voters' spans (0 for every other chain), the counts, and the sum of the depths per draft record
-__global__ __launch_bounds__(256) void k_pl_spans(const msgpu_map_chain *chains, uint32_t n, const uint32_t *vidx, uint32_t *span, kf_ull *rec_depth,
-                                                  kf_ull *st) {
+// rule 2 in ranked form, one pass without an atomic: a chain votes iff it is eligible, primary and of sufficient mapping quality
+__global__ __launch_bounds__(256) void k_pl_voter_ranked(const msgpu_map_chain *chains, const msgpu_map_rank *ranks, uint32_t n,
+                                                         uint32_t min_identity, uint32_t min_mapq, uint32_t *vflag) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  const bool     live = i < n, votes = live && vidx[chains[i].query] == i;
+  if (i < n) vflag[i] = pl_eligible(chains[i], min_identity) && ranks[i].parent == i && ranks[i].mapq >= min_mapq;
+}
+// is chain i a voter: by its flag in ranked form, else as its query record's one voter
+__device__ inline bool pl_votes(const msgpu_map_chain *chains, const uint32_t *vidx, const uint32_t *vflag, uint32_t i) {
+  return vflag ? vflag[i] != 0 : vidx[chains[i].query] == i;
+}
+// the voters' spans (0 for every other chain), the counts, and the sum of the depths per draft record
+__global__ __launch_bounds__(256) void k_pl_spans(const msgpu_map_chain *chains, uint32_t n, const uint32_t *vidx, const uint32_t *vflag,
+                                                  uint32_t *span, kf_ull *rec_depth, kf_ull *st) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const bool     live = i < n, votes = live && pl_votes(chains, vidx, vflag, i);
   if (live) span[i] = votes ? chains[i].t_end - chains[i].t_start : 0;
   if (votes) atomicAdd(&rec_depth[chains[i].target], static_cast<kf_ull>(chains[i].t_end - chains[i].t_start));
   pl_count(votes, st + PL_ST_VOTERS);
@@ -204,7 +221,7 @@ __global__ __launch_bounds__(256) void k_pl_pileup(PlTables X, const uint64_t *S
 // rule 4, the insertion events.  FILL = false: flag[u] = the run is a usable event at a slot 0 < p < tlen, and the counts;
 // FILL = true: event E[u] = (slot in the store << 6 | L, the 2-bit packed letters, the first in the highest bits).
 template <bool FILL>
-__global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_chain, const uint32_t *vidx, PlRecs R, PlRecs Q, uint32_t *flag,
+__global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_chain, const uint32_t *vidx, const uint32_t *vflag, PlRecs R, PlRecs Q, uint32_t *flag,
                                                 const uint32_t *E, uint64_t *ev_key, uint64_t *ev_seq, kf_ull *st) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   bool           ins = false, ends = false, usable = false;
@@ -212,7 +229,7 @@ __global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_
   if (u < X.n_runs && (X.ops[u] & 15) == PL_I && (!FILL || flag[u])) {
     const uint32_t        i = run_chain[u];
     const msgpu_map_chain ch = X.chains[i];
-    if (vidx[ch.query] == i) {
+    if (pl_votes(X.chains, vidx, vflag, i)) {
       const uint32_t a = static_cast<uint32_t>(X.off[i]), b = static_cast<uint32_t>(X.off[i + 1]);
       ins  = true;
       L    = X.ops[u] >> 4;
@@ -386,7 +403,8 @@ const char *const PL_WHAT[] = {"query order (the chains are not ordered by query
                                "query range (not q_start <= q_end <= qlen)", "run (a length of 0, or an op that is none of I, D, =, X)",
                                "target consumption (the runs do not consume t_end - t_start target bases)",
                                "query consumption (the runs do not consume q_end - q_start query bases)",
-                               "offsets (the run offsets decrease or exceed the run table)"};
+                               "offsets (the run offsets decrease or exceed the run table)",
+                               "rank (the parent is out of range, of another query record or no primary, or mapq exceeds 60)"};
 
 struct PlFile { // a file in its store
   SeqFileHold f;
@@ -457,7 +475,7 @@ template <class T> hipError_t pl_zeroed(DevArena &D, hipStream_t st, T **out, si
 }
 
 int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
-           uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, msgpu_pl_result *res) {
+           uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq, msgpu_pl_result *res) {
   msgpu_pl_stats &S = res->stats;
   hipStream_t     st = c->stream;
   DevArena        D;
@@ -497,7 +515,8 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   // length and its scan; per run the op, what it consumes on both sides with the two scans, its chain, the event flag and
   // its scan; per chain the entry, the offset, the span and its scan; per read the voter's key and index
   const uint64_t fixed_bytes = NB * (PL_CLASSES * 4ull + 8 + 1 + 4 + 8) + n_runs * (4ull + 4 + 4 + 8 + 8 + 4 + 4 + 4) +
-                               n_chains * (sizeof(msgpu_map_chain) + 8ull + 4 + 8) + Q.n * 12ull + R.n * 48ull + (8ull << 20);
+                               n_chains * (sizeof(msgpu_map_chain) + 8ull + 4 + 8) + Q.n * 12ull + R.n * 48ull + (8ull << 20) +
+                               (ranks ? n_chains * (sizeof(msgpu_map_rank) + 4ull) : 0); // (ranked form: the rows and the voters' flags)
   if ((rc = pl_room(c, fixed_bytes, "the pile-up", NB, "draft bases", n_runs, "runs")) != MSGPU_OK) return rc;
 
   kf_ull *d_st, *d_bad = reinterpret_cast<kf_ull *>(c->sc.d + PL_SC_BAD);
@@ -521,6 +540,13 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     STAGE_HIP(c, hipMemcpyAsync(d_off, off, (n_chains + 1ull) * 8, hipMemcpyHostToDevice, st));
   }
   if (n_runs) STAGE_HIP(c, hipMemcpyAsync(d_ops, ops, n_runs * 4ull, hipMemcpyHostToDevice, st));
+  msgpu_map_rank *d_ranks = nullptr;
+  uint32_t       *d_vflag = nullptr;
+  if (ranks) {
+    STAGE_HIP(c, D.get(&d_ranks, n_chains));
+    STAGE_HIP(c, D.get(&d_vflag, n_chains));
+    if (n_chains) STAGE_HIP(c, hipMemcpyAsync(d_ranks, ranks, n_chains * sizeof(msgpu_map_rank), hipMemcpyHostToDevice, st));
+  }
   auto bad_chain = [&]() -> int { // the smallest bad chain, through the scalar block
     const int r2 = c->sc.read(c);
     if (r2 != MSGPU_OK) return r2;
@@ -542,7 +568,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   STAGE_HIP(c, clock.end());
   const PlTables X{d_chains, d_off, d_ops, d_T, d_Q, n_chains, n_runs};
   STAGE_HIP(c, clock.begin(&S.validate_ms));
-  if (n_chains) hipLaunchKernelGGL(k_pl_check_chain, dim3(grid256(n_chains)), dim3(256), 0, st, X, R, Q, d_bad);
+  if (n_chains) hipLaunchKernelGGL(k_pl_check_chain, dim3(grid256(n_chains)), dim3(256), 0, st, X, R, Q, d_ranks, d_bad);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, clock.end());
   if ((rc = bad_chain()) != MSGPU_OK) return rc; // no kernel below runs on a table that breaks rule 1
@@ -563,9 +589,13 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   STAGE_HIP(c, clock.begin(&S.voters_ms));
   if (n_chains) {
     const uint32_t mi = static_cast<uint32_t>(prm.min_identity);
-    hipLaunchKernelGGL(k_pl_voter_key, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey);
-    hipLaunchKernelGGL(k_pl_voter_idx, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey, d_vidx);
-    hipLaunchKernelGGL(k_pl_spans, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, d_vidx, d_span, d_rec_depth, d_st);
+    if (ranks) {
+      hipLaunchKernelGGL(k_pl_voter_ranked, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, d_ranks, n_chains, mi, min_mapq, d_vflag);
+    } else {
+      hipLaunchKernelGGL(k_pl_voter_key, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey);
+      hipLaunchKernelGGL(k_pl_voter_idx, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey, d_vidx);
+    }
+    hipLaunchKernelGGL(k_pl_spans, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, d_vidx, d_vflag, d_span, d_rec_depth, d_st);
   }
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_span, d_S, n_chains + 1ull));
@@ -593,7 +623,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   STAGE_HIP(c, D.get(&d_E, n_runs + 1ull));
   STAGE_HIP(c, pl_zeroed(D, st, &d_best, NB));
   STAGE_HIP(c, clock.begin(&S.insertions_ms));
-  if (n_runs) hipLaunchKernelGGL((k_pl_ins<false>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, R, Q, d_flag, nullptr, nullptr, nullptr, d_st);
+  if (n_runs) hipLaunchKernelGGL((k_pl_ins<false>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, d_vflag, R, Q, d_flag, nullptr, nullptr, nullptr, d_st);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_flag, d_E, n_runs + 1ull));
   hipLaunchKernelGGL(k_pl_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_E + n_runs);
@@ -615,7 +645,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     STAGE_HIP(c, D.get(&d_G, n_ev + 1ull));
     STAGE_HIP(c, D.get(&d_gstart, n_ev + 1ull));
     STAGE_HIP(c, clock.begin(&S.insertions_ms));
-    hipLaunchKernelGGL((k_pl_ins<true>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, R, Q, d_flag, d_E, d_key, d_seq, d_st);
+    hipLaunchKernelGGL((k_pl_ins<true>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, d_vflag, R, Q, d_flag, d_E, d_key, d_seq, d_st);
     STAGE_HIP(c, hipGetLastError());
     // two stable sorts: by the letters, then by (slot, L), whose 44 bits are the store's 38 and L's 6
     STAGE_HIP(c, stage_sort_pairs(D, st, d_seq, d_seq2, d_key, d_key2, n_ev));
@@ -741,8 +771,9 @@ void msgpu_pl_destroy(msgpu_plctx *c) { stage_destroy(c); }
 
 const char *msgpu_pl_last_error(const msgpu_plctx *c) { return c ? c->err : "null context"; }
 
-int msgpu_pl_run(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
-                 uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags, msgpu_pl_result **out) {
+static int pl_entry(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
+                    uint64_t n_chains, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq, uint32_t flags,
+                    msgpu_pl_result **out) {
   if (!c || !out) return MSGPU_E_ARG;
   *out      = nullptr;
   c->err[0] = 0;
@@ -759,12 +790,29 @@ int msgpu_pl_run(msgpu_plctx *c, const msgpu_pl_params *params, const char *draf
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   const StageTimer wall;
   const uint64_t   lost0 = c->sc.lost;
-  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, res.get());
+  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, ranks, min_mapq, res.get());
   if (rc != MSGPU_OK) return rc;
   res->stats.n_lost_publications = c->sc.lost - lost0;
   res->stats.wall_ms             = wall.ms();
   *out                           = res.release();
   return MSGPU_OK;
+}
+
+int msgpu_pl_run(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
+                 uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags, msgpu_pl_result **out) {
+  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, nullptr, 0, flags, out);
+}
+
+int msgpu_pl_run_ranked(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
+                        const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks,
+                        uint32_t min_mapq, uint32_t flags, msgpu_pl_result **out) {
+  static const msgpu_map_rank none{};
+  if (c && out && !ranks && n_chains) {
+    *out = nullptr;
+    snprintf(c->err, sizeof(c->err), "no rank rows for %llu chains", static_cast<unsigned long long>(n_chains));
+    return MSGPU_E_ARG;
+  }
+  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, ranks ? ranks : &none, min_mapq, flags, out);
 }
 
 int msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out) {

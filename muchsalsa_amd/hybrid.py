@@ -84,7 +84,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None, extend=None):
+        bubble=None, polish=None, extend=None, min_mapq=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -94,7 +94,9 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     last stage ``"polish"``: N rounds of muchsalsa_amd.polish of the assembly by the scrubbed reads into POLISHED_NAME, named by
     ``files["polished"]``; every other file is the same.  ``extend`` (None or 0: off) = N is the mapper's rule 11 parameter: step 9
     then runs with cigar = 1 and extend = N, and so does every mapping of the polish stage; every file written before step 9's
-    PAF is the same."""
+    PAF is the same.  ``min_mapq`` (None: off) = N goes to the polish stage only (muchsalsa_amd.polish's rule 2 in ranked form: its
+    mappings run with the mapper's rule 12 on, and a read votes with its primaries of mapping quality N or more); the four
+    mappings of the pipeline keep ranking off: their consumers read columns 1 to 11 and want every chain, as with ``-P``."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -147,7 +149,7 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
         from . import polish as polisher
         result["files"]["polished"] = os.path.join(out, POLISHED_NAME)
         stage("polish", polisher.run, files["assembly"], files["scrubbed"], result["files"]["polished"], rounds=int(polish),
-              device=device, extend=int(extend or 0))
+              device=device, extend=int(extend or 0), min_mapq=min_mapq)
     result["seconds"] = round(time.perf_counter() - t_all, 4)
     return result
 

@@ -3,7 +3,7 @@ write -- a PAF of every record of a query file against every record of a target 
 
     python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--cigar] [--ava]
             [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
-            [--extend N]
+            [--extend N] [--rank]
 
 prints one JSON line of counts and seconds.  ``--budget-mb`` (N > 0) bounds the device memory of a batch of query records
 (rule 9; without it: the free device memory).  With ``--ava`` the two paths name the same file (the reads against
@@ -11,12 +11,13 @@ themselves: the read-to-read PAF muchsalsa_amd.scrubber takes as its fourth inpu
 count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call); ``--cigar`` (which implies ``--exact``) aligns
 every segment base by base (rule 10): column 10 is then the number of ``=`` columns, column 11 the number of alignment columns,
 and the line ends in a ``cg:Z:`` string of ``=``, ``X``, ``I`` and ``D`` runs; ``--extend N`` (1..65535, which implies
-``--cigar``) extends every chain beyond its outermost seeds by up to N bases at either end (rule 11).  minimap2 is not needed, and it is not part of
+``--cigar``) extends every chain beyond its outermost seeds by up to N bases at either end (rule 11); ``--rank`` marks every chain
+as primary or secondary and writes a mapping quality into column 12 (rule 12).  minimap2 is not needed, and it is not part of
 the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
 tests' restatement in plain Python (tests/map_oracle.py), not against minimap2.  The rules (include/msgpu.h,
 "unitig-to-read mapping"); parameters k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth
-(2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1); cigar (0 / 1)
-and extend (0..65535) are keywords of ``run`` beside them:
+(2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1); cigar (0 / 1),
+extend (0..65535) and rank (False / True) are keywords of ``run`` beside them:
 
  1. windows: the alphabet, case folding, 2-bit code, canonical key (min(fw, rc) as 2k-bit numbers) and the break at any
     other byte are those of the k-mer filter's rolling window (KfRoll).  A stretch is a maximal run of k-mer start
@@ -120,6 +121,24 @@ and extend (0..65535) are keywords of ``run`` beside them:
     side's start without an edit is extended to that sequence's end: cell (0, 0) wins.  Rule 9 with E > 0:
     msgpu_map_batch_bytes_ext adds, per anchor, two ends' descriptors (24 bytes each), end cells (24 bytes each) and
     band + 1 script words each; the slab is cigar mode's.
+12. primaries, secondaries and mapping quality, on request (``rank``; msgpu_map_set_ranking; off by default; it needs no other
+    mode: seed, exact, cigar, ava and extend all combine with it).  The chains of one query record, over all targets and both
+    strands, with their indices in output order (rule 8), are ranked among themselves.  For a chain c: len(c) = q_end - q_start
+    of rule 7's forward query range, and ov(c, p) = max(0, min(q_end_c, q_end_p) - max(q_start_c, q_start_p)).  Rule 11 changes
+    no rank: rule 12 reads the ranges as rule 7 leaves them, before any extension.  (1) Visiting order: by (score descending,
+    output index ascending).  (2) A visited chain c is compared with the primaries visited before it, in visiting order: the
+    first primary p with 2 * ov(c, p) > min(len(c), len(p)) makes c secondary with parent(c) = p; if there is none, c is
+    primary and parent(c) = c.  The mask level is one half and the comparison is strict.  (3) Of a primary p: sub(p) is the
+    greatest score among its secondaries, 0 if it has none; n_secondary(p) is the number of its secondaries s with
+    10 * score(s) >= 9 * score(p); both are 0 for a secondary.  (4) mapq of a primary with s1 = score(p) > 0:
+    (60 * (s1 - sub) * min(n_anchors, 10)) / (10 * s1), the products in 64 bits, integer division, clamped to 0..60; 0 if
+    s1 <= 0; 0 for a secondary.  (5) With ranking on column 12 is mapq and the tags are tp:A:P or tp:A:S, cm:i, s1:i,
+    s2:i:<sub>, then NM and cg as before; line order, every other column, the chain table and the run tables are untouched.
+    (6) With ranking off every byte is as before: 255, no tp, no s2.  (7) A query record's chains never span two batches (rule
+    9), so the rule runs per batch; parent is an index into the whole run's chain table; with ranking on a run has fewer than
+    2^32 chains, else MSGPU_E_ARG.  msgpu_map_batch_bytes_rank bounds a batch (104 bytes per anchor and a fixed 24 * 256 bytes
+    more than msgpu_map_batch_bytes_ext).  The mask level 1/2, the ratio 0.9 and the mapq formula are choices modelled on
+    minimap2's, unchecked on real reads.
 
 Known differences from minimap2, none of which could be checked against the program (it is not installed where this project
 is built):
@@ -130,8 +149,9 @@ is built):
 * a fixed window of 64 predecessors instead of the skip heuristic of ``--max-chain-skip``;
 * an integer gap cost;
 * no ``--dual`` / ``-D`` diagonal filtering beyond the ava rule;
-* no primary / secondary marking, as with ``-P``: all chains are kept;
-* no mapping quality (column 12 is 255);
+* primary / secondary marking and a mapping quality only with ``--rank`` (rule 12): without it all chains are kept unmarked,
+  as with ``-P``, and column 12 is 255; rule 12 decides by query overlap alone, and its integer formula has none of
+  minimap2's chain-length terms;
 * no CIGAR without ``--cigar``: exact mode alone gives a match count that is a lower bound from unit-cost distances per
   link, not minimap2's count of ``=`` columns.  With ``--cigar`` the columns are counted on a unit-cost alignment of every
   segment between two seeds (rule 10), not on minimap2's affine-gap alignment, and a segment beyond the band is written
@@ -150,10 +170,12 @@ import os
 import sys
 import time
 
+import numpy as np
+
 from . import _lib
 from ._stage import StageError, stage_context, text_view
 
-__all__ = ["MapError", "Index", "run", "main", "DEFAULTS"]
+__all__ = ["MapError", "Index", "run", "rank_tables", "main", "DEFAULTS"]
 
 DEFAULTS = dict(k=15, w=5, max_occ=200, max_gap=10000, bandwidth=2000, min_score=100, min_count=3, exact=0, band=64, ava=0)
 
@@ -208,7 +230,31 @@ class Index:
         return False
 
 
-def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, extend=0, **params):
+def _rank_stats(rst):
+    return dict({name: int(getattr(rst, name)) for name, t in _lib.MapRankStats._fields_ if t is not C.c_float},
+                seconds={"rank": rst.rank_ms / 1e3})
+
+
+def rank_tables(chains, device=0, context=None, stats=None):
+    """Rule 12 on a chain table (msgpu_map_rank_tables): ``chains`` holds per chain the tuple ``tables["chains"]`` of ``run`` has
+    (only query, anchors, score, q_start and q_end are read), in output order.  Returns per chain the tuple (parent, sub,
+    n_secondary, mapq), parent an index into ``chains``.  ``context``: an entered ``stage_context("map", ...)`` or an Index's
+    ``stage``; ``stats`` (a dict) receives the counts of msgpu_map_rstats."""
+    table = np.zeros(len(chains), dtype=_lib.MAP_CHAIN_DTYPE)
+    for i, ch in enumerate(chains):
+        table[i] = tuple(int(x) for x in ch)
+    rows = np.zeros(len(chains), dtype=_lib.MAP_RANK_DTYPE)
+    L = _lib.lib()
+    with (stage_context("map", device, MapError) if context is None else contextlib.nullcontext(context)) as stage:
+        stage.check(L.msgpu_map_rank_tables(stage.ctx, table.ctypes.data, len(chains), rows.ctypes.data))
+        if stats is not None:
+            rst = _lib.MapRankStats()
+            L.msgpu_map_rank_tables_stats(stage.ctx, C.byref(rst))
+            stats.update(_rank_stats(rst))
+    return [tuple(int(x) for x in r) for r in rows]
+
+
+def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, extend=0, rank=False, **params):
     """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
     per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
     ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
@@ -221,7 +267,10 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     holds the counts and seconds of msgpu_map_astats.  ``extend`` = E > 0 (rule 11; it needs cigar = 1) extends every chain at
     both ends; the returned dict then has ``extend`` (the fields of msgpu_map_xstats, the time under ``seconds``) and ``tables``
     receives ``ext``: per line the pair (left end, right end), each (e, k, x, y, score, rows).  The value is set on the context
-    for this run: an ``index`` serves runs with any extend, one after the other."""
+    for this run: an ``index`` serves runs with any extend, one after the other.  ``rank`` = True (rule 12) marks primaries and
+    secondaries and writes the mapping quality; the result then carries ``ranks`` (per line the tuple (parent, sub, n_secondary,
+    mapq)) and ``rank`` (the counts of msgpu_map_rstats, the time under ``seconds``); ``tables`` receives ``ranks`` too.  Like
+    extend it is set on the context for this run."""
     if index is not None:
         params = dict({"k": index.k, "w": index.w}, **params)
     unknown = set(params) - set(DEFAULTS)
@@ -240,6 +289,7 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
         if not 0 <= int(extend) < (1 << 32):
             raise MapError(_lib.E_ARG, "extend = %d" % int(extend))
         stage.check(L.msgpu_map_set_extension(stage.ctx, int(extend)))
+        stage.check(L.msgpu_map_set_ranking(stage.ctx, 1 if rank else 0))
         with (stage.run(C.byref(prm), os.fsencode(targets), qpath, 0, budget) if index is None else
               stage.run(C.byref(prm), index.handle, qpath, 0, budget, fn="run_index")) as res:
             st = _lib.MapStats()
@@ -254,7 +304,17 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             L.msgpu_map_result_align_stats(res, C.byref(ast))
             xst = _lib.MapExtStats()
             L.msgpu_map_result_ext_stats(res, C.byref(xst))
+            rst, ranks = _lib.MapRankStats(), None
+            L.msgpu_map_result_rank_stats(res, C.byref(rst))
+            if rst.ranking:
+                rp, m = C.POINTER(_lib.MapRank)(), C.c_uint64()
+                L.msgpu_map_result_ranks(res, C.byref(rp), C.byref(m))
+                rows = (np.frombuffer((C.c_char * (16 * m.value)).from_address(C.addressof(rp.contents)), dtype=_lib.MAP_RANK_DTYPE)
+                        if m.value else [])
+                ranks = [tuple(int(x) for x in r) for r in rows]
             if tables is not None:
+                if ranks is not None:
+                    tables["ranks"] = ranks
                 cp = C.POINTER(_lib.MapChain)()
                 m = C.c_uint64()
                 L.msgpu_map_result_chains(res, C.byref(cp), C.byref(m))
@@ -282,6 +342,9 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     if xst.extend:
         ext["extend"] = dict({name: int(getattr(xst, name)) for name, t in _lib.MapExtStats._fields_
                               if t is not C.c_float and name != "reserved"}, seconds={"extend": xst.extend_ms / 1e3})
+    if ranks is not None:
+        ext["ranks"] = ranks
+        ext["rank"] = _rank_stats(rst)
     return {**ext, "params": {name: int(getattr(st.params, name)) for name in DEFAULTS}, "records": [int(x) for x in st.n_records],
             "bases": [int(x) for x in st.n_bases], "minimizers": [int(x) for x in st.n_minimizers], "keys": int(st.n_keys),
             "keys_dropped": int(st.n_keys_dropped), "entries_dropped": int(st.n_entries_dropped), "anchors": int(st.n_anchors),
@@ -319,6 +382,9 @@ def main(argv):
             ok = False
         del args[i:i + 2]
         cigar = p["exact"] = 1
+    rank = "--rank" in args
+    if rank:
+        args.remove("--rank")
     for name, key in _OPTS.items():
         if name in args:
             i = args.index(name)
@@ -343,7 +409,8 @@ def main(argv):
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, extend=extend, **p)
+    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, extend=extend, rank=rank, **p)
+    out.pop("ranks", None)  # (the table is the PAF's; the line keeps the counts)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0
