@@ -292,7 +292,7 @@ struct msgpu_ctx : msgpu::StageCtx {
   uint32_t n_cls[4] = {0, 0, 0, 0}; // edges of 9..16, 17..32, 33..64 and <= 8 EdgeMatches
   uint64_t n_edges_fast = 0;
   uint64_t chain_E = 0; // edges of the last chaining pass (where its band counts lie in chain_chunks)
-  DevBuf ems, order_scr, ids_scr, edge_norders, edge_nids, orders, ids, big_list, cls_list, big_elems,
+  DevBuf ems, order_scr, ids_scr, orders, ids, big_list, cls_list, big_elems,
       big_paths;
   DevBuf g_deg, g_off, g_adj, g_cand, g_sane, g_out; // findContractionEdges
   DevBuf sel_idx, sel_cnt, sel_off, sel_ems;          // msgpu_get_edgematches
@@ -1145,8 +1145,6 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   STAGE_HIP(c, c->ems.ensure((M ? M : 1) * sizeof(msgpu_edgematch)));
   STAGE_HIP(c, c->order_scr.ensure((M ? M : 1) * sizeof(msgpu_order)));
   STAGE_HIP(c, c->ids_scr.ensure((M ? M : 1) * 4));
-  STAGE_HIP(c, c->edge_norders.ensure((E + 4) * 4));
-  STAGE_HIP(c, c->edge_nids.ensure((E + 4) * 4));
   STAGE_HIP(c, c->chain_chunks.ensure(chunk_words(E) * 8));
 
   ChainArgs a;
@@ -1162,8 +1160,6 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
   a.ems          = c->ems.as<msgpu_edgematch>();
   a.order_scr    = c->order_scr.as<msgpu_order>();
   a.ids_scr      = c->ids_scr.as<uint32_t>();
-  a.edge_norders = c->edge_norders.as<uint32_t>();
-  a.edge_nids    = c->edge_nids.as<uint32_t>();
   a.err          = scalar<uint32_t>(c, SC_ERR);
   if (!c->pair_tab.p) {
     STAGE_HIP(c, c->pair_tab.ensure(PAIR_TAB_WORDS * sizeof(uint32_t)));
@@ -1258,8 +1254,6 @@ int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
     CompactArgs k;
     k.edges        = c->edges.as<msgpu_edge>();
     k.n_edges      = E;
-    k.edge_norders = c->edge_norders.as<uint32_t>();
-    k.edge_nids    = c->edge_nids.as<uint32_t>();
     k.chunk_sums   = c->chain_chunks.as<unsigned long long>();
     k.n_chunks     = static_cast<uint32_t>((E + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
     k.scalars      = c->sc.d;

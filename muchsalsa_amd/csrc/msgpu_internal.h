@@ -98,7 +98,7 @@ struct EmitArgs {
 };
 
 struct ChainArgs {
-  msgpu_edge      *edges;
+  msgpu_edge      *edges;     // bytes 16..31 of an edge: the chain kernels' counts for k_compact (edge_counts)
   const uint64_t  *edge_cand;
   uint64_t         n_edges;
   const uint32_t  *cand_j, *cand_q; // per EdgeMatch: its row in v1's and in v2's segment of by_read
@@ -108,7 +108,6 @@ struct ChainArgs {
   msgpu_edgematch *ems;
   msgpu_order     *order_scr; // slot em_off + i for the i-th order of an edge
   uint32_t        *ids_scr;   // slots em_off .. em_off + em_cnt of an edge
-  uint32_t        *edge_norders, *edge_nids;
   uint32_t        *err;
   const uint32_t  *pair_tab; // four tables (sweep width 64, 32, 16, 8) of PAIR_TAB_STRIDE entries: k | l << 8 | run << 16
   const uint32_t  *pair_tab64; // the width-64 table with every field k_chain's sweep needs ready to use (k_fill_pair_tab)
@@ -124,7 +123,6 @@ constexpr uint32_t COMPACT_CHUNK = 1024; // edges per workgroup of k_compact = p
 struct CompactArgs {
   msgpu_edge        *edges;
   uint64_t           n_edges;
-  const uint32_t    *edge_norders, *edge_nids;
   const unsigned long long *chunk_sums; // [2 n_chunks], left by the chain kernels
   uint32_t           n_chunks;          // ceil(n_edges / COMPACT_CHUNK)
   // the read-back of the table sizes rides on workgroup 0: it writes them into the scalar block (device; SC_TOTAL_A / _B / _C:

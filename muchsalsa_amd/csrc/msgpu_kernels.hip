@@ -1524,6 +1524,12 @@ __device__ __forceinline__ void chunk_add(unsigned long long *chunk_sums, uint64
   __hip_atomic_fetch_add(c, (clean ? 1ull : 0ull) | (banded ? 1ull << 16 : 0ull) | (static_cast<unsigned long long>(n_orders) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_fetch_add(c + 1, static_cast<unsigned long long>(n_ids), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// What a chain kernel leaves of an edge for k_compact, in the second half of the edge's own record and as ONE 16-byte store:
+// order_off = the edge's ids, order_cnt = its orders (k_compact reads the record once and turns order_off into the position),
+// em_cnt as it was and shadow.  An edge no chain kernel visits keeps k_emit_edges' zeros.
+__device__ __forceinline__ void edge_counts(msgpu_edge *edges, uint64_t e, uint32_t em_cnt, uint32_t n_orders, uint32_t n_ids, bool shadow) {
+  reinterpret_cast<uint4 *>(&edges[e])[1] = make_uint4(n_ids, 0u, em_cnt, (n_orders & 0xffffu) | (shadow ? 1u << 16 : 0u));
+}
 __device__ __forceinline__ void band_fallback_add(unsigned long long *chunk_sums, uint64_t n_edges) {
   __hip_atomic_fetch_add(chunk_sums + 2 * (n_edges / COMPACT_CHUNK + 1), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -2215,9 +2221,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     }
   }
   if (lane == 0) {
-    a.edge_norders[e] = n_orders;
-    a.edge_nids[e]    = n_ids;
-    a.edges[e].shadow = shadow ? 1 : 0;
+    edge_counts(a.edges, e, n, n_orders, n_ids, shadow);
     chunk_add(a.chunk_sums, e, clean, n_orders, n_ids, banded);
   }
 }
@@ -2780,9 +2784,7 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
     }
   }
   if (n && sl == 0) {
-    a.edge_norders[e] = n_orders;
-    a.edge_nids[e]    = n_ids;
-    a.edges[e].shadow = shadow ? 1 : 0;
+    edge_counts(a.edges, e, n, n_orders, n_ids, shadow);
     chunk_add(a.chunk_sums, e, clean, n_orders, n_ids);
   }
 }
@@ -3275,9 +3277,7 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainArgs a, const uint32_t *b
         n_ids += cnt;
       }
     }
-    a.edge_norders[e] = n_orders;
-    a.edge_nids[e]    = n_ids;
-    a.edges[e].shadow = shadow ? 1 : 0;
+    edge_counts(a.edges, e, n, n_orders, n_ids, shadow);
     chunk_add(a.chunk_sums, e, false, n_orders, n_ids);
   }
 }
@@ -3352,16 +3352,35 @@ __global__ __launch_bounds__(256) void k_fill_pair_tab(uint32_t *tab) {
 // ones before its own are its base, all of them the table sizes.  Workgroup 0 writes the sizes into the scalar block and
 // publishes the block to the host AT ONCE (publish_to_host): the host turns around while the tables are still being
 // written.  Then the prefix inside the chunk (a block scan over the per-edge counts), then the move.
+
+// the last edge le of the chunk with tab[le] <= x: tab is an exclusive prefix (ascending, tab[0] = 0), so for x below the
+// chunk's total that is the edge whose range holds x -- edges of no element, which share their successor's prefix, are
+// stepped over.  Ten LDS reads.
+__device__ __forceinline__ uint32_t compact_find(const uint32_t *tab, uint32_t x) {
+  uint32_t le = 0;
+#pragma unroll
+  for (uint32_t s = COMPACT_CHUNK / 2; s; s >>= 1)
+    if (tab[le + s] <= x) le += s;
+  return le;
+}
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_compact(CompactArgs a) {
   __shared__ unsigned long long s_red[16][5], s_tot[5], s_em[COMPACT_CHUNK];
-  __shared__ uint32_t           s_ob[COMPACT_CHUNK], s_ib[COMPACT_CHUNK], s_no[COMPACT_CHUNK], s_w[2][16];
+  __shared__ uint32_t           s_ob[COMPACT_CHUNK + 1], s_ib[COMPACT_CHUNK + 1], s_w[2][16];
   static_assert(COMPACT_CHUNK == 1024, "an edge per thread");
   const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t chunk = blockIdx.x;
-  // (this thread's edge: asked for now, used behind the sums below -- one wait instead of two in a row)
-  const uint64_t my_e  = static_cast<uint64_t>(chunk) * COMPACT_CHUNK + threadIdx.x;
-  const uint32_t my_no = my_e < a.n_edges ? a.edge_norders[my_e] : 0u, my_ni = my_e < a.n_edges ? a.edge_nids[my_e] : 0u;
-  const uint64_t my_em = my_e < a.n_edges ? a.edges[my_e].em_off : 0ull;
+  // (this thread's edge: asked for now, used behind the sums below -- one wait instead of two in a row.  The chain kernels
+  // left their counts in the record's second half: order_off = ids, order_cnt = orders, beside em_cnt and shadow.)
+  const uint64_t my_e = static_cast<uint64_t>(chunk) * COMPACT_CHUNK + threadIdx.x;
+  uint4          my_lo = make_uint4(0, 0, 0, 0), my_hi = make_uint4(0, 0, 0, 0);
+  if (my_e < a.n_edges) {
+    const uint4 *p = reinterpret_cast<const uint4 *>(&a.edges[my_e]);
+    my_lo          = p[0];
+    my_hi          = p[1];
+  }
+  static_assert(sizeof(msgpu_edge) == 32 && offsetof(msgpu_edge, em_off) == 8 && offsetof(msgpu_edge, order_off) == 16 &&
+                    offsetof(msgpu_edge, em_cnt) == 24 && offsetof(msgpu_edge, order_cnt) == 28,
+                "the edge record as two 16-byte halves");
   unsigned long long t[5] = {0, 0, 0, 0, 0}; // orders, ids of the chunks before this one | orders, ids, shortcut edges of all chunks
   for (uint32_t c = threadIdx.x; c < a.n_chunks; c += 1024) {
     const unsigned long long w0 = a.chunk_sums[2 * c], w1 = a.chunk_sums[2 * c + 1];
@@ -3402,16 +3421,17 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     publish_to_host(a.pub, lane, lane == SC_TOTAL_A ? tot_o : lane == SC_TOTAL_B ? tot_i : lane == SC_TOTAL_C ? tot_f : lane < SC_COUNT ? a.scalars[lane] : 0ull);
   }
   // (may be launched before the host knows the table sizes, into whatever the tables hold from earlier calls: if they do not
-  // fit nothing is written; the host, which compares the same numbers, allocates and launches again)
+  // fit nothing is written -- the edge records keep the chain kernels' counts; the host, which compares the same numbers,
+  // allocates and launches again)
   if (tot_o > a.cap_orders || tot_i > a.cap_ids) return;
   const uint64_t e0 = static_cast<uint64_t>(chunk) * COMPACT_CHUNK;
   if (e0 >= a.n_edges) return;
   {
-    // prefix inside the chunk: an edge per thread.  What the move below needs of the edge -- its order count and where its
-    // scratch begins -- is read here too, beside the counts, and handed over through LDS: the move's chain of dependent reads
-    // (edge -> order record -> ids) is one read shorter, and the four rounds of it start together.
-    const uint32_t no = my_no, ni = my_ni;
-    const uint64_t em = my_em;
+    // prefix inside the chunk: an edge per thread, which also finishes its edge's record here -- the second half {order_off,
+    // em_cnt, order_cnt, shadow} leaves as ONE 16-byte store (em_cnt, order_cnt and shadow are what was read).  The moves
+    // below find an edge's prefixes and the start of its scratch in LDS.
+    const uint32_t no = my_hi.w & 0xffffu, ni = my_hi.x;
+    const uint64_t em = static_cast<uint64_t>(my_lo.z) | (static_cast<uint64_t>(my_lo.w) << 32);
     const uint32_t io = wave_incl_scan(no), ii = wave_incl_scan(ni);
     if (lane == 63) {
       s_w[0][wave] = io;
@@ -3425,55 +3445,73 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     }
     s_ob[threadIdx.x] = bo;
     s_ib[threadIdx.x] = bi;
-    s_no[threadIdx.x] = no;
     s_em[threadIdx.x] = em;
+    if (threadIdx.x == COMPACT_CHUNK - 1) { // the chunk's totals close the prefix tables
+      s_ob[COMPACT_CHUNK] = bo + no;
+      s_ib[COMPACT_CHUNK] = bi + ni;
+    }
+    if (my_e < a.n_edges) { // cross references leave as positions in the whole job's tables (a batch / shard adds its bases)
+      const uint64_t oo = base_o + bo + a.out_order_base;
+      reinterpret_cast<uint4 *>(&a.edges[my_e])[1] = make_uint4(static_cast<uint32_t>(oo), static_cast<uint32_t>(oo >> 32), my_hi.z, my_hi.w);
+      if (a.out_em_base) a.edges[my_e].em_off = em + a.out_em_base;
+    }
   }
   __syncthreads();
-  // Four lanes per edge, sixteen edges per wavefront, four rounds per workgroup: a lane moves one 16-byte quarter of an
-  // order record and every fourth id.  (Most edges have one order; the dependent chain "order record -> id count ->
-  // ids" is then as long as a single edge's, not sixteen of them in a row.)  The kernel waits on memory: what counts is how
-  // many such chains a CU has in flight -- two workgroups (64 registers a lane: the rounds are NOT unrolled into each other,
-  // which took 96 and left room for one).
-  constexpr int ROUNDS = COMPACT_CHUNK / 256;
-  const int     sub = lane & 3;
-#pragma unroll 1
-  for (int round = 0; round < ROUNDS; ++round) {
-    const uint32_t le   = round * 256 + wave * 16 + (lane >> 2);
-    const uint64_t e    = e0 + le;
-    const bool     have = e < a.n_edges;
-    const uint32_t no   = have ? s_no[le] : 0u;
-    const uint64_t em_off = s_em[le];
-    uint64_t       oo = 0, io = 0;
-    if (have) {
-      oo = base_o + s_ob[le];
-      io = base_i + s_ib[le];
-      if (sub == 0) { // cross references leave as positions in the whole job's tables (a batch / shard adds its bases)
-        a.edges[e].order_off = oo + a.out_order_base;
-        a.edges[e].order_cnt = static_cast<uint16_t>(no);
-        a.edges[e].em_off    = em_off + a.out_em_base;
+  const uint32_t n_o = s_ob[COMPACT_CHUNK], n_i = s_ib[COMPACT_CHUNK];
+  // The orders, by SLOT of the chunk's output range [base_o, base_o + n_o): four lanes per slot, each moves one 16-byte
+  // quarter; the slot's edge comes from the prefix table, so edges of no order cost nothing and edges of several are as
+  // parallel as the others.  The loads of ORD_U rounds leave before the first store.  (A load beyond the last slot is aimed at
+  // the last slot and dropped: a branch round a load makes the compiler wait for every load on its own.)
+  constexpr uint32_t ORD_U = 4, IDS_U = 8;
+  if (n_o) {
+    const uint32_t sub = threadIdx.x & 3, sl = threadIdx.x >> 2;
+    for (uint32_t s0 = 0;;) {
+      const uint32_t rem = n_o - s0;
+      uint4          w[ORD_U];
+      uint32_t       ib[ORD_U];
+#pragma unroll
+      for (uint32_t k = 0; k < ORD_U; ++k) {
+        const uint32_t s  = s0 + min(k * (COMPACT_CHUNK / 4) + sl, rem - 1);
+        const uint32_t le = compact_find(s_ob, s);
+        w[k]  = reinterpret_cast<const uint4 *>(&a.order_scr[s_em[le] + (s - s_ob[le])])[sub];
+        ib[k] = s_ib[le];
       }
+#pragma unroll
+      for (uint32_t k = 0; k < ORD_U; ++k) {
+        const uint32_t off = k * (COMPACT_CHUNK / 4) + sl;
+        // msgpu_order as 16 dwords: [0] = edge_idx, [8,9] = ids_off (edge-relative in the scratch) -- the third quarter's own
+        if (sub == 0) w[k].x += a.out_edge_base;
+        if (sub == 2) {
+          const uint64_t gio = a.out_ids_base + base_i + ib[k] + w[k].x;
+          w[k].x = static_cast<uint32_t>(gio);
+          w[k].y = static_cast<uint32_t>(gio >> 32);
+        }
+        if (off < rem) reinterpret_cast<uint4 *>(&a.orders[base_o + s0 + off])[sub] = w[k];
+      }
+      if (rem <= ORD_U * (COMPACT_CHUNK / 4)) break;
+      s0 += ORD_U * (COMPACT_CHUNK / 4);
     }
-    uint32_t max_no = no; // every lane runs the same number of rounds (shuffles inside)
-    for (int d = 32; d >= 4; d >>= 1) max_no = max(max_no, static_cast<uint32_t>(__shfl_xor(static_cast<int>(max_no), d)));
-    for (uint32_t i = 0; i < max_no; ++i) {
-      const bool on = i < no;
-      uint4      w  = make_uint4(0, 0, 0, 0);
-      if (on) w = reinterpret_cast<const uint4 *>(&a.order_scr[em_off + i])[sub];
-      // msgpu_order as 16 dwords: [8,9] = ids_off (edge-relative in the scratch), [10] = ids_cnt -- the third quarter
-      const int      q2  = (lane & ~3) + 2;
-      const uint32_t rel = static_cast<uint32_t>(__shfl(static_cast<int>(w.x), q2));
-      const uint32_t cnt = static_cast<uint32_t>(__shfl(static_cast<int>(w.z), q2));
-      if (sub == 2) {
-        const uint64_t gio = io + a.out_ids_base;
-        w.x = static_cast<uint32_t>(gio);
-        w.y = static_cast<uint32_t>(gio >> 32);
+  }
+  // The ids, as the flat range [base_i, base_i + n_i) they are: consecutive lanes write consecutive dwords.  An edge's ids are
+  // ONE run of its scratch (the chain kernels place order after order at em_off + n_ids), so dword q of the chunk is dword
+  // q - s_ib[le] of its edge's run and no order record is read on the way.
+  if (n_i) {
+    for (uint32_t q0 = 0;;) {
+      const uint32_t rem = n_i - q0;
+      uint32_t       v[IDS_U];
+#pragma unroll
+      for (uint32_t k = 0; k < IDS_U; ++k) {
+        const uint32_t q  = q0 + min(k * COMPACT_CHUNK + threadIdx.x, rem - 1);
+        const uint32_t le = compact_find(s_ib, q);
+        v[k] = a.ids_scr[s_em[le] + (q - s_ib[le])];
       }
-      if (sub == 0) w.x += a.out_edge_base; // dword 0 = edge_idx
-      if (on) {
-        reinterpret_cast<uint4 *>(&a.orders[oo + i])[sub] = w;
-        for (uint32_t q = sub; q < cnt; q += 4) a.ids[io + q] = a.ids_scr[em_off + rel + q];
-        io += cnt;
+#pragma unroll
+      for (uint32_t k = 0; k < IDS_U; ++k) {
+        const uint32_t off = k * COMPACT_CHUNK + threadIdx.x;
+        if (off < rem) a.ids[base_i + q0 + off] = v[k];
       }
+      if (rem <= IDS_U * COMPACT_CHUNK) break;
+      q0 += IDS_U * COMPACT_CHUNK;
     }
   }
 }
