@@ -62,17 +62,22 @@ def chain(q, t, qlen, ts, te, runs, strand=0, qs=0, qe=None, score=100, matches=
 
 def case(draft, scripts, params=None, note="", names=None):
     """``scripts``: per read (target record, t_start, script) or a dict with more: strand, flanks (bases put around the read),
-    score, matches, block, read (the index of an earlier read that this chain belongs to)"""
+    score, matches, block, read (the index of an earlier read that this chain belongs to; qs: where in that read the chain
+    starts, 0 if it is not given); a dict with ``bases`` alone is a read record without a chain"""
     if isinstance(draft, bytes):
         draft = [(b"d0", draft)]
     reads, chains, runs = [], [], []
     for n, s in enumerate(scripts):
         s = s if isinstance(s, dict) else dict(t=s[0], ts=s[1], script=s[2])
+        if "bases" in s:
+            reads.append((b"r%d" % len(reads), s["bases"]))
+            continue
         seq, r, te = aligned(draft[s["t"]][1], s["ts"], s["script"])
         left, right = s.get("flanks", (b"", b""))
         if "read" in s:
             q = s["read"]  # a further chain of an earlier read: its columns read that read's first bytes, whatever the script says
-            assert not left and not right and len(seq) <= len(reads[q][1]) and not s.get("strand")
+            assert not left and not right and s.get("qs", 0) + len(seq) <= len(reads[q][1]) and not s.get("strand")
+            left = reads[q][1][:s.get("qs", 0)]
         else:
             q = len(reads)
             whole = left + seq + right
