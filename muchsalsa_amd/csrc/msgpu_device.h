@@ -1,5 +1,6 @@
 // msgpu_device.h -- device-side helpers shared by the kernel files (msgpu_kernels.hip, msgpu_index.hip): 32-byte and 16-byte row
-// loads / stores, readlane of wide types, wavefront and workgroup scans.  gfx950, wave64.
+// loads / stores, readlane of wide types, wavefront and workgroup scans; and the records of a sequence store with their lookup
+// (msgpu_map.hip, msgpu_polish.hip).  gfx950, wave64.
 #ifndef MSGPU_DEVICE_H
 #define MSGPU_DEVICE_H
 
@@ -271,6 +272,31 @@ __device__ __forceinline__ void note_first_row(int lane, unsigned long long key,
     read_first[r] = static_cast<uint32_t>(key >> 32);
     read_len[r]   = rows[static_cast<uint32_t>(key)].read_len;
   }
+}
+
+// ---- the records of a sequence store as the kernels of the stages see them (msgpu_stage.h, stage_load, fills one)
+
+constexpr uint32_t REC_NONE = 0xffffffffu;
+
+struct SeqRecs {
+  const uint8_t  *bases;
+  const uint64_t *off; // ascending
+  const uint32_t *len; // (a zero behind the n lengths)
+  uint32_t        n;
+  uint64_t        n_bases;
+};
+
+// the record that holds byte p of the store, or REC_NONE (padding between records)
+__device__ inline uint32_t seq_record(const SeqRecs &R, uint64_t p) {
+  uint32_t lo = 0, hi = R.n; // the last r with off[r] <= p
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (R.off[mid] <= p) lo = mid + 1;
+    else hi = mid;
+  }
+  if (!lo) return REC_NONE;
+  const uint32_t r = lo - 1;
+  return p < R.off[r] + R.len[r] ? r : REC_NONE;
 }
 
 __device__ __forceinline__ bool key_less(int alo, int ahi, uint32_t aan, int blo, int bhi, uint32_t ban) {

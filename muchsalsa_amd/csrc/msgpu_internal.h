@@ -326,11 +326,15 @@ void launch_em_counts(hipStream_t st, const msgpu_edge *edges, const uint32_t *s
 void launch_em_gather(hipStream_t st, const msgpu_edge *edges, const msgpu_edgematch *ems, const uint32_t *sel, uint64_t n,
                       const uint64_t *off, msgpu_edgematch *out);
 
-// msgpu_seq.hip, for the mapper (msgpu_map.hip): the byte-per-base form of a store on the device (null when it is packed or
-// empty), and the furthest-reaching edit distance of msgpu_edit_distance on a DEVICE pair list, distances left on the device
+// msgpu_seq.hip, for the stages that read a store's bases: the byte-per-base form of a store on the device (null when it is
+// packed or empty)
 const uint8_t *seq_store_bases(const msgpu_seqctx *c, int kind, uint64_t *n_bases);
+// msgpu_align.hip, for msgpu_seq.hip's entry points and the mapper (msgpu_map.hip): the edit distance of msgpu_edit_distance
+// on a DEVICE pair list, distances left on the device; dp: by the anti-diagonal banded DP instead of the furthest-reaching
+// form (the same numbers).  ED_MAXW is the widest band of every routine of the file.
+constexpr uint32_t ED_MAXW = 127;
 void launch_edit_distance_pairs(hipStream_t st, const uint8_t *d_a, const uint8_t *d_b, const msgpu_align_pair *d_pairs, uint32_t n,
-                                uint32_t band, uint32_t *d_out);
+                                uint32_t band, uint32_t *d_out, bool dp);
 // The edit scripts of msgpu_edit_script on a DEVICE pair list, behind the distance pass (d_dist): d_len gets n + 1 words whose
 // exclusive 64-bit scan is d_off; the words of pair p go to d_words[d_off[p] .. d_off[p + 1]) and stay on the device.  d_list
 // (n words) and d_cnt (ES_CNT_COUNT words, zeroed by the call) are the classes' lists and counters, d_slab the

@@ -17,9 +17,9 @@
 //                  predecessors of anchor i are one per lane; argmax by DPP / permlane moves (group_max_i64)
 //   k_mp_chain16   the same for groups of at most 16 anchors, four to a wavefront, a row of 16 lanes each
 //   k_mp_walk      rule 6 behind a segmented sort by (f descending, index ascending): a thread per group
-//   k_mp_pairs     exact mode: the segment pairs of the emitted chains; distances by edit_distance_fr_wave (msgpu_seq.hip)
-//                  against a forward and a reverse-complemented copy of the queries (the existing gather)
-//   cigar mode     rule 10 behind the distances: the scripts' offsets (a scan), launch_edit_script_pairs (msgpu_seq.hip),
+//   k_mp_pairs     exact mode: the segment pairs of the emitted chains; distances by edit_distance_fr_wave (msgpu_align.hip)
+//                  against a forward and a reverse-complemented copy of the queries (the existing gather, mp_oriented)
+//   cigar mode     rule 10 behind the distances: the scripts' offsets (a scan), launch_edit_script_pairs (msgpu_align.hip),
 //                  k_mp_columns per pair, two segmented reductions and k_mp_cigar per chain; the host merges the runs
 //   ranking        rule 12, on request, behind k_mp_table: the chains of a query record are a segment (k_rk_heads, a scan);
 //                  k_rk_wave ranks a segment of at most 64 chains in one wavefront, a lane per chain; k_rk_list walks a longer
@@ -42,35 +42,13 @@
 
 namespace msgpu {
 
-constexpr uint32_t MP_NONE = 0xffffffffu;
 constexpr long long MP_MIN = static_cast<long long>(0x8000000000000000ull);
-
-struct MpRecs { // the records of a store as the kernels see them
-  const uint8_t  *bases;
-  const uint64_t *off; // ascending
-  const uint32_t *len;
-  uint32_t        n;
-  uint64_t        n_bases;
-};
-
-// the record that holds byte p of the store, or MP_NONE (padding between records)
-__device__ inline uint32_t mp_record(const MpRecs &R, uint64_t p) {
-  uint32_t lo = 0, hi = R.n; // the last r with off[r] <= p
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (R.off[mid] <= p) lo = mid + 1;
-    else hi = mid;
-  }
-  if (!lo) return MP_NONE;
-  const uint32_t r = lo - 1;
-  return p < R.off[r] + R.len[r] ? r : MP_NONE;
-}
 
 constexpr int MP_TILE = 256, MP_SPAN = MP_TILE + 2 * 63;
 
 // rule 2.  WRITE = false: minimizers per tile; WRITE = true: (key, record << 32 | position << 1 | strand) at the tile's offset
 template <bool WRITE>
-__global__ __launch_bounds__(256) void k_mp_sketch(MpRecs R, int k, int w, uint32_t *tile_cnt, const uint64_t *tile_off,
+__global__ __launch_bounds__(256) void k_mp_sketch(SeqRecs R, int k, int w, uint32_t *tile_cnt, const uint64_t *tile_off,
                                                    uint64_t *keys, uint64_t *vals, uint64_t cap) {
   __shared__ uint64_t s_h[MP_SPAN], s_key[MP_SPAN];
   __shared__ uint8_t  s_v[MP_SPAN]; // bit 0: a k-mer starts here, bit 1: its strand
@@ -82,8 +60,8 @@ __global__ __launch_bounds__(256) void k_mp_sketch(MpRecs R, int k, int w, uint3
     uint8_t         v = 0;
     uint64_t        h = 0, key = 0;
     if (p >= 0 && static_cast<uint64_t>(p) < R.n_bases) {
-      const uint32_t r = mp_record(R, static_cast<uint64_t>(p));
-      if (r != MP_NONE && static_cast<uint64_t>(p) + k <= R.off[r] + R.len[r]) {
+      const uint32_t r = seq_record(R, static_cast<uint64_t>(p));
+      if (r != REC_NONE && static_cast<uint64_t>(p) + k <= R.off[r] + R.len[r]) {
         KfRoll<uint64_t> roll(k);
         bool             ok = false;
         for (int j = 0; j < k; ++j) ok = roll.step(R.bases[p + j], key);
@@ -115,8 +93,8 @@ __global__ __launch_bounds__(256) void k_mp_sketch(MpRecs R, int k, int w, uint3
   }
   if (!is_min) return;
   const uint64_t p = static_cast<uint64_t>(base + e), slot = tile_off[blockIdx.x] + at;
-  const uint32_t r = mp_record(R, p);
-  if (slot < cap && r != MP_NONE) {
+  const uint32_t r = seq_record(R, p);
+  if (slot < cap && r != REC_NONE) {
     keys[slot] = s_key[e];
     vals[slot] = (static_cast<uint64_t>(r) << 32) | ((p - R.off[r]) << 1) | (s_v[e] >> 1);
   }
@@ -805,67 +783,12 @@ static_assert(MP_SC_CAPPED < SC_COUNT, "the scalar block");
 
 inline kf_ull *mp_slot(msgpu_mapctx *c, int slot) { return reinterpret_cast<kf_ull *>(c->sc.d + slot); }
 
-struct MpFile { // a file in its store
-  msgpu_seqfile *f = nullptr;
-  MpRecs         recs{};
-  uint64_t      *d_off = nullptr;
-  uint32_t      *d_len = nullptr;
-  ~MpFile() { msgpu_seq_free(f); }
-};
-
-int mp_load(msgpu_mapctx *c, DevArena &D, const char *path, int kind, const char *what, MpFile &F) {
-  int rc = msgpu_seq_parse_upload(c->seq, kind, path, -1, &F.f);
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "%s %s: %s", what, path, msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  const uint32_t        n = msgpu_seq_count(F.f);
-  std::vector<uint64_t> off;
-  std::vector<uint32_t> len;
-  try {
-    off.resize(n);
-    len.resize(n);
-  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  uint64_t n_bases = 0;
-  F.recs.bases = seq_store_bases(c->seq, kind, &n_bases);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t L = msgpu_seq_length(F.f, i);
-    off[i] = msgpu_seq_offset(F.f, i);
-    if (L >= (1ull << 31)) {
-      snprintf(c->err, sizeof(c->err), "%s record %u has %llu bases; the limit is 2^31 - 1", what, i, static_cast<kf_ull>(L));
-      return MSGPU_E_ARG;
-    }
-    if ((i && off[i] < off[i - 1] + len[i - 1]) || off[i] + L > n_bases) {
-      snprintf(c->err, sizeof(c->err), "%s record %u does not lie behind record %u in the store", what, i, i ? i - 1 : 0);
-      return MSGPU_E_STATE;
-    }
-    len[i] = static_cast<uint32_t>(L);
-  }
-  if (n_bases >= (1ull << 38)) {
-    snprintf(c->err, sizeof(c->err), "%s: %llu bases; the limit is 2^38 - 1", what, static_cast<kf_ull>(n_bases));
-    return MSGPU_E_ARG;
-  }
-  STAGE_HIP(c, D.get(&F.d_off, n));
-  STAGE_HIP(c, D.get(&F.d_len, n + 1ull)); // (a zero behind the lengths: their scan gives n + 1 sums)
-  STAGE_HIP(c, hipMemsetAsync(F.d_len + n, 0, 4, c->stream));
-  if (n) {
-    STAGE_HIP(c, hipMemcpyAsync(F.d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
-    STAGE_HIP(c, hipMemcpyAsync(F.d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
-    STAGE_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  F.recs.off     = F.d_off;
-  F.recs.len     = F.d_len;
-  F.recs.n       = n;
-  F.recs.n_bases = n_bases;
-  return MSGPU_OK;
-}
-
 struct MpSketch {
   uint64_t *keys = nullptr, *vals = nullptr;
   uint64_t  n = 0;
 };
 
-int mp_sketch(msgpu_mapctx *c, DevArena &D, StageClock &clock, float *ms, const MpRecs &R, int k, int w, const char *what, MpSketch &S) {
+int mp_sketch(msgpu_mapctx *c, DevArena &D, StageClock &clock, float *ms, const SeqRecs &R, int k, int w, const char *what, MpSketch &S) {
   hipStream_t    st = c->stream;
   const uint32_t tiles = grid_of(R.n_bases, MP_TILE);
   uint32_t      *d_cnt;
@@ -1053,7 +976,7 @@ uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, 
 struct MpRun { // what stays on the device for the whole run (rule 9), as a batch sees it
   msgpu_mapctx           *c;
   const msgpu_map_params &prm;
-  const MpFile           &Tf, &Qf;
+  const StageFile        &Tf, &Qf;
   const MpSketch         &Qs;
   MpIndex                 X;
   const uint64_t         *d_aoff; // the anchors in front of every query minimizer
@@ -1158,45 +1081,61 @@ void mp_rank_counts(const kf_ull *h, msgpu_map_rstats &S) { // behind the synchr
   S.n_segments_spilled += h[RK_SPILL];
 }
 
+// ---- the batch's oriented query records, for exact mode's segment pairs and for rule 11's flanks
+
+struct MpOriented { // the batch's query records as they are and reverse-complemented, one record behind the other, one copy behind the other
+  uint8_t           *d = nullptr;    // 2 * n_query_bases + 16 bytes of the batch arena; null: not made yet
+  msgpu_gather_plan *plan = nullptr; // (the gather reads it: it lives until the batch's last synchronisation)
+  ~MpOriented() { msgpu_gather_plan_free(plan); }
+};
+
+// once per batch, by whoever needs the copies first.  ms: a span of the clock that begins in front of the gather and stays open
+int mp_oriented(const MpRun &R, DevArena &B, const msgpu_map_batch &bt, float *ms, MpOriented &O) {
+  msgpu_mapctx           *c = R.c;
+  const uint32_t          q0 = bt.first_query, q1 = q0 + bt.n_queries, from = R.qkind ? MSGPU_COPY_ILLUMINA : 0u;
+  const uint64_t          NB = bt.n_query_bases, b0 = R.bpre[q0];
+  std::vector<msgpu_copy> pieces;
+  try {
+    pieces.reserve(2ull * bt.n_queries);
+    for (uint32_t i = q0; i < q1; ++i) {
+      const uint64_t o = msgpu_seq_offset(R.Qf.f, i), at = R.bpre[i] - b0;
+      const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(R.Qf.f, i));
+      pieces.push_back(msgpu_copy{o, at, L, from});
+      pieces.push_back(msgpu_copy{o, NB + at, L, from | MSGPU_COPY_REVCOMP});
+    }
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  int rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &O.plan);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  STAGE_HIP(c, B.get(&O.d, 2 * NB + 16));
+  if (ms) STAGE_HIP(c, R.clock.begin(ms));
+  rc = msgpu_gather_run(c->seq, O.plan, O.d, 2 * NB + 16, c->stream);
+  if (rc != MSGPU_OK) snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
+  return rc;
+}
+
 // ---- rule 11: the ends of a batch's chains
 
 struct MpExtBatch { // what the extension of a batch leaves for the host, valid after the batch's last synchronisation
   std::vector<msgpu_ext_end> ends;  // the left ends of the batch's chains, then the right ends
   std::vector<uint32_t>      words; // band + 1 words per end, e + 1 of them the script
   uint32_t                   broken = 0;
-  msgpu_gather_plan         *plan = nullptr; // (of a batch without a segment pair, which has no oriented copies yet)
-  ~MpExtBatch() { msgpu_gather_plan_free(plan); }
 };
 
 // the descriptors (k_mp_ends), the extension of the left ends and of the right ends (launch_extend_ends), and their way back
-int mp_extend(const MpRun &R, DevArena &B, const msgpu_map_batch &bt, const msgpu_map_chain *d_chains, uint32_t C_n, uint8_t *d_or,
+int mp_extend(const MpRun &R, DevArena &B, const msgpu_map_batch &bt, const msgpu_map_chain *d_chains, uint32_t C_n, MpOriented &O,
               uint32_t *d_slab, MpExtBatch &xb) {
   msgpu_mapctx  *c = R.c;
   hipStream_t    st = c->stream;
-  const uint32_t band = static_cast<uint32_t>(R.prm.band), slots = edit_script_slots(), q0 = bt.first_query, q1 = q0 + bt.n_queries;
-  const uint64_t NB = bt.n_query_bases, b0 = R.bpre[q0], stride = band + 1ull, slab_words = edit_script_slab_words(slots, band);
-  if (!d_or) { // the batch's query records as they are and reverse-complemented, as exact mode lays them out
-    const uint32_t          from = R.qkind ? MSGPU_COPY_ILLUMINA : 0u;
-    std::vector<msgpu_copy> pieces;
-    try {
-      pieces.reserve(2ull * bt.n_queries);
-      for (uint32_t i = q0; i < q1; ++i) {
-        const uint64_t o = msgpu_seq_offset(R.Qf.f, i), at = R.bpre[i] - b0;
-        const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(R.Qf.f, i));
-        pieces.push_back(msgpu_copy{o, at, L, from});
-        pieces.push_back(msgpu_copy{o, NB + at, L, from | MSGPU_COPY_REVCOMP});
-      }
-    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-    int rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &xb.plan);
-    if (rc == MSGPU_OK) {
-      STAGE_HIP(c, B.get(&d_or, 2 * NB + 16));
-      rc = msgpu_gather_run(c->seq, xb.plan, d_or, 2 * NB + 16, st);
-    }
-    if (rc != MSGPU_OK) {
-      snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
-      return rc;
-    }
+  const uint32_t band = static_cast<uint32_t>(R.prm.band), slots = edit_script_slots();
+  const uint64_t NB = bt.n_query_bases, b0 = R.bpre[bt.first_query], stride = band + 1ull, slab_words = edit_script_slab_words(slots, band);
+  if (!O.d) { // (a batch without a segment pair)
+    const int rc = mp_oriented(R, B, bt, nullptr, O);
+    if (rc != MSGPU_OK) return rc;
   }
+  const uint8_t *const d_or = O.d;
   if (!d_slab && slab_words) STAGE_HIP(c, B.get(&d_slab, slab_words));
   msgpu_align_pair *d_pairs;
   msgpu_ext_end    *d_ends;
@@ -1211,7 +1150,7 @@ int mp_extend(const MpRun &R, DevArena &B, const msgpu_map_batch &bt, const msgp
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   STAGE_HIP(c, hipMemsetAsync(d_broken, 0, 4, st));
   STAGE_HIP(c, R.clock.begin(&R.res->xstats.extend_ms));
-  hipLaunchKernelGGL(k_mp_ends, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, R.Tf.d_off, R.Tf.d_len, R.d_bpre, R.Qf.d_len, b0, NB, R.extend,
+  hipLaunchKernelGGL(k_mp_ends, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, R.Tf.recs.off, R.Tf.recs.len, R.d_bpre, R.Qf.recs.len, b0, NB, R.extend,
                      d_pairs);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, launch_extend_ends(st, R.Tf.recs.bases, d_or, d_pairs, C_n, band, true, d_slab, slots, d_ends, d_words, d_broken));
@@ -1322,7 +1261,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   STAGE_HIP(c, B.get(&d_gcnt, A + 1ull));
   STAGE_HIP(c, B.get(&d_gstart, A + 1ull));
   STAGE_HIP(c, clock.begin(&S.anchors_ms));
-  hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(m1 - m0)), dim3(256), 0, st, R.X, R.Qs.keys, R.Qs.vals, m0, m1, R.Qf.d_len, k, prm.ava,
+  hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(m1 - m0)), dim3(256), 0, st, R.X, R.Qs.keys, R.Qs.vals, m0, m1, R.Qf.recs.len, k, prm.ava,
                      nullptr, R.d_aoff, d_g[0], d_xy[0], A);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, clock.end());
@@ -1398,6 +1337,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
 
   // ---- rule 6
   uint32_t   C_n = 0;
+  MpOriented O;  // exact mode with a segment pair makes the copies, rule 11 otherwise
   MpExtBatch xb; // rule 11: what comes back with the chain table
   kf_ull          h_rk[RK_COUNT] = {}; // rule 12: the counters, likewise
   msgpu_map_rank *d_rows = nullptr;
@@ -1430,7 +1370,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
     STAGE_HIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
     STAGE_HIP(c, clock.begin(&S.backtrack_ms));
     hipLaunchKernelGGL(k_mp_table, dim3(grid256(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
-                       R.Qf.d_len, k, d_chains, d_where, d_np, C_n);
+                       R.Qf.recs.len, k, d_chains, d_where, d_np, C_n);
     STAGE_HIP(c, hipGetLastError());
     STAGE_HIP(c, clock.end());
 
@@ -1447,8 +1387,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
       if (rc != MSGPU_OK) return rc;
     }
 
-    uint8_t  *d_or = nullptr;   // the batch's oriented query records (exact mode with a segment pair; rule 11 makes its own otherwise)
-    uint32_t *d_slab = nullptr; // the tables of the slab class (cigar mode with a segment pair; likewise)
+    uint32_t *d_slab = nullptr; // the tables of the slab class (cigar mode with a segment pair; rule 11 takes its own otherwise)
 
     // ---- rule 7 in exact mode
     if (exact) {
@@ -1461,32 +1400,12 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
       bt.n_pairs = P;
       S.n_pairs += P;
       if (P) {
-        // the batch's query records as they are and reverse-complemented, one record behind the other, one copy behind the other
-        const uint64_t          NB = bt.n_query_bases, b0 = R.bpre[q0];
-        const uint32_t          from = R.qkind ? MSGPU_COPY_ILLUMINA : 0u;
-        std::vector<msgpu_copy> pieces;
-        try {
-          pieces.reserve(2ull * bt.n_queries);
-          for (uint32_t i = q0; i < q1; ++i) {
-            const uint64_t o = msgpu_seq_offset(R.Qf.f, i), at = R.bpre[i] - b0;
-            const uint32_t L = static_cast<uint32_t>(msgpu_seq_length(R.Qf.f, i));
-            pieces.push_back(msgpu_copy{o, at, L, from});
-            pieces.push_back(msgpu_copy{o, NB + at, L, from | MSGPU_COPY_REVCOMP});
-          }
-        } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-        msgpu_gather_plan *plan = nullptr;
-        rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
-        if (rc != MSGPU_OK) {
-          snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
-          return rc;
-        }
-        struct FreePlan {
-          msgpu_gather_plan *p;
-          ~FreePlan() { msgpu_gather_plan_free(p); }
-        } free_plan{plan};
+        const uint64_t    NB = bt.n_query_bases, b0 = R.bpre[q0];
         msgpu_align_pair *d_pairs;
         uint32_t         *d_dist, *d_nm = nullptr, *d_trail = nullptr, *d_head = nullptr;
-        STAGE_HIP(c, B.get(&d_or, 2 * NB + 16));
+        rc = mp_oriented(R, B, bt, &S.pairs_ms, O); // (the gather opens the span of the pairs)
+        if (rc != MSGPU_OK) return rc;
+        const uint8_t *const d_or = O.d;
         STAGE_HIP(c, B.get(&d_pairs, P));
         STAGE_HIP(c, B.get(&d_dist, P));
         if (!cigar) STAGE_HIP(c, B.get(&d_nm, C_n));
@@ -1494,18 +1413,12 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
           STAGE_HIP(c, B.get(&d_trail, P));
           STAGE_HIP(c, B.get(&d_head, C_n));
         }
-        STAGE_HIP(c, clock.begin(&S.pairs_ms));
-        rc = msgpu_gather_run(c->seq, plan, d_or, 2 * NB + 16, st);
-        if (rc != MSGPU_OK) {
-          snprintf(c->err, sizeof(c->err), "gather: %s", msgpu_seq_last_error(c->seq));
-          return rc;
-        }
-        hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, R.Tf.d_off, R.d_bpre,
+        hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, R.Tf.recs.off, R.d_bpre,
                            b0, NB, k, d_pairs, P, d_trail, d_head);
         STAGE_HIP(c, hipGetLastError());
         STAGE_HIP(c, clock.end());
         STAGE_HIP(c, clock.begin(&S.distance_ms));
-        launch_edit_distance_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist);
+        launch_edit_distance_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist, false);
         STAGE_HIP(c, hipGetLastError());
         if (!cigar)
           STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
@@ -1606,13 +1519,12 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
           AS.i_columns += h_xid[2];
           AS.script_words += Wn;
         }
-        STAGE_HIP(c, hipStreamSynchronize(st)); // (the plan goes with this scope)
       }
     }
 
     // ---- rule 11: the ends of every chain, behind the scripts (the slab is theirs first)
     if (R.extend) {
-      rc = mp_extend(R, B, bt, d_chains, C_n, d_or, d_slab, xb);
+      rc = mp_extend(R, B, bt, d_chains, C_n, O, d_slab, xb);
       if (rc != MSGPU_OK) return rc;
     }
 
@@ -1656,7 +1568,7 @@ struct msgpu_map_index {
   int           kind = 1; // the store of owner->seq that holds the targets; a run's queries go into the other one
   int           k = 0, w = 0;
   DevArena      D;
-  MpFile        Tf;
+  StageFile     Tf;
   MpSketch      Ts;
   uint64_t     *d_ivals = nullptr, *d_ukeys = nullptr;
   uint32_t     *d_ucnt = nullptr, *d_ustart = nullptr, *d_slots = nullptr;
@@ -1675,7 +1587,7 @@ int mp_index_build(msgpu_mapctx *c, int k, int w, const char *tpath, msgpu_map_i
   const StageTimer wall;
   I.k = k;
   I.w = w;
-  int rc = mp_load(c, D, tpath, I.kind, "targets", I.Tf);
+  int rc = stage_load(c, D, tpath, I.kind, "targets", I.Tf);
   if (rc != MSGPU_OK) return rc;
   I.load_ms = wall.ms();
 
@@ -1746,14 +1658,14 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   STAGE_HIP(c, hipMemsetAsync(c->sc.d, 0, SC_COUNT * sizeof(uint64_t), st));
 
   // ---- the query file (ava: the index's own store and sketch)
-  const MpFile &Tf = I.Tf;
-  MpFile        Qf_own;
+  const StageFile &Tf = I.Tf;
+  StageFile     Qf_own;
   int           rc;
   if (!ava) {
-    rc = mp_load(c, D, qpath, 1 - I.kind, "queries", Qf_own);
+    rc = stage_load(c, D, qpath, 1 - I.kind, "queries", Qf_own);
     if (rc != MSGPU_OK) return rc;
   }
-  const MpFile &Qf = ava ? Tf : Qf_own;
+  const StageFile &Qf = ava ? Tf : Qf_own;
   const int     qkind = ava ? I.kind : 1 - I.kind;
   S.n_records[0] = Tf.recs.n;
   S.n_records[1] = Qf.recs.n;
@@ -1799,13 +1711,13 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   STAGE_HIP(c, hipMemsetAsync(d_acnt + NQ, 0, 4, st));
   STAGE_HIP(c, clock.begin(&S.anchors_ms));
   if (NQ)
-    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, 0, NQ, Qf.d_len, k, prm.ava, d_acnt,
+    hipLaunchKernelGGL((k_mp_anchors<false>), dim3(grid256(NQ)), dim3(256), 0, st, X, Qs.keys, Qs.vals, 0, NQ, Qf.recs.len, k, prm.ava, d_acnt,
                        nullptr, nullptr, nullptr, 0);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_acnt, d_aoff, NQ + 1));
   hipLaunchKernelGGL(k_mp_prefix, dim3(grid256(NR + 1ull)), dim3(256), 0, st, Qs.vals, NQ, d_aoff, NR, d_pre + 2 * (NR + 1ull), d_pre);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, Qf.d_len, d_pre + (NR + 1ull), NR + 1ull)); // (mp_load: a zero behind the lengths)
+  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, Qf.recs.len, d_pre + (NR + 1ull), NR + 1ull)); // (stage_load: a zero behind the lengths)
   STAGE_HIP(c, clock.end());
   std::vector<uint64_t> pre;
   try {

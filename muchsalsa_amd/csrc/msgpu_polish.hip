@@ -28,7 +28,6 @@
 
 namespace msgpu {
 
-constexpr uint32_t PL_NONE = 0xffffffffu;
 constexpr uint32_t PL_I = 1, PL_D = 2, PL_EQ = 7, PL_X = 8;
 constexpr uint32_t PL_MAX_INS = 32;
 enum { PL_A = 0, PL_C, PL_G, PL_T, PL_DEL, PL_OTHER, PL_CLASSES };
@@ -39,14 +38,6 @@ enum { PL_BAD_ORDER = 0, PL_BAD_STRAND, PL_BAD_QREC, PL_BAD_TREC, PL_BAD_TRANGE,
 enum { PL_ST_VOTERS = 0, PL_ST_IGNORED, PL_ST_EQ, PL_ST_X, PL_ST_D, PL_ST_I, PL_ST_VERBATIM, PL_ST_UNCHANGED, PL_ST_SUBST, PL_ST_DELETED,
        PL_ST_USABLE, PL_ST_UNUSABLE, PL_ST_ENDS, PL_ST_APPLIED, PL_ST_INSERTED, PL_ST_MAXDEPTH, PL_ST_COUNT };
 
-struct PlRecs { // the records of a store as the kernels see them
-  const uint8_t  *bases;
-  const uint64_t *off; // ascending
-  const uint32_t *len;
-  uint32_t        n;
-  uint64_t        n_bases;
-};
-
 struct PlTables { // the chain table and the run tables with their scans
   const msgpu_map_chain *chains;
   const uint64_t        *off;  // n_chains + 1
@@ -54,19 +45,6 @@ struct PlTables { // the chain table and the run tables with their scans
   const uint64_t        *T, *Q; // n_runs + 1: target / query bases that the runs in front of a run consume
   uint32_t               n_chains, n_runs;
 };
-
-// the record that holds byte p of the store, or PL_NONE (padding between records)
-__device__ inline uint32_t pl_record(const PlRecs &R, uint64_t p) {
-  uint32_t lo = 0, hi = R.n; // the last r with off[r] <= p
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (R.off[mid] <= p) lo = mid + 1;
-    else hi = mid;
-  }
-  if (!lo) return PL_NONE;
-  const uint32_t r = lo - 1;
-  return p < R.off[r] + R.len[r] ? r : PL_NONE;
-}
 
 // the last i in [lo, hi) with a[i] <= x (a ascending, a[lo] <= x)
 __device__ inline uint32_t pl_last_le(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t x) {
@@ -104,7 +82,7 @@ __device__ inline uint32_t pl_class(uint8_t b, uint32_t s) {
   return b == 'A' ? PL_A : b == 'C' ? PL_C : b == 'G' ? PL_G : b == 'T' ? PL_T : PL_OTHER;
 }
 // byte j of the chain's stretch of the oriented query, in the query store
-__device__ inline uint8_t pl_query_byte(const PlRecs &Q, const msgpu_map_chain &ch, uint64_t j) {
+__device__ inline uint8_t pl_query_byte(const SeqRecs &Q, const msgpu_map_chain &ch, uint64_t j) {
   const uint64_t qlen = Q.len[ch.query];
   const uint64_t fwd  = ch.strand ? qlen - 1 - (qlen - ch.q_end + j) : ch.q_start + j;
   return Q.bases[Q.off[ch.query] + fwd];
@@ -135,11 +113,11 @@ __global__ __launch_bounds__(256) void k_pl_runs(const uint64_t *off, uint32_t n
 }
 
 // rule 1 on the chain's fields and on what its runs consume
-__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, PlRecs R, PlRecs Q, const msgpu_map_rank *ranks, kf_ull *bad) {
+__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, SeqRecs R, SeqRecs Q, const msgpu_map_rank *ranks, kf_ull *bad) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= X.n_chains) return;
   const msgpu_map_chain ch = X.chains[i];
-  uint32_t              what = PL_NONE;
+  uint32_t              what = ~0u; // (none)
   auto                  found = [&](uint32_t w) { what = w < what ? w : what; };
   if (i && ch.query < X.chains[i - 1].query) found(PL_BAD_ORDER);
   if (ch.strand > 1) found(PL_BAD_STRAND);
@@ -156,7 +134,7 @@ __global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, PlRecs R, Pl
     if (ok) ok = X.chains[r.parent].query == ch.query && ranks[r.parent].parent == r.parent;
     if (!ok) found(PL_BAD_RANK);
   }
-  if (what != PL_NONE) pl_bad(bad, i, what);
+  if (what != ~0u) pl_bad(bad, i, what);
 }
 
 // rule 2 in two order-independent passes: the greatest (score, block) of a query's eligible chains, then the first chain that has it
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(256) void k_pl_spans(const msgpu_map_chain *chains,
 }
 
 // rule 4, the columns: lane g takes column g of the voters' spans laid one behind the other (S = the scan of the spans)
-__global__ __launch_bounds__(256) void k_pl_pileup(PlTables X, const uint64_t *S, uint64_t n_cols, PlRecs R, PlRecs Q, uint32_t *cnt, kf_ull *st) {
+__global__ __launch_bounds__(256) void k_pl_pileup(PlTables X, const uint64_t *S, uint64_t n_cols, SeqRecs R, SeqRecs Q, uint32_t *cnt, kf_ull *st) {
   const uint64_t g = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   const bool     live = g < n_cols;
   uint32_t       op = 0;
@@ -221,7 +199,7 @@ __global__ __launch_bounds__(256) void k_pl_pileup(PlTables X, const uint64_t *S
 // rule 4, the insertion events.  FILL = false: flag[u] = the run is a usable event at a slot 0 < p < tlen, and the counts;
 // FILL = true: event E[u] = (slot in the store << 6 | L, the 2-bit packed letters, the first in the highest bits).
 template <bool FILL>
-__global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_chain, const uint32_t *vidx, const uint32_t *vflag, PlRecs R, PlRecs Q, uint32_t *flag,
+__global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_chain, const uint32_t *vidx, const uint32_t *vflag, SeqRecs R, SeqRecs Q, uint32_t *flag,
                                                 const uint32_t *E, uint64_t *ev_key, uint64_t *ev_seq, kf_ull *st) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   bool           ins = false, ends = false, usable = false;
@@ -277,7 +255,7 @@ __global__ __launch_bounds__(256) void k_pl_best(const uint32_t *gstart, const u
   const uint32_t g = blockIdx.x * 256 + threadIdx.x;
   if (g >= *n_groups) return;
   const uint32_t e = gstart[g], count = gstart[g + 1] - e;
-  atomicMax(&best[key[e] >> 6], (static_cast<kf_ull>(count) << 32) | (PL_NONE - g));
+  atomicMax(&best[key[e] >> 6], (static_cast<kf_ull>(count) << 32) | (0xffffffffu - g));
 }
 
 struct PlCall { // rules 5 and 6 per byte of the draft's store
@@ -298,12 +276,12 @@ __device__ inline uint32_t pl_depth(const uint32_t *cnt, uint64_t plane, uint64_
   return d;
 }
 
-__global__ __launch_bounds__(256) void k_pl_call(PlRecs R, PlCall a, kf_ull *st) {
+__global__ __launch_bounds__(256) void k_pl_call(SeqRecs R, PlCall a, kf_ull *st) {
   const uint64_t pos = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const uint32_t r = pos < R.n_bases ? pl_record(R, pos) : PL_NONE;
+  const uint32_t r = pos < R.n_bases ? seq_record(R, pos) : REC_NONE;
   int            kind = -1; // 0 verbatim, 1 unchanged, 2 substituted, 3 deleted
   uint32_t       depth = 0, ins_len = 0;
-  if (r != PL_NONE) {
+  if (r != REC_NONE) {
     uint32_t v[PL_CLASSES];
     for (int c = 0; c < PL_CLASSES; ++c) {
       v[c] = a.cnt[c * R.n_bases + pos];
@@ -323,7 +301,7 @@ __global__ __launch_bounds__(256) void k_pl_call(PlRecs R, PlCall a, kf_ull *st)
     const kf_ull w = a.best[pos];
     kf_ull       keep = 0;
     if (w && pos > R.off[r]) { // (an event's slot is never a record's first position; the test keeps pos - 1 inside the record)
-      const uint32_t count = static_cast<uint32_t>(w >> 32), e = a.gstart[PL_NONE - static_cast<uint32_t>(w)];
+      const uint32_t count = static_cast<uint32_t>(w >> 32), e = a.gstart[0xffffffffu - static_cast<uint32_t>(w)];
       const uint32_t left = pl_depth(a.cnt, R.n_bases, pos - 1), m = left < depth ? left : depth;
       if (m >= a.min_depth && 2ull * count > m) {
         ins_len = static_cast<uint32_t>(a.key[e] & 63);
@@ -350,7 +328,7 @@ __global__ __launch_bounds__(256) void k_pl_call(PlRecs R, PlCall a, kf_ull *st)
 }
 
 // rule 7: every position's bytes at the scan of the lengths (O), the applied insertion in front of the call
-__global__ __launch_bounds__(256) void k_pl_scatter(PlRecs R, const uint8_t *call, const kf_ull *best, const uint64_t *key, const uint64_t *seq,
+__global__ __launch_bounds__(256) void k_pl_scatter(SeqRecs R, const uint8_t *call, const kf_ull *best, const uint64_t *key, const uint64_t *seq,
                                                     const uint32_t *outlen, const uint64_t *O, uint8_t *raw) {
   const uint64_t pos = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (pos >= R.n_bases || !outlen[pos]) return;
@@ -363,7 +341,7 @@ __global__ __launch_bounds__(256) void k_pl_scatter(PlRecs R, const uint8_t *cal
   }
   if (call[pos] != 1) raw[w] = call[pos] ? call[pos] : R.bases[pos];
 }
-__global__ __launch_bounds__(256) void k_pl_reclen(PlRecs R, const uint64_t *O, uint64_t *rec_start, uint64_t *rec_len) {
+__global__ __launch_bounds__(256) void k_pl_reclen(SeqRecs R, const uint64_t *O, uint64_t *rec_start, uint64_t *rec_len) {
   const uint32_t r = blockIdx.x * 256 + threadIdx.x;
   if (r >= R.n) return;
   rec_start[r] = O[R.off[r]];
@@ -406,59 +384,6 @@ const char *const PL_WHAT[] = {"query order (the chains are not ordered by query
                                "offsets (the run offsets decrease or exceed the run table)",
                                "rank (the parent is out of range, of another query record or no primary, or mapq exceeds 60)"};
 
-struct PlFile { // a file in its store
-  SeqFileHold f;
-  PlRecs      recs{};
-};
-
-int pl_load(msgpu_plctx *c, DevArena &D, const char *path, int kind, const char *what, PlFile &F) {
-  int rc = msgpu_seq_parse_upload(c->seq, kind, path, -1, &F.f.f);
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "%s %s: %s", what, path, msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  const uint32_t        n = msgpu_seq_count(F.f);
-  std::vector<uint64_t> off;
-  std::vector<uint32_t> len;
-  try {
-    off.resize(n);
-    len.resize(n);
-  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  uint64_t n_bases = 0;
-  F.recs.bases = seq_store_bases(c->seq, kind, &n_bases);
-  for (uint32_t i = 0; i < n; ++i) { // the file limits are the mapper's
-    const uint64_t L = msgpu_seq_length(F.f, i);
-    off[i] = msgpu_seq_offset(F.f, i);
-    if (L >= (1ull << 31)) {
-      snprintf(c->err, sizeof(c->err), "%s record %u has %llu bases; the limit is 2^31 - 1", what, i, static_cast<kf_ull>(L));
-      return MSGPU_E_ARG;
-    }
-    if ((i && off[i] < off[i - 1] + len[i - 1]) || off[i] + L > n_bases) {
-      snprintf(c->err, sizeof(c->err), "%s record %u does not lie behind record %u in the store", what, i, i ? i - 1 : 0);
-      return MSGPU_E_STATE;
-    }
-    len[i] = static_cast<uint32_t>(L);
-  }
-  if (n_bases >= (1ull << 38)) {
-    snprintf(c->err, sizeof(c->err), "%s: %llu bases; the limit is 2^38 - 1", what, static_cast<kf_ull>(n_bases));
-    return MSGPU_E_ARG;
-  }
-  uint64_t *d_off;
-  uint32_t *d_len;
-  STAGE_HIP(c, D.get(&d_off, n));
-  STAGE_HIP(c, D.get(&d_len, n));
-  if (n) {
-    STAGE_HIP(c, hipMemcpyAsync(d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
-    STAGE_HIP(c, hipMemcpyAsync(d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
-    STAGE_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  F.recs.off     = d_off;
-  F.recs.len     = d_len;
-  F.recs.n       = n;
-  F.recs.n_bases = n_bases;
-  return MSGPU_OK;
-}
-
 // rule 8: `need` more bytes beside what the device holds already
 int pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const char *a_name, uint64_t b, const char *b_name) {
   size_t free_b = 0, total_b = 0;
@@ -500,11 +425,11 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   S.n_runs   = n_runs;
 
   const StageTimer loading;
-  PlFile           FT, FQ;
-  if ((rc = pl_load(c, D, draft_path, 1, "draft", FT)) != MSGPU_OK) return rc;
-  if ((rc = pl_load(c, D, reads_path, 0, "reads", FQ)) != MSGPU_OK) return rc;
+  StageFile        FT, FQ;
+  if ((rc = stage_load(c, D, draft_path, 1, "draft", FT)) != MSGPU_OK) return rc;
+  if ((rc = stage_load(c, D, reads_path, 0, "reads", FQ)) != MSGPU_OK) return rc;
   S.load_ms = loading.ms();
-  const PlRecs &R = FT.recs, &Q = FQ.recs;
+  const SeqRecs &R = FT.recs, &Q = FQ.recs;
   S.n_records    = R.n;
   S.n_bases      = R.n_bases;
   S.n_reads      = Q.n;

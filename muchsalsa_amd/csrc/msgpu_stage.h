@@ -1,8 +1,9 @@
 // msgpu_stage.h -- the host-side scaffolding of the six contexts, defined once: the overlap context (msgpu_api.hip) and the
 // pipeline stages (msgpu_filter.hip, msgpu_scrub.hip, msgpu_kmer.hip, msgpu_unitig.hip, msgpu_map.hip).  The context with
 // its create / destroy, the HIP-error macro, the holders of an event and of a stream, the device arena with its temporary
-// buffer for rocPRIM, the event clock, the wall-clock timer, the scalar block and its read-back, and the record lookup of
-// the stages that name sequences.  msgpu_seq.hip takes the holders.  No kernels.
+// buffer for rocPRIM, the event clock, the wall-clock timer, the scalar block and its read-back, the record lookup of
+// the stages that name sequences, and the loader of the stages that read a store's bases.  msgpu_seq.hip takes the holders.
+// No kernels.
 #ifndef MSGPU_STAGE_H
 #define MSGPU_STAGE_H
 
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "msgpu.h"
+#include "msgpu_device.h"
 #include "msgpu_internal.h"
 
 namespace msgpu {
@@ -378,6 +380,62 @@ uint32_t stage_first_records(const msgpu_seqfile *f, IdOfName id_of_name, uint32
   for (uint32_t k = 0; k < n_want; ++k)
     if (rec_of[want ? want[k] : k] == STAGE_NONE) return k;
   return STAGE_NONE;
+}
+
+struct StageFile { // a parsed file in its store, and its records as the kernels see them
+  SeqFileHold f;
+  SeqRecs     recs{};
+};
+
+// `path` into store `kind` of the context's sequence store, and the records' offsets and lengths into the arena (a zero behind
+// the lengths: their scan gives n + 1 sums).  `what` names the file in the error texts
+template <class Ctx> int stage_load(Ctx *c, DevArena &D, const char *path, int kind, const char *what, StageFile &F) {
+  int rc = msgpu_seq_parse_upload(c->seq, kind, path, -1, &F.f.f);
+  if (rc != MSGPU_OK) {
+    snprintf(c->err, sizeof(c->err), "%s %s: %s", what, path, msgpu_seq_last_error(c->seq));
+    return rc;
+  }
+  const uint32_t        n = msgpu_seq_count(F.f);
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  try {
+    off.resize(n);
+    len.resize(n);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  uint64_t n_bases = 0;
+  F.recs.bases = seq_store_bases(c->seq, kind, &n_bases);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t L = msgpu_seq_length(F.f, i);
+    off[i] = msgpu_seq_offset(F.f, i);
+    if (L >= (1ull << 31)) {
+      snprintf(c->err, sizeof(c->err), "%s record %u has %llu bases; the limit is 2^31 - 1", what, i, static_cast<unsigned long long>(L));
+      return MSGPU_E_ARG;
+    }
+    if ((i && off[i] < off[i - 1] + len[i - 1]) || off[i] + L > n_bases) {
+      snprintf(c->err, sizeof(c->err), "%s record %u does not lie behind record %u in the store", what, i, i ? i - 1 : 0);
+      return MSGPU_E_STATE;
+    }
+    len[i] = static_cast<uint32_t>(L);
+  }
+  if (n_bases >= (1ull << 38)) {
+    snprintf(c->err, sizeof(c->err), "%s: %llu bases; the limit is 2^38 - 1", what, static_cast<unsigned long long>(n_bases));
+    return MSGPU_E_ARG;
+  }
+  uint64_t *d_off;
+  uint32_t *d_len;
+  STAGE_HIP(c, D.get(&d_off, n));
+  STAGE_HIP(c, D.get(&d_len, n + 1ull));
+  STAGE_HIP(c, hipMemsetAsync(d_len + n, 0, 4, c->stream));
+  if (n) {
+    STAGE_HIP(c, hipMemcpyAsync(d_off, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipMemcpyAsync(d_len, len.data(), n * 4ull, hipMemcpyHostToDevice, c->stream));
+    STAGE_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  F.recs.off     = d_off;
+  F.recs.len     = d_len;
+  F.recs.n       = n;
+  F.recs.n_bases = n_bases;
+  return MSGPU_OK;
 }
 
 } // namespace msgpu

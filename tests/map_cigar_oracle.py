@@ -130,7 +130,7 @@ def chain_runs(anchors, k, tseq, qseq_oriented, band, stats):
     return merge(runs), capped
 
 
-LDS_MAX_D = 31  # msgpu_seq.hip, ES_LDS_MAXD: the class boundary the stats report
+LDS_MAX_D = 31  # msgpu_align.hip, ES_LDS_MAXD: the class boundary the stats report
 
 
 def cigar_run(targets, queries, exact_result=None, **params):

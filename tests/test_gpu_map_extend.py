@@ -90,6 +90,34 @@ def test_random_pairs(which, reverse):
     _compare(pairs, _extend(pairs, band, reverse), extendcases.expected_pairs(("random", which)), "random %d" % which)
 
 
+CHILD = """
+import json, sys
+sys.path.insert(0, %r)
+import extendcases
+import test_gpu_map_extend as T
+pairs, band = extendcases.random_pairs(1)
+print(json.dumps(T._extend(pairs, band, bool(%d))))
+"""
+
+
+@pytest.mark.parametrize("poison", [0, 1])
+@pytest.mark.parametrize("reverse", [False, True], ids=["forward", "reversed"])
+def test_three_slots_serve_the_whole_slab_class(reverse, poison):
+    """MSGPU_ALIGN_SLOTS=3 in a fresh child process (up to 1,024 pairs every pair has a slot of its own otherwise): the 500
+    pairs of the slab class go through three tables, so every slot is reused many times; once more with the buffers poisoned.
+    The end cells and the words do not depend on the number of slots"""
+    env = dict(os.environ, PYTHONPATH=ROOT, MSGPU_ALIGN_SLOTS="3")
+    if poison:
+        env["MSGPU_POISON"] = "1"
+    run = subprocess.run([sys.executable, "-c", CHILD % (os.path.join(ROOT, "tests"), reverse)], cwd=ROOT, env=env, capture_output=True,
+                         timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    ends, off, words = json.loads(run.stdout.decode().strip().splitlines()[-1])
+    pairs, band = extendcases.random_pairs(1)
+    assert band > 31 and len(pairs) > 3
+    _compare(pairs, ([tuple(e) for e in ends], off, words), extendcases.expected_pairs(("random", 1)), "three slots")
+
+
 def test_no_pairs():
     from muchsalsa_amd import sequences as S
     with S.SeqStore(0) as st:
