@@ -1,6 +1,7 @@
 // msgpu_device.h -- device-side helpers shared by the kernel files (msgpu_kernels.hip, msgpu_index.hip): 32-byte and 16-byte row
-// loads / stores, readlane of wide types, wavefront and workgroup scans; and the records of a sequence store with their lookup
-// (msgpu_map.hip, msgpu_polish.hip).  gfx950, wave64.
+// loads / stores, readlane of wide types, wavefront and workgroup scans; the stage files' small idioms (wavefront-aggregated
+// counters and append, the search of a segment table, k_stage_put, k_stage_seg_starts); and the records of a sequence store
+// with their lookup (msgpu_map.hip, msgpu_polish.hip).  gfx950, wave64.
 #ifndef MSGPU_DEVICE_H
 #define MSGPU_DEVICE_H
 
@@ -272,6 +273,65 @@ __device__ __forceinline__ void note_first_row(int lane, unsigned long long key,
     read_first[r] = static_cast<uint32_t>(key >> 32);
     read_len[r]   = rows[static_cast<uint32_t>(key)].read_len;
   }
+}
+
+// ---- the small idioms of the stage files, one copy of each
+
+// Counters that a whole wavefront feeds with one atomic.  Every lane of the wavefront calls these.
+// `each` for every lane that says `mine`, added by the first of them
+__device__ inline void wave_count(bool mine, unsigned long long *counter, unsigned long long each = 1) {
+  const uint64_t who = __ballot(mine);
+  if (who && (threadIdx.x & 63) == static_cast<uint32_t>(__ffsll(static_cast<long long>(who)) - 1)) atomicAdd(counter, each * __popcll(who));
+}
+// the sum of the lanes' values (a sum of zero adds nothing)
+__device__ inline void wave_add(unsigned long long v, unsigned long long *counter) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
+}
+// the maximum of the lanes' values (unsigned, of 32 or 64 bits; a maximum of zero changes nothing)
+template <class T> __device__ inline void wave_max(T v, unsigned long long *counter) {
+  for (int o = 32; o; o >>= 1) {
+    const T w = __shfl_xor(v, o);
+    v = w > v ? w : v;
+  }
+  if ((threadIdx.x & 63) == 0 && v) atomicMax(counter, static_cast<unsigned long long>(v));
+}
+
+// Append behind a 64-bit cursor, one atomic per wavefront: the lanes that `take` get consecutive slots, in lane order.  Every
+// lane of the wavefront calls; the answer means something to the takers only, and whether the slot lies inside the
+// destination is the caller's test.
+__device__ inline uint64_t wave_append(bool take, unsigned long long *cursor) {
+  const uint64_t who = __ballot(take);
+  if (!who) return 0;
+  const int          lane = threadIdx.x & 63, first = __ffsll(static_cast<long long>(who)) - 1;
+  unsigned long long at = 0;
+  if (lane == first) at = atomicAdd(cursor, static_cast<unsigned long long>(__popcll(who)));
+  at = __shfl(at, first);
+  return at + __popcll(who & ((1ull << lane) - 1));
+}
+
+// the last i in [lo, hi) with a[i] <= x (a ascending, a[lo] <= x): the segment of element x in a table of segment offsets
+__device__ inline uint32_t last_le(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t x) {
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// a device word into a slot of the scalar block (msgpu_stage.h, stage_scan_total, launches it behind a scan)
+template <class T> __global__ void k_stage_put(uint64_t *scalars, int slot, const T *src) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) scalars[slot] = static_cast<uint64_t>(*src);
+}
+
+// Segment starts.  head[i] = element i opens a segment, id = the exclusive scan of head over n + 1 words (a zero behind the
+// heads), so id[n] = the segments: start[s] = the first element of segment s, start[segments] = n.  A grid over n + 1:
+// thread n writes the closing entry, whatever n is
+template <class T> __global__ __launch_bounds__(256) void k_stage_seg_starts(const T *head, const T *id, T n, T *start) {
+  const T i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && head[i]) start[id[i]] = i;
+  if (i == n) start[id[n]] = n;
 }
 
 // ---- the records of a sequence store as the kernels of the stages see them (msgpu_stage.h, stage_load, fills one)

@@ -101,23 +101,12 @@ __global__ __launch_bounds__(256) void k_uf_group(const uint32_t *blocks, const 
   if (threadIdx.x == 0) val[b] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
 }
 
-// the segment (of seg_off, n_seg + 1 entries) that element i lies in
-__device__ inline uint32_t uf_segment(const uint64_t *seg_off, uint32_t n_seg, uint64_t i) {
-  uint32_t lo = 0, hi = n_seg; // seg_off[lo] <= i < seg_off[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // giant blocks, step 1: (read << 32 | line inside the block) per line
 __global__ __launch_bounds__(256) void k_uf_read_keys(const uint32_t *blocks, const uint64_t *seg_off, uint32_t n_seg,
                                                       const uint32_t *bfirst, const uint32_t *rd, uint64_t *keys) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= seg_off[n_seg]) return;
-  const uint32_t g = uf_segment(seg_off, n_seg, i), local = static_cast<uint32_t>(i - seg_off[g]);
+  const uint32_t g = last_le(seg_off, 0, n_seg, i), local = static_cast<uint32_t>(i - seg_off[g]);
   keys[i] = (static_cast<uint64_t>(rd[bfirst[blocks[g]] + local]) << 32) | local;
 }
 
@@ -135,7 +124,7 @@ __global__ __launch_bounds__(256) void k_uf_dedup_events(const uint32_t *blocks,
                                                          const uint64_t *sorted, uint64_t *ev) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= seg_off[n_seg]) return;
-  const uint32_t g     = uf_segment(seg_off, n_seg, i);
+  const uint32_t g     = last_le(seg_off, 0, n_seg, i);
   const uint64_t k     = sorted[i];
   const bool     first = i == seg_off[g] || (sorted[i - 1] >> 32) != (k >> 32); // stable by line: the read's first line
   const uint32_t line  = bfirst[blocks[g]] + static_cast<uint32_t>(k & 0xffffffffu);
@@ -149,7 +138,7 @@ __global__ __launch_bounds__(256) void k_uf_all_events(const uint32_t *blocks, c
                                                        uint64_t *ev) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= seg_off[n_seg]) return;
-  const uint32_t g    = uf_segment(seg_off, n_seg, i);
+  const uint32_t g    = last_le(seg_off, 0, n_seg, i);
   const uint32_t line = bfirst[blocks[g]] + static_cast<uint32_t>(i - seg_off[g]);
   const uint32_t s = qs[line], e = qe[line];
   uf_put_events(ev, i, s < e, s, e);
@@ -542,24 +531,13 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- output plan: per block in PAF order the whole record or the fragments
-  const StageTimer                planning;
-  std::vector<msgpu_copy>         pieces;
-  std::vector<msgpu_fasta_record> recs;
-  std::string                     hdr;
-  uint64_t                        raw = 0, text = 0;
+  FastaOut F;
   try {
     auto add = [&](uint32_t id, uint64_t start, uint64_t stop, const char *h, size_t hn) { // bases [start, stop) of id
-      const uint32_t i  = rec_of[id];
-      const uint64_t L  = msgpu_seq_length(f, i);
-      const uint64_t e  = std::min(stop, L), s = std::min(start, e);
-      const uint64_t n  = e - s;
-      // a record without bases: the header without its '\n' (msgpu_fasta_format closes every record with one)
-      const uint32_t hl = static_cast<uint32_t>(n ? hn : hn - 1);
-      if (n) pieces.push_back(msgpu_copy{msgpu_seq_offset(f, i) + s, raw, static_cast<uint32_t>(n), MSGPU_COPY_ILLUMINA});
-      recs.push_back(msgpu_fasta_record{raw, text, static_cast<uint32_t>(n), static_cast<uint32_t>(hdr.size()), hl, 0});
-      hdr.append(h, hl);
-      raw += n;
-      text += msgpu_fasta_text_bytes(hl, n);
+      const uint32_t i = rec_of[id];
+      const uint64_t L = msgpu_seq_length(f, i);
+      const uint64_t e = std::min(stop, L), s = std::min(start, e);
+      F.add(msgpu_seq_offset(f, i) + s, e - s, MSGPU_COPY_ILLUMINA, h, hn);
     };
     std::string h;
     char        buf[96];
@@ -580,44 +558,10 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
       }
     }
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (hdr.size() >= 0xffffffffull) return MSGPU_E_ARG;
-  S.n_records  = recs.size();
-  S.bases      = raw;
-  S.text_bytes = text;
-  msgpu_gather_plan *plan = nullptr;
-  rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  struct FreePlan {
-    msgpu_gather_plan *p;
-    ~FreePlan() { msgpu_gather_plan_free(p); }
-  } free_plan{plan};
-  S.plan_ms = planning.ms();
-  uint8_t *d_raw, *d_text;
-  STAGE_HIP(c, D.get(&d_raw, raw + 16));
-  STAGE_HIP(c, D.get(&d_text, text + 16));
-  STAGE_HIP(c, clock.begin(&S.gather_ms));
-  rc = msgpu_gather_run(c->seq, plan, d_raw, raw + 16, st);
-  if (rc == MSGPU_OK) {
-    STAGE_HIP(c, clock.end());
-    STAGE_HIP(c, clock.begin(&S.format_ms)); // (from the same point of the stream)
-    rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
-  }
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "gather / format: %s", msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, clock.begin(&S.copy_ms)); // (from the same point of the stream)
-  try {
-    res->text.resize(text);
-  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (text) STAGE_HIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, hipStreamSynchronize(st));
-  clock.collect();
+  S.n_records  = F.recs.size();
+  S.bases      = F.raw;
+  S.text_bytes = F.text;
+  if ((rc = F.emit(c, D, clock, nullptr, &S.plan_ms, &S.gather_ms, &S.format_ms, &S.copy_ms, res->text)) != MSGPU_OK) return rc;
   S.wall_ms = wall.ms();
   *out      = res.release();
   return MSGPU_OK;

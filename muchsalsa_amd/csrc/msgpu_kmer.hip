@@ -322,20 +322,6 @@ struct msgpu_kf_result {
 
 namespace {
 
-template <class K> void kf_split(const K *keys, size_t n, std::vector<uint64_t> &hi, std::vector<uint64_t> &lo);
-template <> void kf_split<uint64_t>(const uint64_t *keys, size_t n, std::vector<uint64_t> &hi, std::vector<uint64_t> &lo) {
-  hi.assign(n, 0);
-  lo.assign(keys, keys + n);
-}
-template <> void kf_split<kf_u128>(const kf_u128 *keys, size_t n, std::vector<uint64_t> &hi, std::vector<uint64_t> &lo) {
-  hi.resize(n);
-  lo.resize(n);
-  for (size_t i = 0; i < n; ++i) {
-    hi[i] = static_cast<uint64_t>(keys[i] >> 64);
-    lo[i] = static_cast<uint64_t>(keys[i]);
-  }
-}
-
 // everything behind the format check, for one key width
 template <class K>
 int kf_stage(msgpu_kfctx *c, DevArena &D, const KfFile *F, uint64_t n_pairs, int k, uint64_t budget,
@@ -472,7 +458,9 @@ int kf_stage(msgpu_kfctx *c, DevArena &D, const KfFile *F, uint64_t n_pairs, int
   STAGE_HIP(c, hipStreamSynchronize(st));
   clock.collect();
   try {
-    kf_split<K>(abk.data(), abk.size(), res->key_hi, res->key_lo);
+    res->key_hi.resize(abk.size());
+    res->key_lo.resize(abk.size());
+    for (size_t i = 0; i < abk.size(); ++i) key_split(abk[i], res->key_hi[i], res->key_lo[i]);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   for (uint64_t i = 0; i < n_pairs; ++i) S.n_pairs_out += res->verdict[i] ? 0 : 1;
   return MSGPU_OK;

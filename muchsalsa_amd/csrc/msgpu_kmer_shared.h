@@ -149,19 +149,11 @@ template <class K, bool WRITE>
 __global__ __launch_bounds__(256) void k_kf_select(const K *keys, const uint32_t *cnt, uint64_t n, uint32_t least, K *out_k,
                                                    uint32_t *out_c, uint64_t cap, kf_ull *cursor) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int      lane = threadIdx.x & 63;
   const bool     take = i < n && cnt[i] >= least;
-  const uint64_t who = __ballot(take);
-  if (!who) return;
-  kf_ull at = 0;
-  if (lane == __ffsll(static_cast<long long>(who)) - 1) at = atomicAdd(cursor, static_cast<kf_ull>(__popcll(who)));
-  at = __shfl(at, __ffsll(static_cast<long long>(who)) - 1);
-  if (WRITE && take) {
-    const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
-    if (slot < cap) {
-      out_k[slot] = keys[i];
-      out_c[slot] = cnt[i];
-    }
+  const uint64_t slot = wave_append(take, cursor);
+  if (WRITE && take && slot < cap) {
+    out_k[slot] = keys[i];
+    out_c[slot] = cnt[i];
   }
 }
 

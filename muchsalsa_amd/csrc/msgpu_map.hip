@@ -100,21 +100,11 @@ __global__ __launch_bounds__(256) void k_mp_sketch(SeqRecs R, int k, int w, uint
   }
 }
 
-// a device word into the scalar block
-template <class T> __global__ void k_mp_put(uint64_t *scalars, int slot, const T *src) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) scalars[slot] = static_cast<uint64_t>(*src);
-}
-
-__device__ inline void mp_count(bool mine, kf_ull *counter, kf_ull each = 1) { // all lanes of the wavefront call
-  const uint64_t who = __ballot(mine);
-  if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(counter, each * __popcll(who));
-}
-
 // the keys rule 3 leaves out
 __global__ __launch_bounds__(256) void k_mp_occ(const uint32_t *cnt, uint32_t n, uint32_t max_occ, kf_ull *keys_out, kf_ull *entries_out) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   const bool     over = i < n && cnt[i] > max_occ;
-  mp_count(over, keys_out);
+  wave_count(over, keys_out);
   if (over) atomicAdd(entries_out, static_cast<kf_ull>(cnt[i]));
 }
 
@@ -531,7 +521,7 @@ __global__ __launch_bounds__(256) void k_mp_ends(const msgpu_map_chain *chains, 
 
 __global__ __launch_bounds__(256) void k_mp_capped(const uint32_t *dist, uint32_t n, uint32_t band, kf_ull *capped) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  mp_count(i < n && dist[i] > band, capped);
+  wave_count(i < n && dist[i] > band, capped);
 }
 
 // ---- rule 12: primaries, secondaries and mapping quality over the chains of a query record ("segment": the chains of one
@@ -567,13 +557,6 @@ __global__ __launch_bounds__(256) void k_rk_heads(const msgpu_map_chain *chains,
   if (validate && ((i && q < qp) || chains[i].q_start > chains[i].q_end)) atomicMin(bad, static_cast<kf_ull>(i));
 }
 
-__global__ __launch_bounds__(256) void k_rk_starts(const uint32_t *head, const uint32_t *segid, uint32_t n, uint32_t *start) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (head[i]) start[segid[i]] = i;
-  if (i == n - 1) start[segid[n]] = n;
-}
-
 __global__ __launch_bounds__(256) void k_rk_classify(const uint32_t *start, uint32_t n_seg, uint32_t *flag_wave, uint32_t *flag_list,
                                                      uint32_t *parent, kf_ull *cnt) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;
@@ -583,12 +566,10 @@ __global__ __launch_bounds__(256) void k_rk_classify(const uint32_t *start, uint
     flag_list[s] = n > 64;
     if (n == 1) parent[start[s]] = start[s]; // settled: a primary without a secondary
   }
-  mp_count(n == 1, cnt + RK_SINGLE);
-  mp_count(n >= 2 && n <= 64, cnt + RK_WAVE);
-  mp_count(n > 64, cnt + RK_LIST);
-  uint32_t big = n;
-  for (int o = 32; o > 0; o >>= 1) big = max(big, static_cast<uint32_t>(__shfl_xor(static_cast<int>(big), o)));
-  if ((threadIdx.x & 63) == 0 && big) atomicMax(cnt + RK_LARGEST, static_cast<kf_ull>(big));
+  wave_count(n == 1, cnt + RK_SINGLE);
+  wave_count(n >= 2 && n <= 64, cnt + RK_WAVE);
+  wave_count(n > 64, cnt + RK_LIST);
+  wave_max(n, cnt + RK_LARGEST);
 }
 
 __global__ __launch_bounds__(256) void k_rk_lists(const uint32_t *start, uint32_t n_seg, const uint32_t *flag_wave, const uint32_t *flag_list,
@@ -726,9 +707,9 @@ __global__ __launch_bounds__(256) void k_rk_rows(const msgpu_map_chain *chains, 
     zero    = r.mapq == 0;
     rows[i] = r;
   }
-  mp_count(prim, cnt + RK_PRIM);
-  mp_count(i < n && !prim, cnt + RK_SEC);
-  mp_count(i < n && zero, cnt + RK_MAPQ0);
+  wave_count(prim, cnt + RK_PRIM);
+  wave_count(i < n && !prim, cnt + RK_SEC);
+  wave_count(i < n && zero, cnt + RK_MAPQ0);
 }
 
 } // namespace msgpu
@@ -793,16 +774,14 @@ int mp_sketch(msgpu_mapctx *c, DevArena &D, StageClock &clock, float *ms, const 
   const uint32_t tiles = grid_of(R.n_bases, MP_TILE);
   uint32_t      *d_cnt;
   uint64_t      *d_off;
-  STAGE_HIP(c, D.get(&d_cnt, tiles + 1ull));
+  STAGE_HIP(c, D.get_zeroed(&d_cnt, tiles + 1ull, st));
   STAGE_HIP(c, D.get(&d_off, tiles + 1ull));
-  STAGE_HIP(c, hipMemsetAsync(d_cnt, 0, (tiles + 1ull) * 4, st));
   STAGE_HIP(c, clock.begin(ms));
   if (tiles) hipLaunchKernelGGL((k_mp_sketch<false>), dim3(tiles), dim3(256), 0, st, R, k, w, d_cnt, nullptr, nullptr, nullptr, 0);
   STAGE_HIP(c, hipGetLastError());
   // (the last word is the zero above: d_off[tiles] is the total; every scan of this file reads through a const pointer, one
   // instantiation per output type)
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_cnt, d_off, tiles + 1ull));
-  hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_off + tiles);
+  STAGE_HIP(c, stage_scan_total(D, st, d_cnt, d_off, tiles, c->sc, MP_SC_TOTAL));
   STAGE_HIP(c, clock.end());
   int rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
@@ -1002,20 +981,17 @@ int mp_rank(msgpu_mapctx *c, DevArena &B, StageClock &clock, const msgpu_map_cha
   uint32_t   *d_head, *d_segid, *d_start, *d_fw, *d_fl, *d_pw, *d_pl, *d_lw, *d_ll, *d_parent, *d_nsec;
   kf_ull     *d_sub, *d_cnt;
   for (uint32_t **p : {&d_head, &d_segid, &d_start, &d_fw, &d_fl, &d_pw, &d_pl}) STAGE_HIP(c, B.get(p, n + 1ull));
-  for (uint32_t **p : {&d_lw, &d_ll, &d_parent, &d_nsec}) STAGE_HIP(c, B.get(p, n));
-  STAGE_HIP(c, B.get(&d_sub, n));
-  STAGE_HIP(c, B.get(&d_cnt, RK_COUNT));
-  STAGE_HIP(c, hipMemsetAsync(d_cnt, 0, RK_COUNT * sizeof(kf_ull), st));
+  for (uint32_t **p : {&d_lw, &d_ll, &d_parent}) STAGE_HIP(c, B.get(p, n));
+  STAGE_HIP(c, B.get_zeroed(&d_nsec, n, st));
+  STAGE_HIP(c, B.get_zeroed(&d_sub, n, st));
+  STAGE_HIP(c, B.get_zeroed(&d_cnt, RK_COUNT, st));
   STAGE_HIP(c, hipMemsetAsync(d_cnt + RK_BAD, 0xff, sizeof(kf_ull), st));
   STAGE_HIP(c, hipMemsetAsync(d_head + n, 0, 4, st));
-  STAGE_HIP(c, hipMemsetAsync(d_sub, 0, n * sizeof(kf_ull), st));
-  STAGE_HIP(c, hipMemsetAsync(d_nsec, 0, n * 4ull, st));
   STAGE_HIP(c, clock.begin(&S.rank_ms));
   hipLaunchKernelGGL(k_rk_heads, dim3(grid256(n)), dim3(256), 0, st, d_chains, n, validate ? 1 : 0, d_head, d_cnt + RK_BAD);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_head, d_segid, n + 1ull));
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_segid + n);
-  hipLaunchKernelGGL(k_mp_put<kf_ull>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_cnt + RK_BAD);
+  STAGE_HIP(c, stage_scan_total(B, st, d_head, d_segid, n, c->sc, MP_SC_TOTAL));
+  hipLaunchKernelGGL(k_stage_put<kf_ull>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_cnt + RK_BAD);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, clock.end());
   int rc = c->sc.read(c);
@@ -1026,14 +1002,11 @@ int mp_rank(msgpu_mapctx *c, DevArena &B, StageClock &clock, const msgpu_map_cha
   STAGE_HIP(c, hipMemsetAsync(d_fw + n_seg, 0, 4, st));
   STAGE_HIP(c, hipMemsetAsync(d_fl + n_seg, 0, 4, st));
   STAGE_HIP(c, clock.begin(&S.rank_ms));
-  hipLaunchKernelGGL(k_rk_starts, dim3(grid256(n)), dim3(256), 0, st, d_head, d_segid, n, d_start);
+  hipLaunchKernelGGL(k_stage_seg_starts<uint32_t>, dim3(grid256(n + 1ull)), dim3(256), 0, st, d_head, d_segid, n, d_start);
   hipLaunchKernelGGL(k_rk_classify, dim3(grid256(n_seg)), dim3(256), 0, st, d_start, n_seg, d_fw, d_fl, d_parent, d_cnt);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fw, d_pw, n_seg + 1ull));
-  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fl, d_pl, n_seg + 1ull));
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_pw + n_seg);
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL3, d_pl + n_seg);
-  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan_total(B, st, d_fw, d_pw, n_seg, c->sc, MP_SC_TOTAL2));
+  STAGE_HIP(c, stage_scan_total(B, st, d_fl, d_pl, n_seg, c->sc, MP_SC_TOTAL3));
   STAGE_HIP(c, clock.end());
   rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
@@ -1231,329 +1204,387 @@ int mp_extend_apply(const MpRun &R, uint32_t C_n, const MpExtBatch &xb) {
   return MSGPU_OK;
 }
 
-// rules 4 to 8 for the query records of one batch.  Every array is taken from the reserved arena B and indexed from the
-// batch's first anchor; the record indices in g and in the chain table are the file's.  The counters of the scalar block
-// and the histogram are sums (the largest group: a maximum) over the batches so far: nothing resets them.
-int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
-  msgpu_mapctx           *c = R.c;
-  const msgpu_map_params &prm = R.prm;
-  msgpu_map_stats        &S = R.res->stats;
-  StageClock             &clock = R.clock;
-  hipStream_t             st = c->stream;
-  const int               k = prm.k;
-  const bool              exact = prm.exact != 0, cigar = prm.cigar != 0;
-  msgpu_map_astats       &AS = R.res->astats;
-  const uint32_t          A = static_cast<uint32_t>(bt.n_anchors), q0 = bt.first_query, q1 = q0 + bt.n_queries;
-  const uint64_t          m0 = R.first_min[q0], m1 = R.first_min[q1];
-  int                     rc;
-  B.rewind();
-  if (!A) return MSGPU_OK;
-  if (getenv("MSGPU_POISON")) STAGE_HIP(c, hipMemsetAsync(B.pool, 0xA5, B.pool_bytes, st)); // (see DevBuf::ensure in msgpu_api.hip)
+// ---- rules 4 to 8 for the query records of one batch, a function per step (mp_batch calls them in order).  Every array is taken
+// from the reserved arena B and indexed from the batch's first anchor; the record indices in g and in the chain table are the
+// file's.  The counters of the scalar block and the histogram are sums (the largest group: a maximum) over the batches so
+// far: nothing resets them.
 
-  // ---- rule 4: expand, two stable sorts
-  uint64_t *d_g[2], *d_xy[2], *d_ug;
-  uint32_t *d_gcnt, *d_gstart;
+struct MpBatch { // what a batch carries from step to step
+  uint32_t A = 0, G = 0, n_small = 0, n_large = 0, n_kept = 0, C_n = 0, P = 0; // anchors, groups (of <= 16 anchors, of more, both), chains, pairs
+  uint64_t Wn = 0;                                                              // the words of the scripts
+  // rule 4: the anchors in (group, x, y) order, the groups' keys, sizes and starts; rule 6's sort keys in the sorts' spare buffers
+  const uint64_t *d_xys = nullptr;
+  uint64_t       *d_ug = nullptr, *d_sk[2] = {nullptr, nullptr};
+  uint32_t       *d_gcnt = nullptr, *d_gstart = nullptr;
+  // rule 6's pre-filter: the lists of the small, the large and the kept groups, the kept groups' stretches of the sort keys
+  uint32_t *d_ls = nullptr, *d_ll = nullptr, *d_lk = nullptr, *d_sb = nullptr, *d_se = nullptr;
+  // rule 5 and rule 6's walk: scores and predecessors, the anchors taken, the raw chains, their count per group and its scan
+  int32_t  *d_f = nullptr, *d_pred = nullptr;
+  uint8_t  *d_used = nullptr;
+  MpRaw    *d_raw = nullptr;
+  uint32_t *d_emit = nullptr, *d_coff = nullptr;
+  // the chain table, where a chain lies, its pairs and their scan; rule 12's rows
+  msgpu_map_chain *d_chains = nullptr;
+  MpWhere         *d_where = nullptr;
+  uint32_t        *d_np = nullptr, *d_poff = nullptr;
+  msgpu_map_rank  *d_rows = nullptr;
+  // rule 7: the pairs and their distances; cigar mode: the '=' columns behind a pair and in front of a chain's first
+  msgpu_align_pair *d_pairs = nullptr;
+  uint32_t         *d_dist = nullptr, *d_trail = nullptr, *d_head = nullptr;
+  uint32_t         *d_slab = nullptr; // the tables of the slab class (cigar mode with a segment pair; rule 11 takes its own otherwise)
+  MpOriented O;  // exact mode with a segment pair makes the copies, rule 11 otherwise
+  MpExtBatch xb; // rule 11: what comes back with the chain table
+  kf_ull     h_rk[RK_COUNT] = {}; // rule 12: the counters, likewise
+};
+
+// rule 4: expand, two stable sorts, the groups
+int mp_expand(const MpRun &R, DevArena &B, msgpu_map_batch &bt, MpBatch &b) {
+  msgpu_mapctx    *c = R.c;
+  msgpu_map_stats &S = R.res->stats;
+  hipStream_t      st = c->stream;
+  const uint32_t   A = b.A;
+  const uint64_t   m0 = R.first_min[bt.first_query], m1 = R.first_min[bt.first_query + bt.n_queries];
+  uint64_t        *d_g[2], *d_xy[2];
   for (int i = 0; i < 2; ++i) {
     STAGE_HIP(c, B.get(&d_g[i], A));
     STAGE_HIP(c, B.get(&d_xy[i], A));
   }
-  STAGE_HIP(c, B.get(&d_ug, A));
-  STAGE_HIP(c, B.get(&d_gcnt, A + 1ull));
-  STAGE_HIP(c, B.get(&d_gstart, A + 1ull));
-  STAGE_HIP(c, clock.begin(&S.anchors_ms));
-  hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(m1 - m0)), dim3(256), 0, st, R.X, R.Qs.keys, R.Qs.vals, m0, m1, R.Qf.recs.len, k, prm.ava,
-                     nullptr, R.d_aoff, d_g[0], d_xy[0], A);
+  STAGE_HIP(c, B.get(&b.d_ug, A));
+  STAGE_HIP(c, B.get(&b.d_gcnt, A + 1ull));
+  STAGE_HIP(c, B.get(&b.d_gstart, A + 1ull));
+  STAGE_HIP(c, R.clock.begin(&S.anchors_ms));
+  hipLaunchKernelGGL((k_mp_anchors<true>), dim3(grid256(m1 - m0)), dim3(256), 0, st, R.X, R.Qs.keys, R.Qs.vals, m0, m1, R.Qf.recs.len, R.prm.k,
+                     R.prm.ava, nullptr, R.d_aoff, d_g[0], d_xy[0], A);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, clock.begin(&S.group_ms));
+  STAGE_HIP(c, R.clock.end());
+  STAGE_HIP(c, R.clock.begin(&S.group_ms));
   STAGE_HIP(c, stage_sort_pairs(B, st, d_xy[0], d_xy[1], d_g[0], d_g[1], A)); // by (x, y)
   STAGE_HIP(c, stage_sort_pairs(B, st, d_g[1], d_g[0], d_xy[1], d_xy[0], A)); // then, stable, by group
   STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
-    return rocprim::run_length_encode(tmp, bytes, d_g[0], A, d_ug, d_gcnt, R.d_nruns, st);
+    return rocprim::run_length_encode(tmp, bytes, d_g[0], A, b.d_ug, b.d_gcnt, R.d_nruns, st);
   }));
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, R.d_nruns);
-  STAGE_HIP(c, clock.end());
-  rc = c->sc.read(c);
+  hipLaunchKernelGGL(k_stage_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, R.d_nruns);
+  STAGE_HIP(c, R.clock.end());
+  const int rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  const uint32_t G = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
-  STAGE_HIP(c, hipMemsetAsync(d_gcnt + G, 0, 4, st));
-  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_gcnt, d_gstart, G + 1ull));
-  bt.n_groups = G;
-  S.n_groups += G;
-  const uint64_t *d_xys = d_xy[0];
-  uint64_t       *d_sk[2] = {d_g[1], d_xy[1]}; // (free behind the sorts) rule 6's sort keys
+  b.G = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+  STAGE_HIP(c, hipMemsetAsync(b.d_gcnt + b.G, 0, 4, st));
+  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, b.d_gcnt, b.d_gstart, b.G + 1ull));
+  bt.n_groups = b.G;
+  S.n_groups += b.G;
+  b.d_xys   = d_xy[0];
+  b.d_sk[0] = d_g[1]; // (free behind the sorts)
+  b.d_sk[1] = d_xy[1];
+  return MSGPU_OK;
+}
 
-  // ---- rule 6's pre-filter, the size classes
-  uint32_t *d_fs, *d_fl, *d_ps, *d_pl, *d_ls, *d_ll, *d_lk, *d_sb, *d_se;
+// rule 6's pre-filter, the size classes
+int mp_classes(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx    *c = R.c;
+  msgpu_map_stats &S = R.res->stats;
+  hipStream_t      st = c->stream;
+  const uint32_t   G = b.G;
+  const int        k = R.prm.k;
+  uint32_t        *d_fs, *d_fl, *d_ps, *d_pl;
   for (uint32_t **p : {&d_fs, &d_fl, &d_ps, &d_pl}) STAGE_HIP(c, B.get(p, G + 1ull));
-  for (uint32_t **p : {&d_ls, &d_ll, &d_lk, &d_sb, &d_se}) STAGE_HIP(c, B.get(p, G));
+  for (uint32_t **p : {&b.d_ls, &b.d_ll, &b.d_lk, &b.d_sb, &b.d_se}) STAGE_HIP(c, B.get(p, G));
   STAGE_HIP(c, hipMemsetAsync(d_fs + G, 0, 4, st));
   STAGE_HIP(c, hipMemsetAsync(d_fl + G, 0, 4, st));
-  STAGE_HIP(c, clock.begin(&S.group_ms));
-  hipLaunchKernelGGL(k_mp_classify, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, G, k, prm.min_score, prm.min_count, d_fs, d_fl, R.d_hist,
+  STAGE_HIP(c, R.clock.begin(&S.group_ms));
+  hipLaunchKernelGGL(k_mp_classify, dim3(grid256(G)), dim3(256), 0, st, b.d_gcnt, G, k, R.prm.min_score, R.prm.min_count, d_fs, d_fl, R.d_hist,
                      mp_slot(c, MP_SC_LARGEST));
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fs, d_ps, G + 1ull));
-  STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_fl, d_pl, G + 1ull));
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_ps + G);
-  hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL3, d_pl + G);
-  hipLaunchKernelGGL(k_mp_lists, dim3(grid256(G)), dim3(256), 0, st, d_gcnt, d_gstart, G, d_fs, d_fl, d_ps, d_pl, d_ls, d_ll, d_lk, d_sb, d_se);
+  STAGE_HIP(c, stage_scan_total(B, st, d_fs, d_ps, G, c->sc, MP_SC_TOTAL2));
+  STAGE_HIP(c, stage_scan_total(B, st, d_fl, d_pl, G, c->sc, MP_SC_TOTAL3));
+  hipLaunchKernelGGL(k_mp_lists, dim3(grid256(G)), dim3(256), 0, st, b.d_gcnt, b.d_gstart, G, d_fs, d_fl, d_ps, d_pl, b.d_ls, b.d_ll, b.d_lk, b.d_sb,
+                     b.d_se);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, clock.end());
-  rc = c->sc.read(c);
+  STAGE_HIP(c, R.clock.end());
+  const int rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
-  const uint32_t n_small = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]), n_large = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
-  const uint32_t n_kept = n_small + n_large;
-  S.n_groups_small += n_small;
-  S.n_groups_large += n_large;
-  S.n_groups_kept += n_kept;
+  b.n_small = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]);
+  b.n_large = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
+  b.n_kept  = b.n_small + b.n_large;
+  S.n_groups_small += b.n_small;
+  S.n_groups_large += b.n_large;
+  S.n_groups_kept += b.n_kept;
   S.largest_group = c->sc.h[MP_SC_LARGEST];
   if (S.largest_group * static_cast<uint64_t>(k) >= (1ull << 31)) {
     snprintf(c->err, sizeof(c->err), "a group of %llu anchors: its scores do not fit 31 bits at k = %d", static_cast<kf_ull>(S.largest_group), k);
     return MSGPU_E_ARG;
   }
+  return MSGPU_OK;
+}
 
-  // ---- rule 5
-  int32_t  *d_f, *d_pred;
-  uint8_t  *d_used;
-  MpRaw    *d_raw;
-  uint32_t *d_emit, *d_coff;
-  STAGE_HIP(c, B.get(&d_f, A));
-  STAGE_HIP(c, B.get(&d_pred, A));
-  STAGE_HIP(c, B.get(&d_used, A));
-  STAGE_HIP(c, B.get(&d_raw, A));
-  STAGE_HIP(c, B.get(&d_emit, n_kept + 1ull));
-  STAGE_HIP(c, B.get(&d_coff, n_kept + 1ull));
-  STAGE_HIP(c, hipMemsetAsync(d_used, 0, A, st));
-  STAGE_HIP(c, hipMemsetAsync(d_emit, 0, (n_kept + 1ull) * 4, st));
-  MpChainArgs ca{d_ll, n_large, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[0], k, prm.max_gap, prm.bandwidth};
-  STAGE_HIP(c, clock.begin(&S.chain_ms));
-  if (n_large) hipLaunchKernelGGL(k_mp_chain, dim3(grid_of(n_large, 4)), dim3(256), 0, st, ca);
-  ca.list   = d_ls;
-  ca.n_list = n_small;
-  if (n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(grid_of(n_small, 16)), dim3(256), 0, st, ca);
+// rule 5
+int mp_chain(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx *c = R.c;
+  hipStream_t   st = c->stream;
+  STAGE_HIP(c, B.get(&b.d_f, b.A));
+  STAGE_HIP(c, B.get(&b.d_pred, b.A));
+  STAGE_HIP(c, B.get_zeroed(&b.d_used, b.A, st));
+  STAGE_HIP(c, B.get(&b.d_raw, b.A));
+  STAGE_HIP(c, B.get_zeroed(&b.d_emit, b.n_kept + 1ull, st));
+  STAGE_HIP(c, B.get(&b.d_coff, b.n_kept + 1ull));
+  MpChainArgs ca{b.d_ll, b.n_large, b.d_gstart, b.d_gcnt, b.d_xys, b.d_f, b.d_pred, b.d_sk[0], R.prm.k, R.prm.max_gap, R.prm.bandwidth};
+  STAGE_HIP(c, R.clock.begin(&R.res->stats.chain_ms));
+  if (b.n_large) hipLaunchKernelGGL(k_mp_chain, dim3(grid_of(b.n_large, 4)), dim3(256), 0, st, ca);
+  ca.list   = b.d_ls;
+  ca.n_list = b.n_small;
+  if (b.n_small) hipLaunchKernelGGL(k_mp_chain16, dim3(grid_of(b.n_small, 16)), dim3(256), 0, st, ca);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, R.clock.end());
+  return MSGPU_OK;
+}
 
-  // ---- rule 6
-  uint32_t   C_n = 0;
-  MpOriented O;  // exact mode with a segment pair makes the copies, rule 11 otherwise
-  MpExtBatch xb; // rule 11: what comes back with the chain table
-  kf_ull          h_rk[RK_COUNT] = {}; // rule 12: the counters, likewise
-  msgpu_map_rank *d_rows = nullptr;
-  if (n_kept) {
-    STAGE_HIP(c, clock.begin(&S.backtrack_ms));
+// rule 6: the walk back through every kept group, the chains per group and their count
+int mp_walk(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx *c = R.c;
+  hipStream_t   st = c->stream;
+  STAGE_HIP(c, R.clock.begin(&R.res->stats.backtrack_ms));
+  STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+    return rocprim::segmented_radix_sort_keys_desc(tmp, bytes, b.d_sk[0], b.d_sk[1], b.A, b.n_kept, b.d_sb, b.d_se, 0, 64, st);
+  }));
+  hipLaunchKernelGGL(k_mp_walk, dim3(grid_of(b.n_kept, 64)), dim3(64), 0, st, b.d_lk, b.n_kept, b.d_gstart, b.d_gcnt, b.d_xys, b.d_f, b.d_pred, b.d_sk[1],
+                     b.d_used, R.prm.k, R.prm.min_score, R.prm.min_count, b.d_raw, b.d_emit, mp_slot(c, MP_SC_DROP_SCORE),
+                     mp_slot(c, MP_SC_DROP_COUNT), mp_slot(c, MP_SC_CUT));
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan_total(B, st, b.d_emit, b.d_coff, b.n_kept, c->sc, MP_SC_TOTAL));
+  STAGE_HIP(c, R.clock.end());
+  const int rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  b.C_n = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+  return MSGPU_OK;
+}
+
+// the chain table
+int mp_table(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx  *c = R.c;
+  hipStream_t    st = c->stream;
+  const uint32_t C_n = b.C_n;
+  STAGE_HIP(c, B.get(&b.d_chains, C_n));
+  STAGE_HIP(c, B.get(&b.d_where, C_n));
+  STAGE_HIP(c, B.get(&b.d_np, C_n + 1ull));
+  STAGE_HIP(c, B.get(&b.d_poff, C_n + 1ull));
+  STAGE_HIP(c, hipMemsetAsync(b.d_np + C_n, 0, 4, st));
+  STAGE_HIP(c, R.clock.begin(&R.res->stats.backtrack_ms));
+  hipLaunchKernelGGL(k_mp_table, dim3(grid256(b.n_kept)), dim3(256), 0, st, b.d_lk, b.n_kept, b.d_gstart, b.d_ug, b.d_xys, b.d_raw, b.d_emit, b.d_coff,
+                     R.Qf.recs.len, R.prm.k, b.d_chains, b.d_where, b.d_np, C_n);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, R.clock.end());
+  return MSGPU_OK;
+}
+
+// rule 12, directly behind the table: query, score and the query range are final here, and no extension has moved them
+int mp_rank_batch(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx  *c = R.c;
+  const uint64_t before = R.res->chains.size();
+  if (before + b.C_n >= (1ull << 32)) {
+    snprintf(c->err, sizeof(c->err), "%llu chains; with ranking on the limit of a run is 2^32 - 1 (rule 12)", static_cast<kf_ull>(before + b.C_n));
+    return MSGPU_E_ARG;
+  }
+  uint64_t bad;
+  STAGE_HIP(c, B.get(&b.d_rows, b.C_n));
+  return mp_rank(c, B, R.clock, b.d_chains, b.C_n, static_cast<uint32_t>(before), false, b.d_rows, b.h_rk, R.res->rstats, &bad);
+}
+
+// rule 7 in exact mode: the pairs of the batch (b.P; none: nothing more), their distances, and without cigar mode NM
+int mp_pairs(const MpRun &R, DevArena &B, msgpu_map_batch &bt, MpBatch &b) {
+  msgpu_mapctx    *c = R.c;
+  msgpu_map_stats &S = R.res->stats;
+  hipStream_t      st = c->stream;
+  const bool       cigar = R.prm.cigar != 0;
+  const uint32_t   C_n = b.C_n, band = static_cast<uint32_t>(R.prm.band);
+  STAGE_HIP(c, stage_scan_total(B, st, b.d_np, b.d_poff, C_n, c->sc, MP_SC_TOTAL));
+  int rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t P = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]); // (fewer than the anchors)
+  b.P        = P;
+  bt.n_pairs = P;
+  S.n_pairs += P;
+  if (!P) return MSGPU_OK;
+  const uint64_t NB = bt.n_query_bases, b0 = R.bpre[bt.first_query];
+  uint32_t      *d_nm = nullptr;
+  rc = mp_oriented(R, B, bt, &S.pairs_ms, b.O); // (the gather opens the span of the pairs)
+  if (rc != MSGPU_OK) return rc;
+  STAGE_HIP(c, B.get(&b.d_pairs, P));
+  STAGE_HIP(c, B.get(&b.d_dist, P));
+  if (!cigar) STAGE_HIP(c, B.get(&d_nm, C_n));
+  if (cigar) {
+    STAGE_HIP(c, B.get(&b.d_trail, P));
+    STAGE_HIP(c, B.get(&b.d_head, C_n));
+  }
+  hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, b.d_chains, b.d_where, C_n, b.d_xys, b.d_pred, b.d_poff, R.Tf.recs.off, R.d_bpre,
+                     b0, NB, R.prm.k, b.d_pairs, P, b.d_trail, b.d_head);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, R.clock.end());
+  STAGE_HIP(c, R.clock.begin(&S.distance_ms));
+  launch_edit_distance_pairs(st, R.Tf.recs.bases, b.O.d, b.d_pairs, P, band, b.d_dist, false);
+  STAGE_HIP(c, hipGetLastError());
+  if (!cigar)
     STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
-      return rocprim::segmented_radix_sort_keys_desc(tmp, bytes, d_sk[0], d_sk[1], A, n_kept, d_sb, d_se, 0, 64, st);
+      return rocprim::segmented_reduce(tmp, bytes, b.d_dist, d_nm, C_n, b.d_poff, b.d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
     }));
-    hipLaunchKernelGGL(k_mp_walk, dim3(grid_of(n_kept, 64)), dim3(64), 0, st, d_lk, n_kept, d_gstart, d_gcnt, d_xys, d_f, d_pred, d_sk[1],
-                       d_used, k, prm.min_score, prm.min_count, d_raw, d_emit, mp_slot(c, MP_SC_DROP_SCORE), mp_slot(c, MP_SC_DROP_COUNT),
-                       mp_slot(c, MP_SC_CUT));
-    STAGE_HIP(c, hipGetLastError());
-    STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_emit, d_coff, n_kept + 1ull));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_coff + n_kept);
-    STAGE_HIP(c, clock.end());
-    rc = c->sc.read(c);
-    if (rc != MSGPU_OK) return rc;
-    C_n = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
-  }
-  bt.n_chains = C_n;
-  S.n_chains += C_n;
-  if (C_n) {
-    msgpu_map_chain *d_chains;
-    MpWhere         *d_where;
-    uint32_t        *d_np, *d_poff;
-    STAGE_HIP(c, B.get(&d_chains, C_n));
-    STAGE_HIP(c, B.get(&d_where, C_n));
-    STAGE_HIP(c, B.get(&d_np, C_n + 1ull));
-    STAGE_HIP(c, B.get(&d_poff, C_n + 1ull));
-    STAGE_HIP(c, hipMemsetAsync(d_np + C_n, 0, 4, st));
-    STAGE_HIP(c, clock.begin(&S.backtrack_ms));
-    hipLaunchKernelGGL(k_mp_table, dim3(grid256(n_kept)), dim3(256), 0, st, d_lk, n_kept, d_gstart, d_ug, d_xys, d_raw, d_emit, d_coff,
-                       R.Qf.recs.len, k, d_chains, d_where, d_np, C_n);
-    STAGE_HIP(c, hipGetLastError());
-    STAGE_HIP(c, clock.end());
+  hipLaunchKernelGGL(k_mp_capped, dim3(grid256(P)), dim3(256), 0, st, b.d_dist, P, band, mp_slot(c, MP_SC_CAPPED));
+  if (!cigar) hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, b.d_chains, C_n, d_nm);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, R.clock.end());
+  return MSGPU_OK;
+}
 
-    // ---- rule 12, directly behind the table: query, score and the query range are final here, and no extension has moved them
-    if (R.ranking) {
-      const uint64_t before = R.res->chains.size();
-      if (before + C_n >= (1ull << 32)) {
-        snprintf(c->err, sizeof(c->err), "%llu chains; with ranking on the limit of a run is 2^32 - 1 (rule 12)", static_cast<kf_ull>(before + C_n));
-        return MSGPU_E_ARG;
-      }
-      uint64_t bad;
-      STAGE_HIP(c, B.get(&d_rows, C_n));
-      rc = mp_rank(c, B, clock, d_chains, C_n, static_cast<uint32_t>(before), false, d_rows, h_rk, R.res->rstats, &bad);
-      if (rc != MSGPU_OK) return rc;
-    }
-
-    uint32_t *d_slab = nullptr; // the tables of the slab class (cigar mode with a segment pair; rule 11 takes its own otherwise)
-
-    // ---- rule 7 in exact mode
-    if (exact) {
-      STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_np, d_poff, C_n + 1ull));
-      hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_poff + C_n);
-      STAGE_HIP(c, hipGetLastError());
-      rc = c->sc.read(c);
-      if (rc != MSGPU_OK) return rc;
-      const uint32_t P = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]); // (fewer than the anchors)
-      bt.n_pairs = P;
-      S.n_pairs += P;
-      if (P) {
-        const uint64_t    NB = bt.n_query_bases, b0 = R.bpre[q0];
-        msgpu_align_pair *d_pairs;
-        uint32_t         *d_dist, *d_nm = nullptr, *d_trail = nullptr, *d_head = nullptr;
-        rc = mp_oriented(R, B, bt, &S.pairs_ms, O); // (the gather opens the span of the pairs)
-        if (rc != MSGPU_OK) return rc;
-        const uint8_t *const d_or = O.d;
-        STAGE_HIP(c, B.get(&d_pairs, P));
-        STAGE_HIP(c, B.get(&d_dist, P));
-        if (!cigar) STAGE_HIP(c, B.get(&d_nm, C_n));
-        if (cigar) {
-          STAGE_HIP(c, B.get(&d_trail, P));
-          STAGE_HIP(c, B.get(&d_head, C_n));
-        }
-        hipLaunchKernelGGL(k_mp_pairs, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, d_where, C_n, d_xys, d_pred, d_poff, R.Tf.recs.off, R.d_bpre,
-                           b0, NB, k, d_pairs, P, d_trail, d_head);
-        STAGE_HIP(c, hipGetLastError());
-        STAGE_HIP(c, clock.end());
-        STAGE_HIP(c, clock.begin(&S.distance_ms));
-        launch_edit_distance_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, static_cast<uint32_t>(prm.band), d_dist, false);
-        STAGE_HIP(c, hipGetLastError());
-        if (!cigar)
-          STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
-            return rocprim::segmented_reduce(tmp, bytes, d_dist, d_nm, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
-          }));
-        hipLaunchKernelGGL(k_mp_capped, dim3(grid256(P)), dim3(256), 0, st, d_dist, P, static_cast<uint32_t>(prm.band), mp_slot(c, MP_SC_CAPPED));
-        if (!cigar) hipLaunchKernelGGL(k_mp_exact, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_nm);
-        STAGE_HIP(c, hipGetLastError());
-        STAGE_HIP(c, clock.end());
-        if (cigar) {
-          // ---- rule 10: the scripts' offsets, the scripts, the figures of the pairs and of the chains
-          const uint32_t band = static_cast<uint32_t>(prm.band), slots = edit_script_slots();
-          uint32_t      *d_len, *d_list, *d_cnt, *d_words, *d_eq, *d_cols;
-          const uint64_t slab_words = edit_script_slab_words(slots, band); // (none for a band within the LDS class)
-          uint64_t      *d_off;
-          kf_ull        *d_xid;
-          STAGE_HIP(c, B.get(&d_len, P + 1ull));
-          STAGE_HIP(c, B.get(&d_off, P + 1ull));
-          STAGE_HIP(c, B.get(&d_list, P));
-          STAGE_HIP(c, B.get(&d_cnt, ES_CNT_COUNT));
-          STAGE_HIP(c, B.get(&d_xid, 4));
-          if (slab_words) STAGE_HIP(c, B.get(&d_slab, slab_words));
-          STAGE_HIP(c, B.get(&d_eq, P));
-          STAGE_HIP(c, B.get(&d_cols, P));
-          STAGE_HIP(c, hipMemsetAsync(d_xid, 0, 4 * sizeof(kf_ull), st));
-          STAGE_HIP(c, clock.begin(&AS.align_ms));
-          launch_edit_script_lengths(st, d_dist, P, band, d_len);
-          STAGE_HIP(c, hipGetLastError());
-          STAGE_HIP(c, stage_scan<const uint32_t *>(B, st, d_len, d_off, P + 1ull));
-          hipLaunchKernelGGL(k_mp_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_off + P);
-          STAGE_HIP(c, hipGetLastError());
-          STAGE_HIP(c, clock.end());
-          rc = c->sc.read(c);
-          if (rc != MSGPU_OK) return rc;
-          const uint64_t Wn = c->sc.h[MP_SC_TOTAL2]; // (at most P * (band + 1))
-          STAGE_HIP(c, B.get(&d_words, Wn));
-          STAGE_HIP(c, clock.begin(&AS.align_ms));
-          STAGE_HIP(c, launch_edit_script_pairs(st, R.Tf.recs.bases, d_or, d_pairs, P, band, d_dist, d_off, d_list, d_cnt, d_slab, slots, d_words));
-          hipLaunchKernelGGL(k_mp_columns, dim3(grid256(P)), dim3(256), 0, st, d_pairs, d_dist, d_off, d_words, P, band, d_eq, d_cols, d_xid);
-          STAGE_HIP(c, hipGetLastError());
-          uint32_t *d_seq, *d_scols; // the sums per chain
-          STAGE_HIP(c, B.get(&d_seq, C_n));
-          STAGE_HIP(c, B.get(&d_scols, C_n));
-          STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
-            return rocprim::segmented_reduce(tmp, bytes, d_eq, d_seq, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
-          }));
-          STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
-            return rocprim::segmented_reduce(tmp, bytes, d_cols, d_scols, C_n, d_poff, d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
-          }));
-          hipLaunchKernelGGL(k_mp_cigar, dim3(grid256(C_n)), dim3(256), 0, st, d_chains, C_n, d_seq, d_scols);
-          STAGE_HIP(c, hipGetLastError());
-          STAGE_HIP(c, clock.end());
-          // ---- what the host needs for the runs comes back with the chain table
-          msgpu_map_result &res = *R.res;
-          const size_t      c0 = res.c_head.size(), p0 = res.p_lt.size(), w0 = res.words.size();
-          std::vector<msgpu_align_pair> h_pairs;
-          std::vector<uint32_t>         h_poff;
-          std::vector<uint64_t>         h_off;
-          uint32_t                      h_cnt[ES_CNT_COUNT];
-          kf_ull                        h_xid[4];
-          try {
-            h_pairs.resize(P);
-            h_poff.resize(C_n + 1ull);
-            h_off.resize(P + 1ull);
-            res.c_head.resize(c0 + C_n);
-            res.p_trail.resize(p0 + P);
-            res.p_lt.resize(p0 + P);
-            res.p_lq.resize(p0 + P);
-            res.words.resize(w0 + Wn);
-            res.c_poff.resize(c0 + C_n + 1);
-            res.p_woff.resize(p0 + P + 1);
-          } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-          STAGE_HIP(c, clock.begin(&S.copy_ms));
-          STAGE_HIP(c, hipMemcpyAsync(h_pairs.data(), d_pairs, P * sizeof(msgpu_align_pair), hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, hipMemcpyAsync(h_poff.data(), d_poff, (C_n + 1ull) * 4, hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, hipMemcpyAsync(h_off.data(), d_off, (P + 1ull) * 8, hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, hipMemcpyAsync(res.c_head.data() + c0, d_head, C_n * 4ull, hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, hipMemcpyAsync(res.p_trail.data() + p0, d_trail, P * 4ull, hipMemcpyDeviceToHost, st));
-          if (Wn) STAGE_HIP(c, hipMemcpyAsync(res.words.data() + w0, d_words, Wn * 4, hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, hipMemcpyAsync(h_xid, d_xid, sizeof(h_xid), hipMemcpyDeviceToHost, st));
-          STAGE_HIP(c, clock.end());
-          STAGE_HIP(c, hipStreamSynchronize(st));
-          for (uint32_t i = 0; i < P; ++i) {
-            res.p_lt[p0 + i]       = h_pairs[i].a_len;
-            res.p_lq[p0 + i]       = h_pairs[i].b_len;
-            res.p_woff[p0 + i + 1] = w0 + h_off[i + 1];
-          }
-          for (uint32_t i = 0; i < C_n; ++i) res.c_poff[c0 + i + 1] = p0 + h_poff[i + 1];
-          AS.n_pairs_d0 += h_cnt[ES_CNT_D0];
-          AS.n_pairs_lds += h_cnt[ES_CNT_LDS];
-          AS.n_pairs_slab += h_cnt[ES_CNT_SLAB];
-          AS.n_pairs_capped += h_cnt[ES_CNT_CAPPED];
-          AS.n_inconsistent += h_cnt[ES_CNT_BROKEN];
-          AS.max_d = std::max<uint64_t>(AS.max_d, h_cnt[ES_CNT_MAXD]);
-          AS.x_columns += h_xid[0];
-          AS.d_columns += h_xid[1];
-          AS.i_columns += h_xid[2];
-          AS.script_words += Wn;
-        }
-      }
-    }
-
-    // ---- rule 11: the ends of every chain, behind the scripts (the slab is theirs first)
-    if (R.extend) {
-      rc = mp_extend(R, B, bt, d_chains, C_n, O, d_slab, xb);
-      if (rc != MSGPU_OK) return rc;
-    }
-
-    // ---- the batch's chain table behind those of the batches before it
-    const size_t have = R.res->chains.size();
-    try {
-      R.res->chains.resize(have + C_n);
-      if (R.ranking) R.res->ranks.resize(have + C_n);
-    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-    STAGE_HIP(c, clock.begin(&S.copy_ms));
-    STAGE_HIP(c, hipMemcpyAsync(R.res->chains.data() + have, d_chains, C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
-    if (R.ranking) STAGE_HIP(c, hipMemcpyAsync(R.res->ranks.data() + have, d_rows, C_n * sizeof(msgpu_map_rank), hipMemcpyDeviceToHost, st));
-    STAGE_HIP(c, clock.end());
-  }
+// rule 10: the scripts' offsets, the scripts, the figures of the pairs and of the chains; what the host needs for the runs comes
+// back here, behind a synchronisation of its own
+int mp_scripts(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx     *c = R.c;
+  msgpu_map_result &res = *R.res;
+  msgpu_map_astats &AS = res.astats;
+  hipStream_t       st = c->stream;
+  const uint32_t    C_n = b.C_n, P = b.P, band = static_cast<uint32_t>(R.prm.band), slots = edit_script_slots();
+  uint32_t         *d_len, *d_list, *d_cnt, *d_words, *d_eq, *d_cols;
+  const uint64_t    slab_words = edit_script_slab_words(slots, band); // (none for a band within the LDS class)
+  uint64_t         *d_off;
+  kf_ull           *d_xid;
+  STAGE_HIP(c, B.get(&d_len, P + 1ull));
+  STAGE_HIP(c, B.get(&d_off, P + 1ull));
+  STAGE_HIP(c, B.get(&d_list, P));
+  STAGE_HIP(c, B.get(&d_cnt, ES_CNT_COUNT));
+  STAGE_HIP(c, B.get_zeroed(&d_xid, 4, st));
+  if (slab_words) STAGE_HIP(c, B.get(&b.d_slab, slab_words));
+  STAGE_HIP(c, B.get(&d_eq, P));
+  STAGE_HIP(c, B.get(&d_cols, P));
+  STAGE_HIP(c, R.clock.begin(&AS.align_ms));
+  launch_edit_script_lengths(st, b.d_dist, P, band, d_len);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan_total(B, st, d_len, d_off, P, c->sc, MP_SC_TOTAL2));
+  STAGE_HIP(c, R.clock.end());
+  const int rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint64_t Wn = b.Wn = c->sc.h[MP_SC_TOTAL2]; // (at most P * (band + 1))
+  STAGE_HIP(c, B.get(&d_words, Wn));
+  STAGE_HIP(c, R.clock.begin(&AS.align_ms));
+  STAGE_HIP(c, launch_edit_script_pairs(st, R.Tf.recs.bases, b.O.d, b.d_pairs, P, band, b.d_dist, d_off, d_list, d_cnt, b.d_slab, slots, d_words));
+  hipLaunchKernelGGL(k_mp_columns, dim3(grid256(P)), dim3(256), 0, st, b.d_pairs, b.d_dist, d_off, d_words, P, band, d_eq, d_cols, d_xid);
+  STAGE_HIP(c, hipGetLastError());
+  uint32_t *d_seq, *d_scols; // the sums per chain
+  STAGE_HIP(c, B.get(&d_seq, C_n));
+  STAGE_HIP(c, B.get(&d_scols, C_n));
+  STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+    return rocprim::segmented_reduce(tmp, bytes, d_eq, d_seq, C_n, b.d_poff, b.d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+  }));
+  STAGE_HIP(c, stage_rocprim(B, [&](void *tmp, size_t &bytes) {
+    return rocprim::segmented_reduce(tmp, bytes, d_cols, d_scols, C_n, b.d_poff, b.d_poff + 1, rocprim::plus<uint32_t>(), 0u, st);
+  }));
+  hipLaunchKernelGGL(k_mp_cigar, dim3(grid256(C_n)), dim3(256), 0, st, b.d_chains, C_n, d_seq, d_scols);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, R.clock.end());
+  // ---- what the host needs for the runs comes back with the chain table
+  const size_t                  c0 = res.c_head.size(), p0 = res.p_lt.size(), w0 = res.words.size();
+  std::vector<msgpu_align_pair> h_pairs;
+  std::vector<uint32_t>         h_poff;
+  std::vector<uint64_t>         h_off;
+  uint32_t                      h_cnt[ES_CNT_COUNT];
+  kf_ull                        h_xid[4];
+  try {
+    h_pairs.resize(P);
+    h_poff.resize(C_n + 1ull);
+    h_off.resize(P + 1ull);
+    res.c_head.resize(c0 + C_n);
+    res.p_trail.resize(p0 + P);
+    res.p_lt.resize(p0 + P);
+    res.p_lq.resize(p0 + P);
+    res.words.resize(w0 + Wn);
+    res.c_poff.resize(c0 + C_n + 1);
+    res.p_woff.resize(p0 + P + 1);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  STAGE_HIP(c, R.clock.begin(&res.stats.copy_ms));
+  STAGE_HIP(c, hipMemcpyAsync(h_pairs.data(), b.d_pairs, P * sizeof(msgpu_align_pair), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(h_poff.data(), b.d_poff, (C_n + 1ull) * 4, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(h_off.data(), d_off, (P + 1ull) * 8, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(res.c_head.data() + c0, b.d_head, C_n * 4ull, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(res.p_trail.data() + p0, b.d_trail, P * 4ull, hipMemcpyDeviceToHost, st));
+  if (Wn) STAGE_HIP(c, hipMemcpyAsync(res.words.data() + w0, d_words, Wn * 4, hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, hipMemcpyAsync(h_xid, d_xid, sizeof(h_xid), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, R.clock.end());
   STAGE_HIP(c, hipStreamSynchronize(st));
-  if (cigar && R.res->c_head.size() < R.res->chains.size()) { // a batch without a segment pair: a chain is its seed columns
+  for (uint32_t i = 0; i < P; ++i) {
+    res.p_lt[p0 + i]       = h_pairs[i].a_len;
+    res.p_lq[p0 + i]       = h_pairs[i].b_len;
+    res.p_woff[p0 + i + 1] = w0 + h_off[i + 1];
+  }
+  for (uint32_t i = 0; i < C_n; ++i) res.c_poff[c0 + i + 1] = p0 + h_poff[i + 1];
+  AS.n_pairs_d0 += h_cnt[ES_CNT_D0];
+  AS.n_pairs_lds += h_cnt[ES_CNT_LDS];
+  AS.n_pairs_slab += h_cnt[ES_CNT_SLAB];
+  AS.n_pairs_capped += h_cnt[ES_CNT_CAPPED];
+  AS.n_inconsistent += h_cnt[ES_CNT_BROKEN];
+  AS.max_d = std::max<uint64_t>(AS.max_d, h_cnt[ES_CNT_MAXD]);
+  AS.x_columns += h_xid[0];
+  AS.d_columns += h_xid[1];
+  AS.i_columns += h_xid[2];
+  AS.script_words += Wn;
+  return MSGPU_OK;
+}
+
+// the batch's chain table (and rule 12's rows) behind those of the batches before it
+int mp_tables_back(const MpRun &R, MpBatch &b) {
+  msgpu_mapctx     *c = R.c;
+  msgpu_map_result &res = *R.res;
+  hipStream_t       st = c->stream;
+  const size_t      have = res.chains.size();
+  try {
+    res.chains.resize(have + b.C_n);
+    if (R.ranking) res.ranks.resize(have + b.C_n);
+  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  STAGE_HIP(c, R.clock.begin(&res.stats.copy_ms));
+  STAGE_HIP(c, hipMemcpyAsync(res.chains.data() + have, b.d_chains, b.C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
+  if (R.ranking) STAGE_HIP(c, hipMemcpyAsync(res.ranks.data() + have, b.d_rows, b.C_n * sizeof(msgpu_map_rank), hipMemcpyDeviceToHost, st));
+  STAGE_HIP(c, R.clock.end());
+  return MSGPU_OK;
+}
+
+// the host work behind the batch's last synchronisation
+int mp_batch_host(const MpRun &R, const MpBatch &b) {
+  msgpu_map_result &res = *R.res;
+  if (R.prm.cigar && res.c_head.size() < res.chains.size()) { // a batch without a segment pair: a chain is its seed columns
     try {
-      for (size_t i = R.res->c_head.size(); i < R.res->chains.size(); ++i) {
-        R.res->c_head.push_back(R.res->chains[i].matches);
-        R.res->c_poff.push_back(R.res->p_lt.size());
+      for (size_t i = res.c_head.size(); i < res.chains.size(); ++i) {
+        res.c_head.push_back(res.chains[i].matches);
+        res.c_poff.push_back(res.p_lt.size());
       }
     } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   }
-  if (R.ranking && C_n) mp_rank_counts(h_rk, R.res->rstats);
-  if (R.extend && C_n) {
-    rc = mp_extend_apply(R, C_n, xb);
-    if (rc != MSGPU_OK) return rc;
+  if (R.ranking && b.C_n) mp_rank_counts(b.h_rk, res.rstats);
+  return R.extend && b.C_n ? mp_extend_apply(R, b.C_n, b.xb) : MSGPU_OK;
+}
+
+int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
+  msgpu_mapctx *c = R.c;
+  const bool    exact = R.prm.exact != 0, cigar = R.prm.cigar != 0;
+  MpBatch       b;
+  int           rc;
+  b.A = static_cast<uint32_t>(bt.n_anchors);
+  B.rewind();
+  if (!b.A) return MSGPU_OK;
+  if (getenv("MSGPU_POISON")) STAGE_HIP(c, hipMemsetAsync(B.pool, 0xA5, B.pool_bytes, c->stream)); // (see DevBuf::ensure in msgpu_api.hip)
+  if ((rc = mp_expand(R, B, bt, b)) != MSGPU_OK) return rc;
+  if ((rc = mp_classes(R, B, b)) != MSGPU_OK) return rc;
+  if ((rc = mp_chain(R, B, b)) != MSGPU_OK) return rc;
+  if (b.n_kept && (rc = mp_walk(R, B, b)) != MSGPU_OK) return rc;
+  bt.n_chains = b.C_n;
+  R.res->stats.n_chains += b.C_n;
+  if (b.C_n) {
+    if ((rc = mp_table(R, B, b)) != MSGPU_OK) return rc;
+    if (R.ranking && (rc = mp_rank_batch(R, B, b)) != MSGPU_OK) return rc;
+    if (exact && (rc = mp_pairs(R, B, bt, b)) != MSGPU_OK) return rc;
+    if (exact && cigar && b.P && (rc = mp_scripts(R, B, b)) != MSGPU_OK) return rc;
+    // rule 11: the ends of every chain, behind the scripts (the slab is theirs first)
+    if (R.extend && (rc = mp_extend(R, B, bt, b.d_chains, b.C_n, b.O, b.d_slab, b.xb)) != MSGPU_OK) return rc;
+    if ((rc = mp_tables_back(R, b)) != MSGPU_OK) return rc;
   }
-  clock.collect();
+  STAGE_HIP(c, hipStreamSynchronize(c->stream));
+  if ((rc = mp_batch_host(R, b)) != MSGPU_OK) return rc;
+  R.clock.collect();
   bt.bytes_peak = B.peak;
   return MSGPU_OK;
 }
@@ -1612,7 +1643,7 @@ int mp_index_build(msgpu_mapctx *c, int k, int w, const char *tpath, msgpu_map_i
     STAGE_HIP(c, stage_rocprim(D, [&](void *tmp, size_t &bytes) {
       return rocprim::run_length_encode(tmp, bytes, d_ikeys, NT, I.d_ukeys, I.d_ucnt, d_nruns, st);
     }));
-    hipLaunchKernelGGL(k_mp_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_nruns);
+    hipLaunchKernelGGL(k_stage_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL, d_nruns);
     STAGE_HIP(c, clock.end());
     rc = c->sc.read(c);
     if (rc != MSGPU_OK) return rc;
@@ -1706,8 +1737,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   STAGE_HIP(c, D.get(&d_acnt, NQ + 1));
   STAGE_HIP(c, D.get(&d_aoff, NQ + 1));
   STAGE_HIP(c, D.get(&d_pre, 3 * (NR + 1ull)));
-  STAGE_HIP(c, D.get(&d_hist, 32));
-  STAGE_HIP(c, hipMemsetAsync(d_hist, 0, 32 * 8, st));
+  STAGE_HIP(c, D.get_zeroed(&d_hist, 32, st));
   STAGE_HIP(c, hipMemsetAsync(d_acnt + NQ, 0, 4, st));
   STAGE_HIP(c, clock.begin(&S.anchors_ms));
   if (NQ)

@@ -46,33 +46,6 @@ struct PlTables { // the chain table and the run tables with their scans
   uint32_t               n_chains, n_runs;
 };
 
-// the last i in [lo, hi) with a[i] <= x (a ascending, a[lo] <= x)
-__device__ inline uint32_t pl_last_le(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t x) {
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// every lane of the wavefront calls these
-__device__ inline void pl_count(bool mine, kf_ull *counter) {
-  const uint64_t who = __ballot(mine);
-  if (who && (threadIdx.x & 63) == static_cast<uint32_t>(__ffsll(static_cast<long long>(who)) - 1)) atomicAdd(counter, static_cast<kf_ull>(__popcll(who)));
-}
-__device__ inline void pl_add(kf_ull v, kf_ull *counter) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
-}
-__device__ inline void pl_max(kf_ull v, kf_ull *counter) {
-  for (int o = 32; o; o >>= 1) {
-    const kf_ull w = __shfl_xor(v, o);
-    v = w > v ? w : v;
-  }
-  if ((threadIdx.x & 63) == 0 && v) atomicMax(counter, v);
-}
-
 __device__ inline void pl_bad(kf_ull *bad, uint32_t chain, uint32_t what) { atomicMin(bad, (static_cast<kf_ull>(chain) << 4) | what); }
 
 // rule 3: the class of the oriented query's byte; s = 1 reads the complement (upper case only, as MSGPU_COPY_REVCOMP), then folds
@@ -88,10 +61,6 @@ __device__ inline uint8_t pl_query_byte(const SeqRecs &Q, const msgpu_map_chain 
   return Q.bases[Q.off[ch.query] + fwd];
 }
 
-template <class T> __global__ void k_pl_put(uint64_t *scalars, int slot, const T *src) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) scalars[slot] = static_cast<uint64_t>(*src);
-}
-
 // rule 1, the offsets: nothing else of the tables can be read without them
 __global__ __launch_bounds__(256) void k_pl_check_off(const uint64_t *off, uint32_t n_chains, uint64_t n_runs, kf_ull *bad) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -103,7 +72,7 @@ __global__ __launch_bounds__(256) void k_pl_runs(const uint64_t *off, uint32_t n
                                                  uint32_t *tc, uint32_t *qc, kf_ull *bad) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   if (u >= n_runs) return;
-  const uint32_t i = pl_last_le(off, 0, n_chains, u); // off[0] = 0 <= u, and off[i + 1] > u as off[n_chains] = n_runs
+  const uint32_t i = last_le(off, 0, n_chains, u); // off[0] = 0 <= u, and off[i + 1] > u as off[n_chains] = n_runs
   const uint32_t len = ops[u] >> 4, op = ops[u] & 15;
   const bool     ok = len >= 1 && (op == PL_I || op == PL_D || op == PL_EQ || op == PL_X);
   if (!ok) pl_bad(bad, i, PL_BAD_RUN);
@@ -170,8 +139,8 @@ __global__ __launch_bounds__(256) void k_pl_spans(const msgpu_map_chain *chains,
   const bool     live = i < n, votes = live && pl_votes(chains, vidx, vflag, i);
   if (live) span[i] = votes ? chains[i].t_end - chains[i].t_start : 0;
   if (votes) atomicAdd(&rec_depth[chains[i].target], static_cast<kf_ull>(chains[i].t_end - chains[i].t_start));
-  pl_count(votes, st + PL_ST_VOTERS);
-  pl_count(live && !votes, st + PL_ST_IGNORED);
+  wave_count(votes, st + PL_ST_VOTERS);
+  wave_count(live && !votes, st + PL_ST_IGNORED);
 }
 
 // rule 4, the columns: lane g takes column g of the voters' spans laid one behind the other (S = the scan of the spans)
@@ -180,20 +149,20 @@ __global__ __launch_bounds__(256) void k_pl_pileup(PlTables X, const uint64_t *S
   const bool     live = g < n_cols;
   uint32_t       op = 0;
   if (live) {
-    const uint32_t        i = pl_last_le(S, 0, X.n_chains, g); // S[i] <= g < S[i + 1]: a voter, the others have no columns
+    const uint32_t        i = last_le(S, 0, X.n_chains, g); // S[i] <= g < S[i + 1]: a voter, the others have no columns
     const msgpu_map_chain ch = X.chains[i];
     const uint64_t        x = g - S[i]; // < t_end - t_start
     const uint32_t        a = static_cast<uint32_t>(X.off[i]), b = static_cast<uint32_t>(X.off[i + 1]);
     const uint64_t        t0 = X.T[a];
-    const uint32_t        u = pl_last_le(X.T, a, b, t0 + x); // T[u] <= t0 + x < T[u + 1]: the run consumes target bases
+    const uint32_t        u = last_le(X.T, a, b, t0 + x); // T[u] <= t0 + x < T[u + 1]: the run consumes target bases
     op = X.ops[u] & 15;
     uint32_t cls = PL_DEL;
     if (op != PL_D) cls = pl_class(pl_query_byte(Q, ch, X.Q[u] - X.Q[a] + (t0 + x - X.T[u])), ch.strand);
     atomicAdd(&cnt[cls * R.n_bases + R.off[ch.target] + ch.t_start + x], 1u);
   }
-  pl_count(op == PL_EQ, st + PL_ST_EQ);
-  pl_count(op == PL_X, st + PL_ST_X);
-  pl_count(op == PL_D, st + PL_ST_D);
+  wave_count(op == PL_EQ, st + PL_ST_EQ);
+  wave_count(op == PL_X, st + PL_ST_X);
+  wave_count(op == PL_D, st + PL_ST_D);
 }
 
 // rule 4, the insertion events.  FILL = false: flag[u] = the run is a usable event at a slot 0 < p < tlen, and the counts;
@@ -232,10 +201,10 @@ __global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_
     }
   }
   if (!FILL) {
-    pl_add(L, st + PL_ST_I);
-    pl_count(ends, st + PL_ST_ENDS);
-    pl_count(usable, st + PL_ST_USABLE);
-    pl_count(ins && !ends && !usable, st + PL_ST_UNUSABLE);
+    wave_add(L, st + PL_ST_I);
+    wave_count(ends, st + PL_ST_ENDS);
+    wave_count(usable, st + PL_ST_USABLE);
+    wave_count(ins && !ends && !usable, st + PL_ST_UNUSABLE);
   }
 }
 
@@ -243,12 +212,6 @@ __global__ __launch_bounds__(256) void k_pl_ins(PlTables X, const uint32_t *run_
 __global__ __launch_bounds__(256) void k_pl_heads(const uint64_t *key, const uint64_t *seq, uint32_t n, uint32_t *head) {
   const uint32_t e = blockIdx.x * 256 + threadIdx.x;
   if (e < n) head[e] = e == 0 || key[e] != key[e - 1] || seq[e] != seq[e - 1];
-}
-// gstart[g] = the first event of group g (G = the scan of head, G[n] = the groups), gstart[groups] = n
-__global__ __launch_bounds__(256) void k_pl_gstart(const uint32_t *head, const uint32_t *G, uint32_t n, uint32_t *gstart) {
-  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-  if (e < n && head[e]) gstart[G[e]] = e;
-  if (e == n) gstart[G[n]] = n;
 }
 // per slot the group with the greatest count; groups are numbered by (slot, L, letters), so the smaller number wins a tie
 __global__ __launch_bounds__(256) void k_pl_best(const uint32_t *gstart, const uint32_t *n_groups, const uint64_t *key, kf_ull *best) {
@@ -318,13 +281,13 @@ __global__ __launch_bounds__(256) void k_pl_call(SeqRecs R, PlCall a, kf_ull *st
     a.outlen[pos] = 0;
     a.best[pos]   = 0;
   }
-  pl_count(kind == 0, st + PL_ST_VERBATIM);
-  pl_count(kind == 1, st + PL_ST_UNCHANGED);
-  pl_count(kind == 2, st + PL_ST_SUBST);
-  pl_count(kind == 3, st + PL_ST_DELETED);
-  pl_count(ins_len != 0, st + PL_ST_APPLIED);
-  pl_add(ins_len, st + PL_ST_INSERTED);
-  pl_max(depth, st + PL_ST_MAXDEPTH);
+  wave_count(kind == 0, st + PL_ST_VERBATIM);
+  wave_count(kind == 1, st + PL_ST_UNCHANGED);
+  wave_count(kind == 2, st + PL_ST_SUBST);
+  wave_count(kind == 3, st + PL_ST_DELETED);
+  wave_count(ins_len != 0, st + PL_ST_APPLIED);
+  wave_add(ins_len, st + PL_ST_INSERTED);
+  wave_max(depth, st + PL_ST_MAXDEPTH);
 }
 
 // rule 7: every position's bytes at the scan of the lengths (O), the applied insertion in front of the call
@@ -394,11 +357,6 @@ int pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const c
   return MSGPU_E_NOMEM;
 }
 
-template <class T> hipError_t pl_zeroed(DevArena &D, hipStream_t st, T **out, size_t n) {
-  hipError_t e = D.get(out, n);
-  return e == hipSuccess && n ? hipMemsetAsync(*out, 0, n * sizeof(T), st) : e;
-}
-
 int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
            uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq, msgpu_pl_result *res) {
   msgpu_pl_stats &S = res->stats;
@@ -445,7 +403,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   if ((rc = pl_room(c, fixed_bytes, "the pile-up", NB, "draft bases", n_runs, "runs")) != MSGPU_OK) return rc;
 
   kf_ull *d_st, *d_bad = reinterpret_cast<kf_ull *>(c->sc.d + PL_SC_BAD);
-  STAGE_HIP(c, pl_zeroed(D, st, &d_st, PL_ST_COUNT));
+  STAGE_HIP(c, D.get_zeroed(&d_st, PL_ST_COUNT, st));
   STAGE_HIP(c, hipMemsetAsync(d_bad, 0xff, 8, st));
 
   // ---- rule 1
@@ -453,11 +411,11 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   uint64_t        *d_off, *d_T, *d_Q;
   uint32_t        *d_ops, *d_run_chain, *d_tc, *d_qc;
   STAGE_HIP(c, D.get(&d_chains, n_chains));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_off, n_chains + 1ull));
+  STAGE_HIP(c, D.get_zeroed(&d_off, n_chains + 1ull, st));
   STAGE_HIP(c, D.get(&d_ops, n_runs));
   STAGE_HIP(c, D.get(&d_run_chain, n_runs));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_tc, n_runs + 1ull)); // (a zero behind the last run: the scans give n_runs + 1 sums)
-  STAGE_HIP(c, pl_zeroed(D, st, &d_qc, n_runs + 1ull));
+  STAGE_HIP(c, D.get_zeroed(&d_tc, n_runs + 1ull, st)); // (a zero behind the last run: the scans give n_runs + 1 sums)
+  STAGE_HIP(c, D.get_zeroed(&d_qc, n_runs + 1ull, st));
   STAGE_HIP(c, D.get(&d_T, n_runs + 1ull));
   STAGE_HIP(c, D.get(&d_Q, n_runs + 1ull));
   if (n_chains) {
@@ -502,15 +460,15 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   kf_ull   *d_vkey, *d_rec_depth, *d_rec_sub, *d_rec_del, *d_rec_ins;
   uint32_t *d_vidx, *d_span;
   uint64_t *d_S;
-  STAGE_HIP(c, pl_zeroed(D, st, &d_vkey, Q.n));
+  STAGE_HIP(c, D.get_zeroed(&d_vkey, Q.n, st));
   STAGE_HIP(c, D.get(&d_vidx, Q.n));
   if (Q.n) STAGE_HIP(c, hipMemsetAsync(d_vidx, 0xff, Q.n * 4ull, st));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_span, n_chains + 1ull));
+  STAGE_HIP(c, D.get_zeroed(&d_span, n_chains + 1ull, st));
   STAGE_HIP(c, D.get(&d_S, n_chains + 1ull));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_depth, R.n));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_sub, R.n));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_del, R.n));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_rec_ins, R.n));
+  STAGE_HIP(c, D.get_zeroed(&d_rec_depth, R.n, st));
+  STAGE_HIP(c, D.get_zeroed(&d_rec_sub, R.n, st));
+  STAGE_HIP(c, D.get_zeroed(&d_rec_del, R.n, st));
+  STAGE_HIP(c, D.get_zeroed(&d_rec_ins, R.n, st));
   STAGE_HIP(c, clock.begin(&S.voters_ms));
   if (n_chains) {
     const uint32_t mi = static_cast<uint32_t>(prm.min_identity);
@@ -523,8 +481,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     hipLaunchKernelGGL(k_pl_spans, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, d_vidx, d_vflag, d_span, d_rec_depth, d_st);
   }
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_span, d_S, n_chains + 1ull));
-  hipLaunchKernelGGL(k_pl_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_S + n_chains);
+  STAGE_HIP(c, stage_scan_total(D, st, d_span, d_S, n_chains, c->sc, PL_SC_TOTAL));
   STAGE_HIP(c, clock.end());
   if ((rc = c->sc.read(c)) != MSGPU_OK) return rc;
   const uint64_t n_cols = c->sc.h[PL_SC_TOTAL];
@@ -535,7 +492,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
 
   // ---- rules 3 and 4: the counters
   uint32_t *d_cnt;
-  STAGE_HIP(c, pl_zeroed(D, st, &d_cnt, PL_CLASSES * NB));
+  STAGE_HIP(c, D.get_zeroed(&d_cnt, PL_CLASSES * NB, st));
   STAGE_HIP(c, clock.begin(&S.pileup_ms));
   if (n_cols) hipLaunchKernelGGL(k_pl_pileup, dim3(grid256(n_cols)), dim3(256), 0, st, X, d_S, n_cols, R, Q, d_cnt, d_st);
   STAGE_HIP(c, hipGetLastError());
@@ -544,14 +501,13 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   // ---- rules 4 and 6: the insertion events
   uint32_t *d_flag, *d_E;
   kf_ull   *d_best;
-  STAGE_HIP(c, pl_zeroed(D, st, &d_flag, n_runs + 1ull));
+  STAGE_HIP(c, D.get_zeroed(&d_flag, n_runs + 1ull, st));
   STAGE_HIP(c, D.get(&d_E, n_runs + 1ull));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_best, NB));
+  STAGE_HIP(c, D.get_zeroed(&d_best, NB, st));
   STAGE_HIP(c, clock.begin(&S.insertions_ms));
   if (n_runs) hipLaunchKernelGGL((k_pl_ins<false>), dim3(grid256(n_runs)), dim3(256), 0, st, X, d_run_chain, d_vidx, d_vflag, R, Q, d_flag, nullptr, nullptr, nullptr, d_st);
   STAGE_HIP(c, hipGetLastError());
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_flag, d_E, n_runs + 1ull));
-  hipLaunchKernelGGL(k_pl_put<uint32_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_E + n_runs);
+  STAGE_HIP(c, stage_scan_total(D, st, d_flag, d_E, n_runs, c->sc, PL_SC_TOTAL));
   STAGE_HIP(c, clock.end());
   if ((rc = c->sc.read(c)) != MSGPU_OK) return rc;
   const uint32_t n_ev = static_cast<uint32_t>(c->sc.h[PL_SC_TOTAL]); // <= n_runs < 2^31
@@ -566,7 +522,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     STAGE_HIP(c, D.get(&d_seq, n_ev));
     STAGE_HIP(c, D.get(&d_key2, n_ev));
     STAGE_HIP(c, D.get(&d_seq2, n_ev));
-    STAGE_HIP(c, pl_zeroed(D, st, &d_head, n_ev + 1ull));
+    STAGE_HIP(c, D.get_zeroed(&d_head, n_ev + 1ull, st));
     STAGE_HIP(c, D.get(&d_G, n_ev + 1ull));
     STAGE_HIP(c, D.get(&d_gstart, n_ev + 1ull));
     STAGE_HIP(c, clock.begin(&S.insertions_ms));
@@ -578,7 +534,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     hipLaunchKernelGGL(k_pl_heads, dim3(grid256(n_ev)), dim3(256), 0, st, d_key, d_seq, n_ev, d_head);
     STAGE_HIP(c, hipGetLastError());
     STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_head, d_G, n_ev + 1ull));
-    hipLaunchKernelGGL(k_pl_gstart, dim3(grid256(n_ev + 1ull)), dim3(256), 0, st, d_head, d_G, n_ev, d_gstart);
+    hipLaunchKernelGGL(k_stage_seg_starts<uint32_t>, dim3(grid256(n_ev + 1ull)), dim3(256), 0, st, d_head, d_G, n_ev, d_gstart);
     hipLaunchKernelGGL(k_pl_best, dim3(grid256(n_ev)), dim3(256), 0, st, d_gstart, d_G + n_ev, d_key, d_best);
     STAGE_HIP(c, hipGetLastError());
     STAGE_HIP(c, clock.end());
@@ -589,7 +545,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   uint32_t *d_outlen;
   uint64_t *d_O;
   STAGE_HIP(c, D.get(&d_call, NB));
-  STAGE_HIP(c, pl_zeroed(D, st, &d_outlen, NB + 1ull));
+  STAGE_HIP(c, D.get_zeroed(&d_outlen, NB + 1ull, st));
   STAGE_HIP(c, D.get(&d_O, NB + 1ull));
   STAGE_HIP(c, clock.begin(&S.call_ms));
   const PlCall ca{d_cnt, d_best, d_gstart, d_key, d_call, d_outlen, d_rec_sub, d_rec_del, d_rec_ins, static_cast<uint32_t>(prm.min_depth)};
@@ -599,8 +555,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
 
   // ---- rule 7
   STAGE_HIP(c, clock.begin(&S.output_ms));
-  STAGE_HIP(c, stage_scan<const uint32_t *>(D, st, d_outlen, d_O, NB + 1ull));
-  hipLaunchKernelGGL(k_pl_put<uint64_t>, dim3(1), dim3(64), 0, st, c->sc.d, PL_SC_TOTAL, d_O + NB);
+  STAGE_HIP(c, stage_scan_total(D, st, d_outlen, d_O, NB, c->sc, PL_SC_TOTAL));
   STAGE_HIP(c, clock.end());
   if ((rc = c->sc.read(c)) != MSGPU_OK) return rc;
   const uint64_t raw_bytes = c->sc.h[PL_SC_TOTAL];
@@ -628,9 +583,8 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   STAGE_HIP(c, clock.end());
   STAGE_HIP(c, hipStreamSynchronize(st));
 
-  std::vector<msgpu_fasta_record> recs;
-  std::string                     hdr;
-  uint64_t                        text = 0;
+  FastaOut F; // (no pieces: k_pl_scatter wrote the bases; a record without bases keeps its header's '\n', rule 7)
+  std::string h;
   try {
     for (uint32_t r = 0; r < R.n; ++r) {
       const uint64_t len_in = msgpu_seq_length(FT.f, r), len_out = h_rec[1][r];
@@ -639,28 +593,13 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
         return MSGPU_E_ARG;
       }
       res->records[r] = msgpu_pl_record{len_in, len_out, h_rec[2][r], h_rec[3][r], h_rec[4][r], len_in ? h_rec[5][r] * 100 / len_in : 0};
-      const size_t h0 = hdr.size();
-      hdr.append(">").append(msgpu_seq_name(FT.f, r)).append("\n");
-      recs.push_back(msgpu_fasta_record{h_rec[0][r], text, static_cast<uint32_t>(len_out), static_cast<uint32_t>(h0), static_cast<uint32_t>(hdr.size() - h0), 0});
-      text += msgpu_fasta_text_bytes(static_cast<uint32_t>(hdr.size() - h0), len_out);
+      h.assign(">").append(msgpu_seq_name(FT.f, r)).append("\n");
+      F.recs.push_back(msgpu_fasta_record{h_rec[0][r], F.text, static_cast<uint32_t>(len_out), static_cast<uint32_t>(F.hdr.size()), static_cast<uint32_t>(h.size()), 0});
+      F.hdr.append(h);
+      F.text += msgpu_fasta_text_bytes(static_cast<uint32_t>(h.size()), len_out);
     }
-    res->text.resize(text);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (hdr.size() >= 0xffffffffull) return MSGPU_E_ARG;
-  uint8_t *d_text;
-  STAGE_HIP(c, D.get(&d_text, text + 16));
-  STAGE_HIP(c, clock.begin(&S.format_ms));
-  rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "format: %s", msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, clock.begin(&S.copy_ms));
-  if (text) STAGE_HIP(c, hipMemcpyAsync(&res->text[0], d_text, text, hipMemcpyDeviceToHost, st));
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, hipStreamSynchronize(st));
-  clock.collect();
+  if ((rc = F.emit(c, D, clock, d_raw, nullptr, nullptr, &S.format_ms, &S.copy_ms, res->text)) != MSGPU_OK) return rc;
 
   S.n_voters        = h_st[PL_ST_VOTERS];
   S.n_ignored       = h_st[PL_ST_IGNORED];
@@ -678,7 +617,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   S.ins_applied     = h_st[PL_ST_APPLIED];
   S.bases_inserted  = h_st[PL_ST_INSERTED];
   S.max_depth       = h_st[PL_ST_MAXDEPTH];
-  S.bytes_out       = text;
+  S.bytes_out       = F.text;
   S.bytes_peak      = D.peak;
   return MSGPU_OK;
 }

@@ -40,23 +40,12 @@ constexpr uint64_t SC_SENTINEL = ~0ull;
 constexpr int32_t  SC_NEAR     = 500; // two lines of a pair join when an end of one is nearer than this to the other's
 constexpr int64_t  SC_TRIM     = 200; // bases dropped at both ends of a read
 
-// the segment (of seg_off, n_seg + 1 entries) that element i lies in
-__device__ inline uint32_t sc_segment(const uint64_t *seg_off, uint32_t n_seg, uint64_t i) {
-  uint32_t lo = 0, hi = n_seg; // seg_off[lo] <= i < seg_off[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // pair p -> its chunk and its two lines i < j (p = pair_off[chunk] + j (j - 1) / 2 + i)
 __global__ __launch_bounds__(256) void k_scrub_pairs(const uint64_t *pair_off, uint32_t n_chunks, const uint32_t *chunk_first,
                                                      const uint32_t *hit_node, uint64_t *keys, uint32_t *ord) {
   const uint64_t p = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (p >= pair_off[n_chunks]) return;
-  const uint32_t c     = sc_segment(pair_off, n_chunks, p);
+  const uint32_t c     = last_le(pair_off, 0, n_chunks, p);
   const uint64_t local = p - pair_off[c];
   uint64_t       j     = static_cast<uint64_t>((1.0 + sqrt(1.0 + 8.0 * static_cast<double>(local))) * 0.5);
   while (j > 1 && j * (j - 1) / 2 > local) --j;
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(256) void k_scrub_intervals(const uint64_t *slot_of
                                                          const int32_t *st_e, const uint32_t *st_d, uint64_t *iv) {
   const uint64_t t = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (t >= slot_off[n_nodes]) return;
-  const uint32_t x     = sc_segment(slot_off, n_nodes, t);
+  const uint32_t x     = last_le(slot_off, 0, n_nodes, t);
   const uint64_t local = t - slot_off[x], na = anc_off[x + 1] - anc_off[x];
   uint64_t       v = SC_SENTINEL;
   if (local < na) {
@@ -523,14 +512,10 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
   STAGE_HIP(c, hipStreamSynchronize(st));
 
   // ---- output plan: batch after batch, the centre nodes by id, a node's covered ranges in order
-  const StageTimer                planning;
-  std::vector<msgpu_copy>         pieces;
-  std::vector<msgpu_fasta_record> recs;
-  std::string                     hdr;
-  uint64_t                        raw = 0, text = 0;
+  FastaOut F;
   try {
-    pieces.reserve(NR);
-    recs.reserve(NR);
+    F.pieces.reserve(NR);
+    F.recs.reserve(NR);
     std::string h;
     char        buf[32];
     for (uint64_t k = 0; k < pt.centre_off[NB]; ++k) {
@@ -543,58 +528,17 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
         const int64_t lo = std::max<int64_t>(cr.x, SC_TRIM);
         const int64_t hi = std::min<int64_t>(cr.y, static_cast<int64_t>(tb.node_length[x]) - SC_TRIM); // >= 0: length >= 200
         const int64_t e  = std::min<int64_t>(hi + 1, L), b = std::min<int64_t>(lo, L);
-        const uint64_t n = e > b ? static_cast<uint64_t>(e - b) : 0;
         h.assign(">").append(name);
         snprintf(buf, sizeof(buf), "_%u\n", r);
         h.append(buf);
-        // a record without bases: the header without its '\n' (msgpu_fasta_format closes every record with one)
-        const uint32_t hl = static_cast<uint32_t>(n ? h.size() : h.size() - 1);
-        if (n) pieces.push_back(msgpu_copy{msgpu_seq_offset(f, i) + static_cast<uint64_t>(b), raw, static_cast<uint32_t>(n), 0});
-        recs.push_back(msgpu_fasta_record{raw, text, static_cast<uint32_t>(n), static_cast<uint32_t>(hdr.size()), hl, 0});
-        hdr.append(h.data(), hl);
-        raw += n;
-        text += msgpu_fasta_text_bytes(hl, n);
+        F.add(msgpu_seq_offset(f, i) + static_cast<uint64_t>(b), e > b ? static_cast<uint64_t>(e - b) : 0, 0, h.data(), h.size());
       }
     }
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (hdr.size() >= 0xffffffffull) return MSGPU_E_ARG;
-  S.n_records  = recs.size();
-  S.bases      = raw;
-  S.text_bytes = text;
-  msgpu_gather_plan *plan = nullptr;
-  rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan);
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  struct FreePlan {
-    msgpu_gather_plan *p;
-    ~FreePlan() { msgpu_gather_plan_free(p); }
-  } free_plan{plan};
-  S.plan_ms = planning.ms();
-  uint8_t *d_raw, *d_text;
-  STAGE_HIP(c, D.get(&d_raw, raw + 16));
-  STAGE_HIP(c, D.get(&d_text, text + 16));
-  STAGE_HIP(c, clock.begin(&S.gather_ms));
-  rc = msgpu_gather_run(c->seq, plan, d_raw, raw + 16, st);
-  if (rc == MSGPU_OK) {
-    STAGE_HIP(c, clock.end());
-    STAGE_HIP(c, clock.begin(&S.format_ms)); // (from the same point of the stream)
-    rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
-  }
-  if (rc != MSGPU_OK) {
-    snprintf(c->err, sizeof(c->err), "gather / format: %s", msgpu_seq_last_error(c->seq));
-    return rc;
-  }
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, clock.begin(&S.copy_ms)); // (from the same point of the stream)
-  try {
-    res->text.resize(text);
-  } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
-  if (text) STAGE_HIP(c, hipMemcpyAsync(res->text.data(), d_text, text, hipMemcpyDeviceToHost, st));
-  STAGE_HIP(c, clock.end());
-  STAGE_HIP(c, hipStreamSynchronize(st));
-  clock.collect();
+  S.n_records  = F.recs.size();
+  S.bases      = F.raw;
+  S.text_bytes = F.text;
+  if ((rc = F.emit(c, D, clock, nullptr, &S.plan_ms, &S.gather_ms, &S.format_ms, &S.copy_ms, res->text)) != MSGPU_OK) return rc;
   S.wall_ms = wall.ms();
   *out      = res.release();
   return MSGPU_OK;

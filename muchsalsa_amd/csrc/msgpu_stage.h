@@ -3,7 +3,9 @@
 // its create / destroy, the HIP-error macro, the holders of an event and of a stream, the device arena with its temporary
 // buffer for rocPRIM, the event clock, the wall-clock timer, the scalar block and its read-back, the record lookup of
 // the stages that name sequences, and the loader of the stages that read a store's bases.  msgpu_seq.hip takes the holders.
-// No kernels.
+// And the host-side idioms of the stage files, one copy of each: the arena block that comes zeroed (DevArena::get_zeroed), the
+// scan whose total goes into the scalar block (stage_scan_total), a 64- or 128-bit key as two words (key_split), and the
+// records of a FASTA text with their way through gather, format and copy (FastaOut).  No kernels.
 #ifndef MSGPU_STAGE_H
 #define MSGPU_STAGE_H
 
@@ -17,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -185,6 +188,10 @@ struct DevArena { // device memory freed on every way out of a run
     }
     *out = static_cast<T *>(m);
     return e;
+  }
+  template <class T> hipError_t get_zeroed(T **out, size_t count, hipStream_t st) { // the block, zeroed in st
+    hipError_t e = get(out, count);
+    return e == hipSuccess && count ? hipMemsetAsync(*out, 0, count * sizeof(T), st) : e;
   }
   void drop(void *x) { // (not for the blocks of a reserved arena: rewind() returns those)
     auto it = std::find(p.begin(), p.end(), x);
@@ -360,6 +367,22 @@ struct ScalarBlock {
   }
 };
 
+// Exclusive sums of n + 1 words of which the last is zero, so that out[n] is the total, and the total into `slot` of the
+// scalar block.  Nothing is read back: the caller's sc.read(c) does that, behind whatever else it enqueues first.
+template <class Out> hipError_t stage_scan_total(DevArena &D, hipStream_t st, const uint32_t *in, Out *out, size_t n, ScalarBlock &sc, int slot) {
+  const hipError_t e = stage_scan(D, st, in, out, n + 1);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_stage_put<Out>, dim3(1), dim3(64), 0, st, sc.d, slot, out + n);
+  return hipGetLastError();
+}
+
+// a key of 64 or of 128 bits as (hi, lo)
+template <class K> void key_split(K key, uint64_t &hi, uint64_t &lo) {
+  lo = static_cast<uint64_t>(key);
+  if constexpr (sizeof(K) > 8) hi = static_cast<uint64_t>(key >> 64);
+  else hi = 0;
+}
+
 // ---- the records a stage's ids name
 
 constexpr uint32_t STAGE_NONE = 0xffffffffu;
@@ -437,6 +460,78 @@ template <class Ctx> int stage_load(Ctx *c, DevArena &D, const char *path, int k
   F.recs.n_bases = n_bases;
   return MSGPU_OK;
 }
+
+// ---- a stage's FASTA text
+
+// The records of the text, collected one by one, and their way to the host: the bases gathered from the context's sequence
+// store piece by piece (or written by the stage's own kernels), wrapped by msgpu_fasta_format, copied.
+struct FastaOut {
+  StageTimer                      planning; // from the first record to the gather plan
+  std::vector<msgpu_copy>         pieces;
+  std::vector<msgpu_fasta_record> recs;
+  std::string                     hdr;      // every header, one behind the other
+  uint64_t                        raw = 0, text = 0; // the bases and the bytes of text so far
+  // a record of the n bases at `src` of the store (`from`: the MSGPU_COPY_* flags of its pieces), under header h of hn bytes
+  void add(uint64_t src, uint64_t n, uint32_t from, const char *h, size_t hn) {
+    // a record without bases: the header without its '\n' (msgpu_fasta_format closes every record with one)
+    const uint32_t hl = static_cast<uint32_t>(n ? hn : hn - 1);
+    if (n) pieces.push_back(msgpu_copy{src, raw, static_cast<uint32_t>(n), from});
+    recs.push_back(msgpu_fasta_record{raw, text, static_cast<uint32_t>(n), static_cast<uint32_t>(hdr.size()), hl, 0});
+    hdr.append(h, hl);
+    raw += n;
+    text += msgpu_fasta_text_bytes(hl, n);
+  }
+  // The text -> dest, through the arena; returns behind the stream's synchronisation with the clock collected.  d_raw: the
+  // records' bases where the stage wrote them itself; null: the pieces are gathered from the store.  The four accumulators
+  // take the planning time and the spans of gather, format and copy (null: no span)
+  template <class Ctx, class Text /* of chars: a string or a vector */>
+  int emit(Ctx *c, DevArena &D, StageClock &clock, const uint8_t *d_raw, float *plan_ms, float *gather_ms, float *format_ms, float *copy_ms,
+           Text &dest) {
+    hipStream_t st = c->stream;
+    if (hdr.size() >= 0xffffffffull) return MSGPU_E_ARG;
+    const bool gathers = !d_raw;
+    struct FreePlan {
+      msgpu_gather_plan *p = nullptr;
+      ~FreePlan() { msgpu_gather_plan_free(p); }
+    } plan;
+    int rc = MSGPU_OK;
+    if (gathers) {
+      rc = msgpu_gather_plan_create(c->seq, pieces.data(), pieces.size(), &plan.p);
+      if (rc != MSGPU_OK) {
+        snprintf(c->err, sizeof(c->err), "gather plan: %s", msgpu_seq_last_error(c->seq));
+        return rc;
+      }
+    }
+    if (plan_ms) *plan_ms = planning.ms();
+    uint8_t *d_gathered = nullptr, *d_text;
+    if (gathers) STAGE_HIP(c, D.get(&d_gathered, raw + 16));
+    STAGE_HIP(c, D.get(&d_text, text + 16));
+    if (gathers) {
+      d_raw = d_gathered;
+      if (gather_ms) STAGE_HIP(c, clock.begin(gather_ms));
+      rc = msgpu_gather_run(c->seq, plan.p, d_gathered, raw + 16, st);
+      if (rc == MSGPU_OK && gather_ms) STAGE_HIP(c, clock.end());
+    }
+    if (rc == MSGPU_OK) {
+      if (format_ms) STAGE_HIP(c, clock.begin(format_ms)); // (from the same point of the stream)
+      rc = msgpu_fasta_format(c->seq, d_raw, recs.data(), recs.size(), hdr.data(), hdr.size(), d_text, text + 16, st);
+    }
+    if (rc != MSGPU_OK) {
+      snprintf(c->err, sizeof(c->err), "%s: %s", gathers ? "gather / format" : "format", msgpu_seq_last_error(c->seq));
+      return rc;
+    }
+    if (format_ms) STAGE_HIP(c, clock.end());
+    if (copy_ms) STAGE_HIP(c, clock.begin(copy_ms)); // (from the same point of the stream)
+    try {
+      dest.resize(text);
+    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+    if (text) STAGE_HIP(c, hipMemcpyAsync(&dest[0], d_text, text, hipMemcpyDeviceToHost, st));
+    if (copy_ms) STAGE_HIP(c, clock.end());
+    STAGE_HIP(c, hipStreamSynchronize(st));
+    clock.collect();
+    return MSGPU_OK;
+  }
+};
 
 } // namespace msgpu
 

@@ -144,8 +144,7 @@ __global__ __launch_bounds__(256) void k_ug_apply(uint32_t n, uint8_t *alive, ui
     alive[r] = 0;
     mark[r]  = 0;
   }
-  const uint64_t who = __ballot(go);
-  if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(removed, static_cast<kf_ull>(__popcll(who)));
+  wave_count(go, removed);
 }
 
 // rule 9, the forks of a round: the oriented nodes with two or more successors, compacted into a list (any order)
@@ -153,20 +152,12 @@ template <class K>
 __global__ __launch_bounds__(256) void k_ug_forks(UgGraph<K> g, const uint8_t *alive, const uint8_t *adj, uint32_t *forks, uint64_t cap,
                                                   kf_ull *cursor) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int      lane = threadIdx.x & 63;
   const uint32_t o = static_cast<uint32_t>(i);
   bool           take = false;
   if (i < 2ull * g.n && alive[o >> 1] && __popc(ug_out(adj[o >> 1], o)) >= 2)
     take = !(o & 1) || ug_rc(g.keys[o >> 1], g.k) != g.keys[o >> 1]; // a self-complementary k-mer is one node
-  const uint64_t who = __ballot(take);
-  if (!who) return;
-  kf_ull at = 0;
-  if (lane == __ffsll(static_cast<long long>(who)) - 1) at = atomicAdd(cursor, static_cast<kf_ull>(__popcll(who)));
-  at = __shfl(at, __ffsll(static_cast<long long>(who)) - 1);
-  if (take) {
-    const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
-    if (slot < cap) forks[slot] = o;
-  }
+  const uint64_t slot = wave_append(take, cursor);
+  if (take && slot < cap) forks[slot] = o;
 }
 
 // rule 9, one round: a quad of lanes per fork, lane c walks the branch entered by base c (at most `bubble` look-ups) and
@@ -297,8 +288,7 @@ __global__ __launch_bounds__(256) void k_ug_double(uint64_t n2, const uint32_t *
     ptr_out[o]  = q;
     dist_out[o] = d;
   }
-  const uint64_t who = __ballot(is_open);
-  if (who && (threadIdx.x & 63) == __ffsll(static_cast<long long>(who)) - 1) atomicAdd(open, static_cast<kf_ull>(__popcll(who)));
+  wave_count(is_open, open);
 }
 
 // what still points at no head lies on a cycle: back = the previous node, low = the node itself
@@ -349,7 +339,6 @@ template <class K, bool WRITE>
 __global__ __launch_bounds__(256) void k_ug_heads(UgGraph<K> g, const uint32_t *next, const uint32_t *ptr, K *first, uint32_t *head,
                                                   uint64_t cap, kf_ull *cursor) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int      lane = threadIdx.x & 63;
   bool           take = false;
   K              s = 0;
   const uint32_t o = static_cast<uint32_t>(i);
@@ -358,17 +347,10 @@ __global__ __launch_bounds__(256) void k_ug_heads(UgGraph<K> g, const uint32_t *
     const uint32_t m = ptr[o ^ 1]; // the mirror chain's head (UG_NONE: a self-complementary k-mer, which exists once)
     take = m == UG_NONE || s < ug_seq(g, m);
   }
-  const uint64_t who = __ballot(take);
-  if (!who) return;
-  kf_ull at = 0;
-  if (lane == __ffsll(static_cast<long long>(who)) - 1) at = atomicAdd(cursor, static_cast<kf_ull>(__popcll(who)));
-  at = __shfl(at, __ffsll(static_cast<long long>(who)) - 1);
-  if (WRITE && take) {
-    const uint64_t slot = at + __popcll(who & ((1ull << lane) - 1));
-    if (slot < cap) {
-      first[slot] = s;
-      head[slot]  = o;
-    }
+  const uint64_t slot = wave_append(take, cursor);
+  if (WRITE && take && slot < cap) {
+    first[slot] = s;
+    head[slot]  = o;
   }
 }
 
@@ -451,16 +433,6 @@ enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOT
 static_assert(UG_SC_BUBBLES == UG_SC_FORKS + 1 && UG_SC_BRANCHES == UG_SC_FORKS + 2, "one memset zeroes the bubble rounds' counters");
 
 inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->sc.d + slot, 0, 8, c->stream); }
-
-template <class K> void ug_split(K key, uint64_t &hi, uint64_t &lo);
-template <> void ug_split<uint64_t>(uint64_t key, uint64_t &hi, uint64_t &lo) {
-  hi = 0;
-  lo = key;
-}
-template <> void ug_split<kf_u128>(kf_u128 key, uint64_t &hi, uint64_t &lo) {
-  hi = static_cast<uint64_t>(key >> 64);
-  lo = static_cast<uint64_t>(key);
-}
 
 // everything behind the format check, for one key width
 template <class K>
@@ -783,7 +755,7 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
       T.coverage = cover[u];
       T.cyclic   = cyclic[u];
       T.reserved = 0;
-      ug_split<K>(first[u], T.first_hi, T.first_lo);
+      key_split(first[u], T.first_hi, T.first_lo);
       head_len[u] = static_cast<uint32_t>(snprintf(buf, sizeof(buf), ">%u %llu %llu\n", u, static_cast<kf_ull>(T.length), cover[u]));
       heads.append(buf, head_len[u]);
       T.offset   = total + head_len[u];

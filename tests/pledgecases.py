@@ -80,7 +80,7 @@ def _block_cases(c):
     sub_u = u[:AT] + o(u, AT) + u[AT + 1:]
     voters = [SAME if n % 3 == 2 else SUB for n in range(300)]
     _add(c, "chains_300", u, voters, dict(bases=[sub_u], max_depth=300, n_voters=300, n_ignored=0, cols_x=200, pos_substituted=1),
-         "k_pl_check_chain, k_pl_voter_key / _idx and k_pl_spans over two blocks; pl_count on the 44 live lanes of the second")
+         "k_pl_check_chain, k_pl_voter_key / _idx and k_pl_spans over two blocks; wave_count on the 44 live lanes of the second")
     both = []
     for n, v in enumerate(voters):
         both += [dict(t=0, ts=0, script=v[2], score=100), dict(t=0, ts=0, script=[("X", 130)], read=n, score=90)]
@@ -91,7 +91,7 @@ def _block_cases(c):
     _add(c, "span_1_chains", u, [(0, n % 130, [("X", 1)]) for n in range(390)],
          dict(bases=[bytes(plcases.other(b) for b in u)], max_depth=3, n_voters=390, cols_x=390, cols_eq=0, pos_substituted=130,
               depth_x100=[300]),
-         "every column is a chain of its own: pl_last_le over S ends on every lane, a == u in the search over T")
+         "every column is a chain of its own: last_le over S ends on every lane, a == u in the search over T")
     w = bytes(_genome()[1000:1600])
     spans = [
         (0, 0, [("=", 100), ("X", 1), ("=", 50), ("D", 1), ("=", 40), ("I", b"GT"), ("=", 64)]),  # 256 columns: block 0
@@ -159,9 +159,9 @@ def _insertion_cases(c):
          "and one at slot tlen; record 0 has depth 3 at the same slots and takes nothing")
     _add(c, "events_256", u, [ins(b"AC")] * 256 + [SAME] * 44,
          dict(bases=[ac], ins_usable=256, ins_applied=1, bases_inserted=2, max_depth=300, cols_i=512),
-         "n_ev == 256: k_pl_gstart's e == n thread is alone in a second block; one group that fills a block")
+         "n_ev == 256: k_stage_seg_starts' thread n is alone in a second block; one group that fills a block")
     _add(c, "events_300_one_group", u, [ins(b"AC")] * 300, dict(bases=[ac], ins_usable=300, ins_applied=1, bases_inserted=2),
-         "one group of 300 equal events across the block boundary of k_pl_heads and k_pl_gstart")
+         "one group of 300 equal events across the block boundary of k_pl_heads and k_stage_seg_starts")
     _add(c, "events_two_groups_across_a_block", u, [ins(b"AC")] * 200 + [ins(b"A")] * 100,
          dict(bases=[ac], ins_usable=300, ins_applied=1, bases_inserted=2),
          "sorted, 100 events A stand before 200 events AC: the head of the second group is event 100, its end is in block 1")

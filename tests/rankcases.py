@@ -76,6 +76,15 @@ def tables():
     t["sparse_queries"] = ([ch(5, 100, 0, 10), ch(5, 90, 0, 10), ch(4000000000, 100, 0, 10), ch(4294967295, 100, 0, 10),
                             ch(4294967295, 100, 5, 15)], "query records that are not consecutive numbers")
     t["empty"] = ([], "the empty table")
+    # (a generator of their own: the tables above stay what they were)
+    rng = random.Random(256)
+    full = []
+    for q, n in enumerate((1, 2, 64, 189)):
+        full += random_segment(rng, q, n)
+    t["chains_256"] = (full, "256 chains in segments of 1, 2, 64 and 189: k_stage_seg_starts' thread n, which writes the closing "
+                             "entry of the segment starts, is alone in a second workgroup")
+    t["chains_257"] = (full + random_segment(rng, 4, 1), "the same and one more segment of 1 chain: the last chain and the closing "
+                                                         "entry come from the second workgroup")
     return t
 
 
