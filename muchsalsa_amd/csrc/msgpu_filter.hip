@@ -562,6 +562,7 @@ int msgpu_uf_run(msgpu_ufctx *c, const msgpu_uf *u, const char *unitigs_path, ui
   S.bases      = F.raw;
   S.text_bytes = F.text;
   if ((rc = F.emit(c, D, clock, nullptr, &S.plan_ms, &S.gather_ms, &S.format_ms, &S.copy_ms, res->text)) != MSGPU_OK) return rc;
+  if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
   S.wall_ms = wall.ms();
   *out      = res.release();
   return MSGPU_OK;

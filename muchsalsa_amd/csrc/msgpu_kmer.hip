@@ -289,6 +289,7 @@ int kf_pair_open(StageCtx *c, const char *path_a, const char *path_b, msgpu_pair
     p->F[1].ls = p->F[0].ls;
   }
   p->records_ms = records.ms();
+  if (stage_verify(c, p->D) != MSGPU_OK) return MSGPU_E_HIP;
   *out          = p.release();
   return MSGPU_OK;
 }
@@ -296,6 +297,8 @@ int kf_pair_open(StageCtx *c, const char *path_a, const char *path_b, msgpu_pair
 void kf_pair_close(msgpu_pair *p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
+  char err[256]; // (nobody takes an error here: one line)
+  if (p->D.verify(nullptr, err, sizeof(err)) != hipSuccess) fprintf(stderr, "msgpu_pair_close: %s\n", err);
   delete p;
 }
 
@@ -565,6 +568,7 @@ int msgpu_kf_run_pair(msgpu_kfctx *c, int k, const msgpu_pair *pair, uint32_t fl
     (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
     return rc;
   }
+  if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
   char buf[96];
   snprintf(buf, sizeof(buf), "abundance threshold for k-mer filtering:  %lld\n", static_cast<long long>(S.upper));
   try {

@@ -1564,9 +1564,8 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   MpBatch       b;
   int           rc;
   b.A = static_cast<uint32_t>(bt.n_anchors);
-  B.rewind();
+  STAGE_HIP(c, B.rewind());
   if (!b.A) return MSGPU_OK;
-  if (getenv("MSGPU_POISON")) STAGE_HIP(c, hipMemsetAsync(B.pool, 0xA5, B.pool_bytes, c->stream)); // (see DevBuf::ensure in msgpu_api.hip)
   if ((rc = mp_expand(R, B, bt, b)) != MSGPU_OK) return rc;
   if ((rc = mp_classes(R, B, b)) != MSGPU_OK) return rc;
   if ((rc = mp_chain(R, B, b)) != MSGPU_OK) return rc;
@@ -1586,7 +1585,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
   if ((rc = mp_batch_host(R, b)) != MSGPU_OK) return rc;
   R.clock.collect();
   bt.bytes_peak = B.peak;
-  return MSGPU_OK;
+  return stage_verify(c, B);
 }
 
 } // namespace
@@ -1605,6 +1604,10 @@ struct msgpu_map_index {
   uint32_t     *d_ucnt = nullptr, *d_ustart = nullptr, *d_slots = nullptr;
   uint32_t      n_keys = 0, slots_n = 0;
   float         load_ms = 0.f, sketch_ms = 0.f, sort_ms = 0.f, table_ms = 0.f, wall_ms = 0.f;
+  ~msgpu_map_index() { // (on the owner's device, behind its stream; nobody takes an error here: one line)
+    char err[256];
+    if (D.verify(nullptr, err, sizeof(err)) != hipSuccess) fprintf(stderr, "msgpu_map_index_free: %s\n", err);
+  }
 };
 
 msgpu_mapctx::~msgpu_mapctx() { delete index; }
@@ -1673,7 +1676,7 @@ int mp_index_build(msgpu_mapctx *c, int k, int w, const char *tpath, msgpu_map_i
   I.n_keys  = n_keys;
   I.slots_n = sn;
   I.wall_ms = wall.ms();
-  return MSGPU_OK;
+  return stage_verify(c, D);
 }
 
 // a run on an index: the query side, rule 3's cap at this run's max_occ, rules 4 to 9
@@ -1824,6 +1827,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   STAGE_HIP(c, hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, st));
   STAGE_HIP(c, hipStreamSynchronize(st));
   clock.collect();
+  if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
   for (int i = 0; i < 32; ++i) S.group_hist[i < 15 ? i : 15] += hist[i];
   const StageTimer formatting;
   try {
@@ -2164,6 +2168,7 @@ int msgpu_map_rank_tables(msgpu_mapctx *c, const msgpu_map_chain *chains, uint64
   const hipError_t e = hipStreamSynchronize(st);
   if (rc == MSGPU_OK && e != hipSuccess) rc = stage_fail(c, MSGPU_E_HIP, "hipStreamSynchronize", e);
   clock.collect();
+  if (rc == MSGPU_OK) rc = stage_verify(c, D);
   if (rc == MSGPU_E_ARG && bad != ~0ull && bad < n) {
     c->table_rstats = msgpu_map_rstats{};
     if (chains[bad].q_start > chains[bad].q_end)

@@ -600,6 +600,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     }
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   if ((rc = F.emit(c, D, clock, d_raw, nullptr, nullptr, &S.format_ms, &S.copy_ms, res->text)) != MSGPU_OK) return rc;
+  if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
 
   S.n_voters        = h_st[PL_ST_VOTERS];
   S.n_ignored       = h_st[PL_ST_IGNORED];

@@ -539,6 +539,7 @@ int msgpu_scrub_run(msgpu_scrubctx *c, const msgpu_scrub *s, const char *reads_p
   S.bases      = F.raw;
   S.text_bytes = F.text;
   if ((rc = F.emit(c, D, clock, nullptr, &S.plan_ms, &S.gather_ms, &S.format_ms, &S.copy_ms, res->text)) != MSGPU_OK) return rc;
+  if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
   S.wall_ms = wall.ms();
   *out      = res.release();
   return MSGPU_OK;

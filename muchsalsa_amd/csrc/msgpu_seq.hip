@@ -1257,7 +1257,7 @@ int msgpu_edit_script(msgpu_seqctx *c, const void *d_a, const void *d_b, const m
              h_cnt[ES_CNT_BROKEN]);
     return MSGPU_E_STATE;
   }
-  return MSGPU_OK;
+  return stage_verify(c, D);
 }
 
 int msgpu_extend_ends(msgpu_seqctx *c, const void *d_a, const void *d_b, const msgpu_align_pair *pairs, size_t n, uint32_t band,
@@ -1321,7 +1321,7 @@ int msgpu_extend_ends(msgpu_seqctx *c, const void *d_a, const void *d_b, const m
   STAGE_HIP(c, hipMemcpyAsync(h_words.data(), d_words, n * stride * 4, hipMemcpyDeviceToHost, st));
   STAGE_HIP(c, hipStreamSynchronize(st));
   for (size_t i = 0; i < n; ++i) std::copy_n(h_words.data() + i * stride, ends[i].e + 1ull, words + off[i]);
-  return MSGPU_OK;
+  return stage_verify(c, D);
 }
 
 } // extern "C"

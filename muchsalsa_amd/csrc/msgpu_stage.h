@@ -153,9 +153,41 @@ struct DevArena { // device memory freed on every way out of a run
   size_t   pool_bytes = 0, pool_used = 0;
   static constexpr size_t ALIGN = 256;
   static size_t           aligned(size_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
+  // MSGPU_POISON (debugging, asked per call; see DevBuf::ensure in msgpu_api.hip): whatever get(), room(), reserve() and
+  // rewind() hand out is filled with 0xA5, and the fill is complete when they return (the stage streams do not wait for the
+  // null stream).  A block from hipMalloc, and a reservation as a whole, then lies between two guards of GUARD bytes of
+  // 0xC3 that belong to the same allocation and to nobody: drop() checks those of its block, verify() those of every block
+  // still held.  The blocks inside a reservation stay adjacent and are not fenced from one another.  The guards are not
+  // counted in live / peak.  Without the variable none of this exists: the same calls, sizes and addresses as ever.
+  static constexpr size_t  GUARD = 256;
+  static constexpr uint8_t POISON_BYTE = 0xA5, GUARD_BYTE = 0xC3;
+  struct Fenced { // a block between guards: its address as handed out, its bytes, its number among the arena's allocations
+    void  *x;
+    size_t bytes, index;
+  };
+  std::vector<Fenced> fenced;
+  bool                pool_fenced = false;
+  size_t              n_blocks = 0; // the blocks from hipMalloc so far (a reservation is the one block of its arena)
+  std::string         broken;       // the first guard found overwritten, kept for verify()
+  static bool poisoned() { return getenv("MSGPU_POISON") != nullptr; }
+  static hipError_t fill(void *x, size_t n, bool wait_first) { // 0xA5 over n bytes that work in flight may still use, or nobody
+    hipError_t e = wait_first ? hipDeviceSynchronize() : hipSuccess;
+    if (e == hipSuccess) e = hipMemset(x, POISON_BYTE, n);
+    return e == hipSuccess ? hipDeviceSynchronize() : e;
+  }
+  static hipError_t fence(uint8_t *base, size_t n) { // guard, n bytes of poison, guard
+    hipError_t e = hipMemset(base, GUARD_BYTE, GUARD);
+    if (e == hipSuccess) e = hipMemset(base + GUARD + n, GUARD_BYTE, GUARD);
+    return e == hipSuccess ? fill(base + GUARD, n, false) : e;
+  }
+  void *base_of(void *x) const { // what hipMalloc returned for block x
+    for (const Fenced &f : fenced)
+      if (f.x == x) return static_cast<uint8_t *>(x) - GUARD;
+    return x;
+  }
   ~DevArena() {
-    for (void *x : p) (void)hipFree(x);
-    if (pool) (void)hipFree(pool);
+    for (void *x : p) (void)hipFree(base_of(x));
+    if (pool) (void)hipFree(pool_fenced ? pool - GUARD : pool);
   }
   void hold(size_t n) {
     live += n;
@@ -163,28 +195,56 @@ struct DevArena { // device memory freed on every way out of a run
   }
   hipError_t reserve(size_t n) { // once, on an arena that holds nothing
     pool_bytes = aligned(n ? n : 1);
-    return hipMalloc(reinterpret_cast<void **>(&pool), pool_bytes);
+    if (!poisoned()) return hipMalloc(reinterpret_cast<void **>(&pool), pool_bytes);
+    uint8_t   *m = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&m), pool_bytes + 2 * GUARD);
+    if (e != hipSuccess) return e;
+    e = fence(m, pool_bytes);
+    if (e != hipSuccess) {
+      (void)hipFree(m);
+      return e;
+    }
+    pool        = m + GUARD;
+    pool_fenced = true;
+    return hipSuccess;
   }
-  void rewind() { // (after a synchronisation) a reserved arena as it was after reserve()
+  hipError_t rewind() { // (after a synchronisation) a reserved arena as it was after reserve()
     pool_used = tmp_bytes = live = peak = 0;
     tmp = nullptr;
+    return pool && poisoned() ? fill(pool, pool_bytes, false) : hipSuccess;
   }
   template <class T> hipError_t get(T **out, size_t count) {
     const size_t n = (count ? count : 1) * sizeof(T);
     if (pool) {
       *out = nullptr;
       if (aligned(n) > pool_bytes - pool_used - tmp_bytes) return hipErrorOutOfMemory;
+      if (poisoned()) { // (bytes that an earlier temporary buffer of the batch may have held)
+        const hipError_t e = fill(pool + pool_used, aligned(n), true);
+        if (e != hipSuccess) return e;
+      }
       *out = reinterpret_cast<T *>(pool + pool_used);
       pool_used += aligned(n);
       hold(aligned(n));
       return hipSuccess;
     }
+    const bool fenced_block = poisoned();
     void      *m = nullptr;
-    hipError_t e = hipMalloc(&m, n);
+    hipError_t e = hipMalloc(&m, fenced_block ? n + 2 * GUARD : n);
+    if (e == hipSuccess && fenced_block) {
+      e = fence(static_cast<uint8_t *>(m), n);
+      if (e == hipSuccess) {
+        m = static_cast<uint8_t *>(m) + GUARD;
+        fenced.push_back(Fenced{m, n, n_blocks});
+      } else {
+        (void)hipFree(m);
+        m = nullptr;
+      }
+    }
     if (e == hipSuccess) {
       p.push_back(m);
       p_bytes.push_back(n);
       hold(n);
+      ++n_blocks;
     }
     *out = static_cast<T *>(m);
     return e;
@@ -200,6 +260,15 @@ struct DevArena { // device memory freed on every way out of a run
       p_bytes.erase(p_bytes.begin() + (it - p.begin()));
       p.erase(it);
     }
+    for (size_t i = 0; i < fenced.size(); ++i)
+      if (fenced[i].x == x) { // its guards, behind everything that may still write: hipFree would wait for that as well
+        hipError_t e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = check(x, fenced[i].bytes, fenced[i].index, false);
+        if (e != hipSuccess && broken.empty()) broken = std::string("arena guard: ") + hipGetErrorString(e);
+        x = static_cast<uint8_t *>(x) - GUARD;
+        fenced.erase(fenced.begin() + i);
+        break;
+      }
     (void)hipFree(x);
   }
   hipError_t room(size_t need) {
@@ -207,6 +276,10 @@ struct DevArena { // device memory freed on every way out of a run
     if (pool) {
       const size_t n = aligned(need ? need : 1);
       if (n > pool_bytes - pool_used) return hipErrorOutOfMemory;
+      if (poisoned()) { // (the smaller buffer it grows over may be in use)
+        const hipError_t e = fill(pool + pool_bytes - n, n, true);
+        if (e != hipSuccess) return e;
+      }
       hold(n - tmp_bytes);
       tmp       = pool + pool_bytes - n;
       tmp_bytes = n;
@@ -226,7 +299,40 @@ struct DevArena { // device memory freed on every way out of a run
     tmp       = nullptr;
     tmp_bytes = 0;
   }
+  // the two guards around the n bytes at x (behind a synchronisation); the first byte that is not a guard's goes into `broken`
+  hipError_t check(const void *x, size_t n, size_t index, bool reservation) {
+    uint8_t        h[2 * GUARD];
+    const uint8_t *b = static_cast<const uint8_t *>(x);
+    hipError_t     e = hipMemcpy(h, b - GUARD, GUARD, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h + GUARD, b + n, GUARD, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (size_t i = 0; i < 2 * GUARD && broken.empty(); ++i)
+      if (h[i] != GUARD_BYTE) {
+        char t[192];
+        snprintf(t, sizeof(t), "arena guard: block %zu%s of %zu bytes: the %s guard was written (0x%02x at byte %zu of its %zu)", index,
+                 reservation ? " (the reservation)" : "", n, i < GUARD ? "front" : "back", h[i], i % GUARD, GUARD);
+        broken = t;
+      }
+    return hipSuccess;
+  }
+  // The guards of every block still held, behind a synchronisation of st; nothing without MSGPU_POISON.  Anything but
+  // hipSuccess: a guard was written (here, or in a block that drop() gave back), or the check itself failed; `err` says which
+  hipError_t verify(hipStream_t st, char *err, size_t err_bytes) {
+    if (!poisoned()) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(st);
+    for (size_t i = 0; i < fenced.size() && e == hipSuccess; ++i) e = check(fenced[i].x, fenced[i].bytes, fenced[i].index, false);
+    if (e == hipSuccess && pool_fenced) e = check(pool, pool_bytes, 0, true);
+    if (e != hipSuccess) snprintf(err, err_bytes, "arena guard: %s", hipGetErrorString(e));
+    else if (!broken.empty()) snprintf(err, err_bytes, "%s", broken.c_str());
+    else return hipSuccess;
+    return e != hipSuccess ? e : hipErrorIllegalState;
+  }
 };
+
+// the arena's guards before a run returns MSGPU_OK (DevArena::verify): a written guard is an error of the run
+template <class C> int stage_verify(C *c, DevArena &D) {
+  return D.verify(c->stream, c->err, sizeof(c->err)) == hipSuccess ? MSGPU_OK : MSGPU_E_HIP;
+}
 
 // rocPRIM's two calls on the arena's temporary buffer: call(null, bytes) answers the size, call(tmp, bytes) runs
 template <class Call> hipError_t stage_rocprim(DevArena &D, Call &&call) {

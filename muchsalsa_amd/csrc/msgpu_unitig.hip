@@ -903,6 +903,7 @@ int msgpu_ug_run_pair(msgpu_ugctx *c, const msgpu_ug_params *params, const msgpu
     (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
     return rc;
   }
+  if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
   S.n_lost_publications = c->sc.lost - lost0;
   S.wall_ms             = wall.ms();
   *out                  = res.release();
