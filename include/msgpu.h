@@ -1095,7 +1095,28 @@ void        msgpu_kf_result_free(msgpu_kf_result *r);
  *         cleaning is done, otherwise the next bubble phase runs.  Rules 5-8 then run on what is left; n_solid_trimmed is
  *         what cleaning leaves.
  *     (f) Not done: complex bubbles (overlapping variants whose branches fork again or merge at different nodes) and
- *         zero-length branches are left alone, and there is no erosion. */
+ *         zero-length branches are left alone, and there is no erosion.
+ * 10. the unitig graph as GFA 1, on request (msgpu_ug_set_graph).  It is off by default, and with it off every output, table,
+ *     count and kernel launch of the stage is what rules 1-9 make it.  The rule is defined on what rules 1-9 leave.
+ *     (a) Oriented unitigs.  Unitig i (its id is its rank, rule 6) exists as i+ and i-: i+ is the emitted chain and i- is its
+ *         mirror.  A unitig that is one self-complementary k-mer exists as i+ only.  first(x) and last(x) are the first and
+ *         the last oriented node of the oriented unitig x.
+ *     (b) Adjacencies.  For every oriented unitig x and every t in succ(last(x)) (rule 3, on the cleaned set) there is an
+ *         adjacency x -> y with first(y) = t.  Such a y always exists: an edge that rule 5 did not join ends at a node
+ *         without a joined predecessor.  The closing join of a cycle is the adjacency i+ -> i+.
+ *     (c) Mirror.  x -> y and y' -> x' are one link; ' flips the orientation.  As tuples (from id, from orientation, to id,
+ *         to orientation) with + < -, the smaller of the two is written.  Equal tuples (a hairpin i+ -> i-) are written
+ *         once.  A unitig that exists as i+ only has no i-, so an adjacency with such a unitig at either end has no mirror:
+ *         it is written as it is and is counted with the self-mirrored links.  (A reader of GFA takes the mirror of
+ *         x+ -> i+ to be i- -> x-, so the adjacency i+ -> x- needs a line of its own.)
+ *     (d) Order.  The links are written ascending by that tuple.
+ *     (e) Text, GFA 1.  The header "H\tVN:Z:1.0\n"; one line per unitig in id order,
+ *         "S\t<id>\t<sequence>\tLN:i:<length>\tKC:i:<coverage>\n", where sequence, length and coverage are exactly those of
+ *         the FASTA record (rule 6); one line per link, "L\t<from>\t<+|->\t<to>\t<+|->\t<k-1>M\n".  All unitigs are
+ *         written, with no length cut: links to short unitigs would otherwise dangle.
+ *     (f) Limits, each an error and never a fault.  Rule 7's bound of fewer than 2^31 solid k-mers makes the tuple fit 64 bits
+ *         (31 + 1 + 31 + 1); fewer than 2^32 links; device memory as in rule 7, MSGPU_E_NOMEM naming the sizes.  The counts
+ *         obey adjacencies = 2 links - self-mirrored links. */
 typedef struct msgpu_ugctx msgpu_ugctx; /* a device context of the stage */
 typedef struct msgpu_ug_result msgpu_ug_result;
 typedef struct msgpu_ug_params {
@@ -1174,8 +1195,28 @@ typedef struct msgpu_ug_bubble_round {
 int         msgpu_ug_set_bubbles(msgpu_ugctx *ctx, uint32_t bubble);
 int         msgpu_ug_result_bubbles(const msgpu_ug_result *r, msgpu_ug_bubble_stats *out, const msgpu_ug_bubble_round **rounds,
                                     uint64_t *n);
+/* Rule 10.  msgpu_ug_set_graph switches the unitig graph on (on != 0) or off (0, what a new context has) for every later
+ * msgpu_ug_run / msgpu_ug_run_pair on the context, until it is set again.  With it off msgpu_ug_result_links gives zeros and
+ * an empty table, and msgpu_ug_result_text has no MSGPU_UG_TEXT_GFA ("" and length 0, as for any unknown text). */
+typedef struct msgpu_ug_link { /* in rule 10 (d)'s order */
+  uint32_t from, to;           /* unitig ids */
+  uint8_t  from_rev, to_rev;   /* 0: +, 1: - */
+  uint16_t reserved;
+} msgpu_ug_link;
+typedef struct msgpu_ug_graph_stats {
+  uint64_t n_links;                    /* L lines written                                                                  */
+  uint64_t n_adjacencies;              /* oriented adjacencies seen, rule 10 (b): 2 n_links - n_self_mirror                 */
+  uint64_t n_self_mirror;              /* links that stand for themselves, rule 10 (c)                                     */
+  uint64_t n_dead_ends;                /* oriented unitig ends without a link                                              */
+  uint64_t gfa_bytes;                  /* bytes of the GFA text                                                            */
+  float    links_ms, sort_ms, text_ms; /* device, by events: the links; their sort; line lengths, offsets and the text     */
+  float    reserved;
+} msgpu_ug_graph_stats;
+int         msgpu_ug_set_graph(msgpu_ugctx *ctx, int on);
+int         msgpu_ug_result_links(const msgpu_ug_result *r, msgpu_ug_graph_stats *out, const msgpu_ug_link **links, uint64_t *n);
 #define MSGPU_UG_TEXT_ALL 0 /* every record */
 #define MSGPU_UG_TEXT_CUT 1 /* the records with length >= min_length */
+#define MSGPU_UG_TEXT_GFA 2 /* rule 10 (e); only after msgpu_ug_set_graph(ctx, 1) */
 const char *msgpu_ug_result_text(const msgpu_ug_result *r, int which, uint64_t *len);
 void        msgpu_ug_result_free(msgpu_ug_result *r);
 

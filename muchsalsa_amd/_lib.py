@@ -204,7 +204,16 @@ class UgBubbleRound(C.Structure):  # msgpu_ug_bubble_round
                 [("forks_ms", C.c_float), ("walk_ms", C.c_float)])
 
 
-UG_TEXT_ALL, UG_TEXT_CUT = 0, 1
+class UgLink(C.Structure):  # msgpu_ug_link
+    _fields_ = [("from", C.c_uint32), ("to", C.c_uint32), ("from_rev", C.c_uint8), ("to_rev", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class UgGraphStats(C.Structure):  # msgpu_ug_graph_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_links", "n_adjacencies", "n_self_mirror", "n_dead_ends", "gfa_bytes")] +
+                [(n, C.c_float) for n in ("links_ms", "sort_ms", "text_ms", "reserved")])
+
+
+UG_TEXT_ALL, UG_TEXT_CUT, UG_TEXT_GFA = 0, 1, 2
 
 
 class MapParams(C.Structure):  # msgpu_map_params
@@ -536,6 +545,8 @@ SYMBOLS = [
     ("msgpu_ug_set_bubbles", C.c_int, [C.c_void_p, C.c_uint32]),
     ("msgpu_ug_result_bubbles", C.c_int, [C.c_void_p, C.POINTER(UgBubbleStats), C.POINTER(C.POINTER(UgBubbleRound)),
                                           C.POINTER(C.c_uint64)]),
+    ("msgpu_ug_set_graph", C.c_int, [C.c_void_p, C.c_int]),
+    ("msgpu_ug_result_links", C.c_int, [C.c_void_p, C.POINTER(UgGraphStats), C.POINTER(C.POINTER(UgLink)), C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_free", None, [C.c_void_p]),
     ("msgpu_map_default_params", None, [C.POINTER(MapParams)]),

@@ -19,9 +19,14 @@
 //                and doubled again as a linear chain
 //   k_ug_heads   the heads that are emitted (rule 5's mirror choice), with their first k-mer; rocPRIM sorts them by it
 //   k_ug_cover   coverage: 64-bit atomics per unitig
-//   k_ug_write   every node writes one base at offset + distance + k - 1, the head writes its k bases and the '\n'
+//   k_ug_write   every node writes one base at offset + distance + k - 1, the head writes its k bases and the closing byte
+//   k_ug_links   rule 10 (on request): a quad of lanes per unitig end, lane c resolves the unitig behind the successor by
+//                base c (one look-up) and appends the link's 64-bit key unless the mirror link is the smaller; rocPRIM
+//                sorts the keys
+//   k_ug_link_*  rule 10: the link table and the byte length of every L line; behind a 64-bit scan a lane per link writes
+//                its line into the GFA text, where k_ug_write has put the segments' bases
 // No kernel loops over a unitig or over rounds: the longest loops are `limit` <= trim steps (k_ug_tips), `bubble` steps
-// (k_ug_bubbles) and k bases.
+// (k_ug_bubbles), k bases and the ten digits of an id.
 // Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 
@@ -378,9 +383,11 @@ __global__ __launch_bounds__(256) void k_ug_cover(uint64_t n2, const uint32_t *p
   if (u != UG_NONE) atomicAdd(&cover[u], static_cast<kf_ull>(count[i >> 1]));
 }
 
+// `close` is the byte behind a sequence: the '\n' of a FASTA record, the '\t' of a GFA segment line
 template <class K>
 __global__ __launch_bounds__(256) void k_ug_write(UgGraph<K> g, const uint32_t *ptr, const uint32_t *dist, const uint32_t *unit_of,
-                                                  const uint32_t *n_kmers, const uint64_t *seq_off, uint8_t *text, uint64_t cap) {
+                                                  const uint32_t *n_kmers, const uint64_t *seq_off, uint8_t *text, uint64_t cap,
+                                                  uint8_t close) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= 2ull * g.n) return;
   const uint32_t o = static_cast<uint32_t>(i), h = ptr[o];
@@ -397,7 +404,121 @@ __global__ __launch_bounds__(256) void k_ug_write(UgGraph<K> g, const uint32_t *
   }
   if (at + n_kmers[u] + g.k > cap) return;
   for (int j = 0; j < g.k; ++j) text[at + j] = "ACGT"[static_cast<uint32_t>(s >> (2 * (g.k - 1 - j))) & 3u];
-  text[at + n_kmers[u] + g.k - 1] = '\n';
+  text[at + n_kmers[u] + g.k - 1] = close;
+}
+
+// ---- rule 10: the links between the unitig ends
+
+// a link as a 64-bit key in rule 10 (d)'s order: from id (31 bits), from orientation, to id (31 bits), to orientation
+__device__ inline uint64_t ug_link_key(uint32_t from, uint32_t from_rev, uint32_t to, uint32_t to_rev) {
+  return (static_cast<uint64_t>(from) << 33) | (static_cast<uint64_t>(from_rev) << 32) | (static_cast<uint64_t>(to) << 1) | to_rev;
+}
+
+// Rule 10 (b), (c): a quad of lanes per unitig end (end e = 2 id + orientation; the - end of a unitig that is one
+// self-complementary k-mer does not exist), lane c asks for the successor by base c of the end's last node, resolves the
+// unitig that starts there and keeps the link unless its mirror is the smaller tuple.  sc: links (the cursor), adjacencies,
+// self-mirrored links, ends without a link, targets that are no unitig's first node -- five words side by side
+template <class K>
+__global__ __launch_bounds__(256) void k_ug_links(UgGraph<K> g, const uint8_t *adj, const uint32_t *ptr, const uint32_t *dist,
+                                                  const uint32_t *unit_of, const uint32_t *head, const uint32_t *n_kmers,
+                                                  const uint8_t *cyc, const uint32_t *cyc_last, uint32_t n_units, uint64_t *keys,
+                                                  uint64_t cap, kf_ull *sc) {
+  const uint64_t e = (static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x) >> 2;
+  const uint32_t c = threadIdx.x & 3;
+  bool           live = false, has = false, keep = false, own_mirror = false, lost = false;
+  uint32_t       out = 0;
+  uint64_t       own = 0;
+  if (e < 2ull * n_units) {
+    const uint32_t u = static_cast<uint32_t>(e >> 1), rev = static_cast<uint32_t>(e & 1), h = head[u], m = ptr[h ^ 1];
+    const bool     single = m == UG_NONE; // one self-complementary k-mer: + only
+    live = !(rev && single);
+    if (live) {
+      const uint32_t end = rev ? (h ^ 1) : ((cyc && cyc[h]) ? cyc_last[h] : (single ? h : (m ^ 1)));
+      out = ug_out(adj[end >> 1], end);
+      if (out & (1u << c)) {
+        has = true;
+        const uint32_t v = ug_node(g, ug_succ(g, ug_seq(g, end), c));
+        uint32_t       to = UG_NONE, to_rev = 0;
+        bool           to_single = false;
+        if (v != UG_NONE) { // (the byte said it is there)
+          const uint32_t p = ptr[v], q = ptr[v ^ 1];
+          if (p == v && unit_of[v] != UG_NONE) { // the head of an emitted chain
+            to        = unit_of[v];
+            to_single = q == UG_NONE;
+          } else if (q != UG_NONE && unit_of[q] != UG_NONE && dist[v ^ 1] + 1 == n_kmers[unit_of[q]]) { // the mirror of its last node
+            to     = unit_of[q];
+            to_rev = 1;
+          }
+        }
+        lost = to == UG_NONE;
+        if (!lost) {
+          own = ug_link_key(u, rev, to, to_rev);
+          const uint64_t mirror = ug_link_key(to, to_rev ^ 1, u, rev ^ 1);
+          own_mirror = single || to_single || own == mirror; // a unitig without a - has no mirror link
+          keep       = own_mirror || own < mirror;
+        }
+      }
+    }
+  }
+  const uint64_t slot = wave_append(keep, sc);
+  if (keep && slot < cap) keys[slot] = own;
+  wave_count(has, sc + 1);
+  wave_count(own_mirror, sc + 2);
+  wave_count(live && c == 0 && !out, sc + 3);
+  wave_count(lost, sc + 4);
+}
+
+__device__ inline uint32_t ug_digits(uint32_t x) { // decimal digits of x
+  uint32_t d = 1;
+  for (uint64_t p = 10; x >= p; p *= 10) ++d;
+  return d;
+}
+// x in d decimal digits, the last at text[end - 1]
+__device__ inline void ug_put_decimal(uint8_t *text, uint64_t end, uint32_t x, uint32_t d) {
+  for (uint32_t j = 0; j < d; ++j, x /= 10) text[end - 1 - j] = static_cast<uint8_t>('0' + x % 10);
+}
+
+// Rule 10 (e): the sorted keys as the link table and as the byte length of each L line, "L\t<from>\t<o>\t<to>\t<o>\t<k-1>M\n";
+// thread n writes the zero behind the lengths (stage_scan_total)
+__global__ __launch_bounds__(256) void k_ug_link_lens(const uint64_t *keys, uint64_t n, uint32_t overlap_digits, msgpu_ug_link *links,
+                                                      uint32_t *len) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    len[i] = 0;
+    return;
+  }
+  const uint64_t key = keys[i];
+  const uint32_t from = static_cast<uint32_t>(key >> 33), to = static_cast<uint32_t>(key >> 1) & 0x7fffffffu;
+  links[i] = msgpu_ug_link{from, to, static_cast<uint8_t>((key >> 32) & 1), static_cast<uint8_t>(key & 1), 0};
+  len[i]   = 10 + ug_digits(from) + ug_digits(to) + overlap_digits;
+}
+
+// a lane per link writes its line at base + off[i]
+__global__ __launch_bounds__(256) void k_ug_link_write(const msgpu_ug_link *links, const uint64_t *off, uint64_t n, uint32_t overlap,
+                                                       uint32_t overlap_digits, uint64_t base, uint8_t *text, uint64_t cap) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  const msgpu_ug_link l = links[i];
+  const uint32_t      df = ug_digits(l.from), dt = ug_digits(l.to);
+  uint64_t            at = base + off[i];
+  if (at + 10 + df + dt + overlap_digits > cap) return;
+  text[at]     = 'L';
+  text[at + 1] = '\t';
+  at += 2 + df;
+  ug_put_decimal(text, at, l.from, df);
+  text[at]     = '\t';
+  text[at + 1] = l.from_rev ? '-' : '+';
+  text[at + 2] = '\t';
+  at += 3 + dt;
+  ug_put_decimal(text, at, l.to, dt);
+  text[at]     = '\t';
+  text[at + 1] = l.to_rev ? '-' : '+';
+  text[at + 2] = '\t';
+  at += 3 + overlap_digits;
+  ug_put_decimal(text, at, overlap, overlap_digits);
+  text[at]     = 'M';
+  text[at + 1] = '\n';
 }
 
 } // namespace msgpu
@@ -409,6 +530,7 @@ using namespace msgpu;
 struct msgpu_ugctx : msgpu::StageCtx {
   ScalarBlock sc;
   uint32_t    bubble = 0; // rule 9's parameter (msgpu_ug_set_bubbles)
+  bool        graph = false; // rule 10 (msgpu_ug_set_graph)
   int         open() { return sc.create(); }
 };
 
@@ -421,8 +543,13 @@ struct msgpu_ug_result {
   char                        *all = nullptr; // page-locked
   uint64_t                     all_len = 0;
   std::string                  cut;
+  msgpu_ug_graph_stats         graph_stats{};
+  std::vector<msgpu_ug_link>   links;
+  char                        *gfa = nullptr; // page-locked; rule 10
+  uint64_t                     gfa_len = 0;
   ~msgpu_ug_result() {
     if (all) (void)hipHostFree(all);
+    if (gfa) (void)hipHostFree(gfa);
   }
 };
 
@@ -431,13 +558,17 @@ namespace {
 enum { UG_SC_REMOVED = SC_TOTAL_A, UG_SC_OPEN = SC_TOTAL_B, UG_SC_UNITS = SC_TOTAL_C,
        UG_SC_FORKS = SC_NBIG, UG_SC_BUBBLES = SC_NALIVE, UG_SC_BRANCHES = SC_IXFLAGS }; // (the last three lie side by side)
 static_assert(UG_SC_BUBBLES == UG_SC_FORKS + 1 && UG_SC_BRANCHES == UG_SC_FORKS + 2, "one memset zeroes the bubble rounds' counters");
+// rule 10: k_ug_links' five counters side by side; the bytes of the L lines come back in UG_SC_OPEN
+enum { UG_SC_LINKS = SC_BIGSTATS, UG_SC_ADJACENCIES, UG_SC_SELF_MIRROR, UG_SC_DEAD_ENDS, UG_SC_LOST_LINKS };
+static_assert(UG_SC_LOST_LINKS == SC_CLS && SC_CLS < SC_COUNT, "five free words of the scalar block");
+constexpr char UG_GFA_HEADER[] = "H\tVN:Z:1.0\n";
 
 inline hipError_t ug_zero_scalar(msgpu_ugctx *c, int slot) { return hipMemsetAsync(c->sc.d + slot, 0, 8, c->stream); }
 
 // everything behind the format check, for one key width
 template <class K>
 int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_dropped, const msgpu_ug_params &prm, uint32_t bubble,
-             uint64_t budget, msgpu_ug_result *res) {
+             bool graph, uint64_t budget, msgpu_ug_result *res) {
   msgpu_ug_stats &S = res->stats;
   hipStream_t     st = c->stream;
   StageClock      clock(st);
@@ -773,13 +904,131 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
   }
   S.host_ms += host0.ms();
 
+  // ---- rule 10 (on request): the links of the unitig ends, their sort, the GFA text
+  msgpu_ug_graph_stats &G = res->graph_stats;
+  std::string           gfa_fix; // what the host writes of every S line: "S\t<id>\t" and "LN:i:<length>\tKC:i:<coverage>\n"
+  std::vector<uint32_t> gfa_fix_len;
+  std::vector<uint64_t> gfa_off; // of every sequence in the GFA text
+  if (graph) {
+    kf_ull        *sc_d = reinterpret_cast<kf_ull *>(c->sc.d);
+    const uint64_t cap = 8ull * U; // 2 U ends, 4 successors each
+    STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
+    if (cap * 8 > free_b) {
+      snprintf(c->err, sizeof(c->err), "%u unitigs need %llu bytes for the keys of their links; %zu bytes of device memory are free", U,
+               static_cast<kf_ull>(cap * 8), free_b);
+      return MSGPU_E_NOMEM;
+    }
+    uint64_t *d_key[2];
+    STAGE_HIP(c, D.get(&d_key[0], cap));
+    STAGE_HIP(c, hipMemsetAsync(c->sc.d + UG_SC_LINKS, 0, 5 * 8, st));
+    STAGE_HIP(c, clock.begin(&G.links_ms));
+    if (U)
+      hipLaunchKernelGGL(k_ug_links<K>, dim3(grid256(cap)), dim3(256), 0, st, g, d_adj, d_p, d_d, d_unit_of, d_head[1], d_nk, d_cyc,
+                         d_cyc_last, U, d_key[0], cap, sc_d + UG_SC_LINKS);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
+    if (rc != MSGPU_OK) return rc;
+    const uint64_t L = c->sc.h[UG_SC_LINKS];
+    G.n_links       = L;
+    G.n_adjacencies = c->sc.h[UG_SC_ADJACENCIES];
+    G.n_self_mirror = c->sc.h[UG_SC_SELF_MIRROR];
+    G.n_dead_ends   = c->sc.h[UG_SC_DEAD_ENDS];
+    if (c->sc.h[UG_SC_LOST_LINKS] || L > cap) { // rule 10 (b): never seen
+      snprintf(c->err, sizeof(c->err), "%llu of %llu adjacencies end at no unitig's first node; %llu links of %u unitigs",
+               static_cast<kf_ull>(c->sc.h[UG_SC_LOST_LINKS]), static_cast<kf_ull>(G.n_adjacencies), static_cast<kf_ull>(L), U);
+      return MSGPU_E_STATE;
+    }
+    if (L >= (1ull << 32)) {
+      snprintf(c->err, sizeof(c->err), "%llu links; the limit is 2^32 - 1", static_cast<kf_ull>(L));
+      return MSGPU_E_ARG;
+    }
+    // the host's part of the S lines, and where the sequences go
+    const StageTimer host_s;
+    uint64_t         seg_bytes = 0;
+    try {
+      gfa_fix_len.resize(2ull * U);
+      gfa_off.resize(U);
+      res->links.resize(L);
+      for (uint32_t u = 0; u < U; ++u) {
+        const msgpu_ug_unitig &T = res->units[u];
+        gfa_fix_len[2 * u] = static_cast<uint32_t>(snprintf(buf, sizeof(buf), "S\t%u\t", u));
+        gfa_fix.append(buf, gfa_fix_len[2 * u]);
+        gfa_fix_len[2 * u + 1] =
+            static_cast<uint32_t>(snprintf(buf, sizeof(buf), "LN:i:%llu\tKC:i:%llu\n", static_cast<kf_ull>(T.length), static_cast<kf_ull>(T.coverage)));
+        gfa_fix.append(buf, gfa_fix_len[2 * u + 1]);
+        gfa_off[u] = sizeof(UG_GFA_HEADER) - 1 + seg_bytes + gfa_fix_len[2 * u];
+        seg_bytes += gfa_fix_len[2 * u] + T.length + 1 + gfa_fix_len[2 * u + 1];
+      }
+    } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+    S.host_ms += host_s.ms();
+    const uint64_t link_base = sizeof(UG_GFA_HEADER) - 1 + seg_bytes;
+    uint32_t       overlap_digits = 1;
+    for (int x = k - 1; x >= 10; x /= 10) ++overlap_digits;
+    // the sorted keys, the table, a length and an offset per link, the segments; the L lines' bytes are not known yet
+    STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
+    const uint64_t link_bytes = L * (8 + sizeof(msgpu_ug_link) + 4 + 8) + 12 + U * 8ull + link_base;
+    if (link_bytes + L * 10 > free_b) {
+      snprintf(c->err, sizeof(c->err), "%llu links and %llu bytes of segment lines need more than %llu bytes for the graph's text; %zu "
+               "bytes of device memory are free", static_cast<kf_ull>(L), static_cast<kf_ull>(link_base), static_cast<kf_ull>(link_bytes + L * 10), free_b);
+      return MSGPU_E_NOMEM;
+    }
+    msgpu_ug_link *d_link;
+    uint32_t      *d_len;
+    uint64_t      *d_off, *d_gfa_off;
+    uint8_t       *d_gfa;
+    STAGE_HIP(c, D.get(&d_key[1], L));
+    STAGE_HIP(c, D.get(&d_link, L));
+    STAGE_HIP(c, D.get(&d_len, L + 1));
+    STAGE_HIP(c, D.get(&d_off, L + 1));
+    STAGE_HIP(c, D.get(&d_gfa_off, U));
+    STAGE_HIP(c, clock.begin(&G.sort_ms));
+    if (L)
+      STAGE_HIP(c, stage_rocprim(D, [&](void *t, size_t &b) {
+                  return rocprim::radix_sort_keys(t, b, d_key[0], d_key[1], static_cast<unsigned int>(L), 0, 64, st);
+                }));
+    STAGE_HIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(&G.text_ms));
+    hipLaunchKernelGGL(k_ug_link_lens, dim3(grid256(L + 1)), dim3(256), 0, st, d_key[1], L, overlap_digits, d_link, d_len);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, stage_scan_total(D, st, d_len, d_off, L, c->sc, UG_SC_OPEN));
+    STAGE_HIP(c, clock.end());
+    rc = c->sc.read(c);
+    if (rc != MSGPU_OK) return rc;
+    const uint64_t gfa_total = link_base + c->sc.h[UG_SC_OPEN];
+    if (c->sc.h[UG_SC_OPEN] < L * 12 || c->sc.h[UG_SC_OPEN] > L * 32) {
+      snprintf(c->err, sizeof(c->err), "%llu links in %llu bytes of L lines", static_cast<kf_ull>(L), static_cast<kf_ull>(c->sc.h[UG_SC_OPEN]));
+      return MSGPU_E_STATE;
+    }
+    STAGE_HIP(c, D.get(&d_gfa, gfa_total));
+    STAGE_HIP(c, clock.begin(&G.text_ms));
+    if (U) {
+      STAGE_HIP(c, hipMemcpyAsync(d_gfa_off, gfa_off.data(), U * 8ull, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_ug_write<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_p, d_d, d_unit_of, d_nk, d_gfa_off, d_gfa, gfa_total,
+                         static_cast<uint8_t>('\t'));
+    }
+    if (L)
+      hipLaunchKernelGGL(k_ug_link_write, dim3(grid256(L)), dim3(256), 0, st, d_link, d_off, L, static_cast<uint32_t>(k - 1),
+                         overlap_digits, link_base, d_gfa, gfa_total);
+    STAGE_HIP(c, hipGetLastError());
+    STAGE_HIP(c, clock.end());
+    STAGE_HIP(c, clock.begin(&S.copy_ms));
+    STAGE_HIP(c, hipHostMalloc(reinterpret_cast<void **>(&res->gfa), gfa_total, hipHostMallocDefault));
+    STAGE_HIP(c, hipMemcpyAsync(res->gfa, d_gfa, gfa_total, hipMemcpyDeviceToHost, st));
+    if (L) STAGE_HIP(c, hipMemcpyAsync(res->links.data(), d_link, L * sizeof(msgpu_ug_link), hipMemcpyDeviceToHost, st));
+    STAGE_HIP(c, clock.end());
+    res->gfa_len = gfa_total;
+    G.gfa_bytes  = gfa_total;
+  }
+
   // ---- the bases
   uint8_t *d_text;
   STAGE_HIP(c, D.get(&d_text, total));
   STAGE_HIP(c, clock.begin(&S.write_ms));
   if (U) {
     STAGE_HIP(c, hipMemcpyAsync(d_seq_off, seq_off.data(), U * 8ull, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ug_write<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_p, d_d, d_unit_of, d_nk, d_seq_off, d_text, total);
+    hipLaunchKernelGGL(k_ug_write<K>, dim3(grid256(n2)), dim3(256), 0, st, g, d_p, d_d, d_unit_of, d_nk, d_seq_off, d_text, total,
+                       static_cast<uint8_t>('\n'));
     STAGE_HIP(c, hipGetLastError());
   }
   STAGE_HIP(c, clock.end());
@@ -812,6 +1061,16 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
     res->rounds.assign(rounds.begin(), rounds.end());
     res->bubble_rounds.assign(bubble_rounds.begin(), bubble_rounds.end());
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
+  if (graph) { // the header and the host's part of the S lines into the GFA text
+    memcpy(res->gfa, UG_GFA_HEADER, sizeof(UG_GFA_HEADER) - 1);
+    uint64_t at = 0;
+    for (uint32_t u = 0; u < U; ++u) {
+      memcpy(res->gfa + gfa_off[u] - gfa_fix_len[2 * u], gfa_fix.data() + at, gfa_fix_len[2 * u]);
+      at += gfa_fix_len[2 * u];
+      memcpy(res->gfa + gfa_off[u] + res->units[u].length + 1, gfa_fix.data() + at, gfa_fix_len[2 * u + 1]);
+      at += gfa_fix_len[2 * u + 1];
+    }
+  }
   for (const msgpu_ug_round &R : res->rounds) {
     S.tips_ms += R.tips_ms;
     S.adjacency_ms += R.adjacency_ms;
@@ -897,8 +1156,8 @@ int msgpu_ug_run_pair(msgpu_ugctx *c, const msgpu_ug_params *params, const msgpu
     if (n_pairs) STAGE_HIP(c, hipMemcpyAsync(d_dropped, dropped, n_pairs, hipMemcpyHostToDevice, c->stream));
     STAGE_HIP(c, hipStreamSynchronize(c->stream)); // (the caller's array may go when the call returns)
   }
-  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, c->bubble, budget_bytes, res.get())
-                   : ug_stage<kf_u128>(c, D, F, d_dropped, prm, c->bubble, budget_bytes, res.get());
+  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get())
+                   : ug_stage<kf_u128>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get());
   if (rc != MSGPU_OK) {
     (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
     return rc;
@@ -947,6 +1206,20 @@ int msgpu_ug_set_bubbles(msgpu_ugctx *c, uint32_t bubble) {
   return MSGPU_OK;
 }
 
+int msgpu_ug_set_graph(msgpu_ugctx *c, int on) {
+  if (!c) return MSGPU_E_ARG;
+  c->graph = on != 0;
+  return MSGPU_OK;
+}
+
+int msgpu_ug_result_links(const msgpu_ug_result *r, msgpu_ug_graph_stats *out, const msgpu_ug_link **links, uint64_t *n) {
+  if (!r || !out || !links || !n) return MSGPU_E_ARG;
+  *out   = r->graph_stats;
+  *links = r->links.data();
+  *n     = r->links.size();
+  return MSGPU_OK;
+}
+
 int msgpu_ug_result_stats(const msgpu_ug_result *r, msgpu_ug_stats *out) {
   if (!r || !out) return MSGPU_E_ARG;
   *out = r->stats;
@@ -985,6 +1258,10 @@ const char *msgpu_ug_result_text(const msgpu_ug_result *r, int which, uint64_t *
   if (which == MSGPU_UG_TEXT_CUT) {
     if (len) *len = r->cut.size();
     return r->cut.data();
+  }
+  if (which == MSGPU_UG_TEXT_GFA && r->gfa) {
+    if (len) *len = r->gfa_len;
+    return r->gfa;
   }
   return "";
 }

@@ -26,6 +26,7 @@ Files under ``outdir``, with the script's names (BASE = the long-read file's bas
 ``01_unitigs.to_<BASE>.paf``, ``01_contigs_corrected.to_<BASE>.paf``, ``02_<BASE>.scrubbed.fa``,
 ``02_contigs_corrected.to_<BASE>.scrubbed.paf``, ``03.assembly.unpolished.fa``.  What the script leaves in its temporary
 folder goes under ``outdir/tmp/``: ``unitigs_corrected.fa``, ``<BASE>.ava.paf`` and the three ``temp_1.*`` files.
+``run(..., gfa=True)`` adds ``ABYSS/<name>-unitigs.gfa``, the unitig graph (what ``abyss-pe graph=gfa`` leaves there).
 
 Between stages whose hand-off is one of those files -- the pipeline's deliverables and its checkpoints -- the file stays the
 hand-off.  An error in any stage stops the run: HybridError, the stage's name in front of the stage's own message; the
@@ -39,7 +40,7 @@ import time
 
 from . import _lib
 
-__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "output_names", "link_input", "run", "main"]
+__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "gfa_name", "output_names", "link_input", "run", "main"]
 
 MIN_LENGTH = 500  # pipeline.sh:29
 POLISHED_NAME = "04.assembly.polished.fa"  # written only by run(..., polish=N): not one of output_names
@@ -73,6 +74,11 @@ def output_names(name, nanopore):
             "align": os.path.join("tmp", "temp_1.align.paf")}
 
 
+def gfa_name(name):
+    """the unitig graph beside the unitigs, written only by run(..., gfa=True): not one of output_names"""
+    return os.path.join("ABYSS", "%s-unitigs.gfa" % name)
+
+
 def link_input(path, directory, prefix="00_"):
     """pipeline.sh's make_link (91-99): a relative symbolic link to ``path`` in ``directory``, replacing one that exists"""
     link = os.path.join(directory, prefix + os.path.basename(path))
@@ -84,7 +90,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None, extend=None, min_mapq=None):
+        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -96,7 +102,9 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     then runs with cigar = 1 and extend = N, and so does every mapping of the polish stage; every file written before step 9's
     PAF is the same.  ``min_mapq`` (None: off) = N goes to the polish stage only (muchsalsa_amd.polish's rule 2 in ranked form: its
     mappings run with the mapper's rule 12 on, and a read votes with its primaries of mapping quality N or more); the four
-    mappings of the pipeline keep ranking off: their consumers read columns 1 to 11 and want every chain, as with ``-P``."""
+    mappings of the pipeline keep ranking off: their consumers read columns 1 to 11 and want every chain, as with ``-P``.
+    ``gfa`` = True: the unitig assembly also writes its graph (muchsalsa_amd.unitigs' rule 10) to ``ABYSS/<name>-unitigs.gfa``
+    (gfa_name), named by ``files["gfa"]``; every other file is the same."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -108,6 +116,7 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     for d in (out, os.path.join(out, "ABYSS"), os.path.join(out, "tmp")):
         os.makedirs(d, exist_ok=True)
     reads = link_input(nanopore, out)  # pipeline.sh:134: every step reads the link
+    gfa_path = os.path.join(out, gfa_name(name)) if gfa else None
     result = {}
 
     def stage(key, fn, *args, **kw):
@@ -125,7 +134,7 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     try:
         stage("filter", kmer_filter.run, int(k_filter), None, None, files["report"], None, None, pair=pair, tables=tables)
         stage("unitigs", unitigs.run, int(k_assembly), None, None, files["unitigs"], files["unitigs_cut"], pair=pair,
-              dropped=tables["verdict"], min_length=MIN_LENGTH, bubble=bubble)
+              dropped=tables["verdict"], min_length=MIN_LENGTH, bubble=bubble, gfa=gfa_path)
     finally:
         pair.__exit__(None, None, None)
     index = mapper.Index(reads, device=device)
@@ -145,6 +154,8 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
           threads=int(cores), device=device)
     shutil.copyfile(files["target"], files["assembly"])  # pipeline.sh:181
     result["files"] = dict(files, link=reads)
+    if gfa:
+        result["files"]["gfa"] = gfa_path
     if polish:
         from . import polish as polisher
         result["files"]["polished"] = os.path.join(out, POLISHED_NAME)

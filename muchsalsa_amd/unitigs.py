@@ -3,9 +3,10 @@ at MINLENGTH behind it write in the reference pipeline -- ``NAME-unitigs.fa`` an
 FASTQ files (the k-mer filter's outputs) alone.
 
     python -m muchsalsa_amd.unitigs <k> <in_1.fq> <in_2.fq> <out_all.fa> <out_cut.fa>
-            [--min-count N] [--trim N] [--min-length N] [--budget-mb N] [--bubble N]
+            [--min-count N] [--trim N] [--min-length N] [--budget-mb N] [--bubble N] [--gfa F]
 
-prints one JSON line of counts and seconds.  ABySS is not needed, and it is not part of the reference tree: the stage is
+prints one JSON line of counts and seconds; with ``--gfa F`` the unitig graph is written to F as GFA 1 (rule 10), where
+``abyss-pe graph=gfa`` leaves its adjacency graph beside the FASTA.  ABySS is not needed, and it is not part of the reference tree: the stage is
 defined by the rules below and checked, without tolerance, against the tests' restatement in plain Python
 (tests/ug_oracle.py), not against ABySS.  The rules (include/msgpu.h, "short-read unitig assembly"); parameters k (2..64),
 min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500, the pipeline's
@@ -64,6 +65,27 @@ MINLENGTH), bubble (0..4096, default 0 = off: rule 9):
        what cleaning leaves.
    (f) Not done: complex bubbles (overlapping variants whose branches fork again or merge at different nodes) and
        zero-length branches are left alone, and there is no erosion.
+10. The unitig graph as GFA 1, on request (``gfa``; msgpu_ug_set_graph).  It is off by default, and with it off every output,
+    table, count and kernel launch of the stage is what rules 1-9 make it.  The rule is defined on what rules 1-9 leave.
+    (a) Oriented unitigs.  Unitig i (its id is its rank, rule 6) exists as i+ and i-: i+ is the emitted chain and i- is its
+        mirror.  A unitig that is one self-complementary k-mer exists as i+ only.  first(x) and last(x) are the first and
+        the last oriented node of the oriented unitig x.
+    (b) Adjacencies.  For every oriented unitig x and every t in succ(last(x)) (rule 3, on the cleaned set) there is an
+        adjacency x -> y with first(y) = t.  Such a y always exists: an edge that rule 5 did not join ends at a node
+        without a joined predecessor.  The closing join of a cycle is the adjacency i+ -> i+.
+    (c) Mirror.  x -> y and y' -> x' are one link; ' flips the orientation.  As tuples (from id, from orientation, to id,
+        to orientation) with + < -, the smaller of the two is written.  Equal tuples (a hairpin i+ -> i-) are written
+        once.  A unitig that exists as i+ only has no i-, so an adjacency with such a unitig at either end has no mirror:
+        it is written as it is and is counted with the self-mirrored links.  (A reader of GFA takes the mirror of
+        x+ -> i+ to be i- -> x-, so the adjacency i+ -> x- needs a line of its own.)
+    (d) Order.  The links are written ascending by that tuple.
+    (e) Text, GFA 1.  The header "H\\tVN:Z:1.0\\n"; one line per unitig in id order,
+        "S\\t<id>\\t<sequence>\\tLN:i:<length>\\tKC:i:<coverage>\\n", where sequence, length and coverage are exactly those of
+        the FASTA record (rule 6); one line per link, "L\\t<from>\\t<+|->\\t<to>\\t<+|->\\t<k-1>M\\n".  All unitigs are
+        written, with no length cut: links to short unitigs would otherwise dangle.
+    (f) Limits, each an error and never a fault.  Rule 7's bound of fewer than 2^31 solid k-mers makes the tuple fit 64 bits
+        (31 + 1 + 31 + 1); fewer than 2^32 links; device memory as in rule 7, MSGPU_E_NOMEM naming the sizes.  The counts
+        obey adjacencies = 2 links - self-mirrored links.
 
 Known differences from ``abyss-pe unitigs``, none of which could be checked against the program (it is not installed where
 this project is built):
@@ -102,7 +124,7 @@ class UnitigError(StageError):
 
 
 def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_length=500, budget_mb=None, tables=None,
-        timings=None, pair=None, dropped=None, bubble=None):
+        timings=None, pair=None, dropped=None, bubble=None, gfa=None):
     """The whole stage: writes ``out_all`` and ``out_cut``; returns the counts.  ``in_2`` may be None.  ``trim`` None: k.
     With ``pair`` (an entered kmer_filter.Pair) the stage runs on the resident files on the pair's device and ``in_1`` /
     ``in_2`` / ``device`` are not read; ``dropped`` (bytes or a uint8 array, one per pair, 1 = dropped) is the mask.
@@ -113,7 +135,9 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
     ``bubbles``, ``bubble_rounds`` [[tip rounds before it, bubbles, k-mers removed]], ``bubble_kmers`` and ``bubble_max_forks`` (the
     largest fork list of a round), ``tables`` receives
     ``bubble_rounds`` [(tip rounds before it, forks, bubbles, branches removed, k-mers removed)] and ``timings``
-    ``bubble_forks`` / ``bubble_walk`` / ``bubble_adjacency`` (seconds)."""
+    ``bubble_forks`` / ``bubble_walk`` / ``bubble_adjacency`` (seconds).  ``gfa`` (None: off) is a path: rule 10's text is
+    written there, the dict then holds ``links``, ``link_self_mirror``, ``dead_ends`` and ``gfa_bytes``, ``tables`` receives
+    ``links`` [(from, from_rev, to, to_rev)] and ``timings`` ``graph_links`` / ``graph_sort`` / ``graph_text`` (seconds)."""
     L = _lib.lib()
     t0 = time.perf_counter()
     if dropped is not None and pair is None:
@@ -130,6 +154,8 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
             raise UnitigError(_lib.E_ARG, detail="trim = %d" % int(trim))
         if bubble:
             stage.check(L.msgpu_ug_set_bubbles(stage.ctx, bubble))
+        if gfa is not None:
+            stage.check(L.msgpu_ug_set_graph(stage.ctx, 1))
         with (stage.run(C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget) if pair is None
               else stage.run(C.byref(prm), pair.handle, mask, 0 if mask is None else len(mask), 0, budget, fn="run_pair")) as res:
             st = _lib.UgStats()
@@ -149,8 +175,14 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
                 tables["bubble_rounds"] = bubble_rounds
                 tables["unitigs"] = [(int(u.length), int(u.coverage), (int(u.first_hi) << 64) | int(u.first_lo), int(u.offset),
                                       int(u.cyclic)) for u in (up[i] for i in range(n.value))]
+            gs, lp = _lib.UgGraphStats(), C.POINTER(_lib.UgLink)()
+            L.msgpu_ug_result_links(res, C.byref(gs), C.byref(lp), C.byref(n))
+            if tables is not None and gfa is not None:
+                tables["links"] = [(int(getattr(l, "from")), int(l.from_rev), int(l.to), int(l.to_rev))
+                                   for l in (lp[i] for i in range(n.value))]
             t1 = time.perf_counter()
-            for path, which in ((out_all, _lib.UG_TEXT_ALL), (out_cut, _lib.UG_TEXT_CUT)):
+            texts = ((out_all, _lib.UG_TEXT_ALL), (out_cut, _lib.UG_TEXT_CUT))
+            for path, which in texts if gfa is None else texts + ((gfa, _lib.UG_TEXT_GFA),):
                 with open(path, "wb") as h:
                     h.write(text_view(L.msgpu_ug_result_text, res, which))
             t_write = time.perf_counter() - t1
@@ -158,8 +190,12 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
         timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.UgStats._fields_ if name.endswith("_ms")})
         timings["stage_wall"] = timings.pop("wall")
         timings.update({"bubble_" + name[:-3]: getattr(bs, name) / 1e3 for name in ("forks_ms", "walk_ms", "adjacency_ms")})
+        if gfa is not None:
+            timings.update({"graph_" + name[:-3]: getattr(gs, name) / 1e3 for name in ("links_ms", "sort_ms", "text_ms")})
         timings.update({"files": t_write, "total": time.perf_counter() - t0, "round_seconds": round_s})
-    return {"k": int(st.k), "min_count": int(st.min_count), "trim": int(st.trim), "min_length": int(st.min_length),
+    graph = {} if gfa is None else {"links": int(gs.n_links), "link_self_mirror": int(gs.n_self_mirror),
+                                    "dead_ends": int(gs.n_dead_ends), "gfa_bytes": int(gs.gfa_bytes)}
+    return dict({"k": int(st.k), "min_count": int(st.min_count), "trim": int(st.trim), "min_length": int(st.min_length),
             "records": [int(x) for x in st.n_records], "windows": int(st.n_windows), "distinct": int(st.n_distinct),
             "solid": int(st.n_solid), "solid_after": int(st.n_solid_trimmed), "tip_rounds": int(st.n_tip_rounds),
             "rounds": [list(r) for r in rounds], "unitigs": int(st.n_unitigs), "kept": int(st.n_unitigs_kept),
@@ -168,18 +204,19 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
             "lost_publications": int(st.n_lost_publications), "bytes_in": [int(x) for x in st.bytes_in],
             "bytes_out": [int(x) for x in st.bytes_out], "bubble": int(bs.bubble), "bubbles": int(bs.n_bubbles),
             "bubble_rounds": [[r[0], r[2], r[4]] for r in bubble_rounds], "bubble_kmers": int(bs.n_kmers_removed),
-            "bubble_max_forks": int(bs.max_forks)}
+            "bubble_max_forks": int(bs.max_forks)}, **graph)
 
 
 def main(argv):
     args = list(argv)
-    opts = {"--min-count": 2, "--trim": None, "--min-length": 500, "--budget-mb": None, "--bubble": 0}
+    opts = {"--min-count": 2, "--trim": None, "--min-length": 500, "--budget-mb": None, "--bubble": 0, "--gfa": None}
     ok = True
     for name in opts:
         if name in args:
             i = args.index(name)
             try:
-                opts[name] = (float if name == "--budget-mb" else int)(args[i + 1])
+                opts[name] = (float if name == "--budget-mb" else str if name == "--gfa" else int)(args[i + 1])
+                ok = ok and not (name == "--gfa" and (not opts[name] or opts[name].startswith("--")))
             except (IndexError, ValueError):
                 ok = False
             del args[i:i + 2]
@@ -195,7 +232,8 @@ def main(argv):
         return 2
     timings = {}
     out = run(k, args[1], args[2], args[3], args[4], min_count=opts["--min-count"], trim=opts["--trim"],
-              min_length=opts["--min-length"], budget_mb=opts["--budget-mb"], timings=timings, bubble=opts["--bubble"])
+              min_length=opts["--min-length"], budget_mb=opts["--budget-mb"], timings=timings, bubble=opts["--bubble"],
+              gfa=opts["--gfa"])
     rs = timings.pop("round_seconds")
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     out["round_seconds"] = [[round(a, 5), round(b, 5)] for a, b in rs]

@@ -6,11 +6,11 @@ makes the input error-free and repeat-free, so that it is one chain as long as t
 tests' plain-Python restatement (tests/ug_oracle.py -- a restatement, NOT ABySS) is timed on a smaller shape
 (--oracle-genome; 0 = not at all) as orientation, not as a claim.  --diploid takes the input from synth.diploid_workload
 instead (two haplotypes with a variant every 400 bases, --coverage / 2 each, one file), --bubble N runs the stage with rule 9
-(bubble popping) at N and reports its fork, walk and neighbour-byte times and its rounds.  Prints one JSON object; --out also
-writes it to a file.
+(bubble popping) at N and reports its fork, walk and neighbour-byte times and its rounds, --gfa with rule 10 (the unitig
+graph) and reports its links, sort and text times.  Prints one JSON object; --out also writes it to a file.
 
     python tools/unitigs_timing.py [--genome 1000000 --coverage 40 --read-len 150 -k 31] [--clean] [--diploid] [--bubble N]
-                                   [--repeat 3] [--out F]
+                                   [--gfa] [--repeat 3] [--out F]
 """
 import argparse
 import json
@@ -42,6 +42,7 @@ def main():
     ap.add_argument("--clean", action="store_true", help="no repeats, no errors, no N: one chain as long as the genome")
     ap.add_argument("--diploid", action="store_true", help="two haplotypes with a variant every 400 bases (synth.diploid_workload)")
     ap.add_argument("--bubble", type=int, default=0, help="rule 9's parameter (0: off)")
+    ap.add_argument("--gfa", action="store_true", help="rule 10: the unitig graph is written as well")
     ap.add_argument("--repeat", type=int, default=3, help="stage runs (fresh process each); the fastest is reported")
     ap.add_argument("--oracle-genome", type=int, default=0, help="genome of the shape the restatement is timed on")
     ap.add_argument("--timeout", type=int, default=600)
@@ -68,7 +69,7 @@ def main():
         for i in range(a.repeat):
             t = time.perf_counter()
             r = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, "-m", "muchsalsa_amd.unitigs", str(a.k)] +
-                               paths + ["--bubble", str(a.bubble)], cwd=ROOT, env=env, capture_output=True, text=True)
+                               paths + ["--bubble", str(a.bubble)] + (["--gfa", os.path.join(d, "graph.gfa")] if a.gfa else []), cwd=ROOT, env=env, capture_output=True, text=True)
             if r.returncode != 0:
                 res["error"] = {"run": i, "rc": r.returncode, "stderr": r.stderr[-2000:]}
                 break
@@ -88,6 +89,7 @@ def main():
             "rounds": [{"limit": l, "removed": n, "tips_s": t, "adjacency_s": b}
                        for (l, n), (t, b) in zip(best["rounds"], best["round_seconds"])],
             "bubble_steps_s": {x: s[x] for x in ("bubble_forks", "bubble_walk", "bubble_adjacency")},
+            "graph_steps_s": {x: s[x] for x in ("graph_links", "graph_sort", "graph_text") if x in s},
             "device_steps_s": round(dev, 5), "count_step_s": round(count, 5),
             "count_share_of_device_steps": round(count / dev, 4) if dev else None,
             "doubling_s_per_round": round(s["doubling"] / best["doubling_rounds"], 6) if best["doubling_rounds"] else None,
