@@ -636,6 +636,26 @@ def diploid_workload(genome=6000, every=400, coverage=15, read_len=100, seed=7, 
     return rec.tobytes(), None, {"haplotypes": (a.tobytes(), b.tobytes()), "variants": variants}
 
 
+def _tile(seq, L, step=10):
+    """the reads of L bases at every ``step``-th position of seq, and the one that ends with it"""
+    starts = list(range(0, len(seq) - L + 1, step))
+    if starts[-1] != len(seq) - L:
+        starts.append(len(seq) - L)
+    return [seq[s:s + L] for s in starts]
+
+
+def _snp(seq, at, step=1):
+    return seq[:at] + bytes([_other_base(seq[at], step)]) + seq[at + 1:]
+
+
+def _bubble_case(haps, extra, L, **meta):
+    """-> (FASTQ file, None, meta and ``haplotypes``): every haplotype (sequence, multiplicity) tiled into reads of L bases,
+    each read written ``multiplicity`` times, then the reads of ``extra``"""
+    reads = [r for seq, m in haps for r in _tile(seq, L) for _ in range(m)] + list(extra)
+    fq = b"".join(b"@b%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads))
+    return fq, None, dict({"haplotypes": haps}, **meta)
+
+
 def unitig_bubble_cases(k=21):
     """Hand-made inputs of rule 9 (bubble popping) of the unitig assembly: name -> (FASTQ file, None, what the case is made
     of: ``haplotypes`` [(sequence, multiplicity)], ``bubble`` and ``trim`` to run it with).  A is a random sequence of 400
@@ -644,7 +664,9 @@ def unitig_bubble_cases(k=21):
     edge        A x 3, A with one substitution at p x 2: one bubble of two branches of k k-mers
     indel_long  A x 3, A without its bases p, p + 1 x 2: the longer branch is the majority
     indel_short A x 2, the deletion x 2 and the deletion's read over the site once more: the shorter branch has the greater
-                mean and the smaller sum
+                mean and the smaller sum.  Above k = 21 its haplotypes are tiled into reads of k + 100 bases: the one extra
+                read adds 1 to each of the shorter branch's k - 1 k-mers, so its sum stays below that of the longer branch's
+                k + 1 only where a k-mer is counted more than (k - 1) / 2 times, and 80-base reads count a 33-mer 10 times
     tie         A x 2, the substitution x 2: equal counts, the smaller base wins
     three_way   three bases at p, x 3, x 2, x 1: one bubble of three branches
     nested      A x 3, B = A with substitutions at p and p + 12 x 2, B with a further one at p + 6 x 1: a bubble inside a
@@ -654,19 +676,10 @@ def unitig_bubble_cases(k=21):
     palindrome  P + A + rc(P) x 3 beside P + C + rc(P) x 2 for 150 bases P: fork and merge are one k-mer
     alternate   A x 3, A with a substitution at k + 9 x 2, and 100 random bases followed by A[k + 16 : k + 76] x 2: a junction
                 just behind the bubble, so the start of A is a tip once the bubble is gone; trim = bubble = 3 k"""
-    def tile(seq, step=10, L=80):
-        starts = list(range(0, len(seq) - L + 1, step))
-        if starts[-1] != len(seq) - L:
-            starts.append(len(seq) - L)
-        return [seq[s:s + L] for s in starts]
+    snp = _snp
 
-    def snp(seq, at, step=1):
-        return seq[:at] + bytes([_other_base(seq[at], step)]) + seq[at + 1:]
-
-    def case(haps, extra=(), **kw):
-        reads = [r for seq, m in haps for r in tile(seq) for _ in range(m)] + list(extra)
-        fq = b"".join(b"@b%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads))
-        return fq, None, dict({"haplotypes": haps, "bubble": 3 * k, "trim": k}, **kw)
+    def case(haps, extra=(), L=80, **kw):
+        return _bubble_case(haps, extra, L, **dict({"bubble": 3 * k, "trim": k}, **kw))
 
     A, p = genome_bases(400, 401).tobytes(), 200
     dele = A[:p] + A[p + 2:]
@@ -675,13 +688,191 @@ def unitig_bubble_cases(k=21):
     R = genome_bases(100, 403).tobytes()
     return {"edge": case([(A, 3), (snp(A, p), 2)]),
             "indel_long": case([(A, 3), (dele, 2)]),
-            "indel_short": case([(A, 2), (dele, 2)], extra=[dele[p - 40:p + 40]]),
+            "indel_short": case([(A, 2), (dele, 2)], extra=[dele[p - 40:p + 40]], L=80 if k <= 21 else k + 100),
             "tie": case([(A, 2), (snp(A, p), 2)]),
             "three_way": case([(A, 3), (snp(A, p, 1), 2), (snp(A, p, 2), 1)]),
             "nested": case([(A, 3), (B, 2), (snp(B, p + 6), 1)]),
             "overlapped": case([(A, 3), (snp(A, p), 2), (snp(snp(A, p), p + 5), 1)]),
             "palindrome": case([(P + b"A" + _revcomp(P), 3), (P + b"C" + _revcomp(P), 2)]),
             "alternate": case([(A, 3), (snp(A, k + 9), 2), (R + A[k + 16:k + 76], 2)], bubble=3 * k, trim=3 * k)}
+
+
+def _pick(n, seed, ok):
+    """the first of genome_bases(n, seed), genome_bases(n, seed + 1000), ... that ``ok`` accepts"""
+    while True:
+        s = genome_bases(n, seed).tobytes()
+        if ok(s):
+            return s
+        seed += 1000
+
+
+def _plain_kmers(seq, k):
+    """every k-mer of seq occurs once on its two strands together (a self-complementary one counts as one)"""
+    mers = [seq[i:i + k] for i in range(len(seq) - k + 1)]
+    both = set(mers) | {_revcomp(m) for m in mers}
+    return len(both) == 2 * len(mers) - sum(1 for m in mers if m == _revcomp(m))
+
+
+def unitig_bubble_edge_cases(k, read_len=None):
+    """Edge inputs of rule 9 aimed at the bubble kernels: name -> (FASTQ file, None, what the case is made of), laid out as
+    unitig_bubble_cases lays its cases out -- haplotypes tiled into reads of ``read_len`` bases (default 80 up to k = 33, 140
+    above: an 80-base read holds 17 windows of k = 64, and a haplotype written once is not solid) at a step of 10.  A is a
+    random sequence of 400 bases, p = 200, u = A[p - k : p] the fork and t = A[p + 1 : p + 1 + k] the merge of a substitution
+    at p.  Strings compare as the 2k-bit keys do (A < C < G < T), so which side judges a bubble (u < rc(t)) and on which strand
+    a fork is stored (u < rc(u)) is decided here: where a case needs one of the two, A is the first of a sequence of seeds
+    that has it.  ``fork`` and ``merge`` in what a case is made of are these strings.
+
+    four_way      the four bases at p, x 4, x 3, x 2, x 2: one bubble of four branches, every lane of the quad walks
+    two_pairs     A x 3, A with the second base at p x 2, C = A with the third base at p and a substitution at p + 5 x 3,
+                  D = C with the fourth base at p x 2, and u < rc(t) for both merges: one quad judges two bubbles
+    homopolymer   left + 'A' (k - 1) + right x 3, left + 'A' (k - 2) + right x 2: branches of 2 and of 1 k-mers
+    blocked_lane  three bases at p, x 3, x 2, x 1, and a path x 2 that joins the second k-mer of the x 2 branch: that lane's
+                  walk ends at a merge of its own, the other two lanes are a bubble.  (The first k-mers of a fork's branches
+                  share their first k - 1 bases and so their predecessors: one of them alone cannot be joined)
+    blocked_fork  the same with the path joining the first k-mers: every branch starts at a merge, no lane walks
+    second_phase  A x 3, the substitution x 2, and Dg = R + A[p - 5 : p - 5 + read_len] x 2 beside Dg with a substitution at
+                  k + 4 x 2, R random of 2k + 10 bases; trim = bubble = 3k.  Dg's bubble pops in the first phase, R is then a
+                  tip, and without R the junction inside A's branch is gone: A's bubble pops in the second phase
+    limit_split   A x 3, A without its bases p, p + 1 x 2 (indel_long): branches of k + 1 and k - 1 k-mers
+    near_tie_a/b  A x 2, the deletion x 2, and reads of k bases, one k-mer each, from the middle of either branch, as many as
+                  bring sum_a len_b - sum_b len_a into (0, min len) -- the longer branch a wins by less than one branch
+                  length -- or into (-min len, 0)
+    tie_fwd/rev   A x 2, the substitution x 2, the judging fork on its canonical strand / on the other one
+    two_loops     L + U + X1 + U + X2 + U + R x 2 with U of k and X1, X2 of 10 bases: two branches that leave U and come back
+                  to it, fork and merge are one oriented node
+    even k only, x of k / 2 bases:
+    selfcomp_fork   L + x + rc(x) + c + R for two bases c, x 3 and x 2, and u = x + rc(x) < rc(t)
+    selfcomp_merge  L + c + x + rc(x) + R likewise, and u < t = x + rc(x)
+    hairpin_even    P + AT + rc(P) x 3 beside P + CG + rc(P) x 2: a self-complementary k-mer in the middle of either branch"""
+    L = int(read_len) if read_len else (80 if k <= 33 else 140)
+    snp, rc, p = _snp, _revcomp, 200
+
+    def case(haps, extra=(), **kw):
+        return _bubble_case(haps, extra, L, **dict({"bubble": 3 * k, "trim": k}, **kw))
+
+    def fork(A):
+        return A[p - k:p]
+
+    def merge(A):
+        return A[p + 1:p + 1 + k]
+
+    def judged_from_u(A):
+        return _plain_kmers(A, k) and fork(A) < rc(merge(A))
+
+    out = {}
+    A = _pick(400, 501, judged_from_u)
+    out["four_way"] = case([(A, 4), (snp(A, p, 1), 3), (snp(A, p, 2), 2), (snp(A, p, 3), 2)], fork=fork(A), merge=merge(A))
+
+    A = _pick(400, 502, lambda s: judged_from_u(s) and fork(s) < rc(merge(snp(s, p + 5))))
+    C = snp(snp(A, p, 2), p + 5)
+    out["two_pairs"] = case([(A, 3), (snp(A, p, 1), 2), (C, 3), (snp(C, p, 1), 2)], fork=fork(A), merge=merge(A), merge2=merge(C))
+
+    left = _pick(200, 503, lambda s: s[-1:] != b"A" and _plain_kmers(s, k))
+    right = _pick(200, 504, lambda s: s[:1] != b"A" and _plain_kmers(s, k))
+    out["homopolymer"] = case([(left + b"A" * (k - 1) + right, 3), (left + b"A" * (k - 2) + right, 2)],
+                              short=left[-1:] + b"A" * (k - 2) + right[:1])
+
+    A = _pick(400, 505, judged_from_u)
+    B, R = snp(A, p, 1), genome_bases(2 * k + 10, 506).tobytes()
+    three = [(A, 3), (B, 2), (snp(A, p, 2), 1)]
+    join2 = R + bytes([_other_base(A[p - k + 1], 1)]) + B[p - k + 2:p - k + 2 + L]
+    join1 = R + bytes([_other_base(A[p - k], 1)]) + B[p - k + 1:p - k + 1 + L]
+    out["blocked_lane"] = case(three + [(join2, 2)], fork=fork(A), merge=merge(A), blocked=B[p - k + 1:p + 1])
+    out["blocked_fork"] = case(three + [(join1, 2)], fork=fork(A), merge=merge(A))
+
+    A = _pick(400, 507, lambda s: _plain_kmers(s, k))
+    Dg = genome_bases(2 * k + 10, 508).tobytes() + A[p - 5:p - 5 + L]
+    out["second_phase"] = case([(A, 3), (snp(A, p), 2), (Dg, 2), (snp(Dg, k + 4), 2)], bubble=3 * k, trim=3 * k)
+
+    A = _pick(400, 509, lambda s: _plain_kmers(s, k))
+    dele = A[:p] + A[p + 2:]
+    out["limit_split"] = case([(A, 3), (dele, 2)])
+
+    # the near ties: the branches are the k-mers of one haplotype alone; every k-mer of the tiled reads is counted here
+    A = _pick(400, 510, lambda s: _plain_kmers(s, k))
+    dele = A[:p] + A[p + 2:]
+    mers = lambda s: [s[i:i + k] for i in range(len(s) - k + 1)]
+    a = [m for m in mers(A) if m not in set(mers(dele))]
+    b = [m for m in mers(dele) if m not in set(mers(A))]
+    count = {}
+    for seq, m in ((A, 2), (dele, 2)):
+        for r in _tile(seq, L):
+            for w in mers(r):
+                count[w] = count.get(w, 0) + m
+    d0 = sum(count[m] for m in a) * len(b) - sum(count[m] for m in b) * len(a)
+    for name, sign in (("near_tie_a", 1), ("near_tie_b", -1)):
+        x, y = next((x, n - x) for n in range(2000) for x in range(n + 1)
+                    if 0 < sign * (d0 + x * len(b) - (n - x) * len(a)) < min(len(a), len(b)))
+        out[name] = case([(A, 2), (dele, 2)], extra=[a[len(a) // 2]] * x + [b[len(b) // 2]] * y, extra_a=x, extra_b=y)
+
+    def judging(A):
+        return min(fork(A), rc(merge(A)))
+
+    A = _pick(400, 511, lambda s: _plain_kmers(s, k) and judging(s) < rc(judging(s)))
+    out["tie_fwd"] = case([(A, 2), (snp(A, p), 2)], fork=fork(A), merge=merge(A))
+    A = _pick(400, 512, lambda s: _plain_kmers(s, k) and judging(s) > rc(judging(s)))
+    out["tie_rev"] = case([(A, 2), (snp(A, p), 2)], fork=fork(A), merge=merge(A))
+
+    Lf, Rr, U = genome_bases(150, 513).tobytes(), genome_bases(150, 514).tobytes(), genome_bases(k, 515).tobytes()
+    X1, X2 = genome_bases(10, 516).tobytes(), genome_bases(10, 517).tobytes()
+    X1 = bytes([_other_base(Rr[0], 1)]) + X1[1:-1] + bytes([_other_base(Lf[-1], 1)])
+    X2 = bytes([_other_base(Rr[0], 2)]) + X2[1:-1] + bytes([_other_base(Lf[-1], 2)])
+    out["two_loops"] = case([(Lf + U + X1 + U + X2 + U + Rr, 2)], fork=U)
+
+    if k % 2 == 0:
+        comp = lambda c: rc(bytes([c]))[0]
+        Lf, Rr = genome_bases(150, 521).tobytes(), genome_bases(150, 522).tobytes()
+        x = _pick(k // 2, 523, lambda s: s + rc(s) < rc(Rr[:k]))
+        cs = [c for c in b"ACGT" if c != comp(Lf[-1])][:2]
+        out["selfcomp_fork"] = case([(Lf + x + rc(x) + bytes([c]) + Rr, m) for c, m in zip(cs, (3, 2))], fork=x + rc(x), merge=Rr[:k])
+        x = _pick(k // 2, 524, lambda s: Lf[-k:] < s + rc(s))
+        cs = [c for c in b"ACGT" if c != comp(Rr[0])][:2]
+        out["selfcomp_merge"] = case([(Lf + bytes([c]) + x + rc(x) + Rr, m) for c, m in zip(cs, (3, 2))], fork=Lf[-k:], merge=x + rc(x))
+        P = genome_bases(150, 525).tobytes()
+        out["hairpin_even"] = case([(P + b"AT" + rc(P), 3), (P + b"CG" + rc(P), 2)], fork=P[-k:])
+    return out
+
+
+def unitig_bubble_cap_cases(k=21, d=5):
+    """Two inputs at the cap of rule 9's parameter (MSGPU_UG_BUBBLE_MAX = 4096): A of 4500 random bases x 3 beside A with a
+    substitution every ``d`` bases from position 200 on x 2, tiled into 80-base reads.  With m sites the two branches have
+    (m - 1) d + k k-mers each: 4096 in ``cap_4096``; ``cap_4097`` has one more site, one base behind the last."""
+    m = (4096 - k) // d + 1
+    assert (m - 1) * d + k == 4096
+    A = _pick(4500, 531, lambda s: _plain_kmers(s, k))
+    B = A
+    for i in range(m):
+        B = _snp(B, 200 + i * d)
+    meta = dict(bubble=4096, trim=k)
+    return {"cap_4096": _bubble_case([(A, 3), (B, 2)], (), 80, branch=4096, **meta),
+            "cap_4097": _bubble_case([(A, 3), (_snp(B, 200 + (m - 1) * d + 1), 2)], (), 80, branch=4097, **meta)}
+
+
+def unitig_tangle(k, genome, seed):
+    """A tangled input of rule 9: (FASTQ file, None, what it is made of).  A random genome of ``genome`` bases and three
+    copies of it edited at two positions in 5k -- half substitutions, a quarter insertions of a base, a quarter deletions of
+    one; each whole sequence is one read, written one to three times.  At k = 8 .. 12 the k-mers repeat by chance: hundreds of
+    forks, bubbles inside and beside each other, branches from one k-mer on.  To be run at min_count = 1."""
+    g = genome_bases(genome, seed)
+    seqs = [g.tobytes()]
+    for j in range(3):
+        hit = (splitmix64(seed, 100 + j, genome) % np.uint64(5 * k)) < np.uint64(2)
+        kind = splitmix64(seed, 110 + j, genome) % np.uint64(4)  # 0, 1: substitution, 2: insertion, 3: deletion
+        draw = splitmix64(seed, 120 + j, genome)
+        parts = []
+        for i in range(genome):
+            b = int(g[i])
+            if not hit[i]:
+                parts.append(b)
+            elif kind[i] < 2:
+                parts.append(_other_base(b, int(draw[i] % np.uint64(3)) + 1))
+            elif kind[i] == 2:
+                parts += [b"ACGT"[int(draw[i] % np.uint64(4))], b]
+        seqs.append(bytes(parts))
+    times = [int(x) + 1 for x in splitmix64(seed, 130, 4) % np.uint64(3)]
+    reads = [s for s, m in zip(seqs, times) for _ in range(m)]
+    fq = b"".join(b"@t%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads))
+    return fq, None, {"sequences": list(zip(seqs, times)), "bubble": 3 * k, "trim": k, "min_count": 1}
 
 
 def mapper_workload(n_reads, read_len, n_unitigs, seed, coverage=10, error=0.06, families=2, copies=6, repeat_len=600,

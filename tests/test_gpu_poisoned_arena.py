@@ -34,10 +34,12 @@ import test_gpu_pair as pair_tests
 import test_gpu_polish_edges as polish_edges
 import test_gpu_polish_rank as polish_rank
 import test_gpu_scrub_uf_edges as scrub_uf_edges
+import test_gpu_unitigs_bubble_edges as bubble_edge_tests
 import test_gpu_unitigs_bubbles as bubble_tests
 import test_mapper_batches_host as batches_host
 import ufedgecases
 import ugbubblecases
+import ugbubbleedgecases
 
 pytestmark = pytest.mark.gpu
 
@@ -102,6 +104,11 @@ def test_kmer_partitions(mods, tmp_path, stage):
 @pytest.mark.parametrize("name,k", bubble_tests.HAND_AT)
 def test_unitig_bubbles(mods, tmp_path, name, k):
     bubble_tests.test_hand_made_cases(mods["ug"], tmp_path, name, k)
+
+
+@pytest.mark.parametrize("name,k", ugbubbleedgecases.HAND_AT + [ugbubbleedgecases.TANGLE_AT[0], ugbubbleedgecases.TANGLE_AT[-1]])
+def test_unitig_bubble_edges(mods, tmp_path, name, k):
+    bubble_edge_tests.test_against_the_restatement(mods["ug"], tmp_path, name, k)
 
 
 @pytest.mark.parametrize("name", ugbubblecases.DIPLOID)

@@ -17,7 +17,7 @@ import ugcases
 pytestmark = pytest.mark.gpu
 
 LIMIT = 300  # seconds per test
-HAND_AT = [(n, cases.K_HAND) for n in cases.HAND] + [(n, 33) for n in cases.HAND_33]
+HAND_AT = cases.HAND_AT
 
 
 @pytest.fixture(scope="module")
@@ -119,10 +119,10 @@ class _Ctx:
     def set(self, bubble):
         return self.L.msgpu_ug_set_bubbles(self.ctx, bubble)
 
-    def run(self, k, paths, trim=-1, min_length=500):
+    def run(self, k, paths, trim=-1, min_length=500, min_count=2):
         """-> (all text, cut text, tip rounds, bubble stats as a dict, bubble rounds)"""
         lib, L, res = self.lib, self.L, C.c_void_p()
-        prm = lib.UgParams(k, 2, trim, min_length)
+        prm = lib.UgParams(k, min_count, trim, min_length)
         rc = L.msgpu_ug_run(self.ctx, C.byref(prm), os.fsencode(paths[0]), None, 0, 0, C.byref(res))
         assert rc == lib.OK, L.msgpu_ug_last_error(self.ctx)
         try:

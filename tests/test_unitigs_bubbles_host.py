@@ -23,7 +23,7 @@ import ugcases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "unitigs_bubbles")
-HAND_AT = [(n, cases.K_HAND) for n in cases.HAND] + [(n, 33) for n in cases.HAND_33]
+HAND_AT = cases.HAND_AT
 
 
 @pytest.fixture(scope="module")

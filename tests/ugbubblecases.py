@@ -11,7 +11,11 @@ KS_DIPLOID = (15, 31, 32, 33, 64)
 KS_CONDITIONS = (15, 31, 32, 33)  # at k = 64 a 100-base read holds 37 k-mers: too few of them are solid for the conditions
 HAND = ("edge", "indel_long", "indel_short", "tie", "three_way", "nested", "overlapped", "palindrome", "alternate")
 K_HAND = 21
-HAND_33 = ("edge", "nested", "alternate")
+HAND_33 = HAND  # every hand-made case runs at k = 33 (the first 128-bit keys) and at k = 32 (the key mask is all ones) as well
+KS_HAND = (K_HAND, 33, 32)
+HAND_AT = [(n, k) for k in KS_HAND for n in HAND]
+# every condition of meets_conditions holds at the three k.  indel_short needs reads of k + 100 bases above k = 21 for "the
+# sum and the mean disagree" (synth.unitig_bubble_cases says why); every haplotype written once is solid in 80-base reads
 MIN_LENGTH = 100  # of the hand-made cases
 
 

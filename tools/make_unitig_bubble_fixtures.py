@@ -26,7 +26,7 @@ def record(name, k):
 if __name__ == "__main__":
     out = os.path.join(ROOT, "tests", "golden", "unitigs_bubbles")
     os.makedirs(out, exist_ok=True)
-    for name, k in [(n, cases.K_HAND) for n in cases.HAND] + [(n, 33) for n in cases.HAND_33]:
+    for name, k in cases.HAND_AT:
         with open(os.path.join(out, "%s_k%d.json" % (name, k)), "w") as f:
             json.dump(record(name, k), f, indent=1)
             f.write("\n")
