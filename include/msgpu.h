@@ -1349,7 +1349,33 @@ void        msgpu_ug_result_free(msgpu_ug_result *r);
  *     msgpu_map_batch_bytes_ext for ranking = 0): per anchor it adds 104 bytes (seven words of segment heads, numbers,
  *     starts, class flags and their scans, four of class lists and sort bounds, parent, n_secondary, a 64-bit sub, the row,
  *     two 64-bit sort keys, 12 bytes of the list class's stretch) and a fixed 24 * 256 bytes.  The mask level 1/2, the ratio
- *     0.9 and the mapq formula are choices modelled on minimap2's, unchecked on real reads. */
+ *     0.9 and the mapq formula are choices modelled on minimap2's, unchecked on real reads.
+ * 13. mates, on request (msgpu_map_set_mates(ctx, on, max_insert); off on a new context; it needs no other mode: seed, exact,
+ *     cigar, extend and rank all combine with it; with ava it is MSGPU_E_ARG).  The query file is interleaved: records 2p and
+ *     2p + 1 are mate 1 and mate 2 of pair p; the names are not compared; an odd number of query records is MSGPU_E_ARG naming
+ *     the count.  max_insert is 1..2^31 - 1, default 1000.  The rule reads the chain table as the run leaves it, behind rule
+ *     11's extension.  (1) Concordant: chain a of record 2p and chain b of record 2p + 1 are concordant iff they have the same
+ *     target record, their strands differ, and with f the chain of strand 0 and r the chain of strand 1:
+ *     f.t_start <= r.t_start, f.t_end <= r.t_end (the forward mate lies to the left and neither passes the other) and
+ *     tl = r.t_end - f.t_start <= max_insert.  Either mate may be the forward one.  (2) Selection: among the concordant
+ *     combinations of a pair one is selected: the greatest score(a) + score(b) (a 64-bit sum), then the smaller tl, then the
+ *     smaller index of a, then the smaller index of b.  n_best is the number of concordant combinations whose sum equals the
+ *     greatest sum, whatever their tl, clamped to 2^32 - 1.  (3) Rows, one per chain in output order, {mate, tlen, cls,
+ *     n_best}: the two selected chains have cls = 1, mate = the other's index in the whole run's chain table, tlen = tl and
+ *     the pair's n_best; every other chain has {0xffffffff, 0, 0, 0}.  (4) Counts (msgpu_map_mstats): the pairs of the input,
+ *     proper pairs, ambiguous pairs (proper with n_best > 1), discordant pairs (chains on both mates, none concordant),
+ *     single pairs (chains on one mate only), unmapped pairs, the pairs per kernel class, the largest pair in chains, the
+ *     sum, minimum and maximum of tlen over the proper pairs (integers: no order reaches them) and the step's device time.
+ *     (5) With mates on every line carries pr:A:P or pr:A:U behind s1:i (behind s2:i with ranking on); a P line also carries
+ *     mi:i:<the mate's line, 0-based>, tl:i:<tlen>, nb:i:<n_best>; NM and cg follow as before; line order and every other
+ *     column are untouched.  (6) With mates off every byte of every output is as before.  (7) Rule 9 with mates on: the unit
+ *     of the greedy cut is the pair: a batch starts at an even record and holds whole pairs, a(p) = a(2p) + a(2p + 1) and
+ *     likewise the bases; a pair that exceeds the budget on its own is MSGPU_E_NOMEM naming the pair; with mates on a run has
+ *     fewer than 2^32 chains, else MSGPU_E_ARG.  msgpu_map_batch_bytes_mates bounds a batch (it equals
+ *     msgpu_map_batch_bytes_rank for mates = 0): per anchor it adds 60 bytes (three words of segment heads, numbers and
+ *     starts, the count of mate 1's chains, three words of class lists, 16 bytes of the pair's selection, the row) and a fixed
+ *     12 * 256 bytes.  (8) Orientation FR only, the selection order and n_best are choices modelled on short-read mappers,
+ *     unchecked on real reads. */
 typedef struct msgpu_mapctx msgpu_mapctx; /* a device context of the stage */
 typedef struct msgpu_map_result msgpu_map_result;
 typedef struct msgpu_map_params {
@@ -1509,6 +1535,43 @@ uint64_t    msgpu_map_batch_bytes_rank(const msgpu_map_params *params, uint32_t 
                                        uint64_t n_query_bases);
 int         msgpu_map_rank_tables(msgpu_mapctx *ctx, const msgpu_map_chain *chains, uint64_t n, msgpu_map_rank *ranks_out);
 int         msgpu_map_rank_tables_stats(const msgpu_mapctx *ctx, msgpu_map_rstats *out);
+/* Rule 13.  msgpu_map_set_mates switches it on (on != 0) or off and sets max_insert for every later msgpu_map_run /
+ * msgpu_map_run_index, until it is set again; a max_insert outside 1..2^31 - 1 is MSGPU_E_ARG, the previous values stay and
+ * msgpu_map_last_error names the value.  msgpu_map_result_mates: entry i belongs to line i; *n = 0 when mates was off.
+ * msgpu_map_result_mate_stats gives zeros when it was off.  msgpu_map_mate_tables is the table-level entry (as
+ * msgpu_map_rank_tables is rule 12's): rule 13 on n chains of the host in output order, copied to the device; mate is relative
+ * to that table; of a chain only query, target, strand, score, t_start and t_end are read.  query must not decrease,
+ * strand <= 1 and t_start <= t_end, else MSGPU_E_ARG "chain <i>: order", "chain <i>: strand" or "chain <i>: range", naming the
+ * smallest bad chain and the first violated of the three: a device pass, complete before any mates kernel runs.  n = 0 is
+ * fine.  The table knows the pairs with a chain only: its n_pairs counts those and n_unmapped is 0.
+ * msgpu_map_mate_tables_stats: the counts of the context's last msgpu_map_mate_tables (zeros after an error).
+ * MSGPU_MAP_MATES_ANCHOR_BYTES, MSGPU_MAP_MATES_FIXED_BYTES: what msgpu_map_batch_bytes_mates adds per anchor and once. */
+#define MSGPU_MAP_MATES_ANCHOR_BYTES 60u
+#define MSGPU_MAP_MATES_FIXED_BYTES (12u * 256u)
+#define MSGPU_MAP_MAX_INSERT_DEFAULT 1000u
+typedef struct msgpu_map_mate { /* in output order: entry i belongs to chain i */
+  uint32_t mate;   /* the selected mate's chain; 0xffffffff for a chain that is not selected */
+  uint32_t tlen;   /* rule 13.1's tl of the selected combination */
+  uint32_t cls;    /* 1: selected (a proper pair's chain); 0: not */
+  uint32_t n_best; /* rule 13.2 */
+} msgpu_map_mate;
+typedef struct msgpu_map_mstats { /* rule 13, summed over the batches */
+  uint32_t mates, max_insert;                                         /* the switch; the parameter (0 when off) */
+  uint64_t n_pairs, n_proper, n_ambiguous, n_discordant, n_single, n_unmapped;
+  uint64_t n_pairs_settled, n_pairs_lanes16, n_pairs_lanes64, n_pairs_list; /* by kernel: the classifier (a mate without a chain, or
+                                                                         one chain each); at most 16 chains; at most 64; more */
+  uint64_t largest_pair;                                              /* in chains */
+  uint64_t tlen_sum, tlen_min, tlen_max;                              /* over the proper pairs; 0 without one */
+  float    mate_ms, reserved2;                                        /* device, by events */
+} msgpu_map_mstats;
+int         msgpu_map_set_mates(msgpu_mapctx *ctx, int on, uint32_t max_insert);
+int         msgpu_map_result_mates(const msgpu_map_result *r, const msgpu_map_mate **mates, uint64_t *n);
+int         msgpu_map_result_mate_stats(const msgpu_map_result *r, msgpu_map_mstats *out);
+uint64_t    msgpu_map_batch_bytes_mates(const msgpu_map_params *params, uint32_t extend, uint32_t ranking, uint32_t mates,
+                                        uint64_t n_anchors, uint64_t n_query_bases);
+int         msgpu_map_mate_tables(msgpu_mapctx *ctx, const msgpu_map_chain *chains, uint64_t n, uint32_t max_insert,
+                                  msgpu_map_mate *rows_out);
+int         msgpu_map_mate_tables_stats(const msgpu_mapctx *ctx, msgpu_map_mstats *out);
 void        msgpu_map_result_free(msgpu_map_result *r);
 
 /* ---- pileup consensus: polishing a draft from the mapper's run tables ------------------------------
@@ -1528,12 +1591,18 @@ void        msgpu_map_result_free(msgpu_map_result *r);
  *     scalar block, and it is complete before any kernel walks a run: a bad table ends in an error, never in a fault.
  *     In ranked form (msgpu_pl_run_ranked) a check (j) is added and reported last: the rank row's parent is in range and names
  *     a chain of the same query record that is its own parent, and mapq <= 60; otherwise "chain <i>: rank".
+ *     In mates form (msgpu_pl_run_mates) a check (k) is added and reported last: cls <= 1 on every row, and for a row with
+ *     cls == 1 the mate is in range, the mate's row has cls == 1 and names this chain, the mate's query record is this
+ *     one's ^ 1, and n_best >= 1; otherwise "chain <i>: mates".
  *  2. voters.  A chain is eligible iff matches * 100 >= min_identity * block.  Per query record the voter is the eligible
  *     chain with the greatest score, then the greatest block, then the first in table order.  Every other chain is ignored
  *     and counted.  Ranked form (msgpu_pl_run_ranked, with the mapper's rule 12 rows): a chain votes iff it is eligible,
  *     primary (parent == its own index) and mapq >= min_mapq.  So a read may have several voters (a split alignment votes
  *     with every part), a secondary never votes, and a read placed equally on two repeat copies (mapq 0) votes only at
- *     min_mapq = 0.  Everything behind the voters' spans is the same in both forms.
+ *     min_mapq = 0.  Everything behind the voters' spans is the same in both forms.  Mates form (msgpu_pl_run_mates, with
+ *     the mapper's rule 13 rows): a chain votes iff it is eligible, selected (cls == 1) and n_best == 1.  So a pair placed
+ *     equally well twice does not vote, an unselected chain never votes, and a read inside a repeat copy votes on the copy
+ *     that its mate names.  Everything behind the voters' spans is the same code in all three forms.
  *  3. oriented query.  Column j of a chain reads byte q_start + j_q of the query for strand 0 (j_q: the query bases that the
  *     columns in front of j consume); for strand 1 the oriented query is MSGPU_COPY_REVCOMP's of the whole record (reversed,
  *     A <-> T and C <-> G in upper case, every other byte as it is), and the chain starts at qlen - q_end in it.  The byte is
@@ -1597,6 +1666,12 @@ int         msgpu_pl_run(msgpu_plctx *ctx, const msgpu_pl_params *params, const 
 int         msgpu_pl_run_ranked(msgpu_plctx *ctx, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
                                 const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off,
                                 const msgpu_map_rank *ranks, uint32_t min_mapq, uint32_t flags, msgpu_pl_result **out);
+/* The stage with rule 2 in mates form: mates holds n_chains rows of the mapper's rule 13 (msgpu_map_result_mates or
+ * msgpu_map_mate_tables; mate indexes this chain table), checked by rule 1 (k).  msgpu_pl_run and msgpu_pl_run_ranked are
+ * untouched by it. */
+int         msgpu_pl_run_mates(msgpu_plctx *ctx, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
+                               const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off,
+                               const msgpu_map_mate *mates, uint32_t flags, msgpu_pl_result **out);
 const char *msgpu_pl_result_text(const msgpu_pl_result *r, uint64_t *len);
 int         msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out);
 int         msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **records, uint64_t *n);

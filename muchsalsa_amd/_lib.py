@@ -285,6 +285,24 @@ MAP_CHAIN_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("strand", "<u4
 MAP_RANK_DTYPE = np.dtype([("parent", "<u4"), ("sub", "<i4"), ("n_secondary", "<u4"), ("mapq", "<u4")])
 
 
+class MapMate(C.Structure):  # msgpu_map_mate
+    _fields_ = [("mate", C.c_uint32), ("tlen", C.c_uint32), ("cls", C.c_uint32), ("n_best", C.c_uint32)]
+
+
+class MapMateStats(C.Structure):  # msgpu_map_mstats
+    _fields_ = ([("mates", C.c_uint32), ("max_insert", C.c_uint32)] +
+                [(n, C.c_uint64) for n in ("n_pairs", "n_proper", "n_ambiguous", "n_discordant", "n_single", "n_unmapped",
+                                           "n_pairs_settled", "n_pairs_lanes16", "n_pairs_lanes64", "n_pairs_list", "largest_pair",
+                                           "tlen_sum", "tlen_min", "tlen_max")] +
+                [("mate_ms", C.c_float), ("reserved2", C.c_float)])
+
+
+MAP_MATE_DTYPE = np.dtype([("mate", "<u4"), ("tlen", "<u4"), ("cls", "<u4"), ("n_best", "<u4")])
+MAP_MATES_ANCHOR_BYTES = 60          # MSGPU_MAP_MATES_ANCHOR_BYTES
+MAP_MATES_FIXED_BYTES = 12 * 256     # MSGPU_MAP_MATES_FIXED_BYTES
+MAP_MAX_INSERT_DEFAULT = 1000        # MSGPU_MAP_MAX_INSERT_DEFAULT
+
+
 class MapBatch(C.Structure):  # msgpu_map_batch
     _fields_ = [("first_query", C.c_uint32), ("n_queries", C.c_uint32)] + [
         (n, C.c_uint64) for n in ("n_anchors", "n_query_bases", "n_groups", "n_chains", "n_pairs", "bytes_bound", "bytes_peak")]
@@ -579,6 +597,12 @@ SYMBOLS = [
     ("msgpu_map_batch_bytes_rank", C.c_uint64, [C.POINTER(MapParams), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
     ("msgpu_map_rank_tables", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("msgpu_map_rank_tables_stats", C.c_int, [C.c_void_p, C.POINTER(MapRankStats)]),
+    ("msgpu_map_set_mates", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    ("msgpu_map_result_mates", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(MapMate)), C.POINTER(C.c_uint64)]),
+    ("msgpu_map_result_mate_stats", C.c_int, [C.c_void_p, C.POINTER(MapMateStats)]),
+    ("msgpu_map_batch_bytes_mates", C.c_uint64, [C.POINTER(MapParams), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    ("msgpu_map_mate_tables", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("msgpu_map_mate_tables_stats", C.c_int, [C.c_void_p, C.POINTER(MapMateStats)]),
     ("msgpu_map_result_free", None, [C.c_void_p]),
     ("msgpu_pl_default_params", None, [C.POINTER(PlParams)]),
     ("msgpu_pl_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -586,6 +610,8 @@ SYMBOLS = [
     ("msgpu_pl_last_error", C.c_char_p, [C.c_void_p]),
     ("msgpu_pl_run", C.c_int, [C.c_void_p, C.POINTER(PlParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("msgpu_pl_run_mates", C.c_int, [C.c_void_p, C.POINTER(PlParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("msgpu_pl_run_ranked", C.c_int, [C.c_void_p, C.POINTER(PlParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("msgpu_pl_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),

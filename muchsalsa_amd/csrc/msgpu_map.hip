@@ -24,6 +24,10 @@
 //   ranking        rule 12, on request, behind k_mp_table: the chains of a query record are a segment (k_rk_heads, a scan);
 //                  k_rk_wave ranks a segment of at most 64 chains in one wavefront, a lane per chain; k_rk_list walks a longer
 //                  one in sorted order against its list of primaries (LDS, then the arena); k_rk_figures and k_rk_rows finish
+//   mates          rule 13, on request, the last device step of a batch (behind rule 11's extension): the chains of a pair of
+//                  query records are a segment (k_mt_heads, a scan); k_mt_classify settles a pair with one chain per mate or
+//                  none on one, k_mt_lanes<16> and <64> take a pair in 16 lanes or a wavefront, a lane per mate-1 chain,
+//                  k_mt_list a longer one in tiles (mate 2's in LDS); k_mt_rows writes the rows and the counts
 // Integers only.  Kernel rules: vector stores and vector atomics only; no inline asm.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
@@ -712,6 +716,232 @@ __global__ __launch_bounds__(256) void k_rk_rows(const msgpu_map_chain *chains, 
   wave_count(i < n && zero, cnt + RK_MAPQ0);
 }
 
+// ---- rule 13: mates.  A segment is the chains of one pair (query >> 1), consecutive in the table, mate 1's chains in front:
+// a start and the two counts n1, n2.  k_mt_heads marks where the pair changes (and, for a table from the host, looks for the
+// first chain that breaks 13's conditions), a scan numbers the segments, k_mt_classify settles with a lane per pair the pairs
+// with n1 * n2 = 0 and with n1 = n2 = 1 and appends the others to three lists: at most 16 chains (k_mt_lanes<16>: four pairs
+// per wavefront, a row of 16 lanes each), at most 64 (k_mt_lanes<64>: a wavefront per pair), more (k_mt_list: tiles of 64
+// mate-1 chains in registers against tiles of mate-2 chains in LDS).  All three leave one MtSel per pair; k_mt_rows writes
+// the rows in output order and the counts.  The lists are in no fixed order: a pair's selection depends on its chains alone.
+
+enum { MT_PROPER = 0, MT_AMBIG, MT_DISCORD, MT_SINGLE, MT_SETTLED, MT_L16, MT_L64, MT_LIST, MT_LARGEST, MT_TLSUM, MT_TLMIN, MT_TLMAX, MT_BAD,
+       MT_COUNT };
+constexpr uint32_t MT_NONE = 0xffffffffu, MT_TILE = 256;
+
+struct MtChain { // what 13.1 and 13.2 read of a chain, behind rule 11's extension
+  uint32_t target, ts, te, strand;
+  int32_t  score;
+};
+struct MtSel { // the selection of a pair: a, b index the table (MT_NONE: no concordant combination)
+  uint32_t a, b, tl, n_best;
+};
+struct MtAcc { // a lane's best combination so far as 13.2's key in two words (greater is better), and the combinations at its best sum
+  uint64_t hi, lo, cnt;
+};
+
+// chain i of a table of n; ends (rule 11, or null): the left end cells, then the right ones, whose x move the target range
+__device__ __forceinline__ MtChain mt_load(const msgpu_map_chain *chains, const msgpu_ext_end *ends, uint32_t n, uint32_t i) {
+  const msgpu_map_chain c = chains[i];
+  MtChain m{c.target, c.t_start, c.t_end, c.strand, c.score};
+  if (ends) {
+    m.ts -= ends[i].x;
+    m.te += ends[n + i].x;
+  }
+  return m;
+}
+
+// 13.1; *tl is written for a concordant combination
+__device__ __forceinline__ bool mt_concordant(const MtChain &a, const MtChain &b, uint32_t max_insert, uint32_t *tl) {
+  if (a.target != b.target || a.strand == b.strand) return false;
+  const MtChain &f = a.strand ? b : a, &r = a.strand ? a : b;
+  if (f.ts > r.ts || f.te > r.te || r.te < f.ts) return false;
+  const uint32_t d = r.te - f.ts;
+  *tl = d;
+  return d <= max_insert;
+}
+
+// 13.2's key without truncation: hi = (sum + 2^32) in 33 bits, then 2^31 - 1 - tl in 31 (tl <= max_insert < 2^31);
+// lo = the complements of the two indices inside the pair.  lo > 0: an index is below 2^32 - 1
+__device__ __forceinline__ void mt_take(MtAcc &acc, const MtChain &a, const MtChain &b, uint32_t ia, uint32_t ib, uint32_t max_insert) {
+  uint32_t tl;
+  if (!mt_concordant(a, b, max_insert, &tl)) return;
+  const uint64_t sum = static_cast<uint64_t>(static_cast<long long>(a.score) + b.score + (1ll << 32));
+  const uint64_t hi = (sum << 31) | (0x7fffffffu - tl), lo = (static_cast<uint64_t>(~ia) << 32) | static_cast<uint32_t>(~ib);
+  const uint64_t best = acc.hi >> 31;
+  if (!acc.cnt || sum > best) acc.cnt = 1;
+  else if (sum == best) ++acc.cnt;
+  if (hi > acc.hi || (hi == acc.hi && lo > acc.lo)) {
+    acc.hi = hi;
+    acc.lo = lo;
+  }
+}
+
+// the sum of every aligned group of W lanes (W = 16 or 64), in all of its lanes: group_max_i64's exchanges.  All 64 lanes active
+template <int CTRL> __device__ __forceinline__ uint64_t mt_dpp_add(uint64_t v) {
+  const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(static_cast<uint32_t>(v)), CTRL, 0xf, 0xf, false));
+  const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(static_cast<uint32_t>(v >> 32)), CTRL, 0xf, 0xf, false));
+  return v + ((static_cast<uint64_t>(hi) << 32) | lo);
+}
+template <int W> __device__ __forceinline__ uint64_t mt_group_sum(uint64_t v) {
+  static_assert(W == 16 || W == 64, "group width");
+  v = mt_dpp_add<0xb1>(v);  // quad_perm:[1,0,3,2]
+  v = mt_dpp_add<0x4e>(v);  // quad_perm:[2,3,0,1]
+  v = mt_dpp_add<0x141>(v); // row_half_mirror
+  v = mt_dpp_add<0x140>(v); // row_mirror
+  if constexpr (W == 64) {
+    auto lo = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(v), static_cast<uint32_t>(v), false, false);
+    auto hi = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(v >> 32), static_cast<uint32_t>(v >> 32), false, false);
+    v = ((static_cast<uint64_t>(hi[0]) << 32) | lo[0]) + ((static_cast<uint64_t>(hi[1]) << 32) | lo[1]);
+    lo = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(v), static_cast<uint32_t>(v), false, false);
+    hi = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(v >> 32), static_cast<uint32_t>(v >> 32), false, false);
+    v = ((static_cast<uint64_t>(hi[0]) << 32) | lo[0]) + ((static_cast<uint64_t>(hi[1]) << 32) | lo[1]);
+  }
+  return v;
+}
+
+// the lanes' accumulators of a group of W lanes -> the pair's selection, in every lane of the group.  Two maxima (the first
+// word, then the second among the lanes that hold the first) and one sum (the counts of the lanes whose best sum is the
+// pair's); a lane without a combination has cnt = 0 and the smallest key.  s0: the pair's first chain, n1: its mate-1 chains
+template <int W> __device__ __forceinline__ MtSel mt_select(const MtAcc &acc, uint32_t s0, uint32_t n1) {
+  constexpr long long SIGN = static_cast<long long>(0x8000000000000000ull);
+  const uint64_t any = mt_group_sum<W>(acc.cnt ? 1 : 0);
+  const uint64_t hi = static_cast<uint64_t>(group_max_i64<W>(static_cast<long long>(acc.hi) ^ SIGN) ^ SIGN);
+  const uint64_t lo = static_cast<uint64_t>(group_max_i64<W>(acc.cnt && acc.hi == hi ? static_cast<long long>(acc.lo) ^ SIGN : SIGN) ^ SIGN);
+  const uint64_t nb = mt_group_sum<W>(acc.cnt && (acc.hi >> 31) == (hi >> 31) ? acc.cnt : 0);
+  if (!any) return MtSel{MT_NONE, MT_NONE, 0, 0};
+  return MtSel{s0 + ~static_cast<uint32_t>(lo >> 32), s0 + n1 + ~static_cast<uint32_t>(lo), 0x7fffffffu - static_cast<uint32_t>(hi & 0x7fffffffu),
+               static_cast<uint32_t>(min(nb, static_cast<uint64_t>(0xffffffffu)))};
+}
+
+__global__ __launch_bounds__(256) void k_mt_heads(const msgpu_map_chain *chains, uint32_t n, int validate, uint32_t *head, kf_ull *bad) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t q = chains[i].query, qp = i ? chains[i - 1].query : 0;
+  head[i] = !i || (q >> 1) != (qp >> 1);
+  if (validate && ((i && q < qp) || chains[i].strand > 1 || chains[i].t_start > chains[i].t_end)) atomicMin(bad, static_cast<kf_ull>(i));
+}
+
+// a lane per pair: n1 by a binary search for the pair's first chain of mate 2 (no step for a pair of one or two chains)
+__global__ __launch_bounds__(256) void k_mt_classify(const msgpu_map_chain *chains, const msgpu_ext_end *ends, uint32_t n_chains,
+                                                     const uint32_t *start, uint32_t n_seg, uint32_t max_insert, uint32_t *n1_out, MtSel *sel,
+                                                     uint32_t *list16, uint32_t *list64, uint32_t *listL, kf_ull *cursor, kf_ull *cnt) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  uint32_t       n = 0, n1 = 0, s0 = 0;
+  if (s < n_seg) {
+    s0 = start[s];
+    n  = start[s + 1] - s0;
+    uint32_t lo = 0, hi = n; // the first chain of the segment with an odd query record
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (chains[s0 + mid].query & 1u) hi = mid;
+      else lo = mid + 1;
+    }
+    n1        = lo;
+    n1_out[s] = n1;
+  }
+  const uint32_t n2 = n - n1;
+  const bool     both = n1 && n2, one = both && n == 2;
+  const bool     c16 = both && n > 2 && n <= 16, c64 = both && n > 16 && n <= 64, cl = both && n > 64;
+  if (s < n_seg && !c16 && !c64 && !cl) {
+    MtSel r{MT_NONE, MT_NONE, 0, 0};
+    if (one) {
+      uint32_t tl;
+      if (mt_concordant(mt_load(chains, ends, n_chains, s0), mt_load(chains, ends, n_chains, s0 + 1), max_insert, &tl)) r = MtSel{s0, s0 + 1, tl, 1};
+    }
+    sel[s] = r;
+  }
+  const uint64_t a16 = wave_append(c16, cursor + 0), a64 = wave_append(c64, cursor + 1), al = wave_append(cl, cursor + 2);
+  if (c16) list16[a16] = s;
+  if (c64) list64[a64] = s;
+  if (cl) listL[al] = s;
+  wave_count(s < n_seg && !c16 && !c64 && !cl, cnt + MT_SETTLED);
+  wave_count(c16, cnt + MT_L16);
+  wave_count(c64, cnt + MT_L64);
+  wave_count(cl, cnt + MT_LIST);
+  wave_count(s < n_seg && !both, cnt + MT_SINGLE);
+  wave_max(n, cnt + MT_LARGEST);
+}
+
+// pairs of at most W chains, 64 / W of them per wavefront: lane l of a group holds chain l of mate 1 and chain l of mate 2
+// (n1, n2 < W), takes the mate-2 chains one by one through shuffles inside its group and keeps its best combination
+template <int W>
+__global__ __launch_bounds__(256) void k_mt_lanes(const msgpu_map_chain *chains, const msgpu_ext_end *ends, uint32_t n_chains, const uint32_t *start,
+                                                  const uint32_t *n1s, const uint32_t *list, uint32_t n_list, uint32_t max_insert, MtSel *sel) {
+  constexpr uint32_t PER = 64 / W;
+  const uint32_t wv = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, gl = lane & (W - 1);
+  if (wv * PER >= n_list) return; // (whole wavefronts leave; the reductions below need all 64 lanes)
+  const uint32_t g = wv * PER + lane / W;
+  const bool     live = g < n_list;
+  const uint32_t s = live ? list[g] : 0, s0 = live ? start[s] : 0, n1 = live ? n1s[s] : 0, n2 = live ? start[s + 1] - s0 - n1 : 0;
+  MtChain a{0, 0, 0, 0, 0}, b{0, 0, 0, 0, 0};
+  if (gl < n1) a = mt_load(chains, ends, n_chains, s0 + gl);
+  if (gl < n2) b = mt_load(chains, ends, n_chains, s0 + n1 + gl);
+  MtAcc acc{0, 0, 0};
+  for (uint32_t j = 0; j < W - 1 && __ballot(j < n2); ++j) {
+    MtChain bj;
+    bj.target = static_cast<uint32_t>(__shfl(static_cast<int>(b.target), static_cast<int>(j), W));
+    bj.ts     = static_cast<uint32_t>(__shfl(static_cast<int>(b.ts), static_cast<int>(j), W));
+    bj.te     = static_cast<uint32_t>(__shfl(static_cast<int>(b.te), static_cast<int>(j), W));
+    bj.strand = static_cast<uint32_t>(__shfl(static_cast<int>(b.strand), static_cast<int>(j), W));
+    bj.score  = __shfl(b.score, static_cast<int>(j), W);
+    if (gl < n1 && j < n2) mt_take(acc, a, bj, gl, j, max_insert);
+  }
+  const MtSel r = mt_select<W>(acc, s0, n1);
+  if (live && gl == 0) sel[s] = r;
+}
+
+// pairs of more than 64 chains: a wavefront (a workgroup of one) per pair.  Lane l holds chain a0 + l of mate 1; the mate-2
+// chains pass through LDS MT_TILE at a time and every lane reads them all (one address per read: a broadcast)
+__global__ __launch_bounds__(64) void k_mt_list(const msgpu_map_chain *chains, const msgpu_ext_end *ends, uint32_t n_chains, const uint32_t *start,
+                                                const uint32_t *n1s, const uint32_t *list, uint32_t max_insert, MtSel *sel) {
+  __shared__ MtChain s_b[MT_TILE];
+  const uint32_t s = list[blockIdx.x], s0 = start[s], n1 = n1s[s], n2 = start[s + 1] - s0 - n1, lane = threadIdx.x;
+  MtAcc          acc{0, 0, 0};
+  for (uint32_t b0 = 0; b0 < n2; b0 += MT_TILE) {
+    const uint32_t m = min(MT_TILE, n2 - b0);
+    __syncthreads(); // (the tile before this one has been read)
+    for (uint32_t e = lane; e < m; e += 64) s_b[e] = mt_load(chains, ends, n_chains, s0 + n1 + b0 + e);
+    __syncthreads();
+    for (uint32_t a0 = 0; a0 < n1; a0 += 64) {
+      const bool    have = a0 + lane < n1;
+      const MtChain a = have ? mt_load(chains, ends, n_chains, s0 + a0 + lane) : MtChain{0, 0, 0, 0, 0};
+      if (have)
+        for (uint32_t j = 0; j < m; ++j) mt_take(acc, a, s_b[j], a0 + lane, b0 + j, max_insert);
+    }
+  }
+  const MtSel r = mt_select<64>(acc, s0, n1);
+  if (lane == 0) sel[s] = r;
+}
+
+// 13.3 in output order; `base`: the chains of the run in front of this table.  The chain that opens a pair counts it
+__global__ __launch_bounds__(256) void k_mt_rows(const uint32_t *head, const uint32_t *segid, const uint32_t *n1s, const uint32_t *start,
+                                                 const MtSel *sel, uint32_t n, uint32_t base, msgpu_map_mate *rows, kf_ull *cnt) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  bool           proper = false, ambig = false, discord = false;
+  uint32_t       tl = 0;
+  if (i < n) {
+    const uint32_t s = segid[i] + head[i] - 1; // (segid: the heads in front of chain i)
+    const MtSel    r = sel[s];
+    msgpu_map_mate row{MT_NONE, 0, 0, 0};
+    if (r.a == i) row = msgpu_map_mate{base + r.b, r.tl, 1, r.n_best};
+    else if (r.b == i) row = msgpu_map_mate{base + r.a, r.tl, 1, r.n_best};
+    rows[i] = row;
+    if (head[i]) {
+      const uint32_t n1 = n1s[s], n2 = start[s + 1] - start[s] - n1;
+      proper  = r.a != MT_NONE;
+      ambig   = proper && r.n_best > 1;
+      discord = !proper && n1 && n2;
+      tl      = proper ? r.tl : 0;
+    }
+  }
+  wave_count(proper, cnt + MT_PROPER);
+  wave_count(ambig, cnt + MT_AMBIG);
+  wave_count(discord, cnt + MT_DISCORD);
+  wave_add(tl, cnt + MT_TLSUM);
+  wave_max(tl, cnt + MT_TLMAX);
+  wave_max(proper ? 0x80000000u - tl : 0u, cnt + MT_TLMIN); // (the smallest tl as the greatest 2^31 - tl; 0: no proper pair)
+}
+
 } // namespace msgpu
 
 using namespace msgpu;
@@ -725,6 +955,8 @@ struct msgpu_mapctx : msgpu::StageCtx {
   uint32_t         extend = 0;      // rule 11's parameter (msgpu_map_set_extension)
   uint32_t         ranking = 0;     // rule 12's switch (msgpu_map_set_ranking)
   msgpu_map_rstats table_rstats{};  // of the last msgpu_map_rank_tables
+  uint32_t         mates = 0, max_insert = 1000; // rule 13's switch and parameter (msgpu_map_set_mates)
+  msgpu_map_mstats table_mstats{};  // of the last msgpu_map_mate_tables
   ~msgpu_mapctx();
   int open() {
     const int rc = msgpu_seq_create(device, &seq.p);
@@ -754,6 +986,9 @@ struct msgpu_map_result {
   // rule 12.  A row per chain when ranking was on
   msgpu_map_rstats            rstats{};
   std::vector<msgpu_map_rank> ranks;
+  // rule 13.  A row per chain when mates was on
+  msgpu_map_mstats            mstats{};
+  std::vector<msgpu_map_mate> mates;
 };
 
 namespace {
@@ -839,7 +1074,8 @@ void mp_runs(const msgpu_map_result &r, uint64_t i, std::vector<std::pair<uint32
 }
 
 void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_seqfile *Q, bool exact, std::string &out,
-               const std::vector<std::pair<uint32_t, uint64_t>> *runs = nullptr, const msgpu_map_rank *rk = nullptr, bool primary = false) {
+               const std::vector<std::pair<uint32_t, uint64_t>> *runs = nullptr, const msgpu_map_rank *rk = nullptr, bool primary = false,
+               const msgpu_map_mate *mt = nullptr) {
   char buf[224];
   out += msgpu_seq_name(Q, ch.query);
   int n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%c\t", static_cast<kf_ull>(msgpu_seq_length(Q, ch.query)), ch.q_start, ch.q_end,
@@ -854,6 +1090,11 @@ void mp_format(const msgpu_map_chain &ch, const msgpu_seqfile *T, const msgpu_se
     n = snprintf(buf, sizeof(buf), "\t%llu\t%u\t%u\t%u\t%u\t255\tcm:i:%u\ts1:i:%d", static_cast<kf_ull>(msgpu_seq_length(T, ch.target)),
                  ch.t_start, ch.t_end, ch.matches, ch.block, ch.n_anchors, ch.score);
   out.append(buf, n);
+  if (mt) { // rule 13.5
+    if (mt->cls) n = snprintf(buf, sizeof(buf), "\tpr:A:P\tmi:i:%u\ttl:i:%u\tnb:i:%u", mt->mate, mt->tlen, mt->n_best);
+    else n = snprintf(buf, sizeof(buf), "\tpr:A:U");
+    out.append(buf, n);
+  }
   if (exact) {
     n = snprintf(buf, sizeof(buf), "\tNM:i:%u", ch.nm);
     out.append(buf, n);
@@ -910,42 +1151,56 @@ constexpr uint64_t MP_BYTES_ANCHOR_RANK = 7 * 4 + 4 * 4 + 4 + 4 + 8 + sizeof(msg
 constexpr uint64_t MP_BYTES_FIXED_RANK = 24 * DevArena::ALIGN;
 static_assert(sizeof(msgpu_map_rank) == 16 && sizeof(RkPrim) == 12 && RK_COUNT * 8 <= DevArena::ALIGN, "rule 12's bytes per chain");
 
-uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, uint64_t n_anchors, uint64_t n_query_bases) {
+// rule 13 (mates on), per chain: head, segment number and segment start (three words), n1, the three class lists (three
+// words), the pair's selection (16 bytes, one per segment) and the row (16 bytes).  The scan is the one rule 12 runs, inside
+// MP_BYTES_ANCHOR_TMP.  Fixed: the counters with the lists' cursors and the rounding of the ten arrays, three of them with one
+// more word than items
+constexpr uint64_t MP_BYTES_ANCHOR_MATES = 3 * 4 + 4 + 3 * 4 + sizeof(MtSel) + sizeof(msgpu_map_mate);
+constexpr uint64_t MP_BYTES_FIXED_MATES = 12 * DevArena::ALIGN;
+static_assert(MP_BYTES_ANCHOR_MATES == MSGPU_MAP_MATES_ANCHOR_BYTES && MP_BYTES_FIXED_MATES == MSGPU_MAP_MATES_FIXED_BYTES &&
+              sizeof(msgpu_map_mate) == 16 && sizeof(MtSel) == 16 && (MT_COUNT + 3) * 8 <= DevArena::ALIGN, "rule 13's bytes per chain");
+
+uint64_t mp_batch_bytes(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, uint64_t n_anchors, uint64_t n_query_bases,
+                        uint32_t mates = 0) {
   const bool     exact = prm.exact != 0, cigar = exact && prm.cigar != 0;
   const uint64_t band1 = static_cast<uint64_t>(prm.band < 0 ? 0 : prm.band > 127 ? 127 : prm.band) + 1;
   const bool     ext = cigar && extend != 0;
   const uint64_t per = MP_BYTES_ANCHOR + MP_BYTES_ANCHOR_TMP + (exact ? MP_BYTES_ANCHOR_EXACT : 0) +
                        (cigar ? MP_BYTES_ANCHOR_CIGAR + 4 * band1 : 0) + (ext ? MP_BYTES_ANCHOR_EXT + 2 * 4 * band1 : 0) +
-                       (ranking ? MP_BYTES_ANCHOR_RANK : 0);
+                       (ranking ? MP_BYTES_ANCHOR_RANK : 0) + (mates ? MP_BYTES_ANCHOR_MATES : 0);
   // beyond every device, and no overflow: per < 2^8 (2^10 in cigar mode: band + 1 words of script per anchor beside the rest;
   // below 2^12 with rule 11's two more scripts, descriptors and end cells)
   if (n_anchors >= (1ull << (cigar ? 50 : 54)) || n_query_bases >= (1ull << 62)) return ~0ull;
   const uint64_t fixed = MP_BYTES_FIXED + (cigar ? MP_BYTES_FIXED_CIGAR + DevArena::aligned(4 * edit_script_slab_words(edit_script_slots(), static_cast<uint32_t>(band1 - 1))) : 0) +
-                         (ext ? MP_BYTES_FIXED_EXT : 0) + (ranking ? MP_BYTES_FIXED_RANK : 0);
+                         (ext ? MP_BYTES_FIXED_EXT : 0) + (ranking ? MP_BYTES_FIXED_RANK : 0) + (mates ? MP_BYTES_FIXED_MATES : 0);
   return fixed + per * n_anchors + (exact ? 2 * n_query_bases : 0);
 }
 
 // The greedy cut of rule 9 over the prefix sums of the records' anchors and bases (n + 1 entries each): a binary search per
-// batch for the last record that still fits.  Returns the first record that fits no batch on its own, or n.
-uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, const uint64_t *apre, const uint64_t *bpre, uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
+// batch for the last record that still fits.  Returns the first record that fits no batch on its own, or n.  With mates
+// (rule 13.7; n is even) the unit is the pair: `unit` = 2 records, and the first record of the pair that does not fit
+uint32_t mp_cut(const msgpu_map_params &prm, uint32_t extend, uint32_t ranking, uint32_t mates, const uint64_t *apre, const uint64_t *bpre,
+                uint32_t n, uint64_t budget, std::vector<msgpu_map_batch> &out) {
+  const uint32_t unit = mates ? 2 : 1;
   for (uint32_t first = 0; first < n;) {
     auto fits = [&](uint32_t end) {
       const uint64_t a = apre[end] - apre[first];
-      return a < (1ull << 31) && mp_batch_bytes(prm, extend, ranking, a, bpre[end] - bpre[first]) <= budget;
+      return a < (1ull << 31) && mp_batch_bytes(prm, extend, ranking, a, bpre[end] - bpre[first], mates) <= budget;
     };
-    if (!fits(first + 1)) return first;
-    uint32_t lo = first + 1, hi = n; // the last end that fits
+    if (!fits(first + unit)) return first;
+    uint32_t lo = 1, hi = (n - first) / unit; // the last end that fits, in units behind `first`
     while (lo < hi) {
       const uint32_t mid = lo + ((hi - lo + 1) >> 1);
-      if (fits(mid)) lo = mid;
+      if (fits(first + mid * unit)) lo = mid;
       else hi = mid - 1;
     }
+    lo = first + lo * unit;
     msgpu_map_batch b{};
     b.first_query   = first;
     b.n_queries     = lo - first;
     b.n_anchors     = apre[lo] - apre[first];
     b.n_query_bases = bpre[lo] - bpre[first];
-    b.bytes_bound   = mp_batch_bytes(prm, extend, ranking, b.n_anchors, b.n_query_bases);
+    b.bytes_bound   = mp_batch_bytes(prm, extend, ranking, b.n_anchors, b.n_query_bases, mates);
     out.push_back(b);
     first = lo;
   }
@@ -968,6 +1223,7 @@ struct MpRun { // what stays on the device for the whole run (rule 9), as a batc
   msgpu_map_result       *res;
   uint32_t                extend; // rule 11's parameter
   uint32_t                ranking; // rule 12's switch
+  uint32_t                mates, max_insert; // rule 13's switch and parameter
 };
 
 // ---- rule 12 on a chain table that lies on the device
@@ -1054,6 +1310,79 @@ void mp_rank_counts(const kf_ull *h, msgpu_map_rstats &S) { // behind the synchr
   S.n_segments_spilled += h[RK_SPILL];
 }
 
+// ---- rule 13 on a chain table that lies on the device
+
+// n chains in output order -> n rows; d_ends: rule 11's end cells of these chains (the left ones, then the right ones) or null;
+// `base` is added to every mate; `validate` and *bad as in mp_rank.  h_cnt: MT_COUNT counters on the host, valid after the
+// caller's next synchronisation; *n_seg: the pairs with a chain.
+int mp_mates(msgpu_mapctx *c, DevArena &B, StageClock &clock, const msgpu_map_chain *d_chains, const msgpu_ext_end *d_ends, uint32_t n,
+             uint32_t base, uint32_t max_insert, bool validate, msgpu_map_mate *d_rows, kf_ull *h_cnt, float *ms, uint64_t *n_seg_out,
+             uint64_t *bad) {
+  hipStream_t st = c->stream;
+  uint32_t   *d_head, *d_segid, *d_start, *d_n1, *d_l16, *d_l64, *d_ll;
+  MtSel      *d_sel;
+  kf_ull     *d_cnt; // the counters, then the three cursors of the class lists
+  for (uint32_t **p : {&d_head, &d_segid, &d_start}) STAGE_HIP(c, B.get(p, n + 1ull));
+  for (uint32_t **p : {&d_n1, &d_l16, &d_l64, &d_ll}) STAGE_HIP(c, B.get(p, n));
+  STAGE_HIP(c, B.get(&d_sel, n));
+  STAGE_HIP(c, B.get_zeroed(&d_cnt, MT_COUNT + 3, st));
+  STAGE_HIP(c, hipMemsetAsync(d_cnt + MT_BAD, 0xff, sizeof(kf_ull), st));
+  STAGE_HIP(c, hipMemsetAsync(d_head + n, 0, 4, st));
+  STAGE_HIP(c, clock.begin(ms));
+  hipLaunchKernelGGL(k_mt_heads, dim3(grid256(n)), dim3(256), 0, st, d_chains, n, validate ? 1 : 0, d_head, d_cnt + MT_BAD);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, stage_scan_total(B, st, d_head, d_segid, n, c->sc, MP_SC_TOTAL));
+  hipLaunchKernelGGL(k_stage_put<kf_ull>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL2, d_cnt + MT_BAD);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  int rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t n_seg = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]);
+  *bad = c->sc.h[MP_SC_TOTAL2];
+  if (validate && *bad != ~0ull) return MSGPU_E_ARG; // (the caller names the chain)
+  STAGE_HIP(c, clock.begin(ms));
+  hipLaunchKernelGGL(k_stage_seg_starts<uint32_t>, dim3(grid256(n + 1ull)), dim3(256), 0, st, d_head, d_segid, n, d_start);
+  hipLaunchKernelGGL(k_mt_classify, dim3(grid256(n_seg)), dim3(256), 0, st, d_chains, d_ends, n, d_start, n_seg, max_insert, d_n1, d_sel, d_l16,
+                     d_l64, d_ll, d_cnt + MT_COUNT, d_cnt);
+  STAGE_HIP(c, hipGetLastError());
+  for (int k = 0; k < 3; ++k) hipLaunchKernelGGL(k_stage_put<kf_ull>, dim3(1), dim3(64), 0, st, c->sc.d, MP_SC_TOTAL + k, d_cnt + MT_COUNT + k);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  rc = c->sc.read(c);
+  if (rc != MSGPU_OK) return rc;
+  const uint32_t n16 = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL]), n64 = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL2]),
+                 nl = static_cast<uint32_t>(c->sc.h[MP_SC_TOTAL3]);
+  STAGE_HIP(c, clock.begin(ms));
+  if (n16) hipLaunchKernelGGL(k_mt_lanes<16>, dim3(grid_of(n16, 16)), dim3(256), 0, st, d_chains, d_ends, n, d_start, d_n1, d_l16, n16, max_insert, d_sel);
+  if (n64) hipLaunchKernelGGL(k_mt_lanes<64>, dim3(grid_of(n64, 4)), dim3(256), 0, st, d_chains, d_ends, n, d_start, d_n1, d_l64, n64, max_insert, d_sel);
+  if (nl) hipLaunchKernelGGL(k_mt_list, dim3(nl), dim3(64), 0, st, d_chains, d_ends, n, d_start, d_n1, d_ll, max_insert, d_sel);
+  hipLaunchKernelGGL(k_mt_rows, dim3(grid256(n)), dim3(256), 0, st, d_head, d_segid, d_n1, d_start, d_sel, n, base, d_rows, d_cnt);
+  STAGE_HIP(c, hipGetLastError());
+  STAGE_HIP(c, clock.end());
+  STAGE_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, MT_COUNT * sizeof(kf_ull), hipMemcpyDeviceToHost, st));
+  *n_seg_out = n_seg;
+  return MSGPU_OK;
+}
+
+void mp_mate_counts(const kf_ull *h, uint64_t n_seg, msgpu_map_mstats &S) { // behind the synchronisation
+  S.n_pairs += n_seg; // (the pairs with a chain; a run adds its pairs without one at its end)
+  S.n_proper += h[MT_PROPER];
+  S.n_ambiguous += h[MT_AMBIG];
+  S.n_discordant += h[MT_DISCORD];
+  S.n_single += h[MT_SINGLE];
+  S.n_pairs_settled += h[MT_SETTLED];
+  S.n_pairs_lanes16 += h[MT_L16];
+  S.n_pairs_lanes64 += h[MT_L64];
+  S.n_pairs_list += h[MT_LIST];
+  S.largest_pair = std::max<uint64_t>(S.largest_pair, h[MT_LARGEST]);
+  S.tlen_sum += h[MT_TLSUM];
+  S.tlen_max = std::max<uint64_t>(S.tlen_max, h[MT_TLMAX]);
+  if (h[MT_TLMIN]) {
+    const uint64_t lo = 0x80000000ull - h[MT_TLMIN];
+    S.tlen_min = S.n_proper == h[MT_PROPER] ? lo : std::min(S.tlen_min, lo); // (the first batch with a proper pair sets it)
+  }
+}
+
 // ---- the batch's oriented query records, for exact mode's segment pairs and for rule 11's flanks
 
 struct MpOriented { // the batch's query records as they are and reverse-complemented, one record behind the other, one copy behind the other
@@ -1095,6 +1424,7 @@ struct MpExtBatch { // what the extension of a batch leaves for the host, valid 
   std::vector<msgpu_ext_end> ends;  // the left ends of the batch's chains, then the right ends
   std::vector<uint32_t>      words; // band + 1 words per end, e + 1 of them the script
   uint32_t                   broken = 0;
+  const msgpu_ext_end       *d_ends = nullptr; // the same cells in the batch arena: rule 13 reads the target ranges behind them
 };
 
 // the descriptors (k_mp_ends), the extension of the left ends and of the right ends (launch_extend_ends), and their way back
@@ -1135,6 +1465,7 @@ int mp_extend(const MpRun &R, DevArena &B, const msgpu_map_batch &bt, const msgp
   STAGE_HIP(c, hipMemcpyAsync(xb.words.data(), d_words, xb.words.size() * 4, hipMemcpyDeviceToHost, st));
   STAGE_HIP(c, hipMemcpyAsync(&xb.broken, d_broken, 4, hipMemcpyDeviceToHost, st));
   STAGE_HIP(c, R.clock.end());
+  xb.d_ends = d_ends;
   return MSGPU_OK;
 }
 
@@ -1235,6 +1566,10 @@ struct MpBatch { // what a batch carries from step to step
   MpOriented O;  // exact mode with a segment pair makes the copies, rule 11 otherwise
   MpExtBatch xb; // rule 11: what comes back with the chain table
   kf_ull     h_rk[RK_COUNT] = {}; // rule 12: the counters, likewise
+  // rule 13: the rows, the counters and the pairs with a chain
+  msgpu_map_mate *d_mrows = nullptr;
+  kf_ull          h_mt[MT_COUNT] = {};
+  uint64_t        n_mseg = 0;
 };
 
 // rule 4: expand, two stable sorts, the groups
@@ -1388,6 +1723,21 @@ int mp_rank_batch(const MpRun &R, DevArena &B, MpBatch &b) {
   return mp_rank(c, B, R.clock, b.d_chains, b.C_n, static_cast<uint32_t>(before), false, b.d_rows, b.h_rk, R.res->rstats, &bad);
 }
 
+// rule 13, the last device step of a batch: behind the extension, whose end cells move the target ranges it reads.  (An end
+// cell that the host would refuse ends the run with MSGPU_E_STATE in mp_extend_apply, so the rows of such a run reach nobody.)
+int mp_mates_batch(const MpRun &R, DevArena &B, MpBatch &b) {
+  msgpu_mapctx  *c = R.c;
+  const uint64_t before = R.res->chains.size();
+  if (before + b.C_n >= (1ull << 32)) {
+    snprintf(c->err, sizeof(c->err), "%llu chains; with mates on the limit of a run is 2^32 - 1 (rule 13)", static_cast<kf_ull>(before + b.C_n));
+    return MSGPU_E_ARG;
+  }
+  uint64_t bad;
+  STAGE_HIP(c, B.get(&b.d_mrows, b.C_n));
+  return mp_mates(c, B, R.clock, b.d_chains, R.extend ? b.xb.d_ends : nullptr, b.C_n, static_cast<uint32_t>(before), R.max_insert, false, b.d_mrows,
+                  b.h_mt, &R.res->mstats.mate_ms, &b.n_mseg, &bad);
+}
+
 // rule 7 in exact mode: the pairs of the batch (b.P; none: nothing more), their distances, and without cigar mode NM
 int mp_pairs(const MpRun &R, DevArena &B, msgpu_map_batch &bt, MpBatch &b) {
   msgpu_mapctx    *c = R.c;
@@ -1535,10 +1885,12 @@ int mp_tables_back(const MpRun &R, MpBatch &b) {
   try {
     res.chains.resize(have + b.C_n);
     if (R.ranking) res.ranks.resize(have + b.C_n);
+    if (R.mates) res.mates.resize(have + b.C_n);
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   STAGE_HIP(c, R.clock.begin(&res.stats.copy_ms));
   STAGE_HIP(c, hipMemcpyAsync(res.chains.data() + have, b.d_chains, b.C_n * sizeof(msgpu_map_chain), hipMemcpyDeviceToHost, st));
   if (R.ranking) STAGE_HIP(c, hipMemcpyAsync(res.ranks.data() + have, b.d_rows, b.C_n * sizeof(msgpu_map_rank), hipMemcpyDeviceToHost, st));
+  if (R.mates) STAGE_HIP(c, hipMemcpyAsync(res.mates.data() + have, b.d_mrows, b.C_n * sizeof(msgpu_map_mate), hipMemcpyDeviceToHost, st));
   STAGE_HIP(c, R.clock.end());
   return MSGPU_OK;
 }
@@ -1555,6 +1907,7 @@ int mp_batch_host(const MpRun &R, const MpBatch &b) {
     } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   }
   if (R.ranking && b.C_n) mp_rank_counts(b.h_rk, res.rstats);
+  if (R.mates && b.C_n) mp_mate_counts(b.h_mt, b.n_mseg, res.mstats);
   return R.extend && b.C_n ? mp_extend_apply(R, b.C_n, b.xb) : MSGPU_OK;
 }
 
@@ -1579,6 +1932,7 @@ int mp_batch(const MpRun &R, DevArena &B, msgpu_map_batch &bt) {
     if (exact && cigar && b.P && (rc = mp_scripts(R, B, b)) != MSGPU_OK) return rc;
     // rule 11: the ends of every chain, behind the scripts (the slab is theirs first)
     if (R.extend && (rc = mp_extend(R, B, bt, b.d_chains, b.C_n, b.O, b.d_slab, b.xb)) != MSGPU_OK) return rc;
+    if (R.mates && (rc = mp_mates_batch(R, B, b)) != MSGPU_OK) return rc;
     if ((rc = mp_tables_back(R, b)) != MSGPU_OK) return rc;
   }
   STAGE_HIP(c, hipStreamSynchronize(c->stream));
@@ -1706,6 +2060,10 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   S.n_bases[0]   = Tf.recs.n_bases;
   S.n_bases[1]   = Qf.recs.n_bases;
   S.load_ms      = ava ? 0.f : wall.ms();
+  if (c->mates && (Qf.recs.n & 1u)) {
+    snprintf(c->err, sizeof(c->err), "%u query records; with mates on the file is interleaved and holds an even number (rule 13)", Qf.recs.n);
+    return MSGPU_E_ARG;
+  }
 
   // ---- rule 2 on the queries, rule 3's cap
   const MpSketch &Ts = I.Ts;
@@ -1777,7 +2135,19 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   for (;;) {
     res->budget = budget;
     res->batches.clear();
-    const uint32_t bad = mp_cut(prm, c->extend, c->ranking, apre, bpre, NR, budget, res->batches);
+    const uint32_t bad = mp_cut(prm, c->extend, c->ranking, c->mates, apre, bpre, NR, budget, res->batches);
+    if (bad < NR && c->mates) { // rule 13.7: the unit is the pair
+      const uint64_t a = apre[bad + 2] - apre[bad], b = bpre[bad + 2] - bpre[bad];
+      if (a >= (1ull << 31)) {
+        snprintf(c->err, sizeof(c->err), "pair %u (query records %u and %u) has %llu anchors; the limit of a batch is 2^31 - 1 (rule 13: a pair is "
+                 "not split)", bad / 2, bad, bad + 1, static_cast<kf_ull>(a));
+        return MSGPU_E_ARG;
+      }
+      snprintf(c->err, sizeof(c->err), "pair %u (query records %u and %u) with %llu anchors and %llu bases needs %llu bytes on its own; the budget "
+               "of a batch is %llu bytes (rule 13: a pair is not split)", bad / 2, bad, bad + 1, static_cast<kf_ull>(a), static_cast<kf_ull>(b),
+               static_cast<kf_ull>(mp_batch_bytes(prm, c->extend, c->ranking, a, b, 1)), static_cast<kf_ull>(budget));
+      return MSGPU_E_NOMEM;
+    }
     if (bad < NR) {
       const uint64_t a = apre[bad + 1] - apre[bad], b = bpre[bad + 1] - bpre[bad];
       if (a >= (1ull << 31)) {
@@ -1806,13 +2176,19 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
   }
 
   // ---- rules 4 to 8, batch by batch
-  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res, c->extend, c->ranking};
+  const MpRun run{c, prm, Tf, Qf, Qs, X, d_aoff, d_pre + (NR + 1ull), first_min, bpre, qkind, d_nruns, d_hist, clock, res, c->extend, c->ranking, c->mates, c->max_insert};
   res->xstats.extend = c->extend;
   res->rstats.ranking = c->ranking;
   res->rstats.lds_primaries = MSGPU_MAP_RANK_LDS;
+  res->mstats.mates = c->mates;
+  res->mstats.max_insert = c->mates ? c->max_insert : 0;
   for (msgpu_map_batch &b : res->batches) {
     rc = mp_batch(run, B, b);
     if (rc != MSGPU_OK) return rc;
+  }
+  if (c->mates) { // the pairs without a chain never reached a table
+    res->mstats.n_unmapped = NR / 2 - res->mstats.n_pairs;
+    res->mstats.n_pairs    = NR / 2;
   }
   rc = c->sc.read(c);
   if (rc != MSGPU_OK) return rc;
@@ -1845,8 +2221,9 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
       for (uint64_t i = a; i < b; ++i) {
         const msgpu_map_rank *rk = res->ranks.empty() ? nullptr : &res->ranks[i];
         const bool            prim = rk && rk->parent == i;
+        const msgpu_map_mate *mt = c->mates ? &res->mates[i] : nullptr;
         if (!cigar) {
-          mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], nullptr, rk, prim);
+          mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], nullptr, rk, prim, mt);
           continue;
         }
         const StageTimer merging;
@@ -1860,7 +2237,7 @@ int mp_run(msgpu_mapctx *c, const msgpu_map_params &prm, const msgpu_map_index &
           }
         part_cnt[t].push_back(n_packed);
         part_ms[t] += merging.ms();
-        mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], &runs, rk, prim);
+        mp_format(res->chains[i], Tf.f, Qf.f, exact, part[t], &runs, rk, prim, mt);
       }
     });
     size_t total = 0;
@@ -1918,6 +2295,25 @@ int msgpu_map_set_ranking(msgpu_mapctx *c, int on) {
   return MSGPU_OK;
 }
 
+uint64_t msgpu_map_batch_bytes_mates(const msgpu_map_params *p, uint32_t extend, uint32_t ranking, uint32_t mates, uint64_t n_anchors,
+                                     uint64_t n_query_bases) {
+  msgpu_map_params prm{};
+  if (p) prm = *p;
+  return mp_batch_bytes(prm, extend, ranking, n_anchors, n_query_bases, mates);
+}
+
+int msgpu_map_set_mates(msgpu_mapctx *c, int on, uint32_t max_insert) {
+  if (!c) return MSGPU_E_ARG;
+  c->err[0] = 0;
+  if (max_insert < 1 || max_insert > 0x7fffffffu) {
+    snprintf(c->err, sizeof(c->err), "max_insert = %u; it is 1..2^31 - 1 (rule 13)", max_insert);
+    return MSGPU_E_ARG;
+  }
+  c->mates      = on != 0;
+  c->max_insert = max_insert;
+  return MSGPU_OK;
+}
+
 int msgpu_map_set_extension(msgpu_mapctx *c, uint32_t extend) {
   if (!c) return MSGPU_E_ARG;
   c->err[0] = 0;
@@ -1941,6 +2337,10 @@ static int mp_check_params(msgpu_mapctx *c, const msgpu_map_params &p) {
     snprintf(c->err, sizeof(c->err), "parameters: k = %d (4..32), w = %d (1..64), max_occ = %u (>= 1), max_gap = %d, bandwidth = %d "
              "(>= 0), max_pred = %d (64), band = %d (1..127), exact = %d, ava = %d (0 / 1), cigar = %d (0 / 1; 1 needs exact = 1)", p.k, p.w,
              p.max_occ, p.max_gap, p.bandwidth, p.max_pred, p.band, p.exact, p.ava, p.cigar);
+    return MSGPU_E_ARG;
+  }
+  if (c->mates && p.ava) {
+    snprintf(c->err, sizeof(c->err), "parameters: mates needs a query file of pairs; the run has ava = 1 (rule 13)");
     return MSGPU_E_ARG;
   }
   if (c->extend && !p.cigar) {
@@ -2184,6 +2584,73 @@ int msgpu_map_rank_tables(msgpu_mapctx *c, const msgpu_map_chain *chains, uint64
 int msgpu_map_rank_tables_stats(const msgpu_mapctx *c, msgpu_map_rstats *out) {
   if (!c || !out) return MSGPU_E_ARG;
   *out = c->table_rstats;
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_mates(const msgpu_map_result *r, const msgpu_map_mate **mates, uint64_t *n) {
+  if (!r || !mates || !n) return MSGPU_E_ARG;
+  *mates = r->mates.data();
+  *n     = r->mates.size();
+  return MSGPU_OK;
+}
+
+int msgpu_map_result_mate_stats(const msgpu_map_result *r, msgpu_map_mstats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->mstats;
+  return MSGPU_OK;
+}
+
+// rule 13 on a chain table of the host
+int msgpu_map_mate_tables(msgpu_mapctx *c, const msgpu_map_chain *chains, uint64_t n, uint32_t max_insert, msgpu_map_mate *rows_out) {
+  if (!c) return MSGPU_E_ARG;
+  c->err[0]       = 0;
+  c->table_mstats = msgpu_map_mstats{};
+  if (n && (!chains || !rows_out)) return MSGPU_E_ARG;
+  if (max_insert < 1 || max_insert > 0x7fffffffu) {
+    snprintf(c->err, sizeof(c->err), "max_insert = %u; it is 1..2^31 - 1 (rule 13)", max_insert);
+    return MSGPU_E_ARG;
+  }
+  if (n >= (1ull << 32)) {
+    snprintf(c->err, sizeof(c->err), "%llu chains; the limit of a table is 2^32 - 1 (rule 13)", static_cast<kf_ull>(n));
+    return MSGPU_E_ARG;
+  }
+  c->table_mstats.mates      = 1;
+  c->table_mstats.max_insert = max_insert;
+  if (!n) return MSGPU_OK;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  hipStream_t      st = c->stream;
+  DevArena         D;
+  StageClock       clock(st);
+  msgpu_map_chain *d_chains;
+  msgpu_map_mate  *d_rows;
+  kf_ull           h_cnt[MT_COUNT] = {};
+  uint64_t         bad = ~0ull, n_seg = 0;
+  STAGE_HIP(c, D.get(&d_chains, n));
+  STAGE_HIP(c, D.get(&d_rows, n));
+  STAGE_HIP(c, hipMemcpyAsync(d_chains, chains, n * sizeof(msgpu_map_chain), hipMemcpyHostToDevice, st));
+  int rc = mp_mates(c, D, clock, d_chains, nullptr, static_cast<uint32_t>(n), 0, max_insert, true, d_rows, h_cnt, &c->table_mstats.mate_ms, &n_seg,
+                    &bad);
+  if (rc == MSGPU_OK) {
+    const hipError_t e = hipMemcpyAsync(rows_out, d_rows, n * sizeof(msgpu_map_mate), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) rc = stage_fail(c, MSGPU_E_HIP, "rows", e);
+  }
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc == MSGPU_OK && e != hipSuccess) rc = stage_fail(c, MSGPU_E_HIP, "hipStreamSynchronize", e);
+  clock.collect();
+  if (rc == MSGPU_OK) rc = stage_verify(c, D);
+  if (rc == MSGPU_E_ARG && bad != ~0ull && bad < n) { // the first violated of the three, in 13's order
+    const msgpu_map_chain &ch = chains[bad];
+    c->table_mstats = msgpu_map_mstats{};
+    snprintf(c->err, sizeof(c->err), "chain %llu: %s", static_cast<kf_ull>(bad),
+             bad && ch.query < chains[bad - 1].query ? "order" : ch.strand > 1 ? "strand" : "range");
+  }
+  if (rc == MSGPU_OK) mp_mate_counts(h_cnt, n_seg, c->table_mstats);
+  return rc;
+}
+
+int msgpu_map_mate_tables_stats(const msgpu_mapctx *c, msgpu_map_mstats *out) {
+  if (!c || !out) return MSGPU_E_ARG;
+  *out = c->table_mstats;
   return MSGPU_OK;
 }
 

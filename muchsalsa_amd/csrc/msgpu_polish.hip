@@ -33,7 +33,8 @@ constexpr uint32_t PL_MAX_INS = 32;
 enum { PL_A = 0, PL_C, PL_G, PL_T, PL_DEL, PL_OTHER, PL_CLASSES };
 // rule 1: what can be wrong with a chain, in the order in which one chain's violations are looked at
 enum { PL_BAD_ORDER = 0, PL_BAD_STRAND, PL_BAD_QREC, PL_BAD_TREC, PL_BAD_TRANGE, PL_BAD_QRANGE, PL_BAD_RUN, PL_BAD_TCONS, PL_BAD_QCONS,
-       PL_BAD_OFF, PL_BAD_RANK /* (j), ranked form only: behind every other violation of its chain */ };
+       PL_BAD_OFF, PL_BAD_RANK /* (j), ranked form only: behind every other violation of its chain */,
+       PL_BAD_MATE /* (k), mates form only: likewise */ };
 // the counts of msgpu_pl_stats that the kernels add up, one 64-bit word each
 enum { PL_ST_VOTERS = 0, PL_ST_IGNORED, PL_ST_EQ, PL_ST_X, PL_ST_D, PL_ST_I, PL_ST_VERBATIM, PL_ST_UNCHANGED, PL_ST_SUBST, PL_ST_DELETED,
        PL_ST_USABLE, PL_ST_UNUSABLE, PL_ST_ENDS, PL_ST_APPLIED, PL_ST_INSERTED, PL_ST_MAXDEPTH, PL_ST_COUNT };
@@ -82,7 +83,8 @@ __global__ __launch_bounds__(256) void k_pl_runs(const uint64_t *off, uint32_t n
 }
 
 // rule 1 on the chain's fields and on what its runs consume
-__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, SeqRecs R, SeqRecs Q, const msgpu_map_rank *ranks, kf_ull *bad) {
+__global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, SeqRecs R, SeqRecs Q, const msgpu_map_rank *ranks, const msgpu_map_mate *mates,
+                                                        kf_ull *bad) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= X.n_chains) return;
   const msgpu_map_chain ch = X.chains[i];
@@ -102,6 +104,15 @@ __global__ __launch_bounds__(256) void k_pl_check_chain(PlTables X, SeqRecs R, S
     bool                 ok = r.parent < X.n_chains && r.mapq <= 60;
     if (ok) ok = X.chains[r.parent].query == ch.query && ranks[r.parent].parent == r.parent;
     if (!ok) found(PL_BAD_RANK);
+  }
+  if (mates) { // (k): cls is 0 or 1; a selected chain's mate is a chain of the table whose row names this one, of the pair's other record
+    const msgpu_map_mate m = mates[i];
+    bool                 ok = m.cls <= 1;
+    if (ok && m.cls == 1) {
+      ok = m.mate < X.n_chains && m.n_best >= 1;
+      if (ok) ok = mates[m.mate].cls == 1 && mates[m.mate].mate == i && X.chains[m.mate].query == (ch.query ^ 1u);
+    }
+    if (!ok) found(PL_BAD_MATE);
   }
   if (what != ~0u) pl_bad(bad, i, what);
 }
@@ -128,7 +139,13 @@ __global__ __launch_bounds__(256) void k_pl_voter_ranked(const msgpu_map_chain *
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) vflag[i] = pl_eligible(chains[i], min_identity) && ranks[i].parent == i && ranks[i].mapq >= min_mapq;
 }
-// is chain i a voter: by its flag in ranked form, else as its query record's one voter
+// rule 2 in mates form, likewise: a chain votes iff it is eligible, selected and its pair is placed best once
+__global__ __launch_bounds__(256) void k_pl_voter_mates(const msgpu_map_chain *chains, const msgpu_map_mate *mates, uint32_t n, uint32_t min_identity,
+                                                        uint32_t *vflag) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) vflag[i] = pl_eligible(chains[i], min_identity) && mates[i].cls == 1 && mates[i].n_best == 1;
+}
+// is chain i a voter: by its flag in ranked and in mates form, else as its query record's one voter
 __device__ inline bool pl_votes(const msgpu_map_chain *chains, const uint32_t *vidx, const uint32_t *vflag, uint32_t i) {
   return vflag ? vflag[i] != 0 : vidx[chains[i].query] == i;
 }
@@ -345,7 +362,8 @@ const char *const PL_WHAT[] = {"query order (the chains are not ordered by query
                                "target consumption (the runs do not consume t_end - t_start target bases)",
                                "query consumption (the runs do not consume q_end - q_start query bases)",
                                "offsets (the run offsets decrease or exceed the run table)",
-                               "rank (the parent is out of range, of another query record or no primary, or mapq exceeds 60)"};
+                               "rank (the parent is out of range, of another query record or no primary, or mapq exceeds 60)",
+                               "mates (cls exceeds 1, or the mate is out of range, names another chain or is no mate of this read, or n_best is 0)"};
 
 // rule 8: `need` more bytes beside what the device holds already
 int pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const char *a_name, uint64_t b, const char *b_name) {
@@ -358,7 +376,8 @@ int pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const c
 }
 
 int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
-           uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq, msgpu_pl_result *res) {
+           uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq,
+           const msgpu_map_mate *mates, msgpu_pl_result *res) {
   msgpu_pl_stats &S = res->stats;
   hipStream_t     st = c->stream;
   DevArena        D;
@@ -399,7 +418,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   // its scan; per chain the entry, the offset, the span and its scan; per read the voter's key and index
   const uint64_t fixed_bytes = NB * (PL_CLASSES * 4ull + 8 + 1 + 4 + 8) + n_runs * (4ull + 4 + 4 + 8 + 8 + 4 + 4 + 4) +
                                n_chains * (sizeof(msgpu_map_chain) + 8ull + 4 + 8) + Q.n * 12ull + R.n * 48ull + (8ull << 20) +
-                               (ranks ? n_chains * (sizeof(msgpu_map_rank) + 4ull) : 0); // (ranked form: the rows and the voters' flags)
+                               (ranks || mates ? n_chains * (sizeof(msgpu_map_rank) + 4ull) : 0); // (ranked and mates form: the rows and the voters' flags)
   if ((rc = pl_room(c, fixed_bytes, "the pile-up", NB, "draft bases", n_runs, "runs")) != MSGPU_OK) return rc;
 
   kf_ull *d_st, *d_bad = reinterpret_cast<kf_ull *>(c->sc.d + PL_SC_BAD);
@@ -430,6 +449,12 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
     STAGE_HIP(c, D.get(&d_vflag, n_chains));
     if (n_chains) STAGE_HIP(c, hipMemcpyAsync(d_ranks, ranks, n_chains * sizeof(msgpu_map_rank), hipMemcpyHostToDevice, st));
   }
+  msgpu_map_mate *d_mates = nullptr;
+  if (mates) {
+    STAGE_HIP(c, D.get(&d_mates, n_chains));
+    STAGE_HIP(c, D.get(&d_vflag, n_chains));
+    if (n_chains) STAGE_HIP(c, hipMemcpyAsync(d_mates, mates, n_chains * sizeof(msgpu_map_mate), hipMemcpyHostToDevice, st));
+  }
   auto bad_chain = [&]() -> int { // the smallest bad chain, through the scalar block
     const int r2 = c->sc.read(c);
     if (r2 != MSGPU_OK) return r2;
@@ -451,7 +476,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   STAGE_HIP(c, clock.end());
   const PlTables X{d_chains, d_off, d_ops, d_T, d_Q, n_chains, n_runs};
   STAGE_HIP(c, clock.begin(&S.validate_ms));
-  if (n_chains) hipLaunchKernelGGL(k_pl_check_chain, dim3(grid256(n_chains)), dim3(256), 0, st, X, R, Q, d_ranks, d_bad);
+  if (n_chains) hipLaunchKernelGGL(k_pl_check_chain, dim3(grid256(n_chains)), dim3(256), 0, st, X, R, Q, d_ranks, d_mates, d_bad);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, clock.end());
   if ((rc = bad_chain()) != MSGPU_OK) return rc; // no kernel below runs on a table that breaks rule 1
@@ -472,7 +497,9 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   STAGE_HIP(c, clock.begin(&S.voters_ms));
   if (n_chains) {
     const uint32_t mi = static_cast<uint32_t>(prm.min_identity);
-    if (ranks) {
+    if (mates) {
+      hipLaunchKernelGGL(k_pl_voter_mates, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, d_mates, n_chains, mi, d_vflag);
+    } else if (ranks) {
       hipLaunchKernelGGL(k_pl_voter_ranked, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, d_ranks, n_chains, mi, min_mapq, d_vflag);
     } else {
       hipLaunchKernelGGL(k_pl_voter_key, dim3(grid256(n_chains)), dim3(256), 0, st, d_chains, n_chains, mi, d_vkey);
@@ -637,8 +664,8 @@ void msgpu_pl_destroy(msgpu_plctx *c) { stage_destroy(c); }
 const char *msgpu_pl_last_error(const msgpu_plctx *c) { return c ? c->err : "null context"; }
 
 static int pl_entry(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
-                    uint64_t n_chains, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq, uint32_t flags,
-                    msgpu_pl_result **out) {
+                    uint64_t n_chains, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq, const msgpu_map_mate *mates,
+                    uint32_t flags, msgpu_pl_result **out) {
   if (!c || !out) return MSGPU_E_ARG;
   *out      = nullptr;
   c->err[0] = 0;
@@ -655,7 +682,7 @@ static int pl_entry(msgpu_plctx *c, const msgpu_pl_params *params, const char *d
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   const StageTimer wall;
   const uint64_t   lost0 = c->sc.lost;
-  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, ranks, min_mapq, res.get());
+  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, ranks, min_mapq, mates, res.get());
   if (rc != MSGPU_OK) return rc;
   res->stats.n_lost_publications = c->sc.lost - lost0;
   res->stats.wall_ms             = wall.ms();
@@ -665,7 +692,7 @@ static int pl_entry(msgpu_plctx *c, const msgpu_pl_params *params, const char *d
 
 int msgpu_pl_run(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
                  uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags, msgpu_pl_result **out) {
-  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, nullptr, 0, flags, out);
+  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, nullptr, 0, nullptr, flags, out);
 }
 
 int msgpu_pl_run_ranked(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
@@ -677,7 +704,19 @@ int msgpu_pl_run_ranked(msgpu_plctx *c, const msgpu_pl_params *params, const cha
     snprintf(c->err, sizeof(c->err), "no rank rows for %llu chains", static_cast<unsigned long long>(n_chains));
     return MSGPU_E_ARG;
   }
-  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, ranks ? ranks : &none, min_mapq, flags, out);
+  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, ranks ? ranks : &none, min_mapq, nullptr, flags, out);
+}
+
+int msgpu_pl_run_mates(msgpu_plctx *c, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
+                       const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off, const msgpu_map_mate *mates,
+                       uint32_t flags, msgpu_pl_result **out) {
+  static const msgpu_map_mate none{};
+  if (c && out && !mates && n_chains) {
+    *out = nullptr;
+    snprintf(c->err, sizeof(c->err), "no mate rows for %llu chains", static_cast<unsigned long long>(n_chains));
+    return MSGPU_E_ARG;
+  }
+  return pl_entry(c, params, draft_path, reads_path, chains, n_chains, ops, off, nullptr, 0, mates ? mates : &none, flags, out);
 }
 
 int msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out) {

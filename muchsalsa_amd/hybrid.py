@@ -40,10 +40,15 @@ import time
 
 from . import _lib
 
-__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "gfa_name", "output_names", "link_input", "run", "main"]
+__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "POLISHED_MATES_NAME", "INTERLEAVED_NAME", "MATES_MAPPING", "gfa_name", "output_names", "link_input", "run", "main"]
 
 MIN_LENGTH = 500  # pipeline.sh:29
 POLISHED_NAME = "04.assembly.polished.fa"  # written only by run(..., polish=N): not one of output_names
+POLISHED_MATES_NAME = "05.assembly.polished.mates.fa"  # written only by run(..., polish_mates=N): not one of output_names
+INTERLEAVED_NAME = os.path.join("tmp", "illumina.interleaved.fq")  # the two Illumina inputs as one file of pairs, likewise
+# The mapper's parameters for the short reads of the polish_mates stage.  The mapper's default min_score of 100 is the score of
+# a perfect 100-base read and would drop nearly every mate; 40 is a choice, unchecked on real reads.
+MATES_MAPPING = dict(min_score=40)
 
 
 class HybridError(RuntimeError):
@@ -90,7 +95,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False):
+        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -104,7 +109,13 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     mappings run with the mapper's rule 12 on, and a read votes with its primaries of mapping quality N or more); the four
     mappings of the pipeline keep ranking off: their consumers read columns 1 to 11 and want every chain, as with ``-P``.
     ``gfa`` = True: the unitig assembly also writes its graph (muchsalsa_amd.unitigs' rule 10) to ``ABYSS/<name>-unitigs.gfa``
-    (gfa_name), named by ``files["gfa"]``; every other file is the same."""
+    (gfa_name), named by ``files["gfa"]``; every other file is the same.  ``polish_mates`` (None or 0: off) = N >= 1 adds a last
+    stage ``"polish_mates"``, the accurate short reads' pass over the assembly: mapper.interleave writes the two Illumina inputs
+    as one file of pairs (INTERLEAVED_NAME), then N rounds of muchsalsa_amd.polish with mates on (the mapper's rule 13, the
+    polisher's rule 2 in mates form) polish the long-read-polished file if ``polish`` was given, else the assembly, into
+    POLISHED_MATES_NAME, named by ``files["polished_mates"]``; every other file is the same.  Its mappings run with MATES_MAPPING
+    (a min_score fit for 100-base reads: a choice, unchecked on real reads) and ``max_insert`` (None: the mapper's default);
+    neither the extension nor the mapping quality threshold reaches this stage."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -161,6 +172,15 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
         result["files"]["polished"] = os.path.join(out, POLISHED_NAME)
         stage("polish", polisher.run, files["assembly"], files["scrubbed"], result["files"]["polished"], rounds=int(polish),
               device=device, extend=int(extend or 0), min_mapq=min_mapq)
+    if polish_mates:
+        from . import polish as polisher
+        pairs = os.path.join(out, INTERLEAVED_NAME)
+        result["files"]["interleaved"] = pairs
+        result["files"]["polished_mates"] = os.path.join(out, POLISHED_MATES_NAME)
+        stage("interleave", lambda: {"pairs": mapper.interleave(illumina_1, illumina_2, pairs)})
+        more = {} if max_insert is None else {"max_insert": int(max_insert)}
+        stage("polish_mates", polisher.run, result["files"]["polished"] if polish else files["assembly"], pairs,
+              result["files"]["polished_mates"], rounds=int(polish_mates), device=device, mates=True, **more, **MATES_MAPPING)
     result["seconds"] = round(time.perf_counter() - t_all, 4)
     return result
 

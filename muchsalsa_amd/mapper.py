@@ -3,7 +3,7 @@ write -- a PAF of every record of a query file against every record of a target 
 
     python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--cigar] [--ava]
             [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
-            [--extend N] [--rank]
+            [--extend N] [--rank] [--mates] [--max-insert N]
 
 prints one JSON line of counts and seconds.  ``--budget-mb`` (N > 0) bounds the device memory of a batch of query records
 (rule 9; without it: the free device memory).  With ``--ava`` the two paths name the same file (the reads against
@@ -12,12 +12,14 @@ count of the PAF muchsalsa itself parses (the pipeline's ``-c --eqx`` call); ``-
 every segment base by base (rule 10): column 10 is then the number of ``=`` columns, column 11 the number of alignment columns,
 and the line ends in a ``cg:Z:`` string of ``=``, ``X``, ``I`` and ``D`` runs; ``--extend N`` (1..65535, which implies
 ``--cigar``) extends every chain beyond its outermost seeds by up to N bases at either end (rule 11); ``--rank`` marks every chain
-as primary or secondary and writes a mapping quality into column 12 (rule 12).  minimap2 is not needed, and it is not part of
+as primary or secondary and writes a mapping quality into column 12 (rule 12); ``--mates`` reads the query file as interleaved
+pairs and marks the proper pair of every pair (rule 13), ``--max-insert N`` (1..2^31 - 1, default 1000, which implies
+``--mates``) is its longest template.  minimap2 is not needed, and it is not part of
 the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
 tests' restatement in plain Python (tests/map_oracle.py), not against minimap2.  The rules (include/msgpu.h,
 "unitig-to-read mapping"); parameters k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth
 (2000), max_pred (fixed at 64), min_score (100), min_count (3), exact (0 / 1), band (1..127, 64), ava (0 / 1); cigar (0 / 1),
-extend (0..65535) and rank (False / True) are keywords of ``run`` beside them:
+extend (0..65535), rank (False / True), mates (False / True) and max_insert are keywords of ``run`` beside them:
 
  1. windows: the alphabet, case folding, 2-bit code, canonical key (min(fw, rc) as 2k-bit numbers) and the break at any
     other byte are those of the k-mer filter's rolling window (KfRoll).  A stretch is a maximal run of k-mer start
@@ -139,6 +141,32 @@ extend (0..65535) and rank (False / True) are keywords of ``run`` beside them:
     2^32 chains, else MSGPU_E_ARG.  msgpu_map_batch_bytes_rank bounds a batch (104 bytes per anchor and a fixed 24 * 256 bytes
     more than msgpu_map_batch_bytes_ext).  The mask level 1/2, the ratio 0.9 and the mapq formula are choices modelled on
     minimap2's, unchecked on real reads.
+13. mates, on request (``mates``; msgpu_map_set_mates(ctx, on, max_insert); off by default; it needs no other mode: seed, exact,
+    cigar, extend and rank all combine with it; with ava it is MSGPU_E_ARG).  The query file is interleaved: records 2p and
+    2p + 1 are mate 1 and mate 2 of pair p; the names are not compared; an odd number of query records is MSGPU_E_ARG naming
+    the count.  max_insert is 1..2^31 - 1, default 1000.  The rule reads the chain table as the run leaves it, behind rule
+    11's extension.  (1) Concordant: chain a of record 2p and chain b of record 2p + 1 are concordant iff they have the same
+    target record, their strands differ, and with f the chain of strand 0 and r the chain of strand 1:
+    f.t_start <= r.t_start, f.t_end <= r.t_end (the forward mate lies to the left and neither passes the other) and
+    tl = r.t_end - f.t_start <= max_insert.  Either mate may be the forward one.  (2) Selection: among the concordant
+    combinations of a pair one is selected: the greatest score(a) + score(b) (a 64-bit sum), then the smaller tl, then the
+    smaller index of a, then the smaller index of b.  n_best is the number of concordant combinations whose sum equals the
+    greatest sum, whatever their tl, clamped to 2^32 - 1.  (3) Rows, one per chain in output order, {mate, tlen, cls,
+    n_best}: the two selected chains have cls = 1, mate = the other's index in the whole run's chain table, tlen = tl and
+    the pair's n_best; every other chain has {0xffffffff, 0, 0, 0}.  (4) Counts (msgpu_map_mstats): the pairs of the input,
+    proper pairs, ambiguous pairs (proper with n_best > 1), discordant pairs (chains on both mates, none concordant),
+    single pairs (chains on one mate only), unmapped pairs, the pairs per kernel class, the largest pair in chains, the
+    sum, minimum and maximum of tlen over the proper pairs (integers: no order reaches them) and the step's device time.
+    (5) With mates on every line carries pr:A:P or pr:A:U behind s1:i (behind s2:i with ranking on); a P line also carries
+    mi:i:<the mate's line, 0-based>, tl:i:<tlen>, nb:i:<n_best>; NM and cg follow as before; line order and every other
+    column are untouched.  (6) With mates off every byte of every output is as before.  (7) Rule 9 with mates on: the unit
+    of the greedy cut is the pair: a batch starts at an even record and holds whole pairs, a(p) = a(2p) + a(2p + 1) and
+    likewise the bases; a pair that exceeds the budget on its own is MSGPU_E_NOMEM naming the pair; with mates on a run has
+    fewer than 2^32 chains, else MSGPU_E_ARG.  msgpu_map_batch_bytes_mates bounds a batch (it equals
+    msgpu_map_batch_bytes_rank for mates = 0): per anchor it adds 60 bytes (three words of segment heads, numbers and
+    starts, the count of mate 1's chains, three words of class lists, 16 bytes of the pair's selection, the row) and a fixed
+    12 * 256 bytes.  (8) Orientation FR only, the selection order and n_best are choices modelled on short-read mappers,
+    unchecked on real reads.
 
 Known differences from minimap2, none of which could be checked against the program (it is not installed where this project
 is built):
@@ -156,7 +184,10 @@ is built):
   link, not minimap2's count of ``=`` columns.  With ``--cigar`` the columns are counted on a unit-cost alignment of every
   segment between two seeds (rule 10), not on minimap2's affine-gap alignment, and a segment beyond the band is written
   as a deletion and an insertion;
-* end extension: none without ``--extend``; with it, rule 11 (unit costs, P = 8, no end bonus).
+* end extension: none without ``--extend``; with it, rule 11 (unit costs, P = 8, no end bonus);
+* pairs: none without ``--mates``; with it, rule 13: orientation FR only, one insert bound and no insert-size model, no mate
+  rescue, the selection order (score sum, then the shorter template, then the chains' indices) and n_best are choices
+  modelled on short-read mappers, unchecked on real reads.
 
 ``Index(targets, k=, w=)`` is a context manager that keeps the targets' store, sketch and index on the device;
 ``run(None, queries, out, index=ix, ...)`` then maps onto it, any number of times, with any parameters but k and w (the
@@ -175,7 +206,7 @@ import numpy as np
 from . import _lib
 from ._stage import StageError, stage_context, text_view
 
-__all__ = ["MapError", "Index", "run", "rank_tables", "main", "DEFAULTS"]
+__all__ = ["MapError", "Index", "run", "rank_tables", "mate_tables", "interleave", "main", "DEFAULTS"]
 
 DEFAULTS = dict(k=15, w=5, max_occ=200, max_gap=10000, bandwidth=2000, min_score=100, min_count=3, exact=0, band=64, ava=0)
 
@@ -254,7 +285,70 @@ def rank_tables(chains, device=0, context=None, stats=None):
     return [tuple(int(x) for x in r) for r in rows]
 
 
-def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, extend=0, rank=False, **params):
+def _mate_stats(mst):
+    return dict({name: int(getattr(mst, name)) for name, t in _lib.MapMateStats._fields_ if t is not C.c_float},
+                seconds={"mates": mst.mate_ms / 1e3})
+
+
+def mate_tables(chains, max_insert=_lib.MAP_MAX_INSERT_DEFAULT, device=0, context=None, stats=None):
+    """Rule 13 on a chain table (msgpu_map_mate_tables): ``chains`` holds per chain the tuple ``tables["chains"]`` of ``run`` has
+    (only query, target, strand, score, t_start and t_end are read), in output order.  Returns per chain the tuple (mate, tlen,
+    cls, n_best), mate an index into ``chains``.  ``context``: an entered ``stage_context("map", ...)`` or an Index's ``stage``;
+    ``stats`` (a dict) receives the counts of msgpu_map_mstats (n_pairs: the pairs with a chain)."""
+    if not 0 <= int(max_insert) < (1 << 32):
+        raise MapError(_lib.E_ARG, "max_insert = %d" % int(max_insert))
+    table = np.zeros(len(chains), dtype=_lib.MAP_CHAIN_DTYPE)
+    for i, ch in enumerate(chains):
+        table[i] = tuple(int(x) for x in ch)
+    rows = np.zeros(len(chains), dtype=_lib.MAP_MATE_DTYPE)
+    L = _lib.lib()
+    with (stage_context("map", device, MapError) if context is None else contextlib.nullcontext(context)) as stage:
+        stage.check(L.msgpu_map_mate_tables(stage.ctx, table.ctypes.data, len(chains), int(max_insert), rows.ctypes.data))
+        if stats is not None:
+            mst = _lib.MapMateStats()
+            L.msgpu_map_mate_tables_stats(stage.ctx, C.byref(mst))
+            stats.update(_mate_stats(mst))
+    return [tuple(int(x) for x in r) for r in rows]
+
+
+def interleave(in_1, in_2, out):
+    """Two FASTQ files of four-line records, mate 1's and mate 2's in the same order, streamed into one interleaved file (record
+    2p from ``in_1``, 2p + 1 from ``in_2``): rule 13's query file.  Host only.  Returns the pairs; ValueError on unequal record
+    counts or on a record that is not ``@name``, bases, ``+``, as many qualities (``out`` is then removed).  The sequence loader
+    keeps the reference's reading of FASTQ, in which a quality line that starts with ``@`` is taken for a description line; that
+    would drop records and shift every pair behind it, so such a quality line is written with ``A`` (the next quality) as its
+    first byte.  The mapper reads no qualities; every other byte is copied."""
+    def record(h, path, number):
+        lines = [h.readline() for _ in range(4)]
+        if not lines[0]:
+            return None
+        if (not lines[3] or not lines[0].startswith(b"@") or not lines[2].startswith(b"+") or
+                len(lines[1].rstrip(b"\r\n")) != len(lines[3].rstrip(b"\r\n")) or not lines[1].rstrip(b"\r\n")):
+            raise ValueError("%s: record %d is not a four-line FASTQ record" % (path, number))
+        if lines[3].startswith(b"@"):
+            lines[3] = b"A" + lines[3][1:]
+        return b"".join(line if line.endswith(b"\n") else line + b"\n" for line in lines)
+
+    pairs = 0
+    try:
+        with open(in_1, "rb") as h1, open(in_2, "rb") as h2, open(out, "wb") as o:
+            while True:
+                r1, r2 = record(h1, in_1, pairs), record(h2, in_2, pairs)
+                if r1 is None and r2 is None:
+                    return pairs
+                if r1 is None or r2 is None:
+                    raise ValueError("%s has %s records than %s (%d pairs read)" % (in_1, "fewer" if r1 is None else "more", in_2, pairs))
+                o.write(r1)
+                o.write(r2)
+                pairs += 1
+    except ValueError:
+        with contextlib.suppress(OSError):
+            os.remove(out)
+        raise
+
+
+def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, extend=0, rank=False, mates=False,
+        max_insert=_lib.MAP_MAX_INSERT_DEFAULT, **params):
     """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
     per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
     ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
@@ -270,7 +364,10 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     for this run: an ``index`` serves runs with any extend, one after the other.  ``rank`` = True (rule 12) marks primaries and
     secondaries and writes the mapping quality; the result then carries ``ranks`` (per line the tuple (parent, sub, n_secondary,
     mapq)) and ``rank`` (the counts of msgpu_map_rstats, the time under ``seconds``); ``tables`` receives ``ranks`` too.  Like
-    extend it is set on the context for this run."""
+    extend it is set on the context for this run.  ``mates`` = True (rule 13) reads ``queries`` as interleaved pairs with
+    ``max_insert`` as the longest template; the result then carries ``mates`` (per line the tuple (mate, tlen, cls, n_best)) and
+    ``mate`` (the counts of msgpu_map_mstats, the time under ``seconds``); ``tables`` receives ``mates`` too.  Set on the context
+    for this run, like rank."""
     if index is not None:
         params = dict({"k": index.k, "w": index.w}, **params)
     unknown = set(params) - set(DEFAULTS)
@@ -290,6 +387,9 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             raise MapError(_lib.E_ARG, "extend = %d" % int(extend))
         stage.check(L.msgpu_map_set_extension(stage.ctx, int(extend)))
         stage.check(L.msgpu_map_set_ranking(stage.ctx, 1 if rank else 0))
+        if not 0 <= int(max_insert) < (1 << 32):
+            raise MapError(_lib.E_ARG, "max_insert = %d" % int(max_insert))
+        stage.check(L.msgpu_map_set_mates(stage.ctx, 1 if mates else 0, int(max_insert)))
         with (stage.run(C.byref(prm), os.fsencode(targets), qpath, 0, budget) if index is None else
               stage.run(C.byref(prm), index.handle, qpath, 0, budget, fn="run_index")) as res:
             st = _lib.MapStats()
@@ -312,9 +412,19 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
                 rows = (np.frombuffer((C.c_char * (16 * m.value)).from_address(C.addressof(rp.contents)), dtype=_lib.MAP_RANK_DTYPE)
                         if m.value else [])
                 ranks = [tuple(int(x) for x in r) for r in rows]
+            mst, mate_rows = _lib.MapMateStats(), None
+            L.msgpu_map_result_mate_stats(res, C.byref(mst))
+            if mst.mates:
+                mp_, m = C.POINTER(_lib.MapMate)(), C.c_uint64()
+                L.msgpu_map_result_mates(res, C.byref(mp_), C.byref(m))
+                rows = (np.frombuffer((C.c_char * (16 * m.value)).from_address(C.addressof(mp_.contents)), dtype=_lib.MAP_MATE_DTYPE)
+                        if m.value else [])
+                mate_rows = [tuple(int(x) for x in r) for r in rows]
             if tables is not None:
                 if ranks is not None:
                     tables["ranks"] = ranks
+                if mate_rows is not None:
+                    tables["mates"] = mate_rows
                 cp = C.POINTER(_lib.MapChain)()
                 m = C.c_uint64()
                 L.msgpu_map_result_chains(res, C.byref(cp), C.byref(m))
@@ -345,6 +455,9 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     if ranks is not None:
         ext["ranks"] = ranks
         ext["rank"] = _rank_stats(rst)
+    if mate_rows is not None:
+        ext["mates"] = mate_rows
+        ext["mate"] = _mate_stats(mst)
     return {**ext, "params": {name: int(getattr(st.params, name)) for name in DEFAULTS}, "records": [int(x) for x in st.n_records],
             "bases": [int(x) for x in st.n_bases], "minimizers": [int(x) for x in st.n_minimizers], "keys": int(st.n_keys),
             "keys_dropped": int(st.n_keys_dropped), "entries_dropped": int(st.n_entries_dropped), "anchors": int(st.n_anchors),
@@ -385,6 +498,18 @@ def main(argv):
     rank = "--rank" in args
     if rank:
         args.remove("--rank")
+    mates, max_insert = "--mates" in args, _lib.MAP_MAX_INSERT_DEFAULT
+    if mates:
+        args.remove("--mates")
+    if "--max-insert" in args:  # (implies --mates)
+        i = args.index("--max-insert")
+        try:
+            max_insert = int(args[i + 1])
+            ok = ok and 1 <= max_insert < (1 << 31)
+        except (IndexError, ValueError):
+            ok = False
+        del args[i:i + 2]
+        mates = True
     for name, key in _OPTS.items():
         if name in args:
             i = args.index(name)
@@ -404,13 +529,15 @@ def main(argv):
     q = dict(DEFAULTS, **p)
     ok = ok and 4 <= q["k"] <= 32 and 1 <= q["w"] <= 64 and q["max_occ"] >= 1 and 1 <= q["band"] <= 127
     ok = ok and q["max_gap"] >= 0 and q["bandwidth"] >= 0 and not any(a.startswith("-") for a in args)
-    ok = ok and len(args) == 3 and (not q["ava"] or args[0] == args[1])
+    ok = ok and len(args) == 3 and (not q["ava"] or args[0] == args[1]) and not (mates and q["ava"])
     if not ok:
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, extend=extend, rank=rank, **p)
+    more = dict(mates=True, max_insert=max_insert) if mates else {}  # (without the option the call is the one it always was)
+    out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, extend=extend, rank=rank, **p, **more)
     out.pop("ranks", None)  # (the table is the PAF's; the line keeps the counts)
+    out.pop("mates", None)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0

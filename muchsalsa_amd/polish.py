@@ -2,12 +2,14 @@
 
     python -m muchsalsa_amd.polish <draft.fa> <reads.fa|fq> <out.fa> [--rounds N] [--min-depth N] [--min-identity N] [--paf F]
             [-k N] [-w N] [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
-            [--extend N] [--min-mapq N]
+            [--extend N] [--min-mapq N] [--mates] [--max-insert N]
 
 prints one JSON line of counts and seconds.  Each round maps the reads onto the draft with muchsalsa_amd.mapper in cigar mode
 (its rule 10; the options of the second line are the mapper's) and lets the chains vote; the output of a round is the draft of
 the next.  With ``--min-mapq N`` (0..60) the mapping also ranks the chains (the mapper's rule 12) and rule 2 takes its ranked
-form.  ``--paf F`` keeps the last round's PAF in F.  The reference tree has no polisher: the stage is defined by the rules
+form.  With ``--mates`` the reads file is an interleaved file of pairs (``mapper.interleave``), the mapping marks the proper pairs
+(the mapper's rule 13, ``--max-insert N`` its longest template) and rule 2 takes its mates form; it does not combine with
+``--min-mapq``.  ``--paf F`` keeps the last round's PAF in F.  The reference tree has no polisher: the stage is defined by the rules
 below, in integers only, and checked, without tolerance, against the tests' restatement in plain Python (tests/pl_oracle.py).
 The rules (include/msgpu.h, "pileup consensus"); parameters min_depth (>= 1, default 3) and min_identity (a percentage, 0..100,
 default 0):
@@ -21,13 +23,18 @@ default 0):
     MSGPU_E_ARG, "chain <i>: <what>".  The check is a device pass that publishes the smallest bad chain through the scalar
     block, and it is complete before any kernel walks a run: a bad table ends in an error, never in a fault.  In ranked form
     (``ranks`` given; msgpu_pl_run_ranked) a check (j) is added and reported last: the rank row's parent is in range and names a
-    chain of the same query record that is its own parent, and mapq <= 60; otherwise "chain <i>: rank".
+    chain of the same query record that is its own parent, and mapq <= 60; otherwise "chain <i>: rank".  In mates form
+    (``mates`` given; msgpu_pl_run_mates) a check (k) is added and reported last: cls <= 1 on every row, and for a row with
+    cls == 1 the mate is in range, the mate's row has cls == 1 and names this chain, the mate's query record is this one's ^ 1,
+    and n_best >= 1; otherwise "chain <i>: mates".
  2. voters.  A chain is eligible iff matches * 100 >= min_identity * block.  Per query record the voter is the eligible chain
     with the greatest score, then the greatest block, then the first in table order.  Every other chain is ignored and counted.
     Ranked form (with the mapper's rule 12 rows): a chain votes iff it is eligible, primary (parent == its own index) and
     mapq >= min_mapq.  So a read may have several voters (a split alignment votes with every part), a secondary never votes, and
     a read placed equally on two repeat copies (mapq 0) votes only at min_mapq = 0.  Everything behind the voters' spans is the
-    same in both forms.
+    same in both forms.  Mates form (with the mapper's rule 13 rows): a chain votes iff it is eligible, selected (cls == 1)
+    and n_best == 1.  So a pair placed equally well twice does not vote, an unselected chain never votes, and a read inside a
+    repeat copy votes on the copy that its mate names.  Everything behind the voters' spans is the same code in all three forms.
  3. oriented query.  Column j of a chain reads byte q_start + j_q of the query for strand 0 (j_q: the query bases that the
     columns in front of j consume); for strand 1 the oriented query is MSGPU_COPY_REVCOMP's of the whole record (reversed,
     A <-> T and C <-> G in upper case, every other byte as it is), and the chain starts at qlen - q_end in it.  The byte is then
@@ -89,14 +96,17 @@ def _strip(name):
     return name[2:] if name.startswith("n_") else name
 
 
-def run_tables(draft, reads, out, chains, runs, device=0, tables=None, timings=None, context=None, ranks=None, min_mapq=0, **params):
+def run_tables(draft, reads, out, chains, runs, device=0, tables=None, timings=None, context=None, ranks=None, min_mapq=0, mates=None,
+               **params):
     """The stage on given tables: ``chains`` holds per chain the tuple (query, target, strand, anchors, score, nm, q_start, q_end,
     t_start, t_end, matches, block) and ``runs`` per chain the list of len << 4 | op, as muchsalsa_amd.mapper's ``tables`` have
     them (reads = queries, draft = targets).  Writes ``out`` (nothing on an error); returns the counts of msgpu_pl_stats.
     ``params``: the names of DEFAULTS.  ``tables`` (a dict) receives ``records`` (per draft record the tuple of RECORD) and
     ``text`` (bytes); ``timings`` (a dict) seconds per step; ``context`` an entered Context to run on (``device`` is not read).
     ``ranks`` (per chain the tuple (parent, sub, n_secondary, mapq) of the mapper's rule 12, as ``mapper.run(..., rank=True)`` and
-    ``mapper.rank_tables`` give it) switches rule 2 to its ranked form with ``min_mapq``."""
+    ``mapper.rank_tables`` give it) switches rule 2 to its ranked form with ``min_mapq``.  ``mates`` (per chain the tuple (mate,
+    tlen, cls, n_best) of the mapper's rule 13, as ``mapper.run(..., mates=True)`` and ``mapper.mate_tables`` give it) switches
+    rule 2 to its mates form; giving both is a TypeError."""
     unknown = set(params) - set(DEFAULTS)
     if unknown:
         raise TypeError("unknown parameters: %s" % ", ".join(sorted(unknown)))
@@ -105,6 +115,10 @@ def run_tables(draft, reads, out, chains, runs, device=0, tables=None, timings=N
     L = _lib.lib()
     if len(chains) != len(runs):
         raise PolishError(_lib.E_ARG, "%d chains, %d run lists" % (len(chains), len(runs)))
+    if ranks is not None and mates is not None:
+        raise TypeError("ranks and mates: rule 2 takes one form")
+    if mates is not None and len(mates) != len(chains):
+        raise PolishError(_lib.E_ARG, "%d chains, %d mate rows" % (len(chains), len(mates)))
     if ranks is not None and len(ranks) != len(chains):
         raise PolishError(_lib.E_ARG, "%d chains, %d rank rows" % (len(chains), len(ranks)))
     if ranks is not None and not 0 <= int(min_mapq) < (1 << 32):
@@ -123,8 +137,16 @@ def run_tables(draft, reads, out, chains, runs, device=0, tables=None, timings=N
         rows = np.zeros(len(ranks), dtype=_lib.MAP_RANK_DTYPE)
         for i, r in enumerate(ranks):
             rows[i] = tuple(int(x) for x in r)
+    if mates is not None:
+        rows = np.zeros(len(mates), dtype=_lib.MAP_MATE_DTYPE)
+        for i, r in enumerate(mates):
+            if not all(0 <= int(x) < (1 << 32) for x in r):
+                raise PolishError(_lib.E_ARG, "mate row %d: %r" % (i, tuple(r)))
+            rows[i] = tuple(int(x) for x in r)
     with (stage_context("pl", device, PolishError) if context is None else contextlib.nullcontext(context)) as stage:
         with (stage.run(C.byref(prm), os.fsencode(draft), os.fsencode(reads), table.ctypes.data, len(chains), ops.ctypes.data,
+                        off.ctypes.data, rows.ctypes.data, 0, fn="run_mates") if mates is not None else
+              stage.run(C.byref(prm), os.fsencode(draft), os.fsencode(reads), table.ctypes.data, len(chains), ops.ctypes.data,
                         off.ctypes.data, 0) if ranks is None else
               stage.run(C.byref(prm), os.fsencode(draft), os.fsencode(reads), table.ctypes.data, len(chains), ops.ctypes.data,
                         off.ctypes.data, rows.ctypes.data, int(min_mapq), 0, fn="run_ranked")) as res:
@@ -148,14 +170,19 @@ def run_tables(draft, reads, out, chains, runs, device=0, tables=None, timings=N
                 params={name: int(getattr(st.params, name)) for name in DEFAULTS})
 
 
-def run(draft, reads, out, rounds=1, budget_mb=None, device=0, paf=None, tables=None, timings=None, extend=0, min_mapq=None, **params):
+def run(draft, reads, out, rounds=1, budget_mb=None, device=0, paf=None, tables=None, timings=None, extend=0, min_mapq=None, mates=False,
+        max_insert=_lib.MAP_MAX_INSERT_DEFAULT, **params):
     """``rounds`` times: mapper.run(draft_i, reads, ..., exact=1, cigar=1) and run_tables on its tables; the output of round i is
     the draft of round i + 1, the last one is ``out``.  Intermediate drafts and PAFs are written beside ``out`` and removed
     afterwards; ``paf`` keeps the last round's PAF.  ``params``: the names of DEFAULTS and of mapper.DEFAULTS (exact and ava are
     the stage's own).  Returns the last round's counts with ``rounds`` (per round ``map`` and ``polish``); ``tables`` and
     ``timings`` receive the last round's.  ``extend`` (0: off) is the mapper's rule 11 parameter for every round's mapping: the
     reads then vote beyond their outermost seeds too.  ``min_mapq`` not None switches the mapper's rule 12 on for every round's
-    mapping and rule 2 to its ranked form: the PAF then carries the mapping quality and the tp / s2 tags."""
+    mapping and rule 2 to its ranked form: the PAF then carries the mapping quality and the tp / s2 tags.  ``mates`` = True:
+    ``reads`` is an interleaved file of pairs (mapper.interleave), every round's mapping runs the mapper's rule 13 with
+    ``max_insert`` and rule 2 takes its mates form; with ``min_mapq`` it is a TypeError (one form at a time)."""
+    if mates and min_mapq is not None:
+        raise TypeError("mates and min_mapq: rule 2 takes one form")
     rounds = int(rounds)
     unknown = set(params) - set(DEFAULTS) - (set(mapper.DEFAULTS) - {"exact", "ava"})
     if unknown or rounds < 1:
@@ -174,11 +201,14 @@ def run(draft, reads, out, rounds=1, budget_mb=None, device=0, paf=None, tables=
                 made.append(target)
             tb, tm = {}, {}
             ranked = min_mapq is not None
+            paired = dict(mates=True, max_insert=max_insert) if mates else {}  # (without the option the calls are what they were)
             mapped = mapper.run(current, reads, paf_r, device=device, tables=tb, budget_mb=budget_mb, cigar=1, exact=1, extend=extend,
-                                rank=ranked, **theirs)
+                                rank=ranked, **paired, **theirs)
+            voters = dict(mates=tb["mates"]) if mates else {}
             got = run_tables(current, reads, target, tb["chains"], tb["runs"], device=device, tables=tables if last else None,
-                             timings=tm, ranks=tb["ranks"] if ranked else None, min_mapq=min_mapq if ranked else 0, **own)
-            per_round.append({"map": {k: mapped[k] for k in ("chains", "anchors", "pairs", "capped")}, "polish": got})
+                             timings=tm, ranks=tb["ranks"] if ranked else None, min_mapq=min_mapq if ranked else 0, **voters, **own)
+            per_round.append({"map": dict({k: mapped[k] for k in ("chains", "anchors", "pairs", "capped")},
+                                          **({"mate": mapped["mate"]} if mates else {})), "polish": got})
             current = target
     finally:
         for path in made:
@@ -231,6 +261,19 @@ def main(argv):
         except (IndexError, ValueError):
             ok = False
         del args[i:i + 2]
+    mates, max_insert = "--mates" in args, _lib.MAP_MAX_INSERT_DEFAULT
+    if mates:
+        args.remove("--mates")
+    if "--max-insert" in args:  # (implies --mates)
+        i = args.index("--max-insert")
+        try:
+            max_insert = int(args[i + 1])
+            ok = ok and 1 <= max_insert < (1 << 31)
+        except (IndexError, ValueError):
+            ok = False
+        del args[i:i + 2]
+        mates = True
+    ok = ok and not (mates and min_mapq is not None)
     rounds = p.pop("rounds", 1)
     q = dict(mapper.DEFAULTS, **dict(DEFAULTS, **p))
     ok = ok and 4 <= q["k"] <= 32 and 1 <= q["w"] <= 64 and q["max_occ"] >= 1 and 1 <= q["band"] <= 127
@@ -240,7 +283,9 @@ def main(argv):
         sys.stderr.write(__doc__.split("\n\n")[1] + "\n")
         return 2
     timings = {}
-    out = run(args[0], args[1], args[2], rounds=rounds, budget_mb=budget, paf=paf, timings=timings, extend=extend, min_mapq=min_mapq, **p)
+    paired = dict(mates=True, max_insert=max_insert) if mates else {}
+    out = run(args[0], args[1], args[2], rounds=rounds, budget_mb=budget, paf=paf, timings=timings, extend=extend, min_mapq=min_mapq, **paired,
+              **p)
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     print(json.dumps(out))
     return 0

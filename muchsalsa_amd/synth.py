@@ -971,3 +971,22 @@ def hybrid_workload(genome, seed, coverage=40, read_len=100, n_long=50, long_len
     recs, r_start, r_fwd = _long_reads(g, n_long, int(long_len), seed + 2, long_error, n_frac, lower_frac, fastq)  # (streams of their own)
     return {"illumina_1": one, "illumina_2": two, "reads": b"".join(recs), "genome": g.tobytes(), "read_start": r_start,
             "read_fwd": r_fwd}
+
+
+def mates_workload(genome=4000, seed=1, coverage=8, read_len=100, insert=300, repeat_len=250, copies=2, error=0.0, n_frac=0.0,
+                   lower_frac=0.0):
+    """Input of the mapper's rule 13 (mates): a dict with ``genome`` (bytes: one record's bases), ``illumina_1`` / ``illumina_2``
+    (FASTQ bytes) and ``repeats`` (the start of every copy of the repeat).  The genome has ``genome`` bases and one repeat unit
+    of ``repeat_len`` bases written ``copies`` times, as kmer_filter_workload plants it; the pairs are drawn from it as
+    kmer_filter_workload draws them, fragments of ``insert`` bases.  A read that falls inside a copy maps equally well onto
+    every copy; its mate in the unique flank says which.  Deterministic in (seed, shape)."""
+    G, L = int(genome), int(read_len)
+    g = _planted_genome(G, seed, 1, copies, repeat_len, 70, at_least=int(insert))
+    unit = genome_bases(int(repeat_len), seed + 1).tobytes()
+    text = g.tobytes()
+    starts, at = [], text.find(unit)
+    while at >= 0:
+        starts.append(at)
+        at = text.find(unit, at + 1)
+    one, two = _illumina_pairs(g, coverage, L, seed, error, n_frac, lower_frac, int(insert))
+    return {"genome": text, "illumina_1": one, "illumina_2": two, "repeats": starts}
