@@ -1819,6 +1819,128 @@ int msgpu_extend_ends(msgpu_seqctx *ctx, const void *d_a, const void *d_b, const
                       uint32_t band, uint32_t flags, msgpu_ext_end *ends, uint64_t *off /* n + 1 */, uint32_t *words,
                       uint64_t capacity, uint64_t *n_words);
 
+/* ---- assembly evaluation (no reference counterpart) ---------------------------------------------
+ * Consensus QV and completeness of an assembly from the k-mers of the accurate short reads, without a reference genome:
+ * the k-mer spectrum of the reads against the k-mers of the assembly, which is Merqury's method.  Merqury is not part of the
+ * reference tree: the stage is defined by the rules below and is checked without tolerance, on integers, against their
+ * restatement in plain Python (tests/ev_oracle.py).  Parameters: k (1..64), min_count (1..10000, default 2, the unitig
+ * stage's default; anything else is MSGPU_E_ARG), intervals (rule 7, 0 = off).
+ *  1. Read k-mers.  These follow the k-mer abundance filter's rules for FASTQ, for windows (k in 1..64, case folded, any
+ *     byte outside ACGTacgt breaks the windows that hold it) and for canonical keys, error code, file and line included.
+ *     The two cases are one file, and two files, which may have different record counts (the unitig stage's msgpu_pair
+ *     semantics).  R(x) is the exact number of windows of the read files whose canonical k-mer is x.
+ *  2. Assembly k-mers.  A window is k consecutive bases of one FASTA record, with the same alphabet rule.  It never crosses
+ *     two records.  A(x) is the number of assembly windows whose canonical k-mer is x (its copy number).  A window with
+ *     R(x) = 0 is missing.
+ *  3. Per record and in total.  The figures are length, windows, missing.  A record shorter than k has 0 windows.
+ *  4. QV.  This is host arithmetic in double precision from the two integers (msgpu_ev_qv).  With p = missing / windows,
+ *     the error rate is e = -expm1(log1p(-p) / k).  This form avoids cancellation for small p.
+ *     qv = -10 * log10(e) + 0.0, so that e = 1 prints 0.00, never -0.00.  missing = 0 gives +inf (text inf).
+ *     windows = 0 gives no value (NaN, text -).
+ *  5. Spectrum.  S[c][a] is the number of distinct canonical k-mers x with copy class c = min(A(x), 4) and read
+ *     abundance a.  a is 0 for assembly-only k-mers; there c >= 1.  Otherwise a = min(R(x), 10001); row 10001 is the
+ *     filter's cap row.  That makes 5 x 10002 counters.  For every a >= 1 the sum over c is the filter's histogram row.
+ *  6. Completeness.  This is host arithmetic on the spectrum for the parameter min_count.  solid is the sum of S[c][a] over
+ *     a >= min_count and all c.  found is the same sum over c >= 1.
+ *  7. Error intervals, on request.  One interval is made per maximal run of consecutive missing windows of a record.  A
+ *     run of windows s..e gives (record, s, e + k).  Intervals are not merged, so two runs separated by one present window
+ *     give two intervals that overlap.  They are ordered by record, then start.  A run never continues into the next record.
+ *  8. Report text.  It is tab-separated.  The first line is "#k <k> min_count <m>" (MSGPU_EV_TEXT_HEAD).  Per assembly
+ *     (MSGPU_EV_TEXT_REPORT): a line "#assembly <file name>" (the path's last component), then the header
+ *     "record length windows missing qv", then one line per record in file order; the name is the record name up to the
+ *     first blank; qv is printed with %.2f.  Then a line "total ...", and a line
+ *     "completeness <found> <solid> <100 * found / solid with %.4f, or - when solid = 0>".  MSGPU_EV_TEXT_SPECTRUM holds
+ *     the lines "a c0 c1 c2 c3 c4" for the rows that are not all zero, MSGPU_EV_TEXT_BED the lines "name start end"; each
+ *     of the two opens with the "#assembly" line as well, so that the texts of several assemblies can follow one another.
+ *  9. Limits.  Each is an error that names the figure, never a fault.  At most 2^30 distinct read k-mers (the hash table
+ *     over them has 2^31 slots at most).  Fewer than 2^31 assembly windows: the bases of an assembly, as its store holds
+ *     them, stay below 2^31 (a 3 Gb genome is out of scope).  The file limits of the filter and of the sequence store.
+ *     Everything resident together within the budget, else MSGPU_E_NOMEM naming the sizes.
+ * The table of the reads (sorted distinct keys, R, an open-addressing table over them) is a handle of its own: it is made
+ * once, from files or from a resident msgpu_pair, and serves any number of assemblies, as msgpu_map_index serves the mapper.
+ * A run reads it; the only array of it a run writes is the per-key assembly count A, which the run zeroes itself.  A context
+ * holds one table at a time (a second one is MSGPU_E_STATE until the first is freed), and a table of another context, or a
+ * pair on another device than the context's, is MSGPU_E_ARG. */
+typedef struct msgpu_evctx msgpu_evctx; /* a device context of the stage */
+typedef struct msgpu_ev_table msgpu_ev_table;
+typedef struct msgpu_ev_result msgpu_ev_result;
+#define MSGPU_EV_CLASSES 5u    /* copy classes 0..4 */
+#define MSGPU_EV_ROWS 10002u   /* read abundance 0..10001 */
+typedef struct msgpu_ev_params {
+  int32_t  k;
+  uint32_t min_count; /* rule 6 */
+  uint32_t intervals; /* rule 7: 0 = off */
+  uint32_t reserved;
+} msgpu_ev_params;
+void        msgpu_ev_default_params(msgpu_ev_params *p); /* k = 21, min_count = 2, intervals = 0 */
+int         msgpu_ev_create(int device, msgpu_evctx **out); /* MSGPU_E_NODEVICE without a GPU */
+void        msgpu_ev_destroy(msgpu_evctx *ctx);
+const char *msgpu_ev_last_error(const msgpu_evctx *ctx);
+uint64_t    msgpu_ev_error_line(const msgpu_evctx *ctx); /* after MSGPU_E_FORMAT: the 1-based line of a read file */
+int         msgpu_ev_error_file(const msgpu_evctx *ctx); /* after MSGPU_E_FORMAT / MSGPU_E_IO: read file 0 or 1 */
+/* Rule 4 on its own: host only, no device.  MSGPU_E_ARG for k outside 1..64 or missing > windows. */
+int         msgpu_ev_qv(uint64_t missing, uint64_t windows, int k, double *qv);
+typedef struct msgpu_ev_tstats {
+  uint64_t n_records[2], bytes_in[2];
+  uint64_t n_windows, n_distinct, largest_partition;
+  uint64_t bytes_resident;  /* keys, R, A and the hash table */
+  uint32_t k, n_partitions;
+  float load_ms, records_ms; /* host wall, as msgpu_kf_stats */
+  float bins_ms, extract_ms, sort_ms, runs_ms, select_ms; /* the count, device by events */
+  float table_ms;            /* gather, sort and the hash table (host wall) */
+  float wall_ms;
+  uint32_t reserved;
+} msgpu_ev_tstats;
+/* The table of one (path_b NULL) or two read files, or of a pair opened by msgpu_kf_open_pair.  budget_bytes bounds the
+ * count's partition buffers as in msgpu_kf_run (0: half of the free device memory). */
+int         msgpu_ev_table_open(msgpu_evctx *ctx, int k, const char *path_a, const char *path_b, uint64_t budget_bytes,
+                                msgpu_ev_table **out);
+int         msgpu_ev_table_open_pair(msgpu_evctx *ctx, int k, const msgpu_pair *pair, uint64_t budget_bytes, msgpu_ev_table **out);
+int         msgpu_ev_table_stats(const msgpu_ev_table *table, msgpu_ev_tstats *out);
+void        msgpu_ev_table_free(msgpu_ev_table *table);
+typedef struct msgpu_ev_record { /* rule 3, in file order */
+  uint64_t length, windows, missing;
+} msgpu_ev_record;
+typedef struct msgpu_ev_interval { /* rule 7 */
+  uint64_t start, end;
+  uint32_t record, reserved;
+} msgpu_ev_interval;
+typedef struct msgpu_ev_stats {
+  uint64_t n_records, n_bases, n_windows, n_missing;
+  uint64_t n_missing_distinct;  /* distinct assembly-only k-mers: the sum of row a = 0 */
+  uint64_t n_intervals;
+  uint64_t solid, found;        /* rule 6 */
+  uint64_t n_lost_publications; /* scalar read-backs that had to fall back to a copy */
+  uint64_t bytes_peak;          /* the run's own device memory, the table and the store not counted */
+  uint32_t k, min_count;
+  float load_ms;                /* the assembly into its store (host wall) */
+  float window_ms;              /* the window kernel, device by events from here on */
+  float reduce_ms;              /* the per-record sums */
+  float missing_ms;             /* sort and run lengths of the missing keys, row a = 0 */
+  float spectrum_ms, intervals_ms, copy_ms;
+  float host_ms;                /* the texts (wall) */
+  float wall_ms;
+  uint32_t reserved;
+} msgpu_ev_stats;
+/* One assembly on a table.  params->k must be the table's.  flags must be 0.  Synchronous; tables and texts are kept in
+ * the result. */
+int         msgpu_ev_run_table(msgpu_evctx *ctx, const msgpu_ev_params *params, msgpu_ev_table *table, const char *assembly_path,
+                               uint32_t flags, msgpu_ev_result **out);
+/* table_open + run_table + table_free */
+int         msgpu_ev_run(msgpu_evctx *ctx, const msgpu_ev_params *params, const char *path_a, const char *path_b,
+                         const char *assembly_path, uint32_t flags, uint64_t budget_bytes, msgpu_ev_result **out);
+int         msgpu_ev_result_stats(const msgpu_ev_result *r, msgpu_ev_stats *out);
+int         msgpu_ev_result_records(const msgpu_ev_result *r, const msgpu_ev_record **records, const msgpu_ev_record **total, uint64_t *n);
+/* MSGPU_EV_CLASSES rows of MSGPU_EV_ROWS counters: S[c][a] = spectrum[c * MSGPU_EV_ROWS + a] */
+int         msgpu_ev_result_spectrum(const msgpu_ev_result *r, const uint64_t **spectrum);
+int         msgpu_ev_result_intervals(const msgpu_ev_result *r, const msgpu_ev_interval **intervals, uint64_t *n);
+#define MSGPU_EV_TEXT_HEAD 0
+#define MSGPU_EV_TEXT_REPORT 1
+#define MSGPU_EV_TEXT_SPECTRUM 2
+#define MSGPU_EV_TEXT_BED 3 /* empty unless params->intervals */
+const char *msgpu_ev_result_text(const msgpu_ev_result *r, int which, uint64_t *len);
+void        msgpu_ev_result_free(msgpu_ev_result *r);
+
 #ifdef __cplusplus
 }
 #endif

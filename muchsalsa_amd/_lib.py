@@ -328,6 +328,38 @@ class PlRecord(C.Structure):  # msgpu_pl_record
     _fields_ = [(n, C.c_uint64) for n in ("len_in", "len_out", "n_substituted", "n_deleted", "n_inserted", "depth_x100")]
 
 
+class EvParams(C.Structure):  # msgpu_ev_params
+    _fields_ = [("k", C.c_int32), ("min_count", C.c_uint32), ("intervals", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EvTableStats(C.Structure):  # msgpu_ev_tstats
+    _fields_ = ([("n_records", C.c_uint64 * 2), ("bytes_in", C.c_uint64 * 2)] +
+                [(n, C.c_uint64) for n in ("n_windows", "n_distinct", "largest_partition", "bytes_resident")] +
+                [("k", C.c_uint32), ("n_partitions", C.c_uint32)] +
+                [(n, C.c_float) for n in ("load_ms", "records_ms", "bins_ms", "extract_ms", "sort_ms", "runs_ms", "select_ms",
+                                          "table_ms", "wall_ms")] + [("reserved", C.c_uint32)])
+
+
+class EvRecord(C.Structure):  # msgpu_ev_record
+    _fields_ = [(n, C.c_uint64) for n in ("length", "windows", "missing")]
+
+
+class EvInterval(C.Structure):  # msgpu_ev_interval
+    _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("record", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EvStats(C.Structure):  # msgpu_ev_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_records", "n_bases", "n_windows", "n_missing", "n_missing_distinct", "n_intervals",
+                                           "solid", "found", "n_lost_publications", "bytes_peak")] +
+                [("k", C.c_uint32), ("min_count", C.c_uint32)] +
+                [(n, C.c_float) for n in ("load_ms", "window_ms", "reduce_ms", "missing_ms", "spectrum_ms", "intervals_ms", "copy_ms",
+                                          "host_ms", "wall_ms")] + [("reserved", C.c_uint32)])
+
+
+EV_CLASSES, EV_ROWS = 5, 10002  # MSGPU_EV_CLASSES, MSGPU_EV_ROWS
+EV_TEXT_HEAD, EV_TEXT_REPORT, EV_TEXT_SPECTRUM, EV_TEXT_BED = 0, 1, 2, 3
+
+
 # every symbol include/msgpu.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("msgpu_default_params", None, [C.POINTER(Params)]),
@@ -618,6 +650,27 @@ SYMBOLS = [
     ("msgpu_pl_result_stats", C.c_int, [C.c_void_p, C.POINTER(PlStats)]),
     ("msgpu_pl_result_records", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(PlRecord)), C.POINTER(C.c_uint64)]),
     ("msgpu_pl_result_free", None, [C.c_void_p]),
+    ("msgpu_ev_default_params", None, [C.POINTER(EvParams)]),
+    ("msgpu_ev_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_ev_destroy", None, [C.c_void_p]),
+    ("msgpu_ev_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_ev_error_line", C.c_uint64, [C.c_void_p]),
+    ("msgpu_ev_error_file", C.c_int, [C.c_void_p]),
+    ("msgpu_ev_qv", C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
+    ("msgpu_ev_table_open", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("msgpu_ev_table_open_pair", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("msgpu_ev_table_stats", C.c_int, [C.c_void_p, C.POINTER(EvTableStats)]),
+    ("msgpu_ev_table_free", None, [C.c_void_p]),
+    ("msgpu_ev_run_table", C.c_int, [C.c_void_p, C.POINTER(EvParams), C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("msgpu_ev_run", C.c_int, [C.c_void_p, C.POINTER(EvParams), C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64,
+                               C.POINTER(C.c_void_p)]),
+    ("msgpu_ev_result_stats", C.c_int, [C.c_void_p, C.POINTER(EvStats)]),
+    ("msgpu_ev_result_records", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(EvRecord)), C.POINTER(C.POINTER(EvRecord)),
+                                          C.POINTER(C.c_uint64)]),
+    ("msgpu_ev_result_spectrum", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64))]),
+    ("msgpu_ev_result_intervals", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(EvInterval)), C.POINTER(C.c_uint64)]),
+    ("msgpu_ev_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    ("msgpu_ev_result_free", None, [C.c_void_p]),
     ("msgpu_gather_plan_out_bytes", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_plan_bases", C.c_uint64, [C.c_void_p]),
     ("msgpu_gather_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -27,6 +27,8 @@ Files under ``outdir``, with the script's names (BASE = the long-read file's bas
 ``02_contigs_corrected.to_<BASE>.scrubbed.paf``, ``03.assembly.unpolished.fa``.  What the script leaves in its temporary
 folder goes under ``outdir/tmp/``: ``unitigs_corrected.fa``, ``<BASE>.ava.paf`` and the three ``temp_1.*`` files.
 ``run(..., gfa=True)`` adds ``ABYSS/<name>-unitigs.gfa``, the unitig graph (what ``abyss-pe graph=gfa`` leaves there).
+``run(..., evaluate=K)`` adds ``06.assembly.evaluation.tsv``: QV and completeness of the assembly, and of its polished forms,
+from the Illumina reads' k-mers at k = K (muchsalsa_amd.evaluate).
 
 Between stages whose hand-off is one of those files -- the pipeline's deliverables and its checkpoints -- the file stays the
 hand-off.  An error in any stage stops the run: HybridError, the stage's name in front of the stage's own message; the
@@ -40,11 +42,12 @@ import time
 
 from . import _lib
 
-__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "POLISHED_MATES_NAME", "INTERLEAVED_NAME", "MATES_MAPPING", "gfa_name", "output_names", "link_input", "run", "main"]
+__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "POLISHED_MATES_NAME", "EVALUATION_NAME", "INTERLEAVED_NAME", "MATES_MAPPING", "gfa_name", "output_names", "link_input", "run", "main"]
 
 MIN_LENGTH = 500  # pipeline.sh:29
 POLISHED_NAME = "04.assembly.polished.fa"  # written only by run(..., polish=N): not one of output_names
 POLISHED_MATES_NAME = "05.assembly.polished.mates.fa"  # written only by run(..., polish_mates=N): not one of output_names
+EVALUATION_NAME = "06.assembly.evaluation.tsv"  # written only by run(..., evaluate=K): not one of output_names
 INTERLEAVED_NAME = os.path.join("tmp", "illumina.interleaved.fq")  # the two Illumina inputs as one file of pairs, likewise
 # The mapper's parameters for the short reads of the polish_mates stage.  The mapper's default min_score of 100 is the score of
 # a perfect 100-base read and would drop nearly every mate; 40 is a choice, unchecked on real reads.
@@ -95,7 +98,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None):
+        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None, evaluate=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -115,7 +118,11 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     polisher's rule 2 in mates form) polish the long-read-polished file if ``polish`` was given, else the assembly, into
     POLISHED_MATES_NAME, named by ``files["polished_mates"]``; every other file is the same.  Its mappings run with MATES_MAPPING
     (a min_score fit for 100-base reads: a choice, unchecked on real reads) and ``max_insert`` (None: the mapper's default);
-    neither the extension nor the mapping quality threshold reaches this stage."""
+    neither the extension nor the mapping quality threshold reaches this stage.  ``evaluate`` (None or 0: off) = K adds a last
+    stage ``"evaluate"`` (muchsalsa_amd.evaluate): the Illumina pair is opened again (it is not kept resident through the mapping
+    stages), one table of its k-mers is built at k = K, and the assembly, and the polished files where they were written, are
+    evaluated on it into EVALUATION_NAME (QV per record and in total, completeness), named by ``files["evaluation"]``; every
+    other file is the same."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -181,6 +188,11 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
         more = {} if max_insert is None else {"max_insert": int(max_insert)}
         stage("polish_mates", polisher.run, result["files"]["polished"] if polish else files["assembly"], pairs,
               result["files"]["polished_mates"], rounds=int(polish_mates), device=device, mates=True, **more, **MATES_MAPPING)
+    if evaluate:
+        from . import evaluate as evaluator
+        result["files"]["evaluation"] = os.path.join(out, EVALUATION_NAME)
+        drafts = [files["assembly"]] + [result["files"][key] for key in ("polished", "polished_mates") if key in result["files"]]
+        stage("evaluate", evaluator.run, int(evaluate), illumina_1, illumina_2, drafts, result["files"]["evaluation"], device=device)
     result["seconds"] = round(time.perf_counter() - t_all, 4)
     return result
 
