@@ -545,6 +545,17 @@ int msgpu_set_deadline(msgpu_ctx *ctx, uint32_t timeout_ms);
 uint64_t msgpu_chain_launches(msgpu_ctx *ctx);
 int msgpu_wait_chain_launch(msgpu_ctx *ctx, uint64_t count, uint32_t timeout_us);
 
+/* ---- for tests: the context's device buffers --------------------------------------------------------------------
+ * One text line per device buffer of the context, in the order of the buffer table in csrc/msgpu_api.hip:
+ *   "<name> <bytes> <guarded 0|1> <carries 0|1> <generation>\n"
+ * bytes: the size of the block the buffer holds now (0: none); guarded: the block lies between guards (it was allocated
+ * under MSGPU_POISON: exactly as large as the request, filled with 0xA5, and every entry that launches work compares its
+ * guards before it returns MSGPU_OK -- a written one is MSGPU_E_HIP with a text that begins with "arena guard:"); carries:
+ * the buffer carries something across the start of a job (the table says what) and is not given back there; generation: the
+ * allocations made through this buffer so far.  The text is cut to text_bytes - 1 characters and closed with a 0;
+ * *needed (may be NULL) = the bytes the whole text takes, the 0 included.  No device work. */
+int msgpu_debug_buffers(msgpu_ctx *ctx, char *text, size_t text_bytes, size_t *needed);
+
 /* ==== sequence store + slice / reverse-complement / stitch kernel: device half of the "consensus" stage (A9) ========
  *
  * assemblePath (libms/src/kernel/ap.cpp:615-1362) decides where every piece of sequence goes; the bytes come from

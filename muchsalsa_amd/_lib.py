@@ -416,6 +416,7 @@ SYMBOLS = [
     ("msgpu_load_rows_packed", C.c_int, [C.c_void_p, C.POINTER(PackedRows)]),
     ("msgpu_synchronize", C.c_int, [C.c_void_p]),
     ("msgpu_set_deadline", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("msgpu_debug_buffers", C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("msgpu_seq_parse", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("msgpu_seq_free", None, [C.c_void_p]),
     ("msgpu_seq_count", C.c_uint32, [C.c_void_p]),

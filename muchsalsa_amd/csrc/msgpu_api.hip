@@ -25,6 +25,7 @@
 #include "host_pool.h"
 #include "msgpu.h"
 #include "msgpu_internal.h"
+#include "msgpu_devbuf.h"
 #include "msgpu_stage.h"
 
 using namespace msgpu;
@@ -141,81 +142,6 @@ void host_table_pin(void *q) noexcept {
 
 namespace {
 
-struct DevBuf { // device memory that grows and is kept from job to job; gives itself back, moves, does not copy
-  void  *p   = nullptr; // the allocation
-  size_t cap = 0;       // its size in bytes
-  // A buffer can be used as a VIEW that starts `off` bytes into the allocation: the job-wide result tables of a
-  // resident batched run (msgpu_overlap_batched_ex) -- window k writes behind what the windows before it left, and a
-  // reallocation keeps those first `off` bytes.  off = 0 everywhere else.
-  size_t off  = 0;
-  size_t hint = 0; // expected final size of the allocation (bytes): a reallocation asks for at least this much
-  // While a batched job runs its first windows, every (re)allocation on this thread asks for the size the job's LARGEST
-  // window will need, not the current one's (msgpu_overlap_batched_ex sets this: windows grow, and a scratch table that
-  // grows with them is freed and allocated again -- a device-wide synchronisation -- in every window of a first call)
-  static inline thread_local double grow_by = 1.0;
-  double own_grow_by = 0.0; // the same for this buffer alone (a job-wide result table while the job's FIRST window fills it)
-  DevBuf() = default;
-  DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
-  DevBuf &operator=(DevBuf &&o) noexcept {
-    std::swap(p, o.p);
-    std::swap(cap, o.cap);
-    std::swap(off, o.off);
-    std::swap(hint, o.hint);
-    std::swap(own_grow_by, o.own_grow_by);
-    return *this;
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t ensure(size_t bytes) { // room for `bytes` behind `off`
-    if (off + bytes <= cap) return hipSuccess;
-    const size_t need = off + bytes;
-    size_t       want = need + need / 8 + 256; // slack so slowly growing inputs do not reallocate each run
-    const double by = own_grow_by > grow_by ? own_grow_by : grow_by;
-    if (by > 1.0) want = off + static_cast<size_t>(double(want - off) * by);
-    if (hint > want) want = hint;
-    static const bool dbg_alloc = std::getenv("MSGPU_ALLOC_DEBUG") != nullptr;
-    if (dbg_alloc) fprintf(stderr, "[alloc] %zu -> %zu bytes (need %zu, kept %zu, hint %zu, grow_by %.2f)\n", cap, want, need, off, hint, grow_by);
-    void      *np = nullptr;
-    hipError_t e;
-    if (p && !off) { // nothing to keep: give the old block back first
-      e   = hipFree(p);
-      p   = nullptr;
-      cap = 0;
-      if (e != hipSuccess) return e;
-    }
-    e = hipMalloc(&np, want);
-    if (e != hipSuccess) return e;
-    // MSGPU_POISON=1 (debugging): fresh device memory is filled with 0xA5 so that a kernel which relies on zeroed scratch
-    // fails every time instead of only when the allocator hands back recycled pages
-    static const bool poison = std::getenv("MSGPU_POISON") != nullptr;
-    if (poison) {
-      e = hipMemset(np, 0xA5, want); // null stream, may return before it ran: wait, the context's stream does not
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) {
-        (void)hipFree(np);
-        return e;
-      }
-    }
-    if (p) { // a view that outgrew its allocation: everything in flight on the old block first, then its kept part moves
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(np, p, off, hipMemcpyDeviceToDevice);
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) {
-        (void)hipFree(np);
-        return e;
-      }
-      (void)hipFree(p);
-    }
-    p   = np;
-    cap = want;
-    return hipSuccess;
-  }
-  template <class T> T *as() const { return reinterpret_cast<T *>(static_cast<char *>(p) + off); }
-  void  *at() const { return static_cast<char *>(p) + off; }
-  size_t room() const { return cap > off ? cap - off : 0; } // bytes behind `off`
-};
-
 struct HostBuf { // a page-locked host table (ensure_host); gives itself back, moves, does not copy
   void  *p   = nullptr;
   size_t cap = 0;
@@ -232,7 +158,108 @@ struct HostBuf { // a page-locked host table (ensure_host); gives itself back, m
 enum State { ST_CREATED = 0, ST_LOADED = 1, ST_EDGES = 2, ST_CHAINED = 3,
              ST_RESULT = 4 /* the whole job's tables, built window by window (msgpu_overlap_batched_ex, resident): no per-edge scratch */ };
 
+// how long what a DevBuf of the context holds is of use
+enum BufLife {
+  BUF_CALL,  // scratch of one public entry: nothing reads it once the entry has returned
+  BUF_JOB,   // the index, the scratch and the tables of one job: msgpu_load_rows* (msgpu_overlap_batched*) to the next one
+  BUF_CARRY, // carries something ACROSS the start of a job
+};
+
 } // namespace
+
+// THE AT-REST PROTOCOL, as far as it lives in device buffers: every DevBuf of msgpu_ctx by name, the stage that uses it, and
+// whether it carries something across the start of a job -- and if so what, and who leaves it that way.  ("Whoever consumes a
+// counter last leaves it zero."  The scalar block, ScalarBlock sc, is no DevBuf: scalars_clean and nlists_clean are its flags.)
+// Everything that does not carry is, by this table's word, written by its job before the job reads it.  Under MSGPU_POISON
+// (DevBuf, msgpu_devbuf.h) the context holds the table to that word: a job start (job_start below) gives back every buffer
+// that carries nothing, so that the job allocates each at its exact size, filled with 0xA5 and between guards, and every
+// public entry that launched work compares the guards before it returns MSGPU_OK (verify_guards).  The flags that describe
+// a BUF_JOB buffer inside a job (cand_zeroed, chain_zeroed, prologue_ok, full_scan_ok) are all set anew by the job's own
+// index build or candidate stage: none of them crosses a job start.
+// tests/test_gpu_poisoned_overlap.py keeps the second copy of the names that carry.
+#define MSGPU_CTX_BUFS(X)                                                                                                                  \
+  /* rows */                                                                                                                               \
+  X(rows_in, "load", BUF_JOB, "")        /* the 40-byte rows (host rows copied, packed rows expanded) */                                 \
+  X(rows_pk, "load", BUF_JOB, "")        /* msgpu_load_rows_packed: the 28-byte rows, read lengths and line runs as they crossed */      \
+  /* the index build (build_index_once) */                                                                                                 \
+  X(cnt_read, "index", BUF_JOB, "")                                                                                                        \
+  X(read_off, "index", BUF_JOB, "")                                                                                                        \
+  X(cursor, "index", BUF_JOB, "")                                                                                                          \
+  X(bkt_key, "index", BUF_JOB, "")                                                                                                         \
+  X(bkt_dead, "index", BUF_JOB, "")                                                                                                        \
+  X(by_read, "index", BUF_JOB, "")                                                                                                         \
+  X(read_cnt, "index", BUF_JOB, "")                                                                                                        \
+  X(alive_rank, "index", BUF_JOB, "")                                                                                                      \
+  X(anchor_cnt, "index", BUF_JOB, "")                                                                                                      \
+  X(anchor_off, "index", BUF_JOB, "")                                                                                                      \
+  X(anchor_first, "index", BUF_JOB, "")                                                                                                    \
+  X(anchor_off_gen, "index", BUF_JOB, "")                                                                                                  \
+  X(bkt2_idx, "index", BUF_JOB, "")                                                                                                        \
+  X(bkt2_line, "index", BUF_JOB, "")                                                                                                       \
+  X(by_anchor, "index", BUF_JOB, "")                                                                                                       \
+  X(read_len, "index", BUF_JOB, "")      /* (msgpu_copy_reads reads it until the next load) */                                            \
+  X(read_first, "index", BUF_JOB, "")                                                                                                      \
+  X(scan_tmp, "every scan", BUF_JOB, "") /* sized by the index build for the job's scans (candidates, dispatcher); other entries grow it */ \
+  X(vis16, "index", BUF_JOB, "")                                                                                                           \
+  X(spos2, "index", BUF_JOB, "")                                                                                                           \
+  X(visits, "index", BUF_JOB, "")                                                                                                          \
+  X(bin_cursor, "index", BUF_CARRY,                                                                                                        \
+    "the bin path's bucket cursors and its row base, ZERO over the first bin_zero_words words while bin_clean holds: "                     \
+    "k_index_sort_bin takes every cursor it consumed back to zero, k_index_epilogue the row base")                                         \
+  X(bin_start, "index", BUF_JOB, "")                                                                                                       \
+  X(bucket_visits, "index", BUF_JOB, "")                                                                                                   \
+  /* the candidate stage (msgpu_calculate_edges; its opening may run inside the index build) */                                            \
+  X(bound, "candidates", BUF_JOB, "")                                                                                                      \
+  X(cand_off, "candidates", BUF_JOB, "") /* (full_scan_ok: the index build's scan stands for the job's windows) */                         \
+  X(cand_j, "candidates", BUF_JOB, "")                                                                                                     \
+  X(cand_q, "candidates", BUF_JOB, "")                                                                                                     \
+  X(scr_v2, "candidates", BUF_JOB, "")                                                                                                     \
+  X(scr_start, "candidates", BUF_JOB, "")                                                                                                  \
+  X(n_cand, "candidates", BUF_JOB, "")   /* (cand_zeroed: k_classify_reads zeroed it, in this job's index build) */                       \
+  X(n_edge, "candidates", BUF_JOB, "")                                                                                                     \
+  X(cand_sums, "candidates", BUF_JOB, "")                                                                                                  \
+  X(lists, "candidates", BUF_JOB, "")                                                                                                      \
+  X(big_key, "candidates", BUF_JOB, "")                                                                                                    \
+  X(big_t, "candidates", BUF_JOB, "")                                                                                                      \
+  X(big_r2s, "candidates", BUF_JOB, "")                                                                                                    \
+  X(big_pfx, "candidates", BUF_JOB, "")                                                                                                    \
+  X(edges, "candidates", BUF_JOB, "")    /* the edge table (a view in a resident batched job: its kept part goes from window to window) */ \
+  X(edge_cand, "candidates", BUF_JOB, "")                                                                                                  \
+  X(cls_list, "candidates", BUF_JOB, "")                                                                                                   \
+  X(big_list, "candidates", BUF_JOB, "")                                                                                                   \
+  X(big_off, "candidates", BUF_JOB, "")                                                                                                    \
+  /* the chain stage (msgpu_chaining_and_overlaps) */                                                                                      \
+  X(chain_chunks, "chain", BUF_JOB, "")  /* (chain_zeroed: k_emit_edges zeroed it, in this job's candidate stage) */                      \
+  X(pair_tab, "chain", BUF_CARRY,                                                                                                          \
+    "the chain kernels' pair tables, constants: launch_fill_pair_tab fills them in the call that allocates the buffer, "                  \
+    "nothing writes them afterwards")                                                                                                      \
+  X(ems, "chain", BUF_JOB, "")           /* the EdgeMatch, order and id tables: views as the edge table is */                             \
+  X(order_scr, "chain", BUF_JOB, "")                                                                                                       \
+  X(ids_scr, "chain", BUF_JOB, "")                                                                                                         \
+  X(orders, "chain", BUF_JOB, "")                                                                                                          \
+  X(ids, "chain", BUF_JOB, "")                                                                                                             \
+  X(big_elems, "chain", BUF_JOB, "")                                                                                                       \
+  X(big_paths, "chain", BUF_JOB, "")                                                                                                       \
+  /* msgpu_find_contraction_edges */                                                                                                       \
+  X(g_deg, "contraction", BUF_CALL, "")                                                                                                    \
+  X(g_off, "contraction", BUF_CALL, "")                                                                                                    \
+  X(g_adj, "contraction", BUF_CALL, "")                                                                                                    \
+  X(g_cand, "contraction", BUF_CALL, "")                                                                                                   \
+  X(g_sane, "contraction", BUF_CALL, "")                                                                                                   \
+  X(g_out, "contraction", BUF_CALL, "")                                                                                                    \
+  /* msgpu_get_edgematches */                                                                                                              \
+  X(sel_idx, "edgematches", BUF_CALL, "")                                                                                                  \
+  X(sel_cnt, "edgematches", BUF_CALL, "")                                                                                                  \
+  X(sel_off, "edgematches", BUF_CALL, "")                                                                                                  \
+  X(sel_ems, "edgematches", BUF_CALL, "")                                                                                                  \
+  /* the dispatcher (msgpu_overlap_batched*) */                                                                                            \
+  X(alt_edges, "dispatcher", BUF_JOB, "") /* the second set of output tables: a window computes while the one before it is copied */      \
+  X(alt_ems, "dispatcher", BUF_JOB, "")                                                                                                    \
+  X(alt_orders, "dispatcher", BUF_JOB, "")                                                                                                 \
+  X(alt_ids, "dispatcher", BUF_JOB, "")                                                                                                    \
+  X(win_cuts, "dispatcher", BUF_JOB, "") /* the window cuts by measured work (k_window_cuts) */                                            \
+  X(wire_dev0, "dispatcher", BUF_JOB, "") /* a window's edge / order / id tables in wire form, on their way to the host (two sets) */     \
+  X(wire_dev1, "dispatcher", BUF_JOB, "")
 
 // `stream` (StageCtx) is the stream the calls use, which msgpu_set_stream may point at a caller's; own_stream is the one
 // stage_create made, and the one stage_destroy gets back.  Everything else the context owns is held by members that release it.
@@ -276,11 +303,28 @@ struct msgpu_ctx : msgpu::StageCtx {
   uint32_t n_list[4] = {0, 0, 0, 0};
 
   // arena
-  DevBuf rows_in, rows_pk, cnt_read, read_off, cursor, bkt_key, bkt_dead, by_read, read_cnt, alive_rank,
-      anchor_cnt, anchor_off, anchor_first, anchor_off_gen, bkt2_idx, bkt2_line, by_anchor, read_len, read_first,
-      scan_tmp, vis16, spos2, visits, bin_cursor, bin_start;
-  DevBuf bound, cand_off, cand_j, cand_q, scr_v2, scr_start, n_cand, n_edge, lists, edges, edge_cand;
-  DevBuf big_key, big_t, big_r2s, big_pfx, pair_tab, chain_chunks, big_off, cand_sums, bucket_visits;
+#define X(member, stage, life, note) DevBuf member;
+  MSGPU_CTX_BUFS(X) // every DevBuf of the context: the table above
+#undef X
+  DevBuf &wire_dev(int set) { return set ? wire_dev1 : wire_dev0; }
+  struct BufInfo { // a row of the table
+    DevBuf msgpu_ctx::*m;
+    const char        *name, *stage;
+    BufLife            life;
+    const char        *carries;
+  };
+  static const std::vector<BufInfo> &buf_table() {
+    static const std::vector<BufInfo> t = {
+#define X(member, stage, life, note) BufInfo{&msgpu_ctx::member, #member, stage, life, note},
+        MSGPU_CTX_BUFS(X)
+#undef X
+    };
+    return t;
+  }
+  msgpu_ctx() {
+    for (const BufInfo &b : buf_table()) (this->*b.m).name = b.name;
+  }
+  bool poison = false; // MSGPU_POISON as the public entry that is running found it (asked once per entry)
   EventHold ev_side[2], ev_side2;
   uint64_t    n_big_edges = 0, n_big_ems = 0;
   bool   fast_path = true;
@@ -292,13 +336,8 @@ struct msgpu_ctx : msgpu::StageCtx {
   uint32_t n_cls[4] = {0, 0, 0, 0}; // edges of 9..16, 17..32, 33..64 and <= 8 EdgeMatches
   uint64_t n_edges_fast = 0;
   uint64_t chain_E = 0; // edges of the last chaining pass (where its band counts lie in chain_chunks)
-  DevBuf ems, order_scr, ids_scr, orders, ids, big_list, cls_list, big_elems,
-      big_paths;
-  DevBuf g_deg, g_off, g_adj, g_cand, g_sane, g_out; // findContractionEdges
-  DevBuf sel_idx, sel_cnt, sel_off, sel_ems;          // msgpu_get_edgematches
 
   // batched execution (msgpu_overlap_batched): second set of output tables, copy stream, pinned result arena
-  DevBuf    alt_edges, alt_ems, alt_orders, alt_ids;
   EventHold ev_done[2], ev_copied[2];
   HostBuf   h_edges, h_ems, h_orders, h_ids, h_read_len, h_read_first, h_sel_off, h_sel_ems, h_wire[2];
   EventHold ev_part[2][3]; // a window's wire blocks, copied one by one
@@ -307,8 +346,6 @@ struct msgpu_ctx : msgpu::StageCtx {
   std::mutex              gate_m;
   std::condition_variable gate_cv;
   uint64_t                chain_launches = 0;
-  DevBuf win_cuts;        // the dispatcher's window cuts by measured work (k_window_cuts)
-  DevBuf wire_dev[2];     // a window's edge / order / id tables in wire form, on their way to the host (two sets: see the dispatcher)
   bool   wire_copy = true; // MSGPU_NO_WIRE_COPY=1: windows always leave as whole records (A/B switch)
 
   // timing
@@ -365,6 +402,48 @@ int fail(msgpu_ctx *c, int code, const char *fmt, ...) {
   vsnprintf(c->err, sizeof(c->err), fmt, ap);
   va_end(ap);
   return code;
+}
+
+// ---- MSGPU_POISON: the table above, enforced (nothing of this runs without the variable)
+//
+// A job start -- msgpu_load_rows*, msgpu_overlap_batched* (whose windows are no job starts: the job-wide tables with off > 0
+// carry their kept part from window to window) -- gives back every buffer that carries nothing, behind everything the device
+// has in flight and before anything is launched.  msgpu_find_contraction_edges and msgpu_merge_* are job starts for the
+// BUF_CALL buffers alone: the tables of the job that stands (msgpu_copy_tables, msgpu_get_edgematches, msgpu_pack_wire and
+// msgpu_find_contraction_edges itself read them afterwards) are somebody's input there, not left-overs.
+int job_start(msgpu_ctx *c, bool whole_job) {
+  if (!c->poison) return MSGPU_OK;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  STAGE_HIP(c, hipDeviceSynchronize());
+  for (const msgpu_ctx::BufInfo &b : msgpu_ctx::buf_table())
+    if (b.life == BUF_CALL || (whole_job && b.life == BUF_JOB)) STAGE_HIP(c, (c->*b.m).release(false)); // (a written guard: kept for verify_guards)
+  if (whole_job) c->state = ST_CREATED; // (the job that stood is gone with its tables, whatever the entry goes on to say about its arguments)
+  return MSGPU_OK;
+}
+// Before a public entry that launched work returns MSGPU_OK: the context's streams have drained, and no guard of any
+// guarded block is written -- now, or when a block was given back
+int verify_guards(msgpu_ctx *c) {
+  if (!c->poison) return MSGPU_OK;
+  STAGE_HIP(c, hipSetDevice(c->device));
+  for (hipStream_t s : {c->stream, static_cast<hipStream_t>(c->side_stream), static_cast<hipStream_t>(c->side_stream2),
+                        static_cast<hipStream_t>(c->copy_stream)})
+    if (s) STAGE_HIP(c, hipStreamSynchronize(s));
+  for (const msgpu_ctx::BufInfo &b : msgpu_ctx::buf_table()) {
+    DevBuf &d = c->*b.m;
+    STAGE_HIP(c, d.look());
+    if (!d.broken.empty()) return fail(c, MSGPU_E_HIP, "%s", d.broken.c_str());
+  }
+  return MSGPU_OK;
+}
+// a public entry: MSGPU_POISON is asked once, `body` runs, and an MSGPU_OK is one behind verify_guards
+enum EntryKind { ENTRY_PLAIN, ENTRY_CALL_START, ENTRY_JOB_START };
+template <class Body> int entry(msgpu_ctx *c, EntryKind kind, Body body) {
+  if (!c) return MSGPU_E_ARG;
+  c->poison = DevArena::poisoned();
+  if (kind != ENTRY_PLAIN)
+    if (int rc = job_start(c, kind == ENTRY_JOB_START)) return rc;
+  const int rc = body();
+  return rc == MSGPU_OK ? verify_guards(c) : rc;
 }
 
 template <class T> T *scalar(msgpu_ctx *c, int slot) { return reinterpret_cast<T *>(c->sc.d + slot); }
@@ -799,6 +878,8 @@ void msgpu_destroy(msgpu_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream); // (before anything is freed; a caller's stream is not ours to destroy)
   c->stream = c->own_stream;
+  c->poison = DevArena::poisoned();
+  if (verify_guards(c) != MSGPU_OK) fprintf(stderr, "msgpu_destroy: %s\n", c->err); // (nobody is left to return it to)
   stage_destroy(c);
 }
 
@@ -850,7 +931,11 @@ int msgpu_set_id_space(msgpu_ctx *c, uint32_t n_reads, uint32_t n_anchors) {
   return MSGPU_OK;
 }
 
+static int load_rows_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows);
 int msgpu_load_rows(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows) {
+  return entry(c, ENTRY_JOB_START, [&] { return load_rows_impl(c, rows, n_rows); });
+}
+static int load_rows_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows) {
   if (!c) return MSGPU_E_ARG;
   if (n_rows && !rows) return fail(c, MSGPU_E_ARG, "Unexpected nullptr.");
   if (n_rows > (1ull << 30)) return fail(c, MSGPU_E_ARG, "row table too large (%zu rows, at most 2^30)", n_rows);
@@ -864,7 +949,11 @@ int msgpu_load_rows(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows) {
   return build_index(c);
 }
 
+static int load_rows_packed_impl(msgpu_ctx *c, const msgpu_packed_rows *p);
 int msgpu_load_rows_packed(msgpu_ctx *c, const msgpu_packed_rows *p) {
+  return entry(c, ENTRY_JOB_START, [&] { return load_rows_packed_impl(c, p); });
+}
+static int load_rows_packed_impl(msgpu_ctx *c, const msgpu_packed_rows *p) {
   if (!c) return MSGPU_E_ARG;
   if (!p || (p->n_rows && (!p->rows || !p->run_start || !p->run_delta || !p->n_runs)) || (p->n_reads && !p->read_len))
     return fail(c, MSGPU_E_ARG, "Unexpected nullptr.");
@@ -895,7 +984,11 @@ int msgpu_load_rows_packed(msgpu_ctx *c, const msgpu_packed_rows *p) {
   return build_index(c);
 }
 
+static int load_rows_device_impl(msgpu_ctx *c, const void *d_rows, size_t n_rows);
 int msgpu_load_rows_device(msgpu_ctx *c, const void *d_rows, size_t n_rows) {
+  return entry(c, ENTRY_JOB_START, [&] { return load_rows_device_impl(c, d_rows, n_rows); });
+}
+static int load_rows_device_impl(msgpu_ctx *c, const void *d_rows, size_t n_rows) {
   if (!c) return MSGPU_E_ARG;
   if (n_rows && !d_rows) return fail(c, MSGPU_E_ARG, "Unexpected nullptr.");
   if (n_rows > (1ull << 30)) return fail(c, MSGPU_E_ARG, "row table too large (%zu rows, at most 2^30)", n_rows);
@@ -909,7 +1002,11 @@ int msgpu_load_rows_device(msgpu_ctx *c, const void *d_rows, size_t n_rows) {
 // words of the chain stage's chunk sums (two 64-bit words per chunk of COMPACT_CHUNK edges) for a table of up to n edges
 static size_t chunk_words(uint64_t n_edges) { return 2 * static_cast<size_t>(n_edges / COMPACT_CHUNK + 2); }
 
+static int calculate_edges_impl(msgpu_ctx *c);
 int msgpu_calculate_edges(msgpu_ctx *c) {
+  return entry(c, ENTRY_PLAIN, [&] { return calculate_edges_impl(c); });
+}
+static int calculate_edges_impl(msgpu_ctx *c) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_LOADED) return fail(c, MSGPU_E_STATE, "msgpu_calculate_edges before msgpu_load_rows");
   STAGE_HIP(c, hipSetDevice(c->device));
@@ -957,6 +1054,7 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     // visits, no scan of its own (three launches per window fewer)
     if (!c->nlists_clean) STAGE_HIP(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
     c->nlists_clean = false;
+    c->prologue_ok  = false; // (the read lists are rewritten below for this window: the index build's no longer stand)
     launch_classify_reads(st, c->read_off.as<uint32_t>(), c->read_cnt.as<uint32_t>(), c->visits.as<uint32_t>(),
                           c->cand_off.as<uint64_t>(), V, 0, 1, c->win_lo, c->win_hi, l0, l1, l2, l3,
                           scalar<uint32_t>(c, SC_NLISTS), cand_zero(c, V), scalar<unsigned long long>(c, SC_OWN));
@@ -972,6 +1070,9 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
     // that ended between k_classify_reads and k_emit_edges left them dirty
     if (!c->nlists_clean) STAGE_HIP(c, hipMemsetAsync(scalar<uint32_t>(c, SC_NLISTS), 0, 16, st));
     c->full_scan_ok = false; // (cand_off is rewritten below for this subset of the reads)
+    // ... and so are the read lists: the ones the index build's prologue classified for ITS shard no longer stand.  (Without
+    // this a context that went from the prologue's shard to another one and back ran the other shard's lists again.)
+    c->prologue_ok = false;
     if (!all_reads)
       launch_bound(st, c->read_off.as<uint32_t>(), c->read_cnt.as<uint32_t>(), c->vis16.as<uint4>(), V, c->shard,
                    c->nshards, c->win_lo, c->win_hi, c->bound.as<uint32_t>());
@@ -1130,7 +1231,11 @@ int msgpu_calculate_edges(msgpu_ctx *c) {
   return MSGPU_OK;
 }
 
+static int chaining_and_overlaps_impl(msgpu_ctx *c);
 int msgpu_chaining_and_overlaps(msgpu_ctx *c) {
+  return entry(c, ENTRY_PLAIN, [&] { return chaining_and_overlaps_impl(c); });
+}
+static int chaining_and_overlaps_impl(msgpu_ctx *c) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_EDGES || c->state == ST_RESULT)
     return fail(c, MSGPU_E_STATE, "msgpu_chaining_and_overlaps before msgpu_calculate_edges");
@@ -1319,7 +1424,11 @@ int msgpu_chain_band_width(void) { return MSGPU_CHAIN_BAND; }
 
 // The chain kernels leave the banded edges in bits 16..31 of every chunk sum and the fallbacks in the spare chunk behind the
 // last one (chunk_add, band_fallback_add); nothing on the hot path reads them, this call copies the words on demand.
+static int chain_band_counts_impl(msgpu_ctx *c, uint64_t *n_banded, uint64_t *n_fallback);
 int msgpu_get_chain_band_counts(msgpu_ctx *c, uint64_t *n_banded, uint64_t *n_fallback) {
+  return entry(c, ENTRY_PLAIN, [&] { return chain_band_counts_impl(c, n_banded, n_fallback); });
+}
+static int chain_band_counts_impl(msgpu_ctx *c, uint64_t *n_banded, uint64_t *n_fallback) {
   if (!c || !n_banded || !n_fallback) return MSGPU_E_ARG;
   *n_banded = *n_fallback = 0;
   if (c->state < ST_CHAINED || !c->chain_chunks.p) return MSGPU_OK;
@@ -1362,7 +1471,11 @@ int msgpu_get_timings(msgpu_ctx *c, msgpu_timings *out) {
   return MSGPU_OK;
 }
 
+static int copy_tables_impl(msgpu_ctx *c, void *edges, void *ems, void *orders, void *ids, hipMemcpyKind kind);
 static int copy_tables(msgpu_ctx *c, void *edges, void *ems, void *orders, void *ids, hipMemcpyKind kind) {
+  return entry(c, ENTRY_PLAIN, [&] { return copy_tables_impl(c, edges, ems, orders, ids, kind); });
+}
+static int copy_tables_impl(msgpu_ctx *c, void *edges, void *ems, void *orders, void *ids, hipMemcpyKind kind) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_EDGES) return fail(c, MSGPU_E_STATE, "no tables yet");
   if ((ems || orders || ids) && c->state < ST_CHAINED)
@@ -1384,7 +1497,11 @@ int msgpu_copy_tables_device(msgpu_ctx *c, void *d_edges, void *d_ems, void *d_o
   return copy_tables(c, d_edges, d_ems, d_orders, d_ids, hipMemcpyDeviceToDevice);
 }
 
+static int copy_reads_impl(msgpu_ctx *c, int32_t *read_len, uint32_t *read_first_line);
 int msgpu_copy_reads(msgpu_ctx *c, int32_t *read_len, uint32_t *read_first_line) {
+  return entry(c, ENTRY_PLAIN, [&] { return copy_reads_impl(c, read_len, read_first_line); });
+}
+static int copy_reads_impl(msgpu_ctx *c, int32_t *read_len, uint32_t *read_first_line) {
   if (!c) return MSGPU_E_ARG;
   if (c->state < ST_LOADED) return fail(c, MSGPU_E_STATE, "no rows loaded");
   STAGE_HIP(c, hipSetDevice(c->device));
@@ -1396,7 +1513,13 @@ int msgpu_copy_reads(msgpu_ctx *c, int32_t *read_len, uint32_t *read_first_line)
 }
 
 // findContractionEdges (src/main.cpp:183-190, 416-463) + sanityCheck (sc.cpp:29-90) over a resident edge/order table
+static int find_contraction_edges_impl(msgpu_ctx *c, const void *d_edges, uint64_t n_edges, const void *d_orders,
+                                 uint64_t n_orders, uint32_t n_reads, int64_t *contraction_order);
 int msgpu_find_contraction_edges(msgpu_ctx *c, const void *d_edges, uint64_t n_edges, const void *d_orders,
+                                 uint64_t n_orders, uint32_t n_reads, int64_t *contraction_order) {
+  return entry(c, ENTRY_CALL_START, [&] { return find_contraction_edges_impl(c, d_edges, n_edges, d_orders, n_orders, n_reads, contraction_order); });
+}
+static int find_contraction_edges_impl(msgpu_ctx *c, const void *d_edges, uint64_t n_edges, const void *d_orders,
                                  uint64_t n_orders, uint32_t n_reads, int64_t *contraction_order) {
   if (!c) return MSGPU_E_ARG;
   if ((d_edges == nullptr) != (d_orders == nullptr)) return fail(c, MSGPU_E_ARG, "pass both tables or neither");
@@ -1450,7 +1573,18 @@ int msgpu_merge_gathered(msgpu_ctx *c, const void *d_gathered, uint32_t world, c
                                  d_orders, d_ids, nullptr);
 }
 
+static int merge_gathered_impl(msgpu_ctx *c, const void *d_gathered, uint32_t world, const uint64_t *counts,
+                            uint64_t slab_bytes, uint64_t off_edges, uint64_t off_orders, uint64_t off_ids,
+                            const uint32_t *id_base, void *d_edges, void *d_orders, void *d_ids, void *hip_stream);
 int msgpu_merge_gathered_ex(msgpu_ctx *c, const void *d_gathered, uint32_t world, const uint64_t *counts,
+                            uint64_t slab_bytes, uint64_t off_edges, uint64_t off_orders, uint64_t off_ids,
+                            const uint32_t *id_base, void *d_edges, void *d_orders, void *d_ids, void *hip_stream) {
+  // with a stream of the caller's the call may come from any thread, beside the one that drives the context (rule 5 of the
+  // STREAM AND THREAD CONTRACT): it then touches no buffer of the context, under MSGPU_POISON as without it
+  if (hip_stream) return merge_gathered_impl(c, d_gathered, world, counts, slab_bytes, off_edges, off_orders, off_ids, id_base, d_edges, d_orders, d_ids, hip_stream);
+  return entry(c, ENTRY_CALL_START, [&] { return merge_gathered_impl(c, d_gathered, world, counts, slab_bytes, off_edges, off_orders, off_ids, id_base, d_edges, d_orders, d_ids, hip_stream); });
+}
+static int merge_gathered_impl(msgpu_ctx *c, const void *d_gathered, uint32_t world, const uint64_t *counts,
                             uint64_t slab_bytes, uint64_t off_edges, uint64_t off_orders, uint64_t off_ids,
                             const uint32_t *id_base, void *d_edges, void *d_orders, void *d_ids, void *hip_stream) {
   if (!c) return MSGPU_E_ARG;
@@ -1487,7 +1621,11 @@ uint64_t msgpu_wire_edges_bytes(uint64_t n_edges) { return wire_edges_bytes(n_ed
 uint64_t msgpu_wire_orders_bytes(uint64_t n_orders) { return wire_orders_bytes(n_orders); }
 uint64_t msgpu_wire_ids_bytes(uint64_t n_ids, uint32_t id_bytes) { return wire_ids_bytes(n_ids, id_bytes); }
 
+static int pack_wire_impl(msgpu_ctx *c, void *d_wire_edges, void *d_wire_orders, void *d_ids, uint32_t id_bytes);
 int msgpu_pack_wire(msgpu_ctx *c, void *d_wire_edges, void *d_wire_orders, void *d_ids, uint32_t id_bytes) {
+  return entry(c, ENTRY_PLAIN, [&] { return pack_wire_impl(c, d_wire_edges, d_wire_orders, d_ids, id_bytes); });
+}
+static int pack_wire_impl(msgpu_ctx *c, void *d_wire_edges, void *d_wire_orders, void *d_ids, uint32_t id_bytes) {
   if (!c) return MSGPU_E_ARG;
   if (id_bytes != 3 && id_bytes != 4) return fail(c, MSGPU_E_ARG, "msgpu_pack_wire: id_bytes is 3 or 4");
   if (id_bytes == 3 && c->A > (1u << 24))
@@ -1538,7 +1676,18 @@ int msgpu_unpack_wire_host(const void *wire_edges, const void *wire_orders, cons
   return MSGPU_OK;
 }
 
+static int merge_wire_impl(msgpu_ctx *c, const void *d_gathered, uint32_t world, const uint64_t *counts, uint64_t slab_bytes,
+                     uint64_t off_edges, uint64_t off_orders, uint64_t off_ids, uint32_t id_bytes, const uint32_t *id_base,
+                     void *d_edges, void *d_orders, void *d_ids, void *hip_stream);
 int msgpu_merge_wire(msgpu_ctx *c, const void *d_gathered, uint32_t world, const uint64_t *counts, uint64_t slab_bytes,
+                     uint64_t off_edges, uint64_t off_orders, uint64_t off_ids, uint32_t id_bytes, const uint32_t *id_base,
+                     void *d_edges, void *d_orders, void *d_ids, void *hip_stream) {
+  // with a stream of the caller's the call may come from any thread, beside the one that drives the context (rule 5 of the
+  // STREAM AND THREAD CONTRACT): it then touches no buffer of the context, under MSGPU_POISON as without it
+  if (hip_stream) return merge_wire_impl(c, d_gathered, world, counts, slab_bytes, off_edges, off_orders, off_ids, id_bytes, id_base, d_edges, d_orders, d_ids, hip_stream);
+  return entry(c, ENTRY_CALL_START, [&] { return merge_wire_impl(c, d_gathered, world, counts, slab_bytes, off_edges, off_orders, off_ids, id_bytes, id_base, d_edges, d_orders, d_ids, hip_stream); });
+}
+static int merge_wire_impl(msgpu_ctx *c, const void *d_gathered, uint32_t world, const uint64_t *counts, uint64_t slab_bytes,
                      uint64_t off_edges, uint64_t off_orders, uint64_t off_ids, uint32_t id_bytes, const uint32_t *id_base,
                      void *d_edges, void *d_orders, void *d_ids, void *hip_stream) {
   if (!c) return MSGPU_E_ARG;
@@ -1720,13 +1869,15 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
 int msgpu_overlap_batched_ex(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows, uint32_t n_batches, uint32_t flags,
                              msgpu_host_tables *out) {
   if (!c || !out) return MSGPU_E_ARG;
-  try { // (the dispatcher keeps a few small host containers and starts a thread: nothing C++ may leave through the C boundary)
-    return overlap_batched_impl(c, rows, n_rows, n_batches, flags, out);
-  } catch (const std::bad_alloc &) {
-    return fail(c, MSGPU_E_NOMEM, "host memory for the dispatcher's bookkeeping");
-  } catch (...) {
-    return fail(c, MSGPU_E_HIP, "unexpected C++ exception in the dispatcher");
-  }
+  return entry(c, ENTRY_JOB_START, [&] {
+    try { // (the dispatcher keeps a few small host containers and starts a thread: nothing C++ may leave through the C boundary)
+      return overlap_batched_impl(c, rows, n_rows, n_batches, flags, out);
+    } catch (const std::bad_alloc &) {
+      return fail(c, MSGPU_E_NOMEM, "host memory for the dispatcher's bookkeeping");
+    } catch (...) {
+      return fail(c, MSGPU_E_HIP, "unexpected C++ exception in the dispatcher");
+    }
+  });
 }
 static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_rows, uint32_t n_batches, uint32_t flags,
                                 msgpu_host_tables *out) {
@@ -1927,10 +2078,10 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
       guarded(hipGetLastError(), "the pack kernel");
     };
     if (w_this) {
-      guarded(c->wire_dev[set].ensure(w_total), "device block of the wire form");
+      guarded(c->wire_dev(set).ensure(w_total), "device block of the wire form");
       if (rc == MSGPU_OK && k >= 2) guarded(hipStreamWaitEvent(st, c->ev_copied[set], 0), "hipStreamWaitEvent");
       if (rc != MSGPU_OK) break;
-      pack_into(c->wire_dev[set].p, st);
+      pack_into(c->wire_dev(set).p, st);
     }
     guarded(hipEventRecord(c->ev_done[set], st), "hipEventRecord");
     if (dbg) fprintf(stderr, "[batched] window %u: launched at %.2f ms (edges %llu, orders %llu, ids %llu%s)\n", k, ms_since(t_start),
@@ -1981,7 +2132,7 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
       const uint64_t lo[3] = {0, w_off_o, w_off_i}, hi[3] = {w_off_o, w_off_i, w_total};
       for (int part = 0; part < 3 && rc == MSGPU_OK; ++part) {
         if (hi[part] > lo[part])
-          guarded(hipMemcpyAsync(static_cast<char *>(c->h_wire[set].p) + lo[part], static_cast<const char *>(c->wire_dev[set].p) + lo[part],
+          guarded(hipMemcpyAsync(static_cast<char *>(c->h_wire[set].p) + lo[part], static_cast<const char *>(c->wire_dev(set).p) + lo[part],
                                  hi[part] - lo[part], hipMemcpyDeviceToHost, cs), "copy of a wire block");
         if (part == 2 && !wire_ids3 && c->n_ids) // 4-byte ids are not packed: they go straight into the id table
           guarded(hipMemcpyAsync(static_cast<uint32_t *>(c->h_ids.p) + tot_i, c->ids.at(), c->n_ids * 4, hipMemcpyDeviceToHost, cs), "copy of the id table");
@@ -2053,7 +2204,13 @@ static int overlap_batched_impl(msgpu_ctx *c, const msgpu_row *rows, size_t n_ro
 
 // MatchMap::getEdgeMatches(edge) (libms/src/matching/MatchMap.cpp:136-159) for a list of edges, out of the EdgeMatch table
 // resident in HBM: what assemblePath reads of it (ap.cpp:631-706 via dg.cpp:99-101) is the EdgeMatches of the path edges.
+static int get_edgematches_impl(msgpu_ctx *c, const uint32_t *edge_idx, size_t n, const uint64_t **em_off,
+                          const msgpu_edgematch **ems);
 int msgpu_get_edgematches(msgpu_ctx *c, const uint32_t *edge_idx, size_t n, const uint64_t **em_off,
+                          const msgpu_edgematch **ems) {
+  return entry(c, ENTRY_CALL_START, [&] { return get_edgematches_impl(c, edge_idx, n, em_off, ems); });
+}
+static int get_edgematches_impl(msgpu_ctx *c, const uint32_t *edge_idx, size_t n, const uint64_t **em_off,
                           const msgpu_edgematch **ems) {
   if (!c || !em_off || !ems || (n && !edge_idx)) return MSGPU_E_ARG;
   *em_off = nullptr;
@@ -2112,6 +2269,20 @@ int msgpu_wait_chain_launch(msgpu_ctx *c, uint64_t count, uint32_t timeout_us) {
 int msgpu_synchronize(msgpu_ctx *c) {
   if (!c) return MSGPU_E_ARG;
   return host_sync(c, c->stream);
+}
+
+int msgpu_debug_buffers(msgpu_ctx *c, char *text, size_t text_bytes, size_t *needed) {
+  if (!c || (text_bytes && !text)) return MSGPU_E_ARG;
+  std::string t;
+  for (const msgpu_ctx::BufInfo &b : msgpu_ctx::buf_table()) {
+    const DevBuf &d = c->*b.m;
+    char          line[160];
+    snprintf(line, sizeof(line), "%s %zu %d %d %llu\n", b.name, d.cap, d.guarded ? 1 : 0, b.life == BUF_CARRY ? 1 : 0, (unsigned long long)d.gen);
+    t += line;
+  }
+  if (needed) *needed = t.size() + 1;
+  if (text_bytes) snprintf(text, text_bytes, "%s", t.c_str());
+  return MSGPU_OK;
 }
 
 int msgpu_set_deadline(msgpu_ctx *c, uint32_t timeout_ms) {

@@ -1082,7 +1082,7 @@ int msgpu_assembly_finish(msgpu_assembly *a, void *hip_stream) {
     if (!h_text) e = hipErrorOutOfMemory;
     if (e == hipSuccess) parked().lend(h_text, text_bytes + 16);
   }
-  if (e == hipSuccess && std::getenv("MSGPU_POISON")) { // see DevBuf::ensure in msgpu_api.hip
+  if (e == hipSuccess && std::getenv("MSGPU_POISON")) { // see DevBuf::ensure in msgpu_devbuf.h
     e = hipMemset(d_raw, 0xA5, a->raw_bytes + 64);
     if (e == hipSuccess) e = hipMemset(c->scr_text.p, 0xA5, text_bytes + 16);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1241,7 +1241,7 @@ int msgpu_edit_script(msgpu_seqctx *c, const void *d_a, const void *d_b, const m
   STAGE_HIP(c, D.get(&d_words, total));
   d_slab = nullptr;
   if (slab_words) STAGE_HIP(c, D.get(&d_slab, slab_words));
-  if (std::getenv("MSGPU_POISON")) { // (see DevBuf::ensure in msgpu_api.hip)
+  if (std::getenv("MSGPU_POISON")) { // (see DevBuf::ensure in msgpu_devbuf.h)
     if (slab_words) STAGE_HIP(c, hipMemsetAsync(d_slab, 0xA5, slab_words * 4, st));
     STAGE_HIP(c, hipMemsetAsync(d_words, 0xA5, (total ? total : 1) * 4, st));
     STAGE_HIP(c, hipMemsetAsync(d_list, 0xA5, n * 4, st));
@@ -1284,7 +1284,7 @@ int msgpu_extend_ends(msgpu_seqctx *c, const void *d_a, const void *d_b, const m
   STAGE_HIP(c, D.get(&d_words, n * stride));
   STAGE_HIP(c, D.get(&d_broken, 1));
   if (slab_words) STAGE_HIP(c, D.get(&d_slab, slab_words));
-  if (std::getenv("MSGPU_POISON")) { // (see DevBuf::ensure in msgpu_api.hip)
+  if (std::getenv("MSGPU_POISON")) { // (see DevBuf::ensure in msgpu_devbuf.h)
     if (slab_words) STAGE_HIP(c, hipMemsetAsync(d_slab, 0xA5, slab_words * 4, st));
     STAGE_HIP(c, hipMemsetAsync(d_words, 0xA5, n * stride * 4, st));
   }

@@ -153,7 +153,7 @@ struct DevArena { // device memory freed on every way out of a run
   size_t   pool_bytes = 0, pool_used = 0;
   static constexpr size_t ALIGN = 256;
   static size_t           aligned(size_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
-  // MSGPU_POISON (debugging, asked per call; see DevBuf::ensure in msgpu_api.hip): whatever get(), room(), reserve() and
+  // MSGPU_POISON (debugging, asked per call; see DevBuf::ensure in msgpu_devbuf.h): whatever get(), room(), reserve() and
   // rewind() hand out is filled with 0xA5, and the fill is complete when they return (the stage streams do not wait for the
   // null stream).  A block from hipMalloc, and a reservation as a whole, then lies between two guards of GUARD bytes of
   // 0xC3 that belong to the same allocation and to nobody: drop() checks those of its block, verify() those of every block

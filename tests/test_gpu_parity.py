@@ -232,8 +232,8 @@ def test_index_bin_path_and_atomic_path_agree(oracle, monkeypatch):
 def test_a_context_reused_for_growing_and_failing_jobs_stays_on_the_bin_path(oracle):
     """The bin path's bucket cursors and the scalar block are zero AT REST (no init launch, no memset per build: round 5): whoever
     consumes a counter last leaves it zero.  The corner cases of that bookkeeping on ONE context: a job with more buckets than any
-    before it but inside the buffer's slack (words no init launch has reached: poisoned when the suite runs under MSGPU_POISON=1,
-    as tools/gpu_cycle.sh does), a job the bin path refuses (duplicates: flags raised, cursors left behind), the same sizes again
+    before it but inside the buffer's slack (words no init launch has reached; tests/test_gpu_poisoned_overlap.py runs this check
+    under MSGPU_POISON, where the buffer has no slack and the larger job gets a block of 0xA5), a job the bin path refuses (duplicates: flags raised, cursors left behind), the same sizes again
     afterwards, and back-to-back loads without the later stages -- every loader-shaped job must take the bin path and give the
     oracle's tables."""
     from muchsalsa_amd import _lib, overlap, synth
@@ -467,6 +467,23 @@ def test_shards_union_equals_single_gpu(oracle, world):
     canon["edges"]["em_off"] = 0
     canon["ems"] = want["ems"] = np.zeros(0, dtype=full["ems"].dtype)
     assert_tables_equal(canon, want, "merged world=%d" % world)
+
+
+def test_one_context_goes_from_shard_to_shard_and_back(oracle):
+    """The index build classifies the owner reads of the context's shard (the prologue); a later msgpu_calculate_edges for
+    another shard writes its own read lists over them.  Back on the first shard the prologue's lists no longer stand: the
+    candidate stage must classify again (it once ran the other shard's lists and returned the other shard's tables)."""
+    from muchsalsa_amd import distributed as D, overlap, synth
+    rows = synth.synth_rows(300, 3000, 900, 1)
+    full = oracle.overlap(rows)
+    with overlap.OverlapContext(0) as ctx:
+        ctx.set_shard(0, 2)
+        ctx.load_rows(rows)
+        for r in (0, 1, 0, 0, 1):
+            ctx.set_shard(r, 2)
+            ctx.calculate_edges()
+            ctx.chaining_and_overlaps()
+            assert_tables_equal(ctx.tables(), D.shard_view_host(full, r, 2), "shard %d of 2" % r)
 
 
 @pytest.mark.parametrize("world", [1, 3, 8])
