@@ -1046,8 +1046,8 @@ void        msgpu_kf_result_free(msgpu_kf_result *r);
 
 /* ==== short-read unitig assembly: the step behind the k-mer filter, `abyss-pe ... unitigs` and the awk cut at MINLENGTH ===
  * (pipeline/pipeline.sh).  ABySS is not part of the reference tree, so the stage is defined by these
- * rules and checked against their plain-Python restatement (tests/ug_oracle.py), not against ABySS.  Parameters: k (2..64),
- * min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500).
+ * rules and checked against their plain-Python restatement (tests/ug_oracle.py), not against ABySS.  Parameters: k (2..64,
+ * or 2..128 after msgpu_ug_set_wide), min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500).
  *  1. input: one or two FASTQ files.  The FASTQ rules and the window rules are rules 1 and 2 of the k-mer abundance filter,
  *     word for word, error code, file and line included.  The files are not pairs: their record counts may differ and the
  *     second path may be NULL.  count(x) = windows of all files whose canonical k-mer is x, exact.
@@ -1171,7 +1171,7 @@ typedef struct msgpu_ug_round {
 } msgpu_ug_round;
 typedef struct msgpu_ug_unitig { /* in output order: entry i is the unitig with id i */
   uint64_t length, coverage;
-  uint64_t first_hi, first_lo;   /* its first k-mer (upper half 0 for k <= 32) */
+  uint64_t first_hi, first_lo;   /* its first k-mer (upper half 0 for k <= 32; above k = 64 its low 128 bits) */
   uint64_t offset;               /* of its sequence in the all text */
   uint32_t cyclic, reserved;
 } msgpu_ug_unitig;
@@ -1224,6 +1224,18 @@ typedef struct msgpu_ug_graph_stats {
   float    reserved;
 } msgpu_ug_graph_stats;
 int         msgpu_ug_set_graph(msgpu_ugctx *ctx, int on);
+/* k up to 128, on request.  msgpu_ug_set_wide switches the wide keys on (on != 0) or off (0, what a new context has) for every
+ * later msgpu_ug_run / msgpu_ug_run_pair on the context, until it is set again.  Off: k above 64 is MSGPU_E_ARG ("k = 65 is
+ * outside 2..64"), and every error, output, table, count and kernel launch is what it was.  On: the upper bound of k is 128
+ * (k = 129 is MSGPU_E_ARG naming the figure); k <= 64 runs what it runs with the switch off and gives the same bytes;
+ * k = 65..96 runs on keys of three 64-bit words, k = 97..128 on keys of four.  Rules 1-10 hold as they stand.
+ * msgpu_ug_result_first_kmers gives the whole first k-mer of every unitig at any k: *words holds *words_per_kmer words per
+ * unitig, least significant first, for the *n unitigs in output order; *words_per_kmer is 1 for k <= 32, 2 for k <= 64, 3 for
+ * k <= 96 and 4 above.  The array lives as long as the result.  msgpu_ug_result_peak_bytes gives the most device memory the
+ * run's own arena held at once, in bytes (the files of a pair are the pair's and are not counted; 0 for NULL). */
+int         msgpu_ug_set_wide(msgpu_ugctx *ctx, int on);
+int         msgpu_ug_result_first_kmers(const msgpu_ug_result *r, const uint64_t **words, uint32_t *words_per_kmer, uint64_t *n);
+uint64_t    msgpu_ug_result_peak_bytes(const msgpu_ug_result *r);
 int         msgpu_ug_result_links(const msgpu_ug_result *r, msgpu_ug_graph_stats *out, const msgpu_ug_link **links, uint64_t *n);
 #define MSGPU_UG_TEXT_ALL 0 /* every record */
 #define MSGPU_UG_TEXT_CUT 1 /* the records with length >= min_length */

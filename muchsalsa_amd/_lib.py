@@ -597,6 +597,10 @@ SYMBOLS = [
     ("msgpu_ug_result_bubbles", C.c_int, [C.c_void_p, C.POINTER(UgBubbleStats), C.POINTER(C.POINTER(UgBubbleRound)),
                                           C.POINTER(C.c_uint64)]),
     ("msgpu_ug_set_graph", C.c_int, [C.c_void_p, C.c_int]),
+    ("msgpu_ug_set_wide", C.c_int, [C.c_void_p, C.c_int]),
+    ("msgpu_ug_result_peak_bytes", C.c_uint64, [C.c_void_p]),
+    ("msgpu_ug_result_first_kmers", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_links", C.c_int, [C.c_void_p, C.POINTER(UgGraphStats), C.POINTER(C.POINTER(UgLink)), C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_text", C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     ("msgpu_ug_result_free", None, [C.c_void_p]),

@@ -18,12 +18,12 @@
 
 #include "msgpu.h"
 #include "msgpu_internal.h"
+#include "msgpu_kmer_wide.h"
 #include "msgpu_stage.h"
 
 namespace msgpu {
 
-typedef unsigned __int128      kf_u128;
-typedef unsigned long long     kf_ull;
+typedef unsigned long long     kf_ull; // (kf_u128 and the key of three and of four words: msgpu_kmer_wide.h)
 constexpr uint32_t KF_TILE   = 4096;  // bytes of a file per workgroup in the line kernels (16 per thread)
 constexpr uint32_t KF_BINS   = 4096;  // hash bins the partitions are cut from
 constexpr uint32_t KF_KEEP   = 5;     // a k-mer below this count can never reach the threshold (upper >= 5)
@@ -51,10 +51,14 @@ __device__ inline uint64_t kf_mix(uint64_t lo, uint64_t hi) {
 }
 __device__ inline uint64_t kf_hash(uint64_t k) { return kf_mix(k, 0); }
 __device__ inline uint64_t kf_hash(kf_u128 k) { return kf_mix(static_cast<uint64_t>(k), static_cast<uint64_t>(k >> 64)); }
+// every word of a wider key, folded pairwise
+__device__ inline uint64_t kf_hash(const KfWide<3> &k) { return kf_mix(kf_mix(k.w[0], k.w[1]), k.w[2]); }
+__device__ inline uint64_t kf_hash(const KfWide<4> &k) { return kf_mix(kf_mix(k.w[0], k.w[1]), kf_mix(k.w[2], k.w[3])); }
 template <class K> __device__ inline uint32_t kf_bin(K key) { return static_cast<uint32_t>(kf_hash(key) >> 52); } // KF_BINS = 2^12
 __device__ inline uint32_t kf_part(uint32_t bin, uint32_t P) { return (bin * P) >> 12; }
 
-// the rolling window: step() takes one byte of a sequence line and says whether a window ends on it
+// the rolling window: step() takes one byte of a sequence line and says whether a window ends on it (a key of W words has a
+// step of its own, msgpu_kmer_wide.h)
 template <class K> struct KfRoll {
   K        fw = 0, rc = 0, mask;
   uint32_t run = 0, k;
@@ -175,6 +179,37 @@ template <class K> __device__ inline uint32_t kf_find(const K *keys, const uint3
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
+// rocPRIM's radix sorts over the key's bits [0, end_bit): a built-in integer as it is, a key of W words through a decomposer
+// whose tuple names the words from the top one down, so that bit 0 is bit 0 of w[0] and the bits at and above end_bit stay
+// out of the sort
+template <int W> struct KfWideDecomposer;
+template <> struct KfWideDecomposer<3> {
+  __host__ __device__ rocprim::tuple<uint64_t &, uint64_t &, uint64_t &> operator()(KfWide<3> &key) const {
+    return rocprim::tuple<uint64_t &, uint64_t &, uint64_t &>(key.w[2], key.w[1], key.w[0]);
+  }
+};
+template <> struct KfWideDecomposer<4> {
+  __host__ __device__ rocprim::tuple<uint64_t &, uint64_t &, uint64_t &, uint64_t &> operator()(KfWide<4> &key) const {
+    return rocprim::tuple<uint64_t &, uint64_t &, uint64_t &, uint64_t &>(key.w[3], key.w[2], key.w[1], key.w[0]);
+  }
+};
+template <class K, class Size>
+hipError_t kf_sort_keys(void *tmp, size_t &bytes, rocprim::double_buffer<K> &db, Size n, int end_bit, hipStream_t st) {
+  return rocprim::radix_sort_keys(tmp, bytes, db, n, 0, end_bit, st);
+}
+template <int W, class Size>
+hipError_t kf_sort_keys(void *tmp, size_t &bytes, rocprim::double_buffer<KfWide<W>> &db, Size n, int end_bit, hipStream_t st) {
+  return rocprim::radix_sort_keys(tmp, bytes, db, n, KfWideDecomposer<W>{}, 0u, static_cast<unsigned int>(end_bit), st);
+}
+template <class K, class V, class Size>
+hipError_t kf_sort_pairs(void *tmp, size_t &bytes, K *kin, K *kout, V *vin, V *vout, Size n, int end_bit, hipStream_t st) {
+  return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, n, 0, end_bit, st);
+}
+template <int W, class V, class Size>
+hipError_t kf_sort_pairs(void *tmp, size_t &bytes, KfWide<W> *kin, KfWide<W> *kout, V *vin, V *vout, Size n, int end_bit, hipStream_t st) {
+  return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, n, KfWideDecomposer<W>{}, 0u, static_cast<unsigned int>(end_bit), st);
+}
+
 struct KfFile {
   uint8_t  *d = nullptr;
   uint64_t  size = 0, n_lines = 0;
@@ -272,7 +307,7 @@ int kf_count(StageCtx *c, DevArena &D, StageClock &clock, const KfIn &in, const 
   size_t need_sort = 0, need_rle = 0;
   {
     rocprim::double_buffer<K> db(d_a, d_b);
-    STAGE_HIP(c, rocprim::radix_sort_keys(nullptr, need_sort, db, largest, 0, 2 * k, st));
+    STAGE_HIP(c, kf_sort_keys(nullptr, need_sort, db, largest, 2 * k, st));
     STAGE_HIP(c, rocprim::run_length_encode(nullptr, need_rle, d_a, static_cast<unsigned int>(largest), d_b, d_rl, d_nruns, st));
   }
   const size_t tmp_bytes = std::max(need_sort, need_rle);
@@ -289,7 +324,7 @@ int kf_count(StageCtx *c, DevArena &D, StageClock &clock, const KfIn &in, const 
     rocprim::double_buffer<K> db(d_a, d_b);
     size_t                    tb = tmp_bytes;
     STAGE_HIP(c, clock.begin(ms.sort));
-    STAGE_HIP(c, rocprim::radix_sort_keys(d_tmp, tb, db, n, 0, 2 * k, st));
+    STAGE_HIP(c, kf_sort_keys(d_tmp, tb, db, n, 2 * k, st));
     STAGE_HIP(c, clock.end());
     K *sorted = db.current(), *uniq = db.alternate();
     tb = tmp_bytes;
@@ -371,10 +406,10 @@ int kf_gather_sorted(StageCtx *c, DevArena &D, std::vector<KfChunk<K>> &chunks, 
                          ch.n, least, d_k_in, d_c_in, n, d_cur);
     STAGE_HIP(c, hipGetLastError());
     size_t need = 0;
-    STAGE_HIP(c, rocprim::radix_sort_pairs(nullptr, need, d_k_in, d_k, d_c_in, d_c, n, 0, 2 * k, st));
+    STAGE_HIP(c, kf_sort_pairs(nullptr, need, d_k_in, d_k, d_c_in, d_c, n, 2 * k, st));
     uint8_t *tmp;
     STAGE_HIP(c, D.get(&tmp, need));
-    STAGE_HIP(c, rocprim::radix_sort_pairs(tmp, need, d_k_in, d_k, d_c_in, d_c, n, 0, 2 * k, st));
+    STAGE_HIP(c, kf_sort_pairs(tmp, need, d_k_in, d_k, d_c_in, d_c, n, 2 * k, st));
     STAGE_HIP(c, hipStreamSynchronize(st));
     D.drop(tmp);
     D.drop(d_k_in);

@@ -50,11 +50,7 @@ template <class K> struct UgGraph { // the solid set as the kernels see it
   K               kmask;
 };
 
-// the 2-bit groups of a word in reverse order
-__device__ inline uint64_t ug_rev2(uint64_t x) {
-  x = __brevll(x);
-  return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-}
+// the reverse complement (ug_rev2, and ug_rc of a key of W words: msgpu_kmer_wide.h)
 __device__ inline uint64_t ug_rc(uint64_t x, int k) { return (~ug_rev2(x)) >> (64 - 2 * k); }
 __device__ inline kf_u128 ug_rc(kf_u128 x, int k) {
   const kf_u128 f = (static_cast<kf_u128>(ug_rev2(static_cast<uint64_t>(x))) << 64) | ug_rev2(static_cast<uint64_t>(x >> 64));
@@ -74,6 +70,15 @@ template <class K> __device__ inline uint32_t ug_node(const UgGraph<K> &g, K t) 
 }
 template <class K> __device__ inline K ug_succ(const UgGraph<K> &g, K s, uint32_t c) { return ((s << 2) | static_cast<K>(c)) & g.kmask; }
 template <class K> __device__ inline K ug_pred(const UgGraph<K> &g, K s, uint32_t c) { return (s >> 2) | (static_cast<K>(c) << g.top); }
+// the same two steps on a key of W words: carried shifts by 2, the mask's top word, the first base's place in the top word
+template <int W> __device__ inline KfWide<W> ug_succ(const UgGraph<KfWide<W>> &g, KfWide<W> s, uint32_t c) {
+  s.push_low(c, g.kmask.w[W - 1]);
+  return s;
+}
+template <int W> __device__ inline KfWide<W> ug_pred(const UgGraph<KfWide<W>> &g, KfWide<W> s, uint32_t c) {
+  s.push_high(c, g.top - 64 * (W - 1));
+  return s;
+}
 // the successor / predecessor bits of an oriented node from its k-mer's byte: the reverse strand's successor by base c is
 // the mirror of the canonical string's predecessor by base 3 - c
 __device__ inline uint32_t ug_out(uint32_t byte, uint32_t o) { return (o & 1) ? ug_rev4(byte >> 4) : (byte & 0xfu); }
@@ -399,11 +404,11 @@ __global__ __launch_bounds__(256) void k_ug_write(UgGraph<K> g, const uint32_t *
   const uint32_t d = dist[o];
   if (d) {
     const uint64_t w = at + d + g.k - 1;
-    if (w < cap) text[w] = "ACGT"[static_cast<uint32_t>(s) & 3u];
+    if (w < cap) text[w] = "ACGT"[kf_base(s, 0)];
     return;
   }
   if (at + n_kmers[u] + g.k > cap) return;
-  for (int j = 0; j < g.k; ++j) text[at + j] = "ACGT"[static_cast<uint32_t>(s >> (2 * (g.k - 1 - j))) & 3u];
+  for (int j = 0; j < g.k; ++j) text[at + j] = "ACGT"[kf_base(s, g.k - 1 - j)];
   text[at + n_kmers[u] + g.k - 1] = close;
 }
 
@@ -531,6 +536,7 @@ struct msgpu_ugctx : msgpu::StageCtx {
   ScalarBlock sc;
   uint32_t    bubble = 0; // rule 9's parameter (msgpu_ug_set_bubbles)
   bool        graph = false; // rule 10 (msgpu_ug_set_graph)
+  bool        wide = false; // k up to 128 (msgpu_ug_set_wide)
   int         open() { return sc.create(); }
 };
 
@@ -540,6 +546,9 @@ struct msgpu_ug_result {
   msgpu_ug_bubble_stats              bubble_stats{};
   std::vector<msgpu_ug_bubble_round> bubble_rounds;
   std::vector<msgpu_ug_unitig> units;
+  std::vector<uint64_t>        first_words; // first_w words per unitig, least significant first (msgpu_ug_result_first_kmers)
+  uint32_t                     first_w = 1;
+  uint64_t                     bytes_peak = 0; // of the run's arena (msgpu_ug_result_peak_bytes)
   char                        *all = nullptr; // page-locked
   uint64_t                     all_len = 0;
   std::string                  cut;
@@ -624,8 +633,7 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
   rc = kf_gather_sorted<K>(c, D, chunks, prm.min_count, n, k, d_cur, &d_keys, &d_cnt, &d_slots, &slots_n);
   if (rc != MSGPU_OK) return rc;
   STAGE_HIP(c, clock.end());
-  UgGraph<K> g{d_keys, d_slots, slots_n - 1, n, k, 2 * (k - 1),
-               (2 * k == static_cast<int>(sizeof(K) * 8)) ? ~static_cast<K>(0) : ((static_cast<K>(1) << (2 * k)) - 1)};
+  UgGraph<K> g{d_keys, d_slots, slots_n - 1, n, k, 2 * (k - 1), kf_mask<K>(k)};
 
   // ---- neighbour bytes, tip rounds
   uint8_t *d_alive, *d_adj, *d_mark;
@@ -843,7 +851,9 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
     STAGE_HIP(c, ug_zero_scalar(c, UG_SC_UNITS));
     hipLaunchKernelGGL((k_ug_heads<K, true>), dim3(grid256(n2)), dim3(256), 0, st, g, d_next, d_p, d_first[0], d_head[0], U, d_units_n);
     STAGE_HIP(c, hipGetLastError());
-    STAGE_HIP(c, stage_sort_pairs(D, st, d_first[0], d_first[1], d_head[0], d_head[1], U, 2 * k));
+    STAGE_HIP(c, stage_rocprim(D, [&](void *t, size_t &b) {
+                return kf_sort_pairs(t, b, d_first[0], d_first[1], d_head[0], d_head[1], static_cast<unsigned int>(U), 2 * k, st);
+              }));
     hipLaunchKernelGGL(k_ug_units, dim3(grid256(U)), dim3(256), 0, st, U, d_head[1], d_p, d_d, d_cyc, d_cyc_last, d_unit_of, d_nk,
                        d_cyclic);
     hipLaunchKernelGGL(k_ug_cover, dim3(grid256(n2)), dim3(256), 0, st, n2, d_p, d_unit_of, d_cnt, d_cover);
@@ -862,6 +872,8 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
     first.resize(U);
     seq_off.resize(U);
     res->units.resize(U);
+    res->first_w = sizeof(K) / 8;
+    res->first_words.resize(U * (sizeof(K) / 8));
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   STAGE_HIP(c, clock.begin(&S.copy_ms));
   if (U) {
@@ -887,6 +899,7 @@ int ug_stage(msgpu_ugctx *c, DevArena &D, const KfFile *F, const uint8_t *d_drop
       T.cyclic   = cyclic[u];
       T.reserved = 0;
       key_split(first[u], T.first_hi, T.first_lo);
+      key_words(first[u], res->first_words.data() + u * (sizeof(K) / 8));
       head_len[u] = static_cast<uint32_t>(snprintf(buf, sizeof(buf), ">%u %llu %llu\n", u, static_cast<kf_ull>(T.length), cover[u]));
       heads.append(buf, head_len[u]);
       T.offset   = total + head_len[u];
@@ -1099,8 +1112,8 @@ int         msgpu_ug_error_file(const msgpu_ugctx *c) { return c ? c->err_file :
 // the parameters as a run uses them; the context takes the error
 static int ug_params(msgpu_ugctx *c, const msgpu_ug_params *params, msgpu_ug_params &prm) {
   prm = *params;
-  if (prm.k < 2 || prm.k > 64) {
-    snprintf(c->err, sizeof(c->err), "k = %d is outside 2..64", prm.k);
+  if (prm.k < 2 || prm.k > (c->wide ? 128 : 64)) {
+    snprintf(c->err, sizeof(c->err), "k = %d is outside 2..%d", prm.k, c->wide ? 128 : 64);
     return MSGPU_E_ARG;
   }
   if (prm.trim == -1) prm.trim = prm.k;
@@ -1156,13 +1169,16 @@ int msgpu_ug_run_pair(msgpu_ugctx *c, const msgpu_ug_params *params, const msgpu
     if (n_pairs) STAGE_HIP(c, hipMemcpyAsync(d_dropped, dropped, n_pairs, hipMemcpyHostToDevice, c->stream));
     STAGE_HIP(c, hipStreamSynchronize(c->stream)); // (the caller's array may go when the call returns)
   }
-  rc = prm.k <= 32 ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get())
-                   : ug_stage<kf_u128>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get());
+  rc = prm.k <= 32   ? ug_stage<uint64_t>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get())
+       : prm.k <= 64 ? ug_stage<kf_u128>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get())
+       : prm.k <= 96 ? ug_stage<KfWide<3>>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get())
+                     : ug_stage<KfWide<4>>(c, D, F, d_dropped, prm, c->bubble, c->graph, budget_bytes, res.get());
   if (rc != MSGPU_OK) {
     (void)hipStreamSynchronize(c->stream); // (nothing of the run is still reading the pair when the arena goes)
     return rc;
   }
   if (stage_verify(c, D) != MSGPU_OK) return MSGPU_E_HIP;
+  res->bytes_peak       = D.peak;
   S.n_lost_publications = c->sc.lost - lost0;
   S.wall_ms             = wall.ms();
   *out                  = res.release();
@@ -1211,6 +1227,22 @@ int msgpu_ug_set_graph(msgpu_ugctx *c, int on) {
   c->graph = on != 0;
   return MSGPU_OK;
 }
+
+int msgpu_ug_set_wide(msgpu_ugctx *c, int on) {
+  if (!c) return MSGPU_E_ARG;
+  c->wide = on != 0;
+  return MSGPU_OK;
+}
+
+int msgpu_ug_result_first_kmers(const msgpu_ug_result *r, const uint64_t **words, uint32_t *words_per_kmer, uint64_t *n) {
+  if (!r || !words || !words_per_kmer || !n) return MSGPU_E_ARG;
+  *words          = r->first_words.data();
+  *words_per_kmer = r->first_w;
+  *n              = r->units.size();
+  return MSGPU_OK;
+}
+
+uint64_t msgpu_ug_result_peak_bytes(const msgpu_ug_result *r) { return r ? r->bytes_peak : 0; }
 
 int msgpu_ug_result_links(const msgpu_ug_result *r, msgpu_ug_graph_stats *out, const msgpu_ug_link **links, uint64_t *n) {
   if (!r || !out || !links || !n) return MSGPU_E_ARG;

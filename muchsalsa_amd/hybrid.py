@@ -5,7 +5,8 @@ every step of the reference's ``pipeline/pipeline.sh`` as the GPU stage of this 
 
 takes the script's seven to nine positional arguments in its order (pipeline.sh:38-57) and prints one JSON line of per-stage
 counts and seconds.  ``bloom_mem`` is accepted and ignored: the counts are exact.  jellyfish, bbduk, ABySS and minimap2 are
-not needed.  The steps, after the inputs are checked to be non-empty files (pipeline.sh:125):
+not needed.  k_assembly may be 2..128: above 64 the unitig assembly's wide keys are switched on (``run(..., wide=None)``); k_filter
+stays 2..64.  The steps, after the inputs are checked to be non-empty files (pipeline.sh:125):
 
  1. the Illumina pair is opened: both files go to device memory once (kmer_filter.Pair);
  2. the k-mer abundance filter runs on it at k_filter; ``report.txt`` is created with the threshold line (pipeline.sh:136-151);
@@ -98,7 +99,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None, evaluate=None):
+        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None, evaluate=None, wide=None):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -122,7 +123,9 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     stage ``"evaluate"`` (muchsalsa_amd.evaluate): the Illumina pair is opened again (it is not kept resident through the mapping
     stages), one table of its k-mers is built at k = K, and the assembly, and the polished files where they were written, are
     evaluated on it into EVALUATION_NAME (QV per record and in total, completeness), named by ``files["evaluation"]``; every
-    other file is the same."""
+    other file is the same.  ``wide`` (None: on exactly when k_assembly > 64) is the unitig assembly's switch for k up to 128
+    (muchsalsa_amd.unitigs; pipeline.sh's README recommends k_assembly = 90); False keeps the refusal of k_assembly > 64.  The
+    k-mer filter and the evaluation stay at k <= 64: their k are parameters of their own."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
@@ -152,7 +155,8 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     try:
         stage("filter", kmer_filter.run, int(k_filter), None, None, files["report"], None, None, pair=pair, tables=tables)
         stage("unitigs", unitigs.run, int(k_assembly), None, None, files["unitigs"], files["unitigs_cut"], pair=pair,
-              dropped=tables["verdict"], min_length=MIN_LENGTH, bubble=bubble, gfa=gfa_path)
+              dropped=tables["verdict"], min_length=MIN_LENGTH, bubble=bubble, gfa=gfa_path,
+              wide=int(k_assembly) > 64 if wide is None else bool(wide))
     finally:
         pair.__exit__(None, None, None)
     index = mapper.Index(reads, device=device)

@@ -3,12 +3,14 @@ at MINLENGTH behind it write in the reference pipeline -- ``NAME-unitigs.fa`` an
 FASTQ files (the k-mer filter's outputs) alone.
 
     python -m muchsalsa_amd.unitigs <k> <in_1.fq> <in_2.fq> <out_all.fa> <out_cut.fa>
-            [--min-count N] [--trim N] [--min-length N] [--budget-mb N] [--bubble N] [--gfa F]
+            [--min-count N] [--trim N] [--min-length N] [--budget-mb N] [--bubble N] [--gfa F] [--wide]
 
 prints one JSON line of counts and seconds; with ``--gfa F`` the unitig graph is written to F as GFA 1 (rule 10), where
-``abyss-pe graph=gfa`` leaves its adjacency graph beside the FASTA.  ABySS is not needed, and it is not part of the reference tree: the stage is
+``abyss-pe graph=gfa`` leaves its adjacency graph beside the FASTA; ``--wide`` moves the upper bound of k from 64 to 128
+(``run(..., wide=True)``; msgpu_ug_set_wide: k = 65..96 runs on keys of three 64-bit words, k = 97..128 on keys of four, k <= 64
+as without it).  ABySS is not needed, and it is not part of the reference tree: the stage is
 defined by the rules below and checked, without tolerance, against the tests' restatement in plain Python
-(tests/ug_oracle.py), not against ABySS.  The rules (include/msgpu.h, "short-read unitig assembly"); parameters k (2..64),
+(tests/ug_oracle.py), not against ABySS.  The rules (include/msgpu.h, "short-read unitig assembly"); parameters k (2..64, or 2..128 after msgpu_ug_set_wide),
 min_count (>= 1, default 2), trim (>= 0, default k: the longest tip, in k-mers), min_length (default 500, the pipeline's
 MINLENGTH), bubble (0..4096, default 0 = off: rule 9):
 
@@ -124,7 +126,7 @@ class UnitigError(StageError):
 
 
 def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_length=500, budget_mb=None, tables=None,
-        timings=None, pair=None, dropped=None, bubble=None, gfa=None):
+        timings=None, pair=None, dropped=None, bubble=None, gfa=None, wide=False):
     """The whole stage: writes ``out_all`` and ``out_cut``; returns the counts.  ``in_2`` may be None.  ``trim`` None: k.
     With ``pair`` (an entered kmer_filter.Pair) the stage runs on the resident files on the pair's device and ``in_1`` /
     ``in_2`` / ``device`` are not read; ``dropped`` (bytes or a uint8 array, one per pair, 1 = dropped) is the mask.
@@ -137,7 +139,10 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
     ``bubble_rounds`` [(tip rounds before it, forks, bubbles, branches removed, k-mers removed)] and ``timings``
     ``bubble_forks`` / ``bubble_walk`` / ``bubble_adjacency`` (seconds).  ``gfa`` (None: off) is a path: rule 10's text is
     written there, the dict then holds ``links``, ``link_self_mirror``, ``dead_ends`` and ``gfa_bytes``, ``tables`` receives
-    ``links`` [(from, from_rev, to, to_rev)] and ``timings`` ``graph_links`` / ``graph_sort`` / ``graph_text`` (seconds)."""
+    ``links`` [(from, from_rev, to, to_rev)] and ``timings`` ``graph_links`` / ``graph_sort`` / ``graph_text`` (seconds).
+    ``wide`` = True moves the upper bound of k from 64 to 128 (msgpu_ug_set_wide); the first k-mer in ``unitigs`` is the whole
+    k-mer at any k (msgpu_ug_result_first_kmers).  ``timings`` also receives ``peak_bytes``, not a time: the most device memory the run's
+    own arena held at once (msgpu_ug_result_peak_bytes; a pair's files are not counted)."""
     L = _lib.lib()
     t0 = time.perf_counter()
     if dropped is not None and pair is None:
@@ -156,6 +161,8 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
             stage.check(L.msgpu_ug_set_bubbles(stage.ctx, bubble))
         if gfa is not None:
             stage.check(L.msgpu_ug_set_graph(stage.ctx, 1))
+        if wide:
+            stage.check(L.msgpu_ug_set_wide(stage.ctx, 1))
         with (stage.run(C.byref(prm), os.fsencode(in_1), None if in_2 is None else os.fsencode(in_2), 0, budget) if pair is None
               else stage.run(C.byref(prm), pair.handle, mask, 0 if mask is None else len(mask), 0, budget, fn="run_pair")) as res:
             st = _lib.UgStats()
@@ -173,8 +180,13 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
                 L.msgpu_ug_result_unitigs(res, C.byref(up), C.byref(n))
                 tables["rounds"] = rounds
                 tables["bubble_rounds"] = bubble_rounds
-                tables["unitigs"] = [(int(u.length), int(u.coverage), (int(u.first_hi) << 64) | int(u.first_lo), int(u.offset),
-                                      int(u.cyclic)) for u in (up[i] for i in range(n.value))]
+                fp, fw = C.POINTER(C.c_uint64)(), C.c_uint32()
+                L.msgpu_ug_result_first_kmers(res, C.byref(fp), C.byref(fw), C.byref(n))
+                w = fw.value
+                first = [sum(int(fp[i * w + j]) << (64 * j) for j in range(w)) for i in range(n.value)]
+                tables["unitigs"] = [(int(u.length), int(u.coverage), first[i], int(u.offset), int(u.cyclic))
+                                     for i, u in ((i, up[i]) for i in range(n.value))]
+            peak = int(L.msgpu_ug_result_peak_bytes(res))
             gs, lp = _lib.UgGraphStats(), C.POINTER(_lib.UgLink)()
             L.msgpu_ug_result_links(res, C.byref(gs), C.byref(lp), C.byref(n))
             if tables is not None and gfa is not None:
@@ -192,7 +204,7 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
         timings.update({"bubble_" + name[:-3]: getattr(bs, name) / 1e3 for name in ("forks_ms", "walk_ms", "adjacency_ms")})
         if gfa is not None:
             timings.update({"graph_" + name[:-3]: getattr(gs, name) / 1e3 for name in ("links_ms", "sort_ms", "text_ms")})
-        timings.update({"files": t_write, "total": time.perf_counter() - t0, "round_seconds": round_s})
+        timings.update({"files": t_write, "total": time.perf_counter() - t0, "round_seconds": round_s, "peak_bytes": peak})
     graph = {} if gfa is None else {"links": int(gs.n_links), "link_self_mirror": int(gs.n_self_mirror),
                                     "dead_ends": int(gs.n_dead_ends), "gfa_bytes": int(gs.gfa_bytes)}
     return dict({"k": int(st.k), "min_count": int(st.min_count), "trim": int(st.trim), "min_length": int(st.min_length),
@@ -210,6 +222,9 @@ def run(k, in_1, in_2, out_all, out_cut, device=0, min_count=2, trim=None, min_l
 def main(argv):
     args = list(argv)
     opts = {"--min-count": 2, "--trim": None, "--min-length": 500, "--budget-mb": None, "--bubble": 0, "--gfa": None}
+    wide = "--wide" in args
+    if wide:
+        args.remove("--wide")
     ok = True
     for name in opts:
         if name in args:
@@ -233,7 +248,7 @@ def main(argv):
     timings = {}
     out = run(k, args[1], args[2], args[3], args[4], min_count=opts["--min-count"], trim=opts["--trim"],
               min_length=opts["--min-length"], budget_mb=opts["--budget-mb"], timings=timings, bubble=opts["--bubble"],
-              gfa=opts["--gfa"])
+              gfa=opts["--gfa"], wide=wide)
     rs = timings.pop("round_seconds")
     out["seconds"] = {key: round(v, 4) for key, v in timings.items()}
     out["round_seconds"] = [[round(a, 5), round(b, 5)] for a, b in rs]

@@ -7,10 +7,11 @@ tests' plain-Python restatement (tests/ug_oracle.py -- a restatement, NOT ABySS)
 (--oracle-genome; 0 = not at all) as orientation, not as a claim.  --diploid takes the input from synth.diploid_workload
 instead (two haplotypes with a variant every 400 bases, --coverage / 2 each, one file), --bubble N runs the stage with rule 9
 (bubble popping) at N and reports its fork, walk and neighbour-byte times and its rounds, --gfa with rule 10 (the unitig
-graph) and reports its links, sort and text times.  Prints one JSON object; --out also writes it to a file.
+graph) and reports its links, sort and text times, --wide with the keys of three and of four words switched on (k up to 128;
+above k = 64 it is needed; the read length left to itself is then at least 2 k, so that the reads hold k-mers).  Prints one JSON object; --out also writes it to a file.
 
     python tools/unitigs_timing.py [--genome 1000000 --coverage 40 --read-len 150 -k 31] [--clean] [--diploid] [--bubble N]
-                                   [--gfa] [--repeat 3] [--out F]
+                                   [--gfa] [--wide] [--repeat 3] [--out F]
 """
 import argparse
 import json
@@ -36,18 +37,25 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome", type=int, default=1000000)
     ap.add_argument("--coverage", type=int, default=40)
-    ap.add_argument("--read-len", type=int, default=150)
+    ap.add_argument("--read-len", type=int, default=None, help="150, or 2 k above k = 75: the reads must hold k-mers")
     ap.add_argument("-k", type=int, default=31)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--clean", action="store_true", help="no repeats, no errors, no N: one chain as long as the genome")
     ap.add_argument("--diploid", action="store_true", help="two haplotypes with a variant every 400 bases (synth.diploid_workload)")
     ap.add_argument("--bubble", type=int, default=0, help="rule 9's parameter (0: off)")
     ap.add_argument("--gfa", action="store_true", help="rule 10: the unitig graph is written as well")
+    ap.add_argument("--wide", action="store_true", help="k up to 128 (msgpu_ug_set_wide)")
     ap.add_argument("--repeat", type=int, default=3, help="stage runs (fresh process each); the fastest is reported")
     ap.add_argument("--oracle-genome", type=int, default=0, help="genome of the shape the restatement is timed on")
     ap.add_argument("--timeout", type=int, default=600)
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.read_len is None:
+        a.read_len = max(150, 2 * a.k)
+    if a.k > 64 and not a.wide:
+        ap.error("k = %d needs --wide" % a.k)
+    if a.read_len <= a.k:
+        ap.error("reads of %d bases hold no %d-mer" % (a.read_len, a.k))
     from muchsalsa_amd import synth
     extra = dict(families=0, copies=0, error=0.0, n_frac=0.0) if a.clean else {}
     t0 = time.perf_counter()
@@ -58,7 +66,7 @@ def main():
     gen_s = time.perf_counter() - t0
     note("workload in %.1f s" % gen_s)
     res = {"shape": {"genome": a.genome, "coverage": a.coverage, "read_len": a.read_len, "k": a.k, "seed": a.seed,
-                     "clean": a.clean, "diploid": a.diploid, "bubble": a.bubble, "bytes": [len(fq1), len(fq2)]}, "generate_s": round(gen_s, 3), "runs": []}
+                     "clean": a.clean, "diploid": a.diploid, "bubble": a.bubble, "wide": a.wide, "bytes": [len(fq1), len(fq2)]}, "generate_s": round(gen_s, 3), "runs": []}
     with tempfile.TemporaryDirectory() as d:
         paths = [os.path.join(d, n) for n in ("in_1.fq", "in_2.fq", "all.fa", "cut.fa")]
         for p, data in zip(paths, (fq1, fq2)):
@@ -69,7 +77,8 @@ def main():
         for i in range(a.repeat):
             t = time.perf_counter()
             r = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, "-m", "muchsalsa_amd.unitigs", str(a.k)] +
-                               paths + ["--bubble", str(a.bubble)] + (["--gfa", os.path.join(d, "graph.gfa")] if a.gfa else []), cwd=ROOT, env=env, capture_output=True, text=True)
+                               paths + ["--bubble", str(a.bubble)] + (["--gfa", os.path.join(d, "graph.gfa")] if a.gfa else []) +
+                               (["--wide"] if a.wide else []), cwd=ROOT, env=env, capture_output=True, text=True)
             if r.returncode != 0:
                 res["error"] = {"run": i, "rc": r.returncode, "stderr": r.stderr[-2000:]}
                 break
