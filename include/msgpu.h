@@ -1700,6 +1700,132 @@ int         msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out)
 int         msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **records, uint64_t *n);
 void        msgpu_pl_result_free(msgpu_pl_result *r);
 
+/* ---- SAM output: the mapper's tables as SAM 1.6 text, formatted on the device ---------------------
+ * The chain table of a mapper run with its run tables (msgpu_map_result_cigars), rank rows (rule 12) and, for pairs, mate rows
+ * (rule 13) becomes the text that samtools, IGV and variant callers read.  The stage is additive: nothing else changes by
+ * it.  It loads both files itself through msgpu_seq_parse_upload, as the polisher does.  Parameters: eqx (0 / 1, default 1),
+ * md (0 / 1, default 0), unmapped (0 / 1, default 1).  The stage is defined by the rules below, in integers only, and checked,
+ * without tolerance, against the tests' restatement in plain Python (tests/sam_oracle.py), not against another tool:
+ *  S1. inputs and checks.  Both files through msgpu_seq_parse_upload; the chain table in output order; the run tables (runs
+ *      of chain i: ops[off[i] .. off[i + 1]), each len << 4 | op); the rank rows (required); optionally the mate rows.  The
+ *      checks are complete on the device before any formatting kernel runs; a failure is MSGPU_E_ARG "chain <i>: <what>" for
+ *      the smallest bad chain and, of that chain, the first violated check in this order: (a) off[0] = 0, the offsets do not
+ *      decrease (and none exceeds off[n_chains], the size of the run table); (b) query does not decrease; (c) strand <= 1;
+ *      (d) the query record and the target record are in range; (e) t_start <= t_end <= tlen; (f) q_start <= q_end <= qlen;
+ *      (g) every op is one of 1 (I), 2 (D), 7 (=), 8 (X) with length > 0 (a run that breaks this consumes nothing); (h) the
+ *      runs consume exactly t_end - t_start target bases and (i) q_end - q_start query bases; (j) parent is in range, lies in
+ *      the same query record and names a chain that is its own parent; (k) with mates, for a chain with cls = 1: mate is in
+ *      range, lies in the partner record (query ^ 1) and its row has cls = 1 and points back.  With mates an odd number of query
+ *      records is MSGPU_E_ARG naming the count.  Host checks, each MSGPU_E_ARG naming the record: two target records with the
+ *      same name (the loader keeps the first record of a name and drops the later ones, so a file cannot bring this about:
+ *      the records, and the chain table's indices, are those the loader keeps, and the check guards the header); a name
+ *      longer than 254 bytes; an empty name (both files).
+ *  S2. header.  "@HD\tVN:1.6\tSO:unsorted\tGO:query", one "@SQ\tSN:<name>\tLN:<length>" per target record in file order,
+ *      "@PG\tID:muchsalsa_amd\tPN:muchsalsa_amd"; nothing else (no version, no command line): the text is a function of the
+ *      inputs alone.
+ *  S3. lines and their order.  One line per chain, in the chain table's order.  With unmapped = 1 a query record without a
+ *      chain gets one unmapped line in its place in query record order: every read appears, and a pair's lines are adjacent.
+ *  S4. roles within a query record.  The representative is the rank-primary chain (parent == own index) with the greatest
+ *      score, the smallest index on a tie.  The other primaries are supplementary (0x800), the rank-secondaries secondary
+ *      (0x100).
+ *  S5. clips and CIGAR.  With oq the oriented query: left clip = q_start on strand 0, qlen - q_end on strand 1; right clip =
+ *      the other remainder.  The CIGAR is the left clip, the runs, the right clip; zero-length clips are left out; a CIGAR
+ *      without any run or clip is '*'.  The representative clips with S, supplementary and secondary lines with H.  With
+ *      eqx = 1 the runs are written as they are (=, X, I, D); with eqx = 0 every maximal stretch of neighbouring = and X runs
+ *      becomes one M run.
+ *  S6. SEQ.  A byte is folded to upper case; A, C, G, T stay (on strand 1 they are complemented and the read reversed); every
+ *      other byte becomes N.  Representative: the whole oriented read.  Supplementary: oq's aligned part only.  Secondary: '*'.
+ *      Unmapped: the read as the file holds it, folded the same way.  A SEQ without bases is '*'.  QUAL is always '*'.  (The
+ *      = / X letters are rule 10's, on the bytes as the stores hold them: on lower-case or non-ACGT input they can disagree
+ *      with a comparison of SEQ against the reference; on upper-case ACGT input they cannot.)
+ *  S7. columns of a chain line.  QNAME: the query name; with mates a trailing "/1" or "/2" is removed when the name is longer
+ *      than two bytes.  FLAG: S8.  RNAME: the target name.  POS: t_start + 1.  MAPQ: the rank row's mapq.  CIGAR: S5.  RNEXT,
+ *      PNEXT, TLEN: S8.  SEQ, QUAL: S6.  Then the tags, in this order: NM:i:<nm>, AS:i:<score>, cm:i:<n_anchors>, s2:i:<sub>
+ *      (representative and supplementary lines only), tp:A:P (primaries) or tp:A:S (secondaries), nb:i:<n_best> (lines with
+ *      cls = 1 only), MD:Z:<md> (with md = 1).
+ *  S8. FLAG and the mate columns.  0x10 iff strand = 1; 0x100 and 0x800 by S4.  Without mates: RNEXT '*', PNEXT 0, TLEN 0.
+ *      With mates: 0x1 on every line; 0x40 on the lines of record 2p, 0x80 on those of record 2p + 1; 0x2 iff cls = 1.  The
+ *      mate line of a chain is `mate` if cls = 1, else the representative of the partner record, else none.  If it exists:
+ *      0x20 iff it is on strand 1; RNEXT is '=' on the same target, else its target's name; PNEXT is its POS; on the same
+ *      target TLEN's magnitude is max(t_end) - min(t_start) over the two, positive on the line with the smaller t_start and
+ *      negative on the other, on equal t_start the line of record 2p is the positive one (for a proper pair this is +- rule
+ *      13's tl); on different targets TLEN is 0.  If no mate line exists: 0x8, RNEXT '=', PNEXT = own POS, TLEN 0.
+ *  S9. unmapped lines.  FLAG 0x4, plus 0x1 and 0x40 / 0x80 with mates.  With a mate line (paired only: the representative of
+ *      the partner record): 0x20 iff it is reverse; RNAME and POS are the mate line's; RNEXT '='; PNEXT is the mate line's
+ *      POS; TLEN 0.  Without: 0x8 too when paired; RNAME '*', POS 0, RNEXT '*', PNEXT 0, TLEN 0.  In both cases MAPQ 0,
+ *      CIGAR '*', no tags.
+ * S10. MD (with md = 1).  Walk the runs with the target bytes folded as in S6 (no complement).  = columns add to a running
+ *      count; an X column writes the count, the target base, and resets the count; a D run writes the count, '^', the target
+ *      bases, and resets the count; I runs do nothing (they do not split a count); the final count is written.  So the string
+ *      begins and ends with a number; neighbouring mismatches, and a mismatch next to a deletion, are separated by 0.
+ * S11. batches and limits.  Resident for a run: the two stores, the names, the chain, rank and mate rows with every chain's
+ *      FLAG and mate line, the run tables with their scans.  Per batch of consecutive query records (whole pairs with mates):
+ *      the line table, the per-line sizes and their 64-bit scan, the class lists, the text.  A line's text bound is
+ *      1024 + qlen + 11 * (runs + 2), with md = 1 plus 2 * (t_end - t_start) + 11 * (runs + 1); an unmapped line's is
+ *      1024 + qlen.  msgpu_sam_batch_bytes(params, lines, text bound) bounds the device bytes of a batch; the cut is the
+ *      mapper's greedy cut (rule 9) on msgpu_sam_batch_bytes <= budget with fewer than 2^31 lines per batch; budget_bytes = 0
+ *      stands for the free device memory once the resident part is allocated (an eighth less, again and again, while the
+ *      device cannot give the largest batch's bytes as one block).  The batches' texts one behind the other, behind the header,
+ *      are the file.  A record (with mates: a pair) that exceeds the budget alone is MSGPU_E_NOMEM naming it.  Fewer than 2^31
+ *      chains and runs, fewer than 2^32 lines; the file limits are the mapper's.  Every limit is an error, never a fault.  On
+ *      any error there is no result.
+ * For instance target t = ACGTACGTACGTACGTACGT, query q = TTCGTGGTAACG, one chain: strand 0, q 2..11, t 5..14, runs
+ * 3= 1X 1D 2= 1I 2=, score 40, 3 anchors, primary, mapq 60, with md = 1:
+ *   q\t0\tt\t6\t60\t2S3=1X1D2=1I2=1S\t*\t0\t0\tTTCGTGGTAACG\t*\tNM:i:3\tAS:i:40\tcm:i:3\ts2:i:0\ttp:A:P\tMD:Z:3A0^C4
+ * and with eqx = 0 the CIGAR is 2S4M1D2M1I2M1S.
+ * Out of scope: base qualities (the stores keep none), the SA:Z and MC:Z tags, BAM, coordinate sorting. */
+typedef struct msgpu_samctx msgpu_samctx; /* a device context of the stage */
+typedef struct msgpu_sam_result msgpu_sam_result;
+typedef struct msgpu_sam_params {
+  int32_t eqx, md, unmapped, reserved; /* defaults 1, 0, 1, 0 */
+} msgpu_sam_params;
+#define MSGPU_SAM_UNMAPPED 0xffffffffu  /* msgpu_sam_line.chain of an unmapped line */
+#define MSGPU_SAM_LINE_FIXED 1024u      /* S11: the part of a line's text bound that does not depend on the line */
+#define MSGPU_SAM_SHORT_BYTES 2048u     /* a line of at most this many bytes is written by one wavefront, a longer one by 8 workgroups */
+typedef struct msgpu_sam_line { /* per alignment line, in file order */
+  uint32_t chain;    /* MSGPU_SAM_UNMAPPED: an unmapped line */
+  uint32_t query, flag, reserved;
+  uint64_t offset;   /* of the line's first byte in the text */
+} msgpu_sam_line;
+typedef struct msgpu_sam_batch { /* a batch of S11, modelled on msgpu_map_batch */
+  uint32_t first_query, n_queries; /* consecutive query records */
+  uint64_t n_lines, text_bound;
+  uint64_t n_short, n_long;        /* lines by class */
+  uint64_t text_bytes;
+  uint64_t bytes_bound;            /* msgpu_sam_batch_bytes of this batch */
+  uint64_t bytes_peak;             /* the most bytes the batch held at once */
+} msgpu_sam_batch;
+typedef struct msgpu_sam_stats {
+  uint64_t n_targets, n_queries, n_chains, n_runs;
+  uint64_t n_lines, n_representative, n_supplementary, n_secondary, n_unmapped;
+  uint64_t n_short, n_long;                     /* lines by class */
+  uint64_t n_batches, budget_bytes;             /* budget_bytes: what a batch had (budget_bytes of the call, or what 0 stood for) */
+  uint64_t header_bytes, bytes_out, bytes_peak; /* bytes_peak: the most device bytes held beside the stores, resident part and batch */
+  uint64_t n_lost_publications;
+  msgpu_sam_params params;
+  float load_ms;                                /* host wall: both files into their stores */
+  float validate_ms, scan_ms, roles_ms, format_ms, copy_ms; /* device, by events; format_ms: line table, sizes, scan and write */
+  float wall_ms;
+  uint32_t reserved;
+} msgpu_sam_stats;
+void        msgpu_sam_default_params(msgpu_sam_params *p);
+int         msgpu_sam_create(int device, msgpu_samctx **out); /* MSGPU_E_NODEVICE without a GPU */
+void        msgpu_sam_destroy(msgpu_samctx *ctx);
+const char *msgpu_sam_last_error(const msgpu_samctx *ctx);
+/* S11's bound on the device bytes of a batch.  A host function without a device call. */
+uint64_t    msgpu_sam_batch_bytes(const msgpu_sam_params *params, uint64_t n_lines, uint64_t text_bound);
+/* The whole stage.  chains, ranks (and mates, or NULL: single-end): n_chains entries; off: n_chains + 1 entries; ops:
+ * off[n_chains] entries (host tables, copied).  flags must be 0.  Synchronous; the text is kept in the result. */
+int         msgpu_sam_run(msgpu_samctx *ctx, const msgpu_sam_params *params, const char *targets_path, const char *queries_path,
+                          const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off,
+                          const msgpu_map_rank *ranks, const msgpu_map_mate *mates, uint32_t flags, uint64_t budget_bytes,
+                          msgpu_sam_result **out);
+const char *msgpu_sam_result_text(const msgpu_sam_result *r, uint64_t *len);
+int         msgpu_sam_result_stats(const msgpu_sam_result *r, msgpu_sam_stats *out);
+int         msgpu_sam_result_lines(const msgpu_sam_result *r, const msgpu_sam_line **lines, uint64_t *n);
+int         msgpu_sam_result_batches(const msgpu_sam_result *r, const msgpu_sam_batch **batches, uint64_t *n); /* in order */
+void        msgpu_sam_result_free(msgpu_sam_result *r);
+
 /* ---- between the overlap path and assemblePath (host) -----------------------------
  * graph clean-up (src/main.cpp:194-288, 465-618: contraction targets and roots, ContainElements, deletions,
  * computeBitweight, getMaxSpanTree mst.cpp:34-111, decycle), getConnectedComponents (cc.cpp:33-70) and, per component,

@@ -328,6 +328,34 @@ class PlRecord(C.Structure):  # msgpu_pl_record
     _fields_ = [(n, C.c_uint64) for n in ("len_in", "len_out", "n_substituted", "n_deleted", "n_inserted", "depth_x100")]
 
 
+class SamParams(C.Structure):  # msgpu_sam_params
+    _fields_ = [("eqx", C.c_int32), ("md", C.c_int32), ("unmapped", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SamLine(C.Structure):  # msgpu_sam_line
+    _fields_ = [("chain", C.c_uint32), ("query", C.c_uint32), ("flag", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64)]
+
+
+SAM_LINE_DTYPE = np.dtype([("chain", "<u4"), ("query", "<u4"), ("flag", "<u4"), ("reserved", "<u4"), ("offset", "<u8")])
+SAM_UNMAPPED = 0xffffffff    # MSGPU_SAM_UNMAPPED
+SAM_LINE_FIXED = 1024        # MSGPU_SAM_LINE_FIXED
+SAM_SHORT_BYTES = 2048       # MSGPU_SAM_SHORT_BYTES
+
+
+class SamBatch(C.Structure):  # msgpu_sam_batch
+    _fields_ = [("first_query", C.c_uint32), ("n_queries", C.c_uint32)] + [
+        (n, C.c_uint64) for n in ("n_lines", "text_bound", "n_short", "n_long", "text_bytes", "bytes_bound", "bytes_peak")]
+
+
+class SamStats(C.Structure):  # msgpu_sam_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_targets", "n_queries", "n_chains", "n_runs", "n_lines", "n_representative",
+                                           "n_supplementary", "n_secondary", "n_unmapped", "n_short", "n_long", "n_batches",
+                                           "budget_bytes", "header_bytes", "bytes_out", "bytes_peak", "n_lost_publications")] +
+                [("params", SamParams)] +
+                [(n, C.c_float) for n in ("load_ms", "validate_ms", "scan_ms", "roles_ms", "format_ms", "copy_ms", "wall_ms")] +
+                [("reserved", C.c_uint32)])
+
+
 class EvParams(C.Structure):  # msgpu_ev_params
     _fields_ = [("k", C.c_int32), ("min_count", C.c_uint32), ("intervals", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -655,6 +683,18 @@ SYMBOLS = [
     ("msgpu_pl_result_stats", C.c_int, [C.c_void_p, C.POINTER(PlStats)]),
     ("msgpu_pl_result_records", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(PlRecord)), C.POINTER(C.c_uint64)]),
     ("msgpu_pl_result_free", None, [C.c_void_p]),
+    ("msgpu_sam_default_params", None, [C.POINTER(SamParams)]),
+    ("msgpu_sam_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    ("msgpu_sam_destroy", None, [C.c_void_p]),
+    ("msgpu_sam_last_error", C.c_char_p, [C.c_void_p]),
+    ("msgpu_sam_batch_bytes", C.c_uint64, [C.POINTER(SamParams), C.c_uint64, C.c_uint64]),
+    ("msgpu_sam_run", C.c_int, [C.c_void_p, C.POINTER(SamParams), C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("msgpu_sam_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_sam_result_stats", C.c_int, [C.c_void_p, C.POINTER(SamStats)]),
+    ("msgpu_sam_result_lines", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SamLine)), C.POINTER(C.c_uint64)]),
+    ("msgpu_sam_result_batches", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SamBatch)), C.POINTER(C.c_uint64)]),
+    ("msgpu_sam_result_free", None, [C.c_void_p]),
     ("msgpu_ev_default_params", None, [C.POINTER(EvParams)]),
     ("msgpu_ev_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     ("msgpu_ev_destroy", None, [C.c_void_p]),

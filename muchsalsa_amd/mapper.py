@@ -3,7 +3,7 @@ write -- a PAF of every record of a query file against every record of a target 
 
     python -m muchsalsa_amd.mapper <targets.fa|fq> <queries.fa|fq> <out.paf> [-k N] [-w N] [--exact] [--cigar] [--ava]
             [--max-occ N] [--min-score N] [--min-count N] [--max-gap N] [--bandwidth N] [--band N] [--budget-mb N]
-            [--extend N] [--rank] [--mates] [--max-insert N]
+            [--extend N] [--rank] [--mates] [--max-insert N] [--sam F] [--md] [--cigar-m]
 
 prints one JSON line of counts and seconds.  ``--budget-mb`` (N > 0) bounds the device memory of a batch of query records
 (rule 9; without it: the free device memory).  With ``--ava`` the two paths name the same file (the reads against
@@ -14,7 +14,10 @@ and the line ends in a ``cg:Z:`` string of ``=``, ``X``, ``I`` and ``D`` runs; `
 ``--cigar``) extends every chain beyond its outermost seeds by up to N bases at either end (rule 11); ``--rank`` marks every chain
 as primary or secondary and writes a mapping quality into column 12 (rule 12); ``--mates`` reads the query file as interleaved
 pairs and marks the proper pair of every pair (rule 13), ``--max-insert N`` (1..2^31 - 1, default 1000, which implies
-``--mates``) is its longest template.  minimap2 is not needed, and it is not part of
+``--mates``) is its longest template; ``--sam F`` (which implies ``--cigar`` and ``--rank``) also writes the chains as SAM 1.6 text
+into F, formatted on the device by muchsalsa_amd.sam (its rules S1 - S11): with ``--mates`` the mate rows become the pair's flags
+and mate columns, ``--md`` adds the MD tag and ``--cigar-m`` writes M in place of = and X; the PAF is written as before.
+minimap2 is not needed, and it is not part of
 the reference tree: the stage is defined by the rules below, in integers only, and checked, without tolerance, against the
 tests' restatement in plain Python (tests/map_oracle.py), not against minimap2.  The rules (include/msgpu.h,
 "unitig-to-read mapping"); parameters k (4..32, default 15), w (1..64, 5), max_occ (>= 1, 200), max_gap (10000), bandwidth
@@ -348,7 +351,7 @@ def interleave(in_1, in_2, out):
 
 
 def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=None, index=None, cigar=0, extend=0, rank=False, mates=False,
-        max_insert=_lib.MAP_MAX_INSERT_DEFAULT, **params):
+        max_insert=_lib.MAP_MAX_INSERT_DEFAULT, sam=None, sam_md=False, sam_m=False, **params):
     """The whole stage: writes ``out`` (nothing on an error); returns the counts, among them ``batches`` (rule 9's cut: a dict
     per batch with the fields of msgpu_map_batch) and ``budget_bytes`` (what a batch had).  ``params``: the names of DEFAULTS.
     ``budget_mb`` bounds the device memory of a batch (None: the free device memory).  With
@@ -367,7 +370,12 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     extend it is set on the context for this run.  ``mates`` = True (rule 13) reads ``queries`` as interleaved pairs with
     ``max_insert`` as the longest template; the result then carries ``mates`` (per line the tuple (mate, tlen, cls, n_best)) and
     ``mate`` (the counts of msgpu_map_mstats, the time under ``seconds``); ``tables`` receives ``mates`` too.  Set on the context
-    for this run, like rank."""
+    for this run, like rank.  ``sam`` = PATH also writes the chains as SAM into PATH (muchsalsa_amd.sam, from the result's own
+    tables; with ``mates`` the mate rows are passed on): it implies cigar = 1, exact = 1 and rank = True, ``sam_md`` adds the MD
+    tag, ``sam_m`` writes M runs; the returned dict then has ``sam`` (the counts of msgpu_sam_stats).  The PAF in ``out`` is that
+    of the same run without ``sam``; on any error neither file is written."""
+    if sam is not None:
+        cigar, rank, params = 1, True, dict(params, exact=1)
     if index is not None:
         params = dict({"k": index.k, "w": index.w}, **params)
     unknown = set(params) - set(DEFAULTS)
@@ -417,6 +425,7 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
             if mst.mates:
                 mp_, m = C.POINTER(_lib.MapMate)(), C.c_uint64()
                 L.msgpu_map_result_mates(res, C.byref(mp_), C.byref(m))
+                mates_at = C.addressof(mp_.contents) if m.value else None
                 rows = (np.frombuffer((C.c_char * (16 * m.value)).from_address(C.addressof(mp_.contents)), dtype=_lib.MAP_MATE_DTYPE)
                         if m.value else [])
                 mate_rows = [tuple(int(x) for x in r) for r in rows]
@@ -440,9 +449,29 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
                     L.msgpu_map_result_ext_ends(res, C.byref(ep), C.byref(m))
                     end = [tuple(int(getattr(ep[i], f)) for f, _ in _lib.ExtEnd._fields_) for i in range(m.value)]
                     tables["ext"] = list(zip(end[0::2], end[1::2]))
+            sam_text = None
+            if sam is not None:  # (before the PAF is written: an error leaves neither file)
+                from . import sam as sam_stage
+                cp, rp = C.POINTER(_lib.MapChain)(), C.POINTER(_lib.MapRank)()
+                ops, off, m = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+                L.msgpu_map_result_ranks(res, C.byref(rp), C.byref(m))
+                L.msgpu_map_result_cigars(res, C.byref(ops), C.byref(off), C.byref(m))
+                L.msgpu_map_result_chains(res, C.byref(cp), C.byref(m))
+                none = np.zeros(1, dtype=_lib.MAP_MATE_DTYPE)  # (mates without a chain: rows there are none of)
+                sam_timings = {}
+                tpath = index.targets if index is not None else targets
+                sam_text, _, sam_stats = sam_stage.run_pointers(
+                    tpath, queries if queries is not None else tpath,
+                    C.cast(cp, C.c_void_p), m.value, C.cast(ops, C.c_void_p), C.cast(off, C.c_void_p), C.cast(rp, C.c_void_p),
+                    (mates_at or none.ctypes.data) if mst.mates else None, eqx=not sam_m, md=sam_md, budget=budget,
+                    device=index.device if index is not None else device, timings=sam_timings, lines=False)
+                sam_stats["seconds"] = sam_timings
             t1 = time.perf_counter()
             with open(out, "wb") as h:
                 h.write(text)
+            if sam_text is not None:
+                with open(sam, "wb") as h:
+                    h.write(sam_text)
             t_write = time.perf_counter() - t1
     if timings is not None:
         timings.update({name[:-3]: getattr(st, name) / 1e3 for name, _ in _lib.MapStats._fields_ if name.endswith("_ms")})
@@ -458,6 +487,8 @@ def run(targets, queries, out, device=0, tables=None, timings=None, budget_mb=No
     if mate_rows is not None:
         ext["mates"] = mate_rows
         ext["mate"] = _mate_stats(mst)
+    if sam is not None:
+        ext["sam"] = sam_stats
     return {**ext, "params": {name: int(getattr(st.params, name)) for name in DEFAULTS}, "records": [int(x) for x in st.n_records],
             "bases": [int(x) for x in st.n_bases], "minimizers": [int(x) for x in st.n_minimizers], "keys": int(st.n_keys),
             "keys_dropped": int(st.n_keys_dropped), "entries_dropped": int(st.n_entries_dropped), "anchors": int(st.n_anchors),
@@ -510,6 +541,17 @@ def main(argv):
             ok = False
         del args[i:i + 2]
         mates = True
+    sam = {}
+    if "--sam" in args:  # (implies --cigar and --rank)
+        i = args.index("--sam")
+        ok = ok and i + 1 < len(args) and not args[i + 1].startswith("-")
+        sam["sam"] = args[i + 1] if i + 1 < len(args) else None
+        del args[i:i + 2]
+    for flag, key in (("--md", "sam_md"), ("--cigar-m", "sam_m")):
+        if flag in args:
+            args.remove(flag)
+            sam[key] = True
+            ok = ok and "sam" in sam
     for name, key in _OPTS.items():
         if name in args:
             i = args.index(name)
@@ -535,6 +577,7 @@ def main(argv):
         return 2
     timings = {}
     more = dict(mates=True, max_insert=max_insert) if mates else {}  # (without the option the call is the one it always was)
+    more.update(sam)
     out = run(args[0], args[1], args[2], timings=timings, budget_mb=budget, cigar=cigar, extend=extend, rank=rank, **p, **more)
     out.pop("ranks", None)  # (the table is the PAF's; the line keeps the counts)
     out.pop("mates", None)
