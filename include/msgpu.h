@@ -1680,7 +1680,7 @@ int         msgpu_pl_create(int device, msgpu_plctx **out); /* MSGPU_E_NODEVICE 
 void        msgpu_pl_destroy(msgpu_plctx *ctx);
 const char *msgpu_pl_last_error(const msgpu_plctx *ctx);
 /* The whole stage.  chains: n_chains entries; off: n_chains + 1 entries; ops: off[n_chains] entries (host tables, copied).
- * flags must be 0.  Synchronous; the FASTA is kept in the result. */
+ * flags is 0 or MSGPU_PL_VCF (below; here and in the two forms that follow).  Synchronous; the FASTA is kept in the result. */
 int         msgpu_pl_run(msgpu_plctx *ctx, const msgpu_pl_params *params, const char *draft_path, const char *reads_path,
                          const msgpu_map_chain *chains, uint64_t n_chains, const uint32_t *ops, const uint64_t *off, uint32_t flags,
                          msgpu_pl_result **out);
@@ -1699,6 +1699,67 @@ const char *msgpu_pl_result_text(const msgpu_pl_result *r, uint64_t *len);
 int         msgpu_pl_result_stats(const msgpu_pl_result *r, msgpu_pl_stats *out);
 int         msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **records, uint64_t *n);
 void        msgpu_pl_result_free(msgpu_pl_result *r);
+
+/* What the polisher changed, as VCF 4.2 formatted on the device (msgpu_vcf.hip).  On request only: bit
+ * MSGPU_PL_VCF of the `flags` of msgpu_pl_run, msgpu_pl_run_ranked and msgpu_pl_run_mates (any other bit stays MSGPU_E_ARG).
+ * Without the bit no kernel of it is launched and no byte allocated; with it the FASTA, the record table and every field of
+ * msgpu_pl_stats but bytes_peak, wall_ms and the times are those of the run without it.  The rules, per draft record of tlen
+ * bases; e(p): rule 5 substituted or deleted position p; ins(p): the letters rule 6 applies at slot p (empty for p = 0 and
+ * p = tlen):
+ *  V1. blocks.  A block is a maximal run [a, b) of positions with e(p); it owns the applied insertions at slots a .. b, both
+ *      ends included.  An applied insertion at a slot p with neither e(p - 1) nor e(p) is a block of its own with a = b = p.
+ *      Every position heads at most one block, and blocks never touch: an unchanged position lies between two of them.
+ *  V2. alleles.  REF0 = the draft's bytes of [a, b), folded to upper case, any byte outside ACGT written N.  ALT0 =
+ *      ins(a) call(a) ins(a + 1) call(a + 1) ... call(b - 1) ins(b), for a = b ins(a) alone: the bytes the polisher emits for
+ *      the block, always upper-case ACGT.
+ *  V3. anchoring.  Both non-empty: POS = a + 1, REF = REF0, ALT = ALT0 (MSGPU_VCF_ANCHOR_NONE).  One of them empty and a > 0:
+ *      the draft's byte at a - 1 (unchanged by maximality; folded, non-ACGT as N) is put in front of both, POS = a
+ *      (MSGPU_VCF_ANCHOR_LEFT).  One empty, a = 0 and b < tlen: the draft's byte at b is put behind both, POS = 1
+ *      (MSGPU_VCF_ANCHOR_RIGHT).  a = 0 and b = tlen, the whole record deleted: POS = 1, REF = the folded first base, ALT =
+ *      <DEL>, and INFO gains END=<tlen> in front of DP (MSGPU_VCF_ANCHOR_WHOLE).  Indels inside repeats are not left-aligned:
+ *      positions are where the alignment put them (out of scope).
+ *  V4. INFO, integers only.  DP = the minimum of depth(p) over [a, b), for a = b min(depth(a - 1), depth(a)).  AO = the minimum
+ *      over the block's edits of their support: the winning counter at an edited position, the applied group's count at an
+ *      applied slot.  TYPE = ins if REF0 is empty; del if ALT0 is empty; snp or mnp if |REF0| = |ALT0| (1, or more) and the
+ *      block holds neither a deletion nor an insertion; complex otherwise.
+ *  V5. line.  <name> TAB <POS> TAB . TAB <REF> TAB <ALT> TAB . TAB PASS TAB [END=n;]DP=d;AO=a;TYPE=t LF.  Lines come in
+ *      draft-record order, then by a.
+ *  V6. header, written on the host as the FASTA headers are: ##fileformat=VCFv4.2, ##source=muchsalsa_amd.polish, one
+ *      ##contig=<ID=name,length=tlen> per draft record in order, ##INFO lines for DP, AO, TYPE and END, ##ALT=<ID=DEL,...>, and
+ *      the #CHROM ... INFO line without sample columns.  A draft without variants is the header alone.
+ *  V7. names, checked only when VCF is asked for: a draft record is refused with MSGPU_E_ARG naming the record if its cleaned
+ *      name is empty, longer than 254 bytes, holds a byte outside 0x21..0x7e or one of , < >, begins with * or =, or repeats
+ *      an earlier record's name.  Nothing is written in that case, and the context goes on.
+ *  V8. rounds.  A VCF's coordinates are those of the draft of its own round: muchsalsa_amd.polish refuses VCF together with
+ *      more than one round (TypeError; from the command usage and exit status 2).
+ *  V9. limits, each an error and never a fault: fewer than 2^31 blocks; decimal widths up to the existing limits of positions
+ *      and depths; the extra device memory (12 bytes per draft base: the flag word and its scan; per block the row, the size
+ *      and its scan and the two class lists, 72 bytes; the text) is compared with what is free where the number of blocks and
+ *      the text size are known, else MSGPU_E_NOMEM naming the sizes.  The text's size by the scan is checked against a bound
+ *      from the stage's own counts and against the lines by class; a mismatch is MSGPU_E_STATE. */
+#define MSGPU_PL_VCF 1u           /* flags: write the VCF too */
+#define MSGPU_VCF_SHORT_BYTES 512u /* a line of at most this many bytes is written by one wavefront, a longer one by 8 workgroups */
+#define MSGPU_VCF_LINE_FIXED 96u  /* the part of a line's text bound beside its name and its alleles */
+enum { MSGPU_VCF_SNP = 0, MSGPU_VCF_MNP = 1, MSGPU_VCF_INS = 2, MSGPU_VCF_DEL = 3, MSGPU_VCF_COMPLEX = 4 };
+enum { MSGPU_VCF_ANCHOR_NONE = 0, MSGPU_VCF_ANCHOR_LEFT = 1, MSGPU_VCF_ANCHOR_RIGHT = 2, MSGPU_VCF_ANCHOR_WHOLE = 3 };
+typedef struct msgpu_pl_variant { /* per block, in the order of the lines; 48 bytes */
+  uint32_t record, a, ref_len, alt_len; /* the draft record; [a, a + ref_len) = REF0; |ALT0| */
+  uint32_t dp, ao, type, anchor;        /* V4; MSGPU_VCF_*; MSGPU_VCF_ANCHOR_* */
+  uint64_t offset, length;              /* the line in the text of msgpu_pl_result_vcf */
+} msgpu_pl_variant;
+typedef struct msgpu_pl_vcf_stats {
+  uint64_t n_variants, n_snp, n_mnp, n_ins, n_del, n_complex, n_whole_deleted;
+  uint64_t n_short, n_long;          /* the lines by class (MSGPU_VCF_SHORT_BYTES) */
+  uint64_t ref_bases, alt_bases;     /* the sums of |REF0| and of |ALT0| */
+  uint64_t header_bytes, text_bytes; /* text_bytes: the whole text, the header included */
+  uint64_t bytes_peak;               /* the most device bytes the run held beside the stores, VCF included */
+  float    vcf_ms;                   /* device, by events: everything of the VCF */
+  uint32_t reserved;
+} msgpu_pl_vcf_stats;
+/* The text (NULL and 0 when it was not asked for), the rows and the counts (zeroed when it was not asked for). */
+const char *msgpu_pl_result_vcf(const msgpu_pl_result *r, uint64_t *len);
+int         msgpu_pl_result_variants(const msgpu_pl_result *r, const msgpu_pl_variant **rows, uint64_t *n);
+int         msgpu_pl_result_vcf_stats(const msgpu_pl_result *r, msgpu_pl_vcf_stats *out);
 
 /* ---- SAM output: the mapper's tables as SAM 1.6 text, formatted on the device ---------------------
  * The chain table of a mapper run with its run tables (msgpu_map_result_cigars), rank rows (rule 12) and, for pairs, mate rows

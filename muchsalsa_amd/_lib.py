@@ -328,6 +328,25 @@ class PlRecord(C.Structure):  # msgpu_pl_record
     _fields_ = [(n, C.c_uint64) for n in ("len_in", "len_out", "n_substituted", "n_deleted", "n_inserted", "depth_x100")]
 
 
+class PlVariant(C.Structure):  # msgpu_pl_variant
+    _fields_ = [(n, C.c_uint32) for n in ("record", "a", "ref_len", "alt_len", "dp", "ao", "type", "anchor")] + [
+        ("offset", C.c_uint64), ("length", C.c_uint64)]
+
+
+class PlVcfStats(C.Structure):  # msgpu_pl_vcf_stats
+    _fields_ = ([(n, C.c_uint64) for n in ("n_variants", "n_snp", "n_mnp", "n_ins", "n_del", "n_complex", "n_whole_deleted", "n_short",
+                                           "n_long", "ref_bases", "alt_bases", "header_bytes", "text_bytes", "bytes_peak")] +
+                [("vcf_ms", C.c_float), ("reserved", C.c_uint32)])
+
+
+PL_VARIANT_DTYPE = np.dtype([(n, "<u4") for n in ("record", "a", "ref_len", "alt_len", "dp", "ao", "type", "anchor")] +
+                            [("offset", "<u8"), ("length", "<u8")])
+PL_VCF = 1                   # MSGPU_PL_VCF
+VCF_SHORT_BYTES = 512        # MSGPU_VCF_SHORT_BYTES
+VCF_LINE_FIXED = 96          # MSGPU_VCF_LINE_FIXED
+VCF_TYPES = ("snp", "mnp", "ins", "del", "complex")  # MSGPU_VCF_SNP .. MSGPU_VCF_COMPLEX
+
+
 class SamParams(C.Structure):  # msgpu_sam_params
     _fields_ = [("eqx", C.c_int32), ("md", C.c_int32), ("unmapped", C.c_int32), ("reserved", C.c_int32)]
 
@@ -682,6 +701,9 @@ SYMBOLS = [
     ("msgpu_pl_result_text", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msgpu_pl_result_stats", C.c_int, [C.c_void_p, C.POINTER(PlStats)]),
     ("msgpu_pl_result_records", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(PlRecord)), C.POINTER(C.c_uint64)]),
+    ("msgpu_pl_result_vcf", C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msgpu_pl_result_variants", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(PlVariant)), C.POINTER(C.c_uint64)]),
+    ("msgpu_pl_result_vcf_stats", C.c_int, [C.c_void_p, C.POINTER(PlVcfStats)]),
     ("msgpu_pl_result_free", None, [C.c_void_p]),
     ("msgpu_sam_default_params", None, [C.POINTER(SamParams)]),
     ("msgpu_sam_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),

@@ -320,6 +320,34 @@ __device__ inline uint32_t last_le(const uint64_t *a, uint32_t lo, uint32_t hi, 
   return lo;
 }
 
+// decimal text, of the stages that format on the device (msgpu_sam.hip, msgpu_vcf.hip): the digits of a value, and the value
+// in a width that the caller took from them
+__device__ inline uint32_t dec_dig(uint64_t v) { // decimal digits
+  uint32_t d = 1;
+  for (uint64_t p = 10; d < 20 && v >= p; p *= 10) ++d;
+  return d;
+}
+__device__ inline uint32_t dec_sdig(long long v) { return v < 0 ? 1 + dec_dig(0ull - static_cast<uint64_t>(v)) : dec_dig(static_cast<uint64_t>(v)); }
+__device__ inline void dec_put(uint8_t *p, uint64_t v, uint32_t w) { // v in w digits
+  for (uint32_t i = w; i--;) {
+    p[i] = static_cast<uint8_t>('0' + v % 10);
+    v /= 10;
+  }
+}
+__device__ inline void dec_sput(uint8_t *p, long long v, uint32_t w) { // v in w bytes, the sign among them
+  if (v < 0) {
+    p[0] = '-';
+    dec_put(p + 1, 0ull - static_cast<uint64_t>(v), w - 1);
+  } else dec_put(p, static_cast<uint64_t>(v), w);
+}
+// a base as the text formats write it: upper case, anything but A, C, G, T -> N, the complement on request
+__device__ inline uint8_t text_base(uint8_t b, uint32_t comp) {
+  if (b >= 'a' && b <= 'z') b -= 32;
+  if (b != 'A' && b != 'C' && b != 'G' && b != 'T') return 'N';
+  if (comp) b = b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : 'C';
+  return b;
+}
+
 // a device word into a slot of the scalar block (msgpu_stage.h, stage_scan_total, launches it behind a scan)
 template <class T> __global__ void k_stage_put(uint64_t *scalars, int slot, const T *src) {
   if (threadIdx.x == 0 && blockIdx.x == 0) scalars[slot] = static_cast<uint64_t>(*src);

@@ -21,23 +21,17 @@
 #include <new>
 #include <string>
 
-#include "msgpu_device.h"
-#include "msgpu_internal.h"
-#include "msgpu_kmer_shared.h"
-#include "msgpu_stage.h"
+#include "msgpu_polish.h"
 
 namespace msgpu {
 
 constexpr uint32_t PL_I = 1, PL_D = 2, PL_EQ = 7, PL_X = 8;
 constexpr uint32_t PL_MAX_INS = 32;
-enum { PL_A = 0, PL_C, PL_G, PL_T, PL_DEL, PL_OTHER, PL_CLASSES };
 // rule 1: what can be wrong with a chain, in the order in which one chain's violations are looked at
 enum { PL_BAD_ORDER = 0, PL_BAD_STRAND, PL_BAD_QREC, PL_BAD_TREC, PL_BAD_TRANGE, PL_BAD_QRANGE, PL_BAD_RUN, PL_BAD_TCONS, PL_BAD_QCONS,
        PL_BAD_OFF, PL_BAD_RANK /* (j), ranked form only: behind every other violation of its chain */,
        PL_BAD_MATE /* (k), mates form only: likewise */ };
-// the counts of msgpu_pl_stats that the kernels add up, one 64-bit word each
-enum { PL_ST_VOTERS = 0, PL_ST_IGNORED, PL_ST_EQ, PL_ST_X, PL_ST_D, PL_ST_I, PL_ST_VERBATIM, PL_ST_UNCHANGED, PL_ST_SUBST, PL_ST_DELETED,
-       PL_ST_USABLE, PL_ST_UNUSABLE, PL_ST_ENDS, PL_ST_APPLIED, PL_ST_INSERTED, PL_ST_MAXDEPTH, PL_ST_COUNT };
+// (the classes of the counters, the counts PL_ST_* that the kernels add up, pl_class and pl_depth: msgpu_polish.h)
 
 struct PlTables { // the chain table and the run tables with their scans
   const msgpu_map_chain *chains;
@@ -49,12 +43,6 @@ struct PlTables { // the chain table and the run tables with their scans
 
 __device__ inline void pl_bad(kf_ull *bad, uint32_t chain, uint32_t what) { atomicMin(bad, (static_cast<kf_ull>(chain) << 4) | what); }
 
-// rule 3: the class of the oriented query's byte; s = 1 reads the complement (upper case only, as MSGPU_COPY_REVCOMP), then folds
-__device__ inline uint32_t pl_class(uint8_t b, uint32_t s) {
-  if (s) b = b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b;
-  if (b >= 'a' && b <= 'z') b -= 32;
-  return b == 'A' ? PL_A : b == 'C' ? PL_C : b == 'G' ? PL_G : b == 'T' ? PL_T : PL_OTHER;
-}
 // byte j of the chain's stretch of the oriented query, in the query store
 __device__ inline uint8_t pl_query_byte(const SeqRecs &Q, const msgpu_map_chain &ch, uint64_t j) {
   const uint64_t qlen = Q.len[ch.query];
@@ -240,7 +228,7 @@ __global__ __launch_bounds__(256) void k_pl_best(const uint32_t *gstart, const u
 
 struct PlCall { // rules 5 and 6 per byte of the draft's store
   const uint32_t *cnt;
-  kf_ull         *best; // in: the slot's winner (0: none); out: 1 << 63 | its first event when it is applied, else 0
+  kf_ull         *best; // in: the slot's winner (0: none); out: 1 << 63 | its count << 32 | its first event when it is applied, else 0
   const uint32_t *gstart;
   const uint64_t *key;
   uint8_t        *call;   // 0: the draft's byte; 'A' 'C' 'G' 'T': that letter; 1: nothing
@@ -248,13 +236,6 @@ struct PlCall { // rules 5 and 6 per byte of the draft's store
   kf_ull         *rec_sub, *rec_del, *rec_ins;
   uint32_t        min_depth;
 };
-constexpr kf_ull PL_APPLIED = 1ull << 63;
-
-__device__ inline uint32_t pl_depth(const uint32_t *cnt, uint64_t plane, uint64_t pos) {
-  uint32_t d = 0;
-  for (int c = 0; c < PL_CLASSES; ++c) d += cnt[c * plane + pos];
-  return d;
-}
 
 __global__ __launch_bounds__(256) void k_pl_call(SeqRecs R, PlCall a, kf_ull *st) {
   const uint64_t pos = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -285,7 +266,7 @@ __global__ __launch_bounds__(256) void k_pl_call(SeqRecs R, PlCall a, kf_ull *st
       const uint32_t left = pl_depth(a.cnt, R.n_bases, pos - 1), m = left < depth ? left : depth;
       if (m >= a.min_depth && 2ull * count > m) {
         ins_len = static_cast<uint32_t>(a.key[e] & 63);
-        keep    = PL_APPLIED | e;
+        keep    = PL_APPLIED | static_cast<kf_ull>(count) << 32 | e; // (count <= the events, below 2^31)
       }
     }
     a.best[pos]   = keep;
@@ -334,25 +315,27 @@ using namespace msgpu;
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-struct msgpu_plctx : msgpu::StageCtx {
-  SeqCtxHold  seq;
-  ScalarBlock sc;
-  int         open() {
-    const int rc = msgpu_seq_create(device, &seq.p);
-    return rc != MSGPU_OK ? rc : sc.create();
-  }
-};
-
 struct msgpu_pl_result {
   msgpu_pl_stats               stats{};
   std::vector<msgpu_pl_record> records;
   std::string                  text;
+  bool                         has_vcf = false; // MSGPU_PL_VCF
+  VcfOut                       vcf;
 };
+
+// rule 8: `need` more bytes beside what the device holds already
+int msgpu::pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const char *a_name, uint64_t b, const char *b_name) {
+  size_t free_b = 0, total_b = 0;
+  STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
+  if (need <= free_b) return MSGPU_OK;
+  snprintf(c->err, sizeof(c->err), "%s: %llu %s and %llu %s need %llu bytes of device memory beside the two stores; %zu are free", what,
+           static_cast<kf_ull>(a), a_name, static_cast<kf_ull>(b), b_name, static_cast<kf_ull>(need), free_b);
+  return MSGPU_E_NOMEM;
+}
 
 namespace {
 
-enum { PL_SC_BAD = 0, PL_SC_TOTAL };
-static_assert(PL_SC_TOTAL < SC_COUNT, "the scalar block");
+static_assert(sizeof(msgpu_pl_variant) == 48 && sizeof(msgpu_pl_vcf_stats) == 120, "the C-ABI's sizes");
 static_assert(sizeof(msgpu_pl_stats) == 256 && sizeof(msgpu_pl_record) == 48 && sizeof(msgpu_map_chain) == 48, "the C-ABI's sizes");
 
 // (each begins with the words tests/pl_oracle.py uses for it)
@@ -365,19 +348,9 @@ const char *const PL_WHAT[] = {"query order (the chains are not ordered by query
                                "rank (the parent is out of range, of another query record or no primary, or mapq exceeds 60)",
                                "mates (cls exceeds 1, or the mate is out of range, names another chain or is no mate of this read, or n_best is 0)"};
 
-// rule 8: `need` more bytes beside what the device holds already
-int pl_room(msgpu_plctx *c, uint64_t need, const char *what, uint64_t a, const char *a_name, uint64_t b, const char *b_name) {
-  size_t free_b = 0, total_b = 0;
-  STAGE_HIP(c, hipMemGetInfo(&free_b, &total_b));
-  if (need <= free_b) return MSGPU_OK;
-  snprintf(c->err, sizeof(c->err), "%s: %llu %s and %llu %s need %llu bytes of device memory beside the two stores; %zu are free", what,
-           static_cast<kf_ull>(a), a_name, static_cast<kf_ull>(b), b_name, static_cast<kf_ull>(need), free_b);
-  return MSGPU_E_NOMEM;
-}
-
 int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, const char *reads_path, const msgpu_map_chain *chains,
            uint64_t n_chains64, const uint32_t *ops, const uint64_t *off, const msgpu_map_rank *ranks, uint32_t min_mapq,
-           const msgpu_map_mate *mates, msgpu_pl_result *res) {
+           const msgpu_map_mate *mates, bool vcf, msgpu_pl_result *res) {
   msgpu_pl_stats &S = res->stats;
   hipStream_t     st = c->stream;
   DevArena        D;
@@ -412,6 +385,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   S.n_reads      = Q.n;
   S.n_read_bases = Q.n_bases;
   const uint64_t NB = R.n_bases;
+  if (vcf && (rc = vcf_header(c, FT.f, res->vcf)) != MSGPU_OK) return rc; // V7, before any kernel
 
   // rule 8, what does not depend on the events: per draft byte the six counters, the slot's winner, the call, the output
   // length and its scan; per run the op, what it consumes on both sides with the two scans, its chain, the event flag and
@@ -598,6 +572,7 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   if (R.n) hipLaunchKernelGGL(k_pl_reclen, dim3(grid256(R.n)), dim3(256), 0, st, R, d_O, d_rec_start, d_rec_len);
   STAGE_HIP(c, hipGetLastError());
   STAGE_HIP(c, clock.end());
+  if (vcf && (rc = vcf_run(c, D, clock, VcfIn{R, d_cnt, d_best, d_key, d_call, d_O, d_raw, d_st}, res->vcf)) != MSGPU_OK) return rc;
 
   try {
     for (auto &v : h_rec) v.resize(R.n);
@@ -647,6 +622,8 @@ int pl_run(msgpu_plctx *c, const msgpu_pl_params &prm, const char *draft_path, c
   S.max_depth       = h_st[PL_ST_MAXDEPTH];
   S.bytes_out       = F.text;
   S.bytes_peak      = D.peak;
+  res->has_vcf      = vcf;
+  res->vcf.stats.bytes_peak = vcf ? D.peak : 0;
   return MSGPU_OK;
 }
 
@@ -669,7 +646,7 @@ static int pl_entry(msgpu_plctx *c, const msgpu_pl_params *params, const char *d
   if (!c || !out) return MSGPU_E_ARG;
   *out      = nullptr;
   c->err[0] = 0;
-  if (!params || !draft_path || !reads_path || flags || (n_chains && (!chains || !off)) || (n_chains && off[n_chains] && !ops)) return MSGPU_E_ARG;
+  if (!params || !draft_path || !reads_path || (flags & ~MSGPU_PL_VCF) || (n_chains && (!chains || !off)) || (n_chains && off[n_chains] && !ops)) return MSGPU_E_ARG;
   const msgpu_pl_params p = *params;
   if (p.min_depth < 1 || p.min_identity < 0 || p.min_identity > 100) {
     snprintf(c->err, sizeof(c->err), "min_depth = %d (at least 1), min_identity = %d (0..100)", p.min_depth, p.min_identity);
@@ -682,7 +659,7 @@ static int pl_entry(msgpu_plctx *c, const msgpu_pl_params *params, const char *d
   } catch (std::bad_alloc const &) { return MSGPU_E_NOMEM; }
   const StageTimer wall;
   const uint64_t   lost0 = c->sc.lost;
-  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, ranks, min_mapq, mates, res.get());
+  const int        rc = pl_run(c, p, draft_path, reads_path, chains, n_chains, ops, off, ranks, min_mapq, mates, (flags & MSGPU_PL_VCF) != 0, res.get());
   if (rc != MSGPU_OK) return rc;
   res->stats.n_lost_publications = c->sc.lost - lost0;
   res->stats.wall_ms             = wall.ms();
@@ -735,6 +712,25 @@ int msgpu_pl_result_records(const msgpu_pl_result *r, const msgpu_pl_record **re
 const char *msgpu_pl_result_text(const msgpu_pl_result *r, uint64_t *len) {
   if (len) *len = r ? r->text.size() : 0;
   return r ? r->text.data() : "";
+}
+
+const char *msgpu_pl_result_vcf(const msgpu_pl_result *r, uint64_t *len) {
+  const bool has = r && r->has_vcf;
+  if (len) *len = has ? r->vcf.text.size() : 0;
+  return has ? r->vcf.text.data() : nullptr;
+}
+
+int msgpu_pl_result_variants(const msgpu_pl_result *r, const msgpu_pl_variant **rows, uint64_t *n) {
+  if (!r || !rows || !n) return MSGPU_E_ARG;
+  *rows = r->vcf.rows.data();
+  *n    = r->vcf.rows.size();
+  return MSGPU_OK;
+}
+
+int msgpu_pl_result_vcf_stats(const msgpu_pl_result *r, msgpu_pl_vcf_stats *out) {
+  if (!r || !out) return MSGPU_E_ARG;
+  *out = r->vcf.stats;
+  return MSGPU_OK;
 }
 
 void msgpu_pl_result_free(msgpu_pl_result *r) {

@@ -58,31 +58,7 @@ struct SamTables { // the resident tables as the kernels see them
 
 __device__ inline void sam_bad(kf_ull *bad, uint32_t chain, uint32_t what) { atomicMin(bad, (static_cast<kf_ull>(chain) << 4) | what); }
 __device__ inline bool sam_is_m(uint32_t op) { return op == SAM_EQ || op == SAM_X; }
-__device__ inline uint32_t sam_dig(uint64_t v) { // decimal digits
-  uint32_t d = 1;
-  for (uint64_t p = 10; d < 20 && v >= p; p *= 10) ++d;
-  return d;
-}
-__device__ inline uint32_t sam_sdig(long long v) { return v < 0 ? 1 + sam_dig(0ull - static_cast<uint64_t>(v)) : sam_dig(static_cast<uint64_t>(v)); }
-__device__ inline void sam_put(uint8_t *p, uint64_t v, uint32_t w) { // v in w digits
-  for (uint32_t i = w; i--;) {
-    p[i] = static_cast<uint8_t>('0' + v % 10);
-    v /= 10;
-  }
-}
-__device__ inline void sam_sput(uint8_t *p, long long v, uint32_t w) { // v in w bytes, the sign among them
-  if (v < 0) {
-    p[0] = '-';
-    sam_put(p + 1, 0ull - static_cast<uint64_t>(v), w - 1);
-  } else sam_put(p, static_cast<uint64_t>(v), w);
-}
-// S6: upper case, anything but A, C, G, T -> N, the complement on request
-__device__ inline uint8_t sam_base(uint8_t b, uint32_t comp) {
-  if (b >= 'a' && b <= 'z') b -= 32;
-  if (b != 'A' && b != 'C' && b != 'G' && b != 'T') return 'N';
-  if (comp) b = b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : 'C';
-  return b;
-}
+// (the decimal helpers dec_dig, dec_sdig, dec_put, dec_sput and S6's text_base: msgpu_device.h)
 // S4: the representative of a query record, or SAM_NONE
 __device__ inline uint32_t sam_rep(const kf_ull *vkey, uint32_t r) {
   const kf_ull k = vkey[r];
@@ -145,15 +121,15 @@ __global__ __launch_bounds__(256) void k_sam_widths(SamTables X, const uint32_t 
   if (u >= X.n_runs) return;
   const uint32_t i = run_chain[u], len = X.ops[u] >> 4, op = X.ops[u] & 15;
   const uint32_t a = static_cast<uint32_t>(X.off[i]), b = static_cast<uint32_t>(X.off[i + 1]);
-  uint32_t       w = sam_dig(len) + 1;
+  uint32_t       w = dec_dig(len) + 1;
   if (!X.eqx && sam_is_m(op)) { // the stretch's last run writes the M
     const bool tail = u + 1 == b || !sam_is_m(X.ops[u + 1] & 15);
-    w = tail ? sam_dig(X.T[u + 1] - X.T[X.mhead[u]]) + 1 : 0;
+    w = tail ? dec_dig(X.T[u + 1] - X.T[X.mhead[u]]) + 1 : 0;
   }
   cw[u] = w;
   if (X.md) {
     const uint32_t p = X.pe[u] > a ? X.pe[u] : a;
-    const uint32_t d = sam_dig(X.E[u] - X.E[p]); // the count in front of the run
+    const uint32_t d = dec_dig(X.E[u] - X.E[p]); // the count in front of the run
     mw[u] = op == SAM_X ? d + 1 + 2 * (len - 1) : op == SAM_D ? d + 1 + len : 0;
   }
 }
@@ -260,7 +236,7 @@ __device__ inline SamF sam_fields(const SamTables &X, const SeqRecs &Q, uint32_t
   f.clip  = f.flag & 0x900u ? 'H' : 'S';
   f.a     = static_cast<uint32_t>(X.off[chain]);
   f.b     = static_cast<uint32_t>(X.off[chain + 1]);
-  f.cig_len = X.CW[f.b] - X.CW[f.a] + (f.lclip ? sam_dig(f.lclip) + 1 : 0) + (f.rclip ? sam_dig(f.rclip) + 1 : 0);
+  f.cig_len = X.CW[f.b] - X.CW[f.a] + (f.lclip ? dec_dig(f.lclip) + 1 : 0) + (f.rclip ? dec_dig(f.rclip) + 1 : 0);
   if (!(f.flag & 0x900u)) f.seq_n = qlen; // S6: the whole read; the aligned part; nothing
   else if (f.flag & 0x800u) {
     f.seq_s = ch.q_start;
@@ -294,7 +270,7 @@ __device__ inline SamF sam_fields(const SamTables &X, const SeqRecs &Q, uint32_t
   if (X.md) { // S10: the runs' tokens and the final count
     const uint32_t p = X.pe[f.b] > f.a ? X.pe[f.b] : f.a;
     f.md_final = X.E[f.b] - X.E[p];
-    f.md_len   = X.MW[f.b] - X.MW[f.a] + sam_dig(f.md_final);
+    f.md_len   = X.MW[f.b] - X.MW[f.a] + dec_dig(f.md_final);
   }
   return f;
 }
@@ -303,10 +279,10 @@ __device__ inline uint64_t sam_size(const SamTables &X, const SamF &f) {
   const uint64_t qn = X.qn_off[f.query + 1] - X.qn_off[f.query];
   const uint64_t rn = f.rname == SAM_NONE ? 1 : X.tn_off[f.rname + 1] - X.tn_off[f.rname];
   const uint64_t nx = f.rnext_kind == 2 ? X.tn_off[f.rnext + 1] - X.tn_off[f.rnext] : 1;
-  uint64_t       n = qn + 1 + sam_dig(f.flag) + 1 + rn + 1 + sam_dig(f.pos) + 1 + sam_dig(f.mapq) + 1 + (f.cig_len ? f.cig_len : 1) + 1 + nx + 1 +
-               sam_dig(f.pnext) + 1 + sam_sdig(f.tlen) + 1 + (f.seq_n ? f.seq_n : 1) + 2;
+  uint64_t       n = qn + 1 + dec_dig(f.flag) + 1 + rn + 1 + dec_dig(f.pos) + 1 + dec_dig(f.mapq) + 1 + (f.cig_len ? f.cig_len : 1) + 1 + nx + 1 +
+               dec_dig(f.pnext) + 1 + dec_sdig(f.tlen) + 1 + (f.seq_n ? f.seq_n : 1) + 2;
   if (f.chain != SAM_NONE) {
-    n += 6 + sam_dig(f.nm) + 6 + sam_sdig(f.as) + 6 + sam_dig(f.cm) + (f.has_s2 ? 6 + sam_sdig(f.s2) : 0) + 7 + (f.has_nb ? 6 + sam_dig(f.nb) : 0);
+    n += 6 + dec_dig(f.nm) + 6 + dec_sdig(f.as) + 6 + dec_dig(f.cm) + (f.has_s2 ? 6 + dec_sdig(f.s2) : 0) + 7 + (f.has_nb ? 6 + dec_dig(f.nb) : 0);
     if (X.md) n += 6 + f.md_len;
   }
   return n + 1;
@@ -354,19 +330,19 @@ __device__ inline void sam_write_line(const SamTables &X, const SeqRecs &R, cons
     w += 1 + tab;
   };
   auto num = [&](long long v) { // '\t' and the number
-    const uint32_t d = sam_sdig(v);
+    const uint32_t d = dec_sdig(v);
     if (t == k) {
       p[w] = '\t';
-      sam_sput(p + w + 1, v, d);
+      dec_sput(p + w + 1, v, d);
     }
     ++k;
     w += 1 + d;
   };
   auto tag = [&](char c0, char c1, long long v) { // '\t' and XX:i:<v>
-    const uint32_t d = sam_sdig(v);
+    const uint32_t d = dec_sdig(v);
     if (t == k) {
       p[w] = '\t', p[w + 1] = c0, p[w + 2] = c1, p[w + 3] = ':', p[w + 4] = 'i', p[w + 5] = ':';
-      sam_sput(p + w + 6, v, d);
+      dec_sput(p + w + 6, v, d);
     }
     ++k;
     w += 6 + d;
@@ -382,9 +358,9 @@ __device__ inline void sam_write_line(const SamTables &X, const SeqRecs &R, cons
     if (t == 0) p[w] = '\t';
     uint64_t c = w + 1;
     if (f.lclip) {
-      const uint32_t d = sam_dig(f.lclip);
+      const uint32_t d = dec_dig(f.lclip);
       if (t == k) {
-        sam_put(p + c, f.lclip, d);
+        dec_put(p + c, f.lclip, d);
         p[c + d] = static_cast<uint8_t>(f.clip);
       }
       ++k;
@@ -397,14 +373,14 @@ __device__ inline void sam_write_line(const SamTables &X, const SeqRecs &R, cons
       const bool     m = !X.eqx && sam_is_m(op);
       const uint64_t len = m ? X.T[u + 1] - X.T[X.mhead[u]] : X.ops[u] >> 4;
       uint8_t       *at = p + c + (X.CW[u] - X.CW[f.a]);
-      sam_put(at, len, cw - 1);
+      dec_put(at, len, cw - 1);
       at[cw - 1] = m ? 'M' : op == SAM_I ? 'I' : op == SAM_D ? 'D' : op == SAM_EQ ? '=' : 'X';
     }
     c += X.CW[f.b] - X.CW[f.a];
     if (f.rclip) {
-      const uint32_t d = sam_dig(f.rclip);
+      const uint32_t d = dec_dig(f.rclip);
       if (t == k) {
-        sam_put(p + c, f.rclip, d);
+        dec_put(p + c, f.rclip, d);
         p[c + d] = static_cast<uint8_t>(f.clip);
       }
       ++k;
@@ -421,7 +397,7 @@ __device__ inline void sam_write_line(const SamTables &X, const SeqRecs &R, cons
     ++w;
     const uint8_t *src = Q.bases + Q.off[f.query] + f.seq_s;
     const uint32_t n = f.seq_n, rc = f.seq_rc;
-    auto           at = [&](uint32_t j) { return sam_base(rc ? src[n - 1 - j] : src[j], rc); };
+    auto           at = [&](uint32_t j) { return text_base(rc ? src[n - 1 - j] : src[j], rc); };
     uint32_t       head = static_cast<uint32_t>((4 - (reinterpret_cast<uintptr_t>(p + w) & 3)) & 3);
     head = head < n ? head : n;
     const uint32_t words = (n - head) >> 2, tail = head + 4 * words;
@@ -447,8 +423,8 @@ __device__ inline void sam_write_line(const SamTables &X, const SeqRecs &R, cons
       if (t == k) p[w] = '\t', p[w + 1] = 'M', p[w + 2] = 'D', p[w + 3] = ':', p[w + 4] = 'Z', p[w + 5] = ':';
       ++k;
       w += 6;
-      const uint32_t df = sam_dig(f.md_final);
-      if (t == k) sam_put(p + w + f.md_len - df, f.md_final, df);
+      const uint32_t df = dec_dig(f.md_final);
+      if (t == k) dec_put(p + w + f.md_len - df, f.md_final, df);
       ++k;
       const msgpu_map_chain ch = X.chains[f.chain];
       const uint8_t        *tb = R.bases + R.off[ch.target] + ch.t_start;
@@ -459,11 +435,11 @@ __device__ inline void sam_write_line(const SamTables &X, const SeqRecs &R, cons
         if (op == SAM_EQ) continue;
         const uint32_t col = static_cast<uint32_t>(t0 + x - X.T[u]), pa = X.pe[u] > f.a ? X.pe[u] : f.a;
         const uint64_t count = X.E[u] - X.E[pa];
-        const uint32_t d = sam_dig(count);
+        const uint32_t d = dec_dig(count);
         uint8_t       *at = p + w + (X.MW[u] - X.MW[f.a]);
-        const uint8_t  base = sam_base(tb[x], 0);
+        const uint8_t  base = text_base(tb[x], 0);
         if (col == 0) {
-          sam_put(at, count, d);
+          dec_put(at, count, d);
           at[d] = op == SAM_X ? base : '^';
         }
         if (op == SAM_D) at[d + 1 + col] = base;

@@ -43,11 +43,13 @@ import time
 
 from . import _lib
 
-__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "POLISHED_MATES_NAME", "EVALUATION_NAME", "INTERLEAVED_NAME", "MATES_MAPPING", "gfa_name", "output_names", "link_input", "run", "main"]
+__all__ = ["HybridError", "MIN_LENGTH", "POLISHED_NAME", "POLISHED_MATES_NAME", "POLISHED_VCF_NAME", "POLISHED_MATES_VCF_NAME", "EVALUATION_NAME", "INTERLEAVED_NAME", "MATES_MAPPING", "gfa_name", "output_names", "link_input", "run", "main"]
 
 MIN_LENGTH = 500  # pipeline.sh:29
 POLISHED_NAME = "04.assembly.polished.fa"  # written only by run(..., polish=N): not one of output_names
 POLISHED_MATES_NAME = "05.assembly.polished.mates.fa"  # written only by run(..., polish_mates=N): not one of output_names
+POLISHED_VCF_NAME = "04.assembly.polished.vcf"  # written only by run(..., polish=1, vcf=True): not one of output_names
+POLISHED_MATES_VCF_NAME = "05.assembly.polished.mates.vcf"  # written only by run(..., polish_mates=1, vcf=True), likewise
 EVALUATION_NAME = "06.assembly.evaluation.tsv"  # written only by run(..., evaluate=K): not one of output_names
 INTERLEAVED_NAME = os.path.join("tmp", "illumina.interleaved.fq")  # the two Illumina inputs as one file of pairs, likewise
 # The mapper's parameters for the short reads of the polish_mates stage.  The mapper's default min_score of 100 is the score of
@@ -99,7 +101,7 @@ def link_input(path, directory, prefix="00_"):
 
 
 def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, cores=4, bloom_mem=None, device=0, cigar=False,
-        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None, evaluate=None, wide=None):
+        bubble=None, polish=None, extend=None, min_mapq=None, gfa=False, polish_mates=None, max_insert=None, evaluate=None, wide=None, vcf=False):
     """The whole pipeline (the module's docstring); returns one dict: per stage its counts and ``seconds`` (wall, the stage
     call alone; every stage call ends in a device synchronise), ``files`` (the names of output_names, absolute) and the
     total ``seconds``.  ``bloom_mem`` is ignored.  ``cigar`` = True: the exact mapping (step 9) aligns base by base and writes
@@ -125,12 +127,20 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     evaluated on it into EVALUATION_NAME (QV per record and in total, completeness), named by ``files["evaluation"]``; every
     other file is the same.  ``wide`` (None: on exactly when k_assembly > 64) is the unitig assembly's switch for k up to 128
     (muchsalsa_amd.unitigs; pipeline.sh's README recommends k_assembly = 90); False keeps the refusal of k_assembly > 64.  The
-    k-mer filter and the evaluation stay at k <= 64: their k are parameters of their own."""
+    k-mer filter and the evaluation stay at k <= 64: their k are parameters of their own.  ``vcf`` = True: every polishing stage
+    that was asked for also writes what it changed as VCF 4.2 (muchsalsa_amd.polish, rules V1 - V9) beside its FASTA, into
+    POLISHED_VCF_NAME (``files["polished_vcf"]``) and POLISHED_MATES_VCF_NAME (``files["polished_mates_vcf"]``); such a stage
+    with more than one round is a HybridError before any stage runs (a VCF's coordinates are its own round's draft's); every
+    other file is the same."""
     from . import kmer_filter, mapper, pipeline, scrubber, unitig_filter, unitigs
     t_all = time.perf_counter()
     for path in (illumina_1, illumina_2, nanopore):  # pipeline.sh:68-75, 125
         if not os.path.isfile(path) or os.path.getsize(path) == 0:
             raise HybridError("inputs", "file '%s' is empty or does not exist" % path)
+    if vcf:
+        for key, rounds in (("polish", polish), ("polish_mates", polish_mates)):
+            if rounds and int(rounds) > 1:
+                raise HybridError(key, "vcf with %d rounds: a VCF's coordinates are those of the draft of its own round" % int(rounds))
     out = os.path.realpath(outdir)  # pipeline.sh:60
     names = output_names(name, nanopore)
     files = {key: os.path.join(out, rel) for key, rel in names.items()}
@@ -181,8 +191,11 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
     if polish:
         from . import polish as polisher
         result["files"]["polished"] = os.path.join(out, POLISHED_NAME)
+        more = {}
+        if vcf:
+            result["files"]["polished_vcf"] = more["vcf"] = os.path.join(out, POLISHED_VCF_NAME)
         stage("polish", polisher.run, files["assembly"], files["scrubbed"], result["files"]["polished"], rounds=int(polish),
-              device=device, extend=int(extend or 0), min_mapq=min_mapq)
+              device=device, extend=int(extend or 0), min_mapq=min_mapq, **more)
     if polish_mates:
         from . import polish as polisher
         pairs = os.path.join(out, INTERLEAVED_NAME)
@@ -190,6 +203,8 @@ def run(k_filter, k_assembly, name, illumina_1, illumina_2, nanopore, outdir, co
         result["files"]["polished_mates"] = os.path.join(out, POLISHED_MATES_NAME)
         stage("interleave", lambda: {"pairs": mapper.interleave(illumina_1, illumina_2, pairs)})
         more = {} if max_insert is None else {"max_insert": int(max_insert)}
+        if vcf:
+            result["files"]["polished_mates_vcf"] = more["vcf"] = os.path.join(out, POLISHED_MATES_VCF_NAME)
         stage("polish_mates", polisher.run, result["files"]["polished"] if polish else files["assembly"], pairs,
               result["files"]["polished_mates"], rounds=int(polish_mates), device=device, mates=True, **more, **MATES_MAPPING)
     if evaluate:
