@@ -320,6 +320,10 @@ int msgpu_get_timings(msgpu_ctx *ctx, msgpu_timings *out);
  * on demand (synchronises the context's stream); not part of msgpu_counts. */
 int msgpu_get_chain_band_counts(msgpu_ctx *ctx, uint64_t *n_banded, uint64_t *n_fallback);
 int msgpu_chain_band_width(void); /* B, a build-time constant (MSGPU_CHAIN_BAND) */
+/* The candidate stage hands the chain stage one word per EdgeMatch (both row ranks, sixteen bits each) unless the job has a
+ * read of more than 65,535 rows: 1 = the host keeps the ranks in two arrays for a job whose largest read has that many rows.
+ * MSGPU_CAND_WIDE=1 forces that form. */
+int msgpu_cand_wide(uint32_t largest_read_cnt);
 /* The stage boundaries (index / candidates / chain / compact) are marked with HIP events on the context's stream; every
  * marker costs a few microseconds of command-processor time.  on = 0 drops them: msgpu_get_timings then reports only
  * chain_kernel_ms (the two events around the chain kernels stay) and zeros for the stages.  Default: on. */

@@ -225,7 +225,7 @@ enum BufLife {
   X(big_pfx, "candidates", BUF_JOB, "")                                                                                                    \
   X(edges, "candidates", BUF_JOB, "")    /* the edge table (a view in a resident batched job: its kept part goes from window to window) */ \
   X(edge_cand, "candidates", BUF_JOB, "")                                                                                                  \
-  X(cls_list, "candidates", BUF_JOB, "")                                                                                                   \
+  X(cls_desc, "candidates", BUF_JOB, "")                                                                                                   \
   X(big_list, "candidates", BUF_JOB, "")                                                                                                   \
   X(big_off, "candidates", BUF_JOB, "")                                                                                                    \
   /* the chain stage (msgpu_chaining_and_overlaps) */                                                                                      \
@@ -333,6 +333,8 @@ struct msgpu_ctx : msgpu::StageCtx {
   bool   use_fork  = true; // the candidate classes side by side (MSGPU_NO_FORK: one after the other)
   bool   use_prologue = true; // the candidate stage's opening inside the index build (MSGPU_NO_PROLOGUE: never)
   bool   chain_serial = false; // MSGPU_CHAIN_SERIAL: the chain stage's classes one after the other, a launch each
+  bool   force_cand_wide = false; // MSGPU_CAND_WIDE=1: the two-array form of the candidates for every job (tests)
+  bool   job_cand_wide = false;   // this job's form: forced, or a read of more than CAND_RANK_MAX rows (set by the index build)
   uint32_t n_cls[4] = {0, 0, 0, 0}; // edges of 9..16, 17..32, 33..64 and <= 8 EdgeMatches
   uint64_t n_edges_fast = 0;
   uint64_t chain_E = 0; // edges of the last chaining pass (where its band counts lie in chain_chunks)
@@ -381,6 +383,8 @@ struct msgpu_ctx : msgpu::StageCtx {
     use_prologue = !getenv("MSGPU_NO_PROLOGUE"); // no classification inside the index build
     use_fork     = !getenv("MSGPU_NO_FORK");     // the candidate classes one after the other
     chain_serial = getenv("MSGPU_CHAIN_SERIAL") != nullptr;
+    const char *cw = getenv("MSGPU_CAND_WIDE");
+    force_cand_wide = cw && cw[0] == '1';
     // the side streams have the highest priority, so that their work finishes first and the join never waits for it
     int prio_least = 0, prio_greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_least = prio_greatest = 0;
@@ -728,7 +732,7 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   // form pays for the generic scaffold build (a second read-back).
   launch_index_finish(st, c->read_first.as<uint32_t>(), V, scalar<uint32_t>(c, SC_ERR), d_flags, c->anchor_first.as<uint32_t>(),
                       c->anchor_off_gen.as<uint32_t>(), A, c->anchor_off.as<uint32_t>(), scalar<uint32_t>(c, SC_NALIVE),
-                      static_cast<uint32_t>(n));
+                      static_cast<uint32_t>(n), c->read_cnt.as<uint32_t>(), scalar<uint32_t>(c, SC_MAXCNT));
   STAGE_HIP(c, hipGetLastError());
   if (c->stage_events) STAGE_HIP(c, hipEventRecord(c->ev[1], st));
   if (want_prologue) { // (see the top of this function)
@@ -747,6 +751,9 @@ int build_index_once(msgpu_ctx *c, bool force_generic, bool two_pass, bool bin, 
   if (int rc = read_scalars(c)) return rc;
   }
   const uint32_t err = *host_scalar<uint32_t>(c, SC_ERR), ixf = *host_scalar<uint32_t>(c, SC_IXFLAGS);
+  // the form of the candidate words: the bin path has refused any read of more than CAND_RANK_SURE rows, the atomic path's
+  // k_index_finish left the largest count above that beside the flags
+  c->job_cand_wide = c->force_cand_wide || cand_wide(bshift ? CAND_RANK_SURE : *host_scalar<uint32_t>(c, SC_MAXCNT));
   c->cand_zeroed = false;
   c->full_scan_ok = bshift && ixf == 0 && err == 0;
   c->index_total  = c->full_scan_ok ? *host_scalar<uint64_t>(c, SC_TOTAL_A) : 0;
@@ -1091,7 +1098,7 @@ static int calculate_edges_impl(msgpu_ctx *c) {
 
   const size_t tb = total_bound ? total_bound : 1;
   STAGE_HIP(c, c->cand_j.ensure(tb * 4));
-  STAGE_HIP(c, c->cand_q.ensure(tb * 4));
+  if (c->job_cand_wide) STAGE_HIP(c, c->cand_q.ensure(tb * 4));
   STAGE_HIP(c, c->scr_v2.ensure(tb * 4));
   STAGE_HIP(c, c->scr_start.ensure(tb * 4));
 
@@ -1105,6 +1112,7 @@ static int calculate_edges_impl(msgpu_ctx *c) {
   a.cand_off       = c->cand_off.as<uint64_t>();
   a.cand_j         = c->cand_j.as<uint32_t>();
   a.cand_q         = c->cand_q.as<uint32_t>();
+  a.cand_wide      = c->job_cand_wide ? 1 : 0;
   a.edge_scr_v2    = c->scr_v2.as<uint32_t>();
   a.edge_scr_start = c->scr_start.as<uint32_t>();
   a.n_cand         = c->n_cand.as<uint32_t>();
@@ -1161,7 +1169,7 @@ static int calculate_edges_impl(msgpu_ctx *c) {
   auto capacities = [&](uint64_t *cap_edges, uint64_t *cap_big) {
     uint64_t ce = c->edges.room() / sizeof(msgpu_edge);
     if (c->edge_cand.cap / 8 < ce) ce = c->edge_cand.cap / 8;
-    if (c->cls_list.cap / 4 < ce) ce = c->cls_list.cap / 4;
+    if (c->cls_desc.cap / sizeof(ChainDesc) < ce) ce = c->cls_desc.cap / sizeof(ChainDesc);
     uint64_t cb = c->big_list.cap / 4;
     if (c->big_off.cap / 8 < cb) cb = c->big_off.cap / 8;
     if (c->chain_chunks.cap / 8 < chunk_words(ce)) ce = 0; // (sized with the edge table below: never the limit once both exist)
@@ -1181,7 +1189,7 @@ static int calculate_edges_impl(msgpu_ctx *c) {
     k.n_chunks       = cand_chunks(V);
     k.edges          = c->edges.as<msgpu_edge>();
     k.edge_cand      = c->edge_cand.as<uint64_t>();
-    k.list           = c->cls_list.as<uint32_t>();
+    k.desc           = c->cls_desc.as<ChainDesc>();
     k.big_list       = c->big_list.as<uint32_t>();
     k.big_off        = c->big_off.as<uint64_t>();
     k.big_cursor     = scalar<unsigned long long>(c, SC_BIGCUR);
@@ -1212,7 +1220,7 @@ static int calculate_edges_impl(msgpu_ctx *c) {
   if (c->n_edges > cap_edges || c->n_big_edges >= cap_big) { // (the kernel's own test, see k_emit_edges)
     STAGE_HIP(c, c->edges.ensure((c->n_edges ? c->n_edges : 1) * sizeof(msgpu_edge)));
     STAGE_HIP(c, c->edge_cand.ensure((c->n_edges ? c->n_edges : 1) * 8));
-    STAGE_HIP(c, c->cls_list.ensure((c->n_edges + 1) * 4));
+    STAGE_HIP(c, c->cls_desc.ensure((c->n_edges + 1) * sizeof(ChainDesc)));
     // the edges with more than 64 EdgeMatches (counted by the candidate kernels) are listed as they are emitted
     STAGE_HIP(c, c->big_list.ensure((c->n_big_edges + 1) * 4));
     STAGE_HIP(c, c->big_off.ensure((c->n_big_edges + 1) * 8));
@@ -1258,6 +1266,7 @@ static int chaining_and_overlaps_impl(msgpu_ctx *c) {
   a.n_edges      = E;
   a.cand_j       = c->cand_j.as<uint32_t>();
   a.cand_q       = c->cand_q.as<uint32_t>();
+  a.cand_wide    = c->job_cand_wide ? 1 : 0;
   a.read_off     = c->read_off.as<uint32_t>();
   a.read_cnt     = c->read_cnt.as<uint32_t>();
   a.read_len     = c->read_len.as<int32_t>();
@@ -1317,9 +1326,9 @@ static int chaining_and_overlaps_impl(msgpu_ctx *c) {
   if (int rc = launch_big()) return rc; // (first: its few long-lived wavefronts get their registers before k_chain fills the device)
   STAGE_HIP(c, hipEventRecord(ck_begin, st));
   if (c->sub_wave && E) {
-    // the size-sorted edge list and the class sizes are there since msgpu_calculate_edges
-    const uint32_t *list = c->cls_list.as<uint32_t>();
-    const uint32_t *l64 = list, *l32 = l64 + c->n_cls[2], *l16 = l32 + c->n_cls[1], *l8 = l16 + c->n_cls[0]; // sizes descending
+    // the size-sorted edge descriptors and the class sizes are there since msgpu_calculate_edges
+    const ChainDesc *list = c->cls_desc.as<ChainDesc>();
+    const ChainDesc *l64 = list, *l32 = l64 + c->n_cls[2], *l16 = l32 + c->n_cls[1], *l8 = l16 + c->n_cls[0]; // sizes descending
     // The three sub-wavefront classes go out as ONE launch (k_chain_sub_all: its workgroups take the 32-, 16- and 8-wide class
     // in turn) on the side stream the candidate stage used, beside k_chain: a kernel of a few thousand wavefronts lasts as long
     // as ONE of its wavefronts (45 us each for the 16- and 8-wide classes of a shard of eight, one after the other behind
@@ -1421,6 +1430,7 @@ int msgpu_get_counts(msgpu_ctx *c, msgpu_counts *out) {
 }
 
 int msgpu_chain_band_width(void) { return MSGPU_CHAIN_BAND; }
+int msgpu_cand_wide(uint32_t largest_read_cnt) { return cand_wide(largest_read_cnt) ? 1 : 0; }
 
 // The chain kernels leave the banded edges in bits 16..31 of every chunk sum and the fallbacks in the spare chunk behind the
 // last one (chunk_add, band_fallback_add); nothing on the hot path reads them, this call copies the words on demand.

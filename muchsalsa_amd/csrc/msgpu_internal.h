@@ -36,7 +36,8 @@ enum { SC_MAXIDS = 0 /*2 x u32*/, SC_ERR = 1, SC_TOTAL_A = 2, SC_TOTAL_B = 3, SC
        SC_NBIG = 7, SC_NALIVE = 8, SC_IXFLAGS = 9, SC_BIGSTATS = 10 /*2 x u64*/, SC_BIGCUR = 12 /*2 x u64*/,
        SC_CLS = 14 /*4 x u32: edges per width class, spans 14..15*/,
        SC_HEADS = 16 /*k_index_bin: finished workgroups (low half) | scaffolds that begin (high half)*/, SC_DONE = 17 /*u32: finished workgroups of k_index_epilogue*/,
-       SC_OWN = 18 /*visits of the owner reads classified by k_index_epilogue*/, SC_COUNT = 19 };
+       SC_OWN = 18 /*visits of the owner reads classified by k_index_epilogue*/,
+       SC_MAXCNT = 19 /*u32, atomic-path index build: the largest read_cnt above CAND_RANK_SURE, else 0*/, SC_COUNT = 20 };
 static_assert(SC_COUNT <= 64, "one wavefront publishes the whole scalar block (publish_to_host)");
 // A stage-closing kernel's publication of the scalar block (publish_to_host): the mapped host mirror (SC_COUNT words, then the
 // sequence number the host polls for) and the number to publish.  seq = 0: no publication (the copy read-back, or a launch again).
@@ -52,14 +53,31 @@ struct CandDesc {
 };
 static_assert(sizeof(CandDesc) == 32, "CandDesc must be 32 bytes");
 
+// one edge of <= 64 EdgeMatches as its chain wavefront (or group of lanes) needs it: what k_emit_edges knows when it lists the
+// edge, so that the chain kernels start from ONE 32-byte load at a slot they can compute instead of list -> edge -> candidates
+struct ChainDesc {
+  uint32_t e, v1, v2, em_cnt; // the edge, its reads, its EdgeMatches
+  uint64_t em_off, cand;      // first EdgeMatch in `ems`; first candidate in cand_j / cand_q
+};
+static_assert(sizeof(ChainDesc) == 32, "ChainDesc must be 32 bytes");
+
+// A candidate is one word, j | q << 16, while every rank of the job fits sixteen bits: no read has more than CAND_RANK_MAX rows.
+// The bin path of the index build never takes a read of more than CAND_RANK_SURE rows; the atomic path takes any and leaves
+// the largest row count above CAND_RANK_SURE in the scalar block (SC_MAXCNT, k_index_finish).  Beyond the limit the job keeps
+// the ranks in two arrays (the WIDE form of the candidate and chain kernels), chosen once per job by the host.
+constexpr uint32_t CAND_RANK_MAX = 65535, CAND_RANK_SURE = 256;
+inline bool cand_wide(uint32_t largest_read_cnt) { return largest_read_cnt > CAND_RANK_MAX; }
+
 struct CandArgs {
   const uint32_t *read_off, *read_cnt, *anchor_off;
   const IRow     *by_read;
   const SRow     *by_anchor;
   const uint4    *vis;  // per by_read row:   {i_lo, i_hi, first scaffold row behind it, rows behind it}
   const uint64_t *cand_off;     // per read: first slot of its candidate / edge scratch (exclusive scan of bound)
-  uint32_t       *cand_j;       // sorted candidates: rank of the anchor in v1's row list
-  uint32_t       *cand_q;       // sorted candidates: rank of the anchor in v2's row list (the scaffold row carries it)
+  // sorted candidates: j = rank of the anchor in v1's row list, q = its rank in v2's (the scaffold row carries it)
+  uint32_t       *cand_j;       // ONE word per candidate, j | q << 16; cand_wide: j
+  uint32_t       *cand_q;       // cand_wide only: q
+  int             cand_wide;    // the job has a read of more than CAND_RANK_MAX rows (cand_wide())
   uint32_t       *edge_scr_v2;  // per-read edge scratch: v2
   uint32_t       *edge_scr_start; // per-read edge scratch: first candidate of the edge
   uint32_t       *n_cand, *n_edge; // per read
@@ -84,7 +102,7 @@ struct EmitArgs {
   uint32_t        n_chunks;             // ceil(V / CAND_CHUNK)
   msgpu_edge     *edges;
   uint64_t       *edge_cand;
-  uint32_t       *list;                 // the edges of <= 64 EdgeMatches by size, largest first
+  ChainDesc      *desc;                 // the edges of <= 64 EdgeMatches by size, largest first
   uint32_t       *big_list;
   uint64_t       *big_off;
   unsigned long long *big_cursor;       // [2]
@@ -101,7 +119,8 @@ struct ChainArgs {
   msgpu_edge      *edges;     // bytes 16..31 of an edge: the chain kernels' counts for k_compact (edge_counts)
   const uint64_t  *edge_cand;
   uint64_t         n_edges;
-  const uint32_t  *cand_j, *cand_q; // per EdgeMatch: its row in v1's and in v2's segment of by_read
+  const uint32_t  *cand_j, *cand_q; // per EdgeMatch: its row in v1's and in v2's segment of by_read, as CandArgs has them
+  int              cand_wide;
   const uint32_t  *read_off, *read_cnt;
   const int32_t   *read_len;
   const IRow      *by_read;
@@ -261,7 +280,7 @@ void launch_sort_read(hipStream_t st, const uint32_t *read_off, const uint32_t *
                       const uint2 *spos, uint4 *vis, uint32_t *visits);
 void launch_index_finish(hipStream_t st, const uint32_t *read_first, uint32_t V, uint32_t *err, const uint32_t *flags,
                          const uint32_t *fast_off, const uint32_t *gen_off, uint32_t A, uint32_t *anchor_off, uint32_t *d_n_alive,
-                         uint32_t n_rows);
+                         uint32_t n_rows, const uint32_t *read_cnt, uint32_t *max_cnt);
 void launch_select_anchor_off(hipStream_t st, const uint32_t *flags, const uint32_t *fast_off, const uint32_t *gen_off,
                               uint32_t A, uint32_t *anchor_off, uint32_t *d_n_alive, uint32_t n_rows);
 void launch_scatter_anchor(hipStream_t st, const msgpu_row *rows, uint64_t n, const uint32_t *alive_rank,
@@ -296,14 +315,15 @@ constexpr uint32_t PAIR_TAB_WORDS      = PAIR_TAB_BAND64_OFF + 2 * PAIR_TAB_STRI
 // ChainArgs::fast_path: bit 0 the all-pairs-compatible shortcut, bit 1 the banded sweep
 constexpr int CHAIN_FAST_SHORTCUT = 1, CHAIN_FAST_BAND = 2;
 void launch_fill_pair_tab(hipStream_t st, uint32_t *tab);
-void launch_chain(hipStream_t st, const ChainArgs &a, const uint32_t *list, uint32_t n_list);
-void launch_chain_sub(hipStream_t st, const ChainArgs &a, int width, const uint32_t *list, uint32_t n_list);
-struct ChainSubLists { // the three sub-wavefront classes of k_chain_sub_all: edge lists, their lengths, workgroups of the first two
-  const uint32_t *list32, *list16, *list8;
-  uint32_t        n32, n16, n8, nb32, nb16;
+// desc: the edges' descriptors (the 33..64 class of the size-sorted list); nullptr: wavefront i takes edge i (diagnostic mode)
+void launch_chain(hipStream_t st, const ChainArgs &a, const ChainDesc *desc, uint32_t n_desc);
+void launch_chain_sub(hipStream_t st, const ChainArgs &a, int width, const ChainDesc *desc, uint32_t n_desc);
+struct ChainSubLists { // the three sub-wavefront classes of k_chain_sub_all: edge descriptors, their number, workgroups of the first two
+  const ChainDesc *list32, *list16, *list8;
+  uint32_t         n32, n16, n8, nb32, nb16;
 };
-void launch_chain_sub_all(hipStream_t st, const ChainArgs &a, const uint32_t *l32, uint32_t n32, const uint32_t *l16, uint32_t n16,
-                          const uint32_t *l8, uint32_t n8);
+void launch_chain_sub_all(hipStream_t st, const ChainArgs &a, const ChainDesc *l32, uint32_t n32, const ChainDesc *l16, uint32_t n16,
+                          const ChainDesc *l8, uint32_t n8);
 size_t big_elem_bytes();
 size_t big_path_bytes();
 void launch_chain_big(hipStream_t st, const ChainArgs &a, const uint32_t *big_list, const uint64_t *big_off,

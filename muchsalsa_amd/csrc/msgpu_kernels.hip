@@ -614,10 +614,17 @@ __global__ __launch_bounds__(256) void k_select_anchor_off(const uint32_t *flags
 // the two element-wise closings of an index build in one launch.  Over the reads: the Registry-order check on the first lines
 // the sort found -- ids must follow first-line order (Registry.cpp:36-45); an id without any row (marked 0xffffffff by the
 // sort) means the ids are not dense.  Over the anchors: k_select_anchor_off.
+// Also over the reads: the largest row count of a read, where it exceeds what the bin path takes (CAND_RANK_SURE; the word stays 0
+// otherwise) -- the host chooses the form of the candidate words by it (cand_wide).
 __global__ __launch_bounds__(256) void k_index_finish(const uint32_t *read_first, uint32_t V, uint32_t *err, const uint32_t *flags,
                                                       const uint32_t *fast_off, const uint32_t *gen_off, uint32_t A,
-                                                      uint32_t *anchor_off, uint32_t *d_n_alive, uint32_t n_rows) {
+                                                      uint32_t *anchor_off, uint32_t *d_n_alive, uint32_t n_rows,
+                                                      const uint32_t *read_cnt, uint32_t *max_cnt) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < V) {
+    const uint32_t cnt = read_cnt[i];
+    if (cnt > CAND_RANK_SURE) atomicMax(max_cnt, cnt);
+  }
   if (i + 1 < V) {
     const uint32_t f0 = read_first[i], f1 = read_first[i + 1];
     if (f0 != 0xffffffffu && f1 != 0xffffffffu && f1 <= f0) atomicOr(err, 1u);
@@ -692,7 +699,17 @@ __global__ __launch_bounds__(256) void k_bound(const uint32_t *read_off, const u
 
 // NT threads per workgroup (= per owner read): 128 for the reads with few scaffold rows to visit -- twice as many reads in
 // flight per CU, and the kernel waits on memory for most of its cycles -- 256 otherwise.
-template <int R1MAX, int CMAX, int NT>
+// One candidate: rank j in v1's rows and q in v2's as ONE word j | q << 16 (cand_j), or, in a job with a read of more than 65,535
+// rows (WIDE, the host's choice: cand_wide), as the two words cand_j / cand_q.
+template <bool WIDE> __device__ __forceinline__ void cand_store(const CandArgs &a, uint64_t x, uint32_t j, uint32_t q) {
+  if constexpr (WIDE) {
+    a.cand_j[x] = j;
+    a.cand_q[x] = q;
+  } else {
+    a.cand_j[x] = j | q << 16;
+  }
+}
+template <int R1MAX, int CMAX, int NT, bool WIDE>
 __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *desc, uint32_t n_list) {
   constexpr int      HSZ   = CMAX; // hash slots >= candidates: insertion always terminates
   constexpr int      HBITS = CMAX == 512 ? 9 : CMAX == 1024 ? 10 : CMAX == 2048 ? 11 : CMAX == 4096 ? 12 : 13;
@@ -890,8 +907,7 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
         uint32_t        rr = static_cast<uint32_t>(__popc(g[jw] & ((1u << (c_j[q] & 31)) - 1u)));
         for (uint32_t w = 0; w < jw; ++w) rr += static_cast<uint32_t>(__popc(g[w]));
         const uint64_t dst = co + g_off[c_rk[q]] + rr;
-        a.cand_j[dst]      = c_j[q];
-        a.cand_q[dst]      = c_t[q];
+        cand_store<WIDE>(a, dst, c_j[q], c_t[q]);
       }
     }
   } else { // more groups than bitmaps fit: stage by group, rank by comparison
@@ -911,8 +927,7 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
       const uint16_t mj = s_j[pos];
       uint32_t       rr = 0;
       for (uint32_t q = gs; q < ge; ++q) rr += (s_j[q] < mj) ? 1u : 0u;
-      a.cand_j[co + gs + rr] = mj;
-      a.cand_q[co + gs + rr] = s_t[pos];
+      cand_store<WIDE>(a, co + gs + rr, mj, s_t[pos]);
     }
   }
   // (d) one edge per group (edges with more than 64 EdgeMatches are counted: they take k_chain_big)
@@ -931,9 +946,12 @@ __global__ __launch_bounds__(NT) void k_candidates(CandArgs a, const CandDesc *d
   }
 }
 
-template __global__ void k_candidates<256, 512, 256>(CandArgs, const CandDesc *, uint32_t);
-template __global__ void k_candidates<256, 1024, 256>(CandArgs, const CandDesc *, uint32_t);
-template __global__ void k_candidates<1024, 4096, 256>(CandArgs, const CandDesc *, uint32_t);
+template __global__ void k_candidates<256, 512, 256, false>(CandArgs, const CandDesc *, uint32_t);
+template __global__ void k_candidates<256, 1024, 256, false>(CandArgs, const CandDesc *, uint32_t);
+template __global__ void k_candidates<1024, 4096, 256, false>(CandArgs, const CandDesc *, uint32_t);
+template __global__ void k_candidates<256, 512, 256, true>(CandArgs, const CandDesc *, uint32_t);
+template __global__ void k_candidates<256, 1024, 256, true>(CandArgs, const CandDesc *, uint32_t);
+template __global__ void k_candidates<1024, 4096, 256, true>(CandArgs, const CandDesc *, uint32_t);
 
 // classify reads of this shard by the LDS footprint their candidate scan needs
 // classes by LDS footprint: 0 = <256 rows, 512 candidates> (half the LDS of class 1, so twice as many reads per CU),
@@ -1135,6 +1153,7 @@ void launch_index_epilogue(hipStream_t st, const IndexEpilogueArgs &a) {
 }
 
 // big reads: same algorithm with every staging array in global memory (slow path, any size)
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_candidates_big(CandArgs a, const uint32_t *read_list, uint32_t n_list,
                                                         uint64_t *big_key, uint32_t *big_t, uint32_t *big_r2s,
                                                         uint32_t *big_pfx) {
@@ -1213,8 +1232,7 @@ __global__ __launch_bounds__(256) void k_candidates_big(CandArgs a, const uint32
     uint32_t rank = 0;
     for (uint32_t q = 0; q < nc; ++q) rank += (big_key[bo + q] < k) ? 1u : 0u;
     big_r2s[bo + rank]  = static_cast<uint32_t>(k >> 32);
-    a.cand_j[co + rank] = static_cast<uint32_t>(k);
-    a.cand_q[co + rank] = big_t[bo + c];
+    cand_store<WIDE>(a, co + rank, static_cast<uint32_t>(k), big_t[bo + c]);
   }
   __threadfence_block();
   __syncthreads();
@@ -1307,7 +1325,7 @@ __global__ __launch_bounds__(1024) void k_cand_reduce(const uint32_t *n_edge, co
 }
 
 // The candidate stage closes in ONE more launch: the scans of the per-read candidate / edge counts, the dense edge table (ascending
-// (v1, v2)), the list of big edges, the edges of <= 64 EdgeMatches listed by size (largest first: the width classes of the
+// (v1, v2)), the list of big edges, the edges of <= 64 EdgeMatches listed by size, a ChainDesc each (largest first: the width classes of the
 // chain kernels are contiguous stretches [64..33 | 32..17 | 16..9 | 8..1], the edges that share a wavefront in k_chain_sub have
 // (nearly) the same size, the longest edges of a launch start first), the class sizes, and the read-back of all the sizes.
 // A workgroup per chunk of CAND_CHUNK reads.  Every workgroup sums the rows k_cand_reduce left per chunk: the sums of the chunks before its own are its bases -- first edge, first EdgeMatch, and per size the first
@@ -1494,7 +1512,12 @@ __global__ __launch_bounds__(1024) void k_emit_edges(EmitArgs a) {
         a.big_list[i] = static_cast<uint32_t>(eb + e);
         a.big_off[i]  = atomicAdd(&a.big_cursor[1], static_cast<unsigned long long>(ed.em_cnt));
       } else if (ed.em_cnt) {
-        a.list[atomicAdd(&s_pos[ed.em_cnt - 1], 1u)] = static_cast<uint32_t>(eb + e);
+        // everything the edge's chain wavefront would otherwise fetch again through the list entry (ChainDesc), two 16-byte stores
+        uint4 *d = reinterpret_cast<uint4 *>(&a.desc[atomicAdd(&s_pos[ed.em_cnt - 1], 1u)]);
+        const uint64_t cp = co + st;
+        d[0] = make_uint4(static_cast<uint32_t>(eb + e), ed.v1, ed.v2, ed.em_cnt);
+        d[1] = make_uint4(static_cast<uint32_t>(ed.em_off), static_cast<uint32_t>(ed.em_off >> 32), static_cast<uint32_t>(cp),
+                          static_cast<uint32_t>(cp >> 32));
       }
     }
   }
@@ -1729,7 +1752,10 @@ __device__ __forceinline__ ChainElem lds_elem(uint32_t addr) {
   return e;
 }
 constexpr uint32_t CHAIN_LDS_EL = 0, CHAIN_LDS_CM = sizeof(ChainElem) * 64, CHAIN_LDS_BYTES = CHAIN_LDS_CM + 34 * 8;
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_chain(ChainArgs a, const uint32_t *list, uint32_t n_list) {
+// LISTED: workgroup i takes descriptor i of `desc` (the 33..64 class of the size-sorted list); else edge i of the table, its
+// facts from edges[i] / edge_cand[i] (the mode without size classes: a diagnostic path).
+template <bool LISTED, bool WIDE>
+__device__ __forceinline__ void chain_body(const ChainArgs &a, const ChainDesc *desc, uint32_t n_desc) {
   // ONE wavefront per workgroup, and no static LDS: the dynamic block starts at LDS address 0, so the element table's
   // address is a compile-time constant and the pair table can hold the LDS offsets of a pair's two elements ready to use --
   // the two address additions per sweep step (5 % of the loop's vector instructions) are gone.
@@ -1740,14 +1766,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   static_assert(sizeof(ChainElem) * 64 == sizeof(PathRec) * 2 * 64, "the path lists overlay the element table");
   extern __shared__ __attribute__((aligned(16))) unsigned char s_chain_lds[];
   const int      lane = threadIdx.x;
-  // list == nullptr: wave i takes edge i; else the edges of the list (the 33..64 class of the size-sorted list)
   const uint32_t slot = blockIdx.x;
-  if (list ? slot >= n_list : slot >= a.n_edges) return;
-  const uint64_t e = list ? __builtin_amdgcn_readfirstlane(list[slot]) : slot;
-  const msgpu_edge ed = a.edges[e];
-  const uint32_t   n  = ed.em_cnt;
+  if (LISTED ? slot >= n_desc : slot >= a.n_edges) return;
+  // The front of an edge: its descriptor lies at an address known at launch -- ONE scalar load of eight dwords, where a vector
+  // load of the list entry, a readfirstlane and the loads of edges[e] and edge_cand[e] behind it used to be two dependent levels.
+  ChainDesc ed;
+  if constexpr (LISTED) {
+    ed = desc[slot];
+  } else {
+    const msgpu_edge t = a.edges[slot];
+    ed = ChainDesc{slot, t.v1, t.v2, t.em_cnt, t.em_off, a.edge_cand[slot]};
+  }
+  const uint64_t e = ed.e;
+  const uint32_t n = ed.em_cnt;
   if (n > 64) return; // handled by k_chain_big
-  const uint64_t cp  = a.edge_cand[e];
+  const uint64_t cp  = ed.cand;
   const bool     act = lane < static_cast<int>(n);
   const uint32_t v1 = ed.v1, v2 = ed.v2;
   const uint32_t n1 = a.read_cnt[v1], n2 = a.read_cnt[v2];
@@ -1756,13 +1789,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   uint64_t      *cm = reinterpret_cast<uint64_t *>(s_chain_lds + CHAIN_LDS_CM);
 
   // ---- per-lane element: VertexMatch on v1 (row j of v1), VertexMatch on v2 (scaffold row t), EdgeMatch ----------
-  uint32_t j1 = 0, q2 = 0, anchor = 0;
+  // the candidate: ONE word j | q << 16, in one register until the path code far below takes it apart again (WIDE: the two
+  // words cand_j / cand_q of a job with a read of more than 65,535 rows)
+  uint32_t jq = 0, qw = 0, anchor = 0;
   double   clo1 = 0, clo2 = 0, ovr1 = 0, ovr2 = 0, em_score = 0;
   bool     em_dir = false, em_prim = false;
   ChainElem x{};
   if (act) {
-    j1            = a.cand_j[cp + lane];
-    q2            = a.cand_q[cp + lane];
+    jq            = a.cand_j[cp + lane];
+    if constexpr (WIDE) qw = a.cand_q[cp + lane];
+    const uint32_t j1 = WIDE ? jq : (jq & 0xffffu), q2 = WIDE ? qw : (jq >> 16);
     // both rows from by_read: v2's rows of one edge lie packed in v2's segment (the candidate kernel handed their ranks on)
     const IRow m1 = load_irow(&a.by_read[a.read_off[v1] + j1]);
     const IRow m2 = load_irow(&a.by_read[a.read_off[v2] + q2]);
@@ -2113,6 +2149,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
   // src/main.cpp:341-353: split by EdgeMatch direction, minus then plus
   PathRec  *pmn = reinterpret_cast<PathRec *>(s_chain_lds + CHAIN_LDS_EL), *ppl = pmn + 64; // el[] is dead from here on
+  // (the word opaque here: the two ranks are taken from it anew, not kept in two registers since the element phase)
+  if constexpr (!WIDE) asm volatile("" : "+v"(jq));
+  const uint32_t j1 = WIDE ? jq : (jq & 0xffffu), q2 = WIDE ? qw : (jq >> 16);
   const int n_m = paths_of_direction(m_minus, false, lane, pop, pm, em_prim, j1, q2, n1, n2, a.alt_frac, pmn);
   const int n_p = paths_of_direction(m_plus, true, lane, pop, pm, em_prim, j1, q2, n1, n2, a.alt_frac, ppl);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2224,6 +2263,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     edge_counts(a.edges, e, n, n_orders, n_ids, shadow);
     chunk_add(a.chunk_sums, e, clean, n_orders, n_ids, banded);
   }
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_chain(ChainArgs a, const ChainDesc *desc, uint32_t n_desc) {
+  chain_body<true, false>(a, desc, n_desc);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_chain_wide(ChainArgs a, const ChainDesc *desc, uint32_t n_desc) {
+  chain_body<true, true>(a, desc, n_desc);
+}
+template <bool WIDE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_chain_unlisted(ChainArgs a) {
+  chain_body<false, WIDE>(a, nullptr, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2370,8 +2419,8 @@ __device__ __forceinline__ uint32_t paths_of_direction_sub(uint32_t act, bool di
 
 // The body of k_chain_sub<W> for workgroup `block` of its class (the kernels below supply the LDS: the same two arrays for
 // every width).
-template <int W>
-__device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_t *list, uint32_t n_list, uint32_t block,
+template <int W, bool WIDE>
+__device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const ChainDesc *list, uint32_t n_list, uint32_t block,
                                                unsigned char (*s_wavebuf)[sizeof(ChainElem) * 64], uint32_t (*s_cm)[64],
                                                double (*s_keep)[64][4], uint32_t (*s_anchor)[64]) {
   constexpr int G = 64 / W;
@@ -2382,10 +2431,17 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   const uint32_t slot    = (block * 4 + wave) * G + g;
   const bool     valid_g = slot < n_list;
   if (__ballot(valid_g) == 0) return;
-  const uint32_t   e  = valid_g ? list[slot] : list[0];
-  const msgpu_edge ed = a.edges[e];
+  // The front of a group's edge: its descriptor as two 16-byte loads, the same address in every lane of the group (a group past
+  // the end of the list takes descriptor 0 with n = 0) -- the list entry and edges[e] / edge_cand[e] behind it used to be two
+  // dependent levels of loads.
+  const uint4     *dp = reinterpret_cast<const uint4 *>(&list[valid_g ? slot : 0u]);
+  const uint4      d0 = dp[0], d1 = dp[1];
+  ChainDesc        ed;
+  ed.e = d0.x, ed.v1 = d0.y, ed.v2 = d0.z, ed.em_cnt = d0.w;
+  ed.em_off = d1.x | static_cast<uint64_t>(d1.y) << 32, ed.cand = d1.z | static_cast<uint64_t>(d1.w) << 32;
+  const uint32_t   e  = ed.e;
   const uint32_t   n  = (valid_g && ed.em_cnt <= static_cast<uint32_t>(W)) ? ed.em_cnt : 0u;
-  const uint64_t   cp = a.edge_cand[e];
+  const uint64_t   cp = ed.cand;
   const bool       act = sl < static_cast<int>(n);
   const uint32_t   v1 = ed.v1, v2 = ed.v2;
   const uint32_t   n1 = a.read_cnt[v1], n2 = a.read_cnt[v2];
@@ -2394,14 +2450,16 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   uint32_t        *cm = s_cm[wave];
 
   // ---- per-lane element (as in k_chain) ------------------------------------------------------------------------------
-  uint32_t  j1 = 0, q2 = 0, anchor = 0;
+  // (the candidate word as in k_chain: j | q << 16 in one register across the body; WIDE: two words)
+  uint32_t  jq = 0, qw = 0, anchor = 0;
   double    clo1 = 0, clo2 = 0, ovr1 = 0, ovr2 = 0, em_score = 0;
   bool      em_dir = false, em_prim = false;
   ChainElem x{};
   cm[lane] = 0;
   if (act) {
-    j1            = a.cand_j[cp + sl];
-    const uint32_t qt = a.cand_q[cp + sl];
+    jq            = a.cand_j[cp + sl];
+    const uint32_t j1 = WIDE ? jq : (jq & 0xffffu);
+    const uint32_t qt = WIDE ? a.cand_q[cp + sl] : (jq >> 16);
     const IRow m1 = load_irow(&a.by_read[a.read_off[v1] + j1]);
     const IRow m2 = load_irow(&a.by_read[a.read_off[v2] + qt]);
     anchor        = m1.other;
@@ -2456,9 +2514,10 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
     clo1     = x.clo1;
     clo2     = x.clo2;
     el[lane] = x;
-    // v2's rank for the path code far below, fetched a second time (the line has just been read) rather than kept beside the
-    // row's eight words through the set-up: with it live from the first load the body does not fit seven wavefronts' registers
-    q2       = *static_cast<const volatile uint32_t *>(&a.cand_q[cp + sl]);
+    // WIDE: v2's rank for the path code far below, fetched a second time (the line has just been read) rather than kept beside
+    // the row's eight words through the set-up: with it live from the first load the body does not fit seven wavefronts'
+    // registers.  (The packed word holds it already.)
+    if constexpr (WIDE) qw = *static_cast<const volatile uint32_t *>(&a.cand_q[cp + sl]);
   }
   // the four numbers the overhangs at the very end are made of wait in LDS, not in eight registers across the sweep and the DP
   // (the element table itself is overwritten by the path lists before then)
@@ -2675,6 +2734,8 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   // The direction is a group's own, so a wavefront cannot skip an empty one the way k_chain does.  One pass serves every
   // group's first direction (minus where it has one, else plus) with direction, lanes and list per group; the second pass,
   // the plus list of the groups that have both, runs only in a wavefront that holds such a group.
+  if constexpr (!WIDE) asm volatile("" : "+v"(jq)); // (the ranks taken from the word anew, see k_chain)
+  const uint32_t j1 = WIDE ? jq : (jq & 0xffffu), q2 = WIDE ? qw : (jq >> 16);
   uint32_t n_m = 0, n_p = 0;
 #pragma clang loop unroll(disable)
   for (int trip = 0; trip < 2; ++trip) {
@@ -2789,13 +2850,13 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const uint32_
   }
 }
 
-template <int W>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W == 32 ? 7 : 6, W == 32 ? 7 : 6))) void k_chain_sub(ChainArgs a, const uint32_t *list, uint32_t n_list) {
+template <int W, bool WIDE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W == 32 ? 7 : 6, W == 32 ? 7 : 6))) void k_chain_sub(ChainArgs a, const ChainDesc *list, uint32_t n_list) {
   __shared__ __attribute__((aligned(16))) unsigned char s_wavebuf[4][sizeof(ChainElem) * 64];
   __shared__ uint32_t                                  s_cm[4][64];
   __shared__ __attribute__((aligned(16))) double       s_keep[4][64][4];
   __shared__ uint32_t                                  s_anchor[4][64];
-  chain_sub_body<W>(a, list, n_list, blockIdx.x, s_wavebuf, s_cm, s_keep, s_anchor);
+  chain_sub_body<W, WIDE>(a, list, n_list, blockIdx.x, s_wavebuf, s_cm, s_keep, s_anchor);
 }
 // The three sub-wavefront classes in ONE launch (the step's launches: 14 -> 12): workgroups [0, nb32) take the 32-wide class,
 // the next nb16 the 16-wide one, the rest the 8-wide one -- the longest-lived first.  (One kernel = one register budget for the three bodies.)
@@ -2806,23 +2867,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W == 32 ? 7
 #ifndef MSGPU_SUB_WAVES
 #define MSGPU_SUB_WAVES 7
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSGPU_SUB_WAVES, MSGPU_SUB_WAVES))) void k_chain_sub_all(ChainArgs a, ChainSubLists l) {
+template <bool WIDE>
+__device__ __forceinline__ void chain_sub_all_body(const ChainArgs &a, const ChainSubLists &l) {
   __shared__ __attribute__((aligned(16))) unsigned char s_wavebuf[4][sizeof(ChainElem) * 64];
   __shared__ uint32_t                                  s_cm[4][64];
   __shared__ __attribute__((aligned(16))) double       s_keep[4][64][4];
   __shared__ uint32_t                                  s_anchor[4][64];
   uint32_t b = blockIdx.x; // (workgroup-uniform branches)
   if (b < l.nb32) {
-    chain_sub_body<32>(a, l.list32, l.n32, b, s_wavebuf, s_cm, s_keep, s_anchor);
+    chain_sub_body<32, WIDE>(a, l.list32, l.n32, b, s_wavebuf, s_cm, s_keep, s_anchor);
   } else if ((b -= l.nb32) < l.nb16) {
-    chain_sub_body<16>(a, l.list16, l.n16, b, s_wavebuf, s_cm, s_keep, s_anchor);
+    chain_sub_body<16, WIDE>(a, l.list16, l.n16, b, s_wavebuf, s_cm, s_keep, s_anchor);
   } else {
-    chain_sub_body<8>(a, l.list8, l.n8, b - l.nb16, s_wavebuf, s_cm, s_keep, s_anchor);
+    chain_sub_body<8, WIDE>(a, l.list8, l.n8, b - l.nb16, s_wavebuf, s_cm, s_keep, s_anchor);
   }
 }
-template __global__ void k_chain_sub<8>(ChainArgs, const uint32_t *, uint32_t);
-template __global__ void k_chain_sub<16>(ChainArgs, const uint32_t *, uint32_t);
-template __global__ void k_chain_sub<32>(ChainArgs, const uint32_t *, uint32_t);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSGPU_SUB_WAVES, MSGPU_SUB_WAVES))) void k_chain_sub_all(ChainArgs a, ChainSubLists l) {
+  chain_sub_all_body<false>(a, l);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSGPU_SUB_WAVES, MSGPU_SUB_WAVES))) void k_chain_sub_all_wide(ChainArgs a, ChainSubLists l) {
+  chain_sub_all_body<true>(a, l);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // chain, big edges (> 64 EdgeMatches): same algorithm, one wavefront per edge, element state in global scratch.
@@ -2942,7 +3007,8 @@ __global__ __launch_bounds__(64) void k_chain_big(ChainArgs a, const uint32_t *b
 
   // elements + EdgeMatch table
   for (uint32_t i = lane; i < n; i += 64) {
-    const uint32_t j1 = a.cand_j[cp + i], q2 = a.cand_q[cp + i];
+    const uint32_t jq = a.cand_j[cp + i]; // (the form is a job's, not a kernel's, here: a few thousand wavefronts)
+    const uint32_t j1 = a.cand_wide ? jq : (jq & 0xffffu), q2 = a.cand_wide ? a.cand_q[cp + i] : (jq >> 16);
     const IRow     m1 = load_irow(&a.by_read[a.read_off[v1] + j1]);
     const IRow     m2 = load_irow(&a.by_read[a.read_off[v2] + q2]);
     const int      ov_lo = max(m1.i_lo, m2.i_lo), ov_hi = min(m1.i_hi, m2.i_hi);
@@ -3778,10 +3844,10 @@ void launch_sort_read(hipStream_t st, const uint32_t *read_off, const uint32_t *
 }
 void launch_index_finish(hipStream_t st, const uint32_t *read_first, uint32_t V, uint32_t *err, const uint32_t *flags,
                          const uint32_t *fast_off, const uint32_t *gen_off, uint32_t A, uint32_t *anchor_off, uint32_t *d_n_alive,
-                         uint32_t n_rows) {
+                         uint32_t n_rows, const uint32_t *read_cnt, uint32_t *max_cnt) {
   const uint64_t most = V > static_cast<uint64_t>(A) + 1 ? V : static_cast<uint64_t>(A) + 1;
   hipLaunchKernelGGL(k_index_finish, grid1(most, 256), dim3(256), 0, st, read_first, V, err, flags, fast_off, gen_off, A, anchor_off,
-                     d_n_alive, n_rows);
+                     d_n_alive, n_rows, read_cnt, max_cnt);
 }
 void launch_select_anchor_off(hipStream_t st, const uint32_t *flags, const uint32_t *fast_off, const uint32_t *gen_off,
                               uint32_t A, uint32_t *anchor_off, uint32_t *d_n_alive, uint32_t n_rows) {
@@ -3817,45 +3883,65 @@ void launch_classify_reads(hipStream_t st, const uint32_t *read_off, const uint3
     hipLaunchKernelGGL(k_classify_reads, grid1(V, 1024), dim3(1024), 0, st, read_off, read_cnt, bound, cand_off, V, shard,
                        nshards, lo, hi, l0, l1, l2, l3, n_lists, z, own_total);
 }
+template <bool WIDE> static void launch_candidates_form(hipStream_t st, const CandArgs &a, int cls, const CandDesc *list, uint32_t n_list) {
+  if (cls == 0)
+    hipLaunchKernelGGL((k_candidates<256, 512, 256, WIDE>), dim3(n_list), dim3(256), 0, st, a, list, n_list);
+  else if (cls == 1)
+    hipLaunchKernelGGL((k_candidates<256, 1024, 256, WIDE>), dim3(n_list), dim3(256), 0, st, a, list, n_list);
+  else
+    hipLaunchKernelGGL((k_candidates<1024, 4096, 256, WIDE>), dim3(n_list), dim3(256), 0, st, a, list, n_list);
+}
 void launch_candidates(hipStream_t st, const CandArgs &a, int cls, const CandDesc *list, uint32_t n_list) {
   if (!n_list) return;
-  if (cls == 0)
-    hipLaunchKernelGGL((k_candidates<256, 512, 256>), dim3(n_list), dim3(256), 0, st, a, list, n_list);
-  else if (cls == 1)
-    hipLaunchKernelGGL((k_candidates<256, 1024, 256>), dim3(n_list), dim3(256), 0, st, a, list, n_list);
-  else
-    hipLaunchKernelGGL((k_candidates<1024, 4096, 256>), dim3(n_list), dim3(256), 0, st, a, list, n_list);
+  if (a.cand_wide) launch_candidates_form<true>(st, a, cls, list, n_list);
+  else launch_candidates_form<false>(st, a, cls, list, n_list);
 }
 void launch_candidates_big(hipStream_t st, const CandArgs &a, const uint32_t *list, uint32_t n_list, uint64_t *big_key,
                            uint32_t *big_t, uint32_t *big_r2s, uint32_t *big_pfx) {
   if (!n_list) return;
-  hipLaunchKernelGGL(k_candidates_big, dim3(n_list), dim3(256), 0, st, a, list, n_list, big_key, big_t, big_r2s,
-                     big_pfx);
+  if (a.cand_wide)
+    hipLaunchKernelGGL(k_candidates_big<true>, dim3(n_list), dim3(256), 0, st, a, list, n_list, big_key, big_t, big_r2s, big_pfx);
+  else
+    hipLaunchKernelGGL(k_candidates_big<false>, dim3(n_list), dim3(256), 0, st, a, list, n_list, big_key, big_t, big_r2s, big_pfx);
 }
 void launch_fill_pair_tab(hipStream_t st, uint32_t *tab) {
   hipLaunchKernelGGL(k_fill_pair_tab, dim3((4 * PAIR_TAB_STRIDE + 255) / 256), dim3(256), 0, st, tab);
 }
-void launch_chain(hipStream_t st, const ChainArgs &a, const uint32_t *list, uint32_t n_list) {
-  const uint64_t n = list ? n_list : a.n_edges;
-  if (n) hipLaunchKernelGGL(k_chain, dim3(static_cast<uint32_t>(n)), dim3(64), CHAIN_LDS_BYTES, st, a, list, n_list); // a wavefront per workgroup
+void launch_chain(hipStream_t st, const ChainArgs &a, const ChainDesc *desc, uint32_t n_desc) {
+  // a wavefront per workgroup
+  const dim3 grid(desc ? n_desc : static_cast<uint32_t>(a.n_edges));
+  if (!grid.x) return;
+  if (desc) {
+    if (a.cand_wide) hipLaunchKernelGGL(k_chain_wide, grid, dim3(64), CHAIN_LDS_BYTES, st, a, desc, n_desc);
+    else hipLaunchKernelGGL(k_chain, grid, dim3(64), CHAIN_LDS_BYTES, st, a, desc, n_desc);
+  } else {
+    if (a.cand_wide) hipLaunchKernelGGL(k_chain_unlisted<true>, grid, dim3(64), CHAIN_LDS_BYTES, st, a);
+    else hipLaunchKernelGGL(k_chain_unlisted<false>, grid, dim3(64), CHAIN_LDS_BYTES, st, a);
+  }
 }
-void launch_chain_sub(hipStream_t st, const ChainArgs &a, int width, const uint32_t *list, uint32_t n_list) {
-  if (!n_list) return;
+template <bool WIDE> static void launch_chain_sub_form(hipStream_t st, const ChainArgs &a, int width, const ChainDesc *list, uint32_t n_list) {
   if (width == 8)
-    hipLaunchKernelGGL(k_chain_sub<8>, grid1(n_list, 32), dim3(256), 0, st, a, list, n_list);
+    hipLaunchKernelGGL((k_chain_sub<8, WIDE>), grid1(n_list, 32), dim3(256), 0, st, a, list, n_list);
   else if (width == 16)
-    hipLaunchKernelGGL(k_chain_sub<16>, grid1(n_list, 16), dim3(256), 0, st, a, list, n_list);
+    hipLaunchKernelGGL((k_chain_sub<16, WIDE>), grid1(n_list, 16), dim3(256), 0, st, a, list, n_list);
   else
-    hipLaunchKernelGGL(k_chain_sub<32>, grid1(n_list, 8), dim3(256), 0, st, a, list, n_list);
+    hipLaunchKernelGGL((k_chain_sub<32, WIDE>), grid1(n_list, 8), dim3(256), 0, st, a, list, n_list);
 }
-void launch_chain_sub_all(hipStream_t st, const ChainArgs &a, const uint32_t *l32, uint32_t n32, const uint32_t *l16, uint32_t n16,
-                          const uint32_t *l8, uint32_t n8) {
+void launch_chain_sub(hipStream_t st, const ChainArgs &a, int width, const ChainDesc *list, uint32_t n_list) {
+  if (!n_list) return;
+  if (a.cand_wide) launch_chain_sub_form<true>(st, a, width, list, n_list);
+  else launch_chain_sub_form<false>(st, a, width, list, n_list);
+}
+void launch_chain_sub_all(hipStream_t st, const ChainArgs &a, const ChainDesc *l32, uint32_t n32, const ChainDesc *l16, uint32_t n16,
+                          const ChainDesc *l8, uint32_t n8) {
   ChainSubLists l;
   l.list32 = l32, l.list16 = l16, l.list8 = l8;
   l.n32 = n32, l.n16 = n16, l.n8 = n8;
   l.nb32 = n32 ? grid1(n32, 8).x : 0u, l.nb16 = n16 ? grid1(n16, 16).x : 0u;
   const uint32_t nb8 = n8 ? grid1(n8, 32).x : 0u, nb = l.nb32 + l.nb16 + nb8;
-  if (nb) hipLaunchKernelGGL(k_chain_sub_all, dim3(nb), dim3(256), 0, st, a, l);
+  if (!nb) return;
+  if (a.cand_wide) hipLaunchKernelGGL(k_chain_sub_all_wide, dim3(nb), dim3(256), 0, st, a, l);
+  else hipLaunchKernelGGL(k_chain_sub_all, dim3(nb), dim3(256), 0, st, a, l);
 }
 size_t big_elem_bytes() { return sizeof(BigElem); }
 size_t big_path_bytes() { return sizeof(BigPath); }
