@@ -324,6 +324,13 @@ int msgpu_chain_band_width(void); /* B, a build-time constant (MSGPU_CHAIN_BAND)
  * read of more than 65,535 rows: 1 = the host keeps the ranks in two arrays for a job whose largest read has that many rows.
  * MSGPU_CAND_WIDE=1 forces that form. */
 int msgpu_cand_wide(uint32_t largest_read_cnt);
+/* The chain kernels leave an order as the four overhangs of its path (L1, L2 of the first anchor on v1 / v2, R1, R2 of the last,
+ * the v2 side chosen by direction), its score as a double and raw_flags = MSGPU_ORD_DIR | MSGPU_ORD_PRIMARY; the compaction
+ * kernel makes the msgpu_order of them.  This is that arithmetic on the host (the same function, compiled for both): fills
+ * flags, left_offset, right_offset, score, start, end and base of *out and leaves its other fields alone; returns 1 when
+ * getOverlap has a case for the four values (always, unless one is a NaN), else 0.  score must lie in [0, 2^64). */
+int msgpu_order_finish(uint32_t raw_flags, double score, double L1, double L2, double R1, double R2, uint32_t v1, uint32_t v2,
+                       msgpu_order *out);
 /* The stage boundaries (index / candidates / chain / compact) are marked with HIP events on the context's stream; every
  * marker costs a few microseconds of command-processor time.  on = 0 drops them: msgpu_get_timings then reports only
  * chain_kernel_ms (the two events around the chain kernels stay) and zeros for the stages.  Default: on. */

@@ -438,6 +438,8 @@ SYMBOLS = [
     ("msgpu_get_chain_band_counts", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("msgpu_chain_band_width", C.c_int, []),
     ("msgpu_cand_wide", C.c_int, [C.c_uint32]),
+    ("msgpu_order_finish", C.c_int, [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                     C.c_uint32, C.c_void_p]),
     ("msgpu_set_stage_events", C.c_int, [C.c_void_p, C.c_int]),
     ("msgpu_copy_tables", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("msgpu_copy_tables_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

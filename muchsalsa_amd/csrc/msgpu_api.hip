@@ -1431,6 +1431,20 @@ int msgpu_get_counts(msgpu_ctx *c, msgpu_counts *out) {
 
 int msgpu_chain_band_width(void) { return MSGPU_CHAIN_BAND; }
 int msgpu_cand_wide(uint32_t largest_read_cnt) { return cand_wide(largest_read_cnt) ? 1 : 0; }
+int msgpu_order_finish(uint32_t raw_flags, double score, double L1, double L2, double R1, double R2, uint32_t v1, uint32_t v2,
+                       msgpu_order *out) {
+  const OrderFinish o = order_finish(raw_flags, score, L1, L2, R1, R2, v1, v2);
+  if (out) {
+    out->flags        = o.flags;
+    out->left_offset  = o.lo;
+    out->right_offset = o.ro;
+    out->score        = o.score;
+    out->start        = o.start;
+    out->end          = o.end;
+    out->base         = o.base;
+  }
+  return o.have ? 1 : 0;
+}
 
 // The chain kernels leave the banded edges in bits 16..31 of every chunk sum and the fallbacks in the spare chunk behind the
 // last one (chunk_add, band_fallback_add); nothing on the hot path reads them, this call copies the words on demand.

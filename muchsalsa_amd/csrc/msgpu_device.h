@@ -93,6 +93,51 @@ __device__ __forceinline__ double rl_f64(double v, int lane) {
   return __longlong_as_double(static_cast<long long>(rl_u64(static_cast<uint64_t>(__double_as_longlong(v)), lane)));
 }
 
+// lane K of this lane's quad, to the whole quad (quad_perm:[K,K,K,K]: DPP control K * 0x55); the four lanes must be active
+template <int K> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+  static_assert(K >= 0 && K < 4, "quad lane");
+  return static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), K * 0x55, 0xf, 0xf, false));
+}
+
+// getOverlap (ol.cpp:53-101) on the four overhangs of a path -- L = the first anchor's on v1 / v2, R = the last anchor's, the
+// v2 side already chosen by direction (main.cpp:73-76) -- and the rest of an order that follows from them: start / end / base
+// from the edge's reads, the score truncated like path_t's std::size_t (a score in [0, 2^64): anything else is not a path
+// score).  ONE copy of the arithmetic: k_compact finishes the chain kernels' RAW records with it (ORD_RAW, msgpu_internal.h),
+// the host entry msgpu_order_finish lets a test without a GPU call it.  raw_flags: DIR and PRIMARY (the marker is dropped).
+//
+// The four cases are tried in the reference's order.  With s1 = sign(L1 ? L2), s2 = sign(R1 ? R2) and no NaN among the four:
+//   (<,<) (<,=) (=,<) (=,=) -> case 1      (=,>) (>,=) (>,>) -> case 2      (>,<) -> case 3      (<,>) -> case 4
+// so every ordered combination has a case, and `have` is false exactly when one of the four values is a NaN (every compare
+// with a NaN is false).  The chain kernels decide `have` by that test alone; a record they emit always has its case here.
+struct OrderFinish {
+  bool     have;
+  uint32_t flags; // MSGPU_ORD_*
+  double   lo, ro;
+  uint64_t score;
+  uint32_t start, end, base;
+};
+__host__ __device__ inline OrderFinish order_finish(uint32_t raw_flags, double score, double L1, double L2, double R1, double R2,
+                                                    uint32_t v1, uint32_t v2) {
+  // (selects, not branches: the four lanes of a slot and the slots of a wavefront take different cases in k_compact.  The
+  // offsets are the reference's own subtractions, L2 - L1 in the cases 1 and 4, R2 - R1 in the cases 1 and 3.)
+  const bool c1 = (L1 <= L2) & (R1 <= R2);
+  const bool c2 = !c1 & (L1 >= L2) & (R1 >= R2);
+  const bool c3 = !c1 & !c2 & (L1 > L2) & (R1 < R2);
+  const bool c4 = !c1 & !c2 & !c3 & (L1 < L2) & (R1 > R2);
+  OrderFinish    o;
+  o.have            = c1 | c2 | c3 | c4;
+  const uint32_t fl = c1 ? (MSGPU_ORD_START_V1 | MSGPU_ORD_CONTAINED) : c2 ? MSGPU_ORD_CONTAINED : c3 ? MSGPU_ORD_START_V1 : 0u;
+  const double   dl = L2 - L1, dl_ = L1 - L2, dr = R2 - R1, dr_ = R1 - R2;
+  o.lo    = (c1 | c4) ? dl : (c2 | c3) ? dl_ : 0.0;
+  o.ro    = (c1 | c3) ? dr : (c2 | c4) ? dr_ : 0.0;
+  o.flags = fl | (raw_flags & (MSGPU_ORD_DIR | MSGPU_ORD_PRIMARY));
+  o.score = static_cast<uint64_t>(score);
+  o.start = (fl & MSGPU_ORD_START_V1) ? v1 : v2;
+  o.end   = (fl & MSGPU_ORD_START_V1) ? v2 : v1;
+  o.base  = v1;
+  return o;
+}
+
 // The read-back of the scalar block without a copy or a stream synchronisation, called by one whole wavefront:
 // lane k holds the value of slot k.  The words go into the mapped host mirror, a system-scope fence makes them visible, then
 // lane 0 release-stores the sequence number the host polls for.  Fence and store are the wavefront's own, so nothing else needs

@@ -68,6 +68,16 @@ static_assert(sizeof(ChainDesc) == 32, "ChainDesc must be 32 bytes");
 constexpr uint32_t CAND_RANK_MAX = 65535, CAND_RANK_SURE = 256;
 inline bool cand_wide(uint32_t largest_read_cnt) { return largest_read_cnt > CAND_RANK_MAX; }
 
+// An order slot of the chain scratch (order_scr) as the chain kernels of edges of <= 64 EdgeMatches leave it: the RAW record,
+// one writer per 16-byte quarter, finished into the msgpu_order by k_compact (order_finish, msgpu_device.h):
+//   q0 {edge, ORD_RAW | DIR | PRIMARY, the path's score as its fp64 bits}   lane 0 of the edge (or group)
+//   q1 {L1, L2}                                                             the lane of the path's FIRST anchor
+//   q2 {ids_off (edge-relative), v1, ids_cnt, v2}                           lane 0
+//   q3 {R1, R2}                                                             the lane of the path's LAST anchor
+// A slot without the marker is a finished msgpu_order (k_chain_big) and passes through k_compact as it is.
+constexpr uint32_t ORD_RAW = 1u << 31; // (no MSGPU_ORD_* bit)
+static_assert((ORD_RAW & (MSGPU_ORD_START_V1 | MSGPU_ORD_CONTAINED | MSGPU_ORD_DIR | MSGPU_ORD_PRIMARY)) == 0, "the marker is no flag");
+
 struct CandArgs {
   const uint32_t *read_off, *read_cnt, *anchor_off;
   const IRow     *by_read;

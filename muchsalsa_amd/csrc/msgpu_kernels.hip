@@ -1559,7 +1559,7 @@ __device__ __forceinline__ void band_fallback_add(unsigned long long *chunk_sums
 
 struct PathRec {
   uint64_t mask;    // lanes (= EdgeMatches of the edge, vStart order) on the path
-  uint64_t score;   // truncated like path_t's std::size_t
+  uint64_t score;   // the fp64 bits of the score (k_compact truncates it like path_t's std::size_t: order_finish)
   uint32_t primary;
   uint32_t pad;
 };
@@ -1674,7 +1674,7 @@ __device__ __forceinline__ int paths_of_direction(unsigned long long act, bool d
   hp |= __popcll(m) > 2;                                       // :220
   if (lane == 0) {
     paths[0].mask    = m;
-    paths[0].score   = static_cast<uint64_t>(maxv);
+    paths[0].score   = __builtin_bit_cast(uint64_t, maxv);
     paths[0].primary = hp;
   }
   np = 1;
@@ -1690,7 +1690,7 @@ __device__ __forceinline__ int paths_of_direction(unsigned long long act, bool d
     const double   sp = rl_f64(pop, p);
     if (lane == 0) {
       paths[np].mask    = mp;
-      paths[np].score   = static_cast<uint64_t>(sp);
+      paths[np].score   = __builtin_bit_cast(uint64_t, sp);
       paths[np].primary = (mp & prim_lanes) != 0;
     }
     ++np;
@@ -2192,6 +2192,10 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, const ChainDesc *
   }
 
   // getOverlap (ol.cpp:53-101) per kept path, minus first; orders into this edge's slots, ids into its id slots
+  // The order leaves as a RAW record (ORD_RAW, msgpu_internal.h): the lane of the path's first anchor stores its own L1 / L2, the
+  // lane of its last anchor its own R1 / R2, and k_compact runs getOverlap's cases on them (order_finish) -- here they were the
+  // work of one lane at the price of 64, behind twelve to sixteen v_readlane.  What decides COUNTS stays: an order exists unless
+  // one of the four values is a NaN (order_finish: every ordered combination has a case), one unordered compare per side.
   uint32_t n_orders = 0, n_ids = 0;
   for (int pass = 0; pass < 2; ++pass) {
     unsigned long long keep = pass == 0 ? keep_m : keep_p;
@@ -2202,59 +2206,24 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, const ChainDesc *
       keep &= keep - 1;
       const uint64_t mask = pv[pi].mask;
       const int      f = __builtin_ctzll(mask), l = 63 - __builtin_clzll(mask);
-      const double   L1 = rl_f64(clo1, f), R1 = rl_f64(ovr1, l);
-      double         L2 = rl_f64(clo2, f), R2 = rl_f64(ovr2, l);
-      if (!dir) { // :73-76
-        L2 = rl_f64(ovr2, f);
-        R2 = rl_f64(clo2, l);
-      }
-      bool     have = false;
-      uint32_t fl   = 0;
-      double   lo = 0, ro = 0;
-      if (L1 <= L2 && R1 <= R2) {
-        have = true;
-        fl   = MSGPU_ORD_START_V1 | MSGPU_ORD_CONTAINED;
-        lo   = L2 - L1;
-        ro   = R2 - R1;
-      } else if (L1 >= L2 && R1 >= R2) {
-        have = true;
-        fl   = MSGPU_ORD_CONTAINED;
-        lo   = L1 - L2;
-        ro   = R1 - R2;
-      } else if (L1 > L2 && R1 < R2) {
-        have = true;
-        fl   = MSGPU_ORD_START_V1;
-        lo   = L1 - L2;
-        ro   = R2 - R1;
-      } else if (L1 < L2 && R1 > R2) {
-        have = true;
-        fl   = 0;
-        lo   = L2 - L1;
-        ro   = R1 - R2;
-      }
-      if (!have) continue;
+      // (the v2 side by direction, :73-76; dir is wave-uniform)
+      const double   myL2 = dir ? clo2 : ovr2, myR2 = dir ? ovr2 : clo2;
+      if (__ballot((lane == f && __builtin_isunordered(clo1, myL2)) || (lane == l && __builtin_isunordered(ovr1, myR2))) != 0) continue;
       const uint32_t cnt = static_cast<uint32_t>(__popcll(mask));
       // ids in path order = ascending lane
       if ((mask >> lane) & 1ull) {
         const uint32_t pos = static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1)));
         a.ids_scr[ed.em_off + n_ids + pos] = anchor;
       }
+      uint4 *slot4 = reinterpret_cast<uint4 *>(&a.order_scr[ed.em_off + n_orders]);
       if (lane == 0) {
-        msgpu_order o;
-        o.edge_idx     = static_cast<uint32_t>(e);
-        o.flags        = fl | (dir ? MSGPU_ORD_DIR : 0u) | (pv[pi].primary ? MSGPU_ORD_PRIMARY : 0u);
-        o.left_offset  = lo;
-        o.right_offset = ro;
-        o.score        = pv[pi].score;
-        o.ids_off      = n_ids; // relative to the edge's id slots; made absolute by k_compact
-        o.ids_cnt      = cnt;
-        o.start        = (fl & MSGPU_ORD_START_V1) ? v1 : v2;
-        o.end          = (fl & MSGPU_ORD_START_V1) ? v2 : v1;
-        o.base         = v1;
-        o.pad[0]       = 0;
-        o.pad[1]       = 0;
-        a.order_scr[ed.em_off + n_orders] = o;
+        const uint64_t sc = pv[pi].score;
+        slot4[0] = make_uint4(static_cast<uint32_t>(e), ORD_RAW | (dir ? MSGPU_ORD_DIR : 0u) | (pv[pi].primary ? MSGPU_ORD_PRIMARY : 0u),
+                              static_cast<uint32_t>(sc), static_cast<uint32_t>(sc >> 32));
+        slot4[2] = make_uint4(n_ids, v1, cnt, v2); // n_ids: relative to the edge's id slots; made absolute by k_compact
       }
+      if (lane == f) reinterpret_cast<double2 *>(slot4)[1] = make_double2(clo1, myL2);
+      if (lane == l) reinterpret_cast<double2 *>(slot4)[3] = make_double2(ovr1, myR2);
       ++n_orders;
       n_ids += cnt;
     }
@@ -2290,7 +2259,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
 struct __attribute__((aligned(16))) SubPath { // a path of one direction; mask bit i = the group's i-th EdgeMatch
   uint32_t mask, primary;
-  uint64_t score;
+  uint64_t score; // the fp64 bits, as in PathRec
 };
 
 __device__ __forceinline__ double shfl_f64(double v, int src) {
@@ -2373,7 +2342,7 @@ __device__ __forceinline__ uint32_t paths_of_direction_sub(uint32_t act, bool di
   const uint32_t prim_lanes = group_bits<W>(__ballot(mine && em_prim), gbase);
   const uint32_t m          = __shfl(pm, gbase + maxi);
   const bool     hp         = ((m & prim_lanes) != 0) | (__popc(m) > 2); // :217-220
-  if (live && sl == 0) paths[0] = SubPath{m, hp ? 1u : 0u, static_cast<uint64_t>(maxv)};
+  if (live && sl == 0) paths[0] = SubPath{m, hp ? 1u : 0u, __builtin_bit_cast(uint64_t, maxv)};
   uint32_t np = live ? 1u : 0u;
   // alternatives, :223-249
   const double thr  = maxv * alt_frac;
@@ -2386,7 +2355,7 @@ __device__ __forceinline__ uint32_t paths_of_direction_sub(uint32_t act, bool di
     const int      p   = has ? __builtin_ctz(cand) : 0;
     const uint32_t mp  = __shfl(pm, gbase + p);
     const double   sp  = shfl_f64(pop, gbase + p);
-    if (has && sl == 0) paths[np] = SubPath{mp, (mp & prim_lanes) != 0 ? 1u : 0u, static_cast<uint64_t>(sp)};
+    if (has && sl == 0) paths[np] = SubPath{mp, (mp & prim_lanes) != 0 ? 1u : 0u, __builtin_bit_cast(uint64_t, sp)};
     if (has) {
       ++np;
       used |= mp;
@@ -2782,6 +2751,7 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const ChainDe
   // number of kept paths, not to the largest minus count plus the largest plus count)
   {
     uint32_t km = keep_m, kp = keep_p;
+    const double *own = s_keep[wave][lane]; // clo1, clo2, ovr1, ovr2 of this lane's EdgeMatch (parked above)
     while (__ballot((km | kp) != 0)) {
       const bool     dir  = km == 0;
       const uint32_t keep = dir ? kp : km;
@@ -2792,53 +2762,22 @@ __device__ __forceinline__ void chain_sub_body(const ChainArgs &a, const ChainDe
       const SubPath  rec  = (dir ? ppl : pmn)[pi];
       const uint32_t mask = (has && rec.mask) ? rec.mask : 1u;
       const int      f = __builtin_ctz(mask), l = 31 - __builtin_clz(mask);
-      const double  *kf = s_keep[wave][gbase + f], *kl = s_keep[wave][gbase + l];
-      const double   L1 = kf[0], R1 = kl[2];
-      const double   L2 = dir ? kf[1] : kf[3], R2 = dir ? kl[3] : kl[1]; // :73-76
-      bool     have = false;
-      uint32_t fl   = 0;
-      double   lo = 0, ro = 0;
-      if (L1 <= L2 && R1 <= R2) {
-        have = true;
-        fl   = MSGPU_ORD_START_V1 | MSGPU_ORD_CONTAINED;
-        lo   = L2 - L1;
-        ro   = R2 - R1;
-      } else if (L1 >= L2 && R1 >= R2) {
-        have = true;
-        fl   = MSGPU_ORD_CONTAINED;
-        lo   = L1 - L2;
-        ro   = R1 - R2;
-      } else if (L1 > L2 && R1 < R2) {
-        have = true;
-        fl   = MSGPU_ORD_START_V1;
-        lo   = L1 - L2;
-        ro   = R2 - R1;
-      } else if (L1 < L2 && R1 > R2) {
-        have = true;
-        fl   = 0;
-        lo   = L2 - L1;
-        ro   = R1 - R2;
-      }
-      const bool emit = has && have;
+      // the RAW record, as in k_chain: every lane looks at its OWN four numbers, the lanes f and l store theirs, and the order
+      // exists unless one of the four is a NaN (order_finish)
+      const double   myL2 = dir ? own[1] : own[3], myR2 = dir ? own[3] : own[1]; // :73-76
+      const bool     nan_ = (sl == f && __builtin_isunordered(own[0], myL2)) || (sl == l && __builtin_isunordered(own[2], myR2));
+      const bool     emit = has && group_bits<W>(__ballot(nan_), gbase) == 0;
       if (emit) {
         const uint32_t cnt = static_cast<uint32_t>(__popc(mask));
         if ((mask >> sl) & 1u) a.ids_scr[ed.em_off + n_ids + static_cast<uint32_t>(__popc(mask & ((1u << sl) - 1u)))] = s_anchor[wave][lane];
+        uint4 *slot4 = reinterpret_cast<uint4 *>(&a.order_scr[ed.em_off + n_orders]);
         if (sl == 0) {
-          msgpu_order o;
-          o.edge_idx     = e;
-          o.flags        = fl | (dir ? MSGPU_ORD_DIR : 0u) | (rec.primary ? MSGPU_ORD_PRIMARY : 0u);
-          o.left_offset  = lo;
-          o.right_offset = ro;
-          o.score        = rec.score;
-          o.ids_off      = n_ids;
-          o.ids_cnt      = cnt;
-          o.start        = (fl & MSGPU_ORD_START_V1) ? v1 : v2;
-          o.end          = (fl & MSGPU_ORD_START_V1) ? v2 : v1;
-          o.base         = v1;
-          o.pad[0]       = 0;
-          o.pad[1]       = 0;
-          a.order_scr[ed.em_off + n_orders] = o;
+          slot4[0] = make_uint4(e, ORD_RAW | (dir ? MSGPU_ORD_DIR : 0u) | (rec.primary ? MSGPU_ORD_PRIMARY : 0u),
+                                static_cast<uint32_t>(rec.score), static_cast<uint32_t>(rec.score >> 32));
+          slot4[2] = make_uint4(n_ids, v1, cnt, v2);
         }
+        if (sl == f) reinterpret_cast<double2 *>(slot4)[1] = make_double2(own[0], myL2);
+        if (sl == l) reinterpret_cast<double2 *>(slot4)[3] = make_double2(own[2], myR2);
         ++n_orders;
         n_ids += cnt;
       }
@@ -3544,7 +3483,37 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
       }
 #pragma unroll
       for (uint32_t k = 0; k < ORD_U; ++k) {
+        // (a round past the last slot holds clamped copies only: the whole workgroup steps over it)
+        if (k * (COMPACT_CHUNK / 4) >= rem) break;
         const uint32_t off = k * (COMPACT_CHUNK / 4) + sl;
+        // A RAW record (ORD_RAW, msgpu_internal.h) is finished here: the four lanes of the slot hand each other the flags and
+        // the score (quarter 0), L1 / L2 (quarter 1), the edge's reads (quarter 2) and R1 / R2 (quarter 3) with quad permutes --
+        // all four lanes of a quad hold the same slot, a clamped one included --, run order_finish, and every lane keeps the
+        // quarter of the msgpu_order that is its own.  No branch: the slots of a wavefront differ, and the four rounds'
+        // arithmetic can overlap.  A finished record (k_chain_big) keeps its quarters.  The ids_off of quarter 2 stays
+        // edge-relative until below.
+        {
+          const uint32_t rf = quad_bcast<0>(w[k].y);
+          const uint32_t s_lo = quad_bcast<0>(w[k].z), s_hi = quad_bcast<0>(w[k].w);
+          const uint32_t a0 = quad_bcast<1>(w[k].x), a1 = quad_bcast<1>(w[k].y), a2 = quad_bcast<1>(w[k].z), a3 = quad_bcast<1>(w[k].w);
+          const uint32_t r1 = quad_bcast<2>(w[k].y), r2 = quad_bcast<2>(w[k].w);
+          const uint32_t b0 = quad_bcast<3>(w[k].x), b1 = quad_bcast<3>(w[k].y), b2 = quad_bcast<3>(w[k].z), b3 = quad_bcast<3>(w[k].w);
+          // (On a finished record the same dwords are other fields: what stands where a RAW record has its score is half of
+          // left_offset, any bits at all, and converting a NaN or a negative number to uint64_t is undefined.  Such a slot is
+          // finished with a score of 0 and the result dropped by the select on `raw` below.)
+          const bool        raw = (rf & ORD_RAW) != 0;
+          const OrderFinish o = order_finish(rf, raw ? __hiloint2double(static_cast<int>(s_hi), static_cast<int>(s_lo)) : 0.0,
+                                             __hiloint2double(static_cast<int>(a1), static_cast<int>(a0)),
+                                             __hiloint2double(static_cast<int>(a3), static_cast<int>(a2)),
+                                             __hiloint2double(static_cast<int>(b1), static_cast<int>(b0)),
+                                             __hiloint2double(static_cast<int>(b3), static_cast<int>(b2)), r1, r2);
+          const unsigned long long lo = __builtin_bit_cast(unsigned long long, o.lo), ro = __builtin_bit_cast(unsigned long long, o.ro);
+          const uint4 fin = sub == 0   ? make_uint4(w[k].x, o.flags, static_cast<uint32_t>(lo), static_cast<uint32_t>(lo >> 32))
+                            : sub == 1 ? make_uint4(static_cast<uint32_t>(ro), static_cast<uint32_t>(ro >> 32), static_cast<uint32_t>(o.score), static_cast<uint32_t>(o.score >> 32))
+                            : sub == 2 ? make_uint4(w[k].x, 0u, w[k].z, o.start)
+                                       : make_uint4(o.end, o.base, 0u, 0u);
+          w[k] = make_uint4(raw ? fin.x : w[k].x, raw ? fin.y : w[k].y, raw ? fin.z : w[k].z, raw ? fin.w : w[k].w);
+        }
         // msgpu_order as 16 dwords: [0] = edge_idx, [8,9] = ids_off (edge-relative in the scratch) -- the third quarter's own
         if (sub == 0) w[k].x += a.out_edge_base;
         if (sub == 2) {
