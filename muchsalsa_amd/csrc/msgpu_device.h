@@ -93,6 +93,22 @@ __device__ __forceinline__ double rl_f64(double v, int lane) {
   return __longlong_as_double(static_cast<long long>(rl_u64(static_cast<uint64_t>(__double_as_longlong(v)), lane)));
 }
 
+// v of lane (addr + OFF) / 4 (mod 64) through the LDS crossbar: two ds_bpermute_b32 with the instruction's immediate offset,
+// which the builtin does not fold an addition into.  No vector-ALU instruction and no LDS memory; every lane must be active
+// (an inactive source lane yields 0).  The compiler does not count an LDS instruction inside an asm statement, so the wait
+// stands in the same statement and the outputs are early-clobber; nothing but the two results is written (no SCC, no EXEC,
+// no memory).
+template <int OFF> __device__ __forceinline__ double bpermute_f64(uint32_t addr, double v) {
+  static_assert(OFF >= 0 && OFF < 65536, "16-bit unsigned offset");
+  int lo, hi;
+  asm volatile("ds_bpermute_b32 %0, %2, %3 offset:%5\n\t"
+               "ds_bpermute_b32 %1, %2, %4 offset:%5\n\t"
+               "s_waitcnt lgkmcnt(0)"
+               : "=&v"(lo), "=&v"(hi)
+               : "v"(addr), "v"(__double2loint(v)), "v"(__double2hiint(v)), "i"(OFF));
+  return __hiloint2double(hi, lo);
+}
+
 // lane K of this lane's quad, to the whole quad (quad_perm:[K,K,K,K]: DPP control K * 0x55); the four lanes must be active
 template <int K> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
   static_assert(K >= 0 && K < 4, "quad lane");

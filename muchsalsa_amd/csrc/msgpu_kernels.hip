@@ -1603,7 +1603,16 @@ __device__ __forceinline__ NanoMasks nano_check(double k_clo, double k_chi, doub
   // selects the right difference in every case that has an order.
   const double x = k_chi - l_clo;
   const double y = l_chi - k_clo;
-  double       t = lt_lo_b ? x : y;
+  // WF: the select is min(x, y), ONE v_min_f64 where it was two v_cndmask_b32.  t, ovl and d of a vertex are read only under
+  // `cl` (sweep_step: codir, mixed under cl, need_div under cl), and cl needs pos or neg on this vertex.  Under pos (k_clo <
+  // l_clo and k_chi < l_chi) the real y - x = (l_chi - k_chi) + (l_clo - k_clo) > 0, and rounding is monotone, so fl(x) <=
+  // fl(y): the minimum is x, bit for bit what lt_lo selects (equal roundings are the same number: a difference of two doubles
+  // is +-0 only when it is exactly 0, so +0 against -0 would need y - x = 0).  Under neg, symmetrically, the minimum is y = the
+  // select with lt_lo false.  Infinite ends: under pos k_chi < l_chi and k_clo < l_clo with lo <= hi leave neither difference an
+  // inf - inf, and the order holds in the extended reals; a NaN or a pair of zeros of different sign can only arise in a lane
+  // where neither pos nor neg holds, and pos and neg come from the ranges, not from t.  (x and y are subtraction results, so no
+  // canonicalising v_max_f64 stands in front of the minimum.)
+  double       t = WF ? __builtin_fmin(x, y) : (lt_lo_b ? x : y);
   if (WF) {
     f.ovl = __ballot(t >= 0.0);
     d     = fabs(t) + 1;
@@ -1750,6 +1759,10 @@ __device__ __forceinline__ ChainElem lds_elem(uint32_t addr) {
   e.rlo2 = static_cast<int>(c.z);
   e.rhi2 = static_cast<int>(c.w);
   return e;
+}
+// f(integral_constant<int, K>) for K = 0, 1, ... while it returns true (an unrolled loop whose step number is a constant)
+template <typename F, int... K> __device__ __forceinline__ void unroll_while(F &&f, std::integer_sequence<int, K...>) {
+  (void)(f(std::integral_constant<int, K>{}) && ...);
 }
 constexpr uint32_t CHAIN_LDS_EL = 0, CHAIN_LDS_CM = sizeof(ChainElem) * 64, CHAIN_LDS_BYTES = CHAIN_LDS_CM + 34 * 8;
 // LISTED: workgroup i takes descriptor i of `desc` (the 33..64 class of the size-sorted list); else edge i of the table, its
@@ -2099,12 +2112,22 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, const ChainDesc *
     uint32_t pred = static_cast<uint32_t>(ln);
     // bit k of mycm -> the sign bit after k shifts, in two 32-bit halves (k < 32, k >= 32): 32-bit compare and shift
     uint32_t rev = __builtin_bitreverse32(static_cast<uint32_t>(mycm));
-    const int n1 = static_cast<int>(n) - 1, nlo = n1 < 32 ? n1 : 32;
-    // Seven vector instructions per step (was ten): the compatibility bit and the shift are ONE add with carry-out (rev + rev:
-    // the carry is the old sign bit, as a wavefront mask), and the three conditional moves (score: two, predecessor: one, the
-    // step number copied into a vector register for it: one) are two plain moves under the condition as EXEC mask.
-    auto dp_step = [&](int k) __attribute__((always_inline)) {
-      const double       k_pop = rl_f64(pop, k);
+    const int n1 = static_cast<int>(n) - 1;
+    // Five vector instructions per step (was seven, before that ten): the compatibility bit and the shift are ONE add with
+    // carry-out (rev + rev: the carry is the old sign bit, as a wavefront mask), and the three conditional moves (score: two,
+    // predecessor: one, the step number copied into a vector register for it: one) are two plain moves under the condition as
+    // EXEC mask.
+    // THE DP'S BROADCAST.  population[k] reaches the wavefront through the LDS crossbar: two ds_bpermute_b32 (the halves of pop
+    // from lane k) where two v_readlane_b32 were -- LDS instructions, which the vector-issue limit this kernel sits at does not
+    // count.  Source lane = (address + immediate offset) / 4: the address register holds 4 * k0 for eight steps at a time and the
+    // step inside the eight is the immediate, so the address costs one vector add per EIGHT steps (bpermute_f64, msgpu_device.h:
+    // the builtin folds no addition into the offset, so the pair and its wait are one asm statement).  No LDS memory is touched,
+    // so there is nothing to order and nothing to initialise again on a band fallback.  All 64 lanes are active here (the lanes
+    // past the edge carry em_score = 0 and no compatibility bit), so every source lane is a live one.  The price is an LDS round
+    // trip on the serial chain of every step, which the other seven wavefronts of the SIMD are there to fill.
+    uint32_t bsrc = 0;
+    asm volatile("" : "+v"(bsrc));
+    auto dp_step = [&](double k_pop, int k) __attribute__((always_inline)) {
       const double       cand  = k_pop + em_score; // :189
       unsigned long long comp, saved;
       asm volatile("v_add_co_u32 %0, %1, %0, %0" : "+v"(rev), "=s"(comp));
@@ -2118,9 +2141,18 @@ __device__ __forceinline__ void chain_body(const ChainArgs &a, const ChainDesc *
                    : "scc"); // (s_and_saveexec writes SCC: without the clobber the loop's compare may sit in front of this block
                              // and its branch behind it -- an endless loop, gpurun call 535)
     };
-    for (int k = 0; k < nlo; ++k) dp_step(k);
-    rev = __builtin_bitreverse32(static_cast<uint32_t>(mycm >> 32));
-    for (int k = 32; k < n1; ++k) dp_step(k);
+    for (int k0 = 0; k0 < n1; k0 += 8) {
+      if (k0 == 32) rev = __builtin_bitreverse32(static_cast<uint32_t>(mycm >> 32));
+      unroll_while(
+          [&](auto jt) __attribute__((always_inline)) {
+            constexpr int J = decltype(jt)::value;
+            if (k0 + J >= n1) return false;
+            dp_step(bpermute_f64<4 * J>(bsrc, pop), k0 + J);
+            return true;
+          },
+          std::make_integer_sequence<int, 8>{});
+      bsrc += 32u;
+    }
     // population[l].path = population[pred].path + {l} with pred's path already final when l took it (pred < l): the
     // path masks are the closure of the predecessor pointers, built by pointer doubling in ceil(log2 n) rounds.
     uint32_t ptr = pred;
@@ -2316,11 +2348,6 @@ template <int W, int K> __device__ __forceinline__ double group_bcast_f64(double
   const uint32_t           lo = group_bcast<W, K>(static_cast<uint32_t>(b));
   const uint32_t           hi = group_bcast<W, K>(static_cast<uint32_t>(b >> 32));
   return __builtin_bit_cast(double, (static_cast<unsigned long long>(hi) << 32) | lo);
-}
-
-// f(integral_constant<int, K>) for K = 0, 1, ... while it returns true (an unrolled loop whose step number is a constant)
-template <typename F, int... K> __device__ __forceinline__ void unroll_while(F &&f, std::integer_sequence<int, K...>) {
-  (void)(f(std::integral_constant<int, K>{}) && ...);
 }
 
 // paths_of_direction for a group of W lanes; returns the group's path count (group-uniform, 0 for an empty direction)
